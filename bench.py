@@ -68,7 +68,12 @@ def parse():
     ap.add_argument("--dist-backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for rehearsals "
                     "where several ranks share one GPU)")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="wall budget of the all-core cpu_baseline leg (the one-thread leg adds one short utterance)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64, at most 64 MB in all; "
+                         "with several ranks each writes rank<r>_<name>.npy)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config == "cfg4":
         args.total_utts = 10000
     if args.sum_mode and args.kernel == "prefilter":
@@ -164,10 +169,12 @@ def main():
         bg = model.bigram(word_off, automaton, lex.silence_idx, lm, bg_tdp)
 
     def step():
+        """One step; returns every array the caller of the timed path receives, by name."""
         if bg is not None:
-            w, _, _, off = corpus.recognize_bigram(bg, args.beam, capi.FLT_MAX, kernel)
-            return w, off
-        return corpus.recognize(lexh, args.beam, wp, kernel)
+            w, sc, tm, off = corpus.recognize_bigram(bg, args.beam, capi.FLT_MAX, kernel)
+            return {"words": w, "word_scores": sc, "word_times": tm, "word_off": off}
+        w, off = corpus.recognize(lexh, args.beam, wp, kernel)
+        return {"words": w, "word_off": off}
 
     def fence():
         if distributed:
@@ -175,16 +182,19 @@ def main():
         torch.cuda.synchronize()
 
     for _ in range(args.warmup):
-        words, woff = step()
+        step()
     model.profile(True)
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        words, woff = step()
+        last = step()
     fence()
     elapsed = time.perf_counter() - t0
     prof = model.profile_read()
     model.profile(False)
+    words, woff = last["words"], last["word_off"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, prefix=f"rank{rank}_" if world > 1 else "", limit=DUMP_LIMIT_BYTES // world)
     # north_star's "MFMA utilisation on the GMM step": the headline path no longer executes the dense FP64 contraction, so the
     # dense FP64-MFMA kernel (same scores to 1e-9) is timed once beside it, outside the timed region, for that figure
     dense_mfma = None
@@ -291,6 +301,26 @@ def main():
     if distributed:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, prefix="", limit=DUMP_LIMIT_BYTES):
+    """Writes each array as <dirname>/<prefix><name>.npy in float64 (word ids, offsets and times are integers below 2**53, scores
+    float32: all exact).  Files stay under `limit` bytes in all: if the arrays would not fit, each keeps the same share of its
+    entries, at sorted positions drawn from a fixed seed."""
+    os.makedirs(dirname, exist_ok=True)
+    header = 4096  # upper bound of one .npy header
+    budget = (limit - header * len(arrays)) // 8
+    total = sum(int(np.asarray(a).size) for a in arrays.values())
+    rng = np.random.default_rng(12345)
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if total > budget:
+            keep = a.size * budget // total
+            a = a[np.sort(rng.choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(dirname, prefix + name + ".npy"), a.astype(np.float64))
 
 
 FP64_VALU_UNFUSED_PEAK = 39.3  # Tflop/s: one v_add_f64 / v_mul_f64 per lane and cycle (profiles/r1_fp64_rate_microbench.txt: 36.8)

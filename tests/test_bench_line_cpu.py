@@ -83,3 +83,25 @@ def test_roofline_fractions_do_not_depend_on_the_number_of_score_chunks():
     a = types.SimpleNamespace(kernel="mfma", words=1333, mix=32, steps=3)
     one, two = bench.gmm_roofline(a, prof(1, 3), frames, D, S), bench.gmm_roofline(a, prof(2, 3), frames, D, S)
     assert one["frac"] == two["frac"] and two["chunks_per_step"] == 2
+
+
+def test_dump_outputs_exact_and_bounded(tmp_path):
+    import numpy as np
+
+    words = np.array([3, 1, 4, 1, 5], np.uint32)
+    off = np.array([0, 2, 5], np.uint64)
+    scores = np.array([0.1, -2.5, 1e30], np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), {"words": words, "word_off": off, "word_scores": scores})
+    for name, want in (("words", words), ("word_off", off), ("word_scores", scores)):
+        got = np.load(tmp_path / "a" / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, want.astype(np.float64))
+    # over the limit: a seeded sample of every array, the same from run to run, and the files stay under the limit
+    big = {"words": np.arange(300000, dtype=np.uint32), "word_off": np.arange(100001, dtype=np.uint64)}
+    limit = 1 << 20
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, prefix="rank1_", limit=limit)
+    assert sum(p.stat().st_size for p in (tmp_path / "b").iterdir()) <= limit
+    for name, a in big.items():
+        b, c = np.load(tmp_path / "b" / f"rank1_{name}.npy"), np.load(tmp_path / "c" / f"rank1_{name}.npy")
+        assert np.array_equal(b, c) and 0 < len(b) < len(a)
+        assert np.all(np.diff(b) > 0) and np.isin(b, a.astype(np.float64)).all()

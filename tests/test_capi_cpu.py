@@ -94,13 +94,18 @@ def test_absurd_counts_in_a_model_file_are_errors_not_aborts(built_lib, tmp_path
 def test_exception_barrier_turns_bad_alloc_into_a_status(built_lib):
     """Forces a host allocation that cannot succeed through an entry point that needs no GPU (sr_mixset_write): statistics with
     2^32-1 accumulator rows x 63 dimensions (2 TB of doubles).  The call must come back with SR_ENOMEM / SR_ELIMIT and a
-    message -- in a child process, so that a regression (SIGABRT) fails this test instead of killing pytest."""
+    message -- in a child process, so that a regression (SIGABRT) fails this test instead of killing pytest.  The child's address
+    space is capped first: on a host that overcommits memory the 2 TB allocation could succeed, and the copy would then read far
+    past the 64-double arrays handed in here."""
     import sys
     code = r"""
-import ctypes as C, numpy as np, sys
+import ctypes as C, numpy as np, resource, sys
 sys.path.insert(0, %r)
 from speechrecognition_amd import capi
 L = capi.lib()
+vm = int([l.split()[1] for l in open("/proc/self/status") if l.startswith("VmSize:")][0]) * 1024
+hard = resource.getrlimit(resource.RLIMIT_AS)[1]
+resource.setrlimit(resource.RLIMIT_AS, (vm + (8 << 30) if hard == resource.RLIM_INFINITY else min(hard, vm + (8 << 30)), hard))
 off = np.zeros(2, np.uint32); one = np.zeros(1, np.uint32); d = np.zeros(64, np.float64)
 out = C.c_void_p()
 rc = L.sr_mixset_write(b"/tmp/never_written.mix", 63, 1, off.ctypes.data, 0xFFFFFFFF, 1, one.ctypes.data, one.ctypes.data,

@@ -68,7 +68,15 @@ def env(lib):
     return e
 
 
+def gpu_present():
+    """/dev/kfd is the ROCm kernel driver's node: where it exists, a HIP call in the sanitized process would bring up a GPU under ASan."""
+    return os.path.exists("/dev/kfd")
+
+
 def main(argv):
+    if gpu_present():
+        print("sanitize_host.py: refusing to run on a host with a GPU (ASan runs on the CPU build only)", file=sys.stderr)
+        return 2
     lib, drv = build()
     e = env(lib)
     e["SR_ASAN_DRIVER"] = drv
