@@ -46,7 +46,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <vector>
 
 #include "kernels.h"
@@ -1138,13 +1137,14 @@ static uint32_t defer_cap_for(const GmmRefineArgs& a, int spw) {
   const uint64_t per_wave = ((fps + kRThreads - 1) / kRThreads) * 64;  // frames one wave sees
   return (uint32_t)std::min<uint64_t>(((per_wave / 4 + 63) & ~(uint64_t)63) + 64, 1u << 30);
 }
-void gmm_refine_defer_layout(const GmmRefineArgs& a, size_t budget_bytes, uint32_t* cap, size_t* n_entries, size_t* n_counts) {
+void gmm_refine_defer_layout(const GmmRefineArgs& a, size_t budget_bytes, uint32_t cap_limit, uint32_t* cap, size_t* n_entries,
+                             size_t* n_counts) {
   *cap = 0; *n_entries = 0; *n_counts = 0;
   if (a.chunks < 2 || a.dim > 39 || a.n_slots != 32 || a.n_frames == 0) return;  // (instantiated for the 768-thread, 8-panel geometry)
   uint32_t g; uint64_t sp, fps;
   refine_grid(a, 8, &g, &sp, &fps);
   uint32_t c = defer_cap_for(a, 8);
-  if (const char* e = getenv("SRGPU_DEFER_CAP")) c = std::max(1u, std::min(c, (uint32_t)strtoul(e, nullptr, 10)));  // (tests: full segments)
+  if (cap_limit) c = std::min(c, cap_limit);
   const size_t segs = (size_t)g * sp * kRWaves * 8;
   if (segs * c * 16 > budget_bytes) return;
   *cap = c; *n_entries = segs * c; *n_counts = segs;

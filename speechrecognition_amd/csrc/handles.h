@@ -127,6 +127,8 @@ struct sr_model {
   hipEvent_t ev_scored[2] = {nullptr, nullptr}, ev_consumed[2] = {nullptr, nullptr};
   size_t chunk_frames = 0;
   bool overlap = true;  // search of chunk i on its own stream while chunk i+1 is scored (SRGPU_OVERLAP=0: one stream)
+  size_t defer_budget = (size_t)32 << 30;  // most bytes for the refinement's deferred-leftover segments (SRGPU_DEFER_MB; 0: route off)
+  uint32_t defer_cap_limit = 0;            // most entries per segment, 0: no limit (SRGPU_DEFER_CAP, tests: full segments)
   // profiling
   bool profiling = false;
   std::vector<EventPair> events;

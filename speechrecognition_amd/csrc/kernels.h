@@ -88,8 +88,9 @@ struct GmmRefineArgs {
   uint32_t defer_cap;
 };
 // workspace of the deferred-leftover route for this launch: entries per segment (0: the route does not apply -- one chunk per state, a
-// padded dimension beyond 39, or more than `budget_bytes`), total 16-byte entries, total counters
-void gmm_refine_defer_layout(const GmmRefineArgs& a, size_t budget_bytes, uint32_t* cap, size_t* n_entries, size_t* n_counts);
+// padded dimension beyond 39, or more than `budget_bytes`), at most `cap_limit` when that is not 0; total 16-byte entries, total counters
+void gmm_refine_defer_layout(const GmmRefineArgs& a, size_t budget_bytes, uint32_t cap_limit, uint32_t* cap, size_t* n_entries,
+                             size_t* n_counts);
 size_t gmm_refine_ring_words(const GmmRefineArgs& a);  // needs n_frames, n_pstates, dim, n_slots
 hipError_t launch_gmm_prefilter(const GmmPrefilterArgs& a, int ks32, hipStream_t stream);
 int gmm_prefilter_frames_per_tile();

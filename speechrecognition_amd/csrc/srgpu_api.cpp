@@ -364,9 +364,18 @@ int resolve_dense_kernel(const sr_model* m, int gmm_kernel) {
   return gmm_kernel;
 }
 
-static size_t defer_budget_bytes() {
-  const char* e = getenv("SRGPU_DEFER_MB");
-  return e ? (size_t)strtoull(e, nullptr, 10) << 20 : (size_t)32 << 30;
+// the shape of a refinement launch over n_frames, all that its workspaces depend on
+GmmRefineArgs refine_shape(const sr_model* m, uint64_t n_frames) {
+  GmmRefineArgs ra{};
+  ra.n_frames = n_frames; ra.dim = m->pf_dp; ra.n_pstates = m->pf_pstates; ra.n_slots = m->pf_slots; ra.chunks = m->pf_chunks;
+  return ra;
+}
+// deferred leftovers of a refinement launch over n_frames: entries per segment (0: the route is off), total entries, total counts
+struct DeferLayout { uint32_t cap; size_t n_e, n_c; };
+DeferLayout defer_layout(const sr_model* m, uint64_t n_frames) {
+  DeferLayout d;
+  gmm_refine_defer_layout(refine_shape(m, n_frames), m->defer_budget, m->defer_cap_limit, &d.cap, &d.n_e, &d.n_c);
+  return d;
 }
 
 int reserve_scoring(sr_model* m, int gmm_kernel, uint64_t n_max) {
@@ -389,19 +398,13 @@ int reserve_scoring(sr_model* m, int gmm_kernel, uint64_t n_max) {
     const uint64_t ldT = (n_max + 63) & ~(uint64_t)63;
     const size_t want_T = (size_t)ldT * m->pf_dp, want_mask = (size_t)((m->pf_groups + 1u) & ~1u) * n_max * 4;
     const size_t want_P = m->pf_dp != m->dim ? (size_t)n_max * m->pf_dp + 4 : 0;  // (+4: the rows are read in 16-byte pieces)
-    GmmRefineArgs ra{};
-    ra.n_frames = n_max; ra.dim = m->pf_dp; ra.n_pstates = m->pf_pstates; ra.n_slots = m->pf_slots;
-    const size_t want_ring = gmm_refine_ring_words(ra);
+    const size_t want_ring = gmm_refine_ring_words(refine_shape(m, n_max));
     if (want_T > m->featsT.n || want_P > m->featsP.n || want_mask > m->pf_mask.n || want_ring > m->pf_ring.n) HIP_TRY(hipStreamSynchronize(m->s_gmm));
     HIP_TRY(m->featsT.ensure(want_T));
     if (want_P) HIP_TRY(m->featsP.ensure(want_P));
-    {  // deferred leftovers: within SRGPU_DEFER_MB (default 32 GiB; 0 switches the route off)
-      ra.chunks = m->pf_chunks;
-      uint32_t cap; size_t n_e, n_c;
-      gmm_refine_defer_layout(ra, defer_budget_bytes(), &cap, &n_e, &n_c);
-      if (n_e > m->pf_defer.n || n_c > m->pf_defer_cnt.n) HIP_TRY(hipStreamSynchronize(m->s_gmm));
-      if (n_e) { HIP_TRY(m->pf_defer.ensure(n_e)); HIP_TRY(m->pf_defer_cnt.ensure(n_c)); }
-    }
+    const DeferLayout dl = defer_layout(m, n_max);  // within SRGPU_DEFER_MB (default 32 GiB; 0 switches the route off)
+    if (dl.n_e > m->pf_defer.n || dl.n_c > m->pf_defer_cnt.n) HIP_TRY(hipStreamSynchronize(m->s_gmm));
+    if (dl.n_e) { HIP_TRY(m->pf_defer.ensure(dl.n_e)); HIP_TRY(m->pf_defer_cnt.ensure(dl.n_c)); }
     HIP_TRY(m->pf_mask.ensure(want_mask));  // the refinement reads group pairs
     HIP_TRY(m->pf_ring.ensure(want_ring));
   }
@@ -439,19 +442,15 @@ int launch_scoring(sr_model* m, const float* d_feats, uint64_t n_frames, int gmm
     pa.feats = d_feats; pa.n_frames = n_frames; pa.dim = m->dim;
     pa.apack = m->pf_apack.p; pa.grp_anorm = m->pf_anorm.p; pa.split_begin = m->pf_split_cur;
     pa.mask = m->pf_mask.p; pa.nx = nx; pa.ny = m->pf_ny; pa.chunks = std::min(4u, m->pf_chunks);
-    GmmRefineArgs ra{};
+    GmmRefineArgs ra = refine_shape(m, n_frames);
     const bool padded = m->pf_dp != m->dim;
-    ra.feats = padded ? m->featsP.p : d_feats; ra.featsT = m->featsT.p; ra.n_frames = n_frames; ra.n_frames_ld = ldT; ra.dim = m->pf_dp;
-    ra.n_pstates = m->pf_pstates; ra.chunks = m->pf_chunks;
-    ra.n_dens_ps = m->pf_ndens.p; ra.rows = m->pf_rows.p; ra.n_slots = m->pf_slots;
+    ra.feats = padded ? m->featsP.p : d_feats; ra.featsT = m->featsT.p; ra.n_frames_ld = ldT;
+    ra.n_dens_ps = m->pf_ndens.p; ra.rows = m->pf_rows.p;
     ra.mask = m->pf_mask.p; ra.out = d_out; ra.ld = m->ld;
     ra.n_refined = m->profiling ? m->pf_counter.p : nullptr;
     ra.ring = m->pf_ring.p;
-    {
-      uint32_t cap; size_t n_e, n_c;
-      gmm_refine_defer_layout(ra, defer_budget_bytes(), &cap, &n_e, &n_c);
-      if (cap && n_e <= m->pf_defer.n && n_c <= m->pf_defer_cnt.n) { ra.defer = m->pf_defer.p; ra.defer_cnt = m->pf_defer_cnt.p; ra.defer_cap = cap; }
-    }
+    const DeferLayout dl = defer_layout(m, n_frames);
+    if (dl.cap && dl.n_e <= m->pf_defer.n && dl.n_c <= m->pf_defer_cnt.n) { ra.defer = m->pf_defer.p; ra.defer_cnt = m->pf_defer_cnt.p; ra.defer_cap = dl.cap; }
     if (m->profiling) m->prof.refined_pairs += n_frames * (uint64_t)m->n_states;
     EventPair ep_p{}, ep_r{};
     if ((rc = prof_begin(m, m->s_gmm, 0, &ep))) return rc;
@@ -543,11 +542,38 @@ int score_chunk(sr_model* m, sr_corpus* c, uint64_t f0, uint64_t f1, int gmm_ker
   return SR_OK;
 }
 
-int ensure_score_ws(sr_model* m, const std::vector<Chunk>& chunks) {
+// the chunks of a pass over the corpus, with their score buffers (two when there is more than one chunk) and launch order
+int prepare_chunks(sr_model* m, sr_corpus* c, std::vector<Chunk>* chunks) {
+  *chunks = make_chunks(c, m->chunk_frames);
   uint64_t mx = 0;
-  for (const Chunk& ch : chunks) mx = std::max(mx, ch.f1 - ch.f0);
-  const int nbuf = chunks.size() > 1 ? 2 : 1;
+  for (const Chunk& ch : *chunks) mx = std::max(mx, ch.f1 - ch.f0);
+  const int nbuf = chunks->size() > 1 ? 2 : 1;
   for (int i = 0; i < nbuf; i++) HIP_TRY(m->scores[i].ensure((size_t)mx * m->ld));
+  return ensure_utt_order(m, c, *chunks);
+}
+
+// The pass itself: chunk i is scored on s_gmm into buffer i & 1 while chunk i-1 is searched on s_search (on s_gmm after it with
+// SRGPU_OVERLAP=0).  ev_scored hands a buffer to the search; ev_consumed hands it back to the scoring two chunks later.
+//   score(const Chunk&, double* table)                           enqueues the chunk's scores on s_gmm
+//   search(const Chunk&, const double* table, hipStream_t s)     enqueues its search on s (kind-1 profiling window)
+template <class Score, class Search>
+int run_chunks(sr_model* m, const std::vector<Chunk>& chunks, Score score, Search search) {
+  const hipStream_t s_search = m->overlap ? m->s_search : m->s_gmm;
+  int rc;
+  for (size_t i = 0; i < chunks.size(); i++) {
+    const int buf = (int)(i & 1);
+    if (i >= 2) HIP_TRY(hipStreamWaitEvent(m->s_gmm, m->ev_consumed[buf], 0));
+    if ((rc = score(chunks[i], m->scores[buf].p))) return rc;
+    HIP_TRY(hipEventRecord(m->ev_scored[buf], m->s_gmm));
+    HIP_TRY(hipStreamWaitEvent(s_search, m->ev_scored[buf], 0));
+    EventPair ep{};
+    if ((rc = prof_begin(m, s_search, 1, &ep))) return rc;
+    if ((rc = search(chunks[i], m->scores[buf].p, s_search))) return rc;
+    if ((rc = prof_end(m, s_search, &ep))) return rc;
+    HIP_TRY(hipEventRecord(m->ev_consumed[buf], s_search));
+  }
+  HIP_TRY(hipStreamSynchronize(m->s_search));
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
   return SR_OK;
 }
 
@@ -594,6 +620,12 @@ namespace {
 int check_model(const sr_model* m) {
   if (!m) return fail(SR_EINVAL, "null model handle");
   HIP_TRY(hipSetDevice(m->device));
+  return SR_OK;
+}
+int check_corpus(const sr_model* m, const sr_corpus* c) {
+  int rc = check_model(m);
+  if (rc) return rc;
+  if (!c || c->model != m) return fail(SR_EINVAL, "corpus does not belong to this model");
   return SR_OK;
 }
 
@@ -675,6 +707,8 @@ int model_shell(int device, uint32_t dim, uint32_t n_states, const uint32_t* den
   // the refinement kernel addresses the transposed feature copy of a chunk with 32-bit buffer offsets
   m->chunk_frames = std::min<size_t>(m->chunk_frames, ((size_t)1 << 32) / (4 * (size_t)dim) - 128);
   if (const char* ov = getenv("SRGPU_OVERLAP")) m->overlap = atoi(ov) != 0;
+  if (const char* e = getenv("SRGPU_DEFER_MB")) m->defer_budget = (size_t)strtoull(e, nullptr, 10) << 20;
+  if (const char* e = getenv("SRGPU_DEFER_CAP")) m->defer_cap_limit = std::max(1u, (uint32_t)strtoul(e, nullptr, 10));  // (tests: full segments)
   *out = own.release();
   return SR_OK;
 }
@@ -869,9 +903,8 @@ int sr_corpus_destroy(sr_corpus* c) {
 
 int sr_score_corpus(sr_model* m, sr_corpus* c, int gmm_kernel, double* out) {
   return guarded(__func__, [&]() -> int {
-  int rc = check_model(m);
+  int rc = check_corpus(m, c);
   if (rc) return rc;
-  if (!c || c->model != m) return fail(SR_EINVAL, "corpus does not belong to this model");
   if (!out && c->n_frames) return fail(SR_EINVAL, "out is null");
   // chunk over plain frame ranges; utterance boundaries do not matter for scoring
   const uint64_t F = c->n_frames;
@@ -1111,9 +1144,8 @@ static int gather_words(sr_corpus* c, uint32_t* out_words, uint64_t* out_word_of
 int sr_recognize_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, uint32_t* out_words,
                         uint64_t* out_word_off, double* tb_score, uint16_t* tb_word, uint16_t* tb_bkp) {
   return guarded(__func__, [&]() -> int {
-  int rc = check_model(m);
+  int rc = check_corpus(m, c);
   if (rc) return rc;
-  if (!c || c->model != m) return fail(SR_EINVAL, "corpus does not belong to this model");
   if (!l || l->model != m) return fail(SR_EINVAL, "lexicon does not belong to this model");
   if (!p || !out_word_off || (!out_words && c->n_frames)) return fail(SR_EINVAL, "null argument");
   const uint32_t U = c->n_utts;
@@ -1125,9 +1157,8 @@ int sr_recognize_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_searc
   HIP_TRY(c->out_count.ensure(U));
   HIP_TRY(c->out_flags.ensure(U));
   HIP_TRY(hipMemsetAsync(c->out_flags.p, 0, sizeof(uint32_t) * std::max(1u, U), m->s_gmm));
-  const std::vector<Chunk> chunks = make_chunks(c, m->chunk_frames);
-  if ((rc = ensure_score_ws(m, chunks))) return rc;
-  if ((rc = ensure_utt_order(m, c, chunks))) return rc;
+  std::vector<Chunk> chunks;
+  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
 
   if (l->big) {  // hypothesis arrays of the utterances in flight
     uint32_t most = 0;
@@ -1157,34 +1188,23 @@ int sr_recognize_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_searc
   da.tb_score = c->tb_score.p; da.tb_word = c->tb_word.p; da.tb_bkp = c->tb_bkp.p;
   da.out_words = c->out_words.p; da.out_count = c->out_count.p; da.out_flags = c->out_flags.p;
 
-  // chunk i is scored on s_gmm into buffer i&1 while chunk i-1 is searched on s_search
-  hipStream_t s_search = m->overlap ? m->s_search : m->s_gmm;
-  for (size_t i = 0; i < chunks.size(); i++) {
-    const Chunk& ch = chunks[i];
-    const int buf = (int)(i & 1);
-    if (i >= 2) HIP_TRY(hipStreamWaitEvent(m->s_gmm, m->ev_consumed[buf], 0));
-    if ((rc = score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, m->scores[buf].p))) return rc;
-    HIP_TRY(hipEventRecord(m->ev_scored[buf], m->s_gmm));
-    HIP_TRY(hipStreamWaitEvent(s_search, m->ev_scored[buf], 0));
-    da.scores = m->scores[buf].p; da.frame_base = ch.f0; da.utt_first = ch.u0; da.n_utts = ch.u1 - ch.u0;
-    EventPair ep{};
-    if ((rc = prof_begin(m, s_search, 1, &ep))) return rc;
-    if (l->big && !da.force_general && !da.force_slots && decode_words_applies(da)) {
-      // more than 8192 type-padded positions, but words of at most four: the word-per-lane kernel does not depend on the slot count
-      // (ADVICE r3); what it flags (a negative emission cost) is redone by the device-memory kernel, which exits at once elsewhere
-      HIP_TRY(launch_decode_words(da, s_search));
-      da.only_flagged = 1;
-      HIP_TRY(launch_decode_big(da, c->big_ws.p, s_search));
-      da.only_flagged = 0;
-    } else {
-      HIP_TRY(l->big ? launch_decode_big(da, c->big_ws.p, s_search) : launch_decode(da, s_search));
-    }
-    if ((rc = prof_end(m, s_search, &ep))) return rc;
-    HIP_TRY(hipEventRecord(m->ev_consumed[buf], s_search));
-    if (m->profiling) m->prof.search_bytes += (8.0 * m->n_states + 4.0 * l->n_slots) * (double)(ch.f1 - ch.f0);
-  }
-  HIP_TRY(hipStreamSynchronize(m->s_search));
-  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); },
+      [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
+        da.scores = table; da.frame_base = ch.f0; da.utt_first = ch.u0; da.n_utts = ch.u1 - ch.u0;
+        if (l->big && !da.force_general && !da.force_slots && decode_words_applies(da)) {
+          // more than 8192 type-padded positions, but words of at most four: the word-per-lane kernel does not depend on the slot
+          // count; what it flags (a negative emission cost) is redone by the device-memory kernel, which exits at once elsewhere
+          HIP_TRY(launch_decode_words(da, s));
+          da.only_flagged = 1;
+          HIP_TRY(launch_decode_big(da, c->big_ws.p, s));
+          da.only_flagged = 0;
+        } else {
+          HIP_TRY(l->big ? launch_decode_big(da, c->big_ws.p, s) : launch_decode(da, s));
+        }
+        if (m->profiling) m->prof.search_bytes += (8.0 * m->n_states + 4.0 * l->n_slots) * (double)(ch.f1 - ch.f0);
+        return SR_OK;
+      });
+  if (rc) return rc;
 
   if ((rc = gather_words(c, out_words, out_word_off))) return rc;
   if (tb_score) HIP_TRY(hipMemcpy(tb_score, c->tb_score.p, sizeof(double) * (F + U), hipMemcpyDeviceToHost));
@@ -1198,9 +1218,8 @@ int sr_recognize_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_searc
 int sr_traceback_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const uint16_t* tb_word, const uint16_t* tb_bkp,
                         uint32_t* out_words, uint64_t* out_word_off) {
   return guarded(__func__, [&]() -> int {
-  int rc = check_model(m);
+  int rc = check_corpus(m, c);
   if (rc) return rc;
-  if (!c || c->model != m) return fail(SR_EINVAL, "corpus does not belong to this model");
   if (!l || l->model != m) return fail(SR_EINVAL, "lexicon does not belong to this model");
   if (!tb_word || !tb_bkp || !out_word_off || (!out_words && c->n_frames)) return fail(SR_EINVAL, "null argument");
   const uint32_t U = c->n_utts;
@@ -1324,15 +1343,14 @@ int sr_bigram_destroy(sr_bigram* b) {
 int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr_bigram_params* p, uint32_t* out_word,
                                float* out_score, uint32_t* out_time, uint64_t* out_off) {
   return guarded(__func__, [&]() -> int {
-  int rc = check_model(m);
+  int rc = check_corpus(m, c);
   if (rc) return rc;
-  if (!c || c->model != m) return fail(SR_EINVAL, "corpus does not belong to this model");
   if (!b || b->model != m) return fail(SR_EINVAL, "bigram search net does not belong to this model");
   if (!p || !out_off || ((!out_word || !out_score || !out_time) && c->n_frames)) return fail(SR_EINVAL, "null argument");
   const uint32_t U = c->n_utts, W = b->n_words;
   const uint64_t F = c->n_frames;
-  const std::vector<Chunk> chunks = make_chunks(c, m->chunk_frames);
-  if ((rc = ensure_score_ws(m, chunks))) return rc;
+  std::vector<Chunk> chunks;
+  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
   // traceback book: 2 start entries + (word ends kept per frame <= W) * T per utterance
   const uint64_t per_frame = p->max_word_ends ? std::min<uint64_t>(p->max_word_ends, W) : W;
   std::vector<uint64_t> book_off(U + 1, 0);
@@ -1351,7 +1369,6 @@ int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr
   HIP_TRY(b->out_flags.ensure(U));
 
   BigramArgs ba{};
-  if ((rc = ensure_utt_order(m, c, chunks))) return rc;
   ba.ld = m->ld; ba.frame_off = c->d_frame_off.p; ba.utt_order = c->utt_order.p;
   ba.n_words = W; ba.silence = b->silence; ba.n_positions = b->n_positions;
   ba.slot_off = b->slot_off.p; ba.slot_mix = b->slot_mix.p; ba.mixtures = b->mixtures.p; ba.pos_info = b->pos_info.p; ba.pos_slot = b->pos_slot.p; ba.lmT = b->lmT.p; ba.lm_rowmin = b->lm_rowmin.p; ba.lm_rowmax = b->lm_rowmax.p;
@@ -1367,25 +1384,15 @@ int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr
   ba.out_word = b->out_word.p; ba.out_score = b->out_score.p; ba.out_time = b->out_time.p;
   ba.out_count = b->out_count.p; ba.out_flags = b->out_flags.p;
 
-  hipStream_t s_search = m->overlap ? m->s_search : m->s_gmm;
-  for (size_t i = 0; i < chunks.size(); i++) {
-    const Chunk& ch = chunks[i];
-    const int buf = (int)(i & 1);
-    if (i >= 2) HIP_TRY(hipStreamWaitEvent(m->s_gmm, m->ev_consumed[buf], 0));
-    if ((rc = score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, m->scores[buf].p))) return rc;
-    HIP_TRY(hipEventRecord(m->ev_scored[buf], m->s_gmm));
-    HIP_TRY(hipStreamWaitEvent(s_search, m->ev_scored[buf], 0));
-    ba.scores = m->scores[buf].p; ba.frame_base = ch.f0; ba.utt_first = ch.u0; ba.n_utts = ch.u1 - ch.u0;
-    EventPair ep{};
-    if ((rc = prof_begin(m, s_search, 1, &ep))) return rc;
-    HIP_TRY(launch_bigram(ba, s_search));
-    if ((rc = prof_end(m, s_search, &ep))) return rc;
-    HIP_TRY(hipEventRecord(m->ev_consumed[buf], s_search));
-    // SURVEY 8(d)'s decoder model, 8 S + 4 P bytes per frame, with P = the bigram search's positions (words + their silence copies)
-    if (m->profiling) m->prof.search_bytes += (8.0 * m->n_states + 4.0 * b->n_positions) * (double)(ch.f1 - ch.f0);
-  }
-  HIP_TRY(hipStreamSynchronize(m->s_search));
-  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); },
+      [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
+        ba.scores = table; ba.frame_base = ch.f0; ba.utt_first = ch.u0; ba.n_utts = ch.u1 - ch.u0;
+        HIP_TRY(launch_bigram(ba, s));
+        // SURVEY 8(d)'s decoder model, 8 S + 4 P bytes per frame, with P = the bigram search's positions (words + their silence copies)
+        if (m->profiling) m->prof.search_bytes += (8.0 * m->n_states + 4.0 * b->n_positions) * (double)(ch.f1 - ch.f0);
+        return SR_OK;
+      });
+  if (rc) return rc;
 
   std::vector<uint32_t> counts(U), flags(U), dw(F + U), dt(F + U);
   std::vector<float> ds(F + U);
@@ -1426,10 +1433,9 @@ int sr_recognize_batch(sr_model* m, sr_lexicon* l, const sr_search_params* p, co
 static int align_common(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
                         uint16_t silence_state, double thr, bool pruned, int gmm_kernel, uint16_t* out_states,
                         double* out_cost) {
-  int rc = check_model(m);
+  int rc = check_corpus(m, c);
   if (rc) return rc;
   if (gmm_kernel == SR_GMM_DEFAULT) gmm_kernel = SR_GMM_PREFILTER;  // the aligner scores only its automaton's states: listed, bit-exact
-  if (!c || c->model != m) return fail(SR_EINVAL, "corpus does not belong to this model");
   if (!automata || !aut_off || !tdp || !out_states || !out_cost) return fail(SR_EINVAL, "null argument");
   const uint32_t U = c->n_utts;
   const uint64_t F = c->n_frames;
@@ -1453,8 +1459,8 @@ static int align_common(sr_model* m, sr_corpus* c, const uint16_t* automata, con
   HIP_TRY(c->backptr.ensure(bp_off[U]));
   HIP_TRY(c->out_states.ensure(F));
   HIP_TRY(c->out_cost.ensure(U));
-  const std::vector<Chunk> chunks = make_chunks(c, m->chunk_frames);
-  if ((rc = ensure_score_ws(m, chunks))) return rc;
+  std::vector<Chunk> chunks;
+  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
   // The aligner reads scores of its automaton's states only (N of S): with a bit-exact kernel requested, score just
   // those (frame, state) pairs -- the direct-form kernel in listed mode, the same bits as the dense table would hold.
   // (SR_GMM_MFMA keeps the dense FP64-MFMA table: its rounding differs.)
@@ -1484,43 +1490,34 @@ static int align_common(sr_model* m, sr_corpus* c, const uint16_t* automata, con
     HIP_TRY(c->al_blk_list.upload(blk_list.data(), blk_list.size()));
   }
   AlignArgs aa{};
-  if ((rc = ensure_utt_order(m, c, chunks))) return rc;
   aa.ld = m->ld; aa.frame_off = c->d_frame_off.p; aa.utt_order = c->utt_order.p; aa.automata = c->automata.p; aa.aut_off = c->aut_off.p;
   aa.tdp_loop = tdp[0]; aa.tdp_forward = tdp[1]; aa.tdp_skip = tdp[2]; aa.silence_state = silence_state;
   aa.pruning_threshold = thr; aa.backptr = c->backptr.p; aa.bp_off = c->bp_off.p; aa.max_positions = max_n;
   aa.out_states = c->out_states.p; aa.out_cost = c->out_cost.p;
-  for (size_t i = 0; i < chunks.size(); i++) {
-    const Chunk& ch = chunks[i];
-    const int buf = (int)(i & 1);
-    if (i >= 2) HIP_TRY(hipStreamWaitEvent(m->s_gmm, m->ev_consumed[buf], 0));
-    if ((rc = srhost::corpus_ready(c, ch.f0, ch.f1, m->s_gmm))) return rc;
-    if (listed) {
-      GmmExactArgs ga{};
-      ga.feats = c->feats.p; ga.n_frames = c->n_frames; ga.dim = m->dim; ga.n_states = m->n_states;
-      ga.dens_off = m->dens_off.p; ga.means = m->means.p; ga.inv_vars = m->inv_vars.p; ga.norm = m->norm.p; ga.logw = m->logw.p;
-      ga.out = m->scores[buf].p; ga.ld = m->ld;
-      GmmExactList gl{};
-      gl.blk_frame0 = c->al_blk_frame0.p; gl.blk_frames = c->al_blk_frames.p; gl.blk_list = c->al_blk_list.p;
-      gl.list_off = c->al_list_off.p; gl.states = c->al_states.p;
-      gl.blk_first = blk_first_of_utt[ch.u0]; gl.frame_base = ch.f0;
-      EventPair eg{};
-      if ((rc = prof_begin(m, m->s_gmm, 0, &eg))) return rc;
-      HIP_TRY(launch_gmm_exact_listed(ga, !m->max_approx, gl, blk_first_of_utt[ch.u1] - blk_first_of_utt[ch.u0], m->s_gmm));
-      if ((rc = prof_end(m, m->s_gmm, &eg))) return rc;
-    } else if ((rc = launch_scoring(m, c->feats.p + ch.f0 * m->dim, ch.f1 - ch.f0, gmm_kernel, m->scores[buf].p))) {
-      return rc;
-    }
-    HIP_TRY(hipEventRecord(m->ev_scored[buf], m->s_gmm));
-    HIP_TRY(hipStreamWaitEvent(m->s_search, m->ev_scored[buf], 0));
-    aa.scores = m->scores[buf].p; aa.frame_base = ch.f0; aa.utt_first = ch.u0; aa.n_utts = ch.u1 - ch.u0;
-    EventPair ep{};
-    if ((rc = prof_begin(m, m->s_search, 1, &ep))) return rc;
-    HIP_TRY(pruned ? launch_align_pruned(aa, m->s_search) : launch_align_full(aa, m->s_search));
-    if ((rc = prof_end(m, m->s_search, &ep))) return rc;
-    HIP_TRY(hipEventRecord(m->ev_consumed[buf], m->s_search));
-  }
-  HIP_TRY(hipStreamSynchronize(m->s_search));
-  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  rc = run_chunks(m, chunks,
+      [&](const Chunk& ch, double* table) -> int {
+        int r = srhost::corpus_ready(c, ch.f0, ch.f1, m->s_gmm);
+        if (r) return r;
+        if (!listed) return launch_scoring(m, c->feats.p + ch.f0 * m->dim, ch.f1 - ch.f0, gmm_kernel, table);
+        GmmExactArgs ga{};
+        ga.feats = c->feats.p; ga.n_frames = c->n_frames; ga.dim = m->dim; ga.n_states = m->n_states;
+        ga.dens_off = m->dens_off.p; ga.means = m->means.p; ga.inv_vars = m->inv_vars.p; ga.norm = m->norm.p; ga.logw = m->logw.p;
+        ga.out = table; ga.ld = m->ld;
+        GmmExactList gl{};
+        gl.blk_frame0 = c->al_blk_frame0.p; gl.blk_frames = c->al_blk_frames.p; gl.blk_list = c->al_blk_list.p;
+        gl.list_off = c->al_list_off.p; gl.states = c->al_states.p;
+        gl.blk_first = blk_first_of_utt[ch.u0]; gl.frame_base = ch.f0;
+        EventPair eg{};
+        if ((r = prof_begin(m, m->s_gmm, 0, &eg))) return r;
+        HIP_TRY(launch_gmm_exact_listed(ga, !m->max_approx, gl, blk_first_of_utt[ch.u1] - blk_first_of_utt[ch.u0], m->s_gmm));
+        return prof_end(m, m->s_gmm, &eg);
+      },
+      [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
+        aa.scores = table; aa.frame_base = ch.f0; aa.utt_first = ch.u0; aa.n_utts = ch.u1 - ch.u0;
+        HIP_TRY(pruned ? launch_align_pruned(aa, s) : launch_align_full(aa, s));
+        return SR_OK;
+      });
+  if (rc) return rc;
   if (F) HIP_TRY(hipMemcpy(out_states, c->out_states.p, sizeof(uint16_t) * F, hipMemcpyDeviceToHost));
   if (U) HIP_TRY(hipMemcpy(out_cost, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToHost));
   if (m->profiling) {
@@ -1547,10 +1544,9 @@ int sr_align_corpus_pruned(sr_model* m, sr_corpus* c, const uint16_t* automata, 
 
 int sr_path_scores_corpus(sr_model* m, sr_corpus* c, const uint16_t* states, int gmm_kernel, double* out) {
   return guarded(__func__, [&]() -> int {
-  int rc = check_model(m);
+  int rc = check_corpus(m, c);
   if (rc) return rc;
   if (gmm_kernel == SR_GMM_DEFAULT) gmm_kernel = SR_GMM_PREFILTER;  // (frame, state) pairs scored directly, bit-exact
-  if (!c || c->model != m) return fail(SR_EINVAL, "corpus does not belong to this model");
   const uint64_t F = c->n_frames;
   if (F == 0) return SR_OK;
   if (!states || !out) return fail(SR_EINVAL, "null argument");
@@ -1622,9 +1618,8 @@ int sr_model_tying_info(const sr_model* m, uint32_t* n_mean, uint32_t* n_var) {
 int sr_accumulate_corpus(sr_model* m, sr_corpus* c, const uint16_t* states, int first_pass, int max_approx, double* mean_acc,
                          double* mean_w, double* var_acc, double* var_w) {
   return guarded(__func__, [&]() -> int {
-  int rc = check_model(m);
+  int rc = check_corpus(m, c);
   if (rc) return rc;
-  if (!c || c->model != m) return fail(SR_EINVAL, "corpus does not belong to this model");
   const bool to_host = mean_acc || mean_w || var_acc || var_w;  // all NULL: the statistics stay on the device
   if (to_host && (!mean_acc || !mean_w || !var_acc || !var_w)) return fail(SR_EINVAL, "null output (pass all four arrays, or none)");
   const uint64_t F = c->n_frames;
@@ -1692,9 +1687,8 @@ int sr_model_create_from_accumulated(sr_model* m, sr_corpus* c, int pooling, int
   return guarded(__func__, [&]() -> int {
   if (!out) return fail(SR_EINVAL, "out is null");
   *out = nullptr;
-  int rc = check_model(m);
+  int rc = check_corpus(m, c);
   if (rc) return rc;
-  if (!c || c->model != m) return fail(SR_EINVAL, "corpus does not belong to this model");
   if (pooling < 0 || pooling > 2) return fail(SR_EINVAL, "pooling must be 0 (global), 1 (mixture) or 2 (none)");
   return srhost::finalize_accumulated(m, c, pooling, max_approx, out);
   });

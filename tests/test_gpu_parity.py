@@ -256,23 +256,37 @@ def test_negative_emission_costs_on_short_word_lexica(tmp_path, oracle_lib, seed
     o.close()
 
 
-def test_chunked_pipeline_matches_single_chunk(tmp_path, oracle_lib, monkeypatch):
-    """A tiny score-workspace budget forces many chunks through the two-stream pipeline."""
+@pytest.mark.parametrize("overlap", ["1", "0"])
+def test_chunked_pipeline_matches_single_chunk(tmp_path, oracle_lib, monkeypatch, overlap):
+    """A tiny score-workspace budget forces many chunks through the two-stream pipeline (or, with
+    SRGPU_OVERLAP=0, through one stream): recognition and alignment, listed and dense scoring."""
+    monkeypatch.setenv("SRGPU_OVERLAP", overlap)
     lex, spec, mp = _random_setup(tmp_path, 401, 60, 3, 1, 4, 39)
     feats, off = synth.make_batch(40, 20, 60, 39, seed=402)
     word_off, automaton, sil_state = lex.flatten()
+    rng = np.random.default_rng(403)
+    auts = []
+    for u in range(40):
+        a = [sil_state]
+        for w in rng.integers(1, lex.n_words, size=2):
+            a += list(automaton[word_off[w]:word_off[w + 1]]) + [sil_state]
+        assert len(a) <= int(off[u + 1] - off[u])
+        auts.append(np.asarray(a, dtype=np.uint16))
     results = []
     for mb in ("4096", "1"):
         monkeypatch.setenv("SRGPU_SCORE_CHUNK_MB", mb)
         with capi.Model.from_mixset(mp, 39) as m:
             lexh = m.lexicon(word_off, automaton, lex.silence_idx, (3.0, 0.0, 30.0), sil_state)
             corpus = m.upload(feats, off)
-            results.append((corpus.recognize(lexh, 200.0, 10.0, capi.GMM_MFMA), corpus.score(capi.GMM_MFMA)))
+            results.append((corpus.recognize(lexh, 200.0, 10.0, capi.GMM_MFMA), corpus.score(capi.GMM_MFMA),
+                            [corpus.align(auts, (3.0, 0.0, 30.0), sil_state, k) for k in (capi.GMM_PREFILTER, capi.GMM_MFMA)]))
             corpus.close()
             lexh.close()
-    (w0, o0), s0 = results[0]
-    (w1, o1), s1 = results[1]
+    (w0, o0), s0, al0 = results[0]
+    (w1, o1), s1, al1 = results[1]
     assert np.array_equal(w0, w1) and np.array_equal(o0, o1) and np.array_equal(s0.view(np.uint64), s1.view(np.uint64))
+    for (st0, c0), (st1, c1) in zip(al0, al1):
+        assert np.array_equal(st0, st1) and np.array_equal(c0.view(np.uint64), c1.view(np.uint64))
     o = oracle_lib.Oracle(mp, 39, lex, am_threshold=200.0)
     for u in (0, 17, 39):
         assert np.array_equal(o.decode(feats[int(off[u]):int(off[u + 1])]), w0[int(o0[u]):int(o0[u + 1])])
