@@ -7,18 +7,35 @@
 // on the fp16 matrix cores: both operands rounded ONCE to fp16 (11 significant bits), one MFMA per k-step, fp32
 // accumulation; konst_c enters through three spare k slots as an exact 3-term fp16 expansion (33 bits) times 1.  The
 // model side is scaled by a power of two sA (host: largest coefficient or constant -> below 2^14) so that fp16's
-// narrow exponent range is used well; scores, norms and the candidate test stay in scaled units.  Error bound:
-//   |delta a_k| <= 2^-11 |a_k| + 2^-25 / sA (subnormal spacing), |delta b_k| <= 2^-11 |b_k| + 2^-25; products of two
+// narrow exponent range is used well; scores, norms and the candidate test stay in scaled units.  Error bound, with
+// a^, b^ the fp16 operands and da = a^ - a, db = b^ - b their rounding residuals (all norms 2-norms over k):
+//   sum a^ b^ - sum a b = sum a^ db + sum da b EXACTLY, so |..| <= |a^||db| + |da||b| (Cauchy-Schwarz); products of two
 //   fp16 values are exact in fp32; <= 81 + 3 fp32 additions, each off by 2^-24 of a partial sum that never exceeds
-//   |konst| + sum |a b| (first order):
-//   |approx - exact| <= (2^-10 (1 + 2^-12) + 87 * 2^-24) |a||b| + 87 * 2^-24 |konst| + 2^-25 (|b|_1 / sA + |a|_1) (1 + 2^-11)
-// -> eps = kKappa16 |a||b| + kKonst16 |konst| + kAbs16 (|b| / sA + |a|),  kKappa16 = 1.05e-3 (needed 9.82e-4: the
-//    operand roundings are round-to-nearest by construction -- v_cvt_f16_f32 here, float -> _Float16 on the host, whose
-//    double rounding adds 2^-13 relative to the 2^-11 -- so only the 87 * 2^-24 part rests on the hardware),
-//    kKonst16 = 1.1e-5 (needed 5.19e-6 = 87 * 2^-24: x2, so that an accumulator that TRUNCATED every addition, 2^-23
-//    each, would still be inside), kAbs16 = 6.0e-7 (needed 2^-25 (1 + 2^-11) sqrt(K) = 2.92e-7 at the padded K = 96,
-//    |v|_1 <= sqrt(K) |v|_2: x2);  |a|, |konst| = the largest over the state's densities, rounded up on the host;
-//    |b| per frame, rounded up.
+//   |konst| + sum |a^ b^| <= |konst| + |a^|(|b| + |db|) (first order); the konst expansion is off by 2^-33 |konst|:
+//   |approx - exact| <= (1 + k) |a^||db| + (|da| + k |a^|) |b| + k |konst|,   k = 87 * 2^-24
+// -> eps = (1 + kAcc16) |a^||db| + (|da| + kAcc16 |a^|) |b| + kAcc16 |konst| + kAbs16 (|b| + |a|),
+//    kAcc16 = 1.1e-5 (needed 5.19e-6 = 87 * 2^-24: x2, so that an accumulator that TRUNCATED every addition, 2^-23
+//    each, would still be inside, and for the second-order and konst-expansion terms); the residuals are exact, so only
+//    the accumulation term rests on the hardware.  |a|, |konst|, |da|, |a^| = the largest over the state's densities,
+//    computed in double from the fp16 coefficients the host packs and rounded up (the konst slots are not among them: the
+//    expansion's 2^-33 |konst| is inside kAcc16's factor 2); |b| per frame from the fp32 b, rounded up (x 1.0001: covers the fp32 x^2, the sum of squares and sqrtf);
+//    |db| per frame from the fp32 residuals (fmaf(x, x, -x^2^) against the exact x^2, x - x^ exact), rounded up the
+//    same way and capped at kPfRes16 |b| (below).
+// The candidate limit is never above the norm-only bound this path used before,
+//   eps_0 = kKappa16 |a||b| + kAcc16 |konst| + kAbs16 (|b| + |a|),  kKappa16 = 1.05e-3 (needed 9.82e-4: 2^-10 (1 + 2^-12)
+//   for two round-to-nearest operand roundings -- v_cvt_f16_f32 here, double -> float -> _Float16 on the host -- plus
+//   87 * 2^-24), kAbs16 = 6.0e-7 (fp16 subnormal spacing: needed 2^-25 (1 + 2^-11) sqrt(K) = kSub16 = 2.92e-7 at the
+//   padded K = 96, |v|_1 <= sqrt(K) |v|_2: x2):
+//   * per frame, |db| is capped at kPfRes16 |b|, kPfRes16 = 4.8835e-4 >= 2^-11 (1 + 2^-24) + 2^-24 (one fp16 rounding of the
+//     fp32 x^2, itself 2^-24 off).  A normal fp16 slot is off by at most that fraction of its b_k, a subnormal one by
+//     2^-25 (1 + 2^-11), so |db| <= kPfRes16 |b| + kSub16 and the capped limit undercounts by at most
+//     (1 + kAcc16) kSub16 |a^|, which the kAbs16 |a| term holds wherever (1 + kAcc16) kSub16 |a^| <= kAbs16 |a|;
+//   * per state, the host (pack_prefilter) takes the residual form only where that holds and its |b| coefficient plus
+//     kPfRes16 times its |db| coefficient stays 2^-12 below eps_0's |b| coefficient kKappa16 |a| + kAbs16; every other state
+//     keeps eps_0 (a state of subnormal-range coefficients, or a NaN).  So a candidate mask never grows.
+//   The constants live in kernels.h (pf_bound: kappa, acc, abs, sub; kPfRes16); the host folds them and the state's norms
+//   into three coefficients per state slot, so that the kernel spends one instruction per (frame block, state) on the limit
+//   beyond the norm-only form and nothing per state.
 // The accumulation model itself (<= 2^-24 of the running magnitude per addition, whatever the order inside the
 // instruction) is probed on the device the model is created on, next to the subnormal probe: probe_fp16_accumulation()
 // runs adversarial 96-term dot products with known exact sums through the same three-instruction MFMA chain and
@@ -26,7 +43,7 @@
 // Every density whose approximation lies within 2*eps of the state's smallest approximation -- plus anything that is
 // not a number -- is a candidate; the true arg-min is provably among them.  A feature beyond fp16's range
 // (|x| > 255) turns its frame's scores into inf/NaN: every density stays a candidate.  P writes one 32-bit candidate
-// mask per (frame, state): 1.09 bits set on average on the bench model.
+// mask per (frame, state): 1.09 bits set on average on the bench model with the norm-only bound eps_0.
 // (Measured alternative, removed again: both operands split in two bf16 terms, three products -- a 7x tighter bound,
 // 1.01 candidates, but twice the prefilter time for 20 % less refinement time.)
 //
@@ -34,9 +51,10 @@
 // (Mixtures.cpp:645-690): the minimum over the candidates is the minimum over all densities, bit for bit what
 // MixtureModel::score returns.
 //
-// K = 128 (round 5, dim 47..62: four k-steps): <= 127 + 4 additions -> the same formula with 132 in place of 87:
-//    kKappa16 needs 9.85e-4 (1.05e-3 stays), kKonst16 = 1.6e-5 (2 x 132 * 2^-24 = 1.57e-5), kAbs16 = 7.0e-7 (2 x 2^-25 (1 + 2^-11) sqrt(128)
-//    = 6.75e-7); the accumulation probe runs its 128-term chain against 132 * 2^-24 on such a model's device.
+// K = 128 (round 5, dim 47..62: four k-steps): <= 127 + 4 additions -> the same formulas with 132 in place of 87:
+//    kKappa16 needs 9.85e-4 (1.05e-3 stays), kAcc16 = 1.6e-5 (2 x 132 * 2^-24 = 1.57e-5), kSub16 = 3.38e-7 (2^-25 (1 + 2^-11)
+//    sqrt(128) = 3.373e-7), kAbs16 = 7.0e-7 (x2); the accumulation probe runs its 128-term chain against 132 * 2^-24 on such a
+//    model's device.
 //
 // Limits of this path: max-approx only, <= 128 densities per mixture (a mixture of more than 32 spans 2 or 4
 // consecutive 32-slot pseudo-states; up to 256 = 8 of them while the dimension is <= 39), dim <= 62 (K = 2*dim + 3 <= 128);
@@ -69,12 +87,8 @@ static constexpr int kGroupBlocks = 8;     // every 4-state group is padded to 8
 // stage first, so that the pipeline runs across stage boundaries and the LDS-DMA of stage s+2 goes into the buffer
 // everybody has just finished reading.
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-static constexpr float kKappa16 = 1.05e-3f;
-template <int KS32> struct PfBound { static constexpr float kKonst16 = 1.1e-5f, kAbs16 = 6.0e-7f; };  // K <= 96 (file header)
-template <> struct PfBound<4> { static constexpr float kKonst16 = 1.6e-5f, kAbs16 = 7.0e-7f; };        // K = 128
 
-__device__ inline uint32_t pack_f16x2(float lo, float hi) {
-  const _Float16 l = (_Float16)lo, h = (_Float16)hi;
+__device__ inline uint32_t pack_f16x2(_Float16 l, _Float16 h) {
   return (uint32_t)__builtin_bit_cast(uint16_t, l) | ((uint32_t)__builtin_bit_cast(uint16_t, h) << 16);
 }
 
@@ -101,9 +115,9 @@ __global__ __launch_bounds__(kPWaves * 64, (NB <= 2 ? 3 : 2)) void gmm_prefilter
   const uint32_t g0 = a.split_begin[y], g1 = a.split_begin[y + 1];
   const uint64_t frame0 = (uint64_t)x * kTileFrames + (uint64_t)wave * (NB * 16);
 
-  // ---- B fragments (fp16) and |b| per frame ---------------------------------------------------------------------
+  // ---- B fragments (fp16), |b| and the rounding residual |b^ - b| per frame --------------------------------------
   uint4 bf[NB][KS32];
-  float bnorm[NB];
+  float bnorm[NB], dbnorm[NB];
   {
     float* fl = reinterpret_cast<float*>(lds);
     const uint64_t tile_first = (uint64_t)x * kTileFrames;
@@ -117,24 +131,35 @@ __global__ __launch_bounds__(kPWaves * 64, (NB <= 2 ? 3 : 2)) void gmm_prefilter
       const uint32_t row = (uint32_t)wave * (NB * 16) + nb * 16 + c;
       const bool valid = row < tile_frames;
       const float* xr = fl + (valid ? row : 0u) * a.dim;
-      float n2 = 0.0f;
+      float n2 = 0.0f, e2 = 0.0f;
 #pragma unroll
       for (int ks = 0; ks < KS32; ks++) {
-        float v[8];
+        _Float16 v[8];
 #pragma unroll
         for (int j = 0; j < 8; j++) {
           const uint32_t k = 32u * ks + 8u * g + j, d = k >> 1;
           const float xf = (valid && d < a.dim) ? xr[d < a.dim ? d : 0u] : 0.0f;
-          float b = (k & 1u) ? xf : xf * xf;  // k = 2d -> x^2, 2d+1 -> x   (fp32 rounding of x^2: 2^-24, inside the margin)
+          const float b = (k & 1u) ? xf : xf * xf;  // k = 2d -> x^2, 2d+1 -> x   (fp32 rounding of x^2: 2^-24, inside the margin)
           n2 += b * b;
-          if (valid && k >= 2u * a.dim && k < 2u * a.dim + 3u) b = 1.0f;  // the three konst slots; not part of |b|
-          v[j] = b;
+          _Float16 h = (_Float16)b;
+          const float bh = (float)h;
+          // b - b^ against the EXACT x^2 (one rounding of a residual: 2^-24 of it) or x (exact: both are multiples of ulp(x))
+          const float e = (k & 1u) ? xf - bh : __builtin_fmaf(xf, xf, -bh);
+          e2 += e * e;  // the konst slots and the padding have x = 0 here: residual 0
+          if (valid && k >= 2u * a.dim && k < 2u * a.dim + 3u) h = (_Float16)1.0f;  // the three konst slots; not part of |b|
+          v[j] = h;
         }
         bf[nb][ks] = make_uint4(pack_f16x2(v[0], v[1]), pack_f16x2(v[2], v[3]), pack_f16x2(v[4], v[5]), pack_f16x2(v[6], v[7]));
       }
       n2 += __shfl_xor(n2, 16);
       n2 += __shfl_xor(n2, 32);
+      e2 += __shfl_xor(e2, 16);
+      e2 += __shfl_xor(e2, 32);
       bnorm[nb] = sqrtf(n2) * 1.0001f;  // rounded up
+      // rounded up the same way, then capped at kPfRes16 |b|: what a subnormal residual adds beyond that is inside kAbs16 |a|
+      // (file header).  fminf keeps a NaN of either side only when both are NaN -- a NaN or inf feature makes the
+      // frame's scores inf/NaN and every density a candidate anyway.
+      dbnorm[nb] = fminf(sqrtf(e2) * 1.0001f, kPfRes16 * bnorm[nb]);
     }
     __syncthreads();
   }
@@ -206,10 +231,9 @@ __global__ __launch_bounds__(kPWaves * 64, (NB <= 2 ? 3 : 2)) void gmm_prefilter
       for (int nb = 0; nb < NB; nb++) ap[nb][j] = acc[nb];
     }
     // ---- candidate mask of state slot g of this group, for the lane's frame(s) (scaled units) ---------------------
-    const float2 nk = reinterpret_cast<const float2*>(a.grp_anorm)[4u * grp + g];  // sA |a|, sA |konst| (rounded up)
-    // 2 eps = lim1 |b| + lim0 (the bound of the file header, the frame's part factored out: 2 instructions per frame block)
-    constexpr float kKonst16 = PfBound<KS32>::kKonst16, kAbs16 = PfBound<KS32>::kAbs16;
-    const float lim1 = 2.0f * (kKappa16 * nk.x + kAbs16), lim0 = 2.0f * (kKonst16 * nk.y + kAbs16 * nk.x);
+    // 2 eps = limD |b^ - b| + lim1 |b| + lim0 of state slot g (the bound of the file header, the frame's part factored out and
+    // the state's part folded on the host: 2 instructions per frame block)
+    const float4 lim = reinterpret_cast<const float4*>(a.grp_lim)[4u * grp + g];
 #pragma unroll
     for (int nb = 0; nb < NB; nb++) {
       // v_min3_f32 directly: the hardware minimum already drops (quiet) NaNs; fminf() would canonicalise every operand
@@ -224,7 +248,7 @@ __global__ __launch_bounds__(kPWaves * 64, (NB <= 2 ? 3 : 2)) void gmm_prefilter
               "v"(ap[nb][j + 1][1]), "v"(ap[nb][j + 1][2]), "v"(ap[nb][j + 1][3]));
       if (a.chunks >= 2) { const float o = __shfl_xor(amin, 16); asm("v_min_f32 %0, %0, %1" : "+v"(amin) : "v"(o)); }  // the other chunk(s) of the state
       if (a.chunks >= 4) { const float o = __shfl_xor(amin, 32); asm("v_min_f32 %0, %0, %1" : "+v"(amin) : "v"(o)); }
-      const float limit = amin + __builtin_fmaf(lim1, bnorm[nb], lim0);
+      const float limit = amin + __builtin_fmaf(lim.y, dbnorm[nb], __builtin_fmaf(lim.x, bnorm[nb], lim.z));
       uint32_t mask = 0;
 #pragma unroll
       for (int j = kGroupBlocks - 1; j >= 1; j -= 2)  // densities in descending order, two blocks per asm statement

@@ -59,12 +59,19 @@ struct GmmPrefilterArgs {
   uint64_t n_frames;
   uint32_t dim;
   const unsigned char* apack;   // [n_groups][8 blocks][KS32][64 lanes][8 fp16], scaled by a power of two
-  const float* grp_anorm;       // [n_groups*4][2] largest (scaled) |a|_2 and |konst| over the densities of the state in that slot
+  const float* grp_lim;         // [n_groups*4][4] candidate limit of the state in that slot: 2 eps = [1] |b^ - b| + [0] |b| + [2]
+                                // (pf_bound, gmm_prefilter.hip header; [3] unused)
   const uint32_t* split_begin;  // [ny+1] group ranges
   uint32_t* mask;               // [group][frame][4 state slots] candidate densities of (frame, state)
   uint32_t nx, ny;
   uint32_t chunks;              // 1, 2 or 4 consecutive state slots (of 32 densities) make up one state
 };
+// Constants of the prefilter's error bound (derivation: gmm_prefilter.hip header), by k-steps of 32; the host folds them into grp_lim.
+struct PfBound { float kappa, acc, abs, sub; };
+constexpr float kPfRes16 = 4.8835e-4f;  // cap of |b^ - b| / |b|: one fp16 rounding of a normal fp32 x^2 or x
+inline constexpr PfBound pf_bound(int ks32) {
+  return ks32 == 4 ? PfBound{1.05e-3f, 1.6e-5f, 7.0e-7f, 3.38e-7f} : PfBound{1.05e-3f, 1.1e-5f, 6.0e-7f, 2.92e-7f};
+}
 struct GmmRefineArgs {
   // dim = the PADDED, odd dimension gmm_refine_padded_dim(model dimension): pair dimensions, zeros, the odd tail last (gmm_prefilter.hip)
   const float* feats;           // [n_frames x dim] row-major features in that order (batches of unrelated frames): the corpus' own

@@ -228,9 +228,13 @@ int pack_prefilter(sr_model* m, const uint32_t* dens_off, const double* means, c
   }
   const size_t blk_bytes = (size_t)KS * 1024;
   std::vector<uint16_t> ap((size_t)n_groups * 8 * blk_bytes / 2, 0);
-  std::vector<float> anorm(8 * (size_t)n_groups, 0.0f);  // (sA |a|, sA |konst|) per state slot
+  // per state slot: sA |a|, sA |konst|, sA |a^ - a|, sA |a^| (a^ = the fp16 coefficients packed below), each the largest over the
+  // slot's densities, rounded up -- the candidate limit of gmm_prefilter16_kernel
+  constexpr int kNF = 4;
+  std::vector<float> anorm(kNF * 4 * (size_t)n_groups, 0.0f);
   auto half_bits = [](double v) { const _Float16 h = (_Float16)(float)v; uint16_t u; memcpy(&u, &h, 2); return u; };
   auto half_value = [](uint16_t u) { _Float16 h; memcpy(&h, &u, 2); return (double)(float)h; };
+  auto up = [finf](double v) { return std::nextafter((float)(v * (1.0 + 1e-6)), finf); };
   srhost::parallel_ranges(n_groups, 16, [&](size_t q0, size_t q1) {
   std::vector<double> arow(32 * (size_t)KS);
   for (uint32_t q = (uint32_t)q0; q < (uint32_t)q1; q++) {
@@ -244,13 +248,18 @@ int pack_prefilter(sr_model* m, const uint32_t* dens_off, const double* means, c
         double konst = (double)finf;  // padding slot: never below a real score, masked off again by the refinement
         if (real) {
           konst = coeffs((size_t)dens_off[st] + 32u * (ps % Cs) + i, arow) * sA;
-          double n2 = 0.0;
-          for (uint32_t k = 0; k < 2 * D; k++) { arow[k] *= sA; n2 += arow[k] * arow[k]; }
-          const float na = std::nextafter((float)(std::sqrt(n2) * (1.0 + 1e-6)), finf);
-          const float nk = std::nextafter((float)(std::fabs(konst) * (1.0 + 1e-6)), finf);
+          double n2 = 0.0, d2 = 0.0, h2 = 0.0;
+          for (uint32_t k = 0; k < 2 * D; k++) {
+            arow[k] *= sA;
+            const double h = half_value(half_bits(arow[k]));  // exactly what the packing below writes
+            n2 += arow[k] * arow[k];
+            d2 += (h - arow[k]) * (h - arow[k]);
+            h2 += h * h;
+          }
+          const float f[kNF] = {up(std::sqrt(n2)), up(std::fabs(konst)), up(std::sqrt(d2)), up(std::sqrt(h2))};
           // NaN sticks: everything of that state then stays a candidate
-          if (!(na <= anorm[2 * (4 * q + g)])) anorm[2 * (4 * q + g)] = na;
-          if (!(nk <= anorm[2 * (4 * q + g) + 1])) anorm[2 * (4 * q + g) + 1] = nk;
+          for (int t = 0; t < kNF; t++)
+            if (!(f[t] <= anorm[kNF * (4 * q + g) + t])) anorm[kNF * (4 * q + g) + t] = f[t];
         }
         // konst = c1 + c2 + c3 (3 x 11 bits), multiplied by 1 in three spare k slots: exact products
         double rest = konst;
@@ -270,19 +279,38 @@ int pack_prefilter(sr_model* m, const uint32_t* dens_off, const double* means, c
     }
   }
   });
-  if (Cs > 1) {  // the candidate test of every chunk uses the whole state's largest |a| and |konst|
+  if (Cs > 1) {  // the candidate test of every chunk uses the whole state's largest norms
     for (uint32_t st = 0; st < S; st++)
-      for (int f = 0; f < 2; f++) {
+      for (int f = 0; f < kNF; f++) {
         float mxv = 0.0f;
         for (uint32_t ch = 0; ch < Cs; ch++) {
-          const float v = anorm[2 * (size_t)(st * Cs + ch) + f];
+          const float v = anorm[kNF * (size_t)(st * Cs + ch) + f];
           if (!(v <= mxv)) mxv = v;
         }
-        for (uint32_t ch = 0; ch < Cs; ch++) anorm[2 * (size_t)(st * Cs + ch) + f] = mxv;
+        for (uint32_t ch = 0; ch < Cs; ch++) anorm[kNF * (size_t)(st * Cs + ch) + f] = mxv;
       }
   }
   HIP_TRY(m->pf_apack.upload(reinterpret_cast<const unsigned char*>(ap.data()), ap.size() * 2));
-  HIP_TRY(m->pf_anorm.upload(anorm.data(), anorm.size()));
+  // -> the candidate limit per state slot, 2 eps = limD |b^ - b| + lim1 |b| + lim0 (gmm_prefilter.hip header).  lim0 and the
+  // norm-only lim1 are evaluated in float as the kernel did before; the residual form is taken only where its coefficients, rounded
+  // up, stay 2^-12 below the norm-only lim1 with |b^ - b| at its cap, and where kAbs |a| holds what the cap leaves out.  A NaN
+  // fails both tests and reaches the limit through lim0 and lim1: every density of that state stays a candidate.
+  {
+    const PfBound B = pf_bound(KS);
+    for (size_t slot = 0; slot < 4 * (size_t)n_groups; slot++) {
+      float* v = &anorm[kNF * slot];
+      const float na = v[0], nk = v[1], nd = v[2], nh = v[3];
+      const float lim0 = 2.0f * (B.acc * nk + B.abs * na), lim1_norm = 2.0f * (B.kappa * na + B.abs);
+      const float lim1_res = up(2.0 * ((double)nd + (double)B.acc * nh + (double)B.abs)), limd_res = up(2.0 * (1.0 + (double)B.acc) * nh);
+      const bool res = (double)limd_res * kPfRes16 + lim1_res <= lim1_norm * (1.0 - 0x1p-12) &&
+                       (1.0 + (double)B.acc) * (double)B.sub * nh <= (double)B.abs * na;
+      v[0] = res ? lim1_res : lim1_norm;
+      v[1] = res ? limd_res : 0.0f;
+      v[2] = lim0;
+      v[3] = 0.0f;
+    }
+  }
+  HIP_TRY(m->pf_lim.upload(anorm.data(), anorm.size()));
   m->pf_groups = n_groups;
   m->pf_ks32 = KS;
   m->pf_ny = 0;
@@ -440,7 +468,7 @@ int launch_scoring(sr_model* m, const float* d_feats, uint64_t n_frames, int gmm
     const uint64_t ldT = (n_frames + 63) & ~(uint64_t)63;
     GmmPrefilterArgs pa{};
     pa.feats = d_feats; pa.n_frames = n_frames; pa.dim = m->dim;
-    pa.apack = m->pf_apack.p; pa.grp_anorm = m->pf_anorm.p; pa.split_begin = m->pf_split_cur;
+    pa.apack = m->pf_apack.p; pa.grp_lim = m->pf_lim.p; pa.split_begin = m->pf_split_cur;
     pa.mask = m->pf_mask.p; pa.nx = nx; pa.ny = m->pf_ny; pa.chunks = std::min(4u, m->pf_chunks);
     GmmRefineArgs ra = refine_shape(m, n_frames);
     const bool padded = m->pf_dp != m->dim;
