@@ -263,17 +263,28 @@ typedef struct {
   float lm_pruning;         /* "lm-pruning" (:444-445) */
   int gmm_kernel;
   uint32_t max_word_ends;   /* traceback book capacity per frame and utterance; 0 = W (cannot overflow) */
-  int flags;                /* 0, or SR_BIGRAM_DENSE_STATES */
+  int flags;                /* 0, SR_BIGRAM_DENSE_STATES or SR_BIGRAM_GLOBAL_STATES (both: SR_EINVAL) */
 } sr_bigram_params;
-/* Lexica whose words all have at most four states (and at most 3072 words) keep the state hypotheses of a word in the registers
- * of one lane (viterbi_bigram.hip, KS > 0); this flag keeps them in the dense LDS image every other lexicon uses.  Same results;
- * for cross-checking the two. */
+/* Where the search keeps the state hypotheses (viterbi_bigram.hip); with flags = 0 the first that applies:
+ *   1 "registers": every word has at most four states, at most 3072 words, one-state silence -- a word's states in one lane's registers;
+ *   2 "lds":       the dense image of all positions (8 bytes each) beside the lists (~26 bytes per word) fits the 160 KiB LDS;
+ *   3 "global":    every other lexicon -- the image in device memory, only the positions of the active words visited per frame.
+ * SR_BIGRAM_DENSE_STATES forces layout 2 (SR_ELIMIT if the image does not fit), SR_BIGRAM_GLOBAL_STATES layout 3.  Same results;
+ * for cross-checking the layouts. */
 #define SR_BIGRAM_DENSE_STATES 1
+#define SR_BIGRAM_GLOBAL_STATES 2
+/* Limits: n_words <= 8192 (any lexicon within them is accepted); positions = the words' states plus n_words x the silence word's
+ * states (the silence copies) < 2^31. */
 SR_API int sr_bigram_create(sr_model* m, uint32_t n_words, const uint32_t* word_off, const uint16_t* mixtures,
                             uint32_t silence_word, const float* lm, const float tdp[8], sr_bigram** out);
 SR_API int sr_bigram_destroy(sr_bigram* b);
+/* The layout sr_recognize_bigram_corpus runs with flags = 0: "registers", "lds" or "global" (see above). */
+SR_API int sr_bigram_describe(const sr_bigram* b, char* out, size_t cap);
 /* out_word/out_score/out_time: capacity n_frames + n_utts (LinearSearch::getResult's traceback items, silence included);
- * out_off[n_utts+1]: items of utterance u are [out_off[u], out_off[u+1]).  SR_ELIMIT if a book overflowed. */
+ * out_off[n_utts+1]: items of utterance u are [out_off[u], out_off[u+1]).  SR_ELIMIT if a book overflowed.  The "global" layout
+ * takes a workspace of 16 bytes per position (+ 16 per word above 4 720 words) for each of at most 2 workgroups per CU, bounded by
+ * a quarter of the free device memory and independent of the corpus size (SR_EHIP if even one does not fit).  With the environment
+ * variable SRGPU_BIGRAM_STATS set, that layout reports the mean positions it visited per frame on stderr. */
 SR_API int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr_bigram_params* p,
                                       uint32_t* out_word, float* out_score, uint32_t* out_time, uint64_t* out_off);
 

@@ -20,6 +20,7 @@ POOL_GLOBAL, POOL_MIXTURE, POOL_NONE = 0, 1, 2
 SEARCH_GENERAL_KERNEL = 1
 SEARCH_SLOT_KERNEL = 2
 BIGRAM_DENSE_STATES = 1
+BIGRAM_GLOBAL_STATES = 2
 SR_ECORRUPT = -7
 SR_ABI_VERSION = 4
 
@@ -29,7 +30,7 @@ SYMBOLS = [
     "sr_last_error", "sr_device_count", "sr_model_create", "sr_model_load_mixset", "sr_model_destroy", "sr_model_info",
     "sr_corpus_upload", "sr_corpus_upload_async", "sr_corpus_wait", "sr_corpus_destroy", "sr_shard_utterances", "sr_recognize_batch_multi", "sr_score_corpus", "sr_score_frames", "sr_lexicon_create",
     "sr_lexicon_destroy", "sr_lexicon_describe", "sr_recognize_corpus", "sr_traceback_corpus", "sr_traceback_words", "sr_recognize_batch", "sr_align_corpus", "sr_align_corpus_pruned", "sr_path_scores_corpus", "sr_model_create_from_statistics", "sr_model_create_from_accumulated", "sr_mixset_write", "sr_model_set_tying", "sr_model_tying_info", "sr_model_topology", "sr_accumulate_corpus",
-    "sr_bigram_create", "sr_bigram_destroy", "sr_recognize_bigram_corpus",
+    "sr_bigram_create", "sr_bigram_destroy", "sr_bigram_describe", "sr_recognize_bigram_corpus",
     "sr_probe_fp16_denormals", "sr_probe_fp16_accumulation",
     "sr_profile_enable", "sr_profile_reset", "sr_profile_read",
 ]
@@ -103,6 +104,7 @@ def lib():
         L.sr_accumulate_corpus.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
         L.sr_bigram_create.argtypes = [vp, u32, vp, vp, u32, vp, vp, C.POINTER(vp)]
         L.sr_bigram_destroy.argtypes = [vp]
+        L.sr_bigram_describe.argtypes = [vp, C.c_char_p, C.c_size_t]
         L.sr_recognize_bigram_corpus.argtypes = [vp, vp, vp, C.POINTER(BigramParams), vp, vp, vp, vp]
         L.sr_probe_fp16_denormals.argtypes = [i32, C.POINTER(i32)]
         L.sr_probe_fp16_accumulation.argtypes = [i32, C.POINTER(i32), C.POINTER(dbl)]
@@ -244,6 +246,12 @@ class Bigram:
         self.h = C.c_void_p()
         _check(lib().sr_bigram_create(model.h, W, _ptr(word_off), _ptr(mixtures), silence_word, _ptr(lm), _ptr(tdp), C.byref(self.h)))
 
+    def describe(self):
+        """Where the search keeps the state hypotheses with no flags: "registers", "lds" or "global" (sr_bigram_describe)."""
+        buf = C.create_string_buffer(32)
+        _check(lib().sr_bigram_describe(self.h, buf, len(buf)))
+        return buf.value.decode()
+
     def close(self):
         if self.h:
             lib().sr_bigram_destroy(self.h)
@@ -348,12 +356,14 @@ class Corpus:
                                           _ptr(va), _ptr(vw)))
         return ma, mw, va, vw
 
-    def recognize_bigram(self, bigram, acoustic_pruning=FLT_MAX, lm_pruning=FLT_MAX, kernel=GMM_PREFILTER, max_word_ends=0, dense_states=False):
-        """-> (words u32[], scores f32[], times u32[], off u64[n_utts+1]): LinearSearch::getResult per utterance"""
+    def recognize_bigram(self, bigram, acoustic_pruning=FLT_MAX, lm_pruning=FLT_MAX, kernel=GMM_PREFILTER, max_word_ends=0, dense_states=False,
+                         global_states=False):
+        """-> (words u32[], scores f32[], times u32[], off u64[n_utts+1]): LinearSearch::getResult per utterance.
+        dense_states / global_states force the dense LDS image / the state hypotheses in device memory (both: SrError)."""
         cap = max(self.n_frames + self.n_utts, 1)
         ow, osc, ot = np.zeros(cap, np.uint32), np.zeros(cap, np.float32), np.zeros(cap, np.uint32)
         off = np.zeros(self.n_utts + 1, np.uint64)
-        p = BigramParams(acoustic_pruning, lm_pruning, kernel, max_word_ends, BIGRAM_DENSE_STATES if dense_states else 0)
+        p = BigramParams(acoustic_pruning, lm_pruning, kernel, max_word_ends, (BIGRAM_DENSE_STATES if dense_states else 0) | (BIGRAM_GLOBAL_STATES if global_states else 0))
         _check(lib().sr_recognize_bigram_corpus(self.model.h, self.h, bigram.h, C.byref(p), _ptr(ow), _ptr(osc), _ptr(ot), _ptr(off)))
         n = int(off[-1])
         return ow[:n], osc[:n], ot[:n], off

@@ -195,6 +195,8 @@ struct sr_bigram {
   DevBuf<float> we_score, out_score;
   DevBuf<uint4> book;
   DevBuf<uint64_t> book_off;
+  DevBuf<uint32_t> gs_ws;               // global-states layout: the persistent workgroups' state images (viterbi_bigram.hip)
+  DevBuf<unsigned long long> gs_active; // ... and the SRGPU_BIGRAM_STATS counter
 };
 
 namespace srhost {

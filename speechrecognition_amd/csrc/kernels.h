@@ -239,7 +239,16 @@ struct BigramArgs {
   uint32_t silence_states;      // states of the silence word (= of every silence copy)
   uint32_t dense_states;        // keep the state hypotheses in the dense LDS image even where the register layout applies
   uint32_t row4_mask;           // register layout: bit k = slot row k (words k * 1024 ...) holds a word of four states (the other rows keep three)
+  uint32_t global_states;       // keep the state hypotheses in device memory (bigram_gs_kernel) even where another layout applies
+  uint32_t gs_grid;             // global states: workgroups of the persistent grid (each decodes every gs_grid-th utterance)
+  uint32_t* gs_ws;              // global states: [gs_grid][gs_ws_words] workspace, the state image of every workgroup
+  uint64_t gs_ws_words;         //   >= bigram_gs_ws_words(n_words, n_positions)
+  unsigned long long* gs_active;  // global states, optional: += the positions step 3 visits, every frame
 };
+enum class BigramLayout { kRegisters, kLds, kGlobal, kNone };  // kNone: dense_states asked for an image the LDS cannot hold
+BigramLayout bigram_layout(const BigramArgs& a);  // what launch_bigram runs (register layout, dense LDS image, global states)
+uint64_t bigram_gs_ws_words(uint32_t n_words, uint32_t n_positions);  // global-states workspace per workgroup, 32-bit words
+uint32_t bigram_max_positions();
 hipError_t launch_bigram(const BigramArgs& a, hipStream_t stream);
 size_t bigram_lds_bytes(uint32_t n_words, uint32_t n_positions);
 bool bigram_register_layout(const BigramArgs& a);   // short words, <= 3072 of them, the emission row fits the LDS beside the lists

@@ -1299,6 +1299,9 @@ int sr_bigram_create(sr_model* m, uint32_t n_words, const uint32_t* word_off, co
   }
   // slots: words 0..W-1, then the silence copy of every word (Teaching::LinearSearch: silenceCopy :202-205)
   const uint32_t n_sil = word_off[silence_word + 1] - word_off[silence_word];
+  if ((uint64_t)word_off[W] + (uint64_t)W * n_sil > bigram_max_positions())
+    return fail(SR_ELIMIT, "%llu positions (words and their silence copies): the bigram search handles at most %u",
+                (unsigned long long)word_off[W] + (unsigned long long)W * n_sil, bigram_max_positions());
   std::vector<uint32_t> slot_off(2 * (size_t)W + 1, 0), slot_mix(2 * (size_t)W);
   for (uint32_t a = 0; a < 2 * W; a++) {
     const uint32_t aw = a < W ? a : silence_word;
@@ -1317,13 +1320,8 @@ int sr_bigram_create(sr_model* m, uint32_t n_words, const uint32_t* word_off, co
       pos_slot[slot_off[a] + k] = a;
     }
   }
-  {  // the dense LDS image, or -- short words -- the register layout, which needs less (viterbi_bigram.hip)
-    BigramArgs probe{};
-    probe.n_words = W; probe.ld = m->ld; probe.silence_states = n_sil;
-    for (uint32_t a2 = 0; a2 < 2 * W; a2++) probe.max_slot_states = std::max(probe.max_slot_states, slot_off[a2 + 1] - slot_off[a2]);
-    if (bigram_lds_bytes(W, P2) > 160 * 1024 && !bigram_register_layout(probe))
-      return fail(SR_ELIMIT, "lexicon too large for the bigram search's LDS image (%zu bytes > 160 KiB)", bigram_lds_bytes(W, P2));
-  }
+  // (every lexicon within these limits has a layout: the register layout, the dense LDS image, or the state hypotheses in device
+  // memory -- bigram_layout, viterbi_bigram.hip)
   std::vector<float> lmT((size_t)W * W);
   for (uint32_t w = 0; w < W; w++)
     for (uint32_t h = 0; h < W; h++) lmT[(size_t)h * W + w] = lm[(size_t)w * W + h];
@@ -1361,7 +1359,7 @@ int sr_bigram_destroy(sr_bigram* b) {
   if (!b) return SR_OK;
   if (b->model) { (void)hipSetDevice(b->model->device); (void)hipDeviceSynchronize(); }
   b->slot_off.release(); b->slot_mix.release(); b->mixtures.release(); b->pos_info.release(); b->pos_slot.release(); b->lmT.release(); b->lm_rowmin.release(); b->lm_rowmax.release();
-  b->we_slot.release(); b->we_bp.release(); b->we_score.release(); b->book.release(); b->book_off.release();
+  b->we_slot.release(); b->we_bp.release(); b->we_score.release(); b->book.release(); b->book_off.release(); b->gs_ws.release(); b->gs_active.release();
   b->out_word.release(); b->out_time.release(); b->out_score.release(); b->out_count.release(); b->out_flags.release();
   delete b;
   return SR_OK;
@@ -1402,11 +1400,37 @@ int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr
   ba.slot_off = b->slot_off.p; ba.slot_mix = b->slot_mix.p; ba.mixtures = b->mixtures.p; ba.pos_info = b->pos_info.p; ba.pos_slot = b->pos_slot.p; ba.lmT = b->lmT.p; ba.lm_rowmin = b->lm_rowmin.p; ba.lm_rowmax = b->lm_rowmax.p;
   memcpy(ba.tdp, b->tdp, sizeof(ba.tdp));
   ba.ac_pruning = p->acoustic_pruning; ba.lm_pruning = p->lm_pruning;
-  if (p->flags & ~SR_BIGRAM_DENSE_STATES) return fail(SR_EINVAL, "unknown sr_bigram_params.flags 0x%x", (unsigned)p->flags);
+  if (p->flags & ~(SR_BIGRAM_DENSE_STATES | SR_BIGRAM_GLOBAL_STATES)) return fail(SR_EINVAL, "unknown sr_bigram_params.flags 0x%x", (unsigned)p->flags);
+  if ((p->flags & SR_BIGRAM_DENSE_STATES) && (p->flags & SR_BIGRAM_GLOBAL_STATES))
+    return fail(SR_EINVAL, "SR_BIGRAM_DENSE_STATES and SR_BIGRAM_GLOBAL_STATES exclude each other");
   ba.max_slot_states = b->max_slot_states; ba.silence_states = b->silence_states; ba.row4_mask = b->row4_mask;
   ba.dense_states = (p->flags & SR_BIGRAM_DENSE_STATES) ? 1u : 0u;
-  if (!bigram_register_layout(ba) && bigram_lds_bytes(W, b->n_positions) > 160 * 1024)
-    return fail(SR_ELIMIT, "this lexicon runs in the register layout only (its dense LDS image would take %zu bytes > 160 KiB)", bigram_lds_bytes(W, b->n_positions));
+  ba.global_states = (p->flags & SR_BIGRAM_GLOBAL_STATES) ? 1u : 0u;
+  const BigramLayout layout = bigram_layout(ba);
+  if (layout == BigramLayout::kNone)
+    return fail(SR_ELIMIT, "this lexicon's dense LDS image would take %zu bytes > 160 KiB (SR_BIGRAM_DENSE_STATES)", bigram_lds_bytes(W, b->n_positions));
+  if (layout == BigramLayout::kGlobal) {
+    // a bounded, persistent grid (two workgroups per CU at most, each looping over its utterances): the state images take
+    // grid x gs_ws_words x 4 bytes whatever the corpus size -- and at most a quarter of the free device memory
+    int dev_cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, m->device));
+    const uint64_t per_wg = bigram_gs_ws_words(W, b->n_positions);
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    const uint64_t have = b->gs_ws.n / per_wg;  // (workgroups the workspace of an earlier call holds)
+    const uint64_t cap = std::max<uint64_t>(have, (free_b / 4) / (per_wg * 4));
+    const uint64_t grid = std::min<uint64_t>({(uint64_t)std::max(dev_cus, 1) * 2, (uint64_t)std::max(max_chunk_utts, 1u), cap});
+    if (grid == 0) return fail(SR_ENOMEM, "bigram search: %llu bytes of device memory for one state image, %zu free",
+                                (unsigned long long)(per_wg * 4), free_b);
+    HIP_TRY(b->gs_ws.ensure(grid * per_wg));
+    ba.gs_grid = (uint32_t)grid; ba.gs_ws = b->gs_ws.p; ba.gs_ws_words = per_wg;
+    if (getenv("SRGPU_BIGRAM_STATS")) {
+      HIP_TRY(b->gs_active.ensure(1));
+      HIP_TRY(hipMemset(b->gs_active.p, 0, sizeof(unsigned long long)));
+      HIP_TRY(hipDeviceSynchronize());
+      ba.gs_active = b->gs_active.p;
+    }
+  }
   ba.we_slot = b->we_slot.p; ba.we_bp = b->we_bp.p; ba.we_score = b->we_score.p;
   ba.book = b->book.p; ba.book_off = b->book_off.p;
   ba.out_word = b->out_word.p; ba.out_score = b->out_score.p; ba.out_time = b->out_time.p;
@@ -1415,7 +1439,7 @@ int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr
   rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); },
       [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
         ba.scores = table; ba.frame_base = ch.f0; ba.utt_first = ch.u0; ba.n_utts = ch.u1 - ch.u0;
-        HIP_TRY(launch_bigram(ba, s));
+        HIP_TRY(launch_bigram(ba, s));  // (invalid value: a layout without the workspace it needs -- a bug here, not the caller's)
         // SURVEY 8(d)'s decoder model, 8 S + 4 P bytes per frame, with P = the bigram search's positions (words + their silence copies)
         if (m->profiling) m->prof.search_bytes += (8.0 * m->n_states + 4.0 * b->n_positions) * (double)(ch.f1 - ch.f0);
         return SR_OK;
@@ -1440,7 +1464,25 @@ int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr
     for (uint32_t i = 0; i < counts[u]; i++, n++) { out_word[n] = dw[o + i]; out_score[n] = ds[o + i]; out_time[n] = dt[o + i]; }
     out_off[u + 1] = n;
   }
+  if (ba.gs_active) {  // diagnostic (tools/cliffs.py): positions the global-states search visited per frame
+    unsigned long long visited = 0;
+    HIP_TRY(hipMemcpy(&visited, ba.gs_active, sizeof visited, hipMemcpyDeviceToHost));
+    fprintf(stderr, "srgpu bigram: global states, %llu frames, %.1f active positions per frame\n", (unsigned long long)F,
+            F ? (double)visited / (double)F : 0.0);
+  }
   if (m->profiling) m->prof.frames += F;
+  return SR_OK;
+  });
+}
+
+int sr_bigram_describe(const sr_bigram* b, char* out, size_t cap) {
+  return guarded(__func__, [&]() -> int {
+  if (!b || !out || cap == 0) return fail(SR_EINVAL, "null argument");
+  BigramArgs ba{};
+  ba.n_words = b->n_words; ba.n_positions = b->n_positions; ba.ld = b->model ? b->model->ld : 0;
+  ba.max_slot_states = b->max_slot_states; ba.silence_states = b->silence_states;
+  const BigramLayout layout = bigram_layout(ba);
+  snprintf(out, cap, "%s", layout == BigramLayout::kRegisters ? "registers" : layout == BigramLayout::kLds ? "lds" : "global");
   return SR_OK;
   });
 }

@@ -43,6 +43,14 @@ __host__ __device__ constexpr size_t bigram_lds_small(uint32_t n_words) {
   return 2 * (size_t)n_words * 8 + (3 * kBgStage + kBgWaves + 1 + kBgWaves) * 4 + 2 * (size_t)n_words * 2 * 2 + 2 * (size_t)n_words + 64;
 }
 
+// global states: offset of step 3's prefix sums [2W] behind the small image (without the entries where they live in device memory)
+__host__ __device__ constexpr size_t bigram_gs_pre_off(uint32_t n_words, bool entries_global) {
+  return (bigram_lds_small(n_words) - (entries_global ? 2 * (size_t)n_words * 8 : 0) + 15u) & ~(size_t)15u;
+}
+__host__ __device__ constexpr size_t bigram_gs_lds(uint32_t n_words, bool entries_global) {
+  return bigram_gs_pre_off(n_words, entries_global) + 2 * (size_t)n_words * 4;
+}
+
 // register layout: offset of the emission row behind the small image and the LM row bounds
 __host__ __device__ constexpr size_t bigram_lds_row_off(uint32_t n_words) {
   return (((bigram_lds_small(n_words) + 15u) & ~(size_t)15u) + 2 * (size_t)n_words * 4 + 1023u) & ~(size_t)1023u;
@@ -111,7 +119,36 @@ __device__ inline float wg_min(float v, float* tmp) {
   return r;
 }
 
-// Two layouts of the state hypotheses (steps 3 and 4):
+// One position's new hypothesis in the dense and the global-states layouts (expandHypotheses, LinearSearch.cc:270-339), before its
+// emission cost: fl = the position's flags (pos_info >> 16), sl = its slot, j = its index; c_* = the entry and the OLD scores at
+// j - 2, j - 1, j (read unconditionally -- those that do not apply are ignored here).  Candidates in the order the reference
+// creates them (ascending predecessor state, entry first); >= lets the later one win.  *src = where the winner's back pointer lives:
+// 0xFFFFFFFF none, 0x80000000 | slot = the entry, else a position (hence positions < 2^31).
+// The silence word of SEVERAL states lands in these layouts (bigram_register_layout requires one): inside silence and its copies all
+// three silence penalties apply, tdp[isSilence][s' - s] (LinearSearch.cc:296-326).  Only the register layout may treat forward and
+// skip as the words' scalars.
+__device__ __forceinline__ float bigram_position(const BigramArgs& a, uint32_t fl, uint32_t sl, uint32_t j, bool in, float c_ent, float c_o3,
+                                                 float c_o2, float c_o1, uint32_t* src_out) {
+  const bool sil_ = (fl >> 3) & 1u;
+  const float t0 = sil_ ? a.tdp[1][0] : a.tdp[0][0], t1 = sil_ ? a.tdp[1][1] : a.tdp[0][1], t2 = sil_ ? a.tdp[1][2] : a.tdp[0][2];
+  const float inf = __builtin_inff();
+  // states 1 and 2 are reachable from the virtual entry state 0: free to state 1, skip penalty to state 2
+  const float ent = (in && (fl & 3u)) ? c_ent : inf;
+  const float o3 = (in && !(fl & 3u)) ? c_o3 : inf;  // s >= 3: skip from s - 2
+  const float o2 = (in && !(fl & 1u)) ? c_o2 : inf;  // s >= 2: forward from s - 1
+  const float o1 = in ? c_o1 : inf;                  // loop
+  float best = inf;
+  uint32_t src = 0xFFFFFFFFu;
+  if (ent < inf) { best = (fl & 1u) ? ent : ent + t2; src = 0x80000000u | sl; }
+  { const float c = o3 + t2; if (o3 < inf && !(best < c)) { best = c; src = j - 2; } }
+  { const float c = o2 + t1; if (o2 < inf && !(best < c)) { best = c; src = j - 1; } }
+  { const float c = o1 + t0; if (o1 < inf && !(best < c)) { best = c; src = j; } }
+  *src_out = src;
+  return best;
+}
+
+// Three layouts of the state hypotheses (steps 3 and 4):
+//   GSM > 0  in DEVICE MEMORY (bigram_gs_kernel below): every lexicon whose image does not fit the LDS;
 //   KS == 0  dense in LDS, one thread per POSITION (KP positions per thread): any lexicon whose image fits the LDS;
 //   KS >  0  in REGISTERS, one lane per SLOT: lane tid owns the words tid + k * 1024 (k < KS = KW, at most NP states each) and their
 //            silence copies (one state: the layout asks for a one-state silence) -- lexica of short words (every BASELINE
@@ -123,18 +160,38 @@ __device__ inline float wg_min(float v, float* tmp) {
 // NPM (register layout): 0 = every word has at most three states; else bit k = slot row k (the words k * 1024 .. k * 1024 + 1023) holds a
 // word of four states -- only those rows carry the fourth state's registers and arithmetic (round 4; configs[4]'s lexicon has ONE
 // four-state word, in row 2: rows 0 and 1 are three-state rows).
-template <int KW, int KP, int KS, int NPM>  // KW words per thread in the recombination: W <= KW * kBgThreads
-__global__ __launch_bounds__(kBgThreads) void bigram_kernel(BigramArgs a) {
-  constexpr bool REGS = KS > 0;
+// GSM (global states, bigram_gs_kernel): 0 = the register or the dense LDS layout; 1 = the state hypotheses in device memory, the entry
+// hypotheses in LDS; 2 = the entries in device memory too (the lexica whose entries, lists and flags alone crowd the LDS).
+// One utterance `ui` of the launch, on workgroup `wg` (its slice of the per-workgroup workspaces).
+template <int KW, int KP, int KS, int NPM, int GSM>  // KW words per thread in the recombination: W <= KW * kBgThreads
+__device__ __forceinline__ void bigram_utterance(const BigramArgs& a, uint32_t ui, uint32_t wg) {
+  constexpr bool REGS = KS > 0, GS = GSM > 0, ENG = GSM == 2;
+  static_assert(!(REGS && GS), "the global-states layout keeps one hypothesis per position");
   constexpr int NP = NPM ? 4 : 3;  // states a lane keeps per word at most
   auto np_of = [](int k) constexpr { return ((NPM >> k) & 1) ? 4 : 3; };  // ... and in slot row k
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t W = a.n_words, W2 = 2 * a.n_words, P2 = REGS ? 0u : a.n_positions, sil = a.silence;
+  const uint32_t P2L = GS ? 0u : P2;                          // positions imaged in LDS
   float* st_score = reinterpret_cast<float*>(smem);           // [P2]   (dense layout only)
-  uint32_t* st_bp = reinterpret_cast<uint32_t*>(st_score + P2);  // [P2]
-  float* en_score = reinterpret_cast<float*>(st_bp + P2);     // [2W] entry (start) hypotheses; scratch in step 5
-  uint32_t* en_bp = reinterpret_cast<uint32_t*>(en_score + W2);  // [2W]
-  uint32_t* stage = en_bp + W2;                               // [3 * kBgStage]
+  uint32_t* st_bp = reinterpret_cast<uint32_t*>(st_score + P2L);  // [P2]
+  // global states: workgroup wg's image, two buffers (old / new) of the scores and of the back pointers of all P2 positions, then
+  // (GSM 2) the entries; gs_cur = the buffer that holds the current hypotheses
+  uint32_t* gs_ws = GS ? a.gs_ws + (uint64_t)wg * a.gs_ws_words : nullptr;
+  float* gs_score[2] = {reinterpret_cast<float*>(gs_ws), reinterpret_cast<float*>(gs_ws) + P2};
+  uint32_t* gs_bp[2] = {gs_ws + 2ull * P2, gs_ws + 3ull * P2};
+  int gs_cur = 0;
+  float* en_score;                                            // [2W] entry (start) hypotheses; scratch in step 5
+  uint32_t* en_bp;                                            // [2W]
+  uint32_t* stage;                                            // [3 * kBgStage]
+  if constexpr (ENG) {
+    en_score = reinterpret_cast<float*>(gs_ws + 4ull * P2);
+    en_bp = gs_ws + 4ull * P2 + W2;
+    stage = reinterpret_cast<uint32_t*>(smem);
+  } else {
+    en_score = reinterpret_cast<float*>(st_bp + P2L);
+    en_bp = reinterpret_cast<uint32_t*>(en_score + W2);
+    stage = en_bp + W2;
+  }
   uint32_t* scan_tmp = stage + 3 * kBgStage;                  // [kBgWaves + 1]
   float* red_tmp = reinterpret_cast<float*>(scan_tmp + kBgWaves + 1);  // [kBgWaves]
   uint16_t* L[2];
@@ -151,18 +208,19 @@ __global__ __launch_bounds__(kBgThreads) void bigram_kernel(BigramArgs a) {
   uint16_t* pm_slot = lm_hi_lds + W;  // [2W]
   uint32_t* n_pairs = reinterpret_cast<uint32_t*>(active + ((W2 + 3u) & ~3u));  // histories whose word AND silence copy end this frame
   unsigned char* row_lds = smem + bigram_lds_row_off(a.n_words);
+  uint32_t* gs_pre = reinterpret_cast<uint32_t*>(smem + bigram_gs_pre_off(a.n_words, ENG));  // [2W] global states: step 3's prefix sums
   auto rowmin = [&](uint32_t h) -> float { if constexpr (REGS) return __uint_as_float((uint32_t)lm_lo_lds[h] << 16); else return a.lm_rowmin[h]; };
   auto rowmax = [&](uint32_t h) -> float { if constexpr (REGS) return __uint_as_float((uint32_t)lm_hi_lds[h] << 16); else return a.lm_rowmax[h]; };
   float* fin_score = en_score;                                // [2W] final-state score / back pointer of the slots whose word end survived
   uint32_t* fin_bp = en_bp;                                   //      (written in step 4, read by its compaction; the entries are consumed by then)
 
-  const uint32_t u = a.utt_order ? a.utt_order[a.utt_first + blockIdx.x] : a.utt_first + blockIdx.x, tid = threadIdx.x;
+  const uint32_t u = a.utt_order ? a.utt_order[a.utt_first + ui] : a.utt_first + ui, tid = threadIdx.x;
   const uint64_t f0 = a.frame_off[u], T = a.frame_off[u + 1] - f0;
   const double* dense = a.scores + (f0 - a.frame_base) * a.ld;
   // per-utterance global workspaces
   uint32_t* we_slot[2]; float* we_score[2]; uint32_t* we_bp[2];
   for (int i = 0; i < 2; i++) {
-    const uint64_t o = ((uint64_t)blockIdx.x * 2 + i) * W2;
+    const uint64_t o = ((uint64_t)wg * 2 + i) * W2;
     we_slot[i] = a.we_slot + o; we_score[i] = a.we_score + o; we_bp[i] = a.we_bp + o;
   }
   uint4* book = a.book + a.book_off[u];  // (word, score bits, backpointer, time)
@@ -174,7 +232,7 @@ __global__ __launch_bounds__(kBgThreads) void bigram_kernel(BigramArgs a) {
   auto ac_word = [&](uint32_t w) { return w < W ? w : sil; };
   auto is_sil = [&](uint32_t w) { return (w == sil || w >= W) ? 1 : 0; };
 
-  for (uint32_t i = tid; i < P2; i += kBgThreads) { st_score[i] = __builtin_inff(); st_bp[i] = 0; }
+  for (uint32_t i = tid; i < P2L; i += kBgThreads) { st_score[i] = __builtin_inff(); st_bp[i] = 0; }
   for (uint32_t i = tid; i < W2; i += kBgThreads) active[i] = 0;
   // register layout: word w = tid + k * 1024 (slot w) and its silence copy (slot W + w): state count, silence flag, row offsets of the
   // states, hypotheses
@@ -241,6 +299,8 @@ __global__ __launch_bounds__(kBgThreads) void bigram_kernel(BigramArgs a) {
   __syncthreads();
   bool overflow = false;
   const __amdgpu_buffer_rsrc_t info_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(a.pos_info), 0, (int)(P2 * 4u), 0x00020000);
+  const __amdgpu_buffer_rsrc_t lm_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.lmT), 0, (int)(W * W * 4u), 0x00020000);
+  const __amdgpu_buffer_rsrc_t en_rsrc = __builtin_amdgcn_make_buffer_rsrc(en_score, 0, (int)(W2 * 8u), 0x00020000);  // (GSM 2)
   const __amdgpu_buffer_rsrc_t slot_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(a.pos_slot), 0, (int)(P2 * 4u), 0x00020000);
   // The merged word-end list of the previous frame, the thread's own entries [tid * ce, (tid + 1) * ce): in the register layout step 6
   // hands them over in these registers (round 4: the thread that writes an entry is the thread that reads it next frame -- step 6 used
@@ -329,17 +389,26 @@ __global__ __launch_bounds__(kBgThreads) void bigram_kernel(BigramArgs a) {
       const uint32_t ne = (ne_all - r0 < stg_cap) ? ne_all - r0 : stg_cap;
       // eight word ends at a time (two in the register layout, whose state hypotheses stay live across this loop): their LM rows
       // are loaded first (independent loads in flight together), then compared in list order
-      constexpr int KE = REGS ? 2 : 8;
+      // (global states: four, two, one as the lexicon grows -- the image pointers take the registers a bigger batch would)
+      constexpr int KE = REGS ? 2 : GS ? (KW <= 1 ? 4 : KW <= 4 ? 2 : 1) : 8;
       for (uint32_t e = 0; e < ne; e += KE) {
         float v[KE][KW];
 #pragma unroll
         for (int j = 0; j < KE; j++) {
           const uint32_t ej = (e + j < ne) ? e + j : e;
+          if constexpr (GS) {  // (buffer loads: one VGPR offset, the row and k * 4096 bytes scalar -- KW hoisted addresses spill at KW = 8;
+                               // a word w >= W reads the next row or 0, and is not used)
+            const uint32_t rb = stg[3 * ej] * W * 4u;
+#pragma unroll
+            for (int k = 0; k < KW; k++)
+              v[j][k] = __uint_as_float((uint32_t)__builtin_amdgcn_raw_buffer_load_b32(lm_rsrc, tid * 4u, rb + (uint32_t)k * (kBgThreads * 4u), 0));
+          } else {
           const float* row = a.lmT + (uint64_t)stg[3 * ej] * W;
 #pragma unroll
           for (int k = 0; k < KW; k++) {
             const uint32_t w = tid + k * kBgThreads;
             v[j][k] = row[w < W ? w : 0];
+          }
           }
         }
 #pragma unroll
@@ -363,8 +432,13 @@ __global__ __launch_bounds__(kBgThreads) void bigram_kernel(BigramArgs a) {
     for (int k = 0; k < KW; k++) {
       const uint32_t w = tid + k * kBgThreads;
       if (w < W && w != sil) {
-        en_score[w] = my_score[k];
-        en_bp[w] = my_bp[k];
+        if constexpr (ENG) {  // (scalar offsets, as the LM rows above)
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(my_score[k]), en_rsrc, tid * 4u, (uint32_t)k * (kBgThreads * 4u), 0);
+          __builtin_amdgcn_raw_buffer_store_b32((int)my_bp[k], en_rsrc, tid * 4u, W2 * 4u + (uint32_t)k * (kBgThreads * 4u), 0);
+        } else {
+          en_score[w] = my_score[k];
+          en_bp[w] = my_bp[k];
+        }
         lmin = fmin_raw(lmin, my_score[k]);
       }
     }
@@ -435,6 +509,7 @@ __global__ __launch_bounds__(kBgThreads) void bigram_kernel(BigramArgs a) {
     // needs the OLD states s-2, s-1, s: all reads, a barrier, then the writes.  Candidates in the order the reference creates
     // them (ascending predecessor state, entry first); >= lets the later one win.
     float lbest = kFltMax;
+    uint32_t gs_n_act = 0;  // global states: positions of the slots on L
     constexpr int KPD = REGS ? 1 : KP;
     float nsc[KPD];
     uint32_t nbp[KPD];
@@ -492,6 +567,43 @@ __global__ __launch_bounds__(kBgThreads) void bigram_kernel(BigramArgs a) {
         rc_sc[k] = best;
         rc_bp[k] = best < inf ? bb : 0u;
       }
+    } else if constexpr (GS) {
+    // ---- global states: the positions of the slots on L only, one thread per position of the flattened list ---------------------
+    // A slot that is not on L holds +inf at every position in BOTH buffers (a slot leaves L in step 4 only when all of its positions
+    // failed the beam, which set them to +inf in the new buffer; the compaction clears the old one) and has no entry hypothesis
+    // (step 2 activates every finite entry), so the dense update would leave it at +inf: skipping it computes the same values.
+    // The old hypotheses are read from buffer gs_cur, the new ones written to the other: no barrier between the reads and writes.
+    const uint32_t cl3 = (n_L + kBgThreads - 1) / kBgThreads;
+    const uint32_t l_lo = tid * cl3 < n_L ? tid * cl3 : n_L, l_hi = (l_lo + cl3 < n_L) ? l_lo + cl3 : n_L;
+    uint32_t n_mine = 0;
+    for (uint32_t i = l_lo; i < l_hi; i++) { const uint32_t sl = L[lcur][i]; n_mine += a.slot_off[sl + 1] - a.slot_off[sl]; }
+    uint32_t& n_act = gs_n_act;
+    uint32_t base = wg_excl_scan(n_mine, scan_tmp, &n_act);
+    for (uint32_t i = l_lo; i < l_hi; i++) { const uint32_t sl = L[lcur][i]; gs_pre[i] = base; base += a.slot_off[sl + 1] - a.slot_off[sl]; }
+    if (a.gs_active && tid == 0) atomicAdd(a.gs_active, (unsigned long long)n_act);
+    __syncthreads();
+    const double* row = dense + (t - 1) * a.ld;
+    const float* o_sc = gs_score[gs_cur];
+    const uint32_t* o_bp = gs_bp[gs_cur];
+    float* n_sc = gs_score[gs_cur ^ 1];
+    uint32_t* n_bp = gs_bp[gs_cur ^ 1];
+    for (uint32_t f = tid; f < n_act; f += kBgThreads) {
+      uint32_t lo = 0, hi = n_L;  // the last list entry whose prefix is <= f: gs_pre[lo] <= f < gs_pre[hi] (gs_pre[n_L] = n_act)
+      while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (gs_pre[mid] <= f) lo = mid; else hi = mid; }
+      const uint32_t sl = L[lcur][lo], j = a.slot_off[sl] + (f - gs_pre[lo]);
+      const uint32_t info = a.pos_info[j], fl = info >> 16;
+      const float pem = (float)row[info & 0xFFFFu];
+      const float c_ent = en_score[sl], c_o3 = o_sc[(fl & 3u) ? j : j - 2], c_o2 = o_sc[(fl & 1u) ? j : j - 1], c_o1 = o_sc[j];
+      uint32_t src;
+      float best = bigram_position(a, fl, sl, j, true, c_ent, c_o3, c_o2, c_o1, &src);
+      if (best < __builtin_inff()) {
+        best += pem;
+        lbest = fmin_raw(lbest, best);
+      }
+      n_sc[j] = best;
+      n_bp[j] = src == 0xFFFFFFFFu ? 0u : (src & 0x80000000u) ? en_bp[sl] : o_bp[src];
+    }
+    for (uint32_t i = tid; i < W2; i += kBgThreads) active[i] &= 1u;  // bit 0 = on the active list; bits 1, 2 = this frame's survivors
     } else {
     const double* row = dense + (t - 1) * a.ld;
     // kCh positions at a time: emission state | flags, slot (frame-invariant, but held in registers across the frame loop they
@@ -537,24 +649,10 @@ __global__ __launch_bounds__(kBgThreads) void bigram_kernel(BigramArgs a) {
         const int q = q0 + r, k = k0 + q;
         const uint32_t j = tid + (uint32_t)k * kBgThreads;
         const uint32_t fl = pinfo[q] >> 16, sl = pslot[q];
-        const bool sil_ = (fl >> 3) & 1u, in = j < P2;
-        // the dense layout is where a silence word of SEVERAL states lands (bigram_register_layout requires one): inside silence
-        // and its copies all three silence penalties apply, tdp[isSilence][s' - s] (LinearSearch.cc:296-326).  Only the register
-        // layout above may treat forward and skip as the words' scalars.
-        const float t0 = sil_ ? a.tdp[1][0] : a.tdp[0][0], t1 = sil_ ? a.tdp[1][1] : a.tdp[0][1], t2 = sil_ ? a.tdp[1][2] : a.tdp[0][2];
-        const float inf = __builtin_inff();
-        // states 1 and 2 are reachable from the virtual entry state 0: free to state 1, skip penalty to state 2
-        const float ent = (in && (fl & 3u)) ? c_ent[r] : inf;
-        const float o3 = (in && !(fl & 3u)) ? c_o3[r] : inf;  // s >= 3: skip from s - 2
-        const float o2 = (in && !(fl & 1u)) ? c_o2[r] : inf;  // s >= 2: forward from s - 1
-        const float o1 = in ? c_o1[r] : inf;                  // loop
-        float best = inf;
-        uint32_t src = 0xFFFFFFFFu;
-        if (ent < inf) { best = (fl & 1u) ? ent : ent + t2; src = 0x80000000u | sl; }
-        { const float c = o3 + t2; if (o3 < inf && !(best < c)) { best = c; src = j - 2; } }
-        { const float c = o2 + t1; if (o2 < inf && !(best < c)) { best = c; src = j - 1; } }
-        { const float c = o1 + t0; if (o1 < inf && !(best < c)) { best = c; src = j; } }
-        if (best < inf) {
+        const bool in = j < P2;
+        uint32_t src;
+        float best = bigram_position(a, fl, sl, j, in, c_ent[r], c_o3[r], c_o2[r], c_o1[r], &src);
+        if (best < __builtin_inff()) {
           best += pem[q];
           lbest = fmin_raw(lbest, best);
         }
@@ -619,6 +717,21 @@ __global__ __launch_bounds__(kBgThreads) void bigram_kernel(BigramArgs a) {
           if ((flags & 4u) && cflags) atomicAdd(n_pairs, 1u);  // both word ends of this history survive: the merge keeps one entry for them
         }
       }
+    } else if constexpr (GS) {
+      uint32_t* active_w = reinterpret_cast<uint32_t*>(active);
+      float* n_sc = gs_score[gs_cur ^ 1];
+      for (uint32_t f = tid; f < gs_n_act; f += kBgThreads) {  // (the positions this thread wrote in step 3)
+        uint32_t lo = 0, hi = n_L;
+        while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (gs_pre[mid] <= f) lo = mid; else hi = mid; }
+        const uint32_t sl = L[lcur][lo], j = a.slot_off[sl] + (f - gs_pre[lo]);
+        const float v = n_sc[j];
+        if (v < __builtin_inff()) {
+          const uint32_t fl = a.pos_info[j] >> 16;
+          const float tv = v + exit_pen[(fl >> 3) & 1];
+          if (tv < ac_thr) atomicOr(&active_w[sl >> 2], ((fl & 4u) ? 6u : 2u) << (8u * (sl & 3u)));  // alive; its final state too
+          else n_sc[j] = __builtin_inff();
+        }
+      }
     } else {
       uint32_t* active_w = reinterpret_cast<uint32_t*>(active);  // (byte flags, OR-ed through their 32-bit word)
 #pragma unroll
@@ -651,7 +764,13 @@ __global__ __launch_bounds__(kBgThreads) void bigram_kernel(BigramArgs a) {
     for (uint32_t i = i_lo; i < i_hi; i++) {
       const uint32_t sl = L[lcur][i];
       const uint32_t fa = active[sl];
-      if (!(fa & 2u)) { active[sl] = 0; continue; }
+      if (!(fa & 2u)) {
+        active[sl] = 0;
+        if constexpr (GS) {  // leaves the list: the new buffer is +inf there already (step 4), the old one is cleared
+          for (uint32_t q = a.slot_off[sl]; q < a.slot_off[sl + 1]; q++) gs_score[gs_cur][q] = __builtin_inff();
+        }
+        continue;
+      }
       active[sl] = 1;
       L[lcur ^ 1][pa++] = (uint16_t)sl;
       if (fa & 4u) {  // the final state survived: a word end, carrying the exit-penalised score
@@ -660,13 +779,14 @@ __global__ __launch_bounds__(kBgThreads) void bigram_kernel(BigramArgs a) {
         } else {
           const uint32_t last = a.slot_off[sl + 1] - 1;
           we_slot[nxt][pe] = sl;
-          we_score[nxt][pe] = st_score[last] + exit_pen[is_sil(sl)];
-          we_bp[nxt][pe] = st_bp[last];
+          we_score[nxt][pe] = (GS ? gs_score[gs_cur ^ 1][last] : st_score[last]) + exit_pen[is_sil(sl)];
+          we_bp[nxt][pe] = GS ? gs_bp[gs_cur ^ 1][last] : st_bp[last];
         }
         pe++;
       }
     }
     lcur ^= 1;
+    gs_cur ^= 1;
     n_L = tot_alive;
     __syncthreads();  // the word-end list in global memory is complete (same workgroup: visible after the barrier)
 
@@ -796,6 +916,31 @@ __global__ __launch_bounds__(kBgThreads) void bigram_kernel(BigramArgs a) {
     }
     a.out_count[u] = n_out;
   }
+  if constexpr (GS) {  // leave the image as it was found, +inf everywhere: clear the slots still on the list in both buffers
+    for (uint32_t i = tid; i < n_L; i += kBgThreads) {
+      const uint32_t sl = L[lcur][i];
+      for (uint32_t q = a.slot_off[sl]; q < a.slot_off[sl + 1]; q++) { gs_score[0][q] = __builtin_inff(); gs_score[1][q] = __builtin_inff(); }
+    }
+  }
+}
+
+template <int KW, int KP, int KS, int NPM>
+__global__ __launch_bounds__(kBgThreads) void bigram_kernel(BigramArgs a) {
+  bigram_utterance<KW, KP, KS, NPM, 0>(a, blockIdx.x, blockIdx.x);
+}
+
+// The global-states layout (lexica whose dense image does not fit the LDS): a bounded, persistent grid -- every workgroup decodes the
+// utterances blockIdx.x, blockIdx.x + gridDim.x, ... of the launch in its own slice of the workspace, so that the workspace does not
+// grow with the corpus.  The image is set to +inf once; every utterance leaves it so.
+template <int KW, int GSM>
+__global__ __launch_bounds__(kBgThreads) void bigram_gs_kernel(BigramArgs a) {
+  uint32_t* img = a.gs_ws + (uint64_t)blockIdx.x * a.gs_ws_words;
+  for (uint64_t i = threadIdx.x; i < 2ull * a.n_positions; i += kBgThreads) img[i] = 0x7F800000u;  // the two score buffers
+  __syncthreads();
+  for (uint32_t ui = blockIdx.x; ui < a.n_utts; ui += gridDim.x) {
+    bigram_utterance<KW, 4, 0, 0, GSM>(a, ui, blockIdx.x);
+    __syncthreads();  // (the next utterance re-initialises the LDS lists and flags)
+  }
 }
 
 size_t bigram_lds_bytes(uint32_t n_words, uint32_t n_positions) { return (size_t)n_positions * 8 + bigram_lds_small(n_words); }
@@ -803,12 +948,47 @@ uint32_t bigram_max_words() { return 8 * kBgThreads; }
 
 static size_t bigram_lds_regs(uint32_t n_words, uint32_t ld) { return bigram_lds_row_off(n_words) + (((size_t)ld * 8 + 1023u) & ~(size_t)1023u); }
 bool bigram_register_layout(const BigramArgs& a) {
-  return !a.dense_states && a.max_slot_states <= 4 && a.silence_states == 1 && a.n_words <= 3 * kBgThreads && bigram_lds_regs(a.n_words, a.ld) <= 160 * 1024;
+  return !a.dense_states && !a.global_states && a.max_slot_states <= 4 && a.silence_states == 1 && a.n_words <= 3 * kBgThreads && bigram_lds_regs(a.n_words, a.ld) <= 160 * 1024;
+}
+
+static bool bigram_gs_entries_global(uint32_t n_words) { return bigram_gs_lds(n_words, false) > 160 * 1024; }
+uint64_t bigram_gs_ws_words(uint32_t n_words, uint32_t n_positions) {
+  return 4ull * n_positions + (bigram_gs_entries_global(n_words) ? 4ull * n_words : 0ull);
+}
+uint32_t bigram_max_positions() { return 0x7FFFFFFFu; }  // a position index must stay clear of the entry tag 0x80000000 (bigram_position)
+
+BigramLayout bigram_layout(const BigramArgs& a) {
+  if (a.global_states) return BigramLayout::kGlobal;
+  if (bigram_register_layout(a)) return BigramLayout::kRegisters;
+  if (bigram_lds_bytes(a.n_words, a.n_positions) <= 160 * 1024) return BigramLayout::kLds;
+  return a.dense_states ? BigramLayout::kNone : BigramLayout::kGlobal;
+}
+
+static hipError_t launch_bigram_gs(const BigramArgs& a, hipStream_t stream) {
+  const bool eng = bigram_gs_entries_global(a.n_words);
+  const size_t smem = bigram_gs_lds(a.n_words, eng);
+  const uint32_t grid = a.gs_grid < a.n_utts ? a.gs_grid : a.n_utts;
+  if (grid == 0 || !a.gs_ws || a.gs_ws_words < bigram_gs_ws_words(a.n_words, a.n_positions)) return hipErrorInvalidValue;
+  auto go = [&](auto kernel) {
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBgThreads), smem, stream, a);
+    return hipGetLastError();
+  };
+  const uint32_t kw = (a.n_words + kBgThreads - 1) / kBgThreads;
+  if (kw <= 1) return go(bigram_gs_kernel<1, 1>);
+  if (kw <= 2) return go(bigram_gs_kernel<2, 1>);
+  if (kw <= 4) return go(bigram_gs_kernel<4, 1>);
+  if (!eng) return go(bigram_gs_kernel<8, 1>);
+  return go(bigram_gs_kernel<8, 2>);
 }
 
 hipError_t launch_bigram(const BigramArgs& a, hipStream_t stream) {
   if (a.n_utts == 0) return hipSuccess;
-  const bool regs = bigram_register_layout(a);
+  const BigramLayout layout = bigram_layout(a);
+  if (layout == BigramLayout::kNone) return hipErrorInvalidValue;
+  if (layout == BigramLayout::kGlobal) return launch_bigram_gs(a, stream);
+  const bool regs = layout == BigramLayout::kRegisters;
   const size_t smem = regs ? bigram_lds_regs(a.n_words, a.ld) : (bigram_lds_bytes(a.n_words, a.n_positions) + 15) & ~(size_t)15;
   auto go = [&](auto kernel) {
     hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);

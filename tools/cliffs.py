@@ -6,9 +6,13 @@ HIP events (sr_profile_*), per launch, median of `--reps` passes, and the cost p
   dim 13 / 26 / 33 / 39 / 40 / 45 / 50 / 62 at 32 densities per mixture   (the refinement's padded dimensions; K = 128 from dim 47)
   160 densities per mixture at dim 39                                     (> 128: beyond the fp16 pass' four chunks)
   the zerogram search on the headline lexicon with negative emission costs (variances x 0.004: entry-slot costs below zero)
-usage (GPU box): python tools/cliffs.py [--frames-scale 1.0] [--reps 3] [--only dims|m160|neg] > gpurun_out/r5_cliffs.txt"""
+  the bigram search beyond the LDS (--only bigram): ms per 100 000 frames of the search kernel at W = 700 words of 18-24 positions
+    on the dense LDS image and on the forced global-states layout (the price of the new layout), and global states at W = 2 000,
+    6 500, 8 192 -- each line with the mean positions the global-states kernel visits per frame (its cost follows that number)
+usage (GPU host): python tools/cliffs.py [--reps 3] [--only dims|m160|neg|bigram] > cliffs.txt"""
 import argparse
 import os
+import re
 import sys
 import tempfile
 import time
@@ -40,6 +44,66 @@ def time_scoring(mp, D, feats, off, reps, kernel=capi.GMM_PREFILTER):
     return tuple(float(np.median([r[i] for r in rows])) for i in range(5))
 
 
+def bigram_lines(tmp, reps, frames=100_000):
+    """The bigram search on lexica beyond the register layout: model of 1 000 states x 4 densities (dim 39) shared by the words,
+    LM scores Exp(mean 4) (the LM beam of 6 lets ~78 % of the words in), acoustic beam 120; utterances of ~330 frames sampled along
+    the lexicon."""
+    S, D, M, acp, lmp = 1000, 39, 4, 120.0, 6.0
+    spec = synth.make_mixset(S, M, D, seed=61)
+    mp = os.path.join(tmp, "bigram.mix")
+    synth.write_mixset(mp, spec)
+    print(f"# bigram search: {frames} frames, S = {S} x {M} densities, acoustic beam {acp}, LM beam {lmp}; search kernel ms per 100 000 frames "
+          f"(sr_profile_*, median of {reps}); 'active' = mean positions per frame the global-states kernel visits")
+    for W, lens, layouts in ((700, (18, 24), ("lds", "global")), (2000, (18, 24), ("global",)), (6500, (2, 2), ("global",)),
+                             (8192, (3, 3), ("global",))):
+        rng = np.random.default_rng(W)
+        off_w, aut = [0, 1], [0]
+        for n in rng.integers(lens[0], lens[1] + 1, size=W - 1):
+            aut.extend(int(x) for x in rng.integers(1, S, size=int(n)))
+            off_w.append(len(aut))
+        lex = synth.ExplicitLexicon(np.asarray(off_w, np.uint32), np.asarray(aut, np.uint16), 0)
+        lm = rng.exponential(4.0, size=(W, W)).astype(np.float32)
+        tdp = np.array([[3.0, 0.0, 30.0, 5.0], [1.0, 0.0, 40.0, 2.0]], np.float32)
+        utts, n = [], 0
+        while n < frames:
+            x = synth.sample_utterance(spec, lex, rng.integers(1, W, size=int(np.ceil(330 / (2 * np.mean(lens))))), seed=n, frames_per_state=(1, 3))
+            x = x[: min(len(x), frames - n)]
+            utts.append(x)
+            n += len(x)
+        off = np.concatenate([[0], np.cumsum([len(x) for x in utts])]).astype(np.uint64)
+        with capi.Model.from_mixset(mp, D) as m:
+            bg = m.bigram(lex.word_off, lex.automaton, 0, lm, tdp)
+            corpus = m.upload(np.concatenate(utts), off)
+            for layout in layouts:
+                forced = layout == "global" and bg.describe() != "global"
+                corpus.recognize_bigram(bg, acp, lmp, global_states=forced)  # warm-up: workspaces
+                ts = []
+                for _ in range(reps):
+                    m.profile(True)
+                    w, _, _, woff = corpus.recognize_bigram(bg, acp, lmp, global_states=forced)
+                    ts.append(m.profile_read()["search_ms"])
+                    m.profile(False)
+                active = ""
+                if layout == "global":  # one more pass with the library's counter on (SRGPU_BIGRAM_STATS: a line on stderr)
+                    log = os.path.join(tmp, "stats.txt")
+                    fd, keep = os.open(log, os.O_WRONLY | os.O_CREAT | os.O_TRUNC), os.dup(2)
+                    os.dup2(fd, 2)
+                    os.environ["SRGPU_BIGRAM_STATS"] = "1"
+                    try:
+                        corpus.recognize_bigram(bg, acp, lmp, global_states=forced)
+                    finally:
+                        del os.environ["SRGPU_BIGRAM_STATS"]
+                        os.dup2(keep, 2)
+                        os.close(fd); os.close(keep)
+                    mm = re.search(r"([0-9.]+) active positions per frame", open(log).read())
+                    active = f"active {float(mm.group(1)):9.1f}" if mm else "active ?"
+                P2 = int(lex.word_off[-1]) + W
+                tag = f"bigram W {W}, {lens[0]}-{lens[1]} pos, {layout}{' (forced)' if forced else ''}"
+                print(f"  {tag:42s} {np.median(ts) * 1e5 / n:9.2f} ms/100k frames  positions {P2:7d}  {active}  words {int(woff[-1])}", flush=True)
+            corpus.close()
+            bg.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -48,6 +112,9 @@ def main():
     ap.add_argument("--dims", default="13,26,33,40,45,50,62")
     args = ap.parse_args()
     tmp = tempfile.mkdtemp(prefix="cliffs_")
+    if args.only == "bigram":
+        bigram_lines(tmp, args.reps)
+        return
     S = 4000
     print(f"# cliff ledger: S = {S}, {args.utts} utterances U{{200..400}} frames, median of {args.reps} passes; kernel times from sr_profile_* (HIP events)")
     print(f"# {'model':34s} {'P ms':>8s} {'R ms':>8s} {'GMM ms':>8s} {'eval/pair':>9s} {'ps per dens*dim':>16s} {'vs headline':>11s}")
