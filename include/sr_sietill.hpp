@@ -10,6 +10,7 @@
 //   sr::MixtureModel           MixtureModel (as scorer)     sietill/Mixtures.hpp:18-92
 //   sr::Corpus                 Corpus (feature store)       sietill/Corpus.hpp:55-84
 //   sr::Recognizer             Recognizer                   sietill/Recognizer.hpp:91-132
+//   sr::StreamingRecognizer    Recognizer fed frame by frame (sr_stream_*; the shape of RWTH ASR's OfflineRecognizer::processFeature)
 //   sr::Aligner                Aligner                      sietill/Alignment.hpp:19-63
 //   sr::FeaturePostProcessor   SignalAnalysis::process_features  sietill/SignalAnalysis.cpp:320-336,340-349,379-399
 //   sr::read_feature_file, write_alignment, read_alignment    sietill/IO.cpp:48-69, Alignment.cpp:303-318
@@ -385,6 +386,77 @@ class Recognizer {
   StateIdx silence_state_ = 0;
   sr_lexicon* net_ = nullptr;
   std::vector<Replica> replicas_;
+};
+
+// ---- streaming: recognizeSequence_pruned while the frames of several utterances are still arriving (sr_stream_*, srgpu.h) --------
+// begin() opens an utterance; push() hands over new frames of one or several open utterances (one scoring and one search launch
+// per call); partial() is what recognizeSequence_pruned returns for the frames pushed so far; end() returns its result on the
+// whole utterance and frees the id.  Errors are thrown as std::runtime_error with sr_last_error()'s text.
+class StreamingRecognizer {
+ public:
+  StreamingRecognizer(Lexicon const& lexicon, MixtureModel& scorer, TdpModel const& tdp_model, double am_threshold = 20.0,
+                      double word_penalty = 10.0, uint32_t max_streams = 64, uint64_t max_frames = 65535)
+      : max_frames_(max_frames) {
+    std::vector<uint32_t> word_off(1, 0);
+    std::vector<uint16_t> automaton;
+    for (WordIdx w = 0; w < lexicon.num_words(); w++) {
+      auto const& a = lexicon.get_automaton_for_word(w);
+      automaton.insert(automaton.end(), a.states.begin(), a.states.end());
+      word_off.push_back((uint32_t)automaton.size());
+    }
+    const double tdp[3] = {tdp_model.tdp_loop, tdp_model.tdp_forward, tdp_model.tdp_skip};
+    check(sr_lexicon_create(scorer.handle(), (uint32_t)lexicon.num_words(), word_off.data(), automaton.data(),
+                            (uint32_t)lexicon.silence_idx(), tdp, tdp_model.silence_state, &net_));
+    sr_search_params p = sr_search_params();  // zeroed, then field by field
+    p.am_threshold = am_threshold;
+    p.word_penalty = word_penalty;
+    p.gmm_kernel = scorer.gmm_kernel;
+    const int rc = sr_stream_open(scorer.handle(), net_, &p, max_streams, max_frames, &s_);
+    if (rc != SR_OK) {
+      const std::string msg = sr_last_error();
+      sr_lexicon_destroy(net_);
+      throw std::runtime_error(msg);
+    }
+  }
+  ~StreamingRecognizer() {
+    sr_stream_destroy(s_);  // before its lexicon
+    sr_lexicon_destroy(net_);
+  }
+  StreamingRecognizer(StreamingRecognizer const&) = delete;
+  StreamingRecognizer& operator=(StreamingRecognizer const&) = delete;
+
+  uint32_t begin() {
+    uint32_t id = 0;
+    check(sr_stream_begin(s_, &id));
+    return id;
+  }
+  // n_frames new frames ([n_frames x dimension] float32) of one utterance
+  void push(uint32_t id, const float* frames, size_t n_frames) {
+    const uint64_t off[2] = {0, n_frames};
+    check(sr_stream_push(s_, 1, &id, frames, off));
+  }
+  // new frames of several utterances back to back: ids[i] owns rows [frame_off[i], frame_off[i+1])
+  void push(std::vector<uint32_t> const& ids, const float* frames, std::vector<uint64_t> const& frame_off) {
+    if (frame_off.size() != ids.size() + 1) throw std::runtime_error("StreamingRecognizer::push: frame_off needs ids.size() + 1 entries");
+    check(sr_stream_push(s_, (uint32_t)ids.size(), ids.data(), frames, frame_off.data()));
+  }
+  std::vector<WordIdx> partial(uint32_t id) {
+    std::vector<uint32_t> w(max_frames_);
+    uint32_t n = 0;
+    check(sr_stream_partial(s_, id, w.data(), (uint32_t)w.size(), &n, nullptr));
+    return std::vector<WordIdx>(w.begin(), w.begin() + n);
+  }
+  std::vector<WordIdx> end(uint32_t id) {
+    std::vector<uint32_t> w(max_frames_);
+    uint32_t n = 0;
+    check(sr_stream_end(s_, id, w.data(), (uint32_t)w.size(), &n, nullptr, nullptr, nullptr));
+    return std::vector<WordIdx>(w.begin(), w.begin() + n);
+  }
+
+ private:
+  const uint64_t max_frames_;
+  sr_lexicon* net_ = nullptr;
+  sr_stream* s_ = nullptr;
 };
 
 // ---- Alignment.hpp:19-63 -------------------------------------------------------------------------------------

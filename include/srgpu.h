@@ -192,6 +192,45 @@ SR_API int sr_traceback_words(uint32_t n_frames, const uint16_t* tb_word, const 
 SR_API int sr_recognize_batch(sr_model* m, sr_lexicon* l, const sr_search_params* p, const float* feats,
                        const uint64_t* frame_off, uint32_t n_utts, uint32_t* out_words, uint64_t* out_word_off);
 
+/* ---- streaming recognition: Recognizer::recognizeSequence_pruned (Recognizer.cpp:103-232) fed frame by frame -------------
+ * The frame-at-a-time shape of Mm::FeatureScorer::addFeature / OfflineRecognizer::processFeature (RWTH ASR): an utterance is
+ * begun, its frames are pushed as they arrive, the best words so far can be read after any push, and ending it returns exactly
+ * what sr_recognize_corpus returns for the whole utterance (same gmm_kernel): words and traceback, bit for bit.  After t frames
+ * the partial result is what sr_recognize_corpus returns for the first t frames as a complete utterance (the reference's
+ * traceback[1..t] does not depend on later frames); a later frame can still change which words the final result holds.
+ *
+ * sr_stream_open     a set of up to max_streams concurrently open utterances of up to max_frames frames (<= 65535, the 16-bit
+ *                    back pointers) on (m, l).  p->flags must be 0; p->gmm_kernel as for sr_recognize_corpus.  Device memory:
+ *                    max_streams x (20 P + 12 (max_frames + 1) + 4 max_frames + 40) bytes (P = the lexicon's positions; 20 P
+ *                    rounded up to 256), plus staging for the largest push: 4 dim + 8 n_states bytes per frame and the scoring
+ *                    kernel's own workspaces.  The search always keeps its hypotheses in device memory (decode_stream_kernel).
+ * sr_stream_begin    a fresh utterance (the initial hypothesis of Recognizer.cpp:116-120); *id names it until sr_stream_end.  Ids
+ *                    are not reused soon after their utterance ended: an ended id is refused, not confused with a newer one.
+ * sr_stream_push     n utterances, ids[n], each at most once; their new frames back to back in feats ([frames x dim] float32),
+ *                    utterance i owning rows [frame_off[i], frame_off[i+1]) (frame_off[0] == 0; an empty range is allowed).
+ *                    Every frame of the push is scored in one launch, then one search launch advances every utterance; returns
+ *                    when both have finished.  Everything is checked before anything is launched: a refused push changes no
+ *                    utterance.
+ * sr_stream_partial  the words after the frames pushed so far (*frames); cap = capacity of out_words (may be NULL if cap is 0).
+ * sr_stream_end      the final words and, optionally (each may be NULL), the utterance's T + 1 traceback entries in
+ *                    sr_recognize_corpus' per-utterance layout (words, not slots); frees the id (also on SR_ECORRUPT).  An
+ *                    utterance ended after 0 frames reports what sr_recognize_corpus reports for an empty utterance: no words,
+ *                    traceback[0] = (0.0, 0, 0).
+ * sr_stream_destroy  before its lexicon and its model.
+ * Errors: SR_EINVAL for an unknown or ended id, an id repeated within one push, max_streams == 0, max_frames == 0, p->flags != 0, a
+ * malformed frame_off, and a cap below the word count (*count then holds the count needed; the id stays open); SR_ELIMIT for a
+ * push that would take an utterance past max_frames, sr_stream_begin with every id in use, max_frames > 65535 and a lexicon of
+ * more than 65534 positions; SR_ECORRUPT as for sr_recognize_corpus.  Threading: like the model, one host thread at a time. */
+typedef struct sr_stream sr_stream;   /* a set of concurrently open utterances on one (model, lexicon) */
+SR_API int sr_stream_open(sr_model* m, sr_lexicon* l, const sr_search_params* p, uint32_t max_streams, uint64_t max_frames,
+                          sr_stream** out);
+SR_API int sr_stream_begin(sr_stream* s, uint32_t* id);
+SR_API int sr_stream_push(sr_stream* s, uint32_t n, const uint32_t* ids, const float* feats, const uint64_t* frame_off);
+SR_API int sr_stream_partial(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_t cap, uint32_t* count, uint64_t* frames);
+SR_API int sr_stream_end(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_t cap, uint32_t* count, double* tb_score,
+                         uint16_t* tb_word, uint16_t* tb_bkp);
+SR_API int sr_stream_destroy(sr_stream* s);
+
 /* ---- several devices: the `#pragma omp parallel for` over segments of Recognizer::recognize (Recognizer.cpp:46-47) -------
  * Utterances are independent, so a batch shards across devices with no collective: sr_shard_utterances deals them by
  * greedy longest-processing-time on frame counts (decreasing length, each to the lightest shard so far; deterministic);

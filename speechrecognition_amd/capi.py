@@ -31,6 +31,7 @@ SYMBOLS = [
     "sr_corpus_upload", "sr_corpus_upload_async", "sr_corpus_wait", "sr_corpus_destroy", "sr_shard_utterances", "sr_recognize_batch_multi", "sr_score_corpus", "sr_score_frames", "sr_lexicon_create",
     "sr_lexicon_destroy", "sr_lexicon_describe", "sr_recognize_corpus", "sr_traceback_corpus", "sr_traceback_words", "sr_recognize_batch", "sr_align_corpus", "sr_align_corpus_pruned", "sr_path_scores_corpus", "sr_model_create_from_statistics", "sr_model_create_from_accumulated", "sr_mixset_write", "sr_model_set_tying", "sr_model_tying_info", "sr_model_topology", "sr_accumulate_corpus",
     "sr_bigram_create", "sr_bigram_destroy", "sr_bigram_describe", "sr_recognize_bigram_corpus",
+    "sr_stream_open", "sr_stream_begin", "sr_stream_push", "sr_stream_partial", "sr_stream_end", "sr_stream_destroy",
     "sr_probe_fp16_denormals", "sr_probe_fp16_accumulation",
     "sr_profile_enable", "sr_profile_reset", "sr_profile_read",
 ]
@@ -106,6 +107,12 @@ def lib():
         L.sr_bigram_destroy.argtypes = [vp]
         L.sr_bigram_describe.argtypes = [vp, C.c_char_p, C.c_size_t]
         L.sr_recognize_bigram_corpus.argtypes = [vp, vp, vp, C.POINTER(BigramParams), vp, vp, vp, vp]
+        L.sr_stream_open.argtypes = [vp, vp, C.POINTER(SearchParams), u32, u64, C.POINTER(vp)]
+        L.sr_stream_begin.argtypes = [vp, C.POINTER(u32)]
+        L.sr_stream_push.argtypes = [vp, u32, vp, vp, vp]
+        L.sr_stream_partial.argtypes = [vp, u32, vp, u32, C.POINTER(u32), C.POINTER(u64)]
+        L.sr_stream_end.argtypes = [vp, u32, vp, u32, C.POINTER(u32), vp, vp, vp]
+        L.sr_stream_destroy.argtypes = [vp]
         L.sr_probe_fp16_denormals.argtypes = [i32, C.POINTER(i32)]
         L.sr_probe_fp16_accumulation.argtypes = [i32, C.POINTER(i32), C.POINTER(dbl)]
         L.sr_profile_enable.argtypes = [vp, i32]
@@ -217,6 +224,10 @@ class Model:
     def bigram(self, word_off, mixtures, silence_word, lm, tdp):
         return Bigram(self, word_off, mixtures, silence_word, lm, tdp)
 
+    def stream(self, lexicon, am_threshold, word_penalty, kernel=GMM_PREFILTER, max_streams=1, max_frames=65535):
+        """sr_stream_open: a set of up to max_streams concurrently open utterances of up to max_frames frames each."""
+        return Stream(self, lexicon, am_threshold, word_penalty, kernel, max_streams, max_frames)
+
     # -- profiling ---------------------------------------------------------------------------------
     def profile(self, on=True):
         _check(lib().sr_profile_enable(self.h, int(on)))
@@ -256,6 +267,69 @@ class Bigram:
         if self.h:
             lib().sr_bigram_destroy(self.h)
             self.h = None
+
+
+class Stream:
+    """sr_stream handle: utterances fed frame by frame (sr_stream_*).  end() returns what Corpus.recognize returns for the whole
+    utterance; partial() after t frames what it returns for the first t frames."""
+
+    def __init__(self, model, lexicon, am_threshold, word_penalty, kernel, max_streams, max_frames):
+        self.model = model
+        self.max_frames = int(max_frames)
+        self.frames = {}  # frames pushed per open id
+        self.h = C.c_void_p()
+        sp = SearchParams(am_threshold, word_penalty, kernel, 0)
+        _check(lib().sr_stream_open(model.h, lexicon.h, C.byref(sp), max_streams, max_frames, C.byref(self.h)))
+
+    def begin(self):
+        """-> the id of a fresh utterance"""
+        i = C.c_uint32()
+        _check(lib().sr_stream_begin(self.h, C.byref(i)))
+        self.frames[i.value] = 0
+        return i.value
+
+    def push(self, frames):
+        """frames: {id: float32 [k x dim]} -> one scoring and one search launch for all of them"""
+        ids = np.ascontiguousarray(list(frames.keys()), dtype=np.uint32)
+        parts = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1, self.model.dim) for f in frames.values()]
+        off = np.concatenate([[0], np.cumsum([len(f) for f in parts])]).astype(np.uint64)
+        feats = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, self.model.dim), np.float32))
+        _check(lib().sr_stream_push(self.h, len(ids), _ptr(ids), _ptr(feats) if len(feats) else None, _ptr(off)))
+        for i, f in zip(ids, parts):
+            self.frames[int(i)] += len(f)
+
+    def partial(self, id, frames=False):
+        """-> the words so far (u32[]) [, frames pushed]"""
+        out = np.zeros(self.max_frames, np.uint32)
+        n, t = C.c_uint32(), C.c_uint64()
+        _check(lib().sr_stream_partial(self.h, id, _ptr(out), len(out), C.byref(n), C.byref(t)))
+        return (out[: n.value].copy(), t.value) if frames else out[: n.value].copy()
+
+    def end(self, id, traceback=False):
+        """-> final words (u32[]) [, (tb_score, tb_word, tb_bkp) of T + 1 entries]; frees the id"""
+        out = np.zeros(self.max_frames, np.uint32)
+        n = C.c_uint32()
+        tbs = tbw = tbb = None
+        if traceback:
+            m = self.max_frames + 1
+            tbs, tbw, tbb = np.zeros(m, np.float64), np.zeros(m, np.uint16), np.zeros(m, np.uint16)
+        _check(lib().sr_stream_end(self.h, id, _ptr(out), len(out), C.byref(n), _ptr(tbs), _ptr(tbw), _ptr(tbb)))
+        T = self.frames.pop(id)
+        words = out[: n.value].copy()
+        if not traceback:
+            return words
+        return words, (tbs[: T + 1], tbw[: T + 1], tbb[: T + 1])
+
+    def close(self):
+        if self.h:
+            lib().sr_stream_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class Corpus:

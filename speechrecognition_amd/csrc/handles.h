@@ -199,6 +199,30 @@ struct sr_bigram {
   DevBuf<unsigned long long> gs_active; // ... and the SRGPU_BIGRAM_STATS counter
 };
 
+// A set of concurrently open utterances on one (model, lexicon) (sr_stream_*, srgpu_api.cpp).  Slot i holds one open utterance;
+// its device state (decode_stream_kernel) lives in the per-slot buffers below, its frame count on the host.
+struct sr_stream {
+  sr_model* model = nullptr;
+  sr_lexicon* lex = nullptr;
+  sr_search_params params{};
+  uint32_t max_streams = 0;
+  uint64_t max_frames = 0;
+  std::vector<uint8_t> open;        // [max_streams]
+  std::vector<uint32_t> id;         // [max_streams] id of the slot's current (or last) utterance: slot + max_streams * generation
+  std::vector<uint32_t> generation; // [max_streams] of the next utterance begun in the slot
+  std::vector<uint64_t> frames;     // [max_streams] frames pushed so far
+  // per slot, device
+  DevBuf<unsigned char> ws;         // decode_big_workspace(P) each
+  DevBuf<srgpu::StreamState> state;
+  DevBuf<double> tb_score;          // max_frames + 1 each
+  DevBuf<uint16_t> tb_word, tb_bkp;
+  DevBuf<uint32_t> words;           // max_frames each
+  // per push, sized by the largest push so far
+  DevBuf<float> feats;
+  DevBuf<double> scores;
+  DevBuf<srgpu::StreamJob> jobs;
+};
+
 namespace srhost {
 // (srgpu_api.cpp) handle without parameter tables / lazily fetched host copies of them
 int model_shell(int device, uint32_t dim, uint32_t n_states, const uint32_t* dens_off, int max_approx, sr_model** out);

@@ -183,6 +183,39 @@ uint32_t decode_max_slots();          // what the LDS-resident kernels hold
 uint32_t decode_big_max_slots();
 size_t decode_big_workspace(uint32_t n_slots);
 hipError_t launch_decode_big(const DecodeArgs& a, unsigned char* ws, hipStream_t stream);
+// streaming (sr_stream_push): decode_stream_kernel advances each of n open utterances by k frames from the state the last push
+// left in device memory.  Per stream slot: decode_big_workspace(P) bytes of hypotheses, a StreamState, max_frames + 1 traceback
+// entries (words, not slots) and max_frames words of partial result.
+struct StreamState {
+  double m_we;            // word-end minimum of the last frame searched (+inf: none survived)
+  uint32_t e_first[4];    // first word-end slot attaining it per boundary class, for the next frame
+  uint32_t flags;         // kFlagSlowPath | kFlagCorrupt (traceback.h), the latter for the last walk
+  uint32_t count;         // words of the partial result, at words + slot * words_stride
+  uint32_t pad[2];
+};
+struct StreamJob {        // one workgroup of a push
+  uint32_t slot;          // stream slot
+  uint32_t t0, k;         // frames searched before this push, frames in it
+  uint32_t pad;
+  uint64_t row0;          // its first frame's row in the push's score table
+};
+struct StreamArgs {
+  DecodeNet net;
+  double am_threshold, word_penalty;
+  const double* scores;   // [push frames x ld]
+  uint32_t ld;
+  const StreamJob* jobs;  // [workgroups]
+  unsigned char* ws;      // [slots x ws_stride]
+  size_t ws_stride;
+  StreamState* state;     // [slots]
+  double* tb_score;       // [slots x tb_stride], entry t = traceback[t]
+  uint16_t* tb_word;
+  uint16_t* tb_bkp;
+  uint64_t tb_stride;     // max_frames + 1
+  uint32_t* words;        // [slots x words_stride]
+  uint64_t words_stride;  // max_frames
+};
+hipError_t launch_decode_stream(const StreamArgs& a, uint32_t n_jobs, hipStream_t stream);
 // the traceback walk alone (traceback.h) on arrays in the traceback layout above; out_flags[u] = kFlagCorrupt where it does not walk
 hipError_t launch_traceback(const uint64_t* frame_off, uint32_t n_utts, const uint16_t* tb_word, const uint16_t* tb_bkp,
                             uint32_t silence_word, uint32_t n_words, uint32_t* out_words, uint32_t* out_count,

@@ -659,6 +659,27 @@ int check_corpus(const sr_model* m, const sr_corpus* c) {
 
 }  // namespace
 
+namespace {  // sr_stream_*
+// the slot of an open utterance's id, or -1
+int64_t stream_slot(const sr_stream* s, uint32_t id) {
+  const uint32_t slot = id % s->max_streams;
+  return s->open[slot] && s->id[slot] == id ? (int64_t)slot : -1;
+}
+// the partial (after every push) or final words of the utterance in `slot`
+int stream_words(sr_stream* s, uint32_t slot, uint32_t id, uint32_t* out_words, uint32_t cap, uint32_t* count) {
+  *count = 0;
+  if (s->frames[slot] == 0) return SR_OK;  // nothing searched yet: the empty utterance's (no) words
+  StreamState st;
+  HIP_TRY(hipMemcpy(&st, s->state.p + slot, sizeof(st), hipMemcpyDeviceToHost));
+  if (st.flags & kFlagCorrupt) return fail(SR_ECORRUPT, "stream %u: the traceback does not walk back to frame 0 (Recognizer.cpp:222-231)", id);
+  if (st.count > s->frames[slot]) return fail(SR_ECORRUPT, "stream %u: %u words for %llu frames", id, st.count, (unsigned long long)s->frames[slot]);
+  *count = st.count;
+  if (st.count > cap) return fail(SR_EINVAL, "stream %u: %u words, out_words holds %u", id, st.count, cap);
+  if (st.count) HIP_TRY(hipMemcpy(out_words, s->words.p + (size_t)slot * s->max_frames, sizeof(uint32_t) * st.count, hipMemcpyDeviceToHost));
+  return SR_OK;
+}
+}  // namespace
+
 extern "C" {
 
 const char* sr_last_error(void) { return g_err; }
@@ -1785,6 +1806,164 @@ int sr_probe_fp16_denormals(int device, int* preserved) {
   bool ok = false;
   HIP_TRY(probe_fp16_denormals(nullptr, &ok));
   *preserved = ok ? 1 : 0;
+  return SR_OK;
+  });
+}
+
+// ---- streaming recognition (sr_stream_*): decode_stream_kernel over per-slot state in device memory ---------------------------
+
+int sr_stream_open(sr_model* m, sr_lexicon* l, const sr_search_params* p, uint32_t max_streams, uint64_t max_frames, sr_stream** out) {
+  return guarded(__func__, [&]() -> int {
+  if (!out) return fail(SR_EINVAL, "out is null");
+  *out = nullptr;
+  int rc = check_model(m);
+  if (rc) return rc;
+  if (!l || l->model != m) return fail(SR_EINVAL, "lexicon does not belong to this model");
+  if (!p) return fail(SR_EINVAL, "null search params");
+  if (p->flags != 0) return fail(SR_EINVAL, "sr_search_params.flags must be 0 for streaming (got 0x%x)", (unsigned)p->flags);
+  if (p->gmm_kernel < SR_GMM_MFMA || p->gmm_kernel > SR_GMM_DEFAULT) return fail(SR_EINVAL, "unknown gmm_kernel %d", p->gmm_kernel);
+  if (max_streams == 0) return fail(SR_EINVAL, "max_streams must be at least 1");
+  if (max_frames == 0) return fail(SR_EINVAL, "max_frames must be at least 1");
+  if (max_frames > 65535) return fail(SR_ELIMIT, "max_frames %llu: back pointers are 16 bit like the reference's Book::bkp (max 65535)", (unsigned long long)max_frames);
+  if (l->n_slots > decode_big_max_slots()) return fail(SR_ELIMIT, "%u trellis positions exceed the stream search's limit of %u", l->n_slots, decode_big_max_slots());
+  sr_stream* s = new sr_stream();
+  std::unique_ptr<sr_stream, int (*)(sr_stream*)> own(s, sr_stream_destroy);
+  s->model = m; s->lex = l; s->params = *p; s->max_streams = max_streams; s->max_frames = max_frames;
+  s->open.assign(max_streams, 0); s->id.assign(max_streams, 0); s->generation.assign(max_streams, 0); s->frames.assign(max_streams, 0);
+  const size_t S = max_streams;
+  HIP_TRY(s->ws.ensure(S * decode_big_workspace(l->n_slots)));
+  HIP_TRY(s->state.ensure(S));
+  HIP_TRY(s->tb_score.ensure(S * (max_frames + 1)));
+  HIP_TRY(s->tb_word.ensure(S * (max_frames + 1)));
+  HIP_TRY(s->tb_bkp.ensure(S * (max_frames + 1)));
+  HIP_TRY(s->words.ensure(S * max_frames));
+  *out = own.release();
+  return SR_OK;
+  });
+}
+
+int sr_stream_begin(sr_stream* s, uint32_t* id) {
+  return guarded(__func__, [&]() -> int {
+  if (!s || !id) return fail(SR_EINVAL, "null argument");
+  uint32_t slot = 0;
+  while (slot < s->max_streams && s->open[slot]) slot++;
+  if (slot == s->max_streams) return fail(SR_ELIMIT, "all %u streams are open", s->max_streams);
+  // id = slot + max_streams * generation, the generation wrapping before the id leaves 32 bits
+  uint32_t g = s->generation[slot];
+  if ((uint64_t)slot + (uint64_t)s->max_streams * g > 0xFFFFFFFFull) g = 0;
+  s->generation[slot] = g + 1;
+  s->id[slot] = slot + s->max_streams * g;
+  s->open[slot] = 1;
+  s->frames[slot] = 0;  // the first push starts from the initial state (decode_stream_kernel)
+  *id = s->id[slot];
+  return SR_OK;
+  });
+}
+
+int sr_stream_push(sr_stream* s, uint32_t n, const uint32_t* ids, const float* feats, const uint64_t* frame_off) {
+  return guarded(__func__, [&]() -> int {
+  if (!s) return fail(SR_EINVAL, "null stream set");
+  if (n == 0) return SR_OK;
+  if (!ids || !frame_off) return fail(SR_EINVAL, "null argument");
+  if (frame_off[0] != 0) return fail(SR_EINVAL, "frame_off[0] must be 0");
+  std::vector<uint8_t> seen(s->max_streams, 0);
+  std::vector<StreamJob> jobs;
+  for (uint32_t i = 0; i < n; i++) {
+    const int64_t slot = stream_slot(s, ids[i]);
+    if (slot < 0) return fail(SR_EINVAL, "push entry %u: stream id %u is not open", i, ids[i]);
+    if (seen[slot]) return fail(SR_EINVAL, "push entry %u: stream id %u appears twice in one push", i, ids[i]);
+    seen[slot] = 1;
+    if (frame_off[i + 1] < frame_off[i]) return fail(SR_EINVAL, "frame_off is not ascending at entry %u", i);
+    const uint64_t k = frame_off[i + 1] - frame_off[i];
+    if (k > s->max_frames - s->frames[slot])
+      return fail(SR_ELIMIT, "stream id %u: %llu + %llu frames exceed max_frames %llu", ids[i], (unsigned long long)s->frames[slot],
+                  (unsigned long long)k, (unsigned long long)s->max_frames);
+    if (k) jobs.push_back({(uint32_t)slot, (uint32_t)s->frames[slot], (uint32_t)k, 0u, frame_off[i]});
+  }
+  const uint64_t F = frame_off[n];
+  if (F == 0) return SR_OK;
+  if (!feats) return fail(SR_EINVAL, "null feats");
+  sr_model* m = s->model;
+  sr_lexicon* l = s->lex;
+  int rc = check_model(m);
+  if (rc) return rc;
+  HIP_TRY(s->feats.ensure((size_t)F * m->dim));
+  HIP_TRY(s->scores.ensure((size_t)F * m->ld));
+  HIP_TRY(s->jobs.ensure(jobs.size()));
+  HIP_TRY(hipMemcpyAsync(s->feats.p, feats, sizeof(float) * F * m->dim, hipMemcpyHostToDevice, m->s_gmm));
+  HIP_TRY(hipMemcpyAsync(s->jobs.p, jobs.data(), sizeof(StreamJob) * jobs.size(), hipMemcpyHostToDevice, m->s_gmm));
+  if ((rc = launch_scoring(m, s->feats.p, F, s->params.gmm_kernel, s->scores.p))) return rc;
+  const hipStream_t s_search = m->overlap ? m->s_search : m->s_gmm;
+  HIP_TRY(hipEventRecord(m->ev_scored[0], m->s_gmm));
+  HIP_TRY(hipStreamWaitEvent(s_search, m->ev_scored[0], 0));
+  StreamArgs a{};
+  a.net.n_slots = l->n_slots; a.net.n_words = l->n_words;
+  a.net.slot_info = l->slot_info.p; a.net.slot_word = l->slot_word.p; a.net.word_end_slot = l->word_end_slot.p;
+  a.net.silence_word = l->silence_idx; a.net.silence_state = l->silence_state;
+  a.net.tdp_loop = l->tdp[0]; a.net.tdp_forward = l->tdp[1]; a.net.tdp_skip = l->tdp[2];
+  a.am_threshold = s->params.am_threshold; a.word_penalty = s->params.word_penalty;
+  a.scores = s->scores.p; a.ld = m->ld; a.jobs = s->jobs.p;
+  a.ws = s->ws.p; a.ws_stride = decode_big_workspace(l->n_slots); a.state = s->state.p;
+  a.tb_score = s->tb_score.p; a.tb_word = s->tb_word.p; a.tb_bkp = s->tb_bkp.p; a.tb_stride = s->max_frames + 1;
+  a.words = s->words.p; a.words_stride = s->max_frames;
+  EventPair ep{};
+  if ((rc = prof_begin(m, s_search, 1, &ep))) return rc;
+  HIP_TRY(launch_decode_stream(a, (uint32_t)jobs.size(), s_search));
+  if ((rc = prof_end(m, s_search, &ep))) return rc;
+  HIP_TRY(hipStreamSynchronize(s_search));
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  for (const StreamJob& j : jobs) s->frames[j.slot] += j.k;
+  if (m->profiling) {
+    m->prof.search_bytes += (8.0 * m->n_states + 4.0 * l->n_slots) * (double)F;
+    m->prof.frames += F;
+  }
+  return SR_OK;
+  });
+}
+
+int sr_stream_partial(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_t cap, uint32_t* count, uint64_t* frames) {
+  return guarded(__func__, [&]() -> int {
+  if (!s || !count || (!out_words && cap)) return fail(SR_EINVAL, "null argument");
+  const int64_t slot = stream_slot(s, id);
+  if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
+  int rc = check_model(s->model);
+  if (rc) return rc;
+  if (frames) *frames = s->frames[slot];
+  return stream_words(s, (uint32_t)slot, id, out_words, cap, count);
+  });
+}
+
+int sr_stream_end(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_t cap, uint32_t* count, double* tb_score, uint16_t* tb_word,
+                  uint16_t* tb_bkp) {
+  return guarded(__func__, [&]() -> int {
+  if (!s || !count || (!out_words && cap)) return fail(SR_EINVAL, "null argument");
+  const int64_t slot = stream_slot(s, id);
+  if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
+  int rc = check_model(s->model);
+  if (rc) return rc;
+  rc = stream_words(s, (uint32_t)slot, id, out_words, cap, count);
+  if (rc == SR_EINVAL) return rc;  // too small a buffer: the utterance stays open
+  const uint64_t T = s->frames[slot];
+  if (rc == SR_OK && T == 0) {  // traceback[0] of the empty utterance (Recognizer.cpp:118-120)
+    if (tb_score) tb_score[0] = 0.0;
+    if (tb_word) tb_word[0] = 0;
+    if (tb_bkp) tb_bkp[0] = 0;
+  } else if (rc == SR_OK) {
+    const size_t b = (size_t)slot * (s->max_frames + 1);
+    if (tb_score) HIP_TRY(hipMemcpy(tb_score, s->tb_score.p + b, sizeof(double) * (T + 1), hipMemcpyDeviceToHost));
+    if (tb_word) HIP_TRY(hipMemcpy(tb_word, s->tb_word.p + b, sizeof(uint16_t) * (T + 1), hipMemcpyDeviceToHost));
+    if (tb_bkp) HIP_TRY(hipMemcpy(tb_bkp, s->tb_bkp.p + b, sizeof(uint16_t) * (T + 1), hipMemcpyDeviceToHost));
+  }
+  s->open[slot] = 0;
+  return rc;
+  });
+}
+
+int sr_stream_destroy(sr_stream* s) {
+  return guarded(__func__, [&]() -> int {
+  if (!s) return SR_OK;
+  if (s->model) { (void)hipSetDevice(s->model->device); (void)hipDeviceSynchronize(); }
+  delete s;
   return SR_OK;
   });
 }

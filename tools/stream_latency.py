@@ -1,0 +1,108 @@
+#!/usr/bin/env python3
+"""Latency of streaming recognition (sr_stream_*) on bench.py's headline workload (BASELINE configs[2]: 4000 states x 32
+densities, 1333 three-state words, 39-dim frames, utterances U{200..400} from bench.py's seed, beam 200, word penalty 10).
+
+N concurrent streams (default 64); every push hands each open stream its next `--piece` frames (default 10, i.e. 100 ms of
+audio); a stream that has had all its frames is ended and the next utterance begun in its place.  Prints the median and p99
+wall time per push (host clock around sr_stream_push, which returns after its search has finished), the device time of the
+scoring and search launches from sr_profile, and the total time to finish the corpus against one sr_recognize_corpus over the
+same utterances (features resident).  The streamed words are checked against the batch's.  Needs a GPU."""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--streams", type=int, default=64)
+    ap.add_argument("--piece", type=int, default=10, help="frames per stream per push")
+    ap.add_argument("--utts", type=int, default=1000, help="utterances of bench.py's corpus to stream")
+    ap.add_argument("--kernel", choices=["default", "prefilter", "exact", "mfma"], default="default")
+    args = ap.parse_args()
+
+    from speechrecognition_amd import capi, synth
+
+    D = 39
+    lex = synth.make_lexicon(1333, 3, 1)
+    tdp, beam, wp = (3.0, 0.0, 30.0), 200.0, 10.0
+    kernel = {"mfma": capi.GMM_MFMA, "exact": capi.GMM_EXACT, "prefilter": capi.GMM_PREFILTER, "default": capi.GMM_DEFAULT}[args.kernel]
+    tmp = tempfile.mkdtemp(prefix="srstream_")
+    mp = os.path.join(tmp, "model.mix")
+    synth.write_mixset(mp, synth.make_mixset(lex.n_states, 32, D, seed=23))  # bench.py's model and corpus
+    feats, off = synth.make_batch(1000, 200, 400, D, seed=7)
+    n = min(args.utts, len(off) - 1)
+    off = off[: n + 1]
+    feats = feats[: int(off[-1])]
+    utts = [feats[int(off[u]):int(off[u + 1])] for u in range(n)]
+    word_off, automaton, sil = lex.flatten()
+
+    with capi.Model.from_mixset(mp, D) as m:
+        lexh = m.lexicon(word_off, automaton, lex.silence_idx, tdp, sil)
+        corpus = m.upload(feats, off)
+        corpus.recognize(lexh, beam, wp, kernel)  # warm: packing, workspaces
+        t = time.perf_counter()
+        words, woff = corpus.recognize(lexh, beam, wp, kernel)
+        batch_s = time.perf_counter() - t
+        corpus.close()
+
+        with m.stream(lexh, beam, wp, kernel, max_streams=args.streams, max_frames=int(np.diff(off.astype(np.int64)).max())) as st:
+            warm = [st.begin() for _ in range(args.streams)]  # warm: staging at the full push size, the kernels' code objects
+            st.push({sid: utts[0][:args.piece] for sid in warm})
+            for sid in warm:
+                st.end(sid)
+            m.profile(True)
+            todo = list(range(n))
+            open_ = {}  # id -> (utterance, frames pushed)
+            got = {}
+            push_ms = []
+            t_all = time.perf_counter()
+            while todo or open_:
+                while todo and len(open_) < args.streams:
+                    u = todo.pop(0)
+                    open_[st.begin()] = (u, 0)
+                batch = {}
+                for sid, (u, t0) in open_.items():
+                    batch[sid] = utts[u][t0:t0 + args.piece]
+                t = time.perf_counter()
+                st.push(batch)
+                push_ms.append(1e3 * (time.perf_counter() - t))
+                for sid in list(open_):
+                    u, t0 = open_[sid]
+                    t0 += len(batch[sid])
+                    if t0 == len(utts[u]):
+                        got[u] = st.end(sid)
+                        del open_[sid]
+                    else:
+                        open_[sid] = (u, t0)
+            stream_s = time.perf_counter() - t_all
+            prof = m.profile_read()
+        lexh.close()
+
+    same = all(np.array_equal(got[u], words[int(woff[u]):int(woff[u + 1])]) for u in range(n))
+    pm = np.asarray(push_ms)
+    pushes = len(pm)
+    print(f"workload: configs[2] model (4000 states x 32, 1333 three-state words), {n} utterances, {int(off[-1])} frames, "
+          f"{args.streams} concurrent streams, {args.piece} frames per stream per push, gmm_kernel {args.kernel}")
+    print(f"pushes: {pushes}; wall per push: median {np.median(pm):.3f} ms, p99 {np.percentile(pm, 99):.3f} ms, "
+          f"min {pm.min():.3f} ms, max {pm.max():.3f} ms")
+    print(f"device per push (sr_profile): scoring {prof['gmm_ms'] / pushes:.3f} ms ({prof['gmm_launches']} launches), "
+          f"search {prof['search_ms'] / pushes:.3f} ms ({prof['search_launches']} launches); frames {prof['frames']}")
+    dev = prof["gmm_ms"] + prof["search_ms"]
+    print(f"device share of push wall time: {dev / pm.sum():.1%} (the rest: copies, launches, synchronisation, host)")
+    print(f"corpus: streamed in {stream_s:.3f} s (of which {pm.sum() / 1e3:.3f} s in sr_stream_push) vs one "
+          f"sr_recognize_corpus {batch_s:.3f} s ({stream_s / batch_s:.1f}x)")
+    print(f"streamed words equal the batch's: {'yes' if same else 'NO'}")
+    return 0 if same else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
