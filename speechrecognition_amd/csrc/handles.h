@@ -167,18 +167,14 @@ struct sr_corpus {
 
 struct sr_lexicon {
   sr_model* model = nullptr;
-  uint32_t n_words = 0, n_slots = 0, silence_idx = 0, silence_state = 0;
-  double tdp[3] = {0, 0, 0};
+  // the search networks (kernels.h; build_decode_net, build_fast_net, build_word_net), pointing into the buffers below
+  srgpu::DecodeNet net{};
+  srgpu::FastNet fast{};    // n_slots = 0: none -- more slots than the LDS kernels hold, decode_big_kernel
+  srgpu::WordNet words{};   // info = null: none -- some word has more than 4 positions, or the words do not fit a workgroup
   DevBuf<uint32_t> slot_info, slot_word, word_end_slot;
-  // type-sorted copy for the fast kernel
   DevBuf<uint32_t> f_state, f_pred, f_orig, f_type, f_word;
-  uint32_t f_n = 0, f_init = 0, f_init_end = 0;
-  DevBuf<uint32_t> w_info;   // word-per-lane network (viterbi_words.hip); empty unless every word has <= 4 positions
+  DevBuf<uint32_t> w_info, w_order;
   DevBuf<uint2> w_states;
-  DevBuf<uint32_t> w_order;
-  uint32_t w_plain_len = 0;  // 0: no word-per-lane network
-  uint32_t w_nw = 0, w_nt = 0, w_general = 0;
-  bool big = false;                 // more slots than the LDS kernels hold: decode_big_kernel, no type-sorted copy
 };
 
 struct sr_bigram {

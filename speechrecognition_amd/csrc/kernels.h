@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 namespace srgpu {
 
 // ---- GMM scoring, FP64 MFMA contraction (gmm_mfma.hip) ------------------------------------------
@@ -119,17 +121,24 @@ hipError_t launch_transpose_feats(const float* feats, uint64_t n_frames, uint32_
 struct DecodeNet {
   uint32_t n_slots;             // P
   uint32_t n_words;
-  const uint32_t* slot_info;    // [P] packed per-slot constants, see viterbi_decode.hip
+  const uint32_t* slot_info;    // [P] emission state (bits 0-15) | the kSlot* flags below
   const uint32_t* slot_word;    // [P] word index of the slot
   const uint32_t* word_end_slot;// [W] slot index of each word's last position
   uint32_t silence_word;
   double tdp_loop, tdp_forward, tdp_skip;
   uint32_t silence_state;
 };
+static constexpr uint32_t kSlotPos0 = 1u << 16;      // position 0 of its word
+static constexpr uint32_t kSlotPos1 = 1u << 17;      // position 1
+static constexpr uint32_t kSlotEnd = 1u << 18;       // last position (word end): no in-word expansion
+static constexpr uint32_t kSlotSilState = 1u << 19;  // its state is the silence state: tdp is always `forward`
+static constexpr uint32_t kSlotSilWord = 1u << 20;   // word is the silence word: no word penalty
+static constexpr uint32_t kSlotFirstSil = 1u << 21;  // word's first state is the silence state
+static constexpr uint32_t kSlotSingle = 1u << 22;    // one-position word: owns the virtual dead slot (w, 1)
 // The same network with slots sorted by type for the fast kernel (viterbi_fast.hip); ids below are positions in
 // the sorted order, every type padded to a multiple of 64 slots.
 struct FastNet {
-  uint32_t n_slots;             // padded total (multiple of 64)
+  uint32_t n_slots;             // padded total (multiple of 64); 0: not built -- more than decode_max_slots(), a `big` lexicon
   const uint32_t* state;        // [n] emission state of the slot
   const uint32_t* pred;         // [n] sorted id of the slot one position back | two positions back << 16
   const uint32_t* orig;         // [n] original slot index | original index of the word's position 0 << 16; 0xFFFFFFFF = padding
@@ -167,22 +176,40 @@ struct DecodeArgs {
   uint32_t* out_words;          // utterance u writes its words at out_words[frame_off[u] ...]
   uint32_t* out_count;          // [n_utts_total]
   uint32_t* out_flags;          // [n_utts_total] kFlagSlowPath | kFlagReplay | kFlagCorrupt (traceback.h)
-  uint32_t force_general;       // skip the fast kernels: every utterance goes through decode_kernel<.., REPLAY = true>
-  uint32_t force_slots;         // the slot-per-lane kernel (viterbi_fast.hip) even where the word-per-lane kernel applies
-  uint32_t only_flagged;        // decode_big_kernel as the replay of the word-per-lane kernel: only utterances flagged kFlagReplay
+  uint32_t only_flagged;        // the replay kernel redoes only the utterances a fast kernel flagged kFlagReplay (set by launch_decode)
   uint32_t exact_negative;      // the model's emission costs can be negative (some density has norm - log weight < 0): the word-per-lane kernel
                                 // runs its NEG variant, which replays the reference's early-out instead of flagging the utterance
 };
-hipError_t launch_decode(const DecodeArgs& a, hipStream_t stream);       // fast variant, then the replay variant for flagged utterances
-hipError_t launch_decode_fast(const DecodeArgs& a, hipStream_t stream);
-bool decode_words_applies(const DecodeArgs& a);                          // short-word lexicon whose score rows fit the LDS twice
-uint32_t decode_words_max_words();
-hipError_t launch_decode_words(const DecodeArgs& a, hipStream_t stream);
+// The zerogram search of a lexicon: a fast kernel first, if any -- word per lane (viterbi_words.hip) or slot per lane
+// (viterbi_fast.hip) --, then the replay kernel -- decode_kernel (LDS) or, for a lexicon without a FastNet, decode_big_kernel
+// (hypotheses in device memory) -- on the utterances the fast kernel flagged, or on every utterance when there is none.
+enum class DecodeFirst { kNone, kWords, kSlots };
+struct DecodeRoute {
+  DecodeFirst first;
+  bool big;                     // the replay kernel is decode_big_kernel: a workspace of n_utts * decode_big_workspace(P) bytes
+};
+// from the networks, the model's ld and the search flags (SR_SEARCH_GENERAL_KERNEL, SR_SEARCH_SLOT_KERNEL)
+DecodeRoute decode_route(const DecodeArgs& a, bool general, bool slots);
+hipError_t launch_decode(DecodeArgs a, const DecodeRoute& r, unsigned char* big_ws, hipStream_t stream);
 uint32_t decode_max_slots();          // what the LDS-resident kernels hold
-// lexicons beyond that: hypothesis arrays in a global workspace of n_utts * decode_big_workspace(P) bytes
 uint32_t decode_big_max_slots();
 size_t decode_big_workspace(uint32_t n_slots);
-hipError_t launch_decode_big(const DecodeArgs& a, unsigned char* ws, hipStream_t stream);
+uint32_t decode_words_max_words();
+// launch_decode's pieces
+hipError_t launch_decode_fast(const DecodeArgs& a, hipStream_t stream);
+bool decode_words_applies(const DecodeArgs& a);                          // short-word lexicon whose score rows fit the LDS twice
+hipError_t launch_decode_words(const DecodeArgs& a, hipStream_t stream);
+// The networks, built on the host beside the kernels that read them from a lexicon of n_words words, word w's emission states
+// automaton[word_off[w] .. word_off[w + 1]).  A builder fills the net's scalars and writes its arrays into the vectors;
+// sr_lexicon_create uploads those and sets the net's pointers.
+DecodeNet build_decode_net(uint32_t n_words, const uint32_t* word_off, const uint16_t* automaton, uint32_t silence_word,
+                           uint32_t silence_state, const double tdp[3], std::vector<uint32_t>& slot_info,
+                           std::vector<uint32_t>& slot_word, std::vector<uint32_t>& word_end_slot);
+FastNet build_fast_net(const std::vector<uint32_t>& slot_info, const std::vector<uint32_t>& slot_word, const uint32_t* word_off,
+                       std::vector<uint32_t>& state, std::vector<uint32_t>& pred, std::vector<uint32_t>& orig,
+                       std::vector<uint32_t>& chunk_type, std::vector<uint32_t>& word);
+WordNet build_word_net(uint32_t n_words, const uint32_t* word_off, const uint16_t* automaton, uint32_t silence_word,
+                       uint32_t silence_state, std::vector<uint32_t>& info, std::vector<uint2>& states, std::vector<uint32_t>& order);
 // streaming (sr_stream_push): decode_stream_kernel advances each of n open utterances by k frames from the state the last push
 // left in device memory.  Per stream slot: decode_big_workspace(P) bytes of hypotheses, a StreamState, max_frames + 1 traceback
 // entries (words, not slots) and max_frames words of partial result.

@@ -1015,145 +1015,53 @@ int sr_lexicon_create(sr_model* m, uint32_t n_words, const uint32_t* word_off, c
   if (max_pos < 2) return fail(SR_ELIMIT, "lexicon needs at least one word with two or more positions");
   const uint32_t P = word_off[n_words];
   if (P > decode_big_max_slots()) return fail(SR_ELIMIT, "%u trellis positions exceed the decoder's limit of %u", P, decode_big_max_slots());
-  std::vector<uint32_t> info(P), sword(P), wend(n_words);
-  for (uint32_t w = 0; w < n_words; w++) {
-    const uint32_t b = word_off[w], n = word_off[w + 1] - b;
-    const uint32_t first = automaton[b];
-    for (uint32_t k = 0; k < n; k++) {
-      const uint32_t st = automaton[b + k];
+  for (uint32_t w = 0; w < n_words; w++)
+    for (uint32_t k = 0; k < word_off[w + 1] - word_off[w]; k++) {
+      const uint32_t st = automaton[word_off[w] + k];
       if (st >= m->n_states) return fail(SR_EINVAL, "word %u position %u: state %u >= n_states %u", w, k, st, m->n_states);
-      uint32_t f = st;
-      if (k == 0) f |= 1u << 16;
-      if (k == 1) f |= 1u << 17;
-      if (k == n - 1) f |= 1u << 18;
-      if (st == silence_state) f |= 1u << 19;
-      if (w == silence_idx) f |= 1u << 20;
-      if (first == silence_state) f |= 1u << 21;
-      if (n == 1) f |= 1u << 22;
-      info[b + k] = f;
-      sword[b + k] = w;
     }
-    wend[w] = b + n - 1;
-  }
-  // ---- type-sorted network for the fast kernel (viterbi_fast.hip) ---------------------------------------------
-  // key = kind | silence-state << 3 | silence-word << 4 | first-state-is-silence << 5; kinds: 0 entry position 0,
-  // 1 single-position word, 2 entry position 1, 3 position 1 that is also the word end, 4 middle, 5 word end
-  std::vector<uint32_t> key(P);
-  for (uint32_t p = 0; p < P; p++) {
-    const uint32_t f = info[p];
-    const bool pos0 = f & (1u << 16), pos1 = f & (1u << 17), end = f & (1u << 18);
-    const uint32_t kind = pos0 ? (end ? 1u : 0u) : pos1 ? (end ? 3u : 2u) : (end ? 5u : 4u);
-    key[p] = kind | ((f >> 19 & 1u) << 3) | ((f >> 20 & 1u) << 4) | ((f >> 21 & 1u) << 5);
-  }
-  std::vector<uint32_t> new_id(P), f_state, f_pred, f_orig, f_type, f_word;
-  for (uint32_t k = 0; k < 64; k++) {
-    bool any = false;
-    for (uint32_t p = 0; p < P; p++) {
-      if (key[p] != k) continue;
-      any = true;
-      new_id[p] = (uint32_t)f_orig.size();
-      f_orig.push_back(p);  // completed below
-    }
-    if (!any) continue;
-    while (f_orig.size() % 64) f_orig.push_back(0xFFFFFFFFu);
-    f_type.resize(f_orig.size() / 64, k);
-  }
-  uint32_t Pn = (uint32_t)f_orig.size();
-  // beyond what the LDS holds (type padding included) the search runs from a global workspace (decode_big_kernel): no fast net
-  const bool big = Pn > decode_max_slots();
-  if (big) { Pn = 0; f_orig.clear(); f_type.clear(); }
-  f_state.assign(Pn, 0); f_pred.assign(Pn, 0); f_word.assign(Pn, 0);
-  for (uint32_t q = 0; q < Pn; q++) {
-    const uint32_t p = f_orig[q];
-    if (p == 0xFFFFFFFFu) { f_pred[q] = q | (q << 16); continue; }
-    const uint32_t w = sword[p], base = word_off[w], k = p - base;
-    f_state[q] = info[p] & 0xFFFFu;
-    f_word[q] = w;
-    f_pred[q] = (k >= 1 ? new_id[p - 1] : q) | ((k >= 2 ? new_id[p - 2] : q) << 16);
-    f_orig[q] = p | (base << 16);
-  }
-  // ---- word by word for the word-per-lane kernel (viterbi_words.hip): every word at most four positions --------------------
-  std::vector<uint32_t> w_info, w_order;
+  std::vector<uint32_t> info, sword, wend, f_state, f_pred, f_orig, f_type, f_word, w_info, w_order;
   std::vector<uint2> w_states;
-  uint32_t plain_len = 0, w_nw = 0, w_nt = 0, w_general = 0;
-  if (max_pos <= 4 && n_words <= decode_words_max_words()) {
-    w_info.resize(n_words); w_states.resize(n_words);
-    uint32_t hist[5] = {0, 0, 0, 0, 0};
-    for (uint32_t w = 0; w < n_words; w++) {
-      const uint32_t b = word_off[w], n = word_off[w + 1] - b;
-      uint32_t f = n, st[4] = {0, 0, 0, 0};
-      if (w == silence_idx) f |= 8u;
-      if (automaton[b] == silence_state) f |= 16u;
-      for (uint32_t k = 0; k < n; k++) {
-        st[k] = automaton[b + k];
-        if (st[k] == silence_state) f |= 1u << (8 + k);
-      }
-      w_info[w] = f;
-      w_states[w] = make_uint2(st[0] | (st[1] << 16), st[2] | (st[3] << 16));
-      if (f == n) hist[n]++;  // no flags
-    }
-    // plain words: the commonest flag-free length of 2..4 positions.  Every kind fills whole groups of 64 lane slots; slot
-    // s = tid + k * nt belongs to group s / 64 = k * n_waves + wave.  Plain and single groups are dealt to the first waves, nw
-    // per wave; a general group -- three times the instructions of a plain one -- gets a wave of its own (its other groups
-    // stay empty), because a frame lasts as long as its heaviest wave (viterbi_words.hip).
-    plain_len = 3;
-    for (uint32_t n = 2; n <= 4; n++) if (hist[n] > hist[plain_len]) plain_len = n;
-    std::vector<uint32_t> kinds[3];  // plain, single, general
-    for (uint32_t w = 0; w < n_words; w++)
-      kinds[w_info[w] == plain_len ? 0 : (w_info[w] & 7u) == 1u ? 1 : 2].push_back(w);
-    const uint32_t g_plain = ((uint32_t)kinds[0].size() + 63) / 64, g_single = ((uint32_t)kinds[1].size() + 63) / 64,
-                   g_gen = ((uint32_t)kinds[2].size() + 63) / 64;
-    w_general = g_gen ? 1u : 0u;
-    // words per lane: the fewest that leave a workgroup of at most 8 waves -- two of them share a CU then (128 registers per
-    // lane each), and while one waits at its barrier the other computes --, else the fewest that fit 16 waves
-    auto waves_for = [&](uint32_t nw) { return (g_plain + g_single + nw - 1) / nw + g_gen; };
-    uint32_t waves = 0;
-    for (w_nw = 1; w_nw <= 3 && waves_for(w_nw) > 8; w_nw++) {}
-    if (w_nw > 3) for (w_nw = 1; w_nw <= 3 && waves_for(w_nw) > 16; w_nw++) {}
-    if (w_nw <= 3) {
-      waves = waves_for(w_nw);
-      w_nt = waves * 64;
-      w_order.assign((size_t)w_nw * w_nt, 0xFFFFFFFFu);
-      auto put_group = [&](uint32_t wave, uint32_t k, const std::vector<uint32_t>& words, uint32_t g) {
-        for (uint32_t i = 0; i < 64 && (size_t)g * 64 + i < words.size(); i++) w_order[(size_t)k * w_nt + wave * 64 + i] = words[(size_t)g * 64 + i];
-      };
-      uint32_t seq = 0;  // plain groups, then single groups: wave seq / nw, slot row seq % nw
-      for (uint32_t g = 0; g < g_plain; g++, seq++) put_group(seq / w_nw, seq % w_nw, kinds[0], g);
-      for (uint32_t g = 0; g < g_single; g++, seq++) put_group(seq / w_nw, seq % w_nw, kinds[1], g);
-      for (uint32_t g = 0; g < g_gen; g++) put_group(waves - g_gen + g, 0, kinds[2], g);
-    } else {
-      plain_len = 0;  // more groups than a workgroup has room for: the slot-per-lane kernel
-    }
-  }
   sr_lexicon* l = new sr_lexicon();
   std::unique_ptr<sr_lexicon, int (*)(sr_lexicon*)> own(l, sr_lexicon_destroy);
-  l->w_plain_len = plain_len; l->w_nw = w_nw; l->w_nt = w_nt; l->w_general = w_general;
-  l->f_n = Pn; l->f_init = new_id[0]; l->f_init_end = (info[0] >> 18) & 1u; l->big = big;
-  l->model = m; l->n_words = n_words; l->n_slots = P; l->silence_idx = silence_idx; l->silence_state = silence_state;
-  l->tdp[0] = tdp[0]; l->tdp[1] = tdp[1]; l->tdp[2] = tdp[2];
+  l->model = m;
+  l->net = build_decode_net(n_words, word_off, automaton, silence_idx, silence_state, tdp, info, sword, wend);
+  l->fast = build_fast_net(info, sword, word_off, f_state, f_pred, f_orig, f_type, f_word);
+  l->words = build_word_net(n_words, word_off, automaton, silence_idx, silence_state, w_info, w_states, w_order);
   hipError_t e;
   if ((e = l->slot_info.upload(info.data(), P)) != hipSuccess || (e = l->slot_word.upload(sword.data(), P)) != hipSuccess ||
-      (e = l->word_end_slot.upload(wend.data(), n_words)) != hipSuccess || (e = l->f_state.upload(f_state.data(), Pn)) != hipSuccess ||
-      (e = l->f_pred.upload(f_pred.data(), Pn)) != hipSuccess || (e = l->f_orig.upload(f_orig.data(), Pn)) != hipSuccess ||
-      (e = l->f_type.upload(f_type.data(), Pn / 64)) != hipSuccess || (e = l->f_word.upload(f_word.data(), Pn)) != hipSuccess ||
+      (e = l->word_end_slot.upload(wend.data(), n_words)) != hipSuccess || (e = l->f_state.upload(f_state.data(), f_state.size())) != hipSuccess ||
+      (e = l->f_pred.upload(f_pred.data(), f_pred.size())) != hipSuccess || (e = l->f_orig.upload(f_orig.data(), f_orig.size())) != hipSuccess ||
+      (e = l->f_type.upload(f_type.data(), f_type.size())) != hipSuccess || (e = l->f_word.upload(f_word.data(), f_word.size())) != hipSuccess ||
       (e = l->w_info.upload(w_info.data(), w_info.size())) != hipSuccess || (e = l->w_states.upload(w_states.data(), w_states.size())) != hipSuccess ||
       (e = l->w_order.upload(w_order.data(), w_order.size())) != hipSuccess)
     return fail(SR_EHIP, "lexicon upload: %s", hipGetErrorString(e));
+  l->net.slot_info = l->slot_info.p; l->net.slot_word = l->slot_word.p; l->net.word_end_slot = l->word_end_slot.p;
+  l->fast.state = l->f_state.p; l->fast.pred = l->f_pred.p; l->fast.orig = l->f_orig.p; l->fast.chunk_type = l->f_type.p; l->fast.word = l->f_word.p;
+  l->words.info = w_info.empty() ? nullptr : l->w_info.p; l->words.states = l->w_states.p; l->words.order = l->w_order.p;
   *out = own.release();
   return SR_OK;
   });
 }
 
+// the lexicon's networks and the model's row stride: what decode_route decides from
+static DecodeArgs lexicon_args(const sr_lexicon* l) {
+  DecodeArgs da{};
+  da.net = l->net; da.fast = l->fast; da.words = l->words;
+  da.ld = l->model ? l->model->ld : 0;
+  return da;
+}
+
 int sr_lexicon_describe(const sr_lexicon* l, char* out, size_t cap) {
   return guarded(__func__, [&]() -> int {
   if (!l || !out || cap == 0) return fail(SR_EINVAL, "null argument");
-  DecodeArgs da{};
-  da.words.info = l->w_plain_len ? l->w_info.p : nullptr;
-  da.ld = l->model ? l->model->ld : 0;
-  if (l->big && decode_words_applies(da)) snprintf(out, cap, "words %u x %u plain %u%s (replay: big, %u positions)", l->w_nw, l->w_nt, l->w_plain_len, l->w_general ? " general" : "", l->n_slots);
-  else if (l->big) snprintf(out, cap, "big (%u positions: hypotheses in device memory)", l->n_slots);
-  else if (decode_words_applies(da)) snprintf(out, cap, "words %u x %u plain %u%s", l->w_nw, l->w_nt, l->w_plain_len, l->w_general ? " general" : "");
-  else snprintf(out, cap, "slots (%u type-padded positions)", l->f_n);
+  const DecodeRoute r = decode_route(lexicon_args(l), false, false);
+  const WordNet& w = l->words;
+  if (r.first == DecodeFirst::kWords && r.big)
+    snprintf(out, cap, "words %u x %u plain %u%s (replay: big, %u positions)", w.nw, w.nt, w.plain_len, w.has_general ? " general" : "", l->net.n_slots);
+  else if (r.first == DecodeFirst::kWords) snprintf(out, cap, "words %u x %u plain %u%s", w.nw, w.nt, w.plain_len, w.has_general ? " general" : "");
+  else if (r.big) snprintf(out, cap, "big (%u positions: hypotheses in device memory)", l->net.n_slots);
+  else snprintf(out, cap, "slots (%u type-padded positions)", l->fast.n_slots);
   return SR_OK;
   });
 }
@@ -1162,9 +1070,7 @@ int sr_lexicon_destroy(sr_lexicon* l) {
   return guarded(__func__, [&]() -> int {
   if (!l) return SR_OK;
   if (l->model) { (void)hipSetDevice(l->model->device); (void)hipDeviceSynchronize(); }
-  l->slot_info.release(); l->slot_word.release(); l->word_end_slot.release();
-  l->f_state.release(); l->f_pred.release(); l->f_orig.release(); l->f_type.release(); l->f_word.release(); l->w_info.release(); l->w_states.release(); l->w_order.release();
-  delete l;
+  delete l;  // (the buffers go with it)
   return SR_OK;
   });
 }
@@ -1209,26 +1115,16 @@ int sr_recognize_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_searc
   std::vector<Chunk> chunks;
   if ((rc = prepare_chunks(m, c, &chunks))) return rc;
 
-  if (l->big) {  // hypothesis arrays of the utterances in flight
-    uint32_t most = 0;
-    for (const Chunk& ch : chunks) most = std::max(most, ch.u1 - ch.u0);
-    HIP_TRY(c->big_ws.ensure((size_t)most * decode_big_workspace(l->n_slots)));
-  }
-  DecodeArgs da{};
-  da.net.n_slots = l->n_slots; da.net.n_words = l->n_words;
-  da.net.slot_info = l->slot_info.p; da.net.slot_word = l->slot_word.p; da.net.word_end_slot = l->word_end_slot.p;
-  da.net.silence_word = l->silence_idx; da.net.silence_state = l->silence_state;
-  da.net.tdp_loop = l->tdp[0]; da.net.tdp_forward = l->tdp[1]; da.net.tdp_skip = l->tdp[2];
-  da.fast.n_slots = l->f_n; da.fast.state = l->f_state.p; da.fast.pred = l->f_pred.p; da.fast.orig = l->f_orig.p;
-  da.fast.chunk_type = l->f_type.p; da.fast.word = l->f_word.p; da.fast.init_slot = l->f_init; da.fast.init_is_end = l->f_init_end;
-  da.words.info = l->w_plain_len ? l->w_info.p : nullptr; da.words.states = l->w_states.p; da.words.order = l->w_order.p;
-  da.words.plain_len = l->w_plain_len; da.words.nw = l->w_nw; da.words.nt = l->w_nt; da.words.has_general = l->w_general;
-  da.words.init_is_end = l->f_init_end;
-  da.ld = m->ld; da.frame_off = c->d_frame_off.p; da.utt_order = c->utt_order.p;
+  DecodeArgs da = lexicon_args(l);
+  da.frame_off = c->d_frame_off.p; da.utt_order = c->utt_order.p;
   da.am_threshold = p->am_threshold; da.word_penalty = p->word_penalty;
   if (p->flags & ~(SR_SEARCH_GENERAL_KERNEL | SR_SEARCH_SLOT_KERNEL)) return fail(SR_EINVAL, "unknown sr_search_params.flags 0x%x", (unsigned)p->flags);
-  da.force_general = (p->flags & SR_SEARCH_GENERAL_KERNEL) ? 1u : 0u;
-  da.force_slots = (p->flags & SR_SEARCH_SLOT_KERNEL) ? 1u : 0u;
+  const DecodeRoute route = decode_route(da, p->flags & SR_SEARCH_GENERAL_KERNEL, p->flags & SR_SEARCH_SLOT_KERNEL);
+  if (route.big) {  // hypothesis arrays of the utterances in flight
+    uint32_t most = 0;
+    for (const Chunk& ch : chunks) most = std::max(most, ch.u1 - ch.u0);
+    HIP_TRY(c->big_ws.ensure((size_t)most * decode_big_workspace(l->net.n_slots)));
+  }
   {
     bool neg = false;
     if ((rc = srhost::may_go_negative(m, &neg))) return rc;
@@ -1240,17 +1136,8 @@ int sr_recognize_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_searc
   rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); },
       [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
         da.scores = table; da.frame_base = ch.f0; da.utt_first = ch.u0; da.n_utts = ch.u1 - ch.u0;
-        if (l->big && !da.force_general && !da.force_slots && decode_words_applies(da)) {
-          // more than 8192 type-padded positions, but words of at most four: the word-per-lane kernel does not depend on the slot
-          // count; what it flags (a negative emission cost) is redone by the device-memory kernel, which exits at once elsewhere
-          HIP_TRY(launch_decode_words(da, s));
-          da.only_flagged = 1;
-          HIP_TRY(launch_decode_big(da, c->big_ws.p, s));
-          da.only_flagged = 0;
-        } else {
-          HIP_TRY(l->big ? launch_decode_big(da, c->big_ws.p, s) : launch_decode(da, s));
-        }
-        if (m->profiling) m->prof.search_bytes += (8.0 * m->n_states + 4.0 * l->n_slots) * (double)(ch.f1 - ch.f0);
+        HIP_TRY(launch_decode(da, route, c->big_ws.p, s));
+        if (m->profiling) m->prof.search_bytes += (8.0 * m->n_states + 4.0 * l->net.n_slots) * (double)(ch.f1 - ch.f0);
         return SR_OK;
       });
   if (rc) return rc;
@@ -1280,7 +1167,7 @@ int sr_traceback_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const uint16_t
   HIP_TRY(c->out_flags.ensure(U));
   HIP_TRY(hipMemcpyAsync(c->tb_word.p, tb_word, sizeof(uint16_t) * (F + U), hipMemcpyHostToDevice, m->s_gmm));
   HIP_TRY(hipMemcpyAsync(c->tb_bkp.p, tb_bkp, sizeof(uint16_t) * (F + U), hipMemcpyHostToDevice, m->s_gmm));
-  HIP_TRY(launch_traceback(c->d_frame_off.p, U, c->tb_word.p, c->tb_bkp.p, l->silence_idx, l->n_words, c->out_words.p,
+  HIP_TRY(launch_traceback(c->d_frame_off.p, U, c->tb_word.p, c->tb_bkp.p, l->net.silence_word, l->net.n_words, c->out_words.p,
                            c->out_count.p, c->out_flags.p, m->s_gmm));
   HIP_TRY(hipStreamSynchronize(m->s_gmm));
   return gather_words(c, out_words, out_word_off);
@@ -1825,13 +1712,13 @@ int sr_stream_open(sr_model* m, sr_lexicon* l, const sr_search_params* p, uint32
   if (max_streams == 0) return fail(SR_EINVAL, "max_streams must be at least 1");
   if (max_frames == 0) return fail(SR_EINVAL, "max_frames must be at least 1");
   if (max_frames > 65535) return fail(SR_ELIMIT, "max_frames %llu: back pointers are 16 bit like the reference's Book::bkp (max 65535)", (unsigned long long)max_frames);
-  if (l->n_slots > decode_big_max_slots()) return fail(SR_ELIMIT, "%u trellis positions exceed the stream search's limit of %u", l->n_slots, decode_big_max_slots());
+  if (l->net.n_slots > decode_big_max_slots()) return fail(SR_ELIMIT, "%u trellis positions exceed the stream search's limit of %u", l->net.n_slots, decode_big_max_slots());
   sr_stream* s = new sr_stream();
   std::unique_ptr<sr_stream, int (*)(sr_stream*)> own(s, sr_stream_destroy);
   s->model = m; s->lex = l; s->params = *p; s->max_streams = max_streams; s->max_frames = max_frames;
   s->open.assign(max_streams, 0); s->id.assign(max_streams, 0); s->generation.assign(max_streams, 0); s->frames.assign(max_streams, 0);
   const size_t S = max_streams;
-  HIP_TRY(s->ws.ensure(S * decode_big_workspace(l->n_slots)));
+  HIP_TRY(s->ws.ensure(S * decode_big_workspace(l->net.n_slots)));
   HIP_TRY(s->state.ensure(S));
   HIP_TRY(s->tb_score.ensure(S * (max_frames + 1)));
   HIP_TRY(s->tb_word.ensure(S * (max_frames + 1)));
@@ -1897,13 +1784,10 @@ int sr_stream_push(sr_stream* s, uint32_t n, const uint32_t* ids, const float* f
   HIP_TRY(hipEventRecord(m->ev_scored[0], m->s_gmm));
   HIP_TRY(hipStreamWaitEvent(s_search, m->ev_scored[0], 0));
   StreamArgs a{};
-  a.net.n_slots = l->n_slots; a.net.n_words = l->n_words;
-  a.net.slot_info = l->slot_info.p; a.net.slot_word = l->slot_word.p; a.net.word_end_slot = l->word_end_slot.p;
-  a.net.silence_word = l->silence_idx; a.net.silence_state = l->silence_state;
-  a.net.tdp_loop = l->tdp[0]; a.net.tdp_forward = l->tdp[1]; a.net.tdp_skip = l->tdp[2];
+  a.net = l->net;
   a.am_threshold = s->params.am_threshold; a.word_penalty = s->params.word_penalty;
   a.scores = s->scores.p; a.ld = m->ld; a.jobs = s->jobs.p;
-  a.ws = s->ws.p; a.ws_stride = decode_big_workspace(l->n_slots); a.state = s->state.p;
+  a.ws = s->ws.p; a.ws_stride = decode_big_workspace(l->net.n_slots); a.state = s->state.p;
   a.tb_score = s->tb_score.p; a.tb_word = s->tb_word.p; a.tb_bkp = s->tb_bkp.p; a.tb_stride = s->max_frames + 1;
   a.words = s->words.p; a.words_stride = s->max_frames;
   EventPair ep{};
@@ -1914,7 +1798,7 @@ int sr_stream_push(sr_stream* s, uint32_t n, const uint32_t* ids, const float* f
   HIP_TRY(hipStreamSynchronize(m->s_gmm));
   for (const StreamJob& j : jobs) s->frames[j.slot] += j.k;
   if (m->profiling) {
-    m->prof.search_bytes += (8.0 * m->n_states + 4.0 * l->n_slots) * (double)F;
+    m->prof.search_bytes += (8.0 * m->n_states + 4.0 * l->net.n_slots) * (double)F;
     m->prof.frames += F;
   }
   return SR_OK;

@@ -24,9 +24,9 @@
 //      word end (:199-205), publish the word-end minimum and first-index per class for frame t+1.
 //
 // This file holds the GENERAL kernel: slots in reference order, every per-slot decision taken per lane, the
-// sequential boundary replay inline.  Production launches run viterbi_fast.hip's type-sorted kernel first (same
-// results, ~5x fewer instructions per frame) and this one, as decode_kernel<.., REPLAY = true>, only for the
-// utterances the fast kernel hands back (out_flags bit 1: a negative emission cost was seen).
+// sequential boundary replay inline.  Production launches run a fast kernel first (viterbi_words.hip or viterbi_fast.hip:
+// same results, ~5x fewer instructions per frame) and decode_kernel only for the utterances it hands back (out_flags
+// kFlagReplay: a negative emission cost was seen); decode_route, at the end of this file, picks the kernels.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -36,15 +36,7 @@
 
 namespace srgpu {
 
-// slot_info bit layout (built in srgpu_api.cpp: build_decode_net)
-static constexpr uint32_t kSlotPos0 = 1u << 16;      // position 0 of its word
-static constexpr uint32_t kSlotPos1 = 1u << 17;      // position 1
-static constexpr uint32_t kSlotEnd = 1u << 18;       // last position (word end): no in-word expansion
-static constexpr uint32_t kSlotSilState = 1u << 19;  // its state is the silence state: tdp is always `forward`
-static constexpr uint32_t kSlotSilWord = 1u << 20;   // word is the silence word: no word penalty
-static constexpr uint32_t kSlotFirstSil = 1u << 21;  // word's first state is the silence state
-static constexpr uint32_t kSlotSingle = 1u << 22;    // one-position word: owns the virtual dead slot (w, 1)
-
+// slot_info: the kSlot* bits of kernels.h, built by build_decode_net (end of this file)
 static constexpr double kInf = __builtin_huge_val();
 
 struct Merge {  // one target hypothesis being built (Book, Recognizer.hpp:75-89; word/pos are static)
@@ -108,28 +100,55 @@ __device__ inline Merge replay_boundary(const uint32_t* word_end_slot, uint32_t 
   return mg;
 }
 
-// REPLAY = false: the fast variant.  It carries no sequential-replay code; if an entry slot ever meets a
-// negative emission cost it raises out_flags bit 1 for the utterance and the whole workgroup stops.
-// REPLAY = true: launched right after on the same stream; workgroups of unflagged utterances exit at
-// once, flagged utterances are decoded again from frame 1 with the replay inline (exact, slower).
-template <int NT, int SPT, bool REPLAY>
+// B: the block minimum of the frame's new scores and the first minimal word end (score, slot) from every lane's partials.  Its
+// barrier also ends every read of the previous frame's hypotheses.
+template <int NT>
+__device__ __forceinline__ void block_minima(double my_best, double my_we, uint32_t my_we_idx, double* red_best, double* red_we,
+                                             uint32_t* red_idx, double& best, double& we, uint32_t& we_idx) {
+  constexpr uint32_t kWavesPerWg = NT / 64;
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  my_best = wave_min(my_best);
+  wave_min_idx(my_we, my_we_idx);
+  if (lane == 0) { red_best[wave] = my_best; red_we[wave] = my_we; red_idx[wave] = my_we_idx; }
+  __syncthreads();
+  best = red_best[0]; we = red_we[0];
+  we_idx = red_idx[0];
+#pragma unroll
+  for (uint32_t w = 1; w < kWavesPerWg; w++) {
+    const double ob = red_best[w];
+    best = ob < best ? ob : best;
+    const double ow = red_we[w];
+    const uint32_t oi = red_idx[w];
+    if (ow < we || (ow == we && oi < we_idx)) { we = ow; we_idx = oi; }
+  }
+}
+// C: the first slot (in index order) whose boundary candidate equals the minimum's, per (word penalty, tdp) class -- for word end p
+// of score v near the surviving minimum m_we, into the next frame's ef_nxt (reset in phase A)
+__device__ __forceinline__ void publish_word_end(uint32_t* ef_nxt, uint32_t p, double v, double m_we, double wp_word, double tf, double ts) {
+  if (v + 0.0 + tf == m_we + 0.0 + tf) atomicMin(&ef_nxt[0], p);
+  if (v + 0.0 + ts == m_we + 0.0 + ts) atomicMin(&ef_nxt[1], p);
+  if (v + wp_word + tf == m_we + wp_word + tf) atomicMin(&ef_nxt[2], p);
+  if (v + wp_word + ts == m_we + wp_word + ts) atomicMin(&ef_nxt[3], p);
+}
+
+// Launched right after a fast kernel on the same stream (launch_decode): workgroups of unflagged utterances exit at once, flagged
+// utterances are decoded again from frame 1 with the replay inline (exact, slower).  Without a fast kernel: every utterance.
+template <int NT, int SPT>
 __global__ __launch_bounds__(NT) void decode_kernel(DecodeArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr uint32_t kWavesPerWg = NT / 64;
   const uint32_t P = a.net.n_slots;
-  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const uint32_t tid = threadIdx.x;
   constexpr uint32_t PP = NT * SPT;                                // slot arrays are padded to the thread grid
   double* sc = reinterpret_cast<double*>(smem);                    // [PP] hypothesis scores
   double* am_l = sc + PP;                                          // [PP] this frame's emission cost per slot (for position-1 slots' neighbours)
   double* red_best = am_l + PP;                                    // [16]
   double* red_we = red_best + 16;                                  // [16]
   uint32_t* red_idx = reinterpret_cast<uint32_t*>(red_we + 16);    // [16]
-  uint32_t* e_first = red_idx + 16;                                // [2][4] first word-end slot per class, by frame parity
-  uint32_t* bail = e_first + 8;                                    // [1] fast variant: an entry slot needs the replay
+  uint32_t* e_first = red_idx + 16;                                // [2][4] first word-end slot per class, by frame parity; [4] unused
   uint16_t* bk = reinterpret_cast<uint16_t*>(e_first + 12);         // [PP] back pointers (start frame of the word)
 
   const uint32_t u = a.utt_order ? a.utt_order[a.utt_first + blockIdx.x] : a.utt_first + blockIdx.x;
-  if (REPLAY && !a.force_general && !(a.out_flags[u] & kFlagReplay)) return;  // wave-uniform: nothing to redo for this utterance
+  if (a.only_flagged && !(a.out_flags[u] & kFlagReplay)) return;  // wave-uniform: nothing to redo for this utterance
   const uint64_t f0 = a.frame_off[u];
   const uint32_t T = (uint32_t)(a.frame_off[u + 1] - f0);
   const double* row0 = a.scores + (f0 - a.frame_base) * a.ld;
@@ -147,7 +166,6 @@ __global__ __launch_bounds__(NT) void decode_kernel(DecodeArgs a) {
     sc[p] = kInf; bk[p] = 0;
   }
   if (tid < 8) e_first[tid] = 0xFFFFFFFFu;
-  if (tid == 8) *bail = 0;
   __syncthreads();
   // initial hypothesis: word 0, position 0, score 0 (Recognizer.cpp:120)
   const bool init_is_end = a.net.slot_info[0] & kSlotEnd;
@@ -171,8 +189,7 @@ __global__ __launch_bounds__(NT) void decode_kernel(DecodeArgs a) {
   __syncthreads();
   uint32_t slow_taken = 0;
 
-  // one frame; returns true when the fast variant has to hand the utterance to the replay variant
-  auto frame = [&](const uint32_t t, double (&am_issue)[SPT], double (&am_consume)[SPT]) -> bool {
+  auto frame = [&](const uint32_t t, double (&am_issue)[SPT], double (&am_consume)[SPT]) {
     const uint32_t* ef_cur = e_first + 4 * (t & 1);
     uint32_t* ef_nxt = e_first + 4 * ((t + 1) & 1);
     const uint32_t bkp_new = (t - 1) & 0xFFFFu;  // merge_hypothesis(.., t - 1, ..) truncated to uint16 (:154, Recognizer.hpp:79)
@@ -237,9 +254,7 @@ __global__ __launch_bounds__(NT) void decode_kernel(DecodeArgs a) {
       // keep the slots' live ranges apart (otherwise every slot's LDS reads are hoisted to the top: +60 VGPRs)
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (!REPLAY) {
-      if (any_slow) *bail = 1;  // seen by everyone after the reduction barrier below
-    } else if (REPLAY && __any(any_slow)) {  // wave-uniform: some lane has a negative emission cost on an entry slot
+    if (__any(any_slow)) {  // wave-uniform: some lane has a negative emission cost on an entry slot
       slow_taken = 1;
       my_best = kInf;
 #pragma unroll
@@ -277,24 +292,9 @@ __global__ __launch_bounds__(NT) void decode_kernel(DecodeArgs a) {
     if (tid < 4) ef_nxt[tid] = 0xFFFFFFFFu;
 
     // ---- B: block reductions -----------------------------------------------------------------------
-    my_best = wave_min(my_best);
-    wave_min_idx(my_we, my_we_idx);
-    if (lane == 0) { red_best[wave] = my_best; red_we[wave] = my_we; red_idx[wave] = my_we_idx; }
-    __syncthreads();  // also: every read of sc/bk of frame t-1 is done
-    if (!REPLAY && *bail) {  // workgroup-uniform
-      if (tid == 0) { atomicOr(&a.out_flags[u], kFlagReplay); a.out_count[u] = 0; }
-      return true;
-    }
-    double best = red_best[0], we = red_we[0];
-    uint32_t we_idx = red_idx[0];
-#pragma unroll
-    for (uint32_t w = 1; w < kWavesPerWg; w++) {
-      const double ob = red_best[w];
-      best = ob < best ? ob : best;
-      const double ow = red_we[w];
-      const uint32_t oi = red_idx[w];
-      if (ow < we || (ow == we && oi < we_idx)) { we = ow; we_idx = oi; }
-    }
+    double best, we;
+    uint32_t we_idx;
+    block_minima<NT>(my_best, my_we, my_we_idx, red_best, red_we, red_idx, best, we, we_idx);
 
     // ---- C: prune, traceback, publish word-end minimum ------------------------------------------------
     const double limit = best + thr;
@@ -315,54 +315,30 @@ __global__ __launch_bounds__(NT) void decode_kernel(DecodeArgs a) {
         if (p == we_idx) {  // first minimal surviving word end -> traceback[t] (:199-205)
           a.tb_score[tb0 + t] = v; a.tb_word[tb0 + t] = (uint16_t)p; a.tb_bkp[tb0 + t] = (uint16_t)pk[i];  // slot now, word after the loop
         }
-        // first slot (in index order) whose boundary candidate equals the minimum's, per (wp, tdp) class
-        if (v + 0.0 + tf == m_we + 0.0 + tf) atomicMin(&ef_nxt[0], p);
-        if (v + 0.0 + ts == m_we + 0.0 + ts) atomicMin(&ef_nxt[1], p);
-        if (v + wp_word + tf == m_we + wp_word + tf) atomicMin(&ef_nxt[2], p);
-        if (v + wp_word + ts == m_we + wp_word + ts) atomicMin(&ef_nxt[3], p);
+        publish_word_end(ef_nxt, p, v, m_we, wp_word, tf, ts);
       }
     }
     if (!we_alive && tid == 0) { a.tb_score[tb0 + t] = kInf; a.tb_word[tb0 + t] = 0xFFFFu; a.tb_bkp[tb0 + t] = 0; }
     __syncthreads();
-    return false;
   };
 
   for (uint32_t t = 1; t <= T; t += 2) {
-    if (frame(t, am_s1, am_s0)) return;                 // odd frame: refill set 1 (frame t+2), mirror set 0 (frame t+1)
-    if (t + 1 <= T && frame(t + 1, am_s0, am_s1)) return;
+    frame(t, am_s1, am_s0);  // odd frame: refill set 1 (frame t+2), mirror set 0 (frame t+1)
+    if (t + 1 <= T) frame(t + 1, am_s0, am_s1);
   }
 
-  // ---- traceback (Recognizer.cpp:222-231) -------------------------------------------------------------
+  // ---- traceback (Recognizer.cpp:222-231; traceback.h) ------------------------------------------------------
   __threadfence();
   __syncthreads();
-  // entries 1..T hold the winning word-end SLOT (0xFFFF: no surviving word end -> word 0, :118,191): map to words
-  bool bad = false;
-  for (uint32_t t = 1 + tid; t <= T; t += NT) {
-    const uint32_t sl = __hip_atomic_load(&a.tb_word[tb0 + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    uint16_t w = 0;
-    if (sl != 0xFFFFu) { if (sl < P) w = (uint16_t)a.net.slot_word[sl]; else bad = true; }
-    a.tb_word[tb0 + t] = w;
-  }
-  if (bad) atomicOr(&a.out_flags[u], kFlagCorrupt);
-  __threadfence();
-  __syncthreads();
-  if (slow_taken) atomicOr(&a.out_flags[u], kFlagSlowPath);
-  if (tid == 0) {  // guarded walk: traceback.h
-    const uint32_t n = walk_traceback(
-        T, a.net.silence_word, a.net.n_words,
-        [&](uint32_t t) -> uint32_t { return __hip_atomic_load(&a.tb_word[tb0 + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); },
-        [&](uint32_t t) -> uint32_t { return __hip_atomic_load(&a.tb_bkp[tb0 + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); },
-        a.out_words + f0, T);
-    if (n == kTbCorrupt) atomicOr(&a.out_flags[u], kFlagCorrupt);
-    a.out_count[u] = n == kTbCorrupt ? 0u : n;
-  }
+  traceback_slots_to_words<NT>(a, u, tb0, T, a.net.slot_word, P);
+  traceback_walk(a, u, f0, tb0, T, slow_taken);
 }
 
 // ---- the same search for lexicons whose hypothesis arrays do not fit the LDS (more than 8192 slots) -----------------------
 // Scores and back pointers of the two frames in flight live in a per-workgroup global workspace (20 bytes per slot: L2
 // resident), emission costs are gathered where they are used, and a thread walks its slots in a loop instead of keeping them in
-// registers.  Phases, merge order and the exactness argument are decode_kernel's (REPLAY = true: the sequential boundary
-// replay is inline, per lane); slot ids stay 16 bit in the traceback, so P <= 65534.  A capacity path: measured 12.3 ms for
+// registers.  Phases, merge order and the exactness argument are decode_kernel's (the sequential boundary replay is inline,
+// per lane); slot ids stay 16 bit in the traceback, so P <= 65534.  A capacity path: measured 12.3 ms for
 // 256 utterances at 9001 slots against 5.3 ms at 8000 slots in the type-sorted LDS kernel (2 x per slot).
 //
 // big_frame is one frame t of that search, shared by decode_big_kernel (a whole utterance) and decode_stream_kernel (k frames
@@ -374,9 +350,8 @@ __device__ __forceinline__ void big_frame(const DecodeNet& net, double wp_word, 
                                           const double* sc, const uint16_t* bk, double* scn, uint16_t* bkn, const uint32_t* ef_cur,
                                           uint32_t* ef_nxt, double* red_best, double* red_we, uint32_t* red_idx, double& m_we,
                                           uint32_t& slow_taken, Record record) {
-  constexpr uint32_t kWavesPerWg = NT / 64;
   const uint32_t P = net.n_slots;
-  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const uint32_t tid = threadIdx.x;
   const double tl = net.tdp_loop, tf = net.tdp_forward, ts = net.tdp_skip;
   const uint32_t bkp_new = (t - 1) & 0xFFFFu;
   // ---- A: the new hypotheses, unpruned, into the other buffer ---------------------------------------------------
@@ -425,20 +400,9 @@ __device__ __forceinline__ void big_frame(const DecodeNet& net, double wp_word, 
   }
   if (tid < 4) ef_nxt[tid] = 0xFFFFFFFFu;
   // ---- B ---------------------------------------------------------------------------------------------------------
-  my_best = wave_min(my_best);
-  wave_min_idx(my_we, my_we_idx);
-  if (lane == 0) { red_best[wave] = my_best; red_we[wave] = my_we; red_idx[wave] = my_we_idx; }
-  __syncthreads();
-  double best = red_best[0], we = red_we[0];
-  uint32_t we_idx = red_idx[0];
-#pragma unroll
-  for (uint32_t w = 1; w < kWavesPerWg; w++) {
-    const double ob = red_best[w];
-    best = ob < best ? ob : best;
-    const double ow = red_we[w];
-    const uint32_t oi = red_idx[w];
-    if (ow < we || (ow == we && oi < we_idx)) { we = ow; we_idx = oi; }
-  }
+  double best, we;
+  uint32_t we_idx;
+  block_minima<NT>(my_best, my_we, my_we_idx, red_best, red_we, red_idx, best, we, we_idx);
   // ---- C: prune, traceback, publish the word-end minimum -----------------------------------------------------------
   const double limit = best + thr;
   const bool we_alive = !(we > limit) && we != kInf;
@@ -449,10 +413,7 @@ __device__ __forceinline__ void big_frame(const DecodeNet& net, double wp_word, 
     if (v > limit) { scn[p] = kInf; continue; }  // :194-196
     if ((net.slot_info[p] & kSlotEnd) && we_alive && v <= near) {
       if (p == we_idx) record(v, p, (uint32_t)bkn[p]);
-      if (v + 0.0 + tf == m_we + 0.0 + tf) atomicMin(&ef_nxt[0], p);
-      if (v + 0.0 + ts == m_we + 0.0 + ts) atomicMin(&ef_nxt[1], p);
-      if (v + wp_word + tf == m_we + wp_word + tf) atomicMin(&ef_nxt[2], p);
-      if (v + wp_word + ts == m_we + wp_word + ts) atomicMin(&ef_nxt[3], p);
+      publish_word_end(ef_nxt, p, v, m_we, wp_word, tf, ts);
     }
   }
   if (!we_alive && tid == 0) record(kInf, 0xFFFFu, 0u);
@@ -467,7 +428,7 @@ __global__ __launch_bounds__(NT) void decode_big_kernel(DecodeArgs a, unsigned c
   const uint32_t P = a.net.n_slots;
   const uint32_t tid = threadIdx.x;
   const uint32_t u = a.utt_order ? a.utt_order[a.utt_first + blockIdx.x] : a.utt_first + blockIdx.x;
-  if (a.only_flagged && !(a.out_flags[u] & kFlagReplay)) return;  // workgroup-uniform: replay of the word-per-lane kernel, nothing to redo
+  if (a.only_flagged && !(a.out_flags[u] & kFlagReplay)) return;  // workgroup-uniform: nothing to redo for this utterance
   const uint64_t f0 = a.frame_off[u];
   const uint32_t T = (uint32_t)(a.frame_off[u + 1] - f0);
   const double* row0 = a.scores + (f0 - a.frame_base) * a.ld;
@@ -498,29 +459,11 @@ __global__ __launch_bounds__(NT) void decode_big_kernel(DecodeArgs a, unsigned c
                   });
   }
 
-  // ---- traceback (Recognizer.cpp:222-231) -------------------------------------------------------------
+  // ---- traceback (Recognizer.cpp:222-231; traceback.h) ------------------------------------------------------
   __threadfence();
   __syncthreads();
-  bool bad = false;
-  for (uint32_t t = 1 + tid; t <= T; t += NT) {
-    const uint32_t sl = __hip_atomic_load(&a.tb_word[tb0 + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    uint16_t w = 0;
-    if (sl != 0xFFFFu) { if (sl < P) w = (uint16_t)a.net.slot_word[sl]; else bad = true; }
-    a.tb_word[tb0 + t] = w;
-  }
-  if (bad) atomicOr(&a.out_flags[u], kFlagCorrupt);
-  __threadfence();
-  __syncthreads();
-  if (slow_taken) atomicOr(&a.out_flags[u], kFlagSlowPath);
-  if (tid == 0) {  // guarded walk: traceback.h
-    const uint32_t n = walk_traceback(
-        T, a.net.silence_word, a.net.n_words,
-        [&](uint32_t t) -> uint32_t { return __hip_atomic_load(&a.tb_word[tb0 + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); },
-        [&](uint32_t t) -> uint32_t { return __hip_atomic_load(&a.tb_bkp[tb0 + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); },
-        a.out_words + f0, T);
-    if (n == kTbCorrupt) atomicOr(&a.out_flags[u], kFlagCorrupt);
-    a.out_count[u] = n == kTbCorrupt ? 0u : n;
-  }
+  traceback_slots_to_words<NT>(a, u, tb0, T, a.net.slot_word, P);
+  traceback_walk(a, u, f0, tb0, T, slow_taken);
 }
 
 // ---- streaming (sr_stream_push): k more frames of each of n open utterances --------------------------------------------
@@ -597,8 +540,7 @@ __global__ __launch_bounds__(NT) void decode_stream_kernel(StreamArgs a) {
 
 uint32_t decode_big_max_slots() { return 65534; }  // slot ids are 16 bit in the traceback, 0xFFFF = no surviving word end
 size_t decode_big_workspace(uint32_t n_slots) { return (((size_t)n_slots * 20) + 255) & ~(size_t)255; }  // per utterance in flight
-hipError_t launch_decode_big(const DecodeArgs& a, unsigned char* ws, hipStream_t stream) {
-  if (a.n_utts == 0) return hipSuccess;
+static hipError_t launch_decode_big(const DecodeArgs& a, unsigned char* ws, hipStream_t stream) {
   if (a.net.n_slots > decode_big_max_slots() || !ws) return hipErrorInvalidValue;
   hipLaunchKernelGGL((decode_big_kernel<1024>), dim3(a.n_utts), dim3(1024), 0, stream, a, ws, decode_big_workspace(a.net.n_slots));
   return hipGetLastError();
@@ -614,22 +556,15 @@ uint32_t decode_max_slots() { return 8192; }
 
 static size_t decode_smem(uint32_t PP) { return (size_t)PP * 16 + 16 * 8 * 2 + 16 * 4 + 12 * 4 + (size_t)PP * 2 + 16; }
 
-hipError_t launch_decode(const DecodeArgs& a, hipStream_t stream) {
-  if (a.n_utts == 0) return hipSuccess;
+static hipError_t launch_decode_lds(const DecodeArgs& a, hipStream_t stream) {
   const uint32_t P = a.net.n_slots;
   const dim3 grid(a.n_utts);
-  // a fast variant first (viterbi_words.hip for short-word lexica, else viterbi_fast.hip); then the replay variant, whose workgroups exit at once unless the fast
-  // one flagged their utterance (negative emission cost)
-  if (!a.force_general) {
-    hipError_t e = (!a.force_slots && decode_words_applies(a)) ? launch_decode_words(a, stream) : launch_decode_fast(a, stream);
-    if (e != hipSuccess) return e;
-  }
 #define SR_LAUNCH(NT, SPT)                                                                                   \
   do {                                                                                                       \
     const size_t smem = decode_smem((NT) * (SPT));                                                           \
-    hipError_t e = hipFuncSetAttribute((const void*)decode_kernel<NT, SPT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
+    hipError_t e = hipFuncSetAttribute((const void*)decode_kernel<NT, SPT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
     if (e != hipSuccess) return e;                                                                           \
-    hipLaunchKernelGGL((decode_kernel<NT, SPT, true>), grid, dim3(NT), smem, stream, a);                     \
+    hipLaunchKernelGGL((decode_kernel<NT, SPT>), grid, dim3(NT), smem, stream, a);                           \
     return hipGetLastError();                                                                                \
   } while (0)
   if (P <= 64) SR_LAUNCH(64, 1);
@@ -640,6 +575,59 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t stream) {
   if (P <= 8192) SR_LAUNCH(1024, 8);
 #undef SR_LAUNCH
   return hipErrorInvalidValue;
+}
+
+// The one place that decides which kernels search a lexicon (kernels.h: DecodeRoute):
+//   flags      word net applies   first kernel   replay kernel (decode_kernel; decode_big_kernel without a FastNet)
+//   GENERAL    -                  none           every utterance
+//   SLOT       -                  slots          flagged ones  (a big lexicon: none, every utterance)
+//   none       yes                words          flagged ones
+//   none       no                 slots          flagged ones  (a big lexicon: none, every utterance)
+DecodeRoute decode_route(const DecodeArgs& a, bool general, bool slots) {
+  const bool big = a.fast.n_slots == 0;
+  DecodeFirst first = DecodeFirst::kNone;
+  if (!general && !slots && decode_words_applies(a)) first = DecodeFirst::kWords;
+  else if (!general && !big) first = DecodeFirst::kSlots;
+  return DecodeRoute{first, big};
+}
+
+hipError_t launch_decode(DecodeArgs a, const DecodeRoute& r, unsigned char* big_ws, hipStream_t stream) {
+  if (a.n_utts == 0) return hipSuccess;
+  if (r.first != DecodeFirst::kNone) {
+    hipError_t e = r.first == DecodeFirst::kWords ? launch_decode_words(a, stream) : launch_decode_fast(a, stream);
+    if (e != hipSuccess) return e;
+  }
+  // the replay kernel, whose workgroups exit at once unless the fast one flagged their utterance (negative emission cost)
+  a.only_flagged = r.first != DecodeFirst::kNone ? 1u : 0u;
+  return r.big ? launch_decode_big(a, big_ws, stream) : launch_decode_lds(a, stream);
+}
+
+DecodeNet build_decode_net(uint32_t n_words, const uint32_t* word_off, const uint16_t* automaton, uint32_t silence_word,
+                           uint32_t silence_state, const double tdp[3], std::vector<uint32_t>& slot_info,
+                           std::vector<uint32_t>& slot_word, std::vector<uint32_t>& word_end_slot) {
+  const uint32_t P = word_off[n_words];
+  slot_info.assign(P, 0); slot_word.assign(P, 0); word_end_slot.assign(n_words, 0);
+  for (uint32_t w = 0; w < n_words; w++) {
+    const uint32_t b = word_off[w], n = word_off[w + 1] - b;
+    for (uint32_t k = 0; k < n; k++) {
+      const uint32_t st = automaton[b + k];
+      uint32_t f = st;
+      if (k == 0) f |= kSlotPos0;
+      if (k == 1) f |= kSlotPos1;
+      if (k == n - 1) f |= kSlotEnd;
+      if (st == silence_state) f |= kSlotSilState;
+      if (w == silence_word) f |= kSlotSilWord;
+      if (automaton[b] == silence_state) f |= kSlotFirstSil;
+      if (n == 1) f |= kSlotSingle;
+      slot_info[b + k] = f;
+      slot_word[b + k] = w;
+    }
+    word_end_slot[w] = b + n - 1;
+  }
+  DecodeNet net{};
+  net.n_slots = P; net.n_words = n_words; net.silence_word = silence_word; net.silence_state = silence_state;
+  net.tdp_loop = tdp[0]; net.tdp_forward = tdp[1]; net.tdp_skip = tdp[2];
+  return net;
 }
 
 }  // namespace srgpu

@@ -2,7 +2,7 @@
 // sietill/Recognizer.cpp:103-232); see viterbi_decode.hip for the algorithm, the exactness argument and the
 // general (replay) kernel.  Same results bit for bit; what differs is the work layout:
 //
-//   * slots are SORTED BY TYPE on the host (srgpu_api.cpp: build_fast_net) -- entry position 0 / entry position 1
+//   * slots are SORTED BY TYPE on the host (build_fast_net, end of this file) -- entry position 0 / entry position 1
 //     / middle / word end, times the silence flags that select the transition penalties and the word penalty --
 //     and every type is padded to whole waves.  A wave therefore handles one type: each per-slot decision of
 //     the general kernel becomes a wave-uniform branch, a slot evaluates only the candidates its type has, and
@@ -10,7 +10,7 @@
 //   * it assumes every emission cost of the frame is >= 0, which makes the reference's pre-AM early-out
 //     (Recognizer.cpp:143,173) inert so a slot is the first minimum over its candidates in source order; an
 //     utterance in which any emission cost was negative (or not a number) is flagged after its last frame
-//     (out_flags kFlagReplay, no words reported) and decode_kernel<.., REPLAY=true> redoes it exactly.
+//     (out_flags kFlagReplay, no words reported) and decode_kernel (launch_decode) redoes it exactly.
 //   * reductions use DPP row operations and LDS ds_min_f64 cells; the frame's score row is staged in LDS by LDS-DMA.
 //
 // Ties are broken by ORIGINAL slot index (the reference's visiting order), which every slot carries along.
@@ -397,35 +397,14 @@ __global__ __launch_bounds__(NT) void decode_fast_kernel(DecodeArgs a) {
   }
   if (T > 0) flush_pending(T);
 
-  // the fast path's premise failed somewhere (a negative or NaN emission cost): hand the utterance to the replay variant
+  // the fast path's premise failed somewhere (a negative or NaN emission cost): hand the utterance to the replay kernel
   if (bad) *s_bad = 1;
   __threadfence();
   __syncthreads();
-  if (*s_bad) {  // workgroup-uniform
-    if (tid == 0) { atomicOr(&a.out_flags[u], kFlagReplay); a.out_count[u] = 0; }
-    return;
-  }
-
-  // ---- traceback (Recognizer.cpp:222-231; guarded walk: traceback.h) -------------------------------------------
-  bool corrupt = false;
-  for (uint32_t t = 1 + tid; t <= T; t += NT) {  // winning slot -> word
-    const uint32_t sl = __hip_atomic_load(&a.tb_word[tb0 + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    uint16_t w = 0;  // 0xFFFF: no surviving word end -> Book(inf, 0, 0), :118,191
-    if (sl != 0xFFFFu) { if (sl < net.n_slots) w = (uint16_t)net.word[sl]; else corrupt = true; }
-    a.tb_word[tb0 + t] = w;
-  }
-  if (corrupt) atomicOr(&a.out_flags[u], kFlagCorrupt);
-  __threadfence();
-  __syncthreads();
-  if (tid == 0) {
-    const uint32_t n = walk_traceback(
-        T, a.net.silence_word, a.net.n_words,
-        [&](uint32_t t) -> uint32_t { return __hip_atomic_load(&a.tb_word[tb0 + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); },
-        [&](uint32_t t) -> uint32_t { return __hip_atomic_load(&a.tb_bkp[tb0 + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); },
-        a.out_words + f0, T);
-    if (n == kTbCorrupt) atomicOr(&a.out_flags[u], kFlagCorrupt);
-    a.out_count[u] = n == kTbCorrupt ? 0u : n;
-  }
+  if (*s_bad) return hand_off_to_replay(a, u);  // workgroup-uniform
+  // ---- traceback (Recognizer.cpp:222-231; traceback.h): winning slot -> word, the guarded walk ------------------
+  traceback_slots_to_words<NT>(a, u, tb0, T, net.word, net.n_slots);
+  traceback_walk(a, u, f0, tb0, T, false);
 }
 
 static size_t fast_smem(uint32_t PP, uint32_t ld, bool rows) {
@@ -467,6 +446,49 @@ hipError_t launch_decode_fast(const DecodeArgs& a, hipStream_t stream) {
   if (P <= 8192) SR_LAUNCH(1024, 8);
 #undef SR_LAUNCH
   return hipErrorInvalidValue;
+}
+
+FastNet build_fast_net(const std::vector<uint32_t>& slot_info, const std::vector<uint32_t>& slot_word, const uint32_t* word_off,
+                       std::vector<uint32_t>& state, std::vector<uint32_t>& pred, std::vector<uint32_t>& orig,
+                       std::vector<uint32_t>& chunk_type, std::vector<uint32_t>& word) {
+  const uint32_t P = (uint32_t)slot_info.size();
+  std::vector<uint32_t> key(P), new_id(P);  // sort key: the chunk type word
+  for (uint32_t p = 0; p < P; p++) {
+    const uint32_t f = slot_info[p];
+    const bool pos0 = f & kSlotPos0, pos1 = f & kSlotPos1, end = f & kSlotEnd;
+    const uint32_t kind = pos0 ? (end ? kE0S : kE0) : pos1 ? (end ? kE1E : kE1) : (end ? kME : kM);
+    key[p] = kind | ((f & kSlotSilState) ? kTSilState : 0u) | ((f & kSlotSilWord) ? kTSilWord : 0u) | ((f & kSlotFirstSil) ? kTFirstSil : 0u);
+  }
+  orig.clear(); chunk_type.clear();
+  for (uint32_t k = 0; k < 64; k++) {  // by key, each padded to whole chunks of 64
+    bool any = false;
+    for (uint32_t p = 0; p < P; p++) {
+      if (key[p] != k) continue;
+      any = true;
+      new_id[p] = (uint32_t)orig.size();
+      orig.push_back(p);  // completed below
+    }
+    if (!any) continue;
+    while (orig.size() % 64) orig.push_back(0xFFFFFFFFu);
+    chunk_type.resize(orig.size() / 64, k);
+  }
+  FastNet net{};
+  net.init_slot = new_id[0];
+  net.init_is_end = (slot_info[0] & kSlotEnd) ? 1u : 0u;
+  // beyond what the LDS holds (type padding included) the search runs from a global workspace (decode_big_kernel): no fast net
+  if (orig.size() > decode_max_slots()) { orig.clear(); chunk_type.clear(); }
+  const uint32_t n = net.n_slots = (uint32_t)orig.size();
+  state.assign(n, 0); pred.assign(n, 0); word.assign(n, 0);
+  for (uint32_t q = 0; q < n; q++) {
+    const uint32_t p = orig[q];
+    if (p == 0xFFFFFFFFu) { pred[q] = q | (q << 16); continue; }
+    const uint32_t w = slot_word[p], base = word_off[w], k = p - base;
+    state[q] = slot_info[p] & 0xFFFFu;
+    word[q] = w;
+    pred[q] = (k >= 1 ? new_id[p - 1] : q) | ((k >= 2 ? new_id[p - 2] : q) << 16);
+    orig[q] = p | (base << 16);
+  }
+  return net;
 }
 
 }  // namespace srgpu

@@ -23,8 +23,8 @@
 // reset one barrier before their next use), which is what lets a frame do with one barrier.
 //
 // Same premise as the slot kernel: every emission cost of the utterance is >= 0 (the reference's pre-AM early-out,
-// Recognizer.cpp:143,173, is inert then); an utterance that breaks it is flagged kFlagReplay and redone by
-// decode_kernel<.., REPLAY = true>.  Results are bit-identical to the slot kernel, the general kernel and the oracle; tie
+// Recognizer.cpp:143,173, is inert then); an utterance that breaks it is flagged kFlagReplay and redone by the replay kernel
+// (launch_decode).  Results are bit-identical to the slot kernel, the general kernel and the oracle; tie
 // order is the reference's hypothesis index word * max_pos + pos, which orders like word_off[word] + pos.
 //
 // NEG = true (round 5): the same kernel WITHOUT that premise, for models whose emission costs can be negative (the host decides from
@@ -58,7 +58,7 @@ static constexpr uint32_t kWSilWord = 8u, kWFirstSil = 16u, kWSilStates = 0xF00u
 
 static constexpr uint32_t kWordsCellBytes = 1024;  // minima and first-index cells; the row buffers follow, 1 KB aligned
 
-// Lanes take their words from an ORDER the host chose (srgpu_api.cpp: sr_lexicon_create).  A (wave, k) GROUP of 64 word slots
+// Lanes take their words from an ORDER the host chose (build_word_net, end of this file).  A (wave, k) GROUP of 64 word slots
 // holds words of one kind -- the host pads every kind to whole groups -- and runs that kind's code:
 //   plain    exactly L positions, not the silence word, no silence state: every transition penalty a scalar, the role of
 //            every position known at compile time -- a third of the general path's instructions.  In SURVEY 8d's lexica
@@ -145,8 +145,8 @@ __global__ __launch_bounds__(MAXT) void decode_words_kernel(DecodeArgs a) {
     const uint32_t flags = info[k] & (7u | kWSilWord | kWFirstSil | kWSilStates);
     kind[k] = real[k] == 0 ? kGSkip : __all(!in || flags == (uint32_t)L) ? kGPlain : __all(!in || (info[k] & 7u) == 1u) ? kGSingle : kGGeneral;
   }
-  // The host puts a general group into slot row k = 0 of a wave of its own (srgpu_api.cpp), so only k = 0 carries the registers of
-  // a fourth position and the general code.  (A general group anywhere else -- not something sr_lexicon_create produces -- sends the
+  // The host puts a general group into slot row k = 0 of a wave of its own (build_word_net), so only k = 0 carries the registers of
+  // a fourth position and the general code.  (A general group anywhere else -- not something build_word_net produces -- sends the
   // utterance to the replay kernel.)
   bool misplaced = false;
 #pragma unroll
@@ -550,25 +550,13 @@ __global__ __launch_bounds__(MAXT) void decode_words_kernel(DecodeArgs a) {
   __syncthreads();
   if (T > 0) flush_pending(T);
 
-  // the premise failed somewhere (a negative or NaN emission cost): hand the utterance to the replay variant
+  // the premise failed somewhere (a negative or NaN emission cost): hand the utterance to the replay kernel
   if (bad) *s_bad = 1;
   __threadfence();
   __syncthreads();
-  if (*s_bad) {  // workgroup-uniform
-    if (tid == 0) { atomicOr(&a.out_flags[u], kFlagReplay); a.out_count[u] = 0; }
-    return;
-  }
-
-  // ---- traceback (Recognizer.cpp:222-231; guarded walk: traceback.h) ---------------------------------------------------
-  if (tid == 0) {
-    const uint32_t n = walk_traceback(
-        T, a.net.silence_word, a.net.n_words,
-        [&](uint32_t t) -> uint32_t { return __hip_atomic_load(&a.tb_word[tb0 + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); },
-        [&](uint32_t t) -> uint32_t { return __hip_atomic_load(&a.tb_bkp[tb0 + t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); },
-        a.out_words + f0, T);
-    if (n == kTbCorrupt) atomicOr(&a.out_flags[u], kFlagCorrupt);
-    a.out_count[u] = n == kTbCorrupt ? 0u : n;
-  }
+  if (*s_bad) return hand_off_to_replay(a, u);  // workgroup-uniform
+  // ---- traceback (Recognizer.cpp:222-231; the entries hold words already: the guarded walk, traceback.h) ---------------------
+  traceback_walk(a, u, f0, tb0, T, false);
 }
 
 static size_t words_smem(uint32_t ld, uint32_t n_words = 0, bool neg = false) {
@@ -603,6 +591,63 @@ hipError_t launch_decode_words(const DecodeArgs& a, hipStream_t stream) {
 #undef SR_WORDS
 #undef SR_WORDS_G
 #undef SR_WORDS_N
+}
+
+WordNet build_word_net(uint32_t n_words, const uint32_t* word_off, const uint16_t* automaton, uint32_t silence_word,
+                       uint32_t silence_state, std::vector<uint32_t>& info, std::vector<uint2>& states, std::vector<uint32_t>& order) {
+  WordNet net{};
+  info.clear(); states.clear(); order.clear();
+  net.init_is_end = word_off[1] - word_off[0] == 1 ? 1u : 0u;
+  for (uint32_t w = 0; w < n_words; w++)
+    if (word_off[w + 1] - word_off[w] > 4) return net;  // every word at most four positions
+  if (n_words > decode_words_max_words()) return net;
+  info.resize(n_words); states.resize(n_words);
+  uint32_t hist[5] = {0, 0, 0, 0, 0};
+  for (uint32_t w = 0; w < n_words; w++) {
+    const uint32_t b = word_off[w], n = word_off[w + 1] - b;
+    uint32_t f = n, st[4] = {0, 0, 0, 0};
+    if (w == silence_word) f |= kWSilWord;
+    if (automaton[b] == silence_state) f |= kWFirstSil;
+    for (uint32_t k = 0; k < n; k++) {
+      st[k] = automaton[b + k];
+      if (st[k] == silence_state) f |= 1u << (8 + k);  // kWSilStates
+    }
+    info[w] = f;
+    states[w] = make_uint2(st[0] | (st[1] << 16), st[2] | (st[3] << 16));
+    if (f == n) hist[n]++;  // no flags
+  }
+  // plain words: the commonest flag-free length of 2..4 positions.  Every kind fills whole groups of 64 lane slots; slot
+  // s = tid + k * nt belongs to group s / 64 = k * n_waves + wave.  Plain and single groups are dealt to the first waves, nw
+  // per wave; a general group -- three times the instructions of a plain one -- gets a wave of its own (its other groups
+  // stay empty), because a frame lasts as long as its heaviest wave.
+  uint32_t plain_len = 3;
+  for (uint32_t n = 2; n <= 4; n++) if (hist[n] > hist[plain_len]) plain_len = n;
+  std::vector<uint32_t> kinds[3];  // plain, single, general
+  for (uint32_t w = 0; w < n_words; w++)
+    kinds[info[w] == plain_len ? 0 : (info[w] & 7u) == 1u ? 1 : 2].push_back(w);
+  const uint32_t g_plain = ((uint32_t)kinds[0].size() + 63) / 64, g_single = ((uint32_t)kinds[1].size() + 63) / 64,
+                 g_gen = ((uint32_t)kinds[2].size() + 63) / 64;
+  // words per lane: the fewest that leave a workgroup of at most 8 waves -- two of them share a CU then (128 registers per
+  // lane each), and while one waits at its barrier the other computes --, else the fewest that fit 16 waves
+  auto waves_for = [&](uint32_t nw) { return (g_plain + g_single + nw - 1) / nw + g_gen; };
+  uint32_t nw = 1;
+  for (; nw <= 3 && waves_for(nw) > 8; nw++) {}
+  if (nw > 3) for (nw = 1; nw <= 3 && waves_for(nw) > 16; nw++) {}
+  if (nw > 3) {  // more groups than a workgroup has room for: the slot-per-lane kernel
+    info.clear(); states.clear();
+    return net;
+  }
+  const uint32_t waves = waves_for(nw), nt = waves * 64;
+  order.assign((size_t)nw * nt, 0xFFFFFFFFu);
+  auto put_group = [&](uint32_t wave, uint32_t k, const std::vector<uint32_t>& words, uint32_t g) {
+    for (uint32_t i = 0; i < 64 && (size_t)g * 64 + i < words.size(); i++) order[(size_t)k * nt + wave * 64 + i] = words[(size_t)g * 64 + i];
+  };
+  uint32_t seq = 0;  // plain groups, then single groups: wave seq / nw, slot row seq % nw
+  for (uint32_t g = 0; g < g_plain; g++, seq++) put_group(seq / nw, seq % nw, kinds[0], g);
+  for (uint32_t g = 0; g < g_single; g++, seq++) put_group(seq / nw, seq % nw, kinds[1], g);
+  for (uint32_t g = 0; g < g_gen; g++) put_group(waves - g_gen + g, 0, kinds[2], g);
+  net.nw = nw; net.nt = nt; net.plain_len = plain_len; net.has_general = g_gen ? 1u : 0u;
+  return net;
 }
 
 }  // namespace srgpu

@@ -61,7 +61,8 @@ def test_big_short_word_lexicon_runs_the_word_per_lane_kernel(tight, tmp_path, o
     """about 2 700 .. 3 072 three-state words are more than 8 192 type-padded positions, so the lexicon is `big`, but the
     word-per-lane kernel does not depend on the slot count: it runs first, and what it flags (negative emission costs: the `tight`
     model) is redone by decode_big_kernel, which exits at once for every other utterance.  Words and traceback against the oracle
-    and against decode_big_kernel on everything (SR_SEARCH_GENERAL_KERNEL)."""
+    and against decode_big_kernel on everything (SR_SEARCH_GENERAL_KERNEL, and SR_SEARCH_SLOT_KERNEL, which takes the same route
+    on a big lexicon)."""
     dim = 12
     lex = synth.make_lexicon(2900, 3, 1)  # 1 + 3 * 2900 = 8701 positions
     word_off, automaton, sil_state = lex.flatten()
@@ -85,6 +86,10 @@ def test_big_short_word_lexicon_runs_the_word_per_lane_kernel(tight, tmp_path, o
         gw, goff, (gs, gtw, gtb) = corpus.recognize(lexh, beam, wp, capi.GMM_EXACT, traceback=True, general_kernel=True)
         assert np.array_equal(words, gw) and np.array_equal(woff, goff) and np.array_equal(tbw, gtw) and np.array_equal(tbb, gtb)
         assert np.array_equal(tbs.view(np.uint64), gs.view(np.uint64))
+        # SR_SEARCH_SLOT_KERNEL on a big lexicon: no type-sorted net, so decode_big_kernel on every utterance
+        sw, soff, (ss, stw, stb) = corpus.recognize(lexh, beam, wp, capi.GMM_EXACT, traceback=True, slot_kernel=True)
+        assert np.array_equal(sw, gw) and np.array_equal(soff, goff) and np.array_equal(stw, gtw) and np.array_equal(stb, gtb)
+        assert np.array_equal(ss.view(np.uint64), gs.view(np.uint64))
         n_items = 0
         for u in range(len(utts)):
             w, (os_, ow, ob) = o.decode(utts[u], traceback=True)
