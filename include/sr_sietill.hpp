@@ -720,4 +720,80 @@ class LinearSearch {
   sr_bigram* net_ = nullptr;
 };
 
+// ---- streaming LinearSearch: initialize / processFrame / getResult (LinearSearch.cc:489-520) over many concurrent utterances ------
+// (sr_bigram_stream_*, srgpu.h).  begin() is initialize(); push() hands over new frames of one or several open utterances (one
+// scoring and one search launch per call: processFrame for each of their frames); getResult() is the traceback after the frames
+// pushed so far; end() returns it for the whole utterance -- what LinearSearch::recognize returns for it -- and frees the id.
+// Errors are thrown as std::runtime_error with sr_last_error()'s text.
+class StreamingLinearSearch {
+ public:
+  typedef LinearSearch::TracebackItem TracebackItem;
+  typedef LinearSearch::Traceback Traceback;
+
+  StreamingLinearSearch(MixtureModel& scorer, std::vector<std::vector<uint16_t> > const& linear_lexicon, uint32_t silence,
+                        std::vector<float> const& lm, const float tdp[2][4], float acoustic_pruning = std::numeric_limits<float>::max(),
+                        float lm_pruning = std::numeric_limits<float>::max(), uint32_t max_streams = 64, uint64_t max_frames = 65535)
+      : max_frames_(max_frames) {
+    std::vector<uint32_t> word_off(1, 0);
+    std::vector<uint16_t> mixtures;
+    for (size_t w = 0; w < linear_lexicon.size(); w++) {
+      mixtures.insert(mixtures.end(), linear_lexicon[w].begin(), linear_lexicon[w].end());
+      word_off.push_back((uint32_t)mixtures.size());
+    }
+    if (lm.size() != linear_lexicon.size() * linear_lexicon.size()) throw std::runtime_error("StreamingLinearSearch: lm must be W x W");
+    check(sr_bigram_create(scorer.handle(), (uint32_t)linear_lexicon.size(), word_off.data(), mixtures.data(), silence, lm.data(),
+                           &tdp[0][0], &net_));
+    sr_bigram_params p = sr_bigram_params();  // zeroed, then field by field
+    p.acoustic_pruning = acoustic_pruning;
+    p.lm_pruning = lm_pruning;
+    p.gmm_kernel = scorer.gmm_kernel;
+    const int rc = sr_bigram_stream_open(scorer.handle(), net_, &p, max_streams, max_frames, &s_);
+    if (rc != SR_OK) {
+      const std::string msg = sr_last_error();
+      sr_bigram_destroy(net_);
+      throw std::runtime_error(msg);
+    }
+  }
+  ~StreamingLinearSearch() {
+    sr_bigram_stream_destroy(s_);  // before its search net
+    sr_bigram_destroy(net_);
+  }
+  StreamingLinearSearch(StreamingLinearSearch const&) = delete;
+  StreamingLinearSearch& operator=(StreamingLinearSearch const&) = delete;
+
+  uint32_t begin() {
+    uint32_t id = 0;
+    check(sr_bigram_stream_begin(s_, &id));
+    return id;
+  }
+  // n_frames new frames ([n_frames x dimension] float32) of one utterance
+  void push(uint32_t id, const float* frames, size_t n_frames) {
+    const uint64_t off[2] = {0, n_frames};
+    check(sr_bigram_stream_push(s_, 1, &id, frames, off));
+  }
+  // new frames of several utterances back to back: ids[i] owns rows [frame_off[i], frame_off[i+1])
+  void push(std::vector<uint32_t> const& ids, const float* frames, std::vector<uint64_t> const& frame_off) {
+    if (frame_off.size() != ids.size() + 1) throw std::runtime_error("StreamingLinearSearch::push: frame_off needs ids.size() + 1 entries");
+    check(sr_bigram_stream_push(s_, (uint32_t)ids.size(), ids.data(), frames, frame_off.data()));
+  }
+  void getResult(uint32_t id, Traceback& result) { items(id, result, false); }
+  void end(uint32_t id, Traceback& result) { items(id, result, true); }
+
+ private:
+  void items(uint32_t id, Traceback& result, bool final_) {
+    std::vector<uint32_t> words(max_frames_ + 1), times(max_frames_ + 1);
+    std::vector<float> scores(max_frames_ + 1);
+    uint32_t n = 0;
+    if (final_)
+      check(sr_bigram_stream_end(s_, id, words.data(), scores.data(), times.data(), (uint32_t)words.size(), &n));
+    else
+      check(sr_bigram_stream_partial(s_, id, words.data(), scores.data(), times.data(), (uint32_t)words.size(), &n, nullptr));
+    result.clear();
+    for (uint32_t i = 0; i < n; i++) result.push_back(TracebackItem{words[i], scores[i], times[i]});
+  }
+  const uint64_t max_frames_;
+  sr_bigram* net_ = nullptr;
+  sr_bigram_stream* s_ = nullptr;
+};
+
 }  // namespace sr

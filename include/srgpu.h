@@ -327,6 +327,45 @@ SR_API int sr_bigram_describe(const sr_bigram* b, char* out, size_t cap);
 SR_API int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr_bigram_params* p,
                                       uint32_t* out_word, float* out_score, uint32_t* out_time, uint64_t* out_off);
 
+/* ---- streaming bigram-LM recognition: LinearSearch's own initialize / processFrame / getResult (:489-520) -------------------
+ * The sr_stream_* interface for the bigram search: utterances fed as their frames arrive, many at once.  sr_bigram_stream_end
+ * returns, bit for bit, the items sr_recognize_bigram_corpus returns for that utterance with the same p (any layout: they agree);
+ * after t frames sr_bigram_stream_partial returns what it returns for the first t frames taken as a whole utterance.  Items are
+ * LinearSearch::getResult's traceback items (word, score, time; silence included), as out_word / out_score / out_time there.
+ *
+ * sr_bigram_stream_open     up to max_streams concurrently open utterances of up to max_frames frames on (m, b).  p->acoustic_pruning,
+ *                           p->lm_pruning and p->gmm_kernel as for sr_recognize_bigram_corpus; p->flags and p->max_word_ends must be 0
+ *                           (the stream always runs the "global" layout, and its book grows with the utterance).  Device memory per
+ *                           stream: the state image, 16 bytes per position (+ 16 per word above 4 720 words); the two word-end lists,
+ *                           48 W bytes; the active list, 4 W bytes; the partial-result items, 12 (max_frames + 1) bytes; and the
+ *                           book, 16 bytes per kept word end, grown before each push to hold W entries per frame of it (geometric
+ *                           growth).  Plus staging for the largest push: 4 dim + 8 n_states bytes per frame and the scoring kernel's
+ *                           own workspaces.
+ * sr_bigram_stream_begin    a fresh utterance (initialize, :489-495); *id names it until sr_bigram_stream_end.  Ids as sr_stream_begin.
+ * sr_bigram_stream_push     n utterances, ids[n], each at most once; their new frames back to back in feats ([frames x dim] float32),
+ *                           utterance i owning rows [frame_off[i], frame_off[i+1]) (frame_off[0] == 0; an empty range is allowed).
+ *                           One scoring launch, one search launch; returns when both have finished.  Everything is checked before
+ *                           anything is launched: a refused push changes no utterance.
+ * sr_bigram_stream_partial  the items after the frames pushed so far (*frames, may be NULL); cap = capacity of each output array (they
+ *                           may be NULL if cap is 0).
+ * sr_bigram_stream_end      the final items; frees the id.  An utterance ended after 0 frames returns no items.
+ * sr_bigram_stream_destroy  before its bigram search net and its model.
+ * Errors: SR_EINVAL for an unknown or ended id, an id repeated within one push, max_streams == 0, max_frames == 0, p->flags != 0,
+ * p->max_word_ends != 0, a malformed frame_off, and a cap below the item count (*count then holds the count needed; the id stays
+ * open); SR_ELIMIT for a push that would take an utterance past max_frames or its book past 2^32 - 1 entries, and for
+ * sr_bigram_stream_begin with every id in use; SR_EINTERNAL if a book append found the book full (the growth rule excludes it).
+ * Threading: like the model, one host thread at a time. */
+typedef struct sr_bigram_stream sr_bigram_stream;  /* a set of concurrently open utterances on one (model, bigram search net) */
+SR_API int sr_bigram_stream_open(sr_model* m, sr_bigram* b, const sr_bigram_params* p, uint32_t max_streams, uint64_t max_frames,
+                                 sr_bigram_stream** out);
+SR_API int sr_bigram_stream_begin(sr_bigram_stream* s, uint32_t* id);
+SR_API int sr_bigram_stream_push(sr_bigram_stream* s, uint32_t n, const uint32_t* ids, const float* feats, const uint64_t* frame_off);
+SR_API int sr_bigram_stream_partial(sr_bigram_stream* s, uint32_t id, uint32_t* out_word, float* out_score, uint32_t* out_time,
+                                    uint32_t cap, uint32_t* count, uint64_t* frames);
+SR_API int sr_bigram_stream_end(sr_bigram_stream* s, uint32_t id, uint32_t* out_word, float* out_score, uint32_t* out_time,
+                                uint32_t cap, uint32_t* count);
+SR_API int sr_bigram_stream_destroy(sr_bigram_stream* s);
+
 /* Diagnostic: does the fp16 matrix pipe keep subnormal inputs on this device (an assumption of SR_GMM_PREFILTER's
  * error bound; when it does not hold, models are scored by SR_GMM_EXACT's kernel instead)? */
 SR_API int sr_probe_fp16_denormals(int device, int* preserved);

@@ -32,6 +32,8 @@ SYMBOLS = [
     "sr_lexicon_destroy", "sr_lexicon_describe", "sr_recognize_corpus", "sr_traceback_corpus", "sr_traceback_words", "sr_recognize_batch", "sr_align_corpus", "sr_align_corpus_pruned", "sr_path_scores_corpus", "sr_model_create_from_statistics", "sr_model_create_from_accumulated", "sr_mixset_write", "sr_model_set_tying", "sr_model_tying_info", "sr_model_topology", "sr_accumulate_corpus",
     "sr_bigram_create", "sr_bigram_destroy", "sr_bigram_describe", "sr_recognize_bigram_corpus",
     "sr_stream_open", "sr_stream_begin", "sr_stream_push", "sr_stream_partial", "sr_stream_end", "sr_stream_destroy",
+    "sr_bigram_stream_open", "sr_bigram_stream_begin", "sr_bigram_stream_push", "sr_bigram_stream_partial", "sr_bigram_stream_end",
+    "sr_bigram_stream_destroy",
     "sr_probe_fp16_denormals", "sr_probe_fp16_accumulation",
     "sr_profile_enable", "sr_profile_reset", "sr_profile_read",
 ]
@@ -113,6 +115,12 @@ def lib():
         L.sr_stream_partial.argtypes = [vp, u32, vp, u32, C.POINTER(u32), C.POINTER(u64)]
         L.sr_stream_end.argtypes = [vp, u32, vp, u32, C.POINTER(u32), vp, vp, vp]
         L.sr_stream_destroy.argtypes = [vp]
+        L.sr_bigram_stream_open.argtypes = [vp, vp, C.POINTER(BigramParams), u32, u64, C.POINTER(vp)]
+        L.sr_bigram_stream_begin.argtypes = [vp, C.POINTER(u32)]
+        L.sr_bigram_stream_push.argtypes = [vp, u32, vp, vp, vp]
+        L.sr_bigram_stream_partial.argtypes = [vp, u32, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(u64)]
+        L.sr_bigram_stream_end.argtypes = [vp, u32, vp, vp, vp, u32, C.POINTER(u32)]
+        L.sr_bigram_stream_destroy.argtypes = [vp]
         L.sr_probe_fp16_denormals.argtypes = [i32, C.POINTER(i32)]
         L.sr_probe_fp16_accumulation.argtypes = [i32, C.POINTER(i32), C.POINTER(dbl)]
         L.sr_profile_enable.argtypes = [vp, i32]
@@ -228,6 +236,12 @@ class Model:
         """sr_stream_open: a set of up to max_streams concurrently open utterances of up to max_frames frames each."""
         return Stream(self, lexicon, am_threshold, word_penalty, kernel, max_streams, max_frames)
 
+    def bigram_stream(self, bigram, acoustic_pruning=None, lm_pruning=None, kernel=GMM_PREFILTER, max_streams=1, max_frames=65535):
+        """sr_bigram_stream_open: up to max_streams concurrently open utterances of up to max_frames frames each on a bigram search
+        net (beams default to off, as Corpus.recognize_bigram)."""
+        return BigramStream(self, bigram, FLT_MAX if acoustic_pruning is None else acoustic_pruning,
+                            FLT_MAX if lm_pruning is None else lm_pruning, kernel, max_streams, max_frames)
+
     # -- profiling ---------------------------------------------------------------------------------
     def profile(self, on=True):
         _check(lib().sr_profile_enable(self.h, int(on)))
@@ -323,6 +337,68 @@ class Stream:
     def close(self):
         if self.h:
             lib().sr_stream_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class BigramStream:
+    """sr_bigram_stream handle: utterances fed frame by frame to the bigram-LM search (sr_bigram_stream_*).  end() returns what
+    Corpus.recognize_bigram returns for the whole utterance; partial() after t frames what it returns for the first t frames.
+    Items are (words u32[], scores f32[], times u32[])."""
+
+    def __init__(self, model, bigram, acoustic_pruning, lm_pruning, kernel, max_streams, max_frames, max_word_ends=0, flags=0):
+        self.model = model
+        self.max_frames = int(max_frames)
+        self.frames = {}  # frames pushed per open id
+        self.h = C.c_void_p()
+        p = BigramParams(acoustic_pruning, lm_pruning, kernel, max_word_ends, flags)
+        _check(lib().sr_bigram_stream_open(model.h, bigram.h, C.byref(p), max_streams, max_frames, C.byref(self.h)))
+
+    def begin(self):
+        """-> the id of a fresh utterance"""
+        i = C.c_uint32()
+        _check(lib().sr_bigram_stream_begin(self.h, C.byref(i)))
+        self.frames[i.value] = 0
+        return i.value
+
+    def push(self, frames):
+        """frames: {id: float32 [k x dim]} -> one scoring and one search launch for all of them"""
+        ids = np.ascontiguousarray(list(frames.keys()), dtype=np.uint32)
+        parts = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1, self.model.dim) for f in frames.values()]
+        off = np.concatenate([[0], np.cumsum([len(f) for f in parts])]).astype(np.uint64)
+        feats = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, self.model.dim), np.float32))
+        _check(lib().sr_bigram_stream_push(self.h, len(ids), _ptr(ids), _ptr(feats) if len(feats) else None, _ptr(off)))
+        for i, f in zip(ids, parts):
+            self.frames[int(i)] += len(f)
+
+    def _out(self):
+        cap = self.max_frames + 1
+        return np.zeros(cap, np.uint32), np.zeros(cap, np.float32), np.zeros(cap, np.uint32)
+
+    def partial(self, id, frames=False):
+        """-> the items so far (words, scores, times) [, frames pushed]"""
+        ow, osc, ot = self._out()
+        n, t = C.c_uint32(), C.c_uint64()
+        _check(lib().sr_bigram_stream_partial(self.h, id, _ptr(ow), _ptr(osc), _ptr(ot), len(ow), C.byref(n), C.byref(t)))
+        items = (ow[: n.value].copy(), osc[: n.value].copy(), ot[: n.value].copy())
+        return (items, t.value) if frames else items
+
+    def end(self, id):
+        """-> the final items (words, scores, times); frees the id"""
+        ow, osc, ot = self._out()
+        n = C.c_uint32()
+        _check(lib().sr_bigram_stream_end(self.h, id, _ptr(ow), _ptr(osc), _ptr(ot), len(ow), C.byref(n)))
+        self.frames.pop(id)
+        return ow[: n.value].copy(), osc[: n.value].copy(), ot[: n.value].copy()
+
+    def close(self):
+        if self.h:
+            lib().sr_bigram_stream_destroy(self.h)
             self.h = None
 
     def __enter__(self):

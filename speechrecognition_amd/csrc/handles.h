@@ -219,6 +219,36 @@ struct sr_stream {
   DevBuf<srgpu::StreamJob> jobs;
 };
 
+// A set of concurrently open utterances on one (model, bigram search net) (sr_bigram_stream_*, srgpu_api.cpp).  Slot i holds one open
+// utterance; its device state (bigram_stream_kernel, global-states layout) lives in the per-slot buffers below, its frame count and
+// a copy of its BigramStreamState (read back after every push) on the host.
+struct sr_bigram_stream {
+  sr_model* model = nullptr;
+  sr_bigram* bigram = nullptr;
+  sr_bigram_params params{};
+  uint32_t max_streams = 0;
+  uint64_t max_frames = 0;
+  std::vector<uint8_t> open;        // [max_streams]
+  std::vector<uint32_t> id;         // [max_streams] slot + max_streams * generation, as sr_stream
+  std::vector<uint32_t> generation;
+  std::vector<uint64_t> frames;     // [max_streams] frames pushed so far
+  std::vector<srgpu::BigramStreamState> host_state;  // [max_streams] as of the slot's last push
+  std::vector<uint8_t> failed;      // [max_streams] a push flagged the slot (SR_EINTERNAL until it ends)
+  // per slot, device
+  DevBuf<uint32_t> gs_ws;           // bigram_gs_ws_words each
+  DevBuf<uint32_t> we_slot, we_bp;  // 4W each
+  DevBuf<float> we_score;
+  DevBuf<uint16_t> lsave;           // 2W each
+  DevBuf<srgpu::BigramStreamState> state;
+  DevBuf<uint32_t> out_word, out_time;  // max_frames + 1 each
+  DevBuf<float> out_score;
+  std::vector<std::unique_ptr<DevBuf<uint4>>> book;  // [max_streams] grown before a push to n_book + W x (its frames)
+  // per push, sized by the largest push so far
+  DevBuf<float> feats;
+  DevBuf<double> scores;
+  DevBuf<srgpu::BigramStreamJob> jobs;
+};
+
 namespace srhost {
 // (srgpu_api.cpp) handle without parameter tables / lazily fetched host copies of them
 int model_shell(int device, uint32_t dim, uint32_t n_states, const uint32_t* dens_off, int max_approx, sr_model** out);

@@ -313,6 +313,33 @@ hipError_t launch_bigram(const BigramArgs& a, hipStream_t stream);
 size_t bigram_lds_bytes(uint32_t n_words, uint32_t n_positions);
 bool bigram_register_layout(const BigramArgs& a);   // short words, <= 3072 of them, the emission row fits the LDS beside the lists
 uint32_t bigram_max_words();
+// streaming (sr_bigram_stream_push): bigram_stream_kernel advances each of n open utterances by k frames on the global-states layout,
+// from the state the last push left in device memory.  Per stream slot: the state image (a.gs_ws, bigram_gs_ws_words each), the two
+// word-end lists (a.we_*, 2 x 2W entries each), the active list (lsave, 2W), a BigramStreamState, the book (its own allocation, grown by
+// the host between pushes; back pointers are indices into it) and items_stride partial-result items.
+static constexpr uint32_t kBgStreamOverflow = 1u, kBgStreamCorrupt = 2u;  // BigramStreamState::flags
+struct BigramStreamState {
+  uint32_t n_book, n_we, n_L;  // book entries, word ends of the last frame, slots on the active list
+  uint32_t lcur, gs_cur;       // which half of the active-list double buffer / of the image holds the current hypotheses
+  uint32_t flags;              // kBgStreamOverflow: an append would have passed book_cap; kBgStreamCorrupt: the partial walk failed
+  uint32_t count;              // items of the partial result
+  uint32_t pad;
+};
+struct BigramStreamJob {       // one workgroup of a push
+  uint32_t slot, t0, k, pad;   // stream slot, frames searched before this push, frames in it
+  uint64_t row0;               // its first frame's row in the push's score table
+  uint4* book;                 // the slot's book and its capacity (entries)
+  uint64_t book_cap;
+};
+struct BigramStreamArgs {
+  BigramArgs a;                // lexicon, LM, penalties, beams, scores = the push's table; gs_ws, we_* per slot (frame_off etc. unused)
+  const BigramStreamJob* jobs; // [workgroups]
+  BigramStreamState* state;    // [slots]
+  uint16_t* lsave;             // [slots x 2W] the active list between pushes
+  uint32_t* out_word; float* out_score; uint32_t* out_time;  // [slots x items_stride] the partial result
+  uint64_t items_stride;       // max_frames + 1
+};
+hipError_t launch_bigram_stream(const BigramStreamArgs& s, uint32_t n_jobs, hipStream_t stream);
 
 // out[f] = scores[(f - frame_base) * ld + states[f]] for f in [f0, f1)  (Trainer::calc_am_score, Training.cpp:605)
 hipError_t launch_path_scores(const double* scores, uint32_t ld, uint64_t frame_base, uint64_t f0, uint64_t f1,

@@ -680,6 +680,31 @@ int stream_words(sr_stream* s, uint32_t slot, uint32_t id, uint32_t* out_words, 
 }
 }  // namespace
 
+namespace {  // sr_bigram_stream_*
+int64_t bigram_stream_slot(const sr_bigram_stream* s, uint32_t id) {
+  const uint32_t slot = id % s->max_streams;
+  return s->open[slot] && s->id[slot] == id ? (int64_t)slot : -1;
+}
+// the partial (after every push) or final traceback items of the utterance in `slot`: the state record read back after its last push
+int bigram_stream_items(sr_bigram_stream* s, uint32_t slot, uint32_t id, uint32_t* out_word, float* out_score, uint32_t* out_time,
+                        uint32_t cap, uint32_t* count) {
+  *count = 0;
+  if (s->frames[slot] == 0) return SR_OK;  // nothing searched yet: the empty utterance's (no) items
+  if (s->failed[slot]) return fail(SR_EINTERNAL, "stream %u: a push overflowed its book", id);
+  const BigramStreamState& st = s->host_state[slot];
+  if (st.flags & kBgStreamCorrupt) return fail(SR_ECORRUPT, "stream %u: the book walk does not end at its start entry", id);
+  *count = st.count;
+  if (st.count > cap) return fail(SR_EINVAL, "stream %u: %u items, the output arrays hold %u", id, st.count, cap);
+  const size_t o = (size_t)slot * (s->max_frames + 1);
+  if (st.count) {
+    HIP_TRY(hipMemcpy(out_word, s->out_word.p + o, sizeof(uint32_t) * st.count, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_score, s->out_score.p + o, sizeof(float) * st.count, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_time, s->out_time.p + o, sizeof(uint32_t) * st.count, hipMemcpyDeviceToHost));
+  }
+  return SR_OK;
+}
+}  // namespace
+
 extern "C" {
 
 const char* sr_last_error(void) { return g_err; }
@@ -1844,6 +1869,195 @@ int sr_stream_end(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_t cap, 
 }
 
 int sr_stream_destroy(sr_stream* s) {
+  return guarded(__func__, [&]() -> int {
+  if (!s) return SR_OK;
+  if (s->model) { (void)hipSetDevice(s->model->device); (void)hipDeviceSynchronize(); }
+  delete s;
+  return SR_OK;
+  });
+}
+
+// ---- streaming bigram-LM recognition (sr_bigram_stream_*): bigram_stream_kernel over per-slot state in device memory --------------
+
+int sr_bigram_stream_open(sr_model* m, sr_bigram* b, const sr_bigram_params* p, uint32_t max_streams, uint64_t max_frames,
+                          sr_bigram_stream** out) {
+  return guarded(__func__, [&]() -> int {
+  if (!out) return fail(SR_EINVAL, "out is null");
+  *out = nullptr;
+  int rc = check_model(m);
+  if (rc) return rc;
+  if (!b || b->model != m) return fail(SR_EINVAL, "bigram search net does not belong to this model");
+  if (!p) return fail(SR_EINVAL, "null bigram params");
+  if (p->flags != 0) return fail(SR_EINVAL, "sr_bigram_params.flags must be 0 for streaming (got 0x%x)", (unsigned)p->flags);
+  if (p->max_word_ends != 0)
+    return fail(SR_EINVAL, "sr_bigram_params.max_word_ends must be 0 for streaming (got %u): the book grows with the utterance", p->max_word_ends);
+  if (p->gmm_kernel < SR_GMM_MFMA || p->gmm_kernel > SR_GMM_DEFAULT) return fail(SR_EINVAL, "unknown gmm_kernel %d", p->gmm_kernel);
+  if (max_streams == 0) return fail(SR_EINVAL, "max_streams must be at least 1");
+  if (max_frames == 0) return fail(SR_EINVAL, "max_frames must be at least 1");
+  if (max_frames > 0xFFFFFFFEull) return fail(SR_ELIMIT, "max_frames %llu: frame times are 32 bit", (unsigned long long)max_frames);
+  sr_bigram_stream* s = new sr_bigram_stream();
+  std::unique_ptr<sr_bigram_stream, int (*)(sr_bigram_stream*)> own(s, sr_bigram_stream_destroy);
+  s->model = m; s->bigram = b; s->params = *p; s->max_streams = max_streams; s->max_frames = max_frames;
+  s->open.assign(max_streams, 0); s->id.assign(max_streams, 0); s->generation.assign(max_streams, 0); s->frames.assign(max_streams, 0);
+  s->host_state.assign(max_streams, BigramStreamState{}); s->failed.assign(max_streams, 0);
+  const size_t S = max_streams, W = b->n_words;
+  HIP_TRY(s->gs_ws.ensure(S * bigram_gs_ws_words(b->n_words, b->n_positions)));
+  HIP_TRY(s->we_slot.ensure(S * 4 * W));
+  HIP_TRY(s->we_bp.ensure(S * 4 * W));
+  HIP_TRY(s->we_score.ensure(S * 4 * W));
+  HIP_TRY(s->lsave.ensure(S * 2 * W));
+  HIP_TRY(s->state.ensure(S));
+  HIP_TRY(s->out_word.ensure(S * (max_frames + 1)));
+  HIP_TRY(s->out_time.ensure(S * (max_frames + 1)));
+  HIP_TRY(s->out_score.ensure(S * (max_frames + 1)));
+  for (size_t i = 0; i < S; i++) s->book.emplace_back(new DevBuf<uint4>());
+  *out = own.release();
+  return SR_OK;
+  });
+}
+
+int sr_bigram_stream_begin(sr_bigram_stream* s, uint32_t* id) {
+  return guarded(__func__, [&]() -> int {
+  if (!s || !id) return fail(SR_EINVAL, "null argument");
+  uint32_t slot = 0;
+  while (slot < s->max_streams && s->open[slot]) slot++;
+  if (slot == s->max_streams) return fail(SR_ELIMIT, "all %u streams are open", s->max_streams);
+  uint32_t g = s->generation[slot];  // (ids as sr_stream_begin)
+  if ((uint64_t)slot + (uint64_t)s->max_streams * g > 0xFFFFFFFFull) g = 0;
+  s->generation[slot] = g + 1;
+  s->id[slot] = slot + s->max_streams * g;
+  s->open[slot] = 1;
+  s->frames[slot] = 0;  // the first push starts from the initial state (bigram_stream_kernel)
+  s->host_state[slot] = BigramStreamState{};
+  s->host_state[slot].n_book = 2;  // the two start entries the first push writes
+  s->failed[slot] = 0;
+  *id = s->id[slot];
+  return SR_OK;
+  });
+}
+
+int sr_bigram_stream_push(sr_bigram_stream* s, uint32_t n, const uint32_t* ids, const float* feats, const uint64_t* frame_off) {
+  return guarded(__func__, [&]() -> int {
+  if (!s) return fail(SR_EINVAL, "null stream set");
+  if (n == 0) return SR_OK;
+  if (!ids || !frame_off) return fail(SR_EINVAL, "null argument");
+  if (frame_off[0] != 0) return fail(SR_EINVAL, "frame_off[0] must be 0");
+  sr_bigram* b = s->bigram;
+  const uint64_t W = b->n_words;
+  std::vector<uint8_t> seen(s->max_streams, 0);
+  std::vector<BigramStreamJob> jobs;
+  std::vector<uint64_t> need;  // per job: book entries the push may reach (n_book + W per frame: a frame keeps at most one word end per history)
+  for (uint32_t i = 0; i < n; i++) {
+    const int64_t slot = bigram_stream_slot(s, ids[i]);
+    if (slot < 0) return fail(SR_EINVAL, "push entry %u: stream id %u is not open", i, ids[i]);
+    if (seen[slot]) return fail(SR_EINVAL, "push entry %u: stream id %u appears twice in one push", i, ids[i]);
+    seen[slot] = 1;
+    if (frame_off[i + 1] < frame_off[i]) return fail(SR_EINVAL, "frame_off is not ascending at entry %u", i);
+    const uint64_t k = frame_off[i + 1] - frame_off[i];
+    if (k > s->max_frames - s->frames[slot])
+      return fail(SR_ELIMIT, "stream id %u: %llu + %llu frames exceed max_frames %llu", ids[i], (unsigned long long)s->frames[slot],
+                  (unsigned long long)k, (unsigned long long)s->max_frames);
+    if (s->failed[slot] && k) return fail(SR_EINTERNAL, "stream id %u: an earlier push overflowed its book", ids[i]);
+    if (!k) continue;
+    const uint64_t nb = (s->frames[slot] ? s->host_state[slot].n_book : 2u) + W * k;
+    if (nb > 0xFFFFFFFFull)
+      return fail(SR_ELIMIT, "stream id %u: this push may need %llu book entries, more than 2^32 - 1", ids[i], (unsigned long long)nb);
+    jobs.push_back({(uint32_t)slot, (uint32_t)s->frames[slot], (uint32_t)k, 0u, frame_off[i], nullptr, 0});
+    need.push_back(nb);
+  }
+  const uint64_t F = frame_off[n];
+  if (F == 0) return SR_OK;
+  if (!feats) return fail(SR_EINVAL, "null feats");
+  sr_model* m = s->model;
+  int rc = check_model(m);
+  if (rc) return rc;
+  // every book to at least n_book + W k entries (geometric growth; the entries so far are copied: back pointers are indices)
+  for (size_t j = 0; j < jobs.size(); j++) {
+    DevBuf<uint4>& bk = *s->book[jobs[j].slot];
+    if (bk.n < need[j]) {
+      DevBuf<uint4> grown;
+      HIP_TRY(grown.ensure(std::max<uint64_t>(need[j], std::min<uint64_t>(2 * (uint64_t)bk.n, 0xFFFFFFFFull))));
+      if (jobs[j].t0) HIP_TRY(hipMemcpy(grown.p, bk.p, sizeof(uint4) * s->host_state[jobs[j].slot].n_book, hipMemcpyDeviceToDevice));
+      bk.swap(grown);
+    }
+    jobs[j].book = bk.p;
+    jobs[j].book_cap = bk.n;
+  }
+  HIP_TRY(s->feats.ensure((size_t)F * m->dim));
+  HIP_TRY(s->scores.ensure((size_t)F * m->ld));
+  HIP_TRY(s->jobs.ensure(jobs.size()));
+  HIP_TRY(hipMemcpyAsync(s->feats.p, feats, sizeof(float) * F * m->dim, hipMemcpyHostToDevice, m->s_gmm));
+  HIP_TRY(hipMemcpyAsync(s->jobs.p, jobs.data(), sizeof(BigramStreamJob) * jobs.size(), hipMemcpyHostToDevice, m->s_gmm));
+  if ((rc = launch_scoring(m, s->feats.p, F, s->params.gmm_kernel, s->scores.p))) return rc;
+  const hipStream_t s_search = m->overlap ? m->s_search : m->s_gmm;
+  HIP_TRY(hipEventRecord(m->ev_scored[0], m->s_gmm));
+  HIP_TRY(hipStreamWaitEvent(s_search, m->ev_scored[0], 0));
+  BigramStreamArgs a{};
+  BigramArgs& ba = a.a;
+  ba.scores = s->scores.p; ba.ld = m->ld;
+  ba.n_words = b->n_words; ba.silence = b->silence; ba.n_positions = b->n_positions;
+  ba.slot_off = b->slot_off.p; ba.slot_mix = b->slot_mix.p; ba.mixtures = b->mixtures.p; ba.pos_info = b->pos_info.p; ba.pos_slot = b->pos_slot.p;
+  ba.lmT = b->lmT.p; ba.lm_rowmin = b->lm_rowmin.p; ba.lm_rowmax = b->lm_rowmax.p;
+  memcpy(ba.tdp, b->tdp, sizeof(ba.tdp));
+  ba.ac_pruning = s->params.acoustic_pruning; ba.lm_pruning = s->params.lm_pruning;
+  ba.max_slot_states = b->max_slot_states; ba.silence_states = b->silence_states;
+  ba.global_states = 1;
+  ba.gs_ws = s->gs_ws.p; ba.gs_ws_words = bigram_gs_ws_words(b->n_words, b->n_positions);
+  ba.we_slot = s->we_slot.p; ba.we_bp = s->we_bp.p; ba.we_score = s->we_score.p;
+  a.jobs = s->jobs.p; a.state = s->state.p; a.lsave = s->lsave.p;
+  a.out_word = s->out_word.p; a.out_score = s->out_score.p; a.out_time = s->out_time.p; a.items_stride = s->max_frames + 1;
+  EventPair ep{};
+  if ((rc = prof_begin(m, s_search, 1, &ep))) return rc;
+  HIP_TRY(launch_bigram_stream(a, (uint32_t)jobs.size(), s_search));
+  if ((rc = prof_end(m, s_search, &ep))) return rc;
+  HIP_TRY(hipStreamSynchronize(s_search));
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  std::vector<BigramStreamState> st(s->max_streams);  // (one copy of every slot's 32 bytes: cheaper than one per pushed slot)
+  HIP_TRY(hipMemcpy(st.data(), s->state.p, sizeof(BigramStreamState) * st.size(), hipMemcpyDeviceToHost));
+  uint32_t bad = 0xFFFFFFFFu;
+  for (const BigramStreamJob& j : jobs) {
+    s->frames[j.slot] += j.k;
+    s->host_state[j.slot] = st[j.slot];
+    if (st[j.slot].flags & kBgStreamOverflow) { s->failed[j.slot] = 1; bad = s->id[j.slot]; }
+  }
+  if (m->profiling) {  // SURVEY 8(d)'s decoder model, 8 S + 4 P bytes per frame, as sr_recognize_bigram_corpus
+    m->prof.search_bytes += (8.0 * m->n_states + 4.0 * b->n_positions) * (double)F;
+    m->prof.frames += F;
+  }
+  if (bad != 0xFFFFFFFFu) return fail(SR_EINTERNAL, "stream id %u: a book append passed the capacity the host grew it to", bad);
+  return SR_OK;
+  });
+}
+
+int sr_bigram_stream_partial(sr_bigram_stream* s, uint32_t id, uint32_t* out_word, float* out_score, uint32_t* out_time, uint32_t cap,
+                             uint32_t* count, uint64_t* frames) {
+  return guarded(__func__, [&]() -> int {
+  if (!s || !count || ((!out_word || !out_score || !out_time) && cap)) return fail(SR_EINVAL, "null argument");
+  const int64_t slot = bigram_stream_slot(s, id);
+  if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
+  int rc = check_model(s->model);
+  if (rc) return rc;
+  if (frames) *frames = s->frames[slot];
+  return bigram_stream_items(s, (uint32_t)slot, id, out_word, out_score, out_time, cap, count);
+  });
+}
+
+int sr_bigram_stream_end(sr_bigram_stream* s, uint32_t id, uint32_t* out_word, float* out_score, uint32_t* out_time, uint32_t cap,
+                         uint32_t* count) {
+  return guarded(__func__, [&]() -> int {
+  if (!s || !count || ((!out_word || !out_score || !out_time) && cap)) return fail(SR_EINVAL, "null argument");
+  const int64_t slot = bigram_stream_slot(s, id);
+  if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
+  int rc = check_model(s->model);
+  if (rc) return rc;
+  rc = bigram_stream_items(s, (uint32_t)slot, id, out_word, out_score, out_time, cap, count);
+  if (rc == SR_EINVAL) return rc;  // too small a buffer: the utterance stays open
+  s->open[slot] = 0;
+  return rc;
+  });
+}
+
+int sr_bigram_stream_destroy(sr_bigram_stream* s) {
   return guarded(__func__, [&]() -> int {
   if (!s) return SR_OK;
   if (s->model) { (void)hipSetDevice(s->model->device); (void)hipDeviceSynchronize(); }

@@ -163,10 +163,15 @@ __device__ __forceinline__ float bigram_position(const BigramArgs& a, uint32_t f
 // GSM (global states, bigram_gs_kernel): 0 = the register or the dense LDS layout; 1 = the state hypotheses in device memory, the entry
 // hypotheses in LDS; 2 = the entries in device memory too (the lexica whose entries, lists and flags alone crowd the LDS).
 // One utterance `ui` of the launch, on workgroup `wg` (its slice of the per-workgroup workspaces).
-template <int KW, int KP, int KS, int NPM, int GSM>  // KW words per thread in the recombination: W <= KW * kBgThreads
-__device__ __forceinline__ void bigram_utterance(const BigramArgs& a, uint32_t ui, uint32_t wg) {
+// STREAM (bigram_stream_kernel, global states only): frames job->t0 + 1 .. job->t0 + job->k of the utterance in stream slot wg = job->slot,
+// from the state the last push left (sa->state, sa->lsave and the slot's workspaces); at the end the state is saved and the traceback of
+// the frames so far written as the slot's partial result.  The batch instantiations (STREAM = false) compile exactly as before.
+template <int KW, int KP, int KS, int NPM, int GSM, bool STREAM = false>  // KW words per thread in the recombination: W <= KW * kBgThreads
+__device__ __forceinline__ void bigram_utterance(const BigramArgs& a, uint32_t ui, uint32_t wg, const BigramStreamArgs* sa = nullptr,
+                                                 const BigramStreamJob* job = nullptr) {
   constexpr bool REGS = KS > 0, GS = GSM > 0, ENG = GSM == 2;
   static_assert(!(REGS && GS), "the global-states layout keeps one hypothesis per position");
+  static_assert(!STREAM || GS, "a stream keeps its state hypotheses in device memory");
   constexpr int NP = NPM ? 4 : 3;  // states a lane keeps per word at most
   auto np_of = [](int k) constexpr { return ((NPM >> k) & 1) ? 4 : 3; };  // ... and in slot row k
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -214,8 +219,8 @@ __device__ __forceinline__ void bigram_utterance(const BigramArgs& a, uint32_t u
   float* fin_score = en_score;                                // [2W] final-state score / back pointer of the slots whose word end survived
   uint32_t* fin_bp = en_bp;                                   //      (written in step 4, read by its compaction; the entries are consumed by then)
 
-  const uint32_t u = a.utt_order ? a.utt_order[a.utt_first + ui] : a.utt_first + ui, tid = threadIdx.x;
-  const uint64_t f0 = a.frame_off[u], T = a.frame_off[u + 1] - f0;
+  const uint32_t u = STREAM ? 0u : a.utt_order ? a.utt_order[a.utt_first + ui] : a.utt_first + ui, tid = threadIdx.x;
+  const uint64_t f0 = STREAM ? 0u : a.frame_off[u], T = STREAM ? (uint64_t)job->t0 + job->k : a.frame_off[u + 1] - f0;
   const double* dense = a.scores + (f0 - a.frame_base) * a.ld;
   // per-utterance global workspaces
   uint32_t* we_slot[2]; float* we_score[2]; uint32_t* we_bp[2];
@@ -223,8 +228,8 @@ __device__ __forceinline__ void bigram_utterance(const BigramArgs& a, uint32_t u
     const uint64_t o = ((uint64_t)wg * 2 + i) * W2;
     we_slot[i] = a.we_slot + o; we_score[i] = a.we_score + o; we_bp[i] = a.we_bp + o;
   }
-  uint4* book = a.book + a.book_off[u];  // (word, score bits, backpointer, time)
-  const uint64_t book_cap = a.book_off[u + 1] - a.book_off[u];
+  uint4* book = STREAM ? job->book : a.book + a.book_off[u];  // (word, score bits, backpointer, time)
+  const uint64_t book_cap = STREAM ? job->book_cap : a.book_off[u + 1] - a.book_off[u];
   const float exit_pen[2] = {a.tdp[0][3], a.tdp[1][3]};
 
   auto map_copy = [&](uint32_t w) { return w == sil ? w : (w >= W ? w - W : w); };
@@ -291,10 +296,22 @@ __device__ __forceinline__ void bigram_utterance(const BigramArgs& a, uint32_t u
   // initialize (:211-216, :397-418 at t = 0): book[0] = sentinel, book[1] = (silence, 0, self, 0); one word end
   uint32_t n_book = 2, n_we = 1, n_L = 0;
   int cur = 0, lcur = 0;  // we_*[cur] = current word ends, L[lcur] = current active list
-  if (tid == 0) {
-    book[0] = make_uint4(0xFFFFFFFFu, __float_as_uint(kFltMax), 0u, 0u);
-    book[1] = make_uint4(sil, __float_as_uint(0.0f), 1u, 0u);
-    we_slot[0][0] = sil; we_score[0][0] = 0.0f; we_bp[0][0] = 1u;
+  if (!STREAM || job->t0 == 0) {
+    if (tid == 0) {
+      book[0] = make_uint4(0xFFFFFFFFu, __float_as_uint(kFltMax), 0u, 0u);
+      book[1] = make_uint4(sil, __float_as_uint(0.0f), 1u, 0u);
+      we_slot[0][0] = sil; we_score[0][0] = 0.0f; we_bp[0][0] = 1u;
+    }
+    if constexpr (STREAM)  // a fresh utterance: the slot's image is +inf everywhere (whatever an earlier utterance of the slot left)
+      for (uint64_t i = tid; i < 2ull * P2; i += kBgThreads) gs_ws[i] = 0x7F800000u;
+  } else if constexpr (STREAM) {
+    // resume: the counters and the active list the last push saved; `cur` is always 0 (step 6 writes the merged list
+    // back to we_*[cur]); `active` holds only list membership between frames (step 4's compaction), so it is rebuilt from L
+    const BigramStreamState& st = sa->state[wg];
+    n_book = st.n_book; n_we = st.n_we; n_L = st.n_L; lcur = (int)st.lcur; gs_cur = (int)st.gs_cur;
+    __syncthreads();  // active[] has been cleared above
+    const uint16_t* ls = sa->lsave + (uint64_t)wg * W2;
+    for (uint32_t i = tid; i < n_L; i += kBgThreads) { const uint32_t sl = ls[i]; L[lcur][i] = (uint16_t)sl; active[sl] = 1; }
   }
   __syncthreads();
   bool overflow = false;
@@ -308,7 +325,7 @@ __device__ __forceinline__ void bigram_utterance(const BigramArgs& a, uint32_t u
   // the copies in HBM are still written, for the final traceback.
   uint32_t m_raw[KW], m_bp[KW];
   float m_sc[KW];
-  for (uint64_t t = 1; t <= T; t++) {
+  for (uint64_t t = STREAM ? (uint64_t)job->t0 + 1 : 1; t <= T; t++) {
     // ---- 1 bigramRecombination + LM beam ------------------------------------------------------------------------
     for (uint32_t i = W + tid; i < W2; i += kBgThreads) en_score[i] = __builtin_inff();
     if (tid == 0) { en_score[sil] = __builtin_inff(); if (REGS) *n_pairs = 0; }
@@ -582,7 +599,8 @@ __device__ __forceinline__ void bigram_utterance(const BigramArgs& a, uint32_t u
     for (uint32_t i = l_lo; i < l_hi; i++) { const uint32_t sl = L[lcur][i]; gs_pre[i] = base; base += a.slot_off[sl + 1] - a.slot_off[sl]; }
     if (a.gs_active && tid == 0) atomicAdd(a.gs_active, (unsigned long long)n_act);
     __syncthreads();
-    const double* row = dense + (t - 1) * a.ld;
+    // (a stream: frame t is row job->row0 + (t - t0 - 1) of the push's score table)
+    const double* row = STREAM ? a.scores + (job->row0 + (t - 1 - job->t0)) * a.ld : dense + (t - 1) * a.ld;
     const float* o_sc = gs_score[gs_cur];
     const uint32_t* o_bp = gs_bp[gs_cur];
     float* n_sc = gs_score[gs_cur ^ 1];
@@ -892,6 +910,39 @@ __device__ __forceinline__ void bigram_utterance(const BigramArgs& a, uint32_t u
   }
 
   // ---- traceback (:420-436): first minimum in list order --------------------------------------------------------
+  if constexpr (STREAM) {
+    // save what the next push resumes from, and the traceback of the frames so far as the partial result.  The walk is guarded: at
+    // most `stride` items (a chain steps back at least one frame per item) and only through entries below n_book.
+    uint16_t* ls = sa->lsave + (uint64_t)wg * W2;
+    for (uint32_t i = tid; i < n_L; i += kBgThreads) ls[i] = L[lcur][i];
+    if (tid == 0) {
+      uint32_t n_out = 0, flags = overflow ? kBgStreamOverflow : 0u;
+      if (!overflow && n_we > 0) {
+        uint32_t bi = 0;
+        float bs = we_score[cur][0];
+        for (uint32_t i = 1; i < n_we; i++) { const float s = we_score[cur][i]; if (s < bs) { bs = s; bi = i; } }
+        const uint32_t bp0 = we_bp[cur][bi];
+        const uint64_t stride = sa->items_stride;
+        uint32_t len = 0, b = bp0;
+        while (b < n_book && book[b].w > 0 && len <= stride) { len++; b = book[b].z; }
+        if (b >= n_book || len > stride) {
+          flags |= kBgStreamCorrupt;
+        } else {
+          n_out = len;
+          const uint64_t o = (uint64_t)wg * stride;
+          for (b = bp0; book[b].w > 0; b = book[b].z) {
+            len--;
+            const uint4 e = book[b];
+            sa->out_word[o + len] = e.x; sa->out_score[o + len] = __uint_as_float(e.y); sa->out_time[o + len] = e.w;
+          }
+        }
+      }
+      BigramStreamState& st = sa->state[wg];
+      st.n_book = n_book; st.n_we = n_we; st.n_L = n_L; st.lcur = (uint32_t)lcur; st.gs_cur = (uint32_t)gs_cur;
+      st.flags = flags; st.count = n_out;
+    }
+    return;  // (the image stays: the next push resumes from it)
+  }
   if (tid == 0) {
     uint32_t n_out = 0;
     if (overflow) {
@@ -943,6 +994,14 @@ __global__ __launch_bounds__(kBgThreads) void bigram_gs_kernel(BigramArgs a) {
   }
 }
 
+// Streaming (sr_bigram_stream_push): one workgroup per (slot, frames) job of a push, the frames t0 + 1 .. t0 + k of the slot's utterance
+// through the same per-frame code as bigram_gs_kernel, then the partial traceback.  Workspaces are indexed by slot.
+template <int KW, int GSM>
+__global__ __launch_bounds__(kBgThreads) void bigram_stream_kernel(BigramStreamArgs s) {
+  const BigramStreamJob job = s.jobs[blockIdx.x];
+  bigram_utterance<KW, 4, 0, 0, GSM, true>(s.a, 0, job.slot, &s, &job);
+}
+
 size_t bigram_lds_bytes(uint32_t n_words, uint32_t n_positions) { return (size_t)n_positions * 8 + bigram_lds_small(n_words); }
 uint32_t bigram_max_words() { return 8 * kBgThreads; }
 
@@ -981,6 +1040,26 @@ static hipError_t launch_bigram_gs(const BigramArgs& a, hipStream_t stream) {
   if (kw <= 4) return go(bigram_gs_kernel<4, 1>);
   if (!eng) return go(bigram_gs_kernel<8, 1>);
   return go(bigram_gs_kernel<8, 2>);
+}
+
+hipError_t launch_bigram_stream(const BigramStreamArgs& s, uint32_t n_jobs, hipStream_t stream) {
+  if (n_jobs == 0) return hipSuccess;
+  const BigramArgs& a = s.a;
+  const bool eng = bigram_gs_entries_global(a.n_words);
+  const size_t smem = bigram_gs_lds(a.n_words, eng);
+  if (!a.gs_ws || a.gs_ws_words < bigram_gs_ws_words(a.n_words, a.n_positions)) return hipErrorInvalidValue;
+  auto go = [&](auto kernel) {
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(n_jobs), dim3(kBgThreads), smem, stream, s);
+    return hipGetLastError();
+  };
+  const uint32_t kw = (a.n_words + kBgThreads - 1) / kBgThreads;
+  if (kw <= 1) return go(bigram_stream_kernel<1, 1>);
+  if (kw <= 2) return go(bigram_stream_kernel<2, 1>);
+  if (kw <= 4) return go(bigram_stream_kernel<4, 1>);
+  if (!eng) return go(bigram_stream_kernel<8, 1>);
+  return go(bigram_stream_kernel<8, 2>);
 }
 
 hipError_t launch_bigram(const BigramArgs& a, hipStream_t stream) {

@@ -6,7 +6,11 @@ N concurrent streams (default 64); every push hands each open stream its next `-
 audio); a stream that has had all its frames is ended and the next utterance begun in its place.  Prints the median and p99
 wall time per push (host clock around sr_stream_push, which returns after its search has finished), the device time of the
 scoring and search launches from sr_profile, and the total time to finish the corpus against one sr_recognize_corpus over the
-same utterances (features resident).  The streamed words are checked against the batch's.  Needs a GPU."""
+same utterances (features resident).  The streamed words are checked against the batch's.  Needs a GPU.
+
+--decoder bigram: the bigram-LM stream (sr_bigram_stream_*) on BASELINE configs[4]'s shape instead -- 8000 states x 64 densities,
+2666 words, bench.py's seeded bigram table and transition scores, acoustic beam 200, no LM beam -- against one
+sr_recognize_bigram_corpus; the streamed items (words, score bits, times) are checked against the batch's."""
 from __future__ import annotations
 
 import argparse
@@ -27,7 +31,10 @@ def main():
     ap.add_argument("--piece", type=int, default=10, help="frames per stream per push")
     ap.add_argument("--utts", type=int, default=1000, help="utterances of bench.py's corpus to stream")
     ap.add_argument("--kernel", choices=["default", "prefilter", "exact", "mfma"], default="default")
+    ap.add_argument("--decoder", choices=["zerogram", "bigram"], default="zerogram")
     args = ap.parse_args()
+    if args.decoder == "bigram":
+        return main_bigram(args)
 
     from speechrecognition_amd import capi, synth
 
@@ -102,6 +109,93 @@ def main():
           f"sr_recognize_corpus {batch_s:.3f} s ({stream_s / batch_s:.1f}x)")
     print(f"streamed words equal the batch's: {'yes' if same else 'NO'}")
     return 0 if same else 1
+
+
+def main_bigram(args):
+    from speechrecognition_amd import capi, synth
+
+    D = 39
+    lex = synth.make_lexicon(2666, 3, 1, extra_states_last=1)  # bench.py --config cfg5
+    beam = 200.0
+    kernel = {"mfma": capi.GMM_MFMA, "exact": capi.GMM_EXACT, "prefilter": capi.GMM_PREFILTER, "default": capi.GMM_DEFAULT}[args.kernel]
+    tmp = tempfile.mkdtemp(prefix="srstream_")
+    mp = os.path.join(tmp, "model.mix")
+    synth.write_mixset(mp, synth.make_mixset(lex.n_states, 64, D, seed=23))
+    feats, off = synth.make_batch(1000, 200, 400, D, seed=7)
+    n = min(args.utts, len(off) - 1)
+    off = off[: n + 1]
+    feats = feats[: int(off[-1])]
+    utts = [feats[int(off[u]):int(off[u + 1])] for u in range(n)]
+    word_off, automaton, _ = lex.flatten()
+    lm_rng = np.random.default_rng(99)  # bench.py's bigram table and transition scores
+    nW = lex.n_words
+    lm = np.empty((nW, nW), np.float32)
+    for h0 in range(0, nW, 256):
+        p = lm_rng.dirichlet(np.ones(nW), size=min(256, nW - h0))
+        lm[:, h0:h0 + p.shape[0]] = (-np.log(np.maximum(p, 1e-30))).T
+    bg_tdp = np.array([[3.0, 0.0, 3.0, 150.0], [0.0001, 3.0, np.inf, 15.0]], np.float32)
+
+    with capi.Model.from_mixset(mp, D) as m:
+        bg = m.bigram(word_off, automaton, lex.silence_idx, lm, bg_tdp)
+        corpus = m.upload(feats, off)
+        corpus.recognize_bigram(bg, beam, capi.FLT_MAX, kernel)  # warm: packing, workspaces
+        t = time.perf_counter()
+        bw, bs, bt, boff = corpus.recognize_bigram(bg, beam, capi.FLT_MAX, kernel)
+        batch_s = time.perf_counter() - t
+        corpus.close()
+
+        with m.bigram_stream(bg, beam, capi.FLT_MAX, kernel, max_streams=args.streams, max_frames=int(np.diff(off.astype(np.int64)).max())) as st:
+            warm = [st.begin() for _ in range(args.streams)]
+            st.push({sid: utts[0][:args.piece] for sid in warm})
+            for sid in warm:
+                st.end(sid)
+            m.profile(True)
+            todo = list(range(n))
+            open_ = {}
+            got = {}
+            push_ms = []
+            t_all = time.perf_counter()
+            while todo or open_:
+                while todo and len(open_) < args.streams:
+                    u = todo.pop(0)
+                    open_[st.begin()] = (u, 0)
+                batch = {sid: utts[u][t0:t0 + args.piece] for sid, (u, t0) in open_.items()}
+                t = time.perf_counter()
+                st.push(batch)
+                push_ms.append(1e3 * (time.perf_counter() - t))
+                for sid in list(open_):
+                    u, t0 = open_[sid]
+                    t0 += len(batch[sid])
+                    if t0 == len(utts[u]):
+                        got[u] = st.end(sid)
+                        del open_[sid]
+                    else:
+                        open_[sid] = (u, t0)
+            stream_s = time.perf_counter() - t_all
+            prof = m.profile_read()
+        bg.close()
+
+    def same(u):
+        a, b = int(boff[u]), int(boff[u + 1])
+        w, s, tm = got[u]
+        return np.array_equal(w, bw[a:b]) and np.array_equal(tm, bt[a:b]) and np.array_equal(s.view(np.uint32), bs[a:b].view(np.uint32))
+
+    ok = all(same(u) for u in range(n))
+    pm = np.asarray(push_ms)
+    pushes = len(pm)
+    print(f"workload: configs[4] shape (8000 states x 64, 2666 words, bench.py's bigram table), bigram stream (global-states layout), "
+          f"{n} utterances, {int(off[-1])} frames, {args.streams} concurrent streams, {args.piece} frames per stream per push, "
+          f"gmm_kernel {args.kernel}")
+    print(f"pushes: {pushes}; wall per push: median {np.median(pm):.3f} ms, p99 {np.percentile(pm, 99):.3f} ms, "
+          f"min {pm.min():.3f} ms, max {pm.max():.3f} ms")
+    print(f"device per push (sr_profile): scoring {prof['gmm_ms'] / pushes:.3f} ms ({prof['gmm_launches']} launches), "
+          f"search {prof['search_ms'] / pushes:.3f} ms ({prof['search_launches']} launches); frames {prof['frames']}")
+    dev = prof["gmm_ms"] + prof["search_ms"]
+    print(f"device share of push wall time: {dev / pm.sum():.1%} (the rest: copies, launches, synchronisation, host)")
+    print(f"corpus: streamed in {stream_s:.3f} s (of which {pm.sum() / 1e3:.3f} s in sr_bigram_stream_push) vs one "
+          f"sr_recognize_bigram_corpus {batch_s:.3f} s ({stream_s / batch_s:.1f}x)")
+    print(f"streamed items equal the batch's (words, times, score bits): {'yes' if ok else 'NO'}")
+    return 0 if ok else 1
 
 
 if __name__ == "__main__":
