@@ -283,22 +283,23 @@ class Bigram:
             self.h = None
 
 
-class Stream:
-    """sr_stream handle: utterances fed frame by frame (sr_stream_*).  end() returns what Corpus.recognize returns for the whole
-    utterance; partial() after t frames what it returns for the first t frames."""
+class _StreamSet:
+    """What Stream and BigramStream share: the handle of a stream set over a search net (`_fn`_open), begin, push and close.  The
+    subclass names its C functions by the prefix `_fn`; partial and end are its own."""
 
-    def __init__(self, model, lexicon, am_threshold, word_penalty, kernel, max_streams, max_frames):
+    _fn = None
+
+    def __init__(self, model, net, params, max_streams, max_frames):
         self.model = model
         self.max_frames = int(max_frames)
         self.frames = {}  # frames pushed per open id
         self.h = C.c_void_p()
-        sp = SearchParams(am_threshold, word_penalty, kernel, 0)
-        _check(lib().sr_stream_open(model.h, lexicon.h, C.byref(sp), max_streams, max_frames, C.byref(self.h)))
+        _check(getattr(lib(), self._fn + "_open")(model.h, net.h, C.byref(params), max_streams, max_frames, C.byref(self.h)))
 
     def begin(self):
         """-> the id of a fresh utterance"""
         i = C.c_uint32()
-        _check(lib().sr_stream_begin(self.h, C.byref(i)))
+        _check(getattr(lib(), self._fn + "_begin")(self.h, C.byref(i)))
         self.frames[i.value] = 0
         return i.value
 
@@ -308,9 +309,30 @@ class Stream:
         parts = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1, self.model.dim) for f in frames.values()]
         off = np.concatenate([[0], np.cumsum([len(f) for f in parts])]).astype(np.uint64)
         feats = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, self.model.dim), np.float32))
-        _check(lib().sr_stream_push(self.h, len(ids), _ptr(ids), _ptr(feats) if len(feats) else None, _ptr(off)))
+        _check(getattr(lib(), self._fn + "_push")(self.h, len(ids), _ptr(ids), _ptr(feats) if len(feats) else None, _ptr(off)))
         for i, f in zip(ids, parts):
             self.frames[int(i)] += len(f)
+
+    def close(self):
+        if self.h:
+            getattr(lib(), self._fn + "_destroy")(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class Stream(_StreamSet):
+    """sr_stream handle: utterances fed frame by frame (sr_stream_*).  end() returns what Corpus.recognize returns for the whole
+    utterance; partial() after t frames what it returns for the first t frames."""
+
+    _fn = "sr_stream"
+
+    def __init__(self, model, lexicon, am_threshold, word_penalty, kernel, max_streams, max_frames):
+        super().__init__(model, lexicon, SearchParams(am_threshold, word_penalty, kernel, 0), max_streams, max_frames)
 
     def partial(self, id, frames=False):
         """-> the words so far (u32[]) [, frames pushed]"""
@@ -334,47 +356,17 @@ class Stream:
             return words
         return words, (tbs[: T + 1], tbw[: T + 1], tbb[: T + 1])
 
-    def close(self):
-        if self.h:
-            lib().sr_stream_destroy(self.h)
-            self.h = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class BigramStream:
+class BigramStream(_StreamSet):
     """sr_bigram_stream handle: utterances fed frame by frame to the bigram-LM search (sr_bigram_stream_*).  end() returns what
     Corpus.recognize_bigram returns for the whole utterance; partial() after t frames what it returns for the first t frames.
     Items are (words u32[], scores f32[], times u32[])."""
 
+    _fn = "sr_bigram_stream"
+
     def __init__(self, model, bigram, acoustic_pruning, lm_pruning, kernel, max_streams, max_frames, max_word_ends=0, flags=0):
-        self.model = model
-        self.max_frames = int(max_frames)
-        self.frames = {}  # frames pushed per open id
-        self.h = C.c_void_p()
         p = BigramParams(acoustic_pruning, lm_pruning, kernel, max_word_ends, flags)
-        _check(lib().sr_bigram_stream_open(model.h, bigram.h, C.byref(p), max_streams, max_frames, C.byref(self.h)))
-
-    def begin(self):
-        """-> the id of a fresh utterance"""
-        i = C.c_uint32()
-        _check(lib().sr_bigram_stream_begin(self.h, C.byref(i)))
-        self.frames[i.value] = 0
-        return i.value
-
-    def push(self, frames):
-        """frames: {id: float32 [k x dim]} -> one scoring and one search launch for all of them"""
-        ids = np.ascontiguousarray(list(frames.keys()), dtype=np.uint32)
-        parts = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1, self.model.dim) for f in frames.values()]
-        off = np.concatenate([[0], np.cumsum([len(f) for f in parts])]).astype(np.uint64)
-        feats = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, self.model.dim), np.float32))
-        _check(lib().sr_bigram_stream_push(self.h, len(ids), _ptr(ids), _ptr(feats) if len(feats) else None, _ptr(off)))
-        for i, f in zip(ids, parts):
-            self.frames[int(i)] += len(f)
+        super().__init__(model, bigram, p, max_streams, max_frames)
 
     def _out(self):
         cap = self.max_frames + 1
@@ -395,17 +387,6 @@ class BigramStream:
         _check(lib().sr_bigram_stream_end(self.h, id, _ptr(ow), _ptr(osc), _ptr(ot), len(ow), C.byref(n)))
         self.frames.pop(id)
         return ow[: n.value].copy(), osc[: n.value].copy(), ot[: n.value].copy()
-
-    def close(self):
-        if self.h:
-            lib().sr_bigram_stream_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 class Corpus:

@@ -179,9 +179,7 @@ struct sr_lexicon {
 
 struct sr_bigram {
   sr_model* model = nullptr;
-  uint32_t n_words = 0, silence = 0, n_positions = 0, max_slot_states = 0, silence_states = 0;
-  uint32_t row4_mask = 0;  // bit k: some word of slot row k (words k * 1024 .. k * 1024 + 1023) has four states (register layout)
-  float tdp[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+  srgpu::BigramArgs net{};  // the search net (kernels.h; build_bigram_net): only its network fields set, pointing into the buffers below
   DevBuf<uint32_t> slot_off, slot_mix;
   DevBuf<uint16_t> mixtures;
   DevBuf<uint32_t> pos_info, pos_slot;
@@ -195,18 +193,46 @@ struct sr_bigram {
   DevBuf<unsigned long long> gs_active; // ... and the SRGPU_BIGRAM_STATS counter
 };
 
-// A set of concurrently open utterances on one (model, lexicon) (sr_stream_*, srgpu_api.cpp).  Slot i holds one open utterance;
-// its device state (decode_stream_kernel) lives in the per-slot buffers below, its frame count on the host.
+// The slots of a stream set (sr_stream_*, sr_bigram_stream_*): slot i holds one open utterance, named by the id
+// slot + max_streams * generation, and its frame count.
+struct StreamSlots {
+  uint32_t max_streams = 0;
+  uint64_t max_frames = 0;
+  std::vector<uint8_t> open;        // [max_streams]
+  std::vector<uint32_t> id;         // [max_streams] id of the slot's current (or last) utterance
+  std::vector<uint32_t> generation; // [max_streams] of the next utterance begun in the slot
+  std::vector<uint64_t> frames;     // [max_streams] frames pushed so far
+  StreamSlots() = default;
+  StreamSlots(uint32_t n, uint64_t max_frames_)
+      : max_streams(n), max_frames(max_frames_), open(n, 0), id(n, 0), generation(n, 0), frames(n, 0) {}
+  // opens the first free slot for a fresh utterance, *out_id its id: the generation wraps before the id leaves 32 bits
+  int begin(uint32_t* out_id) {
+    uint32_t slot = 0;
+    while (slot < max_streams && open[slot]) slot++;
+    if (slot == max_streams) return srhost::fail(SR_ELIMIT, "all %u streams are open", max_streams);
+    uint32_t g = generation[slot];
+    if ((uint64_t)slot + (uint64_t)max_streams * g > 0xFFFFFFFFull) g = 0;
+    generation[slot] = g + 1;
+    id[slot] = slot + max_streams * g;
+    open[slot] = 1;
+    frames[slot] = 0;  // the first push starts from the initial state
+    *out_id = id[slot];
+    return SR_OK;
+  }
+  // the slot of an open utterance's id, or -1
+  int64_t find(uint32_t i) const {
+    const uint32_t slot = i % max_streams;
+    return open[slot] && id[slot] == i ? (int64_t)slot : -1;
+  }
+};
+
+// A set of concurrently open utterances on one (model, lexicon) (sr_stream_*, srgpu_api.cpp).  The device state of slot i's
+// utterance (decode_stream_kernel) lives in the per-slot buffers below.
 struct sr_stream {
   sr_model* model = nullptr;
   sr_lexicon* lex = nullptr;
   sr_search_params params{};
-  uint32_t max_streams = 0;
-  uint64_t max_frames = 0;
-  std::vector<uint8_t> open;        // [max_streams]
-  std::vector<uint32_t> id;         // [max_streams] id of the slot's current (or last) utterance: slot + max_streams * generation
-  std::vector<uint32_t> generation; // [max_streams] of the next utterance begun in the slot
-  std::vector<uint64_t> frames;     // [max_streams] frames pushed so far
+  StreamSlots slots;
   // per slot, device
   DevBuf<unsigned char> ws;         // decode_big_workspace(P) each
   DevBuf<srgpu::StreamState> state;
@@ -215,23 +241,17 @@ struct sr_stream {
   DevBuf<uint32_t> words;           // max_frames each
   // per push, sized by the largest push so far
   DevBuf<float> feats;
-  DevBuf<double> scores;
   DevBuf<srgpu::StreamJob> jobs;
 };
 
-// A set of concurrently open utterances on one (model, bigram search net) (sr_bigram_stream_*, srgpu_api.cpp).  Slot i holds one open
-// utterance; its device state (bigram_stream_kernel, global-states layout) lives in the per-slot buffers below, its frame count and
-// a copy of its BigramStreamState (read back after every push) on the host.
+// A set of concurrently open utterances on one (model, bigram search net) (sr_bigram_stream_*, srgpu_api.cpp).  The device state of
+// slot i's utterance (bigram_stream_kernel, global-states layout) lives in the per-slot buffers below, a copy of its BigramStreamState
+// (read back after every push) on the host.
 struct sr_bigram_stream {
   sr_model* model = nullptr;
   sr_bigram* bigram = nullptr;
   sr_bigram_params params{};
-  uint32_t max_streams = 0;
-  uint64_t max_frames = 0;
-  std::vector<uint8_t> open;        // [max_streams]
-  std::vector<uint32_t> id;         // [max_streams] slot + max_streams * generation, as sr_stream
-  std::vector<uint32_t> generation;
-  std::vector<uint64_t> frames;     // [max_streams] frames pushed so far
+  StreamSlots slots;
   std::vector<srgpu::BigramStreamState> host_state;  // [max_streams] as of the slot's last push
   std::vector<uint8_t> failed;      // [max_streams] a push flagged the slot (SR_EINTERNAL until it ends)
   // per slot, device
@@ -245,7 +265,6 @@ struct sr_bigram_stream {
   std::vector<std::unique_ptr<DevBuf<uint4>>> book;  // [max_streams] grown before a push to n_book + W x (its frames)
   // per push, sized by the largest push so far
   DevBuf<float> feats;
-  DevBuf<double> scores;
   DevBuf<srgpu::BigramStreamJob> jobs;
 };
 

@@ -313,6 +313,15 @@ hipError_t launch_bigram(const BigramArgs& a, hipStream_t stream);
 size_t bigram_lds_bytes(uint32_t n_words, uint32_t n_positions);
 bool bigram_register_layout(const BigramArgs& a);   // short words, <= 3072 of them, the emission row fits the LDS beside the lists
 uint32_t bigram_max_words();
+// The search net, built on the host beside the kernels that read it (as build_decode_net) from a lexicon of n_words words, word w's
+// emission states mixtures[word_off[w] .. word_off[w + 1]), the dense [W x W] table lm[w * W + h] = -log p(w | h) and tdp
+// [isSilence][loop, forward, skip, exit].  Returns a BigramArgs with only the network's scalars set (n_words, silence, n_positions, tdp,
+// max_slot_states, silence_states, row4_mask) and writes its arrays into the vectors; sr_bigram_create uploads those and mixtures and
+// sets the pointers.
+BigramArgs build_bigram_net(uint32_t n_words, const uint32_t* word_off, const uint16_t* mixtures, uint32_t silence_word, const float* lm,
+                            const float tdp[8], std::vector<uint32_t>& slot_off, std::vector<uint32_t>& slot_mix,
+                            std::vector<uint32_t>& pos_info, std::vector<uint32_t>& pos_slot, std::vector<float>& lmT,
+                            std::vector<float>& lm_rowmin, std::vector<float>& lm_rowmax);
 // streaming (sr_bigram_stream_push): bigram_stream_kernel advances each of n open utterances by k frames on the global-states layout,
 // from the state the last push left in device memory.  Per stream slot: the state image (a.gs_ws, bigram_gs_ws_words each), the two
 // word-end lists (a.we_*, 2 x 2W entries each), the active list (lsave, 2W), a BigramStreamState, the book (its own allocation, grown by

@@ -659,43 +659,69 @@ int check_corpus(const sr_model* m, const sr_corpus* c) {
 
 }  // namespace
 
-namespace {  // sr_stream_*
-// the slot of an open utterance's id, or -1
-int64_t stream_slot(const sr_stream* s, uint32_t id) {
-  const uint32_t slot = id % s->max_streams;
-  return s->open[slot] && s->id[slot] == id ? (int64_t)slot : -1;
+namespace {  // sr_stream_*, sr_bigram_stream_*
+// an entry of a push with frames: its stream slot, the frames searched before the push, the frames in it, its first frame's row in
+// the push's features
+struct PushEntry { uint32_t slot; uint64_t t0, k, row0; };
+// checks a push against the open utterances -- every id open and named once, frame_off ascending from 0, no utterance past
+// max_frames -- and lists its entries with frames (none for an empty push)
+int check_push(const StreamSlots& sl, uint32_t n, const uint32_t* ids, const uint64_t* frame_off, std::vector<PushEntry>* out) {
+  if (n == 0) return SR_OK;
+  if (!ids || !frame_off) return fail(SR_EINVAL, "null argument");
+  if (frame_off[0] != 0) return fail(SR_EINVAL, "frame_off[0] must be 0");
+  std::vector<uint8_t> seen(sl.max_streams, 0);
+  for (uint32_t i = 0; i < n; i++) {
+    const int64_t slot = sl.find(ids[i]);
+    if (slot < 0) return fail(SR_EINVAL, "push entry %u: stream id %u is not open", i, ids[i]);
+    if (seen[slot]) return fail(SR_EINVAL, "push entry %u: stream id %u appears twice in one push", i, ids[i]);
+    seen[slot] = 1;
+    if (frame_off[i + 1] < frame_off[i]) return fail(SR_EINVAL, "frame_off is not ascending at entry %u", i);
+    const uint64_t k = frame_off[i + 1] - frame_off[i];
+    if (k > sl.max_frames - sl.frames[slot])
+      return fail(SR_ELIMIT, "stream id %u: %llu + %llu frames exceed max_frames %llu", ids[i], (unsigned long long)sl.frames[slot],
+                  (unsigned long long)k, (unsigned long long)sl.max_frames);
+    if (k) out->push_back({(uint32_t)slot, sl.frames[slot], k, frame_off[i]});
+  }
+  return SR_OK;
 }
+// A push's pass: its F frames and its jobs staged on the device, then one chunk of run_chunks -- the frames scored into m->scores[0],
+// search(chunk, table, stream) enqueuing the push's search.  (Every call synchronises before it returns: the buffer is free.)
+template <class Job, class Search>
+int push_pass(sr_model* m, int gmm_kernel, const float* feats, uint64_t F, DevBuf<float>& d_feats, const std::vector<Job>& jobs,
+              DevBuf<Job>& d_jobs, Search search) {
+  HIP_TRY(d_feats.ensure((size_t)F * m->dim));
+  HIP_TRY(m->scores[0].ensure((size_t)F * m->ld));
+  HIP_TRY(d_jobs.ensure(jobs.size()));
+  HIP_TRY(hipMemcpyAsync(d_feats.p, feats, sizeof(float) * F * m->dim, hipMemcpyHostToDevice, m->s_gmm));
+  HIP_TRY(hipMemcpyAsync(d_jobs.p, jobs.data(), sizeof(Job) * jobs.size(), hipMemcpyHostToDevice, m->s_gmm));
+  return run_chunks(m, {Chunk{0, (uint32_t)jobs.size(), 0, F}},
+                    [&](const Chunk&, double* table) { return launch_scoring(m, d_feats.p, F, gmm_kernel, table); }, search);
+}
+
 // the partial (after every push) or final words of the utterance in `slot`
 int stream_words(sr_stream* s, uint32_t slot, uint32_t id, uint32_t* out_words, uint32_t cap, uint32_t* count) {
   *count = 0;
-  if (s->frames[slot] == 0) return SR_OK;  // nothing searched yet: the empty utterance's (no) words
+  if (s->slots.frames[slot] == 0) return SR_OK;  // nothing searched yet: the empty utterance's (no) words
   StreamState st;
   HIP_TRY(hipMemcpy(&st, s->state.p + slot, sizeof(st), hipMemcpyDeviceToHost));
   if (st.flags & kFlagCorrupt) return fail(SR_ECORRUPT, "stream %u: the traceback does not walk back to frame 0 (Recognizer.cpp:222-231)", id);
-  if (st.count > s->frames[slot]) return fail(SR_ECORRUPT, "stream %u: %u words for %llu frames", id, st.count, (unsigned long long)s->frames[slot]);
+  if (st.count > s->slots.frames[slot]) return fail(SR_ECORRUPT, "stream %u: %u words for %llu frames", id, st.count, (unsigned long long)s->slots.frames[slot]);
   *count = st.count;
   if (st.count > cap) return fail(SR_EINVAL, "stream %u: %u words, out_words holds %u", id, st.count, cap);
-  if (st.count) HIP_TRY(hipMemcpy(out_words, s->words.p + (size_t)slot * s->max_frames, sizeof(uint32_t) * st.count, hipMemcpyDeviceToHost));
+  if (st.count) HIP_TRY(hipMemcpy(out_words, s->words.p + (size_t)slot * s->slots.max_frames, sizeof(uint32_t) * st.count, hipMemcpyDeviceToHost));
   return SR_OK;
-}
-}  // namespace
-
-namespace {  // sr_bigram_stream_*
-int64_t bigram_stream_slot(const sr_bigram_stream* s, uint32_t id) {
-  const uint32_t slot = id % s->max_streams;
-  return s->open[slot] && s->id[slot] == id ? (int64_t)slot : -1;
 }
 // the partial (after every push) or final traceback items of the utterance in `slot`: the state record read back after its last push
 int bigram_stream_items(sr_bigram_stream* s, uint32_t slot, uint32_t id, uint32_t* out_word, float* out_score, uint32_t* out_time,
                         uint32_t cap, uint32_t* count) {
   *count = 0;
-  if (s->frames[slot] == 0) return SR_OK;  // nothing searched yet: the empty utterance's (no) items
+  if (s->slots.frames[slot] == 0) return SR_OK;  // nothing searched yet: the empty utterance's (no) items
   if (s->failed[slot]) return fail(SR_EINTERNAL, "stream %u: a push overflowed its book", id);
   const BigramStreamState& st = s->host_state[slot];
   if (st.flags & kBgStreamCorrupt) return fail(SR_ECORRUPT, "stream %u: the book walk does not end at its start entry", id);
   *count = st.count;
   if (st.count > cap) return fail(SR_EINVAL, "stream %u: %u items, the output arrays hold %u", id, st.count, cap);
-  const size_t o = (size_t)slot * (s->max_frames + 1);
+  const size_t o = (size_t)slot * (s->slots.max_frames + 1);
   if (st.count) {
     HIP_TRY(hipMemcpy(out_word, s->out_word.p + o, sizeof(uint32_t) * st.count, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(out_score, s->out_score.p + o, sizeof(float) * st.count, hipMemcpyDeviceToHost));
@@ -1230,58 +1256,30 @@ int sr_bigram_create(sr_model* m, uint32_t n_words, const uint32_t* word_off, co
     for (uint32_t i = word_off[w]; i < word_off[w + 1]; i++)
       if (mixtures[i] >= m->n_states) return fail(SR_EINVAL, "word %u: mixture %u out of range", w, mixtures[i]);
   }
-  // slots: words 0..W-1, then the silence copy of every word (Teaching::LinearSearch: silenceCopy :202-205)
+  // (slots: the words, then the silence copy of every word -- build_bigram_net)
   const uint32_t n_sil = word_off[silence_word + 1] - word_off[silence_word];
   if ((uint64_t)word_off[W] + (uint64_t)W * n_sil > bigram_max_positions())
     return fail(SR_ELIMIT, "%llu positions (words and their silence copies): the bigram search handles at most %u",
                 (unsigned long long)word_off[W] + (unsigned long long)W * n_sil, bigram_max_positions());
-  std::vector<uint32_t> slot_off(2 * (size_t)W + 1, 0), slot_mix(2 * (size_t)W);
-  for (uint32_t a = 0; a < 2 * W; a++) {
-    const uint32_t aw = a < W ? a : silence_word;
-    slot_off[a + 1] = slot_off[a] + (a < W ? word_off[a + 1] - word_off[a] : n_sil);
-    slot_mix[a] = word_off[aw];
-  }
-  const uint32_t P2 = slot_off[2 * W];
-  // per dense position: emission state | flags << 16 and the slot (the state update runs one thread per position)
-  std::vector<uint32_t> pos_info(P2);
-  std::vector<uint32_t> pos_slot(P2);
-  for (uint32_t a = 0; a < 2 * W; a++) {
-    const uint32_t n = slot_off[a + 1] - slot_off[a], sil = (a >= W || a == silence_word) ? 8u : 0u;
-    for (uint32_t k = 0; k < n; k++) {
-      const uint32_t flags = (k == 0 ? 1u : 0u) | (k == 1 ? 2u : 0u) | (k == n - 1 ? 4u : 0u) | sil;
-      pos_info[slot_off[a] + k] = (uint32_t)mixtures[slot_mix[a] + k] | (flags << 16);
-      pos_slot[slot_off[a] + k] = a;
-    }
-  }
-  // (every lexicon within these limits has a layout: the register layout, the dense LDS image, or the state hypotheses in device
-  // memory -- bigram_layout, viterbi_bigram.hip)
-  std::vector<float> lmT((size_t)W * W);
-  for (uint32_t w = 0; w < W; w++)
-    for (uint32_t h = 0; h < W; h++) lmT[(size_t)h * W + w] = lm[(size_t)w * W + h];
-  std::vector<float> rowmin(W, std::numeric_limits<float>::infinity()), rowmax(W, -std::numeric_limits<float>::infinity());
-  for (uint32_t h = 0; h < W; h++)
-    for (uint32_t w = 0; w < W; w++) {
-      if (w == silence_word) continue;  // no transition into silence through the LM (LinearSearch.cc:231)
-      const float v = lmT[(size_t)h * W + w];
-      // NaN entries: the bounds become NaN and the skip test fails safe (nothing is skipped against a NaN bound)
-      rowmin[h] = (v < rowmin[h] || v != v) ? v : rowmin[h];
-      rowmax[h] = (v > rowmax[h] || v != v) ? v : rowmax[h];
-    }
+  std::vector<uint32_t> slot_off, slot_mix, pos_info, pos_slot;
+  std::vector<float> lmT, rowmin, rowmax;
   sr_bigram* b = new sr_bigram();
   std::unique_ptr<sr_bigram, int (*)(sr_bigram*)> own(b, sr_bigram_destroy);
-  b->model = m; b->n_words = W; b->silence = silence_word; b->n_positions = P2;
-  for (uint32_t a2 = 0; a2 < 2 * W; a2++) b->max_slot_states = std::max(b->max_slot_states, slot_off[a2 + 1] - slot_off[a2]);
-  b->silence_states = n_sil;
-  for (uint32_t w = 0; w < W; w++)  // (words only: a silence copy has the silence word's one state in the register layout)
-    if (slot_off[w + 1] - slot_off[w] >= 4) b->row4_mask |= 1u << (w / 1024u);
-  memcpy(b->tdp, tdp, sizeof(b->tdp));
+  b->model = m;
+  // (every lexicon within these limits has a layout: the register layout, the dense LDS image, or the state hypotheses in device
+  // memory -- bigram_layout, viterbi_bigram.hip)
+  b->net = build_bigram_net(W, word_off, mixtures, silence_word, lm, tdp, slot_off, slot_mix, pos_info, pos_slot, lmT, rowmin, rowmax);
   hipError_t e;
   if ((e = b->slot_off.upload(slot_off.data(), slot_off.size())) != hipSuccess ||
       (e = b->slot_mix.upload(slot_mix.data(), slot_mix.size())) != hipSuccess ||
       (e = b->mixtures.upload(mixtures, word_off[W])) != hipSuccess || (e = b->lmT.upload(lmT.data(), lmT.size())) != hipSuccess ||
       (e = b->lm_rowmin.upload(rowmin.data(), W)) != hipSuccess || (e = b->lm_rowmax.upload(rowmax.data(), W)) != hipSuccess ||
-      (e = b->pos_info.upload(pos_info.data(), P2)) != hipSuccess || (e = b->pos_slot.upload(pos_slot.data(), P2)) != hipSuccess)
+      (e = b->pos_info.upload(pos_info.data(), pos_info.size())) != hipSuccess ||
+      (e = b->pos_slot.upload(pos_slot.data(), pos_slot.size())) != hipSuccess)
     return fail(SR_EHIP, "bigram upload: %s", hipGetErrorString(e));
+  BigramArgs& net = b->net;
+  net.slot_off = b->slot_off.p; net.slot_mix = b->slot_mix.p; net.mixtures = b->mixtures.p; net.pos_info = b->pos_info.p;
+  net.pos_slot = b->pos_slot.p; net.lmT = b->lmT.p; net.lm_rowmin = b->lm_rowmin.p; net.lm_rowmax = b->lm_rowmax.p;
   *out = own.release();
   return SR_OK;
   });
@@ -1291,10 +1289,7 @@ int sr_bigram_destroy(sr_bigram* b) {
   return guarded(__func__, [&]() -> int {
   if (!b) return SR_OK;
   if (b->model) { (void)hipSetDevice(b->model->device); (void)hipDeviceSynchronize(); }
-  b->slot_off.release(); b->slot_mix.release(); b->mixtures.release(); b->pos_info.release(); b->pos_slot.release(); b->lmT.release(); b->lm_rowmin.release(); b->lm_rowmax.release();
-  b->we_slot.release(); b->we_bp.release(); b->we_score.release(); b->book.release(); b->book_off.release(); b->gs_ws.release(); b->gs_active.release();
-  b->out_word.release(); b->out_time.release(); b->out_score.release(); b->out_count.release(); b->out_flags.release();
-  delete b;
+  delete b;  // (the buffers go with it)
   return SR_OK;
   });
 }
@@ -1306,7 +1301,7 @@ int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr
   if (rc) return rc;
   if (!b || b->model != m) return fail(SR_EINVAL, "bigram search net does not belong to this model");
   if (!p || !out_off || ((!out_word || !out_score || !out_time) && c->n_frames)) return fail(SR_EINVAL, "null argument");
-  const uint32_t U = c->n_utts, W = b->n_words;
+  const uint32_t U = c->n_utts, W = b->net.n_words;
   const uint64_t F = c->n_frames;
   std::vector<Chunk> chunks;
   if ((rc = prepare_chunks(m, c, &chunks))) return rc;
@@ -1327,27 +1322,23 @@ int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr
   HIP_TRY(b->out_count.ensure(U));
   HIP_TRY(b->out_flags.ensure(U));
 
-  BigramArgs ba{};
+  BigramArgs ba = b->net;
   ba.ld = m->ld; ba.frame_off = c->d_frame_off.p; ba.utt_order = c->utt_order.p;
-  ba.n_words = W; ba.silence = b->silence; ba.n_positions = b->n_positions;
-  ba.slot_off = b->slot_off.p; ba.slot_mix = b->slot_mix.p; ba.mixtures = b->mixtures.p; ba.pos_info = b->pos_info.p; ba.pos_slot = b->pos_slot.p; ba.lmT = b->lmT.p; ba.lm_rowmin = b->lm_rowmin.p; ba.lm_rowmax = b->lm_rowmax.p;
-  memcpy(ba.tdp, b->tdp, sizeof(ba.tdp));
   ba.ac_pruning = p->acoustic_pruning; ba.lm_pruning = p->lm_pruning;
   if (p->flags & ~(SR_BIGRAM_DENSE_STATES | SR_BIGRAM_GLOBAL_STATES)) return fail(SR_EINVAL, "unknown sr_bigram_params.flags 0x%x", (unsigned)p->flags);
   if ((p->flags & SR_BIGRAM_DENSE_STATES) && (p->flags & SR_BIGRAM_GLOBAL_STATES))
     return fail(SR_EINVAL, "SR_BIGRAM_DENSE_STATES and SR_BIGRAM_GLOBAL_STATES exclude each other");
-  ba.max_slot_states = b->max_slot_states; ba.silence_states = b->silence_states; ba.row4_mask = b->row4_mask;
   ba.dense_states = (p->flags & SR_BIGRAM_DENSE_STATES) ? 1u : 0u;
   ba.global_states = (p->flags & SR_BIGRAM_GLOBAL_STATES) ? 1u : 0u;
   const BigramLayout layout = bigram_layout(ba);
   if (layout == BigramLayout::kNone)
-    return fail(SR_ELIMIT, "this lexicon's dense LDS image would take %zu bytes > 160 KiB (SR_BIGRAM_DENSE_STATES)", bigram_lds_bytes(W, b->n_positions));
+    return fail(SR_ELIMIT, "this lexicon's dense LDS image would take %zu bytes > 160 KiB (SR_BIGRAM_DENSE_STATES)", bigram_lds_bytes(W, ba.n_positions));
   if (layout == BigramLayout::kGlobal) {
     // a bounded, persistent grid (two workgroups per CU at most, each looping over its utterances): the state images take
     // grid x gs_ws_words x 4 bytes whatever the corpus size -- and at most a quarter of the free device memory
     int dev_cus = 0;
     HIP_TRY(hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, m->device));
-    const uint64_t per_wg = bigram_gs_ws_words(W, b->n_positions);
+    const uint64_t per_wg = bigram_gs_ws_words(W, ba.n_positions);
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     const uint64_t have = b->gs_ws.n / per_wg;  // (workgroups the workspace of an earlier call holds)
@@ -1374,7 +1365,7 @@ int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr
         ba.scores = table; ba.frame_base = ch.f0; ba.utt_first = ch.u0; ba.n_utts = ch.u1 - ch.u0;
         HIP_TRY(launch_bigram(ba, s));  // (invalid value: a layout without the workspace it needs -- a bug here, not the caller's)
         // SURVEY 8(d)'s decoder model, 8 S + 4 P bytes per frame, with P = the bigram search's positions (words + their silence copies)
-        if (m->profiling) m->prof.search_bytes += (8.0 * m->n_states + 4.0 * b->n_positions) * (double)(ch.f1 - ch.f0);
+        if (m->profiling) m->prof.search_bytes += (8.0 * m->n_states + 4.0 * ba.n_positions) * (double)(ch.f1 - ch.f0);
         return SR_OK;
       });
   if (rc) return rc;
@@ -1411,9 +1402,8 @@ int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr
 int sr_bigram_describe(const sr_bigram* b, char* out, size_t cap) {
   return guarded(__func__, [&]() -> int {
   if (!b || !out || cap == 0) return fail(SR_EINVAL, "null argument");
-  BigramArgs ba{};
-  ba.n_words = b->n_words; ba.n_positions = b->n_positions; ba.ld = b->model ? b->model->ld : 0;
-  ba.max_slot_states = b->max_slot_states; ba.silence_states = b->silence_states;
+  BigramArgs ba = b->net;
+  ba.ld = b->model ? b->model->ld : 0;
   const BigramLayout layout = bigram_layout(ba);
   snprintf(out, cap, "%s", layout == BigramLayout::kRegisters ? "registers" : layout == BigramLayout::kLds ? "lds" : "global");
   return SR_OK;
@@ -1740,8 +1730,7 @@ int sr_stream_open(sr_model* m, sr_lexicon* l, const sr_search_params* p, uint32
   if (l->net.n_slots > decode_big_max_slots()) return fail(SR_ELIMIT, "%u trellis positions exceed the stream search's limit of %u", l->net.n_slots, decode_big_max_slots());
   sr_stream* s = new sr_stream();
   std::unique_ptr<sr_stream, int (*)(sr_stream*)> own(s, sr_stream_destroy);
-  s->model = m; s->lex = l; s->params = *p; s->max_streams = max_streams; s->max_frames = max_frames;
-  s->open.assign(max_streams, 0); s->id.assign(max_streams, 0); s->generation.assign(max_streams, 0); s->frames.assign(max_streams, 0);
+  s->model = m; s->lex = l; s->params = *p; s->slots = StreamSlots(max_streams, max_frames);
   const size_t S = max_streams;
   HIP_TRY(s->ws.ensure(S * decode_big_workspace(l->net.n_slots)));
   HIP_TRY(s->state.ensure(S));
@@ -1757,75 +1746,40 @@ int sr_stream_open(sr_model* m, sr_lexicon* l, const sr_search_params* p, uint32
 int sr_stream_begin(sr_stream* s, uint32_t* id) {
   return guarded(__func__, [&]() -> int {
   if (!s || !id) return fail(SR_EINVAL, "null argument");
-  uint32_t slot = 0;
-  while (slot < s->max_streams && s->open[slot]) slot++;
-  if (slot == s->max_streams) return fail(SR_ELIMIT, "all %u streams are open", s->max_streams);
-  // id = slot + max_streams * generation, the generation wrapping before the id leaves 32 bits
-  uint32_t g = s->generation[slot];
-  if ((uint64_t)slot + (uint64_t)s->max_streams * g > 0xFFFFFFFFull) g = 0;
-  s->generation[slot] = g + 1;
-  s->id[slot] = slot + s->max_streams * g;
-  s->open[slot] = 1;
-  s->frames[slot] = 0;  // the first push starts from the initial state (decode_stream_kernel)
-  *id = s->id[slot];
-  return SR_OK;
+  return s->slots.begin(id);  // (the first push starts from the initial state: decode_stream_kernel)
   });
 }
 
 int sr_stream_push(sr_stream* s, uint32_t n, const uint32_t* ids, const float* feats, const uint64_t* frame_off) {
   return guarded(__func__, [&]() -> int {
   if (!s) return fail(SR_EINVAL, "null stream set");
-  if (n == 0) return SR_OK;
-  if (!ids || !frame_off) return fail(SR_EINVAL, "null argument");
-  if (frame_off[0] != 0) return fail(SR_EINVAL, "frame_off[0] must be 0");
-  std::vector<uint8_t> seen(s->max_streams, 0);
-  std::vector<StreamJob> jobs;
-  for (uint32_t i = 0; i < n; i++) {
-    const int64_t slot = stream_slot(s, ids[i]);
-    if (slot < 0) return fail(SR_EINVAL, "push entry %u: stream id %u is not open", i, ids[i]);
-    if (seen[slot]) return fail(SR_EINVAL, "push entry %u: stream id %u appears twice in one push", i, ids[i]);
-    seen[slot] = 1;
-    if (frame_off[i + 1] < frame_off[i]) return fail(SR_EINVAL, "frame_off is not ascending at entry %u", i);
-    const uint64_t k = frame_off[i + 1] - frame_off[i];
-    if (k > s->max_frames - s->frames[slot])
-      return fail(SR_ELIMIT, "stream id %u: %llu + %llu frames exceed max_frames %llu", ids[i], (unsigned long long)s->frames[slot],
-                  (unsigned long long)k, (unsigned long long)s->max_frames);
-    if (k) jobs.push_back({(uint32_t)slot, (uint32_t)s->frames[slot], (uint32_t)k, 0u, frame_off[i]});
-  }
-  const uint64_t F = frame_off[n];
-  if (F == 0) return SR_OK;
+  std::vector<PushEntry> entries;
+  int rc = check_push(s->slots, n, ids, frame_off, &entries);
+  if (rc || entries.empty()) return rc;
   if (!feats) return fail(SR_EINVAL, "null feats");
   sr_model* m = s->model;
-  sr_lexicon* l = s->lex;
-  int rc = check_model(m);
+  const sr_lexicon* l = s->lex;
+  if ((rc = check_model(m))) return rc;
+  std::vector<StreamJob> jobs;
+  for (const PushEntry& e : entries) jobs.push_back({e.slot, (uint32_t)e.t0, (uint32_t)e.k, 0u, e.row0});
+  const uint64_t F = frame_off[n];
+  rc = push_pass(m, s->params.gmm_kernel, feats, F, s->feats, jobs, s->jobs, [&](const Chunk&, const double* table, hipStream_t st) -> int {
+    StreamArgs a{};
+    a.net = l->net;
+    a.am_threshold = s->params.am_threshold; a.word_penalty = s->params.word_penalty;
+    a.scores = table; a.ld = m->ld; a.jobs = s->jobs.p;
+    a.ws = s->ws.p; a.ws_stride = decode_big_workspace(l->net.n_slots); a.state = s->state.p;
+    a.tb_score = s->tb_score.p; a.tb_word = s->tb_word.p; a.tb_bkp = s->tb_bkp.p; a.tb_stride = s->slots.max_frames + 1;
+    a.words = s->words.p; a.words_stride = s->slots.max_frames;
+    HIP_TRY(launch_decode_stream(a, (uint32_t)jobs.size(), st));
+    if (m->profiling) {
+      m->prof.search_bytes += (8.0 * m->n_states + 4.0 * l->net.n_slots) * (double)F;
+      m->prof.frames += F;
+    }
+    return SR_OK;
+  });
   if (rc) return rc;
-  HIP_TRY(s->feats.ensure((size_t)F * m->dim));
-  HIP_TRY(s->scores.ensure((size_t)F * m->ld));
-  HIP_TRY(s->jobs.ensure(jobs.size()));
-  HIP_TRY(hipMemcpyAsync(s->feats.p, feats, sizeof(float) * F * m->dim, hipMemcpyHostToDevice, m->s_gmm));
-  HIP_TRY(hipMemcpyAsync(s->jobs.p, jobs.data(), sizeof(StreamJob) * jobs.size(), hipMemcpyHostToDevice, m->s_gmm));
-  if ((rc = launch_scoring(m, s->feats.p, F, s->params.gmm_kernel, s->scores.p))) return rc;
-  const hipStream_t s_search = m->overlap ? m->s_search : m->s_gmm;
-  HIP_TRY(hipEventRecord(m->ev_scored[0], m->s_gmm));
-  HIP_TRY(hipStreamWaitEvent(s_search, m->ev_scored[0], 0));
-  StreamArgs a{};
-  a.net = l->net;
-  a.am_threshold = s->params.am_threshold; a.word_penalty = s->params.word_penalty;
-  a.scores = s->scores.p; a.ld = m->ld; a.jobs = s->jobs.p;
-  a.ws = s->ws.p; a.ws_stride = decode_big_workspace(l->net.n_slots); a.state = s->state.p;
-  a.tb_score = s->tb_score.p; a.tb_word = s->tb_word.p; a.tb_bkp = s->tb_bkp.p; a.tb_stride = s->max_frames + 1;
-  a.words = s->words.p; a.words_stride = s->max_frames;
-  EventPair ep{};
-  if ((rc = prof_begin(m, s_search, 1, &ep))) return rc;
-  HIP_TRY(launch_decode_stream(a, (uint32_t)jobs.size(), s_search));
-  if ((rc = prof_end(m, s_search, &ep))) return rc;
-  HIP_TRY(hipStreamSynchronize(s_search));
-  HIP_TRY(hipStreamSynchronize(m->s_gmm));
-  for (const StreamJob& j : jobs) s->frames[j.slot] += j.k;
-  if (m->profiling) {
-    m->prof.search_bytes += (8.0 * m->n_states + 4.0 * l->net.n_slots) * (double)F;
-    m->prof.frames += F;
-  }
+  for (const StreamJob& j : jobs) s->slots.frames[j.slot] += j.k;
   return SR_OK;
   });
 }
@@ -1833,11 +1787,11 @@ int sr_stream_push(sr_stream* s, uint32_t n, const uint32_t* ids, const float* f
 int sr_stream_partial(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_t cap, uint32_t* count, uint64_t* frames) {
   return guarded(__func__, [&]() -> int {
   if (!s || !count || (!out_words && cap)) return fail(SR_EINVAL, "null argument");
-  const int64_t slot = stream_slot(s, id);
+  const int64_t slot = s->slots.find(id);
   if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
   int rc = check_model(s->model);
   if (rc) return rc;
-  if (frames) *frames = s->frames[slot];
+  if (frames) *frames = s->slots.frames[slot];
   return stream_words(s, (uint32_t)slot, id, out_words, cap, count);
   });
 }
@@ -1846,24 +1800,24 @@ int sr_stream_end(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_t cap, 
                   uint16_t* tb_bkp) {
   return guarded(__func__, [&]() -> int {
   if (!s || !count || (!out_words && cap)) return fail(SR_EINVAL, "null argument");
-  const int64_t slot = stream_slot(s, id);
+  const int64_t slot = s->slots.find(id);
   if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
   int rc = check_model(s->model);
   if (rc) return rc;
   rc = stream_words(s, (uint32_t)slot, id, out_words, cap, count);
   if (rc == SR_EINVAL) return rc;  // too small a buffer: the utterance stays open
-  const uint64_t T = s->frames[slot];
+  const uint64_t T = s->slots.frames[slot];
   if (rc == SR_OK && T == 0) {  // traceback[0] of the empty utterance (Recognizer.cpp:118-120)
     if (tb_score) tb_score[0] = 0.0;
     if (tb_word) tb_word[0] = 0;
     if (tb_bkp) tb_bkp[0] = 0;
   } else if (rc == SR_OK) {
-    const size_t b = (size_t)slot * (s->max_frames + 1);
+    const size_t b = (size_t)slot * (s->slots.max_frames + 1);
     if (tb_score) HIP_TRY(hipMemcpy(tb_score, s->tb_score.p + b, sizeof(double) * (T + 1), hipMemcpyDeviceToHost));
     if (tb_word) HIP_TRY(hipMemcpy(tb_word, s->tb_word.p + b, sizeof(uint16_t) * (T + 1), hipMemcpyDeviceToHost));
     if (tb_bkp) HIP_TRY(hipMemcpy(tb_bkp, s->tb_bkp.p + b, sizeof(uint16_t) * (T + 1), hipMemcpyDeviceToHost));
   }
-  s->open[slot] = 0;
+  s->slots.open[slot] = 0;
   return rc;
   });
 }
@@ -1897,11 +1851,10 @@ int sr_bigram_stream_open(sr_model* m, sr_bigram* b, const sr_bigram_params* p, 
   if (max_frames > 0xFFFFFFFEull) return fail(SR_ELIMIT, "max_frames %llu: frame times are 32 bit", (unsigned long long)max_frames);
   sr_bigram_stream* s = new sr_bigram_stream();
   std::unique_ptr<sr_bigram_stream, int (*)(sr_bigram_stream*)> own(s, sr_bigram_stream_destroy);
-  s->model = m; s->bigram = b; s->params = *p; s->max_streams = max_streams; s->max_frames = max_frames;
-  s->open.assign(max_streams, 0); s->id.assign(max_streams, 0); s->generation.assign(max_streams, 0); s->frames.assign(max_streams, 0);
+  s->model = m; s->bigram = b; s->params = *p; s->slots = StreamSlots(max_streams, max_frames);
   s->host_state.assign(max_streams, BigramStreamState{}); s->failed.assign(max_streams, 0);
-  const size_t S = max_streams, W = b->n_words;
-  HIP_TRY(s->gs_ws.ensure(S * bigram_gs_ws_words(b->n_words, b->n_positions)));
+  const size_t S = max_streams, W = b->net.n_words;
+  HIP_TRY(s->gs_ws.ensure(S * bigram_gs_ws_words(b->net.n_words, b->net.n_positions)));
   HIP_TRY(s->we_slot.ensure(S * 4 * W));
   HIP_TRY(s->we_bp.ensure(S * 4 * W));
   HIP_TRY(s->we_score.ensure(S * 4 * W));
@@ -1919,19 +1872,12 @@ int sr_bigram_stream_open(sr_model* m, sr_bigram* b, const sr_bigram_params* p, 
 int sr_bigram_stream_begin(sr_bigram_stream* s, uint32_t* id) {
   return guarded(__func__, [&]() -> int {
   if (!s || !id) return fail(SR_EINVAL, "null argument");
-  uint32_t slot = 0;
-  while (slot < s->max_streams && s->open[slot]) slot++;
-  if (slot == s->max_streams) return fail(SR_ELIMIT, "all %u streams are open", s->max_streams);
-  uint32_t g = s->generation[slot];  // (ids as sr_stream_begin)
-  if ((uint64_t)slot + (uint64_t)s->max_streams * g > 0xFFFFFFFFull) g = 0;
-  s->generation[slot] = g + 1;
-  s->id[slot] = slot + s->max_streams * g;
-  s->open[slot] = 1;
-  s->frames[slot] = 0;  // the first push starts from the initial state (bigram_stream_kernel)
+  int rc = s->slots.begin(id);  // (the first push starts from the initial state: bigram_stream_kernel)
+  if (rc) return rc;
+  const uint32_t slot = *id % s->slots.max_streams;
   s->host_state[slot] = BigramStreamState{};
   s->host_state[slot].n_book = 2;  // the two start entries the first push writes
   s->failed[slot] = 0;
-  *id = s->id[slot];
   return SR_OK;
   });
 }
@@ -1939,38 +1885,25 @@ int sr_bigram_stream_begin(sr_bigram_stream* s, uint32_t* id) {
 int sr_bigram_stream_push(sr_bigram_stream* s, uint32_t n, const uint32_t* ids, const float* feats, const uint64_t* frame_off) {
   return guarded(__func__, [&]() -> int {
   if (!s) return fail(SR_EINVAL, "null stream set");
-  if (n == 0) return SR_OK;
-  if (!ids || !frame_off) return fail(SR_EINVAL, "null argument");
-  if (frame_off[0] != 0) return fail(SR_EINVAL, "frame_off[0] must be 0");
-  sr_bigram* b = s->bigram;
-  const uint64_t W = b->n_words;
-  std::vector<uint8_t> seen(s->max_streams, 0);
+  std::vector<PushEntry> entries;
+  int rc = check_push(s->slots, n, ids, frame_off, &entries);
+  if (rc) return rc;
+  const sr_bigram* b = s->bigram;
   std::vector<BigramStreamJob> jobs;
   std::vector<uint64_t> need;  // per job: book entries the push may reach (n_book + W per frame: a frame keeps at most one word end per history)
-  for (uint32_t i = 0; i < n; i++) {
-    const int64_t slot = bigram_stream_slot(s, ids[i]);
-    if (slot < 0) return fail(SR_EINVAL, "push entry %u: stream id %u is not open", i, ids[i]);
-    if (seen[slot]) return fail(SR_EINVAL, "push entry %u: stream id %u appears twice in one push", i, ids[i]);
-    seen[slot] = 1;
-    if (frame_off[i + 1] < frame_off[i]) return fail(SR_EINVAL, "frame_off is not ascending at entry %u", i);
-    const uint64_t k = frame_off[i + 1] - frame_off[i];
-    if (k > s->max_frames - s->frames[slot])
-      return fail(SR_ELIMIT, "stream id %u: %llu + %llu frames exceed max_frames %llu", ids[i], (unsigned long long)s->frames[slot],
-                  (unsigned long long)k, (unsigned long long)s->max_frames);
-    if (s->failed[slot] && k) return fail(SR_EINTERNAL, "stream id %u: an earlier push overflowed its book", ids[i]);
-    if (!k) continue;
-    const uint64_t nb = (s->frames[slot] ? s->host_state[slot].n_book : 2u) + W * k;
+  for (const PushEntry& e : entries) {
+    const uint32_t id = s->slots.id[e.slot];
+    if (s->failed[e.slot]) return fail(SR_EINTERNAL, "stream id %u: an earlier push overflowed its book", id);
+    const uint64_t nb = (e.t0 ? s->host_state[e.slot].n_book : 2u) + (uint64_t)b->net.n_words * e.k;
     if (nb > 0xFFFFFFFFull)
-      return fail(SR_ELIMIT, "stream id %u: this push may need %llu book entries, more than 2^32 - 1", ids[i], (unsigned long long)nb);
-    jobs.push_back({(uint32_t)slot, (uint32_t)s->frames[slot], (uint32_t)k, 0u, frame_off[i], nullptr, 0});
+      return fail(SR_ELIMIT, "stream id %u: this push may need %llu book entries, more than 2^32 - 1", id, (unsigned long long)nb);
+    jobs.push_back({e.slot, (uint32_t)e.t0, (uint32_t)e.k, 0u, e.row0, nullptr, 0});
     need.push_back(nb);
   }
-  const uint64_t F = frame_off[n];
-  if (F == 0) return SR_OK;
+  if (jobs.empty()) return SR_OK;
   if (!feats) return fail(SR_EINVAL, "null feats");
   sr_model* m = s->model;
-  int rc = check_model(m);
-  if (rc) return rc;
+  if ((rc = check_model(m))) return rc;
   // every book to at least n_book + W k entries (geometric growth; the entries so far are copied: back pointers are indices)
   for (size_t j = 0; j < jobs.size(); j++) {
     DevBuf<uint4>& bk = *s->book[jobs[j].slot];
@@ -1983,46 +1916,33 @@ int sr_bigram_stream_push(sr_bigram_stream* s, uint32_t n, const uint32_t* ids, 
     jobs[j].book = bk.p;
     jobs[j].book_cap = bk.n;
   }
-  HIP_TRY(s->feats.ensure((size_t)F * m->dim));
-  HIP_TRY(s->scores.ensure((size_t)F * m->ld));
-  HIP_TRY(s->jobs.ensure(jobs.size()));
-  HIP_TRY(hipMemcpyAsync(s->feats.p, feats, sizeof(float) * F * m->dim, hipMemcpyHostToDevice, m->s_gmm));
-  HIP_TRY(hipMemcpyAsync(s->jobs.p, jobs.data(), sizeof(BigramStreamJob) * jobs.size(), hipMemcpyHostToDevice, m->s_gmm));
-  if ((rc = launch_scoring(m, s->feats.p, F, s->params.gmm_kernel, s->scores.p))) return rc;
-  const hipStream_t s_search = m->overlap ? m->s_search : m->s_gmm;
-  HIP_TRY(hipEventRecord(m->ev_scored[0], m->s_gmm));
-  HIP_TRY(hipStreamWaitEvent(s_search, m->ev_scored[0], 0));
-  BigramStreamArgs a{};
-  BigramArgs& ba = a.a;
-  ba.scores = s->scores.p; ba.ld = m->ld;
-  ba.n_words = b->n_words; ba.silence = b->silence; ba.n_positions = b->n_positions;
-  ba.slot_off = b->slot_off.p; ba.slot_mix = b->slot_mix.p; ba.mixtures = b->mixtures.p; ba.pos_info = b->pos_info.p; ba.pos_slot = b->pos_slot.p;
-  ba.lmT = b->lmT.p; ba.lm_rowmin = b->lm_rowmin.p; ba.lm_rowmax = b->lm_rowmax.p;
-  memcpy(ba.tdp, b->tdp, sizeof(ba.tdp));
-  ba.ac_pruning = s->params.acoustic_pruning; ba.lm_pruning = s->params.lm_pruning;
-  ba.max_slot_states = b->max_slot_states; ba.silence_states = b->silence_states;
-  ba.global_states = 1;
-  ba.gs_ws = s->gs_ws.p; ba.gs_ws_words = bigram_gs_ws_words(b->n_words, b->n_positions);
-  ba.we_slot = s->we_slot.p; ba.we_bp = s->we_bp.p; ba.we_score = s->we_score.p;
-  a.jobs = s->jobs.p; a.state = s->state.p; a.lsave = s->lsave.p;
-  a.out_word = s->out_word.p; a.out_score = s->out_score.p; a.out_time = s->out_time.p; a.items_stride = s->max_frames + 1;
-  EventPair ep{};
-  if ((rc = prof_begin(m, s_search, 1, &ep))) return rc;
-  HIP_TRY(launch_bigram_stream(a, (uint32_t)jobs.size(), s_search));
-  if ((rc = prof_end(m, s_search, &ep))) return rc;
-  HIP_TRY(hipStreamSynchronize(s_search));
-  HIP_TRY(hipStreamSynchronize(m->s_gmm));
-  std::vector<BigramStreamState> st(s->max_streams);  // (one copy of every slot's 32 bytes: cheaper than one per pushed slot)
+  const uint64_t F = frame_off[n];
+  rc = push_pass(m, s->params.gmm_kernel, feats, F, s->feats, jobs, s->jobs, [&](const Chunk&, const double* table, hipStream_t stream) -> int {
+    BigramStreamArgs a{};
+    BigramArgs& ba = a.a;
+    ba = b->net;
+    ba.scores = table; ba.ld = m->ld;
+    ba.ac_pruning = s->params.acoustic_pruning; ba.lm_pruning = s->params.lm_pruning;
+    ba.global_states = 1;
+    ba.gs_ws = s->gs_ws.p; ba.gs_ws_words = bigram_gs_ws_words(ba.n_words, ba.n_positions);
+    ba.we_slot = s->we_slot.p; ba.we_bp = s->we_bp.p; ba.we_score = s->we_score.p;
+    a.jobs = s->jobs.p; a.state = s->state.p; a.lsave = s->lsave.p;
+    a.out_word = s->out_word.p; a.out_score = s->out_score.p; a.out_time = s->out_time.p; a.items_stride = s->slots.max_frames + 1;
+    HIP_TRY(launch_bigram_stream(a, (uint32_t)jobs.size(), stream));
+    if (m->profiling) {  // SURVEY 8(d)'s decoder model, 8 S + 4 P bytes per frame, as sr_recognize_bigram_corpus
+      m->prof.search_bytes += (8.0 * m->n_states + 4.0 * ba.n_positions) * (double)F;
+      m->prof.frames += F;
+    }
+    return SR_OK;
+  });
+  if (rc) return rc;
+  std::vector<BigramStreamState> st(s->slots.max_streams);  // (one copy of every slot's 32 bytes: cheaper than one per pushed slot)
   HIP_TRY(hipMemcpy(st.data(), s->state.p, sizeof(BigramStreamState) * st.size(), hipMemcpyDeviceToHost));
   uint32_t bad = 0xFFFFFFFFu;
   for (const BigramStreamJob& j : jobs) {
-    s->frames[j.slot] += j.k;
+    s->slots.frames[j.slot] += j.k;
     s->host_state[j.slot] = st[j.slot];
-    if (st[j.slot].flags & kBgStreamOverflow) { s->failed[j.slot] = 1; bad = s->id[j.slot]; }
-  }
-  if (m->profiling) {  // SURVEY 8(d)'s decoder model, 8 S + 4 P bytes per frame, as sr_recognize_bigram_corpus
-    m->prof.search_bytes += (8.0 * m->n_states + 4.0 * b->n_positions) * (double)F;
-    m->prof.frames += F;
+    if (st[j.slot].flags & kBgStreamOverflow) { s->failed[j.slot] = 1; bad = s->slots.id[j.slot]; }
   }
   if (bad != 0xFFFFFFFFu) return fail(SR_EINTERNAL, "stream id %u: a book append passed the capacity the host grew it to", bad);
   return SR_OK;
@@ -2033,11 +1953,11 @@ int sr_bigram_stream_partial(sr_bigram_stream* s, uint32_t id, uint32_t* out_wor
                              uint32_t* count, uint64_t* frames) {
   return guarded(__func__, [&]() -> int {
   if (!s || !count || ((!out_word || !out_score || !out_time) && cap)) return fail(SR_EINVAL, "null argument");
-  const int64_t slot = bigram_stream_slot(s, id);
+  const int64_t slot = s->slots.find(id);
   if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
   int rc = check_model(s->model);
   if (rc) return rc;
-  if (frames) *frames = s->frames[slot];
+  if (frames) *frames = s->slots.frames[slot];
   return bigram_stream_items(s, (uint32_t)slot, id, out_word, out_score, out_time, cap, count);
   });
 }
@@ -2046,13 +1966,13 @@ int sr_bigram_stream_end(sr_bigram_stream* s, uint32_t id, uint32_t* out_word, f
                          uint32_t* count) {
   return guarded(__func__, [&]() -> int {
   if (!s || !count || ((!out_word || !out_score || !out_time) && cap)) return fail(SR_EINVAL, "null argument");
-  const int64_t slot = bigram_stream_slot(s, id);
+  const int64_t slot = s->slots.find(id);
   if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
   int rc = check_model(s->model);
   if (rc) return rc;
   rc = bigram_stream_items(s, (uint32_t)slot, id, out_word, out_score, out_time, cap, count);
   if (rc == SR_EINVAL) return rc;  // too small a buffer: the utterance stays open
-  s->open[slot] = 0;
+  s->slots.open[slot] = 0;
   return rc;
   });
 }

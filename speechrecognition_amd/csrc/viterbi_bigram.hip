@@ -27,6 +27,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <cstring>
+#include <limits>
+#include <type_traits>
+
 #include "kernels.h"
 
 namespace srgpu {
@@ -1023,43 +1028,47 @@ BigramLayout bigram_layout(const BigramArgs& a) {
   return a.dense_states ? BigramLayout::kNone : BigramLayout::kGlobal;
 }
 
+// The <KW, GSM> instantiation of the global-states kernels (bigram_gs_kernel, bigram_stream_kernel) for a lexicon of n_words words:
+// go(std::integral_constant KW, std::integral_constant GSM) launches it
+template <class Go>
+static hipError_t dispatch_gs(uint32_t n_words, Go go) {
+  using K1 = std::integral_constant<int, 1>;
+  using K2 = std::integral_constant<int, 2>;
+  using K4 = std::integral_constant<int, 4>;
+  using K8 = std::integral_constant<int, 8>;
+  const uint32_t kw = (n_words + kBgThreads - 1) / kBgThreads;
+  if (kw <= 1) return go(K1{}, K1{});
+  if (kw <= 2) return go(K2{}, K1{});
+  if (kw <= 4) return go(K4{}, K1{});
+  if (!bigram_gs_entries_global(n_words)) return go(K8{}, K1{});
+  return go(K8{}, K2{});
+}
+
 static hipError_t launch_bigram_gs(const BigramArgs& a, hipStream_t stream) {
-  const bool eng = bigram_gs_entries_global(a.n_words);
-  const size_t smem = bigram_gs_lds(a.n_words, eng);
+  const size_t smem = bigram_gs_lds(a.n_words, bigram_gs_entries_global(a.n_words));
   const uint32_t grid = a.gs_grid < a.n_utts ? a.gs_grid : a.n_utts;
   if (grid == 0 || !a.gs_ws || a.gs_ws_words < bigram_gs_ws_words(a.n_words, a.n_positions)) return hipErrorInvalidValue;
-  auto go = [&](auto kernel) {
+  return dispatch_gs(a.n_words, [&](auto kw, auto gsm) {
+    const auto kernel = bigram_gs_kernel<decltype(kw)::value, decltype(gsm)::value>;
     hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBgThreads), smem, stream, a);
     return hipGetLastError();
-  };
-  const uint32_t kw = (a.n_words + kBgThreads - 1) / kBgThreads;
-  if (kw <= 1) return go(bigram_gs_kernel<1, 1>);
-  if (kw <= 2) return go(bigram_gs_kernel<2, 1>);
-  if (kw <= 4) return go(bigram_gs_kernel<4, 1>);
-  if (!eng) return go(bigram_gs_kernel<8, 1>);
-  return go(bigram_gs_kernel<8, 2>);
+  });
 }
 
 hipError_t launch_bigram_stream(const BigramStreamArgs& s, uint32_t n_jobs, hipStream_t stream) {
   if (n_jobs == 0) return hipSuccess;
   const BigramArgs& a = s.a;
-  const bool eng = bigram_gs_entries_global(a.n_words);
-  const size_t smem = bigram_gs_lds(a.n_words, eng);
+  const size_t smem = bigram_gs_lds(a.n_words, bigram_gs_entries_global(a.n_words));
   if (!a.gs_ws || a.gs_ws_words < bigram_gs_ws_words(a.n_words, a.n_positions)) return hipErrorInvalidValue;
-  auto go = [&](auto kernel) {
+  return dispatch_gs(a.n_words, [&](auto kw, auto gsm) {
+    const auto kernel = bigram_stream_kernel<decltype(kw)::value, decltype(gsm)::value>;
     hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kernel, dim3(n_jobs), dim3(kBgThreads), smem, stream, s);
     return hipGetLastError();
-  };
-  const uint32_t kw = (a.n_words + kBgThreads - 1) / kBgThreads;
-  if (kw <= 1) return go(bigram_stream_kernel<1, 1>);
-  if (kw <= 2) return go(bigram_stream_kernel<2, 1>);
-  if (kw <= 4) return go(bigram_stream_kernel<4, 1>);
-  if (!eng) return go(bigram_stream_kernel<8, 1>);
-  return go(bigram_stream_kernel<8, 2>);
+  });
 }
 
 hipError_t launch_bigram(const BigramArgs& a, hipStream_t stream) {
@@ -1110,6 +1119,52 @@ hipError_t launch_bigram(const BigramArgs& a, hipStream_t stream) {
   SR_BG_KP(8);
 #undef SR_BG_KP
 #undef SR_BG
+}
+
+BigramArgs build_bigram_net(uint32_t n_words, const uint32_t* word_off, const uint16_t* mixtures, uint32_t silence_word, const float* lm,
+                            const float tdp[8], std::vector<uint32_t>& slot_off, std::vector<uint32_t>& slot_mix,
+                            std::vector<uint32_t>& pos_info, std::vector<uint32_t>& pos_slot, std::vector<float>& lmT,
+                            std::vector<float>& lm_rowmin, std::vector<float>& lm_rowmax) {
+  const uint32_t W = n_words;
+  // slots: words 0..W-1, then the silence copy of every word (Teaching::LinearSearch: silenceCopy :202-205)
+  const uint32_t n_sil = word_off[silence_word + 1] - word_off[silence_word];
+  slot_off.assign(2 * (size_t)W + 1, 0); slot_mix.assign(2 * (size_t)W, 0);
+  for (uint32_t a = 0; a < 2 * W; a++) {
+    const uint32_t aw = a < W ? a : silence_word;
+    slot_off[a + 1] = slot_off[a] + (a < W ? word_off[a + 1] - word_off[a] : n_sil);
+    slot_mix[a] = word_off[aw];
+  }
+  const uint32_t P2 = slot_off[2 * W];
+  // per dense position: emission state | flags << 16 and the slot (the state update runs one thread per position)
+  pos_info.assign(P2, 0); pos_slot.assign(P2, 0);
+  for (uint32_t a = 0; a < 2 * W; a++) {
+    const uint32_t n = slot_off[a + 1] - slot_off[a], sil = (a >= W || a == silence_word) ? 8u : 0u;
+    for (uint32_t k = 0; k < n; k++) {
+      const uint32_t flags = (k == 0 ? 1u : 0u) | (k == 1 ? 2u : 0u) | (k == n - 1 ? 4u : 0u) | sil;
+      pos_info[slot_off[a] + k] = (uint32_t)mixtures[slot_mix[a] + k] | (flags << 16);
+      pos_slot[slot_off[a] + k] = a;
+    }
+  }
+  lmT.assign((size_t)W * W, 0.f);
+  for (uint32_t w = 0; w < W; w++)
+    for (uint32_t h = 0; h < W; h++) lmT[(size_t)h * W + w] = lm[(size_t)w * W + h];
+  lm_rowmin.assign(W, std::numeric_limits<float>::infinity()); lm_rowmax.assign(W, -std::numeric_limits<float>::infinity());
+  for (uint32_t h = 0; h < W; h++)
+    for (uint32_t w = 0; w < W; w++) {
+      if (w == silence_word) continue;  // no transition into silence through the LM (LinearSearch.cc:231)
+      const float v = lmT[(size_t)h * W + w];
+      // NaN entries: the bounds become NaN and the skip test fails safe (nothing is skipped against a NaN bound)
+      lm_rowmin[h] = (v < lm_rowmin[h] || v != v) ? v : lm_rowmin[h];
+      lm_rowmax[h] = (v > lm_rowmax[h] || v != v) ? v : lm_rowmax[h];
+    }
+  BigramArgs net{};
+  net.n_words = W; net.silence = silence_word; net.n_positions = P2;
+  memcpy(net.tdp, tdp, sizeof(net.tdp));
+  for (uint32_t a = 0; a < 2 * W; a++) net.max_slot_states = std::max(net.max_slot_states, slot_off[a + 1] - slot_off[a]);
+  net.silence_states = n_sil;
+  for (uint32_t w = 0; w < W; w++)  // (words only: a silence copy has the silence word's one state in the register layout)
+    if (slot_off[w + 1] - slot_off[w] >= 4) net.row4_mask |= 1u << (w / 1024u);
+  return net;
 }
 
 }  // namespace srgpu
