@@ -15,6 +15,7 @@
 //   sr::FeaturePostProcessor   SignalAnalysis::process_features  sietill/SignalAnalysis.cpp:320-336,340-349,379-399
 //   sr::read_feature_file, write_alignment, read_alignment    sietill/IO.cpp:48-69, Alignment.cpp:303-318
 //   sr::Trainer (re-alignment) Trainer::train's align loop   sietill/Training.cpp:163-184, :239-253, :585-612
+//                              (+ baum_welch: forward-backward E-step in place of realign + accumulate)
 //
 // Differences, all forced by the device boundary: features are passed as (pointer, frame count)
 // instead of FeatureIter pairs; MixtureModel::prepare_sequence really does work (it fills the dense
@@ -149,6 +150,7 @@ class MixtureModel : public FeatureScorer {
   size_t num_densities() const { return num_densities_; }
   sr_model* handle() const { return h_; }
   int device() const { return device_; }
+  bool max_approx() const { return max_approx_; }
   // another replica of the same model file on `device` (utterance batches shard across devices, every device holds the
   // whole model: Recognizer::recognize(corpus, devices))
   std::unique_ptr<MixtureModel> replicate(int device) const {
@@ -586,7 +588,8 @@ inline void read_alignment(std::istream& in, std::vector<AlignmentItem>& alignme
 
 // ---- the training-side callers of the path (Training.hpp:18-107): NOT the EM trainer, only the two loops of
 // Trainer::train that run the scorer and the aligner over the whole corpus -- re-alignment (Training.cpp:163-184)
-// and the average acoustic score along the alignment (calc_am_score, :585-612) -- each as one device pass.
+// and the average acoustic score along the alignment (calc_am_score, :585-612) -- each as one device pass; and the
+// Baum-Welch E-step that can take re-alignment's and accumulation's place (baum_welch).
 class Trainer {
  public:
   Trainer(Lexicon const& lexicon, MixtureModel& mixtures, TdpModel const& tdp_model, double pruning_threshold = 50.0,
@@ -610,13 +613,8 @@ class Trainer {
   void realign(Corpus const& corpus, std::vector<AlignmentItem>& alignment, std::vector<double>* costs = nullptr) {
     const size_t n = corpus.get_corpus_size();
     std::vector<uint16_t> automata;
-    std::vector<uint64_t> aut_off(1, 0);
-    for (size_t s = 0; s < n; s++) {
-      auto w = corpus.get_word_sequence(s);
-      MarkovAutomaton a = build_segment_automaton(w.first, w.second);
-      automata.insert(automata.end(), a.states.begin(), a.states.end());
-      aut_off.push_back(automata.size());
-    }
+    std::vector<uint64_t> aut_off;
+    segment_automata(corpus, automata, aut_off);
     const uint64_t F = corpus.get_total_frame_count();
     const double tdp[3] = {tdp_.tdp_loop, tdp_.tdp_forward, tdp_.tdp_skip};
     sr_corpus* c = nullptr;
@@ -632,6 +630,40 @@ class Trainer {
     check(rc);
     alignment.assign(F, AlignmentItem());
     for (uint64_t t = 0; t < F; t++) { alignment[t].state = states[t]; alignment[t].weight = 1; alignment[t].count = 1; }
+    if (costs) costs->assign(cost.begin(), cost.begin() + n);
+  }
+
+  // MixtureModel's accumulators (Mixtures.hpp:80-86) as sr_accumulate_corpus / sr_baum_welch_corpus return them
+  struct Statistics {
+    std::vector<double> mean_acc, mean_w, var_acc, var_w;
+  };
+
+  // Baum-Welch in place of Viterbi training: one device pass does the forward-backward over every segment's automaton and the
+  // posterior-weighted accumulation (sr_baum_welch_corpus) -- what realign + MixtureModel::accumulate do in Trainer::train, with
+  // every frame shared among the states by its posterior instead of one hard decision.  costs (optional): the per-segment
+  // -log P(X | transcript), the quantity EM lowers.  Memberships within a state follow the model (arg-min with max-approx
+  // scoring, soft otherwise); posteriors below posterior_floor are dropped.
+  void baum_welch(Corpus const& corpus, Statistics& stats, std::vector<double>* costs = nullptr, double posterior_floor = 0.0,
+                  bool first_pass = false) {
+    const size_t n = corpus.get_corpus_size();
+    std::vector<uint16_t> automata;
+    std::vector<uint64_t> aut_off;
+    segment_automata(corpus, automata, aut_off);
+    uint32_t n_mean = 0, n_var = 0;
+    check(sr_model_tying_info(mixtures_.handle(), &n_mean, &n_var));
+    const size_t D = mixtures_.dimension;
+    stats.mean_acc.assign(n_mean * D, 0.0); stats.mean_w.assign(n_mean, 0.0);
+    stats.var_acc.assign(n_var * D, 0.0); stats.var_w.assign(n_var, 0.0);
+    const double tdp[3] = {tdp_.tdp_loop, tdp_.tdp_forward, tdp_.tdp_skip};
+    sr_corpus* c = nullptr;
+    check(sr_corpus_upload(mixtures_.handle(), corpus.features(), corpus.frame_offsets(), (uint32_t)n, &c));
+    std::vector<double> cost(std::max<size_t>(n, 1));
+    const int rc = sr_baum_welch_corpus(mixtures_.handle(), c, automata.data(), aut_off.data(), tdp, tdp_.silence_state,
+                                        mixtures_.gmm_kernel, posterior_floor, first_pass ? 1 : 0, mixtures_.max_approx() ? 1 : 0,
+                                        cost.data(), stats.mean_acc.data(), stats.mean_w.data(), stats.var_acc.data(),
+                                        stats.var_w.data());
+    sr_corpus_destroy(c);
+    check(rc);
     if (costs) costs->assign(cost.begin(), cost.begin() + n);
   }
 
@@ -652,6 +684,18 @@ class Trainer {
   }
 
  private:
+  // every segment's automaton (build_segment_automaton), concatenated, with offsets
+  void segment_automata(Corpus const& corpus, std::vector<uint16_t>& automata, std::vector<uint64_t>& aut_off) const {
+    automata.clear();
+    aut_off.assign(1, 0);
+    for (size_t s = 0; s < corpus.get_corpus_size(); s++) {
+      auto w = corpus.get_word_sequence(s);
+      MarkovAutomaton a = build_segment_automaton(w.first, w.second);
+      automata.insert(automata.end(), a.states.begin(), a.states.end());
+      aut_off.push_back(automata.size());
+    }
+  }
+
   const double pruning_threshold_;
   const bool alignment_pruning_;
   Lexicon const& lexicon_;

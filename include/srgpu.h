@@ -288,6 +288,38 @@ SR_API int sr_accumulate_corpus(sr_model* m, sr_corpus* c, const uint16_t* state
  * (for the host-side logarithms, see sr_model_create_from_statistics) cross the bus. */
 SR_API int sr_model_create_from_accumulated(sr_model* m, sr_corpus* c, int pooling, int max_approx, sr_model** out);
 
+/* ---- Baum-Welch: forward-backward over the aligner's automata and topology ---------------------------------------
+ * Same automata, 0-1-2 topology and transition penalties as sr_align_corpus (keyed on the SOURCE position; any jump out of
+ * silence costs `forward`), summed over all paths instead of minimised.  F_u = -log sum_paths exp(-cost), so
+ * V_u - log(#paths) <= F_u <= V_u for the Viterbi cost V_u.  Requires 1 <= N_u <= 2 T_u - 1 (a path must exist; unlike
+ * sr_align_corpus N_u > T_u is allowed) and N_u <= 8192 (SR_ELIMIT).  T_u = 1 gives F_u = e(0, automaton[0]), where
+ * sr_align_corpus returns +inf.  Forbidden jumps (+inf penalties) and unreachable cells stay +inf, never NaN.
+ * gamma_t(k) = sum over the positions s carrying mixture k of P(s_t = s | X).  Workspace: 8 bytes per (frame, position) for
+ * the utterances processed together, at most SRGPU_FB_MB MiB (default 1024); an utterance that alone needs more: SR_ELIMIT.
+ * gmm_kernel resolves as in sr_align_corpus (SR_GMM_DEFAULT: listed exact scoring, the reference's bits).  SR_EINVAL also for
+ * posterior_floor negative or NaN, max_items outside 1 .. 65535 with posterior outputs, and a partial set of optional outputs. */
+
+/* out_cost[n_utts] = F_u (required).  Posteriors in AlignmentItem shape, all three optional (all or none): out_count[total_frames],
+ * out_state[total_frames * max_items], out_weight[total_frames * max_items] -- per frame the mixtures of the utterance's automaton
+ * with gamma > 0 and gamma >= posterior_floor, largest first (ties: smaller id first), at most max_items, not renormalised;
+ * entries past out_count are 0. */
+SR_API int sr_state_posteriors_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off,
+                                      const double tdp[3], uint16_t silence_state, int gmm_kernel, double posterior_floor,
+                                      uint32_t max_items, double* out_cost, uint16_t* out_count, uint16_t* out_state,
+                                      double* out_weight);
+
+/* One Baum-Welch E-step: forward-backward + posterior-weighted statistics in one device pass, no posteriors crossing the bus.
+ * Accumulators, seeds and formulas as sr_accumulate_corpus; every frame contributes, for each mixture k with gamma_t(k) > 0 and
+ * >= posterior_floor, each density d of k with weight gamma_t(k) * p_d (p_d: density 0 on first_pass, else the arg-min with
+ * max_approx, else the soft membership with its < 1e-8 drop).  Every accumulator row is summed frames in order, then mixtures in
+ * ascending id, then densities in mixture order, without atomics: two identical calls return identical bits.  Statistics of
+ * corpus shards add up like sr_accumulate_corpus'.  Output arrays as sr_accumulate_corpus: all four, or all NULL to keep the
+ * statistics in the corpus handle for sr_model_create_from_accumulated. */
+SR_API int sr_baum_welch_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off,
+                                const double tdp[3], uint16_t silence_state, int gmm_kernel, double posterior_floor,
+                                int first_pass, int max_approx, double* out_cost, double* mean_acc, double* mean_w,
+                                double* var_acc, double* var_w);
+
 /* ---- bigram-LM beam search over a linear lexicon ---------------------------------------------------------------
  * Replaces Teaching::LinearSearch (rwth-asr-0.5/src/Teaching/LinearSearch.cc: initialize :489-495, processFrame
  * :496-515, getResult :517-520) for a whole corpus.  Scores are float there (Teaching/Types.hh:17); the acoustic
@@ -385,7 +417,7 @@ typedef struct {
   double gmm_flops;     /* algorithmic: 4 * dim * densities * frames per launch, summed */
   double search_ms;     /* Viterbi decode / align kernels */
   uint64_t search_launches;
-  double search_bytes;  /* algorithmic: (8*S + 4*P) * frames (decode) / (8+1)*N * frames (align) */
+  double search_bytes;  /* algorithmic: (8*S + 4*P) * frames (decode) / (8+1)*N * frames (align) / 32*N * frames (forward-backward) */
   uint64_t frames;      /* frames processed */
   uint64_t refined_pairs;      /* SR_GMM_PREFILTER: (frame, state) pairs scored ... */
   uint64_t refined_densities;  /* ... and densities the FP64 stage had to evaluate for them (>= 1 per pair) */

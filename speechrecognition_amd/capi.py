@@ -30,6 +30,7 @@ SYMBOLS = [
     "sr_last_error", "sr_device_count", "sr_model_create", "sr_model_load_mixset", "sr_model_destroy", "sr_model_info",
     "sr_corpus_upload", "sr_corpus_upload_async", "sr_corpus_wait", "sr_corpus_destroy", "sr_shard_utterances", "sr_recognize_batch_multi", "sr_score_corpus", "sr_score_frames", "sr_lexicon_create",
     "sr_lexicon_destroy", "sr_lexicon_describe", "sr_recognize_corpus", "sr_traceback_corpus", "sr_traceback_words", "sr_recognize_batch", "sr_align_corpus", "sr_align_corpus_pruned", "sr_path_scores_corpus", "sr_model_create_from_statistics", "sr_model_create_from_accumulated", "sr_mixset_write", "sr_model_set_tying", "sr_model_tying_info", "sr_model_topology", "sr_accumulate_corpus",
+    "sr_state_posteriors_corpus", "sr_baum_welch_corpus",
     "sr_bigram_create", "sr_bigram_destroy", "sr_bigram_describe", "sr_recognize_bigram_corpus",
     "sr_stream_open", "sr_stream_begin", "sr_stream_push", "sr_stream_partial", "sr_stream_end", "sr_stream_destroy",
     "sr_bigram_stream_open", "sr_bigram_stream_begin", "sr_bigram_stream_push", "sr_bigram_stream_partial", "sr_bigram_stream_end",
@@ -105,6 +106,8 @@ def lib():
         L.sr_model_tying_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
         L.sr_model_topology.argtypes = [vp, vp, vp, vp]
         L.sr_accumulate_corpus.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
+        L.sr_state_posteriors_corpus.argtypes = [vp, vp, vp, vp, C.POINTER(dbl * 3), C.c_uint16, i32, dbl, u32, vp, vp, vp, vp]
+        L.sr_baum_welch_corpus.argtypes = [vp, vp, vp, vp, C.POINTER(dbl * 3), C.c_uint16, i32, dbl, i32, i32, vp, vp, vp, vp, vp]
         L.sr_bigram_create.argtypes = [vp, u32, vp, vp, u32, vp, vp, C.POINTER(vp)]
         L.sr_bigram_destroy.argtypes = [vp]
         L.sr_bigram_describe.argtypes = [vp, C.c_char_p, C.c_size_t]
@@ -486,6 +489,43 @@ class Corpus:
         _check(lib().sr_accumulate_corpus(self.model.h, self.h, _ptr(states), int(first_pass), int(max_approx), _ptr(ma), _ptr(mw),
                                           _ptr(va), _ptr(vw)))
         return ma, mw, va, vw
+
+    def state_posteriors(self, automata, tdp, silence_state, kernel=GMM_DEFAULT, floor=0.0, max_items=8):
+        """Forward-backward over the aligner's automata -> (cost f64[n_utts] = -log P(X | automaton), count u16[total_frames],
+        state u16[total_frames, max_items], weight f64[total_frames, max_items]): per frame the mixtures with posterior >= floor,
+        largest first, at most max_items (sr_state_posteriors_corpus)."""
+        flat, off = self._aut(automata)
+        F = max(self.n_frames, 1)
+        cost = np.zeros(max(self.n_utts, 1), dtype=np.float64)
+        count = np.zeros(F, dtype=np.uint16)
+        state = np.zeros((F, max(int(max_items), 1)), dtype=np.uint16)
+        weight = np.zeros((F, max(int(max_items), 1)), dtype=np.float64)
+        t3 = (C.c_double * 3)(*tdp)
+        _check(lib().sr_state_posteriors_corpus(self.model.h, self.h, _ptr(flat), _ptr(off), C.byref(t3), silence_state, kernel, float(floor),
+                                                int(max_items), _ptr(cost), _ptr(count), _ptr(state), _ptr(weight)))
+        n = self.n_frames
+        return cost[: self.n_utts], count[:n], state[:n], weight[:n]
+
+    def _baum_welch(self, automata, tdp, silence_state, kernel, floor, first_pass, max_approx, out):
+        flat, off = self._aut(automata)
+        cost = np.zeros(max(self.n_utts, 1), dtype=np.float64)
+        t3 = (C.c_double * 3)(*tdp)
+        _check(lib().sr_baum_welch_corpus(self.model.h, self.h, _ptr(flat), _ptr(off), C.byref(t3), silence_state, kernel, float(floor),
+                                          int(first_pass), int(max_approx), _ptr(cost), *[_ptr(a) for a in out]))
+        return cost[: self.n_utts]
+
+    def baum_welch(self, automata, tdp, silence_state, kernel=GMM_DEFAULT, floor=0.0, first_pass=False, max_approx=True):
+        """One Baum-Welch E-step (sr_baum_welch_corpus) -> (cost f64[n_utts], (mean_acc, mean_w, var_acc, var_w))."""
+        nm, nv = C.c_uint32(), C.c_uint32()
+        _check(lib().sr_model_tying_info(self.model.h, C.byref(nm), C.byref(nv)))
+        D = self.model.dim
+        stats = (np.zeros((nm.value, D)), np.zeros(nm.value), np.zeros((nv.value, D)), np.zeros(nv.value))
+        cost = self._baum_welch(automata, tdp, silence_state, kernel, floor, first_pass, max_approx, stats)
+        return cost, stats
+
+    def baum_welch_on_device(self, automata, tdp, silence_state, kernel=GMM_DEFAULT, floor=0.0, first_pass=False, max_approx=True):
+        """The same, the statistics kept in this corpus handle for next_model() -> cost f64[n_utts]."""
+        return self._baum_welch(automata, tdp, silence_state, kernel, floor, first_pass, max_approx, (None, None, None, None))
 
     def recognize_bigram(self, bigram, acoustic_pruning=FLT_MAX, lm_pruning=FLT_MAX, kernel=GMM_PREFILTER, max_word_ends=0, dense_states=False,
                          global_states=False):

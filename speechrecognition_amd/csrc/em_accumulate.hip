@@ -204,14 +204,11 @@ size_t em_sort_temp_bytes(uint64_t n_pairs) {
   return bytes;
 }
 
-hipError_t launch_em_accumulate(const EmArgs& a, void* sort_temp, size_t sort_temp_bytes, uint32_t* iota, uint32_t* keys_sorted,
-                                uint32_t* pairs_sorted, uint32_t* row_begin, double* mean_acc, double* mean_w, double* var_acc, double* var_w,
-                                hipStream_t stream) {
-  if (a.n_frames == 0 || a.n_pairs == 0) return hipSuccess;
-  hipLaunchKernelGGL(em_assign_kernel, dim3((unsigned)((a.n_frames + kAssignThreads - 1) / kAssignThreads)), dim3(kAssignThreads), 0,
-                     stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
+// steps 2-3 on the pairs in a.pair_frame / pair_w / key_mean / key_var
+static hipError_t sort_and_sum(const EmArgs& a, void* sort_temp, size_t sort_temp_bytes, uint32_t* iota, uint32_t* keys_sorted,
+                               uint32_t* pairs_sorted, uint32_t* row_begin, double* mean_acc, double* mean_w, double* var_acc, double* var_w,
+                               hipStream_t stream) {
+  hipError_t e;
   // LSD radix sort is stable: pairs of one row stay in generation (= frame, then density) order
   e = hipcub::DeviceRadixSort::SortPairs(sort_temp, sort_temp_bytes, a.key_mean, keys_sorted, iota, pairs_sorted, (int)a.n_pairs, 0, 32, stream);
   if (e != hipSuccess) return e;
@@ -225,6 +222,102 @@ hipError_t launch_em_accumulate(const EmArgs& a, void* sort_temp, size_t sort_te
   hipLaunchKernelGGL((em_sum_kernel<true>), dim3((a.n_var + 3) / 4), dim3(256), 0, stream, a,
                      row_begin, pairs_sorted, a.n_var, var_acc, var_w);
   return hipGetLastError();
+}
+
+hipError_t launch_em_accumulate(const EmArgs& a, void* sort_temp, size_t sort_temp_bytes, uint32_t* iota, uint32_t* keys_sorted,
+                                uint32_t* pairs_sorted, uint32_t* row_begin, double* mean_acc, double* mean_w, double* var_acc, double* var_w,
+                                hipStream_t stream) {
+  if (a.n_frames == 0 || a.n_pairs == 0) return hipSuccess;
+  hipLaunchKernelGGL(em_assign_kernel, dim3((unsigned)((a.n_frames + kAssignThreads - 1) / kAssignThreads)), dim3(kAssignThreads), 0,
+                     stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return sort_and_sum(a, sort_temp, sort_temp_bytes, iota, keys_sorted, pairs_sorted, row_begin, mean_acc, mean_w, var_acc, var_w, stream);
+}
+
+// ---- Baum-Welch: posterior-weighted pairs -------------------------------------------------------------------------------
+// Item i = (frame, mixture k, gamma) from the forward-backward (viterbi_fb.hip), items in frame order and ascending mixture id.
+// Its pairs are em_assign_kernel's for (frame, k) with every weight multiplied by gamma: w = gamma * p_d, p_d the membership of
+// density d (1 for density 0 / the arg-min, else soft with the < 1e-8 drop applied to p_d).  Generated in item order, then density
+// order, the stable sort keeps every row's pairs in (frame, mixture id, density) order.
+
+__global__ __launch_bounds__(256) void em_item_pairs_kernel(EmArgs a, uint64_t* cnt) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n_items) return;
+  const uint32_t k = a.item_mix[i];
+  cnt[i] = (a.first_pass || a.max_approx) ? 1u : a.dens_off[k + 1] - a.dens_off[k];
+}
+
+__global__ __launch_bounds__(kAssignThreads) void em_assign_weighted_kernel(EmArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * kAssignThreads + threadIdx.x;
+  if (i >= a.n_items) return;
+  const uint32_t D = a.dim, t = a.item_frame[i];
+  const float* x = a.feats + (uint64_t)t * D;
+  const uint32_t s = a.item_mix[i], c0 = a.dens_off[s], c1 = a.dens_off[s + 1];
+  const double g = a.item_w[i];
+  const uint64_t p0 = i ? a.item_pair_end[i - 1] : 0;
+  if (a.first_pass || a.max_approx) {
+    uint32_t arg = c0;
+    if (!a.first_pass) {
+      double best = 1e10;
+      for (uint32_t c = c0; c < c1; c++) {
+        const double sc = em_density_score(x, a.means + (uint64_t)c * D, a.inv_vars + (uint64_t)c * D, a.norm[c], a.logw[c], D);
+        if (sc < best) { best = sc; arg = c; }
+      }
+    }
+    const bool any = c1 > c0;
+    a.pair_frame[p0] = t;
+    a.pair_w[p0] = g;
+    a.key_mean[p0] = any ? a.dens_mean[arg] : 0xFFFFFFFFu;
+    a.key_var[p0] = any ? a.dens_var[arg] : 0xFFFFFFFFu;
+    return;
+  }
+  double sum = 0.0;
+  for (uint32_t c = c0; c < c1; c++) {
+    const double p = exp(-1 * em_density_score(x, a.means + (uint64_t)c * D, a.inv_vars + (uint64_t)c * D, a.norm[c], a.logw[c], D));
+    a.pair_w[p0 + (c - c0)] = p;
+    sum += p;
+  }
+  for (uint32_t c = c0; c < c1; c++) {
+    const uint64_t j = p0 + (c - c0);
+    const double p = a.pair_w[j] / sum;
+    const bool keep = !(p < 1e-8);
+    a.pair_frame[j] = t;
+    a.pair_w[j] = g * p;
+    a.key_mean[j] = keep ? a.dens_mean[c] : 0xFFFFFFFFu;
+    a.key_var[j] = keep ? a.dens_var[c] : 0xFFFFFFFFu;
+  }
+}
+
+__global__ __launch_bounds__(256) void em_iota_kernel(uint32_t* out, uint64_t n) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = (uint32_t)i;
+}
+
+size_t em_item_scan_temp_bytes(uint64_t n_items) {
+  size_t bytes = 0;
+  (void)hipcub::DeviceScan::InclusiveSum(nullptr, bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)n_items);
+  return bytes;
+}
+
+hipError_t launch_em_item_pairs(const EmArgs& a, void* scan_temp, size_t scan_temp_bytes, uint64_t* cnt, hipStream_t stream) {
+  if (a.n_items == 0) return hipSuccess;
+  hipLaunchKernelGGL(em_item_pairs_kernel, dim3((unsigned)((a.n_items + 255) / 256)), dim3(256), 0, stream, a, cnt);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return hipcub::DeviceScan::InclusiveSum(scan_temp, scan_temp_bytes, cnt, a.item_pair_end, (int)a.n_items, stream);
+}
+
+hipError_t launch_em_accumulate_weighted(const EmArgs& a, void* sort_temp, size_t sort_temp_bytes, uint32_t* iota, uint32_t* keys_sorted,
+                                         uint32_t* pairs_sorted, uint32_t* row_begin, double* mean_acc, double* mean_w, double* var_acc,
+                                         double* var_w, hipStream_t stream) {
+  if (a.n_items == 0 || a.n_pairs == 0) return hipSuccess;
+  hipLaunchKernelGGL(em_assign_weighted_kernel, dim3((unsigned)((a.n_items + kAssignThreads - 1) / kAssignThreads)), dim3(kAssignThreads),
+                     0, stream, a);
+  hipLaunchKernelGGL(em_iota_kernel, dim3((unsigned)((a.n_pairs + 255) / 256)), dim3(256), 0, stream, iota, a.n_pairs);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return sort_and_sum(a, sort_temp, sort_temp_bytes, iota, keys_sorted, pairs_sorted, row_begin, mean_acc, mean_w, var_acc, var_w, stream);
 }
 
 }  // namespace srgpu

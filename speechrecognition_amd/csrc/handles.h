@@ -129,6 +129,7 @@ struct sr_model {
   bool overlap = true;  // search of chunk i on its own stream while chunk i+1 is scored (SRGPU_OVERLAP=0: one stream)
   size_t defer_budget = (size_t)32 << 30;  // most bytes for the refinement's deferred-leftover segments (SRGPU_DEFER_MB; 0: route off)
   uint32_t defer_cap_limit = 0;            // most entries per segment, 0: no limit (SRGPU_DEFER_CAP, tests: full segments)
+  size_t fb_budget = (size_t)1 << 30;      // most bytes for the forward-backward trellises of one launch (SRGPU_FB_MB)
   // profiling
   bool profiling = false;
   std::vector<EventPair> events;
@@ -163,6 +164,12 @@ struct sr_corpus {
   bool acc_valid = false;           // acc_* hold the statistics of the last sr_accumulate_corpus (for sr_model_create_from_accumulated)
   uint32_t acc_n_mean = 0, acc_n_var = 0;
   DevBuf<unsigned char> sort_temp;
+  // forward-backward workspace (viterbi_fb.hip): the trellis of one launch group, the automata's distinct mixtures, the items
+  DevBuf<double> fb_trellis, fb_item_w, fb_weight;
+  DevBuf<uint64_t> fb_trellis_off, fb_pair_cnt, fb_pair_end;
+  DevBuf<uint32_t> fb_mix_off, fb_slot_beg, fb_cnt, fb_scan, fb_base, fb_item_off, fb_item_frame;
+  DevBuf<uint16_t> fb_mix, fb_slot_pos, fb_item_mix, fb_count, fb_state;
+  DevBuf<unsigned char> fb_scan_temp;
 };
 
 struct sr_lexicon {

@@ -271,6 +271,45 @@ hipError_t launch_align_full(const AlignArgs& a, hipStream_t stream);
 hipError_t launch_align_pruned(const AlignArgs& a, hipStream_t stream);
 uint32_t align_max_positions();
 
+// ---- forward-backward over the aligner's automata and topology (viterbi_fb.hip) --------------------------------------
+// A launch covers utterances [utt_first, utt_first + n_utts) of one score chunk whose trellises fit the workspace together.
+struct FbArgs {
+  const double* scores;         // [frames x ld], row 0 = frame frame_base (as AlignArgs)
+  uint32_t ld;
+  uint64_t frame_base;
+  const uint64_t* frame_off;    // [n_utts_total+1]
+  uint32_t utt_first, n_utts;
+  const uint16_t* automata;     // concatenated automata
+  const uint64_t* aut_off;      // [n_utts_total+1]
+  double tdp_loop, tdp_forward, tdp_skip;
+  uint32_t silence_state;
+  uint32_t max_positions;       // max N_u over the launch (sizes the LDS)
+  double* trellis;              // workspace: [T_u][N_u] per utterance at trellis_off[u] - trellis_off[utt_first]; alpha, then gamma
+  const uint64_t* trellis_off;  // [n_utts_total+1] prefix sums of T_u * N_u
+  double* out_cost;             // [n_utts_total] forward cost F_u
+  // per-frame mixture posteriors -> items (frame, mixture, gamma), in frame order then ascending mixture id
+  const uint32_t* mix_off;      // [n_utts_total+1] range of utterance u in mix[] / slot_beg[]
+  const uint16_t* mix;          // distinct mixtures of each automaton, ascending
+  const uint32_t* slot_beg;     // [sum M_u + 1] positions of mixture j: slot_pos[slot_beg[j] .. slot_beg[j+1])
+  const uint16_t* slot_pos;     // [sum N_u] automaton positions grouped by mixture, ascending within
+  double floor;                 // items: gamma > 0 and gamma >= floor
+  uint64_t group_f0;            // first frame of the launch
+  uint32_t* group_cnt;          // [frames of the launch] items per frame (count pass)
+  const uint32_t* group_scan;   // [frames of the launch] exclusive prefix sum of group_cnt (write pass)
+  uint32_t* item_base;          // device scalar: items written so far
+  uint32_t* item_off;           // [n_frames_total+1] first item of each frame
+  uint32_t* item_frame; uint16_t* item_mix; double* item_w;
+};
+hipError_t launch_fb_forward(const FbArgs& a, hipStream_t stream);
+hipError_t launch_fb_backward(const FbArgs& a, hipStream_t stream);
+// items of the launch's frames (count pass, device scan, write pass), appended at *item_base; scan_temp from fb_scan_temp_bytes
+size_t fb_scan_temp_bytes(uint64_t n_frames);
+hipError_t launch_fb_items(const FbArgs& a, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes, uint32_t* scan_out,
+                           hipStream_t stream);
+// per frame the max_items largest items (ties: smaller mixture id first); entries past out_count are zero
+hipError_t launch_fb_top(const uint32_t* item_off, const uint16_t* item_mix, const double* item_w, uint64_t n_frames,
+                         uint32_t max_items, uint16_t* out_count, uint16_t* out_state, double* out_weight, hipStream_t stream);
+
 // ---- bigram-LM beam search over a linear lexicon (viterbi_bigram.hip; Teaching::LinearSearch) -----------------------
 struct BigramArgs {
   const double* scores;         // [frames x ld]
@@ -367,6 +406,10 @@ struct EmArgs {
   uint32_t n_mean, n_var;
   int first_pass, max_approx;
   uint32_t* pair_frame; double* pair_w; uint32_t* key_mean; uint32_t* key_var;  // [n_pairs] workspace
+  // posterior-weighted pairs (Baum-Welch): item i = (item_frame[i], mixture item_mix[i], gamma item_w[i]); its pairs end at item_pair_end[i]
+  uint64_t n_items;
+  const uint32_t* item_frame; const uint16_t* item_mix; const double* item_w;
+  uint64_t* item_pair_end;
 };
 size_t em_sort_temp_bytes(uint64_t n_pairs);
 // out[t] = score(frame t, a.states[t]); uses feats, n_frames, dim, states, dens_off, means, inv_vars, norm, logw, max_approx
@@ -374,5 +417,12 @@ hipError_t launch_path_scores_direct(const EmArgs& a, double* out, hipStream_t s
 hipError_t launch_em_accumulate(const EmArgs& a, void* sort_temp, size_t sort_temp_bytes, uint32_t* iota, uint32_t* keys_sorted,
                                 uint32_t* pairs_sorted, uint32_t* row_begin /* [max(n_mean, n_var) + 1] */, double* mean_acc,
                                 double* mean_w, double* var_acc, double* var_w, hipStream_t stream);
+// Baum-Welch: pair counts of the items, then their inclusive device scan into a.item_pair_end (scan_temp from em_item_scan_temp_bytes) ...
+size_t em_item_scan_temp_bytes(uint64_t n_items);
+hipError_t launch_em_item_pairs(const EmArgs& a, void* scan_temp, size_t scan_temp_bytes, uint64_t* cnt, hipStream_t stream);
+// ... and, with a.n_pairs = item_pair_end[n_items - 1]: (frame, density, gamma * p_d) pairs into the same sort and row sums
+hipError_t launch_em_accumulate_weighted(const EmArgs& a, void* sort_temp, size_t sort_temp_bytes, uint32_t* iota, uint32_t* keys_sorted,
+                                         uint32_t* pairs_sorted, uint32_t* row_begin, double* mean_acc, double* mean_w, double* var_acc,
+                                         double* var_w, hipStream_t stream);
 
 }  // namespace srgpu

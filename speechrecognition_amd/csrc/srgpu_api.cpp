@@ -808,6 +808,7 @@ int model_shell(int device, uint32_t dim, uint32_t n_states, const uint32_t* den
   m->chunk_frames = std::min<size_t>(m->chunk_frames, ((size_t)1 << 32) / (4 * (size_t)dim) - 128);
   if (const char* ov = getenv("SRGPU_OVERLAP")) m->overlap = atoi(ov) != 0;
   if (const char* e = getenv("SRGPU_DEFER_MB")) m->defer_budget = (size_t)strtoull(e, nullptr, 10) << 20;
+  if (const char* e = getenv("SRGPU_FB_MB")) m->fb_budget = std::max<size_t>(1, (size_t)strtoull(e, nullptr, 10)) << 20;
   if (const char* e = getenv("SRGPU_DEFER_CAP")) m->defer_cap_limit = std::max(1u, (uint32_t)strtoul(e, nullptr, 10));  // (tests: full segments)
   *out = own.release();
   return SR_OK;
@@ -1423,43 +1424,29 @@ int sr_recognize_batch(sr_model* m, sr_lexicon* l, const sr_search_params* p, co
   });
 }
 
-static int align_common(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
-                        uint16_t silence_state, double thr, bool pruned, int gmm_kernel, uint16_t* out_states,
-                        double* out_cost) {
-  int rc = check_corpus(m, c);
-  if (rc) return rc;
-  if (gmm_kernel == SR_GMM_DEFAULT) gmm_kernel = SR_GMM_PREFILTER;  // the aligner scores only its automaton's states: listed, bit-exact
-  if (!automata || !aut_off || !tdp || !out_states || !out_cost) return fail(SR_EINVAL, "null argument");
+// The score side of a pass over per-utterance automata (the aligner, the forward-backward): automata on the device, the corpus'
+// chunks with their score buffers and, with a bit-exact kernel requested, the listed tables -- such a pass reads scores of its
+// automaton's states only (N of S), so just those (frame, state) pairs are scored: the direct-form kernel in listed mode, the
+// same bits as the dense table would hold.  (SR_GMM_MFMA keeps the dense FP64-MFMA table: its rounding differs.)
+struct AutomatonScoring {
+  std::vector<Chunk> chunks;
+  std::vector<uint32_t> blk_first_of_utt;
+  bool listed = false;
+  int gmm_kernel = SR_GMM_PREFILTER;
+};
+
+static int automaton_scoring_setup(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, int gmm_kernel,
+                                   AutomatonScoring* p) {
   const uint32_t U = c->n_utts;
-  const uint64_t F = c->n_frames;
-  std::vector<uint64_t> bp_off(U + 1, 0);
-  uint32_t max_n = 1;
-  for (uint32_t u = 0; u < U; u++) {
-    const uint64_t N = aut_off[u + 1] - aut_off[u], T = c->frame_off[u + 1] - c->frame_off[u];
-    if (N < 1 || T < 1) return fail(SR_EINVAL, "utterance %u: automaton and utterance must be non-empty", u);
-    if (!pruned && N > T)
-      return fail(SR_EINVAL, "utterance %u: automaton length %llu exceeds %llu frames (Aligner::align_sequence_full indexes "
-                  "its T-sized cost arrays by position)", u, (unsigned long long)N, (unsigned long long)T);
-    if (N > align_max_positions()) return fail(SR_ELIMIT, "utterance %u: automaton length %llu exceeds %u", u, (unsigned long long)N, align_max_positions());
-    for (uint64_t i = aut_off[u]; i < aut_off[u + 1]; i++)
-      if (automata[i] >= m->n_states) return fail(SR_EINVAL, "utterance %u: automaton state %u >= n_states", u, automata[i]);
-    max_n = std::max<uint32_t>(max_n, (uint32_t)N);
-    bp_off[u + 1] = bp_off[u] + N * T;
-  }
+  if (gmm_kernel == SR_GMM_DEFAULT) gmm_kernel = SR_GMM_PREFILTER;  // scores of the automaton's states only: listed, bit-exact
+  p->gmm_kernel = gmm_kernel;
   HIP_TRY(c->automata.upload(automata, aut_off[U]));
   HIP_TRY(c->aut_off.upload(aut_off, U + 1));
-  HIP_TRY(c->bp_off.upload(bp_off.data(), U + 1));
-  HIP_TRY(c->backptr.ensure(bp_off[U]));
-  HIP_TRY(c->out_states.ensure(F));
-  HIP_TRY(c->out_cost.ensure(U));
-  std::vector<Chunk> chunks;
-  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
-  // The aligner reads scores of its automaton's states only (N of S): with a bit-exact kernel requested, score just
-  // those (frame, state) pairs -- the direct-form kernel in listed mode, the same bits as the dense table would hold.
-  // (SR_GMM_MFMA keeps the dense FP64-MFMA table: its rounding differs.)
-  const bool listed = gmm_kernel != SR_GMM_MFMA;
-  std::vector<uint32_t> blk_first_of_utt(U + 1, 0);
-  if (listed) {
+  int rc = prepare_chunks(m, c, &p->chunks);
+  if (rc) return rc;
+  p->listed = gmm_kernel != SR_GMM_MFMA;
+  p->blk_first_of_utt.assign(U + 1, 0);
+  if (p->listed) {
     const uint32_t fpb = (uint32_t)gmm_exact_frames_per_block();
     std::vector<uint32_t> list_off(U + 1, 0), list_states, blk_frames, blk_list;
     std::vector<uint64_t> blk_frame0;
@@ -1474,7 +1461,7 @@ static int align_common(sr_model* m, sr_corpus* c, const uint16_t* automata, con
         blk_frames.push_back((uint32_t)std::min<uint64_t>(fpb, c->frame_off[u + 1] - f));
         blk_list.push_back(u);
       }
-      blk_first_of_utt[u + 1] = (uint32_t)blk_frame0.size();
+      p->blk_first_of_utt[u + 1] = (uint32_t)blk_frame0.size();
     }
     HIP_TRY(c->al_list_off.upload(list_off.data(), list_off.size()));
     HIP_TRY(c->al_states.upload(list_states.data(), list_states.size()));
@@ -1482,29 +1469,68 @@ static int align_common(sr_model* m, sr_corpus* c, const uint16_t* automata, con
     HIP_TRY(c->al_blk_frames.upload(blk_frames.data(), blk_frames.size()));
     HIP_TRY(c->al_blk_list.upload(blk_list.data(), blk_list.size()));
   }
+  return SR_OK;
+}
+
+// run_chunks' score step of such a pass
+static int automaton_scoring_chunk(sr_model* m, sr_corpus* c, const AutomatonScoring& p, const Chunk& ch, double* table) {
+  int r = srhost::corpus_ready(c, ch.f0, ch.f1, m->s_gmm);
+  if (r) return r;
+  if (!p.listed) return launch_scoring(m, c->feats.p + ch.f0 * m->dim, ch.f1 - ch.f0, p.gmm_kernel, table);
+  GmmExactArgs ga{};
+  ga.feats = c->feats.p; ga.n_frames = c->n_frames; ga.dim = m->dim; ga.n_states = m->n_states;
+  ga.dens_off = m->dens_off.p; ga.means = m->means.p; ga.inv_vars = m->inv_vars.p; ga.norm = m->norm.p; ga.logw = m->logw.p;
+  ga.out = table; ga.ld = m->ld;
+  GmmExactList gl{};
+  gl.blk_frame0 = c->al_blk_frame0.p; gl.blk_frames = c->al_blk_frames.p; gl.blk_list = c->al_blk_list.p;
+  gl.list_off = c->al_list_off.p; gl.states = c->al_states.p;
+  gl.blk_first = p.blk_first_of_utt[ch.u0]; gl.frame_base = ch.f0;
+  EventPair eg{};
+  if ((r = prof_begin(m, m->s_gmm, 0, &eg))) return r;
+  HIP_TRY(launch_gmm_exact_listed(ga, !m->max_approx, gl, p.blk_first_of_utt[ch.u1] - p.blk_first_of_utt[ch.u0], m->s_gmm));
+  return prof_end(m, m->s_gmm, &eg);
+}
+
+static int check_automaton(const sr_model* m, const uint16_t* automata, const uint64_t* aut_off, uint32_t u) {
+  for (uint64_t i = aut_off[u]; i < aut_off[u + 1]; i++)
+    if (automata[i] >= m->n_states) return fail(SR_EINVAL, "utterance %u: automaton state %u >= n_states", u, automata[i]);
+  return SR_OK;
+}
+
+static int align_common(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
+                        uint16_t silence_state, double thr, bool pruned, int gmm_kernel, uint16_t* out_states,
+                        double* out_cost) {
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  if (!automata || !aut_off || !tdp || !out_states || !out_cost) return fail(SR_EINVAL, "null argument");
+  const uint32_t U = c->n_utts;
+  const uint64_t F = c->n_frames;
+  std::vector<uint64_t> bp_off(U + 1, 0);
+  uint32_t max_n = 1;
+  for (uint32_t u = 0; u < U; u++) {
+    const uint64_t N = aut_off[u + 1] - aut_off[u], T = c->frame_off[u + 1] - c->frame_off[u];
+    if (N < 1 || T < 1) return fail(SR_EINVAL, "utterance %u: automaton and utterance must be non-empty", u);
+    if (!pruned && N > T)
+      return fail(SR_EINVAL, "utterance %u: automaton length %llu exceeds %llu frames (Aligner::align_sequence_full indexes "
+                  "its T-sized cost arrays by position)", u, (unsigned long long)N, (unsigned long long)T);
+    if (N > align_max_positions()) return fail(SR_ELIMIT, "utterance %u: automaton length %llu exceeds %u", u, (unsigned long long)N, align_max_positions());
+    if ((rc = check_automaton(m, automata, aut_off, u))) return rc;
+    max_n = std::max<uint32_t>(max_n, (uint32_t)N);
+    bp_off[u + 1] = bp_off[u] + N * T;
+  }
+  HIP_TRY(c->bp_off.upload(bp_off.data(), U + 1));
+  HIP_TRY(c->backptr.ensure(bp_off[U]));
+  HIP_TRY(c->out_states.ensure(F));
+  HIP_TRY(c->out_cost.ensure(U));
+  AutomatonScoring sc;
+  if ((rc = automaton_scoring_setup(m, c, automata, aut_off, gmm_kernel, &sc))) return rc;
   AlignArgs aa{};
   aa.ld = m->ld; aa.frame_off = c->d_frame_off.p; aa.utt_order = c->utt_order.p; aa.automata = c->automata.p; aa.aut_off = c->aut_off.p;
   aa.tdp_loop = tdp[0]; aa.tdp_forward = tdp[1]; aa.tdp_skip = tdp[2]; aa.silence_state = silence_state;
   aa.pruning_threshold = thr; aa.backptr = c->backptr.p; aa.bp_off = c->bp_off.p; aa.max_positions = max_n;
   aa.out_states = c->out_states.p; aa.out_cost = c->out_cost.p;
-  rc = run_chunks(m, chunks,
-      [&](const Chunk& ch, double* table) -> int {
-        int r = srhost::corpus_ready(c, ch.f0, ch.f1, m->s_gmm);
-        if (r) return r;
-        if (!listed) return launch_scoring(m, c->feats.p + ch.f0 * m->dim, ch.f1 - ch.f0, gmm_kernel, table);
-        GmmExactArgs ga{};
-        ga.feats = c->feats.p; ga.n_frames = c->n_frames; ga.dim = m->dim; ga.n_states = m->n_states;
-        ga.dens_off = m->dens_off.p; ga.means = m->means.p; ga.inv_vars = m->inv_vars.p; ga.norm = m->norm.p; ga.logw = m->logw.p;
-        ga.out = table; ga.ld = m->ld;
-        GmmExactList gl{};
-        gl.blk_frame0 = c->al_blk_frame0.p; gl.blk_frames = c->al_blk_frames.p; gl.blk_list = c->al_blk_list.p;
-        gl.list_off = c->al_list_off.p; gl.states = c->al_states.p;
-        gl.blk_first = blk_first_of_utt[ch.u0]; gl.frame_base = ch.f0;
-        EventPair eg{};
-        if ((r = prof_begin(m, m->s_gmm, 0, &eg))) return r;
-        HIP_TRY(launch_gmm_exact_listed(ga, !m->max_approx, gl, blk_first_of_utt[ch.u1] - blk_first_of_utt[ch.u0], m->s_gmm));
-        return prof_end(m, m->s_gmm, &eg);
-      },
+  rc = run_chunks(m, sc.chunks,
+      [&](const Chunk& ch, double* table) -> int { return automaton_scoring_chunk(m, c, sc, ch, table); },
       [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
         aa.scores = table; aa.frame_base = ch.f0; aa.utt_first = ch.u0; aa.n_utts = ch.u1 - ch.u0;
         HIP_TRY(pruned ? launch_align_pruned(aa, s) : launch_align_full(aa, s));
@@ -1684,6 +1710,229 @@ int sr_model_create_from_accumulated(sr_model* m, sr_corpus* c, int pooling, int
   if (rc) return rc;
   if (pooling < 0 || pooling > 2) return fail(SR_EINVAL, "pooling must be 0 (global), 1 (mixture) or 2 (none)");
   return srhost::finalize_accumulated(m, c, pooling, max_approx, out);
+  });
+}
+
+// ---- forward-backward (viterbi_fb.hip) -----------------------------------------------------------------------------------
+// The argument checks both entry points share: the aligner's, with N_u <= 2 T_u - 1 (a path must exist) in place of N_u <= T_u.
+static int fb_check(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
+                    double posterior_floor, const double* out_cost) {
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  if (!automata || !aut_off || !tdp || !out_cost) return fail(SR_EINVAL, "null argument");
+  if (!(posterior_floor >= 0.0)) return fail(SR_EINVAL, "posterior_floor must be >= 0 (got %g)", posterior_floor);
+  for (uint32_t u = 0; u < c->n_utts; u++) {
+    const uint64_t N = aut_off[u + 1] - aut_off[u], T = c->frame_off[u + 1] - c->frame_off[u];
+    if (N < 1 || T < 1) return fail(SR_EINVAL, "utterance %u: automaton and utterance must be non-empty", u);
+    if (N > align_max_positions()) return fail(SR_ELIMIT, "utterance %u: automaton length %llu exceeds %u", u, (unsigned long long)N, align_max_positions());
+    if (N > 2 * T - 1)
+      return fail(SR_EINVAL, "utterance %u: automaton length %llu: no path through it in %llu frames (at most 2 T - 1 positions)", u,
+                  (unsigned long long)N, (unsigned long long)T);
+    if ((rc = check_automaton(m, automata, aut_off, u))) return rc;
+    if (8 * N * T > m->fb_budget)
+      return fail(SR_ELIMIT, "utterance %u: trellis of %llu bytes exceeds the forward-backward workspace of %llu (SRGPU_FB_MB)", u,
+                  (unsigned long long)(8 * N * T), (unsigned long long)m->fb_budget);
+  }
+  return SR_OK;
+}
+
+// One pass over the corpus on the aligner's scoring chunks; inside a chunk, consecutive utterances whose trellises fit m->fb_budget
+// together (8 B per frame and position) run forward, backward and -- want_items -- the posterior items.  Leaves F_u in c->out_cost
+// and, with want_items, *n_items items in c->fb_item_* (frame order, ascending mixture id) with c->fb_item_off[F + 1].
+static int fb_pass(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
+                   uint16_t silence_state, int gmm_kernel, double posterior_floor, bool want_items, uint64_t* n_items) {
+  const uint32_t U = c->n_utts;
+  const uint64_t F = c->n_frames;
+  *n_items = 0;
+  HIP_TRY(c->out_cost.ensure(U));
+  if (U == 0) return SR_OK;
+  // per utterance: trellis offset; its automaton's distinct mixtures (ascending) and the positions carrying each
+  std::vector<uint64_t> tr_off(U + 1, 0);
+  std::vector<uint32_t> mix_off(U + 1, 0), slot_beg;
+  std::vector<uint16_t> mix, slot_pos;
+  uint64_t item_bound = 0;
+  std::vector<std::pair<uint16_t, uint16_t>> ps;
+  for (uint32_t u = 0; u < U; u++) {
+    const uint64_t N = aut_off[u + 1] - aut_off[u], T = c->frame_off[u + 1] - c->frame_off[u];
+    tr_off[u + 1] = tr_off[u] + N * T;
+    ps.clear();
+    for (uint64_t i = 0; i < N; i++) ps.push_back({automata[aut_off[u] + i], (uint16_t)i});
+    std::sort(ps.begin(), ps.end());
+    for (size_t i = 0; i < ps.size(); i++) {
+      if (i == 0 || ps[i].first != ps[i - 1].first) {
+        mix.push_back(ps[i].first);
+        slot_beg.push_back((uint32_t)slot_pos.size());
+      }
+      slot_pos.push_back(ps[i].second);
+    }
+    mix_off[u + 1] = (uint32_t)mix.size();
+    item_bound += T * (mix_off[u + 1] - mix_off[u]);
+  }
+  slot_beg.push_back((uint32_t)slot_pos.size());
+  if (want_items && item_bound >= (1ull << 31)) return fail(SR_ELIMIT, "too many (frame, mixture) posteriors");
+  AutomatonScoring sc;
+  int rc = automaton_scoring_setup(m, c, automata, aut_off, gmm_kernel, &sc);
+  if (rc) return rc;
+  // launch groups: consecutive utterances of a chunk within the trellis budget (fb_check: every utterance fits alone)
+  struct Group { uint32_t u0, u1, max_n; };
+  std::vector<std::vector<Group>> groups(sc.chunks.size());
+  uint64_t ws = 1, max_gf = 1;
+  for (size_t ci = 0; ci < sc.chunks.size(); ci++) {
+    const Chunk& ch = sc.chunks[ci];
+    for (uint32_t u = ch.u0; u < ch.u1;) {
+      uint32_t v = u, max_n = 1;
+      while (v < ch.u1 && (v == u || 8 * (tr_off[v + 1] - tr_off[u]) <= m->fb_budget)) {
+        max_n = std::max<uint32_t>(max_n, (uint32_t)(aut_off[v + 1] - aut_off[v]));
+        v++;
+      }
+      groups[ci].push_back({u, v, max_n});
+      ws = std::max<uint64_t>(ws, tr_off[v] - tr_off[u]);
+      max_gf = std::max<uint64_t>(max_gf, c->frame_off[v] - c->frame_off[u]);
+      u = v;
+    }
+  }
+  HIP_TRY(c->fb_trellis_off.upload(tr_off.data(), U + 1));
+  HIP_TRY(c->fb_trellis.ensure(ws));
+  size_t scan_bytes = 0;
+  if (want_items) {
+    HIP_TRY(c->fb_mix_off.upload(mix_off.data(), U + 1));
+    HIP_TRY(c->fb_mix.upload(mix.data(), mix.size()));
+    HIP_TRY(c->fb_slot_beg.upload(slot_beg.data(), slot_beg.size()));
+    HIP_TRY(c->fb_slot_pos.upload(slot_pos.data(), slot_pos.size()));
+    scan_bytes = fb_scan_temp_bytes(max_gf);
+    HIP_TRY(c->fb_scan_temp.ensure(scan_bytes));
+    HIP_TRY(c->fb_cnt.ensure(max_gf)); HIP_TRY(c->fb_scan.ensure(max_gf)); HIP_TRY(c->fb_base.ensure(1));
+    HIP_TRY(c->fb_item_off.ensure(F + 1));
+    HIP_TRY(c->fb_item_frame.ensure(item_bound)); HIP_TRY(c->fb_item_mix.ensure(item_bound)); HIP_TRY(c->fb_item_w.ensure(item_bound));
+  }
+  FbArgs fa{};
+  fa.ld = m->ld; fa.frame_off = c->d_frame_off.p; fa.automata = c->automata.p; fa.aut_off = c->aut_off.p;
+  fa.tdp_loop = tdp[0]; fa.tdp_forward = tdp[1]; fa.tdp_skip = tdp[2]; fa.silence_state = silence_state;
+  fa.trellis = c->fb_trellis.p; fa.trellis_off = c->fb_trellis_off.p; fa.out_cost = c->out_cost.p;
+  fa.mix_off = c->fb_mix_off.p; fa.mix = c->fb_mix.p; fa.slot_beg = c->fb_slot_beg.p; fa.slot_pos = c->fb_slot_pos.p;
+  fa.floor = posterior_floor; fa.group_cnt = c->fb_cnt.p; fa.item_base = c->fb_base.p; fa.item_off = c->fb_item_off.p;
+  fa.item_frame = c->fb_item_frame.p; fa.item_mix = c->fb_item_mix.p; fa.item_w = c->fb_item_w.p;
+  size_t ci = 0;  // run_chunks searches the chunks in order
+  rc = run_chunks(m, sc.chunks,
+      [&](const Chunk& ch, double* table) -> int { return automaton_scoring_chunk(m, c, sc, ch, table); },
+      [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
+        if (want_items && ci == 0) HIP_TRY(hipMemsetAsync(c->fb_base.p, 0, sizeof(uint32_t), s));
+        for (const Group& g : groups[ci]) {
+          fa.scores = table; fa.frame_base = ch.f0; fa.utt_first = g.u0; fa.n_utts = g.u1 - g.u0; fa.max_positions = g.max_n;
+          fa.group_f0 = c->frame_off[g.u0];
+          HIP_TRY(launch_fb_forward(fa, s));
+          HIP_TRY(launch_fb_backward(fa, s));
+          if (want_items)
+            HIP_TRY(launch_fb_items(fa, c->frame_off[g.u1] - c->frame_off[g.u0], c->fb_scan_temp.p, scan_bytes, c->fb_scan.p, s));
+        }
+        ci++;
+        return SR_OK;
+      });
+  if (rc) return rc;
+  if (want_items) {
+    uint32_t n = 0;
+    HIP_TRY(hipMemcpy(&n, c->fb_base.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *n_items = n;
+  }
+  if (m->profiling) {  // trellis traffic per (frame, position): alpha out, alpha in + gamma out, gamma in (items)
+    m->prof.frames += F;
+    m->prof.search_bytes += (want_items ? 32.0 : 24.0) * (double)tr_off[U];
+  }
+  return SR_OK;
+}
+
+int sr_state_posteriors_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
+                               uint16_t silence_state, int gmm_kernel, double posterior_floor, uint32_t max_items, double* out_cost,
+                               uint16_t* out_count, uint16_t* out_state, double* out_weight) {
+  return guarded(__func__, [&]() -> int {
+  int rc = fb_check(m, c, automata, aut_off, tdp, posterior_floor, out_cost);
+  if (rc) return rc;
+  const bool post = out_count || out_state || out_weight;
+  if (post && (!out_count || !out_state || !out_weight)) return fail(SR_EINVAL, "null output (pass out_count, out_state and out_weight, or none)");
+  if (post && (max_items == 0 || max_items > 65535)) return fail(SR_EINVAL, "max_items must be 1 .. 65535 (got %u)", max_items);
+  const uint64_t F = c->n_frames;
+  const uint32_t U = c->n_utts;
+  uint64_t n_items = 0;
+  if ((rc = fb_pass(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, post, &n_items))) return rc;
+  if (U) HIP_TRY(hipMemcpy(out_cost, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToHost));
+  if (!post || F == 0) return SR_OK;
+  HIP_TRY(c->fb_count.ensure(F));
+  HIP_TRY(c->fb_state.ensure((size_t)F * max_items));
+  HIP_TRY(c->fb_weight.ensure((size_t)F * max_items));
+  HIP_TRY(launch_fb_top(c->fb_item_off.p, c->fb_item_mix.p, c->fb_item_w.p, F, max_items, c->fb_count.p, c->fb_state.p, c->fb_weight.p,
+                        m->s_gmm));
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  HIP_TRY(hipMemcpy(out_count, c->fb_count.p, sizeof(uint16_t) * F, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_state, c->fb_state.p, sizeof(uint16_t) * F * max_items, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_weight, c->fb_weight.p, sizeof(double) * F * max_items, hipMemcpyDeviceToHost));
+  return SR_OK;
+  });
+}
+
+int sr_baum_welch_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
+                         uint16_t silence_state, int gmm_kernel, double posterior_floor, int first_pass, int max_approx,
+                         double* out_cost, double* mean_acc, double* mean_w, double* var_acc, double* var_w) {
+  return guarded(__func__, [&]() -> int {
+  int rc = fb_check(m, c, automata, aut_off, tdp, posterior_floor, out_cost);
+  if (rc) return rc;
+  const bool to_host = mean_acc || mean_w || var_acc || var_w;  // all NULL: the statistics stay on the device
+  if (to_host && (!mean_acc || !mean_w || !var_acc || !var_w)) return fail(SR_EINVAL, "null output (pass all four arrays, or none)");
+  const uint32_t U = c->n_utts, D = m->dim;
+  c->acc_valid = false;
+  uint64_t n_items = 0;
+  if ((rc = fb_pass(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, true, &n_items))) return rc;
+  if (U) HIP_TRY(hipMemcpy(out_cost, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToHost));
+  EmArgs a{};
+  a.feats = c->feats.p; a.n_frames = c->n_frames; a.dim = D;
+  a.dens_off = m->dens_off.p; a.means = m->means.p; a.inv_vars = m->inv_vars.p; a.norm = m->norm.p; a.logw = m->logw.p;
+  a.dens_mean = m->dens_mean.p; a.dens_var = m->dens_var.p; a.n_mean = m->n_mean; a.n_var = m->n_var;
+  a.first_pass = first_pass; a.max_approx = max_approx;
+  a.n_items = n_items; a.item_frame = c->fb_item_frame.p; a.item_mix = c->fb_item_mix.p; a.item_w = c->fb_item_w.p;
+  uint64_t n_pairs = 0;
+  if (n_items) {
+    HIP_TRY(c->fb_pair_cnt.ensure(n_items));
+    HIP_TRY(c->fb_pair_end.ensure(n_items));
+    a.item_pair_end = c->fb_pair_end.p;
+    const size_t scan = em_item_scan_temp_bytes(n_items);
+    HIP_TRY(c->fb_scan_temp.ensure(scan));
+    HIP_TRY(launch_em_item_pairs(a, c->fb_scan_temp.p, scan, c->fb_pair_cnt.p, m->s_gmm));
+    HIP_TRY(hipStreamSynchronize(m->s_gmm));
+    HIP_TRY(hipMemcpy(&n_pairs, c->fb_pair_end.p + (n_items - 1), sizeof(uint64_t), hipMemcpyDeviceToHost));
+  }
+  if (n_pairs >= (1ull << 31)) return fail(SR_ELIMIT, "too many (frame, density) pairs");
+  if (n_pairs == 0) {  // nothing above the floor: reset_accumulators()
+    if (to_host) {
+      std::fill(mean_acc, mean_acc + (size_t)m->n_mean * D, 0.0);
+      std::fill(mean_w, mean_w + m->n_mean, 0.0);
+      std::fill(var_acc, var_acc + (size_t)m->n_var * D, 1e-4);
+      std::fill(var_w, var_w + m->n_var, 0.0);
+    }
+    return to_host ? SR_OK : fail(SR_EINVAL, "no posterior above the floor: nothing to keep on the device");
+  }
+  a.n_pairs = n_pairs;
+  HIP_TRY(c->pair_frame.ensure(n_pairs)); HIP_TRY(c->key_mean.ensure(n_pairs)); HIP_TRY(c->key_var.ensure(n_pairs));
+  HIP_TRY(c->pair_w.ensure(n_pairs)); HIP_TRY(c->keys_sorted.ensure(n_pairs)); HIP_TRY(c->pairs_sorted.ensure(n_pairs));
+  HIP_TRY(c->iota.ensure(n_pairs));
+  const size_t temp = em_sort_temp_bytes(n_pairs);
+  HIP_TRY(c->sort_temp.ensure(temp));
+  HIP_TRY(c->row_begin.ensure((size_t)std::max(m->n_mean, m->n_var) + 1));
+  HIP_TRY(c->acc_mean.ensure((size_t)m->n_mean * D)); HIP_TRY(c->w_mean.ensure(m->n_mean));
+  HIP_TRY(c->acc_var.ensure((size_t)m->n_var * D)); HIP_TRY(c->w_var.ensure(m->n_var));
+  a.pair_frame = c->pair_frame.p; a.pair_w = c->pair_w.p; a.key_mean = c->key_mean.p; a.key_var = c->key_var.p;
+  EventPair ep{};
+  if ((rc = prof_begin(m, m->s_gmm, 1, &ep))) return rc;
+  HIP_TRY(launch_em_accumulate_weighted(a, c->sort_temp.p, temp, c->iota.p, c->keys_sorted.p, c->pairs_sorted.p, c->row_begin.p,
+                                        c->acc_mean.p, c->w_mean.p, c->acc_var.p, c->w_var.p, m->s_gmm));
+  if ((rc = prof_end(m, m->s_gmm, &ep))) return rc;
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  c->acc_valid = true; c->acc_n_mean = m->n_mean; c->acc_n_var = m->n_var;
+  if (to_host) {
+    HIP_TRY(hipMemcpy(mean_acc, c->acc_mean.p, sizeof(double) * (size_t)m->n_mean * D, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mean_w, c->w_mean.p, sizeof(double) * m->n_mean, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(var_acc, c->acc_var.p, sizeof(double) * (size_t)m->n_var * D, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(var_w, c->w_var.p, sizeof(double) * m->n_var, hipMemcpyDeviceToHost));
+  }
+  return SR_OK;
   });
 }
 

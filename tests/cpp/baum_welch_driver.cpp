@@ -1,0 +1,72 @@
+// baum_welch_driver.cpp -- drives include/sr_sietill.hpp's sr::Trainer::baum_welch for tests/test_gpu_baum_welch.py.
+//   bw <mixset> <dim> <case.bin>   case.bin: u32 n_words, per word (u16 states, u16 repetitions), u32 silence word, f64 loop,
+//                                  forward, skip, f64 posterior_floor, u32 n_utts, per utterance u32 n_words, u32 words[],
+//                                  u32 T, f32 feats[T * dim].  Prints "cost <u> <hex bits>" per utterance and
+//                                  "stat <name> <hex bits> ..." for mean_w and var_w, then "checksum <mean_acc bits xor>".
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <string>
+#include <vector>
+
+#include "sr_sietill.hpp"
+
+template <typename T>
+static T rd(std::istream& in) {
+  T v;
+  in.read(reinterpret_cast<char*>(&v), sizeof v);
+  return v;
+}
+
+static unsigned long long bits(double d) {
+  unsigned long long b;
+  memcpy(&b, &d, sizeof b);
+  return b;
+}
+
+int main(int argc, char** argv) {
+  if (argc < 5 || strcmp(argv[1], "bw")) {
+    fprintf(stderr, "usage: %s bw <mixset> <dim> <case.bin>\n", argv[0]);
+    return 2;
+  }
+  try {
+    const size_t dim = std::stoul(argv[3]);
+    std::ifstream in(argv[4], std::ios::binary);
+    sr::Lexicon lex;
+    const uint32_t n_words = rd<uint32_t>(in);
+    std::vector<std::pair<uint16_t, uint16_t>> ws(n_words);
+    for (auto& w : ws) { w.first = rd<uint16_t>(in); w.second = rd<uint16_t>(in); }
+    const uint32_t sil = rd<uint32_t>(in);
+    for (uint32_t w = 0; w < n_words; w++) lex.add_word("w" + std::to_string(w), ws[w].first, ws[w].second, w == sil);
+    const double tl = rd<double>(in), tf = rd<double>(in), ts = rd<double>(in), floor = rd<double>(in);
+    sr::MixtureModel mm(argv[2], dim, sr::MixtureModel::NO_POOLING, true);
+    sr::TdpModel tdp(lex.get_silence_automaton().first_state(), tl, tf, ts);
+    sr::Corpus corpus(dim);
+    const uint32_t n_utts = rd<uint32_t>(in);
+    for (uint32_t u = 0; u < n_utts; u++) {
+      std::vector<sr::WordIdx> orth(rd<uint32_t>(in));
+      for (auto& w : orth) w = rd<uint32_t>(in);
+      const uint32_t T = rd<uint32_t>(in);
+      std::vector<float> f((size_t)T * dim);
+      in.read(reinterpret_cast<char*>(f.data()), sizeof(float) * f.size());
+      corpus.add_segment(f.data(), T, orth);
+    }
+    sr::Trainer trainer(lex, mm, tdp);
+    sr::Trainer::Statistics st;
+    std::vector<double> costs;
+    trainer.baum_welch(corpus, st, &costs, floor);
+    for (size_t u = 0; u < costs.size(); u++) printf("cost %zu %llx\n", u, bits(costs[u]));
+    printf("stat mean_w");
+    for (double w : st.mean_w) printf(" %llx", bits(w));
+    printf("\nstat var_w");
+    for (double w : st.var_w) printf(" %llx", bits(w));
+    unsigned long long x = 0;
+    for (double a : st.mean_acc) x ^= bits(a);
+    for (double a : st.var_acc) x ^= bits(a);
+    printf("\nchecksum %llx\n", x);
+  } catch (std::exception const& e) {
+    printf("error %s\n", e.what());
+    return 1;
+  }
+  return 0;
+}
