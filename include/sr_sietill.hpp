@@ -10,6 +10,7 @@
 //   sr::MixtureModel           MixtureModel (as scorer)     sietill/Mixtures.hpp:18-92
 //   sr::Corpus                 Corpus (feature store)       sietill/Corpus.hpp:55-84
 //   sr::Recognizer             Recognizer                   sietill/Recognizer.hpp:91-132
+//                              (+ recognize_with_confidence: each word's frame-based confidence C_max, Wessel et al. 2001)
 //   sr::StreamingRecognizer    Recognizer fed frame by frame (sr_stream_*; the shape of RWTH ASR's OfflineRecognizer::processFeature)
 //   sr::Aligner                Aligner                      sietill/Alignment.hpp:19-63
 //   sr::FeaturePostProcessor   SignalAnalysis::process_features  sietill/SignalAnalysis.cpp:320-336,340-349,379-399
@@ -331,6 +332,34 @@ class Recognizer {
     st.ser = 100.0 * st.sentence_errors / (double)n;
     st.rtf = st.seconds / (corpus.get_frame_duration() * (double)total);  // Recognizer.cpp:85
     return st;
+  }
+
+  // A recognised word with its frames within the segment and its confidence: the largest posterior p_t(word | X) over those
+  // frames, from a forward-backward over the whole recognition network without a beam (sr_recognize_confidence_corpus).
+  struct ScoredWord {
+    WordIdx word;
+    double confidence;
+    uint32_t first_frame, last_frame;
+  };
+  // The words recognize() returns for each segment (same beam and word penalty), each with its confidence.  scale (kappa > 0)
+  // multiplies every path cost before the sum: below 1 it flattens the posteriors (usual for confidences), at 1 they are peaked.
+  std::vector<std::vector<ScoredWord>> recognize_with_confidence(Corpus const& corpus, double scale = 1.0) {
+    const size_t n = std::min(corpus.get_corpus_size(), max_recognition_runs_);
+    const uint64_t total = corpus.frame_offsets()[n];
+    std::vector<uint32_t> words(std::max<uint64_t>(total, 1)), first(words.size()), last(words.size());
+    std::vector<double> conf(words.size());
+    std::vector<uint64_t> woff(n + 1);
+    const sr_search_params p = search_params();
+    sr_corpus* c = nullptr;
+    check(sr_corpus_upload(scorer_.handle(), corpus.features(), corpus.frame_offsets(), (uint32_t)n, &c));
+    const int rc = sr_recognize_confidence_corpus(scorer_.handle(), c, net_, &p, scale, words.data(), woff.data(), conf.data(),
+                                                  first.data(), last.data());
+    sr_corpus_destroy(c);
+    check(rc);
+    std::vector<std::vector<ScoredWord>> out(n);
+    for (size_t s = 0; s < n; s++)
+      for (uint64_t i = woff[s]; i < woff[s + 1]; i++) out[s].push_back(ScoredWord{(WordIdx)words[i], conf[i], first[i], last[i]});
+    return out;
   }
 
   // Recognizer::editDistance (Recognizer.cpp:332-389), including its 16-bit counters and the stale row-0

@@ -320,6 +320,34 @@ SR_API int sr_baum_welch_corpus(sr_model* m, sr_corpus* c, const uint16_t* autom
                                 int first_pass, int max_approx, double* out_cost, double* mean_acc, double* mean_w,
                                 double* var_acc, double* var_w);
 
+/* ---- word posteriors and confidences: forward-backward over the recognition network --------------------------------
+ * The network sr_recognize_corpus searches (Recognizer.cpp:103-232: the start hypothesis at word 0 position 0, in-word 0-1-2 jumps
+ * with the penalty keyed on the DESTINATION state, every word end entering every word at position 0 or 1 with the word penalty --
+ * 0 for silence -- and the emission of the word's FIRST state in both cases), with every path summed instead of only the best one
+ * kept, no beam (am_threshold is ignored) and every cost multiplied by scale = kappa > 0:
+ *   F_u = -(1/kappa) log sum over the paths that end in a word end at frame T_u - 1 of exp(-kappa cost);  F_u <= tb_score[T_u] of
+ *   sr_recognize_corpus for any beam, nondecreasing in kappa, tending to the unpruned Viterbi cost.  T_u = 0: F_u = +inf.
+ *   p_t(w | X) = the posterior mass of word w's positions at frame t (silence a word like any other; sum over w = 1).
+ * p supplies word_penalty and gmm_kernel; p->flags must be 0.  Lexica of at most 8192 positions (SR_ELIMIT).  Workspace: 8 bytes per
+ * (frame, position) for the utterances processed together, at most SRGPU_FB_MB MiB (default 1024); an utterance that alone needs
+ * more: SR_ELIMIT.  SR_EINVAL for scale not finite or not > 0, posterior_floor negative or NaN, max_items outside 1 .. 65535 with
+ * item outputs, a partial set of item outputs, a lexicon of another model.  FP64 log space without atomics: two identical calls
+ * return identical bits; +inf penalties and unreachable positions stay +inf, never NaN. */
+
+/* out_cost[n_utts] = F_u (required).  Items all or none: out_count[total_frames], out_word[total_frames * max_items],
+ * out_weight[total_frames * max_items] -- per frame the words with p > 0 and p >= posterior_floor, largest first (ties: smaller
+ * word id first), at most max_items, not renormalised; entries past out_count are 0. */
+SR_API int sr_word_posteriors_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale,
+                                     double posterior_floor, uint32_t max_items, double* out_cost, uint16_t* out_count,
+                                     uint32_t* out_word, double* out_weight);
+/* Words and out_word_off exactly as sr_recognize_corpus with the same p (beam included).  For recognised word i, out_first[i] ..
+ * out_last[i] are its frames within the utterance (from the traceback: bkp .. t - 1), and out_conf[i] = max over those frames of
+ * p_t(word | X), computed without a beam (Wessel et al. 2001's C_max).  out_words, out_conf, out_first, out_last: capacity
+ * total_frames like sr_recognize_corpus' out_words. */
+SR_API int sr_recognize_confidence_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale,
+                                          uint32_t* out_words, uint64_t* out_word_off, double* out_conf, uint32_t* out_first,
+                                          uint32_t* out_last);
+
 /* ---- bigram-LM beam search over a linear lexicon ---------------------------------------------------------------
  * Replaces Teaching::LinearSearch (rwth-asr-0.5/src/Teaching/LinearSearch.cc: initialize :489-495, processFrame
  * :496-515, getResult :517-520) for a whole corpus.  Scores are float there (Teaching/Types.hh:17); the acoustic
@@ -417,7 +445,7 @@ typedef struct {
   double gmm_flops;     /* algorithmic: 4 * dim * densities * frames per launch, summed */
   double search_ms;     /* Viterbi decode / align kernels */
   uint64_t search_launches;
-  double search_bytes;  /* algorithmic: (8*S + 4*P) * frames (decode) / (8+1)*N * frames (align) / 32*N * frames (forward-backward) */
+  double search_bytes;  /* algorithmic: (8*S + 4*P) * frames (decode) / (8+1)*N * frames (align) / 32*N * frames (forward-backward; N = P over a network) */
   uint64_t frames;      /* frames processed */
   uint64_t refined_pairs;      /* SR_GMM_PREFILTER: (frame, state) pairs scored ... */
   uint64_t refined_densities;  /* ... and densities the FP64 stage had to evaluate for them (>= 1 per pair) */

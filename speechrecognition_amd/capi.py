@@ -30,7 +30,7 @@ SYMBOLS = [
     "sr_last_error", "sr_device_count", "sr_model_create", "sr_model_load_mixset", "sr_model_destroy", "sr_model_info",
     "sr_corpus_upload", "sr_corpus_upload_async", "sr_corpus_wait", "sr_corpus_destroy", "sr_shard_utterances", "sr_recognize_batch_multi", "sr_score_corpus", "sr_score_frames", "sr_lexicon_create",
     "sr_lexicon_destroy", "sr_lexicon_describe", "sr_recognize_corpus", "sr_traceback_corpus", "sr_traceback_words", "sr_recognize_batch", "sr_align_corpus", "sr_align_corpus_pruned", "sr_path_scores_corpus", "sr_model_create_from_statistics", "sr_model_create_from_accumulated", "sr_mixset_write", "sr_model_set_tying", "sr_model_tying_info", "sr_model_topology", "sr_accumulate_corpus",
-    "sr_state_posteriors_corpus", "sr_baum_welch_corpus",
+    "sr_state_posteriors_corpus", "sr_baum_welch_corpus", "sr_word_posteriors_corpus", "sr_recognize_confidence_corpus",
     "sr_bigram_create", "sr_bigram_destroy", "sr_bigram_describe", "sr_recognize_bigram_corpus",
     "sr_stream_open", "sr_stream_begin", "sr_stream_push", "sr_stream_partial", "sr_stream_end", "sr_stream_destroy",
     "sr_bigram_stream_open", "sr_bigram_stream_begin", "sr_bigram_stream_push", "sr_bigram_stream_partial", "sr_bigram_stream_end",
@@ -108,6 +108,8 @@ def lib():
         L.sr_accumulate_corpus.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
         L.sr_state_posteriors_corpus.argtypes = [vp, vp, vp, vp, C.POINTER(dbl * 3), C.c_uint16, i32, dbl, u32, vp, vp, vp, vp]
         L.sr_baum_welch_corpus.argtypes = [vp, vp, vp, vp, C.POINTER(dbl * 3), C.c_uint16, i32, dbl, i32, i32, vp, vp, vp, vp, vp]
+        L.sr_word_posteriors_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, vp]
+        L.sr_recognize_confidence_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, vp, vp, vp, vp, vp]
         L.sr_bigram_create.argtypes = [vp, u32, vp, vp, u32, vp, vp, C.POINTER(vp)]
         L.sr_bigram_destroy.argtypes = [vp]
         L.sr_bigram_describe.argtypes = [vp, C.c_char_p, C.c_size_t]
@@ -526,6 +528,37 @@ class Corpus:
     def baum_welch_on_device(self, automata, tdp, silence_state, kernel=GMM_DEFAULT, floor=0.0, first_pass=False, max_approx=True):
         """The same, the statistics kept in this corpus handle for next_model() -> cost f64[n_utts]."""
         return self._baum_welch(automata, tdp, silence_state, kernel, floor, first_pass, max_approx, (None, None, None, None))
+
+    def word_posteriors(self, lexicon, word_penalty, scale=1.0, kernel=GMM_PREFILTER, floor=0.0, max_items=8):
+        """Forward-backward over the recognition network (sr_word_posteriors_corpus) -> (cost f64[n_utts] = -(1/scale) log P(X),
+        count u16[total_frames], word u32[total_frames, max_items], weight f64[total_frames, max_items]): per frame the words with
+        posterior >= floor, largest first, at most max_items."""
+        F = max(self.n_frames, 1)
+        K = max(int(max_items), 1)
+        cost = np.zeros(max(self.n_utts, 1), dtype=np.float64)
+        count = np.zeros(F, dtype=np.uint16)
+        word = np.zeros((F, K), dtype=np.uint32)
+        weight = np.zeros((F, K), dtype=np.float64)
+        sp = SearchParams(np.inf, word_penalty, kernel, 0)
+        _check(lib().sr_word_posteriors_corpus(self.model.h, self.h, lexicon.h, C.byref(sp), float(scale), float(floor), int(max_items),
+                                               _ptr(cost), _ptr(count), _ptr(word), _ptr(weight)))
+        n = self.n_frames
+        return cost[: self.n_utts], count[:n], word[:n], weight[:n]
+
+    def recognize_confidence(self, lexicon, am_threshold, word_penalty, scale=1.0, kernel=GMM_PREFILTER):
+        """recognize()'s words with a confidence each (sr_recognize_confidence_corpus) -> (words u32[], word_off u64[n_utts+1],
+        conf f64[], first u32[], last u32[]): conf = max posterior of the word over its frames first .. last (within the utterance)."""
+        F = max(self.n_frames, 1)
+        words = np.zeros(F, dtype=np.uint32)
+        woff = np.zeros(self.n_utts + 1, dtype=np.uint64)
+        conf = np.zeros(F, dtype=np.float64)
+        first = np.zeros(F, dtype=np.uint32)
+        last = np.zeros(F, dtype=np.uint32)
+        sp = SearchParams(am_threshold, word_penalty, kernel, 0)
+        _check(lib().sr_recognize_confidence_corpus(self.model.h, self.h, lexicon.h, C.byref(sp), float(scale), _ptr(words), _ptr(woff),
+                                                    _ptr(conf), _ptr(first), _ptr(last)))
+        n = int(woff[-1])
+        return words[:n].copy(), woff, conf[:n].copy(), first[:n].copy(), last[:n].copy()
 
     def recognize_bigram(self, bigram, acoustic_pruning=FLT_MAX, lm_pruning=FLT_MAX, kernel=GMM_PREFILTER, max_word_ends=0, dense_states=False,
                          global_states=False):

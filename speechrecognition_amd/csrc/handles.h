@@ -170,6 +170,10 @@ struct sr_corpus {
   DevBuf<uint32_t> fb_mix_off, fb_slot_beg, fb_cnt, fb_scan, fb_base, fb_item_off, fb_item_frame;
   DevBuf<uint16_t> fb_mix, fb_slot_pos, fb_item_mix, fb_count, fb_state;
   DevBuf<unsigned char> fb_scan_temp;
+  // recognition-network forward-backward (viterbi_netfb.hip; the trellis is fb_trellis): word posteriors of one launch group, outputs
+  DevBuf<double> nf_post, nf_weight, nf_conf;
+  DevBuf<uint32_t> nf_word, nf_first, nf_last;
+  DevBuf<uint16_t> nf_count;
 };
 
 struct sr_lexicon {

@@ -310,6 +310,34 @@ hipError_t launch_fb_items(const FbArgs& a, uint64_t n_frames, void* scan_temp, 
 hipError_t launch_fb_top(const uint32_t* item_off, const uint16_t* item_mix, const double* item_w, uint64_t n_frames,
                          uint32_t max_items, uint16_t* out_count, uint16_t* out_state, double* out_weight, hipStream_t stream);
 
+// ---- forward-backward over the recognition network (viterbi_netfb.hip) ------------------------------------------------
+// A launch covers utterances [utt_first, utt_first + n_utts) of one score chunk whose trellises fit the workspace together.
+struct NetFbArgs {
+  DecodeNet net;                // the lexicon's slot tables (build_decode_net); n_slots <= netfb_max_slots()
+  const double* scores;         // [frames x ld], row 0 = frame frame_base (as DecodeArgs)
+  uint32_t ld;
+  uint64_t frame_base;
+  const uint64_t* frame_off;    // [n_utts_total+1]
+  uint32_t utt_first, n_utts;
+  double scale, word_penalty;   // kappa > 0 multiplies every cost
+  uint64_t group_f0;            // first frame of the launch
+  double* trellis;              // [frames of the launch][P]: alpha, then gamma
+  double* out_cost;             // [n_utts_total] kappa F_u
+  double* post;                 // [frames of the launch][W] word posteriors p_t(w)
+};
+size_t netfb_max_slots();
+hipError_t launch_netfb_forward(const NetFbArgs& a, hipStream_t stream);
+hipError_t launch_netfb_backward(const NetFbArgs& a, hipStream_t stream);
+hipError_t launch_netfb_words(const NetFbArgs& a, uint64_t n_frames, hipStream_t stream);
+// per frame of the launch the max_items largest p_t(w) > 0 and >= floor (ties: smaller word first), at out_*[corpus frame]; entries
+// past out_count are zero
+hipError_t launch_netfb_top(const NetFbArgs& a, uint64_t n_frames, uint32_t max_items, double floor, uint16_t* out_count,
+                            uint32_t* out_word, double* out_weight, hipStream_t stream);
+// the recognised words of the launch's utterances (decoder traceback in DecodeArgs' layout, out_count from its walk): frames and
+// max p_t(word) over them at out_*[frame_off[u] + k]
+hipError_t launch_netfb_conf(const NetFbArgs& a, const uint16_t* tb_word, const uint16_t* tb_bkp, const uint32_t* out_count,
+                             double* out_conf, uint32_t* out_first, uint32_t* out_last, hipStream_t stream);
+
 // ---- bigram-LM beam search over a linear lexicon (viterbi_bigram.hip; Teaching::LinearSearch) -----------------------
 struct BigramArgs {
   const double* scores;         // [frames x ld]

@@ -1148,13 +1148,12 @@ static int gather_words(sr_corpus* c, uint32_t* out_words, uint64_t* out_word_of
   return SR_OK;
 }
 
-int sr_recognize_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, uint32_t* out_words,
-                        uint64_t* out_word_off, double* tb_score, uint16_t* tb_word, uint16_t* tb_bkp) {
-  return guarded(__func__, [&]() -> int {
-  int rc = check_corpus(m, c);
-  if (rc) return rc;
-  if (!l || l->model != m) return fail(SR_EINVAL, "lexicon does not belong to this model");
-  if (!p || !out_word_off || (!out_words && c->n_frames)) return fail(SR_EINVAL, "null argument");
+extern "C++" {  // (templates inside the entry points' extern "C" block)
+// The zerogram search of a corpus on `chunks` (prepare_chunks): the words and tracebacks stay in c->out_* / c->tb_*.  after(chunk,
+// table, stream) enqueues more work on a chunk's scores behind its search (a no-op for sr_recognize_corpus).
+template <class After>
+static int recognize_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, const std::vector<Chunk>& chunks,
+                          After after) {
   const uint32_t U = c->n_utts;
   const uint64_t F = c->n_frames;
   HIP_TRY(c->tb_score.ensure(F + U));
@@ -1164,8 +1163,6 @@ int sr_recognize_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_searc
   HIP_TRY(c->out_count.ensure(U));
   HIP_TRY(c->out_flags.ensure(U));
   HIP_TRY(hipMemsetAsync(c->out_flags.p, 0, sizeof(uint32_t) * std::max(1u, U), m->s_gmm));
-  std::vector<Chunk> chunks;
-  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
 
   DecodeArgs da = lexicon_args(l);
   da.frame_off = c->d_frame_off.p; da.utt_order = c->utt_order.p;
@@ -1177,6 +1174,7 @@ int sr_recognize_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_searc
     for (const Chunk& ch : chunks) most = std::max(most, ch.u1 - ch.u0);
     HIP_TRY(c->big_ws.ensure((size_t)most * decode_big_workspace(l->net.n_slots)));
   }
+  int rc;
   {
     bool neg = false;
     if ((rc = srhost::may_go_negative(m, &neg))) return rc;
@@ -1190,15 +1188,30 @@ int sr_recognize_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_searc
         da.scores = table; da.frame_base = ch.f0; da.utt_first = ch.u0; da.n_utts = ch.u1 - ch.u0;
         HIP_TRY(launch_decode(da, route, c->big_ws.p, s));
         if (m->profiling) m->prof.search_bytes += (8.0 * m->n_states + 4.0 * l->net.n_slots) * (double)(ch.f1 - ch.f0);
-        return SR_OK;
+        return after(ch, table, s);
       });
   if (rc) return rc;
+  if (m->profiling) m->prof.frames += F;
+  return SR_OK;
+}
+}  // extern "C++"
 
+int sr_recognize_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, uint32_t* out_words,
+                        uint64_t* out_word_off, double* tb_score, uint16_t* tb_word, uint16_t* tb_bkp) {
+  return guarded(__func__, [&]() -> int {
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  if (!l || l->model != m) return fail(SR_EINVAL, "lexicon does not belong to this model");
+  if (!p || !out_word_off || (!out_words && c->n_frames)) return fail(SR_EINVAL, "null argument");
+  const uint32_t U = c->n_utts;
+  const uint64_t F = c->n_frames;
+  std::vector<Chunk> chunks;
+  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
+  if ((rc = recognize_pass(m, c, l, p, chunks, [](const Chunk&, const double*, hipStream_t) { return (int)SR_OK; }))) return rc;
   if ((rc = gather_words(c, out_words, out_word_off))) return rc;
   if (tb_score) HIP_TRY(hipMemcpy(tb_score, c->tb_score.p, sizeof(double) * (F + U), hipMemcpyDeviceToHost));
   if (tb_word) HIP_TRY(hipMemcpy(tb_word, c->tb_word.p, sizeof(uint16_t) * (F + U), hipMemcpyDeviceToHost));
   if (tb_bkp) HIP_TRY(hipMemcpy(tb_bkp, c->tb_bkp.p, sizeof(uint16_t) * (F + U), hipMemcpyDeviceToHost));
-  if (m->profiling) m->prof.frames += F;
   return SR_OK;
   });
 }
@@ -1932,6 +1945,162 @@ int sr_baum_welch_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, co
     HIP_TRY(hipMemcpy(var_acc, c->acc_var.p, sizeof(double) * (size_t)m->n_var * D, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(var_w, c->w_var.p, sizeof(double) * m->n_var, hipMemcpyDeviceToHost));
   }
+  return SR_OK;
+  });
+}
+
+// ---- forward-backward over the recognition network (viterbi_netfb.hip) ----------------------------------------------------
+static int netfb_check(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor) {
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  if (!l || l->model != m) return fail(SR_EINVAL, "lexicon does not belong to this model");
+  if (!p) return fail(SR_EINVAL, "null argument");
+  if (p->flags != 0) return fail(SR_EINVAL, "sr_search_params.flags must be 0 (got 0x%x)", (unsigned)p->flags);
+  if (!(scale > 0.0) || !std::isfinite(scale)) return fail(SR_EINVAL, "scale must be finite and > 0 (got %g)", scale);
+  if (!(posterior_floor >= 0.0)) return fail(SR_EINVAL, "posterior_floor must be >= 0 (got %g)", posterior_floor);
+  const uint64_t P = l->net.n_slots;
+  if (P > netfb_max_slots())
+    return fail(SR_ELIMIT, "%llu lexicon positions exceed the network forward-backward's %llu", (unsigned long long)P,
+                (unsigned long long)netfb_max_slots());
+  for (uint32_t u = 0; u < c->n_utts; u++) {
+    const uint64_t T = c->frame_off[u + 1] - c->frame_off[u];
+    if (8 * P * T > m->fb_budget)
+      return fail(SR_ELIMIT, "utterance %u: trellis of %llu bytes exceeds the forward-backward workspace of %llu (SRGPU_FB_MB)", u,
+                  (unsigned long long)(8 * P * T), (unsigned long long)m->fb_budget);
+  }
+  return SR_OK;
+}
+
+// The launch groups of a pass -- consecutive utterances of a chunk whose trellises (8 B per frame and position) fit m->fb_budget
+// together (netfb_check: every utterance fits alone) -- and their workspace.  run() enqueues a chunk's groups in order: forward,
+// backward, word posteriors, then per_group(args, frames of the group).
+extern "C++" {
+struct NetFbPass {
+  struct Group { uint32_t u0, u1; };
+  std::vector<std::vector<Group>> groups;  // per chunk
+  NetFbArgs a{};
+  size_t ci = 0;  // run_chunks searches the chunks in order
+
+  int setup(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, const std::vector<Chunk>& chunks) {
+    const uint64_t P = l->net.n_slots;
+    uint64_t max_gf = 1;
+    groups.assign(chunks.size(), {});
+    for (size_t i = 0; i < chunks.size(); i++)
+      for (uint32_t u = chunks[i].u0; u < chunks[i].u1;) {
+        uint32_t v = u + 1;
+        while (v < chunks[i].u1 && 8 * P * (c->frame_off[v + 1] - c->frame_off[u]) <= m->fb_budget) v++;
+        groups[i].push_back({u, v});
+        max_gf = std::max<uint64_t>(max_gf, c->frame_off[v] - c->frame_off[u]);
+        u = v;
+      }
+    HIP_TRY(c->fb_trellis.ensure(max_gf * P));
+    HIP_TRY(c->nf_post.ensure(max_gf * l->net.n_words));
+    HIP_TRY(c->out_cost.ensure(c->n_utts));
+    a.net = l->net; a.ld = m->ld; a.frame_off = c->d_frame_off.p;
+    a.scale = scale; a.word_penalty = p->word_penalty;
+    a.trellis = c->fb_trellis.p; a.out_cost = c->out_cost.p; a.post = c->nf_post.p;
+    // trellis traffic per (frame, position): alpha out, alpha in + gamma out, gamma in (word posteriors)
+    if (m->profiling) m->prof.search_bytes += 32.0 * (double)P * (double)c->n_frames;
+    return SR_OK;
+  }
+  template <class PerGroup>
+  int run(sr_corpus* c, const Chunk& ch, const double* table, hipStream_t s, PerGroup per_group) {
+    for (const Group& g : groups[ci]) {
+      a.scores = table; a.frame_base = ch.f0; a.utt_first = g.u0; a.n_utts = g.u1 - g.u0; a.group_f0 = c->frame_off[g.u0];
+      const uint64_t n = c->frame_off[g.u1] - c->frame_off[g.u0];
+      HIP_TRY(launch_netfb_forward(a, s));
+      HIP_TRY(launch_netfb_backward(a, s));
+      HIP_TRY(launch_netfb_words(a, n, s));
+      int rc = per_group(a, n);
+      if (rc) return rc;
+    }
+    ci++;
+    return SR_OK;
+  }
+};
+}  // extern "C++"
+
+// kappa F_u on the device -> F_u
+static int netfb_costs(sr_corpus* c, double scale, double* out_cost) {
+  const uint32_t U = c->n_utts;
+  if (U) HIP_TRY(hipMemcpy(out_cost, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToHost));
+  for (uint32_t u = 0; u < U; u++) out_cost[u] /= scale;
+  return SR_OK;
+}
+
+int sr_word_posteriors_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
+                              uint32_t max_items, double* out_cost, uint16_t* out_count, uint32_t* out_word, double* out_weight) {
+  return guarded(__func__, [&]() -> int {
+  int rc = netfb_check(m, c, l, p, scale, posterior_floor);
+  if (rc) return rc;
+  if (!out_cost) return fail(SR_EINVAL, "null argument");
+  const bool post = out_count || out_word || out_weight;
+  if (post && (!out_count || !out_word || !out_weight)) return fail(SR_EINVAL, "null output (pass out_count, out_word and out_weight, or none)");
+  if (post && (max_items == 0 || max_items > 65535)) return fail(SR_EINVAL, "max_items must be 1 .. 65535 (got %u)", max_items);
+  const uint64_t F = c->n_frames;
+  std::vector<Chunk> chunks;
+  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
+  NetFbPass fp;
+  if ((rc = fp.setup(m, c, l, p, scale, chunks))) return rc;
+  if (post) {
+    HIP_TRY(c->nf_count.ensure(F));
+    HIP_TRY(c->nf_word.ensure((size_t)F * max_items));
+    HIP_TRY(c->nf_weight.ensure((size_t)F * max_items));
+  }
+  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); },
+      [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
+        return fp.run(c, ch, table, s, [&](const NetFbArgs& a, uint64_t n) -> int {
+          if (post) HIP_TRY(launch_netfb_top(a, n, max_items, posterior_floor, c->nf_count.p, c->nf_word.p, c->nf_weight.p, s));
+          return SR_OK;
+        });
+      });
+  if (rc) return rc;
+  if (m->profiling) m->prof.frames += F;
+  if ((rc = netfb_costs(c, scale, out_cost))) return rc;
+  if (!post || F == 0) return SR_OK;
+  HIP_TRY(hipMemcpy(out_count, c->nf_count.p, sizeof(uint16_t) * F, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_word, c->nf_word.p, sizeof(uint32_t) * F * max_items, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_weight, c->nf_weight.p, sizeof(double) * F * max_items, hipMemcpyDeviceToHost));
+  return SR_OK;
+  });
+}
+
+int sr_recognize_confidence_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale,
+                                   uint32_t* out_words, uint64_t* out_word_off, double* out_conf, uint32_t* out_first,
+                                   uint32_t* out_last) {
+  return guarded(__func__, [&]() -> int {
+  int rc = netfb_check(m, c, l, p, scale, 0.0);
+  if (rc) return rc;
+  const uint64_t F = c->n_frames;
+  if (!out_word_off || (F && (!out_words || !out_conf || !out_first || !out_last))) return fail(SR_EINVAL, "null argument");
+  std::vector<Chunk> chunks;
+  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
+  NetFbPass fp;
+  if ((rc = fp.setup(m, c, l, p, scale, chunks))) return rc;
+  HIP_TRY(c->nf_conf.ensure(F));
+  HIP_TRY(c->nf_first.ensure(F));
+  HIP_TRY(c->nf_last.ensure(F));
+  rc = recognize_pass(m, c, l, p, chunks, [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
+    return fp.run(c, ch, table, s, [&](const NetFbArgs& a, uint64_t) -> int {
+      HIP_TRY(launch_netfb_conf(a, c->tb_word.p, c->tb_bkp.p, c->out_count.p, c->nf_conf.p, c->nf_first.p, c->nf_last.p, s));
+      return SR_OK;
+    });
+  });
+  if (rc) return rc;
+  if ((rc = gather_words(c, out_words, out_word_off))) return rc;
+  // the device holds word k of utterance u at frame_off[u] + k, like out_words
+  std::vector<double> conf(F);
+  std::vector<uint32_t> first(F), last(F);
+  if (F) {
+    HIP_TRY(hipMemcpy(conf.data(), c->nf_conf.p, sizeof(double) * F, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(first.data(), c->nf_first.p, sizeof(uint32_t) * F, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(last.data(), c->nf_last.p, sizeof(uint32_t) * F, hipMemcpyDeviceToHost));
+  }
+  for (uint32_t u = 0; u < c->n_utts; u++)
+    for (uint64_t i = out_word_off[u]; i < out_word_off[u + 1]; i++) {
+      const uint64_t d = c->frame_off[u] + (i - out_word_off[u]);
+      out_conf[i] = conf[d]; out_first[i] = first[d]; out_last[i] = last[d];
+    }
   return SR_OK;
   });
 }
