@@ -11,6 +11,7 @@
 //   sr::Corpus                 Corpus (feature store)       sietill/Corpus.hpp:55-84
 //   sr::Recognizer             Recognizer                   sietill/Recognizer.hpp:91-132
 //                              (+ recognize_with_confidence: each word's frame-based confidence C_max, Wessel et al. 2001)
+//                              (+ recognize_nbest: the N cheapest distinct word strings of each segment's word lattice)
 //   sr::StreamingRecognizer    Recognizer fed frame by frame (sr_stream_*; the shape of RWTH ASR's OfflineRecognizer::processFeature)
 //   sr::Aligner                Aligner                      sietill/Alignment.hpp:19-63
 //   sr::FeaturePostProcessor   SignalAnalysis::process_features  sietill/SignalAnalysis.cpp:320-336,340-349,379-399
@@ -359,6 +360,53 @@ class Recognizer {
     std::vector<std::vector<ScoredWord>> out(n);
     for (size_t s = 0; s < n; s++)
       for (uint64_t i = woff[s]; i < woff[s + 1]; i++) out[s].push_back(ScoredWord{(WordIdx)words[i], conf[i], first[i], last[i]});
+    return out;
+  }
+
+  // One entry of an N-best list: a word string (silence removed) and the cost of its cheapest path through the utterance's lattice.
+  struct Hypothesis {
+    std::vector<WordIdx> words;
+    double cost;
+  };
+  // Per segment the n_best cheapest distinct word strings among the paths of its word lattice (sr_word_lattice_corpus with this
+  // recogniser's word penalty and no search beam, arcs within lattice_beam of the best path; sr_lattice_nbest), cheapest first.
+  // Entry 0 is the unpruned decoder's result; the lattice keeps one arc per (word, end frame), so later entries are upper bounds
+  // of the true k-th best cost.
+  std::vector<std::vector<Hypothesis>> recognize_nbest(Corpus const& corpus, uint32_t n_best,
+                                                       double lattice_beam = std::numeric_limits<double>::infinity()) {
+    const size_t n = std::min(corpus.get_corpus_size(), max_recognition_runs_);
+    const sr_search_params p = search_params();
+    sr_corpus* c = nullptr;
+    check(sr_corpus_upload(scorer_.handle(), corpus.features(), corpus.frame_offsets(), (uint32_t)n, &c));
+    std::vector<uint64_t> off(n + 1);
+    std::vector<double> best(std::max<size_t>(n, 1));
+    int rc = sr_word_lattice_corpus(scorer_.handle(), c, net_, &p, lattice_beam, 0, off.data(), best.data(), nullptr, nullptr,
+                                    nullptr, nullptr, nullptr, nullptr);
+    const uint64_t cap = rc == SR_OK ? std::max<uint64_t>(off[n], 1) : 1;
+    std::vector<uint32_t> word(cap), first(cap), last(cap);
+    std::vector<double> fwd(cap), bwd(cap), cost(cap);
+    if (rc == SR_OK)
+      rc = sr_word_lattice_corpus(scorer_.handle(), c, net_, &p, lattice_beam, cap, off.data(), best.data(), word.data(),
+                                  first.data(), last.data(), fwd.data(), bwd.data(), cost.data());
+    sr_corpus_destroy(c);
+    check(rc);
+    std::vector<std::vector<Hypothesis>> out(n);
+    for (size_t s = 0; s < n; s++) {
+      const uint32_t T = (uint32_t)(corpus.frame_offsets()[s + 1] - corpus.frame_offsets()[s]);
+      const uint64_t a = off[s], na = off[s + 1] - off[s];
+      std::vector<uint32_t> words((size_t)n_best * std::max<uint32_t>(T, 1));  // (a path has at most one word per frame)
+      std::vector<uint64_t> woff((size_t)n_best + 1);
+      std::vector<double> costs(std::max<uint32_t>(n_best, 1));
+      uint32_t count = 0;
+      check(sr_lattice_nbest(T, na, word.data() + a, first.data() + a, last.data() + a, cost.data() + a,
+                             (uint32_t)lexicon_.silence_idx(), n_best, words.data(), words.size(), woff.data(), costs.data(), &count));
+      for (uint32_t k = 0; k < count; k++) {
+        Hypothesis h;
+        for (uint64_t i = woff[k]; i < woff[k + 1]; i++) h.words.push_back((WordIdx)words[i]);
+        h.cost = costs[k];
+        out[s].push_back(std::move(h));
+      }
+    }
     return out;
   }
 

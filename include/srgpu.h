@@ -348,6 +348,45 @@ SR_API int sr_recognize_confidence_corpus(sr_model* m, sr_corpus* c, sr_lexicon*
                                           uint32_t* out_words, uint64_t* out_word_off, double* out_conf, uint32_t* out_first,
                                           uint32_t* out_last);
 
+/* ---- word lattices and N-best lists over the recognition network --------------------------------------------------------
+ * The same network in the MIN semiring, without a beam (am_threshold is ignored) and with the decoder's order of additions, so
+ * that every number below is a sum the decoder itself would form.  For an utterance of T frames:
+ *   A_t(s)   the cheapest path from the start hypothesis to lexicon position s at frame t; E_t = min of A_t over the word ends
+ *            (= tb_score[t + 1] of sr_recognize_corpus at an infinite beam), E_{-1} = 0;
+ *   Bend_t   the cheapest continuation after a word end at frame t to a word end at frame T - 1 (Bend_{T-1} = 0).
+ * An ARC per (word w, frame t) whose last position is reachable at t: word = w, last = t, first = the frame at which the cheapest
+ * path to (w, t) entered w (ties resolved as the decoder resolves them), fwd = A_t(end of w), bwd = Bend_t, cost = fwd -
+ * E_{first-1} (penalties and emissions of frames first .. last).  fwd + bwd is the cost of the cheapest complete path on which w
+ * ends at t.  The LATTICE of an utterance holds the arcs with fwd + bwd <= E_{T-1} + lattice_beam, ordered by last, then word
+ * (+inf: every arc on some complete path).  Silence is a word like any other.  A lattice path is a chain of arcs with first_0 = 0,
+ * first_{k+1} = last_k + 1, last_K = T - 1, its cost the sum of the arcs' cost from left to right; the cheapest one spells
+ * sr_recognize_corpus' words (infinite beam) and costs E_{T-1} up to the rounding of the arcs' cost and of their sum.  exp(-kappa (fwd + bwd - best)) is an arc's posterior-style score.
+ * APPROXIMATION: there is one arc per (word, end frame), carrying the best start only.  The paths through the lattice are a subset
+ * of the network's: the first entry of an N-best list is exact, the k-th is an upper bound of the network's k-th best cost.
+ * Limits: lexica of at most 8176 positions (SR_ELIMIT; the forward keeps 20 bytes per position in the 160 KiB LDS), utterances
+ * of at most 65535 frames.  Workspace: 10 bytes per (frame, word) + 32 per frame for the utterances processed together, at most
+ * SRGPU_FB_MB MiB (default 1024); an utterance that alone needs more: SR_ELIMIT.  min and + in FP64 without atomics: two
+ * identical calls return identical bits; +inf penalties and unreachable positions stay +inf, never NaN. */
+
+/* Lattice of every utterance.  p supplies word_penalty and gmm_kernel; p->flags must be 0; am_threshold is ignored.
+ * out_arc_off[n_utts + 1] and out_best[n_utts] (= E_{T-1}; +inf for T = 0, which has no arcs) are always written; utterance u owns
+ * arcs out_arc_off[u] .. out_arc_off[u + 1], first and last counted within the utterance.  The arc arrays (all six or none) have
+ * capacity cap arcs.  All NULL: the sizing call, SR_OK with the counts in out_arc_off.  Given but the total exceeds cap: nothing
+ * is written to them, out_arc_off still holds the counts needed, SR_EINVAL.  SR_EINVAL also for lattice_beam negative or NaN,
+ * p->flags != 0, a lexicon of another model, a partial set of arc arrays. */
+SR_API int sr_word_lattice_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double lattice_beam,
+                                  uint64_t cap, uint64_t* out_arc_off, double* out_best, uint32_t* out_word, uint32_t* out_first,
+                                  uint32_t* out_last, double* out_fwd, double* out_bwd, double* out_cost);
+/* Host only, one utterance: the n_best cheapest DISTINCT word strings (silence removed, as sr_recognize_corpus) among the lattice
+ * paths, cheapest first.  A string's cost is that of its cheapest path (the arcs' cost summed from left to right).  out_words has
+ * capacity words_cap, hypothesis k owns out_words[out_off[k] .. out_off[k + 1]); out_off[n_best + 1], out_cost[n_best];
+ * *out_count <= n_best of them exist (0 for n_frames = 0).  Arcs that no complete path uses are skipped.  Strings of equal cost
+ * come in an order that is the same on every call.  SR_EINVAL: n_best = 0, arcs not in (last, word) order, first > last, last >=
+ * n_frames, a cost that is NaN or -inf, words_cap too small (*out_count = 0). */
+SR_API int sr_lattice_nbest(uint32_t n_frames, uint64_t n_arcs, const uint32_t* word, const uint32_t* first, const uint32_t* last,
+                            const double* cost, uint32_t silence_word, uint32_t n_best, uint32_t* out_words, uint64_t words_cap,
+                            uint64_t* out_off, double* out_cost, uint32_t* out_count);
+
 /* ---- bigram-LM beam search over a linear lexicon ---------------------------------------------------------------
  * Replaces Teaching::LinearSearch (rwth-asr-0.5/src/Teaching/LinearSearch.cc: initialize :489-495, processFrame
  * :496-515, getResult :517-520) for a whole corpus.  Scores are float there (Teaching/Types.hh:17); the acoustic
@@ -445,7 +484,7 @@ typedef struct {
   double gmm_flops;     /* algorithmic: 4 * dim * densities * frames per launch, summed */
   double search_ms;     /* Viterbi decode / align kernels */
   uint64_t search_launches;
-  double search_bytes;  /* algorithmic: (8*S + 4*P) * frames (decode) / (8+1)*N * frames (align) / 32*N * frames (forward-backward; N = P over a network) */
+  double search_bytes;  /* algorithmic: (8*S + 4*P) * frames (decode) / (8+1)*N * frames (align) / 32*N * frames (forward-backward; N = P over a network) / (30*W + 48) * frames (word lattice) */
   uint64_t frames;      /* frames processed */
   uint64_t refined_pairs;      /* SR_GMM_PREFILTER: (frame, state) pairs scored ... */
   uint64_t refined_densities;  /* ... and densities the FP64 stage had to evaluate for them (>= 1 per pair) */

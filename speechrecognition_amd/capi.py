@@ -31,6 +31,7 @@ SYMBOLS = [
     "sr_corpus_upload", "sr_corpus_upload_async", "sr_corpus_wait", "sr_corpus_destroy", "sr_shard_utterances", "sr_recognize_batch_multi", "sr_score_corpus", "sr_score_frames", "sr_lexicon_create",
     "sr_lexicon_destroy", "sr_lexicon_describe", "sr_recognize_corpus", "sr_traceback_corpus", "sr_traceback_words", "sr_recognize_batch", "sr_align_corpus", "sr_align_corpus_pruned", "sr_path_scores_corpus", "sr_model_create_from_statistics", "sr_model_create_from_accumulated", "sr_mixset_write", "sr_model_set_tying", "sr_model_tying_info", "sr_model_topology", "sr_accumulate_corpus",
     "sr_state_posteriors_corpus", "sr_baum_welch_corpus", "sr_word_posteriors_corpus", "sr_recognize_confidence_corpus",
+    "sr_word_lattice_corpus", "sr_lattice_nbest",
     "sr_bigram_create", "sr_bigram_destroy", "sr_bigram_describe", "sr_recognize_bigram_corpus",
     "sr_stream_open", "sr_stream_begin", "sr_stream_push", "sr_stream_partial", "sr_stream_end", "sr_stream_destroy",
     "sr_bigram_stream_open", "sr_bigram_stream_begin", "sr_bigram_stream_push", "sr_bigram_stream_partial", "sr_bigram_stream_end",
@@ -110,6 +111,8 @@ def lib():
         L.sr_baum_welch_corpus.argtypes = [vp, vp, vp, vp, C.POINTER(dbl * 3), C.c_uint16, i32, dbl, i32, i32, vp, vp, vp, vp, vp]
         L.sr_word_posteriors_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, vp]
         L.sr_recognize_confidence_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, vp, vp, vp, vp, vp]
+        L.sr_word_lattice_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, u64, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.sr_lattice_nbest.argtypes = [u32, u64, vp, vp, vp, vp, u32, u32, vp, u64, vp, vp, C.POINTER(u32)]
         L.sr_bigram_create.argtypes = [vp, u32, vp, vp, u32, vp, vp, C.POINTER(vp)]
         L.sr_bigram_destroy.argtypes = [vp]
         L.sr_bigram_describe.argtypes = [vp, C.c_char_p, C.c_size_t]
@@ -560,6 +563,23 @@ class Corpus:
         n = int(woff[-1])
         return words[:n].copy(), woff, conf[:n].copy(), first[:n].copy(), last[:n].copy()
 
+    def word_lattice(self, lexicon, word_penalty, lattice_beam=np.inf, kernel=GMM_PREFILTER):
+        """Word lattices over the recognition network (sr_word_lattice_corpus: the sizing call, then the filling call) ->
+        (arc_off u64[n_utts+1], best f64[n_utts], word u32[], first u32[], last u32[], fwd f64[], bwd f64[], cost f64[]): utterance
+        u owns arcs arc_off[u] .. arc_off[u+1], in (last, word) order, the frames counted within the utterance."""
+        sp = SearchParams(np.inf, word_penalty, kernel, 0)
+        off = np.zeros(self.n_utts + 1, dtype=np.uint64)
+        best = np.zeros(max(self.n_utts, 1), dtype=np.float64)
+        _check(lib().sr_word_lattice_corpus(self.model.h, self.h, lexicon.h, C.byref(sp), float(lattice_beam), 0, _ptr(off), _ptr(best),
+                                            None, None, None, None, None, None))
+        n = int(off[-1])
+        cap = max(n, 1)
+        word, first, last = (np.zeros(cap, dtype=np.uint32) for _ in range(3))
+        fwd, bwd, cost = (np.zeros(cap, dtype=np.float64) for _ in range(3))
+        _check(lib().sr_word_lattice_corpus(self.model.h, self.h, lexicon.h, C.byref(sp), float(lattice_beam), cap, _ptr(off), _ptr(best),
+                                            _ptr(word), _ptr(first), _ptr(last), _ptr(fwd), _ptr(bwd), _ptr(cost)))
+        return off, best[: self.n_utts], word[:n], first[:n], last[:n], fwd[:n], bwd[:n], cost[:n]
+
     def recognize_bigram(self, bigram, acoustic_pruning=FLT_MAX, lm_pruning=FLT_MAX, kernel=GMM_PREFILTER, max_word_ends=0, dense_states=False,
                          global_states=False):
         """-> (words u32[], scores f32[], times u32[], off u64[n_utts+1]): LinearSearch::getResult per utterance.
@@ -612,6 +632,23 @@ def traceback_words(tb_word, tb_bkp, silence_word, n_words):
     n = C.c_uint32(0)
     _check(lib().sr_traceback_words(T, _ptr(tb_word), _ptr(tb_bkp), silence_word, n_words, _ptr(out), C.byref(n)))
     return out[: n.value].copy()
+
+
+def lattice_nbest(n_frames, word, first, last, cost, silence_word, n_best, words_cap=None):
+    """sr_lattice_nbest on one utterance's arcs (host side) -> [(words u32[], cost)]: the n_best cheapest distinct word strings
+    among the lattice paths, cheapest first."""
+    word, first, last = (np.ascontiguousarray(a, dtype=np.uint32) for a in (word, first, last))
+    cost = np.ascontiguousarray(cost, dtype=np.float64)
+    assert len(word) == len(first) == len(last) == len(cost)
+    K = max(int(n_best), 1)
+    cap = K * max(int(n_frames), 1) if words_cap is None else int(words_cap)  # (a path has at most one word per frame)
+    out = np.zeros(max(cap, 1), dtype=np.uint32)
+    off = np.zeros(K + 1, dtype=np.uint64)
+    oc = np.zeros(K, dtype=np.float64)
+    n = C.c_uint32(0)
+    _check(lib().sr_lattice_nbest(int(n_frames), len(word), _ptr(word), _ptr(first), _ptr(last), _ptr(cost), int(silence_word), int(n_best),
+                                  _ptr(out), cap, _ptr(off), _ptr(oc), C.byref(n)))
+    return [(out[int(off[k]):int(off[k + 1])].copy(), float(oc[k])) for k in range(n.value)]
 
 
 def mixset_write(path, dim, dens_off, dens_mean, dens_var, acc):

@@ -174,6 +174,11 @@ struct sr_corpus {
   DevBuf<double> nf_post, nf_weight, nf_conf;
   DevBuf<uint32_t> nf_word, nf_first, nf_last;
   DevBuf<uint16_t> nf_count;
+  // word lattices (viterbi_lattice.hip): the word-end tables of one launch group, the scan's workspace, the compacted arcs
+  DevBuf<double> lat_fwd, lat_ends, lat_bend, lat_arc_fwd, lat_arc_bwd, lat_arc_cost;
+  DevBuf<uint16_t> lat_first;
+  DevBuf<uint64_t> lat_cnt, lat_scan, lat_base, lat_frame_arc;
+  DevBuf<uint32_t> lat_arc_word, lat_arc_first, lat_arc_last;
 };
 
 struct sr_lexicon {

@@ -338,6 +338,34 @@ hipError_t launch_netfb_top(const NetFbArgs& a, uint64_t n_frames, uint32_t max_
 hipError_t launch_netfb_conf(const NetFbArgs& a, const uint16_t* tb_word, const uint16_t* tb_bkp, const uint32_t* out_count,
                              double* out_conf, uint32_t* out_first, uint32_t* out_last, hipStream_t stream);
 
+// ---- word lattices over the recognition network (viterbi_lattice.hip) --------------------------------------------------
+// A launch covers utterances [utt_first, utt_first + n_utts) of one score chunk whose word-end tables fit the workspace together.
+struct LatticeArgs {
+  DecodeNet net;                // the lexicon's slot tables; n_slots <= lattice_max_slots()
+  const double* scores;         // [frames x ld], row 0 = frame frame_base (as DecodeArgs)
+  uint32_t ld;
+  uint64_t frame_base;
+  const uint64_t* frame_off;    // [n_utts_total+1]
+  uint32_t utt_first, n_utts;
+  double word_penalty, beam;    // beam >= 0 (+inf: every arc on a complete path)
+  uint64_t group_f0;            // first frame of the launch
+  double* fwd;                  // [frames of the launch][W] A_t(end slot of w)
+  uint16_t* first;              // [frames of the launch][W] the frame at which that path entered w
+  double* ends;                 // [frames of the launch] E_t = min over w of fwd
+  double* bend;                 // [frames of the launch] Bend_t
+  double* out_best;             // [n_utts_total] E_{T-1} (+inf for T = 0)
+  uint32_t *arc_word, *arc_first, *arc_last;  // the compacted arcs (null: count only)
+  double *arc_fwd, *arc_bwd, *arc_cost;
+};
+size_t lattice_max_slots();
+hipError_t launch_lattice_forward(const LatticeArgs& a, hipStream_t stream);
+hipError_t launch_lattice_backward(const LatticeArgs& a, hipStream_t stream);
+size_t lattice_scan_temp_bytes(uint64_t n_frames);
+// after forward and backward: cnt / scan [n_frames] workspace; the launch's arcs go to arc_*[arc_base[0] + ...] (only below cap),
+// frame_arc[corpus frame] = the position of the frame's first arc, arc_base[0] += the launch's arcs
+hipError_t launch_lattice_emit(const LatticeArgs& a, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes, uint64_t* cnt,
+                               uint64_t* scan, uint64_t* arc_base, uint64_t* frame_arc, uint64_t cap, hipStream_t stream);
+
 // ---- bigram-LM beam search over a linear lexicon (viterbi_bigram.hip; Teaching::LinearSearch) -----------------------
 struct BigramArgs {
   const double* scores;         // [frames x ld]

@@ -13,9 +13,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <numeric>
+#include <queue>
 #include <string>
 #include <vector>
 
@@ -2101,6 +2103,219 @@ int sr_recognize_confidence_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, con
       const uint64_t d = c->frame_off[u] + (i - out_word_off[u]);
       out_conf[i] = conf[d]; out_first[i] = first[d]; out_last[i] = last[d];
     }
+  return SR_OK;
+  });
+}
+
+// ---- word lattices over the recognition network (viterbi_lattice.hip) ---------------------------------------------------------
+// Per frame the word-end tables take 8 W (fwd) + 2 W (first) + 16 (E, Bend) bytes, and the emit step's count and scan 16 more.
+static uint64_t lattice_frame_bytes(const sr_lexicon* l) { return 10ull * l->net.n_words + 32; }
+
+// The launch groups of a lattice pass -- NetFbPass' grouping on the lattice's bytes per frame: consecutive utterances of a chunk
+// whose word-end tables fit m->fb_budget together (every utterance fits alone: checked by the entry point).  run() enqueues a
+// chunk's groups in order: forward, backward, emit.
+extern "C++" {
+struct LatticePass {
+  struct Group { uint32_t u0, u1; };
+  std::vector<std::vector<Group>> groups;  // per chunk
+  LatticeArgs a{};
+  size_t ci = 0, scan_bytes = 0;
+  uint64_t cap = 0;
+
+  int setup(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double beam, uint64_t arc_cap,
+            const std::vector<Chunk>& chunks) {
+    const uint64_t per = lattice_frame_bytes(l), W = l->net.n_words;
+    uint64_t max_gf = 1;
+    groups.assign(chunks.size(), {});
+    for (size_t i = 0; i < chunks.size(); i++)
+      for (uint32_t u = chunks[i].u0; u < chunks[i].u1;) {
+        uint32_t v = u + 1;
+        while (v < chunks[i].u1 && per * (c->frame_off[v + 1] - c->frame_off[u]) <= m->fb_budget) v++;
+        groups[i].push_back({u, v});
+        max_gf = std::max<uint64_t>(max_gf, c->frame_off[v] - c->frame_off[u]);
+        u = v;
+      }
+    if (max_gf >= (1ull << 31)) return fail(SR_ELIMIT, "too many frames in one launch group");
+    HIP_TRY(c->lat_fwd.ensure(max_gf * W));
+    HIP_TRY(c->lat_first.ensure(max_gf * W));
+    HIP_TRY(c->lat_ends.ensure(max_gf));
+    HIP_TRY(c->lat_bend.ensure(max_gf));
+    HIP_TRY(c->lat_cnt.ensure(max_gf));
+    HIP_TRY(c->lat_scan.ensure(max_gf));
+    HIP_TRY(c->lat_base.ensure(1));
+    HIP_TRY(c->lat_frame_arc.ensure(c->n_frames + 1));
+    HIP_TRY(c->out_cost.ensure(c->n_utts));
+    scan_bytes = lattice_scan_temp_bytes(max_gf);
+    HIP_TRY(c->fb_scan_temp.ensure(scan_bytes));
+    HIP_TRY(hipMemset(c->lat_base.p, 0, sizeof(uint64_t)));
+    a.net = l->net; a.ld = m->ld; a.frame_off = c->d_frame_off.p;
+    a.word_penalty = p->word_penalty; a.beam = beam;
+    a.fwd = c->lat_fwd.p; a.first = c->lat_first.p; a.ends = c->lat_ends.p; a.bend = c->lat_bend.p; a.out_best = c->out_cost.p;
+    cap = arc_cap;
+    if (cap) {
+      HIP_TRY(c->lat_arc_word.ensure(cap)); HIP_TRY(c->lat_arc_first.ensure(cap)); HIP_TRY(c->lat_arc_last.ensure(cap));
+      HIP_TRY(c->lat_arc_fwd.ensure(cap)); HIP_TRY(c->lat_arc_bwd.ensure(cap)); HIP_TRY(c->lat_arc_cost.ensure(cap));
+      a.arc_word = c->lat_arc_word.p; a.arc_first = c->lat_arc_first.p; a.arc_last = c->lat_arc_last.p;
+      a.arc_fwd = c->lat_arc_fwd.p; a.arc_bwd = c->lat_arc_bwd.p; a.arc_cost = c->lat_arc_cost.p;
+    }
+    // word-end tables per frame: fwd, first, E and Bend out, then in again for the count and for the write
+    if (m->profiling) m->prof.search_bytes += (30.0 * (double)W + 48.0) * (double)c->n_frames;
+    return SR_OK;
+  }
+  int run(sr_corpus* c, const Chunk& ch, const double* table, hipStream_t s) {
+    for (const Group& g : groups[ci]) {
+      a.scores = table; a.frame_base = ch.f0; a.utt_first = g.u0; a.n_utts = g.u1 - g.u0; a.group_f0 = c->frame_off[g.u0];
+      const uint64_t n = c->frame_off[g.u1] - c->frame_off[g.u0];
+      HIP_TRY(launch_lattice_forward(a, s));
+      HIP_TRY(launch_lattice_backward(a, s));
+      HIP_TRY(launch_lattice_emit(a, n, c->fb_scan_temp.p, scan_bytes, c->lat_cnt.p, c->lat_scan.p, c->lat_base.p,
+                                  c->lat_frame_arc.p, cap, s));
+    }
+    ci++;
+    return SR_OK;
+  }
+};
+}  // extern "C++"
+
+int sr_word_lattice_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double lattice_beam, uint64_t cap,
+                           uint64_t* out_arc_off, double* out_best, uint32_t* out_word, uint32_t* out_first, uint32_t* out_last,
+                           double* out_fwd, double* out_bwd, double* out_cost) {
+  return guarded(__func__, [&]() -> int {
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  if (!l || l->model != m) return fail(SR_EINVAL, "lexicon does not belong to this model");
+  if (!p || !out_arc_off || !out_best) return fail(SR_EINVAL, "null argument");
+  if (p->flags != 0) return fail(SR_EINVAL, "sr_search_params.flags must be 0 (got 0x%x)", (unsigned)p->flags);
+  if (!(lattice_beam >= 0.0)) return fail(SR_EINVAL, "lattice_beam must be >= 0 (got %g)", lattice_beam);
+  const bool fill = out_word || out_first || out_last || out_fwd || out_bwd || out_cost;
+  if (fill && (!out_word || !out_first || !out_last || !out_fwd || !out_bwd || !out_cost))
+    return fail(SR_EINVAL, "null output (pass all six arc arrays, or none)");
+  const uint64_t P = l->net.n_slots;
+  if (P > lattice_max_slots())
+    return fail(SR_ELIMIT, "%llu lexicon positions exceed the word lattice's %llu", (unsigned long long)P,
+                (unsigned long long)lattice_max_slots());
+  const uint32_t U = c->n_utts;
+  const uint64_t F = c->n_frames, per = lattice_frame_bytes(l);
+  for (uint32_t u = 0; u < U; u++) {
+    const uint64_t T = c->frame_off[u + 1] - c->frame_off[u];
+    if (T > 65535) return fail(SR_ELIMIT, "utterance %u: %llu frames exceed the lattice's 65535", u, (unsigned long long)T);
+    if (per * T > m->fb_budget)
+      return fail(SR_ELIMIT, "utterance %u: word-end tables of %llu bytes exceed the forward-backward workspace of %llu (SRGPU_FB_MB)",
+                  u, (unsigned long long)(per * T), (unsigned long long)m->fb_budget);
+  }
+  std::vector<Chunk> chunks;
+  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
+  LatticePass lp;
+  const uint64_t dev_cap = fill ? std::min<uint64_t>(cap, F * l->net.n_words) : 0;  // (no lattice has more than F * W arcs)
+  if ((rc = lp.setup(m, c, l, p, lattice_beam, dev_cap, chunks))) return rc;
+  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); },
+                  [&](const Chunk& ch, const double* table, hipStream_t s) -> int { return lp.run(c, ch, table, s); });
+  if (rc) return rc;
+  if (m->profiling) m->prof.frames += F;
+  uint64_t total = 0;
+  HIP_TRY(hipMemcpy(&total, c->lat_base.p, sizeof(uint64_t), hipMemcpyDeviceToHost));
+  std::vector<uint64_t> frame_arc(F + 1);
+  if (F) HIP_TRY(hipMemcpy(frame_arc.data(), c->lat_frame_arc.p, sizeof(uint64_t) * F, hipMemcpyDeviceToHost));
+  frame_arc[F] = total;
+  for (uint32_t u = 0; u <= U; u++) out_arc_off[u] = frame_arc[c->frame_off[u]];
+  if (U) HIP_TRY(hipMemcpy(out_best, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToHost));
+  if (!fill) return SR_OK;
+  if (total > cap) return fail(SR_EINVAL, "the lattices hold %llu arcs, the arrays %llu", (unsigned long long)total, (unsigned long long)cap);
+  if (total) {
+    HIP_TRY(hipMemcpy(out_word, c->lat_arc_word.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_first, c->lat_arc_first.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_last, c->lat_arc_last.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_fwd, c->lat_arc_fwd.p, sizeof(double) * total, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_bwd, c->lat_arc_bwd.p, sizeof(double) * total, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_cost, c->lat_arc_cost.p, sizeof(double) * total, hipMemcpyDeviceToHost));
+  }
+  return SR_OK;
+  });
+}
+
+// Best-first search over (frame, word string so far) with the exact heuristic h[f] = the cheapest completion from frame f (one
+// backward pass over the arcs): the first time a state leaves the queue its cost is that of the string's cheapest path to it, so
+// the complete strings leave in order of their cheapest paths.  The strings live in a trie (node = parent node + word).
+int sr_lattice_nbest(uint32_t n_frames, uint64_t n_arcs, const uint32_t* word, const uint32_t* first, const uint32_t* last,
+                     const double* cost, uint32_t silence_word, uint32_t n_best, uint32_t* out_words, uint64_t words_cap,
+                     uint64_t* out_off, double* out_cost, uint32_t* out_count) {
+  return guarded(__func__, [&]() -> int {
+  if (!out_off || !out_cost || !out_count || (n_arcs && (!word || !first || !last || !cost)) || (words_cap && !out_words))
+    return fail(SR_EINVAL, "null argument");
+  *out_count = 0;
+  out_off[0] = 0;
+  if (n_best == 0) return fail(SR_EINVAL, "n_best must be >= 1");
+  const double inf = std::numeric_limits<double>::infinity();
+  for (uint64_t i = 0; i < n_arcs; i++) {
+    if (first[i] > last[i] || last[i] >= n_frames) return fail(SR_EINVAL, "arc %llu: frames %u .. %u of %u", (unsigned long long)i, first[i], last[i], n_frames);
+    if (i && (last[i] < last[i - 1] || (last[i] == last[i - 1] && word[i] < word[i - 1])))
+      return fail(SR_EINVAL, "arc %llu: the arcs are not in (last, word) order", (unsigned long long)i);
+    if (std::isnan(cost[i]) || cost[i] == -inf) return fail(SR_EINVAL, "arc %llu: cost %g", (unsigned long long)i, cost[i]);
+  }
+  if (n_frames == 0) return SR_OK;
+  const uint32_t T = n_frames;
+  // the arcs by first frame (a counting sort: arcs of one frame keep their order)
+  std::vector<uint64_t> beg(T + 2, 0);
+  for (uint64_t i = 0; i < n_arcs; i++) beg[first[i] + 1]++;
+  for (uint32_t f = 0; f <= T; f++) beg[f + 1] += beg[f];
+  std::vector<uint64_t> by_first(n_arcs), fill(beg.begin(), beg.end() - 1);
+  for (uint64_t i = 0; i < n_arcs; i++) by_first[fill[first[i]]++] = i;
+  std::vector<double> h(T + 1, inf);
+  h[T] = 0.0;
+  for (uint32_t f = T; f-- > 0;)
+    for (uint64_t k = beg[f]; k < beg[f + 1]; k++) {
+      const uint64_t i = by_first[k];
+      const double x = cost[i] + h[last[i] + 1];
+      if (x < h[f]) h[f] = x;
+    }
+  struct Node { uint32_t parent, word; };
+  std::vector<Node> trie{{0xFFFFFFFFu, 0}};  // node 0: the empty string
+  std::map<std::pair<uint32_t, uint32_t>, uint32_t> child;
+  std::map<std::pair<uint32_t, uint32_t>, double> best_g;  // (frame, node) -> the cheapest cost pushed
+  struct Item { double f, g; uint32_t frame, node; uint64_t seq; };
+  auto later = [](const Item& x, const Item& y) { return x.f > y.f || (x.f == y.f && x.seq > y.seq); };
+  std::priority_queue<Item, std::vector<Item>, decltype(later)> queue(later);
+  uint64_t seq = 0, n_words_out = 0;
+  if (h[0] < inf) {
+    best_g[{0u, 0u}] = 0.0;
+    queue.push(Item{h[0], 0.0, 0, 0, seq++});
+  }
+  uint32_t n_out = 0;
+  std::vector<uint32_t> rev;
+  while (!queue.empty() && n_out < n_best) {
+    const Item it = queue.top();
+    queue.pop();
+    if (it.g > best_g[{it.frame, it.node}]) continue;  // a cheaper path reached this state later
+    if (it.frame == T) {
+      rev.clear();
+      for (uint32_t n = it.node; n != 0; n = trie[n].parent) rev.push_back(trie[n].word);
+      if (n_words_out + rev.size() > words_cap) {
+        *out_count = 0;
+        return fail(SR_EINVAL, "words_cap %llu is too small", (unsigned long long)words_cap);
+      }
+      for (size_t k = rev.size(); k-- > 0;) out_words[n_words_out++] = rev[k];
+      out_cost[n_out] = it.g;
+      out_off[++n_out] = n_words_out;
+      continue;
+    }
+    for (uint64_t k = beg[it.frame]; k < beg[it.frame + 1]; k++) {
+      const uint64_t i = by_first[k];
+      const uint32_t nf = last[i] + 1;
+      if (!(h[nf] < inf) || !(cost[i] < inf)) continue;  // no complete path uses this arc
+      uint32_t node = it.node;
+      if (word[i] != silence_word) {
+        auto ins = child.emplace(std::make_pair(it.node, word[i]), (uint32_t)trie.size());
+        if (ins.second) trie.push_back(Node{it.node, word[i]});
+        node = ins.first->second;
+      }
+      const double g = it.g + cost[i];
+      auto bg = best_g.find({nf, node});
+      if (bg != best_g.end() && !(g < bg->second)) continue;
+      best_g[{nf, node}] = g;
+      queue.push(Item{g + h[nf], g, nf, node, seq++});
+    }
+  }
+  *out_count = n_out;
   return SR_OK;
   });
 }
