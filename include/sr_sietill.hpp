@@ -140,6 +140,10 @@ class MixtureModel : public FeatureScorer {
     num_mixtures_ = s;
     num_densities_ = c;
   }
+  // takes over a device model derived from `like` (sr::Trainer::mmi_iteration); it has no file, so it cannot replicate()
+  MixtureModel(sr_model* adopted, MixtureModel const& like)
+      : dimension(like.dimension), var_model(like.var_model), gmm_kernel(like.gmm_kernel), h_(adopted),
+        num_mixtures_(like.num_mixtures_), num_densities_(like.num_densities_), max_approx_(like.max_approx_), device_(like.device_) {}
   ~MixtureModel() { sr_model_destroy(h_); }
   MixtureModel(MixtureModel const&) = delete;
   MixtureModel& operator=(MixtureModel const&) = delete;
@@ -742,6 +746,70 @@ class Trainer {
     sr_corpus_destroy(c);
     check(rc);
     if (costs) costs->assign(cost.begin(), cost.begin() + n);
+  }
+
+  // One iteration of MMI training (sr_mmi_statistics_corpus + sr_model_create_from_mmi_statistics): the numerator over the recognition
+  // network restricted to each segment's transcript (lexicon word ids, silence not listed; silence must be word 0), the denominator
+  // over the free network, every cost multiplied by scale (kappa); then the extended Baum-Welch update of means and variances with
+  // smoothing constant E per density (D = E x denominator count, at least what keeps the variances above var_floor) and I-smoothing
+  // tau.  Returns the next model -- mixture weights unchanged -- and sets *objective (optional) to sum(F_num - F_den) >= 0 under the
+  // CURRENT model over the segments with a path through their transcript: the quantity the iteration lowers.
+  std::unique_ptr<MixtureModel> mmi_iteration(Corpus const& corpus, std::vector<std::vector<WordIdx>> const& transcripts, double scale,
+                                              double E, double tau, double* objective = nullptr, double word_penalty = 0.0,
+                                              double posterior_floor = 0.0, double var_floor = 1e-6) {
+    const size_t n = corpus.get_corpus_size();
+    if (transcripts.size() != n) throw std::invalid_argument("mmi_iteration: one transcript per segment");
+    std::vector<uint32_t> word_off(1, 0), trans(1, 0);
+    std::vector<uint16_t> automaton;
+    for (WordIdx w = 0; w < lexicon_.num_words(); w++) {
+      auto const& a = lexicon_.get_automaton_for_word(w);
+      automaton.insert(automaton.end(), a.states.begin(), a.states.end());
+      word_off.push_back((uint32_t)automaton.size());
+    }
+    std::vector<uint64_t> trans_off(1, 0);
+    trans.clear();
+    for (auto const& t : transcripts) {
+      trans.insert(trans.end(), t.begin(), t.end());
+      trans_off.push_back(trans.size());
+    }
+    trans.push_back(0);  // (never empty: the ABI tells "no transcripts" by a null pointer)
+    uint32_t n_mean = 0, n_var = 0;
+    check(sr_model_tying_info(mixtures_.handle(), &n_mean, &n_var));
+    const size_t D = mixtures_.dimension;
+    Statistics num, den;
+    for (Statistics* st : {&num, &den}) {
+      st->mean_acc.assign(n_mean * D, 0.0); st->mean_w.assign(n_mean, 0.0);
+      st->var_acc.assign(n_var * D, 0.0); st->var_w.assign(n_var, 0.0);
+    }
+    const double tdp[3] = {tdp_.tdp_loop, tdp_.tdp_forward, tdp_.tdp_skip};
+    sr_lexicon* net = nullptr;
+    check(sr_lexicon_create(mixtures_.handle(), (uint32_t)lexicon_.num_words(), word_off.data(), automaton.data(),
+                            (uint32_t)lexicon_.silence_idx(), tdp, tdp_.silence_state, &net));
+    sr_corpus* c = nullptr;
+    int rc = sr_corpus_upload(mixtures_.handle(), corpus.features(), corpus.frame_offsets(), (uint32_t)n, &c);
+    std::vector<double> f_num(std::max<size_t>(n, 1)), f_den(std::max<size_t>(n, 1));
+    if (rc == SR_OK) {
+      sr_search_params p = sr_search_params();  // zeroed, then field by field: a field added to the struct cannot shift these
+      p.word_penalty = word_penalty;
+      p.gmm_kernel = mixtures_.gmm_kernel;
+      rc = sr_mmi_statistics_corpus(mixtures_.handle(), c, net, &p, scale, posterior_floor, mixtures_.max_approx() ? 1 : 0, trans.data(),
+                                    trans_off.data(), f_num.data(), f_den.data(), num.mean_acc.data(), num.mean_w.data(),
+                                    num.var_acc.data(), num.var_w.data(), den.mean_acc.data(), den.mean_w.data(), den.var_acc.data(),
+                                    den.var_w.data());
+      sr_corpus_destroy(c);
+    }
+    sr_lexicon_destroy(net);
+    check(rc);
+    if (objective) {
+      *objective = 0.0;
+      for (size_t u = 0; u < n; u++)
+        if (f_num[u] < std::numeric_limits<double>::infinity()) *objective += f_num[u] - f_den[u];
+    }
+    sr_model* next = nullptr;
+    check(sr_model_create_from_mmi_statistics(mixtures_.handle(), num.mean_acc.data(), num.mean_w.data(), num.var_acc.data(),
+                                              num.var_w.data(), den.mean_acc.data(), den.mean_w.data(), den.var_acc.data(),
+                                              den.var_w.data(), E, tau, var_floor, &next));
+    return std::unique_ptr<MixtureModel>(new MixtureModel(next, mixtures_));
   }
 
   // Trainer::calc_am_score (Training.cpp:585-612): sequential sum of score(frame, aligned state) / frames

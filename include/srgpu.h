@@ -348,6 +348,52 @@ SR_API int sr_recognize_confidence_corpus(sr_model* m, sr_corpus* c, sr_lexicon*
                                           uint32_t* out_words, uint64_t* out_word_off, double* out_conf, uint32_t* out_first,
                                           uint32_t* out_last);
 
+/* ---- MMI training: mixture occupancies, numerator / denominator statistics, extended Baum-Welch ---------------------------------
+ * Both networks are the one above (scale, penalties, start hypothesis, p as sr_word_posteriors_corpus).
+ *   FREE network (denominator): every path, F_den = the F_u of sr_word_posteriors_corpus.
+ *   TRANSCRIPT-CONSTRAINED network (numerator): transcript of utterance u = trans[trans_off[u] .. trans_off[u + 1]) (lexicon word
+ *   ids, silence not listed, possibly empty); the subset of the free network's paths whose word string with silence removed -- what
+ *   sr_recognize_corpus would print for the path -- is the transcript: the chain of segments sil_0 w_1 sil_1 .. w_n sil_n, a word end
+ *   entering the next word segment, the silence segment after it and, from a silence segment, that segment again.  It needs the
+ *   lexicon's word 0 to be its silence word.  F_num is the same formula over the subset, so F_num >= F_den up to rounding; a
+ *   transcript without a path (too few frames) has F_num = +inf.
+ *   occ_t(k) = the posterior probability that frame t's emission is mixture k's = dF / d e(t, k); sum over k = 1.  An entry into
+ *   position 1 of a word emits the word's FIRST state (the reference's quirk) and counts for that state.
+ * Limits as sr_word_posteriors_corpus; a chain of more than 8192 positions: SR_ELIMIT; its trellis takes 8 bytes per (frame, chain
+ * position) of the SRGPU_FB_MB workspace.  SR_EINVAL also for trans without trans_off or the reverse, trans_off[0] != 0 or
+ * decreasing, a word id >= n_words or equal to the silence word, word 0 not the silence word with a transcript.  No atomics: two
+ * identical calls return identical bits. */
+
+/* out_cost[n_utts] = F_u (required) of the free network (trans and trans_off NULL) or the constrained one (both given).  Items in
+ * AlignmentItem shape like sr_state_posteriors_corpus, all or none: per frame the mixtures with occ > 0 and occ >=
+ * posterior_floor, largest first (ties: smaller id first), at most max_items (1 .. 65535), not renormalised. */
+SR_API int sr_net_occupancies_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale,
+                                     double posterior_floor, uint32_t max_items, const uint32_t* trans, const uint64_t* trans_off,
+                                     double* out_cost, uint16_t* out_count, uint16_t* out_state, double* out_weight);
+
+/* One MMI E-step: both passes, each side's occupancies accumulated as sr_baum_welch_corpus accumulates its posteriors (max_approx:
+ * the arg-min density, else the soft memberships), ONLY over utterances with finite F_num (the others contribute to neither side).
+ * out_num_cost[n_utts] = F_num, out_den_cost[n_utts] = F_den.  All outputs required, the statistics shaped as sr_accumulate_corpus'.
+ * Statistics of corpus shards add up like sr_accumulate_corpus'; the var_acc seed of 1e-4 is present once per call and side. */
+SR_API int sr_mmi_statistics_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale,
+                                    double posterior_floor, int max_approx, const uint32_t* trans, const uint64_t* trans_off,
+                                    double* out_num_cost, double* out_den_cost, double* num_mean_acc, double* num_mean_w,
+                                    double* num_var_acc, double* num_var_w, double* den_mean_acc, double* den_mean_w,
+                                    double* den_var_acc, double* den_var_w);
+
+/* Extended Baum-Welch update of the means and variances of m from one call's (or the summed shards') statistics -> new device
+ * model of m's topology.  Per density, with counts gn, gd (the mean_w), sums xn, xd, second-order sums sn, sd (the 1e-4 seed
+ * subtracted), old mu and var = 1 / inv_var:  if tau > 0 and gn > 0 the numerator's three are scaled by (gn + tau) / gn
+ * (I-smoothing);  D = max(E gd, 2 max(gd - gn, 0) + 1e-10), doubled (at most 64 times) until every dimension's new variance is
+ * >= var_floor, what still is not is set to var_floor;  mu' = (xn - xd + D mu) / (gn - gd + D),
+ * var' = (sn - sd + D (var + mu^2)) / (gn - gd + D) - mu'^2.  A density with gn = gd = 0 keeps mean and variance.  The mixture
+ * weights are m's (no weight update); norm is recomputed from the new variances.  m must be untied -- every density with its own
+ * mean and variance row -- else SR_EINVAL; SR_EINVAL also for E <= 0, tau < 0, var_floor <= 0 or any of them not finite. */
+SR_API int sr_model_create_from_mmi_statistics(sr_model* m, const double* num_mean_acc, const double* num_mean_w,
+                                               const double* num_var_acc, const double* num_var_w, const double* den_mean_acc,
+                                               const double* den_mean_w, const double* den_var_acc, const double* den_var_w,
+                                               double E, double tau, double var_floor, sr_model** out);
+
 /* ---- word lattices and N-best lists over the recognition network --------------------------------------------------------
  * The same network in the MIN semiring, without a beam (am_threshold is ignored) and with the decoder's order of additions, so
  * that every number below is a sum the decoder itself would form.  For an utterance of T frames:

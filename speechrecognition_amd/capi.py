@@ -31,6 +31,7 @@ SYMBOLS = [
     "sr_corpus_upload", "sr_corpus_upload_async", "sr_corpus_wait", "sr_corpus_destroy", "sr_shard_utterances", "sr_recognize_batch_multi", "sr_score_corpus", "sr_score_frames", "sr_lexicon_create",
     "sr_lexicon_destroy", "sr_lexicon_describe", "sr_recognize_corpus", "sr_traceback_corpus", "sr_traceback_words", "sr_recognize_batch", "sr_align_corpus", "sr_align_corpus_pruned", "sr_path_scores_corpus", "sr_model_create_from_statistics", "sr_model_create_from_accumulated", "sr_mixset_write", "sr_model_set_tying", "sr_model_tying_info", "sr_model_topology", "sr_accumulate_corpus",
     "sr_state_posteriors_corpus", "sr_baum_welch_corpus", "sr_word_posteriors_corpus", "sr_recognize_confidence_corpus",
+    "sr_net_occupancies_corpus", "sr_mmi_statistics_corpus", "sr_model_create_from_mmi_statistics",
     "sr_word_lattice_corpus", "sr_lattice_nbest",
     "sr_bigram_create", "sr_bigram_destroy", "sr_bigram_describe", "sr_recognize_bigram_corpus",
     "sr_stream_open", "sr_stream_begin", "sr_stream_push", "sr_stream_partial", "sr_stream_end", "sr_stream_destroy",
@@ -111,6 +112,9 @@ def lib():
         L.sr_baum_welch_corpus.argtypes = [vp, vp, vp, vp, C.POINTER(dbl * 3), C.c_uint16, i32, dbl, i32, i32, vp, vp, vp, vp, vp]
         L.sr_word_posteriors_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, vp]
         L.sr_recognize_confidence_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, vp, vp, vp, vp, vp]
+        L.sr_net_occupancies_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, vp, vp, vp]
+        L.sr_mmi_statistics_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, i32, vp, vp] + [vp] * 10
+        L.sr_model_create_from_mmi_statistics.argtypes = [vp] + [vp] * 8 + [dbl, dbl, dbl, C.POINTER(vp)]
         L.sr_word_lattice_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, u64, vp, vp, vp, vp, vp, vp, vp, vp]
         L.sr_lattice_nbest.argtypes = [u32, u64, vp, vp, vp, vp, u32, u32, vp, u64, vp, vp, C.POINTER(u32)]
         L.sr_bigram_create.argtypes = [vp, u32, vp, vp, u32, vp, vp, C.POINTER(vp)]
@@ -190,6 +194,15 @@ class Model:
                                                      _ptr(dens_var), _ptr(ma), _ptr(mw), _ptr(va), _ptr(vw), pooling, int(max_approx),
                                                      C.byref(h)))
         return cls(h)
+
+    def from_mmi_statistics(self, num, den, E, tau=0.0, var_floor=1e-6):
+        """Extended Baum-Welch update of this model's means and variances from the statistics of Corpus.mmi_statistics
+        (sr_model_create_from_mmi_statistics) -> new device model; the mixture weights stay."""
+        arrs = [np.ascontiguousarray(x, dtype=np.float64) for x in tuple(num) + tuple(den)]
+        h = C.c_void_p()
+        _check(lib().sr_model_create_from_mmi_statistics(self.h, *[_ptr(a) for a in arrs], float(E), float(tau), float(var_floor),
+                                                         C.byref(h)))
+        return Model(h)
 
     def topology(self):
         """-> (dens_off u32[S+1], dens_mean u32[C], dens_var u32[C]): what mixset_write / from_statistics take."""
@@ -547,6 +560,46 @@ class Corpus:
                                                _ptr(cost), _ptr(count), _ptr(word), _ptr(weight)))
         n = self.n_frames
         return cost[: self.n_utts], count[:n], word[:n], weight[:n]
+
+    @staticmethod
+    def _transcripts(transcripts):
+        """list of word-id sequences -> (trans u32[], trans_off u64[n_utts + 1]); None -> (None, None): the free network"""
+        if transcripts is None:
+            return None, None
+        off = np.concatenate([[0], np.cumsum([len(t) for t in transcripts])]).astype(np.uint64)
+        flat = np.concatenate([np.asarray(t, dtype=np.uint32) for t in transcripts] + [np.zeros(1, np.uint32)])
+        return np.ascontiguousarray(flat, dtype=np.uint32), off
+
+    def net_occupancies(self, lexicon, word_penalty, scale=1.0, transcripts=None, kernel=GMM_PREFILTER, floor=0.0, max_items=8):
+        """Mixture occupancies over the recognition network (sr_net_occupancies_corpus): the free network, or -- transcripts = one
+        sequence of word ids per utterance, silence not listed -- the network restricted to them -> (cost f64[n_utts], count
+        u16[total_frames], state u16[total_frames, max_items], weight f64[total_frames, max_items]) as state_posteriors."""
+        F = max(self.n_frames, 1)
+        K = max(int(max_items), 1)
+        cost = np.zeros(max(self.n_utts, 1), dtype=np.float64)
+        count = np.zeros(F, dtype=np.uint16)
+        state = np.zeros((F, K), dtype=np.uint16)
+        weight = np.zeros((F, K), dtype=np.float64)
+        sp = SearchParams(np.inf, word_penalty, kernel, 0)
+        flat, off = self._transcripts(transcripts)
+        _check(lib().sr_net_occupancies_corpus(self.model.h, self.h, lexicon.h, C.byref(sp), float(scale), float(floor), int(max_items),
+                                               _ptr(flat), _ptr(off), _ptr(cost), _ptr(count), _ptr(state), _ptr(weight)))
+        n = self.n_frames
+        return cost[: self.n_utts], count[:n], state[:n], weight[:n]
+
+    def mmi_statistics(self, lexicon, word_penalty, transcripts, scale=1.0, kernel=GMM_PREFILTER, floor=0.0, max_approx=True):
+        """One MMI E-step (sr_mmi_statistics_corpus) -> (F_num f64[n_utts], F_den f64[n_utts], num, den), each side's statistics
+        (mean_acc, mean_w, var_acc, var_w) over the utterances with finite F_num."""
+        nm, nv = C.c_uint32(), C.c_uint32()
+        _check(lib().sr_model_tying_info(self.model.h, C.byref(nm), C.byref(nv)))
+        D = self.model.dim
+        num, den = ((np.zeros((nm.value, D)), np.zeros(nm.value), np.zeros((nv.value, D)), np.zeros(nv.value)) for _ in range(2))
+        fn, fd = (np.zeros(max(self.n_utts, 1), dtype=np.float64) for _ in range(2))
+        sp = SearchParams(np.inf, word_penalty, kernel, 0)
+        flat, off = self._transcripts(transcripts)
+        _check(lib().sr_mmi_statistics_corpus(self.model.h, self.h, lexicon.h, C.byref(sp), float(scale), float(floor), int(max_approx),
+                                              _ptr(flat), _ptr(off), _ptr(fn), _ptr(fd), *[_ptr(a) for a in num + den]))
+        return fn[: self.n_utts], fd[: self.n_utts], num, den
 
     def recognize_confidence(self, lexicon, am_threshold, word_penalty, scale=1.0, kernel=GMM_PREFILTER):
         """recognize()'s words with a confidence each (sr_recognize_confidence_corpus) -> (words u32[], word_off u64[n_utts+1],

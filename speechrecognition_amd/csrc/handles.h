@@ -174,6 +174,11 @@ struct sr_corpus {
   DevBuf<double> nf_post, nf_weight, nf_conf;
   DevBuf<uint32_t> nf_word, nf_first, nf_last;
   DevBuf<uint16_t> nf_count;
+  // MMI training (viterbi_mmi.hip; trellis, mixture lists and items are the fb_* buffers): the word-end sums of one launch group, the
+  // transcripts' chains, the numerator's costs (the gate of the denominator's statistics)
+  DevBuf<double> nf_ends, mmi_num_cost;
+  DevBuf<uint64_t> mmi_chain_off;
+  DevBuf<uint32_t> mmi_info, mmi_src, mmi_dst;
   // word lattices (viterbi_lattice.hip): the word-end tables of one launch group, the scan's workspace, the compacted arcs
   DevBuf<double> lat_fwd, lat_ends, lat_bend, lat_arc_fwd, lat_arc_bwd, lat_arc_cost;
   DevBuf<uint16_t> lat_first;
@@ -185,6 +190,7 @@ struct sr_lexicon {
   sr_model* model = nullptr;
   // the search networks (kernels.h; build_decode_net, build_fast_net, build_word_net), pointing into the buffers below
   srgpu::DecodeNet net{};
+  std::vector<uint32_t> h_slot_info, h_word_off;  // host copies of net.slot_info and the words' first slots [W + 1] (transcript chains)
   srgpu::FastNet fast{};    // n_slots = 0: none -- more slots than the LDS kernels hold, decode_big_kernel
   srgpu::WordNet words{};   // info = null: none -- some word has more than 4 positions, or the words do not fit a workgroup
   DevBuf<uint32_t> slot_info, slot_word, word_end_slot;

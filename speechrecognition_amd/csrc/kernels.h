@@ -324,6 +324,7 @@ struct NetFbArgs {
   double* trellis;              // [frames of the launch][P]: alpha, then gamma
   double* out_cost;             // [n_utts_total] kappa F_u
   double* post;                 // [frames of the launch][W] word posteriors p_t(w)
+  double* ends;                 // [frames of the launch] the word-end sums E_t, kept for netocc_backward_kernel; null: not kept
 };
 size_t netfb_max_slots();
 hipError_t launch_netfb_forward(const NetFbArgs& a, hipStream_t stream);
@@ -337,6 +338,68 @@ hipError_t launch_netfb_top(const NetFbArgs& a, uint64_t n_frames, uint32_t max_
 // max p_t(word) over them at out_*[frame_off[u] + k]
 hipError_t launch_netfb_conf(const NetFbArgs& a, const uint16_t* tb_word, const uint16_t* tb_bkp, const uint32_t* out_count,
                              double* out_conf, uint32_t* out_first, uint32_t* out_last, hipStream_t stream);
+
+// ---- MMI training over the recognition network (viterbi_mmi.hip) ------------------------------------------------------------------
+// netfb_backward_kernel's twin that leaves mixture-occupancy parts instead of gamma in the trellis (a.ends = the E_t of the forward pass)
+hipError_t launch_netocc_backward(const NetFbArgs& a, hipStream_t stream);
+// The network restricted to a transcript: utterance u's chain of segments sil_0 w_1 sil_1 .. w_n sil_n, its positions at
+// chain_off[u] .. chain_off[u + 1] (at most netfb_max_slots()).  A launch covers utterances [utt_first, utt_first + n_utts) of one score
+// chunk whose trellises fit the workspace together.
+struct ChainArgs {
+  const double* scores;         // [frames x ld], row 0 = frame frame_base (as DecodeArgs)
+  uint32_t ld;
+  uint64_t frame_base;
+  const uint64_t* frame_off;    // [n_utts_total+1]
+  uint32_t utt_first, n_utts;
+  double scale, word_penalty;   // as NetFbArgs
+  double tdp_loop, tdp_forward, tdp_skip;
+  const uint64_t* chain_off;    // [n_utts_total+1]
+  const uint32_t* info;         // per chain position: the slot_info of its lexicon slot
+  const uint32_t* src;          // positions 0 and 1 of a segment: the (up to two) word ends that enter it, chain position | chain position << 16, 0xFFFF = none
+  const uint32_t* dst;          // word ends: position 0 of the (up to two) segments they enter, packed the same way
+  uint32_t sil_len;             // positions of the silence word: the word end of w_n is that far before the chain's last position
+  uint32_t max_positions;       // longest chain of the launch (sizes the LDS)
+  double* trellis;              // [T_u][N_u] per utterance at trellis_off[u] - trellis_off[utt_first]: alpha, then the occupancy parts
+  const uint64_t* trellis_off;  // [n_utts_total+1] prefix sums of T_u * N_u
+  double* out_cost;             // [n_utts_total] kappa F_u
+};
+hipError_t launch_chain_forward(const ChainArgs& a, hipStream_t stream);
+hipError_t launch_chain_backward(const ChainArgs& a, hipStream_t stream);
+// Items (frame, mixture, occupancy) from the occupancy parts of either network, in FbArgs' item layout.
+struct OccItemArgs {
+  const uint64_t* frame_off;    // [n_utts_total+1]
+  uint32_t utt_first, n_utts;
+  uint64_t group_f0;            // first frame of the launch
+  const double* trellis;
+  const uint64_t* trellis_off;  // chains: as ChainArgs; null: the free network, rows of n_cols at (frame - group_f0) * n_cols
+  const uint64_t* chain_off;    // chains: as ChainArgs; null
+  uint32_t n_cols, n_mix;       // free network: slots, distinct mixtures of the lexicon (one list for every utterance)
+  const uint32_t* mix_off;      // chains: [n_utts_total+1] range of utterance u in mix[] / slot_beg[]; null
+  const uint16_t* mix;          // distinct mixtures, ascending
+  const uint32_t* slot_beg;     // positions of mixture j: slot_pos[slot_beg[j] .. slot_beg[j+1])
+  const uint16_t* slot_pos;     // positions grouped by mixture, ascending within
+  const double* gate;           // optional [n_utts_total]: an utterance whose gate is +inf gives no items
+  double floor;                 // items: occupancy > 0 and >= floor
+  uint32_t* group_cnt;          // the rest as in FbArgs
+  const uint32_t* group_scan;
+  uint32_t* item_base;
+  uint32_t* item_off;
+  uint32_t* item_frame; uint16_t* item_mix; double* item_w;
+};
+hipError_t launch_occ_items(const OccItemArgs& a, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes, uint32_t* scan_out,
+                            hipStream_t stream);
+// Extended Baum-Welch: numerator and denominator statistics (accumulator rows as EmArgs) + the old tables -> new means, variances and
+// inverse variances per density
+struct EbwArgs {
+  uint64_t n_dens;
+  uint32_t dim;
+  const uint32_t* dens_mean; const uint32_t* dens_var;
+  const double* old_means; const double* old_inv_vars;  // [C x dim]
+  const double *num_mean_acc, *num_mean_w, *num_var_acc, *den_mean_acc, *den_mean_w, *den_var_acc;
+  double E, tau, var_floor;
+  double* means; double* vars; double* inv_vars;          // [C x dim]
+};
+hipError_t launch_ebw_combine(const EbwArgs& a, hipStream_t stream);
 
 // ---- word lattices over the recognition network (viterbi_lattice.hip) --------------------------------------------------
 // A launch covers utterances [utt_first, utt_first + n_utts) of one score chunk whose word-end tables fit the workspace together.

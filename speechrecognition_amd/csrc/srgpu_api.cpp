@@ -1080,6 +1080,8 @@ int sr_lexicon_create(sr_model* m, uint32_t n_words, const uint32_t* word_off, c
   std::unique_ptr<sr_lexicon, int (*)(sr_lexicon*)> own(l, sr_lexicon_destroy);
   l->model = m;
   l->net = build_decode_net(n_words, word_off, automaton, silence_idx, silence_state, tdp, info, sword, wend);
+  l->h_slot_info = info;
+  l->h_word_off.assign(word_off, word_off + n_words + 1);
   l->fast = build_fast_net(info, sword, word_off, f_state, f_pred, f_orig, f_type, f_word);
   l->words = build_word_net(n_words, word_off, automaton, silence_idx, silence_state, w_info, w_states, w_order);
   hipError_t e;
@@ -1884,19 +1886,12 @@ int sr_state_posteriors_corpus(sr_model* m, sr_corpus* c, const uint16_t* automa
   });
 }
 
-int sr_baum_welch_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
-                         uint16_t silence_state, int gmm_kernel, double posterior_floor, int first_pass, int max_approx,
-                         double* out_cost, double* mean_acc, double* mean_w, double* var_acc, double* var_w) {
-  return guarded(__func__, [&]() -> int {
-  int rc = fb_check(m, c, automata, aut_off, tdp, posterior_floor, out_cost);
-  if (rc) return rc;
-  const bool to_host = mean_acc || mean_w || var_acc || var_w;  // all NULL: the statistics stay on the device
-  if (to_host && (!mean_acc || !mean_w || !var_acc || !var_w)) return fail(SR_EINVAL, "null output (pass all four arrays, or none)");
-  const uint32_t U = c->n_utts, D = m->dim;
-  c->acc_valid = false;
-  uint64_t n_items = 0;
-  if ((rc = fb_pass(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, true, &n_items))) return rc;
-  if (U) HIP_TRY(hipMemcpy(out_cost, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToHost));
+// The posterior-weighted statistics of the n_items items a pass left in c->fb_item_* (fb_pass, occ_pass), in c->acc_* and -- to_host --
+// the four arrays.
+static int accumulate_items(sr_model* m, sr_corpus* c, uint64_t n_items, int first_pass, int max_approx, bool to_host, double* mean_acc,
+                            double* mean_w, double* var_acc, double* var_w) {
+  const uint32_t D = m->dim;
+  int rc;
   EmArgs a{};
   a.feats = c->feats.p; a.n_frames = c->n_frames; a.dim = D;
   a.dens_off = m->dens_off.p; a.means = m->means.p; a.inv_vars = m->inv_vars.p; a.norm = m->norm.p; a.logw = m->logw.p;
@@ -1948,6 +1943,22 @@ int sr_baum_welch_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, co
     HIP_TRY(hipMemcpy(var_w, c->w_var.p, sizeof(double) * m->n_var, hipMemcpyDeviceToHost));
   }
   return SR_OK;
+}
+
+int sr_baum_welch_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
+                         uint16_t silence_state, int gmm_kernel, double posterior_floor, int first_pass, int max_approx,
+                         double* out_cost, double* mean_acc, double* mean_w, double* var_acc, double* var_w) {
+  return guarded(__func__, [&]() -> int {
+  int rc = fb_check(m, c, automata, aut_off, tdp, posterior_floor, out_cost);
+  if (rc) return rc;
+  const bool to_host = mean_acc || mean_w || var_acc || var_w;  // all NULL: the statistics stay on the device
+  if (to_host && (!mean_acc || !mean_w || !var_acc || !var_w)) return fail(SR_EINVAL, "null output (pass all four arrays, or none)");
+  const uint32_t U = c->n_utts;
+  c->acc_valid = false;
+  uint64_t n_items = 0;
+  if ((rc = fb_pass(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, true, &n_items))) return rc;
+  if (U) HIP_TRY(hipMemcpy(out_cost, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToHost));
+  return accumulate_items(m, c, n_items, first_pass, max_approx, to_host, mean_acc, mean_w, var_acc, var_w);
   });
 }
 
@@ -2103,6 +2114,333 @@ int sr_recognize_confidence_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, con
       const uint64_t d = c->frame_off[u] + (i - out_word_off[u]);
       out_conf[i] = conf[d]; out_first[i] = first[d]; out_last[i] = last[d];
     }
+  return SR_OK;
+  });
+}
+
+// ---- MMI training over the recognition network (viterbi_mmi.hip) -----------------------------------------------------------------
+// The transcripts' chains: segment g of utterance u is the silence word (g even) or w_{(g+1)/2} (g odd), each with the slot_info of
+// its lexicon word; ChainArgs' src / dst links as its header says.
+extern "C++" {
+struct Chains {
+  std::vector<uint64_t> off;  // [U + 1]
+  std::vector<uint32_t> info, src, dst;
+  uint32_t sil_len = 0;
+};
+}  // extern "C++"
+
+// netfb_check plus the transcript's: *constrained = a transcript pair is given
+static int occ_check(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
+                     const uint32_t* trans, const uint64_t* trans_off, bool* constrained) {
+  int rc = netfb_check(m, c, l, p, scale, posterior_floor);
+  if (rc) return rc;
+  if ((trans_off == nullptr) != (trans == nullptr))
+    return fail(SR_EINVAL, "partial transcript (pass trans and trans_off, or neither)");
+  *constrained = trans_off != nullptr;
+  if (!*constrained) return SR_OK;
+  if (l->net.silence_word != 0) return fail(SR_EINVAL, "the transcript-constrained network needs the silence word to be word 0 (it is %u)", l->net.silence_word);
+  if (trans_off[0] != 0) return fail(SR_EINVAL, "trans_off[0] must be 0");
+  const uint64_t sil = l->h_word_off[1];
+  for (uint32_t u = 0; u < c->n_utts; u++) {
+    if (trans_off[u + 1] < trans_off[u]) return fail(SR_EINVAL, "trans_off must be non-decreasing (utterance %u)", u);
+    const uint64_t n = trans_off[u + 1] - trans_off[u], T = c->frame_off[u + 1] - c->frame_off[u];
+    if (n > netfb_max_slots()) return fail(SR_ELIMIT, "utterance %u: transcript of %llu words", u, (unsigned long long)n);
+    uint64_t N = sil * (n + 1);
+    for (uint64_t i = trans_off[u]; i < trans_off[u + 1]; i++) {
+      const uint32_t w = trans[i];
+      if (w >= l->net.n_words || w == 0)
+        return fail(SR_EINVAL, "utterance %u: transcript word %u is not a lexicon word other than silence", u, w);
+      N += l->h_word_off[w + 1] - l->h_word_off[w];
+    }
+    if (N > netfb_max_slots())
+      return fail(SR_ELIMIT, "utterance %u: chain of %llu positions exceeds the network forward-backward's %llu", u, (unsigned long long)N,
+                  (unsigned long long)netfb_max_slots());
+    if (8 * N * T > m->fb_budget)
+      return fail(SR_ELIMIT, "utterance %u: trellis of %llu bytes exceeds the forward-backward workspace of %llu (SRGPU_FB_MB)", u,
+                  (unsigned long long)(8 * N * T), (unsigned long long)m->fb_budget);
+  }
+  return SR_OK;
+}
+
+static void build_chains(const sr_lexicon* l, uint32_t U, const uint32_t* trans, const uint64_t* trans_off, Chains* ch) {
+  const std::vector<uint32_t>& woff = l->h_word_off;
+  ch->sil_len = woff[1];
+  ch->off.assign(U + 1, 0);
+  std::vector<uint32_t> beg, end;  // first and last chain position of every segment
+  for (uint32_t u = 0; u < U; u++) {
+    const uint32_t n = (uint32_t)(trans_off[u + 1] - trans_off[u]), G = 2 * n + 1, base = (uint32_t)ch->info.size();
+    beg.assign(G, 0); end.assign(G, 0);
+    for (uint32_t g = 0; g < G; g++) {
+      const uint32_t w = (g & 1) ? trans[trans_off[u] + g / 2] : 0u;
+      beg[g] = (uint32_t)ch->info.size() - base;
+      ch->info.insert(ch->info.end(), l->h_slot_info.begin() + woff[w], l->h_slot_info.begin() + woff[w + 1]);
+      end[g] = (uint32_t)ch->info.size() - base - 1;
+    }
+    ch->src.resize(ch->info.size(), 0xFFFFFFFFu);
+    ch->dst.resize(ch->info.size(), 0xFFFFFFFFu);
+    for (uint32_t g = 0; g < G; g++) {
+      // a word is entered by the silence before it and the word before that; a silence by the word before it and by itself
+      const uint32_t s0 = g ? end[g - 1] : 0xFFFFu, s1 = (g & 1) ? (g >= 2 ? end[g - 2] : 0xFFFFu) : end[g];
+      // a word end enters the next word and the silence after it; a silence's the next word and itself
+      const uint32_t d0 = g + 1 < G ? beg[g + 1] : 0xFFFFu, d1 = (g & 1) ? (g + 2 < G ? beg[g + 2] : 0xFFFFu) : beg[g];
+      ch->src[base + beg[g]] = s0 | s1 << 16;
+      if (end[g] > beg[g]) ch->src[base + beg[g] + 1] = s0 | s1 << 16;
+      ch->dst[base + end[g]] = d0 | d1 << 16;
+    }
+    ch->off[u + 1] = ch->info.size();
+  }
+}
+
+// One occupancy pass over the corpus on the search's scoring chunks: the free network (trans_off null) or the transcripts' chains.
+// Inside a chunk, consecutive utterances whose trellises fit m->fb_budget together (8 B per frame and position) run forward, backward and
+// -- want_items -- the occupancy items.  Leaves kappa F_u in c->out_cost and, with want_items, *n_items items in c->fb_item_* (frame
+// order, ascending mixture id) with c->fb_item_off[F + 1]; utterances whose gate (device, optional) is +inf give no items.
+static int occ_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
+                    const uint32_t* trans, const uint64_t* trans_off, bool want_items, const double* gate, uint64_t* n_items) {
+  const uint32_t U = c->n_utts;
+  const uint64_t F = c->n_frames, P = l->net.n_slots;
+  const bool chain = trans_off != nullptr;
+  *n_items = 0;
+  HIP_TRY(c->out_cost.ensure(U));
+  if (U == 0) return SR_OK;
+  Chains ch;
+  if (chain) build_chains(l, U, trans, trans_off, &ch);
+  // the mixture lists: the distinct mixtures (ascending) of the lexicon, or of each chain, and the positions carrying each
+  std::vector<uint64_t> tr_off(U + 1, 0);
+  std::vector<uint32_t> mix_off(U + 1, 0), slot_beg;
+  std::vector<uint16_t> mix, slot_pos;
+  std::vector<std::pair<uint16_t, uint16_t>> ps;
+  auto add_lists = [&](const uint32_t* info, uint64_t N) {
+    ps.clear();
+    for (uint64_t i = 0; i < N; i++) ps.push_back({(uint16_t)(info[i] & 0xFFFFu), (uint16_t)i});
+    std::sort(ps.begin(), ps.end());
+    for (size_t i = 0; i < ps.size(); i++) {
+      if (i == 0 || ps[i].first != ps[i - 1].first) {
+        mix.push_back(ps[i].first);
+        slot_beg.push_back((uint32_t)slot_pos.size());
+      }
+      slot_pos.push_back(ps[i].second);
+    }
+  };
+  uint64_t item_bound = 0;
+  if (!chain) add_lists(l->h_slot_info.data(), P);
+  for (uint32_t u = 0; u < U; u++) {
+    const uint64_t N = chain ? ch.off[u + 1] - ch.off[u] : P, T = c->frame_off[u + 1] - c->frame_off[u];
+    tr_off[u + 1] = tr_off[u] + N * T;
+    if (chain) {
+      add_lists(ch.info.data() + ch.off[u], N);
+      mix_off[u + 1] = (uint32_t)mix.size();
+    }
+    item_bound += T * (chain ? mix_off[u + 1] - mix_off[u] : mix.size());
+  }
+  slot_beg.push_back((uint32_t)slot_pos.size());
+  if (want_items && item_bound >= (1ull << 31)) return fail(SR_ELIMIT, "too many (frame, mixture) occupancies");
+  std::vector<Chunk> chunks;
+  int rc = prepare_chunks(m, c, &chunks);
+  if (rc) return rc;
+  // launch groups: consecutive utterances of a chunk within the trellis budget (occ_check: every utterance fits alone)
+  struct Group { uint32_t u0, u1, max_n; };
+  std::vector<std::vector<Group>> groups(chunks.size());
+  uint64_t ws = 1, max_gf = 1;
+  for (size_t ci = 0; ci < chunks.size(); ci++)
+    for (uint32_t u = chunks[ci].u0; u < chunks[ci].u1;) {
+      uint32_t v = u, max_n = 1;
+      while (v < chunks[ci].u1 && (v == u || 8 * (tr_off[v + 1] - tr_off[u]) <= m->fb_budget)) {
+        max_n = std::max<uint32_t>(max_n, chain ? (uint32_t)(ch.off[v + 1] - ch.off[v]) : (uint32_t)P);
+        v++;
+      }
+      groups[ci].push_back({u, v, max_n});
+      ws = std::max<uint64_t>(ws, tr_off[v] - tr_off[u]);
+      max_gf = std::max<uint64_t>(max_gf, c->frame_off[v] - c->frame_off[u]);
+      u = v;
+    }
+  HIP_TRY(c->fb_trellis_off.upload(tr_off.data(), U + 1));
+  HIP_TRY(c->fb_trellis.ensure(ws));
+  if (chain) {
+    HIP_TRY(c->mmi_chain_off.upload(ch.off.data(), U + 1));
+    HIP_TRY(c->mmi_info.upload(ch.info.data(), ch.info.size()));
+    HIP_TRY(c->mmi_src.upload(ch.src.data(), ch.src.size()));
+    HIP_TRY(c->mmi_dst.upload(ch.dst.data(), ch.dst.size()));
+  } else {
+    HIP_TRY(c->nf_ends.ensure(max_gf));
+  }
+  size_t scan_bytes = 0;
+  if (want_items) {
+    if (chain) HIP_TRY(c->fb_mix_off.upload(mix_off.data(), U + 1));
+    HIP_TRY(c->fb_mix.upload(mix.data(), mix.size()));
+    HIP_TRY(c->fb_slot_beg.upload(slot_beg.data(), slot_beg.size()));
+    HIP_TRY(c->fb_slot_pos.upload(slot_pos.data(), slot_pos.size()));
+    scan_bytes = fb_scan_temp_bytes(max_gf);
+    HIP_TRY(c->fb_scan_temp.ensure(scan_bytes));
+    HIP_TRY(c->fb_cnt.ensure(max_gf)); HIP_TRY(c->fb_scan.ensure(max_gf)); HIP_TRY(c->fb_base.ensure(1));
+    HIP_TRY(c->fb_item_off.ensure(F + 1));
+    HIP_TRY(c->fb_item_frame.ensure(item_bound)); HIP_TRY(c->fb_item_mix.ensure(item_bound)); HIP_TRY(c->fb_item_w.ensure(item_bound));
+  }
+  NetFbArgs na{};
+  na.net = l->net; na.ld = m->ld; na.frame_off = c->d_frame_off.p; na.scale = scale; na.word_penalty = p->word_penalty;
+  na.trellis = c->fb_trellis.p; na.out_cost = c->out_cost.p; na.ends = c->nf_ends.p;
+  ChainArgs ca{};
+  ca.ld = m->ld; ca.frame_off = c->d_frame_off.p; ca.scale = scale; ca.word_penalty = p->word_penalty;
+  ca.tdp_loop = l->net.tdp_loop; ca.tdp_forward = l->net.tdp_forward; ca.tdp_skip = l->net.tdp_skip;
+  ca.chain_off = c->mmi_chain_off.p; ca.info = c->mmi_info.p; ca.src = c->mmi_src.p; ca.dst = c->mmi_dst.p; ca.sil_len = ch.sil_len;
+  ca.trellis = c->fb_trellis.p; ca.trellis_off = c->fb_trellis_off.p; ca.out_cost = c->out_cost.p;
+  OccItemArgs ia{};
+  ia.frame_off = c->d_frame_off.p; ia.trellis = c->fb_trellis.p; ia.n_cols = (uint32_t)P; ia.n_mix = chain ? 0u : (uint32_t)mix.size();
+  if (chain) { ia.trellis_off = c->fb_trellis_off.p; ia.chain_off = c->mmi_chain_off.p; ia.mix_off = c->fb_mix_off.p; }
+  ia.mix = c->fb_mix.p; ia.slot_beg = c->fb_slot_beg.p; ia.slot_pos = c->fb_slot_pos.p; ia.gate = gate; ia.floor = posterior_floor;
+  ia.group_cnt = c->fb_cnt.p; ia.item_base = c->fb_base.p; ia.item_off = c->fb_item_off.p;
+  ia.item_frame = c->fb_item_frame.p; ia.item_mix = c->fb_item_mix.p; ia.item_w = c->fb_item_w.p;
+  size_t ci = 0;  // run_chunks searches the chunks in order
+  rc = run_chunks(m, chunks, [&](const Chunk& k, double* table) { return score_chunk(m, c, k.f0, k.f1, p->gmm_kernel, table); },
+      [&](const Chunk& k, const double* table, hipStream_t s) -> int {
+        if (want_items && ci == 0) HIP_TRY(hipMemsetAsync(c->fb_base.p, 0, sizeof(uint32_t), s));
+        for (const Group& g : groups[ci]) {
+          if (chain) {
+            ca.scores = table; ca.frame_base = k.f0; ca.utt_first = g.u0; ca.n_utts = g.u1 - g.u0; ca.max_positions = g.max_n;
+            HIP_TRY(launch_chain_forward(ca, s));
+            HIP_TRY(launch_chain_backward(ca, s));
+          } else {
+            na.scores = table; na.frame_base = k.f0; na.utt_first = g.u0; na.n_utts = g.u1 - g.u0; na.group_f0 = c->frame_off[g.u0];
+            HIP_TRY(launch_netfb_forward(na, s));
+            HIP_TRY(launch_netocc_backward(na, s));
+          }
+          if (want_items) {
+            ia.utt_first = g.u0; ia.n_utts = g.u1 - g.u0; ia.group_f0 = c->frame_off[g.u0];
+            HIP_TRY(launch_occ_items(ia, c->frame_off[g.u1] - c->frame_off[g.u0], c->fb_scan_temp.p, scan_bytes, c->fb_scan.p, s));
+          }
+        }
+        ci++;
+        return SR_OK;
+      });
+  if (rc) return rc;
+  if (want_items) {
+    uint32_t n = 0;
+    HIP_TRY(hipMemcpy(&n, c->fb_base.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *n_items = n;
+  }
+  if (m->profiling) {  // trellis traffic per (frame, position) as the network pass counts it: alpha out, alpha in + part out, part in
+    m->prof.frames += F;
+    m->prof.search_bytes += 32.0 * (double)tr_off[U];
+  }
+  return SR_OK;
+}
+
+int sr_net_occupancies_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
+                              uint32_t max_items, const uint32_t* trans, const uint64_t* trans_off, double* out_cost,
+                              uint16_t* out_count, uint16_t* out_state, double* out_weight) {
+  return guarded(__func__, [&]() -> int {
+  bool constrained = false;
+  int rc = occ_check(m, c, l, p, scale, posterior_floor, trans, trans_off, &constrained);
+  if (rc) return rc;
+  if (!out_cost) return fail(SR_EINVAL, "null argument");
+  const bool post = out_count || out_state || out_weight;
+  if (post && (!out_count || !out_state || !out_weight)) return fail(SR_EINVAL, "null output (pass out_count, out_state and out_weight, or none)");
+  if (post && (max_items == 0 || max_items > 65535)) return fail(SR_EINVAL, "max_items must be 1 .. 65535 (got %u)", max_items);
+  const uint64_t F = c->n_frames;
+  uint64_t n_items = 0;
+  if ((rc = occ_pass(m, c, l, p, scale, posterior_floor, trans, constrained ? trans_off : nullptr, post, nullptr, &n_items))) return rc;
+  if ((rc = netfb_costs(c, scale, out_cost))) return rc;
+  if (!post || F == 0) return SR_OK;
+  HIP_TRY(c->fb_count.ensure(F));
+  HIP_TRY(c->fb_state.ensure((size_t)F * max_items));
+  HIP_TRY(c->fb_weight.ensure((size_t)F * max_items));
+  HIP_TRY(launch_fb_top(c->fb_item_off.p, c->fb_item_mix.p, c->fb_item_w.p, F, max_items, c->fb_count.p, c->fb_state.p, c->fb_weight.p,
+                        m->s_gmm));
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  HIP_TRY(hipMemcpy(out_count, c->fb_count.p, sizeof(uint16_t) * F, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_state, c->fb_state.p, sizeof(uint16_t) * F * max_items, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_weight, c->fb_weight.p, sizeof(double) * F * max_items, hipMemcpyDeviceToHost));
+  return SR_OK;
+  });
+}
+
+int sr_mmi_statistics_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
+                             int max_approx, const uint32_t* trans, const uint64_t* trans_off, double* out_num_cost, double* out_den_cost,
+                             double* num_mean_acc, double* num_mean_w, double* num_var_acc, double* num_var_w, double* den_mean_acc,
+                             double* den_mean_w, double* den_var_acc, double* den_var_w) {
+  return guarded(__func__, [&]() -> int {
+  bool constrained = false;
+  int rc = occ_check(m, c, l, p, scale, posterior_floor, trans, trans_off, &constrained);
+  if (rc) return rc;
+  if (!constrained) return fail(SR_EINVAL, "null argument (MMI statistics need the transcripts)");
+  if (!out_num_cost || !out_den_cost || !num_mean_acc || !num_mean_w || !num_var_acc || !num_var_w || !den_mean_acc || !den_mean_w ||
+      !den_var_acc || !den_var_w)
+    return fail(SR_EINVAL, "null output");
+  const uint32_t U = c->n_utts;
+  c->acc_valid = false;
+  // numerator: the transcripts' chains.  Its costs stay on the device as the denominator's gate: an utterance without a path through
+  // its transcript (F_num = +inf) contributes to neither side.
+  uint64_t n_items = 0;
+  if ((rc = occ_pass(m, c, l, p, scale, posterior_floor, trans, trans_off, true, nullptr, &n_items))) return rc;
+  if ((rc = netfb_costs(c, scale, out_num_cost))) return rc;
+  HIP_TRY(c->mmi_num_cost.ensure(U));
+  if (U) HIP_TRY(hipMemcpy(c->mmi_num_cost.p, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToDevice));
+  if ((rc = accumulate_items(m, c, n_items, 0, max_approx, true, num_mean_acc, num_mean_w, num_var_acc, num_var_w))) return rc;
+  // denominator: the free network
+  if ((rc = occ_pass(m, c, l, p, scale, posterior_floor, nullptr, nullptr, true, c->mmi_num_cost.p, &n_items))) return rc;
+  if ((rc = netfb_costs(c, scale, out_den_cost))) return rc;
+  rc = accumulate_items(m, c, n_items, 0, max_approx, true, den_mean_acc, den_mean_w, den_var_acc, den_var_w);
+  c->acc_valid = false;  // (the handle holds one side only: nothing for sr_model_create_from_accumulated)
+  return rc;
+  });
+}
+
+int sr_model_create_from_mmi_statistics(sr_model* m, const double* num_mean_acc, const double* num_mean_w, const double* num_var_acc,
+                                        const double* num_var_w, const double* den_mean_acc, const double* den_mean_w,
+                                        const double* den_var_acc, const double* den_var_w, double E, double tau, double var_floor,
+                                        sr_model** out) {
+  return guarded(__func__, [&]() -> int {
+  if (!out) return fail(SR_EINVAL, "out is null");
+  *out = nullptr;
+  int rc = check_model(m);
+  if (rc) return rc;
+  if (!num_mean_acc || !num_mean_w || !num_var_acc || !num_var_w || !den_mean_acc || !den_mean_w || !den_var_acc || !den_var_w)
+    return fail(SR_EINVAL, "null statistics");
+  if (!(E > 0.0) || !std::isfinite(E)) return fail(SR_EINVAL, "E must be finite and > 0 (got %g)", E);
+  if (!(tau >= 0.0) || !std::isfinite(tau)) return fail(SR_EINVAL, "tau must be finite and >= 0 (got %g)", tau);
+  if (!(var_floor > 0.0) || !std::isfinite(var_floor)) return fail(SR_EINVAL, "var_floor must be finite and > 0 (got %g)", var_floor);
+  const uint64_t C = m->n_dens;
+  const uint32_t D = m->dim;
+  // untied: every density owns a mean row and a variance row
+  if (m->n_mean != C || m->n_var != C) return fail(SR_EINVAL, "the EBW update needs an untied model (%u mean and %u variance rows for %llu densities)", m->n_mean, m->n_var, (unsigned long long)C);
+  {
+    std::vector<uint8_t> seen_m(C, 0), seen_v(C, 0);
+    for (uint64_t d = 0; d < C; d++) {
+      if (seen_m[m->h_dens_mean[d]] || seen_v[m->h_dens_var[d]]) return fail(SR_EINVAL, "the EBW update needs an untied model (density %llu shares a row)", (unsigned long long)d);
+      seen_m[m->h_dens_mean[d]] = seen_v[m->h_dens_var[d]] = 1;
+    }
+  }
+  DevBuf<double> d_nma, d_nmw, d_nva, d_dma, d_dmw, d_dva, d_means, d_vars, d_ivars;
+  HIP_TRY(d_nma.upload(num_mean_acc, C * D)); HIP_TRY(d_nmw.upload(num_mean_w, C)); HIP_TRY(d_nva.upload(num_var_acc, C * D));
+  HIP_TRY(d_dma.upload(den_mean_acc, C * D)); HIP_TRY(d_dmw.upload(den_mean_w, C)); HIP_TRY(d_dva.upload(den_var_acc, C * D));
+  HIP_TRY(d_means.ensure(C * D)); HIP_TRY(d_vars.ensure(C * D)); HIP_TRY(d_ivars.ensure(C * D));
+  EbwArgs a{};
+  a.n_dens = C; a.dim = D; a.dens_mean = m->dens_mean.p; a.dens_var = m->dens_var.p; a.old_means = m->means.p; a.old_inv_vars = m->inv_vars.p;
+  a.num_mean_acc = d_nma.p; a.num_mean_w = d_nmw.p; a.num_var_acc = d_nva.p; a.den_mean_acc = d_dma.p; a.den_mean_w = d_dmw.p; a.den_var_acc = d_dva.p;
+  a.E = E; a.tau = tau; a.var_floor = var_floor; a.means = d_means.p; a.vars = d_vars.p; a.inv_vars = d_ivars.p;
+  HIP_TRY(launch_ebw_combine(a, m->s_gmm));
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  std::vector<double> means(C * D), vars(C * D), ivars(C * D), norm(C), logw(C);
+  if (C) {
+    HIP_TRY(hipMemcpy(means.data(), d_means.p, sizeof(double) * C * D, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(vars.data(), d_vars.p, sizeof(double) * C * D, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ivars.data(), d_ivars.p, sizeof(double) * C * D, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(logw.data(), m->logw.p, sizeof(double) * C, hipMemcpyDeviceToHost));  // the mixture weights stay
+  }
+  for (uint64_t d = 0; d < C; d++) {  // the host's log, in finalize_core's order (em_finalize.hip)
+    double acc = D * log(2 * M_PI);
+    for (uint32_t k = 0; k < D; k++) acc = acc + log(vars[d * D + k]);
+    norm[d] = acc / 2;
+  }
+  sr_model* nm = nullptr;
+  if ((rc = sr_model_create(m->device, D, m->n_states, m->h_dens_off.data(), means.data(), ivars.data(), norm.data(), logw.data(),
+                            m->max_approx ? 1 : 0, &nm)))
+    return rc;
+  if ((rc = sr_model_set_tying(nm, m->n_mean, m->n_var, m->h_dens_mean.data(), m->h_dens_var.data()))) {
+    sr_model_destroy(nm);
+    return rc;
+  }
+  *out = nm;
   return SR_OK;
   });
 }
