@@ -903,6 +903,35 @@ class LinearSearch {
       for (uint64_t i = off[s]; i < off[s + 1]; i++) results[s].push_back(TracebackItem{words[i], scores[i], times[i]});
   }
 
+  // recognize()'s items, bit for bit, and for each the maximum over its frames of the word's posterior in the search network
+  // summed without beams, every cost times `scale` (sr_recognize_bigram_confidence_corpus): confidences[s][i] belongs to results[s][i]
+  void recognize_with_confidence(Corpus const& corpus, double scale, std::vector<Traceback>& results,
+                                 std::vector<std::vector<double> >& confidences) {
+    const size_t n = corpus.get_corpus_size();
+    const uint64_t F = corpus.get_total_frame_count();
+    std::vector<uint32_t> words(F + n + 1), times(F + n + 1);
+    std::vector<float> scores(F + n + 1);
+    std::vector<double> conf(F + n + 1);
+    std::vector<uint64_t> off(n + 1);
+    sr_corpus* c = nullptr;
+    check(sr_corpus_upload(scorer_.handle(), corpus.features(), corpus.frame_offsets(), (uint32_t)n, &c));
+    sr_bigram_params p = sr_bigram_params();
+    p.acoustic_pruning = acoustic_pruning_;
+    p.lm_pruning = lm_pruning_;
+    p.gmm_kernel = scorer_.gmm_kernel;
+    const int rc = sr_recognize_bigram_confidence_corpus(scorer_.handle(), c, net_, &p, scale, words.data(), scores.data(), times.data(),
+                                                         off.data(), conf.data());
+    sr_corpus_destroy(c);
+    check(rc);
+    results.assign(n, Traceback());
+    confidences.assign(n, std::vector<double>());
+    for (size_t s = 0; s < n; s++)
+      for (uint64_t i = off[s]; i < off[s + 1]; i++) {
+        results[s].push_back(TracebackItem{words[i], scores[i], times[i]});
+        confidences[s].push_back(conf[i]);
+      }
+  }
+
  private:
   MixtureModel& scorer_;
   float acoustic_pruning_, lm_pruning_;

@@ -472,6 +472,44 @@ SR_API int sr_bigram_describe(const sr_bigram* b, char* out, size_t cap);
 SR_API int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr_bigram_params* p,
                                       uint32_t* out_word, float* out_score, uint32_t* out_time, uint64_t* out_off);
 
+/* ---- word posteriors and confidences for the bigram search: forward-backward over ITS network ------------------------------------
+ * The network sr_recognize_bigram_corpus searches, with every path summed instead of the best kept, no acoustic and no LM beam, every
+ * cost multiplied by scale = kappa > 0, in FP64 (lm and tdp widened from float; emission costs are the library's FP64 scores):
+ *   slots 0 .. W-1 are the words, slot h + W the silence copy entered after word h != silence (the silence word's states, the silence
+ *   penalties tdp[1]).  Before frame 1 there is one word end: the silence word, cost 0.  A word end of slot x has history x (a word),
+ *   h (the copy h + W) or silence (the silence word); the cost of a history is the log-sum of its word ends -- the decoder's merge
+ *   WITHOUT the positional cut of mergeSilenceToBigramNodes: every history is kept.  Word w != silence is entered from every history h
+ *   at hist_h + lm[w * W + h] (NaN and +inf: a forbidden transition), the copy h + W from the word end of word h alone and the silence
+ *   word from its own word end, both at no LM cost.  An entry moves to the first state at no penalty or to the second at the skip
+ *   penalty; a state moves to itself and the next two at tdp[isSilence][0..2]; the destination's mixture is emitted; a word end is the
+ *   last state plus tdp[isSilence][3].
+ *   F_u = -(1/kappa) log sum over the word ends after frame T_u of exp(-kappa cost) <= the score of the decoder's last item (up to its
+ *   float rounding);  T_u = 0: F_u = 0 and no frames.
+ *   p_t(w | X) = the posterior mass of word w's positions at frame t; for w = silence the silence word and all copies.  Sum over w = 1.
+ * Against the decoder: its merge keeps one hypothesis per history, so besides the cut it does not enter the copy h + W from word h's
+ * end at a frame where the copy's own end is the better of the two; this network does.  The decoder searches a subset of these paths.
+ * The word entry is evaluated in the linear domain as an FP64 matrix product with exp(-kappa lm).  Limits of that: SR_ELIMIT for a
+ * finite score with -kappa lm > 700, SR_EINVAL for a score of -inf; an LM score whose exp underflows counts as forbidden, and word w
+ * is entered at a frame only if some history h has kappa lm[w * W + h] + (hist_h - the frame's best history) below about 708 -- a
+ * word all of whose terms underflow is not entered at that frame, where the log-space network would enter it at that cost.
+ * Memory: the table and its transpose (16 bytes per LM entry, W padded to a multiple of 64: 116 MB at 2 667 words, 1 GiB at 8 192) are
+ * built on the device once per (sr_bigram, kappa), kept on the sr_bigram handle and NOT counted in SRGPU_FB_MB.  Counted in it, for
+ * the utterances processed together: 8 bytes per (frame, position) plus 24 W + 16 positions bytes per utterance; beside it 8 W bytes
+ * per frame of the group for the word posteriors.  An utterance that alone exceeds SRGPU_FB_MB: SR_ELIMIT.  Like the search itself,
+ * the calls use workspace of the sr_bigram and the corpus handle: one call at a time per handle.  Other errors as
+ * sr_word_posteriors_corpus.  No atomics and a fixed summation order: two identical calls return identical bits. */
+
+/* Outputs exactly as sr_word_posteriors_corpus: out_cost[n_utts] = F_u (required); items all or none. */
+SR_API int sr_bigram_word_posteriors_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, double scale,
+                                            double posterior_floor, uint32_t max_items, double* out_cost, uint16_t* out_count,
+                                            uint32_t* out_word, double* out_weight);
+/* Items bit for bit as sr_recognize_bigram_corpus with the same p (beams and layout flags included), and out_conf[i] = the maximum of
+ * p_t(word_i | X) over item i's 0-based frames time_{i-1} .. time_i - 1 (time_{-1} = 0), computed without a beam.  Silence items get a
+ * confidence like any other.  out_conf: capacity n_frames + n_utts like the items. */
+SR_API int sr_recognize_bigram_confidence_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr_bigram_params* p, double scale,
+                                                 uint32_t* out_word, float* out_score, uint32_t* out_time, uint64_t* out_off,
+                                                 double* out_conf);
+
 /* ---- streaming bigram-LM recognition: LinearSearch's own initialize / processFrame / getResult (:489-520) -------------------
  * The sr_stream_* interface for the bigram search: utterances fed as their frames arrive, many at once.  sr_bigram_stream_end
  * returns, bit for bit, the items sr_recognize_bigram_corpus returns for that utterance with the same p (any layout: they agree);

@@ -34,6 +34,7 @@ SYMBOLS = [
     "sr_net_occupancies_corpus", "sr_mmi_statistics_corpus", "sr_model_create_from_mmi_statistics",
     "sr_word_lattice_corpus", "sr_lattice_nbest",
     "sr_bigram_create", "sr_bigram_destroy", "sr_bigram_describe", "sr_recognize_bigram_corpus",
+    "sr_bigram_word_posteriors_corpus", "sr_recognize_bigram_confidence_corpus",
     "sr_stream_open", "sr_stream_begin", "sr_stream_push", "sr_stream_partial", "sr_stream_end", "sr_stream_destroy",
     "sr_bigram_stream_open", "sr_bigram_stream_begin", "sr_bigram_stream_push", "sr_bigram_stream_partial", "sr_bigram_stream_end",
     "sr_bigram_stream_destroy",
@@ -121,6 +122,8 @@ def lib():
         L.sr_bigram_destroy.argtypes = [vp]
         L.sr_bigram_describe.argtypes = [vp, C.c_char_p, C.c_size_t]
         L.sr_recognize_bigram_corpus.argtypes = [vp, vp, vp, C.POINTER(BigramParams), vp, vp, vp, vp]
+        L.sr_bigram_word_posteriors_corpus.argtypes = [vp, vp, vp, i32, dbl, dbl, u32, vp, vp, vp, vp]
+        L.sr_recognize_bigram_confidence_corpus.argtypes = [vp, vp, vp, C.POINTER(BigramParams), dbl, vp, vp, vp, vp, vp]
         L.sr_stream_open.argtypes = [vp, vp, C.POINTER(SearchParams), u32, u64, C.POINTER(vp)]
         L.sr_stream_begin.argtypes = [vp, C.POINTER(u32)]
         L.sr_stream_push.argtypes = [vp, u32, vp, vp, vp]
@@ -644,6 +647,34 @@ class Corpus:
         _check(lib().sr_recognize_bigram_corpus(self.model.h, self.h, bigram.h, C.byref(p), _ptr(ow), _ptr(osc), _ptr(ot), _ptr(off)))
         n = int(off[-1])
         return ow[:n], osc[:n], ot[:n], off
+
+    def bigram_word_posteriors(self, bigram, scale=1.0, kernel=GMM_PREFILTER, floor=0.0, max_items=8):
+        """Forward-backward over the bigram search network (sr_bigram_word_posteriors_corpus) -> (cost, count, word, weight) as
+        word_posteriors; the silence word's posterior includes its copies."""
+        F = max(self.n_frames, 1)
+        K = max(int(max_items), 1)
+        cost = np.zeros(max(self.n_utts, 1), dtype=np.float64)
+        count = np.zeros(F, dtype=np.uint16)
+        word = np.zeros((F, K), dtype=np.uint32)
+        weight = np.zeros((F, K), dtype=np.float64)
+        _check(lib().sr_bigram_word_posteriors_corpus(self.model.h, self.h, bigram.h, kernel, float(scale), float(floor), int(max_items),
+                                                      _ptr(cost), _ptr(count), _ptr(word), _ptr(weight)))
+        n = self.n_frames
+        return cost[: self.n_utts], count[:n], word[:n], weight[:n]
+
+    def recognize_bigram_confidence(self, bigram, scale=1.0, acoustic_pruning=FLT_MAX, lm_pruning=FLT_MAX, kernel=GMM_PREFILTER,
+                                    max_word_ends=0, dense_states=False, global_states=False):
+        """recognize_bigram()'s items with a confidence each (sr_recognize_bigram_confidence_corpus) -> (words u32[], scores f32[],
+        times u32[], off u64[n_utts+1], conf f64[]): conf = max posterior of the item's word over its frames."""
+        cap = max(self.n_frames + self.n_utts, 1)
+        ow, osc, ot = np.zeros(cap, np.uint32), np.zeros(cap, np.float32), np.zeros(cap, np.uint32)
+        conf = np.zeros(cap, np.float64)
+        off = np.zeros(self.n_utts + 1, np.uint64)
+        p = BigramParams(acoustic_pruning, lm_pruning, kernel, max_word_ends, (BIGRAM_DENSE_STATES if dense_states else 0) | (BIGRAM_GLOBAL_STATES if global_states else 0))
+        _check(lib().sr_recognize_bigram_confidence_corpus(self.model.h, self.h, bigram.h, C.byref(p), float(scale), _ptr(ow), _ptr(osc),
+                                                           _ptr(ot), _ptr(off), _ptr(conf)))
+        n = int(off[-1])
+        return ow[:n], osc[:n], ot[:n], off, conf[:n]
 
     def path_scores(self, states, kernel=GMM_PREFILTER):
         """Emission cost along a state path (one state per frame): Trainer::calc_am_score's summands."""

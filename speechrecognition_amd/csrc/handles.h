@@ -179,6 +179,10 @@ struct sr_corpus {
   DevBuf<double> nf_ends, mmi_num_cost;
   DevBuf<uint64_t> mmi_chain_off;
   DevBuf<uint32_t> mmi_info, mmi_src, mmi_dst;
+  // forward-backward over the bigram search network (viterbi_bigram_fb.hip; trellis, posteriors and items are the buffers above):
+  // the launch groups' vectors and utterance orders, the items' confidences
+  DevBuf<double> bgfb_vec, bgfb_prod, bgfb_wend, bgfb_m, bgfb_xb, bgfb_conf;
+  DevBuf<uint32_t> bgfb_order;
   // word lattices (viterbi_lattice.hip): the word-end tables of one launch group, the scan's workspace, the compacted arcs
   DevBuf<double> lat_fwd, lat_ends, lat_bend, lat_arc_fwd, lat_arc_bwd, lat_arc_cost;
   DevBuf<uint16_t> lat_first;
@@ -213,6 +217,11 @@ struct sr_bigram {
   DevBuf<uint64_t> book_off;
   DevBuf<uint32_t> gs_ws;               // global-states layout: the persistent workgroups' state images (viterbi_bigram.hip)
   DevBuf<unsigned long long> gs_active; // ... and the SRGPU_BIGRAM_STATS counter
+  // forward-backward over the search network (viterbi_bigram_fb.hip): exp(-kappa lm) and its transpose, built for fb_kappa and kept
+  // (0: not built).  lm_min: the smallest LM score into a word other than silence (NaN entries aside), from sr_bigram_create
+  double fb_kappa = 0.0;
+  float lm_min = 0.f;
+  DevBuf<double> fb_lk, fb_lkT;
 };
 
 // The slots of a stream set (sr_stream_*, sr_bigram_stream_*): slot i holds one open utterance, named by the id

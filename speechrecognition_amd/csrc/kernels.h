@@ -508,6 +508,45 @@ struct BigramStreamArgs {
 };
 hipError_t launch_bigram_stream(const BigramStreamArgs& s, uint32_t n_jobs, hipStream_t stream);
 
+// ---- forward-backward over the bigram search network (viterbi_bigram_fb.hip) -------------------------------------------------------
+// A launch group = utterances of one score chunk whose trellises fit the workspace together, walked frame by frame: `order` lists them
+// longest first, so the n_alive utterances with more than t frames are its first entries.  Per utterance of the group (index j in
+// `order`) the vectors vec / prod / wend [Kp] and m, Kp = bgfb_padded(W); vec has rows up to the next multiple of 64.
+struct BgFbArgs {
+  uint32_t n_words, silence, n_positions, Kp;
+  const uint32_t *slot_off, *pos_info, *pos_slot;  // the search net's tables (BigramArgs)
+  const float* lmT;             // [W x W] as BigramArgs (frame 0 is entered from the silence history alone)
+  float tdp[2][4];
+  double scale;                 // kappa > 0 multiplies every cost
+  const double* scores;         // [frames x ld], row 0 = frame frame_base
+  uint32_t ld;
+  uint64_t frame_base;
+  const uint64_t* frame_off;    // [n_utts_total+1]
+  const uint32_t* order;        // [n_group] the group's utterances, longest first
+  uint32_t n_group, n_alive, t; // utterances of the group / with more than t frames; the frame index of this launch
+  uint64_t group_f0;            // first frame of the group
+  double* trellis;              // [frames of the group][n_positions]: alpha, then gamma
+  double* vec;                  // forward a[h, u] = exp(m_u - hist_h); backward b[w, u] = exp(m_u - entry cost of word w)
+  double* prod;                 // the product's result X[w, u] / Y[h, u]
+  double* wend;                 // forward: the word-end cost of word h itself; backward: the entry cost of its copy (silence: of itself)
+  double* m;                    // [n_group] the offset of vec
+  double* xb;                   // [2][n_group][n_positions] kappa e_t + beta_t of the last two frames
+  double* out_cost;             // [n_utts_total] kappa F_u
+  double* post;                 // [frames of the group][W] word posteriors
+};
+inline uint32_t bgfb_padded(uint32_t n_words) { return (n_words + 63u) & ~63u; }
+// lk[w][h] = exp(-kappa lm[w, h]) (0: NaN, +inf, the silence row, padding) and its transpose, both [Kp x Kp]
+hipError_t launch_bgfb_table(const float* lmT, uint32_t W, uint32_t Kp, uint32_t silence, double kappa, double* lk, double* lkT,
+                             hipStream_t stream);
+hipError_t launch_bgfb_forward(const BgFbArgs& a, hipStream_t stream);   // frame a.t of the first a.n_alive utterances
+hipError_t launch_bgfb_backward(const BgFbArgs& a, hipStream_t stream);
+// out[n][m] = sum_k table[m][k] v[n][k], n < n_alive (v_mfma_f64_16x16x4_f64; fixed summation order)
+hipError_t launch_bgfb_product(const double* table, const double* v, double* out, uint32_t Kp, uint32_t n_alive, hipStream_t stream);
+hipError_t launch_bgfb_words(const BgFbArgs& a, uint64_t n_frames, hipStream_t stream);
+// per item of the search's result (BigramArgs' out_* layout) the max of p_t(word) over its frames, at out_conf[frame_off[u] + u + i]
+hipError_t launch_bgfb_conf(const BgFbArgs& a, uint32_t n_utts, const uint32_t* it_word, const uint32_t* it_time,
+                            const uint32_t* it_count, double* out_conf, hipStream_t stream);
+
 // out[f] = scores[(f - frame_base) * ld + states[f]] for f in [f0, f1)  (Trainer::calc_am_score, Training.cpp:605)
 hipError_t launch_path_scores(const double* scores, uint32_t ld, uint64_t frame_base, uint64_t f0, uint64_t f1,
                               const uint16_t* states, double* out, hipStream_t stream);

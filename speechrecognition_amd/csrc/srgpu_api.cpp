@@ -1295,6 +1295,9 @@ int sr_bigram_create(sr_model* m, uint32_t n_words, const uint32_t* word_off, co
       (e = b->pos_info.upload(pos_info.data(), pos_info.size())) != hipSuccess ||
       (e = b->pos_slot.upload(pos_slot.data(), pos_slot.size())) != hipSuccess)
     return fail(SR_EHIP, "bigram upload: %s", hipGetErrorString(e));
+  b->lm_min = std::numeric_limits<float>::infinity();  // (a NaN fails the comparison)
+  for (uint32_t w = 0; w < W; w++)
+    for (uint32_t h = 0; h < W && w != silence_word; h++) b->lm_min = std::min(b->lm_min, lm[(size_t)w * W + h]);
   BigramArgs& net = b->net;
   net.slot_off = b->slot_off.p; net.slot_mix = b->slot_mix.p; net.mixtures = b->mixtures.p; net.pos_info = b->pos_info.p;
   net.pos_slot = b->pos_slot.p; net.lmT = b->lmT.p; net.lm_rowmin = b->lm_rowmin.p; net.lm_rowmax = b->lm_rowmax.p;
@@ -1312,17 +1315,31 @@ int sr_bigram_destroy(sr_bigram* b) {
   });
 }
 
-int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr_bigram_params* p, uint32_t* out_word,
-                               float* out_score, uint32_t* out_time, uint64_t* out_off) {
-  return guarded(__func__, [&]() -> int {
+// The bigram search of a corpus (sr_recognize_bigram_corpus).  before(chunks) runs once the chunks are known; after(chunk, table,
+// stream) is enqueued behind each chunk's search on the same score table (sr_recognize_bigram_confidence_corpus: the forward-backward).
+extern "C++" {
+template <class Before, class After>
+static int bigram_recognize_pass(sr_model* m, sr_corpus* c, sr_bigram* b, const sr_bigram_params* p, uint32_t* out_word, float* out_score,
+                                 uint32_t* out_time, uint64_t* out_off, Before before, After after) {
   int rc = check_corpus(m, c);
   if (rc) return rc;
   if (!b || b->model != m) return fail(SR_EINVAL, "bigram search net does not belong to this model");
   if (!p || !out_off || ((!out_word || !out_score || !out_time) && c->n_frames)) return fail(SR_EINVAL, "null argument");
   const uint32_t U = c->n_utts, W = b->net.n_words;
   const uint64_t F = c->n_frames;
+  if (p->flags & ~(SR_BIGRAM_DENSE_STATES | SR_BIGRAM_GLOBAL_STATES)) return fail(SR_EINVAL, "unknown sr_bigram_params.flags 0x%x", (unsigned)p->flags);
+  if ((p->flags & SR_BIGRAM_DENSE_STATES) && (p->flags & SR_BIGRAM_GLOBAL_STATES))
+    return fail(SR_EINVAL, "SR_BIGRAM_DENSE_STATES and SR_BIGRAM_GLOBAL_STATES exclude each other");
+  BigramArgs ba = b->net;
+  ba.ld = m->ld;
+  ba.dense_states = (p->flags & SR_BIGRAM_DENSE_STATES) ? 1u : 0u;
+  ba.global_states = (p->flags & SR_BIGRAM_GLOBAL_STATES) ? 1u : 0u;
+  const BigramLayout layout = bigram_layout(ba);
+  if (layout == BigramLayout::kNone)
+    return fail(SR_ELIMIT, "this lexicon's dense LDS image would take %zu bytes > 160 KiB (SR_BIGRAM_DENSE_STATES)", bigram_lds_bytes(W, ba.n_positions));
   std::vector<Chunk> chunks;
   if ((rc = prepare_chunks(m, c, &chunks))) return rc;
+  if ((rc = before(chunks))) return rc;  // (behind every argument check: the hook may build and keep tables)
   // traceback book: 2 start entries + (word ends kept per frame <= W) * T per utterance
   const uint64_t per_frame = p->max_word_ends ? std::min<uint64_t>(p->max_word_ends, W) : W;
   std::vector<uint64_t> book_off(U + 1, 0);
@@ -1340,17 +1357,8 @@ int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr
   HIP_TRY(b->out_count.ensure(U));
   HIP_TRY(b->out_flags.ensure(U));
 
-  BigramArgs ba = b->net;
-  ba.ld = m->ld; ba.frame_off = c->d_frame_off.p; ba.utt_order = c->utt_order.p;
+  ba.frame_off = c->d_frame_off.p; ba.utt_order = c->utt_order.p;
   ba.ac_pruning = p->acoustic_pruning; ba.lm_pruning = p->lm_pruning;
-  if (p->flags & ~(SR_BIGRAM_DENSE_STATES | SR_BIGRAM_GLOBAL_STATES)) return fail(SR_EINVAL, "unknown sr_bigram_params.flags 0x%x", (unsigned)p->flags);
-  if ((p->flags & SR_BIGRAM_DENSE_STATES) && (p->flags & SR_BIGRAM_GLOBAL_STATES))
-    return fail(SR_EINVAL, "SR_BIGRAM_DENSE_STATES and SR_BIGRAM_GLOBAL_STATES exclude each other");
-  ba.dense_states = (p->flags & SR_BIGRAM_DENSE_STATES) ? 1u : 0u;
-  ba.global_states = (p->flags & SR_BIGRAM_GLOBAL_STATES) ? 1u : 0u;
-  const BigramLayout layout = bigram_layout(ba);
-  if (layout == BigramLayout::kNone)
-    return fail(SR_ELIMIT, "this lexicon's dense LDS image would take %zu bytes > 160 KiB (SR_BIGRAM_DENSE_STATES)", bigram_lds_bytes(W, ba.n_positions));
   if (layout == BigramLayout::kGlobal) {
     // a bounded, persistent grid (two workgroups per CU at most, each looping over its utterances): the state images take
     // grid x gs_ws_words x 4 bytes whatever the corpus size -- and at most a quarter of the free device memory
@@ -1384,7 +1392,7 @@ int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr
         HIP_TRY(launch_bigram(ba, s));  // (invalid value: a layout without the workspace it needs -- a bug here, not the caller's)
         // SURVEY 8(d)'s decoder model, 8 S + 4 P bytes per frame, with P = the bigram search's positions (words + their silence copies)
         if (m->profiling) m->prof.search_bytes += (8.0 * m->n_states + 4.0 * ba.n_positions) * (double)(ch.f1 - ch.f0);
-        return SR_OK;
+        return after(ch, table, s);
       });
   if (rc) return rc;
 
@@ -1414,6 +1422,14 @@ int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr
   }
   if (m->profiling) m->prof.frames += F;
   return SR_OK;
+}
+}  // extern "C++"
+
+int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr_bigram_params* p, uint32_t* out_word,
+                               float* out_score, uint32_t* out_time, uint64_t* out_off) {
+  return guarded(__func__, [&]() -> int {
+  return bigram_recognize_pass(m, c, b, p, out_word, out_score, out_time, out_off, [](const std::vector<Chunk>&) { return SR_OK; },
+                               [](const Chunk&, const double*, hipStream_t) { return SR_OK; });
   });
 }
 
@@ -2114,6 +2130,202 @@ int sr_recognize_confidence_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, con
       const uint64_t d = c->frame_off[u] + (i - out_word_off[u]);
       out_conf[i] = conf[d]; out_first[i] = first[d]; out_last[i] = last[d];
     }
+  return SR_OK;
+  });
+}
+
+// ---- forward-backward over the bigram search network (viterbi_bigram_fb.hip) -----------------------------------------------------
+// bytes of one group's workspace beside the trellis, per utterance: vec, prod, wend (Kp each), the two x rows, m
+static uint64_t bgfb_utt_bytes(const sr_bigram* b) { return 24ull * bgfb_padded(b->net.n_words) + 16ull * b->net.n_positions + 8; }
+
+static int bgfb_check(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, double posterior_floor) {
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  if (!b || b->model != m) return fail(SR_EINVAL, "bigram search net does not belong to this model");
+  if (!(scale > 0.0) || !std::isfinite(scale)) return fail(SR_EINVAL, "scale must be finite and > 0 (got %g)", scale);
+  if (!(posterior_floor >= 0.0)) return fail(SR_EINVAL, "posterior_floor must be >= 0 (got %g)", posterior_floor);
+  if (b->lm_min == -std::numeric_limits<float>::infinity()) return fail(SR_EINVAL, "the language model has a score of -inf");
+  if (-scale * (double)b->lm_min > 700.0)
+    return fail(SR_ELIMIT, "scale %g x LM score %g: exp(%g) is not representable", scale, (double)b->lm_min, -scale * (double)b->lm_min);
+  const uint64_t P = b->net.n_positions;
+  for (uint32_t u = 0; u < c->n_utts; u++) {
+    const uint64_t T = c->frame_off[u + 1] - c->frame_off[u];
+    if (8 * P * T + bgfb_utt_bytes(b) > m->fb_budget)
+      return fail(SR_ELIMIT, "utterance %u: trellis of %llu bytes exceeds the forward-backward workspace of %llu (SRGPU_FB_MB)", u,
+                  (unsigned long long)(8 * P * T + bgfb_utt_bytes(b)), (unsigned long long)m->fb_budget);
+  }
+  return SR_OK;
+}
+
+// The launch groups of a pass, cut like NetFbPass' with the per-utterance vectors counted in, each with its utterances ordered longest
+// first.  run() enqueues a chunk's groups: per frame the step and the product, forward then backward, the word posteriors, per_group.
+extern "C++" {
+struct BgFbPass {
+  struct Group { uint32_t u0, u1, t_max; };
+  std::vector<std::vector<Group>> groups;  // per chunk
+  std::vector<uint32_t> order;             // [U] each group's range, longest first
+  BgFbArgs a{};
+  const double *lk = nullptr, *lkT = nullptr;
+  const uint32_t* d_order = nullptr;       // `order` on the device
+  size_t ci = 0;
+
+  int setup(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, const std::vector<Chunk>& chunks) {
+    const uint64_t P = b->net.n_positions, per_utt = bgfb_utt_bytes(b);
+    const uint32_t W = b->net.n_words, Kp = bgfb_padded(W), U = c->n_utts;
+    auto len = [&](uint32_t u) { return c->frame_off[u + 1] - c->frame_off[u]; };
+    uint64_t max_gf = 1;
+    uint32_t max_gu = 1;
+    groups.assign(chunks.size(), {});
+    order.resize(U);
+    for (uint32_t u = 0; u < U; u++) order[u] = u;
+    for (size_t i = 0; i < chunks.size(); i++)
+      for (uint32_t u = chunks[i].u0; u < chunks[i].u1;) {
+        uint32_t v = u + 1;
+        while (v < chunks[i].u1 && 8 * P * (c->frame_off[v + 1] - c->frame_off[u]) + (v + 1 - u) * per_utt <= m->fb_budget) v++;
+        std::stable_sort(order.begin() + u, order.begin() + v, [&](uint32_t x, uint32_t y) { return len(x) > len(y); });
+        groups[i].push_back({u, v, (uint32_t)len(order[u])});
+        max_gf = std::max<uint64_t>(max_gf, c->frame_off[v] - c->frame_off[u]);
+        max_gu = std::max(max_gu, v - u);
+        u = v;
+      }
+    // exp(-kappa lm) and its transpose: built once per (net, kappa)
+    if (b->fb_kappa != scale || !b->fb_lk.p) {
+      b->fb_kappa = 0.0;
+      HIP_TRY(b->fb_lk.ensure((size_t)Kp * Kp));
+      HIP_TRY(b->fb_lkT.ensure((size_t)Kp * Kp));
+      HIP_TRY(launch_bgfb_table(b->lmT.p, W, Kp, b->net.silence, scale, b->fb_lk.p, b->fb_lkT.p, m->s_search));
+      HIP_TRY(hipStreamSynchronize(m->s_search));
+      b->fb_kappa = scale;
+    }
+    lk = b->fb_lk.p; lkT = b->fb_lkT.p;
+    const size_t rows = ((size_t)max_gu + 63) & ~(size_t)63;  // the product reads whole 16-column tiles of vec
+    HIP_TRY(c->fb_trellis.ensure(max_gf * P));
+    HIP_TRY(c->nf_post.ensure(max_gf * W));
+    HIP_TRY(c->out_cost.ensure(U));
+    HIP_TRY(c->bgfb_vec.ensure(rows * Kp));
+    HIP_TRY(c->bgfb_prod.ensure(rows * Kp));
+    HIP_TRY(c->bgfb_wend.ensure(rows * Kp));
+    HIP_TRY(c->bgfb_m.ensure(rows));
+    HIP_TRY(c->bgfb_xb.ensure(2 * (size_t)max_gu * P));
+    HIP_TRY(c->bgfb_order.upload(order.data(), order.size()));
+    d_order = c->bgfb_order.p;
+    HIP_TRY(hipMemset(c->bgfb_vec.p, 0, rows * Kp * sizeof(double)));  // (the padding columns h >= W stay 0 from here on)
+    if (U) HIP_TRY(hipMemset(c->out_cost.p, 0, sizeof(double) * U));  // T_u = 0: F_u = 0, the start hypothesis is a word end
+    HIP_TRY(hipDeviceSynchronize());
+    a.n_words = W; a.silence = b->net.silence; a.n_positions = (uint32_t)P; a.Kp = Kp;
+    a.slot_off = b->slot_off.p; a.pos_info = b->pos_info.p; a.pos_slot = b->pos_slot.p; a.lmT = b->lmT.p;
+    memcpy(a.tdp, b->net.tdp, sizeof(a.tdp));
+    a.scale = scale; a.ld = m->ld; a.frame_off = c->d_frame_off.p;
+    a.trellis = c->fb_trellis.p; a.vec = c->bgfb_vec.p; a.prod = c->bgfb_prod.p; a.wend = c->bgfb_wend.p; a.m = c->bgfb_m.p; a.xb = c->bgfb_xb.p;
+    a.out_cost = c->out_cost.p; a.post = c->nf_post.p;
+    // trellis traffic per (frame, position) as NetFbPass; the product reads the table once per frame step and direction
+    if (m->profiling) m->prof.search_bytes += 32.0 * (double)P * (double)c->n_frames;
+    return SR_OK;
+  }
+  template <class PerGroup>
+  int run(sr_corpus* c, const Chunk& ch, const double* table, hipStream_t s, PerGroup per_group) {
+    for (const Group& g : groups[ci]) {
+      a.scores = table; a.frame_base = ch.f0; a.group_f0 = c->frame_off[g.u0];
+      a.order = d_order + g.u0; a.n_group = g.u1 - g.u0;
+      auto alive = [&](uint32_t t) {  // utterances of the group with more than t frames: a prefix of its order
+        uint32_t n = 0;
+        while (n < a.n_group && c->frame_off[order[g.u0 + n] + 1] - c->frame_off[order[g.u0 + n]] > t) n++;
+        return n;
+      };
+      for (uint32_t t = 0; t < g.t_max; t++) {
+        a.t = t; a.n_alive = alive(t);
+        HIP_TRY(launch_bgfb_forward(a, s));
+        const uint32_t next = alive(t + 1);  // only those that go on need their entries
+        HIP_TRY(launch_bgfb_product(lk, a.vec, a.prod, a.Kp, next, s));
+      }
+      for (uint32_t t = g.t_max; t-- > 0;) {
+        a.t = t; a.n_alive = alive(t);
+        HIP_TRY(launch_bgfb_backward(a, s));
+        if (t) HIP_TRY(launch_bgfb_product(lkT, a.vec, a.prod, a.Kp, a.n_alive, s));
+      }
+      const uint64_t n = c->frame_off[g.u1] - c->frame_off[g.u0];
+      HIP_TRY(launch_bgfb_words(a, n, s));
+      int rc = per_group(a, n);
+      if (rc) return rc;
+    }
+    ci++;
+    return SR_OK;
+  }
+};
+}  // extern "C++"
+
+// the top items of a group's frames through netfb_top_kernel (it reads the word count, the posteriors and the group's first frame)
+static int bgfb_top(const BgFbArgs& a, uint64_t n, uint32_t max_items, double floor, sr_corpus* c, hipStream_t s) {
+  NetFbArgs t{};
+  t.net.n_words = a.n_words; t.post = a.post; t.group_f0 = a.group_f0;
+  HIP_TRY(launch_netfb_top(t, n, max_items, floor, c->nf_count.p, c->nf_word.p, c->nf_weight.p, s));
+  return SR_OK;
+}
+
+int sr_bigram_word_posteriors_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, double scale, double posterior_floor,
+                                     uint32_t max_items, double* out_cost, uint16_t* out_count, uint32_t* out_word, double* out_weight) {
+  return guarded(__func__, [&]() -> int {
+  int rc = bgfb_check(m, c, b, scale, posterior_floor);
+  if (rc) return rc;
+  if (!out_cost) return fail(SR_EINVAL, "null argument");
+  const bool post = out_count || out_word || out_weight;
+  if (post && (!out_count || !out_word || !out_weight)) return fail(SR_EINVAL, "null output (pass out_count, out_word and out_weight, or none)");
+  if (post && (max_items == 0 || max_items > 65535)) return fail(SR_EINVAL, "max_items must be 1 .. 65535 (got %u)", max_items);
+  const uint64_t F = c->n_frames;
+  std::vector<Chunk> chunks;
+  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
+  BgFbPass fp;
+  if ((rc = fp.setup(m, c, b, scale, chunks))) return rc;
+  if (post) {
+    HIP_TRY(c->nf_count.ensure(F));
+    HIP_TRY(c->nf_word.ensure((size_t)F * max_items));
+    HIP_TRY(c->nf_weight.ensure((size_t)F * max_items));
+  }
+  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, gmm_kernel, table); },
+      [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
+        return fp.run(c, ch, table, s, [&](const BgFbArgs& a, uint64_t n) -> int {
+          return post ? bgfb_top(a, n, max_items, posterior_floor, c, s) : SR_OK;
+        });
+      });
+  if (rc) return rc;
+  if (m->profiling) m->prof.frames += F;
+  if ((rc = netfb_costs(c, scale, out_cost))) return rc;
+  if (!post || F == 0) return SR_OK;
+  HIP_TRY(hipMemcpy(out_count, c->nf_count.p, sizeof(uint16_t) * F, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_word, c->nf_word.p, sizeof(uint32_t) * F * max_items, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_weight, c->nf_weight.p, sizeof(double) * F * max_items, hipMemcpyDeviceToHost));
+  return SR_OK;
+  });
+}
+
+int sr_recognize_bigram_confidence_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr_bigram_params* p, double scale,
+                                          uint32_t* out_word, float* out_score, uint32_t* out_time, uint64_t* out_off, double* out_conf) {
+  return guarded(__func__, [&]() -> int {
+  int rc = bgfb_check(m, c, b, scale, 0.0);
+  if (rc) return rc;
+  if (!out_conf && c->n_frames) return fail(SR_EINVAL, "null argument");
+  const uint64_t F = c->n_frames;
+  const uint32_t U = c->n_utts;
+  BgFbPass fp;
+  rc = bigram_recognize_pass(m, c, b, p, out_word, out_score, out_time, out_off,
+      [&](const std::vector<Chunk>& chunks) -> int {
+        int r = fp.setup(m, c, b, scale, chunks);
+        if (r) return r;
+        HIP_TRY(c->bgfb_conf.ensure(F + U));
+        return SR_OK;
+      },
+      [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
+        return fp.run(c, ch, table, s, [&](const BgFbArgs& a, uint64_t) -> int {
+          HIP_TRY(launch_bgfb_conf(a, a.n_group, b->out_word.p, b->out_time.p, b->out_count.p, c->bgfb_conf.p, s));
+          return SR_OK;
+        });
+      });
+  if (rc) return rc;
+  // the device holds item i of utterance u at frame_off[u] + u + i, like the search's items
+  std::vector<double> conf(F + U);
+  if (U) HIP_TRY(hipMemcpy(conf.data(), c->bgfb_conf.p, sizeof(double) * (F + U), hipMemcpyDeviceToHost));
+  for (uint32_t u = 0; u < U; u++)
+    for (uint64_t i = out_off[u]; i < out_off[u + 1]; i++) out_conf[i] = conf[c->frame_off[u] + u + (i - out_off[u])];
   return SR_OK;
   });
 }
