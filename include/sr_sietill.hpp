@@ -867,7 +867,8 @@ class LinearSearch {
   LinearSearch(MixtureModel& scorer, std::vector<std::vector<uint16_t> > const& linear_lexicon, uint32_t silence,
                std::vector<float> const& lm, const float tdp[2][4], float acoustic_pruning = std::numeric_limits<float>::max(),
                float lm_pruning = std::numeric_limits<float>::max())
-      : scorer_(scorer), acoustic_pruning_(acoustic_pruning), lm_pruning_(lm_pruning) {
+      : scorer_(scorer), acoustic_pruning_(acoustic_pruning), lm_pruning_(lm_pruning), n_words_((uint32_t)linear_lexicon.size()),
+        silence_(silence), lm_(lm) {
     std::vector<uint32_t> word_off(1, 0);
     std::vector<uint16_t> mixtures;
     for (size_t w = 0; w < linear_lexicon.size(); w++) {
@@ -932,9 +933,58 @@ class LinearSearch {
       }
   }
 
+  struct Hypothesis {
+    std::vector<uint32_t> words;  // silence removed
+    double cost;                  // of the string's cheapest lattice path
+  };
+  // Per segment the n_best cheapest distinct word strings among the paths of its word lattice over the search network without beams
+  // (sr_bigram_word_lattice_corpus with this lattice_beam, then sr_bigram_lattice_nbest), cheapest first.  rescoring_lm (W x W, the
+  // constructor's layout; null: the search's own table) and lm_scale price the word entries: another table is second-pass LM
+  // rescoring of the lattice.  With the own table and lm_scale = 1 the first entry is the network's best path.
+  std::vector<std::vector<Hypothesis> > recognize_nbest(Corpus const& corpus, uint32_t n_best,
+                                                        double lattice_beam = std::numeric_limits<double>::infinity(),
+                                                        std::vector<float> const* rescoring_lm = nullptr, double lm_scale = 1.0) {
+    const size_t n = corpus.get_corpus_size();
+    if (rescoring_lm && rescoring_lm->size() != lm_.size()) throw std::runtime_error("LinearSearch: rescoring lm must be W x W");
+    std::vector<float> const& lm = rescoring_lm ? *rescoring_lm : lm_;
+    sr_corpus* c = nullptr;
+    check(sr_corpus_upload(scorer_.handle(), corpus.features(), corpus.frame_offsets(), (uint32_t)n, &c));
+    std::vector<uint64_t> off(n + 1);
+    std::vector<double> best(n + 1), fwd, bwd, am;
+    std::vector<uint32_t> word, hist, pred, first, last;
+    int rc = sr_bigram_word_lattice_corpus(scorer_.handle(), c, net_, scorer_.gmm_kernel, lattice_beam, 0, off.data(), best.data(), nullptr,
+                                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (rc == SR_OK) {
+      const uint64_t cap = off[n] + 1;
+      word.resize(cap); hist.resize(cap); pred.resize(cap); first.resize(cap); last.resize(cap);
+      fwd.resize(cap); bwd.resize(cap); am.resize(cap);
+      rc = sr_bigram_word_lattice_corpus(scorer_.handle(), c, net_, scorer_.gmm_kernel, lattice_beam, cap, off.data(), best.data(),
+                                         word.data(), hist.data(), pred.data(), first.data(), last.data(), fwd.data(), bwd.data(),
+                                         am.data());
+    }
+    sr_corpus_destroy(c);
+    check(rc);
+    std::vector<std::vector<Hypothesis> > out(n);
+    for (size_t s = 0; s < n; s++) {
+      const uint32_t T = (uint32_t)(corpus.frame_offsets()[s + 1] - corpus.frame_offsets()[s]);
+      const uint64_t a = off[s], na = off[s + 1] - off[s];
+      std::vector<uint32_t> words((size_t)n_best * (T ? T : 1));
+      std::vector<uint64_t> hoff(n_best + 1);
+      std::vector<double> cost(n_best);
+      uint32_t count = 0;
+      check(sr_bigram_lattice_nbest(T, na, word.data() + a, hist.data() + a, first.data() + a, last.data() + a, am.data() + a, n_words_,
+                                    silence_, lm.data(), lm_scale, n_best, words.data(), words.size(), hoff.data(), cost.data(), &count));
+      for (uint32_t k = 0; k < count; k++)
+        out[s].push_back(Hypothesis{std::vector<uint32_t>(words.begin() + hoff[k], words.begin() + hoff[k + 1]), cost[k]});
+    }
+    return out;
+  }
+
  private:
   MixtureModel& scorer_;
   float acoustic_pruning_, lm_pruning_;
+  uint32_t n_words_, silence_;
+  std::vector<float> lm_;
   sr_bigram* net_ = nullptr;
 };
 

@@ -510,6 +510,69 @@ SR_API int sr_recognize_bigram_confidence_corpus(sr_model* m, sr_corpus* c, sr_b
                                                  uint32_t* out_word, float* out_score, uint32_t* out_time, uint64_t* out_off,
                                                  double* out_conf);
 
+/* ---- word lattices and N-best lists for the bigram search: ITS network in the min semiring -----------------------------------------
+ * The network of the block above (slots 0 .. W-1 the words, slot h + W the silence copy after word h, the start's word end = the
+ * silence word at cost 0, the merge WITHOUT the positional cut: every history is kept, no beams), evaluated in the MIN semiring, in
+ * FP64 and without a scale (kappa = 1); lm and tdp widened from float, emission costs the library's FP64 scores.  The order of
+ * additions is the specification: a position's cost is min(candidates) + emission; an in-word candidate is prev + penalty; a word
+ * entry is hist_h + (double) lm[w * W + h]; an entry to the second state adds the skip penalty to the entry; a word end is the last
+ * state + the exit penalty.  EQUAL candidates are resolved in a fixed order and the first stays: in-word from the same position, then
+ * one back, then two back, then the entry; among equal entry terms the smallest h.
+ * For an utterance of T frames: WE_t(x) = the cost of slot x's word end after frame t; H_t(h) = the history cost, the min over the
+ * word ends with history h after frame t (H_{-1}: silence 0, everything else +inf); best = min over x of WE_{T-1}(x).
+ * An ARC per (slot x, frame t) with WE_t(x) finite:
+ *   word   x for a word slot, the silence word for a copy;
+ *   hist   the history its end contributes to: x for a word, h for the copy h + W, silence for the silence word;
+ *   last   t;  first = the frame at which the cheapest path to this word end entered the slot;
+ *   pred   the history it was entered from: the arg-min h of the entry for a word, h for the copy h + W, silence for the silence word;
+ *   fwd    WE_t(x);
+ *   bwd    the cheapest continuation from this word end to any word end after frame T - 1 (0 at t = T - 1); unlike the zerogram
+ *          lattice's it depends on the slot (the LM and the own copy);
+ *   am     (fwd - c_in) - lmc, c_in = the cost the entry started from (H_{first-1}(pred) for a word, WE_{first-1}(word h) for the copy
+ *          h + W, WE_{first-1}(silence) for the silence word), lmc = (double) lm[word * W + pred] for a word other than silence, else
+ *          0: the acoustic cost of the arc -- transition penalties, emissions and exit of frames first .. last, independent of the
+ *          LM and of the predecessor.
+ * fwd + bwd is the cost of the cheapest complete path on which slot x ends at t.  The LATTICE of an utterance holds the arcs with
+ * fwd + bwd <= best + lattice_beam, ordered by last, then slot (+inf: every arc on some complete path).  A lattice path is a chain of
+ * arcs with first_0 = 0, first_{k+1} = last_k + 1, last_K = T - 1 that follows the network's entry rules: a copy arc with hist = h
+ * directly follows an arc of word h; a silence-word arc follows the start or a silence-word arc; a word arc follows anything and
+ * pays lm[word * W + hist of the arc before] (silence at the start).  Its cost is the left-to-right sum of (lm term + am).
+ * APPROXIMATION as for the zerogram lattice: one arc per (slot, end frame), carrying the best start only.  The lattice's paths are a
+ * subset of the network's: the first entry of an N-best list is exact (best, up to the rounding of am and of the sum), the k-th is an
+ * upper bound of the network's k-th best cost.
+ * LM scores: -inf is refused (SR_EINVAL); NaN and +inf mean a forbidden transition; negative finite scores are allowed (nothing is
+ * exponentiated here: the -kappa lm > 700 limit above does not apply).  Limits: those of sr_bigram_create; utterances of at most
+ * 65535 frames (SR_ELIMIT).  The word entry, W x W terms per frame and utterance, is a min-plus kernel over the float table; the
+ * table's other orientation (4 bytes per LM entry: 28 MB at 2 667 words) is built on the device on first use, kept on the sr_bigram
+ * handle and NOT counted in SRGPU_FB_MB.  Counted in it, for the utterances processed together: per (frame, slot) 8 (fwd) + 8 (bwd) +
+ * 2 (first) + 4 (pred) bytes over the 2 W slots and 16 bytes per frame, i.e. 44 W + 16 bytes per frame; per utterance 28 W' (W' = W
+ * rounded up to a multiple of 64: three FP64 vectors and the arg-min) + 28 positions bytes (two rows of cost, first, pred).  An
+ * utterance that alone exceeds SRGPU_FB_MB: SR_ELIMIT.  One call at a time per handle.  min and + without atomics: two identical
+ * calls return identical bits; +inf stays +inf, never NaN. */
+
+/* Lattice of every utterance, by sr_word_lattice_corpus' protocol: out_arc_off[n_utts + 1] and out_best[n_utts] are always written
+ * (T = 0: no arcs and best = 0 -- the empty path ends at the start's word end, as F_u = 0 above); utterance u owns arcs out_arc_off[u]
+ * .. out_arc_off[u + 1], first and last counted within the utterance.  The arc arrays (all eight or none) have capacity cap arcs.
+ * All NULL: the sizing call, SR_OK with the counts in out_arc_off.  Given but the total exceeds cap: nothing is written to them,
+ * out_arc_off still holds the counts needed, SR_EINVAL.  SR_EINVAL also for lattice_beam negative or NaN, a partial set of arc
+ * arrays, a bigram net of another model. */
+SR_API int sr_bigram_word_lattice_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, double lattice_beam, uint64_t cap,
+                                         uint64_t* out_arc_off, double* out_best, uint32_t* out_word, uint32_t* out_hist,
+                                         uint32_t* out_pred, uint32_t* out_first, uint32_t* out_last, double* out_fwd, double* out_bwd,
+                                         double* out_am);
+/* Host only, one utterance: the n_best cheapest DISTINCT word strings (silence removed) among the lattice paths defined above,
+ * cheapest first.  lm is any [n_words x n_words] float table in sr_bigram_create's layout; a word entry pays lm_scale * lm[w *
+ * n_words + h] (NaN and +inf: forbidden).  With the search's own table and lm_scale = 1, entry 1 is the network's best path; with
+ * another table the call is LM rescoring of the lattice.  A string's cost is that of its cheapest path.  Outputs as
+ * sr_lattice_nbest; strings of equal cost come in an order that is the same on every call.  SR_EINVAL: as sr_lattice_nbest (n_best
+ * = 0, arcs not in (last, slot) order, first > last, last >= n_frames, an am that is NaN or -inf, words_cap too small: *out_count =
+ * 0), word or hist >= n_words, a word other than silence whose hist is not itself, silence_word >= n_words, lm_scale NaN or
+ * negative, lm NULL. */
+SR_API int sr_bigram_lattice_nbest(uint32_t n_frames, uint64_t n_arcs, const uint32_t* word, const uint32_t* hist,
+                                   const uint32_t* first, const uint32_t* last, const double* am, uint32_t n_words,
+                                   uint32_t silence_word, const float* lm, double lm_scale, uint32_t n_best, uint32_t* out_words,
+                                   uint64_t words_cap, uint64_t* out_off, double* out_cost, uint32_t* out_count);
+
 /* ---- streaming bigram-LM recognition: LinearSearch's own initialize / processFrame / getResult (:489-520) -------------------
  * The sr_stream_* interface for the bigram search: utterances fed as their frames arrive, many at once.  sr_bigram_stream_end
  * returns, bit for bit, the items sr_recognize_bigram_corpus returns for that utterance with the same p (any layout: they agree);
@@ -568,7 +631,7 @@ typedef struct {
   double gmm_flops;     /* algorithmic: 4 * dim * densities * frames per launch, summed */
   double search_ms;     /* Viterbi decode / align kernels */
   uint64_t search_launches;
-  double search_bytes;  /* algorithmic: (8*S + 4*P) * frames (decode) / (8+1)*N * frames (align) / 32*N * frames (forward-backward; N = P over a network) / (30*W + 48) * frames (word lattice) */
+  double search_bytes;  /* algorithmic: (8*S + 4*P) * frames (decode) / (8+1)*N * frames (align) / 32*N * frames (forward-backward; N = P over a network) / (30*W + 48) * frames (word lattice) / (44*P + 120*W) * frames (bigram word lattice: rows of both walks, word-end tables out and in) */
   uint64_t frames;      /* frames processed */
   uint64_t refined_pairs;      /* SR_GMM_PREFILTER: (frame, state) pairs scored ... */
   uint64_t refined_densities;  /* ... and densities the FP64 stage had to evaluate for them (>= 1 per pair) */

@@ -35,6 +35,7 @@ SYMBOLS = [
     "sr_word_lattice_corpus", "sr_lattice_nbest",
     "sr_bigram_create", "sr_bigram_destroy", "sr_bigram_describe", "sr_recognize_bigram_corpus",
     "sr_bigram_word_posteriors_corpus", "sr_recognize_bigram_confidence_corpus",
+    "sr_bigram_word_lattice_corpus", "sr_bigram_lattice_nbest",
     "sr_stream_open", "sr_stream_begin", "sr_stream_push", "sr_stream_partial", "sr_stream_end", "sr_stream_destroy",
     "sr_bigram_stream_open", "sr_bigram_stream_begin", "sr_bigram_stream_push", "sr_bigram_stream_partial", "sr_bigram_stream_end",
     "sr_bigram_stream_destroy",
@@ -124,6 +125,8 @@ def lib():
         L.sr_recognize_bigram_corpus.argtypes = [vp, vp, vp, C.POINTER(BigramParams), vp, vp, vp, vp]
         L.sr_bigram_word_posteriors_corpus.argtypes = [vp, vp, vp, i32, dbl, dbl, u32, vp, vp, vp, vp]
         L.sr_recognize_bigram_confidence_corpus.argtypes = [vp, vp, vp, C.POINTER(BigramParams), dbl, vp, vp, vp, vp, vp]
+        L.sr_bigram_word_lattice_corpus.argtypes = [vp, vp, vp, i32, dbl, u64] + [vp] * 10
+        L.sr_bigram_lattice_nbest.argtypes = [u32, u64, vp, vp, vp, vp, vp, u32, u32, vp, dbl, u32, vp, u64, vp, vp, C.POINTER(u32)]
         L.sr_stream_open.argtypes = [vp, vp, C.POINTER(SearchParams), u32, u64, C.POINTER(vp)]
         L.sr_stream_begin.argtypes = [vp, C.POINTER(u32)]
         L.sr_stream_push.argtypes = [vp, u32, vp, vp, vp]
@@ -676,6 +679,23 @@ class Corpus:
         n = int(off[-1])
         return ow[:n], osc[:n], ot[:n], off, conf[:n]
 
+    def bigram_word_lattice(self, bigram, lattice_beam=np.inf, kernel=GMM_PREFILTER):
+        """Word lattices over the bigram search network (sr_bigram_word_lattice_corpus: the sizing call, then the filling call) ->
+        (arc_off u64[n_utts+1], best f64[n_utts], word u32[], hist u32[], pred u32[], first u32[], last u32[], fwd f64[], bwd f64[],
+        am f64[]): utterance u owns arcs arc_off[u] .. arc_off[u+1], in (last, slot) order, the frames counted within the utterance."""
+        off = np.zeros(self.n_utts + 1, dtype=np.uint64)
+        best = np.zeros(max(self.n_utts, 1), dtype=np.float64)
+        _check(lib().sr_bigram_word_lattice_corpus(self.model.h, self.h, bigram.h, kernel, float(lattice_beam), 0, _ptr(off), _ptr(best),
+                                                   *([None] * 8)))
+        n = int(off[-1])
+        cap = max(n, 1)
+        word, hist, pred, first, last = (np.zeros(cap, dtype=np.uint32) for _ in range(5))
+        fwd, bwd, am = (np.zeros(cap, dtype=np.float64) for _ in range(3))
+        _check(lib().sr_bigram_word_lattice_corpus(self.model.h, self.h, bigram.h, kernel, float(lattice_beam), cap, _ptr(off), _ptr(best),
+                                                   _ptr(word), _ptr(hist), _ptr(pred), _ptr(first), _ptr(last), _ptr(fwd), _ptr(bwd),
+                                                   _ptr(am)))
+        return off, best[: self.n_utts], word[:n], hist[:n], pred[:n], first[:n], last[:n], fwd[:n], bwd[:n], am[:n]
+
     def path_scores(self, states, kernel=GMM_PREFILTER):
         """Emission cost along a state path (one state per frame): Trainer::calc_am_score's summands."""
         states = np.ascontiguousarray(states, dtype=np.uint16)
@@ -732,6 +752,25 @@ def lattice_nbest(n_frames, word, first, last, cost, silence_word, n_best, words
     n = C.c_uint32(0)
     _check(lib().sr_lattice_nbest(int(n_frames), len(word), _ptr(word), _ptr(first), _ptr(last), _ptr(cost), int(silence_word), int(n_best),
                                   _ptr(out), cap, _ptr(off), _ptr(oc), C.byref(n)))
+    return [(out[int(off[k]):int(off[k + 1])].copy(), float(oc[k])) for k in range(n.value)]
+
+
+def bigram_lattice_nbest(n_frames, word, hist, first, last, am, silence_word, lm, n_best, lm_scale=1.0, words_cap=None):
+    """sr_bigram_lattice_nbest on one utterance's arcs (host side) -> [(words u32[], cost)]: the n_best cheapest distinct word
+    strings among the lattice paths, cheapest first; lm [W x W] float32 as for Bigram (another table: LM rescoring)."""
+    word, hist, first, last = (np.ascontiguousarray(a, dtype=np.uint32) for a in (word, hist, first, last))
+    am = np.ascontiguousarray(am, dtype=np.float64)
+    lm = np.ascontiguousarray(lm, dtype=np.float32)
+    assert len(word) == len(hist) == len(first) == len(last) == len(am) and lm.ndim == 2 and lm.shape[0] == lm.shape[1]
+    K = max(int(n_best), 1)
+    cap = K * max(int(n_frames), 1) if words_cap is None else int(words_cap)  # (a path has at most one word per frame)
+    out = np.zeros(max(cap, 1), dtype=np.uint32)
+    off = np.zeros(K + 1, dtype=np.uint64)
+    oc = np.zeros(K, dtype=np.float64)
+    n = C.c_uint32(0)
+    _check(lib().sr_bigram_lattice_nbest(int(n_frames), len(word), _ptr(word), _ptr(hist), _ptr(first), _ptr(last), _ptr(am), lm.shape[0],
+                                         int(silence_word), _ptr(lm), float(lm_scale), int(n_best), _ptr(out), cap, _ptr(off), _ptr(oc),
+                                         C.byref(n)))
     return [(out[int(off[k]):int(off[k + 1])].copy(), float(oc[k])) for k in range(n.value)]
 
 

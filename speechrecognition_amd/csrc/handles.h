@@ -188,6 +188,11 @@ struct sr_corpus {
   DevBuf<uint16_t> lat_first;
   DevBuf<uint64_t> lat_cnt, lat_scan, lat_base, lat_frame_arc;
   DevBuf<uint32_t> lat_arc_word, lat_arc_first, lat_arc_last;
+  // word lattices over the bigram search network (viterbi_bigram_lattice.hip; vectors, rows and order are the bgfb_* buffers, the
+  // scan's workspace and the arcs the lat_* ones): the word-end tables of one launch group, the rolling rows' first / pred, more arc fields
+  DevBuf<double> bglat_fwd, bglat_bwd;
+  DevBuf<uint16_t> bglat_first, bglat_row_first;
+  DevBuf<uint32_t> bglat_pred, bglat_arg, bglat_row_pred, bglat_arc_hist, bglat_arc_pred;
 };
 
 struct sr_lexicon {
@@ -222,6 +227,9 @@ struct sr_bigram {
   double fb_kappa = 0.0;
   float lm_min = 0.f;
   DevBuf<double> fb_lk, fb_lkT;
+  // word lattices (viterbi_bigram_lattice.hip): the table in the caller's orientation, lm[w * W + h], built from lmT on first use
+  DevBuf<float> lat_lm;
+  bool lat_lm_built = false;
 };
 
 // The slots of a stream set (sr_stream_*, sr_bigram_stream_*): slot i holds one open utterance, named by the id

@@ -547,6 +547,47 @@ hipError_t launch_bgfb_words(const BgFbArgs& a, uint64_t n_frames, hipStream_t s
 hipError_t launch_bgfb_conf(const BgFbArgs& a, uint32_t n_utts, const uint32_t* it_word, const uint32_t* it_time,
                             const uint32_t* it_count, double* out_conf, hipStream_t stream);
 
+// ---- word lattices over the bigram search network (viterbi_bigram_lattice.hip) -----------------------------------------------------
+// The launch groups are BgFbArgs' (utterances [utt_first, utt_first + n_group) of one score chunk, `order` = longest first); what a
+// group keeps are the word ends per (frame, slot): fwd, bwd, first, pred [frames of the group][2W].
+struct BgLatArgs {
+  uint32_t n_words, silence, n_positions, Kp;
+  const uint32_t *slot_off, *pos_info, *pos_slot;  // the search net's tables (BigramArgs)
+  const float* lmT;             // [W x W] as BigramArgs
+  float tdp[2][4];
+  const double* scores;         // [frames x ld], row 0 = frame frame_base
+  uint32_t ld;
+  uint64_t frame_base;
+  const uint64_t* frame_off;    // [n_utts_total+1]
+  const uint32_t* order;        // [n_group] the group's utterances, longest first
+  uint32_t utt_first, n_group, n_alive, t;  // n_alive: utterances with more than t frames; t: the frame index of this launch
+  uint64_t group_f0;            // first frame of the group
+  double beam;                  // >= 0 (+inf: every arc on a complete path)
+  double *fwd, *bwd;            // [frames of the group][2W] WE_t(x); the cheapest continuation from that word end
+  uint16_t* first;              // [frames of the group][2W] the frame at which the cheapest path to the word end entered the slot
+  uint32_t* pred;               // [frames of the group][2W] the history it was entered from
+  double *vec, *prod, *wend;    // per utterance of the group [Kp]: the min-plus entry's operand and result; backward: the entry cost of
+                                // the word's own copy (silence: of itself)
+  uint32_t* arg;                // [Kp] per utterance: the entry's arg-min history
+  double* row;                  // [2][n_group][n_positions] forward: the cost rows of two frames; backward: e_t + beta_t
+  uint16_t* row_first;          // [2][n_group][n_positions] forward: first / pred beside the cost
+  uint32_t* row_pred;
+  double* out_best;             // [n_utts_total] min over x of WE_{T-1}(x) (preset to 0: T = 0)
+  uint32_t *arc_word, *arc_hist, *arc_pred, *arc_first, *arc_last;  // the compacted arcs (arc_word null: count only)
+  double *arc_fwd, *arc_bwd, *arc_am;
+};
+hipError_t launch_bglat_transpose(const float* in, uint32_t W, float* out, hipStream_t stream);  // out[h * W + w] = in[w * W + h]
+hipError_t launch_bglat_init(const BgLatArgs& a, uint32_t rows, hipStream_t stream);  // vec rows: the histories before frame 0
+// out[n][i] = min_k (vec[n][k] + (double) tab[k * W + i]) for n < n_alive, i < Kp; arg (null: not wanted) = the smallest such k.
+// argmin: 0 = compare-and-select in the loop, 1 = a min-only loop and an equality rescan (the same bits)
+hipError_t launch_bglat_entry(const float* tab, const double* vec, double* out, uint32_t* arg, uint32_t W, uint32_t Kp, uint32_t n_alive,
+                              int argmin, hipStream_t stream);
+hipError_t launch_bglat_forward(const BgLatArgs& a, hipStream_t stream);   // frame a.t of the first a.n_alive utterances
+hipError_t launch_bglat_backward(const BgLatArgs& a, hipStream_t stream);
+// as launch_lattice_emit, 2W slots per frame
+hipError_t launch_bglat_emit(const BgLatArgs& a, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes, uint64_t* cnt, uint64_t* scan,
+                             uint64_t* arc_base, uint64_t* frame_arc, uint64_t cap, hipStream_t stream);
+
 // out[f] = scores[(f - frame_base) * ld + states[f]] for f in [f0, f1)  (Trainer::calc_am_score, Training.cpp:605)
 hipError_t launch_path_scores(const double* scores, uint32_t ld, uint64_t frame_base, uint64_t f0, uint64_t f1,
                               const uint16_t* states, double* out, hipStream_t stream);

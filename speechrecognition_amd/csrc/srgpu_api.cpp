@@ -18,6 +18,7 @@
 #include <mutex>
 #include <numeric>
 #include <queue>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -2863,6 +2864,314 @@ int sr_lattice_nbest(uint32_t n_frames, uint64_t n_arcs, const uint32_t* word, c
       if (bg != best_g.end() && !(g < bg->second)) continue;
       best_g[{nf, node}] = g;
       queue.push(Item{g + h[nf], g, nf, node, seq++});
+    }
+  }
+  *out_count = n_out;
+  return SR_OK;
+  });
+}
+
+// ---- word lattices over the bigram search network (viterbi_bigram_lattice.hip) -----------------------------------------------------
+// Workspace counted in SRGPU_FB_MB: per (frame, slot) fwd 8 + bwd 8 + first 2 + pred 4 bytes over 2 W slots, and the emit step's count
+// and scan; per utterance the vectors vec / prod / wend (8 Kp each) and arg (4 Kp), the two rows of cost 8 + first 2 + pred 4 per position
+static uint64_t bglat_frame_bytes(const sr_bigram* b) { return 44ull * b->net.n_words + 16; }
+static uint64_t bglat_utt_bytes(const sr_bigram* b) { return 28ull * bgfb_padded(b->net.n_words) + 28ull * b->net.n_positions; }
+
+// The launch groups of a pass, cut like BgFbPass' on the lattice's bytes, each with its utterances ordered longest first.  run()
+// enqueues a chunk's groups: per frame the in-word step and the min-plus entry, forward then backward, then the arcs.
+extern "C++" {
+struct BgLatPass {
+  struct Group { uint32_t u0, u1, t_max; };
+  std::vector<std::vector<Group>> groups;  // per chunk
+  std::vector<uint32_t> order;             // [U] each group's range, longest first
+  BgLatArgs a{};
+  const float *tab_fwd = nullptr, *tab_bwd = nullptr;
+  const uint32_t* d_order = nullptr;
+  size_t ci = 0, scan_bytes = 0;
+  uint64_t cap = 0;
+  uint32_t rows = 0;
+  int argmin = 0;
+
+  int setup(sr_model* m, sr_corpus* c, sr_bigram* b, double beam, uint64_t arc_cap, const std::vector<Chunk>& chunks) {
+    const uint64_t P = b->net.n_positions, per_utt = bglat_utt_bytes(b), per_frame = bglat_frame_bytes(b);
+    const uint32_t W = b->net.n_words, Kp = bgfb_padded(W), U = c->n_utts;
+    auto len = [&](uint32_t u) { return c->frame_off[u + 1] - c->frame_off[u]; };
+    uint64_t max_gf = 1;
+    uint32_t max_gu = 1;
+    groups.assign(chunks.size(), {});
+    order.resize(U);
+    for (uint32_t u = 0; u < U; u++) order[u] = u;
+    for (size_t i = 0; i < chunks.size(); i++)
+      for (uint32_t u = chunks[i].u0; u < chunks[i].u1;) {
+        uint32_t v = u + 1;
+        while (v < chunks[i].u1 && per_frame * (c->frame_off[v + 1] - c->frame_off[u]) + (v + 1 - u) * per_utt <= m->fb_budget) v++;
+        std::stable_sort(order.begin() + u, order.begin() + v, [&](uint32_t x, uint32_t y) { return len(x) > len(y); });
+        groups[i].push_back({u, v, (uint32_t)len(order[u])});
+        max_gf = std::max<uint64_t>(max_gf, c->frame_off[v] - c->frame_off[u]);
+        max_gu = std::max(max_gu, v - u);
+        u = v;
+      }
+    if (max_gf >= (1ull << 31)) return fail(SR_ELIMIT, "too many frames in one launch group");
+    // the table in the other orientation: built once per net
+    if (!b->lat_lm_built) {
+      HIP_TRY(b->lat_lm.ensure((size_t)W * W));
+      HIP_TRY(launch_bglat_transpose(b->lmT.p, W, b->lat_lm.p, m->s_search));
+      HIP_TRY(hipStreamSynchronize(m->s_search));
+      b->lat_lm_built = true;
+    }
+    tab_fwd = b->lmT.p; tab_bwd = b->lat_lm.p;
+    const char* env = getenv("SRGPU_BGLAT_ARGMIN");  // "rescan": the min-only loop with an equality rescan (same bits; for measuring)
+    argmin = env && !strcmp(env, "rescan") ? 1 : 0;
+    rows = max_gu;
+    const size_t S = 2 * (size_t)W;
+    HIP_TRY(c->bglat_fwd.ensure(max_gf * S));
+    HIP_TRY(c->bglat_bwd.ensure(max_gf * S));
+    HIP_TRY(c->bglat_first.ensure(max_gf * S));
+    HIP_TRY(c->bglat_pred.ensure(max_gf * S));
+    HIP_TRY(c->bgfb_vec.ensure((size_t)rows * Kp));
+    HIP_TRY(c->bgfb_prod.ensure((size_t)rows * Kp));
+    HIP_TRY(c->bgfb_wend.ensure((size_t)rows * Kp));
+    HIP_TRY(c->bglat_arg.ensure((size_t)rows * Kp));
+    HIP_TRY(c->bgfb_xb.ensure(2 * (size_t)max_gu * P));
+    HIP_TRY(c->bglat_row_first.ensure(2 * (size_t)max_gu * P));
+    HIP_TRY(c->bglat_row_pred.ensure(2 * (size_t)max_gu * P));
+    HIP_TRY(c->bgfb_order.upload(order.data(), order.size()));
+    d_order = c->bgfb_order.p;
+    HIP_TRY(c->lat_cnt.ensure(max_gf));
+    HIP_TRY(c->lat_scan.ensure(max_gf));
+    HIP_TRY(c->lat_base.ensure(1));
+    HIP_TRY(c->lat_frame_arc.ensure(c->n_frames + 1));
+    HIP_TRY(c->out_cost.ensure(U));
+    scan_bytes = lattice_scan_temp_bytes(max_gf);
+    HIP_TRY(c->fb_scan_temp.ensure(scan_bytes));
+    HIP_TRY(hipMemset(c->lat_base.p, 0, sizeof(uint64_t)));
+    if (U) HIP_TRY(hipMemset(c->out_cost.p, 0, sizeof(double) * U));  // T_u = 0: the empty path ends at the start's word end
+    HIP_TRY(hipDeviceSynchronize());
+    a.n_words = W; a.silence = b->net.silence; a.n_positions = (uint32_t)P; a.Kp = Kp;
+    a.slot_off = b->slot_off.p; a.pos_info = b->pos_info.p; a.pos_slot = b->pos_slot.p; a.lmT = b->lmT.p;
+    memcpy(a.tdp, b->net.tdp, sizeof(a.tdp));
+    a.ld = m->ld; a.frame_off = c->d_frame_off.p; a.beam = beam;
+    a.fwd = c->bglat_fwd.p; a.bwd = c->bglat_bwd.p; a.first = c->bglat_first.p; a.pred = c->bglat_pred.p;
+    a.vec = c->bgfb_vec.p; a.prod = c->bgfb_prod.p; a.wend = c->bgfb_wend.p; a.arg = c->bglat_arg.p;
+    a.row = c->bgfb_xb.p; a.row_first = c->bglat_row_first.p; a.row_pred = c->bglat_row_pred.p;
+    a.out_best = c->out_cost.p;
+    cap = arc_cap;
+    if (cap) {
+      HIP_TRY(c->lat_arc_word.ensure(cap)); HIP_TRY(c->bglat_arc_hist.ensure(cap)); HIP_TRY(c->bglat_arc_pred.ensure(cap));
+      HIP_TRY(c->lat_arc_first.ensure(cap)); HIP_TRY(c->lat_arc_last.ensure(cap));
+      HIP_TRY(c->lat_arc_fwd.ensure(cap)); HIP_TRY(c->lat_arc_bwd.ensure(cap)); HIP_TRY(c->lat_arc_cost.ensure(cap));
+      a.arc_word = c->lat_arc_word.p; a.arc_hist = c->bglat_arc_hist.p; a.arc_pred = c->bglat_arc_pred.p;
+      a.arc_first = c->lat_arc_first.p; a.arc_last = c->lat_arc_last.p;
+      a.arc_fwd = c->lat_arc_fwd.p; a.arc_bwd = c->lat_arc_bwd.p; a.arc_am = c->lat_arc_cost.p;
+    }
+    // per frame: the rows of both walks (cost, first, pred in and out forward: 28, e + beta in and out backward: 16 per position) and
+    // the word-end tables (22 per slot out, fwd and bwd in again for the count, all of it for the write: 60 per slot, 2 W slots)
+    if (m->profiling) m->prof.search_bytes += (44.0 * (double)P + 120.0 * (double)W) * (double)c->n_frames;
+    return SR_OK;
+  }
+  int run(sr_corpus* c, const Chunk& ch, const double* table, hipStream_t s) {
+    for (const Group& g : groups[ci]) {
+      a.scores = table; a.frame_base = ch.f0; a.group_f0 = c->frame_off[g.u0];
+      a.order = d_order + g.u0; a.utt_first = g.u0; a.n_group = g.u1 - g.u0;
+      auto alive = [&](uint32_t t) {  // utterances of the group with more than t frames: a prefix of its order
+        uint32_t n = 0;
+        while (n < a.n_group && c->frame_off[order[g.u0 + n] + 1] - c->frame_off[order[g.u0 + n]] > t) n++;
+        return n;
+      };
+      HIP_TRY(launch_bglat_init(a, rows, s));
+      HIP_TRY(launch_bglat_entry(tab_fwd, a.vec, a.prod, a.arg, a.n_words, a.Kp, alive(0), argmin, s));
+      for (uint32_t t = 0; t < g.t_max; t++) {
+        a.t = t; a.n_alive = alive(t);
+        HIP_TRY(launch_bglat_forward(a, s));
+        HIP_TRY(launch_bglat_entry(tab_fwd, a.vec, a.prod, a.arg, a.n_words, a.Kp, alive(t + 1), argmin, s));
+      }
+      for (uint32_t t = g.t_max; t-- > 0;) {
+        a.t = t; a.n_alive = alive(t);
+        HIP_TRY(launch_bglat_backward(a, s));
+        if (t) HIP_TRY(launch_bglat_entry(tab_bwd, a.vec, a.prod, nullptr, a.n_words, a.Kp, a.n_alive, argmin, s));
+      }
+      const uint64_t n = c->frame_off[g.u1] - c->frame_off[g.u0];
+      HIP_TRY(launch_bglat_emit(a, n, c->fb_scan_temp.p, scan_bytes, c->lat_cnt.p, c->lat_scan.p, c->lat_base.p, c->lat_frame_arc.p, cap, s));
+    }
+    ci++;
+    return SR_OK;
+  }
+};
+}  // extern "C++"
+
+int sr_bigram_word_lattice_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, double lattice_beam, uint64_t cap,
+                                  uint64_t* out_arc_off, double* out_best, uint32_t* out_word, uint32_t* out_hist, uint32_t* out_pred,
+                                  uint32_t* out_first, uint32_t* out_last, double* out_fwd, double* out_bwd, double* out_am) {
+  return guarded(__func__, [&]() -> int {
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  if (!b || b->model != m) return fail(SR_EINVAL, "bigram search net does not belong to this model");
+  if (!out_arc_off || !out_best) return fail(SR_EINVAL, "null argument");
+  if (!(lattice_beam >= 0.0)) return fail(SR_EINVAL, "lattice_beam must be >= 0 (got %g)", lattice_beam);
+  const bool fill = out_word || out_hist || out_pred || out_first || out_last || out_fwd || out_bwd || out_am;
+  if (fill && (!out_word || !out_hist || !out_pred || !out_first || !out_last || !out_fwd || !out_bwd || !out_am))
+    return fail(SR_EINVAL, "null output (pass all eight arc arrays, or none)");
+  if (b->lm_min == -std::numeric_limits<float>::infinity()) return fail(SR_EINVAL, "the language model has a score of -inf");
+  const uint32_t U = c->n_utts;
+  const uint64_t F = c->n_frames, per = bglat_frame_bytes(b), per_utt = bglat_utt_bytes(b), S = 2ull * b->net.n_words;
+  for (uint32_t u = 0; u < U; u++) {
+    const uint64_t T = c->frame_off[u + 1] - c->frame_off[u];
+    if (T > 65535) return fail(SR_ELIMIT, "utterance %u: %llu frames exceed the lattice's 65535", u, (unsigned long long)T);
+    if (per * T + per_utt > m->fb_budget)
+      return fail(SR_ELIMIT, "utterance %u: word-end tables of %llu bytes exceed the forward-backward workspace of %llu (SRGPU_FB_MB)",
+                  u, (unsigned long long)(per * T + per_utt), (unsigned long long)m->fb_budget);
+  }
+  std::vector<Chunk> chunks;
+  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
+  BgLatPass lp;
+  const uint64_t dev_cap = fill ? std::min<uint64_t>(cap, F * S) : 0;  // (no lattice has more than F * 2W arcs)
+  if ((rc = lp.setup(m, c, b, lattice_beam, dev_cap, chunks))) return rc;
+  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, gmm_kernel, table); },
+                  [&](const Chunk& ch, const double* table, hipStream_t s) -> int { return lp.run(c, ch, table, s); });
+  if (rc) return rc;
+  if (m->profiling) m->prof.frames += F;
+  uint64_t total = 0;
+  HIP_TRY(hipMemcpy(&total, c->lat_base.p, sizeof(uint64_t), hipMemcpyDeviceToHost));
+  std::vector<uint64_t> frame_arc(F + 1);
+  if (F) HIP_TRY(hipMemcpy(frame_arc.data(), c->lat_frame_arc.p, sizeof(uint64_t) * F, hipMemcpyDeviceToHost));
+  frame_arc[F] = total;
+  for (uint32_t u = 0; u <= U; u++) out_arc_off[u] = frame_arc[c->frame_off[u]];
+  if (U) HIP_TRY(hipMemcpy(out_best, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToHost));
+  if (!fill) return SR_OK;
+  if (total > cap) return fail(SR_EINVAL, "the lattices hold %llu arcs, the arrays %llu", (unsigned long long)total, (unsigned long long)cap);
+  if (total) {
+    HIP_TRY(hipMemcpy(out_word, c->lat_arc_word.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_hist, c->bglat_arc_hist.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_pred, c->bglat_arc_pred.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_first, c->lat_arc_first.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_last, c->lat_arc_last.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_fwd, c->lat_arc_fwd.p, sizeof(double) * total, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_bwd, c->lat_arc_bwd.p, sizeof(double) * total, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_am, c->lat_arc_cost.p, sizeof(double) * total, hipMemcpyDeviceToHost));
+  }
+  return SR_OK;
+  });
+}
+
+// Best-first search as sr_lattice_nbest over (last arc taken, word string so far): the last arc fixes the frame, the slot it left
+// (what may follow: its own copy after a word, the silence word after the silence word or the start) and the history the next word
+// pays the LM for.  The heuristic h[i] = the cheapest completion after arc i is exact (one backward pass over the arcs).
+int sr_bigram_lattice_nbest(uint32_t n_frames, uint64_t n_arcs, const uint32_t* word, const uint32_t* hist, const uint32_t* first,
+                            const uint32_t* last, const double* am, uint32_t n_words, uint32_t silence_word, const float* lm,
+                            double lm_scale, uint32_t n_best, uint32_t* out_words, uint64_t words_cap, uint64_t* out_off, double* out_cost,
+                            uint32_t* out_count) {
+  return guarded(__func__, [&]() -> int {
+  if (!out_off || !out_cost || !out_count || (n_arcs && (!word || !hist || !first || !last || !am)) || (words_cap && !out_words))
+    return fail(SR_EINVAL, "null argument");
+  *out_count = 0;
+  out_off[0] = 0;
+  if (!lm) return fail(SR_EINVAL, "lm is null");
+  if (n_best == 0) return fail(SR_EINVAL, "n_best must be >= 1");
+  if (!(lm_scale >= 0.0)) return fail(SR_EINVAL, "lm_scale must be >= 0 (got %g)", lm_scale);
+  if (n_words == 0 || silence_word >= n_words) return fail(SR_EINVAL, "silence word %u out of range (%u words)", silence_word, n_words);
+  if (n_arcs >= 0xFFFFFFFFull) return fail(SR_ELIMIT, "too many arcs");
+  const double inf = std::numeric_limits<double>::infinity();
+  const uint32_t W = n_words, sil = silence_word;
+  // the slot an arc ends: the word itself, the silence word, or the copy hist + W
+  auto slot_of = [&](uint64_t i) { return word[i] != sil ? word[i] : (hist[i] == sil ? sil : hist[i] + W); };
+  for (uint64_t i = 0; i < n_arcs; i++) {
+    if (word[i] >= W || hist[i] >= W) return fail(SR_EINVAL, "arc %llu: word %u, history %u of %u words", (unsigned long long)i, word[i], hist[i], W);
+    if (word[i] != sil && hist[i] != word[i]) return fail(SR_EINVAL, "arc %llu: word %u ends with history %u", (unsigned long long)i, word[i], hist[i]);
+    if (first[i] > last[i] || last[i] >= n_frames) return fail(SR_EINVAL, "arc %llu: frames %u .. %u of %u", (unsigned long long)i, first[i], last[i], n_frames);
+    if (i && (last[i] < last[i - 1] || (last[i] == last[i - 1] && slot_of(i) <= slot_of(i - 1))))
+      return fail(SR_EINVAL, "arc %llu: the arcs are not in (last, slot) order", (unsigned long long)i);
+    if (std::isnan(am[i]) || am[i] == -inf) return fail(SR_EINVAL, "arc %llu: cost %g", (unsigned long long)i, am[i]);
+  }
+  if (n_frames == 0) return SR_OK;
+  const uint32_t T = n_frames, kStart = 0xFFFFFFFFu;
+  // the arcs by first frame (a counting sort: arcs of one frame keep their order)
+  std::vector<uint64_t> beg(T + 2, 0);
+  for (uint64_t i = 0; i < n_arcs; i++) beg[first[i] + 1]++;
+  for (uint32_t f = 0; f <= T; f++) beg[f + 1] += beg[f];
+  std::vector<uint32_t> by_first(n_arcs);
+  {
+    std::vector<uint64_t> fill(beg.begin(), beg.end() - 1);
+    for (uint64_t i = 0; i < n_arcs; i++) by_first[fill[first[i]]++] = (uint32_t)i;
+  }
+  // the cost of arc j right after arc i (kStart: the start, a word end of the silence word): +inf where the network has no such entry
+  auto step = [&](uint32_t i, uint32_t j) -> double {
+    const uint32_t pw = i == kStart ? sil : word[i], ph = i == kStart ? sil : hist[i];
+    double c = 0.0;
+    if (word[j] != sil) {
+      const float l = lm[(size_t)word[j] * W + ph];
+      if (!(l < std::numeric_limits<float>::infinity())) return inf;  // NaN and +inf: forbidden
+      c = lm_scale * (double)l;
+    } else if (hist[j] == sil) {
+      if (!(pw == sil && ph == sil)) return inf;  // the silence word follows the start or itself
+    } else if (pw != hist[j] || pw == sil) {
+      return inf;  // the copy h + W follows word h alone
+    }
+    return c + am[j];
+  };
+  std::vector<double> h(n_arcs, inf);
+  double h_start = inf;
+  for (uint64_t k = n_arcs; k-- > 0;) {  // (last ascends with the index, and an arc's successors start after its last: they are done)
+    const uint32_t i = (uint32_t)k, nf = last[i] + 1;
+    if (nf == T) { h[i] = 0.0; continue; }
+    for (uint64_t q = beg[nf]; q < beg[nf + 1]; q++) {
+      const uint32_t j = by_first[q];
+      const double x = step(i, j) + h[j];
+      if (x < h[i]) h[i] = x;
+    }
+  }
+  for (uint64_t q = beg[0]; q < beg[1]; q++) {
+    const uint32_t j = by_first[q];
+    const double x = step(kStart, j) + h[j];
+    if (x < h_start) h_start = x;
+  }
+  struct Node { uint32_t parent, word; };
+  std::vector<Node> trie{{0xFFFFFFFFu, 0}};  // node 0: the empty string
+  std::map<std::pair<uint32_t, uint32_t>, uint32_t> child;
+  std::map<std::pair<uint32_t, uint32_t>, double> best_g;  // (arc, node) -> the cheapest cost pushed
+  struct Item { double f, g; uint32_t arc, node; uint64_t seq; };
+  auto later = [](const Item& x, const Item& y) { return x.f > y.f || (x.f == y.f && x.seq > y.seq); };
+  std::priority_queue<Item, std::vector<Item>, decltype(later)> queue(later);
+  uint64_t seq = 0, n_words_out = 0;
+  if (h_start < inf) {
+    best_g[{kStart, 0u}] = 0.0;
+    queue.push(Item{h_start, 0.0, kStart, 0, seq++});
+  }
+  uint32_t n_out = 0;
+  std::vector<uint32_t> rev;
+  std::set<uint32_t> done;  // the strings (trie nodes) given out
+  while (!queue.empty() && n_out < n_best) {
+    const Item it = queue.top();
+    queue.pop();
+    if (it.g > best_g[{it.arc, it.node}]) continue;  // a cheaper path reached this state later
+    const uint32_t nf = it.arc == kStart ? 0 : last[it.arc] + 1;
+    if (nf == T) {
+      if (!done.insert(it.node).second) continue;  // the string has left already, at its cheapest, through another final arc
+      rev.clear();
+      for (uint32_t n = it.node; n != 0; n = trie[n].parent) rev.push_back(trie[n].word);
+      if (n_words_out + rev.size() > words_cap) {
+        *out_count = 0;
+        return fail(SR_EINVAL, "words_cap %llu is too small", (unsigned long long)words_cap);
+      }
+      for (size_t k = rev.size(); k-- > 0;) out_words[n_words_out++] = rev[k];
+      out_cost[n_out] = it.g;
+      out_off[++n_out] = n_words_out;
+      continue;
+    }
+    for (uint64_t q = beg[nf]; q < beg[nf + 1]; q++) {
+      const uint32_t j = by_first[q];
+      const double st = step(it.arc, j);
+      if (!(h[j] < inf) || !(st < inf)) continue;  // no complete path goes this way
+      uint32_t node = it.node;
+      if (word[j] != sil) {
+        auto ins = child.emplace(std::make_pair(it.node, word[j]), (uint32_t)trie.size());
+        if (ins.second) trie.push_back(Node{it.node, word[j]});
+        node = ins.first->second;
+      }
+      const double g = it.g + st;
+      auto bg = best_g.find({j, node});
+      if (bg != best_g.end() && !(g < bg->second)) continue;
+      best_g[{j, node}] = g;
+      queue.push(Item{g + h[j], g, j, node, seq++});
     }
   }
   *out_count = n_out;
