@@ -933,6 +933,50 @@ class LinearSearch {
       }
   }
 
+  // One MMI E-step against THIS search's network (sr_bigram_mmi_statistics_corpus): the numerator over the network restricted to each
+  // segment's transcript (word ids, silence not listed), the denominator over the free network with the bigram LM, every cost times
+  // scale (kappa).  f_num / f_den per segment (+inf: no path through the transcript; such a segment contributes to neither side) and
+  // both statistics sets, ready for sr_model_create_from_mmi_statistics.  The next iteration needs a LinearSearch on the NEW model: an
+  // sr_bigram belongs to the model it was created on.
+  struct MmiStatistics {
+    std::vector<double> f_num, f_den;
+    Trainer::Statistics num, den;
+  };
+  MmiStatistics mmi_statistics(Corpus const& corpus, std::vector<std::vector<uint32_t> > const& transcripts, double scale,
+                               double posterior_floor = 0.0) {
+    const size_t n = corpus.get_corpus_size();
+    if (transcripts.size() != n) throw std::invalid_argument("mmi_statistics: one transcript per segment");
+    std::vector<uint32_t> trans;
+    std::vector<uint64_t> trans_off(1, 0);
+    for (auto const& t : transcripts) {
+      trans.insert(trans.end(), t.begin(), t.end());
+      trans_off.push_back(trans.size());
+    }
+    trans.push_back(0);  // (never empty: the ABI tells "no transcripts" by a null pointer)
+    uint32_t n_mean = 0, n_var = 0;
+    check(sr_model_tying_info(scorer_.handle(), &n_mean, &n_var));
+    const size_t D = scorer_.dimension;
+    MmiStatistics r;
+    r.f_num.assign(std::max<size_t>(n, 1), 0.0);
+    r.f_den.assign(std::max<size_t>(n, 1), 0.0);
+    for (Trainer::Statistics* st : {&r.num, &r.den}) {
+      st->mean_acc.assign(n_mean * D, 0.0); st->mean_w.assign(n_mean, 0.0);
+      st->var_acc.assign(n_var * D, 0.0); st->var_w.assign(n_var, 0.0);
+    }
+    sr_corpus* c = nullptr;
+    check(sr_corpus_upload(scorer_.handle(), corpus.features(), corpus.frame_offsets(), (uint32_t)n, &c));
+    const int rc = sr_bigram_mmi_statistics_corpus(scorer_.handle(), c, net_, scorer_.gmm_kernel, scale, posterior_floor,
+                                                   scorer_.max_approx() ? 1 : 0, trans.data(), trans_off.data(), r.f_num.data(),
+                                                   r.f_den.data(), r.num.mean_acc.data(), r.num.mean_w.data(), r.num.var_acc.data(),
+                                                   r.num.var_w.data(), r.den.mean_acc.data(), r.den.mean_w.data(), r.den.var_acc.data(),
+                                                   r.den.var_w.data());
+    sr_corpus_destroy(c);
+    check(rc);
+    r.f_num.resize(n);
+    r.f_den.resize(n);
+    return r;
+  }
+
   struct Hypothesis {
     std::vector<uint32_t> words;  // silence removed
     double cost;                  // of the string's cheapest lattice path

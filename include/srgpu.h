@@ -510,6 +510,50 @@ SR_API int sr_recognize_bigram_confidence_corpus(sr_model* m, sr_corpus* c, sr_b
                                                  uint32_t* out_word, float* out_score, uint32_t* out_time, uint64_t* out_off,
                                                  double* out_conf);
 
+/* ---- MMI training against the bigram search: occupancies and numerator / denominator statistics over ITS network -----------------
+ * Both networks are the one of the block above (slots, start, every history kept, no beams, scale = kappa in FP64).
+ *   FREE network (denominator): every path; F_den is bit for bit the F_u of sr_bigram_word_posteriors_corpus (the same forward pass and
+ *   linear-domain word entry, so the same limits: -kappa lm > 700 SR_ELIMIT, a score of -inf SR_EINVAL, the underflow rule).
+ *   TRANSCRIPT-CONSTRAINED network (numerator): transcript of utterance u = trans[trans_off[u] .. trans_off[u + 1]) (word ids, silence
+ *   not listed, possibly empty); the subset of the free network's paths whose sequence of non-silence word ENTRIES is the transcript:
+ *   the chain of segments S w_1 c_1 .. w_n c_n.  S, the silence word, is entered from the start's word end before frame 0 and from its
+ *   own word end afterwards (the LM never enters silence: it can only lead the utterance); w_i from the word end of w_{i-1} or c_{i-1}
+ *   at kappa * (double) lm[w_i * W + w_{i-1}] (w_1: from the start or the end of S, history = silence; a NaN or +inf term: no path,
+ *   F_num = +inf); c_i, the silence copy after w_i, from the word end of w_i alone at no LM cost.  Paths end in the word end of w_n or
+ *   c_n (n = 0: of S).  Inside a segment the rules above.  A repeated word (w w) is two segments joined by lm[w, w], distinct from
+ *   staying inside w.  Evaluated in log space throughout: no product, nothing underflows to "forbidden".  F_num is the same formula
+ *   over the subset, so F_num >= F_den up to rounding.  T_u = 0: F_den = 0; F_num = 0 for an empty transcript, else +inf.
+ *   occ_t(k) = the posterior probability that frame t's emission is mixture k's = dF / d e(t, k) = the sum of gamma over the positions
+ *   that carry k (an entry emits the mixture of the state it moves to); sum over k = 1.
+ * Silence need not be word 0: the search net carries its silence word.  Errors, all found before any launch or table build: as
+ * sr_bigram_word_posteriors_corpus (scale, floor, max_items, a partial item set, a net of another model, the LM limits, an utterance
+ * whose free trellis alone exceeds SRGPU_FB_MB); SR_EINVAL for trans without trans_off or the reverse, trans_off[0] != 0 or decreasing,
+ * a word id >= n_words or equal to the silence word; SR_ELIMIT for a chain of more than 8192 positions, a chain trellis (8 bytes per
+ * frame and chain position) beyond SRGPU_FB_MB, or 2^31 (frame, mixture) pairs.
+ * Memory: launch groups, workspace and the (sr_bigram, kappa) table are the block's above (no word posteriors are kept).  Added, NOT
+ * counted in SRGPU_FB_MB: the item buffers, 14 bytes per (frame, distinct mixture of the net) reserved for the free network -- 9 GB at
+ * 2 667 words of three states and 80 000 frames; per (frame, distinct mixture of its chain) for the constrained one --, 4 bytes per
+ * net position for the position lists; the chains, 20 bytes per chain position; the host keeps slot_off, pos_info and the LM (4 W^2
+ * bytes) on the sr_bigram.  One call at a time per handle.  No atomics and a fixed summation order: two identical calls return
+ * identical bits.
+ * The EBW update is sr_model_create_from_mmi_statistics, unchanged.  An sr_bigram belongs to its model: the next iteration's is created
+ * on the NEW model with sr_bigram_create. */
+
+/* Outputs and protocol exactly as sr_net_occupancies_corpus: trans and trans_off both NULL = the free network, both given = the
+ * constrained one; out_cost required; items all or none, largest first (ties: smaller id first), at most max_items, not renormalised. */
+SR_API int sr_bigram_occupancies_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, double scale,
+                                        double posterior_floor, uint32_t max_items, const uint32_t* trans,
+                                        const uint64_t* trans_off, double* out_cost, uint16_t* out_count,
+                                        uint16_t* out_state, double* out_weight);
+/* One MMI E-step exactly as sr_mmi_statistics_corpus: the numerator pass first, ONLY utterances with finite F_num contribute, to
+ * either side (its cost gates the free pass on the device); all outputs required, statistics shaped and seeded as
+ * sr_accumulate_corpus'; shards add up, the 1e-4 seed once per call and side. */
+SR_API int sr_bigram_mmi_statistics_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, double scale,
+                                           double posterior_floor, int max_approx, const uint32_t* trans,
+                                           const uint64_t* trans_off, double* out_num_cost, double* out_den_cost,
+                                           double* num_mean_acc, double* num_mean_w, double* num_var_acc, double* num_var_w,
+                                           double* den_mean_acc, double* den_mean_w, double* den_var_acc, double* den_var_w);
+
 /* ---- word lattices and N-best lists for the bigram search: ITS network in the min semiring -----------------------------------------
  * The network of the block above (slots 0 .. W-1 the words, slot h + W the silence copy after word h, the start's word end = the
  * silence word at cost 0, the merge WITHOUT the positional cut: every history is kept, no beams), evaluated in the MIN semiring, in
@@ -631,7 +675,7 @@ typedef struct {
   double gmm_flops;     /* algorithmic: 4 * dim * densities * frames per launch, summed */
   double search_ms;     /* Viterbi decode / align kernels */
   uint64_t search_launches;
-  double search_bytes;  /* algorithmic: (8*S + 4*P) * frames (decode) / (8+1)*N * frames (align) / 32*N * frames (forward-backward; N = P over a network) / (30*W + 48) * frames (word lattice) / (44*P + 120*W) * frames (bigram word lattice: rows of both walks, word-end tables out and in) */
+  double search_bytes;  /* algorithmic: (8*S + 4*P) * frames (decode) / (8+1)*N * frames (align) / 32*N * frames (forward-backward; N = P over a network) / (30*W + 48) * frames (word lattice) / (44*P + 120*W) * frames (bigram word lattice: rows of both walks, word-end tables out and in) / bigram MMI passes: 24*N * frames for a chain's forward-backward, 32*P * frames for the free network's, + 16*N (8*P: the count pass is in the 32) * frames for the two item passes' reads of gamma */
   uint64_t frames;      /* frames processed */
   uint64_t refined_pairs;      /* SR_GMM_PREFILTER: (frame, state) pairs scored ... */
   uint64_t refined_densities;  /* ... and densities the FP64 stage had to evaluate for them (>= 1 per pair) */

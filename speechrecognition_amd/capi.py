@@ -35,6 +35,7 @@ SYMBOLS = [
     "sr_word_lattice_corpus", "sr_lattice_nbest",
     "sr_bigram_create", "sr_bigram_destroy", "sr_bigram_describe", "sr_recognize_bigram_corpus",
     "sr_bigram_word_posteriors_corpus", "sr_recognize_bigram_confidence_corpus",
+    "sr_bigram_occupancies_corpus", "sr_bigram_mmi_statistics_corpus",
     "sr_bigram_word_lattice_corpus", "sr_bigram_lattice_nbest",
     "sr_stream_open", "sr_stream_begin", "sr_stream_push", "sr_stream_partial", "sr_stream_end", "sr_stream_destroy",
     "sr_bigram_stream_open", "sr_bigram_stream_begin", "sr_bigram_stream_push", "sr_bigram_stream_partial", "sr_bigram_stream_end",
@@ -124,6 +125,8 @@ def lib():
         L.sr_bigram_describe.argtypes = [vp, C.c_char_p, C.c_size_t]
         L.sr_recognize_bigram_corpus.argtypes = [vp, vp, vp, C.POINTER(BigramParams), vp, vp, vp, vp]
         L.sr_bigram_word_posteriors_corpus.argtypes = [vp, vp, vp, i32, dbl, dbl, u32, vp, vp, vp, vp]
+        L.sr_bigram_occupancies_corpus.argtypes = [vp, vp, vp, i32, dbl, dbl, u32, vp, vp, vp, vp, vp, vp]
+        L.sr_bigram_mmi_statistics_corpus.argtypes = [vp, vp, vp, i32, dbl, dbl, i32, vp, vp] + [vp] * 10
         L.sr_recognize_bigram_confidence_corpus.argtypes = [vp, vp, vp, C.POINTER(BigramParams), dbl, vp, vp, vp, vp, vp]
         L.sr_bigram_word_lattice_corpus.argtypes = [vp, vp, vp, i32, dbl, u64] + [vp] * 10
         L.sr_bigram_lattice_nbest.argtypes = [u32, u64, vp, vp, vp, vp, vp, u32, u32, vp, dbl, u32, vp, u64, vp, vp, C.POINTER(u32)]
@@ -664,6 +667,35 @@ class Corpus:
                                                       _ptr(cost), _ptr(count), _ptr(word), _ptr(weight)))
         n = self.n_frames
         return cost[: self.n_utts], count[:n], word[:n], weight[:n]
+
+    def bigram_occupancies(self, bigram, scale=1.0, transcripts=None, kernel=GMM_PREFILTER, floor=0.0, max_items=8):
+        """Mixture occupancies over the bigram search network (sr_bigram_occupancies_corpus): the free network, or -- transcripts =
+        one sequence of word ids per utterance, silence not listed -- the network restricted to them -> (cost, count, state,
+        weight) as net_occupancies."""
+        F = max(self.n_frames, 1)
+        K = max(int(max_items), 1)
+        cost = np.zeros(max(self.n_utts, 1), dtype=np.float64)
+        count = np.zeros(F, dtype=np.uint16)
+        state = np.zeros((F, K), dtype=np.uint16)
+        weight = np.zeros((F, K), dtype=np.float64)
+        flat, off = self._transcripts(transcripts)
+        _check(lib().sr_bigram_occupancies_corpus(self.model.h, self.h, bigram.h, kernel, float(scale), float(floor), int(max_items),
+                                                  _ptr(flat), _ptr(off), _ptr(cost), _ptr(count), _ptr(state), _ptr(weight)))
+        n = self.n_frames
+        return cost[: self.n_utts], count[:n], state[:n], weight[:n]
+
+    def bigram_mmi_statistics(self, bigram, transcripts, scale=1.0, kernel=GMM_PREFILTER, floor=0.0, max_approx=True):
+        """One MMI E-step against the bigram search network (sr_bigram_mmi_statistics_corpus) -> (F_num, F_den, num, den) as
+        mmi_statistics.  After Model.from_mmi_statistics the next iteration needs a Model.bigram of the NEW model."""
+        nm, nv = C.c_uint32(), C.c_uint32()
+        _check(lib().sr_model_tying_info(self.model.h, C.byref(nm), C.byref(nv)))
+        D = self.model.dim
+        num, den = ((np.zeros((nm.value, D)), np.zeros(nm.value), np.zeros((nv.value, D)), np.zeros(nv.value)) for _ in range(2))
+        fn, fd = (np.zeros(max(self.n_utts, 1), dtype=np.float64) for _ in range(2))
+        flat, off = self._transcripts(transcripts)
+        _check(lib().sr_bigram_mmi_statistics_corpus(self.model.h, self.h, bigram.h, kernel, float(scale), float(floor), int(max_approx),
+                                                     _ptr(flat), _ptr(off), _ptr(fn), _ptr(fd), *[_ptr(a) for a in num + den]))
+        return fn[: self.n_utts], fd[: self.n_utts], num, den
 
     def recognize_bigram_confidence(self, bigram, scale=1.0, acoustic_pruning=FLT_MAX, lm_pruning=FLT_MAX, kernel=GMM_PREFILTER,
                                     max_word_ends=0, dense_states=False, global_states=False):

@@ -183,6 +183,10 @@ struct sr_corpus {
   // the launch groups' vectors and utterance orders, the items' confidences
   DevBuf<double> bgfb_vec, bgfb_prod, bgfb_wend, bgfb_m, bgfb_xb, bgfb_conf;
   DevBuf<uint32_t> bgfb_order;
+  // MMI training over the bigram search network (viterbi_bigram_mmi.hip; chains, mixture lists, items and the gate are the mmi_* / fb_*
+  // buffers above): the 32-bit position lists, the chains' entry LM costs
+  DevBuf<uint32_t> bgmmi_slot_pos;
+  DevBuf<double> bgmmi_lmc;
   // word lattices (viterbi_lattice.hip): the word-end tables of one launch group, the scan's workspace, the compacted arcs
   DevBuf<double> lat_fwd, lat_ends, lat_bend, lat_arc_fwd, lat_arc_bwd, lat_arc_cost;
   DevBuf<uint16_t> lat_first;
@@ -215,6 +219,8 @@ struct sr_bigram {
   DevBuf<uint16_t> mixtures;
   DevBuf<uint32_t> pos_info, pos_slot;
   DevBuf<float> lmT, lm_rowmin, lm_rowmax;
+  std::vector<uint32_t> h_slot_off, h_pos_info;  // host copies of slot_off, pos_info and lmT (transcript chains, mixture lists)
+  std::vector<float> h_lmT;
   // workspace
   DevBuf<uint32_t> we_slot, we_bp, out_word, out_time, out_count, out_flags;
   DevBuf<float> we_score, out_score;

@@ -547,6 +547,58 @@ hipError_t launch_bgfb_words(const BgFbArgs& a, uint64_t n_frames, hipStream_t s
 hipError_t launch_bgfb_conf(const BgFbArgs& a, uint32_t n_utts, const uint32_t* it_word, const uint32_t* it_time,
                             const uint32_t* it_count, double* out_conf, hipStream_t stream);
 
+// ---- MMI training over the bigram search network (viterbi_bigram_mmi.hip) ----------------------------------------------------------
+// The network restricted to a transcript w_1 .. w_n: utterance u's chain of segments S w_1 c_1 .. w_n c_n (S = the silence word, c_i =
+// the silence copy after w_i), its positions at chain_off[u] .. chain_off[u + 1] (at most bgchain_max_positions()).  A launch covers
+// utterances [utt_first, utt_first + n_utts) of one score chunk whose trellises fit the workspace together.
+struct BgChainArgs {
+  const double* scores;         // [frames x ld], row 0 = frame frame_base
+  uint32_t ld;
+  uint64_t frame_base;
+  const uint64_t* frame_off;    // [n_utts_total+1]
+  uint32_t utt_first, n_utts;
+  double scale;                 // kappa
+  float tdp[2][4];              // as BgFbArgs
+  const uint64_t* chain_off;    // [n_utts_total+1]
+  const uint32_t* info;         // per chain position: the pos_info of its position in the search net
+  const uint32_t* src;          // first and second state of a segment: the (up to two) word ends that enter it, chain position | chain position << 16,
+                                // 0xFFFF = none; the start's word end counts as that of S (the low half of S' and w_1's link)
+  const uint32_t* dst;          // word ends: the first state of the (up to two) segments they enter, packed the same way
+  const double* lmc;            // first and second state of a segment: kappa lm of the entry (0: S and the copies; +inf: forbidden)
+  uint32_t sil_len;             // states of the silence word: the word end of w_n is that far before the chain's last position
+  uint32_t max_positions;       // longest chain of the launch (sizes the LDS and the workgroup)
+  double* trellis;              // [T_u][N_u] per utterance at trellis_off[u] - trellis_off[utt_first]: alpha, then gamma
+  const uint64_t* trellis_off;  // [n_utts_total+1] prefix sums of T_u * N_u
+  double* out_cost;             // [n_utts_total] kappa F_u
+};
+inline uint32_t bgchain_max_positions() { return 8192; }
+hipError_t launch_bgchain_forward(const BgChainArgs& a, hipStream_t stream);
+hipError_t launch_bgchain_backward(const BgChainArgs& a, hipStream_t stream);
+// Items (frame, mixture, occupancy) from the gamma of either trellis, in FbArgs' item layout: OccItemArgs with 32-bit position lists; a
+// mixture carried by many positions is summed across the lanes of a wave.
+struct BgOccItemArgs {
+  const uint64_t* frame_off;    // [n_utts_total+1]
+  uint32_t utt_first, n_utts;
+  uint64_t group_f0;            // first frame of the launch
+  const double* trellis;
+  const uint64_t* trellis_off;  // chains: as BgChainArgs; null: the free network, rows of n_cols at (frame - group_f0) * n_cols
+  const uint64_t* chain_off;    // chains: as BgChainArgs; null
+  uint32_t n_cols, n_mix;       // free network: positions, distinct mixtures of the net (one list for every utterance)
+  const uint32_t* mix_off;      // chains: [n_utts_total+1] range of utterance u in mix[] / slot_beg[]; null
+  const uint16_t* mix;          // distinct mixtures, ascending
+  const uint32_t* slot_beg;     // positions of mixture j: slot_pos[slot_beg[j] .. slot_beg[j+1])
+  const uint32_t* slot_pos;     // positions grouped by mixture, ascending within
+  const double* gate;           // optional [n_utts_total]: an utterance whose gate is +inf gives no items
+  double floor;                 // items: occupancy > 0 and >= floor
+  uint32_t* group_cnt;          // the rest as in FbArgs
+  const uint32_t* group_scan;
+  uint32_t* item_base;
+  uint32_t* item_off;
+  uint32_t* item_frame; uint16_t* item_mix; double* item_w;
+};
+hipError_t launch_bgocc_items(const BgOccItemArgs& a, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes, uint32_t* scan_out,
+                              hipStream_t stream);
+
 // ---- word lattices over the bigram search network (viterbi_bigram_lattice.hip) -----------------------------------------------------
 // The launch groups are BgFbArgs' (utterances [utt_first, utt_first + n_group) of one score chunk, `order` = longest first); what a
 // group keeps are the word ends per (frame, slot): fwd, bwd, first, pred [frames of the group][2W].

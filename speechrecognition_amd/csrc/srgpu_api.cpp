@@ -1302,6 +1302,7 @@ int sr_bigram_create(sr_model* m, uint32_t n_words, const uint32_t* word_off, co
   BigramArgs& net = b->net;
   net.slot_off = b->slot_off.p; net.slot_mix = b->slot_mix.p; net.mixtures = b->mixtures.p; net.pos_info = b->pos_info.p;
   net.pos_slot = b->pos_slot.p; net.lmT = b->lmT.p; net.lm_rowmin = b->lm_rowmin.p; net.lm_rowmax = b->lm_rowmax.p;
+  b->h_slot_off = std::move(slot_off); b->h_pos_info = std::move(pos_info); b->h_lmT = std::move(lmT);
   *out = own.release();
   return SR_OK;
   });
@@ -2168,6 +2169,7 @@ struct BgFbPass {
   BgFbArgs a{};
   const double *lk = nullptr, *lkT = nullptr;
   const uint32_t* d_order = nullptr;       // `order` on the device
+  bool want_words = true;                  // the word posteriors of every group (the MMI passes read gamma itself)
   size_t ci = 0;
 
   int setup(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, const std::vector<Chunk>& chunks) {
@@ -2245,7 +2247,7 @@ struct BgFbPass {
         if (t) HIP_TRY(launch_bgfb_product(lkT, a.vec, a.prod, a.Kp, a.n_alive, s));
       }
       const uint64_t n = c->frame_off[g.u1] - c->frame_off[g.u0];
-      HIP_TRY(launch_bgfb_words(a, n, s));
+      if (want_words) HIP_TRY(launch_bgfb_words(a, n, s));
       int rc = per_group(a, n);
       if (rc) return rc;
     }
@@ -2655,6 +2657,305 @@ int sr_model_create_from_mmi_statistics(sr_model* m, const double* num_mean_acc,
   }
   *out = nm;
   return SR_OK;
+  });
+}
+
+// ---- MMI training over the bigram search network (viterbi_bigram_mmi.hip) ---------------------------------------------------------
+// The transcripts' chains: segment 0 of utterance u is the silence word S, segment 2 i - 1 the word w_i and segment 2 i its silence
+// copy c_i, each with the pos_info of its slot of the search net; BgChainArgs' src / dst links and entry LM costs as its header says.
+extern "C++" {
+struct BgChains {
+  std::vector<uint64_t> off;  // [U + 1]
+  std::vector<uint32_t> info, src, dst;
+  std::vector<double> lmc;
+};
+// the distinct mixtures (ascending) of a set of positions and the positions carrying each
+struct BgMixLists {
+  std::vector<uint32_t> slot_beg, slot_pos;
+  std::vector<uint16_t> mix;
+  std::vector<std::pair<uint16_t, uint32_t>> ps;
+  void add(const uint32_t* info, uint64_t N) {
+    ps.clear();
+    for (uint64_t i = 0; i < N; i++) ps.push_back({(uint16_t)(info[i] & 0xFFFFu), (uint32_t)i});
+    std::sort(ps.begin(), ps.end());
+    for (size_t i = 0; i < ps.size(); i++) {
+      if (i == 0 || ps[i].first != ps[i - 1].first) {
+        mix.push_back(ps[i].first);
+        slot_beg.push_back((uint32_t)slot_pos.size());
+      }
+      slot_pos.push_back(ps[i].second);
+    }
+  }
+};
+}  // extern "C++"
+
+// bgfb_check plus the transcript's: *constrained = a transcript pair is given.  free_items: the call makes items of the free network
+static int bgocc_check(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, double posterior_floor, const uint32_t* trans,
+                       const uint64_t* trans_off, bool free_items, bool* constrained) {
+  int rc = bgfb_check(m, c, b, scale, posterior_floor);
+  if (rc) return rc;
+  if (free_items) {
+    std::vector<uint8_t> seen(65536, 0);
+    uint64_t n_mix = 0;
+    for (uint32_t i : b->h_pos_info) n_mix += !seen[i & 0xFFFFu]++;
+    if (n_mix * c->n_frames >= (1ull << 31)) return fail(SR_ELIMIT, "too many (frame, mixture) occupancies");
+  }
+  if ((trans_off == nullptr) != (trans == nullptr))
+    return fail(SR_EINVAL, "partial transcript (pass trans and trans_off, or neither)");
+  *constrained = trans_off != nullptr;
+  if (!*constrained) return SR_OK;
+  if (trans_off[0] != 0) return fail(SR_EINVAL, "trans_off[0] must be 0");
+  const uint32_t W = b->net.n_words, sil = b->net.silence;
+  const uint64_t sil_len = b->net.silence_states;
+  for (uint32_t u = 0; u < c->n_utts; u++) {
+    if (trans_off[u + 1] < trans_off[u]) return fail(SR_EINVAL, "trans_off must be non-decreasing (utterance %u)", u);
+    const uint64_t n = trans_off[u + 1] - trans_off[u], T = c->frame_off[u + 1] - c->frame_off[u];
+    uint64_t N = sil_len * (n + 1);
+    for (uint64_t i = trans_off[u]; i < trans_off[u + 1]; i++) {
+      const uint32_t w = trans[i];
+      if (w >= W || w == sil) return fail(SR_EINVAL, "utterance %u: transcript word %u is not a lexicon word other than silence", u, w);
+      N += b->h_slot_off[w + 1] - b->h_slot_off[w];
+    }
+    if (N > bgchain_max_positions())
+      return fail(SR_ELIMIT, "utterance %u: chain of %llu positions exceeds the transcript network's %u", u, (unsigned long long)N,
+                  bgchain_max_positions());
+    if (8 * N * T > m->fb_budget)
+      return fail(SR_ELIMIT, "utterance %u: trellis of %llu bytes exceeds the forward-backward workspace of %llu (SRGPU_FB_MB)", u,
+                  (unsigned long long)(8 * N * T), (unsigned long long)m->fb_budget);
+  }
+  return SR_OK;
+}
+
+static void build_bgchains(const sr_bigram* b, uint32_t U, double scale, const uint32_t* trans, const uint64_t* trans_off, BgChains* ch) {
+  const std::vector<uint32_t>& soff = b->h_slot_off;
+  const uint32_t W = b->net.n_words, sil = b->net.silence, none = 0xFFFFu;
+  ch->off.assign(U + 1, 0);
+  std::vector<uint32_t> beg, end;  // first and last chain position of every segment
+  for (uint32_t u = 0; u < U; u++) {
+    const uint32_t n = (uint32_t)(trans_off[u + 1] - trans_off[u]), G = 2 * n + 1, base = (uint32_t)ch->info.size();
+    const uint32_t* tr = trans + trans_off[u];
+    beg.assign(G, 0); end.assign(G, 0);
+    for (uint32_t g = 0; g < G; g++) {
+      const uint32_t x = g == 0 ? sil : ((g & 1) ? tr[g / 2] : tr[g / 2 - 1] + W);  // the segment's slot
+      beg[g] = (uint32_t)ch->info.size() - base;
+      ch->info.insert(ch->info.end(), b->h_pos_info.begin() + soff[x], b->h_pos_info.begin() + soff[x + 1]);
+      end[g] = (uint32_t)ch->info.size() - base - 1;
+    }
+    ch->src.resize(ch->info.size(), 0xFFFFFFFFu);
+    ch->dst.resize(ch->info.size(), 0xFFFFFFFFu);
+    ch->lmc.resize(ch->info.size(), 0.0);
+    for (uint32_t g = 0; g < G; g++) {
+      uint32_t s0, s1 = none, d0, d1 = none;
+      double lmc = 0.0;
+      if (g == 0) {  // S: from the start and itself; into itself and w_1
+        s0 = end[0]; d0 = beg[0]; d1 = G > 1 ? beg[1] : none;
+      } else if (g & 1) {  // w_i: from w_{i-1} and c_{i-1} (w_1: the start and S); into c_i and w_{i+1}
+        s0 = g == 1 ? end[0] : end[g - 2]; s1 = g == 1 ? none : end[g - 1];
+        d0 = beg[g + 1]; d1 = g + 2 < G ? beg[g + 2] : none;
+        const float x = b->h_lmT[(size_t)(g == 1 ? sil : tr[g / 2 - 1]) * W + tr[g / 2]];
+        lmc = x < std::numeric_limits<float>::infinity() ? scale * (double)x : std::numeric_limits<double>::infinity();  // (NaN: forbidden)
+      } else {  // c_i: from w_i; into w_{i+1}
+        s0 = end[g - 1]; d0 = g + 1 < G ? beg[g + 1] : none;
+      }
+      for (uint32_t k = beg[g]; k <= std::min(beg[g] + 1, end[g]); k++) {
+        ch->src[base + k] = s0 | s1 << 16;
+        ch->lmc[base + k] = lmc;
+      }
+      ch->dst[base + end[g]] = d0 | d1 << 16;
+    }
+    ch->off[u + 1] = ch->info.size();
+  }
+}
+
+// One occupancy pass over the corpus on the search's scoring chunks: the free network (trans_off null; BgFbPass' launch groups, workspace
+// and table cache) or the transcripts' chains (consecutive utterances whose trellises fit m->fb_budget together).  Leaves kappa F_u in
+// c->out_cost and, with want_items, *n_items items in c->fb_item_* (frame order, ascending mixture id) with c->fb_item_off[F + 1];
+// utterances whose gate (device, optional) is +inf give no items.
+static int bgocc_pass(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, double scale, double posterior_floor, const uint32_t* trans,
+                      const uint64_t* trans_off, bool want_items, const double* gate, uint64_t* n_items) {
+  const uint32_t U = c->n_utts;
+  const uint64_t F = c->n_frames, P = b->net.n_positions;
+  const bool chain = trans_off != nullptr;
+  *n_items = 0;
+  HIP_TRY(c->out_cost.ensure(U));
+  if (U == 0) return SR_OK;
+  BgChains ch;
+  if (chain) build_bgchains(b, U, scale, trans, trans_off, &ch);
+  std::vector<uint64_t> tr_off(U + 1, 0);
+  std::vector<uint32_t> mix_off(U + 1, 0);
+  BgMixLists ml;
+  uint64_t item_bound = 0;
+  if (!chain && want_items) ml.add(b->h_pos_info.data(), P);
+  for (uint32_t u = 0; u < U; u++) {
+    const uint64_t N = chain ? ch.off[u + 1] - ch.off[u] : P, T = c->frame_off[u + 1] - c->frame_off[u];
+    tr_off[u + 1] = tr_off[u] + N * T;
+    if (chain && want_items) {
+      ml.add(ch.info.data() + ch.off[u], N);
+      mix_off[u + 1] = (uint32_t)ml.mix.size();
+    }
+    item_bound += T * (chain ? mix_off[u + 1] - mix_off[u] : ml.mix.size());
+  }
+  ml.slot_beg.push_back((uint32_t)ml.slot_pos.size());
+  if (want_items && item_bound >= (1ull << 31)) return fail(SR_ELIMIT, "too many (frame, mixture) occupancies");
+  std::vector<Chunk> chunks;
+  int rc = prepare_chunks(m, c, &chunks);
+  if (rc) return rc;
+  // the chains' launch groups (bgocc_check: every utterance fits alone); the free network's are BgFbPass'
+  struct Group { uint32_t u0, u1, max_n; };
+  std::vector<std::vector<Group>> groups(chunks.size());
+  BgFbPass fp;
+  fp.want_words = false;
+  uint64_t max_gf = 1;
+  if (chain) {
+    uint64_t ws = 1;
+    for (size_t ci = 0; ci < chunks.size(); ci++)
+      for (uint32_t u = chunks[ci].u0; u < chunks[ci].u1;) {
+        uint32_t v = u, max_n = 1;
+        while (v < chunks[ci].u1 && (v == u || 8 * (tr_off[v + 1] - tr_off[u]) <= m->fb_budget)) {
+          max_n = std::max<uint32_t>(max_n, (uint32_t)(ch.off[v + 1] - ch.off[v]));
+          v++;
+        }
+        groups[ci].push_back({u, v, max_n});
+        ws = std::max<uint64_t>(ws, tr_off[v] - tr_off[u]);
+        max_gf = std::max<uint64_t>(max_gf, c->frame_off[v] - c->frame_off[u]);
+        u = v;
+      }
+    HIP_TRY(c->fb_trellis_off.upload(tr_off.data(), U + 1));
+    HIP_TRY(c->fb_trellis.ensure(ws));
+    HIP_TRY(c->mmi_chain_off.upload(ch.off.data(), U + 1));
+    HIP_TRY(c->mmi_info.upload(ch.info.data(), ch.info.size()));
+    HIP_TRY(c->mmi_src.upload(ch.src.data(), ch.src.size()));
+    HIP_TRY(c->mmi_dst.upload(ch.dst.data(), ch.dst.size()));
+    HIP_TRY(c->bgmmi_lmc.upload(ch.lmc.data(), ch.lmc.size()));
+  } else {
+    if ((rc = fp.setup(m, c, b, scale, chunks))) return rc;
+    for (const auto& gs : fp.groups)
+      for (const auto& g : gs) max_gf = std::max<uint64_t>(max_gf, c->frame_off[g.u1] - c->frame_off[g.u0]);
+  }
+  size_t scan_bytes = 0;
+  if (want_items) {
+    if (chain) HIP_TRY(c->fb_mix_off.upload(mix_off.data(), U + 1));
+    HIP_TRY(c->fb_mix.upload(ml.mix.data(), ml.mix.size()));
+    HIP_TRY(c->fb_slot_beg.upload(ml.slot_beg.data(), ml.slot_beg.size()));
+    HIP_TRY(c->bgmmi_slot_pos.upload(ml.slot_pos.data(), ml.slot_pos.size()));
+    scan_bytes = fb_scan_temp_bytes(max_gf);
+    HIP_TRY(c->fb_scan_temp.ensure(scan_bytes));
+    HIP_TRY(c->fb_cnt.ensure(max_gf)); HIP_TRY(c->fb_scan.ensure(max_gf)); HIP_TRY(c->fb_base.ensure(1));
+    HIP_TRY(c->fb_item_off.ensure(F + 1));
+    HIP_TRY(c->fb_item_frame.ensure(item_bound)); HIP_TRY(c->fb_item_mix.ensure(item_bound)); HIP_TRY(c->fb_item_w.ensure(item_bound));
+  }
+  BgChainArgs ca{};
+  ca.ld = m->ld; ca.frame_off = c->d_frame_off.p; ca.scale = scale;
+  memcpy(ca.tdp, b->net.tdp, sizeof(ca.tdp));
+  ca.chain_off = c->mmi_chain_off.p; ca.info = c->mmi_info.p; ca.src = c->mmi_src.p; ca.dst = c->mmi_dst.p; ca.lmc = c->bgmmi_lmc.p;
+  ca.sil_len = b->net.silence_states;
+  ca.trellis = c->fb_trellis.p; ca.trellis_off = c->fb_trellis_off.p; ca.out_cost = c->out_cost.p;
+  BgOccItemArgs ia{};
+  ia.frame_off = c->d_frame_off.p; ia.trellis = c->fb_trellis.p; ia.n_cols = (uint32_t)P; ia.n_mix = chain ? 0u : (uint32_t)ml.mix.size();
+  if (chain) { ia.trellis_off = c->fb_trellis_off.p; ia.chain_off = c->mmi_chain_off.p; ia.mix_off = c->fb_mix_off.p; }
+  ia.mix = c->fb_mix.p; ia.slot_beg = c->fb_slot_beg.p; ia.slot_pos = c->bgmmi_slot_pos.p; ia.gate = gate; ia.floor = posterior_floor;
+  ia.group_cnt = c->fb_cnt.p; ia.item_base = c->fb_base.p; ia.item_off = c->fb_item_off.p;
+  ia.item_frame = c->fb_item_frame.p; ia.item_mix = c->fb_item_mix.p; ia.item_w = c->fb_item_w.p;
+  auto items = [&](uint32_t u0, uint32_t u1, hipStream_t s) -> int {
+    if (!want_items) return SR_OK;
+    ia.utt_first = u0; ia.n_utts = u1 - u0; ia.group_f0 = c->frame_off[u0];
+    HIP_TRY(launch_bgocc_items(ia, c->frame_off[u1] - c->frame_off[u0], c->fb_scan_temp.p, scan_bytes, c->fb_scan.p, s));
+    return SR_OK;
+  };
+  size_t ci = 0;  // run_chunks searches the chunks in order
+  rc = run_chunks(m, chunks, [&](const Chunk& k, double* table) { return score_chunk(m, c, k.f0, k.f1, gmm_kernel, table); },
+      [&](const Chunk& k, const double* table, hipStream_t s) -> int {
+        if (want_items && ci == 0) HIP_TRY(hipMemsetAsync(c->fb_base.p, 0, sizeof(uint32_t), s));
+        if (!chain) {
+          ci++;
+          return fp.run(c, k, table, s, [&](const BgFbArgs& a, uint64_t) -> int {
+            const uint32_t u0 = (uint32_t)(a.order - fp.d_order);
+            return items(u0, u0 + a.n_group, s);
+          });
+        }
+        for (const Group& g : groups[ci]) {
+          ca.scores = table; ca.frame_base = k.f0; ca.utt_first = g.u0; ca.n_utts = g.u1 - g.u0; ca.max_positions = g.max_n;
+          HIP_TRY(launch_bgchain_forward(ca, s));
+          HIP_TRY(launch_bgchain_backward(ca, s));
+          int r = items(g.u0, g.u1, s);
+          if (r) return r;
+        }
+        ci++;
+        return SR_OK;
+      });
+  if (rc) return rc;
+  if (want_items) {
+    uint32_t n = 0;
+    HIP_TRY(hipMemcpy(&n, c->fb_base.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *n_items = n;
+  }
+  if (m->profiling) {
+    // per (frame, position): alpha out, alpha in + gamma out (the free network: counted by BgFbPass, whose word-posterior read of gamma
+    // is the items' count pass here); the items' write pass reads gamma once more
+    m->prof.frames += F;
+    if (chain) m->prof.search_bytes += (want_items ? 40.0 : 24.0) * (double)tr_off[U];
+    else if (want_items) m->prof.search_bytes += 8.0 * (double)P * (double)F;
+  }
+  return SR_OK;
+}
+
+int sr_bigram_occupancies_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, double scale, double posterior_floor,
+                                 uint32_t max_items, const uint32_t* trans, const uint64_t* trans_off, double* out_cost,
+                                 uint16_t* out_count, uint16_t* out_state, double* out_weight) {
+  return guarded(__func__, [&]() -> int {
+  bool constrained = false;
+  int rc = bgocc_check(m, c, b, scale, posterior_floor, trans, trans_off, !trans_off && (out_count || out_state || out_weight), &constrained);
+  if (rc) return rc;
+  if (!out_cost) return fail(SR_EINVAL, "null argument");
+  const bool post = out_count || out_state || out_weight;
+  if (post && (!out_count || !out_state || !out_weight)) return fail(SR_EINVAL, "null output (pass out_count, out_state and out_weight, or none)");
+  if (post && (max_items == 0 || max_items > 65535)) return fail(SR_EINVAL, "max_items must be 1 .. 65535 (got %u)", max_items);
+  const uint64_t F = c->n_frames;
+  uint64_t n_items = 0;
+  if ((rc = bgocc_pass(m, c, b, gmm_kernel, scale, posterior_floor, trans, constrained ? trans_off : nullptr, post, nullptr, &n_items))) return rc;
+  if ((rc = netfb_costs(c, scale, out_cost))) return rc;
+  if (!post || F == 0) return SR_OK;
+  HIP_TRY(c->fb_count.ensure(F));
+  HIP_TRY(c->fb_state.ensure((size_t)F * max_items));
+  HIP_TRY(c->fb_weight.ensure((size_t)F * max_items));
+  HIP_TRY(launch_fb_top(c->fb_item_off.p, c->fb_item_mix.p, c->fb_item_w.p, F, max_items, c->fb_count.p, c->fb_state.p, c->fb_weight.p,
+                        m->s_gmm));
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  HIP_TRY(hipMemcpy(out_count, c->fb_count.p, sizeof(uint16_t) * F, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_state, c->fb_state.p, sizeof(uint16_t) * F * max_items, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_weight, c->fb_weight.p, sizeof(double) * F * max_items, hipMemcpyDeviceToHost));
+  return SR_OK;
+  });
+}
+
+int sr_bigram_mmi_statistics_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, double scale, double posterior_floor,
+                                    int max_approx, const uint32_t* trans, const uint64_t* trans_off, double* out_num_cost,
+                                    double* out_den_cost, double* num_mean_acc, double* num_mean_w, double* num_var_acc, double* num_var_w,
+                                    double* den_mean_acc, double* den_mean_w, double* den_var_acc, double* den_var_w) {
+  return guarded(__func__, [&]() -> int {
+  bool constrained = false;
+  int rc = bgocc_check(m, c, b, scale, posterior_floor, trans, trans_off, true, &constrained);
+  if (rc) return rc;
+  if (!constrained) return fail(SR_EINVAL, "null argument (MMI statistics need the transcripts)");
+  if (!out_num_cost || !out_den_cost || !num_mean_acc || !num_mean_w || !num_var_acc || !num_var_w || !den_mean_acc || !den_mean_w ||
+      !den_var_acc || !den_var_w)
+    return fail(SR_EINVAL, "null output");
+  const uint32_t U = c->n_utts;
+  c->acc_valid = false;
+  // numerator: the transcripts' chains.  Its costs stay on the device as the denominator's gate: an utterance without a path through
+  // its transcript (F_num = +inf) contributes to neither side.
+  uint64_t n_items = 0;
+  if ((rc = bgocc_pass(m, c, b, gmm_kernel, scale, posterior_floor, trans, trans_off, true, nullptr, &n_items))) return rc;
+  if ((rc = netfb_costs(c, scale, out_num_cost))) return rc;
+  HIP_TRY(c->mmi_num_cost.ensure(U));
+  if (U) HIP_TRY(hipMemcpy(c->mmi_num_cost.p, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToDevice));
+  if ((rc = accumulate_items(m, c, n_items, 0, max_approx, true, num_mean_acc, num_mean_w, num_var_acc, num_var_w))) return rc;
+  // denominator: the free network
+  if ((rc = bgocc_pass(m, c, b, gmm_kernel, scale, posterior_floor, nullptr, nullptr, true, c->mmi_num_cost.p, &n_items))) return rc;
+  if ((rc = netfb_costs(c, scale, out_den_cost))) return rc;
+  rc = accumulate_items(m, c, n_items, 0, max_approx, true, den_mean_acc, den_mean_w, den_var_acc, den_var_w);
+  c->acc_valid = false;  // (the handle holds one side only: nothing for sr_model_create_from_accumulated)
+  return rc;
   });
 }
 
