@@ -187,7 +187,9 @@ class Corpus {
     frame_offsets_.push_back(0);
     orth_offsets_.push_back(0);
   }
-  void add_segment(const float* feats, size_t n_frames, std::vector<WordIdx> const& orth) {
+  // speaker: the segment's speaker index (the corpus description's `speaker` field, numbered by the caller); sr::SpeakerAdaptation
+  void add_segment(const float* feats, size_t n_frames, std::vector<WordIdx> const& orth, uint32_t speaker = 0) {
+    speakers_.push_back(speaker);
     features_.insert(features_.end(), feats, feats + n_frames * features_per_timeframe_);
     frame_offsets_.push_back(frame_offsets_.back() + n_frames);
     orths_.insert(orths_.end(), orth.begin(), orth.end());
@@ -205,8 +207,10 @@ class Corpus {
   }
   const float* features() const { return features_.data(); }
   const uint64_t* frame_offsets() const { return frame_offsets_.data(); }
+  std::vector<uint32_t> const& speakers() const { return speakers_; }
 
  private:
+  std::vector<uint32_t> speakers_;
   size_t features_per_timeframe_;
   double frame_duration_;
   std::vector<uint64_t> frame_offsets_;
@@ -846,6 +850,98 @@ class Trainer {
   Lexicon const& lexicon_;
   MixtureModel& mixtures_;
   TdpModel tdp_;
+};
+
+// ---- fMLLR speaker adaptation (srgpu.h: sr_fmllr_*, sr_corpus_transform) -------------------------------------------------------
+// One affine feature transform per speaker of the corpus (Corpus::speakers()), estimated by maximum likelihood from the trainer's
+// re-alignment; the model is untouched.  In the reference's flow the adapted features take the place of the corpus' features after
+// FeaturePostProcessor::process_features and before any prepare_sequence.
+class SpeakerAdaptation {
+ public:
+  struct Result {
+    uint32_t n_speakers = 0;
+    std::vector<double> transforms;   // [n_speakers x D x (D+1)] W_s = [A_s b_s], row-major
+    std::vector<double> logdet;       // [n_speakers] log|det A_s|
+    std::vector<double> beta;         // [n_speakers] frames (occupancy) behind each estimate
+    std::vector<int32_t> status;      // [n_speakers] sr_fmllr_estimate's: 0 estimated, 1 too little data (identity), 2 failed (identity)
+    std::vector<double> aux;          // [n_speakers x (n_sweeps + 1)] the auxiliary function after 0 .. n_sweeps sweeps
+    std::vector<float> features;      // the adapted corpus features, the corpus' layout (for a FeatureScorer's prepare_sequence)
+    // the adapted corpus, resident (sr_corpus_transform): what sr_recognize_corpus, sr_align_corpus, ... take in place of an upload
+    // of `features`.  Destroyed with the last copy of the Result, which must not outlive the model.
+    std::shared_ptr<sr_corpus> adapted;
+  };
+
+  SpeakerAdaptation(Trainer& trainer, MixtureModel& mixtures, uint32_t n_sweeps = 10, double min_count = 100.0)
+      : trainer_(trainer), mixtures_(mixtures), n_sweeps_(n_sweeps), min_count_(min_count) {}
+
+  static std::vector<double> identity(size_t dim, uint32_t n_speakers) {
+    std::vector<double> W((size_t)n_speakers * dim * (dim + 1), 0.0);
+    for (uint32_t s = 0; s < n_speakers; s++)
+      for (size_t i = 0; i < dim; i++) W[((size_t)s * dim + i) * (dim + 1) + i] = 1.0;
+    return W;
+  }
+
+  // the estimate alone, from statistics, starting at the identity (host code, no device)
+  static void estimate(size_t dim, std::vector<double> const& beta, std::vector<double> const& k, std::vector<double> const& G,
+                       uint32_t n_sweeps, double min_count, Result& r) {
+    r.n_speakers = (uint32_t)beta.size();
+    r.beta = beta;
+    r.transforms = identity(dim, r.n_speakers);
+    r.logdet.assign(r.n_speakers, 0.0);
+    r.status.assign(r.n_speakers, 0);
+    r.aux.assign((size_t)r.n_speakers * (n_sweeps + 1), 0.0);
+    check(sr_fmllr_estimate((uint32_t)dim, r.n_speakers, beta.data(), k.data(), G.data(), n_sweeps, min_count, r.transforms.data(),
+                            r.aux.data(), r.logdet.data(), r.status.data()));
+  }
+
+  // sr_corpus_transform's loop on the host: acc = b_i, then acc = acc + A_ij * (double) x_j for j ascending, every product rounded
+  // before it is added (the volatile keeps a compiler from fusing the two), (float) acc -- the device's bits
+  static void transform_row(const double* W, size_t D, const float* x, float* y) {
+    for (size_t i = 0; i < D; i++) {
+      double acc = W[i * (D + 1) + D];
+      for (size_t j = 0; j < D; j++) {
+        volatile double p = W[i * (D + 1) + j] * (double)x[j];
+        acc = acc + p;
+      }
+      y[i] = (float)acc;
+    }
+  }
+
+  // re-align, take the statistics of the alignment, estimate, transform
+  Result adapt(Corpus const& corpus) {
+    const size_t n = corpus.get_corpus_size(), D = mixtures_.dimension;
+    const uint64_t F = corpus.get_total_frame_count();
+    std::vector<uint32_t> const& spk = corpus.speakers();
+    uint32_t S = 0;
+    for (uint32_t s : spk) S = std::max(S, s + 1);
+    if (S == 0) throw std::runtime_error("SpeakerAdaptation: empty corpus");
+    std::vector<AlignmentItem> alignment;
+    trainer_.realign(corpus, alignment);
+    std::vector<uint16_t> states(std::max<uint64_t>(F, 1));
+    for (uint64_t t = 0; t < F; t++) states[t] = (uint16_t)alignment[t].state;
+    std::vector<double> beta(S), k((size_t)S * D * (D + 1)), G((size_t)S * D * (D + 1) * (D + 1));
+    sr_corpus* c = nullptr;
+    check(sr_corpus_upload(mixtures_.handle(), corpus.features(), corpus.frame_offsets(), (uint32_t)n, &c));
+    std::shared_ptr<sr_corpus> original(c, sr_corpus_destroy);
+    check(sr_fmllr_statistics_corpus(mixtures_.handle(), c, states.data(), spk.data(), S, mixtures_.max_approx() ? 1 : 0, beta.data(),
+                                     k.data(), G.data()));
+    Result r;
+    estimate(D, beta, k, G, n_sweeps_, min_count_, r);
+    sr_corpus* adapted = nullptr;
+    check(sr_corpus_transform(mixtures_.handle(), c, spk.data(), S, r.transforms.data(), &adapted));
+    r.adapted.reset(adapted, sr_corpus_destroy);
+    r.features.resize((size_t)F * D);
+    for (size_t u = 0; u < n; u++)
+      for (uint64_t t = corpus.frame_offsets()[u]; t < corpus.frame_offsets()[u + 1]; t++)
+        transform_row(r.transforms.data() + (size_t)spk[u] * D * (D + 1), D, corpus.features() + t * D, r.features.data() + t * D);
+    return r;
+  }
+
+ private:
+  Trainer& trainer_;
+  MixtureModel& mixtures_;
+  uint32_t n_sweeps_;
+  double min_count_;
 };
 
 // ---- Teaching::LinearSearch (rwth-asr-0.5/src/Teaching/LinearSearch.hh:9-62, SearchInterface.hh:20-30) -------------

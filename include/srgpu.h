@@ -320,6 +320,57 @@ SR_API int sr_baum_welch_corpus(sr_model* m, sr_corpus* c, const uint16_t* autom
                                 int first_pass, int max_approx, double* out_cost, double* mean_acc, double* mean_w,
                                 double* var_acc, double* var_w);
 
+/* ---- fMLLR speaker adaptation (constrained MLLR, Gales 1998) -----------------------------------------------------------
+ * One affine feature transform W_s = [A_s b_s] (D x (D+1), row-major) per speaker, estimated by maximum likelihood from an
+ * alignment or from posteriors; the model is untouched.  With xi_t = (x_t1 .. x_tD, 1), iv = 1/var and mu of density d, speaker s
+ * collects over the pairs (t, d, gamma) of its utterances (utt_speaker[u] < n_speakers names utterance u's speaker; a speaker's
+ * utterances need not be contiguous), everything in FP64:
+ *   out_beta[s]          = sum gamma
+ *   out_k[s][i][j]       = sum gamma mu_di iv_di xi_tj              (D x (D+1))
+ *   out_G[s][i][j][k]    = sum gamma iv_di xi_tj xi_tk              (D x (D+1) x (D+1): full storage, both triangles written from one
+ *                                                                    sum, exactly symmetric)
+ * sr_fmllr_statistics_corpus takes exactly the pairs sr_accumulate_corpus forms with first_pass = 0 (the arg-min density of
+ * states[t] at weight 1 with max_approx, else the soft memberships with their < 1e-8 drop); sr_fmllr_statistics_bw_corpus exactly
+ * those of sr_baum_welch_corpus (gamma_t(k) x membership, the same floor rule; out_cost[n_utts] = F_u).  A frame's pairs are folded in
+ * pair order into two D-vectors; G and k are then contractions over the speaker's frames on the FP64 matrix cores, the products
+ * xi_tj xi_tk formed in FP64 from the float features.  Determinism: no atomics; a speaker's frames are summed in corpus order, cut
+ * into segments of 1024 frames whose partial sums are added in ascending order; the order does not depend on the launch, so two
+ * identical calls return identical bits.  A speaker without frames gets zeros; statistics of corpus shards add up like
+ * sr_accumulate_corpus'.  Device memory: the three outputs, 2 x 8 bytes per (frame, D+1 rounded up to 16) and 8 bytes per (segment,
+ * that row count, (D+1)(D+2)/2 + D+1 columns each rounded up to 16).
+ * Errors, all before any launch: SR_ELIMIT for a dimension above 63 and for n_speakers * D * (D+1)^2 * 8 bytes beyond a quarter of
+ * the free device memory; SR_EINVAL for utt_speaker[u] >= n_speakers, n_speakers == 0 or a NULL output; otherwise the errors of
+ * sr_accumulate_corpus / sr_baum_welch_corpus. */
+SR_API int sr_fmllr_statistics_corpus(sr_model* m, sr_corpus* c, const uint16_t* states, const uint32_t* utt_speaker,
+                                      uint32_t n_speakers, int max_approx, double* out_beta, double* out_k, double* out_G);
+SR_API int sr_fmllr_statistics_bw_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off,
+                                         const double tdp[3], uint16_t silence_state, int gmm_kernel, double posterior_floor,
+                                         const uint32_t* utt_speaker, uint32_t n_speakers, int max_approx, double* out_cost,
+                                         double* out_beta, double* out_k, double* out_G);
+
+/* The transforms from the statistics; host code, no device.  W[n_speakers x D x (D+1)] is in/out: the estimate starts from the caller's
+ * value (identity [I 0] is the usual start).  Auxiliary function Q(W) = beta log|det A| - 1/2 sum_i (w_i G_i w_i^T - 2 w_i k_i^T).
+ * One sweep updates rows i = 0 .. D-1 in order: with p_i = (row i of the cofactor matrix of the current A, 0),
+ *   w_i = (alpha p_i + k_i) G_i^-1,  alpha a root of alpha^2 (p_i G_i^-1 p_i^T) + alpha (p_i G_i^-1 k_i^T) - beta = 0,
+ * the root with the larger beta log|alpha p_i G_i^-1 p_i^T + p_i G_i^-1 k_i^T| - 1/2 w_i G_i w_i^T + w_i k_i^T; every row update
+ * maximises Q over its row, so Q never falls.  Optional outputs: out_aux[s * (n_sweeps+1) + j] = Q_s after j sweeps (j = 0: the
+ * start), out_logdet[s] = log|det A_s| of the result.  out_status[s]: 0 estimated; 1 beta_s < min_count, W_s left as given; 2 some
+ * G_i not positive definite (its Cholesky factorisation fails) or A singular on the way, W_s restored to the value given.  With
+ * status 1 or 2 out_aux holds Q of the W given at every j (NaN where it has none) and out_logdet its log|det A|.
+ * SR_EINVAL for dim == 0, a NULL input or out_status, min_count negative or NaN, n_sweeps == 0. */
+SR_API int sr_fmllr_estimate(uint32_t dim, uint32_t n_speakers, const double* beta, const double* k, const double* G,
+                             uint32_t n_sweeps, double min_count, double* W, double* out_aux, double* out_logdet,
+                             int32_t* out_status);
+
+/* The adapted corpus: a new resident corpus with c's frame offsets whose row t is (float) acc_i, acc_i starting at b_i and taking
+ * acc_i = acc_i + A_ij * (double) x_tj for j ascending, no fused multiply-add (the order of operations is the specification: a loop
+ * over j in FP64 reproduces it bit for bit), with [A b] = W[utt_speaker[u]] of t's utterance.  `c` stays valid (an asynchronous
+ * upload of it is waited for first); *out belongs to the same model, is accepted by every entry point that takes a corpus and is
+ * destroyed with sr_corpus_destroy like any other: it allocates its own buffers rather than adopting the ones the model parked from
+ * its last destroyed corpus, and parks its own on destruction.  SR_EINVAL / SR_ELIMIT as for the statistics (W NULL: SR_EINVAL). */
+SR_API int sr_corpus_transform(sr_model* m, sr_corpus* c, const uint32_t* utt_speaker, uint32_t n_speakers, const double* W,
+                               sr_corpus** out);
+
 /* ---- word posteriors and confidences: forward-backward over the recognition network --------------------------------
  * The network sr_recognize_corpus searches (Recognizer.cpp:103-232: the start hypothesis at word 0 position 0, in-word 0-1-2 jumps
  * with the penalty keyed on the DESTINATION state, every word end entering every word at position 0 or 1 with the word penalty --
@@ -675,7 +726,7 @@ typedef struct {
   double gmm_flops;     /* algorithmic: 4 * dim * densities * frames per launch, summed */
   double search_ms;     /* Viterbi decode / align kernels */
   uint64_t search_launches;
-  double search_bytes;  /* algorithmic: (8*S + 4*P) * frames (decode) / (8+1)*N * frames (align) / 32*N * frames (forward-backward; N = P over a network) / (30*W + 48) * frames (word lattice) / (44*P + 120*W) * frames (bigram word lattice: rows of both walks, word-end tables out and in) / bigram MMI passes: 24*N * frames for a chain's forward-backward, 32*P * frames for the free network's, + 16*N (8*P: the count pass is in the 32) * frames for the two item passes' reads of gamma */
+  double search_bytes;  /* algorithmic: (8*S + 4*P) * frames (decode) / (8+1)*N * frames (align) / 32*N * frames (forward-backward; N = P over a network) / (30*W + 48) * frames (word lattice) / (44*P + 120*W) * frames (bigram word lattice: rows of both walks, word-end tables out and in) / bigram MMI passes: 24*N * frames for a chain's forward-backward, 32*P * frames for the free network's, + 16*N (8*P: the count pass is in the 32) * frames for the two item passes' reads of gamma / fMLLR statistics: (32*R + 4*D) * frames + 16*R*C * segments (R = D+1 rounded up to 16 rows of the two folds out and in, C columns of a segment's partial sums out and in) / 8*D * frames (sr_corpus_transform: a row in, a row out) */
   uint64_t frames;      /* frames processed */
   uint64_t refined_pairs;      /* SR_GMM_PREFILTER: (frame, state) pairs scored ... */
   uint64_t refined_densities;  /* ... and densities the FP64 stage had to evaluate for them (>= 1 per pair) */

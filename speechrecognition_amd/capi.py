@@ -33,6 +33,7 @@ SYMBOLS = [
     "sr_state_posteriors_corpus", "sr_baum_welch_corpus", "sr_word_posteriors_corpus", "sr_recognize_confidence_corpus",
     "sr_net_occupancies_corpus", "sr_mmi_statistics_corpus", "sr_model_create_from_mmi_statistics",
     "sr_word_lattice_corpus", "sr_lattice_nbest",
+    "sr_fmllr_statistics_corpus", "sr_fmllr_statistics_bw_corpus", "sr_fmllr_estimate", "sr_corpus_transform",
     "sr_bigram_create", "sr_bigram_destroy", "sr_bigram_describe", "sr_recognize_bigram_corpus",
     "sr_bigram_word_posteriors_corpus", "sr_recognize_bigram_confidence_corpus",
     "sr_bigram_occupancies_corpus", "sr_bigram_mmi_statistics_corpus",
@@ -113,6 +114,10 @@ def lib():
         L.sr_accumulate_corpus.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
         L.sr_state_posteriors_corpus.argtypes = [vp, vp, vp, vp, C.POINTER(dbl * 3), C.c_uint16, i32, dbl, u32, vp, vp, vp, vp]
         L.sr_baum_welch_corpus.argtypes = [vp, vp, vp, vp, C.POINTER(dbl * 3), C.c_uint16, i32, dbl, i32, i32, vp, vp, vp, vp, vp]
+        L.sr_fmllr_statistics_corpus.argtypes = [vp, vp, vp, vp, u32, i32, vp, vp, vp]
+        L.sr_fmllr_statistics_bw_corpus.argtypes = [vp, vp, vp, vp, C.POINTER(dbl * 3), C.c_uint16, i32, dbl, vp, u32, i32, vp, vp, vp, vp]
+        L.sr_fmllr_estimate.argtypes = [u32, u32, vp, vp, vp, u32, dbl, vp, vp, vp, vp]
+        L.sr_corpus_transform.argtypes = [vp, vp, vp, u32, vp, C.POINTER(vp)]
         L.sr_word_posteriors_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, vp]
         L.sr_recognize_confidence_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, vp, vp, vp, vp, vp]
         L.sr_net_occupancies_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, vp, vp, vp]
@@ -554,6 +559,45 @@ class Corpus:
         """The same, the statistics kept in this corpus handle for next_model() -> cost f64[n_utts]."""
         return self._baum_welch(automata, tdp, silence_state, kernel, floor, first_pass, max_approx, (None, None, None, None))
 
+    def _fmllr_out(self, n_speakers):
+        D = self.model.dim
+        return np.zeros(n_speakers), np.zeros((n_speakers, D, D + 1)), np.zeros((n_speakers, D, D + 1, D + 1))
+
+    def fmllr_statistics(self, states, utt_speaker, n_speakers, max_approx=True):
+        """fMLLR statistics of an alignment per speaker (sr_fmllr_statistics_corpus) -> (beta f64[S], k f64[S, D, D+1],
+        G f64[S, D, D+1, D+1])."""
+        states = np.ascontiguousarray(states, dtype=np.uint16)
+        spk = np.ascontiguousarray(utt_speaker, dtype=np.uint32)
+        assert len(spk) == self.n_utts
+        beta, k, G = self._fmllr_out(n_speakers)
+        _check(lib().sr_fmllr_statistics_corpus(self.model.h, self.h, _ptr(states), _ptr(spk), n_speakers, int(max_approx), _ptr(beta),
+                                                _ptr(k), _ptr(G)))
+        return beta, k, G
+
+    def fmllr_statistics_bw(self, automata, tdp, silence_state, utt_speaker, n_speakers, kernel=GMM_DEFAULT, floor=0.0, max_approx=True):
+        """The same from the forward-backward posteriors (sr_fmllr_statistics_bw_corpus) -> (cost f64[n_utts], (beta, k, G))."""
+        flat, off = self._aut(automata)
+        spk = np.ascontiguousarray(utt_speaker, dtype=np.uint32)
+        assert len(spk) == self.n_utts
+        cost = np.zeros(max(self.n_utts, 1), dtype=np.float64)
+        t3 = (C.c_double * 3)(*tdp)
+        beta, k, G = self._fmllr_out(n_speakers)
+        _check(lib().sr_fmllr_statistics_bw_corpus(self.model.h, self.h, _ptr(flat), _ptr(off), C.byref(t3), silence_state, kernel, float(floor),
+                                                   _ptr(spk), n_speakers, int(max_approx), _ptr(cost), _ptr(beta), _ptr(k), _ptr(G)))
+        return cost[: self.n_utts], (beta, k, G)
+
+    def transform(self, utt_speaker, W):
+        """The adapted corpus y = A x + b, W[s] = [A b] of utterance u's speaker utt_speaker[u] (sr_corpus_transform) -> Corpus."""
+        spk = np.ascontiguousarray(utt_speaker, dtype=np.uint32)
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        D = self.model.dim
+        assert len(spk) == self.n_utts and W.ndim == 3 and W.shape[1:] == (D, D + 1)
+        out = Corpus.__new__(Corpus)
+        out.model, out.frame_off, out.n_utts, out.n_frames = self.model, self.frame_off, self.n_utts, self.n_frames
+        out.h = C.c_void_p()
+        _check(lib().sr_corpus_transform(self.model.h, self.h, _ptr(spk), W.shape[0], _ptr(W), C.byref(out.h)))
+        return out
+
     def word_posteriors(self, lexicon, word_penalty, scale=1.0, kernel=GMM_PREFILTER, floor=0.0, max_items=8):
         """Forward-backward over the recognition network (sr_word_posteriors_corpus) -> (cost f64[n_utts] = -(1/scale) log P(X),
         count u16[total_frames], word u32[total_frames, max_items], weight f64[total_frames, max_items]): per frame the words with
@@ -757,6 +801,25 @@ class Lexicon:
         if self.h:
             lib().sr_lexicon_destroy(self.h)
             self.h = None
+
+
+def fmllr_estimate(beta, k, G, n_sweeps=10, min_count=0.0, W=None):
+    """Row-by-row fMLLR estimate per speaker (sr_fmllr_estimate; host code) from W (default: identity) -> (W f64[S, D, D+1],
+    aux f64[S, n_sweeps+1] = Q after 0 .. n_sweeps sweeps, logdet f64[S], status i32[S])."""
+    beta = np.ascontiguousarray(beta, dtype=np.float64)
+    k = np.ascontiguousarray(k, dtype=np.float64)
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    S, D = k.shape[0], k.shape[1]
+    assert beta.shape == (S,) and k.shape == (S, D, D + 1) and G.shape == (S, D, D + 1, D + 1)
+    if W is None:
+        W = np.tile(np.hstack([np.eye(D), np.zeros((D, 1))]), (S, 1, 1))
+    W = np.array(W, dtype=np.float64, order="C")
+    aux = np.zeros((S, int(n_sweeps) + 1))
+    logdet = np.zeros(S)
+    status = np.zeros(S, dtype=np.int32)
+    _check(lib().sr_fmllr_estimate(D, S, _ptr(beta), _ptr(k), _ptr(G), int(n_sweeps), float(min_count), _ptr(W), _ptr(aux), _ptr(logdet),
+                                   _ptr(status)))
+    return W, aux, logdet, status
 
 
 def traceback_words(tb_word, tb_bkp, silence_word, n_words):

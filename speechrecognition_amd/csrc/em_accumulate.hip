@@ -73,6 +73,7 @@ __global__ __launch_bounds__(kAssignThreads) void em_assign_kernel(EmArgs a) {
     a.pair_w[p0] = 1.0;
     a.key_mean[p0] = any ? a.dens_mean[arg] : 0xFFFFFFFFu;
     a.key_var[p0] = any ? a.dens_var[arg] : 0xFFFFFFFFu;
+    if (a.pair_dens) a.pair_dens[p0] = arg;
     return;
   }
   double sum = 0.0;  // soft memberships: std::accumulate from 0.0 in density order (:320-321)
@@ -89,6 +90,7 @@ __global__ __launch_bounds__(kAssignThreads) void em_assign_kernel(EmArgs a) {
     a.pair_w[i] = p;
     a.key_mean[i] = keep ? a.dens_mean[c] : 0xFFFFFFFFu;
     a.key_var[i] = keep ? a.dens_var[c] : 0xFFFFFFFFu;
+    if (a.pair_dens) a.pair_dens[i] = c;
   }
 }
 
@@ -224,13 +226,18 @@ static hipError_t sort_and_sum(const EmArgs& a, void* sort_temp, size_t sort_tem
   return hipGetLastError();
 }
 
+hipError_t launch_em_pairs(const EmArgs& a, hipStream_t stream) {
+  if (a.n_frames == 0 || a.n_pairs == 0) return hipSuccess;
+  hipLaunchKernelGGL(em_assign_kernel, dim3((unsigned)((a.n_frames + kAssignThreads - 1) / kAssignThreads)), dim3(kAssignThreads), 0,
+                     stream, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_em_accumulate(const EmArgs& a, void* sort_temp, size_t sort_temp_bytes, uint32_t* iota, uint32_t* keys_sorted,
                                 uint32_t* pairs_sorted, uint32_t* row_begin, double* mean_acc, double* mean_w, double* var_acc, double* var_w,
                                 hipStream_t stream) {
   if (a.n_frames == 0 || a.n_pairs == 0) return hipSuccess;
-  hipLaunchKernelGGL(em_assign_kernel, dim3((unsigned)((a.n_frames + kAssignThreads - 1) / kAssignThreads)), dim3(kAssignThreads), 0,
-                     stream, a);
-  hipError_t e = hipGetLastError();
+  hipError_t e = launch_em_pairs(a, stream);
   if (e != hipSuccess) return e;
   return sort_and_sum(a, sort_temp, sort_temp_bytes, iota, keys_sorted, pairs_sorted, row_begin, mean_acc, mean_w, var_acc, var_w, stream);
 }
@@ -270,6 +277,7 @@ __global__ __launch_bounds__(kAssignThreads) void em_assign_weighted_kernel(EmAr
     a.pair_w[p0] = g;
     a.key_mean[p0] = any ? a.dens_mean[arg] : 0xFFFFFFFFu;
     a.key_var[p0] = any ? a.dens_var[arg] : 0xFFFFFFFFu;
+    if (a.pair_dens) a.pair_dens[p0] = arg;
     return;
   }
   double sum = 0.0;
@@ -286,6 +294,7 @@ __global__ __launch_bounds__(kAssignThreads) void em_assign_weighted_kernel(EmAr
     a.pair_w[j] = g * p;
     a.key_mean[j] = keep ? a.dens_mean[c] : 0xFFFFFFFFu;
     a.key_var[j] = keep ? a.dens_var[c] : 0xFFFFFFFFu;
+    if (a.pair_dens) a.pair_dens[j] = c;
   }
 }
 
@@ -308,12 +317,19 @@ hipError_t launch_em_item_pairs(const EmArgs& a, void* scan_temp, size_t scan_te
   return hipcub::DeviceScan::InclusiveSum(scan_temp, scan_temp_bytes, cnt, a.item_pair_end, (int)a.n_items, stream);
 }
 
+hipError_t launch_em_pairs_weighted(const EmArgs& a, hipStream_t stream) {
+  if (a.n_items == 0 || a.n_pairs == 0) return hipSuccess;
+  hipLaunchKernelGGL(em_assign_weighted_kernel, dim3((unsigned)((a.n_items + kAssignThreads - 1) / kAssignThreads)), dim3(kAssignThreads),
+                     0, stream, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_em_accumulate_weighted(const EmArgs& a, void* sort_temp, size_t sort_temp_bytes, uint32_t* iota, uint32_t* keys_sorted,
                                          uint32_t* pairs_sorted, uint32_t* row_begin, double* mean_acc, double* mean_w, double* var_acc,
                                          double* var_w, hipStream_t stream) {
   if (a.n_items == 0 || a.n_pairs == 0) return hipSuccess;
-  hipLaunchKernelGGL(em_assign_weighted_kernel, dim3((unsigned)((a.n_items + kAssignThreads - 1) / kAssignThreads)), dim3(kAssignThreads),
-                     0, stream, a);
+  hipError_t e0 = launch_em_pairs_weighted(a, stream);
+  if (e0 != hipSuccess) return e0;
   hipLaunchKernelGGL(em_iota_kernel, dim3((unsigned)((a.n_pairs + 255) / 256)), dim3(256), 0, stream, iota, a.n_pairs);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;

@@ -197,6 +197,11 @@ struct sr_corpus {
   DevBuf<double> bglat_fwd, bglat_bwd;
   DevBuf<uint16_t> bglat_first, bglat_row_first;
   DevBuf<uint32_t> bglat_pred, bglat_arg, bglat_row_pred, bglat_arc_hist, bglat_arc_pred;
+  // fMLLR statistics (fmllr_stats.hip; the pairs are the EM workspace above): the pairs' densities, the per-frame folds, the speakers'
+  // frame lists and segments, the segments' partial sums, the results
+  DevBuf<uint32_t> fm_pair_dens, fm_frame_list, fm_seg_begin, fm_seg_len, fm_spk_seg_off;
+  DevBuf<uint64_t> fm_frame_pair_off;
+  DevBuf<double> fm_fold_a, fm_fold_c, fm_partial, fm_beta, fm_k, fm_G;
 };
 
 struct sr_lexicon {

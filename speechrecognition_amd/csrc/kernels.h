@@ -657,6 +657,7 @@ struct EmArgs {
   uint32_t n_mean, n_var;
   int first_pass, max_approx;
   uint32_t* pair_frame; double* pair_w; uint32_t* key_mean; uint32_t* key_var;  // [n_pairs] workspace
+  uint32_t* pair_dens;         // optional [n_pairs]: the density of each pair (fMLLR statistics; a dropped pair's keys are 0xFFFFFFFF)
   // posterior-weighted pairs (Baum-Welch): item i = (item_frame[i], mixture item_mix[i], gamma item_w[i]); its pairs end at item_pair_end[i]
   uint64_t n_items;
   const uint32_t* item_frame; const uint16_t* item_mix; const double* item_w;
@@ -668,6 +669,9 @@ hipError_t launch_path_scores_direct(const EmArgs& a, double* out, hipStream_t s
 hipError_t launch_em_accumulate(const EmArgs& a, void* sort_temp, size_t sort_temp_bytes, uint32_t* iota, uint32_t* keys_sorted,
                                 uint32_t* pairs_sorted, uint32_t* row_begin /* [max(n_mean, n_var) + 1] */, double* mean_acc,
                                 double* mean_w, double* var_acc, double* var_w, hipStream_t stream);
+// step 1 alone: the (frame, density, weight) pairs into a.pair_* / key_* (launch_em_accumulate's / launch_em_accumulate_weighted's)
+hipError_t launch_em_pairs(const EmArgs& a, hipStream_t stream);
+hipError_t launch_em_pairs_weighted(const EmArgs& a, hipStream_t stream);
 // Baum-Welch: pair counts of the items, then their inclusive device scan into a.item_pair_end (scan_temp from em_item_scan_temp_bytes) ...
 size_t em_item_scan_temp_bytes(uint64_t n_items);
 hipError_t launch_em_item_pairs(const EmArgs& a, void* scan_temp, size_t scan_temp_bytes, uint64_t* cnt, hipStream_t stream);
@@ -675,5 +679,36 @@ hipError_t launch_em_item_pairs(const EmArgs& a, void* scan_temp, size_t scan_te
 hipError_t launch_em_accumulate_weighted(const EmArgs& a, void* sort_temp, size_t sort_temp_bytes, uint32_t* iota, uint32_t* keys_sorted,
                                          uint32_t* pairs_sorted, uint32_t* row_begin, double* mean_acc, double* mean_w, double* var_acc,
                                          double* var_w, hipStream_t stream);
+
+// ---- fMLLR: per-speaker statistics of a set of pairs, the adapted corpus (fmllr_stats.hip) --------------------------------------------
+// The contraction's shape for a dimension: rows = D + 1 padded to 16 (row D of the k block is beta); columns = the (D+1)(D+2)/2 pairs
+// j <= k of G padded to 16, then the D + 1 columns of k padded to 16.
+struct FmllrShape { uint32_t rows, g_cols, g_tiles, k_tiles, cols; };
+FmllrShape fmllr_shape(uint32_t dim);
+uint32_t fmllr_seg_frames();   // frames per segment: the unit of the fixed summation order
+uint32_t fmllr_max_dim();
+struct FmllrArgs {
+  const float* feats;
+  uint64_t n_frames;
+  uint32_t dim;
+  FmllrShape shape;
+  const double* means; const double* inv_vars;  // [C x dim] per density
+  // the pairs, in frame order: frame t's are [frame_pair_off[t], frame_pair_off[t + 1])
+  const uint64_t* frame_pair_off;  // [n_frames + 1]
+  const uint32_t* pair_dens; const uint32_t* pair_key; const double* pair_w;  // key 0xFFFFFFFF: dropped
+  double *fold_a, *fold_c;         // workspace [n_frames x rows]
+  // speakers: frame_list = every speaker's frames in corpus order, speaker after speaker; segment g = frame_list[seg_begin[g] ..
+  // + seg_len[g]) (at most fmllr_seg_frames()), speaker s owns segments [spk_seg_off[s], spk_seg_off[s + 1])
+  uint32_t n_speakers, n_segs;
+  const uint32_t* frame_list; const uint32_t* seg_begin; const uint32_t* seg_len; const uint32_t* spk_seg_off;
+  double* partial;                 // workspace [n_segs][rows][cols]
+  double *out_beta, *out_k, *out_G;  // device: [S], [S x D x (D+1)], [S x D x (D+1) x (D+1)]
+};
+hipError_t launch_fmllr_item_frames(const uint32_t* item_off, const uint64_t* item_pair_end, uint64_t n_frames, uint64_t* frame_pair_off,
+                                    hipStream_t stream);
+hipError_t launch_fmllr_statistics(const FmllrArgs& a, hipStream_t stream);  // fold, contraction, reduction
+// out[t][i] = (float)(W_s[i][D] + sum_j W_s[i][j] (double) feats[t][j]), j ascending, s = utt_speaker[utterance of t]
+hipError_t launch_fmllr_transform(const float* feats, const uint64_t* frame_off, uint32_t n_utts, const uint32_t* utt_speaker, const double* W,
+                                  uint32_t dim, float* out, hipStream_t stream);
 
 }  // namespace srgpu

@@ -1669,6 +1669,42 @@ int sr_model_tying_info(const sr_model* m, uint32_t* n_mean, uint32_t* n_var) {
   });
 }
 
+// The (frame, density, weight) pairs of an alignment (em_assign_kernel): checks the states, sizes and uploads what the assignment reads
+// and fills `*out` with everything but the accumulators' side (sort workspace, rows); *pair_off_out = the F + 1 pair offsets it uploads
+// (the last one is the pair count, which the fMLLR fold reads as the end of the last frame's pairs).  No pair at all: SR_EINVAL.
+static int alignment_pairs(sr_model* m, sr_corpus* c, const uint16_t* states, int first_pass, int max_approx, EmArgs* out,
+                           std::vector<uint64_t>* pair_off_out) {
+  const uint64_t F = c->n_frames;
+  const uint32_t D = m->dim;
+  int rc;
+  if (!states) return fail(SR_EINVAL, "states is null");
+  const bool soft = !first_pass && !max_approx;
+  std::vector<uint64_t>& pair_off = *pair_off_out;
+  pair_off.assign(F + 1, 0);
+  uint64_t n_pairs = 0;
+  for (uint64_t f = 0; f < F; f++) {
+    if (states[f] >= m->n_states) return fail(SR_EINVAL, "frame %llu: state %u >= n_states", (unsigned long long)f, states[f]);
+    pair_off[f] = n_pairs;
+    n_pairs += soft ? (m->h_dens_off[states[f] + 1] - m->h_dens_off[states[f]]) : 1;
+  }
+  pair_off[F] = n_pairs;
+  if (n_pairs >= (1ull << 31)) return fail(SR_ELIMIT, "too many (frame, density) pairs");
+  if (n_pairs == 0) return fail(SR_EINVAL, "no (frame, density) pairs to accumulate");
+  if ((rc = srhost::corpus_ready(c, 0, F, m->s_gmm))) return rc;
+  HIP_TRY(c->out_states.upload(states, F));
+  HIP_TRY(c->pair_off.upload(pair_off.data(), F + 1));
+  HIP_TRY(c->pair_frame.ensure(n_pairs)); HIP_TRY(c->key_mean.ensure(n_pairs)); HIP_TRY(c->key_var.ensure(n_pairs));
+  HIP_TRY(c->pair_w.ensure(n_pairs));
+  EmArgs a{};
+  a.feats = c->feats.p; a.n_frames = F; a.n_pairs = n_pairs; a.dim = D; a.states = c->out_states.p; a.pair_off = c->pair_off.p;
+  a.dens_off = m->dens_off.p; a.means = m->means.p; a.inv_vars = m->inv_vars.p; a.norm = m->norm.p; a.logw = m->logw.p;
+  a.dens_mean = m->dens_mean.p; a.dens_var = m->dens_var.p; a.n_mean = m->n_mean; a.n_var = m->n_var;
+  a.first_pass = first_pass; a.max_approx = max_approx;
+  a.pair_frame = c->pair_frame.p; a.pair_w = c->pair_w.p; a.key_mean = c->key_mean.p; a.key_var = c->key_var.p;
+  *out = a;
+  return SR_OK;
+}
+
 int sr_accumulate_corpus(sr_model* m, sr_corpus* c, const uint16_t* states, int first_pass, int max_approx, double* mean_acc,
                          double* mean_w, double* var_acc, double* var_w) {
   return guarded(__func__, [&]() -> int {
@@ -1688,22 +1724,11 @@ int sr_accumulate_corpus(sr_model* m, sr_corpus* c, const uint16_t* states, int 
     }
     return to_host ? SR_OK : fail(SR_EINVAL, "empty corpus: nothing to keep on the device");
   }
-  if (!states) return fail(SR_EINVAL, "states is null");
-  const bool soft = !first_pass && !max_approx;
-  std::vector<uint64_t> pair_off(F);
-  uint64_t n_pairs = 0;
-  for (uint64_t f = 0; f < F; f++) {
-    if (states[f] >= m->n_states) return fail(SR_EINVAL, "frame %llu: state %u >= n_states", (unsigned long long)f, states[f]);
-    pair_off[f] = n_pairs;
-    n_pairs += soft ? (m->h_dens_off[states[f] + 1] - m->h_dens_off[states[f]]) : 1;
-  }
-  if (n_pairs >= (1ull << 31)) return fail(SR_ELIMIT, "too many (frame, density) pairs");
-  if (n_pairs == 0) return fail(SR_EINVAL, "no (frame, density) pairs to accumulate");
-  if ((rc = srhost::corpus_ready(c, 0, F, m->s_gmm))) return rc;
-  HIP_TRY(c->out_states.upload(states, F));
-  HIP_TRY(c->pair_off.upload(pair_off.data(), F));
-  HIP_TRY(c->pair_frame.ensure(n_pairs)); HIP_TRY(c->key_mean.ensure(n_pairs)); HIP_TRY(c->key_var.ensure(n_pairs));
-  HIP_TRY(c->pair_w.ensure(n_pairs)); HIP_TRY(c->keys_sorted.ensure(n_pairs)); HIP_TRY(c->pairs_sorted.ensure(n_pairs));
+  EmArgs a{};
+  std::vector<uint64_t> pair_off;
+  if ((rc = alignment_pairs(m, c, states, first_pass, max_approx, &a, &pair_off))) return rc;
+  const uint64_t n_pairs = a.n_pairs;
+  HIP_TRY(c->keys_sorted.ensure(n_pairs)); HIP_TRY(c->pairs_sorted.ensure(n_pairs));
   {
     std::vector<uint32_t> iota(n_pairs);
     std::iota(iota.begin(), iota.end(), 0u);
@@ -1714,12 +1739,6 @@ int sr_accumulate_corpus(sr_model* m, sr_corpus* c, const uint16_t* states, int 
   HIP_TRY(c->row_begin.ensure((size_t)std::max(m->n_mean, m->n_var) + 1));
   HIP_TRY(c->acc_mean.ensure((size_t)m->n_mean * D)); HIP_TRY(c->w_mean.ensure(m->n_mean));
   HIP_TRY(c->acc_var.ensure((size_t)m->n_var * D)); HIP_TRY(c->w_var.ensure(m->n_var));
-  EmArgs a{};
-  a.feats = c->feats.p; a.n_frames = F; a.n_pairs = n_pairs; a.dim = D; a.states = c->out_states.p; a.pair_off = c->pair_off.p;
-  a.dens_off = m->dens_off.p; a.means = m->means.p; a.inv_vars = m->inv_vars.p; a.norm = m->norm.p; a.logw = m->logw.p;
-  a.dens_mean = m->dens_mean.p; a.dens_var = m->dens_var.p; a.n_mean = m->n_mean; a.n_var = m->n_var;
-  a.first_pass = first_pass; a.max_approx = max_approx;
-  a.pair_frame = c->pair_frame.p; a.pair_w = c->pair_w.p; a.key_mean = c->key_mean.p; a.key_var = c->key_var.p;
   EventPair ep{};
   if ((rc = prof_begin(m, m->s_gmm, 1, &ep))) return rc;
   HIP_TRY(launch_em_accumulate(a, c->sort_temp.p, temp, c->iota.p, c->keys_sorted.p, c->pairs_sorted.p, c->row_begin.p, c->acc_mean.p, c->w_mean.p,
@@ -1904,14 +1923,11 @@ int sr_state_posteriors_corpus(sr_model* m, sr_corpus* c, const uint16_t* automa
   });
 }
 
-// The posterior-weighted statistics of the n_items items a pass left in c->fb_item_* (fb_pass, occ_pass), in c->acc_* and -- to_host --
-// the four arrays.
-static int accumulate_items(sr_model* m, sr_corpus* c, uint64_t n_items, int first_pass, int max_approx, bool to_host, double* mean_acc,
-                            double* mean_w, double* var_acc, double* var_w) {
-  const uint32_t D = m->dim;
-  int rc;
+// The pairs of the n_items items a pass left in c->fb_item_* (fb_pass, occ_pass; em_assign_weighted_kernel): counts them, sizes what
+// the assignment writes and fills `a` with everything but the accumulators' side.  a->n_pairs = 0: nothing above the floor.
+static int item_pairs(sr_model* m, sr_corpus* c, uint64_t n_items, int first_pass, int max_approx, EmArgs* out) {
   EmArgs a{};
-  a.feats = c->feats.p; a.n_frames = c->n_frames; a.dim = D;
+  a.feats = c->feats.p; a.n_frames = c->n_frames; a.dim = m->dim;
   a.dens_off = m->dens_off.p; a.means = m->means.p; a.inv_vars = m->inv_vars.p; a.norm = m->norm.p; a.logw = m->logw.p;
   a.dens_mean = m->dens_mean.p; a.dens_var = m->dens_var.p; a.n_mean = m->n_mean; a.n_var = m->n_var;
   a.first_pass = first_pass; a.max_approx = max_approx;
@@ -1928,6 +1944,25 @@ static int accumulate_items(sr_model* m, sr_corpus* c, uint64_t n_items, int fir
     HIP_TRY(hipMemcpy(&n_pairs, c->fb_pair_end.p + (n_items - 1), sizeof(uint64_t), hipMemcpyDeviceToHost));
   }
   if (n_pairs >= (1ull << 31)) return fail(SR_ELIMIT, "too many (frame, density) pairs");
+  a.n_pairs = n_pairs;
+  if (n_pairs) {
+    HIP_TRY(c->pair_frame.ensure(n_pairs)); HIP_TRY(c->key_mean.ensure(n_pairs)); HIP_TRY(c->key_var.ensure(n_pairs));
+    HIP_TRY(c->pair_w.ensure(n_pairs));
+    a.pair_frame = c->pair_frame.p; a.pair_w = c->pair_w.p; a.key_mean = c->key_mean.p; a.key_var = c->key_var.p;
+  }
+  *out = a;
+  return SR_OK;
+}
+
+// The posterior-weighted statistics of the n_items items a pass left in c->fb_item_* (fb_pass, occ_pass), in c->acc_* and -- to_host --
+// the four arrays.
+static int accumulate_items(sr_model* m, sr_corpus* c, uint64_t n_items, int first_pass, int max_approx, bool to_host, double* mean_acc,
+                            double* mean_w, double* var_acc, double* var_w) {
+  const uint32_t D = m->dim;
+  int rc;
+  EmArgs a{};
+  if ((rc = item_pairs(m, c, n_items, first_pass, max_approx, &a))) return rc;
+  const uint64_t n_pairs = a.n_pairs;
   if (n_pairs == 0) {  // nothing above the floor: reset_accumulators()
     if (to_host) {
       std::fill(mean_acc, mean_acc + (size_t)m->n_mean * D, 0.0);
@@ -1937,16 +1972,13 @@ static int accumulate_items(sr_model* m, sr_corpus* c, uint64_t n_items, int fir
     }
     return to_host ? SR_OK : fail(SR_EINVAL, "no posterior above the floor: nothing to keep on the device");
   }
-  a.n_pairs = n_pairs;
-  HIP_TRY(c->pair_frame.ensure(n_pairs)); HIP_TRY(c->key_mean.ensure(n_pairs)); HIP_TRY(c->key_var.ensure(n_pairs));
-  HIP_TRY(c->pair_w.ensure(n_pairs)); HIP_TRY(c->keys_sorted.ensure(n_pairs)); HIP_TRY(c->pairs_sorted.ensure(n_pairs));
+  HIP_TRY(c->keys_sorted.ensure(n_pairs)); HIP_TRY(c->pairs_sorted.ensure(n_pairs));
   HIP_TRY(c->iota.ensure(n_pairs));
   const size_t temp = em_sort_temp_bytes(n_pairs);
   HIP_TRY(c->sort_temp.ensure(temp));
   HIP_TRY(c->row_begin.ensure((size_t)std::max(m->n_mean, m->n_var) + 1));
   HIP_TRY(c->acc_mean.ensure((size_t)m->n_mean * D)); HIP_TRY(c->w_mean.ensure(m->n_mean));
   HIP_TRY(c->acc_var.ensure((size_t)m->n_var * D)); HIP_TRY(c->w_var.ensure(m->n_var));
-  a.pair_frame = c->pair_frame.p; a.pair_w = c->pair_w.p; a.key_mean = c->key_mean.p; a.key_var = c->key_var.p;
   EventPair ep{};
   if ((rc = prof_begin(m, m->s_gmm, 1, &ep))) return rc;
   HIP_TRY(launch_em_accumulate_weighted(a, c->sort_temp.p, temp, c->iota.p, c->keys_sorted.p, c->pairs_sorted.p, c->row_begin.p,
@@ -1977,6 +2009,168 @@ int sr_baum_welch_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, co
   if ((rc = fb_pass(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, true, &n_items))) return rc;
   if (U) HIP_TRY(hipMemcpy(out_cost, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToHost));
   return accumulate_items(m, c, n_items, first_pass, max_approx, to_host, mean_acc, mean_w, var_acc, var_w);
+  });
+}
+
+// ---- fMLLR speaker adaptation (fmllr_stats.hip; the estimate itself is host code, fmllr.cpp) ---------------------------------------
+// The checks every statistics call makes before any launch
+static int fmllr_check(sr_model* m, sr_corpus* c, const uint32_t* utt_speaker, uint32_t n_speakers, const double* out_beta,
+                       const double* out_k, const double* out_G) {
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  if (!out_beta || !out_k || !out_G) return fail(SR_EINVAL, "null output");
+  if (n_speakers == 0) return fail(SR_EINVAL, "n_speakers is 0");
+  if (!utt_speaker && c->n_utts) return fail(SR_EINVAL, "utt_speaker is null");
+  for (uint32_t u = 0; u < c->n_utts; u++)
+    if (utt_speaker[u] >= n_speakers) return fail(SR_EINVAL, "utterance %u: speaker %u >= n_speakers %u", u, utt_speaker[u], n_speakers);
+  const uint32_t D = m->dim;
+  if (D > fmllr_max_dim()) return fail(SR_ELIMIT, "dimension %u exceeds %u (fMLLR statistics)", D, fmllr_max_dim());
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  const double g_bytes = 8.0 * (double)n_speakers * D * (D + 1) * (D + 1);
+  if (g_bytes > (double)free_b / 4)
+    return fail(SR_ELIMIT, "G of %u speakers (%.0f bytes) exceeds a quarter of the free device memory (%llu bytes)", n_speakers, g_bytes,
+                (unsigned long long)free_b);
+  return SR_OK;
+}
+
+// fold, contraction and reduction over the pairs `e` describes (formed already: frame t's at [pair_off[t], pair_off[t + 1])), per
+// speaker; the results to the host
+static int fmllr_statistics(sr_model* m, sr_corpus* c, const EmArgs& e, const uint64_t* d_frame_pair_off, const uint32_t* utt_speaker,
+                            uint32_t S, double* out_beta, double* out_k, double* out_G) {
+  const uint32_t D = m->dim, U = c->n_utts, E = D + 1;
+  const uint64_t F = c->n_frames;
+  int rc;
+  // every speaker's frames in corpus order, cut into segments
+  std::vector<uint32_t> spk_frames(S + 1, 0), frame_list(F), seg_begin, seg_len, spk_seg_off(S + 1, 0);
+  for (uint32_t u = 0; u < U; u++) spk_frames[utt_speaker[u] + 1] += (uint32_t)(c->frame_off[u + 1] - c->frame_off[u]);
+  for (uint32_t s = 0; s < S; s++) spk_frames[s + 1] += spk_frames[s];
+  {
+    std::vector<uint32_t> fill(spk_frames.begin(), spk_frames.end() - 1);
+    for (uint32_t u = 0; u < U; u++)
+      for (uint64_t f = c->frame_off[u]; f < c->frame_off[u + 1]; f++) frame_list[fill[utt_speaker[u]]++] = (uint32_t)f;
+  }
+  const uint32_t L = fmllr_seg_frames();
+  for (uint32_t s = 0; s < S; s++) {
+    for (uint32_t b = spk_frames[s]; b < spk_frames[s + 1]; b += L) {
+      seg_begin.push_back(b);
+      seg_len.push_back(std::min(L, spk_frames[s + 1] - b));
+    }
+    spk_seg_off[s + 1] = (uint32_t)seg_begin.size();
+  }
+  FmllrArgs a{};
+  a.feats = c->feats.p; a.n_frames = F; a.dim = D; a.shape = fmllr_shape(D);
+  a.means = m->means.p; a.inv_vars = m->inv_vars.p;
+  a.frame_pair_off = d_frame_pair_off; a.pair_dens = e.pair_dens; a.pair_key = e.key_mean; a.pair_w = e.pair_w;
+  a.n_speakers = S; a.n_segs = (uint32_t)seg_begin.size();
+  HIP_TRY(c->fm_fold_a.ensure((size_t)F * a.shape.rows)); HIP_TRY(c->fm_fold_c.ensure((size_t)F * a.shape.rows));
+  HIP_TRY(c->fm_frame_list.upload(frame_list.data(), F));
+  HIP_TRY(c->fm_seg_begin.upload(seg_begin.data(), seg_begin.size())); HIP_TRY(c->fm_seg_len.upload(seg_len.data(), seg_len.size()));
+  HIP_TRY(c->fm_spk_seg_off.upload(spk_seg_off.data(), S + 1));
+  HIP_TRY(c->fm_partial.ensure((size_t)a.n_segs * a.shape.rows * a.shape.cols));
+  const size_t nk = (size_t)S * D * E, nG = nk * E;
+  HIP_TRY(c->fm_beta.ensure(S)); HIP_TRY(c->fm_k.ensure(nk)); HIP_TRY(c->fm_G.ensure(nG));
+  a.fold_a = c->fm_fold_a.p; a.fold_c = c->fm_fold_c.p; a.frame_list = c->fm_frame_list.p; a.seg_begin = c->fm_seg_begin.p;
+  a.seg_len = c->fm_seg_len.p; a.spk_seg_off = c->fm_spk_seg_off.p; a.partial = c->fm_partial.p;
+  a.out_beta = c->fm_beta.p; a.out_k = c->fm_k.p; a.out_G = c->fm_G.p;
+  EventPair ep{};
+  if ((rc = prof_begin(m, m->s_gmm, 1, &ep))) return rc;
+  HIP_TRY(launch_fmllr_statistics(a, m->s_gmm));
+  if ((rc = prof_end(m, m->s_gmm, &ep))) return rc;
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  HIP_TRY(hipMemcpy(out_beta, c->fm_beta.p, sizeof(double) * S, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_k, c->fm_k.p, sizeof(double) * nk, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_G, c->fm_G.p, sizeof(double) * nG, hipMemcpyDeviceToHost));
+  if (m->profiling) {  // per frame: the fold's two rows out and in, the features; the partials out and in
+    m->prof.frames += F;
+    m->prof.search_bytes += (double)F * (32.0 * a.shape.rows + 4.0 * D) + 16.0 * (double)a.n_segs * a.shape.rows * a.shape.cols;
+  }
+  return SR_OK;
+}
+
+static void fmllr_zero(uint32_t D, uint32_t S, double* out_beta, double* out_k, double* out_G) {
+  const size_t nk = (size_t)S * D * (D + 1);
+  std::fill(out_beta, out_beta + S, 0.0);
+  std::fill(out_k, out_k + nk, 0.0);
+  std::fill(out_G, out_G + nk * (D + 1), 0.0);
+}
+
+int sr_fmllr_statistics_corpus(sr_model* m, sr_corpus* c, const uint16_t* states, const uint32_t* utt_speaker, uint32_t n_speakers,
+                               int max_approx, double* out_beta, double* out_k, double* out_G) {
+  return guarded(__func__, [&]() -> int {
+  int rc = fmllr_check(m, c, utt_speaker, n_speakers, out_beta, out_k, out_G);
+  if (rc) return rc;
+  if (c->n_frames == 0) { fmllr_zero(m->dim, n_speakers, out_beta, out_k, out_G); return SR_OK; }
+  EmArgs e{};
+  std::vector<uint64_t> pair_off;
+  if ((rc = alignment_pairs(m, c, states, 0, max_approx, &e, &pair_off))) return rc;
+  HIP_TRY(c->fm_pair_dens.ensure(e.n_pairs));
+  e.pair_dens = c->fm_pair_dens.p;
+  HIP_TRY(launch_em_pairs(e, m->s_gmm));
+  return fmllr_statistics(m, c, e, c->pair_off.p, utt_speaker, n_speakers, out_beta, out_k, out_G);
+  });
+}
+
+int sr_fmllr_statistics_bw_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
+                                  uint16_t silence_state, int gmm_kernel, double posterior_floor, const uint32_t* utt_speaker,
+                                  uint32_t n_speakers, int max_approx, double* out_cost, double* out_beta, double* out_k, double* out_G) {
+  return guarded(__func__, [&]() -> int {
+  int rc = fmllr_check(m, c, utt_speaker, n_speakers, out_beta, out_k, out_G);
+  if (rc) return rc;
+  if ((rc = fb_check(m, c, automata, aut_off, tdp, posterior_floor, out_cost))) return rc;
+  const uint32_t U = c->n_utts;
+  uint64_t n_items = 0;
+  if ((rc = fb_pass(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, true, &n_items))) return rc;
+  if (U) HIP_TRY(hipMemcpy(out_cost, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToHost));
+  EmArgs e{};
+  if ((rc = item_pairs(m, c, n_items, 0, max_approx, &e))) return rc;
+  if (e.n_pairs == 0) { fmllr_zero(m->dim, n_speakers, out_beta, out_k, out_G); return SR_OK; }  // nothing above the floor
+  HIP_TRY(c->fm_pair_dens.ensure(e.n_pairs));
+  e.pair_dens = c->fm_pair_dens.p;
+  HIP_TRY(launch_em_pairs_weighted(e, m->s_gmm));
+  HIP_TRY(c->fm_frame_pair_off.ensure(c->n_frames + 1));
+  HIP_TRY(launch_fmllr_item_frames(c->fb_item_off.p, c->fb_pair_end.p, c->n_frames, c->fm_frame_pair_off.p, m->s_gmm));
+  return fmllr_statistics(m, c, e, c->fm_frame_pair_off.p, utt_speaker, n_speakers, out_beta, out_k, out_G);
+  });
+}
+
+int sr_corpus_transform(sr_model* m, sr_corpus* c, const uint32_t* utt_speaker, uint32_t n_speakers, const double* W, sr_corpus** out) {
+  return guarded(__func__, [&]() -> int {
+  if (!out) return fail(SR_EINVAL, "out is null");
+  *out = nullptr;
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  if (n_speakers == 0) return fail(SR_EINVAL, "n_speakers is 0");
+  if (!W) return fail(SR_EINVAL, "W is null");
+  if (!utt_speaker && c->n_utts) return fail(SR_EINVAL, "utt_speaker is null");
+  for (uint32_t u = 0; u < c->n_utts; u++)
+    if (utt_speaker[u] >= n_speakers) return fail(SR_EINVAL, "utterance %u: speaker %u >= n_speakers %u", u, utt_speaker[u], n_speakers);
+  const uint32_t D = m->dim;
+  if (D > fmllr_max_dim()) return fail(SR_ELIMIT, "dimension %u exceeds %u (fMLLR transform)", D, fmllr_max_dim());
+  const uint64_t F = c->n_frames;
+  if ((rc = srhost::corpus_ready(c, 0, F, m->s_gmm))) return rc;  // an asynchronous upload of c: wait for all of it
+  sr_corpus* t = new sr_corpus();
+  std::unique_ptr<sr_corpus, int (*)(sr_corpus*)> own(t, sr_corpus_destroy);
+  t->model = m; t->n_utts = c->n_utts; t->n_frames = F;
+  srhost::corpus_register(t);
+  t->frame_off = c->frame_off;
+  HIP_TRY(t->feats.ensure((size_t)F * D + 64));
+  HIP_TRY(t->d_frame_off.upload(t->frame_off.data(), t->frame_off.size()));
+  DevBuf<uint32_t> d_spk;
+  DevBuf<double> d_W;
+  HIP_TRY(d_spk.upload(utt_speaker, c->n_utts));
+  HIP_TRY(d_W.upload(W, (size_t)n_speakers * D * (D + 1)));
+  EventPair ep{};
+  if ((rc = prof_begin(m, m->s_gmm, 1, &ep))) return rc;
+  HIP_TRY(launch_fmllr_transform(c->feats.p, t->d_frame_off.p, t->n_utts, d_spk.p, d_W.p, D, t->feats.p, m->s_gmm));
+  if ((rc = prof_end(m, m->s_gmm, &ep))) return rc;
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  if (m->profiling) {  // a row in, a row out
+    m->prof.frames += F;
+    m->prof.search_bytes += 8.0 * (double)F * D;
+  }
+  *out = own.release();
+  return SR_OK;
   });
 }
 

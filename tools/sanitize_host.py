@@ -1,7 +1,8 @@
 """ASan + UBSan run of the HOST side of libsrgpu.so (sanitizers on the CPU build only: the GPU pool has no xnack+).
 
-The three host translation units (srgpu_api.cpp: handles, packing, shard/gather glue, the traceback walk; mixset.cpp: the
-MIXSET parser / writer / host finalize; feeder.cpp: feeder, sr_shard_utterances, the multi-device driver) are compiled with
+The host translation units (srgpu_api.cpp: handles, packing, shard/gather glue, the traceback walk; mixset.cpp: the
+MIXSET parser / writer / host finalize; feeder.cpp: feeder, sr_shard_utterances, the multi-device driver; fmllr.cpp: the fMLLR
+estimate) are compiled with
 -fsanitize=address,undefined (device code untouched: -fno-gpu-sanitize) and linked with the regular kernel objects into
 csrc/build/asan/libsrgpu_asan.so; tests/cpp/host_mirror_driver.cpp (include/sr_sietill.hpp: lexicon, edit distance, feature
 post-processing, alignment dump) is built the same way.  Then the CPU tests of the boundary run against that library in a
@@ -24,8 +25,10 @@ from speechrecognition_amd import build as B  # noqa: E402
 
 OUT = os.path.join(B.CSRC, "build", "asan")
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-shared-libsan"]
-HOST_UNITS = ["srgpu_api.cpp", "mixset.cpp", "feeder.cpp"]
-TESTS = ["tests/test_capi_cpu.py", "tests/test_traceback_cpu.py", "tests/test_sanitized_host_paths.py"]
+HOST_UNITS = ["srgpu_api.cpp", "mixset.cpp", "feeder.cpp", "fmllr.cpp"]
+# (test_fmllr_cpu.py's driver test links tests/cpp/fmllr_driver.cpp against the regular libsrgpu.so: in this run it is the only
+# fMLLR test that does not go through the sanitized estimate)
+TESTS = ["tests/test_capi_cpu.py", "tests/test_traceback_cpu.py", "tests/test_sanitized_host_paths.py", "tests/test_fmllr_cpu.py"]
 
 
 def runtime():
