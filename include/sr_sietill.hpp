@@ -816,6 +816,65 @@ class Trainer {
     return std::unique_ptr<MixtureModel>(new MixtureModel(next, mixtures_));
   }
 
+  // One iteration of sMBR training (sr_smbr_statistics_corpus + sr_model_create_from_mmi_statistics): the expected frame accuracy of
+  // the free recognition network against the alignment's mixtures (one AlignmentItem per frame of the corpus, as align() leaves
+  // them), every cost multiplied by scale (kappa); the positive weights are the numerator's statistics, the negative ones the
+  // denominator's, then the extended Baum-Welch update as in mmi_iteration.  Returns the next model and sets *expected_correct
+  // (optional) to the sum of the expected accuracies under the CURRENT model -- the quantity the iteration raises -- and *n_frames
+  // (optional) to the frame count it is out of.
+  std::unique_ptr<MixtureModel> smbr_iteration(Corpus const& corpus, std::vector<AlignmentItem> const& alignment, double scale, double E,
+                                               double tau, double* expected_correct = nullptr, uint64_t* n_frames = nullptr,
+                                               double word_penalty = 0.0, double posterior_floor = 0.0, double var_floor = 1e-6) {
+    const size_t n = corpus.get_corpus_size();
+    const uint64_t F = corpus.get_total_frame_count();
+    if (alignment.size() < F) throw std::invalid_argument("smbr_iteration: one alignment item per frame");
+    std::vector<uint16_t> ref(std::max<uint64_t>(F, 1));
+    for (uint64_t t = 0; t < F; t++) ref[t] = alignment[t].state;
+    std::vector<uint32_t> word_off(1, 0);
+    std::vector<uint16_t> automaton;
+    for (WordIdx w = 0; w < lexicon_.num_words(); w++) {
+      auto const& a = lexicon_.get_automaton_for_word(w);
+      automaton.insert(automaton.end(), a.states.begin(), a.states.end());
+      word_off.push_back((uint32_t)automaton.size());
+    }
+    uint32_t n_mean = 0, n_var = 0;
+    check(sr_model_tying_info(mixtures_.handle(), &n_mean, &n_var));
+    const size_t D = mixtures_.dimension;
+    Statistics num, den;
+    for (Statistics* st : {&num, &den}) {
+      st->mean_acc.assign(n_mean * D, 0.0); st->mean_w.assign(n_mean, 0.0);
+      st->var_acc.assign(n_var * D, 0.0); st->var_w.assign(n_var, 0.0);
+    }
+    const double tdp[3] = {tdp_.tdp_loop, tdp_.tdp_forward, tdp_.tdp_skip};
+    sr_lexicon* net = nullptr;
+    check(sr_lexicon_create(mixtures_.handle(), (uint32_t)lexicon_.num_words(), word_off.data(), automaton.data(),
+                            (uint32_t)lexicon_.silence_idx(), tdp, tdp_.silence_state, &net));
+    sr_corpus* c = nullptr;
+    int rc = sr_corpus_upload(mixtures_.handle(), corpus.features(), corpus.frame_offsets(), (uint32_t)n, &c);
+    std::vector<double> cost(std::max<size_t>(n, 1)), acc(std::max<size_t>(n, 1));
+    if (rc == SR_OK) {
+      sr_search_params p = sr_search_params();  // zeroed, then field by field: a field added to the struct cannot shift these
+      p.word_penalty = word_penalty;
+      p.gmm_kernel = mixtures_.gmm_kernel;
+      rc = sr_smbr_statistics_corpus(mixtures_.handle(), c, net, &p, scale, posterior_floor, mixtures_.max_approx() ? 1 : 0, ref.data(),
+                                     cost.data(), acc.data(), num.mean_acc.data(), num.mean_w.data(), num.var_acc.data(),
+                                     num.var_w.data(), den.mean_acc.data(), den.mean_w.data(), den.var_acc.data(), den.var_w.data());
+      sr_corpus_destroy(c);
+    }
+    sr_lexicon_destroy(net);
+    check(rc);
+    if (expected_correct) {
+      *expected_correct = 0.0;
+      for (size_t u = 0; u < n; u++) *expected_correct += acc[u];
+    }
+    if (n_frames) *n_frames = F;
+    sr_model* next = nullptr;
+    check(sr_model_create_from_mmi_statistics(mixtures_.handle(), num.mean_acc.data(), num.mean_w.data(), num.var_acc.data(),
+                                              num.var_w.data(), den.mean_acc.data(), den.mean_w.data(), den.var_acc.data(),
+                                              den.var_w.data(), E, tau, var_floor, &next));
+    return std::unique_ptr<MixtureModel>(new MixtureModel(next, mixtures_));
+  }
+
   // Trainer::calc_am_score (Training.cpp:585-612): sequential sum of score(frame, aligned state) / frames
   double calc_am_score(Corpus const& corpus, std::vector<AlignmentItem> const& alignment) {
     const uint64_t F = corpus.get_total_frame_count();

@@ -445,6 +445,41 @@ SR_API int sr_model_create_from_mmi_statistics(sr_model* m, const double* num_me
                                                const double* den_mean_w, const double* den_var_acc, const double* den_var_w,
                                                double E, double tau, double var_floor, sr_model** out);
 
+/* ---- sMBR training: expected frame accuracy over the recognition network -----------------------------------------------------------
+ * The FREE network above (scale kappa, penalties, start hypothesis and p as sr_word_posteriors_corpus: every path,
+ * P(pi) proportional to exp(-kappa cost(pi)), no beam, p->flags == 0).
+ *   ref_states[total_frames] = the reference mixture of every frame (for example the output of sr_align_corpus); a value >= the
+ *   model's state count means the frame scores for no mixture.
+ *   A(pi) = sum over t of [k_t(pi) == ref_states[t]], k_t(pi) = the mixture whose emission the path pays at frame t.  An entry into
+ *   position 1 of a word emits the word's FIRST state (the reference's quirk) and is scored as that state.
+ *   out_acc[u] = Abar_u = sum over pi of P(pi) A(pi), 0 <= Abar_u <= T_u.  T_u = 0 or F_u = +inf: Abar_u = 0 and no items.
+ *   gamma_t(k) = occ_t(k) (c_t(k) - Abar_u) = -(1/kappa) d Abar_u / d e(t, k), with occ_t(k) the occupancy of
+ *   sr_net_occupancies_corpus and c_t(k) the expected accuracy of the paths whose frame t emits k; sum over k of gamma_t(k) = 0.
+ * Lexica of at most 5108 positions (what sr_smbr_max_positions reports) (SR_ELIMIT).  Workspace: 16 bytes per (frame, position) for the
+ * utterances processed together, at most SRGPU_FB_MB MiB; an utterance that alone needs more: SR_ELIMIT.  SR_EINVAL as
+ * sr_net_occupancies_corpus, and for a NULL ref_states.  Every check precedes the first launch.  No atomics: two identical calls
+ * return identical bits. */
+SR_API int sr_smbr_max_positions(uint32_t* out);
+
+/* out_cost[n_utts] = F_u and out_acc[n_utts] = Abar_u (both required).  Items all or none: per frame the mixtures with gamma != 0
+ * and |gamma| >= posterior_floor, largest |gamma| first (ties: smaller id first), at most max_items (1 .. 65535); out_weight is
+ * signed; entries past out_count are 0. */
+SR_API int sr_net_accuracies_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale,
+                                    double posterior_floor, uint32_t max_items, const uint16_t* ref_states, double* out_cost,
+                                    double* out_acc, uint16_t* out_count, uint16_t* out_state, double* out_weight);
+
+/* One sMBR E-step.  gamma is split by sign: the items (t, k, gamma) with gamma > 0 and gamma >= posterior_floor go to the numerator,
+ * the items (t, k, -gamma) with -gamma > 0 and -gamma >= posterior_floor to the denominator, each spread over the mixture's
+ * densities exactly as sr_mmi_statistics_corpus spreads an occupancy (max_approx: the arg-min density, else the soft memberships
+ * with their < 1e-8 drop), with the accumulators, seeds and summation order of sr_baum_welch_corpus.  All outputs required; the eight
+ * arrays are shaped so that sr_model_create_from_mmi_statistics takes them unchanged.  Statistics of corpus shards add up like
+ * sr_mmi_statistics_corpus' (the var_acc seed of 1e-4 once per call and side). */
+SR_API int sr_smbr_statistics_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale,
+                                     double posterior_floor, int max_approx, const uint16_t* ref_states, double* out_cost,
+                                     double* out_acc, double* num_mean_acc, double* num_mean_w, double* num_var_acc,
+                                     double* num_var_w, double* den_mean_acc, double* den_mean_w, double* den_var_acc,
+                                     double* den_var_w);
+
 /* ---- word lattices and N-best lists over the recognition network --------------------------------------------------------
  * The same network in the MIN semiring, without a beam (am_threshold is ignored) and with the decoder's order of additions, so
  * that every number below is a sum the decoder itself would form.  For an utterance of T frames:

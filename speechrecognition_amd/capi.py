@@ -32,6 +32,7 @@ SYMBOLS = [
     "sr_lexicon_destroy", "sr_lexicon_describe", "sr_recognize_corpus", "sr_traceback_corpus", "sr_traceback_words", "sr_recognize_batch", "sr_align_corpus", "sr_align_corpus_pruned", "sr_path_scores_corpus", "sr_model_create_from_statistics", "sr_model_create_from_accumulated", "sr_mixset_write", "sr_model_set_tying", "sr_model_tying_info", "sr_model_topology", "sr_accumulate_corpus",
     "sr_state_posteriors_corpus", "sr_baum_welch_corpus", "sr_word_posteriors_corpus", "sr_recognize_confidence_corpus",
     "sr_net_occupancies_corpus", "sr_mmi_statistics_corpus", "sr_model_create_from_mmi_statistics",
+    "sr_smbr_max_positions", "sr_net_accuracies_corpus", "sr_smbr_statistics_corpus",
     "sr_word_lattice_corpus", "sr_lattice_nbest",
     "sr_fmllr_statistics_corpus", "sr_fmllr_statistics_bw_corpus", "sr_fmllr_estimate", "sr_corpus_transform",
     "sr_bigram_create", "sr_bigram_destroy", "sr_bigram_describe", "sr_recognize_bigram_corpus",
@@ -50,6 +51,13 @@ class SrError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libsrgpu error {code}: {msg}")
         self.code = code
+
+
+def smbr_max_positions():
+    """the largest lexicon (positions) sr_net_accuracies_corpus / sr_smbr_statistics_corpus take"""
+    n = C.c_uint32()
+    _check(lib().sr_smbr_max_positions(C.byref(n)))
+    return n.value
 
 
 class SearchParams(C.Structure):
@@ -122,6 +130,9 @@ def lib():
         L.sr_recognize_confidence_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, vp, vp, vp, vp, vp]
         L.sr_net_occupancies_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, vp, vp, vp]
         L.sr_mmi_statistics_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, i32, vp, vp] + [vp] * 10
+        L.sr_smbr_max_positions.argtypes = [vp]
+        L.sr_net_accuracies_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, vp, vp, vp]
+        L.sr_smbr_statistics_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, i32, vp] + [vp] * 10
         L.sr_model_create_from_mmi_statistics.argtypes = [vp] + [vp] * 8 + [dbl, dbl, dbl, C.POINTER(vp)]
         L.sr_word_lattice_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, u64, vp, vp, vp, vp, vp, vp, vp, vp]
         L.sr_lattice_nbest.argtypes = [u32, u64, vp, vp, vp, vp, u32, u32, vp, u64, vp, vp, C.POINTER(u32)]
@@ -653,6 +664,37 @@ class Corpus:
         _check(lib().sr_mmi_statistics_corpus(self.model.h, self.h, lexicon.h, C.byref(sp), float(scale), float(floor), int(max_approx),
                                               _ptr(flat), _ptr(off), _ptr(fn), _ptr(fd), *[_ptr(a) for a in num + den]))
         return fn[: self.n_utts], fd[: self.n_utts], num, den
+
+    def net_accuracies(self, lexicon, word_penalty, ref_states, scale=1.0, kernel=GMM_PREFILTER, floor=0.0, max_items=8):
+        """Expected frame accuracy over the free recognition network (sr_net_accuracies_corpus); ref_states u16[total_frames] = the
+        reference mixture of every frame -> (cost f64[n_utts], acc f64[n_utts], count u16[total_frames], state u16[total_frames,
+        max_items], weight f64[total_frames, max_items]): per frame the signed gamma, largest |gamma| first."""
+        F = max(self.n_frames, 1)
+        K = max(int(max_items), 1)
+        cost, acc = (np.zeros(max(self.n_utts, 1), dtype=np.float64) for _ in range(2))
+        count = np.zeros(F, dtype=np.uint16)
+        state = np.zeros((F, K), dtype=np.uint16)
+        weight = np.zeros((F, K), dtype=np.float64)
+        sp = SearchParams(np.inf, word_penalty, kernel, 0)
+        ref = np.ascontiguousarray(np.concatenate([np.asarray(ref_states, dtype=np.uint16), np.zeros(1, np.uint16)]))
+        _check(lib().sr_net_accuracies_corpus(self.model.h, self.h, lexicon.h, C.byref(sp), float(scale), float(floor), int(max_items),
+                                              _ptr(ref), _ptr(cost), _ptr(acc), _ptr(count), _ptr(state), _ptr(weight)))
+        n = self.n_frames
+        return cost[: self.n_utts], acc[: self.n_utts], count[:n], state[:n], weight[:n]
+
+    def smbr_statistics(self, lexicon, word_penalty, ref_states, scale=1.0, kernel=GMM_PREFILTER, floor=0.0, max_approx=True):
+        """One sMBR E-step (sr_smbr_statistics_corpus) -> (F f64[n_utts], Abar f64[n_utts], num, den), each side's statistics
+        (mean_acc, mean_w, var_acc, var_w) as mmi_statistics': num from the positive gamma, den from the negative."""
+        nm, nv = C.c_uint32(), C.c_uint32()
+        _check(lib().sr_model_tying_info(self.model.h, C.byref(nm), C.byref(nv)))
+        D = self.model.dim
+        num, den = ((np.zeros((nm.value, D)), np.zeros(nm.value), np.zeros((nv.value, D)), np.zeros(nv.value)) for _ in range(2))
+        cost, acc = (np.zeros(max(self.n_utts, 1), dtype=np.float64) for _ in range(2))
+        sp = SearchParams(np.inf, word_penalty, kernel, 0)
+        ref = np.ascontiguousarray(np.concatenate([np.asarray(ref_states, dtype=np.uint16), np.zeros(1, np.uint16)]))
+        _check(lib().sr_smbr_statistics_corpus(self.model.h, self.h, lexicon.h, C.byref(sp), float(scale), float(floor), int(max_approx),
+                                               _ptr(ref), _ptr(cost), _ptr(acc), *[_ptr(a) for a in num + den]))
+        return cost[: self.n_utts], acc[: self.n_utts], num, den
 
     def recognize_confidence(self, lexicon, am_threshold, word_penalty, scale=1.0, kernel=GMM_PREFILTER):
         """recognize()'s words with a confidence each (sr_recognize_confidence_corpus) -> (words u32[], word_off u64[n_utts+1],

@@ -179,6 +179,11 @@ struct sr_corpus {
   DevBuf<double> nf_ends, mmi_num_cost;
   DevBuf<uint64_t> mmi_chain_off;
   DevBuf<uint32_t> mmi_info, mmi_src, mmi_dst;
+  // sMBR training (viterbi_smbr.hip; trellis, mixture lists and the items of one sign are the fb_* buffers): the word-end sums and
+  // accuracies of one launch group, the references, Abar_u, the items of the other sign
+  DevBuf<double> smbr_ends, smbr_acc, smbr_item_w;
+  DevBuf<uint16_t> smbr_ref, smbr_item_mix;
+  DevBuf<uint32_t> smbr_base, smbr_item_off, smbr_item_frame;
   // forward-backward over the bigram search network (viterbi_bigram_fb.hip; trellis, posteriors and items are the buffers above):
   // the launch groups' vectors and utterance orders, the items' confidences
   DevBuf<double> bgfb_vec, bgfb_prod, bgfb_wend, bgfb_m, bgfb_xb, bgfb_conf;

@@ -401,6 +401,34 @@ struct EbwArgs {
 };
 hipError_t launch_ebw_combine(const EbwArgs& a, hipStream_t stream);
 
+// ---- sMBR training over the recognition network (viterbi_smbr.hip) ----------------------------------------------------------------
+// NetFbArgs' launch with the expected frame accuracy beside every cost.
+struct SmbrArgs {
+  DecodeNet net;                // the lexicon's slot tables; n_slots <= smbr_max_slots()
+  const double* scores;         // [frames x ld], row 0 = frame frame_base (as DecodeArgs)
+  uint32_t ld;
+  uint64_t frame_base;
+  const uint64_t* frame_off;    // [n_utts_total+1]
+  uint32_t utt_first, n_utts;
+  double scale, word_penalty;   // as NetFbArgs
+  uint64_t group_f0;            // first frame of the launch
+  const uint16_t* ref;          // [n_frames_total] the reference mixture of every frame; >= the state count: none
+  double* trellis;              // [frames of the launch][2][P]: (alpha, abar), then the signed parts over alpha
+  double* ends;                 // [frames of the launch][2]: the word-end sum E_t and its expected accuracy
+  double* out_cost;             // [n_utts_total] kappa F_u
+  double* out_acc;              // [n_utts_total] Abar_u
+};
+size_t smbr_max_slots();
+hipError_t launch_smbr_forward(const SmbrArgs& a, hipStream_t stream);
+hipError_t launch_smbr_backward(const SmbrArgs& a, hipStream_t stream);
+// launch_occ_items over the signed parts of the free network (OccItemArgs without chains and gate; rows of 2 n_cols doubles).
+// sign = +1 / -1: the items with sign * gamma > 0 and >= floor, weight sign * gamma; 0: gamma != 0 and |gamma| >= floor, weight gamma
+hipError_t launch_smbr_items(const OccItemArgs& a, int sign, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes,
+                             uint32_t* scan_out, hipStream_t stream);
+// launch_fb_top ranked on |weight| (ties: smaller mixture id first), the weights signed
+hipError_t launch_smbr_top(const uint32_t* item_off, const uint16_t* item_mix, const double* item_w, uint64_t n_frames,
+                           uint32_t max_items, uint16_t* out_count, uint16_t* out_state, double* out_weight, hipStream_t stream);
+
 // ---- word lattices over the recognition network (viterbi_lattice.hip) --------------------------------------------------
 // A launch covers utterances [utt_first, utt_first + n_utts) of one score chunk whose word-end tables fit the workspace together.
 struct LatticeArgs {

@@ -2854,6 +2854,221 @@ int sr_model_create_from_mmi_statistics(sr_model* m, const double* num_mean_acc,
   });
 }
 
+// ---- sMBR training over the recognition network (viterbi_smbr.hip) ----------------------------------------------------------------
+int sr_smbr_max_positions(uint32_t* out) {
+  if (!out) return fail(SR_EINVAL, "out is null");
+  *out = (uint32_t)smbr_max_slots();
+  return SR_OK;
+}
+
+// netfb_check with the accuracy pass' position limit and 16 B per (frame, position), plus the references
+static int smbr_check(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
+                      const uint16_t* ref_states) {
+  int rc = netfb_check(m, c, l, p, scale, posterior_floor);
+  if (rc) return rc;
+  if (!ref_states) return fail(SR_EINVAL, "null argument (ref_states)");
+  const uint64_t P = l->net.n_slots;
+  if (P > smbr_max_slots())
+    return fail(SR_ELIMIT, "%llu lexicon positions exceed the accuracy forward-backward's %llu", (unsigned long long)P,
+                (unsigned long long)smbr_max_slots());
+  for (uint32_t u = 0; u < c->n_utts; u++) {
+    const uint64_t T = c->frame_off[u + 1] - c->frame_off[u];
+    if (16 * P * T > m->fb_budget)
+      return fail(SR_ELIMIT, "utterance %u: trellis of %llu bytes exceeds the forward-backward workspace of %llu (SRGPU_FB_MB)", u,
+                  (unsigned long long)(16 * P * T), (unsigned long long)m->fb_budget);
+  }
+  return SR_OK;
+}
+
+// NetFbPass for the accuracy recursions: the launch groups are consecutive utterances of a chunk whose trellises (16 B per frame and
+// position) fit m->fb_budget together (smbr_check: every utterance fits alone).  run() enqueues a chunk's groups in order: forward,
+// backward, then per_group(item arguments of the group, frames of the group).
+extern "C++" {
+struct SmbrPass {
+  struct Group { uint32_t u0, u1; };
+  std::vector<std::vector<Group>> groups;  // per chunk
+  SmbrArgs a{};
+  OccItemArgs ia{};  // the free network's mixture lists; the caller points it at its item buffers
+  uint64_t max_gf = 1, item_bound = 0;
+  size_t scan_bytes = 0;
+  size_t ci = 0;  // run_chunks searches the chunks in order
+
+  int setup(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double floor, const uint16_t* ref_states,
+            const std::vector<Chunk>& chunks) {
+    const uint64_t P = l->net.n_slots, F = c->n_frames;
+    groups.assign(chunks.size(), {});
+    for (size_t i = 0; i < chunks.size(); i++)
+      for (uint32_t u = chunks[i].u0; u < chunks[i].u1;) {
+        uint32_t v = u + 1;
+        while (v < chunks[i].u1 && 16 * P * (c->frame_off[v + 1] - c->frame_off[u]) <= m->fb_budget) v++;
+        groups[i].push_back({u, v});
+        max_gf = std::max<uint64_t>(max_gf, c->frame_off[v] - c->frame_off[u]);
+        u = v;
+      }
+    // the lexicon's distinct mixtures (ascending) and the positions carrying each, as occ_pass lists them
+    std::vector<std::pair<uint16_t, uint16_t>> ps;
+    for (uint64_t i = 0; i < P; i++) ps.push_back({(uint16_t)(l->h_slot_info[i] & 0xFFFFu), (uint16_t)i});
+    std::sort(ps.begin(), ps.end());
+    std::vector<uint32_t> slot_beg;
+    std::vector<uint16_t> mix, slot_pos;
+    for (size_t i = 0; i < ps.size(); i++) {
+      if (i == 0 || ps[i].first != ps[i - 1].first) {
+        mix.push_back(ps[i].first);
+        slot_beg.push_back((uint32_t)slot_pos.size());
+      }
+      slot_pos.push_back(ps[i].second);
+    }
+    slot_beg.push_back((uint32_t)slot_pos.size());
+    item_bound = F * mix.size();
+    if (item_bound >= (1ull << 31)) return fail(SR_ELIMIT, "too many (frame, mixture) weights");
+    HIP_TRY(c->fb_trellis.ensure(max_gf * 2 * P));
+    HIP_TRY(c->smbr_ends.ensure(max_gf * 2));
+    HIP_TRY(c->out_cost.ensure(c->n_utts));
+    HIP_TRY(c->smbr_acc.ensure(c->n_utts));
+    HIP_TRY(c->smbr_ref.upload(ref_states, F));
+    HIP_TRY(c->fb_mix.upload(mix.data(), mix.size()));
+    HIP_TRY(c->fb_slot_beg.upload(slot_beg.data(), slot_beg.size()));
+    HIP_TRY(c->fb_slot_pos.upload(slot_pos.data(), slot_pos.size()));
+    scan_bytes = fb_scan_temp_bytes(max_gf);
+    HIP_TRY(c->fb_scan_temp.ensure(scan_bytes));
+    HIP_TRY(c->fb_cnt.ensure(max_gf)); HIP_TRY(c->fb_scan.ensure(max_gf));
+    a.net = l->net; a.ld = m->ld; a.frame_off = c->d_frame_off.p; a.scale = scale; a.word_penalty = p->word_penalty;
+    a.ref = c->smbr_ref.p; a.trellis = c->fb_trellis.p; a.ends = c->smbr_ends.p; a.out_cost = c->out_cost.p; a.out_acc = c->smbr_acc.p;
+    ia.frame_off = c->d_frame_off.p; ia.trellis = c->fb_trellis.p; ia.n_cols = (uint32_t)P; ia.n_mix = (uint32_t)mix.size();
+    ia.mix = c->fb_mix.p; ia.slot_beg = c->fb_slot_beg.p; ia.slot_pos = c->fb_slot_pos.p; ia.floor = floor; ia.group_cnt = c->fb_cnt.p;
+    // trellis traffic per (frame, position): (alpha, abar) out, both in + the part out, the part in (items)
+    if (m->profiling) m->prof.search_bytes += 48.0 * (double)P * (double)F;
+    return SR_OK;
+  }
+  template <class PerGroup>
+  int run(sr_corpus* c, const Chunk& ch, const double* table, hipStream_t s, PerGroup per_group) {
+    for (const Group& g : groups[ci]) {
+      a.scores = table; a.frame_base = ch.f0; a.utt_first = g.u0; a.n_utts = g.u1 - g.u0; a.group_f0 = c->frame_off[g.u0];
+      HIP_TRY(launch_smbr_forward(a, s));
+      HIP_TRY(launch_smbr_backward(a, s));
+      ia.utt_first = g.u0; ia.n_utts = g.u1 - g.u0; ia.group_f0 = c->frame_off[g.u0];
+      int rc = per_group(ia, c->frame_off[g.u1] - c->frame_off[g.u0]);
+      if (rc) return rc;
+    }
+    ci++;
+    return SR_OK;
+  }
+};
+}  // extern "C++"
+
+// kappa F_u, Abar_u on the device -> F_u, Abar_u
+static int smbr_costs(sr_corpus* c, double scale, double* out_cost, double* out_acc) {
+  int rc = netfb_costs(c, scale, out_cost);
+  if (rc) return rc;
+  if (c->n_utts) HIP_TRY(hipMemcpy(out_acc, c->smbr_acc.p, sizeof(double) * c->n_utts, hipMemcpyDeviceToHost));
+  return SR_OK;
+}
+
+int sr_net_accuracies_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
+                             uint32_t max_items, const uint16_t* ref_states, double* out_cost, double* out_acc, uint16_t* out_count,
+                             uint16_t* out_state, double* out_weight) {
+  return guarded(__func__, [&]() -> int {
+  int rc = smbr_check(m, c, l, p, scale, posterior_floor, ref_states);
+  if (rc) return rc;
+  if (!out_cost || !out_acc) return fail(SR_EINVAL, "null argument");
+  const bool post = out_count || out_state || out_weight;
+  if (post && (!out_count || !out_state || !out_weight)) return fail(SR_EINVAL, "null output (pass out_count, out_state and out_weight, or none)");
+  if (post && (max_items == 0 || max_items > 65535)) return fail(SR_EINVAL, "max_items must be 1 .. 65535 (got %u)", max_items);
+  const uint64_t F = c->n_frames;
+  std::vector<Chunk> chunks;
+  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
+  SmbrPass sp;
+  if ((rc = sp.setup(m, c, l, p, scale, posterior_floor, ref_states, chunks))) return rc;
+  if (post) {
+    HIP_TRY(c->fb_base.ensure(1)); HIP_TRY(c->fb_item_off.ensure(F + 1));
+    HIP_TRY(c->fb_item_frame.ensure(sp.item_bound)); HIP_TRY(c->fb_item_mix.ensure(sp.item_bound)); HIP_TRY(c->fb_item_w.ensure(sp.item_bound));
+    sp.ia.item_base = c->fb_base.p; sp.ia.item_off = c->fb_item_off.p;
+    sp.ia.item_frame = c->fb_item_frame.p; sp.ia.item_mix = c->fb_item_mix.p; sp.ia.item_w = c->fb_item_w.p;
+  }
+  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); },
+      [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
+        if (post && sp.ci == 0) HIP_TRY(hipMemsetAsync(c->fb_base.p, 0, sizeof(uint32_t), s));
+        return sp.run(c, ch, table, s, [&](const OccItemArgs& ia, uint64_t n) -> int {
+          if (post) HIP_TRY(launch_smbr_items(ia, 0, n, c->fb_scan_temp.p, sp.scan_bytes, c->fb_scan.p, s));
+          return SR_OK;
+        });
+      });
+  if (rc) return rc;
+  if (m->profiling) m->prof.frames += F;
+  if ((rc = smbr_costs(c, scale, out_cost, out_acc))) return rc;
+  if (!post || F == 0) return SR_OK;
+  HIP_TRY(c->fb_count.ensure(F));
+  HIP_TRY(c->fb_state.ensure((size_t)F * max_items));
+  HIP_TRY(c->fb_weight.ensure((size_t)F * max_items));
+  HIP_TRY(launch_smbr_top(c->fb_item_off.p, c->fb_item_mix.p, c->fb_item_w.p, F, max_items, c->fb_count.p, c->fb_state.p, c->fb_weight.p,
+                          m->s_gmm));
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  HIP_TRY(hipMemcpy(out_count, c->fb_count.p, sizeof(uint16_t) * F, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_state, c->fb_state.p, sizeof(uint16_t) * F * max_items, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_weight, c->fb_weight.p, sizeof(double) * F * max_items, hipMemcpyDeviceToHost));
+  return SR_OK;
+  });
+}
+
+int sr_smbr_statistics_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
+                              int max_approx, const uint16_t* ref_states, double* out_cost, double* out_acc, double* num_mean_acc,
+                              double* num_mean_w, double* num_var_acc, double* num_var_w, double* den_mean_acc, double* den_mean_w,
+                              double* den_var_acc, double* den_var_w) {
+  return guarded(__func__, [&]() -> int {
+  int rc = smbr_check(m, c, l, p, scale, posterior_floor, ref_states);
+  if (rc) return rc;
+  if (!out_cost || !out_acc || !num_mean_acc || !num_mean_w || !num_var_acc || !num_var_w || !den_mean_acc || !den_mean_w ||
+      !den_var_acc || !den_var_w)
+    return fail(SR_EINVAL, "null output");
+  const uint64_t F = c->n_frames;
+  c->acc_valid = false;
+  std::vector<Chunk> chunks;
+  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
+  SmbrPass sp;
+  if ((rc = sp.setup(m, c, l, p, scale, posterior_floor, ref_states, chunks))) return rc;
+  // one pass, the items of both signs: the positive ones in the fb_item_* buffers, the negative ones beside them
+  const uint64_t nb = sp.item_bound;
+  HIP_TRY(c->fb_base.ensure(1)); HIP_TRY(c->fb_item_off.ensure(F + 1));
+  HIP_TRY(c->fb_item_frame.ensure(nb)); HIP_TRY(c->fb_item_mix.ensure(nb)); HIP_TRY(c->fb_item_w.ensure(nb));
+  HIP_TRY(c->smbr_base.ensure(1)); HIP_TRY(c->smbr_item_off.ensure(F + 1));
+  HIP_TRY(c->smbr_item_frame.ensure(nb)); HIP_TRY(c->smbr_item_mix.ensure(nb)); HIP_TRY(c->smbr_item_w.ensure(nb));
+  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); },
+      [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
+        if (sp.ci == 0) {
+          HIP_TRY(hipMemsetAsync(c->fb_base.p, 0, sizeof(uint32_t), s));
+          HIP_TRY(hipMemsetAsync(c->smbr_base.p, 0, sizeof(uint32_t), s));
+        }
+        return sp.run(c, ch, table, s, [&](const OccItemArgs& ia, uint64_t n) -> int {
+          OccItemArgs pos = ia, neg = ia;
+          pos.item_base = c->fb_base.p; pos.item_off = c->fb_item_off.p;
+          pos.item_frame = c->fb_item_frame.p; pos.item_mix = c->fb_item_mix.p; pos.item_w = c->fb_item_w.p;
+          neg.item_base = c->smbr_base.p; neg.item_off = c->smbr_item_off.p;
+          neg.item_frame = c->smbr_item_frame.p; neg.item_mix = c->smbr_item_mix.p; neg.item_w = c->smbr_item_w.p;
+          HIP_TRY(launch_smbr_items(pos, +1, n, c->fb_scan_temp.p, sp.scan_bytes, c->fb_scan.p, s));
+          HIP_TRY(launch_smbr_items(neg, -1, n, c->fb_scan_temp.p, sp.scan_bytes, c->fb_scan.p, s));
+          return SR_OK;
+        });
+      });
+  if (rc) return rc;
+  if (m->profiling) m->prof.frames += F;
+  if ((rc = smbr_costs(c, scale, out_cost, out_acc))) return rc;
+  uint32_t n_pos = 0, n_neg = 0;
+  if (c->n_utts) {
+    HIP_TRY(hipMemcpy(&n_pos, c->fb_base.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&n_neg, c->smbr_base.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  if ((rc = accumulate_items(m, c, n_pos, 0, max_approx, true, num_mean_acc, num_mean_w, num_var_acc, num_var_w))) return rc;
+  if (n_neg) {  // the negative side through the same buffers
+    HIP_TRY(hipMemcpy(c->fb_item_frame.p, c->smbr_item_frame.p, sizeof(uint32_t) * n_neg, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(c->fb_item_mix.p, c->smbr_item_mix.p, sizeof(uint16_t) * n_neg, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(c->fb_item_w.p, c->smbr_item_w.p, sizeof(double) * n_neg, hipMemcpyDeviceToDevice));
+  }
+  rc = accumulate_items(m, c, n_neg, 0, max_approx, true, den_mean_acc, den_mean_w, den_var_acc, den_var_w);
+  c->acc_valid = false;  // (the handle holds one side only: nothing for sr_model_create_from_accumulated)
+  return rc;
+  });
+}
+
 // ---- MMI training over the bigram search network (viterbi_bigram_mmi.hip) ---------------------------------------------------------
 // The transcripts' chains: segment 0 of utterance u is the silence word S, segment 2 i - 1 the word w_i and segment 2 i its silence
 // copy c_i, each with the pos_info of its slot of the search net; BgChainArgs' src / dst links and entry LM costs as its header says.
