@@ -18,6 +18,7 @@
 //   sr::read_feature_file, write_alignment, read_alignment    sietill/IO.cpp:48-69, Alignment.cpp:303-318
 //   sr::Trainer (re-alignment) Trainer::train's align loop   sietill/Training.cpp:163-184, :239-253, :585-612
 //                              (+ baum_welch: forward-backward E-step in place of realign + accumulate)
+//                              (+ split, eliminate, train: the reference's schedule from one density per mixture upwards)
 //
 // Differences, all forced by the device boundary: features are passed as (pointer, frame count)
 // instead of FeatureIter pairs; MixtureModel::prepare_sequence really does work (it fills the dense
@@ -140,10 +141,28 @@ class MixtureModel : public FeatureScorer {
     num_mixtures_ = s;
     num_densities_ = c;
   }
-  // takes over a device model derived from `like` (sr::Trainer::mmi_iteration); it has no file, so it cannot replicate()
+  // MixtureModel(config, dimension, num_mixtures, var_model, max_approx) with action "train" (Mixtures.cpp:156-174): one density per
+  // mixture, the flat start of sr::Trainer::train.  Its table values (mean 0, variance 1, weight 1) are placeholders: the first
+  // pass of training reads none of them.
+  MixtureModel(size_t dimension, size_t num_mixtures, VarianceModel var_model, bool max_approx, int device = 0,
+               int gmm_kernel = SR_GMM_DEFAULT)
+      : dimension(dimension), var_model(var_model), gmm_kernel(gmm_kernel), num_mixtures_(num_mixtures), num_densities_(num_mixtures),
+        max_approx_(max_approx), device_(device) {
+    check_abi();
+    std::vector<uint32_t> dens_off(num_mixtures + 1);
+    for (size_t s = 0; s <= num_mixtures; s++) dens_off[s] = (uint32_t)s;
+    std::vector<double> zeros(num_mixtures * dimension, 0.0), ones(num_mixtures * dimension, 1.0);
+    check(sr_model_create(device, (uint32_t)dimension, (uint32_t)num_mixtures, dens_off.data(), zeros.data(), ones.data(), zeros.data(),
+                          zeros.data(), max_approx ? 1 : 0, &h_));
+  }
+  // takes over a device model derived from `like` (sr::Trainer::mmi_iteration, split, eliminate, train); it has no file, so it cannot
+  // replicate()
   MixtureModel(sr_model* adopted, MixtureModel const& like)
       : dimension(like.dimension), var_model(like.var_model), gmm_kernel(like.gmm_kernel), h_(adopted),
-        num_mixtures_(like.num_mixtures_), num_densities_(like.num_densities_), max_approx_(like.max_approx_), device_(like.device_) {}
+        num_mixtures_(like.num_mixtures_), num_densities_(like.num_densities_), max_approx_(like.max_approx_), device_(like.device_) {
+    uint64_t c = 0;
+    if (sr_model_info(h_, nullptr, nullptr, &c) == SR_OK) num_densities_ = c;  // split and eliminate change it
+  }
   ~MixtureModel() { sr_model_destroy(h_); }
   MixtureModel(MixtureModel const&) = delete;
   MixtureModel& operator=(MixtureModel const&) = delete;
@@ -161,6 +180,22 @@ class MixtureModel : public FeatureScorer {
   // whole model: Recognizer::recognize(corpus, devices))
   std::unique_ptr<MixtureModel> replicate(int device) const {
     return std::unique_ptr<MixtureModel>(new MixtureModel(path_, dimension, var_model, max_approx_, device, gmm_kernel));
+  }
+
+  // the per-density tables in sr_model_create's shape (sr_model_tables), e.g. for a checkpoint of a model that was just split
+  struct Tables {
+    std::vector<uint32_t> dens_off;             // [num_mixtures + 1]
+    std::vector<double> means, inv_vars;        // [num_densities x dimension]
+    std::vector<double> norm, logw;             // [num_densities]
+  };
+  Tables tables() const {
+    Tables t;
+    t.dens_off.resize(num_mixtures_ + 1);
+    check(sr_model_topology(h_, t.dens_off.data(), nullptr, nullptr));
+    t.means.resize(num_densities_ * dimension); t.inv_vars.resize(num_densities_ * dimension);
+    t.norm.resize(num_densities_); t.logw.resize(num_densities_);
+    check(sr_model_tables(h_, t.means.data(), t.inv_vars.data(), t.norm.data(), t.logw.data()));
+    return t;
   }
 
   // FeatureScorer: one dense [T x S] table per sequence
@@ -701,18 +736,9 @@ class Trainer {
     std::vector<uint64_t> aut_off;
     segment_automata(corpus, automata, aut_off);
     const uint64_t F = corpus.get_total_frame_count();
-    const double tdp[3] = {tdp_.tdp_loop, tdp_.tdp_forward, tdp_.tdp_skip};
-    sr_corpus* c = nullptr;
-    check(sr_corpus_upload(mixtures_.handle(), corpus.features(), corpus.frame_offsets(), (uint32_t)n, &c));
-    std::vector<uint16_t> states(std::max<uint64_t>(F, 1));
-    std::vector<double> cost(std::max<size_t>(n, 1));
-    const int rc = alignment_pruning_
-                       ? sr_align_corpus_pruned(mixtures_.handle(), c, automata.data(), aut_off.data(), tdp, tdp_.silence_state,
-                                                pruning_threshold_, mixtures_.gmm_kernel, states.data(), cost.data())
-                       : sr_align_corpus(mixtures_.handle(), c, automata.data(), aut_off.data(), tdp, tdp_.silence_state,
-                                         mixtures_.gmm_kernel, states.data(), cost.data());
-    sr_corpus_destroy(c);
-    check(rc);
+    std::vector<uint16_t> states;
+    std::vector<double> cost;
+    align_states(mixtures_.handle(), corpus, automata, aut_off, states, cost);
     alignment.assign(F, AlignmentItem());
     for (uint64_t t = 0; t < F; t++) { alignment[t].state = states[t]; alignment[t].weight = 1; alignment[t].count = 1; }
     if (costs) costs->assign(cost.begin(), cost.begin() + n);
@@ -875,23 +901,171 @@ class Trainer {
     return std::unique_ptr<MixtureModel>(new MixtureModel(next, mixtures_));
   }
 
+  // MixtureModel::split / eliminate in the schedule of Trainer::train (sr_model_split, sr_model_eliminate: the operations srgpu.h
+  // specifies, not the reference's bits).  The weights are the per mean row observation counts of the last E-step: Statistics::mean_w,
+  // or a corpus handle of this model in which sr_accumulate_corpus / sr_baum_welch_corpus left its statistics.  Variance rows follow
+  // the model's var_model.  The result is a model of a new shape; this trainer keeps pointing at the old one.
+  std::unique_ptr<MixtureModel> split(std::vector<double> const& mean_w, double min_obs, double epsilon) {
+    return split_of(mixtures_.handle(), nullptr, checked_weights(mixtures_.handle(), mean_w), min_obs, epsilon);
+  }
+  std::unique_ptr<MixtureModel> split(sr_corpus* resident, double min_obs, double epsilon) {
+    return split_of(mixtures_.handle(), resident, nullptr, min_obs, epsilon);
+  }
+  std::unique_ptr<MixtureModel> eliminate(std::vector<double> const& mean_w, double min_obs) {
+    return eliminate_of(mixtures_.handle(), nullptr, checked_weights(mixtures_.handle(), mean_w), min_obs);
+  }
+  std::unique_ptr<MixtureModel> eliminate(sr_corpus* resident, double min_obs) {
+    return eliminate_of(mixtures_.handle(), resident, nullptr, min_obs);
+  }
+
+  // Trainer::train's schedule (Training.cpp:44-235): from the trainer's model -- normally the flat start MixtureModel(dimension,
+  // num_mixtures, ...) -- to a model of up to 2^num_splits densities per mixture.
+  //   1. linear segmentation: every segment's `sil w1 sil ... sil` automaton, frame t of T at position t * N / T of its N positions
+  //      (equal shares; our own variant of the reference's first alignment)
+  //   2. accumulate(first_pass) / finalize
+  //   3. per split: split / accumulate / finalize / eliminate / accumulate / finalize
+  //   4. per alignment round: re-alignment (realign's aligner), then num_estimates x accumulate / finalize
+  // After every finalize the average AM score along the current alignment (calc_am_score) is recorded.  The statistics of every pass
+  // come to the host (sr_accumulate_corpus with its four arrays): the split and the eliminate that follow a finalize need the mean
+  // weights of the pass before it, and a corpus handle belongs to the model it was uploaded for, so every new model gets its own upload.
+  struct TrainSchedule {
+    uint32_t num_splits = 0, num_aligns = 0, num_estimates = 1;
+    double min_obs = 0.0;    // a density splits / survives with at least this many observations
+    double epsilon = 0.2;    // children sit epsilon standard deviations either side of the parent
+    MixtureModel::VarianceModel pooling = MixtureModel::NO_POOLING;
+    bool max_approx = true;
+  };
+  struct TrainResult {
+    std::unique_ptr<MixtureModel> model;
+    std::vector<double> am_scores;            // after every finalize, in order
+    std::vector<AlignmentItem> alignment;     // the last alignment
+  };
+  TrainResult train(Corpus const& corpus, TrainSchedule const& sch) {
+    const size_t n = corpus.get_corpus_size();
+    const uint64_t F = corpus.get_total_frame_count();
+    std::vector<uint16_t> automata, states(std::max<uint64_t>(F, 1));
+    std::vector<uint64_t> aut_off;
+    segment_automata(corpus, automata, aut_off);
+    for (size_t u = 0; u < n; u++) {  // 1. linear segmentation
+      const uint64_t f0 = corpus.frame_offsets()[u], T = corpus.frame_offsets()[u + 1] - f0, N = aut_off[u + 1] - aut_off[u];
+      for (uint64_t t = 0; t < T; t++) states[f0 + t] = automata[aut_off[u] + t * N / T];
+    }
+    TrainResult r;
+    typedef std::unique_ptr<sr_model, int (*)(sr_model*)> Owned;
+    Owned cur(nullptr, sr_model_destroy);
+    sr_model* h = mixtures_.handle();
+    Statistics st;
+    // accumulate on h / finalize -> cur (and h), the AM score of the new model recorded
+    auto estimate = [&](bool first_pass) {
+      accumulate_on(h, corpus, states, first_pass, sch.max_approx, st);
+      uint32_t d = 0, S = 0, n_mean = 0, n_var = 0;
+      uint64_t C = 0;
+      check(sr_model_info(h, &d, &S, &C));
+      check(sr_model_tying_info(h, &n_mean, &n_var));
+      std::vector<uint32_t> off(S + 1), dm(std::max<uint64_t>(C, 1)), dv(std::max<uint64_t>(C, 1));
+      check(sr_model_topology(h, off.data(), dm.data(), dv.data()));
+      sr_model* next = nullptr;
+      check(sr_model_create_from_statistics(mixtures_.device(), d, S, off.data(), n_mean, n_var, dm.data(), dv.data(), st.mean_acc.data(),
+                                            st.mean_w.data(), st.var_acc.data(), st.var_w.data(), (int)sch.pooling,
+                                            sch.max_approx ? 1 : 0, &next));
+      cur.reset(next);
+      h = next;
+      r.am_scores.push_back(am_score_of(h, corpus, states));
+    };
+    auto reshape = [&](bool do_split) {
+      sr_model* next = nullptr;
+      check(do_split ? sr_model_split(h, nullptr, st.mean_w.data(), sch.min_obs, sch.epsilon, (int)sch.pooling, &next, nullptr)
+                     : sr_model_eliminate(h, nullptr, st.mean_w.data(), sch.min_obs, &next, nullptr));
+      cur.reset(next);
+      h = next;
+    };
+    estimate(true);                                    // 2.
+    for (uint32_t s = 0; s < sch.num_splits; s++) {    // 3.
+      reshape(true);
+      estimate(false);
+      reshape(false);
+      estimate(false);
+    }
+    for (uint32_t a = 0; a < sch.num_aligns; a++) {    // 4.
+      std::vector<double> cost;
+      align_states(h, corpus, automata, aut_off, states, cost);
+      for (uint32_t e = 0; e < sch.num_estimates; e++) estimate(false);
+    }
+    r.alignment.assign(F, AlignmentItem());
+    for (uint64_t t = 0; t < F; t++) { r.alignment[t].state = states[t]; r.alignment[t].weight = 1; r.alignment[t].count = 1; }
+    r.model.reset(new MixtureModel(cur.release(), mixtures_));
+    return r;
+  }
+
   // Trainer::calc_am_score (Training.cpp:585-612): sequential sum of score(frame, aligned state) / frames
   double calc_am_score(Corpus const& corpus, std::vector<AlignmentItem> const& alignment) {
     const uint64_t F = corpus.get_total_frame_count();
     std::vector<uint16_t> states(std::max<uint64_t>(F, 1));
     for (uint64_t t = 0; t < F; t++) states[t] = alignment[t].state;
+    return am_score_of(mixtures_.handle(), corpus, states);
+  }
+
+ private:
+  double am_score_of(sr_model* h, Corpus const& corpus, std::vector<uint16_t> const& states) {
+    const uint64_t F = corpus.get_total_frame_count();
     std::vector<double> per_frame(std::max<uint64_t>(F, 1));
     sr_corpus* c = nullptr;
-    check(sr_corpus_upload(mixtures_.handle(), corpus.features(), corpus.frame_offsets(), (uint32_t)corpus.get_corpus_size(), &c));
-    const int rc = sr_path_scores_corpus(mixtures_.handle(), c, states.data(), mixtures_.gmm_kernel, per_frame.data());
+    check(sr_corpus_upload(h, corpus.features(), corpus.frame_offsets(), (uint32_t)corpus.get_corpus_size(), &c));
+    const int rc = sr_path_scores_corpus(h, c, states.data(), mixtures_.gmm_kernel, per_frame.data());
     sr_corpus_destroy(c);
     check(rc);
     double total_score = 0.0;
     for (uint64_t t = 0; t < F; t++) total_score += per_frame[t];
     return total_score / F;
   }
-
- private:
+  // the aligner of realign() over every segment, on model h
+  void align_states(sr_model* h, Corpus const& corpus, std::vector<uint16_t> const& automata, std::vector<uint64_t> const& aut_off,
+                    std::vector<uint16_t>& states, std::vector<double>& cost) {
+    const size_t n = corpus.get_corpus_size();
+    const double tdp[3] = {tdp_.tdp_loop, tdp_.tdp_forward, tdp_.tdp_skip};
+    sr_corpus* c = nullptr;
+    check(sr_corpus_upload(h, corpus.features(), corpus.frame_offsets(), (uint32_t)n, &c));
+    states.assign(std::max<uint64_t>(corpus.get_total_frame_count(), 1), 0);
+    cost.assign(std::max<size_t>(n, 1), 0.0);
+    const int rc = alignment_pruning_
+                       ? sr_align_corpus_pruned(h, c, automata.data(), aut_off.data(), tdp, tdp_.silence_state, pruning_threshold_,
+                                                mixtures_.gmm_kernel, states.data(), cost.data())
+                       : sr_align_corpus(h, c, automata.data(), aut_off.data(), tdp, tdp_.silence_state, mixtures_.gmm_kernel,
+                                         states.data(), cost.data());
+    sr_corpus_destroy(c);
+    check(rc);
+  }
+  // sr_accumulate_corpus of an alignment on model h, the statistics brought to the host
+  void accumulate_on(sr_model* h, Corpus const& corpus, std::vector<uint16_t> const& states, bool first_pass, bool max_approx,
+                     Statistics& st) {
+    uint32_t n_mean = 0, n_var = 0;
+    check(sr_model_tying_info(h, &n_mean, &n_var));
+    const size_t D = mixtures_.dimension;
+    st.mean_acc.assign(std::max<size_t>(n_mean * D, 1), 0.0); st.mean_w.assign(std::max<size_t>(n_mean, 1), 0.0);
+    st.var_acc.assign(std::max<size_t>(n_var * D, 1), 0.0); st.var_w.assign(std::max<size_t>(n_var, 1), 0.0);
+    sr_corpus* c = nullptr;
+    check(sr_corpus_upload(h, corpus.features(), corpus.frame_offsets(), (uint32_t)corpus.get_corpus_size(), &c));
+    const int rc = sr_accumulate_corpus(h, c, states.data(), first_pass ? 1 : 0, max_approx ? 1 : 0, st.mean_acc.data(), st.mean_w.data(),
+                                        st.var_acc.data(), st.var_w.data());
+    sr_corpus_destroy(c);
+    check(rc);
+  }
+  static const double* checked_weights(sr_model* h, std::vector<double> const& mean_w) {
+    uint32_t n_mean = 0, n_var = 0;
+    check(sr_model_tying_info(h, &n_mean, &n_var));
+    if (mean_w.size() < n_mean) throw std::invalid_argument("split / eliminate: one weight per mean row");
+    return mean_w.data();
+  }
+  std::unique_ptr<MixtureModel> split_of(sr_model* h, sr_corpus* c, const double* w, double min_obs, double epsilon) {
+    sr_model* next = nullptr;
+    check(sr_model_split(h, c, w, min_obs, epsilon, (int)mixtures_.var_model, &next, nullptr));
+    return std::unique_ptr<MixtureModel>(new MixtureModel(next, mixtures_));
+  }
+  std::unique_ptr<MixtureModel> eliminate_of(sr_model* h, sr_corpus* c, const double* w, double min_obs) {
+    sr_model* next = nullptr;
+    check(sr_model_eliminate(h, c, w, min_obs, &next, nullptr));
+    return std::unique_ptr<MixtureModel>(new MixtureModel(next, mixtures_));
+  }
   // every segment's automaton (build_segment_automaton), concatenated, with offsets
   void segment_automata(Corpus const& corpus, std::vector<uint16_t>& automata, std::vector<uint64_t>& aut_off) const {
     automata.clear();

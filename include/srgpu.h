@@ -288,6 +288,41 @@ SR_API int sr_accumulate_corpus(sr_model* m, sr_corpus* c, const uint16_t* state
  * (for the host-side logarithms, see sr_model_create_from_statistics) cross the bus. */
 SR_API int sr_model_create_from_accumulated(sr_model* m, sr_corpus* c, int pooling, int max_approx, sr_model** out);
 
+/* ---- growing and pruning mixtures: the split and eliminate steps of Trainer::train (Training.cpp:44-235) ----------------------
+ * These follow the reference's SCHEDULE (split / accumulate / finalize / eliminate / accumulate / finalize), not the bits of its
+ * MixtureModel::split / eliminate: the operations are the ones specified here.  Both take the per mean row observation weights
+ * [n_mean] from exactly one source: the host array mean_w as sr_accumulate_corpus returns it (c NULL), or the statistics a call of
+ * sr_accumulate_corpus / sr_baum_welch_corpus with NULL outputs left in c (mean_w NULL).  `m` and `c` are untouched; *out is a
+ * model in its own right (every scoring route works on it) with its own tying, which sr_model_topology / sr_model_tying_info report
+ * and the next sr_accumulate_corpus fills.  out_parent (optional) [C']: the density of m every density of *out came from.  The
+ * topology is host integer work; the per-density tables are written on the device from m's (FP64, no contraction), so C x D
+ * doubles never cross the bus.  No atomics: two identical calls return identical bits.
+ *
+ * sr_model_split: density k with mean row r = dens_mean[k] splits iff mean_w[r] >= min_obs (a NaN weight does not).  A mixture
+ * keeps its densities in their slots and the upper children of those that split follow, in their parents' order.  The lower child
+ * keeps the parent's (mean row, var row); the j-th upper child, counted in mixture order over the whole model, gets mean row
+ * n_mean + j and var row n_var + j (pooling 2, none) or the parent's var row (pooling 0 global, 1 mixture).  Per dimension i:
+ * delta_i = epsilon * sqrt(1.0 / inv_var_i); lower child mean_i - delta_i, upper child mean_i + delta_i; both children get
+ * logw - M_LN2 (host); inv_vars and norm of both, and every table of a density that does not split, are the parent's bits.  The
+ * tables are a seed: the accumulate / finalize pass that follows re-estimates everything.
+ *
+ * sr_model_eliminate: a density survives iff its weight is >= min_obs; a non-empty mixture that would lose every density keeps its
+ * heaviest one (ties: the lowest index; NaN ranks below everything; all NaN: the first); empty mixtures stay empty.  Survivors keep
+ * their order and the bits of their means, inv_vars and norm; logw' = log(w_k / sum of the mixture's surviving weights, added in
+ * mixture order) through the host's log.  Mean and var rows no survivor references are dropped, the rest renumbered in ascending
+ * old index (sr_mixset_write's rule).
+ *
+ * Errors, all before any launch, *out left NULL: SR_EINVAL for a NULL m or out, min_obs or epsilon negative, NaN or infinite, an
+ * unknown pooling, both weight sources or neither, a corpus of another model or one that holds no statistics of m; SR_ELIMIT for
+ * a split model of 2^31 densities or more. */
+SR_API int sr_model_split(sr_model* m, sr_corpus* c, const double* mean_w, double min_obs, double epsilon, int pooling,
+                          sr_model** out, uint32_t* out_parent);
+SR_API int sr_model_eliminate(sr_model* m, sr_corpus* c, const double* mean_w, double min_obs, sr_model** out, uint32_t* out_parent);
+/* The per-density tables in sr_model_create's shape: means, inv_vars [C x dim], norm, logw [C]; any pointer may be NULL.  A model
+ * from sr_model_create fed with them (plus sr_model_set_tying) scores bit-identically.  For checkpoints: a split model has no
+ * statistics to write until the next E-step. */
+SR_API int sr_model_tables(const sr_model* m, double* means, double* inv_vars, double* norm, double* logw);
+
 /* ---- Baum-Welch: forward-backward over the aligner's automata and topology ---------------------------------------
  * Same automata, 0-1-2 topology and transition penalties as sr_align_corpus (keyed on the SOURCE position; any jump out of
  * silence costs `forward`), summed over all paths instead of minimised.  F_u = -log sum_paths exp(-cost), so

@@ -30,6 +30,7 @@ SYMBOLS = [
     "sr_last_error", "sr_device_count", "sr_model_create", "sr_model_load_mixset", "sr_model_destroy", "sr_model_info",
     "sr_corpus_upload", "sr_corpus_upload_async", "sr_corpus_wait", "sr_corpus_destroy", "sr_shard_utterances", "sr_recognize_batch_multi", "sr_score_corpus", "sr_score_frames", "sr_lexicon_create",
     "sr_lexicon_destroy", "sr_lexicon_describe", "sr_recognize_corpus", "sr_traceback_corpus", "sr_traceback_words", "sr_recognize_batch", "sr_align_corpus", "sr_align_corpus_pruned", "sr_path_scores_corpus", "sr_model_create_from_statistics", "sr_model_create_from_accumulated", "sr_mixset_write", "sr_model_set_tying", "sr_model_tying_info", "sr_model_topology", "sr_accumulate_corpus",
+    "sr_model_split", "sr_model_eliminate", "sr_model_tables",
     "sr_state_posteriors_corpus", "sr_baum_welch_corpus", "sr_word_posteriors_corpus", "sr_recognize_confidence_corpus",
     "sr_net_occupancies_corpus", "sr_mmi_statistics_corpus", "sr_model_create_from_mmi_statistics",
     "sr_smbr_max_positions", "sr_net_accuracies_corpus", "sr_smbr_statistics_corpus",
@@ -115,6 +116,9 @@ def lib():
         L.sr_path_scores_corpus.argtypes = [vp, vp, vp, i32, vp]
         L.sr_model_create_from_statistics.argtypes = [i32, u32, u32, vp, u32, u32, vp, vp, vp, vp, vp, vp, i32, i32, C.POINTER(vp)]
         L.sr_model_create_from_accumulated.argtypes = [vp, vp, i32, i32, C.POINTER(vp)]
+        L.sr_model_split.argtypes = [vp, vp, vp, dbl, dbl, i32, C.POINTER(vp), vp]
+        L.sr_model_eliminate.argtypes = [vp, vp, vp, dbl, C.POINTER(vp), vp]
+        L.sr_model_tables.argtypes = [vp, vp, vp, vp, vp]
         L.sr_mixset_write.argtypes = [C.c_char_p, u32, u32, vp, u32, u32, vp, vp, vp, vp, vp, vp]
         L.sr_model_set_tying.argtypes = [vp, u32, u32, vp, vp]
         L.sr_model_tying_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
@@ -235,6 +239,51 @@ class Model:
         dm, dv = np.zeros(self.n_densities, np.uint32), np.zeros(self.n_densities, np.uint32)
         _check(lib().sr_model_topology(self.h, _ptr(off), _ptr(dm), _ptr(dv)))
         return off, dm, dv
+
+    def tying_info(self):
+        """-> (n_mean, n_var): the accumulator rows of this model's tying"""
+        nm, nv = C.c_uint32(), C.c_uint32()
+        _check(lib().sr_model_tying_info(self.h, C.byref(nm), C.byref(nv)))
+        return nm.value, nv.value
+
+    def tables(self):
+        """-> (means f64[C, D], inv_vars f64[C, D], norm f64[C], logw f64[C]): the per-density tables, in from_tables' shape
+        (sr_model_tables)."""
+        n, D = self.n_densities, self.dim
+        means, ivars, norm, logw = np.zeros((n, D)), np.zeros((n, D)), np.zeros(n), np.zeros(n)
+        _check(lib().sr_model_tables(self.h, _ptr(means), _ptr(ivars), _ptr(norm), _ptr(logw)))
+        return means, ivars, norm, logw
+
+    def _weights(self, weights):
+        """the per mean row weights of split() / eliminate(): a Corpus holding statistics of this model, or a host array"""
+        if isinstance(weights, Corpus):
+            return weights.h, None
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if len(w) != self.tying_info()[0]:
+            raise ValueError("one weight per mean row")
+        return None, w
+
+    def split(self, weights, min_obs, epsilon, pooling=POOL_NONE, parents=False):
+        """sr_model_split: every density whose mean row has weight >= min_obs becomes two, epsilon standard deviations apart on
+        either side -> new Model [, parent u32[C']].  weights: mean_w as Corpus.accumulate returns it, or the Corpus that
+        accumulate_on_device() left the statistics in."""
+        c, w = self._weights(weights)
+        h = C.c_void_p()
+        cap = self.n_densities * 2
+        par = np.zeros(max(cap, 1), np.uint32)
+        _check(lib().sr_model_split(self.h, c, _ptr(w), float(min_obs), float(epsilon), pooling, C.byref(h), _ptr(par)))
+        out = Model(h)
+        return (out, par[: out.n_densities].copy()) if parents else out
+
+    def eliminate(self, weights, min_obs, parents=False):
+        """sr_model_eliminate: the densities whose mean row has weight < min_obs go (a mixture keeps its heaviest), the rest are
+        renormalised and their rows renumbered -> new Model [, parent u32[C']]."""
+        c, w = self._weights(weights)
+        h = C.c_void_p()
+        par = np.zeros(max(self.n_densities, 1), np.uint32)
+        _check(lib().sr_model_eliminate(self.h, c, _ptr(w), float(min_obs), C.byref(h), _ptr(par)))
+        out = Model(h)
+        return (out, par[: out.n_densities].copy()) if parents else out
 
     def close(self):
         if self.h:
