@@ -4,6 +4,8 @@
 // Nothing here computes scores or paths on the host: every sr_score_* / sr_recognize_* / sr_align_*
 // call runs the HIP kernels of gmm_mfma.hip / gmm_exact.hip / viterbi_decode.hip / viterbi_align.hip
 // and fails loudly (SR_EHIP / SR_ENODEV) when no gfx950 device is usable.  There is no CPU fallback.
+// The forward-backward style passes (fb_check .. sr_bigram_lattice_nbest) plan their launch groups, step order and mixture lists
+// with fb_plan.h, host code that is tested on its own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,6 +25,7 @@
 #include <vector>
 
 #include "../../include/srgpu.h"
+#include "fb_plan.h"
 #include "host_util.h"
 #include "kernels.h"
 #include "traceback.h"
@@ -516,7 +519,7 @@ int launch_scoring(sr_model* m, const float* d_feats, uint64_t n_frames, int gmm
 }
 
 // utterance chunks whose score table fits the workspace
-struct Chunk { uint32_t u0, u1; uint64_t f0, f1; };
+using srplan::Chunk;
 std::vector<Chunk> make_chunks(const sr_corpus* c, size_t chunk_frames) {
   std::vector<Chunk> out;
   // chunks of whole utterances, at most chunk_frames each (a longer utterance is a chunk of its own), and of about equal size
@@ -1767,6 +1770,94 @@ int sr_model_create_from_accumulated(sr_model* m, sr_corpus* c, int pooling, int
   });
 }
 
+// ---- what the forward-backward style passes below share: fb_plan.h plans; these check, size and copy -----------------------------
+using srplan::Group;
+
+// An utterance's workspace against m->fb_budget: a launch group takes its first utterance whatever it costs (fb_plan.h), so every
+// utterance has to fit alone.  tables: the lattices' word-end tables in place of a trellis.
+static int check_fits(const sr_model* m, uint32_t u, uint64_t bytes, bool tables = false) {
+  if (bytes <= m->fb_budget) return SR_OK;
+  return fail(SR_ELIMIT, "utterance %u: %s of %llu bytes %s the forward-backward workspace of %llu (SRGPU_FB_MB)", u,
+              tables ? "word-end tables" : "trellis", (unsigned long long)bytes, tables ? "exceed" : "exceeds",
+              (unsigned long long)m->fb_budget);
+}
+// ... for every utterance of the cost prefix a pass cuts its launch groups with
+static int check_fits(const sr_model* m, const std::vector<uint64_t>& cost) {
+  for (uint32_t u = 0; u + 1 < cost.size(); u++)
+    if (int rc = check_fits(m, u, cost[u + 1] - cost[u])) return rc;
+  return SR_OK;
+}
+// the cost prefix of trellises at tr_off[U + 1]: 8 bytes per cell
+static std::vector<uint64_t> trellis_cost(const std::vector<uint64_t>& tr_off) {
+  std::vector<uint64_t> cost(tr_off);
+  for (uint64_t& x : cost) x *= 8;
+  return cost;
+}
+
+extern "C++" {
+// The item path (launch_fb_items, launch_occ_items, launch_smbr_items, launch_bgocc_items): a launch group of at most max_gf frames
+// counts, scans and appends its items to the corpus' c->fb_item_* (at most item_bound) behind the counter c->fb_base.
+static int ensure_items(sr_corpus* c, uint64_t max_gf, uint64_t F, uint64_t item_bound, size_t* scan_bytes) {
+  *scan_bytes = fb_scan_temp_bytes(max_gf);
+  HIP_TRY(c->fb_scan_temp.ensure(*scan_bytes));
+  HIP_TRY(c->fb_cnt.ensure(max_gf)); HIP_TRY(c->fb_scan.ensure(max_gf)); HIP_TRY(c->fb_base.ensure(1));
+  HIP_TRY(c->fb_item_off.ensure(F + 1));
+  HIP_TRY(c->fb_item_frame.ensure(item_bound)); HIP_TRY(c->fb_item_mix.ensure(item_bound)); HIP_TRY(c->fb_item_w.ensure(item_bound));
+  return SR_OK;
+}
+template <class Args>  // FbArgs, OccItemArgs, BgOccItemArgs (kernels.h)
+static void item_fields(Args* a, sr_corpus* c) {
+  a->group_cnt = c->fb_cnt.p; a->item_base = c->fb_base.p; a->item_off = c->fb_item_off.p;
+  a->item_frame = c->fb_item_frame.p; a->item_mix = c->fb_item_mix.p; a->item_w = c->fb_item_w.p;
+}
+// ahead of a pass' first launch group, on its stream
+static hipError_t reset_item_count(DevBuf<uint32_t>& base, hipStream_t s) { return hipMemsetAsync(base.p, 0, sizeof(uint32_t), s); }
+static int read_item_count(const DevBuf<uint32_t>& base, uint64_t* n_items) {
+  uint32_t n = 0;
+  HIP_TRY(hipMemcpy(&n, base.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  *n_items = n;
+  return SR_OK;
+}
+
+// The top items per frame an entry point may give out: all three arrays or none (*post), at most max_items a frame.
+static int top_items_arguments(const void* out_count, const void* out_id, const void* out_weight, const char* id_name, uint32_t max_items,
+                               bool* post) {
+  *post = out_count || out_id || out_weight;
+  if (*post && (!out_count || !out_id || !out_weight))
+    return fail(SR_EINVAL, "null output (pass out_count, %s and out_weight, or none)", id_name);
+  if (*post && (max_items == 0 || max_items > 65535)) return fail(SR_EINVAL, "max_items must be 1 .. 65535 (got %u)", max_items);
+  return SR_OK;
+}
+template <class Id>
+static int ensure_top_items(uint64_t F, uint32_t max_items, DevBuf<uint16_t>& count, DevBuf<Id>& id, DevBuf<double>& weight) {
+  HIP_TRY(count.ensure(F));
+  HIP_TRY(id.ensure((size_t)F * max_items));
+  HIP_TRY(weight.ensure((size_t)F * max_items));
+  return SR_OK;
+}
+template <class Id>
+static int copy_top_items(uint64_t F, uint32_t max_items, const DevBuf<uint16_t>& count, const DevBuf<Id>& id, const DevBuf<double>& weight,
+                          uint16_t* out_count, Id* out_id, double* out_weight) {
+  HIP_TRY(hipMemcpy(out_count, count.p, sizeof(uint16_t) * F, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_id, id.p, sizeof(Id) * F * max_items, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_weight, weight.p, sizeof(double) * F * max_items, hipMemcpyDeviceToHost));
+  return SR_OK;
+}
+// the top items of the items a pass left in c->fb_item_*, through launch_top (launch_fb_top, launch_smbr_top), to the host
+template <class LaunchTop>
+static int top_of_items(sr_model* m, sr_corpus* c, uint32_t max_items, LaunchTop launch_top, uint16_t* out_count, uint16_t* out_state,
+                        double* out_weight) {
+  const uint64_t F = c->n_frames;
+  if (F == 0) return SR_OK;
+  int rc = ensure_top_items(F, max_items, c->fb_count, c->fb_state, c->fb_weight);
+  if (rc) return rc;
+  HIP_TRY(launch_top(c->fb_item_off.p, c->fb_item_mix.p, c->fb_item_w.p, F, max_items, c->fb_count.p, c->fb_state.p, c->fb_weight.p,
+                     m->s_gmm));
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  return copy_top_items(F, max_items, c->fb_count, c->fb_state, c->fb_weight, out_count, out_state, out_weight);
+}
+}  // extern "C++"
+
 // ---- forward-backward (viterbi_fb.hip) -----------------------------------------------------------------------------------
 // The argument checks both entry points share: the aligner's, with N_u <= 2 T_u - 1 (a path must exist) in place of N_u <= T_u.
 static int fb_check(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
@@ -1783,9 +1874,7 @@ static int fb_check(sr_model* m, sr_corpus* c, const uint16_t* automata, const u
       return fail(SR_EINVAL, "utterance %u: automaton length %llu: no path through it in %llu frames (at most 2 T - 1 positions)", u,
                   (unsigned long long)N, (unsigned long long)T);
     if ((rc = check_automaton(m, automata, aut_off, u))) return rc;
-    if (8 * N * T > m->fb_budget)
-      return fail(SR_ELIMIT, "utterance %u: trellis of %llu bytes exceeds the forward-backward workspace of %llu (SRGPU_FB_MB)", u,
-                  (unsigned long long)(8 * N * T), (unsigned long long)m->fb_budget);
+    if ((rc = check_fits(m, u, 8 * N * T))) return rc;
   }
   return SR_OK;
 }
@@ -1802,77 +1891,44 @@ static int fb_pass(sr_model* m, sr_corpus* c, const uint16_t* automata, const ui
   if (U == 0) return SR_OK;
   // per utterance: trellis offset; its automaton's distinct mixtures (ascending) and the positions carrying each
   std::vector<uint64_t> tr_off(U + 1, 0);
-  std::vector<uint32_t> mix_off(U + 1, 0), slot_beg;
-  std::vector<uint16_t> mix, slot_pos;
+  srplan::MixLists<uint16_t> ml;
   uint64_t item_bound = 0;
-  std::vector<std::pair<uint16_t, uint16_t>> ps;
   for (uint32_t u = 0; u < U; u++) {
     const uint64_t N = aut_off[u + 1] - aut_off[u], T = c->frame_off[u + 1] - c->frame_off[u];
     tr_off[u + 1] = tr_off[u] + N * T;
-    ps.clear();
-    for (uint64_t i = 0; i < N; i++) ps.push_back({automata[aut_off[u] + i], (uint16_t)i});
-    std::sort(ps.begin(), ps.end());
-    for (size_t i = 0; i < ps.size(); i++) {
-      if (i == 0 || ps[i].first != ps[i - 1].first) {
-        mix.push_back(ps[i].first);
-        slot_beg.push_back((uint32_t)slot_pos.size());
-      }
-      slot_pos.push_back(ps[i].second);
-    }
-    mix_off[u + 1] = (uint32_t)mix.size();
-    item_bound += T * (mix_off[u + 1] - mix_off[u]);
+    ml.add(automata + aut_off[u], N);
+    item_bound += T * ml.n_mix(u);
   }
-  slot_beg.push_back((uint32_t)slot_pos.size());
   if (want_items && item_bound >= (1ull << 31)) return fail(SR_ELIMIT, "too many (frame, mixture) posteriors");
   AutomatonScoring sc;
   int rc = automaton_scoring_setup(m, c, automata, aut_off, gmm_kernel, &sc);
   if (rc) return rc;
-  // launch groups: consecutive utterances of a chunk within the trellis budget (fb_check: every utterance fits alone)
-  struct Group { uint32_t u0, u1, max_n; };
-  std::vector<std::vector<Group>> groups(sc.chunks.size());
-  uint64_t ws = 1, max_gf = 1;
-  for (size_t ci = 0; ci < sc.chunks.size(); ci++) {
-    const Chunk& ch = sc.chunks[ci];
-    for (uint32_t u = ch.u0; u < ch.u1;) {
-      uint32_t v = u, max_n = 1;
-      while (v < ch.u1 && (v == u || 8 * (tr_off[v + 1] - tr_off[u]) <= m->fb_budget)) {
-        max_n = std::max<uint32_t>(max_n, (uint32_t)(aut_off[v + 1] - aut_off[v]));
-        v++;
-      }
-      groups[ci].push_back({u, v, max_n});
-      ws = std::max<uint64_t>(ws, tr_off[v] - tr_off[u]);
-      max_gf = std::max<uint64_t>(max_gf, c->frame_off[v] - c->frame_off[u]);
-      u = v;
-    }
-  }
+  const srplan::Groups groups = srplan::launch_groups(sc.chunks, trellis_cost(tr_off).data(), m->fb_budget);
   HIP_TRY(c->fb_trellis_off.upload(tr_off.data(), U + 1));
-  HIP_TRY(c->fb_trellis.ensure(ws));
+  HIP_TRY(c->fb_trellis.ensure(std::max<uint64_t>(1, groups.max_span(tr_off.data()))));
+  FbArgs fa{};
   size_t scan_bytes = 0;
   if (want_items) {
-    HIP_TRY(c->fb_mix_off.upload(mix_off.data(), U + 1));
-    HIP_TRY(c->fb_mix.upload(mix.data(), mix.size()));
-    HIP_TRY(c->fb_slot_beg.upload(slot_beg.data(), slot_beg.size()));
-    HIP_TRY(c->fb_slot_pos.upload(slot_pos.data(), slot_pos.size()));
-    scan_bytes = fb_scan_temp_bytes(max_gf);
-    HIP_TRY(c->fb_scan_temp.ensure(scan_bytes));
-    HIP_TRY(c->fb_cnt.ensure(max_gf)); HIP_TRY(c->fb_scan.ensure(max_gf)); HIP_TRY(c->fb_base.ensure(1));
-    HIP_TRY(c->fb_item_off.ensure(F + 1));
-    HIP_TRY(c->fb_item_frame.ensure(item_bound)); HIP_TRY(c->fb_item_mix.ensure(item_bound)); HIP_TRY(c->fb_item_w.ensure(item_bound));
+    HIP_TRY(c->fb_mix_off.upload(ml.mix_off.data(), U + 1));
+    HIP_TRY(c->fb_mix.upload(ml.mix.data(), ml.mix.size()));
+    HIP_TRY(c->fb_slot_beg.upload(ml.slot_beg.data(), ml.slot_beg.size()));
+    HIP_TRY(c->fb_slot_pos.upload(ml.slot_pos.data(), ml.slot_pos.size()));
+    if ((rc = ensure_items(c, std::max<uint64_t>(1, groups.max_span(c->frame_off.data())), F, item_bound, &scan_bytes))) return rc;
   }
-  FbArgs fa{};
   fa.ld = m->ld; fa.frame_off = c->d_frame_off.p; fa.automata = c->automata.p; fa.aut_off = c->aut_off.p;
   fa.tdp_loop = tdp[0]; fa.tdp_forward = tdp[1]; fa.tdp_skip = tdp[2]; fa.silence_state = silence_state;
   fa.trellis = c->fb_trellis.p; fa.trellis_off = c->fb_trellis_off.p; fa.out_cost = c->out_cost.p;
   fa.mix_off = c->fb_mix_off.p; fa.mix = c->fb_mix.p; fa.slot_beg = c->fb_slot_beg.p; fa.slot_pos = c->fb_slot_pos.p;
-  fa.floor = posterior_floor; fa.group_cnt = c->fb_cnt.p; fa.item_base = c->fb_base.p; fa.item_off = c->fb_item_off.p;
-  fa.item_frame = c->fb_item_frame.p; fa.item_mix = c->fb_item_mix.p; fa.item_w = c->fb_item_w.p;
+  fa.floor = posterior_floor;
+  item_fields(&fa, c);
   size_t ci = 0;  // run_chunks searches the chunks in order
   rc = run_chunks(m, sc.chunks,
       [&](const Chunk& ch, double* table) -> int { return automaton_scoring_chunk(m, c, sc, ch, table); },
       [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
-        if (want_items && ci == 0) HIP_TRY(hipMemsetAsync(c->fb_base.p, 0, sizeof(uint32_t), s));
-        for (const Group& g : groups[ci]) {
-          fa.scores = table; fa.frame_base = ch.f0; fa.utt_first = g.u0; fa.n_utts = g.u1 - g.u0; fa.max_positions = g.max_n;
+        if (want_items && ci == 0) HIP_TRY(reset_item_count(c->fb_base, s));
+        for (const Group& g : groups.of_chunk[ci]) {
+          fa.scores = table; fa.frame_base = ch.f0; fa.utt_first = g.u0; fa.n_utts = g.u1 - g.u0; fa.max_positions = 1;
+          for (uint32_t u = g.u0; u < g.u1; u++) fa.max_positions = std::max(fa.max_positions, (uint32_t)(aut_off[u + 1] - aut_off[u]));
           fa.group_f0 = c->frame_off[g.u0];
           HIP_TRY(launch_fb_forward(fa, s));
           HIP_TRY(launch_fb_backward(fa, s));
@@ -1883,11 +1939,7 @@ static int fb_pass(sr_model* m, sr_corpus* c, const uint16_t* automata, const ui
         return SR_OK;
       });
   if (rc) return rc;
-  if (want_items) {
-    uint32_t n = 0;
-    HIP_TRY(hipMemcpy(&n, c->fb_base.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    *n_items = n;
-  }
+  if (want_items && (rc = read_item_count(c->fb_base, n_items))) return rc;
   if (m->profiling) {  // trellis traffic per (frame, position): alpha out, alpha in + gamma out, gamma in (items)
     m->prof.frames += F;
     m->prof.search_bytes += (want_items ? 32.0 : 24.0) * (double)tr_off[U];
@@ -1901,25 +1953,13 @@ int sr_state_posteriors_corpus(sr_model* m, sr_corpus* c, const uint16_t* automa
   return guarded(__func__, [&]() -> int {
   int rc = fb_check(m, c, automata, aut_off, tdp, posterior_floor, out_cost);
   if (rc) return rc;
-  const bool post = out_count || out_state || out_weight;
-  if (post && (!out_count || !out_state || !out_weight)) return fail(SR_EINVAL, "null output (pass out_count, out_state and out_weight, or none)");
-  if (post && (max_items == 0 || max_items > 65535)) return fail(SR_EINVAL, "max_items must be 1 .. 65535 (got %u)", max_items);
-  const uint64_t F = c->n_frames;
+  bool post = false;
+  if ((rc = top_items_arguments(out_count, out_state, out_weight, "out_state", max_items, &post))) return rc;
   const uint32_t U = c->n_utts;
   uint64_t n_items = 0;
   if ((rc = fb_pass(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, post, &n_items))) return rc;
   if (U) HIP_TRY(hipMemcpy(out_cost, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToHost));
-  if (!post || F == 0) return SR_OK;
-  HIP_TRY(c->fb_count.ensure(F));
-  HIP_TRY(c->fb_state.ensure((size_t)F * max_items));
-  HIP_TRY(c->fb_weight.ensure((size_t)F * max_items));
-  HIP_TRY(launch_fb_top(c->fb_item_off.p, c->fb_item_mix.p, c->fb_item_w.p, F, max_items, c->fb_count.p, c->fb_state.p, c->fb_weight.p,
-                        m->s_gmm));
-  HIP_TRY(hipStreamSynchronize(m->s_gmm));
-  HIP_TRY(hipMemcpy(out_count, c->fb_count.p, sizeof(uint16_t) * F, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_state, c->fb_state.p, sizeof(uint16_t) * F * max_items, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_weight, c->fb_weight.p, sizeof(double) * F * max_items, hipMemcpyDeviceToHost));
-  return SR_OK;
+  return post ? top_of_items(m, c, max_items, launch_fb_top, out_count, out_state, out_weight) : SR_OK;
   });
 }
 
@@ -2175,6 +2215,11 @@ int sr_corpus_transform(sr_model* m, sr_corpus* c, const uint32_t* utt_speaker, 
 }
 
 // ---- forward-backward over the recognition network (viterbi_netfb.hip) ----------------------------------------------------
+// 8 B per (frame, position)
+static std::vector<uint64_t> netfb_cost(const sr_corpus* c, const sr_lexicon* l) {
+  return srplan::linear_cost(c->frame_off.data(), c->n_utts, 8ull * l->net.n_slots);
+}
+
 static int netfb_check(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor) {
   int rc = check_corpus(m, c);
   if (rc) return rc;
@@ -2187,13 +2232,7 @@ static int netfb_check(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search
   if (P > netfb_max_slots())
     return fail(SR_ELIMIT, "%llu lexicon positions exceed the network forward-backward's %llu", (unsigned long long)P,
                 (unsigned long long)netfb_max_slots());
-  for (uint32_t u = 0; u < c->n_utts; u++) {
-    const uint64_t T = c->frame_off[u + 1] - c->frame_off[u];
-    if (8 * P * T > m->fb_budget)
-      return fail(SR_ELIMIT, "utterance %u: trellis of %llu bytes exceeds the forward-backward workspace of %llu (SRGPU_FB_MB)", u,
-                  (unsigned long long)(8 * P * T), (unsigned long long)m->fb_budget);
-  }
-  return SR_OK;
+  return check_fits(m, netfb_cost(c, l));
 }
 
 // The launch groups of a pass -- consecutive utterances of a chunk whose trellises (8 B per frame and position) fit m->fb_budget
@@ -2201,23 +2240,14 @@ static int netfb_check(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search
 // backward, word posteriors, then per_group(args, frames of the group).
 extern "C++" {
 struct NetFbPass {
-  struct Group { uint32_t u0, u1; };
-  std::vector<std::vector<Group>> groups;  // per chunk
+  srplan::Groups groups;
   NetFbArgs a{};
   size_t ci = 0;  // run_chunks searches the chunks in order
 
   int setup(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, const std::vector<Chunk>& chunks) {
     const uint64_t P = l->net.n_slots;
-    uint64_t max_gf = 1;
-    groups.assign(chunks.size(), {});
-    for (size_t i = 0; i < chunks.size(); i++)
-      for (uint32_t u = chunks[i].u0; u < chunks[i].u1;) {
-        uint32_t v = u + 1;
-        while (v < chunks[i].u1 && 8 * P * (c->frame_off[v + 1] - c->frame_off[u]) <= m->fb_budget) v++;
-        groups[i].push_back({u, v});
-        max_gf = std::max<uint64_t>(max_gf, c->frame_off[v] - c->frame_off[u]);
-        u = v;
-      }
+    groups = srplan::launch_groups(chunks, netfb_cost(c, l).data(), m->fb_budget);
+    const uint64_t max_gf = std::max<uint64_t>(1, groups.max_span(c->frame_off.data()));
     HIP_TRY(c->fb_trellis.ensure(max_gf * P));
     HIP_TRY(c->nf_post.ensure(max_gf * l->net.n_words));
     HIP_TRY(c->out_cost.ensure(c->n_utts));
@@ -2230,7 +2260,7 @@ struct NetFbPass {
   }
   template <class PerGroup>
   int run(sr_corpus* c, const Chunk& ch, const double* table, hipStream_t s, PerGroup per_group) {
-    for (const Group& g : groups[ci]) {
+    for (const Group& g : groups.of_chunk[ci]) {
       a.scores = table; a.frame_base = ch.f0; a.utt_first = g.u0; a.n_utts = g.u1 - g.u0; a.group_f0 = c->frame_off[g.u0];
       const uint64_t n = c->frame_off[g.u1] - c->frame_off[g.u0];
       HIP_TRY(launch_netfb_forward(a, s));
@@ -2259,19 +2289,14 @@ int sr_word_posteriors_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr
   int rc = netfb_check(m, c, l, p, scale, posterior_floor);
   if (rc) return rc;
   if (!out_cost) return fail(SR_EINVAL, "null argument");
-  const bool post = out_count || out_word || out_weight;
-  if (post && (!out_count || !out_word || !out_weight)) return fail(SR_EINVAL, "null output (pass out_count, out_word and out_weight, or none)");
-  if (post && (max_items == 0 || max_items > 65535)) return fail(SR_EINVAL, "max_items must be 1 .. 65535 (got %u)", max_items);
+  bool post = false;
+  if ((rc = top_items_arguments(out_count, out_word, out_weight, "out_word", max_items, &post))) return rc;
   const uint64_t F = c->n_frames;
   std::vector<Chunk> chunks;
   if ((rc = prepare_chunks(m, c, &chunks))) return rc;
   NetFbPass fp;
   if ((rc = fp.setup(m, c, l, p, scale, chunks))) return rc;
-  if (post) {
-    HIP_TRY(c->nf_count.ensure(F));
-    HIP_TRY(c->nf_word.ensure((size_t)F * max_items));
-    HIP_TRY(c->nf_weight.ensure((size_t)F * max_items));
-  }
+  if (post && (rc = ensure_top_items(F, max_items, c->nf_count, c->nf_word, c->nf_weight))) return rc;
   rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); },
       [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
         return fp.run(c, ch, table, s, [&](const NetFbArgs& a, uint64_t n) -> int {
@@ -2283,10 +2308,7 @@ int sr_word_posteriors_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr
   if (m->profiling) m->prof.frames += F;
   if ((rc = netfb_costs(c, scale, out_cost))) return rc;
   if (!post || F == 0) return SR_OK;
-  HIP_TRY(hipMemcpy(out_count, c->nf_count.p, sizeof(uint16_t) * F, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_word, c->nf_word.p, sizeof(uint32_t) * F * max_items, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_weight, c->nf_weight.p, sizeof(double) * F * max_items, hipMemcpyDeviceToHost));
-  return SR_OK;
+  return copy_top_items(F, max_items, c->nf_count, c->nf_word, c->nf_weight, out_count, out_word, out_weight);
   });
 }
 
@@ -2333,6 +2355,10 @@ int sr_recognize_confidence_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, con
 // ---- forward-backward over the bigram search network (viterbi_bigram_fb.hip) -----------------------------------------------------
 // bytes of one group's workspace beside the trellis, per utterance: vec, prod, wend (Kp each), the two x rows, m
 static uint64_t bgfb_utt_bytes(const sr_bigram* b) { return 24ull * bgfb_padded(b->net.n_words) + 16ull * b->net.n_positions + 8; }
+// 8 B per (frame, position) and the vectors
+static std::vector<uint64_t> bgfb_cost(const sr_corpus* c, const sr_bigram* b) {
+  return srplan::linear_cost(c->frame_off.data(), c->n_utts, 8ull * b->net.n_positions, bgfb_utt_bytes(b));
+}
 
 static int bgfb_check(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, double posterior_floor) {
   int rc = check_corpus(m, c);
@@ -2343,23 +2369,15 @@ static int bgfb_check(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, dou
   if (b->lm_min == -std::numeric_limits<float>::infinity()) return fail(SR_EINVAL, "the language model has a score of -inf");
   if (-scale * (double)b->lm_min > 700.0)
     return fail(SR_ELIMIT, "scale %g x LM score %g: exp(%g) is not representable", scale, (double)b->lm_min, -scale * (double)b->lm_min);
-  const uint64_t P = b->net.n_positions;
-  for (uint32_t u = 0; u < c->n_utts; u++) {
-    const uint64_t T = c->frame_off[u + 1] - c->frame_off[u];
-    if (8 * P * T + bgfb_utt_bytes(b) > m->fb_budget)
-      return fail(SR_ELIMIT, "utterance %u: trellis of %llu bytes exceeds the forward-backward workspace of %llu (SRGPU_FB_MB)", u,
-                  (unsigned long long)(8 * P * T + bgfb_utt_bytes(b)), (unsigned long long)m->fb_budget);
-  }
-  return SR_OK;
+  return check_fits(m, bgfb_cost(c, b));
 }
 
 // The launch groups of a pass, cut like NetFbPass' with the per-utterance vectors counted in, each with its utterances ordered longest
 // first.  run() enqueues a chunk's groups: per frame the step and the product, forward then backward, the word posteriors, per_group.
 extern "C++" {
 struct BgFbPass {
-  struct Group { uint32_t u0, u1, t_max; };
-  std::vector<std::vector<Group>> groups;  // per chunk
-  std::vector<uint32_t> order;             // [U] each group's range, longest first
+  srplan::Groups groups;
+  srplan::StepOrder steps;                 // each group's range, longest first
   BgFbArgs a{};
   const double *lk = nullptr, *lkT = nullptr;
   const uint32_t* d_order = nullptr;       // `order` on the device
@@ -2367,24 +2385,12 @@ struct BgFbPass {
   size_t ci = 0;
 
   int setup(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, const std::vector<Chunk>& chunks) {
-    const uint64_t P = b->net.n_positions, per_utt = bgfb_utt_bytes(b);
+    const uint64_t P = b->net.n_positions;
     const uint32_t W = b->net.n_words, Kp = bgfb_padded(W), U = c->n_utts;
-    auto len = [&](uint32_t u) { return c->frame_off[u + 1] - c->frame_off[u]; };
-    uint64_t max_gf = 1;
-    uint32_t max_gu = 1;
-    groups.assign(chunks.size(), {});
-    order.resize(U);
-    for (uint32_t u = 0; u < U; u++) order[u] = u;
-    for (size_t i = 0; i < chunks.size(); i++)
-      for (uint32_t u = chunks[i].u0; u < chunks[i].u1;) {
-        uint32_t v = u + 1;
-        while (v < chunks[i].u1 && 8 * P * (c->frame_off[v + 1] - c->frame_off[u]) + (v + 1 - u) * per_utt <= m->fb_budget) v++;
-        std::stable_sort(order.begin() + u, order.begin() + v, [&](uint32_t x, uint32_t y) { return len(x) > len(y); });
-        groups[i].push_back({u, v, (uint32_t)len(order[u])});
-        max_gf = std::max<uint64_t>(max_gf, c->frame_off[v] - c->frame_off[u]);
-        max_gu = std::max(max_gu, v - u);
-        u = v;
-      }
+    groups = srplan::launch_groups(chunks, bgfb_cost(c, b).data(), m->fb_budget);
+    steps = srplan::StepOrder(groups, c->frame_off.data(), U);
+    const uint64_t max_gf = std::max<uint64_t>(1, groups.max_span(c->frame_off.data()));
+    const uint32_t max_gu = std::max(1u, groups.max_utts());
     // exp(-kappa lm) and its transpose: built once per (net, kappa)
     if (b->fb_kappa != scale || !b->fb_lk.p) {
       b->fb_kappa = 0.0;
@@ -2404,7 +2410,7 @@ struct BgFbPass {
     HIP_TRY(c->bgfb_wend.ensure(rows * Kp));
     HIP_TRY(c->bgfb_m.ensure(rows));
     HIP_TRY(c->bgfb_xb.ensure(2 * (size_t)max_gu * P));
-    HIP_TRY(c->bgfb_order.upload(order.data(), order.size()));
+    HIP_TRY(c->bgfb_order.upload(steps.order.data(), steps.order.size()));
     d_order = c->bgfb_order.p;
     HIP_TRY(hipMemset(c->bgfb_vec.p, 0, rows * Kp * sizeof(double)));  // (the padding columns h >= W stay 0 from here on)
     if (U) HIP_TRY(hipMemset(c->out_cost.p, 0, sizeof(double) * U));  // T_u = 0: F_u = 0, the start hypothesis is a word end
@@ -2421,22 +2427,18 @@ struct BgFbPass {
   }
   template <class PerGroup>
   int run(sr_corpus* c, const Chunk& ch, const double* table, hipStream_t s, PerGroup per_group) {
-    for (const Group& g : groups[ci]) {
+    for (const Group& g : groups.of_chunk[ci]) {
       a.scores = table; a.frame_base = ch.f0; a.group_f0 = c->frame_off[g.u0];
       a.order = d_order + g.u0; a.n_group = g.u1 - g.u0;
-      auto alive = [&](uint32_t t) {  // utterances of the group with more than t frames: a prefix of its order
-        uint32_t n = 0;
-        while (n < a.n_group && c->frame_off[order[g.u0 + n] + 1] - c->frame_off[order[g.u0 + n]] > t) n++;
-        return n;
-      };
-      for (uint32_t t = 0; t < g.t_max; t++) {
-        a.t = t; a.n_alive = alive(t);
+      const uint32_t t_max = steps.t_max(g);
+      for (uint32_t t = 0; t < t_max; t++) {
+        a.t = t; a.n_alive = steps.alive(g, t);
         HIP_TRY(launch_bgfb_forward(a, s));
-        const uint32_t next = alive(t + 1);  // only those that go on need their entries
+        const uint32_t next = steps.alive(g, t + 1);  // only those that go on need their entries
         HIP_TRY(launch_bgfb_product(lk, a.vec, a.prod, a.Kp, next, s));
       }
-      for (uint32_t t = g.t_max; t-- > 0;) {
-        a.t = t; a.n_alive = alive(t);
+      for (uint32_t t = t_max; t-- > 0;) {
+        a.t = t; a.n_alive = steps.alive(g, t);
         HIP_TRY(launch_bgfb_backward(a, s));
         if (t) HIP_TRY(launch_bgfb_product(lkT, a.vec, a.prod, a.Kp, a.n_alive, s));
       }
@@ -2465,19 +2467,14 @@ int sr_bigram_word_posteriors_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, in
   int rc = bgfb_check(m, c, b, scale, posterior_floor);
   if (rc) return rc;
   if (!out_cost) return fail(SR_EINVAL, "null argument");
-  const bool post = out_count || out_word || out_weight;
-  if (post && (!out_count || !out_word || !out_weight)) return fail(SR_EINVAL, "null output (pass out_count, out_word and out_weight, or none)");
-  if (post && (max_items == 0 || max_items > 65535)) return fail(SR_EINVAL, "max_items must be 1 .. 65535 (got %u)", max_items);
+  bool post = false;
+  if ((rc = top_items_arguments(out_count, out_word, out_weight, "out_word", max_items, &post))) return rc;
   const uint64_t F = c->n_frames;
   std::vector<Chunk> chunks;
   if ((rc = prepare_chunks(m, c, &chunks))) return rc;
   BgFbPass fp;
   if ((rc = fp.setup(m, c, b, scale, chunks))) return rc;
-  if (post) {
-    HIP_TRY(c->nf_count.ensure(F));
-    HIP_TRY(c->nf_word.ensure((size_t)F * max_items));
-    HIP_TRY(c->nf_weight.ensure((size_t)F * max_items));
-  }
+  if (post && (rc = ensure_top_items(F, max_items, c->nf_count, c->nf_word, c->nf_weight))) return rc;
   rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, gmm_kernel, table); },
       [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
         return fp.run(c, ch, table, s, [&](const BgFbArgs& a, uint64_t n) -> int {
@@ -2488,10 +2485,7 @@ int sr_bigram_word_posteriors_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, in
   if (m->profiling) m->prof.frames += F;
   if ((rc = netfb_costs(c, scale, out_cost))) return rc;
   if (!post || F == 0) return SR_OK;
-  HIP_TRY(hipMemcpy(out_count, c->nf_count.p, sizeof(uint16_t) * F, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_word, c->nf_word.p, sizeof(uint32_t) * F * max_items, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_weight, c->nf_weight.p, sizeof(double) * F * max_items, hipMemcpyDeviceToHost));
-  return SR_OK;
+  return copy_top_items(F, max_items, c->nf_count, c->nf_word, c->nf_weight, out_count, out_word, out_weight);
   });
 }
 
@@ -2564,9 +2558,7 @@ static int occ_check(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_p
     if (N > netfb_max_slots())
       return fail(SR_ELIMIT, "utterance %u: chain of %llu positions exceeds the network forward-backward's %llu", u, (unsigned long long)N,
                   (unsigned long long)netfb_max_slots());
-    if (8 * N * T > m->fb_budget)
-      return fail(SR_ELIMIT, "utterance %u: trellis of %llu bytes exceeds the forward-backward workspace of %llu (SRGPU_FB_MB)", u,
-                  (unsigned long long)(8 * N * T), (unsigned long long)m->fb_budget);
+    if ((rc = check_fits(m, u, 8 * N * T))) return rc;
   }
   return SR_OK;
 }
@@ -2616,55 +2608,23 @@ static int occ_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_pa
   if (chain) build_chains(l, U, trans, trans_off, &ch);
   // the mixture lists: the distinct mixtures (ascending) of the lexicon, or of each chain, and the positions carrying each
   std::vector<uint64_t> tr_off(U + 1, 0);
-  std::vector<uint32_t> mix_off(U + 1, 0), slot_beg;
-  std::vector<uint16_t> mix, slot_pos;
-  std::vector<std::pair<uint16_t, uint16_t>> ps;
-  auto add_lists = [&](const uint32_t* info, uint64_t N) {
-    ps.clear();
-    for (uint64_t i = 0; i < N; i++) ps.push_back({(uint16_t)(info[i] & 0xFFFFu), (uint16_t)i});
-    std::sort(ps.begin(), ps.end());
-    for (size_t i = 0; i < ps.size(); i++) {
-      if (i == 0 || ps[i].first != ps[i - 1].first) {
-        mix.push_back(ps[i].first);
-        slot_beg.push_back((uint32_t)slot_pos.size());
-      }
-      slot_pos.push_back(ps[i].second);
-    }
-  };
+  srplan::MixLists<uint16_t> ml;
   uint64_t item_bound = 0;
-  if (!chain) add_lists(l->h_slot_info.data(), P);
+  if (!chain) ml.add(l->h_slot_info.data(), P, 0xFFFFu);
   for (uint32_t u = 0; u < U; u++) {
     const uint64_t N = chain ? ch.off[u + 1] - ch.off[u] : P, T = c->frame_off[u + 1] - c->frame_off[u];
     tr_off[u + 1] = tr_off[u] + N * T;
-    if (chain) {
-      add_lists(ch.info.data() + ch.off[u], N);
-      mix_off[u + 1] = (uint32_t)mix.size();
-    }
-    item_bound += T * (chain ? mix_off[u + 1] - mix_off[u] : mix.size());
+    if (chain) ml.add(ch.info.data() + ch.off[u], N, 0xFFFFu);
+    item_bound += T * ml.n_mix(chain ? u : 0);
   }
-  slot_beg.push_back((uint32_t)slot_pos.size());
   if (want_items && item_bound >= (1ull << 31)) return fail(SR_ELIMIT, "too many (frame, mixture) occupancies");
   std::vector<Chunk> chunks;
   int rc = prepare_chunks(m, c, &chunks);
   if (rc) return rc;
-  // launch groups: consecutive utterances of a chunk within the trellis budget (occ_check: every utterance fits alone)
-  struct Group { uint32_t u0, u1, max_n; };
-  std::vector<std::vector<Group>> groups(chunks.size());
-  uint64_t ws = 1, max_gf = 1;
-  for (size_t ci = 0; ci < chunks.size(); ci++)
-    for (uint32_t u = chunks[ci].u0; u < chunks[ci].u1;) {
-      uint32_t v = u, max_n = 1;
-      while (v < chunks[ci].u1 && (v == u || 8 * (tr_off[v + 1] - tr_off[u]) <= m->fb_budget)) {
-        max_n = std::max<uint32_t>(max_n, chain ? (uint32_t)(ch.off[v + 1] - ch.off[v]) : (uint32_t)P);
-        v++;
-      }
-      groups[ci].push_back({u, v, max_n});
-      ws = std::max<uint64_t>(ws, tr_off[v] - tr_off[u]);
-      max_gf = std::max<uint64_t>(max_gf, c->frame_off[v] - c->frame_off[u]);
-      u = v;
-    }
+  const srplan::Groups groups = srplan::launch_groups(chunks, trellis_cost(tr_off).data(), m->fb_budget);
+  const uint64_t max_gf = std::max<uint64_t>(1, groups.max_span(c->frame_off.data()));
   HIP_TRY(c->fb_trellis_off.upload(tr_off.data(), U + 1));
-  HIP_TRY(c->fb_trellis.ensure(ws));
+  HIP_TRY(c->fb_trellis.ensure(std::max<uint64_t>(1, groups.max_span(tr_off.data()))));
   if (chain) {
     HIP_TRY(c->mmi_chain_off.upload(ch.off.data(), U + 1));
     HIP_TRY(c->mmi_info.upload(ch.info.data(), ch.info.size()));
@@ -2675,15 +2635,11 @@ static int occ_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_pa
   }
   size_t scan_bytes = 0;
   if (want_items) {
-    if (chain) HIP_TRY(c->fb_mix_off.upload(mix_off.data(), U + 1));
-    HIP_TRY(c->fb_mix.upload(mix.data(), mix.size()));
-    HIP_TRY(c->fb_slot_beg.upload(slot_beg.data(), slot_beg.size()));
-    HIP_TRY(c->fb_slot_pos.upload(slot_pos.data(), slot_pos.size()));
-    scan_bytes = fb_scan_temp_bytes(max_gf);
-    HIP_TRY(c->fb_scan_temp.ensure(scan_bytes));
-    HIP_TRY(c->fb_cnt.ensure(max_gf)); HIP_TRY(c->fb_scan.ensure(max_gf)); HIP_TRY(c->fb_base.ensure(1));
-    HIP_TRY(c->fb_item_off.ensure(F + 1));
-    HIP_TRY(c->fb_item_frame.ensure(item_bound)); HIP_TRY(c->fb_item_mix.ensure(item_bound)); HIP_TRY(c->fb_item_w.ensure(item_bound));
+    if (chain) HIP_TRY(c->fb_mix_off.upload(ml.mix_off.data(), U + 1));
+    HIP_TRY(c->fb_mix.upload(ml.mix.data(), ml.mix.size()));
+    HIP_TRY(c->fb_slot_beg.upload(ml.slot_beg.data(), ml.slot_beg.size()));
+    HIP_TRY(c->fb_slot_pos.upload(ml.slot_pos.data(), ml.slot_pos.size()));
+    if ((rc = ensure_items(c, max_gf, F, item_bound, &scan_bytes))) return rc;
   }
   NetFbArgs na{};
   na.net = l->net; na.ld = m->ld; na.frame_off = c->d_frame_off.p; na.scale = scale; na.word_penalty = p->word_penalty;
@@ -2694,18 +2650,18 @@ static int occ_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_pa
   ca.chain_off = c->mmi_chain_off.p; ca.info = c->mmi_info.p; ca.src = c->mmi_src.p; ca.dst = c->mmi_dst.p; ca.sil_len = ch.sil_len;
   ca.trellis = c->fb_trellis.p; ca.trellis_off = c->fb_trellis_off.p; ca.out_cost = c->out_cost.p;
   OccItemArgs ia{};
-  ia.frame_off = c->d_frame_off.p; ia.trellis = c->fb_trellis.p; ia.n_cols = (uint32_t)P; ia.n_mix = chain ? 0u : (uint32_t)mix.size();
+  ia.frame_off = c->d_frame_off.p; ia.trellis = c->fb_trellis.p; ia.n_cols = (uint32_t)P; ia.n_mix = chain ? 0u : ml.n_mix(0);
   if (chain) { ia.trellis_off = c->fb_trellis_off.p; ia.chain_off = c->mmi_chain_off.p; ia.mix_off = c->fb_mix_off.p; }
   ia.mix = c->fb_mix.p; ia.slot_beg = c->fb_slot_beg.p; ia.slot_pos = c->fb_slot_pos.p; ia.gate = gate; ia.floor = posterior_floor;
-  ia.group_cnt = c->fb_cnt.p; ia.item_base = c->fb_base.p; ia.item_off = c->fb_item_off.p;
-  ia.item_frame = c->fb_item_frame.p; ia.item_mix = c->fb_item_mix.p; ia.item_w = c->fb_item_w.p;
+  item_fields(&ia, c);
   size_t ci = 0;  // run_chunks searches the chunks in order
   rc = run_chunks(m, chunks, [&](const Chunk& k, double* table) { return score_chunk(m, c, k.f0, k.f1, p->gmm_kernel, table); },
       [&](const Chunk& k, const double* table, hipStream_t s) -> int {
-        if (want_items && ci == 0) HIP_TRY(hipMemsetAsync(c->fb_base.p, 0, sizeof(uint32_t), s));
-        for (const Group& g : groups[ci]) {
+        if (want_items && ci == 0) HIP_TRY(reset_item_count(c->fb_base, s));
+        for (const Group& g : groups.of_chunk[ci]) {
           if (chain) {
-            ca.scores = table; ca.frame_base = k.f0; ca.utt_first = g.u0; ca.n_utts = g.u1 - g.u0; ca.max_positions = g.max_n;
+            ca.scores = table; ca.frame_base = k.f0; ca.utt_first = g.u0; ca.n_utts = g.u1 - g.u0; ca.max_positions = 1;
+            for (uint32_t u = g.u0; u < g.u1; u++) ca.max_positions = std::max(ca.max_positions, (uint32_t)(ch.off[u + 1] - ch.off[u]));
             HIP_TRY(launch_chain_forward(ca, s));
             HIP_TRY(launch_chain_backward(ca, s));
           } else {
@@ -2722,17 +2678,43 @@ static int occ_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_pa
         return SR_OK;
       });
   if (rc) return rc;
-  if (want_items) {
-    uint32_t n = 0;
-    HIP_TRY(hipMemcpy(&n, c->fb_base.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    *n_items = n;
-  }
+  if (want_items && (rc = read_item_count(c->fb_base, n_items))) return rc;
   if (m->profiling) {  // trellis traffic per (frame, position) as the network pass counts it: alpha out, alpha in + part out, part in
     m->prof.frames += F;
     m->prof.search_bytes += 32.0 * (double)tr_off[U];
   }
   return SR_OK;
 }
+
+// Numerator and denominator statistics of MMI training, for sr_mmi_statistics_corpus and sr_bigram_mmi_statistics_corpus:
+// pass(numerator, gate, &n_items) is the entry point's occupancy pass over the transcripts' chains (numerator) or the free network.
+extern "C++" {
+template <class Pass>
+static int mmi_statistics(sr_model* m, sr_corpus* c, double scale, int max_approx, double* out_num_cost, double* out_den_cost,
+                          double* num_mean_acc, double* num_mean_w, double* num_var_acc, double* num_var_w, double* den_mean_acc,
+                          double* den_mean_w, double* den_var_acc, double* den_var_w, Pass pass) {
+  if (!out_num_cost || !out_den_cost || !num_mean_acc || !num_mean_w || !num_var_acc || !num_var_w || !den_mean_acc || !den_mean_w ||
+      !den_var_acc || !den_var_w)
+    return fail(SR_EINVAL, "null output");
+  const uint32_t U = c->n_utts;
+  int rc;
+  c->acc_valid = false;
+  // numerator: the transcripts' chains.  Its costs stay on the device as the denominator's gate: an utterance without a path through
+  // its transcript (F_num = +inf) contributes to neither side.
+  uint64_t n_items = 0;
+  if ((rc = pass(true, nullptr, &n_items))) return rc;
+  if ((rc = netfb_costs(c, scale, out_num_cost))) return rc;
+  HIP_TRY(c->mmi_num_cost.ensure(U));
+  if (U) HIP_TRY(hipMemcpy(c->mmi_num_cost.p, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToDevice));
+  if ((rc = accumulate_items(m, c, n_items, 0, max_approx, true, num_mean_acc, num_mean_w, num_var_acc, num_var_w))) return rc;
+  // denominator: the free network
+  if ((rc = pass(false, c->mmi_num_cost.p, &n_items))) return rc;
+  if ((rc = netfb_costs(c, scale, out_den_cost))) return rc;
+  rc = accumulate_items(m, c, n_items, 0, max_approx, true, den_mean_acc, den_mean_w, den_var_acc, den_var_w);
+  c->acc_valid = false;  // (the handle holds one side only: nothing for sr_model_create_from_accumulated)
+  return rc;
+}
+}  // extern "C++"
 
 int sr_net_occupancies_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
                               uint32_t max_items, const uint32_t* trans, const uint64_t* trans_off, double* out_cost,
@@ -2742,24 +2724,12 @@ int sr_net_occupancies_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr
   int rc = occ_check(m, c, l, p, scale, posterior_floor, trans, trans_off, &constrained);
   if (rc) return rc;
   if (!out_cost) return fail(SR_EINVAL, "null argument");
-  const bool post = out_count || out_state || out_weight;
-  if (post && (!out_count || !out_state || !out_weight)) return fail(SR_EINVAL, "null output (pass out_count, out_state and out_weight, or none)");
-  if (post && (max_items == 0 || max_items > 65535)) return fail(SR_EINVAL, "max_items must be 1 .. 65535 (got %u)", max_items);
-  const uint64_t F = c->n_frames;
+  bool post = false;
+  if ((rc = top_items_arguments(out_count, out_state, out_weight, "out_state", max_items, &post))) return rc;
   uint64_t n_items = 0;
   if ((rc = occ_pass(m, c, l, p, scale, posterior_floor, trans, constrained ? trans_off : nullptr, post, nullptr, &n_items))) return rc;
   if ((rc = netfb_costs(c, scale, out_cost))) return rc;
-  if (!post || F == 0) return SR_OK;
-  HIP_TRY(c->fb_count.ensure(F));
-  HIP_TRY(c->fb_state.ensure((size_t)F * max_items));
-  HIP_TRY(c->fb_weight.ensure((size_t)F * max_items));
-  HIP_TRY(launch_fb_top(c->fb_item_off.p, c->fb_item_mix.p, c->fb_item_w.p, F, max_items, c->fb_count.p, c->fb_state.p, c->fb_weight.p,
-                        m->s_gmm));
-  HIP_TRY(hipStreamSynchronize(m->s_gmm));
-  HIP_TRY(hipMemcpy(out_count, c->fb_count.p, sizeof(uint16_t) * F, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_state, c->fb_state.p, sizeof(uint16_t) * F * max_items, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_weight, c->fb_weight.p, sizeof(double) * F * max_items, hipMemcpyDeviceToHost));
-  return SR_OK;
+  return post ? top_of_items(m, c, max_items, launch_fb_top, out_count, out_state, out_weight) : SR_OK;
   });
 }
 
@@ -2772,25 +2742,10 @@ int sr_mmi_statistics_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_
   int rc = occ_check(m, c, l, p, scale, posterior_floor, trans, trans_off, &constrained);
   if (rc) return rc;
   if (!constrained) return fail(SR_EINVAL, "null argument (MMI statistics need the transcripts)");
-  if (!out_num_cost || !out_den_cost || !num_mean_acc || !num_mean_w || !num_var_acc || !num_var_w || !den_mean_acc || !den_mean_w ||
-      !den_var_acc || !den_var_w)
-    return fail(SR_EINVAL, "null output");
-  const uint32_t U = c->n_utts;
-  c->acc_valid = false;
-  // numerator: the transcripts' chains.  Its costs stay on the device as the denominator's gate: an utterance without a path through
-  // its transcript (F_num = +inf) contributes to neither side.
-  uint64_t n_items = 0;
-  if ((rc = occ_pass(m, c, l, p, scale, posterior_floor, trans, trans_off, true, nullptr, &n_items))) return rc;
-  if ((rc = netfb_costs(c, scale, out_num_cost))) return rc;
-  HIP_TRY(c->mmi_num_cost.ensure(U));
-  if (U) HIP_TRY(hipMemcpy(c->mmi_num_cost.p, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToDevice));
-  if ((rc = accumulate_items(m, c, n_items, 0, max_approx, true, num_mean_acc, num_mean_w, num_var_acc, num_var_w))) return rc;
-  // denominator: the free network
-  if ((rc = occ_pass(m, c, l, p, scale, posterior_floor, nullptr, nullptr, true, c->mmi_num_cost.p, &n_items))) return rc;
-  if ((rc = netfb_costs(c, scale, out_den_cost))) return rc;
-  rc = accumulate_items(m, c, n_items, 0, max_approx, true, den_mean_acc, den_mean_w, den_var_acc, den_var_w);
-  c->acc_valid = false;  // (the handle holds one side only: nothing for sr_model_create_from_accumulated)
-  return rc;
+  return mmi_statistics(m, c, scale, max_approx, out_num_cost, out_den_cost, num_mean_acc, num_mean_w, num_var_acc, num_var_w, den_mean_acc,
+                        den_mean_w, den_var_acc, den_var_w, [&](bool numerator, const double* gate, uint64_t* n_items) {
+    return occ_pass(m, c, l, p, scale, posterior_floor, numerator ? trans : nullptr, numerator ? trans_off : nullptr, true, gate, n_items);
+  });
   });
 }
 
@@ -2861,6 +2816,11 @@ int sr_smbr_max_positions(uint32_t* out) {
   return SR_OK;
 }
 
+// 16 B per (frame, position)
+static std::vector<uint64_t> smbr_cost(const sr_corpus* c, const sr_lexicon* l) {
+  return srplan::linear_cost(c->frame_off.data(), c->n_utts, 16ull * l->net.n_slots);
+}
+
 // netfb_check with the accuracy pass' position limit and 16 B per (frame, position), plus the references
 static int smbr_check(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
                       const uint16_t* ref_states) {
@@ -2871,78 +2831,56 @@ static int smbr_check(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_
   if (P > smbr_max_slots())
     return fail(SR_ELIMIT, "%llu lexicon positions exceed the accuracy forward-backward's %llu", (unsigned long long)P,
                 (unsigned long long)smbr_max_slots());
-  for (uint32_t u = 0; u < c->n_utts; u++) {
-    const uint64_t T = c->frame_off[u + 1] - c->frame_off[u];
-    if (16 * P * T > m->fb_budget)
-      return fail(SR_ELIMIT, "utterance %u: trellis of %llu bytes exceeds the forward-backward workspace of %llu (SRGPU_FB_MB)", u,
-                  (unsigned long long)(16 * P * T), (unsigned long long)m->fb_budget);
-  }
-  return SR_OK;
+  return check_fits(m, smbr_cost(c, l));
 }
 
 // NetFbPass for the accuracy recursions: the launch groups are consecutive utterances of a chunk whose trellises (16 B per frame and
 // position) fit m->fb_budget together (smbr_check: every utterance fits alone).  run() enqueues a chunk's groups in order: forward,
-// backward, then per_group(item arguments of the group, frames of the group).
+// backward, then per_group(item arguments of the group, frames of the group).  want_items: the item path is ready (ensure_items) and
+// `ia` writes to c->fb_item_*.
 extern "C++" {
 struct SmbrPass {
-  struct Group { uint32_t u0, u1; };
-  std::vector<std::vector<Group>> groups;  // per chunk
+  srplan::Groups groups;
   SmbrArgs a{};
-  OccItemArgs ia{};  // the free network's mixture lists; the caller points it at its item buffers
-  uint64_t max_gf = 1, item_bound = 0;
+  OccItemArgs ia{};  // the free network's mixture lists
+  uint64_t item_bound = 0;
   size_t scan_bytes = 0;
   size_t ci = 0;  // run_chunks searches the chunks in order
 
   int setup(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double floor, const uint16_t* ref_states,
-            const std::vector<Chunk>& chunks) {
+            bool want_items, const std::vector<Chunk>& chunks) {
     const uint64_t P = l->net.n_slots, F = c->n_frames;
-    groups.assign(chunks.size(), {});
-    for (size_t i = 0; i < chunks.size(); i++)
-      for (uint32_t u = chunks[i].u0; u < chunks[i].u1;) {
-        uint32_t v = u + 1;
-        while (v < chunks[i].u1 && 16 * P * (c->frame_off[v + 1] - c->frame_off[u]) <= m->fb_budget) v++;
-        groups[i].push_back({u, v});
-        max_gf = std::max<uint64_t>(max_gf, c->frame_off[v] - c->frame_off[u]);
-        u = v;
-      }
+    groups = srplan::launch_groups(chunks, smbr_cost(c, l).data(), m->fb_budget);
+    const uint64_t max_gf = std::max<uint64_t>(1, groups.max_span(c->frame_off.data()));
     // the lexicon's distinct mixtures (ascending) and the positions carrying each, as occ_pass lists them
-    std::vector<std::pair<uint16_t, uint16_t>> ps;
-    for (uint64_t i = 0; i < P; i++) ps.push_back({(uint16_t)(l->h_slot_info[i] & 0xFFFFu), (uint16_t)i});
-    std::sort(ps.begin(), ps.end());
-    std::vector<uint32_t> slot_beg;
-    std::vector<uint16_t> mix, slot_pos;
-    for (size_t i = 0; i < ps.size(); i++) {
-      if (i == 0 || ps[i].first != ps[i - 1].first) {
-        mix.push_back(ps[i].first);
-        slot_beg.push_back((uint32_t)slot_pos.size());
-      }
-      slot_pos.push_back(ps[i].second);
-    }
-    slot_beg.push_back((uint32_t)slot_pos.size());
-    item_bound = F * mix.size();
+    srplan::MixLists<uint16_t> ml;
+    ml.add(l->h_slot_info.data(), P, 0xFFFFu);
+    item_bound = F * ml.n_mix(0);
     if (item_bound >= (1ull << 31)) return fail(SR_ELIMIT, "too many (frame, mixture) weights");
     HIP_TRY(c->fb_trellis.ensure(max_gf * 2 * P));
     HIP_TRY(c->smbr_ends.ensure(max_gf * 2));
     HIP_TRY(c->out_cost.ensure(c->n_utts));
     HIP_TRY(c->smbr_acc.ensure(c->n_utts));
     HIP_TRY(c->smbr_ref.upload(ref_states, F));
-    HIP_TRY(c->fb_mix.upload(mix.data(), mix.size()));
-    HIP_TRY(c->fb_slot_beg.upload(slot_beg.data(), slot_beg.size()));
-    HIP_TRY(c->fb_slot_pos.upload(slot_pos.data(), slot_pos.size()));
-    scan_bytes = fb_scan_temp_bytes(max_gf);
-    HIP_TRY(c->fb_scan_temp.ensure(scan_bytes));
-    HIP_TRY(c->fb_cnt.ensure(max_gf)); HIP_TRY(c->fb_scan.ensure(max_gf));
+    HIP_TRY(c->fb_mix.upload(ml.mix.data(), ml.mix.size()));
+    HIP_TRY(c->fb_slot_beg.upload(ml.slot_beg.data(), ml.slot_beg.size()));
+    HIP_TRY(c->fb_slot_pos.upload(ml.slot_pos.data(), ml.slot_pos.size()));
+    if (want_items) {
+      int rc = ensure_items(c, max_gf, F, item_bound, &scan_bytes);
+      if (rc) return rc;
+      item_fields(&ia, c);
+    }
     a.net = l->net; a.ld = m->ld; a.frame_off = c->d_frame_off.p; a.scale = scale; a.word_penalty = p->word_penalty;
     a.ref = c->smbr_ref.p; a.trellis = c->fb_trellis.p; a.ends = c->smbr_ends.p; a.out_cost = c->out_cost.p; a.out_acc = c->smbr_acc.p;
-    ia.frame_off = c->d_frame_off.p; ia.trellis = c->fb_trellis.p; ia.n_cols = (uint32_t)P; ia.n_mix = (uint32_t)mix.size();
-    ia.mix = c->fb_mix.p; ia.slot_beg = c->fb_slot_beg.p; ia.slot_pos = c->fb_slot_pos.p; ia.floor = floor; ia.group_cnt = c->fb_cnt.p;
+    ia.frame_off = c->d_frame_off.p; ia.trellis = c->fb_trellis.p; ia.n_cols = (uint32_t)P; ia.n_mix = ml.n_mix(0);
+    ia.mix = c->fb_mix.p; ia.slot_beg = c->fb_slot_beg.p; ia.slot_pos = c->fb_slot_pos.p; ia.floor = floor;
     // trellis traffic per (frame, position): (alpha, abar) out, both in + the part out, the part in (items)
     if (m->profiling) m->prof.search_bytes += 48.0 * (double)P * (double)F;
     return SR_OK;
   }
   template <class PerGroup>
   int run(sr_corpus* c, const Chunk& ch, const double* table, hipStream_t s, PerGroup per_group) {
-    for (const Group& g : groups[ci]) {
+    for (const Group& g : groups.of_chunk[ci]) {
       a.scores = table; a.frame_base = ch.f0; a.utt_first = g.u0; a.n_utts = g.u1 - g.u0; a.group_f0 = c->frame_off[g.u0];
       HIP_TRY(launch_smbr_forward(a, s));
       HIP_TRY(launch_smbr_backward(a, s));
@@ -2971,23 +2909,16 @@ int sr_net_accuracies_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_
   int rc = smbr_check(m, c, l, p, scale, posterior_floor, ref_states);
   if (rc) return rc;
   if (!out_cost || !out_acc) return fail(SR_EINVAL, "null argument");
-  const bool post = out_count || out_state || out_weight;
-  if (post && (!out_count || !out_state || !out_weight)) return fail(SR_EINVAL, "null output (pass out_count, out_state and out_weight, or none)");
-  if (post && (max_items == 0 || max_items > 65535)) return fail(SR_EINVAL, "max_items must be 1 .. 65535 (got %u)", max_items);
+  bool post = false;
+  if ((rc = top_items_arguments(out_count, out_state, out_weight, "out_state", max_items, &post))) return rc;
   const uint64_t F = c->n_frames;
   std::vector<Chunk> chunks;
   if ((rc = prepare_chunks(m, c, &chunks))) return rc;
   SmbrPass sp;
-  if ((rc = sp.setup(m, c, l, p, scale, posterior_floor, ref_states, chunks))) return rc;
-  if (post) {
-    HIP_TRY(c->fb_base.ensure(1)); HIP_TRY(c->fb_item_off.ensure(F + 1));
-    HIP_TRY(c->fb_item_frame.ensure(sp.item_bound)); HIP_TRY(c->fb_item_mix.ensure(sp.item_bound)); HIP_TRY(c->fb_item_w.ensure(sp.item_bound));
-    sp.ia.item_base = c->fb_base.p; sp.ia.item_off = c->fb_item_off.p;
-    sp.ia.item_frame = c->fb_item_frame.p; sp.ia.item_mix = c->fb_item_mix.p; sp.ia.item_w = c->fb_item_w.p;
-  }
+  if ((rc = sp.setup(m, c, l, p, scale, posterior_floor, ref_states, post, chunks))) return rc;
   rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); },
       [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
-        if (post && sp.ci == 0) HIP_TRY(hipMemsetAsync(c->fb_base.p, 0, sizeof(uint32_t), s));
+        if (post && sp.ci == 0) HIP_TRY(reset_item_count(c->fb_base, s));
         return sp.run(c, ch, table, s, [&](const OccItemArgs& ia, uint64_t n) -> int {
           if (post) HIP_TRY(launch_smbr_items(ia, 0, n, c->fb_scan_temp.p, sp.scan_bytes, c->fb_scan.p, s));
           return SR_OK;
@@ -2996,17 +2927,7 @@ int sr_net_accuracies_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_
   if (rc) return rc;
   if (m->profiling) m->prof.frames += F;
   if ((rc = smbr_costs(c, scale, out_cost, out_acc))) return rc;
-  if (!post || F == 0) return SR_OK;
-  HIP_TRY(c->fb_count.ensure(F));
-  HIP_TRY(c->fb_state.ensure((size_t)F * max_items));
-  HIP_TRY(c->fb_weight.ensure((size_t)F * max_items));
-  HIP_TRY(launch_smbr_top(c->fb_item_off.p, c->fb_item_mix.p, c->fb_item_w.p, F, max_items, c->fb_count.p, c->fb_state.p, c->fb_weight.p,
-                          m->s_gmm));
-  HIP_TRY(hipStreamSynchronize(m->s_gmm));
-  HIP_TRY(hipMemcpy(out_count, c->fb_count.p, sizeof(uint16_t) * F, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_state, c->fb_state.p, sizeof(uint16_t) * F * max_items, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_weight, c->fb_weight.p, sizeof(double) * F * max_items, hipMemcpyDeviceToHost));
-  return SR_OK;
+  return post ? top_of_items(m, c, max_items, launch_smbr_top, out_count, out_state, out_weight) : SR_OK;
   });
 }
 
@@ -3025,23 +2946,19 @@ int sr_smbr_statistics_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr
   std::vector<Chunk> chunks;
   if ((rc = prepare_chunks(m, c, &chunks))) return rc;
   SmbrPass sp;
-  if ((rc = sp.setup(m, c, l, p, scale, posterior_floor, ref_states, chunks))) return rc;
+  if ((rc = sp.setup(m, c, l, p, scale, posterior_floor, ref_states, true, chunks))) return rc;
   // one pass, the items of both signs: the positive ones in the fb_item_* buffers, the negative ones beside them
   const uint64_t nb = sp.item_bound;
-  HIP_TRY(c->fb_base.ensure(1)); HIP_TRY(c->fb_item_off.ensure(F + 1));
-  HIP_TRY(c->fb_item_frame.ensure(nb)); HIP_TRY(c->fb_item_mix.ensure(nb)); HIP_TRY(c->fb_item_w.ensure(nb));
   HIP_TRY(c->smbr_base.ensure(1)); HIP_TRY(c->smbr_item_off.ensure(F + 1));
   HIP_TRY(c->smbr_item_frame.ensure(nb)); HIP_TRY(c->smbr_item_mix.ensure(nb)); HIP_TRY(c->smbr_item_w.ensure(nb));
   rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); },
       [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
         if (sp.ci == 0) {
-          HIP_TRY(hipMemsetAsync(c->fb_base.p, 0, sizeof(uint32_t), s));
-          HIP_TRY(hipMemsetAsync(c->smbr_base.p, 0, sizeof(uint32_t), s));
+          HIP_TRY(reset_item_count(c->fb_base, s));
+          HIP_TRY(reset_item_count(c->smbr_base, s));
         }
-        return sp.run(c, ch, table, s, [&](const OccItemArgs& ia, uint64_t n) -> int {
-          OccItemArgs pos = ia, neg = ia;
-          pos.item_base = c->fb_base.p; pos.item_off = c->fb_item_off.p;
-          pos.item_frame = c->fb_item_frame.p; pos.item_mix = c->fb_item_mix.p; pos.item_w = c->fb_item_w.p;
+        return sp.run(c, ch, table, s, [&](const OccItemArgs& pos, uint64_t n) -> int {
+          OccItemArgs neg = pos;
           neg.item_base = c->smbr_base.p; neg.item_off = c->smbr_item_off.p;
           neg.item_frame = c->smbr_item_frame.p; neg.item_mix = c->smbr_item_mix.p; neg.item_w = c->smbr_item_w.p;
           HIP_TRY(launch_smbr_items(pos, +1, n, c->fb_scan_temp.p, sp.scan_bytes, c->fb_scan.p, s));
@@ -3052,11 +2969,8 @@ int sr_smbr_statistics_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr
   if (rc) return rc;
   if (m->profiling) m->prof.frames += F;
   if ((rc = smbr_costs(c, scale, out_cost, out_acc))) return rc;
-  uint32_t n_pos = 0, n_neg = 0;
-  if (c->n_utts) {
-    HIP_TRY(hipMemcpy(&n_pos, c->fb_base.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&n_neg, c->smbr_base.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-  }
+  uint64_t n_pos = 0, n_neg = 0;
+  if (c->n_utts && ((rc = read_item_count(c->fb_base, &n_pos)) || (rc = read_item_count(c->smbr_base, &n_neg)))) return rc;
   if ((rc = accumulate_items(m, c, n_pos, 0, max_approx, true, num_mean_acc, num_mean_w, num_var_acc, num_var_w))) return rc;
   if (n_neg) {  // the negative side through the same buffers
     HIP_TRY(hipMemcpy(c->fb_item_frame.p, c->smbr_item_frame.p, sizeof(uint32_t) * n_neg, hipMemcpyDeviceToDevice));
@@ -3077,24 +2991,6 @@ struct BgChains {
   std::vector<uint64_t> off;  // [U + 1]
   std::vector<uint32_t> info, src, dst;
   std::vector<double> lmc;
-};
-// the distinct mixtures (ascending) of a set of positions and the positions carrying each
-struct BgMixLists {
-  std::vector<uint32_t> slot_beg, slot_pos;
-  std::vector<uint16_t> mix;
-  std::vector<std::pair<uint16_t, uint32_t>> ps;
-  void add(const uint32_t* info, uint64_t N) {
-    ps.clear();
-    for (uint64_t i = 0; i < N; i++) ps.push_back({(uint16_t)(info[i] & 0xFFFFu), (uint32_t)i});
-    std::sort(ps.begin(), ps.end());
-    for (size_t i = 0; i < ps.size(); i++) {
-      if (i == 0 || ps[i].first != ps[i - 1].first) {
-        mix.push_back(ps[i].first);
-        slot_beg.push_back((uint32_t)slot_pos.size());
-      }
-      slot_pos.push_back(ps[i].second);
-    }
-  }
 };
 }  // extern "C++"
 
@@ -3128,9 +3024,7 @@ static int bgocc_check(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, do
     if (N > bgchain_max_positions())
       return fail(SR_ELIMIT, "utterance %u: chain of %llu positions exceeds the transcript network's %u", u, (unsigned long long)N,
                   bgchain_max_positions());
-    if (8 * N * T > m->fb_budget)
-      return fail(SR_ELIMIT, "utterance %u: trellis of %llu bytes exceeds the forward-backward workspace of %llu (SRGPU_FB_MB)", u,
-                  (unsigned long long)(8 * N * T), (unsigned long long)m->fb_budget);
+    if ((rc = check_fits(m, u, 8 * N * T))) return rc;
   }
   return SR_OK;
 }
@@ -3191,46 +3085,28 @@ static int bgocc_pass(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, d
   BgChains ch;
   if (chain) build_bgchains(b, U, scale, trans, trans_off, &ch);
   std::vector<uint64_t> tr_off(U + 1, 0);
-  std::vector<uint32_t> mix_off(U + 1, 0);
-  BgMixLists ml;
+  srplan::MixLists<uint32_t> ml;
   uint64_t item_bound = 0;
-  if (!chain && want_items) ml.add(b->h_pos_info.data(), P);
+  if (!chain && want_items) ml.add(b->h_pos_info.data(), P, 0xFFFFu);
   for (uint32_t u = 0; u < U; u++) {
     const uint64_t N = chain ? ch.off[u + 1] - ch.off[u] : P, T = c->frame_off[u + 1] - c->frame_off[u];
     tr_off[u + 1] = tr_off[u] + N * T;
-    if (chain && want_items) {
-      ml.add(ch.info.data() + ch.off[u], N);
-      mix_off[u + 1] = (uint32_t)ml.mix.size();
-    }
-    item_bound += T * (chain ? mix_off[u + 1] - mix_off[u] : ml.mix.size());
+    if (!want_items) continue;
+    if (chain) ml.add(ch.info.data() + ch.off[u], N, 0xFFFFu);
+    item_bound += T * ml.n_mix(chain ? u : 0);
   }
-  ml.slot_beg.push_back((uint32_t)ml.slot_pos.size());
   if (want_items && item_bound >= (1ull << 31)) return fail(SR_ELIMIT, "too many (frame, mixture) occupancies");
   std::vector<Chunk> chunks;
   int rc = prepare_chunks(m, c, &chunks);
   if (rc) return rc;
   // the chains' launch groups (bgocc_check: every utterance fits alone); the free network's are BgFbPass'
-  struct Group { uint32_t u0, u1, max_n; };
-  std::vector<std::vector<Group>> groups(chunks.size());
+  srplan::Groups groups;
   BgFbPass fp;
   fp.want_words = false;
-  uint64_t max_gf = 1;
   if (chain) {
-    uint64_t ws = 1;
-    for (size_t ci = 0; ci < chunks.size(); ci++)
-      for (uint32_t u = chunks[ci].u0; u < chunks[ci].u1;) {
-        uint32_t v = u, max_n = 1;
-        while (v < chunks[ci].u1 && (v == u || 8 * (tr_off[v + 1] - tr_off[u]) <= m->fb_budget)) {
-          max_n = std::max<uint32_t>(max_n, (uint32_t)(ch.off[v + 1] - ch.off[v]));
-          v++;
-        }
-        groups[ci].push_back({u, v, max_n});
-        ws = std::max<uint64_t>(ws, tr_off[v] - tr_off[u]);
-        max_gf = std::max<uint64_t>(max_gf, c->frame_off[v] - c->frame_off[u]);
-        u = v;
-      }
+    groups = srplan::launch_groups(chunks, trellis_cost(tr_off).data(), m->fb_budget);
     HIP_TRY(c->fb_trellis_off.upload(tr_off.data(), U + 1));
-    HIP_TRY(c->fb_trellis.ensure(ws));
+    HIP_TRY(c->fb_trellis.ensure(std::max<uint64_t>(1, groups.max_span(tr_off.data()))));
     HIP_TRY(c->mmi_chain_off.upload(ch.off.data(), U + 1));
     HIP_TRY(c->mmi_info.upload(ch.info.data(), ch.info.size()));
     HIP_TRY(c->mmi_src.upload(ch.src.data(), ch.src.size()));
@@ -3238,20 +3114,15 @@ static int bgocc_pass(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, d
     HIP_TRY(c->bgmmi_lmc.upload(ch.lmc.data(), ch.lmc.size()));
   } else {
     if ((rc = fp.setup(m, c, b, scale, chunks))) return rc;
-    for (const auto& gs : fp.groups)
-      for (const auto& g : gs) max_gf = std::max<uint64_t>(max_gf, c->frame_off[g.u1] - c->frame_off[g.u0]);
   }
   size_t scan_bytes = 0;
   if (want_items) {
-    if (chain) HIP_TRY(c->fb_mix_off.upload(mix_off.data(), U + 1));
+    const uint64_t max_gf = std::max<uint64_t>(1, (chain ? groups : fp.groups).max_span(c->frame_off.data()));
+    if (chain) HIP_TRY(c->fb_mix_off.upload(ml.mix_off.data(), U + 1));
     HIP_TRY(c->fb_mix.upload(ml.mix.data(), ml.mix.size()));
     HIP_TRY(c->fb_slot_beg.upload(ml.slot_beg.data(), ml.slot_beg.size()));
     HIP_TRY(c->bgmmi_slot_pos.upload(ml.slot_pos.data(), ml.slot_pos.size()));
-    scan_bytes = fb_scan_temp_bytes(max_gf);
-    HIP_TRY(c->fb_scan_temp.ensure(scan_bytes));
-    HIP_TRY(c->fb_cnt.ensure(max_gf)); HIP_TRY(c->fb_scan.ensure(max_gf)); HIP_TRY(c->fb_base.ensure(1));
-    HIP_TRY(c->fb_item_off.ensure(F + 1));
-    HIP_TRY(c->fb_item_frame.ensure(item_bound)); HIP_TRY(c->fb_item_mix.ensure(item_bound)); HIP_TRY(c->fb_item_w.ensure(item_bound));
+    if ((rc = ensure_items(c, max_gf, F, item_bound, &scan_bytes))) return rc;
   }
   BgChainArgs ca{};
   ca.ld = m->ld; ca.frame_off = c->d_frame_off.p; ca.scale = scale;
@@ -3263,8 +3134,7 @@ static int bgocc_pass(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, d
   ia.frame_off = c->d_frame_off.p; ia.trellis = c->fb_trellis.p; ia.n_cols = (uint32_t)P; ia.n_mix = chain ? 0u : (uint32_t)ml.mix.size();
   if (chain) { ia.trellis_off = c->fb_trellis_off.p; ia.chain_off = c->mmi_chain_off.p; ia.mix_off = c->fb_mix_off.p; }
   ia.mix = c->fb_mix.p; ia.slot_beg = c->fb_slot_beg.p; ia.slot_pos = c->bgmmi_slot_pos.p; ia.gate = gate; ia.floor = posterior_floor;
-  ia.group_cnt = c->fb_cnt.p; ia.item_base = c->fb_base.p; ia.item_off = c->fb_item_off.p;
-  ia.item_frame = c->fb_item_frame.p; ia.item_mix = c->fb_item_mix.p; ia.item_w = c->fb_item_w.p;
+  item_fields(&ia, c);
   auto items = [&](uint32_t u0, uint32_t u1, hipStream_t s) -> int {
     if (!want_items) return SR_OK;
     ia.utt_first = u0; ia.n_utts = u1 - u0; ia.group_f0 = c->frame_off[u0];
@@ -3274,7 +3144,7 @@ static int bgocc_pass(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, d
   size_t ci = 0;  // run_chunks searches the chunks in order
   rc = run_chunks(m, chunks, [&](const Chunk& k, double* table) { return score_chunk(m, c, k.f0, k.f1, gmm_kernel, table); },
       [&](const Chunk& k, const double* table, hipStream_t s) -> int {
-        if (want_items && ci == 0) HIP_TRY(hipMemsetAsync(c->fb_base.p, 0, sizeof(uint32_t), s));
+        if (want_items && ci == 0) HIP_TRY(reset_item_count(c->fb_base, s));
         if (!chain) {
           ci++;
           return fp.run(c, k, table, s, [&](const BgFbArgs& a, uint64_t) -> int {
@@ -3282,8 +3152,9 @@ static int bgocc_pass(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, d
             return items(u0, u0 + a.n_group, s);
           });
         }
-        for (const Group& g : groups[ci]) {
-          ca.scores = table; ca.frame_base = k.f0; ca.utt_first = g.u0; ca.n_utts = g.u1 - g.u0; ca.max_positions = g.max_n;
+        for (const Group& g : groups.of_chunk[ci]) {
+          ca.scores = table; ca.frame_base = k.f0; ca.utt_first = g.u0; ca.n_utts = g.u1 - g.u0; ca.max_positions = 1;
+          for (uint32_t u = g.u0; u < g.u1; u++) ca.max_positions = std::max(ca.max_positions, (uint32_t)(ch.off[u + 1] - ch.off[u]));
           HIP_TRY(launch_bgchain_forward(ca, s));
           HIP_TRY(launch_bgchain_backward(ca, s));
           int r = items(g.u0, g.u1, s);
@@ -3293,11 +3164,7 @@ static int bgocc_pass(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, d
         return SR_OK;
       });
   if (rc) return rc;
-  if (want_items) {
-    uint32_t n = 0;
-    HIP_TRY(hipMemcpy(&n, c->fb_base.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    *n_items = n;
-  }
+  if (want_items && (rc = read_item_count(c->fb_base, n_items))) return rc;
   if (m->profiling) {
     // per (frame, position): alpha out, alpha in + gamma out (the free network: counted by BgFbPass, whose word-posterior read of gamma
     // is the items' count pass here); the items' write pass reads gamma once more
@@ -3316,24 +3183,12 @@ int sr_bigram_occupancies_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gm
   int rc = bgocc_check(m, c, b, scale, posterior_floor, trans, trans_off, !trans_off && (out_count || out_state || out_weight), &constrained);
   if (rc) return rc;
   if (!out_cost) return fail(SR_EINVAL, "null argument");
-  const bool post = out_count || out_state || out_weight;
-  if (post && (!out_count || !out_state || !out_weight)) return fail(SR_EINVAL, "null output (pass out_count, out_state and out_weight, or none)");
-  if (post && (max_items == 0 || max_items > 65535)) return fail(SR_EINVAL, "max_items must be 1 .. 65535 (got %u)", max_items);
-  const uint64_t F = c->n_frames;
+  bool post = false;
+  if ((rc = top_items_arguments(out_count, out_state, out_weight, "out_state", max_items, &post))) return rc;
   uint64_t n_items = 0;
   if ((rc = bgocc_pass(m, c, b, gmm_kernel, scale, posterior_floor, trans, constrained ? trans_off : nullptr, post, nullptr, &n_items))) return rc;
   if ((rc = netfb_costs(c, scale, out_cost))) return rc;
-  if (!post || F == 0) return SR_OK;
-  HIP_TRY(c->fb_count.ensure(F));
-  HIP_TRY(c->fb_state.ensure((size_t)F * max_items));
-  HIP_TRY(c->fb_weight.ensure((size_t)F * max_items));
-  HIP_TRY(launch_fb_top(c->fb_item_off.p, c->fb_item_mix.p, c->fb_item_w.p, F, max_items, c->fb_count.p, c->fb_state.p, c->fb_weight.p,
-                        m->s_gmm));
-  HIP_TRY(hipStreamSynchronize(m->s_gmm));
-  HIP_TRY(hipMemcpy(out_count, c->fb_count.p, sizeof(uint16_t) * F, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_state, c->fb_state.p, sizeof(uint16_t) * F * max_items, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_weight, c->fb_weight.p, sizeof(double) * F * max_items, hipMemcpyDeviceToHost));
-  return SR_OK;
+  return post ? top_of_items(m, c, max_items, launch_fb_top, out_count, out_state, out_weight) : SR_OK;
   });
 }
 
@@ -3346,56 +3201,62 @@ int sr_bigram_mmi_statistics_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int
   int rc = bgocc_check(m, c, b, scale, posterior_floor, trans, trans_off, true, &constrained);
   if (rc) return rc;
   if (!constrained) return fail(SR_EINVAL, "null argument (MMI statistics need the transcripts)");
-  if (!out_num_cost || !out_den_cost || !num_mean_acc || !num_mean_w || !num_var_acc || !num_var_w || !den_mean_acc || !den_mean_w ||
-      !den_var_acc || !den_var_w)
-    return fail(SR_EINVAL, "null output");
-  const uint32_t U = c->n_utts;
-  c->acc_valid = false;
-  // numerator: the transcripts' chains.  Its costs stay on the device as the denominator's gate: an utterance without a path through
-  // its transcript (F_num = +inf) contributes to neither side.
-  uint64_t n_items = 0;
-  if ((rc = bgocc_pass(m, c, b, gmm_kernel, scale, posterior_floor, trans, trans_off, true, nullptr, &n_items))) return rc;
-  if ((rc = netfb_costs(c, scale, out_num_cost))) return rc;
-  HIP_TRY(c->mmi_num_cost.ensure(U));
-  if (U) HIP_TRY(hipMemcpy(c->mmi_num_cost.p, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToDevice));
-  if ((rc = accumulate_items(m, c, n_items, 0, max_approx, true, num_mean_acc, num_mean_w, num_var_acc, num_var_w))) return rc;
-  // denominator: the free network
-  if ((rc = bgocc_pass(m, c, b, gmm_kernel, scale, posterior_floor, nullptr, nullptr, true, c->mmi_num_cost.p, &n_items))) return rc;
-  if ((rc = netfb_costs(c, scale, out_den_cost))) return rc;
-  rc = accumulate_items(m, c, n_items, 0, max_approx, true, den_mean_acc, den_mean_w, den_var_acc, den_var_w);
-  c->acc_valid = false;  // (the handle holds one side only: nothing for sr_model_create_from_accumulated)
-  return rc;
+  return mmi_statistics(m, c, scale, max_approx, out_num_cost, out_den_cost, num_mean_acc, num_mean_w, num_var_acc, num_var_w, den_mean_acc,
+                        den_mean_w, den_var_acc, den_var_w, [&](bool numerator, const double* gate, uint64_t* n_items) {
+    return bgocc_pass(m, c, b, gmm_kernel, scale, posterior_floor, numerator ? trans : nullptr, numerator ? trans_off : nullptr, true, gate,
+                      n_items);
+  });
   });
 }
 
 // ---- word lattices over the recognition network (viterbi_lattice.hip) ---------------------------------------------------------
 // Per frame the word-end tables take 8 W (fwd) + 2 W (first) + 16 (E, Bend) bytes, and the emit step's count and scan 16 more.
 static uint64_t lattice_frame_bytes(const sr_lexicon* l) { return 10ull * l->net.n_words + 32; }
+static std::vector<uint64_t> lattice_cost(const sr_corpus* c, const sr_lexicon* l) {
+  return srplan::linear_cost(c->frame_off.data(), c->n_utts, lattice_frame_bytes(l));
+}
+
+// What both lattice entry points do once their pass has run: the arc offsets per utterance from the frames' (c->lat_frame_arc, the
+// total in c->lat_base), the best costs, and -- the caller wants the arcs, and the arrays of `cap` hold them -- *n_arcs for
+// copy_arcs.  *n_arcs = 0: nothing to copy.
+static int lattice_offsets(sr_corpus* c, uint64_t cap, bool fill, uint64_t* out_arc_off, double* out_best, uint64_t* n_arcs) {
+  const uint32_t U = c->n_utts;
+  const uint64_t F = c->n_frames;
+  *n_arcs = 0;
+  uint64_t total = 0;
+  HIP_TRY(hipMemcpy(&total, c->lat_base.p, sizeof(uint64_t), hipMemcpyDeviceToHost));
+  std::vector<uint64_t> frame_arc(F + 1);
+  if (F) HIP_TRY(hipMemcpy(frame_arc.data(), c->lat_frame_arc.p, sizeof(uint64_t) * F, hipMemcpyDeviceToHost));
+  frame_arc[F] = total;
+  for (uint32_t u = 0; u <= U; u++) out_arc_off[u] = frame_arc[c->frame_off[u]];
+  if (U) HIP_TRY(hipMemcpy(out_best, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToHost));
+  if (!fill) return SR_OK;
+  if (total > cap) return fail(SR_EINVAL, "the lattices hold %llu arcs, the arrays %llu", (unsigned long long)total, (unsigned long long)cap);
+  *n_arcs = total;
+  return SR_OK;
+}
+extern "C++" {
+template <class T>
+static hipError_t copy_arcs(T* out, const DevBuf<T>& arcs, uint64_t n_arcs) {
+  return n_arcs ? hipMemcpy(out, arcs.p, sizeof(T) * n_arcs, hipMemcpyDeviceToHost) : hipSuccess;
+}
+}  // extern "C++"
 
 // The launch groups of a lattice pass -- NetFbPass' grouping on the lattice's bytes per frame: consecutive utterances of a chunk
 // whose word-end tables fit m->fb_budget together (every utterance fits alone: checked by the entry point).  run() enqueues a
 // chunk's groups in order: forward, backward, emit.
 extern "C++" {
 struct LatticePass {
-  struct Group { uint32_t u0, u1; };
-  std::vector<std::vector<Group>> groups;  // per chunk
+  srplan::Groups groups;
   LatticeArgs a{};
   size_t ci = 0, scan_bytes = 0;
   uint64_t cap = 0;
 
   int setup(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double beam, uint64_t arc_cap,
             const std::vector<Chunk>& chunks) {
-    const uint64_t per = lattice_frame_bytes(l), W = l->net.n_words;
-    uint64_t max_gf = 1;
-    groups.assign(chunks.size(), {});
-    for (size_t i = 0; i < chunks.size(); i++)
-      for (uint32_t u = chunks[i].u0; u < chunks[i].u1;) {
-        uint32_t v = u + 1;
-        while (v < chunks[i].u1 && per * (c->frame_off[v + 1] - c->frame_off[u]) <= m->fb_budget) v++;
-        groups[i].push_back({u, v});
-        max_gf = std::max<uint64_t>(max_gf, c->frame_off[v] - c->frame_off[u]);
-        u = v;
-      }
+    const uint64_t W = l->net.n_words;
+    groups = srplan::launch_groups(chunks, lattice_cost(c, l).data(), m->fb_budget);
+    const uint64_t max_gf = std::max<uint64_t>(1, groups.max_span(c->frame_off.data()));
     if (max_gf >= (1ull << 31)) return fail(SR_ELIMIT, "too many frames in one launch group");
     HIP_TRY(c->lat_fwd.ensure(max_gf * W));
     HIP_TRY(c->lat_first.ensure(max_gf * W));
@@ -3424,7 +3285,7 @@ struct LatticePass {
     return SR_OK;
   }
   int run(sr_corpus* c, const Chunk& ch, const double* table, hipStream_t s) {
-    for (const Group& g : groups[ci]) {
+    for (const Group& g : groups.of_chunk[ci]) {
       a.scores = table; a.frame_base = ch.f0; a.utt_first = g.u0; a.n_utts = g.u1 - g.u0; a.group_f0 = c->frame_off[g.u0];
       const uint64_t n = c->frame_off[g.u1] - c->frame_off[g.u0];
       HIP_TRY(launch_lattice_forward(a, s));
@@ -3456,13 +3317,12 @@ int sr_word_lattice_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_se
     return fail(SR_ELIMIT, "%llu lexicon positions exceed the word lattice's %llu", (unsigned long long)P,
                 (unsigned long long)lattice_max_slots());
   const uint32_t U = c->n_utts;
-  const uint64_t F = c->n_frames, per = lattice_frame_bytes(l);
+  const uint64_t F = c->n_frames;
+  const std::vector<uint64_t> cost = lattice_cost(c, l);
   for (uint32_t u = 0; u < U; u++) {
     const uint64_t T = c->frame_off[u + 1] - c->frame_off[u];
     if (T > 65535) return fail(SR_ELIMIT, "utterance %u: %llu frames exceed the lattice's 65535", u, (unsigned long long)T);
-    if (per * T > m->fb_budget)
-      return fail(SR_ELIMIT, "utterance %u: word-end tables of %llu bytes exceed the forward-backward workspace of %llu (SRGPU_FB_MB)",
-                  u, (unsigned long long)(per * T), (unsigned long long)m->fb_budget);
+    if ((rc = check_fits(m, u, cost[u + 1] - cost[u], true))) return rc;
   }
   std::vector<Chunk> chunks;
   if ((rc = prepare_chunks(m, c, &chunks))) return rc;
@@ -3473,23 +3333,14 @@ int sr_word_lattice_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_se
                   [&](const Chunk& ch, const double* table, hipStream_t s) -> int { return lp.run(c, ch, table, s); });
   if (rc) return rc;
   if (m->profiling) m->prof.frames += F;
-  uint64_t total = 0;
-  HIP_TRY(hipMemcpy(&total, c->lat_base.p, sizeof(uint64_t), hipMemcpyDeviceToHost));
-  std::vector<uint64_t> frame_arc(F + 1);
-  if (F) HIP_TRY(hipMemcpy(frame_arc.data(), c->lat_frame_arc.p, sizeof(uint64_t) * F, hipMemcpyDeviceToHost));
-  frame_arc[F] = total;
-  for (uint32_t u = 0; u <= U; u++) out_arc_off[u] = frame_arc[c->frame_off[u]];
-  if (U) HIP_TRY(hipMemcpy(out_best, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToHost));
-  if (!fill) return SR_OK;
-  if (total > cap) return fail(SR_EINVAL, "the lattices hold %llu arcs, the arrays %llu", (unsigned long long)total, (unsigned long long)cap);
-  if (total) {
-    HIP_TRY(hipMemcpy(out_word, c->lat_arc_word.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_first, c->lat_arc_first.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_last, c->lat_arc_last.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_fwd, c->lat_arc_fwd.p, sizeof(double) * total, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_bwd, c->lat_arc_bwd.p, sizeof(double) * total, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_cost, c->lat_arc_cost.p, sizeof(double) * total, hipMemcpyDeviceToHost));
-  }
+  uint64_t n = 0;
+  if ((rc = lattice_offsets(c, cap, fill, out_arc_off, out_best, &n))) return rc;
+  HIP_TRY(copy_arcs(out_word, c->lat_arc_word, n));
+  HIP_TRY(copy_arcs(out_first, c->lat_arc_first, n));
+  HIP_TRY(copy_arcs(out_last, c->lat_arc_last, n));
+  HIP_TRY(copy_arcs(out_fwd, c->lat_arc_fwd, n));
+  HIP_TRY(copy_arcs(out_bwd, c->lat_arc_bwd, n));
+  HIP_TRY(copy_arcs(out_cost, c->lat_arc_cost, n));
   return SR_OK;
   });
 }
@@ -3586,14 +3437,16 @@ int sr_lattice_nbest(uint32_t n_frames, uint64_t n_arcs, const uint32_t* word, c
 // and scan; per utterance the vectors vec / prod / wend (8 Kp each) and arg (4 Kp), the two rows of cost 8 + first 2 + pred 4 per position
 static uint64_t bglat_frame_bytes(const sr_bigram* b) { return 44ull * b->net.n_words + 16; }
 static uint64_t bglat_utt_bytes(const sr_bigram* b) { return 28ull * bgfb_padded(b->net.n_words) + 28ull * b->net.n_positions; }
+static std::vector<uint64_t> bglat_cost(const sr_corpus* c, const sr_bigram* b) {
+  return srplan::linear_cost(c->frame_off.data(), c->n_utts, bglat_frame_bytes(b), bglat_utt_bytes(b));
+}
 
 // The launch groups of a pass, cut like BgFbPass' on the lattice's bytes, each with its utterances ordered longest first.  run()
 // enqueues a chunk's groups: per frame the in-word step and the min-plus entry, forward then backward, then the arcs.
 extern "C++" {
 struct BgLatPass {
-  struct Group { uint32_t u0, u1, t_max; };
-  std::vector<std::vector<Group>> groups;  // per chunk
-  std::vector<uint32_t> order;             // [U] each group's range, longest first
+  srplan::Groups groups;
+  srplan::StepOrder steps;                 // each group's range, longest first
   BgLatArgs a{};
   const float *tab_fwd = nullptr, *tab_bwd = nullptr;
   const uint32_t* d_order = nullptr;
@@ -3603,24 +3456,12 @@ struct BgLatPass {
   int argmin = 0;
 
   int setup(sr_model* m, sr_corpus* c, sr_bigram* b, double beam, uint64_t arc_cap, const std::vector<Chunk>& chunks) {
-    const uint64_t P = b->net.n_positions, per_utt = bglat_utt_bytes(b), per_frame = bglat_frame_bytes(b);
+    const uint64_t P = b->net.n_positions;
     const uint32_t W = b->net.n_words, Kp = bgfb_padded(W), U = c->n_utts;
-    auto len = [&](uint32_t u) { return c->frame_off[u + 1] - c->frame_off[u]; };
-    uint64_t max_gf = 1;
-    uint32_t max_gu = 1;
-    groups.assign(chunks.size(), {});
-    order.resize(U);
-    for (uint32_t u = 0; u < U; u++) order[u] = u;
-    for (size_t i = 0; i < chunks.size(); i++)
-      for (uint32_t u = chunks[i].u0; u < chunks[i].u1;) {
-        uint32_t v = u + 1;
-        while (v < chunks[i].u1 && per_frame * (c->frame_off[v + 1] - c->frame_off[u]) + (v + 1 - u) * per_utt <= m->fb_budget) v++;
-        std::stable_sort(order.begin() + u, order.begin() + v, [&](uint32_t x, uint32_t y) { return len(x) > len(y); });
-        groups[i].push_back({u, v, (uint32_t)len(order[u])});
-        max_gf = std::max<uint64_t>(max_gf, c->frame_off[v] - c->frame_off[u]);
-        max_gu = std::max(max_gu, v - u);
-        u = v;
-      }
+    groups = srplan::launch_groups(chunks, bglat_cost(c, b).data(), m->fb_budget);
+    steps = srplan::StepOrder(groups, c->frame_off.data(), U);
+    const uint64_t max_gf = std::max<uint64_t>(1, groups.max_span(c->frame_off.data()));
+    const uint32_t max_gu = std::max(1u, groups.max_utts());
     if (max_gf >= (1ull << 31)) return fail(SR_ELIMIT, "too many frames in one launch group");
     // the table in the other orientation: built once per net
     if (!b->lat_lm_built) {
@@ -3645,7 +3486,7 @@ struct BgLatPass {
     HIP_TRY(c->bgfb_xb.ensure(2 * (size_t)max_gu * P));
     HIP_TRY(c->bglat_row_first.ensure(2 * (size_t)max_gu * P));
     HIP_TRY(c->bglat_row_pred.ensure(2 * (size_t)max_gu * P));
-    HIP_TRY(c->bgfb_order.upload(order.data(), order.size()));
+    HIP_TRY(c->bgfb_order.upload(steps.order.data(), steps.order.size()));
     d_order = c->bgfb_order.p;
     HIP_TRY(c->lat_cnt.ensure(max_gf));
     HIP_TRY(c->lat_scan.ensure(max_gf));
@@ -3680,23 +3521,19 @@ struct BgLatPass {
     return SR_OK;
   }
   int run(sr_corpus* c, const Chunk& ch, const double* table, hipStream_t s) {
-    for (const Group& g : groups[ci]) {
+    for (const Group& g : groups.of_chunk[ci]) {
       a.scores = table; a.frame_base = ch.f0; a.group_f0 = c->frame_off[g.u0];
       a.order = d_order + g.u0; a.utt_first = g.u0; a.n_group = g.u1 - g.u0;
-      auto alive = [&](uint32_t t) {  // utterances of the group with more than t frames: a prefix of its order
-        uint32_t n = 0;
-        while (n < a.n_group && c->frame_off[order[g.u0 + n] + 1] - c->frame_off[order[g.u0 + n]] > t) n++;
-        return n;
-      };
+      const uint32_t t_max = steps.t_max(g);
       HIP_TRY(launch_bglat_init(a, rows, s));
-      HIP_TRY(launch_bglat_entry(tab_fwd, a.vec, a.prod, a.arg, a.n_words, a.Kp, alive(0), argmin, s));
-      for (uint32_t t = 0; t < g.t_max; t++) {
-        a.t = t; a.n_alive = alive(t);
+      HIP_TRY(launch_bglat_entry(tab_fwd, a.vec, a.prod, a.arg, a.n_words, a.Kp, steps.alive(g, 0), argmin, s));
+      for (uint32_t t = 0; t < t_max; t++) {
+        a.t = t; a.n_alive = steps.alive(g, t);
         HIP_TRY(launch_bglat_forward(a, s));
-        HIP_TRY(launch_bglat_entry(tab_fwd, a.vec, a.prod, a.arg, a.n_words, a.Kp, alive(t + 1), argmin, s));
+        HIP_TRY(launch_bglat_entry(tab_fwd, a.vec, a.prod, a.arg, a.n_words, a.Kp, steps.alive(g, t + 1), argmin, s));
       }
-      for (uint32_t t = g.t_max; t-- > 0;) {
-        a.t = t; a.n_alive = alive(t);
+      for (uint32_t t = t_max; t-- > 0;) {
+        a.t = t; a.n_alive = steps.alive(g, t);
         HIP_TRY(launch_bglat_backward(a, s));
         if (t) HIP_TRY(launch_bglat_entry(tab_bwd, a.vec, a.prod, nullptr, a.n_words, a.Kp, a.n_alive, argmin, s));
       }
@@ -3723,13 +3560,12 @@ int sr_bigram_word_lattice_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int g
     return fail(SR_EINVAL, "null output (pass all eight arc arrays, or none)");
   if (b->lm_min == -std::numeric_limits<float>::infinity()) return fail(SR_EINVAL, "the language model has a score of -inf");
   const uint32_t U = c->n_utts;
-  const uint64_t F = c->n_frames, per = bglat_frame_bytes(b), per_utt = bglat_utt_bytes(b), S = 2ull * b->net.n_words;
+  const uint64_t F = c->n_frames, S = 2ull * b->net.n_words;
+  const std::vector<uint64_t> cost = bglat_cost(c, b);
   for (uint32_t u = 0; u < U; u++) {
     const uint64_t T = c->frame_off[u + 1] - c->frame_off[u];
     if (T > 65535) return fail(SR_ELIMIT, "utterance %u: %llu frames exceed the lattice's 65535", u, (unsigned long long)T);
-    if (per * T + per_utt > m->fb_budget)
-      return fail(SR_ELIMIT, "utterance %u: word-end tables of %llu bytes exceed the forward-backward workspace of %llu (SRGPU_FB_MB)",
-                  u, (unsigned long long)(per * T + per_utt), (unsigned long long)m->fb_budget);
+    if ((rc = check_fits(m, u, cost[u + 1] - cost[u], true))) return rc;
   }
   std::vector<Chunk> chunks;
   if ((rc = prepare_chunks(m, c, &chunks))) return rc;
@@ -3740,25 +3576,16 @@ int sr_bigram_word_lattice_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int g
                   [&](const Chunk& ch, const double* table, hipStream_t s) -> int { return lp.run(c, ch, table, s); });
   if (rc) return rc;
   if (m->profiling) m->prof.frames += F;
-  uint64_t total = 0;
-  HIP_TRY(hipMemcpy(&total, c->lat_base.p, sizeof(uint64_t), hipMemcpyDeviceToHost));
-  std::vector<uint64_t> frame_arc(F + 1);
-  if (F) HIP_TRY(hipMemcpy(frame_arc.data(), c->lat_frame_arc.p, sizeof(uint64_t) * F, hipMemcpyDeviceToHost));
-  frame_arc[F] = total;
-  for (uint32_t u = 0; u <= U; u++) out_arc_off[u] = frame_arc[c->frame_off[u]];
-  if (U) HIP_TRY(hipMemcpy(out_best, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToHost));
-  if (!fill) return SR_OK;
-  if (total > cap) return fail(SR_EINVAL, "the lattices hold %llu arcs, the arrays %llu", (unsigned long long)total, (unsigned long long)cap);
-  if (total) {
-    HIP_TRY(hipMemcpy(out_word, c->lat_arc_word.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_hist, c->bglat_arc_hist.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_pred, c->bglat_arc_pred.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_first, c->lat_arc_first.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_last, c->lat_arc_last.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_fwd, c->lat_arc_fwd.p, sizeof(double) * total, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_bwd, c->lat_arc_bwd.p, sizeof(double) * total, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_am, c->lat_arc_cost.p, sizeof(double) * total, hipMemcpyDeviceToHost));
-  }
+  uint64_t n = 0;
+  if ((rc = lattice_offsets(c, cap, fill, out_arc_off, out_best, &n))) return rc;
+  HIP_TRY(copy_arcs(out_word, c->lat_arc_word, n));
+  HIP_TRY(copy_arcs(out_hist, c->bglat_arc_hist, n));
+  HIP_TRY(copy_arcs(out_pred, c->bglat_arc_pred, n));
+  HIP_TRY(copy_arcs(out_first, c->lat_arc_first, n));
+  HIP_TRY(copy_arcs(out_last, c->lat_arc_last, n));
+  HIP_TRY(copy_arcs(out_fwd, c->lat_arc_fwd, n));
+  HIP_TRY(copy_arcs(out_bwd, c->lat_arc_bwd, n));
+  HIP_TRY(copy_arcs(out_am, c->lat_arc_cost, n));
   return SR_OK;
   });
 }

@@ -1,0 +1,94 @@
+// fb_plan_driver.cpp -- runs speechrecognition_amd/csrc/fb_plan.h (host code, no HIP) for tests/test_fb_plan_cpu.py.
+//   fb_plan_driver <cases.txt>
+// cases.txt, whitespace separated, any number of cases; every answer ends with a line "end".
+//   groups <n_chunks> <U> <budget>  u0 u1 (per chunk)  frame_off[U + 1]  cost[U + 1]
+//     -> "chunk u0 u1 u0 u1 ..." per chunk (its groups), "max <frames> <utterances> <cost>" (the accessors), "order ...",
+//        and per group in corpus order "steps <t_max> alive(0) ... alive(t_max)"
+//   mix <16|32> <masked 0|1> <n_sets>  N ids[N] (per set)
+//     -> "mix_off ...", "mix ...", "slot_beg ...", "slot_pos ..."; masked: 32-bit ids under the mask 0xFFFF, else 16-bit ids
+#include <cstdio>
+#include <fstream>
+#include <string>
+#include <vector>
+
+#include "fb_plan.h"
+
+template <typename V>
+static void line(const char* name, V const& v) {
+  printf("%s", name);
+  for (auto x : v) printf(" %llu", (unsigned long long)x);
+  printf("\n");
+}
+
+static bool groups_case(std::ifstream& in) {
+  size_t n_chunks = 0;
+  uint32_t U = 0;
+  uint64_t budget = 0;
+  in >> n_chunks >> U >> budget;
+  std::vector<srplan::Chunk> chunks(n_chunks);
+  for (auto& c : chunks) in >> c.u0 >> c.u1;
+  std::vector<uint64_t> frame_off(U + 1), cost(U + 1);
+  for (auto& v : frame_off) in >> v;
+  for (auto& v : cost) in >> v;
+  if (!in) return false;
+  for (auto& c : chunks) { c.f0 = frame_off[c.u0]; c.f1 = frame_off[c.u1]; }
+  const srplan::Groups g = srplan::launch_groups(chunks, cost.data(), budget);
+  for (const auto& gs : g.of_chunk) {
+    printf("chunk");
+    for (const srplan::Group& x : gs) printf(" %u %u", x.u0, x.u1);
+    printf("\n");
+  }
+  printf("max %llu %u %llu\n", (unsigned long long)g.max_span(frame_off.data()), g.max_utts(), (unsigned long long)g.max_span(cost.data()));
+  const srplan::StepOrder so(g, frame_off.data(), U);
+  line("order", so.order);
+  for (const auto& gs : g.of_chunk)
+    for (const srplan::Group& x : gs) {
+      const uint32_t t_max = so.t_max(x);
+      printf("steps %u", t_max);
+      for (uint32_t t = 0; t <= t_max; t++) printf(" %u", so.alive(x, t));
+      printf("\n");
+    }
+  return true;
+}
+
+template <class Pos>
+static bool mix_case(std::ifstream& in, bool masked, uint32_t n_sets) {
+  srplan::MixLists<Pos> ml;
+  for (uint32_t s = 0; s < n_sets; s++) {
+    uint64_t N = 0;
+    in >> N;
+    std::vector<uint32_t> ids(N);
+    for (auto& v : ids) in >> v;
+    if (!in) return false;
+    if (masked) {
+      ml.add(ids.data(), N, 0xFFFFu);
+    } else {
+      const std::vector<uint16_t> narrow(ids.begin(), ids.end());
+      ml.add(narrow.data(), N);
+    }
+  }
+  line("mix_off", ml.mix_off);
+  line("mix", ml.mix);
+  line("slot_beg", ml.slot_beg);
+  line("slot_pos", ml.slot_pos);
+  return true;
+}
+
+int main(int argc, char** argv) {
+  if (argc != 2) { fprintf(stderr, "usage: %s <cases.txt>\n", argv[0]); return 2; }
+  std::ifstream in(argv[1]);
+  std::string op;
+  while (in >> op) {
+    bool ok = false;
+    if (op == "groups") {
+      ok = groups_case(in);
+    } else if (op == "mix") {
+      uint32_t width = 0, masked = 0, n_sets = 0;
+      in >> width >> masked >> n_sets;
+      ok = width == 16 ? mix_case<uint16_t>(in, masked != 0, n_sets) : mix_case<uint32_t>(in, masked != 0, n_sets);
+    }
+    if (!ok) { fprintf(stderr, "bad case file\n"); return 2; }
+    printf("end\n");
+  }
+  return 0;
+}

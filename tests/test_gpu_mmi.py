@@ -178,6 +178,83 @@ def test_free_occupancies_sum_to_word_posteriors(tmp_path):
         corpus.close()
 
 
+# ---- several launch groups (SRGPU_FB_MB) -------------------------------------------------------------------------------------------
+MULTI_LENS = [150, 200, 420, 130, 110, 300, 180]
+
+
+def launch_groups(nbytes, budget=1 << 20):
+    """the launch groups of one scoring chunk: a group takes its first utterance, then the next ones while the sum stays in the budget"""
+    groups, u = [], 0
+    while u < len(nbytes):
+        v, total = u + 1, nbytes[u]
+        while v < len(nbytes) and total + nbytes[v] <= budget:
+            total += nbytes[v]
+            v += 1
+        groups.append((u, v))
+        u = v
+    return groups
+
+
+def several_groups(nbytes):
+    """the precondition of the multi-group tests: every utterance fits 1 MiB alone; at least three groups, one of a single utterance
+    and one of several"""
+    assert max(nbytes) < 1 << 20
+    groups = launch_groups(nbytes)
+    sizes = [b - a for a, b in groups]
+    assert len(groups) >= 3 and 1 in sizes and max(sizes) > 1, groups
+    return groups
+
+
+def _multi_group_outputs(mp, lex, feats, off, trans, wp, scale):
+    with capi.Model.from_mixset(mp, DIM) as m, _capi_lex(m, lex) as L:  # (the budget is read when the model is made)
+        corpus = m.upload(feats, off)
+        free = corpus.net_occupancies(L, wp, scale, None, capi.GMM_PREFILTER, 1e-6, 3)
+        chain = corpus.net_occupancies(L, wp, scale, trans, capi.GMM_PREFILTER, 1e-6, 3)
+        fn, fd, num, den = corpus.mmi_statistics(L, wp, trans, scale, capi.GMM_PREFILTER, 1e-6, False)
+        corpus.close()
+    return dict(free=free, chain=chain, stats=[fn, fd, *num, *den])
+
+
+def test_several_launch_groups(tmp_path, oracle_lib, monkeypatch):
+    """7 utterances that one launch takes at the default budget and that SRGPU_FB_MB=1 cuts into groups of one and of several, the
+    free network (8 P T bytes) and the chains (8 N_u T_u) differently: equal bytes either way -- an utterance is one workgroup's
+    work and the items are in frame order -- and, for an utterance that is not the first of its group, the restatement's F and
+    occupancies"""
+    lex = _lex([1] + [6] * 50, 0)
+    word_off, aut, _ = lex.flatten()
+    P, W = len(aut), lex.n_words
+    rng = np.random.default_rng(771)
+    n_words = [20, 30, 40, 10, 14, 40, 30]
+    trans = [list(rng.integers(1, W, size=n)) for n in n_words]
+    free_groups = several_groups([8 * P * T for T in MULTI_LENS])
+    chain_groups = several_groups([8 * (7 * n + 1) * T for n, T in zip(n_words, MULTI_LENS)])   # a word: 6 positions and a silence
+    assert free_groups == [(0, 2), (2, 3), (3, 5), (5, 6), (6, 7)] and chain_groups == [(0, 2), (2, 4), (4, 6), (6, 7)]
+    spec, mp = _model(tmp_path, lex.n_states, 770)
+    feats = synth.make_features(sum(MULTI_LENS), DIM, seed=772)
+    off = _off(MULTI_LENS)
+    wp, scale = 10.0, 0.5
+    monkeypatch.delenv("SRGPU_FB_MB", raising=False)
+    one = _multi_group_outputs(mp, lex, feats, off, trans, wp, scale)
+    monkeypatch.setenv("SRGPU_FB_MB", "1")
+    cut = _multi_group_outputs(mp, lex, feats, off, trans, wp, scale)
+    for k in one:
+        for a, b in zip(one[k], cut[k]):
+            assert np.array_equal(np.asarray(a).view(np.uint8), np.asarray(b).view(np.uint8)), k
+    assert np.isfinite(cut["stats"][0]).all() and np.isfinite(cut["stats"][1]).all()
+    # utterance 4 is the second of the free network's group (3, 5), utterance 3 the second of the chains' (2, 4)
+    o = oracle_lib.Oracle(mp, DIM, lex, tdp=TDP)
+    net = _net(lex)
+    for key, u, graph in (("free", 4, M.free_graph(net)), ("chain", 3, M.chain_graph(net, trans[3]))):
+        a, b = int(off[u]), int(off[u + 1])
+        F, occ = M.occupancies(o.score_matrix(feats[a:b]), graph, TDP, wp, scale)
+        cost, count, state, weight = cut[key]
+        print("several groups", key, u, cost[u], F)
+        assert _rel(cost[u], F) <= 1e-10
+        for t in range(b - a):
+            _check_items(occ[t], count[a + t], state[a + t], weight[a + t], 1e-6, 3)
+    o.close()
+
+
 def _recognition_case(tmp_path, seed, n_words=6, n_utts=6):
     lex = synth.make_lexicon(n_words, 3, 2)
     spec, mp = _model(tmp_path, lex.n_states, seed, Mx=3)

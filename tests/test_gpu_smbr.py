@@ -10,7 +10,7 @@ import pytest
 from speechrecognition_amd import capi, synth
 from tests import mmi_reference as M
 from tests import smbr_reference as SM
-from tests.test_gpu_mmi import DIM, EINVAL, ELIMIT, LEXICA, TDP, _capi_lex, _check_stats, _model, _net, _off, _rel
+from tests.test_gpu_mmi import DIM, EINVAL, ELIMIT, LEXICA, MULTI_LENS, TDP, _capi_lex, _check_stats, _model, _net, _off, _rel, several_groups
 from tests.test_mmi_cpu import criterion_task
 from tests.test_smbr_cpu import SMBR_E, criterion_refs
 from tests.test_word_posteriors_cpu import _lex
@@ -185,6 +185,48 @@ def test_determinism_and_shards(tmp_path):
         assert np.all(np.abs(a[2] + b[2] - 1e-4 - whole[2]) <= 1e-9 * np.maximum(np.abs(whole[2]), 1e-4))
     for i in (0, 1):
         assert np.array_equal(np.concatenate([halves[0][i], halves[1][i]]).view(np.uint64), runs[0][i].view(np.uint64))
+
+
+def _multi_group_outputs(mp, lex, feats, off, ref, wp, scale):
+    with capi.Model.from_mixset(mp, DIM) as m, _capi_lex(m, lex) as L:  # (the budget is read when the model is made)
+        corpus = m.upload(feats, off)
+        accs = corpus.net_accuracies(L, wp, ref, scale, capi.GMM_PREFILTER, 1e-6, 3)
+        cost, acc, num, den = corpus.smbr_statistics(L, wp, ref, scale, capi.GMM_PREFILTER, 1e-6, False)
+        corpus.close()
+    return dict(accs=accs, stats=[cost, acc, *num, *den])
+
+
+def test_several_launch_groups(tmp_path, oracle_lib, monkeypatch):
+    """test_gpu_mmi.test_several_launch_groups for the accuracy pass (16 P T bytes): 7 utterances in one launch at the default budget,
+    in groups of one and of several with SRGPU_FB_MB=1 -- equal bytes either way; and the restatement's F, Abar and gamma for an
+    utterance that is not the first of its group"""
+    lex = _lex([1] + [6] * 25, 0)
+    P = len(lex.flatten()[1])
+    assert several_groups([16 * P * T for T in MULTI_LENS]) == [(0, 2), (2, 3), (3, 5), (5, 6), (6, 7)]
+    spec, mp = _model(tmp_path, lex.n_states, 870)
+    feats = synth.make_features(sum(MULTI_LENS), DIM, seed=871)
+    off = _off(MULTI_LENS)
+    ref = np.random.default_rng(872).integers(0, lex.n_states, size=len(feats)).astype(np.uint16)
+    wp, scale = 10.0, 0.5
+    monkeypatch.delenv("SRGPU_FB_MB", raising=False)
+    one = _multi_group_outputs(mp, lex, feats, off, ref, wp, scale)
+    monkeypatch.setenv("SRGPU_FB_MB", "1")
+    cut = _multi_group_outputs(mp, lex, feats, off, ref, wp, scale)
+    for k in one:
+        for a, b in zip(one[k], cut[k]):
+            assert np.array_equal(np.asarray(a).view(np.uint8), np.asarray(b).view(np.uint8)), k
+    # utterance 4 is the second of the group (3, 5)
+    u, a, b = 4, int(off[4]), int(off[5])
+    o = oracle_lib.Oracle(mp, DIM, lex, tdp=TDP)
+    F, A, g = SM.smbr(o.score_matrix(feats[a:b]), M.free_graph(_net(lex)), TDP, wp, ref[a:b].astype(np.int64), scale)
+    o.close()
+    cost, acc, count, state, weight = cut["accs"]
+    tol = 1e-9 * (1 + b - a)
+    print("several groups", cost[u], F, acc[u], A)
+    assert _rel(cost[u], F) <= 1e-10 and abs(acc[u] - A) <= tol
+    assert _rel(cut["stats"][0][u], F) <= 1e-10 and abs(cut["stats"][1][u] - A) <= tol
+    for t in range(b - a):
+        _check_signed_items(g[t], count[a + t], state[a + t], weight[a + t], 1e-6, 3, tol)
 
 
 def _big_lexicon(n_positions, n_states, seed):
