@@ -1177,6 +1177,85 @@ class SpeakerAdaptation {
   double min_count_;
 };
 
+// ---- MLLR of the means with regression classes (srgpu.h: sr_mllr_*, sr_model_transform_means) ----------------------------------
+// One affine transform of the means per speaker and regression class, estimated by maximum likelihood from the trainer's
+// re-alignment over a regression-class tree; the features are untouched.  A speaker is then recognised or aligned with its own adapted
+// model: upload that speaker's utterances to adapted_model(...).
+class MeanAdaptation {
+ public:
+  struct Result {
+    uint32_t n_speakers = 0, n_classes = 0;
+    std::vector<double> transforms;   // [n_speakers x n_classes x D x (D+1)] W_{s,r} = [A b], row-major
+    std::vector<double> beta;         // [n_speakers x n_classes] occupancy of each base class
+    std::vector<int32_t> node;        // [n_speakers x n_classes] the tree node whose statistics gave the transform, -1: identity kept
+    std::vector<double> aux;          // [n_speakers x n_classes x 2] Q of that node at the identity and at the result
+  };
+
+  // dens_class[n_densities] in mixture order, < n_classes; parent[n_nodes]: the tree over the classes (sr_mllr_estimate), empty: none
+  MeanAdaptation(Trainer& trainer, MixtureModel& mixtures, std::vector<uint32_t> dens_class, uint32_t n_classes,
+                 std::vector<int32_t> parent = std::vector<int32_t>(), double min_count = 100.0)
+      : trainer_(trainer), mixtures_(mixtures), dens_class_(std::move(dens_class)), n_classes_(n_classes), parent_(std::move(parent)),
+        min_count_(min_count) {
+    if (parent_.empty()) parent_.assign(n_classes_, -1);
+  }
+
+  // the estimate alone, from statistics, starting at the identity (host code, no device)
+  static void estimate(size_t dim, uint32_t n_speakers, uint32_t n_classes, std::vector<int32_t> const& parent,
+                       std::vector<double> const& beta, std::vector<double> const& k, std::vector<double> const& G, double min_count,
+                       Result& r) {
+    r.n_speakers = n_speakers;
+    r.n_classes = n_classes;
+    r.beta = beta;
+    r.transforms = SpeakerAdaptation::identity(dim, n_speakers * n_classes);
+    r.node.assign((size_t)n_speakers * n_classes, -1);
+    r.aux.assign((size_t)n_speakers * n_classes * 2, 0.0);
+    check(sr_mllr_estimate((uint32_t)dim, n_speakers, n_classes, (uint32_t)parent.size(), parent.data(), beta.data(), k.data(), G.data(),
+                           min_count, r.transforms.data(), r.node.data(), r.aux.data()));
+  }
+
+  // re-align, take the statistics of the alignment per (speaker, class), estimate
+  Result adapt(Corpus const& corpus) {
+    const size_t n = corpus.get_corpus_size(), D = mixtures_.dimension;
+    const uint64_t F = corpus.get_total_frame_count();
+    std::vector<uint32_t> const& spk = corpus.speakers();
+    uint32_t S = 0;
+    for (uint32_t s : spk) S = std::max(S, s + 1);
+    if (S == 0) throw std::runtime_error("MeanAdaptation: empty corpus");
+    std::vector<AlignmentItem> alignment;
+    trainer_.realign(corpus, alignment);
+    std::vector<uint16_t> states(std::max<uint64_t>(F, 1));
+    for (uint64_t t = 0; t < F; t++) states[t] = (uint16_t)alignment[t].state;
+    const size_t groups = (size_t)S * n_classes_;
+    std::vector<double> beta(groups), k(groups * D * (D + 1)), G(groups * D * (D + 1) * (D + 1));
+    sr_corpus* c = nullptr;
+    check(sr_corpus_upload(mixtures_.handle(), corpus.features(), corpus.frame_offsets(), (uint32_t)n, &c));
+    std::shared_ptr<sr_corpus> original(c, sr_corpus_destroy);
+    check(sr_mllr_statistics_corpus(mixtures_.handle(), c, states.data(), spk.data(), S, dens_class_.data(), n_classes_,
+                                    mixtures_.max_approx() ? 1 : 0, beta.data(), k.data(), G.data()));
+    Result r;
+    estimate(D, S, n_classes_, parent_, beta, k, G, min_count_, r);
+    return r;
+  }
+
+  // the model of one speaker (sr_model_transform_means): a model of its own, the base model's tables are copied
+  std::shared_ptr<sr_model> adapted_model(Result const& r, uint32_t speaker) const {
+    const size_t D = mixtures_.dimension;
+    if (speaker >= r.n_speakers) throw std::runtime_error("MeanAdaptation: no such speaker");
+    sr_model* out = nullptr;
+    check(sr_model_transform_means(mixtures_.handle(), dens_class_.data(), n_classes_,
+                                   r.transforms.data() + (size_t)speaker * n_classes_ * D * (D + 1), &out));
+    return std::shared_ptr<sr_model>(out, sr_model_destroy);
+  }
+
+ private:
+  Trainer& trainer_;
+  MixtureModel& mixtures_;
+  std::vector<uint32_t> dens_class_;
+  uint32_t n_classes_;
+  std::vector<int32_t> parent_;
+  double min_count_;
+};
+
 // ---- Teaching::LinearSearch (rwth-asr-0.5/src/Teaching/LinearSearch.hh:9-62, SearchInterface.hh:20-30) -------------
 // Bigram-LM beam search over a linear lexicon, one device pass per corpus.  The toolkit wires lexicon, language model
 // and transition model through Speech::ModelCombination (LinearSearch.cc:462-475); here they are plain arrays:

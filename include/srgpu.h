@@ -406,6 +406,62 @@ SR_API int sr_fmllr_estimate(uint32_t dim, uint32_t n_speakers, const double* be
 SR_API int sr_corpus_transform(sr_model* m, sr_corpus* c, const uint32_t* utt_speaker, uint32_t n_speakers, const double* W,
                                sr_corpus** out);
 
+/* ---- MLLR of the means with regression classes (Leggetter & Woodland 1995) ----------------------------------------------------
+ * One affine transform of the means W_{s,r} = [A b] (D x (D+1), row-major, the layout of sr_fmllr_estimate) per speaker s and
+ * regression class r; dens_class[n_densities] (mixture order, < n_classes) names every density's class.  With the extended mean
+ * xi_d = (mu_d1 .. mu_dD, 1), iv_d = 1/var_d, the adapted mean is mu'_d = W_{s,r} xi_d.  Over the pairs (t, d, gamma) of speaker s'
+ * utterances, everything in FP64:
+ *   occ[s][d]           = sum_t gamma             x_acc[s][d][i] = sum_t gamma x_ti       (the pairs of (s, d), frames ascending)
+ *   out_beta[s][r]      = sum_{d in r} occ[s][d]
+ *   out_k[s][r][i][j]   = sum_{d in r} (iv_di x_acc[s][d][i]) xi_dj                       (D x (D+1))
+ *   out_G[s][r][i][j][k] = sum_{d in r} (occ[s][d] iv_di) xi_dj xi_dk                     (D x (D+1) x (D+1): full storage, both
+ *                                                                                          triangles from one sum, exactly symmetric)
+ * the densities of a group (s, r) in ascending density id.  Q(W) = -1/2 sum_i (w_i G_i w_i^T - 2 w_i k_i^T), maximised at
+ * w_i = k_i G_i^-1 per row.  sr_mllr_statistics_corpus takes exactly the pairs of sr_fmllr_statistics_corpus,
+ * sr_mllr_statistics_bw_corpus exactly those of sr_fmllr_statistics_bw_corpus (out_cost[n_utts] = F_u).  Outputs: [S x R],
+ * [S x R x D x (D+1)], [S x R x D x (D+1) x (D+1)], S = n_speakers, R = n_classes; a group without pairs gets zeros, a class without
+ * densities is allowed.  Determinism: no atomics.  The pairs are sorted stably by speaker * n_densities + density, so that occ and x_acc
+ * add a (speaker, density)'s pairs in the order they were formed (frames ascending); the occupied (speaker, density) entries of a
+ * group, in ascending density id, are cut into segments of 1024 whose partial sums -- chains of FP64 matrix-core accumulations, the
+ * products xi_dj xi_dk formed in FP64 -- are added in ascending order.  Two identical calls return identical bits; statistics of corpus
+ * shards add up.  Device memory: the three outputs, 36 bytes per pair, 8 (D + 4) bytes per entry and 8 bytes per (segment, D+1 rounded
+ * up to 16, (D+1)(D+2)/2 + D+1 columns each rounded up to 16).
+ * Errors, all before any launch: SR_EINVAL for dens_class[d] >= n_classes, n_classes == 0, a NULL output or dens_class, and the
+ * SR_EINVAL cases of the fMLLR calls; SR_ELIMIT for a dimension above 63, for n_speakers * n_densities >= 2^32 - 1 (the 32-bit keys)
+ * and for outputs (8 S R (1 + D (D+1) (D+2)) bytes) beyond a quarter of the free device memory; otherwise the errors of
+ * sr_accumulate_corpus / sr_baum_welch_corpus. */
+SR_API int sr_mllr_statistics_corpus(sr_model* m, sr_corpus* c, const uint16_t* states, const uint32_t* utt_speaker,
+                                     uint32_t n_speakers, const uint32_t* dens_class, uint32_t n_classes, int max_approx,
+                                     double* out_beta, double* out_k, double* out_G);
+SR_API int sr_mllr_statistics_bw_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off,
+                                        const double tdp[3], uint16_t silence_state, int gmm_kernel, double posterior_floor,
+                                        const uint32_t* utt_speaker, uint32_t n_speakers, const uint32_t* dens_class,
+                                        uint32_t n_classes, int max_approx, double* out_cost, double* out_beta, double* out_k,
+                                        double* out_G);
+
+/* The transforms from the statistics over a regression-class tree; host code, no device.  parent[n_nodes]: nodes 0 .. n_classes-1 are
+ * the leaves (the base classes of the statistics), parent[v] is -1 for a root or an inner node (>= n_classes) with parent[v] > v;
+ * n_nodes == n_classes with every parent -1 means no tree.  A node's statistics are the sum of its leaves', added in ascending leaf
+ * id.  Every leaf r of speaker s takes the transform w_i = k_i G_i^-1 (a Cholesky factorisation and two triangular solves per row) of
+ * its lowest ancestor, itself first, whose beta >= min_count and whose every G_i factorises (positive definite, finite solution);
+ * out_node[s * n_classes + r] is that node, or -1 where none qualifies: W[s][r] is then left as given, bit for bit.
+ * W[n_speakers x n_classes x D x (D+1)] is in/out like sr_fmllr_estimate's (the value given only enters out_aux).  Optional
+ * out_aux[(s * n_classes + r) * 2 + {0, 1}] = Q of the node used, at the W given and at the result (NaN for node -1).
+ * SR_EINVAL for dim == 0, a NULL input or out_node, min_count negative or NaN, n_classes == 0, n_nodes < n_classes or a malformed
+ * tree (a parent that is not -1, or not above its child, or a leaf, or >= n_nodes). */
+SR_API int sr_mllr_estimate(uint32_t dim, uint32_t n_speakers, uint32_t n_classes, uint32_t n_nodes, const int32_t* parent,
+                            const double* beta, const double* k, const double* G, double min_count, double* W, int32_t* out_node,
+                            double* out_aux);
+
+/* The adapted model of one speaker: a new device model with m's topology and tying whose means are mu'_di = acc, acc starting at b_i
+ * and taking acc = acc + A_ij * mu_dj for j ascending in FP64, no fused multiply-add (the loop is the specification), with
+ * [A b] = W[dens_class[d]], W[n_classes x D x (D+1)].  inv_vars, norm and logw keep m's bits; the scoring kernels' packed tables are
+ * built on first use like those of sr_model_split's result.  W = [I 0] gives m's means bit for bit (finite means; a mean of -0.0
+ * comes out as +0.0).  The features of that speaker are then uploaded to the new model (a corpus belongs to one model).
+ * SR_EINVAL for a NULL argument, n_classes == 0, dens_class[d] >= n_classes, or two densities that share a mean row (sr_model_set_tying)
+ * in different classes; SR_ELIMIT for a dimension above 63. */
+SR_API int sr_model_transform_means(sr_model* m, const uint32_t* dens_class, uint32_t n_classes, const double* W, sr_model** out);
+
 /* ---- word posteriors and confidences: forward-backward over the recognition network --------------------------------
  * The network sr_recognize_corpus searches (Recognizer.cpp:103-232: the start hypothesis at word 0 position 0, in-word 0-1-2 jumps
  * with the penalty keyed on the DESTINATION state, every word end entering every word at position 0 or 1 with the word penalty --

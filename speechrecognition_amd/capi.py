@@ -36,6 +36,7 @@ SYMBOLS = [
     "sr_smbr_max_positions", "sr_net_accuracies_corpus", "sr_smbr_statistics_corpus",
     "sr_word_lattice_corpus", "sr_lattice_nbest",
     "sr_fmllr_statistics_corpus", "sr_fmllr_statistics_bw_corpus", "sr_fmllr_estimate", "sr_corpus_transform",
+    "sr_mllr_statistics_corpus", "sr_mllr_statistics_bw_corpus", "sr_mllr_estimate", "sr_model_transform_means",
     "sr_bigram_create", "sr_bigram_destroy", "sr_bigram_describe", "sr_recognize_bigram_corpus",
     "sr_bigram_word_posteriors_corpus", "sr_recognize_bigram_confidence_corpus",
     "sr_bigram_occupancies_corpus", "sr_bigram_mmi_statistics_corpus",
@@ -130,6 +131,11 @@ def lib():
         L.sr_fmllr_statistics_bw_corpus.argtypes = [vp, vp, vp, vp, C.POINTER(dbl * 3), C.c_uint16, i32, dbl, vp, u32, i32, vp, vp, vp, vp]
         L.sr_fmllr_estimate.argtypes = [u32, u32, vp, vp, vp, u32, dbl, vp, vp, vp, vp]
         L.sr_corpus_transform.argtypes = [vp, vp, vp, u32, vp, C.POINTER(vp)]
+        L.sr_mllr_statistics_corpus.argtypes = [vp, vp, vp, vp, u32, vp, u32, i32, vp, vp, vp]
+        L.sr_mllr_statistics_bw_corpus.argtypes = [vp, vp, vp, vp, C.POINTER(dbl * 3), C.c_uint16, i32, dbl, vp, u32, vp, u32, i32, vp, vp, vp,
+                                                   vp]
+        L.sr_mllr_estimate.argtypes = [u32, u32, u32, u32, vp, vp, vp, vp, dbl, vp, vp, vp]
+        L.sr_model_transform_means.argtypes = [vp, vp, u32, vp, C.POINTER(vp)]
         L.sr_word_posteriors_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, vp]
         L.sr_recognize_confidence_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, vp, vp, vp, vp, vp]
         L.sr_net_occupancies_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, vp, vp, vp]
@@ -284,6 +290,16 @@ class Model:
         _check(lib().sr_model_eliminate(self.h, c, _ptr(w), float(min_obs), C.byref(h), _ptr(par)))
         out = Model(h)
         return (out, par[: out.n_densities].copy()) if parents else out
+
+    def transform_means(self, dens_class, W):
+        """MLLR: a new Model whose means are W[dens_class[d]] (mu_d, 1), W f64[R, D, D+1] the transforms of one speaker
+        (sr_model_transform_means); topology, tying and every other table are this model's."""
+        cls = np.ascontiguousarray(dens_class, dtype=np.uint32)
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        assert len(cls) == self.n_densities and W.ndim == 3 and W.shape[1:] == (self.dim, self.dim + 1)
+        h = C.c_void_p()
+        _check(lib().sr_model_transform_means(self.h, _ptr(cls), W.shape[0], _ptr(W), C.byref(h)))
+        return Model(h)
 
     def close(self):
         if self.h:
@@ -646,6 +662,34 @@ class Corpus:
                                                    _ptr(spk), n_speakers, int(max_approx), _ptr(cost), _ptr(beta), _ptr(k), _ptr(G)))
         return cost[: self.n_utts], (beta, k, G)
 
+    def _mllr_args(self, utt_speaker, n_speakers, dens_class, n_classes):
+        spk = np.ascontiguousarray(utt_speaker, dtype=np.uint32)
+        cls = np.ascontiguousarray(dens_class, dtype=np.uint32)
+        assert len(spk) == self.n_utts and len(cls) == self.model.n_densities
+        D, S, R = self.model.dim, n_speakers, n_classes
+        return spk, cls, (np.zeros((S, R)), np.zeros((S, R, D, D + 1)), np.zeros((S, R, D, D + 1, D + 1)))
+
+    def mllr_statistics(self, states, utt_speaker, n_speakers, dens_class, n_classes, max_approx=True):
+        """MLLR statistics of an alignment per (speaker, regression class) (sr_mllr_statistics_corpus) -> (beta f64[S, R],
+        k f64[S, R, D, D+1], G f64[S, R, D, D+1, D+1]); dens_class u32[n_densities] in mixture order."""
+        states = np.ascontiguousarray(states, dtype=np.uint16)
+        spk, cls, (beta, k, G) = self._mllr_args(utt_speaker, n_speakers, dens_class, n_classes)
+        _check(lib().sr_mllr_statistics_corpus(self.model.h, self.h, _ptr(states), _ptr(spk), n_speakers, _ptr(cls), n_classes,
+                                               int(max_approx), _ptr(beta), _ptr(k), _ptr(G)))
+        return beta, k, G
+
+    def mllr_statistics_bw(self, automata, tdp, silence_state, utt_speaker, n_speakers, dens_class, n_classes, kernel=GMM_DEFAULT,
+                           floor=0.0, max_approx=True):
+        """The same from the forward-backward posteriors (sr_mllr_statistics_bw_corpus) -> (cost f64[n_utts], (beta, k, G))."""
+        flat, off = self._aut(automata)
+        spk, cls, (beta, k, G) = self._mllr_args(utt_speaker, n_speakers, dens_class, n_classes)
+        cost = np.zeros(max(self.n_utts, 1), dtype=np.float64)
+        t3 = (C.c_double * 3)(*tdp)
+        _check(lib().sr_mllr_statistics_bw_corpus(self.model.h, self.h, _ptr(flat), _ptr(off), C.byref(t3), silence_state, kernel, float(floor),
+                                                  _ptr(spk), n_speakers, _ptr(cls), n_classes, int(max_approx), _ptr(cost), _ptr(beta),
+                                                  _ptr(k), _ptr(G)))
+        return cost[: self.n_utts], (beta, k, G)
+
     def transform(self, utt_speaker, W):
         """The adapted corpus y = A x + b, W[s] = [A b] of utterance u's speaker utt_speaker[u] (sr_corpus_transform) -> Corpus."""
         spk = np.ascontiguousarray(utt_speaker, dtype=np.uint32)
@@ -911,6 +955,27 @@ def fmllr_estimate(beta, k, G, n_sweeps=10, min_count=0.0, W=None):
     _check(lib().sr_fmllr_estimate(D, S, _ptr(beta), _ptr(k), _ptr(G), int(n_sweeps), float(min_count), _ptr(W), _ptr(aux), _ptr(logdet),
                                    _ptr(status)))
     return W, aux, logdet, status
+
+
+def mllr_estimate(beta, k, G, parent=None, min_count=0.0, W=None):
+    """MLLR mean transforms per (speaker, regression class) over a regression-class tree (sr_mllr_estimate; host code):
+    parent i32[n_nodes] with the R base classes as nodes 0 .. R-1 (default: no tree), W the start (default: identity)
+    -> (W f64[S, R, D, D+1], node i32[S, R] = the node whose statistics gave the transform or -1, aux f64[S, R, 2] = Q of that node at
+    the W given and at the result)."""
+    beta = np.ascontiguousarray(beta, dtype=np.float64)
+    k = np.ascontiguousarray(k, dtype=np.float64)
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    S, R, D = k.shape[0], k.shape[1], k.shape[2]
+    assert beta.shape == (S, R) and k.shape == (S, R, D, D + 1) and G.shape == (S, R, D, D + 1, D + 1)
+    parent = np.full(R, -1, np.int32) if parent is None else np.ascontiguousarray(parent, dtype=np.int32)
+    if W is None:
+        W = np.tile(np.hstack([np.eye(D), np.zeros((D, 1))]), (S, R, 1, 1))
+    W = np.array(W, dtype=np.float64, order="C")
+    node = np.zeros((S, R), dtype=np.int32)
+    aux = np.zeros((S, R, 2))
+    _check(lib().sr_mllr_estimate(D, S, R, len(parent), _ptr(parent), _ptr(beta), _ptr(k), _ptr(G), float(min_count), _ptr(W), _ptr(node),
+                                  _ptr(aux)))
+    return W, node, aux
 
 
 def traceback_words(tb_word, tb_bkp, silence_word, n_words):

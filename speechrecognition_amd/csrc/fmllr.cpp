@@ -16,38 +16,9 @@
 
 namespace {
 
+using srhost::chol_solve;  // (host_util.h: shared with mllr.cpp)
+using srhost::cholesky;
 using srhost::set_error;
-
-// in-place Cholesky factor (lower) of the n x n matrix g; false: not positive definite
-bool cholesky(std::vector<double>& g, uint32_t n) {
-  for (uint32_t j = 0; j < n; j++) {
-    double d = g[(size_t)j * n + j];
-    for (uint32_t k = 0; k < j; k++) d -= g[(size_t)j * n + k] * g[(size_t)j * n + k];
-    if (!(d > 0.0) || !std::isfinite(d)) return false;
-    d = std::sqrt(d);
-    g[(size_t)j * n + j] = d;
-    for (uint32_t i = j + 1; i < n; i++) {
-      double s = g[(size_t)i * n + j];
-      for (uint32_t k = 0; k < j; k++) s -= g[(size_t)i * n + k] * g[(size_t)j * n + k];
-      g[(size_t)i * n + j] = s / d;
-    }
-  }
-  return true;
-}
-
-// x = G^-1 b from the factor l (G = l l^T)
-void chol_solve(const std::vector<double>& l, uint32_t n, const double* b, double* x) {
-  for (uint32_t i = 0; i < n; i++) {
-    double s = b[i];
-    for (uint32_t k = 0; k < i; k++) s -= l[(size_t)i * n + k] * x[k];
-    x[i] = s / l[(size_t)i * n + i];
-  }
-  for (uint32_t i = n; i-- > 0;) {
-    double s = x[i];
-    for (uint32_t k = i + 1; k < n; k++) s -= l[(size_t)k * n + i] * x[k];
-    x[i] = s / l[(size_t)i * n + i];
-  }
-}
 
 // inv = A^-1 (D x D, A = the first D columns of W's rows), *sign, *logabs of det A; false: singular
 bool invert(const double* W, uint32_t D, std::vector<double>& inv, double* sign, double* logabs) {
@@ -197,3 +168,5 @@ extern "C" SR_API int sr_fmllr_estimate(uint32_t dim, uint32_t n_speakers, const
   return SR_OK;
   });
 }
+
+#include "mllr.cpp"  // sr_mllr_estimate: the MLLR mean transforms (see the note at its top)

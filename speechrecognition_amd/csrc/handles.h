@@ -207,6 +207,11 @@ struct sr_corpus {
   DevBuf<uint32_t> fm_pair_dens, fm_frame_list, fm_seg_begin, fm_seg_len, fm_spk_seg_off;
   DevBuf<uint64_t> fm_frame_pair_off;
   DevBuf<double> fm_fold_a, fm_fold_c, fm_partial, fm_beta, fm_k, fm_G;
+  // MLLR statistics (mllr_stats.hip; pairs, sort workspace, segments, partial sums and results are the EM and fm_* buffers above): the
+  // frames' speakers and the densities' classes, the pairs' keys and their runs, the entries' groups, order and sums
+  DevBuf<uint32_t> ml_frame_speaker, ml_dens_class, ml_key, ml_run_key, ml_run_len, ml_run_begin, ml_n_runs, ml_gkey, ml_gkey_sorted,
+      ml_ent_order, ml_grp_begin, ml_ent_dens;
+  DevBuf<double> ml_ent_occ, ml_ent_x;
 };
 
 struct sr_lexicon {

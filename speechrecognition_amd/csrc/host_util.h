@@ -3,6 +3,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cmath>
 #include <exception>
 #include <mutex>
 #include <new>
@@ -51,6 +52,37 @@ int guarded(const char* entry, F&& body) noexcept {
     return set_error(SR_EINTERNAL, (std::string(entry) + ": unexpected exception: " + e.what()).c_str());
   } catch (...) {
     return set_error(SR_EINTERNAL, (std::string(entry) + ": unexpected exception").c_str());
+  }
+}
+
+// in-place Cholesky factor (lower) of the n x n matrix g; false: not positive definite  (fmllr.cpp, mllr.cpp)
+inline bool cholesky(std::vector<double>& g, uint32_t n) {
+  for (uint32_t j = 0; j < n; j++) {
+    double d = g[(size_t)j * n + j];
+    for (uint32_t k = 0; k < j; k++) d -= g[(size_t)j * n + k] * g[(size_t)j * n + k];
+    if (!(d > 0.0) || !std::isfinite(d)) return false;
+    d = std::sqrt(d);
+    g[(size_t)j * n + j] = d;
+    for (uint32_t i = j + 1; i < n; i++) {
+      double s = g[(size_t)i * n + j];
+      for (uint32_t k = 0; k < j; k++) s -= g[(size_t)i * n + k] * g[(size_t)j * n + k];
+      g[(size_t)i * n + j] = s / d;
+    }
+  }
+  return true;
+}
+
+// x = G^-1 b from the factor l (G = l l^T)
+inline void chol_solve(const std::vector<double>& l, uint32_t n, const double* b, double* x) {
+  for (uint32_t i = 0; i < n; i++) {
+    double s = b[i];
+    for (uint32_t k = 0; k < i; k++) s -= l[(size_t)i * n + k] * x[k];
+    x[i] = s / l[(size_t)i * n + i];
+  }
+  for (uint32_t i = n; i-- > 0;) {
+    double s = x[i];
+    for (uint32_t k = i + 1; k < n; k++) s -= l[(size_t)k * n + i] * x[k];
+    x[i] = s / l[(size_t)i * n + i];
   }
 }
 

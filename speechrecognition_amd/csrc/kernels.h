@@ -739,4 +739,46 @@ hipError_t launch_fmllr_statistics(const FmllrArgs& a, hipStream_t stream);  // 
 hipError_t launch_fmllr_transform(const float* feats, const uint64_t* frame_off, uint32_t n_utts, const uint32_t* utt_speaker, const double* W,
                                   uint32_t dim, float* out, hipStream_t stream);
 
+// ---- MLLR of the means: per-(speaker, regression class) statistics of a set of pairs, the adapted means (mllr_stats.hip) ----------------
+// The pairs are EmArgs' (pair_frame, pair_dens, pair_w; key_mean 0xFFFFFFFF: dropped).  Three steps with two host reads between them:
+//   launch_mllr_runs     keys speaker * n_dens + density, stable sort, the runs of equal keys           -> *n_runs, run_key[*n_runs - 1]
+//   launch_mllr_groups   the runs ("entries") ordered by (speaker, class, density), the groups' bounds  -> grp_begin[n_groups + 1]
+//   launch_mllr_statistics  entry sums, contraction over the segments the host cut from grp_begin, reduction
+// The contraction has fmllr_shape(dim)'s rows and columns and segments of fmllr_seg_frames() entries.
+struct MllrArgs {
+  const float* feats;
+  uint32_t dim;
+  FmllrShape shape;
+  const double* means; const double* inv_vars;  // [n_dens x dim]
+  uint64_t n_pairs;
+  const uint32_t* pair_frame; const uint32_t* pair_dens; const uint32_t* pair_key; const double* pair_w;
+  const uint32_t* frame_speaker;   // [n_frames]
+  const uint32_t* dens_class;      // [n_dens]
+  uint32_t n_dens, n_speakers, n_classes;
+  // the pairs by key (all [n_pairs]): key / iota in, keys_sorted / pairs_sorted out; runs of equal keys (a last run of 0xFFFFFFFF holds
+  // the dropped pairs): run_key, run_len, run_begin [n_pairs], n_runs [1]
+  uint32_t *key, *iota, *keys_sorted, *pairs_sorted, *run_key, *run_len, *run_begin, *n_runs;
+  void* sort_temp; size_t sort_temp_bytes;  // mllr_temp_bytes(n_pairs)
+  // entries = the runs with a key: gkey = speaker * n_classes + class per run, ent_order = the runs in stable gkey order, grp_begin
+  // [n_groups + 1] the first position of every group; per position: the density, occ and x_acc [n_entries x dim]
+  uint32_t n_entries;
+  uint32_t *gkey, *gkey_sorted, *ent_order, *grp_begin, *ent_dens;
+  double *ent_occ, *ent_x;
+  // segment g = positions [seg_begin[g], + seg_len[g]) of one group (at most fmllr_seg_frames()), group q owns segments
+  // [grp_seg_off[q], grp_seg_off[q + 1])
+  uint32_t n_segs;
+  const uint32_t* seg_begin; const uint32_t* seg_len; const uint32_t* grp_seg_off;
+  double* partial;                    // workspace [n_segs][rows][cols]
+  double *out_beta, *out_k, *out_G;   // device: [S x R], [S x R x D x (D+1)], [S x R x D x (D+1) x (D+1)]
+};
+size_t mllr_temp_bytes(uint64_t n_pairs);
+hipError_t launch_mllr_runs(const MllrArgs& a, hipStream_t stream);
+hipError_t launch_mllr_groups(const MllrArgs& a, hipStream_t stream);
+hipError_t launch_mllr_statistics(const MllrArgs& a, hipStream_t stream);
+// out[d][i] = acc, acc starting at W_r[i][D] and taking acc = acc + W_r[i][j] * means[d][j] for j ascending, r the class of density d.
+// order: the densities by (class, id); block b transforms order[blk[3b + 1] .. blk[3b + 2]) with W[blk[3b]]
+uint32_t mllr_dens_per_block();
+hipError_t launch_mllr_transform_means(const double* means, const uint32_t* order, const uint32_t* blk, uint32_t n_blocks, const double* W,
+                                       uint32_t dim, double* out, hipStream_t stream);
+
 }  // namespace srgpu

@@ -2214,6 +2214,216 @@ int sr_corpus_transform(sr_model* m, sr_corpus* c, const uint32_t* utt_speaker, 
   });
 }
 
+// ---- MLLR of the means (mllr_stats.hip; the estimate itself is host code, mllr.cpp) -------------------------------------------------
+// The checks every statistics call makes before any launch
+static int mllr_check(sr_model* m, sr_corpus* c, const uint32_t* utt_speaker, uint32_t n_speakers, const uint32_t* dens_class,
+                      uint32_t n_classes, const double* out_beta, const double* out_k, const double* out_G) {
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  if (!out_beta || !out_k || !out_G) return fail(SR_EINVAL, "null output");
+  if (n_speakers == 0) return fail(SR_EINVAL, "n_speakers is 0");
+  if (n_classes == 0) return fail(SR_EINVAL, "n_classes is 0");
+  if (!dens_class && m->n_dens) return fail(SR_EINVAL, "dens_class is null");
+  for (uint64_t d = 0; d < m->n_dens; d++)
+    if (dens_class[d] >= n_classes) return fail(SR_EINVAL, "density %llu: class %u >= n_classes %u", (unsigned long long)d, dens_class[d], n_classes);
+  if (!utt_speaker && c->n_utts) return fail(SR_EINVAL, "utt_speaker is null");
+  for (uint32_t u = 0; u < c->n_utts; u++)
+    if (utt_speaker[u] >= n_speakers) return fail(SR_EINVAL, "utterance %u: speaker %u >= n_speakers %u", u, utt_speaker[u], n_speakers);
+  const uint32_t D = m->dim;
+  if (D > fmllr_max_dim()) return fail(SR_ELIMIT, "dimension %u exceeds %u (MLLR statistics)", D, fmllr_max_dim());
+  if ((uint64_t)n_speakers * m->n_dens >= 0xFFFFFFFFull)
+    return fail(SR_ELIMIT, "n_speakers * densities = %llu does not fit the 32-bit (speaker, density) keys", (unsigned long long)n_speakers * m->n_dens);
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  const double groups = (double)n_speakers * n_classes, out_bytes = 8.0 * groups * (1.0 + (double)D * (D + 1) * (D + 2));
+  if (out_bytes > (double)free_b / 4 || groups >= 4294967295.0)
+    return fail(SR_ELIMIT, "the statistics of %u speakers x %u classes (%.0f bytes) exceed a quarter of the free device memory (%llu bytes)",
+                n_speakers, n_classes, out_bytes, (unsigned long long)free_b);
+  return SR_OK;
+}
+
+static void mllr_zero(uint32_t D, uint64_t groups, double* out_beta, double* out_k, double* out_G) {
+  const size_t nk = (size_t)groups * D * (D + 1);
+  std::fill(out_beta, out_beta + groups, 0.0);
+  std::fill(out_k, out_k + nk, 0.0);
+  std::fill(out_G, out_G + nk * (D + 1), 0.0);
+}
+
+// entries, contraction and reduction over the pairs `e` describes (formed already), per (speaker, class); the results to the host
+static int mllr_statistics(sr_model* m, sr_corpus* c, const EmArgs& e, const uint32_t* utt_speaker, uint32_t S, const uint32_t* dens_class,
+                           uint32_t R, double* out_beta, double* out_k, double* out_G) {
+  const uint32_t D = m->dim, U = c->n_utts, E = D + 1, n_groups = S * R;
+  const uint64_t F = c->n_frames, n_pairs = e.n_pairs;
+  int rc;
+  std::vector<uint32_t> frame_speaker(F);
+  for (uint32_t u = 0; u < U; u++) std::fill(frame_speaker.begin() + c->frame_off[u], frame_speaker.begin() + c->frame_off[u + 1], utt_speaker[u]);
+  MllrArgs a{};
+  a.feats = c->feats.p; a.dim = D; a.shape = fmllr_shape(D); a.means = m->means.p; a.inv_vars = m->inv_vars.p;
+  a.n_pairs = n_pairs; a.pair_frame = e.pair_frame; a.pair_dens = e.pair_dens; a.pair_key = e.key_mean; a.pair_w = e.pair_w;
+  a.n_dens = (uint32_t)m->n_dens; a.n_speakers = S; a.n_classes = R;
+  HIP_TRY(c->ml_frame_speaker.upload(frame_speaker.data(), F)); HIP_TRY(c->ml_dens_class.upload(dens_class, m->n_dens));
+  HIP_TRY(c->ml_key.ensure(n_pairs)); HIP_TRY(c->iota.ensure(n_pairs)); HIP_TRY(c->keys_sorted.ensure(n_pairs));
+  HIP_TRY(c->pairs_sorted.ensure(n_pairs)); HIP_TRY(c->ml_run_key.ensure(n_pairs)); HIP_TRY(c->ml_run_len.ensure(n_pairs));
+  HIP_TRY(c->ml_run_begin.ensure(n_pairs)); HIP_TRY(c->ml_n_runs.ensure(1));
+  a.sort_temp_bytes = mllr_temp_bytes(n_pairs);
+  HIP_TRY(c->sort_temp.ensure(a.sort_temp_bytes));
+  a.frame_speaker = c->ml_frame_speaker.p; a.dens_class = c->ml_dens_class.p; a.key = c->ml_key.p; a.iota = c->iota.p;
+  a.keys_sorted = c->keys_sorted.p; a.pairs_sorted = c->pairs_sorted.p; a.run_key = c->ml_run_key.p; a.run_len = c->ml_run_len.p;
+  a.run_begin = c->ml_run_begin.p; a.n_runs = c->ml_n_runs.p; a.sort_temp = c->sort_temp.p;
+  EventPair ep{};
+  if ((rc = prof_begin(m, m->s_gmm, 1, &ep))) return rc;
+  HIP_TRY(launch_mllr_runs(a, m->s_gmm));
+  if ((rc = prof_end(m, m->s_gmm, &ep))) return rc;
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  uint32_t n_runs = 0, last_key = 0;
+  HIP_TRY(hipMemcpy(&n_runs, c->ml_n_runs.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (n_runs == 0 || n_runs > n_pairs) return fail(SR_EINTERNAL, "MLLR statistics: %u runs of %llu pairs", n_runs, (unsigned long long)n_pairs);
+  HIP_TRY(hipMemcpy(&last_key, c->ml_run_key.p + (n_runs - 1), sizeof(uint32_t), hipMemcpyDeviceToHost));
+  a.n_entries = n_runs - (last_key == 0xFFFFFFFFu ? 1u : 0u);  // the dropped pairs sort behind every key
+  const size_t ne = std::max<uint32_t>(1, a.n_entries);
+  HIP_TRY(c->ml_gkey.ensure(ne)); HIP_TRY(c->ml_gkey_sorted.ensure(ne)); HIP_TRY(c->ml_ent_order.ensure(ne));
+  HIP_TRY(c->ml_grp_begin.ensure((size_t)n_groups + 1)); HIP_TRY(c->ml_ent_dens.ensure(ne)); HIP_TRY(c->ml_ent_occ.ensure(ne));
+  HIP_TRY(c->ml_ent_x.ensure(ne * D));
+  a.gkey = c->ml_gkey.p; a.gkey_sorted = c->ml_gkey_sorted.p; a.ent_order = c->ml_ent_order.p; a.grp_begin = c->ml_grp_begin.p;
+  a.ent_dens = c->ml_ent_dens.p; a.ent_occ = c->ml_ent_occ.p; a.ent_x = c->ml_ent_x.p;
+  if ((rc = prof_begin(m, m->s_gmm, 1, &ep))) return rc;
+  HIP_TRY(launch_mllr_groups(a, m->s_gmm));
+  if ((rc = prof_end(m, m->s_gmm, &ep))) return rc;
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  // every group's entries, cut into segments
+  std::vector<uint32_t> grp_begin((size_t)n_groups + 1), seg_begin, seg_len, grp_seg_off((size_t)n_groups + 1, 0);
+  HIP_TRY(hipMemcpy(grp_begin.data(), c->ml_grp_begin.p, sizeof(uint32_t) * grp_begin.size(), hipMemcpyDeviceToHost));
+  if (grp_begin[0] != 0 || grp_begin[n_groups] != a.n_entries) return fail(SR_EINTERNAL, "MLLR statistics: the groups do not cover the entries");
+  const uint32_t L = fmllr_seg_frames();
+  for (uint32_t g = 0; g < n_groups; g++) {
+    if (grp_begin[g + 1] < grp_begin[g]) return fail(SR_EINTERNAL, "MLLR statistics: group bounds out of order");
+    for (uint32_t b = grp_begin[g]; b < grp_begin[g + 1]; b += L) {
+      seg_begin.push_back(b);
+      seg_len.push_back(std::min(L, grp_begin[g + 1] - b));
+    }
+    grp_seg_off[g + 1] = (uint32_t)seg_begin.size();
+  }
+  a.n_segs = (uint32_t)seg_begin.size();
+  HIP_TRY(c->fm_seg_begin.upload(seg_begin.data(), seg_begin.size())); HIP_TRY(c->fm_seg_len.upload(seg_len.data(), seg_len.size()));
+  HIP_TRY(c->fm_spk_seg_off.upload(grp_seg_off.data(), grp_seg_off.size()));
+  HIP_TRY(c->fm_partial.ensure((size_t)a.n_segs * a.shape.rows * a.shape.cols));
+  const size_t nk = (size_t)n_groups * D * E, nG = nk * E;
+  HIP_TRY(c->fm_beta.ensure(n_groups)); HIP_TRY(c->fm_k.ensure(nk)); HIP_TRY(c->fm_G.ensure(nG));
+  a.seg_begin = c->fm_seg_begin.p; a.seg_len = c->fm_seg_len.p; a.grp_seg_off = c->fm_spk_seg_off.p; a.partial = c->fm_partial.p;
+  a.out_beta = c->fm_beta.p; a.out_k = c->fm_k.p; a.out_G = c->fm_G.p;
+  if ((rc = prof_begin(m, m->s_gmm, 1, &ep))) return rc;
+  HIP_TRY(launch_mllr_statistics(a, m->s_gmm));
+  if ((rc = prof_end(m, m->s_gmm, &ep))) return rc;
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  HIP_TRY(hipMemcpy(out_beta, c->fm_beta.p, sizeof(double) * n_groups, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_k, c->fm_k.p, sizeof(double) * nk, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_G, c->fm_G.p, sizeof(double) * nG, hipMemcpyDeviceToHost));
+  if (m->profiling) {  // per pair: keys and sort, weight, frame, a feature row; per entry: its sums out and in; the partials out and in
+    m->prof.frames += F;
+    m->prof.search_bytes += (double)n_pairs * (40.0 + 4.0 * D) + 16.0 * (double)a.n_entries * E +
+                            16.0 * (double)a.n_segs * a.shape.rows * a.shape.cols;
+  }
+  return SR_OK;
+}
+
+int sr_mllr_statistics_corpus(sr_model* m, sr_corpus* c, const uint16_t* states, const uint32_t* utt_speaker, uint32_t n_speakers,
+                              const uint32_t* dens_class, uint32_t n_classes, int max_approx, double* out_beta, double* out_k,
+                              double* out_G) {
+  return guarded(__func__, [&]() -> int {
+  int rc = mllr_check(m, c, utt_speaker, n_speakers, dens_class, n_classes, out_beta, out_k, out_G);
+  if (rc) return rc;
+  const uint64_t groups = (uint64_t)n_speakers * n_classes;
+  if (c->n_frames == 0) { mllr_zero(m->dim, groups, out_beta, out_k, out_G); return SR_OK; }
+  EmArgs e{};
+  std::vector<uint64_t> pair_off;
+  if ((rc = alignment_pairs(m, c, states, 0, max_approx, &e, &pair_off))) return rc;
+  HIP_TRY(c->fm_pair_dens.ensure(e.n_pairs));
+  e.pair_dens = c->fm_pair_dens.p;
+  HIP_TRY(launch_em_pairs(e, m->s_gmm));
+  return mllr_statistics(m, c, e, utt_speaker, n_speakers, dens_class, n_classes, out_beta, out_k, out_G);
+  });
+}
+
+int sr_mllr_statistics_bw_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
+                                 uint16_t silence_state, int gmm_kernel, double posterior_floor, const uint32_t* utt_speaker,
+                                 uint32_t n_speakers, const uint32_t* dens_class, uint32_t n_classes, int max_approx, double* out_cost,
+                                 double* out_beta, double* out_k, double* out_G) {
+  return guarded(__func__, [&]() -> int {
+  int rc = mllr_check(m, c, utt_speaker, n_speakers, dens_class, n_classes, out_beta, out_k, out_G);
+  if (rc) return rc;
+  if ((rc = fb_check(m, c, automata, aut_off, tdp, posterior_floor, out_cost))) return rc;
+  const uint32_t U = c->n_utts;
+  const uint64_t groups = (uint64_t)n_speakers * n_classes;
+  uint64_t n_items = 0;
+  if ((rc = fb_pass(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, true, &n_items))) return rc;
+  if (U) HIP_TRY(hipMemcpy(out_cost, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToHost));
+  EmArgs e{};
+  if ((rc = item_pairs(m, c, n_items, 0, max_approx, &e))) return rc;
+  if (e.n_pairs == 0) { mllr_zero(m->dim, groups, out_beta, out_k, out_G); return SR_OK; }  // nothing above the floor
+  HIP_TRY(c->fm_pair_dens.ensure(e.n_pairs));
+  e.pair_dens = c->fm_pair_dens.p;
+  HIP_TRY(launch_em_pairs_weighted(e, m->s_gmm));
+  return mllr_statistics(m, c, e, utt_speaker, n_speakers, dens_class, n_classes, out_beta, out_k, out_G);
+  });
+}
+
+int sr_model_transform_means(sr_model* m, const uint32_t* dens_class, uint32_t n_classes, const double* W, sr_model** out) {
+  return guarded(__func__, [&]() -> int {
+  if (!out) return fail(SR_EINVAL, "out is null");
+  *out = nullptr;
+  int rc = check_model(m);
+  if (rc) return rc;
+  if (n_classes == 0) return fail(SR_EINVAL, "n_classes is 0");
+  if (!W) return fail(SR_EINVAL, "W is null");
+  if (!dens_class && m->n_dens) return fail(SR_EINVAL, "dens_class is null");
+  const uint64_t C = m->n_dens;
+  const uint32_t D = m->dim;
+  if (m->h_dens_mean.size() != C || m->h_dens_var.size() != C) return fail(SR_EINTERNAL, "the model has no tying tables");
+  std::vector<uint32_t> row_class(m->n_mean, 0xFFFFFFFFu), class_off((size_t)n_classes + 1, 0);
+  for (uint64_t d = 0; d < C; d++) {
+    if (dens_class[d] >= n_classes) return fail(SR_EINVAL, "density %llu: class %u >= n_classes %u", (unsigned long long)d, dens_class[d], n_classes);
+    uint32_t& rc_ = row_class[m->h_dens_mean[d]];
+    if (rc_ != 0xFFFFFFFFu && rc_ != dens_class[d])
+      return fail(SR_EINVAL, "density %llu: its mean row %u is shared with a density of class %u, not %u", (unsigned long long)d,
+                  m->h_dens_mean[d], rc_, dens_class[d]);
+    rc_ = dens_class[d];
+    class_off[dens_class[d] + 1]++;
+  }
+  if (D > fmllr_max_dim()) return fail(SR_ELIMIT, "dimension %u exceeds %u (MLLR mean transform)", D, fmllr_max_dim());
+  // the densities by (class, id); a workgroup takes at most mllr_dens_per_block() of one class
+  for (uint32_t r = 0; r < n_classes; r++) class_off[r + 1] += class_off[r];
+  std::vector<uint32_t> order(std::max<uint64_t>(1, C)), blk;
+  {
+    std::vector<uint32_t> fill(class_off.begin(), class_off.end() - 1);
+    for (uint64_t d = 0; d < C; d++) order[fill[dens_class[d]]++] = (uint32_t)d;
+  }
+  const uint32_t per = mllr_dens_per_block();
+  for (uint32_t r = 0; r < n_classes; r++)
+    for (uint32_t b = class_off[r]; b < class_off[r + 1]; b += per) {
+      blk.push_back(r); blk.push_back(b); blk.push_back(std::min(class_off[r + 1], b + per));
+    }
+  sr_model* o = nullptr;
+  if ((rc = srhost::model_shell(m->device, D, m->n_states, m->h_dens_off.data(), m->max_approx ? 1 : 0, &o))) return rc;
+  std::unique_ptr<sr_model, int (*)(sr_model*)> own(o, sr_model_destroy);
+  HIP_TRY(o->dens_mean.upload(m->h_dens_mean.data(), C)); HIP_TRY(o->dens_var.upload(m->h_dens_var.data(), C));
+  o->n_mean = m->n_mean; o->n_var = m->n_var; o->h_dens_mean = m->h_dens_mean; o->h_dens_var = m->h_dens_var;
+  HIP_TRY(o->means.ensure(C * D)); HIP_TRY(o->inv_vars.ensure(C * D)); HIP_TRY(o->norm.ensure(C)); HIP_TRY(o->logw.ensure(C));
+  if (C) {
+    HIP_TRY(hipMemcpy(o->inv_vars.p, m->inv_vars.p, sizeof(double) * C * D, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(o->norm.p, m->norm.p, sizeof(double) * C, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(o->logw.p, m->logw.p, sizeof(double) * C, hipMemcpyDeviceToDevice));
+  }
+  DevBuf<uint32_t> d_order, d_blk;
+  DevBuf<double> d_W;
+  HIP_TRY(d_order.upload(order.data(), order.size())); HIP_TRY(d_blk.upload(blk.data(), blk.size()));
+  HIP_TRY(d_W.upload(W, (size_t)n_classes * D * (D + 1)));
+  HIP_TRY(launch_mllr_transform_means(m->means.p, d_order.p, d_blk.p, (uint32_t)(blk.size() / 3), d_W.p, D, o->means.p, o->s_gmm));
+  HIP_TRY(hipStreamSynchronize(o->s_gmm));
+  *out = own.release();
+  return SR_OK;
+  });
+}
+
 // ---- forward-backward over the recognition network (viterbi_netfb.hip) ----------------------------------------------------
 // 8 B per (frame, position)
 static std::vector<uint64_t> netfb_cost(const sr_corpus* c, const sr_lexicon* l) {
