@@ -1385,6 +1385,80 @@ class LinearSearch {
     return r;
   }
 
+  // One sMBR E-step against THIS search's network (sr_bigram_smbr_statistics_corpus): the expected frame accuracy of the free network
+  // with the bigram LM against ref_states (one reference mixture per frame of the corpus, for example an alignment; a value >= the
+  // state count scores for none), every cost times scale (kappa).  f and accuracy per segment; num from the positive gamma, den from
+  // the negative, ready for sr_model_create_from_mmi_statistics.  The training loop: align -> ref_states -> smbr_statistics ->
+  // sr_model_create_from_mmi_statistics -> a LinearSearch on the NEW model.
+  struct SmbrStatistics {
+    std::vector<double> f, accuracy;
+    Trainer::Statistics num, den;
+  };
+  SmbrStatistics smbr_statistics(Corpus const& corpus, std::vector<uint16_t> const& ref_states, double scale,
+                                 double posterior_floor = 0.0) {
+    const size_t n = corpus.get_corpus_size();
+    const uint64_t frames = corpus.get_total_frame_count();
+    if (ref_states.size() != frames) throw std::invalid_argument("smbr_statistics: one reference mixture per frame");
+    std::vector<uint16_t> ref(ref_states);
+    ref.push_back(0);  // (never empty: a null pointer is an error of the ABI)
+    uint32_t n_mean = 0, n_var = 0;
+    check(sr_model_tying_info(scorer_.handle(), &n_mean, &n_var));
+    const size_t D = scorer_.dimension;
+    SmbrStatistics r;
+    r.f.assign(std::max<size_t>(n, 1), 0.0);
+    r.accuracy.assign(std::max<size_t>(n, 1), 0.0);
+    for (Trainer::Statistics* st : {&r.num, &r.den}) {
+      st->mean_acc.assign(n_mean * D, 0.0); st->mean_w.assign(n_mean, 0.0);
+      st->var_acc.assign(n_var * D, 0.0); st->var_w.assign(n_var, 0.0);
+    }
+    sr_corpus* c = nullptr;
+    check(sr_corpus_upload(scorer_.handle(), corpus.features(), corpus.frame_offsets(), (uint32_t)n, &c));
+    const int rc = sr_bigram_smbr_statistics_corpus(scorer_.handle(), c, net_, scorer_.gmm_kernel, scale, posterior_floor,
+                                                    scorer_.max_approx() ? 1 : 0, ref.data(), r.f.data(), r.accuracy.data(),
+                                                    r.num.mean_acc.data(), r.num.mean_w.data(), r.num.var_acc.data(),
+                                                    r.num.var_w.data(), r.den.mean_acc.data(), r.den.mean_w.data(),
+                                                    r.den.var_acc.data(), r.den.var_w.data());
+    sr_corpus_destroy(c);
+    check(rc);
+    r.f.resize(n);
+    r.accuracy.resize(n);
+    return r;
+  }
+
+  // Per frame of the corpus the (at most max_items) mixtures with the largest |gamma| of the sMBR criterion (sr_bigram_accuracies_corpus),
+  // gamma signed, beside f and accuracy per segment.
+  struct Accuracies {
+    std::vector<double> f, accuracy;
+    std::vector<uint16_t> count, state;  // [frames], [frames x max_items]
+    std::vector<double> weight;          // [frames x max_items]
+  };
+  Accuracies accuracies(Corpus const& corpus, std::vector<uint16_t> const& ref_states, double scale, uint32_t max_items,
+                        double posterior_floor = 0.0) {
+    const size_t n = corpus.get_corpus_size();
+    const uint64_t frames = corpus.get_total_frame_count();
+    if (ref_states.size() != frames) throw std::invalid_argument("accuracies: one reference mixture per frame");
+    std::vector<uint16_t> ref(ref_states);
+    ref.push_back(0);
+    Accuracies r;
+    r.f.assign(std::max<size_t>(n, 1), 0.0);
+    r.accuracy.assign(std::max<size_t>(n, 1), 0.0);
+    r.count.assign(std::max<uint64_t>(frames, 1), 0);
+    r.state.assign(std::max<uint64_t>(frames, 1) * std::max<uint32_t>(max_items, 1), 0);
+    r.weight.assign(r.state.size(), 0.0);
+    sr_corpus* c = nullptr;
+    check(sr_corpus_upload(scorer_.handle(), corpus.features(), corpus.frame_offsets(), (uint32_t)n, &c));
+    const int rc = sr_bigram_accuracies_corpus(scorer_.handle(), c, net_, scorer_.gmm_kernel, scale, posterior_floor, max_items, ref.data(),
+                                               r.f.data(), r.accuracy.data(), r.count.data(), r.state.data(), r.weight.data());
+    sr_corpus_destroy(c);
+    check(rc);
+    r.f.resize(n);
+    r.accuracy.resize(n);
+    r.count.resize(frames);
+    r.state.resize(frames * std::max<uint32_t>(max_items, 1));
+    r.weight.resize(r.state.size());
+    return r;
+  }
+
   struct Hypothesis {
     std::vector<uint32_t> words;  // silence removed
     double cost;                  // of the string's cheapest lattice path

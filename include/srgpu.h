@@ -731,6 +731,37 @@ SR_API int sr_bigram_mmi_statistics_corpus(sr_model* m, sr_corpus* c, sr_bigram*
                                            double* num_mean_acc, double* num_mean_w, double* num_var_acc, double* num_var_w,
                                            double* den_mean_acc, double* den_mean_w, double* den_var_acc, double* den_var_w);
 
+/* ---- sMBR training against the bigram search: expected frame accuracy over ITS network ---------------------------------------------
+ * Network: the FREE network of sr_bigram_word_posteriors_corpus / sr_bigram_occupancies_corpus, unchanged (the slots, the start's word
+ * end, every history kept, no beams, scale = kappa > 0 multiplying every cost in FP64, the word entry in the linear domain with
+ * exp(-kappa lm) and therefore the same limits: -kappa lm > 700 SR_ELIMIT, a score of -inf SR_EINVAL, the underflow rule).
+ *   ref_states[total_frames] = the reference mixture of every frame; a value >= the model's state count means the frame scores for
+ *   none.
+ *   A(pi) = sum over t of [k_t(pi) == ref_states[t]], k_t(pi) = the mixture of the net position the path occupies at frame t.  An
+ *   entry in this network emits the mixture of the state it moves TO, so the position-1 quirk of sr_net_accuracies_corpus does not
+ *   arise: a position's accuracy at t is [state(s) == ref_t], whole.
+ *   out_cost[u] = F_u, bit for bit the F_u of sr_bigram_word_posteriors_corpus (the alpha arithmetic is the same).
+ *   out_acc[u] = Abar_u = sum over pi of P(pi) A(pi), 0 <= Abar_u <= T_u.  T_u = 0 or F_u = +inf: Abar_u = 0 and no items.
+ *   gamma_t(k) = occ_t(k) (c_t(k) - Abar_u) = -(1/kappa) d Abar_u / d e(t, k), occ that of sr_bigram_occupancies_corpus (free);
+ *   sum over k of gamma_t(k) = 0.  Per position: gamma_t(s) = occ_t(s) (abar_t(s) + bbar_t(s) - Abar_u), abar_t(s) the expected
+ *   accuracy of frames 0 .. t over the paths reaching s, bbar_t(s) that of frames t + 1 .. over its continuations.
+ * Items, signs, floors, max_items, "all or none" and the spreading over densities are those of sr_net_accuracies_corpus /
+ * sr_smbr_statistics_corpus; seeds and shard additivity those of sr_bigram_mmi_statistics_corpus; the eight arrays go into
+ * sr_model_create_from_mmi_statistics unchanged.  The next iteration's sr_bigram is created on the NEW model.
+ * Errors, all found before the first launch or table build: those of sr_bigram_occupancies_corpus (free), plus SR_EINVAL for a NULL
+ * ref_states.  Workspace per utterance of a launch group: 16 bytes per (frame, position) plus twice the per-utterance vectors of the
+ * word-posterior pass, at most SRGPU_FB_MB MiB together; an utterance that alone needs more: SR_ELIMIT.  Item buffers as the free
+ * pass of sr_bigram_mmi_statistics_corpus (the statistics call: once per sign).  No atomics and a fixed summation order: two
+ * identical calls return identical bits. */
+SR_API int sr_bigram_accuracies_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, double scale, double posterior_floor,
+                                       uint32_t max_items, const uint16_t* ref_states, double* out_cost, double* out_acc,
+                                       uint16_t* out_count, uint16_t* out_state, double* out_weight);
+SR_API int sr_bigram_smbr_statistics_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, double scale,
+                                            double posterior_floor, int max_approx, const uint16_t* ref_states, double* out_cost,
+                                            double* out_acc, double* num_mean_acc, double* num_mean_w, double* num_var_acc,
+                                            double* num_var_w, double* den_mean_acc, double* den_mean_w, double* den_var_acc,
+                                            double* den_var_w);
+
 /* ---- word lattices and N-best lists for the bigram search: ITS network in the min semiring -----------------------------------------
  * The network of the block above (slots 0 .. W-1 the words, slot h + W the silence copy after word h, the start's word end = the
  * silence word at cost 0, the merge WITHOUT the positional cut: every history is kept, no beams), evaluated in the MIN semiring, in

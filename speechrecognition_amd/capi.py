@@ -40,6 +40,7 @@ SYMBOLS = [
     "sr_bigram_create", "sr_bigram_destroy", "sr_bigram_describe", "sr_recognize_bigram_corpus",
     "sr_bigram_word_posteriors_corpus", "sr_recognize_bigram_confidence_corpus",
     "sr_bigram_occupancies_corpus", "sr_bigram_mmi_statistics_corpus",
+    "sr_bigram_accuracies_corpus", "sr_bigram_smbr_statistics_corpus",
     "sr_bigram_word_lattice_corpus", "sr_bigram_lattice_nbest",
     "sr_stream_open", "sr_stream_begin", "sr_stream_push", "sr_stream_partial", "sr_stream_end", "sr_stream_destroy",
     "sr_bigram_stream_open", "sr_bigram_stream_begin", "sr_bigram_stream_push", "sr_bigram_stream_partial", "sr_bigram_stream_end",
@@ -153,6 +154,8 @@ def lib():
         L.sr_bigram_word_posteriors_corpus.argtypes = [vp, vp, vp, i32, dbl, dbl, u32, vp, vp, vp, vp]
         L.sr_bigram_occupancies_corpus.argtypes = [vp, vp, vp, i32, dbl, dbl, u32, vp, vp, vp, vp, vp, vp]
         L.sr_bigram_mmi_statistics_corpus.argtypes = [vp, vp, vp, i32, dbl, dbl, i32, vp, vp] + [vp] * 10
+        L.sr_bigram_accuracies_corpus.argtypes = [vp, vp, vp, i32, dbl, dbl, u32, vp, vp, vp, vp, vp, vp]
+        L.sr_bigram_smbr_statistics_corpus.argtypes = [vp, vp, vp, i32, dbl, dbl, i32, vp] + [vp] * 10
         L.sr_recognize_bigram_confidence_corpus.argtypes = [vp, vp, vp, C.POINTER(BigramParams), dbl, vp, vp, vp, vp, vp]
         L.sr_bigram_word_lattice_corpus.argtypes = [vp, vp, vp, i32, dbl, u64] + [vp] * 10
         L.sr_bigram_lattice_nbest.argtypes = [u32, u64, vp, vp, vp, vp, vp, u32, u32, vp, dbl, u32, vp, u64, vp, vp, C.POINTER(u32)]
@@ -875,6 +878,35 @@ class Corpus:
         _check(lib().sr_bigram_mmi_statistics_corpus(self.model.h, self.h, bigram.h, kernel, float(scale), float(floor), int(max_approx),
                                                      _ptr(flat), _ptr(off), _ptr(fn), _ptr(fd), *[_ptr(a) for a in num + den]))
         return fn[: self.n_utts], fd[: self.n_utts], num, den
+
+    def bigram_accuracies(self, bigram, ref_states, scale=1.0, kernel=GMM_PREFILTER, floor=0.0, max_items=8):
+        """Expected frame accuracy over the free bigram search network (sr_bigram_accuracies_corpus); ref_states u16[total_frames] =
+        the reference mixture of every frame -> (cost, acc, count, state, weight) as net_accuracies: per frame the signed gamma,
+        largest |gamma| first."""
+        F = max(self.n_frames, 1)
+        K = max(int(max_items), 1)
+        cost, acc = (np.zeros(max(self.n_utts, 1), dtype=np.float64) for _ in range(2))
+        count = np.zeros(F, dtype=np.uint16)
+        state = np.zeros((F, K), dtype=np.uint16)
+        weight = np.zeros((F, K), dtype=np.float64)
+        ref = np.ascontiguousarray(np.concatenate([np.asarray(ref_states, dtype=np.uint16), np.zeros(1, np.uint16)]))
+        _check(lib().sr_bigram_accuracies_corpus(self.model.h, self.h, bigram.h, kernel, float(scale), float(floor), int(max_items),
+                                                 _ptr(ref), _ptr(cost), _ptr(acc), _ptr(count), _ptr(state), _ptr(weight)))
+        n = self.n_frames
+        return cost[: self.n_utts], acc[: self.n_utts], count[:n], state[:n], weight[:n]
+
+    def bigram_smbr_statistics(self, bigram, ref_states, scale=1.0, kernel=GMM_PREFILTER, floor=0.0, max_approx=True):
+        """One sMBR E-step against the bigram search network (sr_bigram_smbr_statistics_corpus) -> (F, Abar, num, den) as
+        smbr_statistics.  After Model.from_mmi_statistics the next iteration needs a Model.bigram of the NEW model."""
+        nm, nv = C.c_uint32(), C.c_uint32()
+        _check(lib().sr_model_tying_info(self.model.h, C.byref(nm), C.byref(nv)))
+        D = self.model.dim
+        num, den = ((np.zeros((nm.value, D)), np.zeros(nm.value), np.zeros((nv.value, D)), np.zeros(nv.value)) for _ in range(2))
+        cost, acc = (np.zeros(max(self.n_utts, 1), dtype=np.float64) for _ in range(2))
+        ref = np.ascontiguousarray(np.concatenate([np.asarray(ref_states, dtype=np.uint16), np.zeros(1, np.uint16)]))
+        _check(lib().sr_bigram_smbr_statistics_corpus(self.model.h, self.h, bigram.h, kernel, float(scale), float(floor), int(max_approx),
+                                                      _ptr(ref), _ptr(cost), _ptr(acc), *[_ptr(a) for a in num + den]))
+        return cost[: self.n_utts], acc[: self.n_utts], num, den
 
     def recognize_bigram_confidence(self, bigram, scale=1.0, acoustic_pruning=FLT_MAX, lm_pruning=FLT_MAX, kernel=GMM_PREFILTER,
                                     max_word_ends=0, dense_states=False, global_states=False):

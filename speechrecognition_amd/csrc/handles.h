@@ -185,7 +185,8 @@ struct sr_corpus {
   DevBuf<uint16_t> smbr_ref, smbr_item_mix;
   DevBuf<uint32_t> smbr_base, smbr_item_off, smbr_item_frame;
   // forward-backward over the bigram search network (viterbi_bigram_fb.hip; trellis, posteriors and items are the buffers above):
-  // the launch groups' vectors and utterance orders, the items' confidences
+  // the launch groups' vectors and utterance orders, the items' confidences.  The sMBR pass over the same network
+  // (viterbi_bigram_smbr.hip) uses them at twice the size, with smbr_ref / smbr_acc and the smbr_item_* set above
   DevBuf<double> bgfb_vec, bgfb_prod, bgfb_wend, bgfb_m, bgfb_xb, bgfb_conf;
   DevBuf<uint32_t> bgfb_order;
   // MMI training over the bigram search network (viterbi_bigram_mmi.hip; chains, mixture lists, items and the gate are the mmi_* / fb_*

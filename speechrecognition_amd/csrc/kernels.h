@@ -623,9 +623,26 @@ struct BgOccItemArgs {
   uint32_t* item_base;
   uint32_t* item_off;
   uint32_t* item_frame; uint16_t* item_mix; double* item_w;
+  uint32_t row_stride;          // launch_bgocc_signed_items only: doubles between the free network's rows (the weights are the first n_cols)
 };
 hipError_t launch_bgocc_items(const BgOccItemArgs& a, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes, uint32_t* scan_out,
                               hipStream_t stream);
+// launch_bgocc_items over the signed weights of the free network (no chains), the same sums in the same order.  sign = +1 / -1: the
+// items with sign * gamma > 0 and >= floor, weight sign * gamma; 0: gamma != 0 and |gamma| >= floor, weight gamma
+hipError_t launch_bgocc_signed_items(const BgOccItemArgs& a, int sign, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes,
+                                     uint32_t* scan_out, hipStream_t stream);
+
+// ---- sMBR training over the bigram search network (viterbi_bigram_smbr.hip) --------------------------------------------------------
+// BgFbArgs' launch with the expected frame accuracy beside every cost: the trellis has rows [alpha[P], abar[P]] (2 n_positions doubles
+// per frame; the signed gamma goes over alpha), vec / prod / wend two rows [Kp] per utterance (index j: rows 2 j and 2 j + 1, the
+// second the accuracy side; vec has rows up to the next multiple of 64), xb is [2][n_group][2][n_positions].  post is unused.
+struct BgSmbrArgs {
+  BgFbArgs fb;
+  const uint16_t* ref;          // [n_frames_total] the reference mixture of every frame; >= the state count: none
+  double* out_acc;              // [n_utts_total] Abar_u
+};
+hipError_t launch_bgsmbr_forward(const BgSmbrArgs& a, hipStream_t stream);   // frame a.fb.t of the first a.fb.n_alive utterances
+hipError_t launch_bgsmbr_backward(const BgSmbrArgs& a, hipStream_t stream);
 
 // ---- word lattices over the bigram search network (viterbi_bigram_lattice.hip) -----------------------------------------------------
 // The launch groups are BgFbArgs' (utterances [utt_first, utt_first + n_group) of one score chunk, `order` = longest first); what a

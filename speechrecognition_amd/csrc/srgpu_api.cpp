@@ -2582,6 +2582,19 @@ static int bgfb_check(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, dou
   return check_fits(m, bgfb_cost(c, b));
 }
 
+// exp(-kappa lm) and its transpose in b->fb_lk / b->fb_lkT: built once per (net, kappa)
+static int bgfb_tables(sr_model* m, sr_bigram* b, double scale) {
+  if (b->fb_kappa == scale && b->fb_lk.p) return SR_OK;
+  const uint32_t W = b->net.n_words, Kp = bgfb_padded(W);
+  b->fb_kappa = 0.0;
+  HIP_TRY(b->fb_lk.ensure((size_t)Kp * Kp));
+  HIP_TRY(b->fb_lkT.ensure((size_t)Kp * Kp));
+  HIP_TRY(launch_bgfb_table(b->lmT.p, W, Kp, b->net.silence, scale, b->fb_lk.p, b->fb_lkT.p, m->s_search));
+  HIP_TRY(hipStreamSynchronize(m->s_search));
+  b->fb_kappa = scale;
+  return SR_OK;
+}
+
 // The launch groups of a pass, cut like NetFbPass' with the per-utterance vectors counted in, each with its utterances ordered longest
 // first.  run() enqueues a chunk's groups: per frame the step and the product, forward then backward, the word posteriors, per_group.
 extern "C++" {
@@ -2601,15 +2614,8 @@ struct BgFbPass {
     steps = srplan::StepOrder(groups, c->frame_off.data(), U);
     const uint64_t max_gf = std::max<uint64_t>(1, groups.max_span(c->frame_off.data()));
     const uint32_t max_gu = std::max(1u, groups.max_utts());
-    // exp(-kappa lm) and its transpose: built once per (net, kappa)
-    if (b->fb_kappa != scale || !b->fb_lk.p) {
-      b->fb_kappa = 0.0;
-      HIP_TRY(b->fb_lk.ensure((size_t)Kp * Kp));
-      HIP_TRY(b->fb_lkT.ensure((size_t)Kp * Kp));
-      HIP_TRY(launch_bgfb_table(b->lmT.p, W, Kp, b->net.silence, scale, b->fb_lk.p, b->fb_lkT.p, m->s_search));
-      HIP_TRY(hipStreamSynchronize(m->s_search));
-      b->fb_kappa = scale;
-    }
+    int rc = bgfb_tables(m, b, scale);
+    if (rc) return rc;
     lk = b->fb_lk.p; lkT = b->fb_lkT.p;
     const size_t rows = ((size_t)max_gu + 63) & ~(size_t)63;  // the product reads whole 16-column tiles of vec
     HIP_TRY(c->fb_trellis.ensure(max_gf * P));
@@ -3416,6 +3422,197 @@ int sr_bigram_mmi_statistics_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int
     return bgocc_pass(m, c, b, gmm_kernel, scale, posterior_floor, numerator ? trans : nullptr, numerator ? trans_off : nullptr, true, gate,
                       n_items);
   });
+  });
+}
+
+// ---- sMBR training over the bigram search network (viterbi_bigram_smbr.hip) -------------------------------------------------------
+// 16 B per (frame, position) and twice BgFbPass' vectors per utterance
+static std::vector<uint64_t> bgsmbr_cost(const sr_corpus* c, const sr_bigram* b) {
+  return srplan::linear_cost(c->frame_off.data(), c->n_utts, 16ull * b->net.n_positions, 2 * bgfb_utt_bytes(b));
+}
+
+// bgocc_check's free pass with items, at the accuracy pass' bytes, plus the references
+static int bgsmbr_check(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, double posterior_floor, const uint16_t* ref_states) {
+  bool constrained = false;
+  int rc = bgocc_check(m, c, b, scale, posterior_floor, nullptr, nullptr, true, &constrained);
+  if (rc) return rc;
+  if (!ref_states) return fail(SR_EINVAL, "null argument (ref_states)");
+  return check_fits(m, bgsmbr_cost(c, b));
+}
+
+// BgFbPass for the accuracy recursions: the same longest-first groups, cut on 16 B per (frame, position) and twice the vectors; the
+// workspace is BgFbPass' buffers at twice the size, the items' mixture lists are bgocc_pass' free ones.  run() enqueues a chunk's
+// groups: per frame the step and the product on both operand vectors, forward then backward, then per_group(item arguments of the
+// group, frames of the group).  `ia` writes to c->fb_item_*.
+extern "C++" {
+struct BgSmbrPass {
+  srplan::Groups groups;
+  srplan::StepOrder steps;
+  BgSmbrArgs a{};
+  BgOccItemArgs ia{};
+  const double *lk = nullptr, *lkT = nullptr;
+  const uint32_t* d_order = nullptr;
+  uint64_t item_bound = 0;
+  size_t scan_bytes = 0;
+  size_t ci = 0;  // run_chunks searches the chunks in order
+
+  int setup(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, double floor, const uint16_t* ref_states,
+            const std::vector<Chunk>& chunks) {
+    const uint64_t P = b->net.n_positions, F = c->n_frames;
+    const uint32_t W = b->net.n_words, Kp = bgfb_padded(W), U = c->n_utts;
+    groups = srplan::launch_groups(chunks, bgsmbr_cost(c, b).data(), m->fb_budget);
+    steps = srplan::StepOrder(groups, c->frame_off.data(), U);
+    const uint64_t max_gf = std::max<uint64_t>(1, groups.max_span(c->frame_off.data()));
+    const uint32_t max_gu = std::max(1u, groups.max_utts());
+    srplan::MixLists<uint32_t> ml;
+    ml.add(b->h_pos_info.data(), P, 0xFFFFu);
+    item_bound = F * ml.n_mix(0);  // (bgsmbr_check: below 2^31)
+    int rc = bgfb_tables(m, b, scale);
+    if (rc) return rc;
+    lk = b->fb_lk.p; lkT = b->fb_lkT.p;
+    const size_t rows = (2 * (size_t)max_gu + 63) & ~(size_t)63;  // the product reads whole 16-column tiles of vec
+    HIP_TRY(c->fb_trellis.ensure(max_gf * 2 * P));
+    HIP_TRY(c->out_cost.ensure(U));
+    HIP_TRY(c->smbr_acc.ensure(U));
+    HIP_TRY(c->smbr_ref.upload(ref_states, F));
+    HIP_TRY(c->bgfb_vec.ensure(rows * Kp));
+    HIP_TRY(c->bgfb_prod.ensure(rows * Kp));
+    HIP_TRY(c->bgfb_wend.ensure(rows * Kp));
+    HIP_TRY(c->bgfb_m.ensure(rows));
+    HIP_TRY(c->bgfb_xb.ensure(4 * (size_t)max_gu * P));
+    HIP_TRY(c->bgfb_order.upload(steps.order.data(), steps.order.size()));
+    d_order = c->bgfb_order.p;
+    HIP_TRY(c->fb_mix.upload(ml.mix.data(), ml.mix.size()));
+    HIP_TRY(c->fb_slot_beg.upload(ml.slot_beg.data(), ml.slot_beg.size()));
+    HIP_TRY(c->bgmmi_slot_pos.upload(ml.slot_pos.data(), ml.slot_pos.size()));
+    if ((rc = ensure_items(c, max_gf, F, item_bound, &scan_bytes))) return rc;
+    HIP_TRY(hipMemset(c->bgfb_vec.p, 0, rows * Kp * sizeof(double)));  // (the padding columns h >= W stay 0 from here on)
+    if (U) {  // T_u = 0: F_u = 0 (the start hypothesis is a word end), Abar_u = 0
+      HIP_TRY(hipMemset(c->out_cost.p, 0, sizeof(double) * U));
+      HIP_TRY(hipMemset(c->smbr_acc.p, 0, sizeof(double) * U));
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    BgFbArgs& f = a.fb;
+    f.n_words = W; f.silence = b->net.silence; f.n_positions = (uint32_t)P; f.Kp = Kp;
+    f.slot_off = b->slot_off.p; f.pos_info = b->pos_info.p; f.pos_slot = b->pos_slot.p; f.lmT = b->lmT.p;
+    memcpy(f.tdp, b->net.tdp, sizeof(f.tdp));
+    f.scale = scale; f.ld = m->ld; f.frame_off = c->d_frame_off.p;
+    f.trellis = c->fb_trellis.p; f.vec = c->bgfb_vec.p; f.prod = c->bgfb_prod.p; f.wend = c->bgfb_wend.p; f.m = c->bgfb_m.p; f.xb = c->bgfb_xb.p;
+    f.out_cost = c->out_cost.p;
+    a.ref = c->smbr_ref.p; a.out_acc = c->smbr_acc.p;
+    ia.frame_off = c->d_frame_off.p; ia.trellis = c->fb_trellis.p; ia.n_cols = (uint32_t)P; ia.row_stride = (uint32_t)(2 * P);
+    ia.n_mix = ml.n_mix(0); ia.mix = c->fb_mix.p; ia.slot_beg = c->fb_slot_beg.p; ia.slot_pos = c->bgmmi_slot_pos.p; ia.floor = floor;
+    item_fields(&ia, c);
+    // trellis traffic per (frame, position): (alpha, abar) out, the previous row's pair in; both in + gamma out; the items read gamma
+    if (m->profiling) m->prof.search_bytes += 64.0 * (double)P * (double)F;
+    return SR_OK;
+  }
+  template <class PerGroup>
+  int run(sr_corpus* c, const Chunk& ch, const double* table, hipStream_t s, PerGroup per_group) {
+    BgFbArgs& f = a.fb;
+    for (const Group& g : groups.of_chunk[ci]) {
+      f.scores = table; f.frame_base = ch.f0; f.group_f0 = c->frame_off[g.u0];
+      f.order = d_order + g.u0; f.n_group = g.u1 - g.u0;
+      const uint32_t t_max = steps.t_max(g);
+      for (uint32_t t = 0; t < t_max; t++) {
+        f.t = t; f.n_alive = steps.alive(g, t);
+        HIP_TRY(launch_bgsmbr_forward(a, s));
+        const uint32_t next = steps.alive(g, t + 1);  // only those that go on need their entries
+        HIP_TRY(launch_bgfb_product(lk, f.vec, f.prod, f.Kp, 2 * next, s));
+      }
+      for (uint32_t t = t_max; t-- > 0;) {
+        f.t = t; f.n_alive = steps.alive(g, t);
+        HIP_TRY(launch_bgsmbr_backward(a, s));
+        if (t) HIP_TRY(launch_bgfb_product(lkT, f.vec, f.prod, f.Kp, 2 * f.n_alive, s));
+      }
+      ia.utt_first = g.u0; ia.n_utts = g.u1 - g.u0; ia.group_f0 = c->frame_off[g.u0];
+      int rc = per_group(ia, c->frame_off[g.u1] - c->frame_off[g.u0]);
+      if (rc) return rc;
+    }
+    ci++;
+    return SR_OK;
+  }
+};
+}  // extern "C++"
+
+int sr_bigram_accuracies_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, double scale, double posterior_floor,
+                                uint32_t max_items, const uint16_t* ref_states, double* out_cost, double* out_acc, uint16_t* out_count,
+                                uint16_t* out_state, double* out_weight) {
+  return guarded(__func__, [&]() -> int {
+  int rc = bgsmbr_check(m, c, b, scale, posterior_floor, ref_states);
+  if (rc) return rc;
+  if (!out_cost || !out_acc) return fail(SR_EINVAL, "null argument");
+  bool post = false;
+  if ((rc = top_items_arguments(out_count, out_state, out_weight, "out_state", max_items, &post))) return rc;
+  const uint64_t F = c->n_frames;
+  std::vector<Chunk> chunks;
+  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
+  BgSmbrPass sp;
+  if ((rc = sp.setup(m, c, b, scale, posterior_floor, ref_states, chunks))) return rc;
+  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, gmm_kernel, table); },
+      [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
+        if (post && sp.ci == 0) HIP_TRY(reset_item_count(c->fb_base, s));
+        return sp.run(c, ch, table, s, [&](const BgOccItemArgs& ia, uint64_t n) -> int {
+          if (post) HIP_TRY(launch_bgocc_signed_items(ia, 0, n, c->fb_scan_temp.p, sp.scan_bytes, c->fb_scan.p, s));
+          return SR_OK;
+        });
+      });
+  if (rc) return rc;
+  if (m->profiling) m->prof.frames += F;
+  if ((rc = smbr_costs(c, scale, out_cost, out_acc))) return rc;
+  return post ? top_of_items(m, c, max_items, launch_smbr_top, out_count, out_state, out_weight) : SR_OK;
+  });
+}
+
+int sr_bigram_smbr_statistics_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, double scale, double posterior_floor,
+                                     int max_approx, const uint16_t* ref_states, double* out_cost, double* out_acc, double* num_mean_acc,
+                                     double* num_mean_w, double* num_var_acc, double* num_var_w, double* den_mean_acc, double* den_mean_w,
+                                     double* den_var_acc, double* den_var_w) {
+  return guarded(__func__, [&]() -> int {
+  int rc = bgsmbr_check(m, c, b, scale, posterior_floor, ref_states);
+  if (rc) return rc;
+  if (!out_cost || !out_acc || !num_mean_acc || !num_mean_w || !num_var_acc || !num_var_w || !den_mean_acc || !den_mean_w ||
+      !den_var_acc || !den_var_w)
+    return fail(SR_EINVAL, "null output");
+  const uint64_t F = c->n_frames;
+  c->acc_valid = false;
+  std::vector<Chunk> chunks;
+  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
+  BgSmbrPass sp;
+  if ((rc = sp.setup(m, c, b, scale, posterior_floor, ref_states, chunks))) return rc;
+  // one pass, the items of both signs: the positive ones in the fb_item_* buffers, the negative ones beside them
+  const uint64_t nb = sp.item_bound;
+  HIP_TRY(c->smbr_base.ensure(1)); HIP_TRY(c->smbr_item_off.ensure(F + 1));
+  HIP_TRY(c->smbr_item_frame.ensure(nb)); HIP_TRY(c->smbr_item_mix.ensure(nb)); HIP_TRY(c->smbr_item_w.ensure(nb));
+  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, gmm_kernel, table); },
+      [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
+        if (sp.ci == 0) {
+          HIP_TRY(reset_item_count(c->fb_base, s));
+          HIP_TRY(reset_item_count(c->smbr_base, s));
+        }
+        return sp.run(c, ch, table, s, [&](const BgOccItemArgs& pos, uint64_t n) -> int {
+          BgOccItemArgs neg = pos;
+          neg.item_base = c->smbr_base.p; neg.item_off = c->smbr_item_off.p;
+          neg.item_frame = c->smbr_item_frame.p; neg.item_mix = c->smbr_item_mix.p; neg.item_w = c->smbr_item_w.p;
+          HIP_TRY(launch_bgocc_signed_items(pos, +1, n, c->fb_scan_temp.p, sp.scan_bytes, c->fb_scan.p, s));
+          HIP_TRY(launch_bgocc_signed_items(neg, -1, n, c->fb_scan_temp.p, sp.scan_bytes, c->fb_scan.p, s));
+          return SR_OK;
+        });
+      });
+  if (rc) return rc;
+  if (m->profiling) m->prof.frames += F;
+  if ((rc = smbr_costs(c, scale, out_cost, out_acc))) return rc;
+  uint64_t n_pos = 0, n_neg = 0;
+  if (c->n_utts && ((rc = read_item_count(c->fb_base, &n_pos)) || (rc = read_item_count(c->smbr_base, &n_neg)))) return rc;
+  if ((rc = accumulate_items(m, c, n_pos, 0, max_approx, true, num_mean_acc, num_mean_w, num_var_acc, num_var_w))) return rc;
+  if (n_neg) {  // the negative side through the same buffers
+    HIP_TRY(hipMemcpy(c->fb_item_frame.p, c->smbr_item_frame.p, sizeof(uint32_t) * n_neg, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(c->fb_item_mix.p, c->smbr_item_mix.p, sizeof(uint16_t) * n_neg, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(c->fb_item_w.p, c->smbr_item_w.p, sizeof(double) * n_neg, hipMemcpyDeviceToDevice));
+  }
+  rc = accumulate_items(m, c, n_neg, 0, max_approx, true, den_mean_acc, den_mean_w, den_var_acc, den_var_w);
+  c->acc_valid = false;  // (the handle holds one side only: nothing for sr_model_create_from_accumulated)
+  return rc;
   });
 }
 

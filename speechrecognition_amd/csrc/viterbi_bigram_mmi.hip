@@ -18,7 +18,8 @@
 //                            >= floor in launch_fb_items' layout -- count pass, device scan, write pass.  Position lists are 32-bit
 //                            (the free net has up to 2^31 positions).  A lane sums a mixture of few positions alone, in position
 //                            order; a mixture of many (the silence mixtures: W + 1 positions each) is summed by the whole wave, lane l
-//                            its positions l, l + 64, .., then a butterfly over the lanes.
+//                            its positions l, l + 64, .., then a butterfly over the lanes.  SIGNED (sMBR, viterbi_bigram_smbr.hip's
+//                            signed gamma over the free network): the same sums, kept by sign * gamma or by |gamma|.
 //
 // One workgroup per utterance and two FP64 rows in LDS for the chain, one barrier per frame, gamma written over alpha, no atomics and
 // a fixed summation order: two identical calls return identical bits.  +inf stays +inf, never NaN; a transcript without a path
@@ -181,20 +182,22 @@ __device__ inline double shfl_xor_f64(double v, int k) {
 
 // Workgroup (u, y): its waves take every (4 * kBgOccSplit)-th frame of utterance u; lane l of round r owns the utterance's mixture
 // 64 r + l.  WRITE = false counts the items of each frame, WRITE = true stores them at *item_base + the exclusive scan of the counts,
-// a frame's items in ascending mixture order.
-template <bool WRITE>
-__global__ __launch_bounds__(256) void bgocc_items_kernel(BgOccItemArgs a) {
+// a frame's items in ascending mixture order.  SIGNED: rows of a.row_stride doubles; sign = +1 / -1 keeps sign * sum > 0 and >= floor
+// with that weight, sign = 0 keeps sum != 0 and |sum| >= floor with the signed weight.
+template <bool WRITE, bool SIGNED>
+__global__ __launch_bounds__(256) void bgocc_items_kernel(BgOccItemArgs a, int sign) {
   const uint32_t u = a.utt_first + blockIdx.x, lane = threadIdx.x & 63;
   const uint64_t f0 = a.frame_off[u];
   const int T = (int)(a.frame_off[u + 1] - f0);
   const uint32_t N = a.chain_off ? (uint32_t)(a.chain_off[u + 1] - a.chain_off[u]) : a.n_cols;
-  const double* tr = a.trellis + (a.trellis_off ? a.trellis_off[u] - a.trellis_off[a.utt_first] : (f0 - a.group_f0) * N);
+  const uint32_t ld = SIGNED ? a.row_stride : N;
+  const double* tr = a.trellis + (a.trellis_off ? a.trellis_off[u] - a.trellis_off[a.utt_first] : (f0 - a.group_f0) * ld);
   const uint32_t j0 = a.mix_off ? a.mix_off[u] : 0u, j1 = a.mix_off ? a.mix_off[u + 1] : a.n_mix;
   const bool gated = a.gate && !(a.gate[u] < kInf);
   const double fl = a.floor;
   const uint32_t base = WRITE ? *a.item_base : 0u;
   for (int t = blockIdx.y * 4 + (threadIdx.x >> 6); t < T; t += 4 * kBgOccSplit) {
-    const double* g = tr + (size_t)t * N;
+    const double* g = tr + (size_t)t * ld;
     const uint64_t gf = f0 + (uint64_t)t - a.group_f0;  // frame within the launch
     const uint32_t o = WRITE ? base + a.group_scan[gf] : 0u;
     uint32_t n = 0;
@@ -214,7 +217,9 @@ __global__ __launch_bounds__(256) void bgocc_items_kernel(BgOccItemArgs a) {
         for (int k = 1; k < 64; k <<= 1) q += shfl_xor_f64(q, k);  // (both partners add the same two values: every lane the same bits)
         if ((int)lane == l) p = q;
       }
-      const bool keep = j < j1 && p > 0.0 && p >= fl;
+      if (SIGNED && sign < 0) p = -p;
+      const double mag = SIGNED && sign == 0 ? fabs(p) : p;
+      const bool keep = j < j1 && mag > 0.0 && mag >= fl;
       const uint64_t votes = __ballot(keep);
       if (WRITE && keep) {
         const uint32_t k = o + n + (uint32_t)__popcll(votes & ((1ull << lane) - 1));
@@ -243,12 +248,28 @@ hipError_t launch_bgocc_items(const BgOccItemArgs& args, uint64_t n_frames, void
   if (args.n_utts == 0 || n_frames == 0) return hipSuccess;
   BgOccItemArgs a = args;
   a.group_scan = scan_out;
-  hipLaunchKernelGGL((bgocc_items_kernel<false>), dim3(a.n_utts, kBgOccSplit), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL((bgocc_items_kernel<false, false>), dim3(a.n_utts, kBgOccSplit), dim3(256), 0, stream, a, 0);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   e = hipcub::DeviceScan::ExclusiveSum(scan_temp, scan_temp_bytes, a.group_cnt, scan_out, (int)n_frames, stream);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((bgocc_items_kernel<true>), dim3(a.n_utts, kBgOccSplit), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL((bgocc_items_kernel<true, false>), dim3(a.n_utts, kBgOccSplit), dim3(256), 0, stream, a, 0);
+  hipLaunchKernelGGL(bgocc_items_advance_kernel, dim3(1), dim3(1), 0, stream, a, n_frames);
+  return hipGetLastError();
+}
+
+hipError_t launch_bgocc_signed_items(const BgOccItemArgs& args, int sign, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes,
+                                     uint32_t* scan_out, hipStream_t stream) {
+  if (args.n_utts == 0 || n_frames == 0) return hipSuccess;
+  if (args.trellis_off || args.chain_off || args.row_stride < args.n_cols) return hipErrorInvalidValue;
+  BgOccItemArgs a = args;
+  a.group_scan = scan_out;
+  hipLaunchKernelGGL((bgocc_items_kernel<false, true>), dim3(a.n_utts, kBgOccSplit), dim3(256), 0, stream, a, sign);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  e = hipcub::DeviceScan::ExclusiveSum(scan_temp, scan_temp_bytes, a.group_cnt, scan_out, (int)n_frames, stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((bgocc_items_kernel<true, true>), dim3(a.n_utts, kBgOccSplit), dim3(256), 0, stream, a, sign);
   hipLaunchKernelGGL(bgocc_items_advance_kernel, dim3(1), dim3(1), 0, stream, a, n_frames);
   return hipGetLastError();
 }

@@ -27,69 +27,14 @@
 
 #include "kernels.h"
 #include "netfb_device.h"
+#include "smbr_device.h"
 
 namespace srgpu {
 
 static constexpr size_t kSmbrLds = 160 * 1024;
 static constexpr size_t kSmbrRedBytes = 2 * 3 * kNetFbWaves * 8;  // (m, s, sa) per wave, two parities
 
-struct La {  // a log-semiring cost and the expected accuracy of the paths it sums; a is finite, and ignored where x = +inf
-  double x, a;
-};
-__device__ inline La la_add(La p, La q) {
-  const bool pm = !(q.x < p.x);
-  const La m = pm ? p : q, o = pm ? q : p;
-  if (!(o.x < kInf)) return m;
-  const double w = exp(m.x - o.x);
-  return La{m.x - log1p(w), (m.a + w * o.a) / (1.0 + w)};
-}
-__device__ inline La la_add3(La p, La q, La r) {
-  // (m, x, y) = (the smallest, the other two) as nf_ladd3 picks them, by selects on the scalars
-  const bool pm = p.x <= q.x && p.x <= r.x, qm = !pm && q.x <= r.x, rm = !pm && !qm;
-  const La m{pm ? p.x : (qm ? q.x : r.x), pm ? p.a : (qm ? q.a : r.a)};
-  const La x{pm ? q.x : p.x, pm ? q.a : p.a}, y{rm ? q.x : r.x, rm ? q.a : r.a};
-  if (!(m.x < kInf)) return La{kInf, 0.0};
-  double s = 0.0, sa = m.a;
-  if (x.x < kInf) { const double w = exp(m.x - x.x); s += w; sa += w * x.a; }
-  if (y.x < kInf) { const double w = exp(m.x - y.x); s += w; sa += w * y.a; }
-  return s == 0.0 ? m : La{m.x - log1p(s), sa / (1.0 + s)};
-}
-
-// Lse with the accuracy-weighted sum sa = sum exp(m - x) a beside it
-struct LseA {
-  double m, s, sa;
-  __device__ LseA() : m(kInf), s(0.0), sa(0.0) {}
-  __device__ void add(double x, double a) {
-    if (!(x < kInf)) return;
-    if (x < m) { const double r = exp(x - m); s = s * r + 1.0; sa = sa * r + a; m = x; }
-    else { const double w = exp(m - x); s += w; sa += w * a; }
-  }
-  __device__ void merge(double om, double os, double osa) {  // symmetric in the two operands
-    if (!(om < kInf)) return;
-    if (!(m < kInf)) { m = om; s = os; sa = osa; return; }
-    const double n = m < om ? m : om, r = exp(n - m), q = exp(n - om);
-    s = s * r + os * q;
-    sa = sa * r + osa * q;
-    m = n;
-  }
-  __device__ La value() const { return m < kInf ? La{m - log(s), sa / s} : La{kInf, 0.0}; }
-};
-
-__device__ inline double shfl_xor_f64(double v, int k) {
-  return __hiloint2double(__shfl_xor(__double2hiint(v), k), __shfl_xor(__double2loint(v), k));
-}
-// block_lse_store / block_lse_read with the third component: lane 0 of each wave stores to red[3 * wave]
-__device__ inline void block_lsea_store(LseA v, double* red) {
-#pragma unroll
-  for (int k = 1; k < 64; k <<= 1) {
-    const double om = shfl_xor_f64(v.m, k), os = shfl_xor_f64(v.s, k), osa = shfl_xor_f64(v.sa, k);
-    v.merge(om, os, osa);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    double* r = red + 3 * (threadIdx.x >> 6);
-    r[0] = v.m; r[1] = v.s; r[2] = v.sa;
-  }
-}
+// block_lse_read with the third component (smbr_device.h's block_lsea_store)
 __device__ inline La block_lsea_read(const double* red) {
   LseA v;
   for (int w = 0; w < kNetFbWaves; w++) v.merge(red[3 * w], red[3 * w + 1], red[3 * w + 2]);
