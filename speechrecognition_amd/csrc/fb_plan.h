@@ -1,5 +1,6 @@
 // fb_plan.h -- the host planning every forward-backward style pass over a corpus shares (srgpu_api.cpp): the launch groups of a
-// chunk, the longest-first order inside a group with its per-frame alive count, and the mixture lists of the item kernels.  Host code
+// chunk, the longest-first order inside a group with its per-frame alive count, the mixture lists of the item kernels, the trellis
+// offsets and lists of an occupancy pass, and the segments of the adaptation statistics' fixed summation order.  Host code
 // over plain arrays, no HIP include: tests/cpp/fb_plan_driver.cpp compiles it with the host compiler alone and
 // tests/test_fb_plan_cpu.py restates it in Python.
 //
@@ -35,6 +36,13 @@ struct Groups {
     return mx;
   }
 };
+
+// the longest off[u + 1] - off[u] of a group's utterances (automaton or chain positions: sizes a launch's LDS), at least 1
+inline uint32_t max_positions(const Group& g, const uint64_t* off) {
+  uint32_t mx = 1;
+  for (uint32_t u = g.u0; u < g.u1; u++) mx = std::max(mx, (uint32_t)(off[u + 1] - off[u]));
+  return mx;
+}
 
 // cost[u] = per_frame * frame_off[u] + u * per_utt
 inline std::vector<uint64_t> linear_cost(const uint64_t* frame_off, uint32_t U, uint64_t per_frame, uint64_t per_utt = 0) {
@@ -107,6 +115,45 @@ struct MixLists {
 
  private:
   std::vector<std::pair<uint16_t, Pos>> ps_;
+};
+
+// What an occupancy pass over U utterances plans ahead of its launch groups.  Chains (chain_off[U + 1] non-null): utterance u owns
+// the positions info[chain_off[u] .. chain_off[u + 1]) and, with `lists`, set u of the mixture lists.  The free network (chain_off
+// null): every utterance has the P positions of `info` and the lists hold their one set.  A position's mixture is the low 16 bits of
+// its info word.  tr_off[U + 1] = prefix sums of positions x frames; item_bound = the sum of frames x distinct mixtures (0 without
+// lists), which the caller holds below 2^31.
+template <class Pos>
+struct OccPlan {
+  std::vector<uint64_t> tr_off;
+  MixLists<Pos> ml;
+  uint64_t item_bound = 0;
+
+  OccPlan(const uint64_t* frame_off, uint32_t U, const uint64_t* chain_off, const uint32_t* info, uint64_t P, bool lists) : tr_off(U + 1, 0) {
+    if (!chain_off && lists) ml.add(info, P, 0xFFFFu);
+    for (uint32_t u = 0; u < U; u++) {
+      const uint64_t N = chain_off ? chain_off[u + 1] - chain_off[u] : P, T = frame_off[u + 1] - frame_off[u];
+      tr_off[u + 1] = tr_off[u] + N * T;
+      if (!lists) continue;
+      if (chain_off) ml.add(info + chain_off[u], N, 0xFFFFu);
+      item_bound += T * ml.n_mix(chain_off ? u : 0);
+    }
+  }
+};
+
+// Ranges cut into segments of at most L: range r = [bounds[r], bounds[r + 1]) (non-decreasing) owns segments [off[r], off[r + 1]),
+// segment g the positions [begin[g], begin[g] + len[g]).  An empty range has no segment.
+struct Segments {
+  std::vector<uint32_t> begin, len, off;
+
+  Segments(const uint32_t* bounds, uint32_t n_ranges, uint32_t L) : off((size_t)n_ranges + 1, 0) {
+    for (uint32_t r = 0; r < n_ranges; r++) {
+      for (uint32_t b = bounds[r]; b < bounds[r + 1]; b += L) {
+        begin.push_back(b);
+        len.push_back(std::min(L, bounds[r + 1] - b));
+      }
+      off[r + 1] = (uint32_t)begin.size();
+    }
+  }
 };
 
 }  // namespace srplan

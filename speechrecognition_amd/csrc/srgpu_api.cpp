@@ -1787,12 +1787,18 @@ static int check_fits(const sr_model* m, const std::vector<uint64_t>& cost) {
     if (int rc = check_fits(m, u, cost[u + 1] - cost[u])) return rc;
   return SR_OK;
 }
-// the cost prefix of trellises at tr_off[U + 1]: 8 bytes per cell
-static std::vector<uint64_t> trellis_cost(const std::vector<uint64_t>& tr_off) {
+// the launch groups of trellises at tr_off[U + 1], 8 bytes per cell, with the offsets on the device and room for the largest group's
+static int trellis_groups(sr_model* m, sr_corpus* c, const std::vector<Chunk>& chunks, const std::vector<uint64_t>& tr_off,
+                          srplan::Groups* groups) {
   std::vector<uint64_t> cost(tr_off);
   for (uint64_t& x : cost) x *= 8;
-  return cost;
+  *groups = srplan::launch_groups(chunks, cost.data(), m->fb_budget);
+  HIP_TRY(c->fb_trellis_off.upload(tr_off.data(), tr_off.size()));
+  HIP_TRY(c->fb_trellis.ensure(std::max<uint64_t>(1, groups->max_span(tr_off.data()))));
+  return SR_OK;
 }
+// an entry point's output arrays: is one of them missing
+static bool any_null(std::initializer_list<const void*> ps) { return std::find(ps.begin(), ps.end(), nullptr) != ps.end(); }
 
 extern "C++" {
 // The item path (launch_fb_items, launch_occ_items, launch_smbr_items, launch_bgocc_items): a launch group of at most max_gf frames
@@ -1809,6 +1815,41 @@ template <class Args>  // FbArgs, OccItemArgs, BgOccItemArgs (kernels.h)
 static void item_fields(Args* a, sr_corpus* c) {
   a->group_cnt = c->fb_cnt.p; a->item_base = c->fb_base.p; a->item_off = c->fb_item_off.p;
   a->item_frame = c->fb_item_frame.p; a->item_mix = c->fb_item_mix.p; a->item_w = c->fb_item_w.p;
+}
+// a launch group's utterances [u0, u1) in the item arguments; returns its frames
+template <class Args>
+static uint64_t item_group(Args* a, const sr_corpus* c, uint32_t u0, uint32_t u1) {
+  a->utt_first = u0; a->n_utts = u1 - u0; a->group_f0 = c->frame_off[u0];
+  return c->frame_off[u1] - c->frame_off[u0];
+}
+// The mixture lists of a pass' items on the device: c->fb_mix and c->fb_slot_beg, the positions in `slot_pos` (16-bit: c->fb_slot_pos,
+// 32-bit: c->bgmmi_slot_pos) and -- per_utt: a set per utterance -- c->fb_mix_off
+template <class Pos>
+static int upload_mix_lists(sr_corpus* c, const srplan::MixLists<Pos>& ml, bool per_utt, DevBuf<Pos>& slot_pos) {
+  if (per_utt) HIP_TRY(c->fb_mix_off.upload(ml.mix_off.data(), ml.mix_off.size()));
+  HIP_TRY(c->fb_mix.upload(ml.mix.data(), ml.mix.size()));
+  HIP_TRY(c->fb_slot_beg.upload(ml.slot_beg.data(), ml.slot_beg.size()));
+  HIP_TRY(slot_pos.upload(ml.slot_pos.data(), ml.slot_pos.size()));
+  return SR_OK;
+}
+// What OccItemArgs and BgOccItemArgs share, over the uploaded lists `ml`: the free network's rows of P positions, or -- chain -- the
+// transcripts' chains (upload_chains, trellis_groups)
+template <class Args, class Pos>
+static void occ_item_fields(Args* a, sr_corpus* c, const srplan::MixLists<Pos>& ml, bool chain, uint64_t P, const DevBuf<Pos>& slot_pos,
+                            const double* gate, double floor) {
+  a->frame_off = c->d_frame_off.p; a->trellis = c->fb_trellis.p; a->n_cols = (uint32_t)P; a->n_mix = chain ? 0u : (uint32_t)ml.mix.size();
+  if (chain) { a->trellis_off = c->fb_trellis_off.p; a->chain_off = c->mmi_chain_off.p; a->mix_off = c->fb_mix_off.p; }
+  a->mix = c->fb_mix.p; a->slot_beg = c->fb_slot_beg.p; a->slot_pos = slot_pos.p; a->gate = gate; a->floor = floor;
+  item_fields(a, c);
+}
+// the transcripts' chains (Chains, BgChains) on the device
+template <class Ch>
+static int upload_chains(sr_corpus* c, const Ch& ch) {
+  HIP_TRY(c->mmi_chain_off.upload(ch.off.data(), ch.off.size()));
+  HIP_TRY(c->mmi_info.upload(ch.info.data(), ch.info.size()));
+  HIP_TRY(c->mmi_src.upload(ch.src.data(), ch.src.size()));
+  HIP_TRY(c->mmi_dst.upload(ch.dst.data(), ch.dst.size()));
+  return SR_OK;
 }
 // ahead of a pass' first launch group, on its stream
 static hipError_t reset_item_count(DevBuf<uint32_t>& base, hipStream_t s) { return hipMemsetAsync(base.p, 0, sizeof(uint32_t), s); }
@@ -1903,18 +1944,13 @@ static int fb_pass(sr_model* m, sr_corpus* c, const uint16_t* automata, const ui
   AutomatonScoring sc;
   int rc = automaton_scoring_setup(m, c, automata, aut_off, gmm_kernel, &sc);
   if (rc) return rc;
-  const srplan::Groups groups = srplan::launch_groups(sc.chunks, trellis_cost(tr_off).data(), m->fb_budget);
-  HIP_TRY(c->fb_trellis_off.upload(tr_off.data(), U + 1));
-  HIP_TRY(c->fb_trellis.ensure(std::max<uint64_t>(1, groups.max_span(tr_off.data()))));
+  srplan::Groups groups;
+  if ((rc = trellis_groups(m, c, sc.chunks, tr_off, &groups))) return rc;
   FbArgs fa{};
   size_t scan_bytes = 0;
-  if (want_items) {
-    HIP_TRY(c->fb_mix_off.upload(ml.mix_off.data(), U + 1));
-    HIP_TRY(c->fb_mix.upload(ml.mix.data(), ml.mix.size()));
-    HIP_TRY(c->fb_slot_beg.upload(ml.slot_beg.data(), ml.slot_beg.size()));
-    HIP_TRY(c->fb_slot_pos.upload(ml.slot_pos.data(), ml.slot_pos.size()));
-    if ((rc = ensure_items(c, std::max<uint64_t>(1, groups.max_span(c->frame_off.data())), F, item_bound, &scan_bytes))) return rc;
-  }
+  if (want_items && ((rc = upload_mix_lists(c, ml, true, c->fb_slot_pos)) ||
+                     (rc = ensure_items(c, std::max<uint64_t>(1, groups.max_span(c->frame_off.data())), F, item_bound, &scan_bytes))))
+    return rc;
   fa.ld = m->ld; fa.frame_off = c->d_frame_off.p; fa.automata = c->automata.p; fa.aut_off = c->aut_off.p;
   fa.tdp_loop = tdp[0]; fa.tdp_forward = tdp[1]; fa.tdp_skip = tdp[2]; fa.silence_state = silence_state;
   fa.trellis = c->fb_trellis.p; fa.trellis_off = c->fb_trellis_off.p; fa.out_cost = c->out_cost.p;
@@ -1927,9 +1963,8 @@ static int fb_pass(sr_model* m, sr_corpus* c, const uint16_t* automata, const ui
       [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
         if (want_items && ci == 0) HIP_TRY(reset_item_count(c->fb_base, s));
         for (const Group& g : groups.of_chunk[ci]) {
-          fa.scores = table; fa.frame_base = ch.f0; fa.utt_first = g.u0; fa.n_utts = g.u1 - g.u0; fa.max_positions = 1;
-          for (uint32_t u = g.u0; u < g.u1; u++) fa.max_positions = std::max(fa.max_positions, (uint32_t)(aut_off[u + 1] - aut_off[u]));
-          fa.group_f0 = c->frame_off[g.u0];
+          fa.scores = table; fa.frame_base = ch.f0; fa.utt_first = g.u0; fa.n_utts = g.u1 - g.u0;
+          fa.max_positions = srplan::max_positions(g, aut_off); fa.group_f0 = c->frame_off[g.u0];
           HIP_TRY(launch_fb_forward(fa, s));
           HIP_TRY(launch_fb_backward(fa, s));
           if (want_items)
@@ -2052,6 +2087,52 @@ int sr_baum_welch_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, co
   });
 }
 
+// ---- what fMLLR and MLLR share ahead of their statistics ---------------------------------------------------------------------------
+// every utterance's speaker is one of n_speakers (> 0: the caller's check), and the dimension fits; `what` names the call in the message
+static int speaker_check(const sr_model* m, const sr_corpus* c, const uint32_t* utt_speaker, uint32_t n_speakers, const char* what) {
+  if (!utt_speaker && c->n_utts) return fail(SR_EINVAL, "utt_speaker is null");
+  for (uint32_t u = 0; u < c->n_utts; u++)
+    if (utt_speaker[u] >= n_speakers) return fail(SR_EINVAL, "utterance %u: speaker %u >= n_speakers %u", u, utt_speaker[u], n_speakers);
+  if (m->dim > fmllr_max_dim()) return fail(SR_ELIMIT, "dimension %u exceeds %u (%s)", m->dim, fmllr_max_dim(), what);
+  return SR_OK;
+}
+
+// no frame, or nothing above the floor: the statistics of `groups` speakers or (speaker, class) pairs are 0
+static int adapt_zero(uint32_t D, uint64_t groups, double* out_beta, double* out_k, double* out_G) {
+  const size_t nk = (size_t)groups * D * (D + 1);
+  std::fill(out_beta, out_beta + groups, 0.0);
+  std::fill(out_k, out_k + nk, 0.0);
+  std::fill(out_G, out_G + nk * (D + 1), 0.0);
+  return SR_OK;
+}
+
+// The (frame, density, weight) pairs of the adaptation statistics, formed on the device with the density id beside the keys, from an
+// alignment or from a Baum-Welch pass (which also gives out_cost).  e->n_pairs = 0: no frame, or nothing above the floor.
+static int adapt_pairs(sr_model* m, sr_corpus* c, const uint16_t* states, int max_approx, EmArgs* e) {
+  *e = EmArgs{};
+  if (c->n_frames == 0) return SR_OK;
+  std::vector<uint64_t> pair_off;
+  int rc = alignment_pairs(m, c, states, 0, max_approx, e, &pair_off);
+  if (rc) return rc;
+  HIP_TRY(c->fm_pair_dens.ensure(e->n_pairs));
+  e->pair_dens = c->fm_pair_dens.p;
+  HIP_TRY(launch_em_pairs(*e, m->s_gmm));
+  return SR_OK;
+}
+static int adapt_pairs_bw(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
+                          uint16_t silence_state, int gmm_kernel, double posterior_floor, int max_approx, double* out_cost, EmArgs* e) {
+  int rc = fb_check(m, c, automata, aut_off, tdp, posterior_floor, out_cost);
+  if (rc) return rc;
+  uint64_t n_items = 0;
+  if ((rc = fb_pass(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, true, &n_items))) return rc;
+  if (c->n_utts) HIP_TRY(hipMemcpy(out_cost, c->out_cost.p, sizeof(double) * c->n_utts, hipMemcpyDeviceToHost));
+  if ((rc = item_pairs(m, c, n_items, 0, max_approx, e)) || e->n_pairs == 0) return rc;
+  HIP_TRY(c->fm_pair_dens.ensure(e->n_pairs));
+  e->pair_dens = c->fm_pair_dens.p;
+  HIP_TRY(launch_em_pairs_weighted(*e, m->s_gmm));
+  return SR_OK;
+}
+
 // ---- fMLLR speaker adaptation (fmllr_stats.hip; the estimate itself is host code, fmllr.cpp) ---------------------------------------
 // The checks every statistics call makes before any launch
 static int fmllr_check(sr_model* m, sr_corpus* c, const uint32_t* utt_speaker, uint32_t n_speakers, const double* out_beta,
@@ -2060,11 +2141,8 @@ static int fmllr_check(sr_model* m, sr_corpus* c, const uint32_t* utt_speaker, u
   if (rc) return rc;
   if (!out_beta || !out_k || !out_G) return fail(SR_EINVAL, "null output");
   if (n_speakers == 0) return fail(SR_EINVAL, "n_speakers is 0");
-  if (!utt_speaker && c->n_utts) return fail(SR_EINVAL, "utt_speaker is null");
-  for (uint32_t u = 0; u < c->n_utts; u++)
-    if (utt_speaker[u] >= n_speakers) return fail(SR_EINVAL, "utterance %u: speaker %u >= n_speakers %u", u, utt_speaker[u], n_speakers);
+  if ((rc = speaker_check(m, c, utt_speaker, n_speakers, "fMLLR statistics"))) return rc;
   const uint32_t D = m->dim;
-  if (D > fmllr_max_dim()) return fail(SR_ELIMIT, "dimension %u exceeds %u (fMLLR statistics)", D, fmllr_max_dim());
   size_t free_b = 0, total_b = 0;
   HIP_TRY(hipMemGetInfo(&free_b, &total_b));
   const double g_bytes = 8.0 * (double)n_speakers * D * (D + 1) * (D + 1);
@@ -2082,7 +2160,7 @@ static int fmllr_statistics(sr_model* m, sr_corpus* c, const EmArgs& e, const ui
   const uint64_t F = c->n_frames;
   int rc;
   // every speaker's frames in corpus order, cut into segments
-  std::vector<uint32_t> spk_frames(S + 1, 0), frame_list(F), seg_begin, seg_len, spk_seg_off(S + 1, 0);
+  std::vector<uint32_t> spk_frames(S + 1, 0), frame_list(F);
   for (uint32_t u = 0; u < U; u++) spk_frames[utt_speaker[u] + 1] += (uint32_t)(c->frame_off[u + 1] - c->frame_off[u]);
   for (uint32_t s = 0; s < S; s++) spk_frames[s + 1] += spk_frames[s];
   {
@@ -2090,23 +2168,16 @@ static int fmllr_statistics(sr_model* m, sr_corpus* c, const EmArgs& e, const ui
     for (uint32_t u = 0; u < U; u++)
       for (uint64_t f = c->frame_off[u]; f < c->frame_off[u + 1]; f++) frame_list[fill[utt_speaker[u]]++] = (uint32_t)f;
   }
-  const uint32_t L = fmllr_seg_frames();
-  for (uint32_t s = 0; s < S; s++) {
-    for (uint32_t b = spk_frames[s]; b < spk_frames[s + 1]; b += L) {
-      seg_begin.push_back(b);
-      seg_len.push_back(std::min(L, spk_frames[s + 1] - b));
-    }
-    spk_seg_off[s + 1] = (uint32_t)seg_begin.size();
-  }
+  const srplan::Segments seg(spk_frames.data(), S, fmllr_seg_frames());
   FmllrArgs a{};
   a.feats = c->feats.p; a.n_frames = F; a.dim = D; a.shape = fmllr_shape(D);
   a.means = m->means.p; a.inv_vars = m->inv_vars.p;
   a.frame_pair_off = d_frame_pair_off; a.pair_dens = e.pair_dens; a.pair_key = e.key_mean; a.pair_w = e.pair_w;
-  a.n_speakers = S; a.n_segs = (uint32_t)seg_begin.size();
+  a.n_speakers = S; a.n_segs = (uint32_t)seg.begin.size();
   HIP_TRY(c->fm_fold_a.ensure((size_t)F * a.shape.rows)); HIP_TRY(c->fm_fold_c.ensure((size_t)F * a.shape.rows));
   HIP_TRY(c->fm_frame_list.upload(frame_list.data(), F));
-  HIP_TRY(c->fm_seg_begin.upload(seg_begin.data(), seg_begin.size())); HIP_TRY(c->fm_seg_len.upload(seg_len.data(), seg_len.size()));
-  HIP_TRY(c->fm_spk_seg_off.upload(spk_seg_off.data(), S + 1));
+  HIP_TRY(c->fm_seg_begin.upload(seg.begin.data(), seg.begin.size())); HIP_TRY(c->fm_seg_len.upload(seg.len.data(), seg.len.size()));
+  HIP_TRY(c->fm_spk_seg_off.upload(seg.off.data(), seg.off.size()));
   HIP_TRY(c->fm_partial.ensure((size_t)a.n_segs * a.shape.rows * a.shape.cols));
   const size_t nk = (size_t)S * D * E, nG = nk * E;
   HIP_TRY(c->fm_beta.ensure(S)); HIP_TRY(c->fm_k.ensure(nk)); HIP_TRY(c->fm_G.ensure(nG));
@@ -2128,25 +2199,14 @@ static int fmllr_statistics(sr_model* m, sr_corpus* c, const EmArgs& e, const ui
   return SR_OK;
 }
 
-static void fmllr_zero(uint32_t D, uint32_t S, double* out_beta, double* out_k, double* out_G) {
-  const size_t nk = (size_t)S * D * (D + 1);
-  std::fill(out_beta, out_beta + S, 0.0);
-  std::fill(out_k, out_k + nk, 0.0);
-  std::fill(out_G, out_G + nk * (D + 1), 0.0);
-}
-
 int sr_fmllr_statistics_corpus(sr_model* m, sr_corpus* c, const uint16_t* states, const uint32_t* utt_speaker, uint32_t n_speakers,
                                int max_approx, double* out_beta, double* out_k, double* out_G) {
   return guarded(__func__, [&]() -> int {
   int rc = fmllr_check(m, c, utt_speaker, n_speakers, out_beta, out_k, out_G);
   if (rc) return rc;
-  if (c->n_frames == 0) { fmllr_zero(m->dim, n_speakers, out_beta, out_k, out_G); return SR_OK; }
   EmArgs e{};
-  std::vector<uint64_t> pair_off;
-  if ((rc = alignment_pairs(m, c, states, 0, max_approx, &e, &pair_off))) return rc;
-  HIP_TRY(c->fm_pair_dens.ensure(e.n_pairs));
-  e.pair_dens = c->fm_pair_dens.p;
-  HIP_TRY(launch_em_pairs(e, m->s_gmm));
+  if ((rc = adapt_pairs(m, c, states, max_approx, &e))) return rc;
+  if (e.n_pairs == 0) return adapt_zero(m->dim, n_speakers, out_beta, out_k, out_G);
   return fmllr_statistics(m, c, e, c->pair_off.p, utt_speaker, n_speakers, out_beta, out_k, out_G);
   });
 }
@@ -2157,17 +2217,9 @@ int sr_fmllr_statistics_bw_corpus(sr_model* m, sr_corpus* c, const uint16_t* aut
   return guarded(__func__, [&]() -> int {
   int rc = fmllr_check(m, c, utt_speaker, n_speakers, out_beta, out_k, out_G);
   if (rc) return rc;
-  if ((rc = fb_check(m, c, automata, aut_off, tdp, posterior_floor, out_cost))) return rc;
-  const uint32_t U = c->n_utts;
-  uint64_t n_items = 0;
-  if ((rc = fb_pass(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, true, &n_items))) return rc;
-  if (U) HIP_TRY(hipMemcpy(out_cost, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToHost));
   EmArgs e{};
-  if ((rc = item_pairs(m, c, n_items, 0, max_approx, &e))) return rc;
-  if (e.n_pairs == 0) { fmllr_zero(m->dim, n_speakers, out_beta, out_k, out_G); return SR_OK; }  // nothing above the floor
-  HIP_TRY(c->fm_pair_dens.ensure(e.n_pairs));
-  e.pair_dens = c->fm_pair_dens.p;
-  HIP_TRY(launch_em_pairs_weighted(e, m->s_gmm));
+  if ((rc = adapt_pairs_bw(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, max_approx, out_cost, &e))) return rc;
+  if (e.n_pairs == 0) return adapt_zero(m->dim, n_speakers, out_beta, out_k, out_G);
   HIP_TRY(c->fm_frame_pair_off.ensure(c->n_frames + 1));
   HIP_TRY(launch_fmllr_item_frames(c->fb_item_off.p, c->fb_pair_end.p, c->n_frames, c->fm_frame_pair_off.p, m->s_gmm));
   return fmllr_statistics(m, c, e, c->fm_frame_pair_off.p, utt_speaker, n_speakers, out_beta, out_k, out_G);
@@ -2182,11 +2234,8 @@ int sr_corpus_transform(sr_model* m, sr_corpus* c, const uint32_t* utt_speaker, 
   if (rc) return rc;
   if (n_speakers == 0) return fail(SR_EINVAL, "n_speakers is 0");
   if (!W) return fail(SR_EINVAL, "W is null");
-  if (!utt_speaker && c->n_utts) return fail(SR_EINVAL, "utt_speaker is null");
-  for (uint32_t u = 0; u < c->n_utts; u++)
-    if (utt_speaker[u] >= n_speakers) return fail(SR_EINVAL, "utterance %u: speaker %u >= n_speakers %u", u, utt_speaker[u], n_speakers);
+  if ((rc = speaker_check(m, c, utt_speaker, n_speakers, "fMLLR transform"))) return rc;
   const uint32_t D = m->dim;
-  if (D > fmllr_max_dim()) return fail(SR_ELIMIT, "dimension %u exceeds %u (fMLLR transform)", D, fmllr_max_dim());
   const uint64_t F = c->n_frames;
   if ((rc = srhost::corpus_ready(c, 0, F, m->s_gmm))) return rc;  // an asynchronous upload of c: wait for all of it
   sr_corpus* t = new sr_corpus();
@@ -2226,11 +2275,8 @@ static int mllr_check(sr_model* m, sr_corpus* c, const uint32_t* utt_speaker, ui
   if (!dens_class && m->n_dens) return fail(SR_EINVAL, "dens_class is null");
   for (uint64_t d = 0; d < m->n_dens; d++)
     if (dens_class[d] >= n_classes) return fail(SR_EINVAL, "density %llu: class %u >= n_classes %u", (unsigned long long)d, dens_class[d], n_classes);
-  if (!utt_speaker && c->n_utts) return fail(SR_EINVAL, "utt_speaker is null");
-  for (uint32_t u = 0; u < c->n_utts; u++)
-    if (utt_speaker[u] >= n_speakers) return fail(SR_EINVAL, "utterance %u: speaker %u >= n_speakers %u", u, utt_speaker[u], n_speakers);
+  if ((rc = speaker_check(m, c, utt_speaker, n_speakers, "MLLR statistics"))) return rc;
   const uint32_t D = m->dim;
-  if (D > fmllr_max_dim()) return fail(SR_ELIMIT, "dimension %u exceeds %u (MLLR statistics)", D, fmllr_max_dim());
   if ((uint64_t)n_speakers * m->n_dens >= 0xFFFFFFFFull)
     return fail(SR_ELIMIT, "n_speakers * densities = %llu does not fit the 32-bit (speaker, density) keys", (unsigned long long)n_speakers * m->n_dens);
   size_t free_b = 0, total_b = 0;
@@ -2240,13 +2286,6 @@ static int mllr_check(sr_model* m, sr_corpus* c, const uint32_t* utt_speaker, ui
     return fail(SR_ELIMIT, "the statistics of %u speakers x %u classes (%.0f bytes) exceed a quarter of the free device memory (%llu bytes)",
                 n_speakers, n_classes, out_bytes, (unsigned long long)free_b);
   return SR_OK;
-}
-
-static void mllr_zero(uint32_t D, uint64_t groups, double* out_beta, double* out_k, double* out_G) {
-  const size_t nk = (size_t)groups * D * (D + 1);
-  std::fill(out_beta, out_beta + groups, 0.0);
-  std::fill(out_k, out_k + nk, 0.0);
-  std::fill(out_G, out_G + nk * (D + 1), 0.0);
 }
 
 // entries, contraction and reduction over the pairs `e` describes (formed already), per (speaker, class); the results to the host
@@ -2291,21 +2330,14 @@ static int mllr_statistics(sr_model* m, sr_corpus* c, const EmArgs& e, const uin
   if ((rc = prof_end(m, m->s_gmm, &ep))) return rc;
   HIP_TRY(hipStreamSynchronize(m->s_gmm));
   // every group's entries, cut into segments
-  std::vector<uint32_t> grp_begin((size_t)n_groups + 1), seg_begin, seg_len, grp_seg_off((size_t)n_groups + 1, 0);
+  std::vector<uint32_t> grp_begin((size_t)n_groups + 1);
   HIP_TRY(hipMemcpy(grp_begin.data(), c->ml_grp_begin.p, sizeof(uint32_t) * grp_begin.size(), hipMemcpyDeviceToHost));
   if (grp_begin[0] != 0 || grp_begin[n_groups] != a.n_entries) return fail(SR_EINTERNAL, "MLLR statistics: the groups do not cover the entries");
-  const uint32_t L = fmllr_seg_frames();
-  for (uint32_t g = 0; g < n_groups; g++) {
-    if (grp_begin[g + 1] < grp_begin[g]) return fail(SR_EINTERNAL, "MLLR statistics: group bounds out of order");
-    for (uint32_t b = grp_begin[g]; b < grp_begin[g + 1]; b += L) {
-      seg_begin.push_back(b);
-      seg_len.push_back(std::min(L, grp_begin[g + 1] - b));
-    }
-    grp_seg_off[g + 1] = (uint32_t)seg_begin.size();
-  }
-  a.n_segs = (uint32_t)seg_begin.size();
-  HIP_TRY(c->fm_seg_begin.upload(seg_begin.data(), seg_begin.size())); HIP_TRY(c->fm_seg_len.upload(seg_len.data(), seg_len.size()));
-  HIP_TRY(c->fm_spk_seg_off.upload(grp_seg_off.data(), grp_seg_off.size()));
+  if (!std::is_sorted(grp_begin.begin(), grp_begin.end())) return fail(SR_EINTERNAL, "MLLR statistics: group bounds out of order");
+  const srplan::Segments seg(grp_begin.data(), n_groups, fmllr_seg_frames());
+  a.n_segs = (uint32_t)seg.begin.size();
+  HIP_TRY(c->fm_seg_begin.upload(seg.begin.data(), seg.begin.size())); HIP_TRY(c->fm_seg_len.upload(seg.len.data(), seg.len.size()));
+  HIP_TRY(c->fm_spk_seg_off.upload(seg.off.data(), seg.off.size()));
   HIP_TRY(c->fm_partial.ensure((size_t)a.n_segs * a.shape.rows * a.shape.cols));
   const size_t nk = (size_t)n_groups * D * E, nG = nk * E;
   HIP_TRY(c->fm_beta.ensure(n_groups)); HIP_TRY(c->fm_k.ensure(nk)); HIP_TRY(c->fm_G.ensure(nG));
@@ -2332,14 +2364,9 @@ int sr_mllr_statistics_corpus(sr_model* m, sr_corpus* c, const uint16_t* states,
   return guarded(__func__, [&]() -> int {
   int rc = mllr_check(m, c, utt_speaker, n_speakers, dens_class, n_classes, out_beta, out_k, out_G);
   if (rc) return rc;
-  const uint64_t groups = (uint64_t)n_speakers * n_classes;
-  if (c->n_frames == 0) { mllr_zero(m->dim, groups, out_beta, out_k, out_G); return SR_OK; }
   EmArgs e{};
-  std::vector<uint64_t> pair_off;
-  if ((rc = alignment_pairs(m, c, states, 0, max_approx, &e, &pair_off))) return rc;
-  HIP_TRY(c->fm_pair_dens.ensure(e.n_pairs));
-  e.pair_dens = c->fm_pair_dens.p;
-  HIP_TRY(launch_em_pairs(e, m->s_gmm));
+  if ((rc = adapt_pairs(m, c, states, max_approx, &e))) return rc;
+  if (e.n_pairs == 0) return adapt_zero(m->dim, (uint64_t)n_speakers * n_classes, out_beta, out_k, out_G);
   return mllr_statistics(m, c, e, utt_speaker, n_speakers, dens_class, n_classes, out_beta, out_k, out_G);
   });
 }
@@ -2351,18 +2378,9 @@ int sr_mllr_statistics_bw_corpus(sr_model* m, sr_corpus* c, const uint16_t* auto
   return guarded(__func__, [&]() -> int {
   int rc = mllr_check(m, c, utt_speaker, n_speakers, dens_class, n_classes, out_beta, out_k, out_G);
   if (rc) return rc;
-  if ((rc = fb_check(m, c, automata, aut_off, tdp, posterior_floor, out_cost))) return rc;
-  const uint32_t U = c->n_utts;
-  const uint64_t groups = (uint64_t)n_speakers * n_classes;
-  uint64_t n_items = 0;
-  if ((rc = fb_pass(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, true, &n_items))) return rc;
-  if (U) HIP_TRY(hipMemcpy(out_cost, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToHost));
   EmArgs e{};
-  if ((rc = item_pairs(m, c, n_items, 0, max_approx, &e))) return rc;
-  if (e.n_pairs == 0) { mllr_zero(m->dim, groups, out_beta, out_k, out_G); return SR_OK; }  // nothing above the floor
-  HIP_TRY(c->fm_pair_dens.ensure(e.n_pairs));
-  e.pair_dens = c->fm_pair_dens.p;
-  HIP_TRY(launch_em_pairs_weighted(e, m->s_gmm));
+  if ((rc = adapt_pairs_bw(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, max_approx, out_cost, &e))) return rc;
+  if (e.n_pairs == 0) return adapt_zero(m->dim, (uint64_t)n_speakers * n_classes, out_beta, out_k, out_G);
   return mllr_statistics(m, c, e, utt_speaker, n_speakers, dens_class, n_classes, out_beta, out_k, out_G);
   });
 }
@@ -2595,76 +2613,104 @@ static int bgfb_tables(sr_model* m, sr_bigram* b, double scale) {
   return SR_OK;
 }
 
-// The launch groups of a pass, cut like NetFbPass' with the per-utterance vectors counted in, each with its utterances ordered longest
-// first.  run() enqueues a chunk's groups: per frame the step and the product, forward then backward, the word posteriors, per_group.
+// The time-step recursion over the bigram search network with `mult` operand vectors per utterance (1: BgFbPass; 2: BgSmbrPass, the
+// accuracy side beside every cost).  The launch groups are cut like NetFbPass' on a cost prefix that counts the per-utterance vectors
+// in, each with its utterances ordered longest first.  run_groups() enqueues a chunk's groups: per frame the step and the product,
+// forward then backward, then after(group).
 extern "C++" {
-struct BgFbPass {
+struct BgStepPass {
   srplan::Groups groups;
   srplan::StepOrder steps;                 // each group's range, longest first
-  BgFbArgs a{};
   const double *lk = nullptr, *lkT = nullptr;
   const uint32_t* d_order = nullptr;       // `order` on the device
-  bool want_words = true;                  // the word posteriors of every group (the MMI passes read gamma itself)
-  size_t ci = 0;
+  uint64_t max_gf = 1;                     // frames of the largest group
+  uint32_t mult = 1;
+  size_t ci = 0;  // run_chunks searches the chunks in order
 
-  int setup(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, const std::vector<Chunk>& chunks) {
+  // plans the groups on `cost`, sizes and clears the workspace, and fills `a` with everything but the launch's own fields and `post`
+  int workspace(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, uint32_t mult_, const std::vector<uint64_t>& cost,
+                const std::vector<Chunk>& chunks, BgFbArgs* a) {
     const uint64_t P = b->net.n_positions;
     const uint32_t W = b->net.n_words, Kp = bgfb_padded(W), U = c->n_utts;
-    groups = srplan::launch_groups(chunks, bgfb_cost(c, b).data(), m->fb_budget);
+    mult = mult_;
+    groups = srplan::launch_groups(chunks, cost.data(), m->fb_budget);
     steps = srplan::StepOrder(groups, c->frame_off.data(), U);
-    const uint64_t max_gf = std::max<uint64_t>(1, groups.max_span(c->frame_off.data()));
+    max_gf = std::max<uint64_t>(1, groups.max_span(c->frame_off.data()));
     const uint32_t max_gu = std::max(1u, groups.max_utts());
     int rc = bgfb_tables(m, b, scale);
     if (rc) return rc;
     lk = b->fb_lk.p; lkT = b->fb_lkT.p;
-    const size_t rows = ((size_t)max_gu + 63) & ~(size_t)63;  // the product reads whole 16-column tiles of vec
-    HIP_TRY(c->fb_trellis.ensure(max_gf * P));
-    HIP_TRY(c->nf_post.ensure(max_gf * W));
+    const size_t rows = ((size_t)mult * max_gu + 63) & ~(size_t)63;  // the product reads whole 16-column tiles of vec
+    HIP_TRY(c->fb_trellis.ensure(max_gf * mult * P));
     HIP_TRY(c->out_cost.ensure(U));
     HIP_TRY(c->bgfb_vec.ensure(rows * Kp));
     HIP_TRY(c->bgfb_prod.ensure(rows * Kp));
     HIP_TRY(c->bgfb_wend.ensure(rows * Kp));
     HIP_TRY(c->bgfb_m.ensure(rows));
-    HIP_TRY(c->bgfb_xb.ensure(2 * (size_t)max_gu * P));
+    HIP_TRY(c->bgfb_xb.ensure(2 * (size_t)mult * max_gu * P));
     HIP_TRY(c->bgfb_order.upload(steps.order.data(), steps.order.size()));
     d_order = c->bgfb_order.p;
     HIP_TRY(hipMemset(c->bgfb_vec.p, 0, rows * Kp * sizeof(double)));  // (the padding columns h >= W stay 0 from here on)
     if (U) HIP_TRY(hipMemset(c->out_cost.p, 0, sizeof(double) * U));  // T_u = 0: F_u = 0, the start hypothesis is a word end
     HIP_TRY(hipDeviceSynchronize());
-    a.n_words = W; a.silence = b->net.silence; a.n_positions = (uint32_t)P; a.Kp = Kp;
-    a.slot_off = b->slot_off.p; a.pos_info = b->pos_info.p; a.pos_slot = b->pos_slot.p; a.lmT = b->lmT.p;
-    memcpy(a.tdp, b->net.tdp, sizeof(a.tdp));
-    a.scale = scale; a.ld = m->ld; a.frame_off = c->d_frame_off.p;
-    a.trellis = c->fb_trellis.p; a.vec = c->bgfb_vec.p; a.prod = c->bgfb_prod.p; a.wend = c->bgfb_wend.p; a.m = c->bgfb_m.p; a.xb = c->bgfb_xb.p;
-    a.out_cost = c->out_cost.p; a.post = c->nf_post.p;
-    // trellis traffic per (frame, position) as NetFbPass; the product reads the table once per frame step and direction
-    if (m->profiling) m->prof.search_bytes += 32.0 * (double)P * (double)c->n_frames;
+    a->n_words = W; a->silence = b->net.silence; a->n_positions = (uint32_t)P; a->Kp = Kp;
+    a->slot_off = b->slot_off.p; a->pos_info = b->pos_info.p; a->pos_slot = b->pos_slot.p; a->lmT = b->lmT.p;
+    memcpy(a->tdp, b->net.tdp, sizeof(a->tdp));
+    a->scale = scale; a->ld = m->ld; a->frame_off = c->d_frame_off.p;
+    a->trellis = c->fb_trellis.p; a->vec = c->bgfb_vec.p; a->prod = c->bgfb_prod.p; a->wend = c->bgfb_wend.p; a->m = c->bgfb_m.p; a->xb = c->bgfb_xb.p;
+    a->out_cost = c->out_cost.p;
     return SR_OK;
   }
-  template <class PerGroup>
-  int run(sr_corpus* c, const Chunk& ch, const double* table, hipStream_t s, PerGroup per_group) {
+  // forward() and backward() launch frame a->t of the first a->n_alive utterances from the arguments `a` is part of
+  template <class Forward, class Backward, class After>
+  int run_groups(sr_corpus* c, const Chunk& ch, const double* table, hipStream_t s, BgFbArgs* a, Forward forward, Backward backward,
+                 After after) {
     for (const Group& g : groups.of_chunk[ci]) {
-      a.scores = table; a.frame_base = ch.f0; a.group_f0 = c->frame_off[g.u0];
-      a.order = d_order + g.u0; a.n_group = g.u1 - g.u0;
+      a->scores = table; a->frame_base = ch.f0; a->group_f0 = c->frame_off[g.u0];
+      a->order = d_order + g.u0; a->n_group = g.u1 - g.u0;
       const uint32_t t_max = steps.t_max(g);
       for (uint32_t t = 0; t < t_max; t++) {
-        a.t = t; a.n_alive = steps.alive(g, t);
-        HIP_TRY(launch_bgfb_forward(a, s));
+        a->t = t; a->n_alive = steps.alive(g, t);
+        HIP_TRY(forward());
         const uint32_t next = steps.alive(g, t + 1);  // only those that go on need their entries
-        HIP_TRY(launch_bgfb_product(lk, a.vec, a.prod, a.Kp, next, s));
+        HIP_TRY(launch_bgfb_product(lk, a->vec, a->prod, a->Kp, mult * next, s));
       }
       for (uint32_t t = t_max; t-- > 0;) {
-        a.t = t; a.n_alive = steps.alive(g, t);
-        HIP_TRY(launch_bgfb_backward(a, s));
-        if (t) HIP_TRY(launch_bgfb_product(lkT, a.vec, a.prod, a.Kp, a.n_alive, s));
+        a->t = t; a->n_alive = steps.alive(g, t);
+        HIP_TRY(backward());
+        if (t) HIP_TRY(launch_bgfb_product(lkT, a->vec, a->prod, a->Kp, mult * a->n_alive, s));
       }
-      const uint64_t n = c->frame_off[g.u1] - c->frame_off[g.u0];
-      if (want_words) HIP_TRY(launch_bgfb_words(a, n, s));
-      int rc = per_group(a, n);
+      int rc = after(g);
       if (rc) return rc;
     }
     ci++;
     return SR_OK;
+  }
+};
+
+// BgStepPass at multiplicity 1 with the word posteriors: run() enqueues a chunk's groups, after each recursion the word posteriors
+// (want_words) and per_group(args, frames of the group).
+struct BgFbPass : BgStepPass {
+  BgFbArgs a{};
+  bool want_words = true;  // the word posteriors of every group (the MMI passes read gamma itself)
+
+  int setup(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, const std::vector<Chunk>& chunks) {
+    int rc = workspace(m, c, b, scale, 1, bgfb_cost(c, b), chunks, &a);
+    if (rc) return rc;
+    HIP_TRY(c->nf_post.ensure(max_gf * b->net.n_words));
+    a.post = c->nf_post.p;
+    // trellis traffic per (frame, position) as NetFbPass; the product reads the table once per frame step and direction
+    if (m->profiling) m->prof.search_bytes += 32.0 * (double)b->net.n_positions * (double)c->n_frames;
+    return SR_OK;
+  }
+  template <class PerGroup>
+  int run(sr_corpus* c, const Chunk& ch, const double* table, hipStream_t s, PerGroup per_group) {
+    return run_groups(c, ch, table, s, &a, [&] { return launch_bgfb_forward(a, s); }, [&] { return launch_bgfb_backward(a, s); },
+                      [&](const Group& g) -> int {
+                        const uint64_t n = c->frame_off[g.u1] - c->frame_off[g.u0];
+                        if (want_words) HIP_TRY(launch_bgfb_words(a, n, s));
+                        return per_group(a, n);
+                      });
   }
 };
 }  // extern "C++"
@@ -2823,40 +2869,23 @@ static int occ_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_pa
   Chains ch;
   if (chain) build_chains(l, U, trans, trans_off, &ch);
   // the mixture lists: the distinct mixtures (ascending) of the lexicon, or of each chain, and the positions carrying each
-  std::vector<uint64_t> tr_off(U + 1, 0);
-  srplan::MixLists<uint16_t> ml;
-  uint64_t item_bound = 0;
-  if (!chain) ml.add(l->h_slot_info.data(), P, 0xFFFFu);
-  for (uint32_t u = 0; u < U; u++) {
-    const uint64_t N = chain ? ch.off[u + 1] - ch.off[u] : P, T = c->frame_off[u + 1] - c->frame_off[u];
-    tr_off[u + 1] = tr_off[u] + N * T;
-    if (chain) ml.add(ch.info.data() + ch.off[u], N, 0xFFFFu);
-    item_bound += T * ml.n_mix(chain ? u : 0);
-  }
-  if (want_items && item_bound >= (1ull << 31)) return fail(SR_ELIMIT, "too many (frame, mixture) occupancies");
+  const srplan::OccPlan<uint16_t> pl(c->frame_off.data(), U, chain ? ch.off.data() : nullptr, chain ? ch.info.data() : l->h_slot_info.data(), P,
+                                     true);
+  if (want_items && pl.item_bound >= (1ull << 31)) return fail(SR_ELIMIT, "too many (frame, mixture) occupancies");
   std::vector<Chunk> chunks;
   int rc = prepare_chunks(m, c, &chunks);
   if (rc) return rc;
-  const srplan::Groups groups = srplan::launch_groups(chunks, trellis_cost(tr_off).data(), m->fb_budget);
+  srplan::Groups groups;
+  if ((rc = trellis_groups(m, c, chunks, pl.tr_off, &groups))) return rc;
   const uint64_t max_gf = std::max<uint64_t>(1, groups.max_span(c->frame_off.data()));
-  HIP_TRY(c->fb_trellis_off.upload(tr_off.data(), U + 1));
-  HIP_TRY(c->fb_trellis.ensure(std::max<uint64_t>(1, groups.max_span(tr_off.data()))));
   if (chain) {
-    HIP_TRY(c->mmi_chain_off.upload(ch.off.data(), U + 1));
-    HIP_TRY(c->mmi_info.upload(ch.info.data(), ch.info.size()));
-    HIP_TRY(c->mmi_src.upload(ch.src.data(), ch.src.size()));
-    HIP_TRY(c->mmi_dst.upload(ch.dst.data(), ch.dst.size()));
+    if ((rc = upload_chains(c, ch))) return rc;
   } else {
     HIP_TRY(c->nf_ends.ensure(max_gf));
   }
   size_t scan_bytes = 0;
-  if (want_items) {
-    if (chain) HIP_TRY(c->fb_mix_off.upload(ml.mix_off.data(), U + 1));
-    HIP_TRY(c->fb_mix.upload(ml.mix.data(), ml.mix.size()));
-    HIP_TRY(c->fb_slot_beg.upload(ml.slot_beg.data(), ml.slot_beg.size()));
-    HIP_TRY(c->fb_slot_pos.upload(ml.slot_pos.data(), ml.slot_pos.size()));
-    if ((rc = ensure_items(c, max_gf, F, item_bound, &scan_bytes))) return rc;
-  }
+  if (want_items && ((rc = upload_mix_lists(c, pl.ml, chain, c->fb_slot_pos)) || (rc = ensure_items(c, max_gf, F, pl.item_bound, &scan_bytes))))
+    return rc;
   NetFbArgs na{};
   na.net = l->net; na.ld = m->ld; na.frame_off = c->d_frame_off.p; na.scale = scale; na.word_penalty = p->word_penalty;
   na.trellis = c->fb_trellis.p; na.out_cost = c->out_cost.p; na.ends = c->nf_ends.p;
@@ -2866,18 +2895,15 @@ static int occ_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_pa
   ca.chain_off = c->mmi_chain_off.p; ca.info = c->mmi_info.p; ca.src = c->mmi_src.p; ca.dst = c->mmi_dst.p; ca.sil_len = ch.sil_len;
   ca.trellis = c->fb_trellis.p; ca.trellis_off = c->fb_trellis_off.p; ca.out_cost = c->out_cost.p;
   OccItemArgs ia{};
-  ia.frame_off = c->d_frame_off.p; ia.trellis = c->fb_trellis.p; ia.n_cols = (uint32_t)P; ia.n_mix = chain ? 0u : ml.n_mix(0);
-  if (chain) { ia.trellis_off = c->fb_trellis_off.p; ia.chain_off = c->mmi_chain_off.p; ia.mix_off = c->fb_mix_off.p; }
-  ia.mix = c->fb_mix.p; ia.slot_beg = c->fb_slot_beg.p; ia.slot_pos = c->fb_slot_pos.p; ia.gate = gate; ia.floor = posterior_floor;
-  item_fields(&ia, c);
+  occ_item_fields(&ia, c, pl.ml, chain, P, c->fb_slot_pos, gate, posterior_floor);
   size_t ci = 0;  // run_chunks searches the chunks in order
   rc = run_chunks(m, chunks, [&](const Chunk& k, double* table) { return score_chunk(m, c, k.f0, k.f1, p->gmm_kernel, table); },
       [&](const Chunk& k, const double* table, hipStream_t s) -> int {
         if (want_items && ci == 0) HIP_TRY(reset_item_count(c->fb_base, s));
         for (const Group& g : groups.of_chunk[ci]) {
           if (chain) {
-            ca.scores = table; ca.frame_base = k.f0; ca.utt_first = g.u0; ca.n_utts = g.u1 - g.u0; ca.max_positions = 1;
-            for (uint32_t u = g.u0; u < g.u1; u++) ca.max_positions = std::max(ca.max_positions, (uint32_t)(ch.off[u + 1] - ch.off[u]));
+            ca.scores = table; ca.frame_base = k.f0; ca.utt_first = g.u0; ca.n_utts = g.u1 - g.u0;
+            ca.max_positions = srplan::max_positions(g, ch.off.data());
             HIP_TRY(launch_chain_forward(ca, s));
             HIP_TRY(launch_chain_backward(ca, s));
           } else {
@@ -2886,8 +2912,8 @@ static int occ_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_pa
             HIP_TRY(launch_netocc_backward(na, s));
           }
           if (want_items) {
-            ia.utt_first = g.u0; ia.n_utts = g.u1 - g.u0; ia.group_f0 = c->frame_off[g.u0];
-            HIP_TRY(launch_occ_items(ia, c->frame_off[g.u1] - c->frame_off[g.u0], c->fb_scan_temp.p, scan_bytes, c->fb_scan.p, s));
+            const uint64_t n = item_group(&ia, c, g.u0, g.u1);
+            HIP_TRY(launch_occ_items(ia, n, c->fb_scan_temp.p, scan_bytes, c->fb_scan.p, s));
           }
         }
         ci++;
@@ -2897,7 +2923,7 @@ static int occ_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_pa
   if (want_items && (rc = read_item_count(c->fb_base, n_items))) return rc;
   if (m->profiling) {  // trellis traffic per (frame, position) as the network pass counts it: alpha out, alpha in + part out, part in
     m->prof.frames += F;
-    m->prof.search_bytes += 32.0 * (double)tr_off[U];
+    m->prof.search_bytes += 32.0 * (double)pl.tr_off[U];
   }
   return SR_OK;
 }
@@ -2909,8 +2935,8 @@ template <class Pass>
 static int mmi_statistics(sr_model* m, sr_corpus* c, double scale, int max_approx, double* out_num_cost, double* out_den_cost,
                           double* num_mean_acc, double* num_mean_w, double* num_var_acc, double* num_var_w, double* den_mean_acc,
                           double* den_mean_w, double* den_var_acc, double* den_var_w, Pass pass) {
-  if (!out_num_cost || !out_den_cost || !num_mean_acc || !num_mean_w || !num_var_acc || !num_var_w || !den_mean_acc || !den_mean_w ||
-      !den_var_acc || !den_var_w)
+  if (any_null({out_num_cost, out_den_cost, num_mean_acc, num_mean_w, num_var_acc, num_var_w, den_mean_acc, den_mean_w, den_var_acc,
+                den_var_w}))
     return fail(SR_EINVAL, "null output");
   const uint32_t U = c->n_utts;
   int rc;
@@ -3050,6 +3076,14 @@ static int smbr_check(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_
   return check_fits(m, smbr_cost(c, l));
 }
 
+// kappa F_u, Abar_u on the device -> F_u, Abar_u
+static int smbr_costs(sr_corpus* c, double scale, double* out_cost, double* out_acc) {
+  int rc = netfb_costs(c, scale, out_cost);
+  if (rc) return rc;
+  if (c->n_utts) HIP_TRY(hipMemcpy(out_acc, c->smbr_acc.p, sizeof(double) * c->n_utts, hipMemcpyDeviceToHost));
+  return SR_OK;
+}
+
 // NetFbPass for the accuracy recursions: the launch groups are consecutive utterances of a chunk whose trellises (16 B per frame and
 // position) fit m->fb_budget together (smbr_check: every utterance fits alone).  run() enqueues a chunk's groups in order: forward,
 // backward, then per_group(item arguments of the group, frames of the group).  want_items: the item path is ready (ensure_items) and
@@ -3078,18 +3112,12 @@ struct SmbrPass {
     HIP_TRY(c->out_cost.ensure(c->n_utts));
     HIP_TRY(c->smbr_acc.ensure(c->n_utts));
     HIP_TRY(c->smbr_ref.upload(ref_states, F));
-    HIP_TRY(c->fb_mix.upload(ml.mix.data(), ml.mix.size()));
-    HIP_TRY(c->fb_slot_beg.upload(ml.slot_beg.data(), ml.slot_beg.size()));
-    HIP_TRY(c->fb_slot_pos.upload(ml.slot_pos.data(), ml.slot_pos.size()));
-    if (want_items) {
-      int rc = ensure_items(c, max_gf, F, item_bound, &scan_bytes);
-      if (rc) return rc;
-      item_fields(&ia, c);
-    }
+    int rc = upload_mix_lists(c, ml, false, c->fb_slot_pos);
+    if (rc) return rc;
+    if (want_items && (rc = ensure_items(c, max_gf, F, item_bound, &scan_bytes))) return rc;
     a.net = l->net; a.ld = m->ld; a.frame_off = c->d_frame_off.p; a.scale = scale; a.word_penalty = p->word_penalty;
     a.ref = c->smbr_ref.p; a.trellis = c->fb_trellis.p; a.ends = c->smbr_ends.p; a.out_cost = c->out_cost.p; a.out_acc = c->smbr_acc.p;
-    ia.frame_off = c->d_frame_off.p; ia.trellis = c->fb_trellis.p; ia.n_cols = (uint32_t)P; ia.n_mix = ml.n_mix(0);
-    ia.mix = c->fb_mix.p; ia.slot_beg = c->fb_slot_beg.p; ia.slot_pos = c->fb_slot_pos.p; ia.floor = floor;
+    occ_item_fields(&ia, c, ml, false, P, c->fb_slot_pos, nullptr, floor);
     // trellis traffic per (frame, position): (alpha, abar) out, both in + the part out, the part in (items)
     if (m->profiling) m->prof.search_bytes += 48.0 * (double)P * (double)F;
     return SR_OK;
@@ -3100,85 +3128,72 @@ struct SmbrPass {
       a.scores = table; a.frame_base = ch.f0; a.utt_first = g.u0; a.n_utts = g.u1 - g.u0; a.group_f0 = c->frame_off[g.u0];
       HIP_TRY(launch_smbr_forward(a, s));
       HIP_TRY(launch_smbr_backward(a, s));
-      ia.utt_first = g.u0; ia.n_utts = g.u1 - g.u0; ia.group_f0 = c->frame_off[g.u0];
-      int rc = per_group(ia, c->frame_off[g.u1] - c->frame_off[g.u0]);
+      const uint64_t n = item_group(&ia, c, g.u0, g.u1);
+      int rc = per_group(ia, n);
       if (rc) return rc;
     }
     ci++;
     return SR_OK;
   }
 };
-}  // extern "C++"
 
-// kappa F_u, Abar_u on the device -> F_u, Abar_u
-static int smbr_costs(sr_corpus* c, double scale, double* out_cost, double* out_acc) {
-  int rc = netfb_costs(c, scale, out_cost);
-  if (rc) return rc;
-  if (c->n_utts) HIP_TRY(hipMemcpy(out_acc, c->smbr_acc.p, sizeof(double) * c->n_utts, hipMemcpyDeviceToHost));
-  return SR_OK;
-}
-
-int sr_net_accuracies_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
-                             uint32_t max_items, const uint16_t* ref_states, double* out_cost, double* out_acc, uint16_t* out_count,
-                             uint16_t* out_state, double* out_weight) {
-  return guarded(__func__, [&]() -> int {
-  int rc = smbr_check(m, c, l, p, scale, posterior_floor, ref_states);
-  if (rc) return rc;
+// What the accuracy and sMBR statistics calls of either network do once their check has passed.  Pass is the network's pass (SmbrPass,
+// BgSmbrPass), setup(pass, chunks, want_items) its set-up, launch_items its signed-items launcher (launch_smbr_items,
+// launch_bgocc_signed_items).
+template <class Pass, class LaunchItems, class Setup>
+static int smbr_accuracies(sr_model* m, sr_corpus* c, int gmm_kernel, double scale, uint32_t max_items, double* out_cost, double* out_acc,
+                           uint16_t* out_count, uint16_t* out_state, double* out_weight, LaunchItems launch_items, Setup setup) {
   if (!out_cost || !out_acc) return fail(SR_EINVAL, "null argument");
   bool post = false;
-  if ((rc = top_items_arguments(out_count, out_state, out_weight, "out_state", max_items, &post))) return rc;
-  const uint64_t F = c->n_frames;
+  int rc = top_items_arguments(out_count, out_state, out_weight, "out_state", max_items, &post);
+  if (rc) return rc;
   std::vector<Chunk> chunks;
   if ((rc = prepare_chunks(m, c, &chunks))) return rc;
-  SmbrPass sp;
-  if ((rc = sp.setup(m, c, l, p, scale, posterior_floor, ref_states, post, chunks))) return rc;
-  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); },
+  Pass sp;
+  if ((rc = setup(sp, chunks, post))) return rc;
+  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, gmm_kernel, table); },
       [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
         if (post && sp.ci == 0) HIP_TRY(reset_item_count(c->fb_base, s));
-        return sp.run(c, ch, table, s, [&](const OccItemArgs& ia, uint64_t n) -> int {
-          if (post) HIP_TRY(launch_smbr_items(ia, 0, n, c->fb_scan_temp.p, sp.scan_bytes, c->fb_scan.p, s));
+        return sp.run(c, ch, table, s, [&](const auto& ia, uint64_t n) -> int {
+          if (post) HIP_TRY(launch_items(ia, 0, n, c->fb_scan_temp.p, sp.scan_bytes, c->fb_scan.p, s));
           return SR_OK;
         });
       });
   if (rc) return rc;
-  if (m->profiling) m->prof.frames += F;
+  if (m->profiling) m->prof.frames += c->n_frames;
   if ((rc = smbr_costs(c, scale, out_cost, out_acc))) return rc;
   return post ? top_of_items(m, c, max_items, launch_smbr_top, out_count, out_state, out_weight) : SR_OK;
-  });
 }
 
-int sr_smbr_statistics_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
-                              int max_approx, const uint16_t* ref_states, double* out_cost, double* out_acc, double* num_mean_acc,
-                              double* num_mean_w, double* num_var_acc, double* num_var_w, double* den_mean_acc, double* den_mean_w,
-                              double* den_var_acc, double* den_var_w) {
-  return guarded(__func__, [&]() -> int {
-  int rc = smbr_check(m, c, l, p, scale, posterior_floor, ref_states);
-  if (rc) return rc;
-  if (!out_cost || !out_acc || !num_mean_acc || !num_mean_w || !num_var_acc || !num_var_w || !den_mean_acc || !den_mean_w ||
-      !den_var_acc || !den_var_w)
+template <class Pass, class LaunchItems, class Setup>
+static int smbr_statistics(sr_model* m, sr_corpus* c, int gmm_kernel, double scale, int max_approx, double* out_cost, double* out_acc,
+                           double* num_mean_acc, double* num_mean_w, double* num_var_acc, double* num_var_w, double* den_mean_acc,
+                           double* den_mean_w, double* den_var_acc, double* den_var_w, LaunchItems launch_items, Setup setup) {
+  if (any_null({out_cost, out_acc, num_mean_acc, num_mean_w, num_var_acc, num_var_w, den_mean_acc, den_mean_w, den_var_acc, den_var_w}))
     return fail(SR_EINVAL, "null output");
   const uint64_t F = c->n_frames;
+  int rc;
   c->acc_valid = false;
   std::vector<Chunk> chunks;
   if ((rc = prepare_chunks(m, c, &chunks))) return rc;
-  SmbrPass sp;
-  if ((rc = sp.setup(m, c, l, p, scale, posterior_floor, ref_states, true, chunks))) return rc;
+  Pass sp;
+  if ((rc = setup(sp, chunks, true))) return rc;
   // one pass, the items of both signs: the positive ones in the fb_item_* buffers, the negative ones beside them
   const uint64_t nb = sp.item_bound;
   HIP_TRY(c->smbr_base.ensure(1)); HIP_TRY(c->smbr_item_off.ensure(F + 1));
   HIP_TRY(c->smbr_item_frame.ensure(nb)); HIP_TRY(c->smbr_item_mix.ensure(nb)); HIP_TRY(c->smbr_item_w.ensure(nb));
-  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); },
+  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, gmm_kernel, table); },
       [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
         if (sp.ci == 0) {
           HIP_TRY(reset_item_count(c->fb_base, s));
           HIP_TRY(reset_item_count(c->smbr_base, s));
         }
-        return sp.run(c, ch, table, s, [&](const OccItemArgs& pos, uint64_t n) -> int {
-          OccItemArgs neg = pos;
+        return sp.run(c, ch, table, s, [&](const auto& pos, uint64_t n) -> int {
+          auto neg = pos;
           neg.item_base = c->smbr_base.p; neg.item_off = c->smbr_item_off.p;
           neg.item_frame = c->smbr_item_frame.p; neg.item_mix = c->smbr_item_mix.p; neg.item_w = c->smbr_item_w.p;
-          HIP_TRY(launch_smbr_items(pos, +1, n, c->fb_scan_temp.p, sp.scan_bytes, c->fb_scan.p, s));
-          HIP_TRY(launch_smbr_items(neg, -1, n, c->fb_scan_temp.p, sp.scan_bytes, c->fb_scan.p, s));
+          HIP_TRY(launch_items(pos, +1, n, c->fb_scan_temp.p, sp.scan_bytes, c->fb_scan.p, s));
+          HIP_TRY(launch_items(neg, -1, n, c->fb_scan_temp.p, sp.scan_bytes, c->fb_scan.p, s));
           return SR_OK;
         });
       });
@@ -3196,6 +3211,34 @@ int sr_smbr_statistics_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr
   rc = accumulate_items(m, c, n_neg, 0, max_approx, true, den_mean_acc, den_mean_w, den_var_acc, den_var_w);
   c->acc_valid = false;  // (the handle holds one side only: nothing for sr_model_create_from_accumulated)
   return rc;
+}
+}  // extern "C++"
+
+int sr_net_accuracies_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
+                             uint32_t max_items, const uint16_t* ref_states, double* out_cost, double* out_acc, uint16_t* out_count,
+                             uint16_t* out_state, double* out_weight) {
+  return guarded(__func__, [&]() -> int {
+  int rc = smbr_check(m, c, l, p, scale, posterior_floor, ref_states);
+  if (rc) return rc;
+  return smbr_accuracies<SmbrPass>(m, c, p->gmm_kernel, scale, max_items, out_cost, out_acc, out_count, out_state, out_weight,
+                                   launch_smbr_items, [&](SmbrPass& sp, const std::vector<Chunk>& chunks, bool want_items) {
+    return sp.setup(m, c, l, p, scale, posterior_floor, ref_states, want_items, chunks);
+  });
+  });
+}
+
+int sr_smbr_statistics_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
+                              int max_approx, const uint16_t* ref_states, double* out_cost, double* out_acc, double* num_mean_acc,
+                              double* num_mean_w, double* num_var_acc, double* num_var_w, double* den_mean_acc, double* den_mean_w,
+                              double* den_var_acc, double* den_var_w) {
+  return guarded(__func__, [&]() -> int {
+  int rc = smbr_check(m, c, l, p, scale, posterior_floor, ref_states);
+  if (rc) return rc;
+  return smbr_statistics<SmbrPass>(m, c, p->gmm_kernel, scale, max_approx, out_cost, out_acc, num_mean_acc, num_mean_w, num_var_acc, num_var_w,
+                                   den_mean_acc, den_mean_w, den_var_acc, den_var_w, launch_smbr_items,
+                                   [&](SmbrPass& sp, const std::vector<Chunk>& chunks, bool want_items) {
+    return sp.setup(m, c, l, p, scale, posterior_floor, ref_states, want_items, chunks);
+  });
   });
 }
 
@@ -3300,18 +3343,10 @@ static int bgocc_pass(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, d
   if (U == 0) return SR_OK;
   BgChains ch;
   if (chain) build_bgchains(b, U, scale, trans, trans_off, &ch);
-  std::vector<uint64_t> tr_off(U + 1, 0);
-  srplan::MixLists<uint32_t> ml;
-  uint64_t item_bound = 0;
-  if (!chain && want_items) ml.add(b->h_pos_info.data(), P, 0xFFFFu);
-  for (uint32_t u = 0; u < U; u++) {
-    const uint64_t N = chain ? ch.off[u + 1] - ch.off[u] : P, T = c->frame_off[u + 1] - c->frame_off[u];
-    tr_off[u + 1] = tr_off[u] + N * T;
-    if (!want_items) continue;
-    if (chain) ml.add(ch.info.data() + ch.off[u], N, 0xFFFFu);
-    item_bound += T * ml.n_mix(chain ? u : 0);
-  }
-  if (want_items && item_bound >= (1ull << 31)) return fail(SR_ELIMIT, "too many (frame, mixture) occupancies");
+  // the mixture lists only where items are wanted
+  const srplan::OccPlan<uint32_t> pl(c->frame_off.data(), U, chain ? ch.off.data() : nullptr, chain ? ch.info.data() : b->h_pos_info.data(), P,
+                                     want_items);
+  if (want_items && pl.item_bound >= (1ull << 31)) return fail(SR_ELIMIT, "too many (frame, mixture) occupancies");
   std::vector<Chunk> chunks;
   int rc = prepare_chunks(m, c, &chunks);
   if (rc) return rc;
@@ -3320,13 +3355,7 @@ static int bgocc_pass(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, d
   BgFbPass fp;
   fp.want_words = false;
   if (chain) {
-    groups = srplan::launch_groups(chunks, trellis_cost(tr_off).data(), m->fb_budget);
-    HIP_TRY(c->fb_trellis_off.upload(tr_off.data(), U + 1));
-    HIP_TRY(c->fb_trellis.ensure(std::max<uint64_t>(1, groups.max_span(tr_off.data()))));
-    HIP_TRY(c->mmi_chain_off.upload(ch.off.data(), U + 1));
-    HIP_TRY(c->mmi_info.upload(ch.info.data(), ch.info.size()));
-    HIP_TRY(c->mmi_src.upload(ch.src.data(), ch.src.size()));
-    HIP_TRY(c->mmi_dst.upload(ch.dst.data(), ch.dst.size()));
+    if ((rc = trellis_groups(m, c, chunks, pl.tr_off, &groups)) || (rc = upload_chains(c, ch))) return rc;
     HIP_TRY(c->bgmmi_lmc.upload(ch.lmc.data(), ch.lmc.size()));
   } else {
     if ((rc = fp.setup(m, c, b, scale, chunks))) return rc;
@@ -3334,11 +3363,7 @@ static int bgocc_pass(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, d
   size_t scan_bytes = 0;
   if (want_items) {
     const uint64_t max_gf = std::max<uint64_t>(1, (chain ? groups : fp.groups).max_span(c->frame_off.data()));
-    if (chain) HIP_TRY(c->fb_mix_off.upload(ml.mix_off.data(), U + 1));
-    HIP_TRY(c->fb_mix.upload(ml.mix.data(), ml.mix.size()));
-    HIP_TRY(c->fb_slot_beg.upload(ml.slot_beg.data(), ml.slot_beg.size()));
-    HIP_TRY(c->bgmmi_slot_pos.upload(ml.slot_pos.data(), ml.slot_pos.size()));
-    if ((rc = ensure_items(c, max_gf, F, item_bound, &scan_bytes))) return rc;
+    if ((rc = upload_mix_lists(c, pl.ml, chain, c->bgmmi_slot_pos)) || (rc = ensure_items(c, max_gf, F, pl.item_bound, &scan_bytes))) return rc;
   }
   BgChainArgs ca{};
   ca.ld = m->ld; ca.frame_off = c->d_frame_off.p; ca.scale = scale;
@@ -3347,14 +3372,11 @@ static int bgocc_pass(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, d
   ca.sil_len = b->net.silence_states;
   ca.trellis = c->fb_trellis.p; ca.trellis_off = c->fb_trellis_off.p; ca.out_cost = c->out_cost.p;
   BgOccItemArgs ia{};
-  ia.frame_off = c->d_frame_off.p; ia.trellis = c->fb_trellis.p; ia.n_cols = (uint32_t)P; ia.n_mix = chain ? 0u : (uint32_t)ml.mix.size();
-  if (chain) { ia.trellis_off = c->fb_trellis_off.p; ia.chain_off = c->mmi_chain_off.p; ia.mix_off = c->fb_mix_off.p; }
-  ia.mix = c->fb_mix.p; ia.slot_beg = c->fb_slot_beg.p; ia.slot_pos = c->bgmmi_slot_pos.p; ia.gate = gate; ia.floor = posterior_floor;
-  item_fields(&ia, c);
+  occ_item_fields(&ia, c, pl.ml, chain, P, c->bgmmi_slot_pos, gate, posterior_floor);
   auto items = [&](uint32_t u0, uint32_t u1, hipStream_t s) -> int {
     if (!want_items) return SR_OK;
-    ia.utt_first = u0; ia.n_utts = u1 - u0; ia.group_f0 = c->frame_off[u0];
-    HIP_TRY(launch_bgocc_items(ia, c->frame_off[u1] - c->frame_off[u0], c->fb_scan_temp.p, scan_bytes, c->fb_scan.p, s));
+    const uint64_t n = item_group(&ia, c, u0, u1);
+    HIP_TRY(launch_bgocc_items(ia, n, c->fb_scan_temp.p, scan_bytes, c->fb_scan.p, s));
     return SR_OK;
   };
   size_t ci = 0;  // run_chunks searches the chunks in order
@@ -3369,8 +3391,8 @@ static int bgocc_pass(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, d
           });
         }
         for (const Group& g : groups.of_chunk[ci]) {
-          ca.scores = table; ca.frame_base = k.f0; ca.utt_first = g.u0; ca.n_utts = g.u1 - g.u0; ca.max_positions = 1;
-          for (uint32_t u = g.u0; u < g.u1; u++) ca.max_positions = std::max(ca.max_positions, (uint32_t)(ch.off[u + 1] - ch.off[u]));
+          ca.scores = table; ca.frame_base = k.f0; ca.utt_first = g.u0; ca.n_utts = g.u1 - g.u0;
+          ca.max_positions = srplan::max_positions(g, ch.off.data());
           HIP_TRY(launch_bgchain_forward(ca, s));
           HIP_TRY(launch_bgchain_backward(ca, s));
           int r = items(g.u0, g.u1, s);
@@ -3385,7 +3407,7 @@ static int bgocc_pass(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, d
     // per (frame, position): alpha out, alpha in + gamma out (the free network: counted by BgFbPass, whose word-posterior read of gamma
     // is the items' count pass here); the items' write pass reads gamma once more
     m->prof.frames += F;
-    if (chain) m->prof.search_bytes += (want_items ? 40.0 : 24.0) * (double)tr_off[U];
+    if (chain) m->prof.search_bytes += (want_items ? 40.0 : 24.0) * (double)pl.tr_off[U];
     else if (want_items) m->prof.search_bytes += 8.0 * (double)P * (double)F;
   }
   return SR_OK;
@@ -3440,97 +3462,45 @@ static int bgsmbr_check(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, d
   return check_fits(m, bgsmbr_cost(c, b));
 }
 
-// BgFbPass for the accuracy recursions: the same longest-first groups, cut on 16 B per (frame, position) and twice the vectors; the
-// workspace is BgFbPass' buffers at twice the size, the items' mixture lists are bgocc_pass' free ones.  run() enqueues a chunk's
-// groups: per frame the step and the product on both operand vectors, forward then backward, then per_group(item arguments of the
-// group, frames of the group).  `ia` writes to c->fb_item_*.
+// BgStepPass at multiplicity 2 for the accuracy recursions: the groups cut on 16 B per (frame, position) and twice the vectors, the
+// items' mixture lists bgocc_pass' free ones.  run() enqueues a chunk's groups: the recursion on both operand vectors, then
+// per_group(item arguments of the group, frames of the group).  `ia` writes to c->fb_item_*.
 extern "C++" {
-struct BgSmbrPass {
-  srplan::Groups groups;
-  srplan::StepOrder steps;
+struct BgSmbrPass : BgStepPass {
   BgSmbrArgs a{};
   BgOccItemArgs ia{};
-  const double *lk = nullptr, *lkT = nullptr;
-  const uint32_t* d_order = nullptr;
   uint64_t item_bound = 0;
   size_t scan_bytes = 0;
-  size_t ci = 0;  // run_chunks searches the chunks in order
 
   int setup(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, double floor, const uint16_t* ref_states,
             const std::vector<Chunk>& chunks) {
     const uint64_t P = b->net.n_positions, F = c->n_frames;
-    const uint32_t W = b->net.n_words, Kp = bgfb_padded(W), U = c->n_utts;
-    groups = srplan::launch_groups(chunks, bgsmbr_cost(c, b).data(), m->fb_budget);
-    steps = srplan::StepOrder(groups, c->frame_off.data(), U);
-    const uint64_t max_gf = std::max<uint64_t>(1, groups.max_span(c->frame_off.data()));
-    const uint32_t max_gu = std::max(1u, groups.max_utts());
+    const uint32_t U = c->n_utts;
     srplan::MixLists<uint32_t> ml;
     ml.add(b->h_pos_info.data(), P, 0xFFFFu);
     item_bound = F * ml.n_mix(0);  // (bgsmbr_check: below 2^31)
-    int rc = bgfb_tables(m, b, scale);
-    if (rc) return rc;
-    lk = b->fb_lk.p; lkT = b->fb_lkT.p;
-    const size_t rows = (2 * (size_t)max_gu + 63) & ~(size_t)63;  // the product reads whole 16-column tiles of vec
-    HIP_TRY(c->fb_trellis.ensure(max_gf * 2 * P));
-    HIP_TRY(c->out_cost.ensure(U));
+    // what this pass clears and uploads goes ahead of the workspace's synchronisation.  T_u = 0: Abar_u = 0
     HIP_TRY(c->smbr_acc.ensure(U));
+    if (U) HIP_TRY(hipMemset(c->smbr_acc.p, 0, sizeof(double) * U));
     HIP_TRY(c->smbr_ref.upload(ref_states, F));
-    HIP_TRY(c->bgfb_vec.ensure(rows * Kp));
-    HIP_TRY(c->bgfb_prod.ensure(rows * Kp));
-    HIP_TRY(c->bgfb_wend.ensure(rows * Kp));
-    HIP_TRY(c->bgfb_m.ensure(rows));
-    HIP_TRY(c->bgfb_xb.ensure(4 * (size_t)max_gu * P));
-    HIP_TRY(c->bgfb_order.upload(steps.order.data(), steps.order.size()));
-    d_order = c->bgfb_order.p;
-    HIP_TRY(c->fb_mix.upload(ml.mix.data(), ml.mix.size()));
-    HIP_TRY(c->fb_slot_beg.upload(ml.slot_beg.data(), ml.slot_beg.size()));
-    HIP_TRY(c->bgmmi_slot_pos.upload(ml.slot_pos.data(), ml.slot_pos.size()));
+    int rc = upload_mix_lists(c, ml, false, c->bgmmi_slot_pos);
+    if (rc) return rc;
+    if ((rc = workspace(m, c, b, scale, 2, bgsmbr_cost(c, b), chunks, &a.fb))) return rc;
     if ((rc = ensure_items(c, max_gf, F, item_bound, &scan_bytes))) return rc;
-    HIP_TRY(hipMemset(c->bgfb_vec.p, 0, rows * Kp * sizeof(double)));  // (the padding columns h >= W stay 0 from here on)
-    if (U) {  // T_u = 0: F_u = 0 (the start hypothesis is a word end), Abar_u = 0
-      HIP_TRY(hipMemset(c->out_cost.p, 0, sizeof(double) * U));
-      HIP_TRY(hipMemset(c->smbr_acc.p, 0, sizeof(double) * U));
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    BgFbArgs& f = a.fb;
-    f.n_words = W; f.silence = b->net.silence; f.n_positions = (uint32_t)P; f.Kp = Kp;
-    f.slot_off = b->slot_off.p; f.pos_info = b->pos_info.p; f.pos_slot = b->pos_slot.p; f.lmT = b->lmT.p;
-    memcpy(f.tdp, b->net.tdp, sizeof(f.tdp));
-    f.scale = scale; f.ld = m->ld; f.frame_off = c->d_frame_off.p;
-    f.trellis = c->fb_trellis.p; f.vec = c->bgfb_vec.p; f.prod = c->bgfb_prod.p; f.wend = c->bgfb_wend.p; f.m = c->bgfb_m.p; f.xb = c->bgfb_xb.p;
-    f.out_cost = c->out_cost.p;
     a.ref = c->smbr_ref.p; a.out_acc = c->smbr_acc.p;
-    ia.frame_off = c->d_frame_off.p; ia.trellis = c->fb_trellis.p; ia.n_cols = (uint32_t)P; ia.row_stride = (uint32_t)(2 * P);
-    ia.n_mix = ml.n_mix(0); ia.mix = c->fb_mix.p; ia.slot_beg = c->fb_slot_beg.p; ia.slot_pos = c->bgmmi_slot_pos.p; ia.floor = floor;
-    item_fields(&ia, c);
+    occ_item_fields(&ia, c, ml, false, P, c->bgmmi_slot_pos, nullptr, floor);
+    ia.row_stride = (uint32_t)(2 * P);
     // trellis traffic per (frame, position): (alpha, abar) out, the previous row's pair in; both in + gamma out; the items read gamma
     if (m->profiling) m->prof.search_bytes += 64.0 * (double)P * (double)F;
     return SR_OK;
   }
   template <class PerGroup>
   int run(sr_corpus* c, const Chunk& ch, const double* table, hipStream_t s, PerGroup per_group) {
-    BgFbArgs& f = a.fb;
-    for (const Group& g : groups.of_chunk[ci]) {
-      f.scores = table; f.frame_base = ch.f0; f.group_f0 = c->frame_off[g.u0];
-      f.order = d_order + g.u0; f.n_group = g.u1 - g.u0;
-      const uint32_t t_max = steps.t_max(g);
-      for (uint32_t t = 0; t < t_max; t++) {
-        f.t = t; f.n_alive = steps.alive(g, t);
-        HIP_TRY(launch_bgsmbr_forward(a, s));
-        const uint32_t next = steps.alive(g, t + 1);  // only those that go on need their entries
-        HIP_TRY(launch_bgfb_product(lk, f.vec, f.prod, f.Kp, 2 * next, s));
-      }
-      for (uint32_t t = t_max; t-- > 0;) {
-        f.t = t; f.n_alive = steps.alive(g, t);
-        HIP_TRY(launch_bgsmbr_backward(a, s));
-        if (t) HIP_TRY(launch_bgfb_product(lkT, f.vec, f.prod, f.Kp, 2 * f.n_alive, s));
-      }
-      ia.utt_first = g.u0; ia.n_utts = g.u1 - g.u0; ia.group_f0 = c->frame_off[g.u0];
-      int rc = per_group(ia, c->frame_off[g.u1] - c->frame_off[g.u0]);
-      if (rc) return rc;
-    }
-    ci++;
-    return SR_OK;
+    return run_groups(c, ch, table, s, &a.fb, [&] { return launch_bgsmbr_forward(a, s); }, [&] { return launch_bgsmbr_backward(a, s); },
+                      [&](const Group& g) -> int {
+                        const uint64_t n = item_group(&ia, c, g.u0, g.u1);
+                        return per_group(ia, n);
+                      });
   }
 };
 }  // extern "C++"
@@ -3541,26 +3511,10 @@ int sr_bigram_accuracies_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm
   return guarded(__func__, [&]() -> int {
   int rc = bgsmbr_check(m, c, b, scale, posterior_floor, ref_states);
   if (rc) return rc;
-  if (!out_cost || !out_acc) return fail(SR_EINVAL, "null argument");
-  bool post = false;
-  if ((rc = top_items_arguments(out_count, out_state, out_weight, "out_state", max_items, &post))) return rc;
-  const uint64_t F = c->n_frames;
-  std::vector<Chunk> chunks;
-  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
-  BgSmbrPass sp;
-  if ((rc = sp.setup(m, c, b, scale, posterior_floor, ref_states, chunks))) return rc;
-  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, gmm_kernel, table); },
-      [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
-        if (post && sp.ci == 0) HIP_TRY(reset_item_count(c->fb_base, s));
-        return sp.run(c, ch, table, s, [&](const BgOccItemArgs& ia, uint64_t n) -> int {
-          if (post) HIP_TRY(launch_bgocc_signed_items(ia, 0, n, c->fb_scan_temp.p, sp.scan_bytes, c->fb_scan.p, s));
-          return SR_OK;
-        });
-      });
-  if (rc) return rc;
-  if (m->profiling) m->prof.frames += F;
-  if ((rc = smbr_costs(c, scale, out_cost, out_acc))) return rc;
-  return post ? top_of_items(m, c, max_items, launch_smbr_top, out_count, out_state, out_weight) : SR_OK;
+  return smbr_accuracies<BgSmbrPass>(m, c, gmm_kernel, scale, max_items, out_cost, out_acc, out_count, out_state, out_weight,
+                                     launch_bgocc_signed_items, [&](BgSmbrPass& sp, const std::vector<Chunk>& chunks, bool) {
+    return sp.setup(m, c, b, scale, posterior_floor, ref_states, chunks);
+  });
   });
 }
 
@@ -3571,48 +3525,11 @@ int sr_bigram_smbr_statistics_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, in
   return guarded(__func__, [&]() -> int {
   int rc = bgsmbr_check(m, c, b, scale, posterior_floor, ref_states);
   if (rc) return rc;
-  if (!out_cost || !out_acc || !num_mean_acc || !num_mean_w || !num_var_acc || !num_var_w || !den_mean_acc || !den_mean_w ||
-      !den_var_acc || !den_var_w)
-    return fail(SR_EINVAL, "null output");
-  const uint64_t F = c->n_frames;
-  c->acc_valid = false;
-  std::vector<Chunk> chunks;
-  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
-  BgSmbrPass sp;
-  if ((rc = sp.setup(m, c, b, scale, posterior_floor, ref_states, chunks))) return rc;
-  // one pass, the items of both signs: the positive ones in the fb_item_* buffers, the negative ones beside them
-  const uint64_t nb = sp.item_bound;
-  HIP_TRY(c->smbr_base.ensure(1)); HIP_TRY(c->smbr_item_off.ensure(F + 1));
-  HIP_TRY(c->smbr_item_frame.ensure(nb)); HIP_TRY(c->smbr_item_mix.ensure(nb)); HIP_TRY(c->smbr_item_w.ensure(nb));
-  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, gmm_kernel, table); },
-      [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
-        if (sp.ci == 0) {
-          HIP_TRY(reset_item_count(c->fb_base, s));
-          HIP_TRY(reset_item_count(c->smbr_base, s));
-        }
-        return sp.run(c, ch, table, s, [&](const BgOccItemArgs& pos, uint64_t n) -> int {
-          BgOccItemArgs neg = pos;
-          neg.item_base = c->smbr_base.p; neg.item_off = c->smbr_item_off.p;
-          neg.item_frame = c->smbr_item_frame.p; neg.item_mix = c->smbr_item_mix.p; neg.item_w = c->smbr_item_w.p;
-          HIP_TRY(launch_bgocc_signed_items(pos, +1, n, c->fb_scan_temp.p, sp.scan_bytes, c->fb_scan.p, s));
-          HIP_TRY(launch_bgocc_signed_items(neg, -1, n, c->fb_scan_temp.p, sp.scan_bytes, c->fb_scan.p, s));
-          return SR_OK;
-        });
-      });
-  if (rc) return rc;
-  if (m->profiling) m->prof.frames += F;
-  if ((rc = smbr_costs(c, scale, out_cost, out_acc))) return rc;
-  uint64_t n_pos = 0, n_neg = 0;
-  if (c->n_utts && ((rc = read_item_count(c->fb_base, &n_pos)) || (rc = read_item_count(c->smbr_base, &n_neg)))) return rc;
-  if ((rc = accumulate_items(m, c, n_pos, 0, max_approx, true, num_mean_acc, num_mean_w, num_var_acc, num_var_w))) return rc;
-  if (n_neg) {  // the negative side through the same buffers
-    HIP_TRY(hipMemcpy(c->fb_item_frame.p, c->smbr_item_frame.p, sizeof(uint32_t) * n_neg, hipMemcpyDeviceToDevice));
-    HIP_TRY(hipMemcpy(c->fb_item_mix.p, c->smbr_item_mix.p, sizeof(uint16_t) * n_neg, hipMemcpyDeviceToDevice));
-    HIP_TRY(hipMemcpy(c->fb_item_w.p, c->smbr_item_w.p, sizeof(double) * n_neg, hipMemcpyDeviceToDevice));
-  }
-  rc = accumulate_items(m, c, n_neg, 0, max_approx, true, den_mean_acc, den_mean_w, den_var_acc, den_var_w);
-  c->acc_valid = false;  // (the handle holds one side only: nothing for sr_model_create_from_accumulated)
-  return rc;
+  return smbr_statistics<BgSmbrPass>(m, c, gmm_kernel, scale, max_approx, out_cost, out_acc, num_mean_acc, num_mean_w, num_var_acc, num_var_w,
+                                     den_mean_acc, den_mean_w, den_var_acc, den_var_w, launch_bgocc_signed_items,
+                                     [&](BgSmbrPass& sp, const std::vector<Chunk>& chunks, bool) {
+    return sp.setup(m, c, b, scale, posterior_floor, ref_states, chunks);
+  });
   });
 }
 

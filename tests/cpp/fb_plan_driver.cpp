@@ -6,6 +6,11 @@
 //        and per group in corpus order "steps <t_max> alive(0) ... alive(t_max)"
 //   mix <16|32> <masked 0|1> <n_sets>  N ids[N] (per set)
 //     -> "mix_off ...", "mix ...", "slot_beg ...", "slot_pos ..."; masked: 32-bit ids under the mask 0xFFFF, else 16-bit ids
+//   occ <16|32> <chain 0|1> <lists 0|1> <U> <P>  frame_off[U + 1]  chain: chain_off[U + 1] info[chain_off[U]]; else: info[P]
+//     -> "tr_off ...", "bound <item_bound>", the four lines of mix, and "maxpos ..." (max_positions of every single utterance, then of
+//        all of them as one group; over chain_off, or over frame_off for the free network)
+//   seg <n_ranges> <L>  bounds[n_ranges + 1]
+//     -> "begin ...", "len ...", "off ..."
 #include <cstdio>
 #include <fstream>
 #include <string>
@@ -74,6 +79,43 @@ static bool mix_case(std::ifstream& in, bool masked, uint32_t n_sets) {
   return true;
 }
 
+template <class Pos>
+static bool occ_case(std::ifstream& in, bool chain, bool lists, uint32_t U, uint64_t P) {
+  std::vector<uint64_t> frame_off(U + 1), chain_off(chain ? U + 1 : 0);
+  for (auto& v : frame_off) in >> v;
+  for (auto& v : chain_off) in >> v;
+  if (!in) return false;
+  std::vector<uint32_t> info(chain ? chain_off[U] : P);
+  for (auto& v : info) in >> v;
+  if (!in) return false;
+  const srplan::OccPlan<Pos> pl(frame_off.data(), U, chain ? chain_off.data() : nullptr, info.data(), P, lists);
+  line("tr_off", pl.tr_off);
+  printf("bound %llu\n", (unsigned long long)pl.item_bound);
+  line("mix_off", pl.ml.mix_off);
+  line("mix", pl.ml.mix);
+  line("slot_beg", pl.ml.slot_beg);
+  line("slot_pos", pl.ml.slot_pos);
+  const uint64_t* off = chain ? chain_off.data() : frame_off.data();
+  std::vector<uint32_t> maxpos;
+  for (uint32_t u = 0; u < U; u++) maxpos.push_back(srplan::max_positions({u, u + 1}, off));
+  maxpos.push_back(srplan::max_positions({0, U}, off));
+  line("maxpos", maxpos);
+  return true;
+}
+
+static bool seg_case(std::ifstream& in) {
+  uint32_t n = 0, L = 0;
+  in >> n >> L;
+  std::vector<uint32_t> bounds((size_t)n + 1);
+  for (auto& v : bounds) in >> v;
+  if (!in || L == 0) return false;
+  const srplan::Segments seg(bounds.data(), n, L);
+  line("begin", seg.begin);
+  line("len", seg.len);
+  line("off", seg.off);
+  return true;
+}
+
 int main(int argc, char** argv) {
   if (argc != 2) { fprintf(stderr, "usage: %s <cases.txt>\n", argv[0]); return 2; }
   std::ifstream in(argv[1]);
@@ -86,6 +128,13 @@ int main(int argc, char** argv) {
       uint32_t width = 0, masked = 0, n_sets = 0;
       in >> width >> masked >> n_sets;
       ok = width == 16 ? mix_case<uint16_t>(in, masked != 0, n_sets) : mix_case<uint32_t>(in, masked != 0, n_sets);
+    } else if (op == "occ") {
+      uint32_t width = 0, chain = 0, lists = 0, U = 0;
+      uint64_t P = 0;
+      in >> width >> chain >> lists >> U >> P;
+      ok = width == 16 ? occ_case<uint16_t>(in, chain != 0, lists != 0, U, P) : occ_case<uint32_t>(in, chain != 0, lists != 0, U, P);
+    } else if (op == "seg") {
+      ok = seg_case(in);
     }
     if (!ok) { fprintf(stderr, "bad case file\n"); return 2; }
     printf("end\n");

@@ -1,6 +1,7 @@
 """The host planning of the forward-backward passes without a GPU: speechrecognition_amd/csrc/fb_plan.h -- compiled with the host
 compiler alone, under AddressSanitizer and UBSan, into tests/cpp/fb_plan_driver -- against the rules restated here: the launch groups
-of a chunk, the longest-first order with its alive counts, and the mixture lists."""
+of a chunk, the longest-first order with its alive counts, the mixture lists, an occupancy pass' trellis offsets and lists, and the
+segments of the adaptation statistics."""
 import os
 import subprocess
 
@@ -193,6 +194,63 @@ def test_header_mixture_lists(driver, tmp_path):
     toks = [["mix", w, int(m), len(sets)] + [x for s in sets for x in [len(s)] + s] for sets, w, m in cases]
     for (sets, _, masked), a in zip(cases, run_cases(driver, tmp_path, toks)):
         check_mix(sets, masked, a)
+
+
+# ---- an occupancy pass' plan, a group's longest utterance -------------------------------------------------------------------------
+
+def occ_cases():
+    rng = np.random.default_rng(5)
+    ids = [0, 1, 2, 40, 41, 3000, 65535]
+    for k in range(60):
+        U = int(rng.integers(0, 7))
+        lens = rng.choice([0, 1, 4, 7, 20], size=U).tolist()
+        chain, lists, width = bool(k & 1), bool(k & 2) or k % 5 == 0, (16, 32)[(k >> 2) & 1]
+        P = int(rng.integers(0, 12))
+        chains = [rng.choice(ids, size=int(rng.integers(0, 9))).tolist() for _ in range(U)] if chain else None
+        info = [int(i) | int(rng.integers(0, 1 << 15)) << 16 for i in (sum(chains, []) if chain else rng.choice(ids, size=P).tolist())]
+        yield dict(U=U, P=P, lens=lens, chains=chains, info=info, lists=lists, width=width)
+
+
+def test_header_occupancy_plan(driver, tmp_path):
+    cases = list(occ_cases())
+    toks = []
+    for c in cases:
+        frame_off = np.concatenate([[0], np.cumsum(c["lens"])]).astype(np.int64).tolist()
+        chain_off = np.concatenate([[0], np.cumsum([len(x) for x in c["chains"]])]).astype(np.int64).tolist() if c["chains"] is not None else []
+        toks.append(["occ", c["width"], int(c["chains"] is not None), int(c["lists"]), c["U"], c["P"]] + frame_off + chain_off + c["info"])
+    assert any(c["chains"] is not None and c["lists"] and c["U"] > 2 for c in cases) and any(c["chains"] is None and not c["lists"] for c in cases)
+    for c, a in zip(cases, run_cases(driver, tmp_path, toks)):
+        d = dict(a)
+        U, lens, chains = c["U"], c["lens"], c["chains"]
+        n_pos = [len(x) for x in chains] if chains is not None else [c["P"]] * U
+        assert d["tr_off"] == np.concatenate([[0], np.cumsum([n * t for n, t in zip(n_pos, lens)])]).astype(np.int64).tolist()
+        sets = ([[i & 0xFFFF for i in c["info"][sum(n_pos[:u]):sum(n_pos[:u + 1])]] for u in range(U)] if chains is not None
+                else [[i & 0xFFFF for i in c["info"]]]) if c["lists"] else []
+        check_mix(sets, False, a)
+        distinct = [len(set(s)) for s in sets]
+        assert d["bound"] == [sum(t * (distinct[u] if chains is not None else distinct[0]) for u, t in enumerate(lens)) if c["lists"] else 0]
+        per = n_pos if chains is not None else lens          # the driver scans chain_off, or frame_off for the free network
+        assert d["maxpos"] == [max(1, n) for n in per] + [max([1] + per)]
+
+
+# ---- segments ----------------------------------------------------------------------------------------------------------------------
+
+def test_header_segments(driver, tmp_path):
+    rng = np.random.default_rng(9)
+    cases = [([], 4), ([0], 4), ([0, 0, 0], 1), ([4], 4), ([5], 4), ([3, 0, 8, 1], 4), ([128, 129, 127], 128)]
+    cases += [(rng.integers(0, 40, size=int(rng.integers(0, 8))).tolist(), int(rng.choice([1, 3, 16]))) for _ in range(40)]
+    toks = [["seg", len(sizes), L] + np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64).tolist() for sizes, L in cases]
+    for (sizes, L), a in zip(cases, run_cases(driver, tmp_path, toks)):
+        d = dict(a)
+        begin, ln, off = d["begin"], d["len"], d["off"]
+        assert len(off) == len(sizes) + 1 and off[0] == 0 and off[-1] == len(begin) == len(ln)
+        b0 = 0
+        for r, n in enumerate(sizes):
+            mine = list(zip(begin[off[r]:off[r + 1]], ln[off[r]:off[r + 1]]))
+            assert len(mine) == -(-n // L)                                     # no segment for an empty range
+            assert [b for b, _ in mine] == [b0 + k * L for k in range(len(mine))]
+            assert all(x == L for _, x in mine[:-1]) and sum(x for _, x in mine) == n and all(1 <= x <= L for _, x in mine)
+            b0 += n
 
 
 def test_header_has_no_device_include():
