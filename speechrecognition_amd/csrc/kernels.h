@@ -287,28 +287,46 @@ struct FbArgs {
   double* trellis;              // workspace: [T_u][N_u] per utterance at trellis_off[u] - trellis_off[utt_first]; alpha, then gamma
   const uint64_t* trellis_off;  // [n_utts_total+1] prefix sums of T_u * N_u
   double* out_cost;             // [n_utts_total] forward cost F_u
-  // per-frame mixture posteriors -> items (frame, mixture, gamma), in frame order then ascending mixture id
-  const uint32_t* mix_off;      // [n_utts_total+1] range of utterance u in mix[] / slot_beg[]
-  const uint16_t* mix;          // distinct mixtures of each automaton, ascending
-  const uint32_t* slot_beg;     // [sum M_u + 1] positions of mixture j: slot_pos[slot_beg[j] .. slot_beg[j+1])
-  const uint16_t* slot_pos;     // [sum N_u] automaton positions grouped by mixture, ascending within
-  double floor;                 // items: gamma > 0 and gamma >= floor
+};
+hipError_t launch_fb_forward(const FbArgs& a, hipStream_t stream);
+hipError_t launch_fb_backward(const FbArgs& a, hipStream_t stream);
+
+// ---- the items of a training pass (posterior_items.hip) ------------------------------------------------------------------------
+// Items (frame, mixture, weight) from a trellis of per-position weights, in frame order then ascending mixture id: the weight of a
+// mixture is the sum over the positions that carry it.  Either per-utterance trellises [T_u][N_u] with a mixture list each (chains:
+// trellis_off, chain_off and mix_off set), or rows of row_stride doubles per frame of the launch and one list for every utterance.
+struct ItemArgs {
+  const uint64_t* frame_off;    // [n_utts_total+1]
+  uint32_t utt_first, n_utts;
   uint64_t group_f0;            // first frame of the launch
+  const double* trellis;
+  const uint64_t* trellis_off;  // chains: [n_utts_total+1] prefix sums of T_u * N_u, utterance u at trellis_off[u] - trellis_off[utt_first]
+  const uint64_t* chain_off;    // chains: [n_utts_total+1] prefix sums of N_u (FbArgs::aut_off, ChainArgs::chain_off)
+  uint32_t n_cols, n_mix;       // rows: positions, distinct mixtures
+  uint32_t row_stride;          // rows: doubles between the rows (the weights are the first n_cols), frame f at (f - group_f0) * row_stride
+  uint32_t serial_limit;        // 0: a lane sums every mixture alone, in position order; else one of more positions is summed wave-wide
+  const uint32_t* mix_off;      // chains: [n_utts_total+1] range of utterance u in mix[] / slot_beg[]
+  const uint16_t* mix;          // distinct mixtures, ascending
+  const uint32_t* slot_beg;     // positions of mixture j: slot_pos[slot_beg[j] .. slot_beg[j+1])
+  const uint16_t* slot_pos16;   // positions grouped by mixture, ascending within: exactly one of the two widths is set
+  const uint32_t* slot_pos32;
+  const double* gate;           // optional [n_utts_total]: an utterance whose gate is +inf gives no items
+  bool by_frame;                // chains of few mixtures (16-bit, no gate, sign +1): a thread instead of a wave per frame; the same items
+  double floor;                 // items: weight > 0 and >= floor (launch_items' sign)
   uint32_t* group_cnt;          // [frames of the launch] items per frame (count pass)
-  const uint32_t* group_scan;   // [frames of the launch] exclusive prefix sum of group_cnt (write pass)
+  const uint32_t* group_scan;   // [frames of the launch] exclusive prefix sum of group_cnt (write pass; set by launch_items)
   uint32_t* item_base;          // device scalar: items written so far
   uint32_t* item_off;           // [n_frames_total+1] first item of each frame
   uint32_t* item_frame; uint16_t* item_mix; double* item_w;
 };
-hipError_t launch_fb_forward(const FbArgs& a, hipStream_t stream);
-hipError_t launch_fb_backward(const FbArgs& a, hipStream_t stream);
-// items of the launch's frames (count pass, device scan, write pass), appended at *item_base; scan_temp from fb_scan_temp_bytes
-size_t fb_scan_temp_bytes(uint64_t n_frames);
-hipError_t launch_fb_items(const FbArgs& a, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes, uint32_t* scan_out,
-                           hipStream_t stream);
-// per frame the max_items largest items (ties: smaller mixture id first); entries past out_count are zero
-hipError_t launch_fb_top(const uint32_t* item_off, const uint16_t* item_mix, const double* item_w, uint64_t n_frames,
-                         uint32_t max_items, uint16_t* out_count, uint16_t* out_state, double* out_weight, hipStream_t stream);
+// items of the launch's frames (count pass, device scan, write pass), appended at *item_base; scan_temp from items_scan_temp_bytes.
+// sign = +1 / -1: the items with sign * sum > 0 and >= floor, weight sign * sum; 0: sum != 0 and |sum| >= floor, weight sum
+size_t items_scan_temp_bytes(uint64_t n_frames);
+hipError_t launch_items(const ItemArgs& a, int sign, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes, uint32_t* scan_out,
+                        hipStream_t stream);
+// per frame the max_items items of largest |weight| (ties: smaller mixture id first), the weights signed; entries past out_count are zero
+hipError_t launch_items_top(const uint32_t* item_off, const uint16_t* item_mix, const double* item_w, uint64_t n_frames,
+                            uint32_t max_items, uint16_t* out_count, uint16_t* out_state, double* out_weight, hipStream_t stream);
 
 // ---- forward-backward over the recognition network (viterbi_netfb.hip) ------------------------------------------------
 // A launch covers utterances [utt_first, utt_first + n_utts) of one score chunk whose trellises fit the workspace together.
@@ -365,29 +383,6 @@ struct ChainArgs {
 };
 hipError_t launch_chain_forward(const ChainArgs& a, hipStream_t stream);
 hipError_t launch_chain_backward(const ChainArgs& a, hipStream_t stream);
-// Items (frame, mixture, occupancy) from the occupancy parts of either network, in FbArgs' item layout.
-struct OccItemArgs {
-  const uint64_t* frame_off;    // [n_utts_total+1]
-  uint32_t utt_first, n_utts;
-  uint64_t group_f0;            // first frame of the launch
-  const double* trellis;
-  const uint64_t* trellis_off;  // chains: as ChainArgs; null: the free network, rows of n_cols at (frame - group_f0) * n_cols
-  const uint64_t* chain_off;    // chains: as ChainArgs; null
-  uint32_t n_cols, n_mix;       // free network: slots, distinct mixtures of the lexicon (one list for every utterance)
-  const uint32_t* mix_off;      // chains: [n_utts_total+1] range of utterance u in mix[] / slot_beg[]; null
-  const uint16_t* mix;          // distinct mixtures, ascending
-  const uint32_t* slot_beg;     // positions of mixture j: slot_pos[slot_beg[j] .. slot_beg[j+1])
-  const uint16_t* slot_pos;     // positions grouped by mixture, ascending within
-  const double* gate;           // optional [n_utts_total]: an utterance whose gate is +inf gives no items
-  double floor;                 // items: occupancy > 0 and >= floor
-  uint32_t* group_cnt;          // the rest as in FbArgs
-  const uint32_t* group_scan;
-  uint32_t* item_base;
-  uint32_t* item_off;
-  uint32_t* item_frame; uint16_t* item_mix; double* item_w;
-};
-hipError_t launch_occ_items(const OccItemArgs& a, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes, uint32_t* scan_out,
-                            hipStream_t stream);
 // Extended Baum-Welch: numerator and denominator statistics (accumulator rows as EmArgs) + the old tables -> new means, variances and
 // inverse variances per density
 struct EbwArgs {
@@ -421,13 +416,6 @@ struct SmbrArgs {
 size_t smbr_max_slots();
 hipError_t launch_smbr_forward(const SmbrArgs& a, hipStream_t stream);
 hipError_t launch_smbr_backward(const SmbrArgs& a, hipStream_t stream);
-// launch_occ_items over the signed parts of the free network (OccItemArgs without chains and gate; rows of 2 n_cols doubles).
-// sign = +1 / -1: the items with sign * gamma > 0 and >= floor, weight sign * gamma; 0: gamma != 0 and |gamma| >= floor, weight gamma
-hipError_t launch_smbr_items(const OccItemArgs& a, int sign, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes,
-                             uint32_t* scan_out, hipStream_t stream);
-// launch_fb_top ranked on |weight| (ties: smaller mixture id first), the weights signed
-hipError_t launch_smbr_top(const uint32_t* item_off, const uint16_t* item_mix, const double* item_w, uint64_t n_frames,
-                           uint32_t max_items, uint16_t* out_count, uint16_t* out_state, double* out_weight, hipStream_t stream);
 
 // ---- word lattices over the recognition network (viterbi_lattice.hip) --------------------------------------------------
 // A launch covers utterances [utt_first, utt_first + n_utts) of one score chunk whose word-end tables fit the workspace together.
@@ -602,35 +590,6 @@ struct BgChainArgs {
 inline uint32_t bgchain_max_positions() { return 8192; }
 hipError_t launch_bgchain_forward(const BgChainArgs& a, hipStream_t stream);
 hipError_t launch_bgchain_backward(const BgChainArgs& a, hipStream_t stream);
-// Items (frame, mixture, occupancy) from the gamma of either trellis, in FbArgs' item layout: OccItemArgs with 32-bit position lists; a
-// mixture carried by many positions is summed across the lanes of a wave.
-struct BgOccItemArgs {
-  const uint64_t* frame_off;    // [n_utts_total+1]
-  uint32_t utt_first, n_utts;
-  uint64_t group_f0;            // first frame of the launch
-  const double* trellis;
-  const uint64_t* trellis_off;  // chains: as BgChainArgs; null: the free network, rows of n_cols at (frame - group_f0) * n_cols
-  const uint64_t* chain_off;    // chains: as BgChainArgs; null
-  uint32_t n_cols, n_mix;       // free network: positions, distinct mixtures of the net (one list for every utterance)
-  const uint32_t* mix_off;      // chains: [n_utts_total+1] range of utterance u in mix[] / slot_beg[]; null
-  const uint16_t* mix;          // distinct mixtures, ascending
-  const uint32_t* slot_beg;     // positions of mixture j: slot_pos[slot_beg[j] .. slot_beg[j+1])
-  const uint32_t* slot_pos;     // positions grouped by mixture, ascending within
-  const double* gate;           // optional [n_utts_total]: an utterance whose gate is +inf gives no items
-  double floor;                 // items: occupancy > 0 and >= floor
-  uint32_t* group_cnt;          // the rest as in FbArgs
-  const uint32_t* group_scan;
-  uint32_t* item_base;
-  uint32_t* item_off;
-  uint32_t* item_frame; uint16_t* item_mix; double* item_w;
-  uint32_t row_stride;          // launch_bgocc_signed_items only: doubles between the free network's rows (the weights are the first n_cols)
-};
-hipError_t launch_bgocc_items(const BgOccItemArgs& a, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes, uint32_t* scan_out,
-                              hipStream_t stream);
-// launch_bgocc_items over the signed weights of the free network (no chains), the same sums in the same order.  sign = +1 / -1: the
-// items with sign * gamma > 0 and >= floor, weight sign * gamma; 0: gamma != 0 and |gamma| >= floor, weight gamma
-hipError_t launch_bgocc_signed_items(const BgOccItemArgs& a, int sign, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes,
-                                     uint32_t* scan_out, hipStream_t stream);
 
 // ---- sMBR training over the bigram search network (viterbi_bigram_smbr.hip) --------------------------------------------------------
 // BgFbArgs' launch with the expected frame accuracy beside every cost: the trellis has rows [alpha[P], abar[P]] (2 n_positions doubles

@@ -1801,24 +1801,28 @@ static int trellis_groups(sr_model* m, sr_corpus* c, const std::vector<Chunk>& c
 static bool any_null(std::initializer_list<const void*> ps) { return std::find(ps.begin(), ps.end(), nullptr) != ps.end(); }
 
 extern "C++" {
-// The item path (launch_fb_items, launch_occ_items, launch_smbr_items, launch_bgocc_items): a launch group of at most max_gf frames
-// counts, scans and appends its items to the corpus' c->fb_item_* (at most item_bound) behind the counter c->fb_base.
+// The item path (launch_items, posterior_items.hip): a launch group of at most max_gf frames counts, scans and appends its items to
+// the corpus' c->fb_item_* (at most item_bound) behind the counter c->fb_base.
 static int ensure_items(sr_corpus* c, uint64_t max_gf, uint64_t F, uint64_t item_bound, size_t* scan_bytes) {
-  *scan_bytes = fb_scan_temp_bytes(max_gf);
+  *scan_bytes = items_scan_temp_bytes(max_gf);
   HIP_TRY(c->fb_scan_temp.ensure(*scan_bytes));
   HIP_TRY(c->fb_cnt.ensure(max_gf)); HIP_TRY(c->fb_scan.ensure(max_gf)); HIP_TRY(c->fb_base.ensure(1));
   HIP_TRY(c->fb_item_off.ensure(F + 1));
   HIP_TRY(c->fb_item_frame.ensure(item_bound)); HIP_TRY(c->fb_item_mix.ensure(item_bound)); HIP_TRY(c->fb_item_w.ensure(item_bound));
   return SR_OK;
 }
-template <class Args>  // FbArgs, OccItemArgs, BgOccItemArgs (kernels.h)
-static void item_fields(Args* a, sr_corpus* c) {
+// What every pass' ItemArgs share over the uploaded lists (upload_mix_lists; the positions in `slot_pos`); serial_limit as ItemArgs'
+static void set_slot_pos(ItemArgs* a, const uint16_t* p) { a->slot_pos16 = p; }
+static void set_slot_pos(ItemArgs* a, const uint32_t* p) { a->slot_pos32 = p; }
+template <class Pos>
+static void item_fields(ItemArgs* a, sr_corpus* c, const DevBuf<Pos>& slot_pos, uint32_t serial_limit, double floor) {
+  a->frame_off = c->d_frame_off.p; a->trellis = c->fb_trellis.p; a->mix = c->fb_mix.p; a->slot_beg = c->fb_slot_beg.p;
+  set_slot_pos(a, slot_pos.p); a->serial_limit = serial_limit; a->floor = floor;
   a->group_cnt = c->fb_cnt.p; a->item_base = c->fb_base.p; a->item_off = c->fb_item_off.p;
   a->item_frame = c->fb_item_frame.p; a->item_mix = c->fb_item_mix.p; a->item_w = c->fb_item_w.p;
 }
 // a launch group's utterances [u0, u1) in the item arguments; returns its frames
-template <class Args>
-static uint64_t item_group(Args* a, const sr_corpus* c, uint32_t u0, uint32_t u1) {
+static uint64_t item_group(ItemArgs* a, const sr_corpus* c, uint32_t u0, uint32_t u1) {
   a->utt_first = u0; a->n_utts = u1 - u0; a->group_f0 = c->frame_off[u0];
   return c->frame_off[u1] - c->frame_off[u0];
 }
@@ -1832,15 +1836,14 @@ static int upload_mix_lists(sr_corpus* c, const srplan::MixLists<Pos>& ml, bool 
   HIP_TRY(slot_pos.upload(ml.slot_pos.data(), ml.slot_pos.size()));
   return SR_OK;
 }
-// What OccItemArgs and BgOccItemArgs share, over the uploaded lists `ml`: the free network's rows of P positions, or -- chain -- the
+// The item arguments of a network pass over the uploaded lists `ml`: the free network's rows of P positions, or -- chain -- the
 // transcripts' chains (upload_chains, trellis_groups)
-template <class Args, class Pos>
-static void occ_item_fields(Args* a, sr_corpus* c, const srplan::MixLists<Pos>& ml, bool chain, uint64_t P, const DevBuf<Pos>& slot_pos,
-                            const double* gate, double floor) {
-  a->frame_off = c->d_frame_off.p; a->trellis = c->fb_trellis.p; a->n_cols = (uint32_t)P; a->n_mix = chain ? 0u : (uint32_t)ml.mix.size();
+template <class Pos>
+static void occ_item_fields(ItemArgs* a, sr_corpus* c, const srplan::MixLists<Pos>& ml, bool chain, uint64_t P, const DevBuf<Pos>& slot_pos,
+                            uint32_t serial_limit, const double* gate, double floor) {
+  item_fields(a, c, slot_pos, serial_limit, floor);
+  a->n_cols = a->row_stride = (uint32_t)P; a->n_mix = chain ? 0u : (uint32_t)ml.mix.size(); a->gate = gate;
   if (chain) { a->trellis_off = c->fb_trellis_off.p; a->chain_off = c->mmi_chain_off.p; a->mix_off = c->fb_mix_off.p; }
-  a->mix = c->fb_mix.p; a->slot_beg = c->fb_slot_beg.p; a->slot_pos = slot_pos.p; a->gate = gate; a->floor = floor;
-  item_fields(a, c);
 }
 // the transcripts' chains (Chains, BgChains) on the device
 template <class Ch>
@@ -1884,16 +1887,14 @@ static int copy_top_items(uint64_t F, uint32_t max_items, const DevBuf<uint16_t>
   HIP_TRY(hipMemcpy(out_weight, weight.p, sizeof(double) * F * max_items, hipMemcpyDeviceToHost));
   return SR_OK;
 }
-// the top items of the items a pass left in c->fb_item_*, through launch_top (launch_fb_top, launch_smbr_top), to the host
-template <class LaunchTop>
-static int top_of_items(sr_model* m, sr_corpus* c, uint32_t max_items, LaunchTop launch_top, uint16_t* out_count, uint16_t* out_state,
-                        double* out_weight) {
+// the top items of the items a pass left in c->fb_item_* (launch_items_top), to the host
+static int top_of_items(sr_model* m, sr_corpus* c, uint32_t max_items, uint16_t* out_count, uint16_t* out_state, double* out_weight) {
   const uint64_t F = c->n_frames;
   if (F == 0) return SR_OK;
   int rc = ensure_top_items(F, max_items, c->fb_count, c->fb_state, c->fb_weight);
   if (rc) return rc;
-  HIP_TRY(launch_top(c->fb_item_off.p, c->fb_item_mix.p, c->fb_item_w.p, F, max_items, c->fb_count.p, c->fb_state.p, c->fb_weight.p,
-                     m->s_gmm));
+  HIP_TRY(launch_items_top(c->fb_item_off.p, c->fb_item_mix.p, c->fb_item_w.p, F, max_items, c->fb_count.p, c->fb_state.p,
+                           c->fb_weight.p, m->s_gmm));
   HIP_TRY(hipStreamSynchronize(m->s_gmm));
   return copy_top_items(F, max_items, c->fb_count, c->fb_state, c->fb_weight, out_count, out_state, out_weight);
 }
@@ -1954,9 +1955,9 @@ static int fb_pass(sr_model* m, sr_corpus* c, const uint16_t* automata, const ui
   fa.ld = m->ld; fa.frame_off = c->d_frame_off.p; fa.automata = c->automata.p; fa.aut_off = c->aut_off.p;
   fa.tdp_loop = tdp[0]; fa.tdp_forward = tdp[1]; fa.tdp_skip = tdp[2]; fa.silence_state = silence_state;
   fa.trellis = c->fb_trellis.p; fa.trellis_off = c->fb_trellis_off.p; fa.out_cost = c->out_cost.p;
-  fa.mix_off = c->fb_mix_off.p; fa.mix = c->fb_mix.p; fa.slot_beg = c->fb_slot_beg.p; fa.slot_pos = c->fb_slot_pos.p;
-  fa.floor = posterior_floor;
-  item_fields(&fa, c);
+  ItemArgs ia{};  // the automata as chains, every mixture summed in position order
+  item_fields(&ia, c, c->fb_slot_pos, 0, posterior_floor);
+  ia.trellis_off = c->fb_trellis_off.p; ia.chain_off = c->aut_off.p; ia.mix_off = c->fb_mix_off.p; ia.by_frame = true;
   size_t ci = 0;  // run_chunks searches the chunks in order
   rc = run_chunks(m, sc.chunks,
       [&](const Chunk& ch, double* table) -> int { return automaton_scoring_chunk(m, c, sc, ch, table); },
@@ -1964,11 +1965,13 @@ static int fb_pass(sr_model* m, sr_corpus* c, const uint16_t* automata, const ui
         if (want_items && ci == 0) HIP_TRY(reset_item_count(c->fb_base, s));
         for (const Group& g : groups.of_chunk[ci]) {
           fa.scores = table; fa.frame_base = ch.f0; fa.utt_first = g.u0; fa.n_utts = g.u1 - g.u0;
-          fa.max_positions = srplan::max_positions(g, aut_off); fa.group_f0 = c->frame_off[g.u0];
+          fa.max_positions = srplan::max_positions(g, aut_off);
           HIP_TRY(launch_fb_forward(fa, s));
           HIP_TRY(launch_fb_backward(fa, s));
-          if (want_items)
-            HIP_TRY(launch_fb_items(fa, c->frame_off[g.u1] - c->frame_off[g.u0], c->fb_scan_temp.p, scan_bytes, c->fb_scan.p, s));
+          if (want_items) {
+            const uint64_t n = item_group(&ia, c, g.u0, g.u1);
+            HIP_TRY(launch_items(ia, +1, n, c->fb_scan_temp.p, scan_bytes, c->fb_scan.p, s));
+          }
         }
         ci++;
         return SR_OK;
@@ -1994,7 +1997,7 @@ int sr_state_posteriors_corpus(sr_model* m, sr_corpus* c, const uint16_t* automa
   uint64_t n_items = 0;
   if ((rc = fb_pass(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, post, &n_items))) return rc;
   if (U) HIP_TRY(hipMemcpy(out_cost, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToHost));
-  return post ? top_of_items(m, c, max_items, launch_fb_top, out_count, out_state, out_weight) : SR_OK;
+  return post ? top_of_items(m, c, max_items, out_count, out_state, out_weight) : SR_OK;
   });
 }
 
@@ -2894,8 +2897,8 @@ static int occ_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_pa
   ca.tdp_loop = l->net.tdp_loop; ca.tdp_forward = l->net.tdp_forward; ca.tdp_skip = l->net.tdp_skip;
   ca.chain_off = c->mmi_chain_off.p; ca.info = c->mmi_info.p; ca.src = c->mmi_src.p; ca.dst = c->mmi_dst.p; ca.sil_len = ch.sil_len;
   ca.trellis = c->fb_trellis.p; ca.trellis_off = c->fb_trellis_off.p; ca.out_cost = c->out_cost.p;
-  OccItemArgs ia{};
-  occ_item_fields(&ia, c, pl.ml, chain, P, c->fb_slot_pos, gate, posterior_floor);
+  ItemArgs ia{};
+  occ_item_fields(&ia, c, pl.ml, chain, P, c->fb_slot_pos, 0, gate, posterior_floor);
   size_t ci = 0;  // run_chunks searches the chunks in order
   rc = run_chunks(m, chunks, [&](const Chunk& k, double* table) { return score_chunk(m, c, k.f0, k.f1, p->gmm_kernel, table); },
       [&](const Chunk& k, const double* table, hipStream_t s) -> int {
@@ -2913,7 +2916,7 @@ static int occ_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_pa
           }
           if (want_items) {
             const uint64_t n = item_group(&ia, c, g.u0, g.u1);
-            HIP_TRY(launch_occ_items(ia, n, c->fb_scan_temp.p, scan_bytes, c->fb_scan.p, s));
+            HIP_TRY(launch_items(ia, +1, n, c->fb_scan_temp.p, scan_bytes, c->fb_scan.p, s));
           }
         }
         ci++;
@@ -2971,7 +2974,7 @@ int sr_net_occupancies_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr
   uint64_t n_items = 0;
   if ((rc = occ_pass(m, c, l, p, scale, posterior_floor, trans, constrained ? trans_off : nullptr, post, nullptr, &n_items))) return rc;
   if ((rc = netfb_costs(c, scale, out_cost))) return rc;
-  return post ? top_of_items(m, c, max_items, launch_fb_top, out_count, out_state, out_weight) : SR_OK;
+  return post ? top_of_items(m, c, max_items, out_count, out_state, out_weight) : SR_OK;
   });
 }
 
@@ -3092,7 +3095,7 @@ extern "C++" {
 struct SmbrPass {
   srplan::Groups groups;
   SmbrArgs a{};
-  OccItemArgs ia{};  // the free network's mixture lists
+  ItemArgs ia{};  // the free network's mixture lists
   uint64_t item_bound = 0;
   size_t scan_bytes = 0;
   size_t ci = 0;  // run_chunks searches the chunks in order
@@ -3117,7 +3120,8 @@ struct SmbrPass {
     if (want_items && (rc = ensure_items(c, max_gf, F, item_bound, &scan_bytes))) return rc;
     a.net = l->net; a.ld = m->ld; a.frame_off = c->d_frame_off.p; a.scale = scale; a.word_penalty = p->word_penalty;
     a.ref = c->smbr_ref.p; a.trellis = c->fb_trellis.p; a.ends = c->smbr_ends.p; a.out_cost = c->out_cost.p; a.out_acc = c->smbr_acc.p;
-    occ_item_fields(&ia, c, ml, false, P, c->fb_slot_pos, nullptr, floor);
+    occ_item_fields(&ia, c, ml, false, P, c->fb_slot_pos, 0, nullptr, floor);
+    ia.row_stride = (uint32_t)(2 * P);
     // trellis traffic per (frame, position): (alpha, abar) out, both in + the part out, the part in (items)
     if (m->profiling) m->prof.search_bytes += 48.0 * (double)P * (double)F;
     return SR_OK;
@@ -3138,11 +3142,10 @@ struct SmbrPass {
 };
 
 // What the accuracy and sMBR statistics calls of either network do once their check has passed.  Pass is the network's pass (SmbrPass,
-// BgSmbrPass), setup(pass, chunks, want_items) its set-up, launch_items its signed-items launcher (launch_smbr_items,
-// launch_bgocc_signed_items).
-template <class Pass, class LaunchItems, class Setup>
+// BgSmbrPass), setup(pass, chunks, want_items) its set-up.
+template <class Pass, class Setup>
 static int smbr_accuracies(sr_model* m, sr_corpus* c, int gmm_kernel, double scale, uint32_t max_items, double* out_cost, double* out_acc,
-                           uint16_t* out_count, uint16_t* out_state, double* out_weight, LaunchItems launch_items, Setup setup) {
+                           uint16_t* out_count, uint16_t* out_state, double* out_weight, Setup setup) {
   if (!out_cost || !out_acc) return fail(SR_EINVAL, "null argument");
   bool post = false;
   int rc = top_items_arguments(out_count, out_state, out_weight, "out_state", max_items, &post);
@@ -3154,7 +3157,7 @@ static int smbr_accuracies(sr_model* m, sr_corpus* c, int gmm_kernel, double sca
   rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, gmm_kernel, table); },
       [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
         if (post && sp.ci == 0) HIP_TRY(reset_item_count(c->fb_base, s));
-        return sp.run(c, ch, table, s, [&](const auto& ia, uint64_t n) -> int {
+        return sp.run(c, ch, table, s, [&](const ItemArgs& ia, uint64_t n) -> int {
           if (post) HIP_TRY(launch_items(ia, 0, n, c->fb_scan_temp.p, sp.scan_bytes, c->fb_scan.p, s));
           return SR_OK;
         });
@@ -3162,13 +3165,13 @@ static int smbr_accuracies(sr_model* m, sr_corpus* c, int gmm_kernel, double sca
   if (rc) return rc;
   if (m->profiling) m->prof.frames += c->n_frames;
   if ((rc = smbr_costs(c, scale, out_cost, out_acc))) return rc;
-  return post ? top_of_items(m, c, max_items, launch_smbr_top, out_count, out_state, out_weight) : SR_OK;
+  return post ? top_of_items(m, c, max_items, out_count, out_state, out_weight) : SR_OK;
 }
 
-template <class Pass, class LaunchItems, class Setup>
+template <class Pass, class Setup>
 static int smbr_statistics(sr_model* m, sr_corpus* c, int gmm_kernel, double scale, int max_approx, double* out_cost, double* out_acc,
                            double* num_mean_acc, double* num_mean_w, double* num_var_acc, double* num_var_w, double* den_mean_acc,
-                           double* den_mean_w, double* den_var_acc, double* den_var_w, LaunchItems launch_items, Setup setup) {
+                           double* den_mean_w, double* den_var_acc, double* den_var_w, Setup setup) {
   if (any_null({out_cost, out_acc, num_mean_acc, num_mean_w, num_var_acc, num_var_w, den_mean_acc, den_mean_w, den_var_acc, den_var_w}))
     return fail(SR_EINVAL, "null output");
   const uint64_t F = c->n_frames;
@@ -3188,8 +3191,8 @@ static int smbr_statistics(sr_model* m, sr_corpus* c, int gmm_kernel, double sca
           HIP_TRY(reset_item_count(c->fb_base, s));
           HIP_TRY(reset_item_count(c->smbr_base, s));
         }
-        return sp.run(c, ch, table, s, [&](const auto& pos, uint64_t n) -> int {
-          auto neg = pos;
+        return sp.run(c, ch, table, s, [&](const ItemArgs& pos, uint64_t n) -> int {
+          ItemArgs neg = pos;
           neg.item_base = c->smbr_base.p; neg.item_off = c->smbr_item_off.p;
           neg.item_frame = c->smbr_item_frame.p; neg.item_mix = c->smbr_item_mix.p; neg.item_w = c->smbr_item_w.p;
           HIP_TRY(launch_items(pos, +1, n, c->fb_scan_temp.p, sp.scan_bytes, c->fb_scan.p, s));
@@ -3221,7 +3224,7 @@ int sr_net_accuracies_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_
   int rc = smbr_check(m, c, l, p, scale, posterior_floor, ref_states);
   if (rc) return rc;
   return smbr_accuracies<SmbrPass>(m, c, p->gmm_kernel, scale, max_items, out_cost, out_acc, out_count, out_state, out_weight,
-                                   launch_smbr_items, [&](SmbrPass& sp, const std::vector<Chunk>& chunks, bool want_items) {
+                                   [&](SmbrPass& sp, const std::vector<Chunk>& chunks, bool want_items) {
     return sp.setup(m, c, l, p, scale, posterior_floor, ref_states, want_items, chunks);
   });
   });
@@ -3235,7 +3238,7 @@ int sr_smbr_statistics_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr
   int rc = smbr_check(m, c, l, p, scale, posterior_floor, ref_states);
   if (rc) return rc;
   return smbr_statistics<SmbrPass>(m, c, p->gmm_kernel, scale, max_approx, out_cost, out_acc, num_mean_acc, num_mean_w, num_var_acc, num_var_w,
-                                   den_mean_acc, den_mean_w, den_var_acc, den_var_w, launch_smbr_items,
+                                   den_mean_acc, den_mean_w, den_var_acc, den_var_w,
                                    [&](SmbrPass& sp, const std::vector<Chunk>& chunks, bool want_items) {
     return sp.setup(m, c, l, p, scale, posterior_floor, ref_states, want_items, chunks);
   });
@@ -3329,6 +3332,9 @@ static void build_bgchains(const sr_bigram* b, uint32_t U, double scale, const u
   }
 }
 
+// the items of the bigram passes: most positions of a mixture a lane sums alone (a silence mixture has W + 1: summed wave-wide)
+static constexpr uint32_t kBgItemsSerial = 16;
+
 // One occupancy pass over the corpus on the search's scoring chunks: the free network (trans_off null; BgFbPass' launch groups, workspace
 // and table cache) or the transcripts' chains (consecutive utterances whose trellises fit m->fb_budget together).  Leaves kappa F_u in
 // c->out_cost and, with want_items, *n_items items in c->fb_item_* (frame order, ascending mixture id) with c->fb_item_off[F + 1];
@@ -3371,12 +3377,12 @@ static int bgocc_pass(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, d
   ca.chain_off = c->mmi_chain_off.p; ca.info = c->mmi_info.p; ca.src = c->mmi_src.p; ca.dst = c->mmi_dst.p; ca.lmc = c->bgmmi_lmc.p;
   ca.sil_len = b->net.silence_states;
   ca.trellis = c->fb_trellis.p; ca.trellis_off = c->fb_trellis_off.p; ca.out_cost = c->out_cost.p;
-  BgOccItemArgs ia{};
-  occ_item_fields(&ia, c, pl.ml, chain, P, c->bgmmi_slot_pos, gate, posterior_floor);
+  ItemArgs ia{};
+  occ_item_fields(&ia, c, pl.ml, chain, P, c->bgmmi_slot_pos, kBgItemsSerial, gate, posterior_floor);
   auto items = [&](uint32_t u0, uint32_t u1, hipStream_t s) -> int {
     if (!want_items) return SR_OK;
     const uint64_t n = item_group(&ia, c, u0, u1);
-    HIP_TRY(launch_bgocc_items(ia, n, c->fb_scan_temp.p, scan_bytes, c->fb_scan.p, s));
+    HIP_TRY(launch_items(ia, +1, n, c->fb_scan_temp.p, scan_bytes, c->fb_scan.p, s));
     return SR_OK;
   };
   size_t ci = 0;  // run_chunks searches the chunks in order
@@ -3426,7 +3432,7 @@ int sr_bigram_occupancies_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gm
   uint64_t n_items = 0;
   if ((rc = bgocc_pass(m, c, b, gmm_kernel, scale, posterior_floor, trans, constrained ? trans_off : nullptr, post, nullptr, &n_items))) return rc;
   if ((rc = netfb_costs(c, scale, out_cost))) return rc;
-  return post ? top_of_items(m, c, max_items, launch_fb_top, out_count, out_state, out_weight) : SR_OK;
+  return post ? top_of_items(m, c, max_items, out_count, out_state, out_weight) : SR_OK;
   });
 }
 
@@ -3468,7 +3474,7 @@ static int bgsmbr_check(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, d
 extern "C++" {
 struct BgSmbrPass : BgStepPass {
   BgSmbrArgs a{};
-  BgOccItemArgs ia{};
+  ItemArgs ia{};
   uint64_t item_bound = 0;
   size_t scan_bytes = 0;
 
@@ -3488,7 +3494,7 @@ struct BgSmbrPass : BgStepPass {
     if ((rc = workspace(m, c, b, scale, 2, bgsmbr_cost(c, b), chunks, &a.fb))) return rc;
     if ((rc = ensure_items(c, max_gf, F, item_bound, &scan_bytes))) return rc;
     a.ref = c->smbr_ref.p; a.out_acc = c->smbr_acc.p;
-    occ_item_fields(&ia, c, ml, false, P, c->bgmmi_slot_pos, nullptr, floor);
+    occ_item_fields(&ia, c, ml, false, P, c->bgmmi_slot_pos, kBgItemsSerial, nullptr, floor);
     ia.row_stride = (uint32_t)(2 * P);
     // trellis traffic per (frame, position): (alpha, abar) out, the previous row's pair in; both in + gamma out; the items read gamma
     if (m->profiling) m->prof.search_bytes += 64.0 * (double)P * (double)F;
@@ -3512,7 +3518,7 @@ int sr_bigram_accuracies_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm
   int rc = bgsmbr_check(m, c, b, scale, posterior_floor, ref_states);
   if (rc) return rc;
   return smbr_accuracies<BgSmbrPass>(m, c, gmm_kernel, scale, max_items, out_cost, out_acc, out_count, out_state, out_weight,
-                                     launch_bgocc_signed_items, [&](BgSmbrPass& sp, const std::vector<Chunk>& chunks, bool) {
+                                     [&](BgSmbrPass& sp, const std::vector<Chunk>& chunks, bool) {
     return sp.setup(m, c, b, scale, posterior_floor, ref_states, chunks);
   });
   });
@@ -3526,7 +3532,7 @@ int sr_bigram_smbr_statistics_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, in
   int rc = bgsmbr_check(m, c, b, scale, posterior_floor, ref_states);
   if (rc) return rc;
   return smbr_statistics<BgSmbrPass>(m, c, gmm_kernel, scale, max_approx, out_cost, out_acc, num_mean_acc, num_mean_w, num_var_acc, num_var_w,
-                                     den_mean_acc, den_mean_w, den_var_acc, den_var_w, launch_bgocc_signed_items,
+                                     den_mean_acc, den_mean_w, den_var_acc, den_var_w,
                                      [&](BgSmbrPass& sp, const std::vector<Chunk>& chunks, bool) {
     return sp.setup(m, c, b, scale, posterior_floor, ref_states, chunks);
   });

@@ -1,6 +1,6 @@
 // viterbi_bigram_mmi.hip -- the kernels of MMI training over the bigram search network (viterbi_bigram_fb.hip's network, scale kappa,
-// penalties and start): the network restricted to a transcript (numerator), and the mixture-occupancy items of either trellis for the
-// EM accumulation (em_accumulate.hip).  The free network (denominator) is viterbi_bigram_fb.hip's forward-backward unchanged.
+// penalties and start): the network restricted to a transcript (numerator).  The free network (denominator) is
+// viterbi_bigram_fb.hip's forward-backward unchanged.
 //
 // Occupancy.  occ_t(k) = the posterior probability that frame t's emission is mixture k's = dF / d e(t, k).  An entry in this network
 // emits the mixture of the state it moves TO, so a position's gamma counts for its own mixture whole: the occupancy of a mixture is
@@ -14,18 +14,13 @@
 //                            has at most two terms of the previous row (src), a word end at most two segments to enter (dst), and no
 //                            block-wide sum is needed.  Paths end in the word end of w_n or c_n (n = 0: of S).  Everything in log
 //                            space: no product, nothing underflows to "forbidden".
-//   bgocc_items_kernel       one wave per frame, lanes over the mixtures (ascending): items (frame, mixture, occ) with occ > 0 and
-//                            >= floor in launch_fb_items' layout -- count pass, device scan, write pass.  Position lists are 32-bit
-//                            (the free net has up to 2^31 positions).  A lane sums a mixture of few positions alone, in position
-//                            order; a mixture of many (the silence mixtures: W + 1 positions each) is summed by the whole wave, lane l
-//                            its positions l, l + 64, .., then a butterfly over the lanes.  SIGNED (sMBR, viterbi_bigram_smbr.hip's
-//                            signed gamma over the free network): the same sums, kept by sign * gamma or by |gamma|.
+// The items come from the item path (posterior_items.hip) over 32-bit position lists (the free net has up to 2^31 positions), a mixture
+// of more than 16 positions summed across the wave.
 //
 // One workgroup per utterance and two FP64 rows in LDS for the chain, one barrier per frame, gamma written over alpha, no atomics and
 // a fixed summation order: two identical calls return identical bits.  +inf stays +inf, never NaN; a transcript without a path
 // leaves F = +inf and an all-zero trellis.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
 #include "kernels.h"
@@ -169,108 +164,6 @@ hipError_t launch_bgchain_backward(const BgChainArgs& a, hipStream_t stream) {
   hipError_t e = hipFuncSetAttribute((const void*)bgchain_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(bgchain_backward_kernel, dim3(a.n_utts), dim3(bgchain_block(a.max_positions)), smem, stream, a);
-  return hipGetLastError();
-}
-
-// ---- items ------------------------------------------------------------------------------------------------------------------
-static constexpr int kBgOccSplit = 8;          // workgroups (of four waves) per utterance
-static constexpr uint32_t kBgOccSerial = 16;   // most positions a lane sums alone
-
-__device__ inline double shfl_xor_f64(double v, int k) {
-  return __hiloint2double(__shfl_xor(__double2hiint(v), k), __shfl_xor(__double2loint(v), k));
-}
-
-// Workgroup (u, y): its waves take every (4 * kBgOccSplit)-th frame of utterance u; lane l of round r owns the utterance's mixture
-// 64 r + l.  WRITE = false counts the items of each frame, WRITE = true stores them at *item_base + the exclusive scan of the counts,
-// a frame's items in ascending mixture order.  SIGNED: rows of a.row_stride doubles; sign = +1 / -1 keeps sign * sum > 0 and >= floor
-// with that weight, sign = 0 keeps sum != 0 and |sum| >= floor with the signed weight.
-template <bool WRITE, bool SIGNED>
-__global__ __launch_bounds__(256) void bgocc_items_kernel(BgOccItemArgs a, int sign) {
-  const uint32_t u = a.utt_first + blockIdx.x, lane = threadIdx.x & 63;
-  const uint64_t f0 = a.frame_off[u];
-  const int T = (int)(a.frame_off[u + 1] - f0);
-  const uint32_t N = a.chain_off ? (uint32_t)(a.chain_off[u + 1] - a.chain_off[u]) : a.n_cols;
-  const uint32_t ld = SIGNED ? a.row_stride : N;
-  const double* tr = a.trellis + (a.trellis_off ? a.trellis_off[u] - a.trellis_off[a.utt_first] : (f0 - a.group_f0) * ld);
-  const uint32_t j0 = a.mix_off ? a.mix_off[u] : 0u, j1 = a.mix_off ? a.mix_off[u + 1] : a.n_mix;
-  const bool gated = a.gate && !(a.gate[u] < kInf);
-  const double fl = a.floor;
-  const uint32_t base = WRITE ? *a.item_base : 0u;
-  for (int t = blockIdx.y * 4 + (threadIdx.x >> 6); t < T; t += 4 * kBgOccSplit) {
-    const double* g = tr + (size_t)t * ld;
-    const uint64_t gf = f0 + (uint64_t)t - a.group_f0;  // frame within the launch
-    const uint32_t o = WRITE ? base + a.group_scan[gf] : 0u;
-    uint32_t n = 0;
-    for (uint32_t jr = j0; jr < j1 && !gated; jr += 64) {
-      const uint32_t j = jr + lane;
-      const uint32_t b0 = j < j1 ? a.slot_beg[j] : 0u, b1 = j < j1 ? a.slot_beg[j + 1] : 0u;
-      const bool wide = b1 - b0 > kBgOccSerial;
-      double p = 0.0;
-      if (!wide)
-        for (uint32_t i = b0; i < b1; i++) p += g[a.slot_pos[i]];
-      for (uint64_t todo = __ballot(wide); todo; todo &= todo - 1) {  // (wave-uniform) the round's wide mixtures, one after the other
-        const int l = __ffsll((unsigned long long)todo) - 1;
-        const uint32_t w0 = (uint32_t)__shfl((int)b0, l), w1 = (uint32_t)__shfl((int)b1, l);
-        double q = 0.0;
-        for (uint32_t i = w0 + lane; i < w1; i += 64) q += g[a.slot_pos[i]];
-#pragma unroll
-        for (int k = 1; k < 64; k <<= 1) q += shfl_xor_f64(q, k);  // (both partners add the same two values: every lane the same bits)
-        if ((int)lane == l) p = q;
-      }
-      if (SIGNED && sign < 0) p = -p;
-      const double mag = SIGNED && sign == 0 ? fabs(p) : p;
-      const bool keep = j < j1 && mag > 0.0 && mag >= fl;
-      const uint64_t votes = __ballot(keep);
-      if (WRITE && keep) {
-        const uint32_t k = o + n + (uint32_t)__popcll(votes & ((1ull << lane) - 1));
-        a.item_frame[k] = (uint32_t)(f0 + t);
-        a.item_mix[k] = a.mix[j];
-        a.item_w[k] = p;
-      }
-      n += (uint32_t)__popcll(votes);
-    }
-    if (lane == 0) {
-      if (WRITE) a.item_off[f0 + t] = o;
-      else a.group_cnt[gf] = n;
-    }
-  }
-}
-
-// *item_base += the launch's items; item_off[first frame after the launch] = *item_base (as fb_items_advance_kernel)
-__global__ void bgocc_items_advance_kernel(BgOccItemArgs a, uint64_t n_frames) {
-  const uint32_t total = *a.item_base + a.group_scan[n_frames - 1] + a.group_cnt[n_frames - 1];
-  *a.item_base = total;
-  a.item_off[a.group_f0 + n_frames] = total;
-}
-
-hipError_t launch_bgocc_items(const BgOccItemArgs& args, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes, uint32_t* scan_out,
-                              hipStream_t stream) {
-  if (args.n_utts == 0 || n_frames == 0) return hipSuccess;
-  BgOccItemArgs a = args;
-  a.group_scan = scan_out;
-  hipLaunchKernelGGL((bgocc_items_kernel<false, false>), dim3(a.n_utts, kBgOccSplit), dim3(256), 0, stream, a, 0);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  e = hipcub::DeviceScan::ExclusiveSum(scan_temp, scan_temp_bytes, a.group_cnt, scan_out, (int)n_frames, stream);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((bgocc_items_kernel<true, false>), dim3(a.n_utts, kBgOccSplit), dim3(256), 0, stream, a, 0);
-  hipLaunchKernelGGL(bgocc_items_advance_kernel, dim3(1), dim3(1), 0, stream, a, n_frames);
-  return hipGetLastError();
-}
-
-hipError_t launch_bgocc_signed_items(const BgOccItemArgs& args, int sign, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes,
-                                     uint32_t* scan_out, hipStream_t stream) {
-  if (args.n_utts == 0 || n_frames == 0) return hipSuccess;
-  if (args.trellis_off || args.chain_off || args.row_stride < args.n_cols) return hipErrorInvalidValue;
-  BgOccItemArgs a = args;
-  a.group_scan = scan_out;
-  hipLaunchKernelGGL((bgocc_items_kernel<false, true>), dim3(a.n_utts, kBgOccSplit), dim3(256), 0, stream, a, sign);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  e = hipcub::DeviceScan::ExclusiveSum(scan_temp, scan_temp_bytes, a.group_cnt, scan_out, (int)n_frames, stream);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((bgocc_items_kernel<true, true>), dim3(a.n_utts, kBgOccSplit), dim3(256), 0, stream, a, sign);
-  hipLaunchKernelGGL(bgocc_items_advance_kernel, dim3(1), dim3(1), 0, stream, a, n_frames);
   return hipGetLastError();
 }
 

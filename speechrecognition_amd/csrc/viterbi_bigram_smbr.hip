@@ -18,7 +18,7 @@
 //                            it, [state(s) == ref_t] + bbar_t(s); the operands are b[w, u] = exp(m_u - entry cost of w) and b times
 //                            the entry's accuracy, multiplied with the transposed table.  A thread reads row t of the trellis at its
 //                            own position only, so the signed gamma_t(s) goes over alpha_t(s) in the same loop.
-// The items come from bgocc_items_kernel's signed mode (viterbi_bigram_mmi.hip), their ranking from smbr_top_kernel.
+// The items and their ranking come from the item path (posterior_items.hip): the signed sums, wide mixtures across the wave.
 //
 // Per utterance of a group: trellis rows [alpha[P], abar[P]] = 16 B per (frame, position); vec / prod / wend of two rows [Kp] each (the
 // second row is the accuracy side); x of [2][2][P].  No atomics and a fixed summation order: two identical calls return identical bits.

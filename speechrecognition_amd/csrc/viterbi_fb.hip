@@ -4,16 +4,13 @@
 //   fb_forward_kernel    alpha_t(s) = e(t, ref[s]) + logadd_j (alpha_{t-1}(s-j) + tdp(ref[s-j], j)); F_u = alpha_{T-1}(N-1)
 //   fb_backward_kernel   beta_t(s) = logadd_j (tdp(ref[s], j) + e(t+1, ref[s+j]) + beta_{t+1}(s+j)), and in the same frame loop
 //                        gamma_t(s) = exp(F_u - alpha_t(s) - beta_t(s)) over alpha_t(s) in the trellis
-//   fb_items_kernel      per frame the posteriors of the automaton's distinct mixtures (positions of one mixture summed in
-//                        position order), kept when > 0 and >= floor: a count pass, a device scan, a write pass
-//   fb_top_kernel        per frame the largest items in AlignmentItem shape
+// The posteriors of each frame's distinct mixtures, and the largest of them, come from the item path (posterior_items.hip).
 //
 // One workgroup per utterance (one wave when no automaton of the launch has more than 64 positions); positions strided over the
 // threads, the two alpha (beta) rows in LDS, FP64 throughout.  logadd of up to three costs: m - log1p(sum exp(m - x)) over the
 // two that are not the minimum m; +inf (a forbidden jump, an unreachable cell) stays +inf and never turns into NaN.
 // Trellis workspace: 8 B per (frame, position) -- alpha, overwritten in place by gamma -- for the utterances of one launch.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
 #include "kernels.h"
@@ -173,110 +170,6 @@ hipError_t launch_fb_backward(const FbArgs& a, hipStream_t stream) {
   hipError_t e = hipFuncSetAttribute((const void*)fb_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(fb_backward_kernel, dim3(a.n_utts), dim3(fb_block(a.max_positions)), smem, stream, a);
-  return hipGetLastError();
-}
-
-// One workgroup per utterance, one thread per frame: the posterior of each distinct mixture of the automaton (ascending id) is the
-// sum of gamma over its positions, in position order.  WRITE = false counts the items of each frame, WRITE = true stores them at
-// *item_base + the exclusive scan of the counts.
-template <bool WRITE>
-__global__ __launch_bounds__(256) void fb_items_kernel(FbArgs a) {
-  const uint32_t u = a.utt_first + blockIdx.x;
-  const uint64_t f0 = a.frame_off[u];
-  const int T = (int)(a.frame_off[u + 1] - f0);
-  const int N = (int)(a.aut_off[u + 1] - a.aut_off[u]);
-  const double* tr = a.trellis + (a.trellis_off[u] - a.trellis_off[a.utt_first]);
-  const uint32_t j0 = a.mix_off[u], j1 = a.mix_off[u + 1];
-  const double fl = a.floor;
-  const uint32_t base = WRITE ? *a.item_base : 0u;
-  for (int t = threadIdx.x; t < T; t += blockDim.x) {
-    const double* g = tr + (size_t)t * N;
-    const uint64_t gf = f0 + (uint64_t)t - a.group_f0;  // frame within the launch
-    const uint32_t o = WRITE ? base + a.group_scan[gf] : 0u;
-    uint32_t n = 0;
-    for (uint32_t j = j0; j < j1; j++) {
-      double p = 0.0;
-      for (uint32_t i = a.slot_beg[j]; i < a.slot_beg[j + 1]; i++) p += g[a.slot_pos[i]];
-      if (p > 0.0 && p >= fl) {
-        if (WRITE) {
-          a.item_frame[o + n] = (uint32_t)(f0 + t);
-          a.item_mix[o + n] = a.mix[j];
-          a.item_w[o + n] = p;
-        }
-        n++;
-      }
-    }
-    if (WRITE) a.item_off[f0 + t] = o;
-    else a.group_cnt[gf] = n;
-  }
-}
-
-// *item_base += the launch's items; item_off[first frame after the launch] = *item_base (overwritten by the next launch with
-// the same value, the corpus' total after the last one)
-__global__ void fb_items_advance_kernel(FbArgs a, uint64_t n_frames) {
-  const uint32_t total = *a.item_base + a.group_scan[n_frames - 1] + a.group_cnt[n_frames - 1];
-  *a.item_base = total;
-  a.item_off[a.group_f0 + n_frames] = total;
-}
-
-size_t fb_scan_temp_bytes(uint64_t n_frames) {
-  size_t bytes = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n_frames);
-  return bytes;
-}
-
-hipError_t launch_fb_items(const FbArgs& args, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes, uint32_t* scan_out,
-                           hipStream_t stream) {
-  if (args.n_utts == 0 || n_frames == 0) return hipSuccess;
-  FbArgs a = args;
-  a.group_scan = scan_out;
-  hipLaunchKernelGGL((fb_items_kernel<false>), dim3(a.n_utts), dim3(256), 0, stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  e = hipcub::DeviceScan::ExclusiveSum(scan_temp, scan_temp_bytes, a.group_cnt, scan_out, (int)n_frames, stream);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((fb_items_kernel<true>), dim3(a.n_utts), dim3(256), 0, stream, a);
-  hipLaunchKernelGGL(fb_items_advance_kernel, dim3(1), dim3(1), 0, stream, a, n_frames);
-  return hipGetLastError();
-}
-
-// one thread per frame: max_items rounds of "the best item ranked after the previous pick" (gamma descending, then id ascending)
-__global__ __launch_bounds__(256) void fb_top_kernel(const uint32_t* item_off, const uint16_t* item_mix, const double* item_w,
-                                                     uint64_t n_frames, uint32_t K, uint16_t* out_count, uint16_t* out_state,
-                                                     double* out_weight) {
-  const uint64_t f = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (f >= n_frames) return;
-  const uint32_t b = item_off[f], e = item_off[f + 1];
-  double pw = kInf;
-  uint32_t pid = 0;
-  bool first = true;
-  uint32_t r = 0;
-  for (; r < K; r++) {
-    double bw = -1.0;
-    uint32_t bid = 0xFFFFFFFFu;
-    for (uint32_t i = b; i < e; i++) {
-      const double w = item_w[i];
-      const uint32_t id = item_mix[i];
-      if (!first && !(w < pw || (w == pw && id > pid))) continue;  // ranked at or before the previous pick
-      if (w > bw || (w == bw && id < bid)) { bw = w; bid = id; }
-    }
-    if (bid == 0xFFFFFFFFu) break;
-    out_state[f * K + r] = (uint16_t)bid;
-    out_weight[f * K + r] = bw;
-    pw = bw; pid = bid; first = false;
-  }
-  out_count[f] = (uint16_t)r;
-  for (uint32_t q = r; q < K; q++) {
-    out_state[f * K + q] = 0;
-    out_weight[f * K + q] = 0.0;
-  }
-}
-
-hipError_t launch_fb_top(const uint32_t* item_off, const uint16_t* item_mix, const double* item_w, uint64_t n_frames,
-                         uint32_t max_items, uint16_t* out_count, uint16_t* out_state, double* out_weight, hipStream_t stream) {
-  if (n_frames == 0) return hipSuccess;
-  hipLaunchKernelGGL(fb_top_kernel, dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, stream, item_off, item_mix, item_w, n_frames,
-                     max_items, out_count, out_state, out_weight);
   return hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
 // viterbi_mmi.hip -- the kernels of MMI training over the recognition network (viterbi_netfb.hip's network, scale kappa, penalties and
 // start hypothesis): mixture occupancies of the free network (denominator) and of the network restricted to a transcript (numerator),
-// their items for the EM accumulation (em_accumulate.hip), and the extended Baum-Welch update.
+// and the extended Baum-Welch update.  Their items for the EM accumulation come from the item path (posterior_items.hip).
 //
 // Occupancy.  occ_t(k) = the posterior probability that frame t's emission is mixture k's = dF / d e(t, k).  A slot's gamma is that
 // of its own state, except at position 1 of a word: a path that ENTERS there emits the word's first state (the reference's quirk).
@@ -14,14 +14,11 @@
 //                           segment, the silence segment after it and, from a silence segment, that segment again; so the entry sum
 //                           of a segment has at most two terms of the previous row (ChainArgs::src) and no block-wide sum is needed.
 //                           The start hypothesis sits at position 0 of sil_0; paths end in the word end of w_n or sil_n.
-//   occ_items_kernel        one wave per frame, lanes over the mixtures (ascending): items (frame, mixture, occ) with occ > 0 and
-//                           >= floor in launch_fb_items' layout -- count pass, device scan, write pass
 //   ebw_combine_kernel      one thread per (density, dimension): the EBW means and variances from numerator and denominator statistics
 //
 // One workgroup per utterance, two FP64 rows in LDS, the trellis at 8 B per (frame, position) -- alpha, replaced by the occupancy part
 // of the position --, no atomics: two identical calls return identical bits.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
 #include "kernels.h"
@@ -309,72 +306,6 @@ hipError_t launch_chain_backward(const ChainArgs& a, hipStream_t stream) {
   hipError_t e = hipFuncSetAttribute((const void*)chain_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(chain_backward_kernel, dim3(a.n_utts), dim3(chain_block(a.max_positions)), smem, stream, a);
-  return hipGetLastError();
-}
-
-// ---- items ------------------------------------------------------------------------------------------------------------------
-static constexpr int kOccSplit = 8;  // workgroups (of four waves) per utterance
-
-// Workgroup (u, y): its waves take every (4 * kOccSplit)-th frame of utterance u; lane l of round r sums the occupancy parts of the
-// utterance's mixture 64 r + l in position order.  WRITE = false counts the items of each frame, WRITE = true stores them at
-// *item_base + the exclusive scan of the counts, a frame's items in ascending mixture order.
-template <bool WRITE>
-__global__ __launch_bounds__(256) void occ_items_kernel(OccItemArgs a) {
-  const uint32_t u = a.utt_first + blockIdx.x, lane = threadIdx.x & 63;
-  const uint64_t f0 = a.frame_off[u];
-  const int T = (int)(a.frame_off[u + 1] - f0);
-  const uint32_t N = a.chain_off ? (uint32_t)(a.chain_off[u + 1] - a.chain_off[u]) : a.n_cols;
-  const double* tr = a.trellis + (a.trellis_off ? a.trellis_off[u] - a.trellis_off[a.utt_first] : (f0 - a.group_f0) * N);
-  const uint32_t j0 = a.mix_off ? a.mix_off[u] : 0u, j1 = a.mix_off ? a.mix_off[u + 1] : a.n_mix;
-  const bool gated = a.gate && !(a.gate[u] < kInf);
-  const double fl = a.floor;
-  const uint32_t base = WRITE ? *a.item_base : 0u;
-  for (int t = blockIdx.y * 4 + (threadIdx.x >> 6); t < T; t += 4 * kOccSplit) {
-    const double* g = tr + (size_t)t * N;
-    const uint64_t gf = f0 + (uint64_t)t - a.group_f0;  // frame within the launch
-    const uint32_t o = WRITE ? base + a.group_scan[gf] : 0u;
-    uint32_t n = 0;
-    for (uint32_t jr = j0; jr < j1 && !gated; jr += 64) {
-      const uint32_t j = jr + lane;
-      double p = 0.0;
-      if (j < j1)
-        for (uint32_t i = a.slot_beg[j]; i < a.slot_beg[j + 1]; i++) p += g[a.slot_pos[i]];
-      const bool keep = j < j1 && p > 0.0 && p >= fl;
-      const uint64_t votes = __ballot(keep);
-      if (WRITE && keep) {
-        const uint32_t k = o + n + (uint32_t)__popcll(votes & ((1ull << lane) - 1));
-        a.item_frame[k] = (uint32_t)(f0 + t);
-        a.item_mix[k] = a.mix[j];
-        a.item_w[k] = p;
-      }
-      n += (uint32_t)__popcll(votes);
-    }
-    if (lane == 0) {
-      if (WRITE) a.item_off[f0 + t] = o;
-      else a.group_cnt[gf] = n;
-    }
-  }
-}
-
-// *item_base += the launch's items; item_off[first frame after the launch] = *item_base (as fb_items_advance_kernel)
-__global__ void occ_items_advance_kernel(OccItemArgs a, uint64_t n_frames) {
-  const uint32_t total = *a.item_base + a.group_scan[n_frames - 1] + a.group_cnt[n_frames - 1];
-  *a.item_base = total;
-  a.item_off[a.group_f0 + n_frames] = total;
-}
-
-hipError_t launch_occ_items(const OccItemArgs& args, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes, uint32_t* scan_out,
-                            hipStream_t stream) {
-  if (args.n_utts == 0 || n_frames == 0) return hipSuccess;
-  OccItemArgs a = args;
-  a.group_scan = scan_out;
-  hipLaunchKernelGGL((occ_items_kernel<false>), dim3(a.n_utts, kOccSplit), dim3(256), 0, stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  e = hipcub::DeviceScan::ExclusiveSum(scan_temp, scan_temp_bytes, a.group_cnt, scan_out, (int)n_frames, stream);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((occ_items_kernel<true>), dim3(a.n_utts, kOccSplit), dim3(256), 0, stream, a);
-  hipLaunchKernelGGL(occ_items_advance_kernel, dim3(1), dim3(1), 0, stream, a, n_frames);
   return hipGetLastError();
 }
 

@@ -14,15 +14,12 @@
 //                          barrier the occupancy parts where netocc_backward_kernel forms them, each multiplied by (its own c - Abar_u):
 //                          the in-word part of a position 1 from row t - 1 of (alpha, abar), the entry part from E_{t-1}, Ebar_{t-1} and
 //                          added to the word's position 0.  One signed double per slot overwrites alpha_t(s).
-//   smbr_items_kernel      occ_items_kernel's signed sibling over the free network: items (frame, mixture, sign * gamma) with
-//                          sign * gamma > 0 and >= floor, or -- sign 0 -- (frame, mixture, gamma) with gamma != 0 and |gamma| >= floor
-//   smbr_top_kernel        fb_top_kernel ranked on |weight|
+// The items (frame, mixture, sign * gamma) and their ranking on |gamma| come from the item path (posterior_items.hip).
 //
 // One workgroup of 512 threads per utterance, slots strided over the threads, FP64, one barrier per frame, no atomics: two identical
 // calls return identical bits.  LDS: two rows of (cost, accuracy) = 32 B per position + 384 B for the reduction.  Trellis: rows of
 // [alpha[P], abar[P]] = 16 B per (frame, position).
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
 #include "kernels.h"
@@ -218,108 +215,6 @@ hipError_t launch_smbr_backward(const SmbrArgs& a, hipStream_t stream) {
   hipError_t e = hipFuncSetAttribute((const void*)smbr_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(smbr_backward_kernel, dim3(a.n_utts), dim3(kNetFbThreads), smem, stream, a);
-  return hipGetLastError();
-}
-
-// ---- items ------------------------------------------------------------------------------------------------------------------
-static constexpr int kSmbrSplit = 8;  // workgroups (of four waves) per utterance
-
-// occ_items_kernel over the free network's signed parts (rows of 2 n_cols doubles, the parts in the first n_cols).  sign = +1 / -1:
-// the items with sign * gamma > 0 and >= floor, weight sign * gamma; sign = 0: gamma != 0 and |gamma| >= floor, weight gamma.
-template <bool WRITE>
-__global__ __launch_bounds__(256) void smbr_items_kernel(OccItemArgs a, int sign) {
-  const uint32_t u = a.utt_first + blockIdx.x, lane = threadIdx.x & 63;
-  const uint64_t f0 = a.frame_off[u];
-  const int T = (int)(a.frame_off[u + 1] - f0);
-  const uint32_t N = a.n_cols, J = a.n_mix;
-  const double* tr = a.trellis + (f0 - a.group_f0) * 2 * N;
-  const double fl = a.floor;
-  const uint32_t base = WRITE ? *a.item_base : 0u;
-  for (int t = blockIdx.y * 4 + (threadIdx.x >> 6); t < T; t += 4 * kSmbrSplit) {
-    const double* g = tr + (size_t)t * 2 * N;
-    const uint64_t gf = f0 + (uint64_t)t - a.group_f0;  // frame within the launch
-    const uint32_t o = WRITE ? base + a.group_scan[gf] : 0u;
-    uint32_t n = 0;
-    for (uint32_t jr = 0; jr < J; jr += 64) {
-      const uint32_t j = jr + lane;
-      double p = 0.0;
-      if (j < J)
-        for (uint32_t i = a.slot_beg[j]; i < a.slot_beg[j + 1]; i++) p += g[a.slot_pos[i]];
-      const double w = sign < 0 ? -p : p, mag = sign == 0 ? fabs(p) : w;
-      const bool keep = j < J && mag > 0.0 && mag >= fl;
-      const uint64_t votes = __ballot(keep);
-      if (WRITE && keep) {
-        const uint32_t k = o + n + (uint32_t)__popcll(votes & ((1ull << lane) - 1));
-        a.item_frame[k] = (uint32_t)(f0 + t);
-        a.item_mix[k] = a.mix[j];
-        a.item_w[k] = w;
-      }
-      n += (uint32_t)__popcll(votes);
-    }
-    if (lane == 0) {
-      if (WRITE) a.item_off[f0 + t] = o;
-      else a.group_cnt[gf] = n;
-    }
-  }
-}
-
-// *item_base += the launch's items; item_off[first frame after the launch] = *item_base (as occ_items_advance_kernel)
-__global__ void smbr_items_advance_kernel(OccItemArgs a, uint64_t n_frames) {
-  const uint32_t total = *a.item_base + a.group_scan[n_frames - 1] + a.group_cnt[n_frames - 1];
-  *a.item_base = total;
-  a.item_off[a.group_f0 + n_frames] = total;
-}
-
-hipError_t launch_smbr_items(const OccItemArgs& args, int sign, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes,
-                             uint32_t* scan_out, hipStream_t stream) {
-  if (args.n_utts == 0 || n_frames == 0) return hipSuccess;
-  OccItemArgs a = args;
-  a.group_scan = scan_out;
-  hipLaunchKernelGGL((smbr_items_kernel<false>), dim3(a.n_utts, kSmbrSplit), dim3(256), 0, stream, a, sign);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  e = hipcub::DeviceScan::ExclusiveSum(scan_temp, scan_temp_bytes, a.group_cnt, scan_out, (int)n_frames, stream);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((smbr_items_kernel<true>), dim3(a.n_utts, kSmbrSplit), dim3(256), 0, stream, a, sign);
-  hipLaunchKernelGGL(smbr_items_advance_kernel, dim3(1), dim3(1), 0, stream, a, n_frames);
-  return hipGetLastError();
-}
-
-// one thread per frame: max_items rounds of "the best item ranked after the previous pick" (|weight| descending, then id ascending)
-__global__ __launch_bounds__(256) void smbr_top_kernel(const uint32_t* item_off, const uint16_t* item_mix, const double* item_w,
-                                                       uint64_t n_frames, uint32_t K, uint16_t* out_count, uint16_t* out_state,
-                                                       double* out_weight) {
-  const uint64_t f = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (f >= n_frames) return;
-  const uint32_t b = item_off[f], e = item_off[f + 1];
-  double pw = kInf;
-  uint32_t pid = 0, r = 0;
-  for (; r < K; r++) {
-    double bw = -1.0, bs = 0.0;
-    uint32_t bid = 0xFFFFFFFFu;
-    for (uint32_t i = b; i < e; i++) {
-      const double s = item_w[i], w = fabs(s);
-      const uint32_t id = item_mix[i];
-      if (r > 0 && !(w < pw || (w == pw && id > pid))) continue;  // ranked at or before the previous pick
-      if (w > bw || (w == bw && id < bid)) { bw = w; bs = s; bid = id; }
-    }
-    if (bid == 0xFFFFFFFFu) break;
-    out_state[f * K + r] = (uint16_t)bid;
-    out_weight[f * K + r] = bs;
-    pw = bw; pid = bid;
-  }
-  out_count[f] = (uint16_t)r;
-  for (uint32_t q = r; q < K; q++) {
-    out_state[f * K + q] = 0;
-    out_weight[f * K + q] = 0.0;
-  }
-}
-
-hipError_t launch_smbr_top(const uint32_t* item_off, const uint16_t* item_mix, const double* item_w, uint64_t n_frames,
-                           uint32_t max_items, uint16_t* out_count, uint16_t* out_state, double* out_weight, hipStream_t stream) {
-  if (n_frames == 0) return hipSuccess;
-  hipLaunchKernelGGL(smbr_top_kernel, dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, stream, item_off, item_mix, item_w,
-                     n_frames, max_items, out_count, out_state, out_weight);
   return hipGetLastError();
 }
 

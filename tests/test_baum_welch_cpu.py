@@ -15,8 +15,10 @@ from tests.util import Case, golden_names
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = ("sr_state_posteriors_corpus", "sr_baum_welch_corpus")
-FB_KERNELS = ("fb_forward_kernel", "fb_backward_kernel", "fb_items_kernel<false>", "fb_items_kernel<true>", "fb_items_advance_kernel",
-              "fb_top_kernel")
+FB_KERNELS = ("fb_forward_kernel", "fb_backward_kernel")
+ITEM_KERNELS = ("items_kernel<false, unsigned short>", "items_kernel<true, unsigned short>", "items_kernel<false, unsigned int>",
+                "items_kernel<true, unsigned int>", "items_by_frame_kernel<false>", "items_by_frame_kernel<true>", "items_advance_kernel",
+                "items_top_kernel")
 EM_KERNELS = ("em_item_pairs_kernel", "em_assign_weighted_kernel", "em_iota_kernel")
 
 
@@ -94,7 +96,7 @@ def test_new_kernels_have_no_scratch(built_lib):
     if not os.path.exists(os.path.join(isa_info.LLVM, "llvm-objdump")):
         pytest.skip("no ROCm LLVM tools")
     with tempfile.TemporaryDirectory() as tmp:
-        for obj, names in (("viterbi_fb", FB_KERNELS), ("em_accumulate", EM_KERNELS)):
+        for obj, names in (("viterbi_fb", FB_KERNELS), ("posterior_items", ITEM_KERNELS), ("em_accumulate", EM_KERNELS)):
             md = isa_info.kernel_metadata(isa_info.code_object(obj, tmp))
             for k in names:
                 assert k in md, (obj, k, sorted(md))

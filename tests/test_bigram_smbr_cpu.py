@@ -203,7 +203,8 @@ def test_header_declares_the_entry_points():
 
 def test_kernels_have_no_scratch():
     """the gfx950 code objects of viterbi_bigram_smbr.hip: no private segment and no vector spills in its two step kernels (scalar
-    spills go to VGPR lanes), within the 128 VGPRs their 512 threads assume; the signed item kernels likewise"""
+    spills go to VGPR lanes), within the 128 VGPRs their 512 threads assume; the kernels of the item path
+    (posterior_items.hip) likewise"""
     import sys
     import tempfile
     sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -214,11 +215,12 @@ def test_kernels_have_no_scratch():
     build.build()
     with tempfile.TemporaryDirectory() as tmp:
         md = isa_info.kernel_metadata(isa_info.code_object("viterbi_bigram_smbr", tmp))
-        items = isa_info.kernel_metadata(isa_info.code_object("viterbi_bigram_mmi", tmp))
+        items = isa_info.kernel_metadata(isa_info.code_object("posterior_items", tmp))
     mine = {k: v for k, v in md.items() if k.startswith("bgsmbr_")}
     assert set(mine) == {"bgsmbr_forward_kernel", "bgsmbr_backward_kernel"}
-    mine.update({k: v for k, v in items.items() if k.startswith("bgocc_items_kernel<")})
-    assert {"bgocc_items_kernel<false, true>", "bgocc_items_kernel<true, true>"} <= set(mine)
+    mine.update({k: v for k, v in items.items() if k.startswith("items_")})
+    assert {"items_kernel<false, unsigned short>", "items_kernel<true, unsigned short>", "items_kernel<false, unsigned int>",
+            "items_kernel<true, unsigned int>", "items_advance_kernel", "items_top_kernel"} <= set(mine)
     for k, v in mine.items():
         print(k, v)
         assert v["private_segment_fixed_size"] == 0 and v["vgpr_spill_count"] == 0 and v["vgpr_count"] <= 128, (k, v)

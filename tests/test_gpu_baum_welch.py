@@ -195,6 +195,44 @@ def test_posterior_order_floor_and_truncation(tmp_path, oracle_lib):
         assert [int(x) for x in s] == [p[1] for p in want]
 
 
+def _many_mixtures_case(seed):
+    """(automata, frame offsets, features): a random order of 100 distinct mixtures over 60 frames, utterances of one and of three
+    frames, and 20 positions drawn from 5 mixtures (several positions to a mixture) over 37 frames"""
+    rng = np.random.default_rng(seed)
+    auts = [rng.permutation(100).astype(np.uint16), np.asarray([7], np.uint16), np.asarray([3, 90], np.uint16),
+            rng.choice(rng.permutation(100)[:5], size=20).astype(np.uint16)]
+    off = np.concatenate([[0], np.cumsum([60, 1, 3, 37])]).astype(np.uint64)
+    feats = rng.standard_normal((int(off[-1]), 13)).astype(np.float32)
+    return auts, off, feats
+
+
+def test_posteriors_of_many_mixtures_and_short_utterances(tmp_path, oracle_lib):
+    """Baum-Welch's items (a thread per frame sums every mixture of its automaton) on an automaton of 100 distinct mixtures -- every
+    other test here has at most 40 -- beside very short utterances: items at floor 0 and above a floor with truncation, and the same
+    bytes from a second call."""
+    spec, mp, lex = _synthetic(tmp_path, 101, S=100)
+    auts, off, feats = _many_mixtures_case(102)
+    o = oracle_lib.Oracle(mp, 13, lex)
+    # not vacuous: the reference alone puts mixtures of sorted rank >= 64 (here: id >= 64) into the items of many frames
+    _, g = R.posteriors(o.score_matrix(feats[:60]), auts[0], TDP, 0)
+    mix, gm = R.mixture_posteriors(g, auts[0])
+    high_rank = sum(any(k >= 64 for k, _ in it) for it in R.items(mix, gm, 0.0))
+    print("frames with a mixture of rank >= 64:", high_rank)
+    assert len(mix) == 100 and high_rank >= 10
+    with capi.Model.from_mixset(mp, 13) as m:
+        corpus = m.upload(feats, off)
+        full = corpus.state_posteriors(auts, TDP, 0, capi.GMM_DEFAULT, 0.0, 128)
+        cut = corpus.state_posteriors(auts, TDP, 0, capi.GMM_DEFAULT, 1e-4, 4)
+        again = [corpus.state_posteriors(auts, TDP, 0, capi.GMM_DEFAULT, 0.0, 128), corpus.state_posteriors(auts, TDP, 0, capi.GMM_DEFAULT, 1e-4, 4)]
+        corpus.close()
+    _check_utterances(o, feats, off, auts, TDP, 0, *full)
+    _check_utterances(o, feats, off, auts, TDP, 0, *cut, items_floor=1e-4, max_items=4)
+    o.close()
+    for first, second in zip((full, cut), again):
+        for a, b in zip(first, second):
+            assert a.tobytes() == b.tobytes()
+
+
 def _single_path_case(tmp_path, seed, tie_vars=False):
     spec, mp, lex = _synthetic(tmp_path, seed, tie_vars=tie_vars)
     rng = np.random.default_rng(seed + 1)

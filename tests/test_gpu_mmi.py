@@ -116,6 +116,29 @@ def _against_restatement(o, m, lex, feats, off, trans, tdp, wp, scale, floors=(0
     return refs
 
 
+def _long_chain_case():
+    """(lexicon, transcripts, frame counts): 24 words of three fresh states each; the first transcript names them all"""
+    return _lex([1] + [3] * 24, 0), [list(range(1, 25)), [2, 1]], [90, 12]
+
+
+def test_chain_of_more_than_64_mixtures(tmp_path, oracle_lib):
+    """a transcript whose chain carries 73 distinct mixtures: in chain mode the item kernel's lanes take them in two rounds of 64.  The
+    reference alone says that mixtures of sorted rank >= 64 within the chain hold occupancy in at least 10 frames."""
+    lex, trans, lens = _long_chain_case()
+    spec, mp = _model(tmp_path, lex.n_states, 760)
+    feats = synth.make_features(sum(lens), DIM, seed=761)
+    o = oracle_lib.Oracle(mp, DIM, lex, tdp=TDP)
+    with capi.Model.from_mixset(mp, DIM) as m:
+        refs = _against_restatement(o, m, lex, feats, _off(lens), trans, TDP, 10.0, 0.3, floors=(0.0, 1e-6), stats=False)
+    o.close()
+    F, occ = refs[0][0]
+    chain_mix = np.unique(M.chain_graph(_net(lex), trans[0]).state)
+    assert np.isfinite(F) and len(chain_mix) == 73
+    late = sum(bool((occ[t, chain_mix[64:]] > 0).any()) for t in range(lens[0]))
+    print("frames with occupancy on a mixture of rank >= 64:", late)
+    assert late >= 10
+
+
 @pytest.mark.parametrize("li", range(len(LEXICA)))
 def test_against_restatement(li, tmp_path, oracle_lib):
     """ragged lexica with a one- and a multi-position silence; a T = 1 utterance, an empty transcript, a transcript too long for

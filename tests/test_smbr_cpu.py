@@ -181,8 +181,9 @@ def test_one_ebw_step_raises_the_expected_accuracy(tmp_path, oracle_lib):
 
 
 def test_kernels_have_no_scratch():
-    """the gfx950 code objects of viterbi_smbr.hip: no private segment and no vector spills in any of its kernels (the scalar spills
-    of the two recursions go to VGPR lanes), and the recursions stay within the 128 VGPRs their 512 threads assume"""
+    """the gfx950 code objects of viterbi_smbr.hip and of the item path (posterior_items.hip): no private segment and no vector spills
+    in any of their kernels (the scalar spills of the two recursions go to VGPR lanes), and the recursions stay within the
+    128 VGPRs their 512 threads assume"""
     import os
     import sys
     import tempfile
@@ -195,8 +196,10 @@ def test_kernels_have_no_scratch():
     build.build()
     with tempfile.TemporaryDirectory() as tmp:
         md = isa_info.kernel_metadata(isa_info.code_object("viterbi_smbr", tmp))
-    mine = {k: v for k, v in md.items() if k.startswith("smbr_")}
-    assert {"smbr_forward_kernel", "smbr_backward_kernel", "smbr_top_kernel"} <= set(mine)
+        md.update(isa_info.kernel_metadata(isa_info.code_object("posterior_items", tmp)))
+    mine = {k: v for k, v in md.items() if k.startswith(("smbr_", "items_"))}
+    assert {"smbr_forward_kernel", "smbr_backward_kernel", "items_kernel<false, unsigned short>", "items_kernel<true, unsigned short>",
+            "items_advance_kernel", "items_top_kernel"} <= set(mine)
     for k, v in mine.items():
         assert v.get("private_segment_fixed_size", 0) == 0 and v.get("vgpr_spill_count", 0) == 0, (k, v)
         assert v.get("vgpr_count", 0) <= 128, (k, v)

@@ -20,7 +20,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 
 TDP = (3.0, 0.0, 30.0)
-FB_KERNELS = ("fb_", "em_item_pairs", "em_assign_weighted", "em_iota")
+FB_KERNELS = ("fb_", "items_", "em_item_pairs", "em_assign_weighted", "em_iota")
 
 
 def setup():
