@@ -1256,6 +1256,80 @@ class MeanAdaptation {
   double min_count_;
 };
 
+// ---- MLLT, the global semi-tied covariance transform (srgpu.h: sr_mllt_*) --------------------------------------------------------
+// One square matrix A for the whole feature space, estimated by maximum likelihood from the trainer's re-alignment so that the model's
+// diagonal covariances fit as well as they can; features and means both move (y = A x, mu' = A mu).  The variances are re-estimated
+// by the next training pass over the adapted corpus with the adapted model.
+class Mllt {
+ public:
+  struct Result {
+    std::vector<double> A;            // [D x D] row-major
+    std::vector<double> affine;       // [D x (D+1)] = [A 0]: the W of sr_corpus_transform and sr_model_transform_means
+    double logdet = 0.0;              // log|det A|
+    double beta = 0.0;                // frames (occupancy) behind the estimate
+    int32_t status = 0;               // sr_mllt_estimate's: 0 estimated, 1 too little data (identity), 2 failed (identity)
+    std::vector<double> aux;          // [n_sweeps + 1] the auxiliary function after 0 .. n_sweeps sweeps
+    std::vector<float> features;      // the adapted corpus features, the corpus' layout: what is uploaded to `model`
+    // the adapted corpus, resident (sr_corpus_transform), and the adapted model (sr_model_transform_means).  Destroyed with the last
+    // copy of the Result; `adapted` belongs to the base model and must not outlive it.
+    std::shared_ptr<sr_corpus> adapted;
+    std::shared_ptr<sr_model> model;
+  };
+
+  Mllt(Trainer& trainer, MixtureModel& mixtures, uint32_t n_sweeps = 10, double min_count = 100.0)
+      : trainer_(trainer), mixtures_(mixtures), n_sweeps_(n_sweeps), min_count_(min_count) {}
+
+  // the estimate alone, from statistics, starting at the identity (host code, no device)
+  static void estimate(size_t dim, double beta, std::vector<double> const& G, uint32_t n_sweeps, double min_count, Result& r) {
+    r.beta = beta;
+    r.A.assign(dim * dim, 0.0);
+    for (size_t i = 0; i < dim; i++) r.A[i * dim + i] = 1.0;
+    r.aux.assign((size_t)n_sweeps + 1, 0.0);
+    check(sr_mllt_estimate((uint32_t)dim, beta, G.data(), n_sweeps, min_count, r.A.data(), r.aux.data(), &r.logdet, &r.status));
+    r.affine.assign(dim * (dim + 1), 0.0);
+    for (size_t i = 0; i < dim; i++) std::copy(r.A.begin() + i * dim, r.A.begin() + (i + 1) * dim, r.affine.begin() + i * (dim + 1));
+  }
+
+  // re-align, take the statistics of the alignment, estimate, transform the corpus and the means
+  Result adapt(Corpus const& corpus) {
+    const size_t n = corpus.get_corpus_size(), D = mixtures_.dimension;
+    const uint64_t F = corpus.get_total_frame_count();
+    std::vector<AlignmentItem> alignment;
+    trainer_.realign(corpus, alignment);
+    std::vector<uint16_t> states(std::max<uint64_t>(F, 1));
+    for (uint64_t t = 0; t < F; t++) states[t] = (uint16_t)alignment[t].state;
+    double beta = 0.0;
+    std::vector<double> G(D * D * D);
+    sr_corpus* c = nullptr;
+    check(sr_corpus_upload(mixtures_.handle(), corpus.features(), corpus.frame_offsets(), (uint32_t)n, &c));
+    std::shared_ptr<sr_corpus> original(c, sr_corpus_destroy);
+    check(sr_mllt_statistics_corpus(mixtures_.handle(), c, states.data(), mixtures_.max_approx() ? 1 : 0, &beta, G.data()));
+    Result r;
+    estimate(D, beta, G, n_sweeps_, min_count_, r);
+    const std::vector<uint32_t> one_speaker(std::max<size_t>(n, 1), 0);
+    sr_corpus* adapted = nullptr;
+    check(sr_corpus_transform(mixtures_.handle(), c, one_speaker.data(), 1, r.affine.data(), &adapted));
+    r.adapted.reset(adapted, sr_corpus_destroy);
+    r.features.resize((size_t)F * D);
+    for (uint64_t t = 0; t < F; t++)
+      SpeakerAdaptation::transform_row(r.affine.data(), D, corpus.features() + t * D, r.features.data() + t * D);
+    uint32_t dim = 0, n_states = 0;
+    uint64_t n_dens = 0;
+    check(sr_model_info(mixtures_.handle(), &dim, &n_states, &n_dens));
+    const std::vector<uint32_t> one_class(std::max<uint64_t>(n_dens, 1), 0);
+    sr_model* model = nullptr;
+    check(sr_model_transform_means(mixtures_.handle(), one_class.data(), 1, r.affine.data(), &model));
+    r.model.reset(model, sr_model_destroy);
+    return r;
+  }
+
+ private:
+  Trainer& trainer_;
+  MixtureModel& mixtures_;
+  uint32_t n_sweeps_;
+  double min_count_;
+};
+
 // ---- Teaching::LinearSearch (rwth-asr-0.5/src/Teaching/LinearSearch.hh:9-62, SearchInterface.hh:20-30) -------------
 // Bigram-LM beam search over a linear lexicon, one device pass per corpus.  The toolkit wires lexicon, language model
 // and transition model through Speech::ModelCombination (LinearSearch.cc:462-475); here they are plain arrays:

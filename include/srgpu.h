@@ -462,6 +462,48 @@ SR_API int sr_mllr_estimate(uint32_t dim, uint32_t n_speakers, uint32_t n_classe
  * in different classes; SR_ELIMIT for a dimension above 63. */
 SR_API int sr_model_transform_means(sr_model* m, const uint32_t* dens_class, uint32_t n_classes, const double* W, sr_model** out);
 
+/* ---- MLLT: the global semi-tied covariance transform (Gales 1999, one transform class) --------------------------------------------
+ * One square matrix A for the feature space, y = A x with the means following by mu' = A mu, chosen so that the model's diagonal
+ * covariances fit as well as they can: the "MLLT" of the LDA + MLLT + fMLLR pipeline.  With z = (double) x_t - mu_d and iv = 1/var of
+ * density d, the pairs (t, d, gamma) -- exactly those of the fMLLR statistics above, from an alignment or from a Baum-Welch pass --
+ * collect, everything in FP64,
+ *   beta       = sum gamma
+ *   G[i][j][k] = sum (gamma iv_di) z_j z_k                    i, j, k < D      (out_G[D x D x D], full storage)
+ * z is formed with one rounding, z_j z_k with one more, the product with gamma iv_di inside the matrix instruction.
+ * Summation order: the pairs in pair order (frames ascending, a frame's densities in mixture order; a dropped pair -- membership below
+ * 1e-8, empty mixture -- keeps its place with weight 0) are cut into segments of 1024; within a segment one chain of
+ * v_mfma_f64_16x16x4_f64 accumulations per output, pairs ascending; then the segments' partial sums, ascending.  No atomics: two
+ * identical calls return identical bits, and G is exactly symmetric in (j, k) (both triangles are written from one sum).
+ * Limits: D <= 63 (SR_ELIMIT).  Memory: the partial sums of a segment are R x C doubles, R = D + 1 rounded up to 16,
+ * C = D (D + 1) / 2 + 1 rounded up to 16 (0.3 MB at D = 39, i.e. 300 MB per million pairs); they live in a workspace of SRGPU_MLLT_MB
+ * MiB (default 256, read when the model is made), and when the segments do not fit, the call runs in rounds of consecutive segments
+ * whose reduction continues the same chain of additions: the result's bits do not depend on the workspace.  One segment that does not
+ * fit: SR_ELIMIT (none does at D <= 63: at most 64 x 2032 doubles, below 1 MiB).  SR_EINVAL for a NULL output; otherwise the
+ * errors of sr_accumulate_corpus / sr_baum_welch_corpus.  All errors are found before any launch and leave the outputs untouched.
+ * Statistics of corpus shards add up; a corpus without live pairs gives zeros.
+ *
+ * Applying it needs no call of its own: with W = [A 0] (D x (D+1)), the adapted corpus is sr_corpus_transform with one speaker
+ * (utt_speaker all 0), the adapted means are sr_model_transform_means with one class (dens_class all 0); upload or transform the
+ * features for the adapted model, and let the next sr_accumulate_corpus / sr_baum_welch_corpus pass re-estimate the variances in the
+ * new basis.  Costs of the adapted pair compare with the original's after subtracting log|det A| per frame. */
+SR_API int sr_mllt_statistics_corpus(sr_model* m, sr_corpus* c, const uint16_t* states, int max_approx, double* out_beta /*[1]*/,
+                                     double* out_G /*[D*D*D]*/);
+/* out_cost[n_utts] as sr_baum_welch_corpus */
+SR_API int sr_mllt_statistics_bw_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off,
+                                        const double tdp[3], uint16_t silence_state, int gmm_kernel, double posterior_floor,
+                                        int max_approx, double* out_cost /*[n_utts]*/, double* out_beta, double* out_G);
+
+/* The estimate (host code, no device).  Q(A) = beta log|det A| - 1/2 sum_i a_i G_i a_i^T.  A sweep updates rows i = 0 .. D-1 in
+ * order: a_i = alpha p_i G_i^-1 with p_i row i of the cofactor matrix of the current A and alpha = +sqrt(beta / (p_i G_i^-1 p_i^T)).
+ * Every row update maximises Q over its row, so Q never falls; both roots give the same Q, and the positive one makes det A > 0
+ * after every update, which makes the result unique.  A[D x D] holds the start (usually I) and receives the result.
+ * out_aux[n_sweeps + 1] (optional): Q after j sweeps (j = 0: the A given).  out_logdet (optional): log|det A| of the result.
+ * *out_status: 0 estimated; 1 beta < min_count, A left as given; 2 some G_i not positive definite or A singular on the way, A restored
+ * bit for bit.  With status 1 or 2 out_aux holds Q of the A given at every j (NaN where it has none).
+ * SR_EINVAL for dim == 0, a NULL G, A or out_status, min_count negative or NaN, n_sweeps == 0. */
+SR_API int sr_mllt_estimate(uint32_t dim, double beta, const double* G, uint32_t n_sweeps, double min_count, double* A /*[D*D] in/out*/,
+                            double* out_aux /*[n_sweeps+1], optional*/, double* out_logdet /*optional*/, int32_t* out_status);
+
 /* ---- word posteriors and confidences: forward-backward over the recognition network --------------------------------
  * The network sr_recognize_corpus searches (Recognizer.cpp:103-232: the start hypothesis at word 0 position 0, in-word 0-1-2 jumps
  * with the penalty keyed on the DESTINATION state, every word end entering every word at position 0 or 1 with the word penalty --

@@ -37,6 +37,7 @@ SYMBOLS = [
     "sr_word_lattice_corpus", "sr_lattice_nbest",
     "sr_fmllr_statistics_corpus", "sr_fmllr_statistics_bw_corpus", "sr_fmllr_estimate", "sr_corpus_transform",
     "sr_mllr_statistics_corpus", "sr_mllr_statistics_bw_corpus", "sr_mllr_estimate", "sr_model_transform_means",
+    "sr_mllt_statistics_corpus", "sr_mllt_statistics_bw_corpus", "sr_mllt_estimate",
     "sr_bigram_create", "sr_bigram_destroy", "sr_bigram_describe", "sr_recognize_bigram_corpus",
     "sr_bigram_word_posteriors_corpus", "sr_recognize_bigram_confidence_corpus",
     "sr_bigram_occupancies_corpus", "sr_bigram_mmi_statistics_corpus",
@@ -137,6 +138,9 @@ def lib():
                                                    vp]
         L.sr_mllr_estimate.argtypes = [u32, u32, u32, u32, vp, vp, vp, vp, dbl, vp, vp, vp]
         L.sr_model_transform_means.argtypes = [vp, vp, u32, vp, C.POINTER(vp)]
+        L.sr_mllt_statistics_corpus.argtypes = [vp, vp, vp, i32, vp, vp]
+        L.sr_mllt_statistics_bw_corpus.argtypes = [vp, vp, vp, vp, C.POINTER(dbl * 3), C.c_uint16, i32, dbl, i32, vp, vp, vp]
+        L.sr_mllt_estimate.argtypes = [u32, dbl, vp, u32, dbl, vp, vp, vp, vp]
         L.sr_word_posteriors_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, vp]
         L.sr_recognize_confidence_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, vp, vp, vp, vp, vp]
         L.sr_net_occupancies_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, vp, vp, vp]
@@ -693,6 +697,25 @@ class Corpus:
                                                   _ptr(k), _ptr(G)))
         return cost[: self.n_utts], (beta, k, G)
 
+    def mllt_statistics(self, states, max_approx=True):
+        """MLLT statistics of an alignment (sr_mllt_statistics_corpus) -> (beta float, G f64[D, D, D])."""
+        states = np.ascontiguousarray(states, dtype=np.uint16)
+        D = self.model.dim
+        beta, G = np.zeros(1), np.zeros((D, D, D))
+        _check(lib().sr_mllt_statistics_corpus(self.model.h, self.h, _ptr(states), int(max_approx), _ptr(beta), _ptr(G)))
+        return float(beta[0]), G
+
+    def mllt_statistics_bw(self, automata, tdp, silence_state, kernel=GMM_DEFAULT, floor=0.0, max_approx=True):
+        """The same from the forward-backward posteriors (sr_mllt_statistics_bw_corpus) -> (cost f64[n_utts], (beta, G))."""
+        flat, off = self._aut(automata)
+        D = self.model.dim
+        beta, G = np.zeros(1), np.zeros((D, D, D))
+        cost = np.zeros(max(self.n_utts, 1), dtype=np.float64)
+        t3 = (C.c_double * 3)(*tdp)
+        _check(lib().sr_mllt_statistics_bw_corpus(self.model.h, self.h, _ptr(flat), _ptr(off), C.byref(t3), silence_state, kernel, float(floor),
+                                                  int(max_approx), _ptr(cost), _ptr(beta), _ptr(G)))
+        return cost[: self.n_utts], (float(beta[0]), G)
+
     def transform(self, utt_speaker, W):
         """The adapted corpus y = A x + b, W[s] = [A b] of utterance u's speaker utt_speaker[u] (sr_corpus_transform) -> Corpus."""
         spk = np.ascontiguousarray(utt_speaker, dtype=np.uint32)
@@ -1008,6 +1031,27 @@ def mllr_estimate(beta, k, G, parent=None, min_count=0.0, W=None):
     _check(lib().sr_mllr_estimate(D, S, R, len(parent), _ptr(parent), _ptr(beta), _ptr(k), _ptr(G), float(min_count), _ptr(W), _ptr(node),
                                   _ptr(aux)))
     return W, node, aux
+
+
+def mllt_estimate(beta, G, n_sweeps=10, min_count=0.0, A=None):
+    """Row-by-row MLLT / global semi-tied estimate (sr_mllt_estimate; host code) from A (default: identity) -> (A f64[D, D],
+    aux f64[n_sweeps+1] = Q after 0 .. n_sweeps sweeps, logdet float, status int)."""
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    D = G.shape[0]
+    assert G.shape == (D, D, D)
+    A = np.array(np.eye(D) if A is None else A, dtype=np.float64, order="C")
+    assert A.shape == (D, D)
+    aux = np.zeros(int(n_sweeps) + 1)
+    logdet = np.zeros(1)
+    status = np.zeros(1, dtype=np.int32)
+    _check(lib().sr_mllt_estimate(D, float(beta), _ptr(G), int(n_sweeps), float(min_count), _ptr(A), _ptr(aux), _ptr(logdet), _ptr(status)))
+    return A, aux, float(logdet[0]), int(status[0])
+
+
+def mllt_affine(A):
+    """[A 0] as f64[1, D, D+1]: the W of Corpus.transform (one speaker) and Model.transform_means (one class) that applies A."""
+    A = np.asarray(A, dtype=np.float64)
+    return np.ascontiguousarray(np.hstack([A, np.zeros((A.shape[0], 1))])[None])
 
 
 def traceback_words(tb_word, tb_bkp, silence_word, n_words):

@@ -18,44 +18,8 @@ namespace {
 
 using srhost::chol_solve;  // (host_util.h: shared with mllr.cpp)
 using srhost::cholesky;
+using srhost::invert;
 using srhost::set_error;
-
-// inv = A^-1 (D x D, A = the first D columns of W's rows), *sign, *logabs of det A; false: singular
-bool invert(const double* W, uint32_t D, std::vector<double>& inv, double* sign, double* logabs) {
-  const uint32_t E = D + 1;
-  std::vector<double> a((size_t)D * D);
-  for (uint32_t i = 0; i < D; i++)
-    for (uint32_t j = 0; j < D; j++) a[(size_t)i * D + j] = W[(size_t)i * E + j];
-  inv.assign((size_t)D * D, 0.0);
-  for (uint32_t i = 0; i < D; i++) inv[(size_t)i * D + i] = 1.0;
-  double sg = 1.0, la = 0.0;
-  for (uint32_t c = 0; c < D; c++) {
-    uint32_t piv = c;
-    for (uint32_t r = c + 1; r < D; r++)
-      if (std::fabs(a[(size_t)r * D + c]) > std::fabs(a[(size_t)piv * D + c])) piv = r;
-    const double pv = a[(size_t)piv * D + c];
-    if (pv == 0.0 || !std::isfinite(pv)) return false;
-    if (piv != c) {
-      for (uint32_t j = 0; j < D; j++) {
-        std::swap(a[(size_t)piv * D + j], a[(size_t)c * D + j]);
-        std::swap(inv[(size_t)piv * D + j], inv[(size_t)c * D + j]);
-      }
-      sg = -sg;
-    }
-    if (pv < 0.0) sg = -sg;
-    la += std::log(std::fabs(pv));
-    for (uint32_t j = 0; j < D; j++) { a[(size_t)c * D + j] /= pv; inv[(size_t)c * D + j] /= pv; }
-    for (uint32_t r = 0; r < D; r++) {
-      if (r == c) continue;
-      const double f = a[(size_t)r * D + c];
-      if (f == 0.0) continue;
-      for (uint32_t j = 0; j < D; j++) { a[(size_t)r * D + j] -= f * a[(size_t)c * D + j]; inv[(size_t)r * D + j] -= f * inv[(size_t)c * D + j]; }
-    }
-  }
-  *sign = sg;
-  *logabs = la;
-  return std::isfinite(la);
-}
 
 double dot(const double* a, const double* b, uint32_t n) {
   double s = 0.0;
@@ -170,3 +134,4 @@ extern "C" SR_API int sr_fmllr_estimate(uint32_t dim, uint32_t n_speakers, const
 }
 
 #include "mllr.cpp"  // sr_mllr_estimate: the MLLR mean transforms (see the note at its top)
+#include "mllt.cpp"  // sr_mllt_estimate: the MLLT transform, likewise

@@ -130,6 +130,7 @@ struct sr_model {
   size_t defer_budget = (size_t)32 << 30;  // most bytes for the refinement's deferred-leftover segments (SRGPU_DEFER_MB; 0: route off)
   uint32_t defer_cap_limit = 0;            // most entries per segment, 0: no limit (SRGPU_DEFER_CAP, tests: full segments)
   size_t fb_budget = (size_t)1 << 30;      // most bytes for the forward-backward trellises of one launch (SRGPU_FB_MB)
+  size_t mllt_budget = (size_t)256 << 20;  // most bytes for the segment partials of one round of the MLLT statistics (SRGPU_MLLT_MB)
   // profiling
   bool profiling = false;
   std::vector<EventPair> events;

@@ -86,6 +86,44 @@ inline void chol_solve(const std::vector<double>& l, uint32_t n, const double* b
   }
 }
 
+// Gauss-Jordan elimination with partial pivoting: inv = A^-1 (D x D, A = the first D columns of W's D + 1 long rows), *sign and
+// *logabs of det A; false: singular  (fmllr.cpp, mllt.cpp)
+inline bool invert(const double* W, uint32_t D, std::vector<double>& inv, double* sign, double* logabs) {
+  const uint32_t E = D + 1;
+  std::vector<double> a((size_t)D * D);
+  for (uint32_t i = 0; i < D; i++)
+    for (uint32_t j = 0; j < D; j++) a[(size_t)i * D + j] = W[(size_t)i * E + j];
+  inv.assign((size_t)D * D, 0.0);
+  for (uint32_t i = 0; i < D; i++) inv[(size_t)i * D + i] = 1.0;
+  double sg = 1.0, la = 0.0;
+  for (uint32_t c = 0; c < D; c++) {
+    uint32_t piv = c;
+    for (uint32_t r = c + 1; r < D; r++)
+      if (std::fabs(a[(size_t)r * D + c]) > std::fabs(a[(size_t)piv * D + c])) piv = r;
+    const double pv = a[(size_t)piv * D + c];
+    if (pv == 0.0 || !std::isfinite(pv)) return false;
+    if (piv != c) {
+      for (uint32_t j = 0; j < D; j++) {
+        std::swap(a[(size_t)piv * D + j], a[(size_t)c * D + j]);
+        std::swap(inv[(size_t)piv * D + j], inv[(size_t)c * D + j]);
+      }
+      sg = -sg;
+    }
+    if (pv < 0.0) sg = -sg;
+    la += std::log(std::fabs(pv));
+    for (uint32_t j = 0; j < D; j++) { a[(size_t)c * D + j] /= pv; inv[(size_t)c * D + j] /= pv; }
+    for (uint32_t r = 0; r < D; r++) {
+      if (r == c) continue;
+      const double f = a[(size_t)r * D + c];
+      if (f == 0.0) continue;
+      for (uint32_t j = 0; j < D; j++) { a[(size_t)r * D + j] -= f * a[(size_t)c * D + j]; inv[(size_t)r * D + j] -= f * inv[(size_t)c * D + j]; }
+    }
+  }
+  *sign = sg;
+  *logabs = la;
+  return std::isfinite(la);
+}
+
 // Worker threads that cannot outlive their scope and cannot take the process down: the destructor joins (a joinable
 // std::thread that is destroyed calls std::terminate -- what an exception thrown between emplace_back and join used to do),
 // a worker's exception is kept and rethrown by wait() on the caller's thread (where `guarded` turns it into an SR_E* code),

@@ -757,4 +757,27 @@ uint32_t mllr_dens_per_block();
 hipError_t launch_mllr_transform_means(const double* means, const uint32_t* order, const uint32_t* blk, uint32_t n_blocks, const double* W,
                                        uint32_t dim, double* out, hipStream_t stream);
 
+// ---- MLLT: the global semi-tied covariance statistics of a set of pairs (mllt_stats.hip) ------------------------------------------------
+// The pairs are EmArgs' (pair_frame, pair_dens, pair_w; key_mean 0xFFFFFFFF: dropped), taken in pair order and cut into segments of
+// mllt_seg_pairs().  The contraction's shape: rows = D + 1 padded to 16 (row D carries gamma alone); columns = the D (D + 1) / 2 pairs
+// j <= k, then one "ones" column (its row D is beta), padded to 16.
+struct MlltShape { uint32_t rows, tri, tiles, cols; };
+MlltShape mllt_shape(uint32_t dim);
+uint32_t mllt_seg_pairs();   // pairs per segment: the unit of the fixed summation order
+uint32_t mllt_max_dim();
+struct MlltArgs {
+  const float* feats;
+  uint32_t dim;
+  MlltShape shape;
+  const double* means; const double* inv_vars;  // [C x dim] per density
+  uint64_t n_pairs;
+  const uint32_t* pair_frame; const uint32_t* pair_dens; const uint32_t* pair_key; const double* pair_w;
+  // one round: segments [seg0, seg0 + n_segs) into partial; the reduction adds them, ascending, onto the running sums in out_G / out_beta
+  // (seg0 == 0: onto 0)
+  uint32_t seg0, n_segs;
+  double* partial;              // workspace [n_segs][rows][cols]
+  double *out_beta, *out_G;     // device: [1], [D x D x D]
+};
+hipError_t launch_mllt_round(const MlltArgs& a, hipStream_t stream);  // contraction and reduction of one round
+
 }  // namespace srgpu

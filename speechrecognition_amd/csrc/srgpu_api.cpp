@@ -815,6 +815,7 @@ int model_shell(int device, uint32_t dim, uint32_t n_states, const uint32_t* den
   if (const char* ov = getenv("SRGPU_OVERLAP")) m->overlap = atoi(ov) != 0;
   if (const char* e = getenv("SRGPU_DEFER_MB")) m->defer_budget = (size_t)strtoull(e, nullptr, 10) << 20;
   if (const char* e = getenv("SRGPU_FB_MB")) m->fb_budget = std::max<size_t>(1, (size_t)strtoull(e, nullptr, 10)) << 20;
+  if (const char* e = getenv("SRGPU_MLLT_MB")) m->mllt_budget = std::max<size_t>(1, (size_t)strtoull(e, nullptr, 10)) << 20;
   if (const char* e = getenv("SRGPU_DEFER_CAP")) m->defer_cap_limit = std::max(1u, (uint32_t)strtoul(e, nullptr, 10));  // (tests: full segments)
   *out = own.release();
   return SR_OK;
@@ -2442,6 +2443,81 @@ int sr_model_transform_means(sr_model* m, const uint32_t* dens_class, uint32_t n
   HIP_TRY(hipStreamSynchronize(o->s_gmm));
   *out = own.release();
   return SR_OK;
+  });
+}
+
+// ---- MLLT, the global semi-tied covariance transform (mllt_stats.hip; the estimate itself is host code, mllt.cpp) -------------------
+// The checks every statistics call makes before any launch
+static int mllt_check(sr_model* m, sr_corpus* c, const double* out_beta, const double* out_G) {
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  if (!out_beta || !out_G) return fail(SR_EINVAL, "null output");
+  if (m->dim > mllt_max_dim()) return fail(SR_ELIMIT, "dimension %u exceeds %u (MLLT statistics)", m->dim, mllt_max_dim());
+  const MlltShape s = mllt_shape(m->dim);
+  const size_t seg_bytes = sizeof(double) * s.rows * s.cols;
+  if (seg_bytes > m->mllt_budget)
+    return fail(SR_ELIMIT, "one segment's partial sums (%llu bytes) exceed the MLLT workspace of %llu (SRGPU_MLLT_MB)",
+                (unsigned long long)seg_bytes, (unsigned long long)m->mllt_budget);
+  return SR_OK;
+}
+
+// contraction and reduction over the pairs `e` describes (formed already), in rounds of as many consecutive segments as the workspace
+// holds; the results to the host
+static int mllt_statistics(sr_model* m, sr_corpus* c, const EmArgs& e, double* out_beta, double* out_G) {
+  const uint32_t D = m->dim;
+  const size_t nG = (size_t)D * D * D;
+  if (e.n_pairs == 0) {  // no frame, or nothing above the floor
+    *out_beta = 0.0;
+    std::fill(out_G, out_G + nG, 0.0);
+    return SR_OK;
+  }
+  int rc;
+  MlltArgs a{};
+  a.feats = c->feats.p; a.dim = D; a.shape = mllt_shape(D); a.means = m->means.p; a.inv_vars = m->inv_vars.p;
+  a.n_pairs = e.n_pairs; a.pair_frame = e.pair_frame; a.pair_dens = e.pair_dens; a.pair_key = e.key_mean; a.pair_w = e.pair_w;
+  const uint64_t n_segs = (e.n_pairs + mllt_seg_pairs() - 1) / mllt_seg_pairs();
+  const size_t seg_doubles = (size_t)a.shape.rows * a.shape.cols;
+  const uint64_t per_round = std::min<uint64_t>(n_segs, m->mllt_budget / (sizeof(double) * seg_doubles));
+  if (n_segs > 0xFFFFFFFFull || per_round == 0) return fail(SR_EINTERNAL, "MLLT statistics: %llu segments", (unsigned long long)n_segs);
+  HIP_TRY(c->fm_partial.ensure((size_t)per_round * seg_doubles));
+  HIP_TRY(c->fm_beta.ensure(1)); HIP_TRY(c->fm_G.ensure(nG));
+  a.partial = c->fm_partial.p; a.out_beta = c->fm_beta.p; a.out_G = c->fm_G.p;
+  EventPair ep{};
+  if ((rc = prof_begin(m, m->s_gmm, 1, &ep))) return rc;
+  for (uint64_t s0 = 0; s0 < n_segs; s0 += per_round) {
+    a.seg0 = (uint32_t)s0; a.n_segs = (uint32_t)std::min<uint64_t>(per_round, n_segs - s0);
+    HIP_TRY(launch_mllt_round(a, m->s_gmm));
+  }
+  if ((rc = prof_end(m, m->s_gmm, &ep))) return rc;
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  HIP_TRY(hipMemcpy(out_beta, c->fm_beta.p, sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_G, c->fm_G.p, sizeof(double) * nG, hipMemcpyDeviceToHost));
+  if (m->profiling) {  // per pair: key, weight, frame, density; a feature row, a mean row and a variance row; the partials out and in
+    m->prof.frames += c->n_frames;
+    m->prof.search_bytes += (double)e.n_pairs * (20.0 + 20.0 * D) + 16.0 * (double)n_segs * seg_doubles;
+  }
+  return SR_OK;
+}
+
+int sr_mllt_statistics_corpus(sr_model* m, sr_corpus* c, const uint16_t* states, int max_approx, double* out_beta, double* out_G) {
+  return guarded(__func__, [&]() -> int {
+  int rc = mllt_check(m, c, out_beta, out_G);
+  if (rc) return rc;
+  EmArgs e{};
+  if ((rc = adapt_pairs(m, c, states, max_approx, &e))) return rc;
+  return mllt_statistics(m, c, e, out_beta, out_G);
+  });
+}
+
+int sr_mllt_statistics_bw_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
+                                 uint16_t silence_state, int gmm_kernel, double posterior_floor, int max_approx, double* out_cost,
+                                 double* out_beta, double* out_G) {
+  return guarded(__func__, [&]() -> int {
+  int rc = mllt_check(m, c, out_beta, out_G);
+  if (rc) return rc;
+  EmArgs e{};
+  if ((rc = adapt_pairs_bw(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, max_approx, out_cost, &e))) return rc;
+  return mllt_statistics(m, c, e, out_beta, out_G);
   });
 }
 
