@@ -691,22 +691,28 @@ struct FmllrShape { uint32_t rows, g_cols, g_tiles, k_tiles, cols; };
 FmllrShape fmllr_shape(uint32_t dim);
 uint32_t fmllr_seg_frames();   // frames per segment: the unit of the fixed summation order
 uint32_t fmllr_max_dim();
+// What the fMLLR and MLLR contractions share (sym_contract.h): the items of every group, group after group, are cut into segments;
+// segment s = items [seg_begin[s], + seg_len[s]) of one group (at most fmllr_seg_frames()), group q owns segments [grp_seg_off[q],
+// grp_seg_off[q + 1]); G below stands for n_groups
+struct GroupedStats {
+  FmllrShape shape;
+  uint32_t n_groups, n_segs;
+  const uint32_t* seg_begin; const uint32_t* seg_len; const uint32_t* grp_seg_off;
+  double* partial;                   // workspace [n_segs][rows][cols]
+  double *out_beta, *out_k, *out_G;  // device: [G], [G x D x (D+1)], [G x D x (D+1) x (D+1)]
+};
+hipError_t launch_grouped_reduce(const GroupedStats& a, uint32_t dim, hipStream_t stream);  // fmllr_stats.hip: partial -> out_*
 struct FmllrArgs {
   const float* feats;
   uint64_t n_frames;
   uint32_t dim;
-  FmllrShape shape;
   const double* means; const double* inv_vars;  // [C x dim] per density
   // the pairs, in frame order: frame t's are [frame_pair_off[t], frame_pair_off[t + 1])
   const uint64_t* frame_pair_off;  // [n_frames + 1]
   const uint32_t* pair_dens; const uint32_t* pair_key; const double* pair_w;  // key 0xFFFFFFFF: dropped
   double *fold_a, *fold_c;         // workspace [n_frames x rows]
-  // speakers: frame_list = every speaker's frames in corpus order, speaker after speaker; segment g = frame_list[seg_begin[g] ..
-  // + seg_len[g]) (at most fmllr_seg_frames()), speaker s owns segments [spk_seg_off[s], spk_seg_off[s + 1])
-  uint32_t n_speakers, n_segs;
-  const uint32_t* frame_list; const uint32_t* seg_begin; const uint32_t* seg_len; const uint32_t* spk_seg_off;
-  double* partial;                 // workspace [n_segs][rows][cols]
-  double *out_beta, *out_k, *out_G;  // device: [S], [S x D x (D+1)], [S x D x (D+1) x (D+1)]
+  const uint32_t* frame_list;      // every speaker's frames in corpus order, speaker after speaker: the items of g (group = speaker)
+  GroupedStats g;
 };
 hipError_t launch_fmllr_item_frames(const uint32_t* item_off, const uint64_t* item_pair_end, uint64_t n_frames, uint64_t* frame_pair_off,
                                     hipStream_t stream);
@@ -720,11 +726,10 @@ hipError_t launch_fmllr_transform(const float* feats, const uint64_t* frame_off,
 //   launch_mllr_runs     keys speaker * n_dens + density, stable sort, the runs of equal keys           -> *n_runs, run_key[*n_runs - 1]
 //   launch_mllr_groups   the runs ("entries") ordered by (speaker, class, density), the groups' bounds  -> grp_begin[n_groups + 1]
 //   launch_mllr_statistics  entry sums, contraction over the segments the host cut from grp_begin, reduction
-// The contraction has fmllr_shape(dim)'s rows and columns and segments of fmllr_seg_frames() entries.
+// The contraction has fmllr_shape(dim)'s rows and columns and segments of fmllr_seg_frames() entries (GroupedStats).
 struct MllrArgs {
   const float* feats;
   uint32_t dim;
-  FmllrShape shape;
   const double* means; const double* inv_vars;  // [n_dens x dim]
   uint64_t n_pairs;
   const uint32_t* pair_frame; const uint32_t* pair_dens; const uint32_t* pair_key; const double* pair_w;
@@ -740,12 +745,7 @@ struct MllrArgs {
   uint32_t n_entries;
   uint32_t *gkey, *gkey_sorted, *ent_order, *grp_begin, *ent_dens;
   double *ent_occ, *ent_x;
-  // segment g = positions [seg_begin[g], + seg_len[g]) of one group (at most fmllr_seg_frames()), group q owns segments
-  // [grp_seg_off[q], grp_seg_off[q + 1])
-  uint32_t n_segs;
-  const uint32_t* seg_begin; const uint32_t* seg_len; const uint32_t* grp_seg_off;
-  double* partial;                    // workspace [n_segs][rows][cols]
-  double *out_beta, *out_k, *out_G;   // device: [S x R], [S x R x D x (D+1)], [S x R x D x (D+1) x (D+1)]
+  GroupedStats g;                  // the items: the entry positions; group = speaker * n_classes + class
 };
 size_t mllr_temp_bytes(uint64_t n_pairs);
 hipError_t launch_mllr_runs(const MllrArgs& a, hipStream_t stream);

@@ -16,13 +16,10 @@
 //   2. mllr_group_key_kernel an entry's group = speaker * n_classes + class; a stable sort by it orders the entries by (speaker,
 //                            class, density); mllr_bounds_kernel finds every group's first entry.
 //   3. mllr_entry_kernel     one wave per entry, a lane per dimension: occ and x_acc, the entry's pairs one after the other.
-//   4. mllr_contract_kernel  fmllr_contract_kernel's scheme (fmllr_stats.hip) with entries in the place of frames: rows i on the 16-row
-//                            side of v_mfma_f64_16x16x4_f64 (occ iv_di for G, iv_di x_acc_i for k; row D of the k side is occ, so that
-//                            its column D is beta), the columns (j <= k) and (j, D) on the other side, the products xi_dj xi_dk formed
-//                            from the FP64 means when a block of entries is staged into the LDS.  A group's entries are cut into
-//                            segments of fmllr_seg_frames(); a workgroup takes one segment and writes its partial sums.
-//   5. mllr_reduce_kernel    one thread per (group, row, column): the partials of the group's segments added in ascending order; both
-//                            triangles of G from the one sum.
+//   4. mllr_contract_kernel  the shared symmetric contraction (sym_contract.h) with a group's entries as the items: xi_d from the FP64 means
+//                            on the column side; on the row side occ iv_di for G and iv_di x_acc_i for k (row D of the k side is occ, so
+//                            that its column D is beta).  A group's entries are cut into segments of fmllr_seg_frames().
+//   5. grouped_reduce_kernel (fmllr_stats.hip) the partials of a group's segments added in ascending order: G, k and beta.
 // No atomics; every order of summation is fixed by the pairs and the segment length alone: two identical calls return identical bits.
 //
 //   mllr_means_kernel        mu'_di = acc, acc from b_i taking acc = acc + A_ij * mu_dj, j ascending, no contraction into FMAs.
@@ -33,15 +30,12 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "sym_contract.h"
 
 namespace srgpu {
 
 #pragma clang fp contract(off)
 
-static constexpr int kStageEntries = 32;  // entries staged in the LDS at a time
-static constexpr int kWaves = 4;
-static constexpr int kTilesPerWave = 2;   // column tiles whose accumulators a wave keeps
-static constexpr int kTilesPerGroup = kWaves * kTilesPerWave;
 static constexpr int kDensPerBlock = 64;  // densities a workgroup of mllr_means_kernel transforms
 
 uint32_t mllr_dens_per_block() { return kDensPerBlock; }
@@ -94,126 +88,39 @@ __global__ __launch_bounds__(256) void mllr_entry_kernel(MllrArgs a) {
   }
 }
 
-// fmllr_column (fmllr_stats.hip): column n of the contraction -> (j, k): n < g_cols: the n-th pair j <= k in row-major order of the upper
-// triangle; beyond the G tiles: (j, D) of k; padding: (E, E), which reads the zero column of the staged entry
-__device__ inline void mllr_column(const FmllrShape& s, uint32_t E, uint32_t n, uint32_t* j, uint32_t* k) {
-  if (n >= s.g_tiles * 16u) {
-    const uint32_t c = n - s.g_tiles * 16u;
-    *j = c < E ? c : E;
-    *k = c < E ? E - 1 : E;
-    return;
+// a stage of a group's entries: xi_d on the column side, occ iv and iv x_acc on the row side
+struct MllrStager {
+  static constexpr bool kTwoRows = true, kPreStage = false;
+  const MllrArgs& a;
+  const uint32_t s0, sn;  // the segment: entry positions [s0, s0 + sn)
+  __device__ void column(uint32_t n, uint32_t* j, uint32_t* k) const { affine_column(a.g.shape, a.dim + 1, n, j, k); }
+  __device__ double col(uint32_t f0, uint32_t f, uint32_t j) const {
+    const uint32_t D = a.dim;
+    if (f0 + f < sn && j <= D) return j < D ? a.means[(uint64_t)a.ent_dens[s0 + f0 + f] * D + j] : 1.0;
+    return 0.0;
   }
-  if (n >= s.g_cols) { *j = E; *k = E; return; }
-  uint32_t r = 0, left = n;
-  while (left >= E - r) { left -= E - r; r++; }  // row r of the triangle holds E - r columns
-  *j = r;
-  *k = r + left;
-}
+  __device__ void rows(uint32_t f0, uint32_t f, uint32_t i, double* va, double* vc) const {
+    const uint32_t D = a.dim;
+    if (f0 + f >= sn || i > D) return;
+    const uint32_t q = s0 + f0 + f;
+    const double occ = a.ent_occ[q];
+    if (i == D) {
+      *vc = occ;
+    } else {
+      const double iv = a.inv_vars[(uint64_t)a.ent_dens[q] * D + i];
+      *va = occ * iv;
+      *vc = iv * a.ent_x[(uint64_t)q * D + i];
+    }
+  }
+};
 
 // grid (segments, column-tile groups); RT = row tiles of 16
 template <int RT>
 __global__ __launch_bounds__(kWaves * 64) void mllr_contract_kernel(MllrArgs a) {
-  constexpr int R = RT * 16;
-  constexpr int kXs = 66;      // doubles per staged xi row: E <= 64 values, then zeros (column E is read by padding columns)
-  constexpr int kAs = R + 2;   // doubles per staged row of either row-side operand
-  __shared__ double xs[kStageEntries * kXs];
-  __shared__ double as[kStageEntries * kAs];
-  __shared__ double cs[kStageEntries * kAs];
-  const uint32_t D = a.dim, E = D + 1;
-  const uint32_t seg = blockIdx.x;
-  const uint32_t s0 = a.seg_begin[seg], sn = a.seg_len[seg];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t kk = lane >> 4, cc = lane & 15u;
-  const uint32_t n_tiles = a.shape.g_tiles + a.shape.k_tiles;
-  uint32_t tile[kTilesPerWave], cj[kTilesPerWave], ck[kTilesPerWave];
-  bool live[kTilesPerWave], isk[kTilesPerWave];
-#pragma unroll
-  for (int q = 0; q < kTilesPerWave; q++) {
-    tile[q] = blockIdx.y * kTilesPerGroup + wave * kTilesPerWave + q;
-    live[q] = tile[q] < n_tiles;          // wave-uniform
-    isk[q] = tile[q] >= a.shape.g_tiles;  // wave-uniform: a k tile takes iv x_acc on the row side
-    mllr_column(a.shape, E, (live[q] ? tile[q] : 0u) * 16u + cc, &cj[q], &ck[q]);
-  }
-  typedef double d4 __attribute__((ext_vector_type(4)));
-  d4 acc[kTilesPerWave][RT];
-#pragma unroll
-  for (int q = 0; q < kTilesPerWave; q++)
-#pragma unroll
-    for (int r = 0; r < RT; r++) acc[q][r] = d4{0.0, 0.0, 0.0, 0.0};
-
-  for (uint32_t f0 = 0; f0 < sn; f0 += kStageEntries) {
-    __syncthreads();  // the previous stage has been read
-    for (uint32_t e = threadIdx.x; e < kStageEntries * kXs; e += kWaves * 64) {
-      const uint32_t f = e / kXs, j = e - f * kXs;
-      double v = 0.0;
-      if (f0 + f < sn && j < E) v = j < D ? a.means[(uint64_t)a.ent_dens[s0 + f0 + f] * D + j] : 1.0;
-      xs[e] = v;
-    }
-    for (uint32_t e = threadIdx.x; e < kStageEntries * R; e += kWaves * 64) {
-      const uint32_t f = e / R, i = e - f * R;
-      double va = 0.0, vc = 0.0;
-      if (f0 + f < sn && i <= D) {
-        const uint32_t q = s0 + f0 + f;
-        const double occ = a.ent_occ[q];
-        if (i == D) {
-          vc = occ;
-        } else {
-          const double iv = a.inv_vars[(uint64_t)a.ent_dens[q] * D + i];
-          va = occ * iv;
-          vc = iv * a.ent_x[(uint64_t)q * D + i];
-        }
-      }
-      as[f * kAs + i] = va;
-      cs[f * kAs + i] = vc;
-    }
-    __syncthreads();
-#pragma unroll 2
-    for (uint32_t f = 0; f < kStageEntries; f += 4) {
-      const double* xr = xs + (f + kk) * kXs;
-#pragma unroll
-      for (int q = 0; q < kTilesPerWave; q++) {
-        if (!live[q]) continue;
-        const double b = xr[cj[q]] * xr[ck[q]];
-        const double* ar = (isk[q] ? cs : as) + (f + kk) * kAs + cc;
-#pragma unroll
-        for (int r = 0; r < RT; r++) acc[q][r] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[r * 16], b, acc[q][r], 0, 0, 0);
-      }
-    }
-  }
-  // partial[seg][row][column]: the result's row of register v is kk + 4 v, its column cc
-  const uint32_t C = a.shape.cols;
-  double* out = a.partial + (uint64_t)seg * a.shape.rows * C;
-#pragma unroll
-  for (int q = 0; q < kTilesPerWave; q++) {
-    if (!live[q]) continue;
-#pragma unroll
-    for (int r = 0; r < RT; r++)
-#pragma unroll
-      for (int v = 0; v < 4; v++) out[(uint64_t)(r * 16 + kk + 4 * v) * C + tile[q] * 16u + cc] = acc[q][r][v];
-  }
-}
-
-// grid (groups x ceil(cols / 256), rows <= D)
-__global__ __launch_bounds__(256) void mllr_reduce_kernel(MllrArgs a) {
-  const uint32_t D = a.dim, E = D + 1, C = a.shape.cols;
-  const uint32_t nb = (C + 255u) / 256u, g = blockIdx.x / nb;
-  const uint32_t n = (blockIdx.x - g * nb) * 256 + threadIdx.x, i = blockIdx.y;
-  if (n >= C) return;
-  uint32_t j, k;
-  mllr_column(a.shape, E, n, &j, &k);
-  if (j >= E) return;  // padding column
-  const bool is_k = n >= a.shape.g_tiles * 16u;
-  if (i == D && !(is_k && j == D)) return;  // of row D only beta is kept
-  double sum = 0.0;
-  for (uint32_t sg = a.grp_seg_off[g]; sg < a.grp_seg_off[g + 1]; sg++) sum = sum + a.partial[((uint64_t)sg * a.shape.rows + i) * C + n];
-  if (is_k) {
-    if (i == D) a.out_beta[g] = sum;
-    else a.out_k[((uint64_t)g * D + i) * E + j] = sum;
-    return;
-  }
-  double* G = a.out_G + ((uint64_t)g * D + i) * E * E;
-  G[(uint64_t)j * E + k] = sum;
-  G[(uint64_t)k * E + j] = sum;
+  const uint32_t seg = blockIdx.x, sn = a.g.seg_len[seg];
+  const FmllrShape& s = a.g.shape;
+  contract_segment<RT>(MllrStager{a, a.g.seg_begin[seg], sn}, sn, s.g_tiles + s.k_tiles, s.g_tiles,
+                       a.g.partial + (uint64_t)seg * s.rows * s.cols, s.cols);
 }
 
 size_t mllr_temp_bytes(uint64_t n_pairs) {
@@ -257,20 +164,12 @@ hipError_t launch_mllr_groups(const MllrArgs& a, hipStream_t stream) {
 
 hipError_t launch_mllr_statistics(const MllrArgs& a, hipStream_t stream) {
   if (a.n_entries) hipLaunchKernelGGL(mllr_entry_kernel, dim3((a.n_entries + 3) / 4), dim3(256), 0, stream, a);
-  if (a.n_segs) {
-    const uint32_t groups = (a.shape.g_tiles + a.shape.k_tiles + kTilesPerGroup - 1) / kTilesPerGroup;
-    const dim3 grid(a.n_segs, groups), block(kWaves * 64);
-    switch (a.shape.rows / 16) {
-      case 1: hipLaunchKernelGGL((mllr_contract_kernel<1>), grid, block, 0, stream, a); break;
-      case 2: hipLaunchKernelGGL((mllr_contract_kernel<2>), grid, block, 0, stream, a); break;
-      case 3: hipLaunchKernelGGL((mllr_contract_kernel<3>), grid, block, 0, stream, a); break;
-      case 4: hipLaunchKernelGGL((mllr_contract_kernel<4>), grid, block, 0, stream, a); break;
-      default: return hipErrorInvalidValue;
-    }
+  if (a.g.n_segs) {
+    const hipError_t e = launch_contract<mllr_contract_kernel<1>, mllr_contract_kernel<2>, mllr_contract_kernel<3>, mllr_contract_kernel<4>>(
+        a, a.g.shape.rows, a.g.n_segs, a.g.shape.g_tiles + a.g.shape.k_tiles, stream);
+    if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(mllr_reduce_kernel, dim3(a.n_speakers * a.n_classes * ((a.shape.cols + 255) / 256), a.dim + 1), dim3(256), 0, stream,
-                     a);
-  return hipGetLastError();
+  return launch_grouped_reduce(a.g, a.dim, stream);
 }
 
 // One workgroup per block of at most kDensPerBlock densities of one class: the class's W = [A b] in the LDS, a thread per (density, row)
@@ -285,11 +184,7 @@ __global__ __launch_bounds__(256) void mllr_means_kernel(const double* means, co
   for (uint32_t e = threadIdx.x; e < (b1 - b0) * D; e += 256) {
     const uint32_t n = e / D, i = e - n * D;
     const uint64_t d = order[b0 + n];
-    const double* mu = means + d * D;
-    const double* wi = w + i * E;
-    double acc = wi[D];
-    for (uint32_t j = 0; j < D; j++) acc = acc + wi[j] * mu[j];
-    out[d * D + i] = acc;
+    out[d * D + i] = affine_row(w + i * E, means + d * D, D);
   }
 }
 

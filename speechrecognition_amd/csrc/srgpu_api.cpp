@@ -2137,6 +2137,34 @@ static int adapt_pairs_bw(sr_model* m, sr_corpus* c, const uint16_t* automata, c
   return SR_OK;
 }
 
+// What the fMLLR and MLLR statistics end with: the segments of the groups (g->shape is the caller's) to the device, the partials'
+// workspace and the results sized, `launch` under the profile events, the results to the host
+extern "C++" {
+template <class Launch>
+static int grouped_statistics(sr_model* m, sr_corpus* c, const srplan::Segments& seg, uint32_t n_groups, GroupedStats* g, Launch launch,
+                              double* out_beta, double* out_k, double* out_G) {
+  const uint32_t D = m->dim;
+  int rc;
+  g->n_groups = n_groups; g->n_segs = (uint32_t)seg.begin.size();
+  HIP_TRY(c->fm_seg_begin.upload(seg.begin.data(), seg.begin.size())); HIP_TRY(c->fm_seg_len.upload(seg.len.data(), seg.len.size()));
+  HIP_TRY(c->fm_spk_seg_off.upload(seg.off.data(), seg.off.size()));
+  HIP_TRY(c->fm_partial.ensure((size_t)g->n_segs * g->shape.rows * g->shape.cols));
+  const size_t nk = (size_t)n_groups * D * (D + 1), nG = nk * (D + 1);
+  HIP_TRY(c->fm_beta.ensure(n_groups)); HIP_TRY(c->fm_k.ensure(nk)); HIP_TRY(c->fm_G.ensure(nG));
+  g->seg_begin = c->fm_seg_begin.p; g->seg_len = c->fm_seg_len.p; g->grp_seg_off = c->fm_spk_seg_off.p; g->partial = c->fm_partial.p;
+  g->out_beta = c->fm_beta.p; g->out_k = c->fm_k.p; g->out_G = c->fm_G.p;
+  EventPair ep{};
+  if ((rc = prof_begin(m, m->s_gmm, 1, &ep))) return rc;
+  HIP_TRY(launch());
+  if ((rc = prof_end(m, m->s_gmm, &ep))) return rc;
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  HIP_TRY(hipMemcpy(out_beta, c->fm_beta.p, sizeof(double) * n_groups, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_k, c->fm_k.p, sizeof(double) * nk, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_G, c->fm_G.p, sizeof(double) * nG, hipMemcpyDeviceToHost));
+  return SR_OK;
+}
+}  // extern "C++"
+
 // ---- fMLLR speaker adaptation (fmllr_stats.hip; the estimate itself is host code, fmllr.cpp) ---------------------------------------
 // The checks every statistics call makes before any launch
 static int fmllr_check(sr_model* m, sr_corpus* c, const uint32_t* utt_speaker, uint32_t n_speakers, const double* out_beta,
@@ -2160,7 +2188,7 @@ static int fmllr_check(sr_model* m, sr_corpus* c, const uint32_t* utt_speaker, u
 // speaker; the results to the host
 static int fmllr_statistics(sr_model* m, sr_corpus* c, const EmArgs& e, const uint64_t* d_frame_pair_off, const uint32_t* utt_speaker,
                             uint32_t S, double* out_beta, double* out_k, double* out_G) {
-  const uint32_t D = m->dim, U = c->n_utts, E = D + 1;
+  const uint32_t D = m->dim, U = c->n_utts;
   const uint64_t F = c->n_frames;
   int rc;
   // every speaker's frames in corpus order, cut into segments
@@ -2174,31 +2202,16 @@ static int fmllr_statistics(sr_model* m, sr_corpus* c, const EmArgs& e, const ui
   }
   const srplan::Segments seg(spk_frames.data(), S, fmllr_seg_frames());
   FmllrArgs a{};
-  a.feats = c->feats.p; a.n_frames = F; a.dim = D; a.shape = fmllr_shape(D);
+  a.feats = c->feats.p; a.n_frames = F; a.dim = D; a.g.shape = fmllr_shape(D);
   a.means = m->means.p; a.inv_vars = m->inv_vars.p;
   a.frame_pair_off = d_frame_pair_off; a.pair_dens = e.pair_dens; a.pair_key = e.key_mean; a.pair_w = e.pair_w;
-  a.n_speakers = S; a.n_segs = (uint32_t)seg.begin.size();
-  HIP_TRY(c->fm_fold_a.ensure((size_t)F * a.shape.rows)); HIP_TRY(c->fm_fold_c.ensure((size_t)F * a.shape.rows));
+  HIP_TRY(c->fm_fold_a.ensure((size_t)F * a.g.shape.rows)); HIP_TRY(c->fm_fold_c.ensure((size_t)F * a.g.shape.rows));
   HIP_TRY(c->fm_frame_list.upload(frame_list.data(), F));
-  HIP_TRY(c->fm_seg_begin.upload(seg.begin.data(), seg.begin.size())); HIP_TRY(c->fm_seg_len.upload(seg.len.data(), seg.len.size()));
-  HIP_TRY(c->fm_spk_seg_off.upload(seg.off.data(), seg.off.size()));
-  HIP_TRY(c->fm_partial.ensure((size_t)a.n_segs * a.shape.rows * a.shape.cols));
-  const size_t nk = (size_t)S * D * E, nG = nk * E;
-  HIP_TRY(c->fm_beta.ensure(S)); HIP_TRY(c->fm_k.ensure(nk)); HIP_TRY(c->fm_G.ensure(nG));
-  a.fold_a = c->fm_fold_a.p; a.fold_c = c->fm_fold_c.p; a.frame_list = c->fm_frame_list.p; a.seg_begin = c->fm_seg_begin.p;
-  a.seg_len = c->fm_seg_len.p; a.spk_seg_off = c->fm_spk_seg_off.p; a.partial = c->fm_partial.p;
-  a.out_beta = c->fm_beta.p; a.out_k = c->fm_k.p; a.out_G = c->fm_G.p;
-  EventPair ep{};
-  if ((rc = prof_begin(m, m->s_gmm, 1, &ep))) return rc;
-  HIP_TRY(launch_fmllr_statistics(a, m->s_gmm));
-  if ((rc = prof_end(m, m->s_gmm, &ep))) return rc;
-  HIP_TRY(hipStreamSynchronize(m->s_gmm));
-  HIP_TRY(hipMemcpy(out_beta, c->fm_beta.p, sizeof(double) * S, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_k, c->fm_k.p, sizeof(double) * nk, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_G, c->fm_G.p, sizeof(double) * nG, hipMemcpyDeviceToHost));
+  a.fold_a = c->fm_fold_a.p; a.fold_c = c->fm_fold_c.p; a.frame_list = c->fm_frame_list.p;
+  if ((rc = grouped_statistics(m, c, seg, S, &a.g, [&] { return launch_fmllr_statistics(a, m->s_gmm); }, out_beta, out_k, out_G))) return rc;
   if (m->profiling) {  // per frame: the fold's two rows out and in, the features; the partials out and in
     m->prof.frames += F;
-    m->prof.search_bytes += (double)F * (32.0 * a.shape.rows + 4.0 * D) + 16.0 * (double)a.n_segs * a.shape.rows * a.shape.cols;
+    m->prof.search_bytes += (double)F * (32.0 * a.g.shape.rows + 4.0 * D) + 16.0 * (double)a.g.n_segs * a.g.shape.rows * a.g.shape.cols;
   }
   return SR_OK;
 }
@@ -2301,7 +2314,7 @@ static int mllr_statistics(sr_model* m, sr_corpus* c, const EmArgs& e, const uin
   std::vector<uint32_t> frame_speaker(F);
   for (uint32_t u = 0; u < U; u++) std::fill(frame_speaker.begin() + c->frame_off[u], frame_speaker.begin() + c->frame_off[u + 1], utt_speaker[u]);
   MllrArgs a{};
-  a.feats = c->feats.p; a.dim = D; a.shape = fmllr_shape(D); a.means = m->means.p; a.inv_vars = m->inv_vars.p;
+  a.feats = c->feats.p; a.dim = D; a.g.shape = fmllr_shape(D); a.means = m->means.p; a.inv_vars = m->inv_vars.p;
   a.n_pairs = n_pairs; a.pair_frame = e.pair_frame; a.pair_dens = e.pair_dens; a.pair_key = e.key_mean; a.pair_w = e.pair_w;
   a.n_dens = (uint32_t)m->n_dens; a.n_speakers = S; a.n_classes = R;
   HIP_TRY(c->ml_frame_speaker.upload(frame_speaker.data(), F)); HIP_TRY(c->ml_dens_class.upload(dens_class, m->n_dens));
@@ -2339,25 +2352,11 @@ static int mllr_statistics(sr_model* m, sr_corpus* c, const EmArgs& e, const uin
   if (grp_begin[0] != 0 || grp_begin[n_groups] != a.n_entries) return fail(SR_EINTERNAL, "MLLR statistics: the groups do not cover the entries");
   if (!std::is_sorted(grp_begin.begin(), grp_begin.end())) return fail(SR_EINTERNAL, "MLLR statistics: group bounds out of order");
   const srplan::Segments seg(grp_begin.data(), n_groups, fmllr_seg_frames());
-  a.n_segs = (uint32_t)seg.begin.size();
-  HIP_TRY(c->fm_seg_begin.upload(seg.begin.data(), seg.begin.size())); HIP_TRY(c->fm_seg_len.upload(seg.len.data(), seg.len.size()));
-  HIP_TRY(c->fm_spk_seg_off.upload(seg.off.data(), seg.off.size()));
-  HIP_TRY(c->fm_partial.ensure((size_t)a.n_segs * a.shape.rows * a.shape.cols));
-  const size_t nk = (size_t)n_groups * D * E, nG = nk * E;
-  HIP_TRY(c->fm_beta.ensure(n_groups)); HIP_TRY(c->fm_k.ensure(nk)); HIP_TRY(c->fm_G.ensure(nG));
-  a.seg_begin = c->fm_seg_begin.p; a.seg_len = c->fm_seg_len.p; a.grp_seg_off = c->fm_spk_seg_off.p; a.partial = c->fm_partial.p;
-  a.out_beta = c->fm_beta.p; a.out_k = c->fm_k.p; a.out_G = c->fm_G.p;
-  if ((rc = prof_begin(m, m->s_gmm, 1, &ep))) return rc;
-  HIP_TRY(launch_mllr_statistics(a, m->s_gmm));
-  if ((rc = prof_end(m, m->s_gmm, &ep))) return rc;
-  HIP_TRY(hipStreamSynchronize(m->s_gmm));
-  HIP_TRY(hipMemcpy(out_beta, c->fm_beta.p, sizeof(double) * n_groups, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_k, c->fm_k.p, sizeof(double) * nk, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_G, c->fm_G.p, sizeof(double) * nG, hipMemcpyDeviceToHost));
+  if ((rc = grouped_statistics(m, c, seg, n_groups, &a.g, [&] { return launch_mllr_statistics(a, m->s_gmm); }, out_beta, out_k, out_G))) return rc;
   if (m->profiling) {  // per pair: keys and sort, weight, frame, a feature row; per entry: its sums out and in; the partials out and in
     m->prof.frames += F;
     m->prof.search_bytes += (double)n_pairs * (40.0 + 4.0 * D) + 16.0 * (double)a.n_entries * E +
-                            16.0 * (double)a.n_segs * a.shape.rows * a.shape.cols;
+                            16.0 * (double)a.g.n_segs * a.g.shape.rows * a.g.shape.cols;
   }
   return SR_OK;
 }
