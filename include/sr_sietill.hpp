@@ -1330,6 +1330,100 @@ class Mllt {
   double min_count_;
 };
 
+// ---- LDA with frame splicing (srgpu.h: sr_lda_*, sr_corpus_splice_transform) ------------------------------------------------------
+// Every frame is stacked with `context` neighbours on either side and projected to p dimensions so that the classes -- the aligned
+// states through class_of_state, SR_LDA_SKIP for the ones to leave out (silence) -- are separated as well as a linear map can.  The
+// projected corpus lives with a placeholder model of p dimensions; one first-pass accumulate over it gives the first model of the
+// new space (one density per state), from which EM and then sr::Mllt go on.
+class Lda {
+ public:
+  struct Result {
+    uint32_t E = 0, p = 0;
+    std::vector<double> M;            // [p x (E+1)] = [A b], row-major
+    std::vector<double> eig;          // [E] descending (status 0 only)
+    std::vector<double> count;        // [n_classes] kept frames per class
+    int32_t status = 0;               // sr_lda_estimate's: 0 estimated, 1 too little data, 2 failed (then no corpus and no model)
+    // the placeholder that owns the projected corpus, the projected corpus (sr_corpus_splice_transform) and the model of one first-pass
+    // accumulate over it.  Declared in this order: the corpus goes before its model.
+    std::shared_ptr<sr_model> placeholder;
+    std::shared_ptr<sr_corpus> projected;
+    std::shared_ptr<sr_model> model;
+  };
+
+  struct Config {
+    uint32_t context = 4, p = 40;
+    std::vector<uint32_t> class_of_state;  // [n_states]; empty: the state is the class
+    uint32_t n_classes = 0;                // 0: the number of states
+    bool remove_mean = true;
+    double min_count = 100.0;
+    int device = 0;
+  };
+
+  Lda(Trainer& trainer, MixtureModel& mixtures, Config const& config) : trainer_(trainer), mixtures_(mixtures), config_(config) {}
+
+  // the estimate alone, from statistics (host code, no device)
+  static void estimate(uint32_t E, uint32_t n_classes, std::vector<double> const& count, std::vector<double> const& sum,
+                       std::vector<double> const& scatter, uint32_t p, bool remove_mean, double min_count, Result& r) {
+    if (count.size() < n_classes || sum.size() < (size_t)n_classes * E || scatter.size() < (size_t)E * E)
+      throw std::runtime_error("Lda: statistics too short");
+    r.E = E; r.p = p; r.count = count;
+    r.M.assign((size_t)p * (E + 1), 0.0);
+    r.eig.assign(E, 0.0);
+    check(sr_lda_estimate(E, n_classes, count.data(), sum.data(), scatter.data(), p, remove_mean ? 1 : 0, min_count, r.M.data(), r.eig.data(),
+                          &r.status));
+  }
+
+  // statistics of an alignment given by the caller, estimate, projected corpus, first-pass model
+  static Result from_alignment(sr_model* base, Corpus const& corpus, std::vector<uint16_t> const& states, Config const& cfg) {
+    const size_t n = corpus.get_corpus_size();
+    uint32_t D = 0, n_states = 0;
+    uint64_t n_dens = 0;
+    check(sr_model_info(base, &D, &n_states, &n_dens));
+    if (!cfg.class_of_state.empty() && cfg.class_of_state.size() != n_states) throw std::runtime_error("Lda: one class per state");
+    if (states.size() < corpus.get_total_frame_count()) throw std::runtime_error("Lda: one state per frame");
+    const uint32_t K = cfg.n_classes ? cfg.n_classes : n_states, E = (2 * cfg.context + 1) * D;
+    sr_corpus* c = nullptr;
+    check(sr_corpus_upload(base, corpus.features(), corpus.frame_offsets(), (uint32_t)n, &c));
+    std::shared_ptr<sr_corpus> original(c, sr_corpus_destroy);
+    std::vector<double> count(K), sum((size_t)K * E), scatter((size_t)E * E);
+    check(sr_lda_statistics_corpus(base, c, states.data(), cfg.context, cfg.class_of_state.empty() ? nullptr : cfg.class_of_state.data(), K,
+                                   count.data(), sum.data(), scatter.data()));
+    Result r;
+    estimate(E, K, count, sum, scatter, cfg.p, cfg.remove_mean, cfg.min_count, r);
+    if (r.status != 0) return r;
+    // the placeholder: p dimensions, the alignment's states with one density each
+    std::vector<uint32_t> dens_off(n_states + 1);
+    for (uint32_t s = 0; s <= n_states; s++) dens_off[s] = s;
+    const std::vector<double> zeros((size_t)n_states * cfg.p, 0.0), ones((size_t)n_states * cfg.p, 1.0);
+    sr_model* target = nullptr;
+    check(sr_model_create(cfg.device, cfg.p, n_states, dens_off.data(), zeros.data(), ones.data(), zeros.data(), zeros.data(), 1, &target));
+    r.placeholder.reset(target, sr_model_destroy);
+    sr_corpus* projected = nullptr;
+    check(sr_corpus_splice_transform(base, c, target, cfg.context, r.M.data(), &projected));
+    r.projected.reset(projected, sr_corpus_destroy);
+    check(sr_accumulate_corpus(target, projected, states.data(), 1, 1, nullptr, nullptr, nullptr, nullptr));
+    sr_model* model = nullptr;
+    check(sr_model_create_from_accumulated(target, projected, MixtureModel::NO_POOLING, 1, &model));
+    r.model.reset(model, sr_model_destroy);
+    return r;
+  }
+
+  // re-align with the trainer, then from_alignment
+  Result adapt(Corpus const& corpus) {
+    const uint64_t F = corpus.get_total_frame_count();
+    std::vector<AlignmentItem> alignment;
+    trainer_.realign(corpus, alignment);
+    std::vector<uint16_t> states(std::max<uint64_t>(F, 1));
+    for (uint64_t t = 0; t < F; t++) states[t] = (uint16_t)alignment[t].state;
+    return from_alignment(mixtures_.handle(), corpus, states, config_);
+  }
+
+ private:
+  Trainer& trainer_;
+  MixtureModel& mixtures_;
+  Config config_;
+};
+
 // ---- Teaching::LinearSearch (rwth-asr-0.5/src/Teaching/LinearSearch.hh:9-62, SearchInterface.hh:20-30) -------------
 // Bigram-LM beam search over a linear lexicon, one device pass per corpus.  The toolkit wires lexicon, language model
 // and transition model through Speech::ModelCombination (LinearSearch.cc:462-475); here they are plain arrays:

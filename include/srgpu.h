@@ -504,6 +504,64 @@ SR_API int sr_mllt_statistics_bw_corpus(sr_model* m, sr_corpus* c, const uint16_
 SR_API int sr_mllt_estimate(uint32_t dim, double beta, const double* G, uint32_t n_sweeps, double min_count, double* A /*[D*D] in/out*/,
                             double* out_aux /*[n_sweeps+1], optional*/, double* out_logdet /*optional*/, int32_t* out_status);
 
+/* ---- LDA with frame splicing: the step the LDA + MLLT + fMLLR pipeline starts with -----------------------------------------------
+ * A frame is stacked with its `context` neighbours on either side and the stack is projected to p dimensions so that the classes
+ * (usually the aligned states, silence left out) are separated as well as a linear map can.  With D = m's dimension, c = context,
+ * E = (2c + 1) D, the spliced vector of frame t in an utterance whose frames are [a, b) is
+ *   z_t[(o + c) D + j] = (double) x[min(max(t + o, a), b - 1)][j]          o = -c .. c, j < D
+ * (edge frames repeated; a one-frame utterance splices 2c + 1 copies of its frame).  It is never stored: the kernels gather it from
+ * the resident float corpus.
+ *
+ * Statistics.  The class of frame t is class_of_state[states[t]], or states[t] itself when class_of_state is NULL; a frame of class
+ * SR_LDA_SKIP is left out of everything.  The kept frames, in corpus order, are the items:
+ *   out_count[k]       = the number of items of class k (exact)
+ *   out_sum[k][j]      = sum z_tj over the items of class k                   [n_classes x E]
+ *   out_scatter[j][k]  = sum z_tj z_tk over all items                         [E x E], full storage, both triangles written from one
+ *                                                                              sum: exactly symmetric
+ * Both factors of a product are floats widened to double, so every product is exact in FP64 and only the additions round.
+ * Summation order, fixed by the item order alone: the items are cut into segments of 1024; within a segment one chain of
+ * v_mfma_f64_16x16x4_f64 accumulations per output, items ascending; then the segments' partial sums, ascending.  The class sums do
+ * the same over a class's own items (a stable grouping by class keeps them in corpus order), with plain FP64 additions within a
+ * segment.  No atomics: two identical calls return identical bits.  A class without items, and a call without kept frames, gives
+ * zeros; statistics of corpus shards add up.
+ * Limits: E <= 512 (SR_ELIMIT); D itself may be anything a model allows (the statistic never touches the model's tables).  Memory:
+ * a segment's partial sums are the (P (P + 1) / 2) blocks of 64 x 64 doubles of the upper triangle, P = E / 64 rounded up (0.7 MB at
+ * E = 351); they live in a workspace of SRGPU_LDA_MB MiB (default 256, read when the model is made), and when the segments do not fit,
+ * the call runs in rounds of consecutive segments whose reduction continues the same chain of additions: the result's bits do not
+ * depend on the workspace.  A round holds at least one segment (at most 1.2 MB), however small the variable.
+ * Errors, all before any launch and with the outputs untouched: SR_EINVAL for a NULL output, n_classes == 0, a state >= n_states, a
+ * class that is neither < n_classes nor SR_LDA_SKIP; SR_ELIMIT for E > 512, for outputs beyond a quarter of the free device
+ * memory and for n_classes x (E / 256 rounded up) beyond 2^31 - 1; otherwise the errors of any corpus call (a corpus of another model). */
+#define SR_LDA_SKIP 0xFFFFFFFFu
+SR_API int sr_lda_statistics_corpus(sr_model* m, sr_corpus* c, const uint16_t* states, uint32_t context,
+                                    const uint32_t* class_of_state /*[n_states] or NULL = identity*/, uint32_t n_classes,
+                                    double* out_count /*[n_classes]*/, double* out_sum /*[n_classes x E]*/, double* out_scatter /*[E x E]*/);
+
+/* The estimate (host code, no device).  N = sum count; mu_k = sum_k / count_k over the classes with count > 0; mu = (sum of all
+ * sums) / N;  W = (scatter - sum_k count_k mu_k mu_k^T) / N;  B = sum_k count_k mu_k mu_k^T / N - mu mu^T.  With the Cholesky
+ * factor W = L L^T and the symmetric eigendecomposition of L^-1 B L^-T (Householder tridiagonalisation, implicit QR), eigenvalues
+ * descending into out_eig[E] (optional), A = the first p eigenvectors, as rows, times L^-1; every row's sign makes its entry of
+ * largest magnitude positive (the first such entry on a tie).  M = [A b] (p x (E+1), row-major): b_i = -(sum_j A_ij mu_j, j
+ * ascending) with remove_mean, else 0.  The result satisfies A W A^T = I_p and A B A^T = diag(eig[0 .. p-1]).  Rows beyond the rank
+ * of B (classes - 1) and rows of equal eigenvalues are one choice among many.
+ * *out_status: 0 estimated; 1 N < min_count or fewer than two classes with frames; 2 W not positive definite (fewer frames than E,
+ * for one) or something non-finite.  With status 1 or 2 M is left as given, bit for bit, and out_eig is not written.
+ * SR_EINVAL for E == 0, p == 0 or p > E, n_classes == 0, a NULL input, M or out_status, min_count negative or NaN. */
+SR_API int sr_lda_estimate(uint32_t E, uint32_t n_classes, const double* count, const double* sum, const double* scatter, uint32_t p,
+                           int remove_mean, double min_count, double* M /*[p x (E+1)] in/out*/, double* out_eig /*[E], optional*/,
+                           int32_t* out_status);
+
+/* The projected corpus: a new resident corpus of `target` -- any model of dimension p on m's device -- with c's frame offsets whose
+ * row t, column i is (float) acc, acc starting at M[i][E] and taking acc = acc + M[i][n] * z_tn for n ascending in FP64, no fused
+ * multiply-add (the loop is the specification, as for sr_corpus_transform).  A placeholder model from sr_model_create (p dimensions,
+ * the states of the alignment with one density each, any finite tables) is enough to hold the corpus for a first-pass
+ * sr_accumulate_corpus and sr_model_create_from_accumulated, which give the first model of the projected space.  `c` stays valid
+ * (an asynchronous upload of it is waited for first); *out is accepted by every entry point that takes a corpus of `target`, allocates
+ * its own buffers like sr_corpus_transform's result, is destroyed with sr_corpus_destroy, and must be destroyed before `target`.
+ * SR_EINVAL for a NULL M, out or target and a target on another device; SR_ELIMIT for E > 512. */
+SR_API int sr_corpus_splice_transform(sr_model* m, sr_corpus* c, sr_model* target, uint32_t context, const double* M /*[p x (E+1)]*/,
+                                      sr_corpus** out);
+
 /* ---- word posteriors and confidences: forward-backward over the recognition network --------------------------------
  * The network sr_recognize_corpus searches (Recognizer.cpp:103-232: the start hypothesis at word 0 position 0, in-word 0-1-2 jumps
  * with the penalty keyed on the DESTINATION state, every word end entering every word at position 0 or 1 with the word penalty --

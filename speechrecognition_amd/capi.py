@@ -22,6 +22,7 @@ SEARCH_SLOT_KERNEL = 2
 BIGRAM_DENSE_STATES = 1
 BIGRAM_GLOBAL_STATES = 2
 SR_ECORRUPT = -7
+LDA_SKIP = 0xFFFFFFFF  # SR_LDA_SKIP: the class of a frame the LDA statistics leave out
 SR_ABI_VERSION = 4
 
 # every symbol include/srgpu.h declares
@@ -38,6 +39,7 @@ SYMBOLS = [
     "sr_fmllr_statistics_corpus", "sr_fmllr_statistics_bw_corpus", "sr_fmllr_estimate", "sr_corpus_transform",
     "sr_mllr_statistics_corpus", "sr_mllr_statistics_bw_corpus", "sr_mllr_estimate", "sr_model_transform_means",
     "sr_mllt_statistics_corpus", "sr_mllt_statistics_bw_corpus", "sr_mllt_estimate",
+    "sr_lda_statistics_corpus", "sr_lda_estimate", "sr_corpus_splice_transform",
     "sr_bigram_create", "sr_bigram_destroy", "sr_bigram_describe", "sr_recognize_bigram_corpus",
     "sr_bigram_word_posteriors_corpus", "sr_recognize_bigram_confidence_corpus",
     "sr_bigram_occupancies_corpus", "sr_bigram_mmi_statistics_corpus",
@@ -141,6 +143,9 @@ def lib():
         L.sr_mllt_statistics_corpus.argtypes = [vp, vp, vp, i32, vp, vp]
         L.sr_mllt_statistics_bw_corpus.argtypes = [vp, vp, vp, vp, C.POINTER(dbl * 3), C.c_uint16, i32, dbl, i32, vp, vp, vp]
         L.sr_mllt_estimate.argtypes = [u32, dbl, vp, u32, dbl, vp, vp, vp, vp]
+        L.sr_lda_statistics_corpus.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp, vp]
+        L.sr_lda_estimate.argtypes = [u32, u32, vp, vp, vp, u32, i32, dbl, vp, vp, vp]
+        L.sr_corpus_splice_transform.argtypes = [vp, vp, vp, u32, vp, C.POINTER(vp)]
         L.sr_word_posteriors_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, vp]
         L.sr_recognize_confidence_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, vp, vp, vp, vp, vp]
         L.sr_net_occupancies_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, vp, vp, vp]
@@ -728,6 +733,35 @@ class Corpus:
         _check(lib().sr_corpus_transform(self.model.h, self.h, _ptr(spk), W.shape[0], _ptr(W), C.byref(out.h)))
         return out
 
+    def lda_statistics(self, states, context, class_of_state=None, n_classes=None):
+        """LDA statistics of the frames spliced with `context` neighbours on either side (sr_lda_statistics_corpus) ->
+        (count f64[K], sum f64[K, E], scatter f64[E, E]), E = (2 context + 1) D.  class_of_state u32[n_states] maps the aligned
+        states to classes (LDA_SKIP: the frame is left out); None: the state is the class.  n_classes defaults to the number of
+        states, or to the largest class of the map + 1."""
+        states = np.ascontiguousarray(states, dtype=np.uint16)
+        cls = None if class_of_state is None else np.ascontiguousarray(class_of_state, dtype=np.uint32)
+        if n_classes is None:
+            kept = None if cls is None else cls[cls != LDA_SKIP]
+            n_classes = self.model.n_states if cls is None else (int(kept.max()) + 1 if len(kept) else 1)
+        assert cls is None or len(cls) == self.model.n_states
+        E = (2 * int(context) + 1) * self.model.dim
+        count, total, scatter = np.zeros(n_classes), np.zeros((n_classes, E)), np.zeros((E, E))
+        _check(lib().sr_lda_statistics_corpus(self.model.h, self.h, _ptr(states), int(context), _ptr(cls), int(n_classes), _ptr(count),
+                                              _ptr(total), _ptr(scatter)))
+        return count, total, scatter
+
+    def splice_transform(self, target, context, M):
+        """The projected corpus y = M (z, 1) of the spliced frames, M f64[p, E+1], as a resident corpus of the Model `target` of
+        dimension p (sr_corpus_splice_transform) -> Corpus; close it before `target`."""
+        M = np.ascontiguousarray(M, dtype=np.float64)
+        E = (2 * int(context) + 1) * self.model.dim
+        assert M.shape == (target.dim, E + 1)
+        out = Corpus.__new__(Corpus)
+        out.model, out.frame_off, out.n_utts, out.n_frames = target, self.frame_off, self.n_utts, self.n_frames
+        out.h = C.c_void_p()
+        _check(lib().sr_corpus_splice_transform(self.model.h, self.h, target.h, int(context), _ptr(M), C.byref(out.h)))
+        return out
+
     def word_posteriors(self, lexicon, word_penalty, scale=1.0, kernel=GMM_PREFILTER, floor=0.0, max_items=8):
         """Forward-backward over the recognition network (sr_word_posteriors_corpus) -> (cost f64[n_utts] = -(1/scale) log P(X),
         count u16[total_frames], word u32[total_frames, max_items], weight f64[total_frames, max_items]): per frame the words with
@@ -1046,6 +1080,23 @@ def mllt_estimate(beta, G, n_sweeps=10, min_count=0.0, A=None):
     status = np.zeros(1, dtype=np.int32)
     _check(lib().sr_mllt_estimate(D, float(beta), _ptr(G), int(n_sweeps), float(min_count), _ptr(A), _ptr(aux), _ptr(logdet), _ptr(status)))
     return A, aux, float(logdet[0]), int(status[0])
+
+
+def lda_estimate(count, sum, scatter, p, remove_mean=False, min_count=0.0, M=None):
+    """The LDA projection from Corpus.lda_statistics' output (sr_lda_estimate; host code) -> (M f64[p, E+1] = [A b],
+    eig f64[E] descending, status int).  With status 1 or 2 M is the one given (default: zeros) and eig is NaN."""
+    count = np.ascontiguousarray(count, dtype=np.float64)
+    total = np.ascontiguousarray(sum, dtype=np.float64)
+    scatter = np.ascontiguousarray(scatter, dtype=np.float64)
+    K, E = total.shape
+    assert count.shape == (K,) and scatter.shape == (E, E)
+    M = np.array(np.zeros((int(p), E + 1)) if M is None else M, dtype=np.float64, order="C")
+    assert M.shape == (int(p), E + 1)
+    eig = np.full(E, np.nan)
+    status = np.zeros(1, dtype=np.int32)
+    _check(lib().sr_lda_estimate(E, K, _ptr(count), _ptr(total), _ptr(scatter), int(p), int(bool(remove_mean)), float(min_count), _ptr(M),
+                                 _ptr(eig), _ptr(status)))
+    return M, eig, int(status[0])
 
 
 def mllt_affine(A):

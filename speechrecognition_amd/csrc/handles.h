@@ -131,6 +131,7 @@ struct sr_model {
   uint32_t defer_cap_limit = 0;            // most entries per segment, 0: no limit (SRGPU_DEFER_CAP, tests: full segments)
   size_t fb_budget = (size_t)1 << 30;      // most bytes for the forward-backward trellises of one launch (SRGPU_FB_MB)
   size_t mllt_budget = (size_t)256 << 20;  // most bytes for the segment partials of one round of the MLLT statistics (SRGPU_MLLT_MB)
+  size_t lda_budget = (size_t)256 << 20;   // likewise for the segment partials of the LDA scatter (SRGPU_LDA_MB)
   // profiling
   bool profiling = false;
   std::vector<EventPair> events;
@@ -214,6 +215,10 @@ struct sr_corpus {
   DevBuf<uint32_t> ml_frame_speaker, ml_dens_class, ml_key, ml_run_key, ml_run_len, ml_run_begin, ml_n_runs, ml_gkey, ml_gkey_sorted,
       ml_ent_order, ml_grp_begin, ml_ent_dens;
   DevBuf<double> ml_ent_occ, ml_ent_x;
+  // LDA statistics and projection (lda_stats.hip; the scatter's segment partials are fm_partial): the frames' utterance bounds, the kept
+  // frames in corpus order and grouped by class, the classes' segments, their partial sums, the results
+  DevBuf<uint32_t> lda_span, lda_items, lda_class_items, lda_cseg_begin, lda_cseg_len, lda_class_seg_off;
+  DevBuf<double> lda_cpartial, lda_sum, lda_scatter;
 };
 
 struct sr_lexicon {

@@ -780,4 +780,36 @@ struct MlltArgs {
 };
 hipError_t launch_mllt_round(const MlltArgs& a, hipStream_t stream);  // contraction and reduction of one round
 
+// ---- LDA with frame splicing: the scatter and class sums of the spliced frames, the projected corpus (lda_stats.hip) -------------------
+// z_t[(o + c) D + j] = (double) x[clamp(t + o, a, b - 1)][j], o = -c .. c, [a, b) = frame_span[2t], frame_span[2t + 1] the frames of
+// t's utterance; E = (2c + 1) D <= lda_max_e().  The items (kept frames, corpus order) are cut into segments of lda_seg_items(); a
+// segment's partial scatter is stored as the lda_pairs(E) blocks (I <= J) of lda_block() x lda_block() doubles of the upper triangle.
+uint32_t lda_seg_items();
+uint32_t lda_max_e();
+uint32_t lda_block();
+inline uint32_t lda_panels(uint32_t E) { return (E + lda_block() - 1) / lda_block(); }
+inline uint32_t lda_pairs(uint32_t E) { return lda_panels(E) * (lda_panels(E) + 1) / 2; }
+struct LdaArgs {
+  const float* feats;
+  const uint32_t* frame_span;   // [2 x n_frames]
+  uint32_t dim, context, E;
+  // the scatter: items [3 x n_items] = (frame, a, b) of the kept frames in corpus order, [a, b) the frame's utterance.  One round: segments [seg0, seg0 + n_segs) into partial; the
+  // reduction adds them, ascending, onto the running sums in out_scatter (seg0 == 0: onto 0)
+  const uint32_t* items; uint64_t n_items;
+  uint32_t seg0, n_segs;
+  double* partial;              // workspace [n_segs][lda_pairs(E)][lda_block()][lda_block()]
+  double* out_scatter;          // device [E x E]
+  // the class sums: class_items = the kept frames grouped stably by class; segment g = positions [cseg_begin[g], + cseg_len[g]) of one
+  // class, class k owns segments [class_seg_off[k], class_seg_off[k + 1])
+  const uint32_t* class_items; const uint32_t* cseg_begin; const uint32_t* cseg_len; const uint32_t* class_seg_off;
+  uint32_t n_csegs, n_classes;
+  double* cpartial;             // workspace [n_csegs][E]
+  double* out_sum;              // device [n_classes x E]
+};
+hipError_t launch_lda_round(const LdaArgs& a, hipStream_t stream);       // scatter and reduction of one round
+hipError_t launch_lda_class_sums(const LdaArgs& a, hipStream_t stream);  // segment sums and their reduction
+// out[t][i] = (float) acc, acc starting at M[i][E] and taking acc = acc + M[i][n] * z_t[n] for n ascending; M [p x (E + 1)]
+hipError_t launch_lda_project(const float* feats, const uint32_t* frame_span, uint64_t n_frames, uint32_t dim, uint32_t context,
+                              const double* M, uint32_t p, float* out, hipStream_t stream);
+
 }  // namespace srgpu

@@ -816,6 +816,7 @@ int model_shell(int device, uint32_t dim, uint32_t n_states, const uint32_t* den
   if (const char* e = getenv("SRGPU_DEFER_MB")) m->defer_budget = (size_t)strtoull(e, nullptr, 10) << 20;
   if (const char* e = getenv("SRGPU_FB_MB")) m->fb_budget = std::max<size_t>(1, (size_t)strtoull(e, nullptr, 10)) << 20;
   if (const char* e = getenv("SRGPU_MLLT_MB")) m->mllt_budget = std::max<size_t>(1, (size_t)strtoull(e, nullptr, 10)) << 20;
+  if (const char* e = getenv("SRGPU_LDA_MB")) m->lda_budget = std::max<size_t>(1, (size_t)strtoull(e, nullptr, 10)) << 20;
   if (const char* e = getenv("SRGPU_DEFER_CAP")) m->defer_cap_limit = std::max(1u, (uint32_t)strtoul(e, nullptr, 10));  // (tests: full segments)
   *out = own.release();
   return SR_OK;
@@ -2517,6 +2518,152 @@ int sr_mllt_statistics_bw_corpus(sr_model* m, sr_corpus* c, const uint16_t* auto
   EmArgs e{};
   if ((rc = adapt_pairs_bw(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, max_approx, out_cost, &e))) return rc;
   return mllt_statistics(m, c, e, out_beta, out_G);
+  });
+}
+
+// ---- LDA with frame splicing (lda_stats.hip; the estimate itself is host code, lda.cpp) ---------------------------------------------
+// [a, b) of every frame's utterance, for the clamping of the spliced vector
+static int lda_upload_spans(sr_corpus* c) {
+  std::vector<uint32_t> span(2 * (size_t)c->n_frames);
+  for (uint32_t u = 0; u < c->n_utts; u++)
+    for (uint64_t f = c->frame_off[u]; f < c->frame_off[u + 1]; f++) { span[2 * f] = (uint32_t)c->frame_off[u]; span[2 * f + 1] = (uint32_t)c->frame_off[u + 1]; }
+  HIP_TRY(c->lda_span.upload(span.data(), span.size()));
+  return SR_OK;
+}
+
+int sr_lda_statistics_corpus(sr_model* m, sr_corpus* c, const uint16_t* states, uint32_t context, const uint32_t* class_of_state,
+                             uint32_t n_classes, double* out_count, double* out_sum, double* out_scatter) {
+  return guarded(__func__, [&]() -> int {
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  if (!out_count || !out_sum || !out_scatter) return fail(SR_EINVAL, "null output");
+  if (n_classes == 0) return fail(SR_EINVAL, "n_classes is 0");
+  const uint32_t D = m->dim;
+  const uint64_t F = c->n_frames, E64 = (2 * (uint64_t)context + 1) * D;
+  if (E64 > lda_max_e()) return fail(SR_ELIMIT, "spliced dimension (2 x %u + 1) x %u exceeds %u (LDA statistics)", context, D, lda_max_e());
+  const uint32_t E = (uint32_t)E64;
+  if (F >= 0xFFFFFFFFull) return fail(SR_ELIMIT, "%llu frames do not fit the 32-bit frame lists", (unsigned long long)F);
+  if (F && !states) return fail(SR_EINVAL, "states is null");
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  const double out_bytes = 8.0 * ((double)n_classes * E + (double)E * E);
+  if (out_bytes > (double)free_b / 4)
+    return fail(SR_ELIMIT, "the statistics of %u classes (%.0f bytes) exceed a quarter of the free device memory (%llu bytes)", n_classes,
+                out_bytes, (unsigned long long)free_b);
+  if ((uint64_t)n_classes * ((E + 255) / 256) > 0x7FFFFFFFull)  // lda_class_reduce_kernel's grid
+    return fail(SR_ELIMIT, "%u classes x %u columns exceed the class sums' launch grid", n_classes, E);
+  if (class_of_state)
+    for (uint32_t s = 0; s < m->n_states; s++)
+      if (class_of_state[s] >= n_classes && class_of_state[s] != SR_LDA_SKIP)
+        return fail(SR_EINVAL, "state %u: class %u is neither < n_classes %u nor SR_LDA_SKIP", s, class_of_state[s], n_classes);
+  std::vector<uint32_t> bounds((size_t)n_classes + 1, 0), items;
+  items.reserve(F);
+  for (uint64_t t = 0; t < F; t++) {
+    if (states[t] >= m->n_states) return fail(SR_EINVAL, "frame %llu: state %u >= n_states %u", (unsigned long long)t, states[t], m->n_states);
+    const uint32_t k = class_of_state ? class_of_state[states[t]] : states[t];
+    if (k == SR_LDA_SKIP) continue;
+    if (k >= n_classes) return fail(SR_EINVAL, "frame %llu: class %u >= n_classes %u", (unsigned long long)t, k, n_classes);
+    bounds[k + 1]++;
+    items.push_back((uint32_t)t);
+  }
+  const size_t seg_doubles = (size_t)lda_pairs(E) * lda_block() * lda_block();
+  // ---- the checks are done: the outputs are written from here on
+  const uint64_t n_items = items.size();
+  for (uint32_t k = 0; k < n_classes; k++) out_count[k] = (double)bounds[k + 1];
+  if (n_items == 0) {  // no frame, or none kept
+    std::fill(out_sum, out_sum + (size_t)n_classes * E, 0.0);
+    std::fill(out_scatter, out_scatter + (size_t)E * E, 0.0);
+    return SR_OK;
+  }
+  // the kept frames grouped stably by class, every class cut into segments
+  for (uint32_t k = 0; k < n_classes; k++) bounds[k + 1] += bounds[k];
+  std::vector<uint32_t> class_items(n_items);
+  {
+    std::vector<uint32_t> fill(bounds.begin(), bounds.end() - 1);
+    for (uint32_t t : items) class_items[fill[class_of_state ? class_of_state[states[t]] : states[t]]++] = t;
+  }
+  const srplan::Segments seg(bounds.data(), n_classes, lda_seg_items());
+  if ((rc = srhost::corpus_ready(c, 0, F, m->s_gmm))) return rc;  // an asynchronous upload of c: wait for all of it
+  if ((rc = lda_upload_spans(c))) return rc;
+  LdaArgs a{};
+  a.feats = c->feats.p; a.frame_span = c->lda_span.p; a.dim = D; a.context = context; a.E = E;
+  {
+    std::vector<uint32_t> triples(3 * (size_t)n_items);  // (frame, first and end frame of its utterance)
+    uint32_t u = 0;
+    for (size_t i = 0; i < n_items; i++) {
+      while (c->frame_off[u + 1] <= items[i]) u++;
+      triples[3 * i] = items[i]; triples[3 * i + 1] = (uint32_t)c->frame_off[u]; triples[3 * i + 2] = (uint32_t)c->frame_off[u + 1];
+    }
+    HIP_TRY(c->lda_items.upload(triples.data(), triples.size()));
+  }
+  HIP_TRY(c->lda_class_items.upload(class_items.data(), n_items));
+  HIP_TRY(c->lda_cseg_begin.upload(seg.begin.data(), seg.begin.size())); HIP_TRY(c->lda_cseg_len.upload(seg.len.data(), seg.len.size()));
+  HIP_TRY(c->lda_class_seg_off.upload(seg.off.data(), seg.off.size()));
+  a.items = c->lda_items.p; a.n_items = n_items; a.class_items = c->lda_class_items.p;
+  a.cseg_begin = c->lda_cseg_begin.p; a.cseg_len = c->lda_cseg_len.p; a.class_seg_off = c->lda_class_seg_off.p;
+  a.n_csegs = (uint32_t)seg.begin.size(); a.n_classes = n_classes;
+  const uint64_t n_segs = (n_items + lda_seg_items() - 1) / lda_seg_items();
+  // (at least one segment a round: at most 36 blocks of 32 KiB, whatever SRGPU_LDA_MB says)
+  const uint64_t per_round = std::min<uint64_t>(n_segs, std::max<uint64_t>(1, m->lda_budget / (sizeof(double) * seg_doubles)));
+  HIP_TRY(c->fm_partial.ensure((size_t)per_round * seg_doubles));
+  HIP_TRY(c->lda_cpartial.ensure((size_t)a.n_csegs * E));
+  HIP_TRY(c->lda_sum.ensure((size_t)n_classes * E)); HIP_TRY(c->lda_scatter.ensure((size_t)E * E));
+  a.partial = c->fm_partial.p; a.cpartial = c->lda_cpartial.p; a.out_sum = c->lda_sum.p; a.out_scatter = c->lda_scatter.p;
+  EventPair ep{};
+  if ((rc = prof_begin(m, m->s_gmm, 1, &ep))) return rc;
+  HIP_TRY(launch_lda_class_sums(a, m->s_gmm));
+  for (uint64_t s0 = 0; s0 < n_segs; s0 += per_round) {
+    a.seg0 = (uint32_t)s0; a.n_segs = (uint32_t)std::min<uint64_t>(per_round, n_segs - s0);
+    HIP_TRY(launch_lda_round(a, m->s_gmm));
+  }
+  if ((rc = prof_end(m, m->s_gmm, &ep))) return rc;
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  HIP_TRY(hipMemcpy(out_sum, c->lda_sum.p, sizeof(double) * n_classes * E, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_scatter, c->lda_scatter.p, sizeof(double) * E * E, hipMemcpyDeviceToHost));
+  if (m->profiling) {  // per kept frame: its spliced row for the class sums and once per panel pair's side; the partials out and in
+    m->prof.frames += F;
+    m->prof.search_bytes += (double)n_items * 4.0 * E * (1.0 + lda_panels(E)) + 16.0 * (double)n_segs * seg_doubles;
+  }
+  return SR_OK;
+  });
+}
+
+int sr_corpus_splice_transform(sr_model* m, sr_corpus* c, sr_model* target, uint32_t context, const double* M, sr_corpus** out) {
+  return guarded(__func__, [&]() -> int {
+  if (!out) return fail(SR_EINVAL, "out is null");
+  *out = nullptr;
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  if (!target) return fail(SR_EINVAL, "target is null");
+  if (!M) return fail(SR_EINVAL, "M is null");
+  if (target->device != m->device) return fail(SR_EINVAL, "the target model is on device %d, the corpus on device %d", target->device, m->device);
+  const uint32_t D = m->dim, p = target->dim;
+  const uint64_t F = c->n_frames, E64 = (2 * (uint64_t)context + 1) * D;
+  if (E64 > lda_max_e()) return fail(SR_ELIMIT, "spliced dimension (2 x %u + 1) x %u exceeds %u (splice transform)", context, D, lda_max_e());
+  if (F >= 0xFFFFFFFFull) return fail(SR_ELIMIT, "%llu frames do not fit the 32-bit frame lists", (unsigned long long)F);
+  const uint32_t E = (uint32_t)E64;
+  if ((rc = srhost::corpus_ready(c, 0, F, m->s_gmm))) return rc;  // an asynchronous upload of c: wait for all of it
+  if ((rc = lda_upload_spans(c))) return rc;
+  sr_corpus* t = new sr_corpus();
+  std::unique_ptr<sr_corpus, int (*)(sr_corpus*)> own(t, sr_corpus_destroy);
+  t->model = target; t->n_utts = c->n_utts; t->n_frames = F;
+  srhost::corpus_register(t);
+  t->frame_off = c->frame_off;
+  HIP_TRY(t->feats.ensure((size_t)F * p + 64));
+  HIP_TRY(t->d_frame_off.upload(t->frame_off.data(), t->frame_off.size()));
+  DevBuf<double> d_M;
+  HIP_TRY(d_M.upload(M, (size_t)p * (E + 1)));
+  EventPair ep{};
+  if ((rc = prof_begin(m, m->s_gmm, 1, &ep))) return rc;
+  HIP_TRY(launch_lda_project(c->feats.p, c->lda_span.p, F, D, context, d_M.p, p, t->feats.p, m->s_gmm));
+  if ((rc = prof_end(m, m->s_gmm, &ep))) return rc;
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  if (m->profiling) {  // a row in, a row out
+    m->prof.frames += F;
+    m->prof.search_bytes += 4.0 * (double)F * (D + p);
+  }
+  *out = own.release();
+  return SR_OK;
   });
 }
 
