@@ -974,6 +974,16 @@ SR_API int sr_probe_fp16_denormals(int device, int* preserved);
  * length the model uses). */
 SR_API int sr_probe_fp16_accumulation(int device, int* within_model, double* worst_ratio);
 
+/* Test hook: the candidate masks the fp16 prefilter alone writes for `feats` ([n_frames x dim], host), by one of its two routes --
+ * 0: frames stationary, the model staged through LDS; 1: a state group stationary in registers, the frames' operands streamed (models
+ * of dimension <= 46; wider ones run the staged kernel on either route).  Both routes write the same bits; SRGPU_PREFILTER=staged|
+ * stationary (read when a model is created; default stationary) picks the one the scoring calls take.  masks: [n_groups][n_frames][4]
+ * 32-bit words, one per state slot; masks == NULL only reports n_groups.  SR_EINVAL for a model the prefilter does not score. */
+SR_API int sr_prefilter_masks(sr_model* m, const float* feats, uint64_t n_frames, int route, uint32_t* n_groups, uint32_t* masks,
+                              uint64_t cap_words);
+/* The stationary route cuts a launch's frames into ranges; a launch of more than *frames frames has at least two (tests straddle one). */
+SR_API int sr_prefilter_range_frames(uint32_t* frames);
+
 /* ---- measurement --------------------------------------------------------------------------------
  * When enabled, every kernel launch of this model handle is bracketed by HIP events on the
  * launch stream; sr_profile_read() synchronises and returns accumulated device times. */

@@ -48,7 +48,7 @@ SYMBOLS = [
     "sr_stream_open", "sr_stream_begin", "sr_stream_push", "sr_stream_partial", "sr_stream_end", "sr_stream_destroy",
     "sr_bigram_stream_open", "sr_bigram_stream_begin", "sr_bigram_stream_push", "sr_bigram_stream_partial", "sr_bigram_stream_end",
     "sr_bigram_stream_destroy",
-    "sr_probe_fp16_denormals", "sr_probe_fp16_accumulation",
+    "sr_probe_fp16_denormals", "sr_probe_fp16_accumulation", "sr_prefilter_masks", "sr_prefilter_range_frames",
     "sr_profile_enable", "sr_profile_reset", "sr_profile_read",
 ]
 
@@ -57,6 +57,13 @@ class SrError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libsrgpu error {code}: {msg}")
         self.code = code
+
+
+def prefilter_range_frames():
+    """sr_prefilter_range_frames: a stationary-route prefilter launch of more frames than this has at least two frame ranges"""
+    n = C.c_uint32()
+    _check(lib().sr_prefilter_range_frames(C.byref(n)))
+    return n.value
 
 
 def smbr_max_positions():
@@ -182,6 +189,8 @@ def lib():
         L.sr_bigram_stream_destroy.argtypes = [vp]
         L.sr_probe_fp16_denormals.argtypes = [i32, C.POINTER(i32)]
         L.sr_probe_fp16_accumulation.argtypes = [i32, C.POINTER(i32), C.POINTER(dbl)]
+        L.sr_prefilter_masks.argtypes = [vp, vp, u64, i32, C.POINTER(u32), vp, u64]
+        L.sr_prefilter_range_frames.argtypes = [C.POINTER(u32)]
         L.sr_profile_enable.argtypes = [vp, i32]
         L.sr_profile_reset.argtypes = [vp]
         L.sr_profile_read.argtypes = [vp, C.POINTER(Profile)]
@@ -333,6 +342,15 @@ class Model:
         feats = np.ascontiguousarray(feats, dtype=np.float32)
         out = np.empty((feats.shape[0], self.n_states), dtype=np.float64)
         _check(lib().sr_score_frames(self.h, _ptr(feats), feats.shape[0], kernel, _ptr(out)))
+        return out
+
+    def prefilter_masks(self, feats, route):
+        """sr_prefilter_masks (test hook): the prefilter's candidate masks [group][frame][4 state slots], route 0 staged / 1 stationary."""
+        feats = np.ascontiguousarray(feats, dtype=np.float32)
+        n_groups = C.c_uint32()
+        _check(lib().sr_prefilter_masks(self.h, None, feats.shape[0], route, C.byref(n_groups), None, 0))
+        out = np.empty((n_groups.value, feats.shape[0], 4), dtype=np.uint32)
+        _check(lib().sr_prefilter_masks(self.h, _ptr(feats), feats.shape[0], route, C.byref(n_groups), _ptr(out), out.size))
         return out
 
     def upload(self, feats, frame_off, asynchronous=False):

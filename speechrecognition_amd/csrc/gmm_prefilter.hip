@@ -270,6 +270,174 @@ __global__ __launch_bounds__(kPWaves * 64, (NB <= 2 ? 3 : 2)) void gmm_prefilter
   }
 }
 
+// ---- kernel P, group-stationary ------------------------------------------------------------------------------------
+// The reverse orientation of the kernel above: a wave keeps ONE group's A fragments in registers (8 blocks x KS32 k-steps x 4
+// registers: 96 at K = 96) and streams the frames past them, kSNB 16-frame blocks per step.  The frames' operands -- what the
+// kernel above rebuilds in every workgroup -- are built once per launch by gmm_prefilter_operands_kernel and arrive as
+// ready-made B fragments, one coalesced 16-byte load per lane, block and k-step, fetched one step ahead.  No LDS, no LDS-DMA,
+// no barrier.  Per accumulator the MFMA chain is the same (k-steps in order, from zero) and the epilogue is the same code, so
+// the masks are the same bits.
+#ifndef SR_PS_PIN
+#define SR_PS_PIN 1   // 1: the next step's loads are issued before the step's first MFMA (a scheduling fence); 0: where the compiler sinks them, late in the MFMAs (P +0.17 ms)
+#endif
+#if SR_PS_PIN
+#define SR_PS_PIN_FETCH __builtin_amdgcn_sched_barrier(0)
+#else
+#define SR_PS_PIN_FETCH (void)0
+#endif
+static constexpr int kSNB = 2;                 // blocks per step: 96 (A) + 64 (accumulators) + 2 x 24 (B, two steps) registers
+static constexpr int kSRangeFrames = 2048;     // shortest frame range aimed at: the group's 24 KB against 128 blocks x 3 KB
+
+// B fragments and norms of one 16-frame block per wave: the arithmetic of the staged kernel's prologue, operation for
+// operation (this file is compiled without contraction), with the features read straight from their rows.
+template <int KS32>
+__global__ __launch_bounds__(kPWaves * 64) void gmm_prefilter_operands_kernel(const float* feats, uint64_t n_frames, uint32_t dim,
+                                                                              uint64_t n_blocks, uint4* bfrag, float2* bnorm) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t g = lane >> 4, c = lane & 15;
+  const uint64_t blk = (uint64_t)blockIdx.x * kPWaves + wave;
+  if (blk >= n_blocks) return;  // (wave-uniform)
+  const uint64_t f = blk * 16 + c;
+  const bool valid = f < n_frames;
+  const float* xr = feats + (valid ? f : 0u) * dim;
+  float n2 = 0.0f, e2 = 0.0f;
+#pragma unroll
+  for (int ks = 0; ks < KS32; ks++) {
+    _Float16 v[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const uint32_t k = 32u * ks + 8u * g + j, d = k >> 1;
+      const float xf = (valid && d < dim) ? xr[d < dim ? d : 0u] : 0.0f;
+      const float b = (k & 1u) ? xf : xf * xf;
+      n2 += b * b;
+      _Float16 h = (_Float16)b;
+      const float bh = (float)h;
+      const float e = (k & 1u) ? xf - bh : __builtin_fmaf(xf, xf, -bh);
+      e2 += e * e;
+      if (valid && k >= 2u * dim && k < 2u * dim + 3u) h = (_Float16)1.0f;
+      v[j] = h;
+    }
+    bfrag[(blk * KS32 + ks) * 64 + lane] =
+        make_uint4(pack_f16x2(v[0], v[1]), pack_f16x2(v[2], v[3]), pack_f16x2(v[4], v[5]), pack_f16x2(v[6], v[7]));
+  }
+  n2 += __shfl_xor(n2, 16);
+  n2 += __shfl_xor(n2, 32);
+  e2 += __shfl_xor(e2, 16);
+  e2 += __shfl_xor(e2, 32);
+  const float bn = sqrtf(n2) * 1.0001f;
+  const float dbn = fminf(sqrtf(e2) * 1.0001f, kPfRes16 * bn);
+  if (g == 0) bnorm[f] = make_float2(bn, dbn);  // (frames past the end: zeros, never used for a stored mask)
+}
+
+struct GmmStationaryPlan { uint32_t n_quads, n_ranges, range_frames, per_xcd; };
+
+template <int KS32>
+__global__ __launch_bounds__(kPWaves * 64, 2) void gmm_prefilter_stationary_kernel(GmmPrefilterArgs a, GmmStationaryPlan p) {
+  constexpr int NB = kSNB;
+  constexpr int kGroupBytes = kGroupBlocks * KS32 * 1024;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, c = lane & 15;
+  // work item = (group quad, frame range), quad fastest.  Workgroup ids that share an XCD (id mod 8) take CONSECUTIVE items: the 64
+  // workgroups resident on an XCD sweep the same frame range(s), whose B fragments its L2 then fetches once.
+  const uint32_t item = (blockIdx.x & 7u) * p.per_xcd + (blockIdx.x >> 3);
+  if ((blockIdx.x >> 3) >= p.per_xcd || item >= p.n_quads * p.n_ranges) return;
+  const uint32_t grp = (item % p.n_quads) * kPWaves + wave;
+  if (grp >= a.n_groups) return;  // (the last quad's idle waves; there is no barrier below)
+  const uint64_t f_begin = (uint64_t)(item / p.n_quads) * p.range_frames;
+  if (f_begin >= a.n_frames) return;  // (never: the plan's last range is not empty)
+  const uint64_t f_end = f_begin + p.range_frames < a.n_frames ? f_begin + p.range_frames : a.n_frames;
+  const uint32_t n_steps = (uint32_t)((f_end - f_begin + 16 * NB - 1) / (16 * NB));  // (ranges start on step boundaries)
+
+  f16x8 af[kGroupBlocks][KS32];
+  {
+    const uint4* src = reinterpret_cast<const uint4*>(a.apack + (uint64_t)grp * kGroupBytes) + lane;
+#pragma unroll
+    for (int j = 0; j < kGroupBlocks; j++)
+#pragma unroll
+      for (int ks = 0; ks < KS32; ks++) af[j][ks] = __builtin_bit_cast(f16x8, src[(j * KS32 + ks) * 64]);
+  }
+  const float4 lim = reinterpret_cast<const float4*>(a.grp_lim)[4u * grp + g];
+
+  // the operand buffers cover whole steps (gmm_prefilter_operand_sizes), so a step's loads never leave them
+  const uint4* b_src = a.bfrag + (f_begin / 16) * (KS32 * 64) + lane;
+  const float2* n_src = a.bnorm + f_begin + c;
+  uint32_t* m_ptr = a.mask + (uint64_t)grp * a.n_frames * 4u;  // (4 n_frames < 2^32: the launcher checks)
+  uint4 bq[2][NB][KS32];
+  float2 nq[2][NB];
+  auto fetch = [&](int buf, uint32_t s) __attribute__((always_inline)) {
+    const uint4* bs = b_src + (uint64_t)s * (NB * KS32 * 64);
+#pragma unroll
+    for (int nb = 0; nb < NB; nb++) {
+#pragma unroll
+      for (int ks = 0; ks < KS32; ks++) bq[buf][nb][ks] = bs[(nb * KS32 + ks) * 64];
+      nq[buf][nb] = n_src[(uint64_t)s * (NB * 16) + nb * 16];
+    }
+  };
+  auto step = [&](int buf, uint32_t s) __attribute__((always_inline)) {
+    v4f ap[NB][kGroupBlocks];
+#pragma unroll
+    for (int nb = 0; nb < NB; nb++)
+#pragma unroll
+      for (int j = 0; j < kGroupBlocks; j++) ap[nb][j] = (v4f){0.f, 0.f, 0.f, 0.f};
+    // 16 independent accumulators per k-step; each one's chain runs k-steps 0 .. KS32 - 1 from zero, as in the staged kernel
+#pragma unroll
+    for (int ks = 0; ks < KS32; ks++)
+#pragma unroll
+      for (int j = 0; j < kGroupBlocks; j++)
+#pragma unroll
+        for (int nb = 0; nb < NB; nb++)
+          ap[nb][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[j][ks], __builtin_bit_cast(f16x8, bq[buf][nb][ks]), ap[nb][j], 0, 0, 0);
+    // The epilogue reads the accumulators from inline asm, where the compiler sees no MFMA-result hazard: nothing of it may move up
+    // among the MFMAs (the fences), and the accumulators written last (row blocks 6 and 7) are read 12 instructions into it; the
+    // s_nop puts that beyond the 11 wait states an 8-pass MFMA result needs whatever the compiler pads.
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_nop 7");
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- the staged kernel's epilogue, unchanged ----------------------------------------------------------------------
+#pragma unroll
+    for (int nb = 0; nb < NB; nb++) {
+      float amin = __builtin_huge_valf();
+#pragma unroll
+      for (int j = 0; j < kGroupBlocks; j += 2)
+        asm("v_min3_f32 %0, %0, %1, %2\n\tv_min3_f32 %0, %0, %3, %4\n\tv_min3_f32 %0, %0, %5, %6\n\tv_min3_f32 %0, %0, %7, %8"
+            : "+v"(amin)
+            : "v"(ap[nb][j][0]), "v"(ap[nb][j][1]), "v"(ap[nb][j][2]), "v"(ap[nb][j][3]), "v"(ap[nb][j + 1][0]),
+              "v"(ap[nb][j + 1][1]), "v"(ap[nb][j + 1][2]), "v"(ap[nb][j + 1][3]));
+      if (a.chunks >= 2) { const float o = __shfl_xor(amin, 16); asm("v_min_f32 %0, %0, %1" : "+v"(amin) : "v"(o)); }
+      if (a.chunks >= 4) { const float o = __shfl_xor(amin, 32); asm("v_min_f32 %0, %0, %1" : "+v"(amin) : "v"(o)); }
+      const float limit = amin + __builtin_fmaf(lim.y, nq[buf][nb].y, __builtin_fmaf(lim.x, nq[buf][nb].x, lim.z));
+      uint32_t mask = 0;
+#pragma unroll
+      for (int j = kGroupBlocks - 1; j >= 1; j -= 2)
+        asm("v_cmp_ngt_f32 vcc, %2, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+            "v_cmp_ngt_f32 vcc, %3, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+            "v_cmp_ngt_f32 vcc, %4, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+            "v_cmp_ngt_f32 vcc, %5, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+            "v_cmp_ngt_f32 vcc, %6, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+            "v_cmp_ngt_f32 vcc, %7, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+            "v_cmp_ngt_f32 vcc, %8, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+            "v_cmp_ngt_f32 vcc, %9, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc"
+            : "+v"(mask)
+            : "v"(limit), "v"(ap[nb][j][3]), "v"(ap[nb][j][2]), "v"(ap[nb][j][1]), "v"(ap[nb][j][0]), "v"(ap[nb][j - 1][3]),
+              "v"(ap[nb][j - 1][2]), "v"(ap[nb][j - 1][1]), "v"(ap[nb][j - 1][0])
+            : "vcc");
+      const uint64_t f = f_begin + (uint64_t)s * (NB * 16) + nb * 16 + c;
+      if (f < a.n_frames) m_ptr[(uint32_t)f * 4u + (uint32_t)g] = mask;
+    }
+  };
+  // (the step after the last one is fetched again instead of branching around the loads)
+  fetch(0, 0);
+  for (uint32_t s = 0; s < n_steps; s += 2) {
+    fetch(1, s + 1 < n_steps ? s + 1 : n_steps - 1);
+    SR_PS_PIN_FETCH;
+    step(0, s);
+    if (s + 1 >= n_steps) break;
+    fetch(0, s + 2 < n_steps ? s + 2 : n_steps - 1);
+    SR_PS_PIN_FETCH;
+    step(1, s + 1);
+  }
+}
+
 // The error bound above counts fp16 subnormals as representable (spacing 2^-24).  hipcc's default kernel mode keeps
 // them (float_denorm_mode_16_64 = preserve) and MFMA A/B inputs honour that mode; this probe checks it on the device
 // the model is created on: 2^-20 (subnormal in fp16) x 2^10 must come out as 2^-10, not 0.
@@ -403,9 +571,63 @@ hipError_t probe_fp16_accumulation(hipStream_t stream, int ks32, bool* ok, doubl
   return hipSuccess;
 }
 
-hipError_t launch_gmm_prefilter(const GmmPrefilterArgs& a, int ks32, hipStream_t stream) {
-  const dim3 grid(a.nx * a.ny), block(kPWaves * 64);
+// Frame ranges of the stationary route: whole steps, no shorter than kSRangeFrames where the launch has that many frames, and as many
+// of them as makes the workgroups (group quads x ranges) fill whole rounds of the 512 resident slots (2 per CU) best; among equals
+// the fewest, longest ranges.
+static GmmStationaryPlan stationary_plan(uint32_t n_groups, uint64_t n_frames) {
+  GmmStationaryPlan p{};
+  p.n_quads = (n_groups + kPWaves - 1) / kPWaves;
+  const uint64_t steps = (n_frames + 16 * kSNB - 1) / (16 * kSNB);
+  const uint64_t r_max = std::max<uint64_t>(1, std::min<uint64_t>(steps, (n_frames + kSRangeFrames - 1) / kSRangeFrames));
+  uint64_t best_r = 1;
+  double best = -1.0;
+  for (uint64_t r = 1; r <= r_max; r++) {
+    const uint64_t wgs = (uint64_t)p.n_quads * r;
+    const double fill = (double)wgs / (double)((wgs + 511) / 512 * 512);
+    if (fill > best * (1.0 + 1e-9)) { best = fill; best_r = r; }
+  }
+  const uint64_t range_steps = (steps + best_r - 1) / best_r;
+  p.range_frames = (uint32_t)(range_steps * 16 * kSNB);
+  p.n_ranges = (uint32_t)((steps + range_steps - 1) / range_steps);
+  p.per_xcd = (uint32_t)(((uint64_t)p.n_quads * p.n_ranges + 7) / 8);
+  return p;
+}
+
+int gmm_prefilter_route(int ks32, int route) { return (route == kPfStationary && ks32 >= 1 && ks32 <= 3) ? kPfStationary : kPfStaged; }
+int gmm_prefilter_stationary_range_frames() { return kSRangeFrames; }
+void gmm_prefilter_operand_sizes(int ks32, uint64_t n_frames, size_t* n_frag, size_t* n_norm) {
+  const uint64_t blocks = (n_frames + 16 * kSNB - 1) / (16 * kSNB) * kSNB;  // whole steps
+  *n_frag = (size_t)blocks * ks32 * 64;
+  *n_norm = (size_t)blocks * 16;
+}
+
+template <int KS32>
+static hipError_t launch_stationary(const GmmPrefilterArgs& a, hipStream_t stream) {
+  if (!a.bfrag || !a.bnorm || a.n_groups == 0) return hipErrorInvalidValue;
+  size_t n_frag, n_norm;
+  gmm_prefilter_operand_sizes(KS32, a.n_frames, &n_frag, &n_norm);
+  const uint64_t blocks = n_norm / 16;
+  hipLaunchKernelGGL((gmm_prefilter_operands_kernel<KS32>), dim3((unsigned)((blocks + kPWaves - 1) / kPWaves)), dim3(kPWaves * 64), 0, stream,
+                     a.feats, a.n_frames, a.dim, blocks, a.bfrag, a.bnorm);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const GmmStationaryPlan p = stationary_plan(a.n_groups, a.n_frames);
+  hipLaunchKernelGGL((gmm_prefilter_stationary_kernel<KS32>), dim3(8 * p.per_xcd), dim3(kPWaves * 64), 0, stream, a, p);
+  return hipGetLastError();
+}
+
+// the one place that picks the prefilter's kernel
+hipError_t launch_gmm_prefilter(const GmmPrefilterArgs& a, int ks32, int route, hipStream_t stream) {
   if (a.n_frames >= (1ull << 30)) return hipErrorInvalidValue;  // (32-bit mask offsets inside a group)
+  if (a.n_frames == 0) return hipSuccess;
+  if (gmm_prefilter_route(ks32, route) == kPfStationary) {
+    switch (ks32) {
+      case 1: return launch_stationary<1>(a, stream);
+      case 2: return launch_stationary<2>(a, stream);
+      default: return launch_stationary<3>(a, stream);
+    }
+  }
+  const dim3 grid(a.nx * a.ny), block(kPWaves * 64);
   switch (ks32) {
     case 1: hipLaunchKernelGGL((gmm_prefilter16_kernel<1, SR_P16_NB>), grid, block, 0, stream, a); break;
     case 2: hipLaunchKernelGGL((gmm_prefilter16_kernel<2, SR_P16_NB>), grid, block, 0, stream, a); break;

@@ -110,6 +110,9 @@ struct sr_model {
   int neg_possible = -1;                   // can an emission cost of this model be negative?  -1: not looked at yet (srhost::may_go_negative)
   uint32_t pf_dp = 0;                      // gmm_refine_padded_dim(dim): the odd dimension the refinement planes / featsT are laid out in
   DevBuf<uint32_t> pf_mask, pf_ndens, pf_ring;
+  DevBuf<uint4> pf_bfrag;                  // the launch's frames as fp16 B fragments and ...
+  DevBuf<float2> pf_bnorm;                 // ... their norms: the stationary prefilter route's operands, rebuilt by every launch
+  int pf_route = srgpu::kPfStationary;            // SRGPU_PREFILTER=staged|stationary, read once per model (launch_gmm_prefilter)
   DevBuf<double> pf_rows;
   DevBuf<unsigned long long> pf_counter;
   // feeder resources (feeder.cpp), created by the first asynchronous upload and kept: pinning 2 x 8 MiB costs milliseconds

@@ -67,7 +67,12 @@ struct GmmPrefilterArgs {
   uint32_t* mask;               // [group][frame][4 state slots] candidate densities of (frame, state)
   uint32_t nx, ny;
   uint32_t chunks;              // 1, 2 or 4 consecutive state slots (of 32 densities) make up one state
+  // the group-stationary route (gmm_prefilter_stationary_kernel): the launch's frame operands, built once per launch
+  uint32_t n_groups;
+  uint4* bfrag;                 // [16-frame block][k-step][lane][8 fp16] B fragments, gmm_prefilter_operand_sizes() entries
+  float2* bnorm;                // [frame] (|b|, |b^ - b|), both rounded up, the second capped (gmm_prefilter.hip header)
 };
+enum { kPfStaged = 0, kPfStationary = 1 };  // routes of launch_gmm_prefilter
 // Constants of the prefilter's error bound (derivation: gmm_prefilter.hip header), by k-steps of 32; the host folds them into grp_lim.
 struct PfBound { float kappa, acc, abs, sub; };
 constexpr float kPfRes16 = 4.8835e-4f;  // cap of |b^ - b| / |b|: one fp16 rounding of a normal fp32 x^2 or x
@@ -101,8 +106,17 @@ struct GmmRefineArgs {
 void gmm_refine_defer_layout(const GmmRefineArgs& a, size_t budget_bytes, uint32_t cap_limit, uint32_t* cap, size_t* n_entries,
                              size_t* n_counts);
 size_t gmm_refine_ring_words(const GmmRefineArgs& a);  // needs n_frames, n_pstates, dim, n_slots
-hipError_t launch_gmm_prefilter(const GmmPrefilterArgs& a, int ks32, hipStream_t stream);
+// route: kPfStaged -- frames stationary, the model streamed through LDS (needs split_begin, nx, ny); kPfStationary -- a 4-state group
+// stationary in a wave's registers, the frames' ready-made operands streamed past it (needs n_groups, bfrag, bnorm; builds the
+// operands first).  ks32 = 4 has no stationary instantiation (its A operand alone is 128 registers) and takes the staged kernel on
+// either route: gmm_prefilter_route() says which kernel a launch runs.  Both routes write the same masks, bit for bit.
+hipError_t launch_gmm_prefilter(const GmmPrefilterArgs& a, int ks32, int route, hipStream_t stream);
+int gmm_prefilter_route(int ks32, int route);
 int gmm_prefilter_frames_per_tile();
+// the stationary route cuts the frames into ranges of a multiple of 32 frames; a launch of more frames than this has at least two
+int gmm_prefilter_stationary_range_frames();
+// entries of bfrag / bnorm for a launch over n_frames on that route
+void gmm_prefilter_operand_sizes(int ks32, uint64_t n_frames, size_t* n_frag, size_t* n_norm);
 // does the fp16 MFMA keep subnormal inputs on this device / in this build (an assumption of the prefilter's error bound)?
 hipError_t probe_fp16_denormals(hipStream_t stream, bool* preserved);
 // does the fp16 MFMA chain accumulate within the bound's model (|error| <= 87 (K = 96: ks32 3) / 132 (K = 128: ks32 4) * 2^-24 *

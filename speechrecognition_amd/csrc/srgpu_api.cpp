@@ -412,8 +412,9 @@ DeferLayout defer_layout(const sr_model* m, uint64_t n_frames) {
   return d;
 }
 
-int reserve_scoring(sr_model* m, int gmm_kernel, uint64_t n_max) {
+int reserve_scoring(sr_model* m, int gmm_kernel, uint64_t n_max, int pf_route = -1) {  // pf_route: the model's own unless given
   gmm_kernel = resolve_dense_kernel(m, gmm_kernel);
+  if (pf_route < 0) pf_route = m->pf_route;
   if ((gmm_kernel == SR_GMM_MFMA && !m->mfma_packed) || (gmm_kernel == SR_GMM_PREFILTER && !m->pf_packed)) {
     int rc = srhost::ensure_host_tables(m);
     if (rc) return rc;
@@ -441,7 +442,27 @@ int reserve_scoring(sr_model* m, int gmm_kernel, uint64_t n_max) {
     if (dl.n_e) { HIP_TRY(m->pf_defer.ensure(dl.n_e)); HIP_TRY(m->pf_defer_cnt.ensure(dl.n_c)); }
     HIP_TRY(m->pf_mask.ensure(want_mask));  // the refinement reads group pairs
     HIP_TRY(m->pf_ring.ensure(want_ring));
+    if (gmm_prefilter_route(m->pf_ks32, pf_route) == kPfStationary) {
+      size_t want_frag, want_norm;
+      gmm_prefilter_operand_sizes(m->pf_ks32, n_max, &want_frag, &want_norm);
+      if (want_frag > m->pf_bfrag.n || want_norm > m->pf_bnorm.n) HIP_TRY(hipStreamSynchronize(m->s_gmm));
+      HIP_TRY(m->pf_bfrag.ensure(want_frag));
+      HIP_TRY(m->pf_bnorm.ensure(want_norm));
+    }
   }
+  return SR_OK;
+}
+
+// the prefilter's arguments for a launch over n_frames (either route; the workspaces are reserve_scoring's)
+int prefilter_args(sr_model* m, const float* d_feats, uint64_t n_frames, GmmPrefilterArgs* pa) {
+  const uint32_t tile = gmm_prefilter_frames_per_tile();
+  const uint32_t nx = (uint32_t)((n_frames + tile - 1) / tile);
+  int rc = set_prefilter_splits(m, nx);
+  if (rc) return rc;
+  pa->feats = d_feats; pa->n_frames = n_frames; pa->dim = m->dim;
+  pa->apack = m->pf_apack.p; pa->grp_lim = m->pf_lim.p; pa->split_begin = m->pf_split_cur;
+  pa->mask = m->pf_mask.p; pa->nx = nx; pa->ny = m->pf_ny; pa->chunks = std::min(4u, m->pf_chunks);
+  pa->n_groups = m->pf_groups; pa->bfrag = m->pf_bfrag.p; pa->bnorm = m->pf_bnorm.p;
   return SR_OK;
 }
 
@@ -467,15 +488,10 @@ int launch_scoring(sr_model* m, const float* d_feats, uint64_t n_frames, int gmm
     HIP_TRY(launch_gmm_mfma(a, m->ksteps, !m->max_approx, m->s_gmm));
     if ((rc = prof_end(m, m->s_gmm, &ep))) return rc;
   } else if (gmm_kernel == SR_GMM_PREFILTER && m->pf_ks32 > 0) {
-    const uint32_t tile = gmm_prefilter_frames_per_tile();
-    const uint32_t nx = (uint32_t)((n_frames + tile - 1) / tile);
-    int rc = set_prefilter_splits(m, nx);
+    GmmPrefilterArgs pa{};
+    int rc = prefilter_args(m, d_feats, n_frames, &pa);
     if (rc) return rc;
     const uint64_t ldT = (n_frames + 63) & ~(uint64_t)63;
-    GmmPrefilterArgs pa{};
-    pa.feats = d_feats; pa.n_frames = n_frames; pa.dim = m->dim;
-    pa.apack = m->pf_apack.p; pa.grp_lim = m->pf_lim.p; pa.split_begin = m->pf_split_cur;
-    pa.mask = m->pf_mask.p; pa.nx = nx; pa.ny = m->pf_ny; pa.chunks = std::min(4u, m->pf_chunks);
     GmmRefineArgs ra = refine_shape(m, n_frames);
     const bool padded = m->pf_dp != m->dim;
     ra.feats = padded ? m->featsP.p : d_feats; ra.featsT = m->featsT.p; ra.n_frames_ld = ldT;
@@ -490,7 +506,7 @@ int launch_scoring(sr_model* m, const float* d_feats, uint64_t n_frames, int gmm
     if ((rc = prof_begin(m, m->s_gmm, 0, &ep))) return rc;
     if ((rc = prof_begin(m, m->s_gmm, 2, &ep_p))) return rc;
     HIP_TRY(launch_transpose_feats(d_feats, n_frames, m->dim, m->pf_dp, ldT, m->featsT.p, padded ? m->featsP.p : nullptr, m->s_gmm));
-    HIP_TRY(launch_gmm_prefilter(pa, m->pf_ks32, m->s_gmm));
+    HIP_TRY(launch_gmm_prefilter(pa, m->pf_ks32, m->pf_route, m->s_gmm));
     if ((rc = prof_end(m, m->s_gmm, &ep_p))) return rc;
     if ((rc = prof_begin(m, m->s_gmm, 3, &ep_r))) return rc;
     HIP_TRY(launch_gmm_refine(ra, m->s_gmm));
@@ -813,6 +829,11 @@ int model_shell(int device, uint32_t dim, uint32_t n_states, const uint32_t* den
   // the refinement kernel addresses the transposed feature copy of a chunk with 32-bit buffer offsets
   m->chunk_frames = std::min<size_t>(m->chunk_frames, ((size_t)1 << 32) / (4 * (size_t)dim) - 128);
   if (const char* ov = getenv("SRGPU_OVERLAP")) m->overlap = atoi(ov) != 0;
+  if (const char* e = getenv("SRGPU_PREFILTER")) {  // which way round the fp16 prefilter runs (same masks; for measuring)
+    if (!strcmp(e, "staged")) m->pf_route = kPfStaged;
+    else if (!strcmp(e, "stationary")) m->pf_route = kPfStationary;
+    else return fail(SR_EINVAL, "SRGPU_PREFILTER=%s: staged or stationary", e);
+  }
   if (const char* e = getenv("SRGPU_DEFER_MB")) m->defer_budget = (size_t)strtoull(e, nullptr, 10) << 20;
   if (const char* e = getenv("SRGPU_FB_MB")) m->fb_budget = std::max<size_t>(1, (size_t)strtoull(e, nullptr, 10)) << 20;
   if (const char* e = getenv("SRGPU_MLLT_MB")) m->mllt_budget = std::max<size_t>(1, (size_t)strtoull(e, nullptr, 10)) << 20;
@@ -1051,6 +1072,42 @@ int sr_score_frames(sr_model* m, const float* feats, uint64_t n_frames, int gmm_
       (n_frames > 0 && (e = hipMemcpy(c->feats.p, feats, (size_t)n_frames * m->dim * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess))
     return fail(SR_EHIP, "feature upload: %s", hipGetErrorString(e));
   return sr_score_corpus(m, c, gmm_kernel, out);
+  });
+}
+
+// test hook: the candidate masks of `feats` from the prefilter alone, by the given route (kPfStaged 0 / kPfStationary 1), as the
+// kernel leaves them: [group][frame][4 state slots].  masks == null only reports the group count.  Nothing on a scoring path calls this.
+int sr_prefilter_masks(sr_model* m, const float* feats, uint64_t n_frames, int route, uint32_t* n_groups, uint32_t* masks, uint64_t cap_words) {
+  return guarded(__func__, [&]() -> int {
+  int rc = check_model(m);
+  if (rc) return rc;
+  if (route != kPfStaged && route != kPfStationary) return fail(SR_EINVAL, "route %d: 0 (staged) or 1 (stationary)", route);
+  if (!m->max_approx) return fail(SR_EINVAL, "the prefilter scores max-approx models only");
+  if ((rc = reserve_scoring(m, SR_GMM_PREFILTER, n_frames, route))) return rc;
+  if (m->pf_ks32 == 0) return fail(SR_EINVAL, "this model is not scored through the prefilter");
+  if (n_groups) *n_groups = m->pf_groups;
+  if (!masks || n_frames == 0) return SR_OK;
+  if (!feats) return fail(SR_EINVAL, "feats is null");
+  const uint64_t words = (uint64_t)m->pf_groups * n_frames * 4;
+  if (cap_words < words) return fail(SR_EINVAL, "masks holds %llu words, %llu needed", (unsigned long long)cap_words, (unsigned long long)words);
+  DevBuf<float> d_feats;
+  HIP_TRY(d_feats.ensure((size_t)n_frames * m->dim + 64));
+  HIP_TRY(hipMemcpy(d_feats.p, feats, (size_t)n_frames * m->dim * sizeof(float), hipMemcpyHostToDevice));
+  GmmPrefilterArgs pa{};
+  if ((rc = prefilter_args(m, d_feats.p, n_frames, &pa))) return rc;
+  HIP_TRY(hipMemsetAsync(m->pf_mask.p, 0xA5, words * sizeof(uint32_t), m->s_gmm));  // a word no kernel wrote shows
+  HIP_TRY(launch_gmm_prefilter(pa, m->pf_ks32, route, m->s_gmm));
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  HIP_TRY(hipMemcpy(masks, m->pf_mask.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return SR_OK;
+  });
+}
+
+int sr_prefilter_range_frames(uint32_t* frames) {
+  return guarded(__func__, [&]() -> int {
+  if (!frames) return fail(SR_EINVAL, "frames is null");
+  *frames = (uint32_t)gmm_prefilter_stationary_range_frames();
+  return SR_OK;
   });
 }
 
