@@ -983,6 +983,13 @@ SR_API int sr_prefilter_masks(sr_model* m, const float* feats, uint64_t n_frames
                               uint64_t cap_words);
 /* The stationary route cuts a launch's frames into ranges; a launch of more than *frames frames has at least two (tests straddle one). */
 SR_API int sr_prefilter_range_frames(uint32_t* frames);
+/* Test hook: the last step of a recognition call alone, on search outputs the caller supplies (host arrays) instead of a search's:
+ * utterance u has counts[u] words at words[frame_off[u] ..] and the flags flags[u] (4: its traceback did not walk).  Returns what
+ * sr_recognize_corpus would: the words back to back in out_words with out_word_off[n_utts + 1], or SR_ECORRUPT naming the first
+ * utterance whose flag is raised or whose count exceeds its frames.  The words are compacted on the device, or by the host with
+ * SRGPU_GATHER=host (read when a model is created; a diagnostic knob, same output). */
+SR_API int sr_gather_words(sr_model* m, uint32_t n_utts, const uint64_t* frame_off, const uint32_t* counts, const uint32_t* flags,
+                           const uint32_t* words, uint32_t* out_words, uint64_t* out_word_off);
 
 /* ---- measurement --------------------------------------------------------------------------------
  * When enabled, every kernel launch of this model handle is bracketed by HIP events on the

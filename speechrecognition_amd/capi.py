@@ -49,6 +49,7 @@ SYMBOLS = [
     "sr_bigram_stream_open", "sr_bigram_stream_begin", "sr_bigram_stream_push", "sr_bigram_stream_partial", "sr_bigram_stream_end",
     "sr_bigram_stream_destroy",
     "sr_probe_fp16_denormals", "sr_probe_fp16_accumulation", "sr_prefilter_masks", "sr_prefilter_range_frames",
+    "sr_gather_words",
     "sr_profile_enable", "sr_profile_reset", "sr_profile_read",
 ]
 
@@ -191,6 +192,7 @@ def lib():
         L.sr_probe_fp16_accumulation.argtypes = [i32, C.POINTER(i32), C.POINTER(dbl)]
         L.sr_prefilter_masks.argtypes = [vp, vp, u64, i32, C.POINTER(u32), vp, u64]
         L.sr_prefilter_range_frames.argtypes = [C.POINTER(u32)]
+        L.sr_gather_words.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
         L.sr_profile_enable.argtypes = [vp, i32]
         L.sr_profile_reset.argtypes = [vp]
         L.sr_profile_read.argtypes = [vp, C.POINTER(Profile)]
@@ -352,6 +354,19 @@ class Model:
         out = np.empty((n_groups.value, feats.shape[0], 4), dtype=np.uint32)
         _check(lib().sr_prefilter_masks(self.h, _ptr(feats), feats.shape[0], route, C.byref(n_groups), _ptr(out), out.size))
         return out
+
+    def gather_words(self, frame_off, counts, flags, words):
+        """sr_gather_words (test hook): (words, word_off) that a recognition call would return for these search outputs."""
+        frame_off = np.ascontiguousarray(frame_off, dtype=np.uint64)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        flags = np.ascontiguousarray(flags, dtype=np.uint32)
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        n_utts = len(frame_off) - 1
+        assert len(counts) == n_utts and len(flags) == n_utts and len(words) == int(frame_off[-1])
+        out = np.empty(max(1, len(words)), dtype=np.uint32)
+        off = np.empty(n_utts + 1, dtype=np.uint64)
+        _check(lib().sr_gather_words(self.h, n_utts, _ptr(frame_off), _ptr(counts), _ptr(flags), _ptr(words), _ptr(out), _ptr(off)))
+        return out[:int(off[-1])].copy(), off
 
     def upload(self, feats, frame_off, asynchronous=False):
         return Corpus(self, feats, frame_off, asynchronous)

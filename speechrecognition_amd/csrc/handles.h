@@ -54,6 +54,27 @@ struct DevBuf {
   ~DevBuf() { release(); }
 };
 
+// Pinned host memory the device writes straight into (hipHostMalloc, mapped and coherent): same idiom as DevBuf
+template <typename T>
+struct PinnedBuf {
+  T* p = nullptr;
+  size_t n = 0;
+  hipError_t ensure(size_t count) {
+    if (count <= n && p) return hipSuccess;
+    if (p) { hipError_t e = hipHostFree(p); if (e != hipSuccess) return e; p = nullptr; n = 0; }
+    if (count == 0) count = 1;
+    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), count * sizeof(T), hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess) n = count;
+    return e;
+  }
+  void release() { if (p) (void)hipHostFree(p); p = nullptr; n = 0; }
+  void swap(PinnedBuf& o) { T* tp = p; p = o.p; o.p = tp; size_t tn = n; n = o.n; o.n = tn; }
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf&) = delete;
+  PinnedBuf& operator=(const PinnedBuf&) = delete;
+  ~PinnedBuf() { release(); }
+};
+
 struct EventPair { hipEvent_t a, b; int kind; };  // kind 0 = gmm, 1 = search, 2 = prefilter pass, 3 = refinement (inside 0)
 
 
@@ -68,8 +89,11 @@ struct CorpusSpare {
   DevBuf<uint32_t> utt_order, out_words, out_count, out_flags;
   DevBuf<double> tb_score;
   DevBuf<uint16_t> tb_word, tb_bkp;
+  DevBuf<uint64_t> gather_off;
+  PinnedBuf<unsigned char> result;  // (pinning a result block per sr_recognize_batch call would cost more than the compaction saves)
   size_t bytes() const {
-    return feats.n * 4 + d_frame_off.n * 8 + (utt_order.n + out_words.n + out_count.n + out_flags.n) * 4 + tb_score.n * 8 + (tb_word.n + tb_bkp.n) * 2;
+    return feats.n * 4 + d_frame_off.n * 8 + (utt_order.n + out_words.n + out_count.n + out_flags.n) * 4 + tb_score.n * 8 + (tb_word.n + tb_bkp.n) * 2 +
+           gather_off.n * 8 + result.n;
   }
 };
 // ... kept only up to this size (SRGPU_SPARE_MB, default 256): a one-shot call on a huge corpus must not leave the model holding
@@ -113,6 +137,7 @@ struct sr_model {
   DevBuf<uint4> pf_bfrag;                  // the launch's frames as fp16 B fragments and ...
   DevBuf<float2> pf_bnorm;                 // ... their norms: the stationary prefilter route's operands, rebuilt by every launch
   int pf_route = srgpu::kPfStationary;            // SRGPU_PREFILTER=staged|stationary, read once per model (launch_gmm_prefilter)
+  bool gather_device = true;               // SRGPU_GATHER=host|device, read once per model: where the search's words are compacted (gather_words.hip)
   DevBuf<double> pf_rows;
   DevBuf<unsigned long long> pf_counter;
   // feeder resources (feeder.cpp), created by the first asynchronous upload and kept: pinning 2 x 8 MiB costs milliseconds
@@ -155,6 +180,9 @@ struct sr_corpus {
   DevBuf<double> tb_score;
   DevBuf<uint16_t> tb_word, tb_bkp;
   DevBuf<uint32_t> out_words, out_count, out_flags;
+  // the packed result of a recognition call (gather_words.hip): the block the compaction writes and the host reads, the word offsets' device copy
+  PinnedBuf<unsigned char> result;
+  DevBuf<uint64_t> gather_off;
   DevBuf<unsigned char> big_ws;     // decode_big_kernel: hypothesis arrays of the utterances in flight
   // aligner workspace
   DevBuf<uint16_t> automata, out_states;

@@ -262,6 +262,29 @@ hipError_t launch_traceback(const uint64_t* frame_off, uint32_t n_utts, const ui
                             uint32_t silence_word, uint32_t n_words, uint32_t* out_words, uint32_t* out_count,
                             uint32_t* out_flags, hipStream_t stream);
 
+// ---- compaction of a search's words into one result block (gather_words.hip) -----------------------
+constexpr uint32_t kGatherNone = 0xFFFFFFFFu;
+constexpr int kGatherMaxArrays = 3;
+struct GatherHeader {       // the head of the block: what the host checks before it copies
+  uint64_t n_words;         // all utterances' words (a count beyond its slots counted as the slots)
+  uint32_t first_flagged;   // the first utterance with flags & flag_mask, kGatherNone: none
+  uint32_t first_over;      // the first utterance with more words than slots, kGatherNone: none ...
+  uint32_t over_count;      // ... and its count
+  uint32_t reserved[3];
+};
+static_assert(sizeof(GatherHeader) == 32, "word_off follows the header, 8-byte aligned");
+struct GatherArgs {
+  const uint32_t* count;      // [n_utts]
+  const uint32_t* flags;      // [n_utts]
+  const uint64_t* frame_off;  // [n_utts+1]; utterance u owns slots frame_off[u] + u * extra_slots .. of each array, T_u + extra_slots of them
+  uint32_t n_utts, extra_slots, flag_mask;
+  const uint32_t* src[kGatherMaxArrays];  // arrays of 32-bit elements, moved as bits
+  uint64_t* dev_off;          // [n_utts+1] workspace: the offsets for the second launch
+  unsigned char* block;       // GatherHeader, word_off[n_utts+1] (uint64), then n_arrays runs of n_words elements; gather_block_bytes()
+};
+size_t gather_block_bytes(uint32_t n_utts, uint64_t n_slots, int n_arrays);  // n_slots: all utterances' slots, the most n_words can be
+hipError_t launch_gather_words(const GatherArgs& a, int n_arrays, hipStream_t stream);
+
 // ---- forced aligners (viterbi_align.hip) ----------------------------------------------------------
 struct AlignArgs {
   const double* scores;         // [frames x ld]

@@ -606,8 +606,10 @@ int prepare_chunks(sr_model* m, sr_corpus* c, std::vector<Chunk>* chunks) {
 // SRGPU_OVERLAP=0).  ev_scored hands a buffer to the search; ev_consumed hands it back to the scoring two chunks later.
 //   score(const Chunk&, double* table)                           enqueues the chunk's scores on s_gmm
 //   search(const Chunk&, const double* table, hipStream_t s)     enqueues its search on s (kind-1 profiling window)
-template <class Score, class Search>
-int run_chunks(sr_model* m, const std::vector<Chunk>& chunks, Score score, Search search) {
+//   tail(hipStream_t s)                                          enqueues what follows the last chunk's search on its stream, outside
+//                                                                the profiling windows (the compaction of the words)
+template <class Score, class Search, class Tail>
+int run_chunks(sr_model* m, const std::vector<Chunk>& chunks, Score score, Search search, Tail tail) {
   const hipStream_t s_search = m->overlap ? m->s_search : m->s_gmm;
   int rc;
   for (size_t i = 0; i < chunks.size(); i++) {
@@ -622,9 +624,14 @@ int run_chunks(sr_model* m, const std::vector<Chunk>& chunks, Score score, Searc
     if ((rc = prof_end(m, s_search, &ep))) return rc;
     HIP_TRY(hipEventRecord(m->ev_consumed[buf], s_search));
   }
+  if ((rc = tail(s_search))) return rc;
   HIP_TRY(hipStreamSynchronize(m->s_search));
   HIP_TRY(hipStreamSynchronize(m->s_gmm));
   return SR_OK;
+}
+template <class Score, class Search>
+int run_chunks(sr_model* m, const std::vector<Chunk>& chunks, Score score, Search search) {
+  return run_chunks(m, chunks, score, search, [](hipStream_t) { return (int)SR_OK; });
 }
 
 }  // namespace
@@ -632,7 +639,7 @@ namespace srhost {
 static void swap_spare(sr_corpus* c, CorpusSpare& sp) {
   c->feats.swap(sp.feats); c->d_frame_off.swap(sp.d_frame_off); c->utt_order.swap(sp.utt_order); c->out_words.swap(sp.out_words);
   c->out_count.swap(sp.out_count); c->out_flags.swap(sp.out_flags); c->tb_score.swap(sp.tb_score); c->tb_word.swap(sp.tb_word);
-  c->tb_bkp.swap(sp.tb_bkp);
+  c->tb_bkp.swap(sp.tb_bkp); c->gather_off.swap(sp.gather_off); c->result.swap(sp.result);
 }
 void corpus_register(sr_corpus* c) {
   sr_model* m = c->model;
@@ -661,7 +668,13 @@ void corpus_donate_spare(sr_corpus* c) {
   swap_spare(c, *sp);
   std::lock_guard<std::mutex> lk(m->spare_mu);
   m->corpora.erase(std::remove(m->corpora.begin(), m->corpora.end(), c), m->corpora.end());
-  if (sp->bytes() > corpus_spare_cap_bytes()) return;  // too big to keep: freed on return
+  if (sp->bytes() > corpus_spare_cap_bytes()) {
+    // too big to keep: freed on return -- all but the result block, 4 bytes per frame and, being pinned, the dearest to get again
+    std::unique_ptr<CorpusSpare> small(new CorpusSpare());
+    small->result.swap(sp->result); small->gather_off.swap(sp->gather_off);
+    sp = std::move(small);
+    if (sp->bytes() > corpus_spare_cap_bytes()) return;
+  }
   if (!m->spare) m->spare = std::move(sp);  // (else: one spare set is kept, this one is freed on return)
 }
 }  // namespace srhost
@@ -833,6 +846,11 @@ int model_shell(int device, uint32_t dim, uint32_t n_states, const uint32_t* den
     if (!strcmp(e, "staged")) m->pf_route = kPfStaged;
     else if (!strcmp(e, "stationary")) m->pf_route = kPfStationary;
     else return fail(SR_EINVAL, "SRGPU_PREFILTER=%s: staged or stationary", e);
+  }
+  if (const char* e = getenv("SRGPU_GATHER")) {  // where a recognition call's words are compacted (same output; for measuring)
+    if (!strcmp(e, "host")) m->gather_device = false;
+    else if (!strcmp(e, "device")) m->gather_device = true;
+    else return fail(SR_EINVAL, "SRGPU_GATHER=%s: host or device", e);
   }
   if (const char* e = getenv("SRGPU_DEFER_MB")) m->defer_budget = (size_t)strtoull(e, nullptr, 10) << 20;
   if (const char* e = getenv("SRGPU_FB_MB")) m->fb_budget = std::max<size_t>(1, (size_t)strtoull(e, nullptr, 10)) << 20;
@@ -1196,7 +1214,58 @@ int sr_lexicon_destroy(sr_lexicon* l) {
 
 // Words of utterance u start at out_words[frame_off[u]] on the device, out_count[u] of them; a kernel that could not walk an
 // utterance's traceback (traceback.h) has raised kFlagCorrupt instead of reporting words: SR_ECORRUPT, naming the first one.
+//
+// The device packs them (gather_words.hip) into c->result, pinned host memory it writes directly: reserve_gather before the pass
+// (allocation synchronises), enqueue_gather behind the last search on its stream, and after the pass's own synchronisation
+// gather_words checks the block's header and copies offsets and words out.  SRGPU_GATHER=host keeps the earlier route for
+// comparison: three pageable copies of everything and the loop on the host.
+static int reserve_gather(sr_model* m, sr_corpus* c, uint32_t extra_slots, int n_arrays) {
+  if (!m->gather_device) return SR_OK;
+  HIP_TRY(c->result.ensure(gather_block_bytes(c->n_utts, c->n_frames + (uint64_t)c->n_utts * extra_slots, n_arrays)));
+  HIP_TRY(c->gather_off.ensure((size_t)c->n_utts + 1));
+  return SR_OK;
+}
+static int enqueue_gather(sr_model* m, sr_corpus* c, GatherArgs a, int n_arrays, hipStream_t s) {
+  if (!m->gather_device) return SR_OK;
+  a.frame_off = c->d_frame_off.p; a.n_utts = c->n_utts;
+  a.dev_off = c->gather_off.p; a.block = c->result.p;
+  HIP_TRY(launch_gather_words(a, n_arrays, s));
+  return SR_OK;
+}
+static GatherArgs zerogram_gather(const sr_corpus* c) {
+  GatherArgs a{};
+  a.count = c->out_count.p; a.flags = c->out_flags.p; a.flag_mask = kFlagCorrupt; a.extra_slots = 0;
+  a.src[0] = c->out_words.p;
+  return a;
+}
+// the parts of a written block
+struct GatherBlock {
+  const GatherHeader* head;
+  const uint64_t* off;
+  const uint32_t* data;  // array k starts at data + k * head->n_words
+};
+static GatherBlock gather_block(const sr_corpus* c) {
+  const uint64_t* off = reinterpret_cast<const uint64_t*>(c->result.p + sizeof(GatherHeader));
+  return {reinterpret_cast<const GatherHeader*>(c->result.p), off, reinterpret_cast<const uint32_t*>(off + c->n_utts + 1)};
+}
+
+static int gather_words_host(sr_corpus* c, uint32_t* out_words, uint64_t* out_word_off);
 static int gather_words(sr_corpus* c, uint32_t* out_words, uint64_t* out_word_off) {
+  if (!c->model->gather_device) return gather_words_host(c, out_words, out_word_off);
+  const GatherBlock b = gather_block(c);
+  const GatherHeader& h = *b.head;
+  // the serial loop's order: the lower utterance first, and the flag before the count in one utterance
+  if (h.first_flagged != kGatherNone && h.first_flagged <= h.first_over)
+    return fail(SR_ECORRUPT, "utterance %u: the traceback does not walk back to frame 0 (Recognizer.cpp:222-231)", h.first_flagged);
+  if (h.first_over != kGatherNone) {
+    const uint64_t T = c->frame_off[h.first_over + 1] - c->frame_off[h.first_over];
+    return fail(SR_ECORRUPT, "utterance %u: %u words for %llu frames", h.first_over, h.over_count, (unsigned long long)T);
+  }
+  memcpy(out_word_off, b.off, sizeof(uint64_t) * ((size_t)c->n_utts + 1));
+  if (h.n_words) memcpy(out_words, b.data, sizeof(uint32_t) * h.n_words);
+  return SR_OK;
+}
+static int gather_words_host(sr_corpus* c, uint32_t* out_words, uint64_t* out_word_off) {
   const uint32_t U = c->n_utts;
   const uint64_t F = c->n_frames;
   std::vector<uint32_t> counts(U), flags(U), dev_words(F);
@@ -1229,6 +1298,8 @@ static int recognize_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_sea
   HIP_TRY(c->out_words.ensure(F));
   HIP_TRY(c->out_count.ensure(U));
   HIP_TRY(c->out_flags.ensure(U));
+  int rc;
+  if ((rc = reserve_gather(m, c, 0, 1))) return rc;
   HIP_TRY(hipMemsetAsync(c->out_flags.p, 0, sizeof(uint32_t) * std::max(1u, U), m->s_gmm));
 
   DecodeArgs da = lexicon_args(l);
@@ -1241,7 +1312,6 @@ static int recognize_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_sea
     for (const Chunk& ch : chunks) most = std::max(most, ch.u1 - ch.u0);
     HIP_TRY(c->big_ws.ensure((size_t)most * decode_big_workspace(l->net.n_slots)));
   }
-  int rc;
   {
     bool neg = false;
     if ((rc = srhost::may_go_negative(m, &neg))) return rc;
@@ -1256,7 +1326,8 @@ static int recognize_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_sea
         HIP_TRY(launch_decode(da, route, c->big_ws.p, s));
         if (m->profiling) m->prof.search_bytes += (8.0 * m->n_states + 4.0 * l->net.n_slots) * (double)(ch.f1 - ch.f0);
         return after(ch, table, s);
-      });
+      },
+      [&](hipStream_t s) { return enqueue_gather(m, c, zerogram_gather(c), 1, s); });
   if (rc) return rc;
   if (m->profiling) m->prof.frames += F;
   return SR_OK;
@@ -1297,12 +1368,38 @@ int sr_traceback_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const uint16_t
   HIP_TRY(c->out_words.ensure(F));
   HIP_TRY(c->out_count.ensure(U));
   HIP_TRY(c->out_flags.ensure(U));
+  if ((rc = reserve_gather(m, c, 0, 1))) return rc;
   HIP_TRY(hipMemcpyAsync(c->tb_word.p, tb_word, sizeof(uint16_t) * (F + U), hipMemcpyHostToDevice, m->s_gmm));
   HIP_TRY(hipMemcpyAsync(c->tb_bkp.p, tb_bkp, sizeof(uint16_t) * (F + U), hipMemcpyHostToDevice, m->s_gmm));
   HIP_TRY(launch_traceback(c->d_frame_off.p, U, c->tb_word.p, c->tb_bkp.p, l->net.silence_word, l->net.n_words, c->out_words.p,
                            c->out_count.p, c->out_flags.p, m->s_gmm));
+  if ((rc = enqueue_gather(m, c, zerogram_gather(c), 1, m->s_gmm))) return rc;
   HIP_TRY(hipStreamSynchronize(m->s_gmm));
   return gather_words(c, out_words, out_word_off);
+  });
+}
+
+int sr_gather_words(sr_model* m, uint32_t n_utts, const uint64_t* frame_off, const uint32_t* counts, const uint32_t* flags,
+                    const uint32_t* words, uint32_t* out_words, uint64_t* out_word_off) {
+  return guarded(__func__, [&]() -> int {
+  int rc = check_model(m);
+  if (rc) return rc;
+  if (!frame_off || !out_word_off || (n_utts && (!counts || !flags))) return fail(SR_EINVAL, "null argument");
+  if (frame_off[0] != 0) return fail(SR_EINVAL, "frame_off[0] must be 0");
+  for (uint32_t u = 0; u < n_utts; u++)
+    if (frame_off[u + 1] < frame_off[u]) return fail(SR_EINVAL, "frame_off falls at utterance %u", u);
+  sr_corpus c;  // (the search outputs of a corpus, filled by the caller instead of a search; its buffers go with it)
+  c.model = m; c.n_utts = n_utts; c.n_frames = frame_off[n_utts];
+  if (c.n_frames && (!words || !out_words)) return fail(SR_EINVAL, "null argument");
+  c.frame_off.assign(frame_off, frame_off + n_utts + 1);
+  HIP_TRY(c.d_frame_off.upload(frame_off, (size_t)n_utts + 1));
+  HIP_TRY(c.out_count.upload(counts, n_utts));
+  HIP_TRY(c.out_flags.upload(flags, n_utts));
+  HIP_TRY(c.out_words.upload(words, c.n_frames));
+  if ((rc = reserve_gather(m, &c, 0, 1))) return rc;
+  if ((rc = enqueue_gather(m, &c, zerogram_gather(&c), 1, m->s_gmm))) return rc;
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  return gather_words(&c, out_words, out_word_off);
   });
 }
 
@@ -1420,6 +1517,7 @@ static int bigram_recognize_pass(sr_model* m, sr_corpus* c, sr_bigram* b, const 
   HIP_TRY(b->out_score.ensure(F + U));
   HIP_TRY(b->out_count.ensure(U));
   HIP_TRY(b->out_flags.ensure(U));
+  if ((rc = reserve_gather(m, c, 1, 3))) return rc;  // (utterance u's slots start at frame_off[u] + u, T_u + 1 of them)
 
   ba.frame_off = c->d_frame_off.p; ba.utt_order = c->utt_order.p;
   ba.ac_pruning = p->acoustic_pruning; ba.lm_pruning = p->lm_pruning;
@@ -1457,26 +1555,48 @@ static int bigram_recognize_pass(sr_model* m, sr_corpus* c, sr_bigram* b, const 
         // SURVEY 8(d)'s decoder model, 8 S + 4 P bytes per frame, with P = the bigram search's positions (words + their silence copies)
         if (m->profiling) m->prof.search_bytes += (8.0 * m->n_states + 4.0 * ba.n_positions) * (double)(ch.f1 - ch.f0);
         return after(ch, table, s);
+      },
+      [&](hipStream_t s) {
+        GatherArgs ga{};
+        ga.count = b->out_count.p; ga.flags = b->out_flags.p; ga.flag_mask = ~0u; ga.extra_slots = 1;
+        ga.src[0] = b->out_word.p; ga.src[1] = b->out_time.p; ga.src[2] = reinterpret_cast<const uint32_t*>(b->out_score.p);
+        return enqueue_gather(m, c, ga, 3, s);
       });
   if (rc) return rc;
 
-  std::vector<uint32_t> counts(U), flags(U), dw(F + U), dt(F + U);
-  std::vector<float> ds(F + U);
-  if (U) {
-    HIP_TRY(hipMemcpy(counts.data(), b->out_count.p, sizeof(uint32_t) * U, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(flags.data(), b->out_flags.p, sizeof(uint32_t) * U, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(dw.data(), b->out_word.p, sizeof(uint32_t) * (F + U), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(dt.data(), b->out_time.p, sizeof(uint32_t) * (F + U), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(ds.data(), b->out_score.p, sizeof(float) * (F + U), hipMemcpyDeviceToHost));
-  }
-  uint64_t n = 0;
-  out_off[0] = 0;
-  for (uint32_t u = 0; u < U; u++) {
-    if (flags[u]) return fail(SR_ELIMIT, "utterance %u: more than %llu word ends per frame (sr_bigram_params.max_word_ends)", u,
-                              (unsigned long long)per_frame);
-    const uint64_t o = c->frame_off[u] + u;
-    for (uint32_t i = 0; i < counts[u]; i++, n++) { out_word[n] = dw[o + i]; out_score[n] = ds[o + i]; out_time[n] = dt[o + i]; }
-    out_off[u + 1] = n;
+  if (m->gather_device) {
+    const GatherBlock g = gather_block(c);
+    const GatherHeader& h = *g.head;
+    if (h.first_flagged != kGatherNone && h.first_flagged <= h.first_over)
+      return fail(SR_ELIMIT, "utterance %u: more than %llu word ends per frame (sr_bigram_params.max_word_ends)", h.first_flagged,
+                  (unsigned long long)per_frame);
+    // (the search writes at most T + 1 entries; a count beyond them would have made the host's loop read the next utterance's)
+    if (h.first_over != kGatherNone) return fail(SR_ECORRUPT, "utterance %u: %u entries for its frames", h.first_over, h.over_count);
+    memcpy(out_off, g.off, sizeof(uint64_t) * ((size_t)U + 1));
+    if (h.n_words) {
+      memcpy(out_word, g.data, sizeof(uint32_t) * h.n_words);
+      memcpy(out_time, g.data + h.n_words, sizeof(uint32_t) * h.n_words);
+      memcpy(out_score, g.data + 2 * h.n_words, sizeof(float) * h.n_words);
+    }
+  } else {
+    std::vector<uint32_t> counts(U), flags(U), dw(F + U), dt(F + U);
+    std::vector<float> ds(F + U);
+    if (U) {
+      HIP_TRY(hipMemcpy(counts.data(), b->out_count.p, sizeof(uint32_t) * U, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(flags.data(), b->out_flags.p, sizeof(uint32_t) * U, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(dw.data(), b->out_word.p, sizeof(uint32_t) * (F + U), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(dt.data(), b->out_time.p, sizeof(uint32_t) * (F + U), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(ds.data(), b->out_score.p, sizeof(float) * (F + U), hipMemcpyDeviceToHost));
+    }
+    uint64_t n = 0;
+    out_off[0] = 0;
+    for (uint32_t u = 0; u < U; u++) {
+      if (flags[u]) return fail(SR_ELIMIT, "utterance %u: more than %llu word ends per frame (sr_bigram_params.max_word_ends)", u,
+                                (unsigned long long)per_frame);
+      const uint64_t o = c->frame_off[u] + u;
+      for (uint32_t i = 0; i < counts[u]; i++, n++) { out_word[n] = dw[o + i]; out_score[n] = ds[o + i]; out_time[n] = dt[o + i]; }
+      out_off[u + 1] = n;
+    }
   }
   if (ba.gs_active) {  // diagnostic (tools/cliffs.py): positions the global-states search visited per frame
     unsigned long long visited = 0;
