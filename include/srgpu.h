@@ -983,6 +983,16 @@ SR_API int sr_prefilter_masks(sr_model* m, const float* feats, uint64_t n_frames
                               uint64_t cap_words);
 /* The stationary route cuts a launch's frames into ranges; a launch of more than *frames frames has at least two (tests straddle one). */
 SR_API int sr_prefilter_range_frames(uint32_t* frames);
+/* Test hook: the FP64 refinement alone, on candidate masks the caller supplies instead of the prefilter's: uploads `feats` ([n_frames x
+ * dim], host), runs the feature transpose and the refinement (the deferred-leftover route under SRGPU_DEFER_MB / SRGPU_DEFER_CAP as a
+ * scoring call would) and returns the table out[n_frames x n_states]: per (frame, state) the minimum, under strict `<` from 1e10, over
+ * the densities whose bits are set.  masks: sr_prefilter_masks' layout, n_words == n_groups * n_frames * 4 or SR_EINVAL; bits at or
+ * beyond a pseudo-state's density count and slots beyond the last pseudo-state are ignored, so every array of that size is valid. */
+SR_API int sr_refine_masks(sr_model* m, const float* feats, uint64_t n_frames, const uint32_t* masks, uint64_t n_words, double* out);
+/* The refinement's launch geometry for n_frames frames of this model: out[0] threads per workgroup, out[1] pseudo-states per workgroup,
+ * out[2] frames per workgroup (workgroup y of a state group takes frames [y * out[2], (y + 1) * out[2]); the thread (wave, lane) takes
+ * frame y * out[2] + wave * 64 + it * out[0] + lane in iteration it), out[3] chunks of 32 densities per state.  Tests lay masks out by it. */
+SR_API int sr_refine_geometry(sr_model* m, uint64_t n_frames, uint32_t out[4]);
 /* Test hook: the last step of a recognition call alone, on search outputs the caller supplies (host arrays) instead of a search's:
  * utterance u has counts[u] words at words[frame_off[u] ..] and the flags flags[u] (4: its traceback did not walk).  Returns what
  * sr_recognize_corpus would: the words back to back in out_words with out_word_off[n_utts + 1], or SR_ECORRUPT naming the first

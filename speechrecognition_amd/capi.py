@@ -49,6 +49,7 @@ SYMBOLS = [
     "sr_bigram_stream_open", "sr_bigram_stream_begin", "sr_bigram_stream_push", "sr_bigram_stream_partial", "sr_bigram_stream_end",
     "sr_bigram_stream_destroy",
     "sr_probe_fp16_denormals", "sr_probe_fp16_accumulation", "sr_prefilter_masks", "sr_prefilter_range_frames",
+    "sr_refine_masks", "sr_refine_geometry",
     "sr_gather_words",
     "sr_profile_enable", "sr_profile_reset", "sr_profile_read",
 ]
@@ -192,6 +193,8 @@ def lib():
         L.sr_probe_fp16_accumulation.argtypes = [i32, C.POINTER(i32), C.POINTER(dbl)]
         L.sr_prefilter_masks.argtypes = [vp, vp, u64, i32, C.POINTER(u32), vp, u64]
         L.sr_prefilter_range_frames.argtypes = [C.POINTER(u32)]
+        L.sr_refine_masks.argtypes = [vp, vp, u64, vp, u64, vp]
+        L.sr_refine_geometry.argtypes = [vp, u64, vp]
         L.sr_gather_words.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
         L.sr_profile_enable.argtypes = [vp, i32]
         L.sr_profile_reset.argtypes = [vp]
@@ -354,6 +357,22 @@ class Model:
         out = np.empty((n_groups.value, feats.shape[0], 4), dtype=np.uint32)
         _check(lib().sr_prefilter_masks(self.h, _ptr(feats), feats.shape[0], route, C.byref(n_groups), _ptr(out), out.size))
         return out
+
+    def refine_masks(self, feats, masks):
+        """sr_refine_masks (test hook): the refinement alone on the caller's candidate masks [group][frame][4 state slots] (the layout
+        prefilter_masks returns) -> the score table [frames, states]."""
+        feats = np.ascontiguousarray(feats, dtype=np.float32)
+        masks = np.ascontiguousarray(masks, dtype=np.uint32)
+        out = np.empty((feats.shape[0], self.n_states), dtype=np.float64)
+        _check(lib().sr_refine_masks(self.h, _ptr(feats), feats.shape[0], _ptr(masks), masks.size, _ptr(out)))
+        return out
+
+    def refine_geometry(self, n_frames):
+        """sr_refine_geometry -> (threads per workgroup, pseudo-states per workgroup, frames per workgroup, chunks per state) of a
+        refinement launch over n_frames"""
+        g = np.zeros(4, dtype=np.uint32)
+        _check(lib().sr_refine_geometry(self.h, int(n_frames), _ptr(g)))
+        return tuple(int(v) for v in g)
 
     def gather_words(self, frame_off, counts, flags, words):
         """sr_gather_words (test hook): (words, word_off) that a recognition call would return for these search outputs."""

@@ -1376,6 +1376,13 @@ size_t gmm_refine_ring_words(const GmmRefineArgs& a) {
   return (size_t)g * sp * kRWaves * kRingWave;
 }
 
+void gmm_refine_geometry(const GmmRefineArgs& a, uint32_t out[4]) {
+  uint32_t g; uint64_t sp, fps;
+  const int spw = refine_spw(a);
+  refine_grid(a, spw, &g, &sp, &fps);
+  out[0] = (uint32_t)refine_threads(a.dim); out[1] = (uint32_t)spw; out[2] = (uint32_t)fps; out[3] = a.chunks;
+}
+
 // how many entries a wave's segment of one panel holds: a quarter of the wave's (frame, panel) pairs (configs[4]: 5 % of them are listed)
 static uint32_t defer_cap_for(const GmmRefineArgs& a, int spw) {
   uint32_t g; uint64_t sp, fps;

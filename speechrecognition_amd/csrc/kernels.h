@@ -106,6 +106,9 @@ struct GmmRefineArgs {
 void gmm_refine_defer_layout(const GmmRefineArgs& a, size_t budget_bytes, uint32_t cap_limit, uint32_t* cap, size_t* n_entries,
                              size_t* n_counts);
 size_t gmm_refine_ring_words(const GmmRefineArgs& a);  // needs n_frames, n_pstates, dim, n_slots
+// the grid launch_gmm_refine gives this shape (same fields): threads per workgroup, pseudo-states per workgroup, frames per workgroup,
+// chunks per state -- thread (wave, lane) of the workgroup over split y takes frame y * out[2] + wave * 64 + it * out[0] + lane in iteration it
+void gmm_refine_geometry(const GmmRefineArgs& a, uint32_t out[4]);
 // route: kPfStaged -- frames stationary, the model streamed through LDS (needs split_begin, nx, ny); kPfStationary -- a 4-state group
 // stationary in a wave's registers, the frames' ready-made operands streamed past it (needs n_groups, bfrag, bnorm; builds the
 // operands first).  ks32 = 4 has no stationary instantiation (its A operand alone is 128 registers) and takes the staged kernel on

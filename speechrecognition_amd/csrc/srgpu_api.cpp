@@ -252,6 +252,10 @@ int pack_prefilter(sr_model* m, const uint32_t* dens_off, const double* means, c
         const uint32_t st = ps < PS ? ps / Cs : 0;
         std::fill(arow.begin(), arow.end(), 0.0);
         double konst = (double)finf;  // padding slot: never below a real score, masked off again by the refinement
+        // A state slot beyond the last pseudo-state has no real score to stay above: with +inf everywhere its minimum is +inf, and
+        // inf <= inf + limit made every one of its 32 densities a "candidate" (0xFFFFFFFF in words nobody reads).  Its rows score 0
+        // and its limit is negative (below): 0 > 0 - 1, no candidate, the word is 0 for every frame that is a number.
+        if (ps >= PS) konst = 0.0;
         if (real) {
           konst = coeffs((size_t)dens_off[st] + 32u * (ps % Cs) + i, arow) * sA;
           double n2 = 0.0, d2 = 0.0, h2 = 0.0;
@@ -314,6 +318,7 @@ int pack_prefilter(sr_model* m, const uint32_t* dens_off, const double* means, c
       v[1] = res ? limd_res : 0.0f;
       v[2] = lim0;
       v[3] = 0.0f;
+      if (slot >= PS) { v[0] = 0.0f; v[1] = 0.0f; v[2] = -1.0f; }  // a slot without a pseudo-state: all rows score 0, none is <= 0 - 1
     }
   }
   HIP_TRY(m->pf_lim.upload(anorm.data(), anorm.size()));
@@ -466,6 +471,22 @@ int prefilter_args(sr_model* m, const float* d_feats, uint64_t n_frames, GmmPref
   return SR_OK;
 }
 
+// the refinement's arguments for a launch over n_frames into d_out (row stride m->ld; the workspaces are reserve_scoring's): the feature
+// buffers launch_transpose_feats fills, the deferred-leftover segments where their layout (SRGPU_DEFER_MB / SRGPU_DEFER_CAP) fits what is
+// reserved, the evaluation counter while profiling
+GmmRefineArgs refine_args(sr_model* m, const float* d_feats, uint64_t n_frames, double* d_out) {
+  GmmRefineArgs ra = refine_shape(m, n_frames);
+  const bool padded = m->pf_dp != m->dim;
+  ra.feats = padded ? m->featsP.p : d_feats; ra.featsT = m->featsT.p; ra.n_frames_ld = (n_frames + 63) & ~(uint64_t)63;
+  ra.n_dens_ps = m->pf_ndens.p; ra.rows = m->pf_rows.p;
+  ra.mask = m->pf_mask.p; ra.out = d_out; ra.ld = m->ld;
+  ra.n_refined = m->profiling ? m->pf_counter.p : nullptr;
+  ra.ring = m->pf_ring.p;
+  const DeferLayout dl = defer_layout(m, n_frames);
+  if (dl.cap && dl.n_e <= m->pf_defer.n && dl.n_c <= m->pf_defer_cnt.n) { ra.defer = m->pf_defer.p; ra.defer_cnt = m->pf_defer_cnt.p; ra.defer_cap = dl.cap; }
+  return ra;
+}
+
 // score frames [f_begin, f_end) of `feats` into `out` (device, row stride m->ld) on stream s_gmm
 int launch_scoring(sr_model* m, const float* d_feats, uint64_t n_frames, int gmm_kernel, double* d_out) {
   if (n_frames == 0) return SR_OK;
@@ -491,16 +512,9 @@ int launch_scoring(sr_model* m, const float* d_feats, uint64_t n_frames, int gmm
     GmmPrefilterArgs pa{};
     int rc = prefilter_args(m, d_feats, n_frames, &pa);
     if (rc) return rc;
-    const uint64_t ldT = (n_frames + 63) & ~(uint64_t)63;
-    GmmRefineArgs ra = refine_shape(m, n_frames);
+    const GmmRefineArgs ra = refine_args(m, d_feats, n_frames, d_out);
+    const uint64_t ldT = ra.n_frames_ld;
     const bool padded = m->pf_dp != m->dim;
-    ra.feats = padded ? m->featsP.p : d_feats; ra.featsT = m->featsT.p; ra.n_frames_ld = ldT;
-    ra.n_dens_ps = m->pf_ndens.p; ra.rows = m->pf_rows.p;
-    ra.mask = m->pf_mask.p; ra.out = d_out; ra.ld = m->ld;
-    ra.n_refined = m->profiling ? m->pf_counter.p : nullptr;
-    ra.ring = m->pf_ring.p;
-    const DeferLayout dl = defer_layout(m, n_frames);
-    if (dl.cap && dl.n_e <= m->pf_defer.n && dl.n_c <= m->pf_defer_cnt.n) { ra.defer = m->pf_defer.p; ra.defer_cnt = m->pf_defer_cnt.p; ra.defer_cap = dl.cap; }
     if (m->profiling) m->prof.refined_pairs += n_frames * (uint64_t)m->n_states;
     EventPair ep_p{}, ep_r{};
     if ((rc = prof_begin(m, m->s_gmm, 0, &ep))) return rc;
@@ -1117,6 +1131,55 @@ int sr_prefilter_masks(sr_model* m, const float* feats, uint64_t n_frames, int r
   HIP_TRY(launch_gmm_prefilter(pa, m->pf_ks32, route, m->s_gmm));
   HIP_TRY(hipStreamSynchronize(m->s_gmm));
   HIP_TRY(hipMemcpy(masks, m->pf_mask.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return SR_OK;
+  });
+}
+
+// test hook: the refinement alone on candidate masks the caller supplies, in sr_prefilter_masks' layout [group][frame][4 state slots].
+// Any mask word is in range for the kernel (it clears the bits beyond a pseudo-state's densities and ignores the slots beyond the last
+// one); what the host checks is the array's size.  Nothing on a scoring path calls this.
+int sr_refine_masks(sr_model* m, const float* feats, uint64_t n_frames, const uint32_t* masks, uint64_t n_words, double* out) {
+  return guarded(__func__, [&]() -> int {
+  int rc = check_model(m);
+  if (rc) return rc;
+  if (!m->max_approx) return fail(SR_EINVAL, "the refinement scores max-approx models only");
+  if (n_frames >= (1ull << 30)) return fail(SR_ELIMIT, "n_frames %llu: the refinement's lists hold 30-bit frame numbers", (unsigned long long)n_frames);
+  if ((rc = reserve_scoring(m, SR_GMM_PREFILTER, n_frames))) return rc;
+  if (m->pf_ks32 == 0) return fail(SR_EINVAL, "this model is not scored through the prefilter");
+  const uint64_t words = (uint64_t)m->pf_groups * n_frames * 4;
+  if (n_words != words) return fail(SR_EINVAL, "masks holds %llu words, %u groups x %llu frames x 4 = %llu expected", (unsigned long long)n_words,
+                                    m->pf_groups, (unsigned long long)n_frames, (unsigned long long)words);
+  if (n_frames == 0) return SR_OK;
+  if (!feats || !masks || !out) return fail(SR_EINVAL, "%s is null", !feats ? "feats" : !masks ? "masks" : "out");
+  DevBuf<float> d_feats;
+  DevBuf<double> d_out;
+  HIP_TRY(d_feats.ensure((size_t)n_frames * m->dim + 64));
+  HIP_TRY(d_out.ensure((size_t)n_frames * m->ld));
+  HIP_TRY(hipMemcpy(d_feats.p, feats, (size_t)n_frames * m->dim * sizeof(float), hipMemcpyHostToDevice));
+  const GmmRefineArgs ra = refine_args(m, d_feats.p, n_frames, d_out.p);
+  // (the kernel reads group pairs: the pair's second half beyond an odd group count holds no pseudo-state)
+  HIP_TRY(hipMemsetAsync(m->pf_mask.p, 0, (size_t)((m->pf_groups + 1u) & ~1u) * n_frames * 4 * sizeof(uint32_t), m->s_gmm));
+  HIP_TRY(hipMemcpyAsync(m->pf_mask.p, masks, words * sizeof(uint32_t), hipMemcpyHostToDevice, m->s_gmm));
+  HIP_TRY(launch_transpose_feats(d_feats.p, n_frames, m->dim, m->pf_dp, ra.n_frames_ld, m->featsT.p, m->pf_dp != m->dim ? m->featsP.p : nullptr, m->s_gmm));
+  HIP_TRY(launch_gmm_refine(ra, m->s_gmm));
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  HIP_TRY(hipMemcpy2D(out, (size_t)m->n_states * sizeof(double), d_out.p, (size_t)m->ld * sizeof(double), (size_t)m->n_states * sizeof(double),
+                      (size_t)n_frames, hipMemcpyDeviceToHost));
+  return SR_OK;
+  });
+}
+
+// test hook: the geometry launch_gmm_refine gives a launch over n_frames -- threads per workgroup, pseudo-states per workgroup, frames
+// per workgroup (split of the frame range), chunks per state
+int sr_refine_geometry(sr_model* m, uint64_t n_frames, uint32_t out[4]) {
+  return guarded(__func__, [&]() -> int {
+  int rc = check_model(m);
+  if (rc) return rc;
+  if (!out) return fail(SR_EINVAL, "out is null");
+  if (!m->max_approx) return fail(SR_EINVAL, "the refinement scores max-approx models only");
+  if ((rc = reserve_scoring(m, SR_GMM_PREFILTER, 0))) return rc;  // (packs the model on first use; no workspace for 0 frames)
+  if (m->pf_ks32 == 0) return fail(SR_EINVAL, "this model is not scored through the prefilter");
+  gmm_refine_geometry(refine_shape(m, n_frames), out);
   return SR_OK;
   });
 }

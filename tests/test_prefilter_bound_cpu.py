@@ -7,75 +7,10 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
-F32, F16 = np.float32, np.float16
-KAPPA16, KRES16 = F32(1.05e-3), F32(4.8835e-4)
+from tests.prefilter_reference import F32, KRES16, emulated_scores, frame_side, limits, midpoints, pack_model
 
-
-def bound_consts(ks32):
-    """(acc, abs, sub) of pf_bound(ks32) (kernels.h)."""
-    return (F32(1.6e-5), F32(7.0e-7), F32(3.38e-7)) if ks32 == 4 else (F32(1.1e-5), F32(6.0e-7), F32(2.92e-7))
-
-
-def to_f16(v):
-    """double -> float -> _Float16, as the host packs (and float -> _Float16, as the kernel packs)."""
-    return np.asarray(v, dtype=np.float64).astype(F32).astype(F16).astype(np.float64)
-
-
-def up(v):
-    """The host's rounding up of a norm to float."""
-    return np.nextafter((np.asarray(v, dtype=np.float64) * (1.0 + 1e-6)).astype(F32), F32(np.inf))
-
-
-def pack_model(A, konst):
-    """Scaled fp16 coefficients, the 3-term konst expansion and the per-density norms the host computes (pack_prefilter)."""
-    big = max(np.max(np.abs(A)), np.max(np.abs(konst)))
-    sA = 2.0 ** (13 - int(np.floor(np.log2(big))))
-    As, ks = A * sA, konst * sA
-    Ah = to_f16(As)
-    kexp, rest = [], ks.copy()
-    for _ in range(3):
-        c = to_f16(rest)
-        kexp.append(c)
-        rest = rest - c
-    norms = np.stack([up(np.sqrt(np.sum(As * As, 1))), up(np.abs(ks)), up(np.sqrt(np.sum((Ah - As) ** 2, 1))),
-                      up(np.sqrt(np.sum(Ah * Ah, 1)))], 1)
-    return As, ks, Ah, np.stack(kexp, 1), norms
-
-
-def frame_side(X):
-    """b = [x^2; x] interleaved, its fp16 image, and the kernel's bnorm and dbnorm (fp32, rounded up, dbnorm capped)."""
-    T, D = X.shape
-    X = X.astype(F32)
-    b32 = np.empty((T, 2 * D), F32)
-    b32[:, 0::2], b32[:, 1::2] = X * X, X
-    bh = b32.astype(F16).astype(np.float64)
-    bex = np.empty((T, 2 * D))
-    bex[:, 0::2], bex[:, 1::2] = X.astype(np.float64) ** 2, X
-    e = (bex - bh).astype(F32)  # fmaf(x, x, -b^) rounds the exact residual once; x - b^ is exact
-    n2, e2 = np.zeros(T, F32), np.zeros(T, F32)
-    for k in range(2 * D):
-        n2 = (n2 + b32[:, k] * b32[:, k]).astype(F32)
-        e2 = (e2 + e[:, k] * e[:, k]).astype(F32)
-    bnorm = (np.sqrt(n2) * F32(1.0001)).astype(F32)
-    dbn = np.minimum((np.sqrt(e2) * F32(1.0001)).astype(F32), (KRES16 * bnorm).astype(F32))
-    return bh, bex, bnorm, dbn
-
-
-def limits(nk, bnorm, dbn, ks32):
-    """2 eps per (frame, state): (residual form, norm-only form) -- the host's folding of the state's norms into
-    (lim1, limD, lim0) (pack_prefilter) and the kernel's limD |b^ - b| + lim1 |b| + lim0 in fp32."""
-    kacc, kabs, ksub = bound_consts(ks32)
-    na, nko, nd, nh = (nk[:, i].astype(F32) for i in range(4))
-    lim0 = F32(2) * (kacc * nko + kabs * na)
-    lim1_norm = F32(2) * (KAPPA16 * na + kabs)
-    lim1_res = up(2.0 * (nd.astype(np.float64) + float(kacc) * nh + float(kabs)))
-    limd_res = up(2.0 * (1.0 + float(kacc)) * nh.astype(np.float64))
-    res = ((limd_res.astype(np.float64) * float(KRES16) + lim1_res <= lim1_norm * (1.0 - 2.0**-12))
-           & ((1.0 + float(kacc)) * float(ksub) * nh.astype(np.float64) <= float(kabs) * na.astype(np.float64)))
-    lim1, limd = np.where(res, lim1_res, lim1_norm), np.where(res, limd_res, F32(0))
-    new = (limd[None] * dbn[:, None] + (lim1[None] * bnorm[:, None] + lim0[None])).astype(F32)
-    old = (lim1_norm[None] * bnorm[:, None] + lim0[None]).astype(F32)
-    return new, old, res
+# (the restatement itself -- bound_consts, to_f16, up, pack_model, frame_side, limits, emulated_scores, midpoints -- lives in
+# tests/prefilter_reference.py, shared with the tests that hold the device's masks against it)
 
 
 def check(A, konst, states, X):
@@ -84,11 +19,7 @@ def check(A, konst, states, X):
     ks32 = (2 * D + 3 + 31) // 32
     As, ks, Ah, kexp, norms = pack_model(A, konst)
     bh, bex, bnorm, dbn = frame_side(X)
-    approx = np.zeros((T, len(A)), F32)  # products of two fp16 values are exact in fp32; fp32 accumulation in k order
-    for k in range(2 * D):
-        approx = (approx + (bh[:, k:k + 1] * Ah[None, :, k]).astype(F32)).astype(F32)
-    for t in range(3):
-        approx = (approx + kexp[None, :, t].astype(F32)).astype(F32)
+    approx = emulated_scores(Ah, kexp, bh)
     exact = ks[None] + bex @ As.T
     nst = np.stack([np.max(norms[s], 0) for s in states])  # per-state maxima
     new, old, res = limits(nst, bnorm, dbn, ks32)
@@ -118,12 +49,6 @@ def model(rng, S, M, D, tie=False):
     A[:, 0::2], A[:, 1::2] = 0.5 / var, -mu / var
     konst = 0.5 * np.sum(np.log(2 * np.pi * var) + mu * mu / var, 1) + np.log(M)
     return A, konst, [np.arange(s * M, (s + 1) * M) for s in range(S)]
-
-
-def midpoints(rng, shape, lo=-6, hi=3):
-    """Values exactly halfway between two neighbouring fp16 numbers (fp16 rounding's worst case)."""
-    m = rng.integers(1024, 2048, size=shape) + 0.5
-    return m * np.exp2(rng.integers(lo, hi, size=shape) - 10.0) * rng.choice([-1.0, 1.0], size=shape)
 
 
 def test_bench_distribution_halves_the_second_candidates():
