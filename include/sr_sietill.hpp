@@ -1256,6 +1256,68 @@ class MeanAdaptation {
   double min_count_;
 };
 
+// ---- MAP adaptation of the means and weights (srgpu.h: sr_map_statistics_*, sr_model_map_adapt) ---------------------------------
+// Every density a speaker's data reached moves towards that data, (tau mu + X) / (tau + O); every other density stays.  The statistics
+// come from the trainer's re-alignment; a speaker is then recognised or aligned with its own adapted model: upload that speaker's
+// utterances to adapted_model(...).  To iterate, re-align under the adapted model and adapt the speaker-independent model again.
+class MapAdaptation {
+ public:
+  struct Result {
+    uint32_t n_speakers = 0;
+    std::vector<uint64_t> ent_off;    // [n_speakers + 1] speaker s owns entries ent_off[s] .. ent_off[s + 1]
+    std::vector<uint32_t> dens;       // [n_entries] density id in mixture order, ascending within a speaker
+    std::vector<double> occ;          // [n_entries] sum gamma
+    std::vector<double> x;            // [n_entries x D] sum gamma x
+  };
+
+  MapAdaptation(Trainer& trainer, MixtureModel& mixtures) : trainer_(trainer), mixtures_(mixtures) {}
+
+  // re-align, take the statistics of the alignment per (speaker, density): the sizing call, then the filled call
+  Result adapt(Corpus const& corpus) {
+    const size_t n = corpus.get_corpus_size(), D = mixtures_.dimension;
+    const uint64_t F = corpus.get_total_frame_count();
+    std::vector<uint32_t> const& spk = corpus.speakers();
+    uint32_t S = 0;
+    for (uint32_t s : spk) S = std::max(S, s + 1);
+    if (S == 0) throw std::runtime_error("MapAdaptation: empty corpus");
+    std::vector<AlignmentItem> alignment;
+    trainer_.realign(corpus, alignment);
+    std::vector<uint16_t> states(std::max<uint64_t>(F, 1));
+    for (uint64_t t = 0; t < F; t++) states[t] = (uint16_t)alignment[t].state;
+    sr_corpus* c = nullptr;
+    check(sr_corpus_upload(mixtures_.handle(), corpus.features(), corpus.frame_offsets(), (uint32_t)n, &c));
+    std::shared_ptr<sr_corpus> original(c, sr_corpus_destroy);
+    const int max_approx = mixtures_.max_approx() ? 1 : 0;
+    Result r;
+    r.n_speakers = S;
+    r.ent_off.assign((size_t)S + 1, 0);
+    check(sr_map_statistics_corpus(mixtures_.handle(), c, states.data(), spk.data(), S, max_approx, 0, r.ent_off.data(), nullptr, nullptr,
+                                   nullptr));
+    const uint64_t cap = r.ent_off[S];
+    r.dens.assign(std::max<uint64_t>(cap, 1), 0); r.occ.assign(std::max<uint64_t>(cap, 1), 0.0); r.x.assign(std::max<uint64_t>(cap, 1) * D, 0.0);
+    check(sr_map_statistics_corpus(mixtures_.handle(), c, states.data(), spk.data(), S, max_approx, cap, r.ent_off.data(), r.dens.data(),
+                                   r.occ.data(), r.x.data()));
+    r.dens.resize(cap); r.occ.resize(cap); r.x.resize(cap * D);
+    return r;
+  }
+
+  // the model of one speaker (sr_model_map_adapt) with mixtures as the prior -- or `prior`, e.g. MeanAdaptation::adapted_model's
+  // result for MAP on top of MLLR; tau_w > 0: the mixture weights are updated too
+  std::shared_ptr<sr_model> adapted_model(Result const& r, uint32_t speaker, double tau, double tau_w = 0.0, sr_model* prior = nullptr) const {
+    const size_t D = mixtures_.dimension;
+    if (speaker >= r.n_speakers) throw std::runtime_error("MapAdaptation: no such speaker");
+    const uint64_t e0 = r.ent_off[speaker], ne = r.ent_off[speaker + 1] - e0;
+    sr_model* out = nullptr;
+    check(sr_model_map_adapt(prior ? prior : mixtures_.handle(), ne, r.dens.data() + e0, r.occ.data() + e0, r.x.data() + e0 * D, tau,
+                             tau_w > 0.0 ? 1 : 0, tau_w, &out));
+    return std::shared_ptr<sr_model>(out, sr_model_destroy);
+  }
+
+ private:
+  Trainer& trainer_;
+  MixtureModel& mixtures_;
+};
+
 // ---- MLLT, the global semi-tied covariance transform (srgpu.h: sr_mllt_*) --------------------------------------------------------
 // One square matrix A for the whole feature space, estimated by maximum likelihood from the trainer's re-alignment so that the model's
 // diagonal covariances fit as well as they can; features and means both move (y = A x, mu' = A mu).  The variances are re-estimated

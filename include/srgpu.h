@@ -462,6 +462,53 @@ SR_API int sr_mllr_estimate(uint32_t dim, uint32_t n_speakers, uint32_t n_classe
  * in different classes; SR_ELIMIT for a dimension above 63. */
 SR_API int sr_model_transform_means(sr_model* m, const uint32_t* dens_class, uint32_t n_classes, const double* W, sr_model** out);
 
+/* ---- MAP adaptation of the means and weights (Gauvain & Lee 1994, relevance form) ---------------------------------------------
+ * Every density that a speaker's data reached moves towards that data, every other density stays where it was; nothing ties one
+ * density's update to another's.  The statistics are the per-(speaker, density) sums that the MLLR statistics form on the way:
+ * Pairs.  The (frame, density, gamma) pairs are exactly those of sr_mllr_statistics_corpus / sr_mllr_statistics_bw_corpus; a dropped
+ *   pair stays dropped.
+ * Entries.  An entry is a (speaker, density) with at least one kept pair.  Entries come out in ascending (speaker, density); speaker
+ *   s owns entries out_ent_off[s] .. out_ent_off[s + 1]; out_dens is the density id in mixture order.
+ * Values.  Everything is FP64 with no fused multiply-add: occ = sum gamma, x[i] = sum gamma * (double) x_ti.
+ * Order of summation (this is the specification).  An entry's pairs are in the order they were formed, frames ascending.  They are cut
+ *   into segments of 1024 pairs.  Within a segment there is one chain per value, starting at 0.0: sum = sum + gamma * (double) x, the
+ *   product rounded, then the addition.  The segments' partials are then added in ascending order to a total that starts at 0.0.  The
+ *   order depends on the pairs alone, never on the launch; no atomics, so two identical calls return identical bits.  Statistics of
+ *   corpus shards add up, as sr_accumulate_corpus' do.
+ * Sizing (the convention of sr_word_lattice_corpus).  out_ent_off[n_speakers + 1] is required and always written.  The three entry
+ *   arrays -- out_dens[cap], out_occ[cap], out_x[cap x D] -- are given all or none.  None: the sizing call, SR_OK with the counts in
+ *   out_ent_off.  Given but the total exceeds cap: nothing is written to the arrays, out_ent_off still holds the counts needed,
+ *   SR_EINVAL.  With max_approx and an alignment every frame forms one pair, so cap = total_frames always suffices.
+ * Errors, all before any launch: SR_EINVAL for a NULL m, c or out_ent_off, a partial set of arrays, n_speakers == 0,
+ *   utt_speaker[u] >= n_speakers; SR_ELIMIT for n_speakers * n_densities >= 2^32 - 1 (the 32-bit keys, as MLLR); otherwise the errors of
+ *   sr_accumulate_corpus / sr_baum_welch_corpus.  There is no dimension limit beyond the model's own 160: nothing here uses the matrix
+ *   cores.  Device memory: 52 bytes per pair, 8 (D + 2) bytes per entry and 8 (D + 1) per segment of an entry of more than one. */
+SR_API int sr_map_statistics_corpus(sr_model* m, sr_corpus* c, const uint16_t* states, const uint32_t* utt_speaker,
+                                    uint32_t n_speakers, int max_approx, uint64_t cap, uint64_t* out_ent_off /*[n_speakers+1]*/,
+                                    uint32_t* out_dens /*[cap]*/, double* out_occ /*[cap]*/, double* out_x /*[cap*D]*/);
+SR_API int sr_map_statistics_bw_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off,
+                                       const double tdp[3], uint16_t silence_state, int gmm_kernel, double posterior_floor,
+                                       const uint32_t* utt_speaker, uint32_t n_speakers, int max_approx, double* out_cost,
+                                       uint64_t cap, uint64_t* out_ent_off, uint32_t* out_dens, double* out_occ, double* out_x);
+
+/* The adapted model from one speaker's slice of the statistics (dens strictly ascending): a new device model with prior's topology
+ * and tying, built like sr_model_transform_means' result (the scoring kernels' packed tables on first use).
+ * Means.  For a mean row r (sr_model_set_tying): O_r is the sum of occ over the row's entries, X_ri the sum of x_i over the same
+ *   entries, both in ascending density id, each a chain from 0.0.  mu'_ri = (tau * mu_ri + X_ri) / (tau + O_r): one multiplication,
+ *   two additions and one division, each rounded, no contraction.  Every density of the row gets those bits.  A row without an entry
+ *   keeps prior's bits exactly.
+ * inv_vars and norm are always prior's bits; without update_weights, logw is too.
+ * Weights.  With update_weights, for every mixture that has at least one entry: w_d = exp(logw_d) through the host's libm,
+ *   n_d = tau_w * w_d + occ_d (occ_d = 0.0 where there is no entry), logw'_d = log(n_d / N) with N the sum of n_d in mixture order,
+ *   through the host's log (sr_model_eliminate's rule for where the logarithm is taken).  Mixtures without an entry keep their bits.
+ * prior may be any model of the right topology -- the result of sr_model_transform_means gives MAP with an MLLR-adapted prior.
+ * n_entries == 0 is valid: every table equals prior's, bit for bit.
+ * Errors, all before any launch, *out left NULL: SR_EINVAL for a NULL prior or out, NULL arrays with n_entries > 0, dens not strictly
+ * ascending or >= n_densities, an occ that is not finite or not > 0, an x that is not finite, tau negative, NaN or infinite, and with
+ * update_weights a tau_w that is not finite or not > 0. */
+SR_API int sr_model_map_adapt(sr_model* prior, uint64_t n_entries, const uint32_t* dens, const double* occ, const double* x,
+                              double tau, int update_weights, double tau_w, sr_model** out);
+
 /* ---- MLLT: the global semi-tied covariance transform (Gales 1999, one transform class) --------------------------------------------
  * One square matrix A for the feature space, y = A x with the means following by mu' = A mu, chosen so that the model's diagonal
  * covariances fit as well as they can: the "MLLT" of the LDA + MLLT + fMLLR pipeline.  With z = (double) x_t - mu_d and iv = 1/var of

@@ -20,10 +20,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsrgpu.so")
 SOURCES = ["srgpu_api.cpp", "mixset.cpp", "feeder.cpp", "gmm_mfma.hip", "gmm_exact.hip", "gmm_prefilter.hip", "viterbi_decode.hip",
            "viterbi_fast.hip", "viterbi_words.hip", "viterbi_align.hip", "viterbi_fb.hip", "viterbi_netfb.hip", "viterbi_mmi.hip", "viterbi_smbr.hip", "viterbi_lattice.hip", "viterbi_bigram.hip", "viterbi_bigram_fb.hip", "viterbi_bigram_mmi.hip", "viterbi_bigram_smbr.hip", "viterbi_bigram_lattice.hip", "posterior_items.hip",
-           "em_accumulate.hip", "em_finalize.hip", "fmllr_stats.hip", "fmllr.cpp", "mllr_stats.hip", "mllt_stats.hip", "lda_stats.hip", "model_structure.hip",
+           "em_accumulate.hip", "em_finalize.hip", "fmllr_stats.hip", "fmllr.cpp", "mllr_stats.hip", "map_stats.hip", "mllt_stats.hip", "lda_stats.hip", "model_structure.hip",
            "gather_words.hip"]
-# (mllr.cpp, mllt.cpp and lda.cpp are included by fmllr.cpp: listed with the headers so that their content enters the stamps)
-HEADERS = ["mllr.cpp", "mllt.cpp", "lda.cpp", "kernels.h", "host_util.h", "handles.h", "traceback.h", "dpp_util.h", "netfb_device.h", "smbr_device.h", "sym_contract.h", "structure_plan.h", "fb_plan.h", os.path.join("..", "..", "include", "srgpu.h")]
+# (mllr.cpp, mllt.cpp, lda.cpp and map.cpp are included by fmllr.cpp: listed with the headers so that their content enters the stamps)
+HEADERS = ["mllr.cpp", "mllt.cpp", "lda.cpp", "map.cpp", "kernels.h", "host_util.h", "handles.h", "traceback.h", "dpp_util.h", "netfb_device.h", "smbr_device.h", "sym_contract.h", "structure_plan.h", "fb_plan.h", os.path.join("..", "..", "include", "srgpu.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 # these replay the reference's SSE2 operation order and must not contract a*b+c into an FMA
 PER_FILE = {"gmm_exact.hip": ["-ffp-contract=off"], "gmm_prefilter.hip": ["-ffp-contract=off"], "em_accumulate.hip": ["-ffp-contract=off"],
@@ -34,6 +34,8 @@ PER_FILE = {"gmm_exact.hip": ["-ffp-contract=off"], "gmm_prefilter.hip": ["-ffp-
             "fmllr_stats.hip": ["-ffp-contract=off"],
             # sr_model_transform_means' additions likewise; the entry sums replay em_accumulate.hip's
             "mllr_stats.hip": ["-ffp-contract=off"],
+            # the MAP sums: a product, then an addition, segment by segment; the adapted mean's four operations
+            "map_stats.hip": ["-ffp-contract=off"],
             # the products z_j z_k are rounded before the matrix instruction adds them: the statistic's error bound counts on it
             "mllt_stats.hip": ["-ffp-contract=off"],
             # sr_corpus_splice_transform's multiplications and additions, one by one in the documented order

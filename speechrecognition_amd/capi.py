@@ -38,6 +38,7 @@ SYMBOLS = [
     "sr_word_lattice_corpus", "sr_lattice_nbest",
     "sr_fmllr_statistics_corpus", "sr_fmllr_statistics_bw_corpus", "sr_fmllr_estimate", "sr_corpus_transform",
     "sr_mllr_statistics_corpus", "sr_mllr_statistics_bw_corpus", "sr_mllr_estimate", "sr_model_transform_means",
+    "sr_map_statistics_corpus", "sr_map_statistics_bw_corpus", "sr_model_map_adapt",
     "sr_mllt_statistics_corpus", "sr_mllt_statistics_bw_corpus", "sr_mllt_estimate",
     "sr_lda_statistics_corpus", "sr_lda_estimate", "sr_corpus_splice_transform",
     "sr_bigram_create", "sr_bigram_destroy", "sr_bigram_describe", "sr_recognize_bigram_corpus",
@@ -149,6 +150,9 @@ def lib():
                                                    vp]
         L.sr_mllr_estimate.argtypes = [u32, u32, u32, u32, vp, vp, vp, vp, dbl, vp, vp, vp]
         L.sr_model_transform_means.argtypes = [vp, vp, u32, vp, C.POINTER(vp)]
+        L.sr_map_statistics_corpus.argtypes = [vp, vp, vp, vp, u32, i32, u64, vp, vp, vp, vp]
+        L.sr_map_statistics_bw_corpus.argtypes = [vp, vp, vp, vp, C.POINTER(dbl * 3), C.c_uint16, i32, dbl, vp, u32, i32, vp, u64, vp, vp, vp, vp]
+        L.sr_model_map_adapt.argtypes = [vp, u64, vp, vp, vp, dbl, i32, dbl, C.POINTER(vp)]
         L.sr_mllt_statistics_corpus.argtypes = [vp, vp, vp, i32, vp, vp]
         L.sr_mllt_statistics_bw_corpus.argtypes = [vp, vp, vp, vp, C.POINTER(dbl * 3), C.c_uint16, i32, dbl, i32, vp, vp, vp]
         L.sr_mllt_estimate.argtypes = [u32, dbl, vp, u32, dbl, vp, vp, vp, vp]
@@ -325,6 +329,19 @@ class Model:
         assert len(cls) == self.n_densities and W.ndim == 3 and W.shape[1:] == (self.dim, self.dim + 1)
         h = C.c_void_p()
         _check(lib().sr_model_transform_means(self.h, _ptr(cls), W.shape[0], _ptr(W), C.byref(h)))
+        return Model(h)
+
+    def map_adapt(self, dens, occ, x, tau, tau_w=None):
+        """MAP: a new Model whose means are (tau mu + X) / (tau + O) per mean row, from one speaker's entries (dens u32[n] strictly
+        ascending, occ f64[n], x f64[n, D]: a slice of Corpus.map_statistics); tau_w not None: the mixture weights are updated too,
+        n_d = tau_w w_d + occ_d (sr_model_map_adapt).  This model is the prior; topology, tying and variances are its own."""
+        dens = np.ascontiguousarray(dens, dtype=np.uint32)
+        occ = np.ascontiguousarray(occ, dtype=np.float64)
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(len(dens), self.dim)
+        assert len(occ) == len(dens)
+        h = C.c_void_p()
+        _check(lib().sr_model_map_adapt(self.h, len(dens), _ptr(dens), _ptr(occ), _ptr(x), float(tau), int(tau_w is not None),
+                                        float(tau_w if tau_w is not None else 0.0), C.byref(h)))
         return Model(h)
 
     def close(self):
@@ -753,6 +770,37 @@ class Corpus:
                                                   _ptr(spk), n_speakers, _ptr(cls), n_classes, int(max_approx), _ptr(cost), _ptr(beta),
                                                   _ptr(k), _ptr(G)))
         return cost[: self.n_utts], (beta, k, G)
+
+    def _map_statistics(self, call, n_speakers):
+        """the sizing call, then the filled call -> (ent_off u64[S+1], dens u32[n], occ f64[n], x f64[n, D])"""
+        D = self.model.dim
+        ent_off = np.zeros(n_speakers + 1, np.uint64)
+        _check(call(0, ent_off, None, None, None))
+        n = int(ent_off[-1])
+        dens, occ, x = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1)), np.zeros((max(n, 1), D))
+        _check(call(n, ent_off, dens, occ, x))
+        return ent_off, dens[:n], occ[:n], x[:n]
+
+    def map_statistics(self, states, utt_speaker, n_speakers, max_approx=True):
+        """MAP statistics of an alignment per (speaker, density) with at least one pair (sr_map_statistics_corpus) -> (ent_off
+        u64[S+1], dens u32[n], occ f64[n], x f64[n, D]): speaker s owns entries ent_off[s] .. ent_off[s + 1], ascending density id."""
+        states = np.ascontiguousarray(states, dtype=np.uint16)
+        spk = np.ascontiguousarray(utt_speaker, dtype=np.uint32)
+        assert len(spk) == self.n_utts
+        return self._map_statistics(lambda cap, off, d, o, x: lib().sr_map_statistics_corpus(
+            self.model.h, self.h, _ptr(states), _ptr(spk), n_speakers, int(max_approx), cap, _ptr(off), _ptr(d), _ptr(o), _ptr(x)), n_speakers)
+
+    def map_statistics_bw(self, automata, tdp, silence_state, utt_speaker, n_speakers, kernel=GMM_DEFAULT, floor=0.0, max_approx=True):
+        """The same from the forward-backward posteriors (sr_map_statistics_bw_corpus) -> (cost f64[n_utts], (ent_off, dens, occ, x))."""
+        flat, aoff = self._aut(automata)
+        spk = np.ascontiguousarray(utt_speaker, dtype=np.uint32)
+        assert len(spk) == self.n_utts
+        cost = np.zeros(max(self.n_utts, 1), dtype=np.float64)
+        t3 = (C.c_double * 3)(*tdp)
+        out = self._map_statistics(lambda cap, off, d, o, x: lib().sr_map_statistics_bw_corpus(
+            self.model.h, self.h, _ptr(flat), _ptr(aoff), C.byref(t3), silence_state, kernel, float(floor), _ptr(spk), n_speakers,
+            int(max_approx), _ptr(cost), cap, _ptr(off), _ptr(d), _ptr(o), _ptr(x)), n_speakers)
+        return cost[: self.n_utts], out
 
     def mllt_statistics(self, states, max_approx=True):
         """MLLT statistics of an alignment (sr_mllt_statistics_corpus) -> (beta float, G f64[D, D, D])."""

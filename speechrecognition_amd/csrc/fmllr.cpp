@@ -136,3 +136,4 @@ extern "C" SR_API int sr_fmllr_estimate(uint32_t dim, uint32_t n_speakers, const
 #include "mllr.cpp"  // sr_mllr_estimate: the MLLR mean transforms (see the note at its top)
 #include "mllt.cpp"  // sr_mllt_estimate: the MLLT transform, likewise
 #include "lda.cpp"   // sr_lda_estimate: the LDA projection, likewise
+#include "map.cpp"   // the host part of sr_model_map_adapt: checks, the mean rows' plan, the weight update, likewise

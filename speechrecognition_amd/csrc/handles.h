@@ -246,6 +246,11 @@ struct sr_corpus {
   DevBuf<uint32_t> ml_frame_speaker, ml_dens_class, ml_key, ml_run_key, ml_run_len, ml_run_begin, ml_n_runs, ml_gkey, ml_gkey_sorted,
       ml_ent_order, ml_grp_begin, ml_ent_dens;
   DevBuf<double> ml_ent_occ, ml_ent_x;
+  // MAP statistics (map_stats.hip; pairs, keys, sort workspace and runs are the EM and ml_* buffers above, the entries' sums ml_ent_*):
+  // the runs' (segments, pairs) counts and their scan, the segment list, the counts and the speakers' first entries, the partial sums
+  DevBuf<uint64_t> map_cnt, map_scan;
+  DevBuf<uint32_t> map_seg_ent, map_counts, map_ent_off;
+  DevBuf<double> map_partial;
   // LDA statistics and projection (lda_stats.hip; the scatter's segment partials are fm_partial): the frames' utterance bounds, the kept
   // frames in corpus order and grouped by class, the classes' segments, their partial sums, the results
   DevBuf<uint32_t> lda_span, lda_items, lda_class_items, lda_cseg_begin, lda_cseg_len, lda_class_seg_off;

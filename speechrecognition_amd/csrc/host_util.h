@@ -195,3 +195,23 @@ inline void parallel_ranges(size_t n, size_t min_per_thread, F&& fn, size_t max_
 }
 
 }  // namespace srhost
+
+// The host part of sr_model_map_adapt (map.cpp, compiled within fmllr.cpp's unit; the device part is map_stats.hip)
+namespace map_host {
+
+// the occupied mean rows as CSR: what map_means_kernel walks
+struct Plan {
+  std::vector<uint32_t> row_slot;  // [n_mean] the row's slot, 0xFFFFFFFF: no entry
+  std::vector<uint32_t> row_off;   // [slots + 1]
+  std::vector<uint32_t> row_ent;   // [n_entries] a slot's entries, ascending density id
+  std::vector<uint32_t> row_rep;   // [slots] the lowest density of the row
+};
+// SR_OK, or SR_EINVAL with the message set: the argument checks of sr_model_map_adapt that need no handle
+int validate(uint64_t n_dens, uint32_t dim, uint64_t n_entries, const uint32_t* dens, const double* occ, const double* x, double tau,
+             int update_weights, double tau_w);
+void plan(uint64_t n_dens, uint32_t n_mean, const uint32_t* dens_mean, uint64_t n_entries, const uint32_t* dens, Plan* out);
+// logw [n_dens] in/out: the mixtures with an entry get log(n_d / N), n_d = tau_w * exp(logw_d) + occ_d, N their sum in mixture order
+void update_weights(uint32_t n_states, const uint32_t* dens_off, uint64_t n_entries, const uint32_t* dens, const double* occ, double tau_w,
+                    double* logw);
+
+}  // namespace map_host

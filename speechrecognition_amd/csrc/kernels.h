@@ -797,6 +797,46 @@ uint32_t mllr_dens_per_block();
 hipError_t launch_mllr_transform_means(const double* means, const uint32_t* order, const uint32_t* blk, uint32_t n_blocks, const double* W,
                                        uint32_t dim, double* out, hipStream_t stream);
 
+// ---- MAP adaptation of the means: per-(speaker, density) sums of a set of pairs, the adapted means (map_stats.hip) ---------------------
+// After launch_mllr_runs (keys, stable sort, runs: run e is entry e, in ascending (speaker, density)):
+//   launch_map_plan   per entry its first pair and first segment (segments of map_seg_pairs() pairs), the segment list, every speaker's
+//                     first entry                                                            -> counts[2] = entries, segments; ent_off
+//   launch_map_sums   a wave per segment, then the partials of the entries of several segments in ascending order -> out_*
+struct MapArgs {
+  const float* feats;
+  uint32_t dim;
+  uint64_t n_pairs;
+  const uint32_t* pair_frame; const double* pair_w;
+  const uint32_t *pairs_sorted, *run_key, *run_len, *n_runs;  // launch_mllr_runs' results
+  uint32_t n_dens, n_speakers;
+  uint64_t *cnt, *scan;    // [n_pairs + 1] per run (segments << 32 | pairs) and its exclusive scan: (first segment << 32 | first pair)
+  uint32_t* seg_ent;       // [n_pairs + n_pairs / map_seg_pairs() + 1] the entry of every segment
+  uint32_t* counts;        // [2] entries, segments
+  uint32_t* ent_off;       // [n_speakers + 1] every speaker's first entry
+  void* temp; size_t temp_bytes;  // map_temp_bytes(n_pairs): launch_mllr_runs' workspace as well
+  uint32_t n_entries, n_segs;     // launch_map_sums: what counts held
+  double* partial;         // workspace [n_segs][dim + 1]: x, then occ
+  uint32_t* out_dens; double *out_occ, *out_x;  // device: [n_entries], [n_entries], [n_entries x dim]
+};
+uint32_t map_seg_pairs();   // pairs per segment: the unit of the fixed summation order
+size_t map_temp_bytes(uint64_t n_pairs);
+hipError_t launch_map_plan(const MapArgs& a, hipStream_t stream);
+hipError_t launch_map_sums(const MapArgs& a, hipStream_t stream);
+// out[d][i] = (tau * means[rep][i] + X) / (tau + O) for a density whose mean row has entries (slot = row_slot[dens_mean[d]], its entries
+// row_ent[row_off[slot] .. row_off[slot + 1]) in ascending density id, O and X chains from 0.0 over them, rep = row_rep[slot] the row's
+// lowest density); means[d][i] where row_slot is 0xFFFFFFFF.  No contraction.
+struct MapMeansArgs {
+  const double* means;       // [n_dens x dim] the prior's
+  const uint32_t* dens_mean; // [n_dens]
+  const uint32_t *row_slot, *row_off, *row_ent, *row_rep;
+  const double *occ, *x;     // the entries: [n_entries], [n_entries x dim]
+  double tau;
+  uint32_t dim;
+  uint64_t n_dens;
+  double* out;               // [n_dens x dim]
+};
+hipError_t launch_map_means(const MapMeansArgs& a, hipStream_t stream);
+
 // ---- MLLT: the global semi-tied covariance statistics of a set of pairs (mllt_stats.hip) ------------------------------------------------
 // The pairs are EmArgs' (pair_frame, pair_dens, pair_w; key_mean 0xFFFFFFFF: dropped), taken in pair order and cut into segments of
 // mllt_seg_pairs().  The contraction's shape: rows = D + 1 padded to 16 (row D carries gamma alone); columns = the D (D + 1) / 2 pairs

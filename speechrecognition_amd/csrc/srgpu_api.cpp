@@ -2334,11 +2334,12 @@ int sr_baum_welch_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, co
 
 // ---- what fMLLR and MLLR share ahead of their statistics ---------------------------------------------------------------------------
 // every utterance's speaker is one of n_speakers (> 0: the caller's check), and the dimension fits; `what` names the call in the message
+// (null: a call without the contraction's dimension limit -- the MAP statistics)
 static int speaker_check(const sr_model* m, const sr_corpus* c, const uint32_t* utt_speaker, uint32_t n_speakers, const char* what) {
   if (!utt_speaker && c->n_utts) return fail(SR_EINVAL, "utt_speaker is null");
   for (uint32_t u = 0; u < c->n_utts; u++)
     if (utt_speaker[u] >= n_speakers) return fail(SR_EINVAL, "utterance %u: speaker %u >= n_speakers %u", u, utt_speaker[u], n_speakers);
-  if (m->dim > fmllr_max_dim()) return fail(SR_ELIMIT, "dimension %u exceeds %u (%s)", m->dim, fmllr_max_dim(), what);
+  if (what && m->dim > fmllr_max_dim()) return fail(SR_ELIMIT, "dimension %u exceeds %u (%s)", m->dim, fmllr_max_dim(), what);
   return SR_OK;
 }
 
@@ -2680,6 +2681,174 @@ int sr_model_transform_means(sr_model* m, const uint32_t* dens_class, uint32_t n
   HIP_TRY(d_order.upload(order.data(), order.size())); HIP_TRY(d_blk.upload(blk.data(), blk.size()));
   HIP_TRY(d_W.upload(W, (size_t)n_classes * D * (D + 1)));
   HIP_TRY(launch_mllr_transform_means(m->means.p, d_order.p, d_blk.p, (uint32_t)(blk.size() / 3), d_W.p, D, o->means.p, o->s_gmm));
+  HIP_TRY(hipStreamSynchronize(o->s_gmm));
+  *out = own.release();
+  return SR_OK;
+  });
+}
+
+// ---- MAP adaptation of the means (map_stats.hip; checks, the mean rows' plan and the weight update are host code, map.cpp) -----------
+// The checks every statistics call makes before any launch
+static int map_check(sr_model* m, sr_corpus* c, const uint32_t* utt_speaker, uint32_t n_speakers, const uint64_t* out_ent_off,
+                     const uint32_t* out_dens, const double* out_occ, const double* out_x) {
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  if (!out_ent_off) return fail(SR_EINVAL, "out_ent_off is null");
+  const int given = (out_dens ? 1 : 0) + (out_occ ? 1 : 0) + (out_x ? 1 : 0);
+  if (given != 0 && given != 3) return fail(SR_EINVAL, "null output (pass all three entry arrays, or none)");
+  if (n_speakers == 0) return fail(SR_EINVAL, "n_speakers is 0");
+  if ((rc = speaker_check(m, c, utt_speaker, n_speakers, nullptr))) return rc;
+  if ((uint64_t)n_speakers * m->n_dens >= 0xFFFFFFFFull)
+    return fail(SR_ELIMIT, "n_speakers * densities = %llu does not fit the 32-bit (speaker, density) keys", (unsigned long long)n_speakers * m->n_dens);
+  return SR_OK;
+}
+
+// runs, plan and sums over the pairs `e` describes (formed already); the counts, and the entries where asked for, to the host
+static int map_statistics(sr_model* m, sr_corpus* c, const EmArgs& e, const uint32_t* utt_speaker, uint32_t S, uint64_t cap,
+                          uint64_t* out_ent_off, uint32_t* out_dens, double* out_occ, double* out_x) {
+  const uint32_t D = m->dim, U = c->n_utts;
+  const uint64_t F = c->n_frames, n_pairs = e.n_pairs;
+  int rc;
+  if (n_pairs == 0) {  // no frame, or nothing above the floor: no entry
+    std::fill(out_ent_off, out_ent_off + S + 1, (uint64_t)0);
+    return SR_OK;
+  }
+  std::vector<uint32_t> frame_speaker(F);
+  for (uint32_t u = 0; u < U; u++) std::fill(frame_speaker.begin() + c->frame_off[u], frame_speaker.begin() + c->frame_off[u + 1], utt_speaker[u]);
+  MllrArgs r{};  // launch_mllr_runs' share
+  r.n_pairs = n_pairs; r.pair_frame = e.pair_frame; r.pair_dens = e.pair_dens; r.pair_key = e.key_mean; r.pair_w = e.pair_w;
+  r.n_dens = (uint32_t)m->n_dens; r.n_speakers = S;
+  HIP_TRY(c->ml_frame_speaker.upload(frame_speaker.data(), F));
+  HIP_TRY(c->ml_key.ensure(n_pairs)); HIP_TRY(c->iota.ensure(n_pairs)); HIP_TRY(c->keys_sorted.ensure(n_pairs));
+  HIP_TRY(c->pairs_sorted.ensure(n_pairs)); HIP_TRY(c->ml_run_key.ensure(n_pairs)); HIP_TRY(c->ml_run_len.ensure(n_pairs));
+  HIP_TRY(c->ml_n_runs.ensure(1));
+  r.sort_temp_bytes = map_temp_bytes(n_pairs);
+  HIP_TRY(c->sort_temp.ensure(r.sort_temp_bytes));
+  r.frame_speaker = c->ml_frame_speaker.p; r.key = c->ml_key.p; r.iota = c->iota.p; r.keys_sorted = c->keys_sorted.p;
+  r.pairs_sorted = c->pairs_sorted.p; r.run_key = c->ml_run_key.p; r.run_len = c->ml_run_len.p; r.n_runs = c->ml_n_runs.p;
+  r.sort_temp = c->sort_temp.p;
+  MapArgs a{};
+  a.feats = c->feats.p; a.dim = D; a.n_pairs = n_pairs; a.pair_frame = e.pair_frame; a.pair_w = e.pair_w;
+  a.pairs_sorted = r.pairs_sorted; a.run_key = r.run_key; a.run_len = r.run_len; a.n_runs = r.n_runs;
+  a.n_dens = r.n_dens; a.n_speakers = S;
+  HIP_TRY(c->map_cnt.ensure(n_pairs + 1)); HIP_TRY(c->map_scan.ensure(n_pairs + 1));
+  HIP_TRY(c->map_seg_ent.ensure(n_pairs + n_pairs / map_seg_pairs() + 1));
+  HIP_TRY(c->map_counts.ensure(2)); HIP_TRY(c->map_ent_off.ensure((size_t)S + 1));
+  a.cnt = c->map_cnt.p; a.scan = c->map_scan.p; a.seg_ent = c->map_seg_ent.p; a.counts = c->map_counts.p; a.ent_off = c->map_ent_off.p;
+  a.temp = r.sort_temp; a.temp_bytes = r.sort_temp_bytes;
+  EventPair ep{};
+  if ((rc = prof_begin(m, m->s_gmm, 1, &ep))) return rc;
+  HIP_TRY(launch_mllr_runs(r, m->s_gmm));
+  HIP_TRY(launch_map_plan(a, m->s_gmm));
+  if ((rc = prof_end(m, m->s_gmm, &ep))) return rc;
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  uint32_t counts[2] = {0, 0};
+  std::vector<uint32_t> ent_off((size_t)S + 1);
+  HIP_TRY(hipMemcpy(counts, c->map_counts.p, sizeof counts, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(ent_off.data(), c->map_ent_off.p, sizeof(uint32_t) * ent_off.size(), hipMemcpyDeviceToHost));
+  a.n_entries = counts[0]; a.n_segs = counts[1];
+  if (a.n_entries > n_pairs || a.n_segs < a.n_entries || a.n_segs > a.n_entries + n_pairs / map_seg_pairs())
+    return fail(SR_EINTERNAL, "MAP statistics: %u entries in %u segments of %llu pairs", a.n_entries, a.n_segs, (unsigned long long)n_pairs);
+  if (ent_off[0] != 0 || ent_off[S] != a.n_entries || !std::is_sorted(ent_off.begin(), ent_off.end()))
+    return fail(SR_EINTERNAL, "MAP statistics: the speakers do not cover the entries");
+  std::copy(ent_off.begin(), ent_off.end(), out_ent_off);
+  if (m->profiling) {  // per pair: keys and sort
+    m->prof.frames += F;
+    m->prof.search_bytes += (double)n_pairs * 40.0;
+  }
+  if (!out_dens) return SR_OK;  // the sizing call
+  if (a.n_entries > cap)
+    return fail(SR_EINVAL, "%u entries exceed the capacity of %llu (out_ent_off holds the counts)", a.n_entries, (unsigned long long)cap);
+  if (a.n_entries == 0) return SR_OK;  // every pair was dropped
+  const size_t ne = a.n_entries;
+  HIP_TRY(c->ml_ent_dens.ensure(ne)); HIP_TRY(c->ml_ent_occ.ensure(ne)); HIP_TRY(c->ml_ent_x.ensure(ne * D));
+  HIP_TRY(c->map_partial.ensure(a.n_segs > a.n_entries ? (size_t)a.n_segs * (D + 1) : 1));
+  a.partial = c->map_partial.p; a.out_dens = c->ml_ent_dens.p; a.out_occ = c->ml_ent_occ.p; a.out_x = c->ml_ent_x.p;
+  if ((rc = prof_begin(m, m->s_gmm, 1, &ep))) return rc;
+  HIP_TRY(launch_map_sums(a, m->s_gmm));
+  if ((rc = prof_end(m, m->s_gmm, &ep))) return rc;
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  HIP_TRY(hipMemcpy(out_dens, a.out_dens, sizeof(uint32_t) * ne, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_occ, a.out_occ, sizeof(double) * ne, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_x, a.out_x, sizeof(double) * ne * D, hipMemcpyDeviceToHost));
+  if (m->profiling)  // per pair: weight, frame, a feature row; per entry: its sums out; the partials out and in
+    m->prof.search_bytes += (double)n_pairs * (16.0 + 4.0 * D) + 8.0 * (double)ne * (D + 2) +
+                            (a.n_segs > a.n_entries ? 16.0 * (double)a.n_segs * (D + 1) : 0.0);
+  return SR_OK;
+}
+
+int sr_map_statistics_corpus(sr_model* m, sr_corpus* c, const uint16_t* states, const uint32_t* utt_speaker, uint32_t n_speakers,
+                             int max_approx, uint64_t cap, uint64_t* out_ent_off, uint32_t* out_dens, double* out_occ, double* out_x) {
+  return guarded(__func__, [&]() -> int {
+  int rc = map_check(m, c, utt_speaker, n_speakers, out_ent_off, out_dens, out_occ, out_x);
+  if (rc) return rc;
+  EmArgs e{};
+  if ((rc = adapt_pairs(m, c, states, max_approx, &e))) return rc;
+  return map_statistics(m, c, e, utt_speaker, n_speakers, cap, out_ent_off, out_dens, out_occ, out_x);
+  });
+}
+
+int sr_map_statistics_bw_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
+                                uint16_t silence_state, int gmm_kernel, double posterior_floor, const uint32_t* utt_speaker,
+                                uint32_t n_speakers, int max_approx, double* out_cost, uint64_t cap, uint64_t* out_ent_off,
+                                uint32_t* out_dens, double* out_occ, double* out_x) {
+  return guarded(__func__, [&]() -> int {
+  int rc = map_check(m, c, utt_speaker, n_speakers, out_ent_off, out_dens, out_occ, out_x);
+  if (rc) return rc;
+  EmArgs e{};
+  if ((rc = adapt_pairs_bw(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, max_approx, out_cost, &e))) return rc;
+  return map_statistics(m, c, e, utt_speaker, n_speakers, cap, out_ent_off, out_dens, out_occ, out_x);
+  });
+}
+
+int sr_model_map_adapt(sr_model* prior, uint64_t n_entries, const uint32_t* dens, const double* occ, const double* x, double tau,
+                       int update_weights, double tau_w, sr_model** out) {
+  return guarded(__func__, [&]() -> int {
+  if (!out) return fail(SR_EINVAL, "out is null");
+  *out = nullptr;
+  sr_model* m = prior;
+  int rc = check_model(m);
+  if (rc) return rc;
+  const uint64_t C = m->n_dens;
+  const uint32_t D = m->dim;
+  if (m->h_dens_mean.size() != C || m->h_dens_var.size() != C) return fail(SR_EINTERNAL, "the model has no tying tables");
+  if ((rc = map_host::validate(C, D, n_entries, dens, occ, x, tau, update_weights, tau_w))) return rc;
+  map_host::Plan plan;
+  map_host::plan(C, m->n_mean, m->h_dens_mean.data(), n_entries, dens, &plan);
+  std::vector<double> logw;
+  if (update_weights && n_entries) {  // C doubles from the device where the model keeps no host copy
+    logw.resize(C);
+    if (m->h_logw.size() == C) logw = m->h_logw;
+    else HIP_TRY(hipMemcpy(logw.data(), m->logw.p, sizeof(double) * C, hipMemcpyDeviceToHost));
+    map_host::update_weights(m->n_states, m->h_dens_off.data(), n_entries, dens, occ, tau_w, logw.data());
+  }
+  sr_model* o = nullptr;
+  if ((rc = srhost::model_shell(m->device, D, m->n_states, m->h_dens_off.data(), m->max_approx ? 1 : 0, &o))) return rc;
+  std::unique_ptr<sr_model, int (*)(sr_model*)> own(o, sr_model_destroy);
+  HIP_TRY(o->dens_mean.upload(m->h_dens_mean.data(), C)); HIP_TRY(o->dens_var.upload(m->h_dens_var.data(), C));
+  o->n_mean = m->n_mean; o->n_var = m->n_var; o->h_dens_mean = m->h_dens_mean; o->h_dens_var = m->h_dens_var;
+  HIP_TRY(o->means.ensure(C * D)); HIP_TRY(o->inv_vars.ensure(C * D)); HIP_TRY(o->norm.ensure(C)); HIP_TRY(o->logw.ensure(C));
+  if (C) {
+    HIP_TRY(hipMemcpy(o->inv_vars.p, m->inv_vars.p, sizeof(double) * C * D, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(o->norm.p, m->norm.p, sizeof(double) * C, hipMemcpyDeviceToDevice));
+    if (logw.empty()) HIP_TRY(hipMemcpy(o->logw.p, m->logw.p, sizeof(double) * C, hipMemcpyDeviceToDevice));
+    else HIP_TRY(hipMemcpy(o->logw.p, logw.data(), sizeof(double) * C, hipMemcpyHostToDevice));
+  }
+  DevBuf<uint32_t> d_slot, d_off, d_ent, d_rep;
+  DevBuf<double> d_occ, d_x;
+  const size_t ne = std::max<uint64_t>(1, n_entries);
+  HIP_TRY(d_slot.upload(plan.row_slot.data(), plan.row_slot.size())); HIP_TRY(d_off.upload(plan.row_off.data(), plan.row_off.size()));
+  HIP_TRY(d_ent.ensure(ne)); HIP_TRY(d_rep.ensure(ne)); HIP_TRY(d_occ.ensure(ne)); HIP_TRY(d_x.ensure(ne * D));
+  if (n_entries) {
+    HIP_TRY(hipMemcpy(d_ent.p, plan.row_ent.data(), sizeof(uint32_t) * n_entries, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_rep.p, plan.row_rep.data(), sizeof(uint32_t) * plan.row_rep.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_occ.p, occ, sizeof(double) * n_entries, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_x.p, x, sizeof(double) * n_entries * D, hipMemcpyHostToDevice));
+  }
+  MapMeansArgs a{};
+  a.means = m->means.p; a.dens_mean = o->dens_mean.p; a.row_slot = d_slot.p; a.row_off = d_off.p; a.row_ent = d_ent.p; a.row_rep = d_rep.p;
+  a.occ = d_occ.p; a.x = d_x.p; a.tau = tau; a.dim = D; a.n_dens = C; a.out = o->means.p;
+  HIP_TRY(launch_map_means(a, o->s_gmm));
   HIP_TRY(hipStreamSynchronize(o->s_gmm));
   *out = own.release();
   return SR_OK;
