@@ -1047,6 +1047,21 @@ SR_API int sr_refine_geometry(sr_model* m, uint64_t n_frames, uint32_t out[4]);
  * SRGPU_GATHER=host (read when a model is created; a diagnostic knob, same output). */
 SR_API int sr_gather_words(sr_model* m, uint32_t n_utts, const uint64_t* frame_off, const uint32_t* counts, const uint32_t* flags,
                            const uint32_t* words, uint32_t* out_words, uint64_t* out_word_off);
+/* Test hook: the zerogram search alone, on a score table the caller supplies instead of the GMM scores: sr_recognize_corpus' pass
+ * -- the same chunks, launch order, kernel route from p->flags, replay workspace, compaction of the words and traceback copies --
+ * except that a chunk's score step copies rows [f0, f1) of `scores` into the chunk's table (row stride: n_states rounded up to 8,
+ * the padding columns +inf) where sr_recognize_corpus scores the chunk's frames.  scores: host, [total_frames x n_states] row-major,
+ * the corpus's frames in order; any bit pattern is a valid entry (negative, +inf, NaN); n_scores == total_frames * n_states or
+ * SR_EINVAL.  c is an ordinary corpus: its frame offsets are used, its features are never read, and p->gmm_kernel is ignored.
+ * exact_negative (0 or 1, SR_EINVAL otherwise) is what sr_recognize_corpus derives from the model ("an emission cost of this model
+ * can be negative or NaN"): 1 lets the word-per-lane kernel run its variant that replays the reference's early-out in place (where
+ * its word-end arrays fit the LDS), 0 makes a fast kernel that meets such a cost hand the utterance to the replay kernel.  Outputs as
+ * sr_recognize_corpus, and out_flags[n_utts] (not NULL): per utterance the search's flags as left on the device -- 1: the sequential
+ * boundary replay was taken, 2: a fast kernel handed the utterance to the replay kernel, 4: the traceback did not walk (the call
+ * returns SR_ECORRUPT then, out_flags filled). */
+SR_API int sr_recognize_corpus_scores(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, const double* scores,
+                                      uint64_t n_scores, int exact_negative, uint32_t* out_words, uint64_t* out_word_off,
+                                      double* tb_score, uint16_t* tb_word, uint16_t* tb_bkp, uint32_t* out_flags);
 
 /* ---- measurement --------------------------------------------------------------------------------
  * When enabled, every kernel launch of this model handle is bracketed by HIP events on the

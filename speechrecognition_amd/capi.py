@@ -51,7 +51,7 @@ SYMBOLS = [
     "sr_bigram_stream_destroy",
     "sr_probe_fp16_denormals", "sr_probe_fp16_accumulation", "sr_prefilter_masks", "sr_prefilter_range_frames",
     "sr_refine_masks", "sr_refine_geometry",
-    "sr_gather_words",
+    "sr_gather_words", "sr_recognize_corpus_scores",
     "sr_profile_enable", "sr_profile_reset", "sr_profile_read",
 ]
 
@@ -200,6 +200,7 @@ def lib():
         L.sr_refine_masks.argtypes = [vp, vp, u64, vp, u64, vp]
         L.sr_refine_geometry.argtypes = [vp, u64, vp]
         L.sr_gather_words.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
+        L.sr_recognize_corpus_scores.argtypes = [vp, vp, vp, C.POINTER(SearchParams), vp, u64, i32, vp, vp, vp, vp, vp, vp]
         L.sr_profile_enable.argtypes = [vp, i32]
         L.sr_profile_reset.argtypes = [vp]
         L.sr_profile_read.argtypes = [vp, C.POINTER(Profile)]
@@ -626,6 +627,20 @@ class Corpus:
         if traceback:
             return words, woff, (tbs, tbw, tbb)
         return words, woff
+
+    def recognize_scores(self, lexicon, scores, am_threshold, word_penalty, exact_negative, general_kernel=False, slot_kernel=False):
+        """sr_recognize_corpus_scores (test hook): the search alone on the caller's score table [n_frames, n_states] (the corpus's
+        features are not read) -> words u32[], word_off u64[n_utts+1], (tb_score, tb_word, tb_bkp), flags u32[n_utts]"""
+        scores = np.ascontiguousarray(scores, dtype=np.float64)
+        words = np.zeros(max(self.n_frames, 1), dtype=np.uint32)
+        woff = np.zeros(self.n_utts + 1, dtype=np.uint64)
+        sp = SearchParams(am_threshold, word_penalty, GMM_DEFAULT, (SEARCH_GENERAL_KERNEL if general_kernel else 0) | (SEARCH_SLOT_KERNEL if slot_kernel else 0))
+        n = self.n_frames + self.n_utts
+        tbs, tbw, tbb = np.zeros(n, np.float64), np.zeros(n, np.uint16), np.zeros(n, np.uint16)
+        flags = np.zeros(max(self.n_utts, 1), dtype=np.uint32)
+        _check(lib().sr_recognize_corpus_scores(self.model.h, self.h, lexicon.h, C.byref(sp), _ptr(scores), scores.size, int(exact_negative),
+                                                _ptr(words), _ptr(woff), _ptr(tbs), _ptr(tbw), _ptr(tbb), _ptr(flags)))
+        return words[: int(woff[-1])].copy(), woff, (tbs, tbw, tbb), flags[: self.n_utts]
 
     def retrace(self, lexicon, tb_word, tb_bkp):
         """sr_traceback_corpus: the device's traceback walk alone on dumps in recognize(traceback=True)'s layout."""

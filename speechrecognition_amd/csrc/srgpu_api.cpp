@@ -1348,11 +1348,13 @@ static int gather_words_host(sr_corpus* c, uint32_t* out_words, uint64_t* out_wo
 }
 
 extern "C++" {  // (templates inside the entry points' extern "C" block)
-// The zerogram search of a corpus on `chunks` (prepare_chunks): the words and tracebacks stay in c->out_* / c->tb_*.  after(chunk,
-// table, stream) enqueues more work on a chunk's scores behind its search (a no-op for sr_recognize_corpus).
-template <class After>
+// The zerogram search of a corpus on `chunks` (prepare_chunks): the words and tracebacks stay in c->out_* / c->tb_*.
+// score(chunk, table) enqueues the chunk's scores on m->s_gmm (score_chunk, but for the test hook sr_recognize_corpus_scores);
+// exact_negative is DecodeArgs' (-1: asked of the model); after(chunk, table, stream) enqueues more work on a chunk's scores behind
+// its search (a no-op for sr_recognize_corpus).
+template <class Score, class After>
 static int recognize_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, const std::vector<Chunk>& chunks,
-                          After after) {
+                          int exact_negative, Score score, After after) {
   const uint32_t U = c->n_utts;
   const uint64_t F = c->n_frames;
   HIP_TRY(c->tb_score.ensure(F + U));
@@ -1375,15 +1377,17 @@ static int recognize_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_sea
     for (const Chunk& ch : chunks) most = std::max(most, ch.u1 - ch.u0);
     HIP_TRY(c->big_ws.ensure((size_t)most * decode_big_workspace(l->net.n_slots)));
   }
-  {
+  if (exact_negative < 0) {
     bool neg = false;
     if ((rc = srhost::may_go_negative(m, &neg))) return rc;
     da.exact_negative = neg ? 1u : 0u;
+  } else {
+    da.exact_negative = exact_negative ? 1u : 0u;
   }
   da.tb_score = c->tb_score.p; da.tb_word = c->tb_word.p; da.tb_bkp = c->tb_bkp.p;
   da.out_words = c->out_words.p; da.out_count = c->out_count.p; da.out_flags = c->out_flags.p;
 
-  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); },
+  rc = run_chunks(m, chunks, score,
       [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
         da.scores = table; da.frame_base = ch.f0; da.utt_first = ch.u0; da.n_utts = ch.u1 - ch.u0;
         HIP_TRY(launch_decode(da, route, c->big_ws.p, s));
@@ -1394,6 +1398,13 @@ static int recognize_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_sea
   if (rc) return rc;
   if (m->profiling) m->prof.frames += F;
   return SR_OK;
+}
+// ... with the model's scores, as every production pass takes it
+template <class After>
+static int recognize_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, const std::vector<Chunk>& chunks,
+                          After after) {
+  return recognize_pass(m, c, l, p, chunks, -1,
+                        [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); }, after);
 }
 }  // extern "C++"
 
@@ -1463,6 +1474,46 @@ int sr_gather_words(sr_model* m, uint32_t n_utts, const uint64_t* frame_off, con
   if ((rc = enqueue_gather(m, &c, zerogram_gather(&c), 1, m->s_gmm))) return rc;
   HIP_TRY(hipStreamSynchronize(m->s_gmm));
   return gather_words(&c, out_words, out_word_off);
+  });
+}
+
+// test hook: sr_recognize_corpus with the chunk's score step replaced by a copy of the caller's rows (padded to the table's row
+// stride with +inf, the whole table once, so that a chunk is one copy)
+int sr_recognize_corpus_scores(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, const double* scores,
+                               uint64_t n_scores, int exact_negative, uint32_t* out_words, uint64_t* out_word_off, double* tb_score,
+                               uint16_t* tb_word, uint16_t* tb_bkp, uint32_t* out_flags) {
+  return guarded(__func__, [&]() -> int {
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  if (!l || l->model != m) return fail(SR_EINVAL, "lexicon does not belong to this model");
+  if (!p || !out_word_off || !out_flags || (!out_words && c->n_frames) || (!scores && c->n_frames)) return fail(SR_EINVAL, "null argument");
+  if (exact_negative != 0 && exact_negative != 1) return fail(SR_EINVAL, "exact_negative must be 0 or 1");
+  const uint32_t U = c->n_utts;
+  const uint64_t F = c->n_frames;
+  if (n_scores != F * m->n_states)
+    return fail(SR_EINVAL, "%llu scores for %llu frames x %u states", (unsigned long long)n_scores, (unsigned long long)F, m->n_states);
+  const size_t S = m->n_states, ld = m->ld;
+  std::vector<double> padded((size_t)F * ld, std::numeric_limits<double>::infinity());
+  for (uint64_t t = 0; t < F; t++) memcpy(padded.data() + t * ld, scores + t * S, sizeof(double) * S);
+  std::vector<Chunk> chunks;
+  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
+  rc = recognize_pass(m, c, l, p, chunks, exact_negative,
+                      [&](const Chunk& ch, double* table) -> int {
+                        if (ch.f1 > ch.f0)
+                          HIP_TRY(hipMemcpyAsync(table, padded.data() + ch.f0 * ld, sizeof(double) * (ch.f1 - ch.f0) * ld, hipMemcpyHostToDevice, m->s_gmm));
+                        return SR_OK;
+                      },
+                      [](const Chunk&, const double*, hipStream_t) { return (int)SR_OK; });
+  if (rc) {  // (a copy may still be reading `padded`)
+    (void)hipStreamSynchronize(m->s_gmm);
+    return rc;
+  }
+  if (U) HIP_TRY(hipMemcpy(out_flags, c->out_flags.p, sizeof(uint32_t) * U, hipMemcpyDeviceToHost));
+  if ((rc = gather_words(c, out_words, out_word_off))) return rc;
+  if (tb_score) HIP_TRY(hipMemcpy(tb_score, c->tb_score.p, sizeof(double) * (F + U), hipMemcpyDeviceToHost));
+  if (tb_word) HIP_TRY(hipMemcpy(tb_word, c->tb_word.p, sizeof(uint16_t) * (F + U), hipMemcpyDeviceToHost));
+  if (tb_bkp) HIP_TRY(hipMemcpy(tb_bkp, c->tb_bkp.p, sizeof(uint16_t) * (F + U), hipMemcpyDeviceToHost));
+  return SR_OK;
   });
 }
 
