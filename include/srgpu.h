@@ -788,6 +788,11 @@ SR_API int sr_bigram_create(sr_model* m, uint32_t n_words, const uint32_t* word_
 SR_API int sr_bigram_destroy(sr_bigram* b);
 /* The layout sr_recognize_bigram_corpus runs with flags = 0: "registers", "lds" or "global" (see above). */
 SR_API int sr_bigram_describe(const sr_bigram* b, char* out, size_t cap);
+/* The kernel sr_recognize_bigram_corpus runs with sr_bigram_params.flags = flags, as text: "registers R rows4 0bM" (R = 1..3 rows of
+ * 1024 words a lane, M = the rows that carry a fourth state, in binary), "lds KW x KP" (words / positions a thread), "global KW entries
+ * lds" or "global KW entries global" (the entry hypotheses in the LDS / in device memory too), "none" where SR_BIGRAM_DENSE_STATES
+ * asks for an image the LDS cannot hold.  The text comes from the function the launch itself switches on. */
+SR_API int sr_bigram_route(const sr_bigram* b, uint32_t flags, char* out, size_t cap);
 /* out_word/out_score/out_time: capacity n_frames + n_utts (LinearSearch::getResult's traceback items, silence included);
  * out_off[n_utts+1]: items of utterance u are [out_off[u], out_off[u+1]).  SR_ELIMIT if a book overflowed.  The "global" layout
  * takes a workspace of 16 bytes per position (+ 16 per word above 4 720 words) for each of at most 2 workgroups per CU, bounded by
@@ -1062,6 +1067,15 @@ SR_API int sr_gather_words(sr_model* m, uint32_t n_utts, const uint64_t* frame_o
 SR_API int sr_recognize_corpus_scores(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, const double* scores,
                                       uint64_t n_scores, int exact_negative, uint32_t* out_words, uint64_t* out_word_off,
                                       double* tb_score, uint16_t* tb_word, uint16_t* tb_bkp, uint32_t* out_flags);
+/* Test hook: the bigram search alone on a score table the caller supplies: sr_recognize_bigram_corpus' pass -- the same chunks, book
+ * sizing from p->max_word_ends, layout from p->flags, global-states grid, compaction of the items, SR_ELIMIT -- except that a chunk's
+ * score step copies rows [f0, f1) of `scores` into the chunk's table (row stride: n_states rounded up to 8, the padding columns
+ * +inf).  scores: host, [total_frames x n_states] row-major; any bit pattern is a valid entry, but the search converts an entry to
+ * float with a cast, so a finite one must stay below FLT_MAX in magnitude; n_scores == total_frames * n_states or SR_EINVAL.  The
+ * corpus's features are never read and p->gmm_kernel is ignored.  Outputs as sr_recognize_bigram_corpus. */
+SR_API int sr_recognize_bigram_corpus_scores(sr_model* m, sr_corpus* c, sr_bigram* b, const sr_bigram_params* p, const double* scores,
+                                             uint64_t n_scores, uint32_t* out_word, float* out_score, uint32_t* out_time,
+                                             uint64_t* out_off);
 
 /* ---- measurement --------------------------------------------------------------------------------
  * When enabled, every kernel launch of this model handle is bracketed by HIP events on the

@@ -342,7 +342,8 @@ def bigram_decode(dense, word_off, mixtures, silence, lm, tdp, acoustic_pruning=
     assert tdp.shape == (2, 4)
     cap = T + 1
     ow, osc, ot = np.zeros(cap, np.uint32), np.zeros(cap, np.float32), np.zeros(cap, np.uint32)
-    st = np.zeros(4, np.uint64)
+    # sr_oracle.h: [0..3] as ever, [4] longest merged list, [5] frames with a tie, [6] that list's spread, [7] on a beam limit, [8], [9] on the skip bound
+    st = np.zeros(10, np.uint64)
     n = L.orc_bigram_decode(dense, ld, T, W, silence, word_off, mixtures, lm, tdp, acoustic_pruning, lm_pruning, ow, osc, ot, cap, st)
     assert n <= cap
     res = (ow[:n].copy(), osc[:n].copy(), ot[:n].copy())

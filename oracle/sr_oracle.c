@@ -659,6 +659,22 @@ static void bg_expand_state(bg_space* s, uint32_t word, bg_sh h, size_t* cap_nsh
   }
 }
 
+static float bg_bf16(float x, int up) {  /* the nearest bf16 value not above (up = 0) / not below (up = 1) x */
+  uint32_t b;
+  memcpy(&b, &x, sizeof b);
+  if (x != x) return x;
+  uint32_t t = b >> 16;
+  if ((b & 0xFFFFu) && (int)(b >> 31) != up) t += 1u;
+  t <<= 16;
+  memcpy(&x, &t, sizeof x);
+  return x;
+}
+
+static int bg_cmp_float(const void* a, const void* b) {  /* (NaNs compare equal to everything: they only blur the tie statistic) */
+  const float x = *(const float*)a, y = *(const float*)b;
+  return x < y ? -1 : x > y ? 1 : 0;
+}
+
 size_t orc_bigram_decode(const double* dense, size_t dense_stride, size_t T, uint32_t W, uint32_t silence,
                          const uint32_t* word_off, const uint16_t* mixtures, const float* lm, const float tdp[2][4],
                          float acoustic_pruning, float lm_pruning, uint32_t* out_word, float* out_score,
@@ -682,7 +698,23 @@ size_t orc_bigram_decode(const double* dense, size_t dense_stride, size_t T, uin
   bg_wb* ws = (bg_wb*)malloc((2 * (size_t)W + 1) * sizeof(bg_wb));
   size_t n_we = 0, n_ws = 0;
   uint32_t* first_idx = (uint32_t*)malloc((size_t)W * sizeof(uint32_t));
-  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  if (stats) for (int i = 0; i < 10; i++) stats[i] = 0;
+  float* tie_tmp = stats ? (float*)malloc((2 * (size_t)W + 1) * sizeof(float)) : NULL;
+  /* statistics only: the bounds of a history's LM scores, min / max over w != silence of lm[w][h] (a NaN entry makes the bound NaN),
+   * as floats [0 .. W), [W .. 2W) and widened to bf16 (the minimum down, the maximum up) [2W .. 3W), [3W .. 4W) */
+  float* lm_bound = stats ? (float*)malloc(4 * (size_t)W * sizeof(float)) : NULL;
+  if (stats) {
+    for (uint32_t h = 0; h < W; h++) { lm_bound[h] = INFINITY; lm_bound[W + h] = -INFINITY; }
+    for (uint32_t w = 0; w < W; w++) {
+      if (w == silence) continue;
+      for (uint32_t h = 0; h < W; h++) {
+        const float v = lm[(size_t)w * W + h];
+        if (v < lm_bound[h] || v != v) lm_bound[h] = v;
+        if (v > lm_bound[W + h] || v != v) lm_bound[W + h] = v;
+      }
+    }
+    for (uint32_t h = 0; h < W; h++) { lm_bound[2 * W + h] = bg_bf16(lm_bound[h], 0); lm_bound[3 * W + h] = bg_bf16(lm_bound[W + h], 1); }
+  }
 
   /* initialize: addInitialHypothesis :211-216 */
   { bg_wb w0 = {silence, 0.0f, 0}; we[n_we++] = w0; }
@@ -690,6 +722,13 @@ size_t orc_bigram_decode(const double* dense, size_t dense_stride, size_t T, uin
 
   for (size_t t = 1; t <= T; t++) {   /* processFrame(t), t = 1..T (SearchInterface.hh:58-60) */
     const double* row = dense + (t - 1) * dense_stride;
+    if (stats)  /* word ends exactly ON the bound below which none can be left out of the recombination: score + min == min_e (score_e + max_e) */
+      for (int v = 0; v < 2; v++) {
+        const float *lo = lm_bound + 2 * v * (size_t)W, *hi = lo + W;
+        float U = FLT_MAX;
+        for (size_t e = 0; e < n_we; e++) { const float c = we[e].score + hi[bg_map_copy(&sp, we[e].word)]; if (c < U) U = c; }
+        for (size_t e = 0; e < n_we; e++) if (n_we > 1 && we[e].score + lo[bg_map_copy(&sp, we[e].word)] == U) stats[8 + v]++;
+      }
     /* bigramRecombination :219-244 */
     n_ws = W;
     for (uint32_t w = 0; w < W; w++) { bg_wb d = {BG_INVALID, FLT_MAX, BG_INVALID}; ws[w] = d; }
@@ -709,6 +748,7 @@ size_t orc_bigram_decode(const double* dense, size_t dense_stride, size_t T, uin
     if (lm_thr < FLT_MAX) lm_thr += best_start;
     /* insertWordStartHypotheses :246-255 + addEntryStateHypothesis :257-268 */
     for (size_t i = 0; i < n_ws; i++) {
+      if (stats && lm_thr < FLT_MAX && ws[i].score == lm_thr) stats[7]++;
       if (!(ws[i].score < lm_thr)) continue;
       const uint32_t word = ws[i].word;
       if (sp.wh_map[word] == BG_INVALID) {
@@ -754,6 +794,7 @@ size_t orc_bigram_decode(const double* dense, size_t dense_stride, size_t T, uin
         const uint32_t n = bg_len(&sp, wh->word);
         for (; in < end; in++) {
           const float sc = sp.sh[in].score + sp.tdp[bg_is_sil(&sp, wh->word)][3];
+          if (stats && ac_thr < FLT_MAX && sc == ac_thr) stats[7]++;
           if (sc < ac_thr) {
             sp.sh[out++] = sp.sh[in];
             if (sp.sh[in].state == n) { bg_wb h = {wh->word, sc, sp.sh[in].bp}; we[n_we++] = h; }
@@ -780,7 +821,20 @@ size_t orc_bigram_decode(const double* dense, size_t dense_stride, size_t T, uin
       n_we = n_ends;
     }
     bg_book_keeping(&sp, (uint32_t)t, we, n_we);
-    if (stats) { stats[0] += n_we; stats[1] += sp.n_wh; stats[2] += sp.n_sh; stats[3] = sp.n_book; }
+    if (stats) {
+      stats[0] += n_we; stats[1] += sp.n_wh; stats[2] += sp.n_sh; stats[3] = sp.n_book;
+      if (n_we > stats[4]) {  /* the longest merged list, and the spread of its scores */
+        float lo = we[0].score, hi = we[0].score;
+        for (size_t e = 1; e < n_we; e++) { if (we[e].score < lo) lo = we[e].score; if (we[e].score > hi) hi = we[e].score; }
+        const float spread = hi - lo;
+        uint32_t bits;
+        memcpy(&bits, &spread, sizeof bits);
+        stats[4] = n_we; stats[6] = bits;
+      }
+      for (size_t e = 0; e < n_we; e++) tie_tmp[e] = we[e].score;
+      qsort(tie_tmp, n_we, sizeof(float), bg_cmp_float);
+      for (size_t e = 1; e < n_we; e++) if (tie_tmp[e] == tie_tmp[e - 1]) { stats[5]++; break; }
+    }
   }
 
   /* traceback :420-436 */
@@ -797,6 +851,7 @@ size_t orc_bigram_decode(const double* dense, size_t dense_stride, size_t T, uin
       if (len < cap) { out_word[len] = sp.book[b].word; out_score[len] = sp.book[b].score; out_time[len] = sp.book[b].time; }
     }
   }
+  free(tie_tmp); free(lm_bound);
   free(sp.sh); free(sp.nsh); free(sp.wh); free(sp.sh_map); free(sp.wh_map); free(sp.book); free(we); free(ws); free(first_idx);
   return n_out;
 }

@@ -136,7 +136,12 @@ double orc_recognize_batch(const orc_model* m, const orc_lexicon* lex, const orc
  * (SearchSpace::setTransitionScores :169-180).  am scores: (float)dense[t*stride + mixture].
  * Pruning thresholds >= FLT_MAX switch the beam off (:445-455,499-510).
  * Output: the traceback items (word, score, time) of LinearSearch::getResult; returns their number (written up to
- * `cap`).  stats (optional, [4]): sum over frames of word ends after merging, active words, state hyps, book entries. */
+ * `cap`).  stats (optional, [10]): sum over frames of word ends after merging, active words, state hyps; book entries; [4] the most
+ * word ends a frame's merged list held and [6] the float bits of max - min of that list's scores (the first such frame); [5] frames
+ * whose merged list holds two word ends of equal score; [7] hypotheses that sat exactly ON a beam limit (score == best + pruning, at
+ * the LM beam and at the acoustic beam: the strict < drops them); [8] word ends e of a list of two or more with score_e + min_w
+ * lm[w][h_e] == min_e' (score_e' + max_w lm[w][h_e']) exactly, the bound at which a search may still not leave a word end out of the
+ * recombination, and [9] the same with the two bounds widened to bf16. */
 size_t orc_bigram_decode(const double* dense, size_t dense_stride, size_t T, uint32_t W, uint32_t silence,
                          const uint32_t* word_off, const uint16_t* mixtures, const float* lm, const float tdp[2][4],
                          float acoustic_pruning, float lm_pruning, uint32_t* out_word, float* out_score,

@@ -51,7 +51,7 @@ SYMBOLS = [
     "sr_bigram_stream_destroy",
     "sr_probe_fp16_denormals", "sr_probe_fp16_accumulation", "sr_prefilter_masks", "sr_prefilter_range_frames",
     "sr_refine_masks", "sr_refine_geometry",
-    "sr_gather_words", "sr_recognize_corpus_scores",
+    "sr_gather_words", "sr_recognize_corpus_scores", "sr_recognize_bigram_corpus_scores", "sr_bigram_route",
     "sr_profile_enable", "sr_profile_reset", "sr_profile_read",
 ]
 
@@ -200,6 +200,8 @@ def lib():
         L.sr_refine_masks.argtypes = [vp, vp, u64, vp, u64, vp]
         L.sr_refine_geometry.argtypes = [vp, u64, vp]
         L.sr_gather_words.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
+        L.sr_recognize_bigram_corpus_scores.argtypes = [vp, vp, vp, C.POINTER(BigramParams), vp, u64, vp, vp, vp, vp]
+        L.sr_bigram_route.argtypes = [vp, u32, C.c_char_p, C.c_size_t]
         L.sr_recognize_corpus_scores.argtypes = [vp, vp, vp, C.POINTER(SearchParams), vp, u64, i32, vp, vp, vp, vp, vp, vp]
         L.sr_profile_enable.argtypes = [vp, i32]
         L.sr_profile_reset.argtypes = [vp]
@@ -468,6 +470,14 @@ class Bigram:
         """Where the search keeps the state hypotheses with no flags: "registers", "lds" or "global" (sr_bigram_describe)."""
         buf = C.create_string_buffer(32)
         _check(lib().sr_bigram_describe(self.h, buf, len(buf)))
+        return buf.value.decode()
+
+    def route(self, dense_states=False, global_states=False):
+        """The kernel a recognition with these flags runs, as text (sr_bigram_route): "registers 3 rows4 0b100", "lds 2 x 12",
+        "global 8 entries lds", "global 8 entries global", "none"."""
+        buf = C.create_string_buffer(64)
+        flags = (BIGRAM_DENSE_STATES if dense_states else 0) | (BIGRAM_GLOBAL_STATES if global_states else 0)
+        _check(lib().sr_bigram_route(self.h, flags, buf, len(buf)))
         return buf.value.decode()
 
     def close(self):
@@ -1005,6 +1015,20 @@ class Corpus:
         off = np.zeros(self.n_utts + 1, np.uint64)
         p = BigramParams(acoustic_pruning, lm_pruning, kernel, max_word_ends, (BIGRAM_DENSE_STATES if dense_states else 0) | (BIGRAM_GLOBAL_STATES if global_states else 0))
         _check(lib().sr_recognize_bigram_corpus(self.model.h, self.h, bigram.h, C.byref(p), _ptr(ow), _ptr(osc), _ptr(ot), _ptr(off)))
+        n = int(off[-1])
+        return ow[:n], osc[:n], ot[:n], off
+
+    def recognize_bigram_scores(self, bigram, scores, acoustic_pruning=FLT_MAX, lm_pruning=FLT_MAX, max_word_ends=0, dense_states=False,
+                                global_states=False):
+        """sr_recognize_bigram_corpus_scores (test hook): the bigram search alone on the caller's score table [n_frames, n_states] (the
+        corpus's features are not read) -> as recognize_bigram"""
+        scores = np.ascontiguousarray(scores, dtype=np.float64)
+        cap = max(self.n_frames + self.n_utts, 1)
+        ow, osc, ot = np.zeros(cap, np.uint32), np.zeros(cap, np.float32), np.zeros(cap, np.uint32)
+        off = np.zeros(self.n_utts + 1, np.uint64)
+        p = BigramParams(acoustic_pruning, lm_pruning, GMM_DEFAULT, max_word_ends, (BIGRAM_DENSE_STATES if dense_states else 0) | (BIGRAM_GLOBAL_STATES if global_states else 0))
+        _check(lib().sr_recognize_bigram_corpus_scores(self.model.h, self.h, bigram.h, C.byref(p), _ptr(scores), scores.size, _ptr(ow), _ptr(osc),
+                                                       _ptr(ot), _ptr(off)))
         n = int(off[-1])
         return ow[:n], osc[:n], ot[:n], off
 

@@ -5,6 +5,8 @@
 
 #include <vector>
 
+#include "bigram_route.h"
+
 namespace srgpu {
 
 // ---- GMM scoring, FP64 MFMA contraction (gmm_mfma.hip) ------------------------------------------
@@ -519,13 +521,12 @@ struct BigramArgs {
   uint64_t gs_ws_words;         //   >= bigram_gs_ws_words(n_words, n_positions)
   unsigned long long* gs_active;  // global states, optional: += the positions step 3 visits, every frame
 };
-enum class BigramLayout { kRegisters, kLds, kGlobal, kNone };  // kNone: dense_states asked for an image the LDS cannot hold
-BigramLayout bigram_layout(const BigramArgs& a);  // what launch_bigram runs (register layout, dense LDS image, global states)
-uint64_t bigram_gs_ws_words(uint32_t n_words, uint32_t n_positions);  // global-states workspace per workgroup, 32-bit words
+// bigram_route.h: BigramLayout, BigramRoute, bigram_route() -- the one place that chooses the kernel -- and the LDS / workspace size
+// formulas (bigram_lds_bytes, bigram_gs_ws_words)
+BigramRoute bigram_route_of(const BigramArgs& a);  // what launch_bigram runs for these arguments (n_words .. global_states, ld)
+inline BigramLayout bigram_layout(const BigramArgs& a) { return bigram_route_of(a).layout; }
 uint32_t bigram_max_positions();
 hipError_t launch_bigram(const BigramArgs& a, hipStream_t stream);
-size_t bigram_lds_bytes(uint32_t n_words, uint32_t n_positions);
-bool bigram_register_layout(const BigramArgs& a);   // short words, <= 3072 of them, the emission row fits the LDS beside the lists
 uint32_t bigram_max_words();
 // The search net, built on the host beside the kernels that read it (as build_decode_net) from a lexicon of n_words words, word w's
 // emission states mixtures[word_off[w] .. word_off[w + 1]), the dense [W x W] table lm[w * W + h] = -log p(w | h) and tdp

@@ -1590,12 +1590,13 @@ int sr_bigram_destroy(sr_bigram* b) {
   });
 }
 
-// The bigram search of a corpus (sr_recognize_bigram_corpus).  before(chunks) runs once the chunks are known; after(chunk, table,
+// The bigram search of a corpus (sr_recognize_bigram_corpus).  score(chunk, table) enqueues the chunk's scores on m->s_gmm (score_chunk,
+// but for the test hook sr_recognize_bigram_corpus_scores); before(chunks) runs once the chunks are known; after(chunk, table,
 // stream) is enqueued behind each chunk's search on the same score table (sr_recognize_bigram_confidence_corpus: the forward-backward).
 extern "C++" {
-template <class Before, class After>
+template <class Score, class Before, class After>
 static int bigram_recognize_pass(sr_model* m, sr_corpus* c, sr_bigram* b, const sr_bigram_params* p, uint32_t* out_word, float* out_score,
-                                 uint32_t* out_time, uint64_t* out_off, Before before, After after) {
+                                 uint32_t* out_time, uint64_t* out_off, Score score, Before before, After after) {
   int rc = check_corpus(m, c);
   if (rc) return rc;
   if (!b || b->model != m) return fail(SR_EINVAL, "bigram search net does not belong to this model");
@@ -1662,7 +1663,7 @@ static int bigram_recognize_pass(sr_model* m, sr_corpus* c, sr_bigram* b, const 
   ba.out_word = b->out_word.p; ba.out_score = b->out_score.p; ba.out_time = b->out_time.p;
   ba.out_count = b->out_count.p; ba.out_flags = b->out_flags.p;
 
-  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); },
+  rc = run_chunks(m, chunks, score,
       [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
         ba.scores = table; ba.frame_base = ch.f0; ba.utt_first = ch.u0; ba.n_utts = ch.u1 - ch.u0;
         HIP_TRY(launch_bigram(ba, s));  // (invalid value: a layout without the workspace it needs -- a bug here, not the caller's)
@@ -1721,6 +1722,13 @@ static int bigram_recognize_pass(sr_model* m, sr_corpus* c, sr_bigram* b, const 
   if (m->profiling) m->prof.frames += F;
   return SR_OK;
 }
+// ... with the model's scores, as every production pass takes it
+template <class Before, class After>
+static int bigram_recognize_pass(sr_model* m, sr_corpus* c, sr_bigram* b, const sr_bigram_params* p, uint32_t* out_word, float* out_score,
+                                 uint32_t* out_time, uint64_t* out_off, Before before, After after) {
+  return bigram_recognize_pass(m, c, b, p, out_word, out_score, out_time, out_off,
+                               [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); }, before, after);
+}
 }  // extern "C++"
 
 int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr_bigram_params* p, uint32_t* out_word,
@@ -1728,6 +1736,47 @@ int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr
   return guarded(__func__, [&]() -> int {
   return bigram_recognize_pass(m, c, b, p, out_word, out_score, out_time, out_off, [](const std::vector<Chunk>&) { return SR_OK; },
                                [](const Chunk&, const double*, hipStream_t) { return SR_OK; });
+  });
+}
+
+// test hook: sr_recognize_bigram_corpus with the chunk's score step replaced by a copy of the caller's rows (padded to the table's row
+// stride with +inf, the whole table once, so that a chunk is one copy)
+int sr_recognize_bigram_corpus_scores(sr_model* m, sr_corpus* c, sr_bigram* b, const sr_bigram_params* p, const double* scores,
+                                      uint64_t n_scores, uint32_t* out_word, float* out_score, uint32_t* out_time, uint64_t* out_off) {
+  return guarded(__func__, [&]() -> int {
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  if (!scores && c->n_frames) return fail(SR_EINVAL, "null argument");
+  const uint64_t F = c->n_frames;
+  if (n_scores != F * m->n_states)
+    return fail(SR_EINVAL, "%llu scores for %llu frames x %u states", (unsigned long long)n_scores, (unsigned long long)F, m->n_states);
+  const size_t S = m->n_states, ld = m->ld;
+  std::vector<double> padded((size_t)F * ld, std::numeric_limits<double>::infinity());
+  for (uint64_t t = 0; t < F; t++) memcpy(padded.data() + t * ld, scores + t * S, sizeof(double) * S);
+  rc = bigram_recognize_pass(m, c, b, p, out_word, out_score, out_time, out_off,
+                             [&](const Chunk& ch, double* table) -> int {
+                               if (ch.f1 > ch.f0)
+                                 HIP_TRY(hipMemcpyAsync(table, padded.data() + ch.f0 * ld, sizeof(double) * (ch.f1 - ch.f0) * ld, hipMemcpyHostToDevice, m->s_gmm));
+                               return SR_OK;
+                             },
+                             [](const std::vector<Chunk>&) { return SR_OK; }, [](const Chunk&, const double*, hipStream_t) { return SR_OK; });
+  if (rc) (void)hipStreamSynchronize(m->s_gmm);  // (a copy may still be reading `padded`)
+  return rc;
+  });
+}
+
+int sr_bigram_route(const sr_bigram* b, uint32_t flags, char* out, size_t cap) {
+  return guarded(__func__, [&]() -> int {
+  if (!b || !out || cap == 0) return fail(SR_EINVAL, "null argument");
+  if (flags & ~(SR_BIGRAM_DENSE_STATES | SR_BIGRAM_GLOBAL_STATES)) return fail(SR_EINVAL, "unknown sr_bigram_params.flags 0x%x", (unsigned)flags);
+  if ((flags & SR_BIGRAM_DENSE_STATES) && (flags & SR_BIGRAM_GLOBAL_STATES))
+    return fail(SR_EINVAL, "SR_BIGRAM_DENSE_STATES and SR_BIGRAM_GLOBAL_STATES exclude each other");
+  BigramArgs ba = b->net;
+  ba.ld = b->model ? b->model->ld : 0;
+  ba.dense_states = (flags & SR_BIGRAM_DENSE_STATES) ? 1u : 0u;
+  ba.global_states = (flags & SR_BIGRAM_GLOBAL_STATES) ? 1u : 0u;
+  bigram_route_text(bigram_route_of(ba), out, cap);
+  return SR_OK;
   });
 }
 

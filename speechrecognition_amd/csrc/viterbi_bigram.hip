@@ -36,30 +36,10 @@
 
 namespace srgpu {
 
-static constexpr int kBgThreads = 1024;
-static constexpr int kBgWaves = kBgThreads / 64;
-static constexpr int kBgStage = 256;  // word ends staged per pass of the recombination loop (more for big lexica, see `stage`)
+// (kBgThreads, kBgWaves, kBgStage and the LDS size formulas: bigram_route.h, which also chooses the instantiation)
 static constexpr float kFltMax = 3.402823466e+38f;
 // flags on a word end of the merged list (see step 6): the same word end also sits LATER in the list / sat EARLIER
 static constexpr uint32_t kShadowed = 0x80000000u, kRepeat = 0x40000000u, kSlotMask = 0x3FFFFFFFu;
-
-// LDS image without the state hypotheses: entries, staging, scan scratch, the two active lists, the flags
-__host__ __device__ constexpr size_t bigram_lds_small(uint32_t n_words) {
-  return 2 * (size_t)n_words * 8 + (3 * kBgStage + kBgWaves + 1 + kBgWaves) * 4 + 2 * (size_t)n_words * 2 * 2 + 2 * (size_t)n_words + 64;
-}
-
-// global states: offset of step 3's prefix sums [2W] behind the small image (without the entries where they live in device memory)
-__host__ __device__ constexpr size_t bigram_gs_pre_off(uint32_t n_words, bool entries_global) {
-  return (bigram_lds_small(n_words) - (entries_global ? 2 * (size_t)n_words * 8 : 0) + 15u) & ~(size_t)15u;
-}
-__host__ __device__ constexpr size_t bigram_gs_lds(uint32_t n_words, bool entries_global) {
-  return bigram_gs_pre_off(n_words, entries_global) + 2 * (size_t)n_words * 4;
-}
-
-// register layout: offset of the emission row behind the small image and the LM row bounds
-__host__ __device__ constexpr size_t bigram_lds_row_off(uint32_t n_words) {
-  return (((bigram_lds_small(n_words) + 15u) & ~(size_t)15u) + 2 * (size_t)n_words * 4 + 1023u) & ~(size_t)1023u;
-}
 
 // inclusive prefix sum over the wave with DPP row shifts and broadcasts (six vector instructions; __shfl_up is a
 // ds_bpermute round trip per step)
@@ -1007,48 +987,40 @@ __global__ __launch_bounds__(kBgThreads) void bigram_stream_kernel(BigramStreamA
   bigram_utterance<KW, 4, 0, 0, GSM, true>(s.a, 0, job.slot, &s, &job);
 }
 
-size_t bigram_lds_bytes(uint32_t n_words, uint32_t n_positions) { return (size_t)n_positions * 8 + bigram_lds_small(n_words); }
-uint32_t bigram_max_words() { return 8 * kBgThreads; }
-
-static size_t bigram_lds_regs(uint32_t n_words, uint32_t ld) { return bigram_lds_row_off(n_words) + (((size_t)ld * 8 + 1023u) & ~(size_t)1023u); }
-bool bigram_register_layout(const BigramArgs& a) {
-  return !a.dense_states && !a.global_states && a.max_slot_states <= 4 && a.silence_states == 1 && a.n_words <= 3 * kBgThreads && bigram_lds_regs(a.n_words, a.ld) <= 160 * 1024;
-}
-
-static bool bigram_gs_entries_global(uint32_t n_words) { return bigram_gs_lds(n_words, false) > 160 * 1024; }
-uint64_t bigram_gs_ws_words(uint32_t n_words, uint32_t n_positions) {
-  return 4ull * n_positions + (bigram_gs_entries_global(n_words) ? 4ull * n_words : 0ull);
-}
+uint32_t bigram_max_words() { return kBgMaxWords; }
 uint32_t bigram_max_positions() { return 0x7FFFFFFFu; }  // a position index must stay clear of the entry tag 0x80000000 (bigram_position)
 
-BigramLayout bigram_layout(const BigramArgs& a) {
-  if (a.global_states) return BigramLayout::kGlobal;
-  if (bigram_register_layout(a)) return BigramLayout::kRegisters;
-  if (bigram_lds_bytes(a.n_words, a.n_positions) <= 160 * 1024) return BigramLayout::kLds;
-  return a.dense_states ? BigramLayout::kNone : BigramLayout::kGlobal;
+BigramRoute bigram_route_of(const BigramArgs& a) {
+  return bigram_route(a.n_words, a.n_positions, a.ld, a.max_slot_states, a.silence_states, a.row4_mask, a.dense_states != 0, a.global_states != 0);
 }
 
-// The <KW, GSM> instantiation of the global-states kernels (bigram_gs_kernel, bigram_stream_kernel) for a lexicon of n_words words:
+// The launchers below switch on bigram_route's answer (bigram_route.h) and decide nothing themselves; a route without a case here is
+// hipErrorInvalidValue (tests/test_bigram_route_cpu.py holds the cases against the set of routes the function can return).
+#define SR_BG_ROUTE_KEY(kw, b) ((kw) * 32 + (b))
+
+// The <KW, GSM> instantiation of the global-states kernels (bigram_gs_kernel, bigram_stream_kernel) of a kGlobal route:
 // go(std::integral_constant KW, std::integral_constant GSM) launches it
 template <class Go>
-static hipError_t dispatch_gs(uint32_t n_words, Go go) {
-  using K1 = std::integral_constant<int, 1>;
-  using K2 = std::integral_constant<int, 2>;
-  using K4 = std::integral_constant<int, 4>;
-  using K8 = std::integral_constant<int, 8>;
-  const uint32_t kw = (n_words + kBgThreads - 1) / kBgThreads;
-  if (kw <= 1) return go(K1{}, K1{});
-  if (kw <= 2) return go(K2{}, K1{});
-  if (kw <= 4) return go(K4{}, K1{});
-  if (!bigram_gs_entries_global(n_words)) return go(K8{}, K1{});
-  return go(K8{}, K2{});
+static hipError_t dispatch_gs(const BigramRoute& r, Go go) {
+  if (r.layout != BigramLayout::kGlobal) return hipErrorInvalidValue;
+#define SR_BG_GS(KWv, GSMv) case SR_BG_ROUTE_KEY(KWv, GSMv): return go(std::integral_constant<int, KWv>{}, std::integral_constant<int, GSMv>{})
+  switch (SR_BG_ROUTE_KEY(r.kw, r.gsm)) {
+    SR_BG_GS(1, 1); SR_BG_GS(2, 1); SR_BG_GS(4, 1); SR_BG_GS(8, 1); SR_BG_GS(8, 2);
+    default: return hipErrorInvalidValue;
+  }
+#undef SR_BG_GS
 }
 
-static hipError_t launch_bigram_gs(const BigramArgs& a, hipStream_t stream) {
-  const size_t smem = bigram_gs_lds(a.n_words, bigram_gs_entries_global(a.n_words));
+static BigramRoute gs_route_of(BigramArgs a) {
+  a.dense_states = 0; a.global_states = 1;
+  return bigram_route_of(a);
+}
+
+static hipError_t launch_bigram_gs(const BigramArgs& a, const BigramRoute& r, hipStream_t stream) {
+  const size_t smem = r.smem;
   const uint32_t grid = a.gs_grid < a.n_utts ? a.gs_grid : a.n_utts;
   if (grid == 0 || !a.gs_ws || a.gs_ws_words < bigram_gs_ws_words(a.n_words, a.n_positions)) return hipErrorInvalidValue;
-  return dispatch_gs(a.n_words, [&](auto kw, auto gsm) {
+  return dispatch_gs(r, [&](auto kw, auto gsm) {
     const auto kernel = bigram_gs_kernel<decltype(kw)::value, decltype(gsm)::value>;
     hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) return e;
@@ -1060,9 +1032,10 @@ static hipError_t launch_bigram_gs(const BigramArgs& a, hipStream_t stream) {
 hipError_t launch_bigram_stream(const BigramStreamArgs& s, uint32_t n_jobs, hipStream_t stream) {
   if (n_jobs == 0) return hipSuccess;
   const BigramArgs& a = s.a;
-  const size_t smem = bigram_gs_lds(a.n_words, bigram_gs_entries_global(a.n_words));
+  const BigramRoute r = gs_route_of(a);
+  const size_t smem = r.smem;
   if (!a.gs_ws || a.gs_ws_words < bigram_gs_ws_words(a.n_words, a.n_positions)) return hipErrorInvalidValue;
-  return dispatch_gs(a.n_words, [&](auto kw, auto gsm) {
+  return dispatch_gs(r, [&](auto kw, auto gsm) {
     const auto kernel = bigram_stream_kernel<decltype(kw)::value, decltype(gsm)::value>;
     hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) return e;
@@ -1073,53 +1046,37 @@ hipError_t launch_bigram_stream(const BigramStreamArgs& s, uint32_t n_jobs, hipS
 
 hipError_t launch_bigram(const BigramArgs& a, hipStream_t stream) {
   if (a.n_utts == 0) return hipSuccess;
-  const BigramLayout layout = bigram_layout(a);
-  if (layout == BigramLayout::kNone) return hipErrorInvalidValue;
-  if (layout == BigramLayout::kGlobal) return launch_bigram_gs(a, stream);
-  const bool regs = layout == BigramLayout::kRegisters;
-  const size_t smem = regs ? bigram_lds_regs(a.n_words, a.ld) : (bigram_lds_bytes(a.n_words, a.n_positions) + 15) & ~(size_t)15;
+  const BigramRoute r = bigram_route_of(a);
+  if (r.layout == BigramLayout::kNone) return hipErrorInvalidValue;
+  if (r.layout == BigramLayout::kGlobal) return launch_bigram_gs(a, r, stream);
+  const size_t smem = r.smem;
   auto go = [&](auto kernel) {
     hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kernel, dim3(a.n_utts), dim3(kBgThreads), smem, stream, a);
     return hipGetLastError();
   };
-  const uint32_t kw = (a.n_words + kBgThreads - 1) / kBgThreads, kp = (a.n_positions + kBgThreads - 1) / kBgThreads;
-  if (regs) {  // lane tid: words tid + k * 1024 and their silence copies; three states per word, four in the slot rows of row4_mask
-    const uint32_t mask = a.max_slot_states <= 3 ? 0u : (a.row4_mask ? a.row4_mask : (1u << kw) - 1u);
-    switch (kw <= 1 ? 1 : kw <= 2 ? 2 : 3) {
-      case 1:
-        if (mask == 0) return go(bigram_kernel<1, 4, 1, 0>);
-        return go(bigram_kernel<1, 4, 1, 1>);
-      case 2:
-        switch (mask & 3u) {
-          case 0: return go(bigram_kernel<2, 4, 2, 0>);
-          case 1: return go(bigram_kernel<2, 4, 2, 1>);
-          case 2: return go(bigram_kernel<2, 4, 2, 2>);
-          default: return go(bigram_kernel<2, 4, 2, 3>);
-        }
-      default:
-        switch (mask & 7u) {
-          case 0: return go(bigram_kernel<3, 4, 3, 0>);
-          case 1: return go(bigram_kernel<3, 4, 3, 1>);
-          case 2: return go(bigram_kernel<3, 4, 3, 2>);
-          case 3: return go(bigram_kernel<3, 4, 3, 3>);
-          case 4: return go(bigram_kernel<3, 4, 3, 4>);
-          case 5: return go(bigram_kernel<3, 4, 3, 5>);
-          case 6: return go(bigram_kernel<3, 4, 3, 6>);
-          default: return go(bigram_kernel<3, 4, 3, 7>);
-        }
+  if (r.layout == BigramLayout::kRegisters) {
+#define SR_BG_REGS(KWv, NPMv) case SR_BG_ROUTE_KEY(KWv, NPMv): return go(bigram_kernel<KWv, 4, KWv, NPMv>)
+    switch (SR_BG_ROUTE_KEY(r.kw, r.npm)) {
+      SR_BG_REGS(1, 0); SR_BG_REGS(1, 1);
+      SR_BG_REGS(2, 0); SR_BG_REGS(2, 1); SR_BG_REGS(2, 2); SR_BG_REGS(2, 3);
+      SR_BG_REGS(3, 0); SR_BG_REGS(3, 1); SR_BG_REGS(3, 2); SR_BG_REGS(3, 3); SR_BG_REGS(3, 4); SR_BG_REGS(3, 5); SR_BG_REGS(3, 6); SR_BG_REGS(3, 7);
+      default: return hipErrorInvalidValue;
     }
+#undef SR_BG_REGS
   }
-#define SR_BG(KWv, KPv) return go(bigram_kernel<KWv, KPv, 0, 0>)
-#define SR_BG_KP(KWv) do { if (kp <= 4) SR_BG(KWv, 4); if (kp <= 12) SR_BG(KWv, 12); if (kp <= 20) SR_BG(KWv, 20); return hipErrorInvalidValue; } while (0)
-  if (kw <= 1) SR_BG_KP(1);
-  if (kw <= 2) SR_BG_KP(2);
-  if (kw <= 4) SR_BG_KP(4);
-  SR_BG_KP(8);
-#undef SR_BG_KP
-#undef SR_BG
+  // (no <4, 4> and no <8, .>: bigram_route never returns them, see the inequality in bigram_route.h)
+#define SR_BG_LDS(KWv, KPv) case SR_BG_ROUTE_KEY(KWv, KPv): return go(bigram_kernel<KWv, KPv, 0, 0>)
+  switch (SR_BG_ROUTE_KEY(r.kw, r.kp)) {
+    SR_BG_LDS(1, 4); SR_BG_LDS(1, 12); SR_BG_LDS(1, 20);
+    SR_BG_LDS(2, 4); SR_BG_LDS(2, 12); SR_BG_LDS(2, 20);
+    SR_BG_LDS(4, 12); SR_BG_LDS(4, 20);
+    default: return hipErrorInvalidValue;
+  }
+#undef SR_BG_LDS
 }
+#undef SR_BG_ROUTE_KEY
 
 BigramArgs build_bigram_net(uint32_t n_words, const uint32_t* word_off, const uint16_t* mixtures, uint32_t silence_word, const float* lm,
                             const float tdp[8], std::vector<uint32_t>& slot_off, std::vector<uint32_t>& slot_mix,
