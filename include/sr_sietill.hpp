@@ -568,6 +568,18 @@ class StreamingRecognizer {
     check(sr_stream_partial(s_, id, w.data(), (uint32_t)w.size(), &n, nullptr));
     return std::vector<WordIdx>(w.begin(), w.begin() + n);
   }
+  // the leading words of partial(id) that no later frame can change (sr_stream_stable): a prefix of every later partial() and of
+  // end() whose traceback entry is finite.  *commit (may be null): the frame they end at; *trailing_silence (may be null): the frames
+  // the best hypothesis has spent in silence at the end -- an endpointer calls end() once it passes its threshold
+  std::vector<WordIdx> stable(uint32_t id, uint32_t* commit = nullptr, uint32_t* trailing_silence = nullptr) {
+    std::vector<uint32_t> w(max_frames_);
+    uint64_t off[2] = {0, 0};
+    uint32_t c = 0, sil = 0;
+    check(sr_stream_stable(s_, 1, &id, w.data(), w.size(), off, &c, &sil));
+    if (commit) *commit = c;
+    if (trailing_silence) *trailing_silence = sil;
+    return std::vector<WordIdx>(w.begin(), w.begin() + off[1]);
+  }
   std::vector<WordIdx> end(uint32_t id) {
     std::vector<uint32_t> w(max_frames_);
     uint32_t n = 0;
@@ -1802,6 +1814,18 @@ class StreamingLinearSearch {
   }
   void getResult(uint32_t id, Traceback& result) { items(id, result, false); }
   void end(uint32_t id, Traceback& result) { items(id, result, true); }
+  // the leading items of getResult(id) that no later frame can change (sr_bigram_stream_stable): a prefix of every later
+  // getResult() and of end() that is not empty.  *commit (may be null): the time of the last of them, 0 if there is none
+  void stable(uint32_t id, Traceback& result, uint32_t* commit = nullptr) {
+    std::vector<uint32_t> words(max_frames_), times(max_frames_);
+    std::vector<float> scores(max_frames_);
+    uint64_t off[2] = {0, 0};
+    uint32_t c = 0;
+    check(sr_bigram_stream_stable(s_, 1, &id, words.data(), scores.data(), times.data(), words.size(), off, &c));
+    if (commit) *commit = c;
+    result.clear();
+    for (uint64_t i = 0; i < off[1]; i++) result.push_back(TracebackItem{words[i], scores[i], times[i]});
+  }
 
  private:
   void items(uint32_t id, Traceback& result, bool final_) {

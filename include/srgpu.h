@@ -231,6 +231,34 @@ SR_API int sr_stream_end(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_
                          uint16_t* tb_word, uint16_t* tb_bkp);
 SR_API int sr_stream_destroy(sr_stream* s);
 
+/* ---- the stable prefix of a streaming result, and a trailing-silence count -----------------------------------------------
+ * sr_stream_partial's words can still change with later frames; sr_stream_stable returns the leading part of them that cannot.
+ * After t pushed frames of an utterance:
+ *   B           the set { bk[p] : sc[p] finite } over the trellis positions p of the search's current hypotheses (bk: the frame
+ *               before the hypothesis' word started, the reference's Book::bkp); for t = 0, B = {0}.
+ *   the tree    node c > 0 (a frame) has the parent tb_bkp[c] < c, the traceback entry sr_stream_end returns; node 0 is the root.
+ *   commit      c(t) = the nearest common ancestor of B in that tree.  Every traceback a later frame can produce runs through a
+ *               member of B, hence through c(t): no later frame can move it, and c(t + 1) is c(t) or a descendant of it.  With no
+ *               hypothesis alive the commit point stays where it was.
+ *   stable      the words the guarded walk of sr_stream_partial returns when started at frame c(t) instead of t, silence removed.
+ *               They are a prefix of sr_stream_partial at this and at every later frame t' whose tb_score[t'] is finite, and of
+ *               sr_stream_end under the same condition.  (A frame at which no word end survives records (inf, word 0, bkp 0):
+ *               ending there returns no words at all -- the reference's behaviour, stated, not changed.)
+ *   silence     on the alive hypothesis of least score (ties: the smaller position): t - bk if its position belongs to the silence
+ *               word, else 0; 0 with no alive hypothesis.  An endpointer ends the utterance when this passes its threshold.
+ * sr_stream_stable  n utterances, ids[n], each at most once, in ONE launch (stream_commit_kernel: one workgroup per utterance, started
+ *                   only by this call -- sr_stream_push does no work for it) whose results land in one pinned block.  out_words:
+ *                   the stable words back to back, utterance i's at [out_word_off[i], out_word_off[i + 1]) (cap = capacity of
+ *                   out_words, which may be NULL if cap is 0); out_commit[i] = c(t); out_silence[i] (the array may be NULL) = the
+ *                   trailing silence.  The call reads the search's state and changes none of it; it keeps the commit point per
+ *                   utterance, so that a call's walk is bounded by the traceback nodes above the previous call's commit point.
+ *                   First call: 4 + 4 max_frames bytes of device memory per stream.
+ * Errors, everything checked before the launch: SR_EINVAL for an unknown, ended or repeated id; SR_EINVAL for a cap below the
+ * word count (out_word_off then holds the offsets needed, nothing else is written); SR_ECORRUPT for a walk that fails its guards
+ * (nothing is written). */
+SR_API int sr_stream_stable(sr_stream* s, uint32_t n, const uint32_t* ids, uint32_t* out_words, uint64_t cap, uint64_t* out_word_off,
+                            uint32_t* out_commit, uint32_t* out_silence);
+
 /* ---- several devices: the `#pragma omp parallel for` over segments of Recognizer::recognize (Recognizer.cpp:46-47) -------
  * Utterances are independent, so a batch shards across devices with no collective: sr_shard_utterances deals them by
  * greedy longest-processing-time on frame counts (decreasing length, each to the lightest shard so far; deterministic);
@@ -1016,6 +1044,22 @@ SR_API int sr_bigram_stream_end(sr_bigram_stream* s, uint32_t id, uint32_t* out_
                                 uint32_t cap, uint32_t* count);
 SR_API int sr_bigram_stream_destroy(sr_bigram_stream* s);
 
+/* The stable prefix of the bigram stream's result: sr_stream_stable's construction over the utterance's book.
+ *   the tree    the book's entries; the parent of entry b is its back pointer book[b].z < b; the root is the start entry (time 0).
+ *   B           the back pointers a later word end can start from: those of the finite state hypotheses (on the active word
+ *               slots) and those of the last frame's merged word-end list, from which the next frame builds every word start.  A
+ *               silence entry counts as its parent: a silence word end that follows it takes that parent instead (LinearSearch
+ *               avoids chains of silence, :410-415), so both continuations run through the parent.
+ *   commit      the nearest common ancestor of B; it never moves back.
+ *   stable      the items (word, score, time, as sr_bigram_stream_partial reports them) from the start entry to the commit entry.
+ *               They are a prefix of every later sr_bigram_stream_partial and of sr_bigram_stream_end whose count is not 0.
+ * sr_bigram_stream_stable  n utterances in one launch (bigram_stream_commit_kernel), results in one pinned block: the items back to
+ *                          back in out_word / out_score / out_time (cap = capacity of each; NULL allowed if cap is 0), utterance i's
+ *                          at [out_off[i], out_off[i + 1]); out_commit[i] = the book time of the commit entry (0: nothing is stable).
+ * Errors as sr_stream_stable; SR_EINTERNAL for an utterance whose book overflowed. */
+SR_API int sr_bigram_stream_stable(sr_bigram_stream* s, uint32_t n, const uint32_t* ids, uint32_t* out_word, float* out_score,
+                                   uint32_t* out_time, uint64_t cap, uint64_t* out_off, uint32_t* out_commit);
+
 /* Diagnostic: does the fp16 matrix pipe keep subnormal inputs on this device (an assumption of SR_GMM_PREFILTER's
  * error bound; when it does not hold, models are scored by SR_GMM_EXACT's kernel instead)? */
 SR_API int sr_probe_fp16_denormals(int device, int* preserved);
@@ -1052,6 +1096,14 @@ SR_API int sr_refine_geometry(sr_model* m, uint64_t n_frames, uint32_t out[4]);
  * SRGPU_GATHER=host (read when a model is created; a diagnostic knob, same output). */
 SR_API int sr_gather_words(sr_model* m, uint32_t n_utts, const uint64_t* frame_off, const uint32_t* counts, const uint32_t* flags,
                            const uint32_t* words, uint32_t* out_words, uint64_t* out_word_off);
+/* Test hook: the nearest-common-ancestor fold of the stable calls alone (commit_point.h), on forests the caller supplies (host arrays).
+ * Set i: the tree parent[node_off[i] .. node_off[i + 1]) -- parent[0] = 0 is the root, parent[j] < j -- the candidate nodes
+ * set[set_off[i] .. set_off[i + 1]) and floor[i], an ancestor of all of them (the previous commit point; 0 always qualifies), at which
+ * a walk may stop.  out[i] = the nearest common ancestor of the candidates.  One workgroup per set: a thread folds its candidates, a
+ * wave folds by shuffles, the waves through LDS.  SR_EINVAL for a parent not below its child, a node or floor out of range, an empty
+ * set or an empty tree, node_off[0] or set_off[0] != 0. */
+SR_API int sr_commit_points(sr_model* m, uint32_t n_sets, const uint64_t* node_off, const uint32_t* parent, const uint64_t* set_off,
+                            const uint32_t* set, const uint32_t* floor, uint32_t* out);
 /* Test hook: the zerogram search alone, on a score table the caller supplies instead of the GMM scores: sr_recognize_corpus' pass
  * -- the same chunks, launch order, kernel route from p->flags, replay workspace, compaction of the words and traceback copies --
  * except that a chunk's score step copies rows [f0, f1) of `scores` into the chunk's table (row stride: n_states rounded up to 8,

@@ -23,7 +23,7 @@ SOURCES = ["srgpu_api.cpp", "mixset.cpp", "feeder.cpp", "gmm_mfma.hip", "gmm_exa
            "em_accumulate.hip", "em_finalize.hip", "fmllr_stats.hip", "fmllr.cpp", "mllr_stats.hip", "map_stats.hip", "mllt_stats.hip", "lda_stats.hip", "model_structure.hip",
            "gather_words.hip"]
 # (mllr.cpp, mllt.cpp, lda.cpp and map.cpp are included by fmllr.cpp: listed with the headers so that their content enters the stamps)
-HEADERS = ["mllr.cpp", "mllt.cpp", "lda.cpp", "map.cpp", "kernels.h", "host_util.h", "handles.h", "traceback.h", "dpp_util.h", "netfb_device.h", "smbr_device.h", "sym_contract.h", "structure_plan.h", "fb_plan.h", "bigram_route.h", os.path.join("..", "..", "include", "srgpu.h")]
+HEADERS = ["mllr.cpp", "mllt.cpp", "lda.cpp", "map.cpp", "kernels.h", "host_util.h", "handles.h", "traceback.h", "commit_point.h", "dpp_util.h", "netfb_device.h", "smbr_device.h", "sym_contract.h", "structure_plan.h", "fb_plan.h", "bigram_route.h", os.path.join("..", "..", "include", "srgpu.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 # these replay the reference's SSE2 operation order and must not contract a*b+c into an FMA
 PER_FILE = {"gmm_exact.hip": ["-ffp-contract=off"], "gmm_prefilter.hip": ["-ffp-contract=off"], "em_accumulate.hip": ["-ffp-contract=off"],

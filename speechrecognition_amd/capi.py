@@ -47,6 +47,7 @@ SYMBOLS = [
     "sr_bigram_accuracies_corpus", "sr_bigram_smbr_statistics_corpus",
     "sr_bigram_word_lattice_corpus", "sr_bigram_lattice_nbest",
     "sr_stream_open", "sr_stream_begin", "sr_stream_push", "sr_stream_partial", "sr_stream_end", "sr_stream_destroy",
+    "sr_stream_stable", "sr_bigram_stream_stable", "sr_commit_points",
     "sr_bigram_stream_open", "sr_bigram_stream_begin", "sr_bigram_stream_push", "sr_bigram_stream_partial", "sr_bigram_stream_end",
     "sr_bigram_stream_destroy",
     "sr_probe_fp16_denormals", "sr_probe_fp16_accumulation", "sr_prefilter_masks", "sr_prefilter_range_frames",
@@ -187,6 +188,9 @@ def lib():
         L.sr_stream_partial.argtypes = [vp, u32, vp, u32, C.POINTER(u32), C.POINTER(u64)]
         L.sr_stream_end.argtypes = [vp, u32, vp, u32, C.POINTER(u32), vp, vp, vp]
         L.sr_stream_destroy.argtypes = [vp]
+        L.sr_stream_stable.argtypes = [vp, u32, vp, vp, u64, vp, vp, vp]
+        L.sr_bigram_stream_stable.argtypes = [vp, u32, vp, vp, vp, vp, u64, vp, vp]
+        L.sr_commit_points.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
         L.sr_bigram_stream_open.argtypes = [vp, vp, C.POINTER(BigramParams), u32, u64, C.POINTER(vp)]
         L.sr_bigram_stream_begin.argtypes = [vp, C.POINTER(u32)]
         L.sr_bigram_stream_push.argtypes = [vp, u32, vp, vp, vp]
@@ -544,6 +548,17 @@ class Stream(_StreamSet):
         _check(lib().sr_stream_partial(self.h, id, _ptr(out), len(out), C.byref(n), C.byref(t)))
         return (out[: n.value].copy(), t.value) if frames else out[: n.value].copy()
 
+    def stable(self, ids):
+        """sr_stream_stable -> (words per id: list of u32[], commit u32[n], silence u32[n]): the leading words of partial() that no
+        later frame can change, the commit frame they end at, and the frames the best hypothesis has spent in trailing silence"""
+        ids = np.ascontiguousarray(list(ids), dtype=np.uint32)
+        n = len(ids)
+        cap = int(sum(self.frames.get(int(i), 0) for i in ids))  # a word takes a frame at least
+        out, off = np.zeros(max(cap, 1), np.uint32), np.zeros(n + 1, np.uint64)
+        commit, silence = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        _check(lib().sr_stream_stable(self.h, n, _ptr(ids), _ptr(out), cap, _ptr(off), _ptr(commit), _ptr(silence)))
+        return [out[int(off[i]): int(off[i + 1])].copy() for i in range(n)], commit[:n], silence[:n]
+
     def end(self, id, traceback=False):
         """-> final words (u32[]) [, (tb_score, tb_word, tb_bkp) of T + 1 entries]; frees the id"""
         out = np.zeros(self.max_frames, np.uint32)
@@ -582,6 +597,18 @@ class BigramStream(_StreamSet):
         _check(lib().sr_bigram_stream_partial(self.h, id, _ptr(ow), _ptr(osc), _ptr(ot), len(ow), C.byref(n), C.byref(t)))
         items = (ow[: n.value].copy(), osc[: n.value].copy(), ot[: n.value].copy())
         return (items, t.value) if frames else items
+
+    def stable(self, ids):
+        """sr_bigram_stream_stable -> (items per id: list of (words, scores, times), commit u32[n]): the leading items of partial()
+        that no later frame can change, and the book time of the entry they end at"""
+        ids = np.ascontiguousarray(list(ids), dtype=np.uint32)
+        n = len(ids)
+        cap = int(sum(self.frames.get(int(i), 0) for i in ids))  # an item takes a frame at least
+        ow, osc, ot = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.float32), np.zeros(max(cap, 1), np.uint32)
+        off, commit = np.zeros(n + 1, np.uint64), np.zeros(max(n, 1), np.uint32)
+        _check(lib().sr_bigram_stream_stable(self.h, n, _ptr(ids), _ptr(ow), _ptr(osc), _ptr(ot), cap, _ptr(off), _ptr(commit)))
+        cut = [slice(int(off[i]), int(off[i + 1])) for i in range(n)]
+        return [(ow[c].copy(), osc[c].copy(), ot[c].copy()) for c in cut], commit[:n]
 
     def end(self, id):
         """-> the final items (words, scores, times); frees the id"""
@@ -1242,6 +1269,25 @@ def mllt_affine(A):
     """[A 0] as f64[1, D, D+1]: the W of Corpus.transform (one speaker) and Model.transform_means (one class) that applies A."""
     A = np.asarray(A, dtype=np.float64)
     return np.ascontiguousarray(np.hstack([A, np.zeros((A.shape[0], 1))])[None])
+
+
+def commit_points(model, parents, sets, floors=None):
+    """sr_commit_points (test hook): per set i the nearest common ancestor of the nodes sets[i] in the tree parents[i] (parents[i][0] = 0,
+    parents[i][j] < j), found by the device fold of the stable calls; floors[i] (default 0) is an ancestor of all of sets[i]."""
+    n = len(parents)
+    assert len(sets) == n
+    node_off = np.concatenate([[0], np.cumsum([len(p) for p in parents])]).astype(np.uint64)
+    set_off = np.concatenate([[0], np.cumsum([len(x) for x in sets])]).astype(np.uint64)
+    parent = np.ascontiguousarray(np.concatenate([np.asarray(p, np.uint32) for p in parents]) if n else np.zeros(0, np.uint32), dtype=np.uint32)
+    nodes = np.ascontiguousarray(np.concatenate([np.asarray(x, np.uint32) for x in sets]) if n else np.zeros(0, np.uint32), dtype=np.uint32)
+    floor = np.ascontiguousarray(np.zeros(n, np.uint32) if floors is None else floors, dtype=np.uint32)
+    out = np.zeros(max(n, 1), np.uint32)
+    if len(parent) == 0:
+        parent = np.zeros(1, np.uint32)
+    if len(nodes) == 0:
+        nodes = np.zeros(1, np.uint32)
+    _check(lib().sr_commit_points(model.h, n, _ptr(node_off), _ptr(parent), _ptr(set_off), _ptr(nodes), _ptr(floor), _ptr(out)))
+    return out[:n]
 
 
 def traceback_words(tb_word, tb_bkp, silence_word, n_words):

@@ -345,6 +345,11 @@ struct sr_stream {
   // per push, sized by the largest push so far
   DevBuf<float> feats;
   DevBuf<srgpu::StreamJob> jobs;
+  // sr_stream_stable, allocated by its first call: the previous commit point per slot (a separate array: StreamState is the search
+  // kernel's), the walk's words (max_frames each), and the call's pinned block -- its jobs in, its results and words out
+  std::vector<uint8_t> commit_fresh;  // [max_streams] no commit point computed for the slot's utterance yet
+  DevBuf<uint32_t> commit, stable_words;
+  PinnedBuf<unsigned char> stable_block;
 };
 
 // A set of concurrently open utterances on one (model, bigram search net) (sr_bigram_stream_*, srgpu_api.cpp).  The device state of
@@ -369,6 +374,11 @@ struct sr_bigram_stream {
   // per push, sized by the largest push so far
   DevBuf<float> feats;
   DevBuf<srgpu::BigramStreamJob> jobs;
+  // sr_bigram_stream_stable, allocated by its first call: the previous commit entry per slot (a book index; a separate array:
+  // BigramStreamState is the search kernel's) and the call's pinned block -- its jobs in, its results and items out
+  std::vector<uint8_t> commit_fresh;  // [max_streams] no commit entry computed for the slot's utterance yet
+  DevBuf<uint32_t> commit;
+  PinnedBuf<unsigned char> stable_block;
 };
 
 namespace srhost {

@@ -262,6 +262,50 @@ struct StreamArgs {
   uint64_t words_stride;  // max_frames
 };
 hipError_t launch_decode_stream(const StreamArgs& a, uint32_t n_jobs, hipStream_t stream);
+// the stable prefix (sr_stream_stable): stream_commit_kernel, one workgroup per requested stream, reads what the last push left
+// -- the current buffer's scores and back pointers, the traceback -- and changes none of it.  It folds the back pointers of the
+// alive hypotheses into their nearest common ancestor in the traceback (commit_point.h), walks from there (traceback.h) into the
+// slot's own word buffer, and copies the words and a StableResult into the call's result block.
+static constexpr uint32_t kStableCorrupt = 1u;  // StableResult::flags: a parent not below its child, or the walk failed its guards
+struct StableJob {         // one workgroup of a call
+  uint32_t slot;           // stream slot
+  uint32_t t;              // frames searched so far
+  uint32_t fresh;          // no commit point computed for this utterance yet: the floor is 0, commit[slot] is not read
+  uint32_t pad;
+  uint64_t word_off;       // its words' place in the block's word area (t slots: the walk returns at most one word per frame)
+};
+struct StableResult {
+  uint32_t commit;         // the commit point c(t): a frame
+  uint32_t silence;        // trailing silence in frames
+  uint32_t count;          // stable words
+  uint32_t flags;
+};
+struct StableArgs {
+  DecodeNet net;
+  const StableJob* jobs;    // [workgroups]
+  const unsigned char* ws;  // [slots x ws_stride]: the search's hypotheses, read only
+  size_t ws_stride;
+  const uint16_t* tb_word;  // [slots x tb_stride], read only
+  const uint16_t* tb_bkp;
+  uint64_t tb_stride;
+  uint32_t* commit;         // [slots] the previous commit point, carried from call to call
+  uint32_t* words;          // [slots x words_stride] the walk's buffer
+  uint64_t words_stride;    // max_frames
+  StableResult* out_res;    // [workgroups]
+  uint32_t* out_words;      // the block's word area
+};
+hipError_t launch_stream_commit(const StableArgs& a, uint32_t n_jobs, hipStream_t stream);
+// the fold alone (sr_commit_points): set i's nodes set[set_off[i] .. set_off[i + 1]) in the tree parent[node_off[i] ..], out[i] their
+// nearest common ancestor (kCommitCorrupt of commit_point.h where a parent is not below its child)
+struct CommitPointsArgs {
+  const uint64_t* node_off;  // [n_sets + 1]
+  const uint32_t* parent;
+  const uint64_t* set_off;   // [n_sets + 1]
+  const uint32_t* set;
+  const uint32_t* floor;     // [n_sets]
+  uint32_t* out;             // [n_sets]
+};
+hipError_t launch_commit_points(const CommitPointsArgs& a, uint32_t n_sets, hipStream_t stream);
 // the traceback walk alone (traceback.h) on arrays in the traceback layout above; out_flags[u] = kFlagCorrupt where it does not walk
 hipError_t launch_traceback(const uint64_t* frame_off, uint32_t n_utts, const uint16_t* tb_word, const uint16_t* tb_bkp,
                             uint32_t silence_word, uint32_t n_words, uint32_t* out_words, uint32_t* out_count,
@@ -564,6 +608,29 @@ struct BigramStreamArgs {
   uint64_t items_stride;       // max_frames + 1
 };
 hipError_t launch_bigram_stream(const BigramStreamArgs& s, uint32_t n_jobs, hipStream_t stream);
+// the stable prefix (sr_bigram_stream_stable): bigram_stream_commit_kernel, one workgroup per requested stream, reads what the last
+// push left -- the state record, the saved active list, the image's current buffer, the merged word-end list, the book -- and changes
+// none of it.  The nearest common ancestor (commit_point.h; parent(b) = book[b].z) of the entries a later word end can start from is
+// the commit entry; the items from the start entry to it go straight into the call's result block (StableResult::commit = its time).
+struct BigramStableJob {       // one workgroup of a call
+  uint32_t slot, t, fresh, pad;  // stream slot, frames searched so far, no commit entry computed for this utterance yet
+  const uint4* book;           // the slot's book (NULL while t == 0)
+  uint64_t item_off;           // its items' place in each of the block's three item areas (t slots: an item steps back a frame at least)
+};
+struct BigramStableArgs {
+  uint32_t n_words, silence, n_positions;
+  const uint32_t* slot_off;    // [2W + 1]
+  const uint32_t* gs_ws;       // [slots x gs_ws_words], read only
+  uint64_t gs_ws_words;
+  const uint32_t* we_bp;       // [slots x 2 x 2W], read only: list 0 is the merged one
+  const uint16_t* lsave;       // [slots x 2W]
+  const BigramStreamState* state;  // [slots]
+  const BigramStableJob* jobs; // [workgroups]
+  uint32_t* commit;            // [slots] the previous commit entry (a book index), carried from call to call
+  StableResult* out_res;       // [workgroups]
+  uint32_t* out_word; float* out_score; uint32_t* out_time;  // the block's item areas
+};
+hipError_t launch_bigram_stream_commit(const BigramStableArgs& a, uint32_t n_jobs, hipStream_t stream);
 
 // ---- forward-backward over the bigram search network (viterbi_bigram_fb.hip) -------------------------------------------------------
 // A launch group = utterances of one score chunk whose trellises fit the workspace together, walked frame by frame: `order` lists them

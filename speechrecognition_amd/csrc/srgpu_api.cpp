@@ -4821,6 +4821,7 @@ int sr_stream_open(sr_model* m, sr_lexicon* l, const sr_search_params* p, uint32
   sr_stream* s = new sr_stream();
   std::unique_ptr<sr_stream, int (*)(sr_stream*)> own(s, sr_stream_destroy);
   s->model = m; s->lex = l; s->params = *p; s->slots = StreamSlots(max_streams, max_frames);
+  s->commit_fresh.assign(max_streams, 1);
   const size_t S = max_streams;
   HIP_TRY(s->ws.ensure(S * decode_big_workspace(l->net.n_slots)));
   HIP_TRY(s->state.ensure(S));
@@ -4836,7 +4837,9 @@ int sr_stream_open(sr_model* m, sr_lexicon* l, const sr_search_params* p, uint32
 int sr_stream_begin(sr_stream* s, uint32_t* id) {
   return guarded(__func__, [&]() -> int {
   if (!s || !id) return fail(SR_EINVAL, "null argument");
-  return s->slots.begin(id);  // (the first push starts from the initial state: decode_stream_kernel)
+  const int rc = s->slots.begin(id);  // (the first push starts from the initial state: decode_stream_kernel)
+  if (rc == SR_OK) s->commit_fresh[*id % s->slots.max_streams] = 1;  // ... and the first sr_stream_stable from commit point 0
+  return rc;
   });
 }
 
@@ -4912,6 +4915,109 @@ int sr_stream_end(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_t cap, 
   });
 }
 
+// The stable prefix of n open utterances: one launch of stream_commit_kernel, which writes straight into the call's pinned block.
+// Block: StableJob[n] (in), StableResult[n], then the words, utterance i's at jobs[i].word_off (t_i slots: at most a word per frame).
+int sr_stream_stable(sr_stream* s, uint32_t n, const uint32_t* ids, uint32_t* out_words, uint64_t cap, uint64_t* out_word_off,
+                     uint32_t* out_commit, uint32_t* out_silence) {
+  return guarded(__func__, [&]() -> int {
+  if (!s) return fail(SR_EINVAL, "null stream set");
+  if (!out_word_off || (n && (!ids || !out_commit)) || (!out_words && cap)) return fail(SR_EINVAL, "null argument");
+  sr_model* m = s->model;
+  int rc = check_model(m);
+  if (rc) return rc;
+  const StreamSlots& sl = s->slots;
+  std::vector<uint8_t> seen(sl.max_streams, 0);
+  std::vector<StableJob> jobs(n);
+  uint64_t W = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const int64_t slot = sl.find(ids[i]);
+    if (slot < 0) return fail(SR_EINVAL, "entry %u: stream id %u is not open", i, ids[i]);
+    if (seen[slot]) return fail(SR_EINVAL, "entry %u: stream id %u appears twice in one call", i, ids[i]);
+    seen[slot] = 1;
+    jobs[i] = StableJob{(uint32_t)slot, (uint32_t)sl.frames[slot], s->commit_fresh[slot], 0u, W};
+    W += sl.frames[slot];
+  }
+  if (n == 0) { out_word_off[0] = 0; return SR_OK; }
+  const sr_lexicon* l = s->lex;
+  HIP_TRY(s->commit.ensure(sl.max_streams));
+  HIP_TRY(s->stable_words.ensure((size_t)sl.max_streams * sl.max_frames));
+  const size_t res_at = sizeof(StableJob) * n, words_at = res_at + sizeof(StableResult) * n;
+  if (words_at + sizeof(uint32_t) * W > s->stable_block.n)  // (grown geometrically: pinning costs milliseconds, the need grows with every push)
+    HIP_TRY(s->stable_block.ensure(std::max<size_t>(words_at + sizeof(uint32_t) * W, 2 * s->stable_block.n)));
+  unsigned char* blk = s->stable_block.p;
+  memcpy(blk, jobs.data(), sizeof(StableJob) * n);
+  StableArgs a{};
+  a.net = l->net;
+  a.jobs = reinterpret_cast<const StableJob*>(blk);
+  a.ws = s->ws.p; a.ws_stride = decode_big_workspace(l->net.n_slots);
+  a.tb_word = s->tb_word.p; a.tb_bkp = s->tb_bkp.p; a.tb_stride = sl.max_frames + 1;
+  a.commit = s->commit.p; a.words = s->stable_words.p; a.words_stride = sl.max_frames;
+  a.out_res = reinterpret_cast<StableResult*>(blk + res_at); a.out_words = reinterpret_cast<uint32_t*>(blk + words_at);
+  HIP_TRY(launch_stream_commit(a, n, m->s_gmm));
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  const StableResult* res = a.out_res;
+  uint32_t bad = 0xFFFFFFFFu;
+  for (uint32_t i = 0; i < n; i++) {
+    if (res[i].flags || res[i].count > jobs[i].t || res[i].commit > jobs[i].t) { if (bad == 0xFFFFFFFFu) bad = i; }
+    else s->commit_fresh[jobs[i].slot] = 0;  // the kernel left its commit point in commit[slot]
+  }
+  if (bad != 0xFFFFFFFFu)
+    return fail(SR_ECORRUPT, "stream %u: the traceback does not walk back from the commit point to frame 0 (Recognizer.cpp:222-231)", ids[bad]);
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n; i++) { out_word_off[i] = total; total += res[i].count; }
+  out_word_off[n] = total;
+  if (total > cap) return fail(SR_EINVAL, "%llu stable words, out_words holds %llu", (unsigned long long)total, (unsigned long long)cap);
+  for (uint32_t i = 0; i < n; i++) {
+    if (res[i].count) memcpy(out_words + out_word_off[i], a.out_words + jobs[i].word_off, sizeof(uint32_t) * res[i].count);
+    out_commit[i] = res[i].commit;
+    if (out_silence) out_silence[i] = res[i].silence;
+  }
+  return SR_OK;
+  });
+}
+
+// test hook: the nearest-common-ancestor fold of commit_point.h alone, on forests the caller supplies
+int sr_commit_points(sr_model* m, uint32_t n_sets, const uint64_t* node_off, const uint32_t* parent, const uint64_t* set_off,
+                     const uint32_t* set, const uint32_t* floor, uint32_t* out) {
+  return guarded(__func__, [&]() -> int {
+  int rc = check_model(m);
+  if (rc) return rc;
+  if (n_sets == 0) return SR_OK;
+  if (!node_off || !parent || !set_off || !set || !floor || !out) return fail(SR_EINVAL, "null argument");
+  if (node_off[0] != 0 || set_off[0] != 0) return fail(SR_EINVAL, "node_off[0] and set_off[0] must be 0");
+  for (uint32_t i = 0; i < n_sets; i++) {
+    if (node_off[i + 1] <= node_off[i]) return fail(SR_EINVAL, "set %u: a tree has at least its root", i);
+    if (set_off[i + 1] <= set_off[i]) return fail(SR_EINVAL, "set %u is empty", i);
+    const uint64_t nn = node_off[i + 1] - node_off[i];
+    if (nn >= 0xFFFFFFFEull) return fail(SR_ELIMIT, "set %u: %llu nodes, node indices are 32 bit", i, (unsigned long long)nn);
+    const uint32_t* par = parent + node_off[i];
+    if (par[0] != 0) return fail(SR_EINVAL, "set %u: parent[0] must be 0", i);
+    for (uint64_t j = 1; j < nn; j++)
+      if (par[j] >= j) return fail(SR_EINVAL, "set %u: parent[%llu] = %u is not below its child", i, (unsigned long long)j, par[j]);
+    for (uint64_t j = set_off[i]; j < set_off[i + 1]; j++)
+      if (set[j] >= nn) return fail(SR_EINVAL, "set %u: node %u out of range (%llu nodes)", i, set[j], (unsigned long long)nn);
+    if (floor[i] >= nn) return fail(SR_EINVAL, "set %u: floor %u out of range (%llu nodes)", i, floor[i], (unsigned long long)nn);
+  }
+  DevBuf<uint64_t> d_node_off, d_set_off;
+  DevBuf<uint32_t> d_parent, d_set, d_floor, d_out;
+  HIP_TRY(d_node_off.upload(node_off, (size_t)n_sets + 1));
+  HIP_TRY(d_set_off.upload(set_off, (size_t)n_sets + 1));
+  HIP_TRY(d_parent.upload(parent, node_off[n_sets]));
+  HIP_TRY(d_set.upload(set, set_off[n_sets]));
+  HIP_TRY(d_floor.upload(floor, n_sets));
+  HIP_TRY(d_out.ensure(n_sets));
+  CommitPointsArgs a{d_node_off.p, d_parent.p, d_set_off.p, d_set.p, d_floor.p, d_out.p};
+  HIP_TRY(launch_commit_points(a, n_sets, m->s_gmm));
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  std::vector<uint32_t> got(n_sets);
+  HIP_TRY(hipMemcpy(got.data(), d_out.p, sizeof(uint32_t) * n_sets, hipMemcpyDeviceToHost));
+  for (uint32_t i = 0; i < n_sets; i++)
+    if (got[i] >= node_off[i + 1] - node_off[i]) return fail(SR_ECORRUPT, "set %u: the fold left the tree", i);
+  memcpy(out, got.data(), sizeof(uint32_t) * n_sets);
+  return SR_OK;
+  });
+}
+
 int sr_stream_destroy(sr_stream* s) {
   return guarded(__func__, [&]() -> int {
   if (!s) return SR_OK;
@@ -4943,6 +5049,7 @@ int sr_bigram_stream_open(sr_model* m, sr_bigram* b, const sr_bigram_params* p, 
   std::unique_ptr<sr_bigram_stream, int (*)(sr_bigram_stream*)> own(s, sr_bigram_stream_destroy);
   s->model = m; s->bigram = b; s->params = *p; s->slots = StreamSlots(max_streams, max_frames);
   s->host_state.assign(max_streams, BigramStreamState{}); s->failed.assign(max_streams, 0);
+  s->commit_fresh.assign(max_streams, 1);
   const size_t S = max_streams, W = b->net.n_words;
   HIP_TRY(s->gs_ws.ensure(S * bigram_gs_ws_words(b->net.n_words, b->net.n_positions)));
   HIP_TRY(s->we_slot.ensure(S * 4 * W));
@@ -4968,6 +5075,7 @@ int sr_bigram_stream_begin(sr_bigram_stream* s, uint32_t* id) {
   s->host_state[slot] = BigramStreamState{};
   s->host_state[slot].n_book = 2;  // the two start entries the first push writes
   s->failed[slot] = 0;
+  s->commit_fresh[slot] = 1;  // the first sr_bigram_stream_stable starts from the start entry
   return SR_OK;
   });
 }
@@ -5064,6 +5172,74 @@ int sr_bigram_stream_end(sr_bigram_stream* s, uint32_t id, uint32_t* out_word, f
   if (rc == SR_EINVAL) return rc;  // too small a buffer: the utterance stays open
   s->slots.open[slot] = 0;
   return rc;
+  });
+}
+
+// The stable prefix of n open utterances: one launch of bigram_stream_commit_kernel, which writes straight into the call's pinned
+// block.  Block: BigramStableJob[n] (in), StableResult[n], then three item areas (word, score, time) of sum t_i slots each,
+// utterance i's items at jobs[i].item_off.
+int sr_bigram_stream_stable(sr_bigram_stream* s, uint32_t n, const uint32_t* ids, uint32_t* out_word, float* out_score,
+                            uint32_t* out_time, uint64_t cap, uint64_t* out_off, uint32_t* out_commit) {
+  return guarded(__func__, [&]() -> int {
+  if (!s) return fail(SR_EINVAL, "null stream set");
+  if (!out_off || (n && (!ids || !out_commit)) || ((!out_word || !out_score || !out_time) && cap)) return fail(SR_EINVAL, "null argument");
+  sr_model* m = s->model;
+  int rc = check_model(m);
+  if (rc) return rc;
+  const StreamSlots& sl = s->slots;
+  std::vector<uint8_t> seen(sl.max_streams, 0);
+  std::vector<BigramStableJob> jobs(n);
+  uint64_t N = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const int64_t slot = sl.find(ids[i]);
+    if (slot < 0) return fail(SR_EINVAL, "entry %u: stream id %u is not open", i, ids[i]);
+    if (seen[slot]) return fail(SR_EINVAL, "entry %u: stream id %u appears twice in one call", i, ids[i]);
+    seen[slot] = 1;
+    if (s->failed[slot]) return fail(SR_EINTERNAL, "stream %u: a push overflowed its book", ids[i]);
+    jobs[i] = BigramStableJob{(uint32_t)slot, (uint32_t)sl.frames[slot], s->commit_fresh[slot], 0u,
+                              sl.frames[slot] ? s->book[slot]->p : nullptr, N};
+    N += sl.frames[slot];
+  }
+  if (n == 0) { out_off[0] = 0; return SR_OK; }
+  const sr_bigram* b = s->bigram;
+  HIP_TRY(s->commit.ensure(sl.max_streams));
+  const size_t res_at = sizeof(BigramStableJob) * n, items_at = res_at + sizeof(StableResult) * n;
+  if (items_at + 12 * N > s->stable_block.n)  // (grown geometrically: pinning costs milliseconds, the need grows with every push)
+    HIP_TRY(s->stable_block.ensure(std::max<size_t>(items_at + 12 * N, 2 * s->stable_block.n)));
+  unsigned char* blk = s->stable_block.p;
+  memcpy(blk, jobs.data(), sizeof(BigramStableJob) * n);
+  BigramStableArgs a{};
+  a.n_words = b->net.n_words; a.silence = b->net.silence; a.n_positions = b->net.n_positions; a.slot_off = b->net.slot_off;
+  a.gs_ws = s->gs_ws.p; a.gs_ws_words = bigram_gs_ws_words(b->net.n_words, b->net.n_positions);
+  a.we_bp = s->we_bp.p; a.lsave = s->lsave.p; a.state = s->state.p;
+  a.jobs = reinterpret_cast<const BigramStableJob*>(blk);
+  a.commit = s->commit.p;
+  a.out_res = reinterpret_cast<StableResult*>(blk + res_at);
+  a.out_word = reinterpret_cast<uint32_t*>(blk + items_at);
+  a.out_score = reinterpret_cast<float*>(blk + items_at + 4 * N);
+  a.out_time = reinterpret_cast<uint32_t*>(blk + items_at + 8 * N);
+  HIP_TRY(launch_bigram_stream_commit(a, n, m->s_gmm));
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  const StableResult* res = a.out_res;
+  uint32_t bad = 0xFFFFFFFFu;
+  for (uint32_t i = 0; i < n; i++) {
+    if (res[i].flags || res[i].count > jobs[i].t || res[i].commit > jobs[i].t) { if (bad == 0xFFFFFFFFu) bad = i; }
+    else s->commit_fresh[jobs[i].slot] = 0;  // the kernel left its commit entry in commit[slot]
+  }
+  if (bad != 0xFFFFFFFFu) return fail(SR_ECORRUPT, "stream %u: the book walk from the commit entry does not end at its start entry", ids[bad]);
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n; i++) { out_off[i] = total; total += res[i].count; }
+  out_off[n] = total;
+  if (total > cap) return fail(SR_EINVAL, "%llu stable items, the output arrays hold %llu", (unsigned long long)total, (unsigned long long)cap);
+  for (uint32_t i = 0; i < n; i++) {
+    if (res[i].count) {
+      memcpy(out_word + out_off[i], a.out_word + jobs[i].item_off, sizeof(uint32_t) * res[i].count);
+      memcpy(out_score + out_off[i], a.out_score + jobs[i].item_off, sizeof(float) * res[i].count);
+      memcpy(out_time + out_off[i], a.out_time + jobs[i].item_off, sizeof(uint32_t) * res[i].count);
+    }
+    out_commit[i] = res[i].commit;
+  }
+  return SR_OK;
   });
 }
 

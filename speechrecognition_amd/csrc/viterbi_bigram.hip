@@ -32,6 +32,7 @@
 #include <limits>
 #include <type_traits>
 
+#include "commit_point.h"
 #include "kernels.h"
 
 namespace srgpu {
@@ -985,6 +986,84 @@ template <int KW, int GSM>
 __global__ __launch_bounds__(kBgThreads) void bigram_stream_kernel(BigramStreamArgs s) {
   const BigramStreamJob job = s.jobs[blockIdx.x];
   bigram_utterance<KW, 4, 0, 0, GSM, true>(s.a, 0, job.slot, &s, &job);
+}
+
+// ---- the stable prefix of an open utterance (sr_bigram_stream_stable) ----------------------------------------------------
+// One workgroup per requested stream, launched on demand; nothing of the search's state is written.  What the STREAM arm of
+// bigram_utterance resumes from names the book entries a later word end can start from: the back pointers of the finite positions
+// of the image's current buffer on the slots of the saved active list (a slot off the list is +inf in both buffers), and the merged
+// word-end list we_bp[0][0 .. n_we), from which step 1 of the next frame builds every entry hypothesis.  (The entries beside the
+// image of a GSM = 2 lexicon are rebuilt from that list at the top of every frame: they hold nothing a later frame reads.)  A new
+// entry's parent is such a back pointer b -- or, where b is a silence entry and the new word end is silence's, book[b].z (step 6,
+// "avoid chains of silence"): a silence entry is therefore folded in as its parent, which both chains run through.  The nearest
+// common ancestor under parent(b) = book[b].z (commit_point.h) is the commit entry; thread 0 walks from it to the start entry with
+// the partial walk's guards and writes the items in time order.
+__global__ __launch_bounds__(256) void bigram_stream_commit_kernel(BigramStableArgs a) {
+  constexpr int NT = 256;
+  __shared__ uint32_t red[NT / 64];
+  const BigramStableJob job = a.jobs[blockIdx.x];
+  const uint32_t tid = threadIdx.x, W2 = 2 * a.n_words, P2 = a.n_positions, sil = a.silence;
+  const uint4* book = job.book;
+  const uint32_t floor = job.fresh ? 1u : a.commit[job.slot];  // book[1]: the start entry
+  uint32_t n_book = 0;
+  auto parent = [&](uint32_t b) -> uint32_t { return book[b].z; };
+  auto candidate = [&](uint32_t b) -> uint32_t {
+    if (b == 0 || b >= n_book) return kCommitCorrupt;
+    const uint4 e = book[b];
+    if (e.x != sil || e.w == 0) return b;  // (the start entry is silence's and its own parent)
+    return (e.z > 0 && e.z < b) ? e.z : kCommitCorrupt;
+  };
+  uint32_t mine = kCommitNone;
+  if (job.t == 0) {  // nothing searched yet (no state, no book): the start entry
+    if (tid == 0) mine = 1;
+  } else {
+    const BigramStreamState st = a.state[job.slot];
+    n_book = st.n_book;
+    const uint32_t* gs = a.gs_ws + (uint64_t)job.slot * a.gs_ws_words;
+    const float* sc = reinterpret_cast<const float*>(gs) + (uint64_t)(st.gs_cur & 1u) * P2;
+    const uint32_t* bp = gs + (2ull + (st.gs_cur & 1u)) * P2;
+    const uint16_t* ls = a.lsave + (uint64_t)job.slot * W2;
+    const uint32_t n_L = st.n_L < W2 ? st.n_L : W2, n_we = st.n_we < W2 ? st.n_we : W2;
+    for (uint32_t i = tid; i < n_L; i += NT) {
+      const uint32_t sl = ls[i];
+      if (sl >= W2) { mine = kCommitCorrupt; continue; }
+      for (uint32_t q = a.slot_off[sl]; q < a.slot_off[sl + 1]; q++)
+        if (sc[q] < __builtin_inff()) mine = commit_lca(mine, candidate(bp[q]), floor, parent);
+    }
+    const uint32_t* web = a.we_bp + (uint64_t)job.slot * 2 * W2;
+    for (uint32_t e = tid; e < n_we; e += NT) mine = commit_lca(mine, candidate(web[e]), floor, parent);
+  }
+  const uint32_t all = commit_fold<NT>(mine, floor, red, parent);
+  if (tid == 0) {
+    StableResult r{0u, 0u, 0u, 0u};
+    const uint32_t c = all == kCommitNone ? floor : all;  // no hypothesis alive: the commit entry stays where it was
+    if (job.t == 0) {
+      a.commit[job.slot] = 1u;
+    } else if (c == kCommitCorrupt || c == 0 || c >= n_book) {
+      r.flags = kStableCorrupt;
+    } else {
+      uint32_t len = 0, b = c;  // (an item steps back a frame at least: at most t of them)
+      while (b > 0 && b < n_book && book[b].w > 0 && len <= job.t) { const uint32_t z = book[b].z; len++; b = z < b ? z : 0u; }
+      if (b == 0 || b >= n_book || len > job.t) {
+        r.flags = kStableCorrupt;
+      } else {
+        r.commit = book[c].w; r.count = len;
+        for (b = c; book[b].w > 0; b = book[b].z) {
+          len--;
+          const uint4 e = book[b];
+          a.out_word[job.item_off + len] = e.x; a.out_score[job.item_off + len] = __uint_as_float(e.y); a.out_time[job.item_off + len] = e.w;
+        }
+        a.commit[job.slot] = c;
+      }
+    }
+    a.out_res[blockIdx.x] = r;
+  }
+}
+
+hipError_t launch_bigram_stream_commit(const BigramStableArgs& a, uint32_t n_jobs, hipStream_t stream) {
+  if (n_jobs == 0) return hipSuccess;
+  hipLaunchKernelGGL(bigram_stream_commit_kernel, dim3(n_jobs), dim3(256), 0, stream, a);
+  return hipGetLastError();
 }
 
 uint32_t bigram_max_words() { return kBgMaxWords; }

@@ -31,6 +31,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "commit_point.h"
 #include "kernels.h"
 #include "traceback.h"
 
@@ -549,6 +550,106 @@ hipError_t launch_decode_stream(const StreamArgs& a, uint32_t n_jobs, hipStream_
   if (n_jobs == 0) return hipSuccess;
   if (a.net.n_slots > decode_big_max_slots()) return hipErrorInvalidValue;
   hipLaunchKernelGGL((decode_stream_kernel<1024>), dim3(n_jobs), dim3(1024), 0, stream, a);
+  return hipGetLastError();
+}
+
+// ---- the stable prefix of an open utterance (sr_stream_stable) ---------------------------------------------------------------
+// One workgroup per requested stream, launched on demand; the search's state is read, never written.  After t frames the current
+// buffer is the frame parity t & 1 (big_frame wrote frame t's pruned hypotheses there): B = { bk[p] : sc[p] finite } are the
+// traceback nodes a later traceback can still run through, and their nearest common ancestor under parent(c) = tb_bkp[c] is the
+// commit point (commit_point.h).  The same pass keeps the alive hypothesis of least score (ties: the
+// smaller slot) for the trailing silence.  Thread 0 then walks from the commit point with traceback.h's guards into the slot's
+// own word buffer, and the workgroup copies the words into the call's result block.
+template <int NT>
+__global__ __launch_bounds__(NT) void stream_commit_kernel(StableArgs a) {
+  constexpr uint32_t kWavesPerWg = NT / 64;
+  __shared__ double red_sc[kWavesPerWg];
+  __shared__ uint32_t red[kWavesPerWg], red_idx[kWavesPerWg], n_out;
+  const StableJob job = a.jobs[blockIdx.x];
+  const uint32_t P = a.net.n_slots;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t t = job.t;
+  const unsigned char* ws = a.ws + (size_t)job.slot * a.ws_stride;
+  const double* sc = reinterpret_cast<const double*>(ws) + (size_t)(t & 1) * P;
+  const uint16_t* bk = reinterpret_cast<const uint16_t*>(ws + (size_t)P * 16) + (size_t)(t & 1) * P;
+  const uint64_t tb0 = (uint64_t)job.slot * a.tb_stride;
+  const uint32_t floor = job.fresh ? 0u : a.commit[job.slot];
+  auto parent = [&](uint32_t c) -> uint32_t { return a.tb_bkp[tb0 + c]; };
+
+  uint32_t mine = kCommitNone, my_p = 0xFFFFFFFFu;
+  double my_v = kInf;
+  if (t == 0) {  // nothing searched yet (the buffers are not initialised): B = {0}
+    if (tid == 0) mine = 0;
+  } else {
+    for (uint32_t p = tid; p < P; p += NT) {
+      const double v = sc[p];
+      if (!(v < kInf)) continue;  // pruned or never reached
+      const uint32_t b = bk[p];
+      mine = commit_lca(mine, b < t ? b : kCommitCorrupt, floor, parent);
+      if (v < my_v) { my_v = v; my_p = p; }
+    }
+  }
+  const uint32_t all = commit_fold<NT>(mine, floor, red, parent);
+  wave_min_idx(my_v, my_p);
+  if ((tid & 63) == 0) { red_sc[tid >> 6] = my_v; red_idx[tid >> 6] = my_p; }
+  __syncthreads();
+  uint32_t* words = a.words + (uint64_t)job.slot * a.words_stride;
+  if (tid == 0) {
+    double best = red_sc[0];
+    uint32_t best_p = red_idx[0];
+    for (uint32_t w = 1; w < kWavesPerWg; w++)
+      if (red_sc[w] < best || (red_sc[w] == best && red_idx[w] < best_p)) { best = red_sc[w]; best_p = red_idx[w]; }
+    StableResult r{floor, 0u, 0u, 0u};
+    const uint32_t c = all == kCommitNone ? floor : all;  // no hypothesis alive: the commit point stays where it was
+    if (c == kCommitCorrupt || c > t) r.flags = kStableCorrupt;
+    else {
+      const uint32_t n = walk_traceback(
+          c, a.net.silence_word, a.net.n_words, [&](uint32_t f) -> uint32_t { return a.tb_word[tb0 + f]; },
+          [&](uint32_t f) -> uint32_t { return a.tb_bkp[tb0 + f]; }, words, c);
+      if (n == kTbCorrupt) r.flags = kStableCorrupt;
+      else { r.commit = c; r.count = n; }
+    }
+    if (best_p < P && (a.net.slot_info[best_p] & kSlotSilWord)) {
+      const uint32_t b = bk[best_p];
+      r.silence = b < t ? t - b : 0u;
+    }
+    if (!r.flags) a.commit[job.slot] = r.commit;
+    a.out_res[blockIdx.x] = r;
+    n_out = r.count;
+  }
+  __syncthreads();  // workgroup-scope release/acquire: thread 0's words are visible to the copy
+  const uint32_t n = n_out;
+  for (uint32_t i = tid; i < n; i += NT) a.out_words[job.word_off + i] = words[i];
+}
+
+hipError_t launch_stream_commit(const StableArgs& a, uint32_t n_jobs, hipStream_t stream) {
+  if (n_jobs == 0) return hipSuccess;
+  if (a.net.n_slots > decode_big_max_slots()) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((stream_commit_kernel<256>), dim3(n_jobs), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
+// the fold alone (sr_commit_points): one workgroup per set of nodes of a forest the caller supplies
+template <int NT>
+__global__ __launch_bounds__(NT) void commit_points_kernel(CommitPointsArgs a) {
+  __shared__ uint32_t red[NT / 64];
+  const uint64_t n0 = a.node_off[blockIdx.x], s0 = a.set_off[blockIdx.x];
+  const uint64_t n_nodes = a.node_off[blockIdx.x + 1] - n0, n_set = a.set_off[blockIdx.x + 1] - s0;
+  const uint32_t* par = a.parent + n0;
+  const uint32_t floor = a.floor[blockIdx.x];
+  auto parent = [&](uint32_t c) -> uint32_t { return par[c]; };  // c is a candidate or above one: below n_nodes
+  uint32_t mine = kCommitNone;
+  for (uint64_t j = threadIdx.x; j < n_set; j += NT) {
+    const uint32_t x = a.set[s0 + j];
+    mine = commit_lca(mine, x < n_nodes ? x : kCommitCorrupt, floor, parent);
+  }
+  const uint32_t all = commit_fold<NT>(mine, floor, red, parent);
+  if (threadIdx.x == 0) a.out[blockIdx.x] = all;
+}
+
+hipError_t launch_commit_points(const CommitPointsArgs& a, uint32_t n_sets, hipStream_t stream) {
+  if (n_sets == 0) return hipSuccess;
+  hipLaunchKernelGGL((commit_points_kernel<256>), dim3(n_sets), dim3(256), 0, stream, a);
   return hipGetLastError();
 }
 

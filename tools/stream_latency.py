@@ -10,7 +10,11 @@ same utterances (features resident).  The streamed words are checked against the
 
 --decoder bigram: the bigram-LM stream (sr_bigram_stream_*) on BASELINE configs[4]'s shape instead -- 8000 states x 64 densities,
 2666 words, bench.py's seeded bigram table and transition scores, acoustic beam 200, no LM beam -- against one
-sr_recognize_bigram_corpus; the streamed items (words, score bits, times) are checked against the batch's."""
+sr_recognize_bigram_corpus; the streamed items (words, score bits, times) are checked against the batch's.
+
+--stable: after every push also asks for the stable prefix of the pushed streams (sr_stream_stable / sr_bigram_stream_stable, one
+call for all of them) and prints the median and p99 wall time of that call beside the push's; every answer is checked to be a
+prefix of its utterance's final result (where that is not empty)."""
 from __future__ import annotations
 
 import argparse
@@ -32,6 +36,7 @@ def main():
     ap.add_argument("--utts", type=int, default=1000, help="utterances of bench.py's corpus to stream")
     ap.add_argument("--kernel", choices=["default", "prefilter", "exact", "mfma"], default="default")
     ap.add_argument("--decoder", choices=["zerogram", "bigram"], default="zerogram")
+    ap.add_argument("--stable", action="store_true", help="after every push, time the stable-prefix call on the pushed streams")
     args = ap.parse_args()
     if args.decoder == "bigram":
         return main_bigram(args)
@@ -70,7 +75,7 @@ def main():
             todo = list(range(n))
             open_ = {}  # id -> (utterance, frames pushed)
             got = {}
-            push_ms = []
+            push_ms, stable_ms, last_stable, stable_ok = [], [], {}, True
             t_all = time.perf_counter()
             while todo or open_:
                 while todo and len(open_) < args.streams:
@@ -82,11 +87,18 @@ def main():
                 t = time.perf_counter()
                 st.push(batch)
                 push_ms.append(1e3 * (time.perf_counter() - t))
+                if args.stable:
+                    t = time.perf_counter()
+                    sw, _, _ = st.stable(list(batch))
+                    stable_ms.append(1e3 * (time.perf_counter() - t))
+                    last_stable.update(zip(batch, sw))
                 for sid in list(open_):
                     u, t0 = open_[sid]
                     t0 += len(batch[sid])
                     if t0 == len(utts[u]):
                         got[u] = st.end(sid)
+                        if args.stable and len(got[u]):
+                            stable_ok &= np.array_equal(last_stable[sid], got[u][: len(last_stable[sid])])
                         del open_[sid]
                     else:
                         open_[sid] = (u, t0)
@@ -108,6 +120,12 @@ def main():
     print(f"corpus: streamed in {stream_s:.3f} s (of which {pm.sum() / 1e3:.3f} s in sr_stream_push) vs one "
           f"sr_recognize_corpus {batch_s:.3f} s ({stream_s / batch_s:.1f}x)")
     print(f"streamed words equal the batch's: {'yes' if same else 'NO'}")
+    if args.stable:
+        sm = np.asarray(stable_ms)
+        print(f"sr_stream_stable on the pushed streams, after every push: median {np.median(sm):.3f} ms, p99 {np.percentile(sm, 99):.3f} ms, "
+              f"min {sm.min():.3f} ms, max {sm.max():.3f} ms ({np.median(sm) / np.median(pm):.1%} of a push at the median)")
+        print(f"stable words were a prefix of the final words: {'yes' if stable_ok else 'NO'}")
+        same = same and stable_ok
     return 0 if same else 1
 
 
@@ -153,7 +171,7 @@ def main_bigram(args):
             todo = list(range(n))
             open_ = {}
             got = {}
-            push_ms = []
+            push_ms, stable_ms, last_stable, stable_ok = [], [], {}, True
             t_all = time.perf_counter()
             while todo or open_:
                 while todo and len(open_) < args.streams:
@@ -163,11 +181,19 @@ def main_bigram(args):
                 t = time.perf_counter()
                 st.push(batch)
                 push_ms.append(1e3 * (time.perf_counter() - t))
+                if args.stable:
+                    t = time.perf_counter()
+                    si, _ = st.stable(list(batch))
+                    stable_ms.append(1e3 * (time.perf_counter() - t))
+                    last_stable.update(zip(batch, si))
                 for sid in list(open_):
                     u, t0 = open_[sid]
                     t0 += len(batch[sid])
                     if t0 == len(utts[u]):
                         got[u] = st.end(sid)
+                        if args.stable and len(got[u][0]):
+                            k = len(last_stable[sid][0])
+                            stable_ok &= all(np.array_equal(a.view(np.uint32), b[:k].view(np.uint32)) for a, b in zip(last_stable[sid], got[u]))
                         del open_[sid]
                     else:
                         open_[sid] = (u, t0)
@@ -195,6 +221,12 @@ def main_bigram(args):
     print(f"corpus: streamed in {stream_s:.3f} s (of which {pm.sum() / 1e3:.3f} s in sr_bigram_stream_push) vs one "
           f"sr_recognize_bigram_corpus {batch_s:.3f} s ({stream_s / batch_s:.1f}x)")
     print(f"streamed items equal the batch's (words, times, score bits): {'yes' if ok else 'NO'}")
+    if args.stable:
+        sm = np.asarray(stable_ms)
+        print(f"sr_bigram_stream_stable on the pushed streams, after every push: median {np.median(sm):.3f} ms, p99 {np.percentile(sm, 99):.3f} ms, "
+              f"min {sm.min():.3f} ms, max {sm.max():.3f} ms ({np.median(sm) / np.median(pm):.1%} of a push at the median)")
+        print(f"stable items were a prefix of the final items: {'yes' if stable_ok else 'NO'}")
+        ok = ok and stable_ok
     return 0 if ok else 1
 
 
