@@ -215,3 +215,24 @@ void update_weights(uint32_t n_states, const uint32_t* dens_off, uint64_t n_entr
                     double* logw);
 
 }  // namespace map_host
+
+// The transcripts' chains of the MMI passes (chains.cpp, compiled within srgpu_api.cpp's unit; ChainArgs and BgChainArgs of kernels.h)
+namespace chain_host {
+
+struct Chains {
+  std::vector<uint64_t> off;            // [U + 1] an utterance's chain positions
+  std::vector<uint32_t> info, src, dst; // per chain position
+  std::vector<double> lmc;              // per chain position, the bigram network's chains alone
+  uint32_t sil_len = 0;                 // positions of the silence word
+};
+// The recognition network: segment g of utterance u is the silence word 0 (g even) or w_{(g+1)/2} (g odd), each with the slot_info of
+// its lexicon word (word w: slots word_off[w] .. word_off[w + 1]).  trans: words other than 0, utterance u's at trans_off[u] ..
+void build_chains(const uint32_t* word_off, const uint32_t* slot_info, uint32_t U, const uint32_t* trans, const uint64_t* trans_off,
+                  Chains* ch);
+// The bigram search network: segment 0 is the silence word S = slot `sil`, segment 2 i - 1 the word w_i (slot w_i) and segment 2 i its
+// silence copy c_i (slot w_i + W), each with the pos_info of its slot; lmc = scale * lmT[history * W + word] at a word's entry (+inf
+// where the entry is +inf or NaN), 0 elsewhere
+void build_bgchains(const uint32_t* slot_off, const uint32_t* pos_info, uint32_t W, uint32_t sil, const float* lmT, double scale, uint32_t U,
+                    const uint32_t* trans, const uint64_t* trans_off, Chains* ch);
+
+}  // namespace chain_host

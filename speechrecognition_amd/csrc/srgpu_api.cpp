@@ -4,8 +4,11 @@
 // Nothing here computes scores or paths on the host: every sr_score_* / sr_recognize_* / sr_align_*
 // call runs the HIP kernels of gmm_mfma.hip / gmm_exact.hip / viterbi_decode.hip / viterbi_align.hip
 // and fails loudly (SR_EHIP / SR_ENODEV) when no gfx950 device is usable.  There is no CPU fallback.
-// The forward-backward style passes (fb_check .. sr_bigram_lattice_nbest) plan their launch groups, step order and mixture lists
-// with fb_plan.h, host code that is tested on its own.
+// The forward-backward style passes (fb_check .. sr_bigram_word_lattice_corpus) plan their launch groups, step order and mixture lists
+// with fb_plan.h, host code that is tested on its own.  Host algorithms on plain arrays, with no handle and no HIP call, are files of
+// their own that this unit includes, each complete by itself and built alone under the sanitizers by a test driver: chains.cpp (the
+// transcripts' chains of the MMI passes) and nbest.cpp (sr_lattice_nbest, sr_bigram_lattice_nbest).
+// Every entry point is declared extern "C" with SR_API in include/srgpu.h: the definitions here take linkage and visibility from there.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,8 +22,6 @@
 #include <memory>
 #include <mutex>
 #include <numeric>
-#include <queue>
-#include <set>
 #include <string>
 #include <vector>
 
@@ -780,8 +781,6 @@ int bigram_stream_items(sr_bigram_stream* s, uint32_t slot, uint32_t id, uint32_
 }
 }  // namespace
 
-extern "C" {
-
 const char* sr_last_error(void) { return g_err; }
 
 int sr_abi_version(void) { return SR_ABI_VERSION; }
@@ -796,8 +795,6 @@ int sr_device_count(int* count) {
   return SR_OK;
   });
 }
-
-}  // extern "C"
 
 namespace srhost {
 
@@ -926,8 +923,6 @@ int may_go_negative(sr_model* m, bool* out) {
 }
 
 }  // namespace srhost
-
-extern "C" {
 
 int sr_model_create(int device, uint32_t dim, uint32_t n_states, const uint32_t* dens_off, const double* means,
                     const double* inv_vars, const double* norm, const double* logw, int max_approx, sr_model** out) {
@@ -1347,7 +1342,6 @@ static int gather_words_host(sr_corpus* c, uint32_t* out_words, uint64_t* out_wo
   return SR_OK;
 }
 
-extern "C++" {  // (templates inside the entry points' extern "C" block)
 // The zerogram search of a corpus on `chunks` (prepare_chunks): the words and tracebacks stay in c->out_* / c->tb_*.
 // score(chunk, table) enqueues the chunk's scores on m->s_gmm (score_chunk, but for the test hook sr_recognize_corpus_scores);
 // exact_negative is DecodeArgs' (-1: asked of the model); after(chunk, table, stream) enqueues more work on a chunk's scores behind
@@ -1406,7 +1400,6 @@ static int recognize_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_sea
   return recognize_pass(m, c, l, p, chunks, -1,
                         [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); }, after);
 }
-}  // extern "C++"
 
 int sr_recognize_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, uint32_t* out_words,
                         uint64_t* out_word_off, double* tb_score, uint16_t* tb_word, uint16_t* tb_bkp) {
@@ -1593,7 +1586,6 @@ int sr_bigram_destroy(sr_bigram* b) {
 // The bigram search of a corpus (sr_recognize_bigram_corpus).  score(chunk, table) enqueues the chunk's scores on m->s_gmm (score_chunk,
 // but for the test hook sr_recognize_bigram_corpus_scores); before(chunks) runs once the chunks are known; after(chunk, table,
 // stream) is enqueued behind each chunk's search on the same score table (sr_recognize_bigram_confidence_corpus: the forward-backward).
-extern "C++" {
 template <class Score, class Before, class After>
 static int bigram_recognize_pass(sr_model* m, sr_corpus* c, sr_bigram* b, const sr_bigram_params* p, uint32_t* out_word, float* out_score,
                                  uint32_t* out_time, uint64_t* out_off, Score score, Before before, After after) {
@@ -1729,7 +1721,6 @@ static int bigram_recognize_pass(sr_model* m, sr_corpus* c, sr_bigram* b, const 
   return bigram_recognize_pass(m, c, b, p, out_word, out_score, out_time, out_off,
                                [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); }, before, after);
 }
-}  // extern "C++"
 
 int sr_recognize_bigram_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, const sr_bigram_params* p, uint32_t* out_word,
                                float* out_score, uint32_t* out_time, uint64_t* out_off) {
@@ -2142,7 +2133,6 @@ static int trellis_groups(sr_model* m, sr_corpus* c, const std::vector<Chunk>& c
 // an entry point's output arrays: is one of them missing
 static bool any_null(std::initializer_list<const void*> ps) { return std::find(ps.begin(), ps.end(), nullptr) != ps.end(); }
 
-extern "C++" {
 // The item path (launch_items, posterior_items.hip): a launch group of at most max_gf frames counts, scans and appends its items to
 // the corpus' c->fb_item_* (at most item_bound) behind the counter c->fb_base.
 static int ensure_items(sr_corpus* c, uint64_t max_gf, uint64_t F, uint64_t item_bound, size_t* scan_bytes) {
@@ -2187,9 +2177,8 @@ static void occ_item_fields(ItemArgs* a, sr_corpus* c, const srplan::MixLists<Po
   a->n_cols = a->row_stride = (uint32_t)P; a->n_mix = chain ? 0u : (uint32_t)ml.mix.size(); a->gate = gate;
   if (chain) { a->trellis_off = c->fb_trellis_off.p; a->chain_off = c->mmi_chain_off.p; a->mix_off = c->fb_mix_off.p; }
 }
-// the transcripts' chains (Chains, BgChains) on the device
-template <class Ch>
-static int upload_chains(sr_corpus* c, const Ch& ch) {
+// the transcripts' chains of either network (chains.cpp) on the device
+static int upload_chains(sr_corpus* c, const chain_host::Chains& ch) {
   HIP_TRY(c->mmi_chain_off.upload(ch.off.data(), ch.off.size()));
   HIP_TRY(c->mmi_info.upload(ch.info.data(), ch.info.size()));
   HIP_TRY(c->mmi_src.upload(ch.src.data(), ch.src.size()));
@@ -2240,7 +2229,6 @@ static int top_of_items(sr_model* m, sr_corpus* c, uint32_t max_items, uint16_t*
   HIP_TRY(hipStreamSynchronize(m->s_gmm));
   return copy_top_items(F, max_items, c->fb_count, c->fb_state, c->fb_weight, out_count, out_state, out_weight);
 }
-}  // extern "C++"
 
 // ---- forward-backward (viterbi_fb.hip) -----------------------------------------------------------------------------------
 // The argument checks both entry points share: the aligner's, with N_u <= 2 T_u - 1 (a path must exist) in place of N_u <= T_u.
@@ -2481,7 +2469,6 @@ static int adapt_pairs_bw(sr_model* m, sr_corpus* c, const uint16_t* automata, c
 
 // What the fMLLR and MLLR statistics end with: the segments of the groups (g->shape is the caller's) to the device, the partials'
 // workspace and the results sized, `launch` under the profile events, the results to the host
-extern "C++" {
 template <class Launch>
 static int grouped_statistics(sr_model* m, sr_corpus* c, const srplan::Segments& seg, uint32_t n_groups, GroupedStats* g, Launch launch,
                               double* out_beta, double* out_k, double* out_G) {
@@ -2505,7 +2492,6 @@ static int grouped_statistics(sr_model* m, sr_corpus* c, const srplan::Segments&
   HIP_TRY(hipMemcpy(out_G, c->fm_G.p, sizeof(double) * nG, hipMemcpyDeviceToHost));
   return SR_OK;
 }
-}  // extern "C++"
 
 // ---- fMLLR speaker adaptation (fmllr_stats.hip; the estimate itself is host code, fmllr.cpp) ---------------------------------------
 // The checks every statistics call makes before any launch
@@ -2730,6 +2716,24 @@ int sr_mllr_statistics_bw_corpus(sr_model* m, sr_corpus* c, const uint16_t* auto
   });
 }
 
+// What a speaker-adapted model (sr_model_transform_means, sr_model_map_adapt) takes over from its prior `m`: the topology, the tying
+// tables on device and host, and the inverse variances and norms, copied on the device.  means and logw are sized; the caller fills them.
+static int adapted_model_shell(sr_model* m, std::unique_ptr<sr_model, int (*)(sr_model*)>& own) {
+  const uint64_t C = m->n_dens, D = m->dim;
+  sr_model* o = nullptr;
+  int rc = srhost::model_shell(m->device, m->dim, m->n_states, m->h_dens_off.data(), m->max_approx ? 1 : 0, &o);
+  if (rc) return rc;
+  own.reset(o);
+  HIP_TRY(o->dens_mean.upload(m->h_dens_mean.data(), C)); HIP_TRY(o->dens_var.upload(m->h_dens_var.data(), C));
+  o->n_mean = m->n_mean; o->n_var = m->n_var; o->h_dens_mean = m->h_dens_mean; o->h_dens_var = m->h_dens_var;
+  HIP_TRY(o->means.ensure(C * D)); HIP_TRY(o->inv_vars.ensure(C * D)); HIP_TRY(o->norm.ensure(C)); HIP_TRY(o->logw.ensure(C));
+  if (C) {
+    HIP_TRY(hipMemcpy(o->inv_vars.p, m->inv_vars.p, sizeof(double) * C * D, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(o->norm.p, m->norm.p, sizeof(double) * C, hipMemcpyDeviceToDevice));
+  }
+  return SR_OK;
+}
+
 int sr_model_transform_means(sr_model* m, const uint32_t* dens_class, uint32_t n_classes, const double* W, sr_model** out) {
   return guarded(__func__, [&]() -> int {
   if (!out) return fail(SR_EINVAL, "out is null");
@@ -2765,17 +2769,10 @@ int sr_model_transform_means(sr_model* m, const uint32_t* dens_class, uint32_t n
     for (uint32_t b = class_off[r]; b < class_off[r + 1]; b += per) {
       blk.push_back(r); blk.push_back(b); blk.push_back(std::min(class_off[r + 1], b + per));
     }
-  sr_model* o = nullptr;
-  if ((rc = srhost::model_shell(m->device, D, m->n_states, m->h_dens_off.data(), m->max_approx ? 1 : 0, &o))) return rc;
-  std::unique_ptr<sr_model, int (*)(sr_model*)> own(o, sr_model_destroy);
-  HIP_TRY(o->dens_mean.upload(m->h_dens_mean.data(), C)); HIP_TRY(o->dens_var.upload(m->h_dens_var.data(), C));
-  o->n_mean = m->n_mean; o->n_var = m->n_var; o->h_dens_mean = m->h_dens_mean; o->h_dens_var = m->h_dens_var;
-  HIP_TRY(o->means.ensure(C * D)); HIP_TRY(o->inv_vars.ensure(C * D)); HIP_TRY(o->norm.ensure(C)); HIP_TRY(o->logw.ensure(C));
-  if (C) {
-    HIP_TRY(hipMemcpy(o->inv_vars.p, m->inv_vars.p, sizeof(double) * C * D, hipMemcpyDeviceToDevice));
-    HIP_TRY(hipMemcpy(o->norm.p, m->norm.p, sizeof(double) * C, hipMemcpyDeviceToDevice));
-    HIP_TRY(hipMemcpy(o->logw.p, m->logw.p, sizeof(double) * C, hipMemcpyDeviceToDevice));
-  }
+  std::unique_ptr<sr_model, int (*)(sr_model*)> own(nullptr, sr_model_destroy);
+  if ((rc = adapted_model_shell(m, own))) return rc;
+  sr_model* o = own.get();
+  if (C) HIP_TRY(hipMemcpy(o->logw.p, m->logw.p, sizeof(double) * C, hipMemcpyDeviceToDevice));
   DevBuf<uint32_t> d_order, d_blk;
   DevBuf<double> d_W;
   HIP_TRY(d_order.upload(order.data(), order.size())); HIP_TRY(d_blk.upload(blk.data(), blk.size()));
@@ -2922,15 +2919,10 @@ int sr_model_map_adapt(sr_model* prior, uint64_t n_entries, const uint32_t* dens
     else HIP_TRY(hipMemcpy(logw.data(), m->logw.p, sizeof(double) * C, hipMemcpyDeviceToHost));
     map_host::update_weights(m->n_states, m->h_dens_off.data(), n_entries, dens, occ, tau_w, logw.data());
   }
-  sr_model* o = nullptr;
-  if ((rc = srhost::model_shell(m->device, D, m->n_states, m->h_dens_off.data(), m->max_approx ? 1 : 0, &o))) return rc;
-  std::unique_ptr<sr_model, int (*)(sr_model*)> own(o, sr_model_destroy);
-  HIP_TRY(o->dens_mean.upload(m->h_dens_mean.data(), C)); HIP_TRY(o->dens_var.upload(m->h_dens_var.data(), C));
-  o->n_mean = m->n_mean; o->n_var = m->n_var; o->h_dens_mean = m->h_dens_mean; o->h_dens_var = m->h_dens_var;
-  HIP_TRY(o->means.ensure(C * D)); HIP_TRY(o->inv_vars.ensure(C * D)); HIP_TRY(o->norm.ensure(C)); HIP_TRY(o->logw.ensure(C));
+  std::unique_ptr<sr_model, int (*)(sr_model*)> own(nullptr, sr_model_destroy);
+  if ((rc = adapted_model_shell(m, own))) return rc;
+  sr_model* o = own.get();
   if (C) {
-    HIP_TRY(hipMemcpy(o->inv_vars.p, m->inv_vars.p, sizeof(double) * C * D, hipMemcpyDeviceToDevice));
-    HIP_TRY(hipMemcpy(o->norm.p, m->norm.p, sizeof(double) * C, hipMemcpyDeviceToDevice));
     if (logw.empty()) HIP_TRY(hipMemcpy(o->logw.p, m->logw.p, sizeof(double) * C, hipMemcpyDeviceToDevice));
     else HIP_TRY(hipMemcpy(o->logw.p, logw.data(), sizeof(double) * C, hipMemcpyHostToDevice));
   }
@@ -3200,7 +3192,6 @@ static int netfb_check(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search
 // The launch groups of a pass -- consecutive utterances of a chunk whose trellises (8 B per frame and position) fit m->fb_budget
 // together (netfb_check: every utterance fits alone) -- and their workspace.  run() enqueues a chunk's groups in order: forward,
 // backward, word posteriors, then per_group(args, frames of the group).
-extern "C++" {
 struct NetFbPass {
   srplan::Groups groups;
   NetFbArgs a{};
@@ -3235,7 +3226,6 @@ struct NetFbPass {
     return SR_OK;
   }
 };
-}  // extern "C++"
 
 // kappa F_u on the device -> F_u
 static int netfb_costs(sr_corpus* c, double scale, double* out_cost) {
@@ -3351,7 +3341,6 @@ static int bgfb_tables(sr_model* m, sr_bigram* b, double scale) {
 // accuracy side beside every cost).  The launch groups are cut like NetFbPass' on a cost prefix that counts the per-utterance vectors
 // in, each with its utterances ordered longest first.  run_groups() enqueues a chunk's groups: per frame the step and the product,
 // forward then backward, then after(group).
-extern "C++" {
 struct BgStepPass {
   srplan::Groups groups;
   srplan::StepOrder steps;                 // each group's range, longest first
@@ -3447,7 +3436,6 @@ struct BgFbPass : BgStepPass {
                       });
   }
 };
-}  // extern "C++"
 
 // the top items of a group's frames through netfb_top_kernel (it reads the word count, the posteriors and the group's first frame)
 static int bgfb_top(const BgFbArgs& a, uint64_t n, uint32_t max_items, double floor, sr_corpus* c, hipStream_t s) {
@@ -3518,15 +3506,9 @@ int sr_recognize_bigram_confidence_corpus(sr_model* m, sr_corpus* c, sr_bigram* 
 }
 
 // ---- MMI training over the recognition network (viterbi_mmi.hip) -----------------------------------------------------------------
-// The transcripts' chains: segment g of utterance u is the silence word (g even) or w_{(g+1)/2} (g odd), each with the slot_info of
-// its lexicon word; ChainArgs' src / dst links as its header says.
-extern "C++" {
-struct Chains {
-  std::vector<uint64_t> off;  // [U + 1]
-  std::vector<uint32_t> info, src, dst;
-  uint32_t sil_len = 0;
-};
-}  // extern "C++"
+// The transcripts' chains of this network and of the bigram search network: chain_host::build_chains and build_bgchains
+#include "chains.cpp"
+using chain_host::Chains;
 
 // netfb_check plus the transcript's: *constrained = a transcript pair is given
 static int occ_check(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
@@ -3559,35 +3541,6 @@ static int occ_check(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_p
   return SR_OK;
 }
 
-static void build_chains(const sr_lexicon* l, uint32_t U, const uint32_t* trans, const uint64_t* trans_off, Chains* ch) {
-  const std::vector<uint32_t>& woff = l->h_word_off;
-  ch->sil_len = woff[1];
-  ch->off.assign(U + 1, 0);
-  std::vector<uint32_t> beg, end;  // first and last chain position of every segment
-  for (uint32_t u = 0; u < U; u++) {
-    const uint32_t n = (uint32_t)(trans_off[u + 1] - trans_off[u]), G = 2 * n + 1, base = (uint32_t)ch->info.size();
-    beg.assign(G, 0); end.assign(G, 0);
-    for (uint32_t g = 0; g < G; g++) {
-      const uint32_t w = (g & 1) ? trans[trans_off[u] + g / 2] : 0u;
-      beg[g] = (uint32_t)ch->info.size() - base;
-      ch->info.insert(ch->info.end(), l->h_slot_info.begin() + woff[w], l->h_slot_info.begin() + woff[w + 1]);
-      end[g] = (uint32_t)ch->info.size() - base - 1;
-    }
-    ch->src.resize(ch->info.size(), 0xFFFFFFFFu);
-    ch->dst.resize(ch->info.size(), 0xFFFFFFFFu);
-    for (uint32_t g = 0; g < G; g++) {
-      // a word is entered by the silence before it and the word before that; a silence by the word before it and by itself
-      const uint32_t s0 = g ? end[g - 1] : 0xFFFFu, s1 = (g & 1) ? (g >= 2 ? end[g - 2] : 0xFFFFu) : end[g];
-      // a word end enters the next word and the silence after it; a silence's the next word and itself
-      const uint32_t d0 = g + 1 < G ? beg[g + 1] : 0xFFFFu, d1 = (g & 1) ? (g + 2 < G ? beg[g + 2] : 0xFFFFu) : beg[g];
-      ch->src[base + beg[g]] = s0 | s1 << 16;
-      if (end[g] > beg[g]) ch->src[base + beg[g] + 1] = s0 | s1 << 16;
-      ch->dst[base + end[g]] = d0 | d1 << 16;
-    }
-    ch->off[u + 1] = ch->info.size();
-  }
-}
-
 // One occupancy pass over the corpus on the search's scoring chunks: the free network (trans_off null) or the transcripts' chains.
 // Inside a chunk, consecutive utterances whose trellises fit m->fb_budget together (8 B per frame and position) run forward, backward and
 // -- want_items -- the occupancy items.  Leaves kappa F_u in c->out_cost and, with want_items, *n_items items in c->fb_item_* (frame
@@ -3601,7 +3554,7 @@ static int occ_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_pa
   HIP_TRY(c->out_cost.ensure(U));
   if (U == 0) return SR_OK;
   Chains ch;
-  if (chain) build_chains(l, U, trans, trans_off, &ch);
+  if (chain) chain_host::build_chains(l->h_word_off.data(), l->h_slot_info.data(), U, trans, trans_off, &ch);
   // the mixture lists: the distinct mixtures (ascending) of the lexicon, or of each chain, and the positions carrying each
   const srplan::OccPlan<uint16_t> pl(c->frame_off.data(), U, chain ? ch.off.data() : nullptr, chain ? ch.info.data() : l->h_slot_info.data(), P,
                                      true);
@@ -3664,7 +3617,6 @@ static int occ_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_pa
 
 // Numerator and denominator statistics of MMI training, for sr_mmi_statistics_corpus and sr_bigram_mmi_statistics_corpus:
 // pass(numerator, gate, &n_items) is the entry point's occupancy pass over the transcripts' chains (numerator) or the free network.
-extern "C++" {
 template <class Pass>
 static int mmi_statistics(sr_model* m, sr_corpus* c, double scale, int max_approx, double* out_num_cost, double* out_den_cost,
                           double* num_mean_acc, double* num_mean_w, double* num_var_acc, double* num_var_w, double* den_mean_acc,
@@ -3690,7 +3642,6 @@ static int mmi_statistics(sr_model* m, sr_corpus* c, double scale, int max_appro
   c->acc_valid = false;  // (the handle holds one side only: nothing for sr_model_create_from_accumulated)
   return rc;
 }
-}  // extern "C++"
 
 int sr_net_occupancies_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
                               uint32_t max_items, const uint32_t* trans, const uint64_t* trans_off, double* out_cost,
@@ -3822,7 +3773,6 @@ static int smbr_costs(sr_corpus* c, double scale, double* out_cost, double* out_
 // position) fit m->fb_budget together (smbr_check: every utterance fits alone).  run() enqueues a chunk's groups in order: forward,
 // backward, then per_group(item arguments of the group, frames of the group).  want_items: the item path is ready (ensure_items) and
 // `ia` writes to c->fb_item_*.
-extern "C++" {
 struct SmbrPass {
   srplan::Groups groups;
   SmbrArgs a{};
@@ -3946,7 +3896,6 @@ static int smbr_statistics(sr_model* m, sr_corpus* c, int gmm_kernel, double sca
   c->acc_valid = false;  // (the handle holds one side only: nothing for sr_model_create_from_accumulated)
   return rc;
 }
-}  // extern "C++"
 
 int sr_net_accuracies_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
                              uint32_t max_items, const uint16_t* ref_states, double* out_cost, double* out_acc, uint16_t* out_count,
@@ -3977,16 +3926,6 @@ int sr_smbr_statistics_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr
 }
 
 // ---- MMI training over the bigram search network (viterbi_bigram_mmi.hip) ---------------------------------------------------------
-// The transcripts' chains: segment 0 of utterance u is the silence word S, segment 2 i - 1 the word w_i and segment 2 i its silence
-// copy c_i, each with the pos_info of its slot of the search net; BgChainArgs' src / dst links and entry LM costs as its header says.
-extern "C++" {
-struct BgChains {
-  std::vector<uint64_t> off;  // [U + 1]
-  std::vector<uint32_t> info, src, dst;
-  std::vector<double> lmc;
-};
-}  // extern "C++"
-
 // bgfb_check plus the transcript's: *constrained = a transcript pair is given.  free_items: the call makes items of the free network
 static int bgocc_check(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, double posterior_floor, const uint32_t* trans,
                        const uint64_t* trans_off, bool free_items, bool* constrained) {
@@ -4022,47 +3961,6 @@ static int bgocc_check(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, do
   return SR_OK;
 }
 
-static void build_bgchains(const sr_bigram* b, uint32_t U, double scale, const uint32_t* trans, const uint64_t* trans_off, BgChains* ch) {
-  const std::vector<uint32_t>& soff = b->h_slot_off;
-  const uint32_t W = b->net.n_words, sil = b->net.silence, none = 0xFFFFu;
-  ch->off.assign(U + 1, 0);
-  std::vector<uint32_t> beg, end;  // first and last chain position of every segment
-  for (uint32_t u = 0; u < U; u++) {
-    const uint32_t n = (uint32_t)(trans_off[u + 1] - trans_off[u]), G = 2 * n + 1, base = (uint32_t)ch->info.size();
-    const uint32_t* tr = trans + trans_off[u];
-    beg.assign(G, 0); end.assign(G, 0);
-    for (uint32_t g = 0; g < G; g++) {
-      const uint32_t x = g == 0 ? sil : ((g & 1) ? tr[g / 2] : tr[g / 2 - 1] + W);  // the segment's slot
-      beg[g] = (uint32_t)ch->info.size() - base;
-      ch->info.insert(ch->info.end(), b->h_pos_info.begin() + soff[x], b->h_pos_info.begin() + soff[x + 1]);
-      end[g] = (uint32_t)ch->info.size() - base - 1;
-    }
-    ch->src.resize(ch->info.size(), 0xFFFFFFFFu);
-    ch->dst.resize(ch->info.size(), 0xFFFFFFFFu);
-    ch->lmc.resize(ch->info.size(), 0.0);
-    for (uint32_t g = 0; g < G; g++) {
-      uint32_t s0, s1 = none, d0, d1 = none;
-      double lmc = 0.0;
-      if (g == 0) {  // S: from the start and itself; into itself and w_1
-        s0 = end[0]; d0 = beg[0]; d1 = G > 1 ? beg[1] : none;
-      } else if (g & 1) {  // w_i: from w_{i-1} and c_{i-1} (w_1: the start and S); into c_i and w_{i+1}
-        s0 = g == 1 ? end[0] : end[g - 2]; s1 = g == 1 ? none : end[g - 1];
-        d0 = beg[g + 1]; d1 = g + 2 < G ? beg[g + 2] : none;
-        const float x = b->h_lmT[(size_t)(g == 1 ? sil : tr[g / 2 - 1]) * W + tr[g / 2]];
-        lmc = x < std::numeric_limits<float>::infinity() ? scale * (double)x : std::numeric_limits<double>::infinity();  // (NaN: forbidden)
-      } else {  // c_i: from w_i; into w_{i+1}
-        s0 = end[g - 1]; d0 = g + 1 < G ? beg[g + 1] : none;
-      }
-      for (uint32_t k = beg[g]; k <= std::min(beg[g] + 1, end[g]); k++) {
-        ch->src[base + k] = s0 | s1 << 16;
-        ch->lmc[base + k] = lmc;
-      }
-      ch->dst[base + end[g]] = d0 | d1 << 16;
-    }
-    ch->off[u + 1] = ch->info.size();
-  }
-}
-
 // the items of the bigram passes: most positions of a mixture a lane sums alone (a silence mixture has W + 1: summed wave-wide)
 static constexpr uint32_t kBgItemsSerial = 16;
 
@@ -4078,8 +3976,10 @@ static int bgocc_pass(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, d
   *n_items = 0;
   HIP_TRY(c->out_cost.ensure(U));
   if (U == 0) return SR_OK;
-  BgChains ch;
-  if (chain) build_bgchains(b, U, scale, trans, trans_off, &ch);
+  Chains ch;
+  if (chain)
+    chain_host::build_bgchains(b->h_slot_off.data(), b->h_pos_info.data(), b->net.n_words, b->net.silence, b->h_lmT.data(), scale, U, trans,
+                               trans_off, &ch);
   // the mixture lists only where items are wanted
   const srplan::OccPlan<uint32_t> pl(c->frame_off.data(), U, chain ? ch.off.data() : nullptr, chain ? ch.info.data() : b->h_pos_info.data(), P,
                                      want_items);
@@ -4202,7 +4102,6 @@ static int bgsmbr_check(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, d
 // BgStepPass at multiplicity 2 for the accuracy recursions: the groups cut on 16 B per (frame, position) and twice the vectors, the
 // items' mixture lists bgocc_pass' free ones.  run() enqueues a chunk's groups: the recursion on both operand vectors, then
 // per_group(item arguments of the group, frames of the group).  `ia` writes to c->fb_item_*.
-extern "C++" {
 struct BgSmbrPass : BgStepPass {
   BgSmbrArgs a{};
   ItemArgs ia{};
@@ -4240,7 +4139,6 @@ struct BgSmbrPass : BgStepPass {
                       });
   }
 };
-}  // extern "C++"
 
 int sr_bigram_accuracies_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, double scale, double posterior_floor,
                                 uint32_t max_items, const uint16_t* ref_states, double* out_cost, double* out_acc, uint16_t* out_count,
@@ -4296,17 +4194,14 @@ static int lattice_offsets(sr_corpus* c, uint64_t cap, bool fill, uint64_t* out_
   *n_arcs = total;
   return SR_OK;
 }
-extern "C++" {
 template <class T>
 static hipError_t copy_arcs(T* out, const DevBuf<T>& arcs, uint64_t n_arcs) {
   return n_arcs ? hipMemcpy(out, arcs.p, sizeof(T) * n_arcs, hipMemcpyDeviceToHost) : hipSuccess;
 }
-}  // extern "C++"
 
 // The launch groups of a lattice pass -- NetFbPass' grouping on the lattice's bytes per frame: consecutive utterances of a chunk
 // whose word-end tables fit m->fb_budget together (every utterance fits alone: checked by the entry point).  run() enqueues a
 // chunk's groups in order: forward, backward, emit.
-extern "C++" {
 struct LatticePass {
   srplan::Groups groups;
   LatticeArgs a{};
@@ -4358,7 +4253,6 @@ struct LatticePass {
     return SR_OK;
   }
 };
-}  // extern "C++"
 
 int sr_word_lattice_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double lattice_beam, uint64_t cap,
                            uint64_t* out_arc_off, double* out_best, uint32_t* out_word, uint32_t* out_first, uint32_t* out_last,
@@ -4406,93 +4300,6 @@ int sr_word_lattice_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_se
   });
 }
 
-// Best-first search over (frame, word string so far) with the exact heuristic h[f] = the cheapest completion from frame f (one
-// backward pass over the arcs): the first time a state leaves the queue its cost is that of the string's cheapest path to it, so
-// the complete strings leave in order of their cheapest paths.  The strings live in a trie (node = parent node + word).
-int sr_lattice_nbest(uint32_t n_frames, uint64_t n_arcs, const uint32_t* word, const uint32_t* first, const uint32_t* last,
-                     const double* cost, uint32_t silence_word, uint32_t n_best, uint32_t* out_words, uint64_t words_cap,
-                     uint64_t* out_off, double* out_cost, uint32_t* out_count) {
-  return guarded(__func__, [&]() -> int {
-  if (!out_off || !out_cost || !out_count || (n_arcs && (!word || !first || !last || !cost)) || (words_cap && !out_words))
-    return fail(SR_EINVAL, "null argument");
-  *out_count = 0;
-  out_off[0] = 0;
-  if (n_best == 0) return fail(SR_EINVAL, "n_best must be >= 1");
-  const double inf = std::numeric_limits<double>::infinity();
-  for (uint64_t i = 0; i < n_arcs; i++) {
-    if (first[i] > last[i] || last[i] >= n_frames) return fail(SR_EINVAL, "arc %llu: frames %u .. %u of %u", (unsigned long long)i, first[i], last[i], n_frames);
-    if (i && (last[i] < last[i - 1] || (last[i] == last[i - 1] && word[i] < word[i - 1])))
-      return fail(SR_EINVAL, "arc %llu: the arcs are not in (last, word) order", (unsigned long long)i);
-    if (std::isnan(cost[i]) || cost[i] == -inf) return fail(SR_EINVAL, "arc %llu: cost %g", (unsigned long long)i, cost[i]);
-  }
-  if (n_frames == 0) return SR_OK;
-  const uint32_t T = n_frames;
-  // the arcs by first frame (a counting sort: arcs of one frame keep their order)
-  std::vector<uint64_t> beg(T + 2, 0);
-  for (uint64_t i = 0; i < n_arcs; i++) beg[first[i] + 1]++;
-  for (uint32_t f = 0; f <= T; f++) beg[f + 1] += beg[f];
-  std::vector<uint64_t> by_first(n_arcs), fill(beg.begin(), beg.end() - 1);
-  for (uint64_t i = 0; i < n_arcs; i++) by_first[fill[first[i]]++] = i;
-  std::vector<double> h(T + 1, inf);
-  h[T] = 0.0;
-  for (uint32_t f = T; f-- > 0;)
-    for (uint64_t k = beg[f]; k < beg[f + 1]; k++) {
-      const uint64_t i = by_first[k];
-      const double x = cost[i] + h[last[i] + 1];
-      if (x < h[f]) h[f] = x;
-    }
-  struct Node { uint32_t parent, word; };
-  std::vector<Node> trie{{0xFFFFFFFFu, 0}};  // node 0: the empty string
-  std::map<std::pair<uint32_t, uint32_t>, uint32_t> child;
-  std::map<std::pair<uint32_t, uint32_t>, double> best_g;  // (frame, node) -> the cheapest cost pushed
-  struct Item { double f, g; uint32_t frame, node; uint64_t seq; };
-  auto later = [](const Item& x, const Item& y) { return x.f > y.f || (x.f == y.f && x.seq > y.seq); };
-  std::priority_queue<Item, std::vector<Item>, decltype(later)> queue(later);
-  uint64_t seq = 0, n_words_out = 0;
-  if (h[0] < inf) {
-    best_g[{0u, 0u}] = 0.0;
-    queue.push(Item{h[0], 0.0, 0, 0, seq++});
-  }
-  uint32_t n_out = 0;
-  std::vector<uint32_t> rev;
-  while (!queue.empty() && n_out < n_best) {
-    const Item it = queue.top();
-    queue.pop();
-    if (it.g > best_g[{it.frame, it.node}]) continue;  // a cheaper path reached this state later
-    if (it.frame == T) {
-      rev.clear();
-      for (uint32_t n = it.node; n != 0; n = trie[n].parent) rev.push_back(trie[n].word);
-      if (n_words_out + rev.size() > words_cap) {
-        *out_count = 0;
-        return fail(SR_EINVAL, "words_cap %llu is too small", (unsigned long long)words_cap);
-      }
-      for (size_t k = rev.size(); k-- > 0;) out_words[n_words_out++] = rev[k];
-      out_cost[n_out] = it.g;
-      out_off[++n_out] = n_words_out;
-      continue;
-    }
-    for (uint64_t k = beg[it.frame]; k < beg[it.frame + 1]; k++) {
-      const uint64_t i = by_first[k];
-      const uint32_t nf = last[i] + 1;
-      if (!(h[nf] < inf) || !(cost[i] < inf)) continue;  // no complete path uses this arc
-      uint32_t node = it.node;
-      if (word[i] != silence_word) {
-        auto ins = child.emplace(std::make_pair(it.node, word[i]), (uint32_t)trie.size());
-        if (ins.second) trie.push_back(Node{it.node, word[i]});
-        node = ins.first->second;
-      }
-      const double g = it.g + cost[i];
-      auto bg = best_g.find({nf, node});
-      if (bg != best_g.end() && !(g < bg->second)) continue;
-      best_g[{nf, node}] = g;
-      queue.push(Item{g + h[nf], g, nf, node, seq++});
-    }
-  }
-  *out_count = n_out;
-  return SR_OK;
-  });
-}
-
 // ---- word lattices over the bigram search network (viterbi_bigram_lattice.hip) -----------------------------------------------------
 // Workspace counted in SRGPU_FB_MB: per (frame, slot) fwd 8 + bwd 8 + first 2 + pred 4 bytes over 2 W slots, and the emit step's count
 // and scan; per utterance the vectors vec / prod / wend (8 Kp each) and arg (4 Kp), the two rows of cost 8 + first 2 + pred 4 per position
@@ -4504,7 +4311,6 @@ static std::vector<uint64_t> bglat_cost(const sr_corpus* c, const sr_bigram* b) 
 
 // The launch groups of a pass, cut like BgFbPass' on the lattice's bytes, each with its utterances ordered longest first.  run()
 // enqueues a chunk's groups: per frame the in-word step and the min-plus entry, forward then backward, then the arcs.
-extern "C++" {
 struct BgLatPass {
   srplan::Groups groups;
   srplan::StepOrder steps;                 // each group's range, longest first
@@ -4605,7 +4411,6 @@ struct BgLatPass {
     return SR_OK;
   }
 };
-}  // extern "C++"
 
 int sr_bigram_word_lattice_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, double lattice_beam, uint64_t cap,
                                   uint64_t* out_arc_off, double* out_best, uint32_t* out_word, uint32_t* out_hist, uint32_t* out_pred,
@@ -4651,131 +4456,8 @@ int sr_bigram_word_lattice_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int g
   });
 }
 
-// Best-first search as sr_lattice_nbest over (last arc taken, word string so far): the last arc fixes the frame, the slot it left
-// (what may follow: its own copy after a word, the silence word after the silence word or the start) and the history the next word
-// pays the LM for.  The heuristic h[i] = the cheapest completion after arc i is exact (one backward pass over the arcs).
-int sr_bigram_lattice_nbest(uint32_t n_frames, uint64_t n_arcs, const uint32_t* word, const uint32_t* hist, const uint32_t* first,
-                            const uint32_t* last, const double* am, uint32_t n_words, uint32_t silence_word, const float* lm,
-                            double lm_scale, uint32_t n_best, uint32_t* out_words, uint64_t words_cap, uint64_t* out_off, double* out_cost,
-                            uint32_t* out_count) {
-  return guarded(__func__, [&]() -> int {
-  if (!out_off || !out_cost || !out_count || (n_arcs && (!word || !hist || !first || !last || !am)) || (words_cap && !out_words))
-    return fail(SR_EINVAL, "null argument");
-  *out_count = 0;
-  out_off[0] = 0;
-  if (!lm) return fail(SR_EINVAL, "lm is null");
-  if (n_best == 0) return fail(SR_EINVAL, "n_best must be >= 1");
-  if (!(lm_scale >= 0.0)) return fail(SR_EINVAL, "lm_scale must be >= 0 (got %g)", lm_scale);
-  if (n_words == 0 || silence_word >= n_words) return fail(SR_EINVAL, "silence word %u out of range (%u words)", silence_word, n_words);
-  if (n_arcs >= 0xFFFFFFFFull) return fail(SR_ELIMIT, "too many arcs");
-  const double inf = std::numeric_limits<double>::infinity();
-  const uint32_t W = n_words, sil = silence_word;
-  // the slot an arc ends: the word itself, the silence word, or the copy hist + W
-  auto slot_of = [&](uint64_t i) { return word[i] != sil ? word[i] : (hist[i] == sil ? sil : hist[i] + W); };
-  for (uint64_t i = 0; i < n_arcs; i++) {
-    if (word[i] >= W || hist[i] >= W) return fail(SR_EINVAL, "arc %llu: word %u, history %u of %u words", (unsigned long long)i, word[i], hist[i], W);
-    if (word[i] != sil && hist[i] != word[i]) return fail(SR_EINVAL, "arc %llu: word %u ends with history %u", (unsigned long long)i, word[i], hist[i]);
-    if (first[i] > last[i] || last[i] >= n_frames) return fail(SR_EINVAL, "arc %llu: frames %u .. %u of %u", (unsigned long long)i, first[i], last[i], n_frames);
-    if (i && (last[i] < last[i - 1] || (last[i] == last[i - 1] && slot_of(i) <= slot_of(i - 1))))
-      return fail(SR_EINVAL, "arc %llu: the arcs are not in (last, slot) order", (unsigned long long)i);
-    if (std::isnan(am[i]) || am[i] == -inf) return fail(SR_EINVAL, "arc %llu: cost %g", (unsigned long long)i, am[i]);
-  }
-  if (n_frames == 0) return SR_OK;
-  const uint32_t T = n_frames, kStart = 0xFFFFFFFFu;
-  // the arcs by first frame (a counting sort: arcs of one frame keep their order)
-  std::vector<uint64_t> beg(T + 2, 0);
-  for (uint64_t i = 0; i < n_arcs; i++) beg[first[i] + 1]++;
-  for (uint32_t f = 0; f <= T; f++) beg[f + 1] += beg[f];
-  std::vector<uint32_t> by_first(n_arcs);
-  {
-    std::vector<uint64_t> fill(beg.begin(), beg.end() - 1);
-    for (uint64_t i = 0; i < n_arcs; i++) by_first[fill[first[i]]++] = (uint32_t)i;
-  }
-  // the cost of arc j right after arc i (kStart: the start, a word end of the silence word): +inf where the network has no such entry
-  auto step = [&](uint32_t i, uint32_t j) -> double {
-    const uint32_t pw = i == kStart ? sil : word[i], ph = i == kStart ? sil : hist[i];
-    double c = 0.0;
-    if (word[j] != sil) {
-      const float l = lm[(size_t)word[j] * W + ph];
-      if (!(l < std::numeric_limits<float>::infinity())) return inf;  // NaN and +inf: forbidden
-      c = lm_scale * (double)l;
-    } else if (hist[j] == sil) {
-      if (!(pw == sil && ph == sil)) return inf;  // the silence word follows the start or itself
-    } else if (pw != hist[j] || pw == sil) {
-      return inf;  // the copy h + W follows word h alone
-    }
-    return c + am[j];
-  };
-  std::vector<double> h(n_arcs, inf);
-  double h_start = inf;
-  for (uint64_t k = n_arcs; k-- > 0;) {  // (last ascends with the index, and an arc's successors start after its last: they are done)
-    const uint32_t i = (uint32_t)k, nf = last[i] + 1;
-    if (nf == T) { h[i] = 0.0; continue; }
-    for (uint64_t q = beg[nf]; q < beg[nf + 1]; q++) {
-      const uint32_t j = by_first[q];
-      const double x = step(i, j) + h[j];
-      if (x < h[i]) h[i] = x;
-    }
-  }
-  for (uint64_t q = beg[0]; q < beg[1]; q++) {
-    const uint32_t j = by_first[q];
-    const double x = step(kStart, j) + h[j];
-    if (x < h_start) h_start = x;
-  }
-  struct Node { uint32_t parent, word; };
-  std::vector<Node> trie{{0xFFFFFFFFu, 0}};  // node 0: the empty string
-  std::map<std::pair<uint32_t, uint32_t>, uint32_t> child;
-  std::map<std::pair<uint32_t, uint32_t>, double> best_g;  // (arc, node) -> the cheapest cost pushed
-  struct Item { double f, g; uint32_t arc, node; uint64_t seq; };
-  auto later = [](const Item& x, const Item& y) { return x.f > y.f || (x.f == y.f && x.seq > y.seq); };
-  std::priority_queue<Item, std::vector<Item>, decltype(later)> queue(later);
-  uint64_t seq = 0, n_words_out = 0;
-  if (h_start < inf) {
-    best_g[{kStart, 0u}] = 0.0;
-    queue.push(Item{h_start, 0.0, kStart, 0, seq++});
-  }
-  uint32_t n_out = 0;
-  std::vector<uint32_t> rev;
-  std::set<uint32_t> done;  // the strings (trie nodes) given out
-  while (!queue.empty() && n_out < n_best) {
-    const Item it = queue.top();
-    queue.pop();
-    if (it.g > best_g[{it.arc, it.node}]) continue;  // a cheaper path reached this state later
-    const uint32_t nf = it.arc == kStart ? 0 : last[it.arc] + 1;
-    if (nf == T) {
-      if (!done.insert(it.node).second) continue;  // the string has left already, at its cheapest, through another final arc
-      rev.clear();
-      for (uint32_t n = it.node; n != 0; n = trie[n].parent) rev.push_back(trie[n].word);
-      if (n_words_out + rev.size() > words_cap) {
-        *out_count = 0;
-        return fail(SR_EINVAL, "words_cap %llu is too small", (unsigned long long)words_cap);
-      }
-      for (size_t k = rev.size(); k-- > 0;) out_words[n_words_out++] = rev[k];
-      out_cost[n_out] = it.g;
-      out_off[++n_out] = n_words_out;
-      continue;
-    }
-    for (uint64_t q = beg[nf]; q < beg[nf + 1]; q++) {
-      const uint32_t j = by_first[q];
-      const double st = step(it.arc, j);
-      if (!(h[j] < inf) || !(st < inf)) continue;  // no complete path goes this way
-      uint32_t node = it.node;
-      if (word[j] != sil) {
-        auto ins = child.emplace(std::make_pair(it.node, word[j]), (uint32_t)trie.size());
-        if (ins.second) trie.push_back(Node{it.node, word[j]});
-        node = ins.first->second;
-      }
-      const double g = it.g + st;
-      auto bg = best_g.find({j, node});
-      if (bg != best_g.end() && !(g < bg->second)) continue;
-      best_g[{j, node}] = g;
-      queue.push(Item{g + h[j], g, j, node, seq++});
-    }
-  }
-  *out_count = n_out;
-  return SR_OK;
-  });
-}
+// ---- N-best lists from either kind of lattice: sr_lattice_nbest, sr_bigram_lattice_nbest (host code on the caller's arrays) ----------
+#include "nbest.cpp"
 
 int sr_probe_fp16_accumulation(int device, int* within_model, double* worst_ratio) {
   return guarded(__func__, [&]() -> int {
@@ -4915,64 +4597,88 @@ int sr_stream_end(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_t cap, 
   });
 }
 
-// The stable prefix of n open utterances: one launch of stream_commit_kernel, which writes straight into the call's pinned block.
-// Block: StableJob[n] (in), StableResult[n], then the words, utterance i's at jobs[i].word_off (t_i slots: at most a word per frame).
-int sr_stream_stable(sr_stream* s, uint32_t n, const uint32_t* ids, uint32_t* out_words, uint64_t cap, uint64_t* out_word_off,
-                     uint32_t* out_commit, uint32_t* out_silence) {
-  return guarded(__func__, [&]() -> int {
+// The stable prefix of n open utterances of either stream set (Set: sr_stream with StableJob, sr_bigram_stream with BigramStableJob):
+// one launch of the set's commit kernel, one workgroup per utterance, which writes straight into the call's pinned block.  Block:
+// Job[n] (in), StableResult[n], then the items, frame_bytes for every frame the n utterances have seen (an utterance gives at most
+// one item per frame; its items start `frames of the utterances before it` into each item area).  The caller supplies make_job(i,
+// slot, frames before, &job) -> rc, launch(jobs, results, items, frames, stream) -> rc over the block's three parts, copy_out(i, job,
+// result, out_off[i]) for utterance i's items, what a result that fails its checks says, and the middle of the capacity message.
+template <class Job, class Set, class MakeJob, class Launch, class CopyOut>
+static int stable_prefix(Set* s, uint32_t n, const uint32_t* ids, bool missing_array, uint64_t cap, uint64_t* out_off, uint32_t* out_commit,
+                         size_t frame_bytes, const char* corrupt, const char* holds, MakeJob make_job, Launch launch, CopyOut copy_out) {
   if (!s) return fail(SR_EINVAL, "null stream set");
-  if (!out_word_off || (n && (!ids || !out_commit)) || (!out_words && cap)) return fail(SR_EINVAL, "null argument");
+  if (!out_off || (n && (!ids || !out_commit)) || missing_array) return fail(SR_EINVAL, "null argument");
   sr_model* m = s->model;
   int rc = check_model(m);
   if (rc) return rc;
   const StreamSlots& sl = s->slots;
   std::vector<uint8_t> seen(sl.max_streams, 0);
-  std::vector<StableJob> jobs(n);
-  uint64_t W = 0;
+  std::vector<Job> jobs(n);
+  uint64_t F = 0;
   for (uint32_t i = 0; i < n; i++) {
     const int64_t slot = sl.find(ids[i]);
     if (slot < 0) return fail(SR_EINVAL, "entry %u: stream id %u is not open", i, ids[i]);
     if (seen[slot]) return fail(SR_EINVAL, "entry %u: stream id %u appears twice in one call", i, ids[i]);
     seen[slot] = 1;
-    jobs[i] = StableJob{(uint32_t)slot, (uint32_t)sl.frames[slot], s->commit_fresh[slot], 0u, W};
-    W += sl.frames[slot];
+    if ((rc = make_job(i, (uint32_t)slot, F, &jobs[i]))) return rc;
+    F += sl.frames[slot];
   }
-  if (n == 0) { out_word_off[0] = 0; return SR_OK; }
-  const sr_lexicon* l = s->lex;
+  if (n == 0) { out_off[0] = 0; return SR_OK; }
   HIP_TRY(s->commit.ensure(sl.max_streams));
-  HIP_TRY(s->stable_words.ensure((size_t)sl.max_streams * sl.max_frames));
-  const size_t res_at = sizeof(StableJob) * n, words_at = res_at + sizeof(StableResult) * n;
-  if (words_at + sizeof(uint32_t) * W > s->stable_block.n)  // (grown geometrically: pinning costs milliseconds, the need grows with every push)
-    HIP_TRY(s->stable_block.ensure(std::max<size_t>(words_at + sizeof(uint32_t) * W, 2 * s->stable_block.n)));
+  const size_t res_at = sizeof(Job) * n, items_at = res_at + sizeof(StableResult) * n, need = items_at + frame_bytes * F;
+  if (need > s->stable_block.n)  // (grown geometrically: pinning costs milliseconds, the need grows with every push)
+    HIP_TRY(s->stable_block.ensure(std::max<size_t>(need, 2 * s->stable_block.n)));
   unsigned char* blk = s->stable_block.p;
-  memcpy(blk, jobs.data(), sizeof(StableJob) * n);
-  StableArgs a{};
-  a.net = l->net;
-  a.jobs = reinterpret_cast<const StableJob*>(blk);
-  a.ws = s->ws.p; a.ws_stride = decode_big_workspace(l->net.n_slots);
-  a.tb_word = s->tb_word.p; a.tb_bkp = s->tb_bkp.p; a.tb_stride = sl.max_frames + 1;
-  a.commit = s->commit.p; a.words = s->stable_words.p; a.words_stride = sl.max_frames;
-  a.out_res = reinterpret_cast<StableResult*>(blk + res_at); a.out_words = reinterpret_cast<uint32_t*>(blk + words_at);
-  HIP_TRY(launch_stream_commit(a, n, m->s_gmm));
+  memcpy(blk, jobs.data(), sizeof(Job) * n);
+  StableResult* res = reinterpret_cast<StableResult*>(blk + res_at);
+  if ((rc = launch(reinterpret_cast<const Job*>(blk), res, blk + items_at, F, m->s_gmm))) return rc;
   HIP_TRY(hipStreamSynchronize(m->s_gmm));
-  const StableResult* res = a.out_res;
   uint32_t bad = 0xFFFFFFFFu;
   for (uint32_t i = 0; i < n; i++) {
     if (res[i].flags || res[i].count > jobs[i].t || res[i].commit > jobs[i].t) { if (bad == 0xFFFFFFFFu) bad = i; }
     else s->commit_fresh[jobs[i].slot] = 0;  // the kernel left its commit point in commit[slot]
   }
-  if (bad != 0xFFFFFFFFu)
-    return fail(SR_ECORRUPT, "stream %u: the traceback does not walk back from the commit point to frame 0 (Recognizer.cpp:222-231)", ids[bad]);
+  if (bad != 0xFFFFFFFFu) return fail(SR_ECORRUPT, "stream %u: %s", ids[bad], corrupt);
   uint64_t total = 0;
-  for (uint32_t i = 0; i < n; i++) { out_word_off[i] = total; total += res[i].count; }
-  out_word_off[n] = total;
-  if (total > cap) return fail(SR_EINVAL, "%llu stable words, out_words holds %llu", (unsigned long long)total, (unsigned long long)cap);
+  for (uint32_t i = 0; i < n; i++) { out_off[i] = total; total += res[i].count; }
+  out_off[n] = total;
+  if (total > cap) return fail(SR_EINVAL, "%llu stable %s %llu", (unsigned long long)total, holds, (unsigned long long)cap);
   for (uint32_t i = 0; i < n; i++) {
-    if (res[i].count) memcpy(out_words + out_word_off[i], a.out_words + jobs[i].word_off, sizeof(uint32_t) * res[i].count);
+    copy_out(i, jobs[i], res[i], out_off[i]);
     out_commit[i] = res[i].commit;
-    if (out_silence) out_silence[i] = res[i].silence;
   }
   return SR_OK;
+}
+
+// The zerogram set's block holds the words (4 bytes a frame), utterance i's at jobs[i].word_off.
+int sr_stream_stable(sr_stream* s, uint32_t n, const uint32_t* ids, uint32_t* out_words, uint64_t cap, uint64_t* out_word_off,
+                     uint32_t* out_commit, uint32_t* out_silence) {
+  return guarded(__func__, [&]() -> int {
+  StableArgs a{};
+  return stable_prefix<StableJob>(
+      s, n, ids, !out_words && cap, cap, out_word_off, out_commit, sizeof(uint32_t),
+      "the traceback does not walk back from the commit point to frame 0 (Recognizer.cpp:222-231)", "words, out_words holds",
+      [&](uint32_t, uint32_t slot, uint64_t off, StableJob* job) -> int {
+        *job = StableJob{slot, (uint32_t)s->slots.frames[slot], s->commit_fresh[slot], 0u, off};
+        return SR_OK;
+      },
+      [&](const StableJob* jobs, StableResult* res, unsigned char* items, uint64_t, hipStream_t stream) -> int {
+        const StreamSlots& sl = s->slots;
+        const sr_lexicon* l = s->lex;
+        HIP_TRY(s->stable_words.ensure((size_t)sl.max_streams * sl.max_frames));
+        a.net = l->net;
+        a.jobs = jobs;
+        a.ws = s->ws.p; a.ws_stride = decode_big_workspace(l->net.n_slots);
+        a.tb_word = s->tb_word.p; a.tb_bkp = s->tb_bkp.p; a.tb_stride = sl.max_frames + 1;
+        a.commit = s->commit.p; a.words = s->stable_words.p; a.words_stride = sl.max_frames;
+        a.out_res = res; a.out_words = reinterpret_cast<uint32_t*>(items);
+        HIP_TRY(launch_stream_commit(a, n, stream));
+        return SR_OK;
+      },
+      [&](uint32_t i, const StableJob& job, const StableResult& r, uint64_t at) {
+        if (r.count) memcpy(out_words + at, a.out_words + job.word_off, sizeof(uint32_t) * r.count);
+        if (out_silence) out_silence[i] = r.silence;
+      });
   });
 }
 
@@ -5175,71 +4881,41 @@ int sr_bigram_stream_end(sr_bigram_stream* s, uint32_t id, uint32_t* out_word, f
   });
 }
 
-// The stable prefix of n open utterances: one launch of bigram_stream_commit_kernel, which writes straight into the call's pinned
-// block.  Block: BigramStableJob[n] (in), StableResult[n], then three item areas (word, score, time) of sum t_i slots each,
-// utterance i's items at jobs[i].item_off.
+// The stable prefix (stable_prefix above): the bigram set's block holds three item areas (word, score, time: 12 bytes a frame),
+// utterance i's items at jobs[i].item_off of each.
 int sr_bigram_stream_stable(sr_bigram_stream* s, uint32_t n, const uint32_t* ids, uint32_t* out_word, float* out_score,
                             uint32_t* out_time, uint64_t cap, uint64_t* out_off, uint32_t* out_commit) {
   return guarded(__func__, [&]() -> int {
-  if (!s) return fail(SR_EINVAL, "null stream set");
-  if (!out_off || (n && (!ids || !out_commit)) || ((!out_word || !out_score || !out_time) && cap)) return fail(SR_EINVAL, "null argument");
-  sr_model* m = s->model;
-  int rc = check_model(m);
-  if (rc) return rc;
-  const StreamSlots& sl = s->slots;
-  std::vector<uint8_t> seen(sl.max_streams, 0);
-  std::vector<BigramStableJob> jobs(n);
-  uint64_t N = 0;
-  for (uint32_t i = 0; i < n; i++) {
-    const int64_t slot = sl.find(ids[i]);
-    if (slot < 0) return fail(SR_EINVAL, "entry %u: stream id %u is not open", i, ids[i]);
-    if (seen[slot]) return fail(SR_EINVAL, "entry %u: stream id %u appears twice in one call", i, ids[i]);
-    seen[slot] = 1;
-    if (s->failed[slot]) return fail(SR_EINTERNAL, "stream %u: a push overflowed its book", ids[i]);
-    jobs[i] = BigramStableJob{(uint32_t)slot, (uint32_t)sl.frames[slot], s->commit_fresh[slot], 0u,
-                              sl.frames[slot] ? s->book[slot]->p : nullptr, N};
-    N += sl.frames[slot];
-  }
-  if (n == 0) { out_off[0] = 0; return SR_OK; }
-  const sr_bigram* b = s->bigram;
-  HIP_TRY(s->commit.ensure(sl.max_streams));
-  const size_t res_at = sizeof(BigramStableJob) * n, items_at = res_at + sizeof(StableResult) * n;
-  if (items_at + 12 * N > s->stable_block.n)  // (grown geometrically: pinning costs milliseconds, the need grows with every push)
-    HIP_TRY(s->stable_block.ensure(std::max<size_t>(items_at + 12 * N, 2 * s->stable_block.n)));
-  unsigned char* blk = s->stable_block.p;
-  memcpy(blk, jobs.data(), sizeof(BigramStableJob) * n);
   BigramStableArgs a{};
-  a.n_words = b->net.n_words; a.silence = b->net.silence; a.n_positions = b->net.n_positions; a.slot_off = b->net.slot_off;
-  a.gs_ws = s->gs_ws.p; a.gs_ws_words = bigram_gs_ws_words(b->net.n_words, b->net.n_positions);
-  a.we_bp = s->we_bp.p; a.lsave = s->lsave.p; a.state = s->state.p;
-  a.jobs = reinterpret_cast<const BigramStableJob*>(blk);
-  a.commit = s->commit.p;
-  a.out_res = reinterpret_cast<StableResult*>(blk + res_at);
-  a.out_word = reinterpret_cast<uint32_t*>(blk + items_at);
-  a.out_score = reinterpret_cast<float*>(blk + items_at + 4 * N);
-  a.out_time = reinterpret_cast<uint32_t*>(blk + items_at + 8 * N);
-  HIP_TRY(launch_bigram_stream_commit(a, n, m->s_gmm));
-  HIP_TRY(hipStreamSynchronize(m->s_gmm));
-  const StableResult* res = a.out_res;
-  uint32_t bad = 0xFFFFFFFFu;
-  for (uint32_t i = 0; i < n; i++) {
-    if (res[i].flags || res[i].count > jobs[i].t || res[i].commit > jobs[i].t) { if (bad == 0xFFFFFFFFu) bad = i; }
-    else s->commit_fresh[jobs[i].slot] = 0;  // the kernel left its commit entry in commit[slot]
-  }
-  if (bad != 0xFFFFFFFFu) return fail(SR_ECORRUPT, "stream %u: the book walk from the commit entry does not end at its start entry", ids[bad]);
-  uint64_t total = 0;
-  for (uint32_t i = 0; i < n; i++) { out_off[i] = total; total += res[i].count; }
-  out_off[n] = total;
-  if (total > cap) return fail(SR_EINVAL, "%llu stable items, the output arrays hold %llu", (unsigned long long)total, (unsigned long long)cap);
-  for (uint32_t i = 0; i < n; i++) {
-    if (res[i].count) {
-      memcpy(out_word + out_off[i], a.out_word + jobs[i].item_off, sizeof(uint32_t) * res[i].count);
-      memcpy(out_score + out_off[i], a.out_score + jobs[i].item_off, sizeof(float) * res[i].count);
-      memcpy(out_time + out_off[i], a.out_time + jobs[i].item_off, sizeof(uint32_t) * res[i].count);
-    }
-    out_commit[i] = res[i].commit;
-  }
-  return SR_OK;
+  return stable_prefix<BigramStableJob>(
+      s, n, ids, (!out_word || !out_score || !out_time) && cap, cap, out_off, out_commit, 12,
+      "the book walk from the commit entry does not end at its start entry", "items, the output arrays hold",
+      [&](uint32_t i, uint32_t slot, uint64_t off, BigramStableJob* job) -> int {
+        if (s->failed[slot]) return fail(SR_EINTERNAL, "stream %u: a push overflowed its book", ids[i]);
+        const uint64_t t = s->slots.frames[slot];
+        *job = BigramStableJob{slot, (uint32_t)t, s->commit_fresh[slot], 0u, t ? s->book[slot]->p : nullptr, off};
+        return SR_OK;
+      },
+      [&](const BigramStableJob* jobs, StableResult* res, unsigned char* items, uint64_t N, hipStream_t stream) -> int {
+        const sr_bigram* b = s->bigram;
+        a.n_words = b->net.n_words; a.silence = b->net.silence; a.n_positions = b->net.n_positions; a.slot_off = b->net.slot_off;
+        a.gs_ws = s->gs_ws.p; a.gs_ws_words = bigram_gs_ws_words(b->net.n_words, b->net.n_positions);
+        a.we_bp = s->we_bp.p; a.lsave = s->lsave.p; a.state = s->state.p;
+        a.jobs = jobs;
+        a.commit = s->commit.p;
+        a.out_res = res;
+        a.out_word = reinterpret_cast<uint32_t*>(items);
+        a.out_score = reinterpret_cast<float*>(items + 4 * N);
+        a.out_time = reinterpret_cast<uint32_t*>(items + 8 * N);
+        HIP_TRY(launch_bigram_stream_commit(a, n, stream));
+        return SR_OK;
+      },
+      [&](uint32_t, const BigramStableJob& job, const StableResult& r, uint64_t at) {
+        if (!r.count) return;
+        memcpy(out_word + at, a.out_word + job.item_off, sizeof(uint32_t) * r.count);
+        memcpy(out_score + at, a.out_score + job.item_off, sizeof(float) * r.count);
+        memcpy(out_time + at, a.out_time + job.item_off, sizeof(uint32_t) * r.count);
+      });
   });
 }
 
@@ -5300,5 +4976,3 @@ int sr_profile_read(sr_model* m, sr_profile* out) {
   return SR_OK;
   });
 }
-
-}  // extern "C"

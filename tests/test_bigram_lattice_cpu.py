@@ -258,6 +258,61 @@ def test_nbest_errors(capi):
     assert call(sil=W)[0] == EINVAL
 
 
+def test_nbest_standalone_driver_under_the_sanitizers(tmp_path):
+    """tests/cpp/nbest_host_driver.cpp and nbest.cpp alone, built with -fsanitize=address,undefined and run as a plain program, every
+    output array exactly as long as the call may fill it: test_nbest_against_enumeration_random_lattices' lattices and tables (T = 5, W 3 .. 4,
+    one +inf and one NaN entry) at n_best 1, 3, 1000 and lm_scale 0, 1, 2.5, and every malformed input of test_nbest_errors.  Strings,
+    counts and costs (1e-9) are the enumeration's; no report."""
+    from tests.test_word_lattice_cpu import nbest_driver_case, run_nbest_driver
+    cases, want = [], []
+    for seed in range(8):
+        W, sil, T = 3 + seed % 2, seed % 3, 5
+        A = _random_lattice(800 + seed, W, sil, T)
+        rng = np.random.default_rng(900 + seed)
+        lm = rng.uniform(-0.5, 3.0, size=(W, W)).astype(np.float32)
+        lm[(sil + 1) % W, (sil + 2) % W] = np.inf
+        lm[(sil + 2) % W, (sil + 1) % W] = np.nan
+        klm = R._klm(R.Net(np.arange(W + 1), np.arange(W), sil), lm, 1.0)
+        for n_best, scale in ((1, 1.0), (3, 1.0), (1000, 1.0), (5, 0.0), (5, 2.5)):
+            allc = BL.strings_of(A, BL.lattice_paths(A, T, sil, klm, scale), sil)
+            ref = BL.nbest(A, T, sil, klm, n_best, scale)
+            # all the words of all strings: enough for any n_best, and exactly the need where every string is given out
+            cases.append(nbest_driver_case(T, A, sil, n_best, sum(len(s) for s in allc), W=W, lm=lm, lm_scale=scale))
+            want.append((ref, allc))
+    # the malformed inputs of test_nbest_errors
+    net, lm, e = _tiny(0, 4)
+    _, A = BL.arcs(e, net, lm, TDP)
+    A = {k: A[k] for k in ("word", "hist", "first", "last", "am")}
+    W, sil, T, n = net.W, net.sil, 4, len(A["word"])
+
+    def case(T=T, a=A, W=W, sil=sil, scale=1.0, n_best=3, cap=100, **kw):
+        return nbest_driver_case(T, a, sil, n_best, cap, W=W, lm=lm, lm_scale=scale, **kw)
+
+    def with_(field, idx, val):
+        a = {k: np.array(v) for k, v in A.items()}
+        a[field][idx] = val
+        return a
+
+    bad_hist = int(np.flatnonzero(A["word"] != sil)[0])
+    errs = [(case(), 0, 3), (case(T=0, a={k: v[:0] for k, v in A.items()}), 0, 0), (case(n_best=0), EINVAL, None),
+            (case(null_lm=True), EINVAL, None), (case(null_cost=True), EINVAL, None)]
+    errs += [(case(scale=s), EINVAL, None) for s in (np.nan, -1.0, -np.inf)]
+    errs += [(case(cap=0), EINVAL, 0)]
+    errs += [(case(a=with_(f, i, v)), EINVAL, None) for f, i, v in (("hist", 0, W), ("word", 0, W), ("last", n - 1, T), ("first", n - 1, T),
+                                                                     ("am", 1, np.nan), ("am", 1, -np.inf))]
+    errs += [(case(a={k: v[::-1] for k, v in A.items()}), EINVAL, None),   # not in (last, slot) order
+             (case(a=with_("hist", bad_hist, (A["hist"][bad_hist] + 1) % W)), EINVAL, None),   # a word whose history is not itself
+             (case(sil=W), EINVAL, None)]
+    got = run_nbest_driver(tmp_path, cases + [c for c, _, _ in errs])
+    for (ref, allc), (rc, count, err, strings) in zip(want, got):
+        assert rc == 0 and count == len(strings) == len(ref), (rc, count, err, ref)
+        for (gw, gc), (_, wc) in zip(strings, ref):
+            assert abs(gc - wc) <= 1e-9 and abs(allc[gw] - gc) <= 1e-9, (strings, ref)   # the k-th cost; the string's own cheapest path
+        assert len({w for w, _ in strings}) == count
+    for (_, want_rc, want_count), (rc, count, err, strings) in zip(errs, got[len(want):]):
+        assert rc == want_rc and (want_count is None or count == want_count) and bool(err) == bool(rc), (rc, count, err)
+
+
 @pytest.mark.parametrize("shape", [s for s in SHAPES if s[0] in QUIRK_FREE])
 def test_first_entry_is_the_oracle_decoders_result(shape, tmp_path, oracle_lib, capi):
     """beams off, the shapes on which the decoder's merge loses nothing: entry 1 spells the decoder's words with silence removed; its

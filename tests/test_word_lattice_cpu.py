@@ -5,6 +5,7 @@ library, the header and the bindings, the C++ driver compiles, and the new kerne
 import ctypes as C
 import os
 import re
+import struct
 import subprocess
 import sys
 import tempfile
@@ -246,6 +247,100 @@ def test_nbest_errors(built_lib):
     assert call(na=0) == 0 and n.value == 0
     with pytest.raises(capi.SrError):
         capi.lattice_nbest(2, word, first, last, cost, 7, 0)
+
+
+def nbest_driver_case(T, arcs, sil, n_best, cap, W=None, lm=None, lm_scale=1.0, null_lm=False, null_cost=False):
+    """one case of tests/cpp/nbest_host_driver.cpp's file: sr_lattice_nbest, or -- W given -- sr_bigram_lattice_nbest (arcs with hist, am)"""
+    kind = W is not None
+    u32 = lambda k: np.ascontiguousarray(arcs[k], np.uint32).tobytes()
+    n = len(arcs["word"])
+    head = struct.pack("<IIIIIIQId", int(kind), int(null_lm) + 2 * int(null_cost), T, n, sil, n_best, cap, W or 0, lm_scale)
+    body = u32("word") + (u32("hist") if kind else b"") + u32("first") + u32("last")
+    body += np.ascontiguousarray(arcs["am" if kind else "cost"], np.float64).tobytes()
+    if kind:
+        body += (np.zeros((W, W), np.float32) if lm is None else np.ascontiguousarray(lm, np.float32)).tobytes()
+    return head + body
+
+
+def run_nbest_driver(tmp_path, cases):
+    """builds nbest_host_driver.cpp with nbest.cpp alone under the sanitizers, runs it as a plain program on `cases` ->
+    [(rc, count, error text, [(words, cost)])]; the run must end with status 0 and say nothing on stderr"""
+    drv = str(tmp_path / "nbest_host_driver")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           os.path.join(ROOT, "tests", "cpp", "nbest_host_driver.cpp"),
+                           os.path.join(ROOT, "speechrecognition_amd", "csrc", "nbest.cpp"), "-o", drv])
+    path = tmp_path / "cases.bin"
+    path.write_bytes(struct.pack("<I", len(cases)) + b"".join(cases))
+    p = subprocess.run([drv, str(path)], text=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert p.returncode == 0 and not p.stderr, (p.stdout[-2000:], p.stderr[-2000:])
+    out = []
+    for ln in p.stdout.splitlines():
+        f = ln.split()
+        if f[0] == "case":
+            assert int(f[1]) == len(out)
+            out.append([int(f[3]), int(f[5]), "", []])
+        elif f[0] == "err":
+            out[-1][2] = ln[4:]
+        else:
+            assert f[0] == "s", ln
+            out[-1][3].append((tuple(int(x) for x in f[2:]), struct.unpack("<d", struct.pack("<Q", int(f[1], 16)))[0]))
+    assert len(out) == len(cases)
+    return [tuple(o) for o in out]
+
+
+def test_nbest_standalone_driver_under_the_sanitizers(tmp_path):
+    """tests/cpp/nbest_host_driver.cpp and nbest.cpp alone, built with -fsanitize=address,undefined and run as a plain program, every
+    output array exactly as long as the call may fill it: test_nbest_against_exhaustive_enumeration's lattices (T = 1 and 2 .. 7, W 2 .. 4,
+    costs on the grid of 1/8, dangling arcs, lattices without a complete path, an arc of +inf cost), n_best 1, 3 and beyond the number
+    of strings, a words_cap one short of the need, and every malformed input of test_nbest_errors.  Strings, counts and costs are the
+    enumeration's, the costs to the bit; no report."""
+    rng = np.random.default_rng(1234)
+    cases, want = [], []
+    n_nonempty = n_dangling = n_empty = n_inf = n_short = 0
+    for case in range(80):
+        T = 1 if case % 10 == 0 else int(rng.integers(2, 8))
+        W = int(rng.integers(2, 5))
+        sil = int(rng.integers(0, W))
+        arcs = _random_lattice(rng, T, W, rng.uniform(0.3, 0.9))
+        if case % 7 == 3 and len(arcs["cost"]):
+            arcs["cost"][int(rng.integers(0, len(arcs["cost"])))] = np.inf   # on no path: its strings are not given out
+            n_inf += 1
+        ref_all = [(ws, c) for ws, c in LR.nbest(arcs, T, sil, 10 ** 9) if c < np.inf]
+        used = {i for _, path in LR.lattice_paths(arcs, T) for i in path}
+        n_dangling += len(used) < len(arcs["word"])
+        n_nonempty += bool(ref_all)
+        n_empty += not ref_all
+        need = sum(len(ws) for ws, _ in ref_all)
+        for n in (1, 3, len(ref_all) + 5):
+            cases.append(nbest_driver_case(T, arcs, sil, n, need))
+            want.append((sil, n, ref_all))
+        if need:
+            cases.append(nbest_driver_case(T, arcs, sil, len(ref_all) + 5, need - 1))
+            want.append((sil, None, need - 1))
+            n_short += 1
+    assert n_nonempty > 30 and n_dangling > 30 and n_empty >= 1 and n_inf >= 5 and n_short > 30
+    # the malformed inputs of test_nbest_errors (and its good calls)
+    good = {"word": [0, 1, 1], "first": [0, 0, 1], "last": [0, 1, 1], "cost": [1.0, 2.5, 1.0]}
+    none = {k: [] for k in good}
+    errs = [(2, good, 4, 16, 0, 2), (2, good, 0, 16, EINVAL, None),
+            (2, dict(good, last=[0, 1, 2]), 4, 16, EINVAL, None), (2, dict(good, first=[0, 2, 1]), 4, 16, EINVAL, None),
+            (2, dict(good, word=[0, 1, 0]), 4, 16, EINVAL, None), (2, dict(good, last=[1, 0, 1], first=[0, 0, 0]), 4, 16, EINVAL, None),
+            (2, dict(good, cost=[1.0, np.nan, 1.0]), 4, 16, EINVAL, None), (2, good, 4, 2, EINVAL, 0), (2, good, 4, 3, 0, 2),
+            (2, dict(good, cost=[1.0, np.inf, 1.0]), 4, 16, 0, 1), (0, none, 4, 16, 0, 0), (2, none, 4, 16, 0, 0)]
+    for T, a, nb, cap, _, _ in errs:
+        cases.append(nbest_driver_case(T, a, 7, nb, cap))
+    got = run_nbest_driver(tmp_path, cases)
+    for (sil, n, ref_all), (rc, count, err, strings) in zip(want, got):
+        if n is None:   # one word short: refused, nothing given out
+            assert rc == EINVAL and count == 0 and err == f"words_cap {ref_all} is too small", (rc, count, err)
+            continue
+        assert rc == 0 and count == len(strings) == min(n, len(ref_all)), (rc, count, n, len(ref_all), err)
+        assert [c for _, c in strings] == [c for _, c in ref_all[:count]]
+        table = dict(ref_all)
+        assert len({ws for ws, _ in strings}) == count and all(table[ws] == c and sil not in ws for ws, c in strings)
+    for (T, a, nb, cap, want_rc, want_count), (rc, count, err, strings) in zip(errs, got[len(want):]):
+        assert rc == want_rc and (want_count is None or count == want_count) and bool(err) == bool(rc), (a, nb, cap, rc, count, err)
+    assert got[len(want)][3] == [((0, 1), 2.0), ((1,), 2.5)]
 
 
 def test_entry_points_are_exported(built_lib):
