@@ -277,13 +277,21 @@ SR_API int sr_recognize_batch_multi(sr_model* const* models, sr_lexicon* const* 
  * builds `sil w1 sil ... sil`, Training.cpp:239-253).  Requires 1 <= N_u <= T_u (the reference
  * indexes T-sized cost arrays by position).  out_states[total_frames] receives
  * AlignmentItem::state per frame (count = 1, weight = 1 implied, Alignment.cpp:131-134);
- * out_cost[n_utts] the returned path cost. */
+ * out_cost[n_utts] the returned path cost.  Limits: N_u <= 8192 (SR_ELIMIT; 18 bytes per position in the
+ * 160 KiB LDS).  An utterance with no path of finite cost (emission costs or penalties of +inf) gets
+ * that cost (+inf, or NaN) and, from the frame at which the reference's back-trace would leave the
+ * cells it has computed, the position the walk stands on. */
 SR_API int sr_align_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off,
                     const double tdp[3], uint16_t silence_state, int gmm_kernel,
                     uint16_t* out_states, double* out_cost);
 
 /* Aligner::align_sequence_pruned (Alignment.cpp:149-288): beam `pruning_threshold` on the per-frame
- * best, transition penalty keyed on the destination state, ends at the highest position reached. */
+ * best, transition penalty keyed on the destination state, ends at the highest position reached.
+ * pruning_threshold must not be negative (SR_EINVAL): a negative beam prunes a frame's best node with
+ * the others and leaves the back-trace nothing to follow, in the reference as here.  -0.0, +inf and NaN
+ * are legal (they prune strict losers only, or nothing).  N_u > T_u is allowed.  Limits: N_u <= 8189
+ * (SR_ELIMIT; 20 bytes per position and 48 more in the 160 KiB LDS, where sr_align_corpus and the
+ * forward-backward passes take 8192). */
 SR_API int sr_align_corpus_pruned(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off,
                            const double tdp[3], uint16_t silence_state, double pruning_threshold, int gmm_kernel,
                            uint16_t* out_states, double* out_cost);
@@ -1128,6 +1136,29 @@ SR_API int sr_recognize_corpus_scores(sr_model* m, sr_corpus* c, sr_lexicon* l, 
 SR_API int sr_recognize_bigram_corpus_scores(sr_model* m, sr_corpus* c, sr_bigram* b, const sr_bigram_params* p, const double* scores,
                                              uint64_t n_scores, uint32_t* out_word, float* out_score, uint32_t* out_time,
                                              uint64_t* out_off);
+
+/* Test hook: the forced aligners alone on a score table the caller supplies: sr_align_corpus' (pruned 0) or sr_align_corpus_pruned's
+ * (pruned 1; SR_EINVAL for another value) pass -- the same checks and limits, chunks, utterance order and launches -- except that a
+ * chunk's score step copies rows [f0, f1) of `scores` into the chunk's table (row stride: n_states rounded up to 8, the padding columns
+ * +inf).  scores: host, [total_frames x n_states] row-major; n_scores == total_frames * n_states or SR_EINVAL.  Entries: any finite
+ * value and +inf are valid.  NaN and -inf are no emission costs, but the aligners define what they do with them: the comparisons of the
+ * reference (Alignment.cpp) in the reference's order, so the result is the oracle's on the same table, bit for bit (a NaN compares
+ * false and stays where the loop transition carries it; -inf wins every comparison and -inf + inf is NaN).  pruning_threshold is
+ * ignored with pruned 0.  The corpus's features are never read. */
+SR_API int sr_align_corpus_scores(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
+                                  uint16_t silence_state, int pruned, double pruning_threshold, const double* scores,
+                                  uint64_t n_scores, uint16_t* out_states, double* out_cost);
+/* Test hook: the forward-backward pass alone on a score table the caller supplies: sr_state_posteriors_corpus' pass -- the same
+ * checks, chunks, launch groups (SRGPU_FB_MB), block sizes, item path and outputs -- with the score step replaced as above.  Entries:
+ * any finite value and +inf are valid.  A NaN entry counts as +inf (the cell is on no path); a -inf entry takes every path through
+ * its cell to -inf.  An utterance whose F_u is not finite (+inf: no path; -inf or NaN from such entries) returns F_u as computed and
+ * no items; no weight returned is NaN or exceeds 1 by more than rounding, and the other utterances of the call are unaffected.  The
+ * production passes (sr_state_posteriors_corpus, sr_baum_welch_corpus and the adaptation statistics over them) run the same kernels,
+ * so the same holds for a model whose scores overflow. */
+SR_API int sr_state_posteriors_corpus_scores(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off,
+                                             const double tdp[3], uint16_t silence_state, const double* scores, uint64_t n_scores,
+                                             double posterior_floor, uint32_t max_items, double* out_cost, uint16_t* out_count,
+                                             uint16_t* out_state, double* out_weight);
 
 /* ---- measurement --------------------------------------------------------------------------------
  * When enabled, every kernel launch of this model handle is bracketed by HIP events on the

@@ -439,7 +439,10 @@ double orc_align_full(const orc_model* m, const double* dense, size_t dense_stri
   if (N < 1 || T < 1 || N > T) { set_err("align_full requires 1 <= N <= T"); return NAN; }
   const int Ti = (int)T, Ni = (int)N;
   int* bp = (int*)malloc(sizeof(int) * N * T); /* [state][frame], Alignment.cpp:54-60 */
-  for (size_t i = 0; i < N * T; i++) bp[i] = -1;
+  /* The reference leaves the cells outside a frame's window unset, and its back-trace reads them when the path it follows costs
+   * +inf or NaN (a finite cell has a finite predecessor inside the window; a forbidden one loops in place until the window has
+   * moved past it).  Specified here, and in align_full_kernel: from such a cell the walk stays at its position. */
+  for (size_t i = 0; i < N * T; i++) bp[i] = (int)(i / T);
   double* prev = (double*)malloc(sizeof(double) * T);
   double* cur = (double*)malloc(sizeof(double) * T);
   for (size_t i = 0; i < T; i++) prev[i] = cur[i] = INFINITY;

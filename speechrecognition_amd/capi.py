@@ -53,6 +53,7 @@ SYMBOLS = [
     "sr_probe_fp16_denormals", "sr_probe_fp16_accumulation", "sr_prefilter_masks", "sr_prefilter_range_frames",
     "sr_refine_masks", "sr_refine_geometry",
     "sr_gather_words", "sr_recognize_corpus_scores", "sr_recognize_bigram_corpus_scores", "sr_bigram_route",
+    "sr_align_corpus_scores", "sr_state_posteriors_corpus_scores",
     "sr_profile_enable", "sr_profile_reset", "sr_profile_read",
 ]
 
@@ -207,6 +208,8 @@ def lib():
         L.sr_recognize_bigram_corpus_scores.argtypes = [vp, vp, vp, C.POINTER(BigramParams), vp, u64, vp, vp, vp, vp]
         L.sr_bigram_route.argtypes = [vp, u32, C.c_char_p, C.c_size_t]
         L.sr_recognize_corpus_scores.argtypes = [vp, vp, vp, C.POINTER(SearchParams), vp, u64, i32, vp, vp, vp, vp, vp, vp]
+        L.sr_align_corpus_scores.argtypes = [vp, vp, vp, vp, C.POINTER(dbl * 3), C.c_uint16, i32, dbl, vp, u64, vp, vp]
+        L.sr_state_posteriors_corpus_scores.argtypes = [vp, vp, vp, vp, C.POINTER(dbl * 3), C.c_uint16, vp, u64, dbl, u32, vp, vp, vp, vp]
         L.sr_profile_enable.argtypes = [vp, i32]
         L.sr_profile_reset.argtypes = [vp]
         L.sr_profile_read.argtypes = [vp, C.POINTER(Profile)]
@@ -708,6 +711,20 @@ class Corpus:
                                                 float(pruning_threshold), kernel, _ptr(states), _ptr(cost)))
         return states[: self.n_frames], cost[: self.n_utts]
 
+    def align_scores(self, automata, tdp, silence_state, scores, pruning_threshold=None):
+        """sr_align_corpus_scores (test hook): align() on the caller's score table [n_frames, n_states] (the corpus's features are not
+        read); pruning_threshold None: the full aligner -> (states u16[total_frames], cost f64[n_utts])"""
+        flat, off = self._aut(automata)
+        scores = np.ascontiguousarray(scores, dtype=np.float64)
+        states = np.zeros(max(self.n_frames, 1), dtype=np.uint16)
+        cost = np.zeros(max(self.n_utts, 1), dtype=np.float64)
+        t3 = (C.c_double * 3)(*tdp)
+        pruned = pruning_threshold is not None
+        _check(lib().sr_align_corpus_scores(self.model.h, self.h, _ptr(flat), _ptr(off), C.byref(t3), silence_state, int(pruned),
+                                            float(pruning_threshold) if pruned else 0.0, _ptr(scores), scores.size, _ptr(states),
+                                            _ptr(cost)))
+        return states[: self.n_frames], cost[: self.n_utts]
+
     def accumulate_on_device(self, states, first_pass=False, max_approx=True):
         """The same, but the statistics stay in this corpus handle on the device (for next_model())."""
         states = np.ascontiguousarray(states, dtype=np.uint16)
@@ -744,6 +761,22 @@ class Corpus:
         t3 = (C.c_double * 3)(*tdp)
         _check(lib().sr_state_posteriors_corpus(self.model.h, self.h, _ptr(flat), _ptr(off), C.byref(t3), silence_state, kernel, float(floor),
                                                 int(max_items), _ptr(cost), _ptr(count), _ptr(state), _ptr(weight)))
+        n = self.n_frames
+        return cost[: self.n_utts], count[:n], state[:n], weight[:n]
+
+    def state_posteriors_scores(self, automata, tdp, silence_state, scores, floor=0.0, max_items=8):
+        """sr_state_posteriors_corpus_scores (test hook): state_posteriors() on the caller's score table [n_frames, n_states]"""
+        flat, off = self._aut(automata)
+        scores = np.ascontiguousarray(scores, dtype=np.float64)
+        F = max(self.n_frames, 1)
+        cost = np.zeros(max(self.n_utts, 1), dtype=np.float64)
+        count = np.zeros(F, dtype=np.uint16)
+        state = np.zeros((F, max(int(max_items), 1)), dtype=np.uint16)
+        weight = np.zeros((F, max(int(max_items), 1)), dtype=np.float64)
+        t3 = (C.c_double * 3)(*tdp)
+        _check(lib().sr_state_posteriors_corpus_scores(self.model.h, self.h, _ptr(flat), _ptr(off), C.byref(t3), silence_state, _ptr(scores),
+                                                       scores.size, float(floor), int(max_items), _ptr(cost), _ptr(count), _ptr(state),
+                                                       _ptr(weight)))
         n = self.n_frames
         return cost[: self.n_utts], count[:n], state[:n], weight[:n]
 

@@ -44,6 +44,11 @@ inline uint32_t max_positions(const Group& g, const uint64_t* off) {
   return mx;
 }
 
+// The threads of a forward-backward launch over the aligner's automata (viterbi_fb.hip) whose longest automaton has max_positions
+// positions: one wave while every position has a lane of its own, else four -- a barrier of one wave costs nothing, and at 65
+// positions a second wave already pays for itself.  (The kernels stride positions over whatever block they get: the same bits.)
+inline uint32_t fb_block_threads(uint32_t max_positions) { return max_positions <= 64 ? 64u : 256u; }
+
 // cost[u] = per_frame * frame_off[u] + u * per_utt
 inline std::vector<uint64_t> linear_cost(const uint64_t* frame_off, uint32_t U, uint64_t per_frame, uint64_t per_utt = 0) {
   std::vector<uint64_t> cost(U + 1);

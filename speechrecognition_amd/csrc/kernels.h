@@ -356,6 +356,17 @@ struct AlignArgs {
 hipError_t launch_align_full(const AlignArgs& a, hipStream_t stream);
 hipError_t launch_align_pruned(const AlignArgs& a, hipStream_t stream);
 uint32_t align_max_positions();
+// The LDS bytes of an aligner launch whose longest automaton has max_positions positions -- the kernels' layouts: cost[2][N] f64 and
+// ref[N] u16; the pruned kernel's alive[2][N] u8 and red[4] f64 beside them; 16 for the alignment of the base -- against the 160 KiB
+// a workgroup can have (gfx950).  The launchers size their launches with these, align_common refuses what does not fit.
+constexpr size_t kAlignLdsLimit = 160 * 1024;
+constexpr size_t align_full_lds_bytes(uint32_t max_positions) { return (size_t)max_positions * (2 * 8 + 2) + 16; }
+constexpr size_t align_pruned_lds_bytes(uint32_t max_positions) { return (size_t)max_positions * (2 * 8 + 2 + 2) + 4 * 8 + 16; }
+constexpr uint32_t kAlignMaxPositions = 8192;        // align_max_positions(): sr_align_corpus, the forward-backward passes
+constexpr uint32_t kAlignPrunedMaxPositions = 8189;  // sr_align_corpus_pruned: 20 bytes a position
+static_assert(align_full_lds_bytes(kAlignMaxPositions) <= kAlignLdsLimit, "align_full_kernel at the position limit");
+static_assert(align_pruned_lds_bytes(kAlignPrunedMaxPositions) <= kAlignLdsLimit &&
+              align_pruned_lds_bytes(kAlignPrunedMaxPositions + 1) > kAlignLdsLimit, "align_pruned_kernel at the position limit");
 
 // ---- forward-backward over the aligner's automata and topology (viterbi_fb.hip) --------------------------------------
 // A launch covers utterances [utt_first, utt_first + n_utts) of one score chunk whose trellises fit the workspace together.

@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <map>
 #include <memory>
@@ -1868,12 +1869,55 @@ static int check_automaton(const sr_model* m, const uint16_t* automata, const ui
   return SR_OK;
 }
 
+// The score step of an automaton pass (align_common, fb_pass): score(scoring, chunk, table) enqueues the chunk's scores on m->s_gmm --
+// automaton_scoring_chunk for every production pass; the test hooks sr_align_corpus_scores / sr_state_posteriors_corpus_scores copy
+// the caller's rows instead (ScoreTable below).
+static auto model_scores(sr_model* m, sr_corpus* c) {
+  return [m, c](const AutomatonScoring& sc, const Chunk& ch, double* table) -> int { return automaton_scoring_chunk(m, c, sc, ch, table); };
+}
+
+// A caller's score table [F x n_states] as the hooks' score step: the rows padded to the chunk tables' stride m->ld with +inf, the
+// whole table once, so that a chunk is one copy.
+struct ScoreTable {
+  sr_model* m = nullptr;
+  std::vector<double> padded;
+  int set(sr_model* model, const sr_corpus* c, const double* scores, uint64_t n_scores) {
+    m = model;
+    const uint64_t F = c->n_frames;
+    const size_t S = m->n_states, ld = m->ld;
+    if (n_scores != F * S)
+      return fail(SR_EINVAL, "%llu scores for %llu frames x %u states", (unsigned long long)n_scores, (unsigned long long)F, m->n_states);
+    if (!scores && F) return fail(SR_EINVAL, "null argument");
+    padded.assign((size_t)F * ld, std::numeric_limits<double>::infinity());
+    for (uint64_t t = 0; t < F; t++) memcpy(padded.data() + t * ld, scores + t * S, sizeof(double) * S);
+    return SR_OK;
+  }
+  int operator()(const AutomatonScoring&, const Chunk& ch, double* table) const {
+    if (ch.f1 > ch.f0)
+      HIP_TRY(hipMemcpyAsync(table, padded.data() + ch.f0 * m->ld, sizeof(double) * (ch.f1 - ch.f0) * m->ld, hipMemcpyHostToDevice, m->s_gmm));
+    return SR_OK;
+  }
+  // after a pass over the table, failed or not: no copy still reads `padded`
+  int done(int rc) const {
+    const hipError_t e = hipStreamSynchronize(m->s_gmm);
+    if (rc) return rc;
+    HIP_TRY(e);
+    return SR_OK;
+  }
+};
+
+template <class Score>
 static int align_common(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
-                        uint16_t silence_state, double thr, bool pruned, int gmm_kernel, uint16_t* out_states,
+                        uint16_t silence_state, double thr, bool pruned, int gmm_kernel, Score score, uint16_t* out_states,
                         double* out_cost) {
   int rc = check_corpus(m, c);
   if (rc) return rc;
   if (!automata || !aut_off || !tdp || !out_states || !out_cost) return fail(SR_EINVAL, "null argument");
+  // (a negative threshold prunes a frame's best node with the rest: no node is left, and neither the kernel's nor the reference's
+  // back-trace has anything to follow; -0.0, +inf and NaN prune nothing or strict losers only)
+  if (pruned && thr < 0.0) return fail(SR_EINVAL, "pruning_threshold must not be negative (got %g)", thr);
+  const uint32_t max_pos = pruned ? kAlignPrunedMaxPositions : kAlignMaxPositions;
+  static_assert(kAlignPrunedMaxPositions <= kAlignMaxPositions, "");
   const uint32_t U = c->n_utts;
   const uint64_t F = c->n_frames;
   std::vector<uint64_t> bp_off(U + 1, 0);
@@ -1884,7 +1928,9 @@ static int align_common(sr_model* m, sr_corpus* c, const uint16_t* automata, con
     if (!pruned && N > T)
       return fail(SR_EINVAL, "utterance %u: automaton length %llu exceeds %llu frames (Aligner::align_sequence_full indexes "
                   "its T-sized cost arrays by position)", u, (unsigned long long)N, (unsigned long long)T);
-    if (N > align_max_positions()) return fail(SR_ELIMIT, "utterance %u: automaton length %llu exceeds %u", u, (unsigned long long)N, align_max_positions());
+    if (N > max_pos)
+      return fail(SR_ELIMIT, "utterance %u: automaton length %llu exceeds %u%s", u, (unsigned long long)N, max_pos,
+                  pruned ? " (the pruned aligner keeps 20 bytes per position in the 160 KiB LDS)" : "");
     if ((rc = check_automaton(m, automata, aut_off, u))) return rc;
     max_n = std::max<uint32_t>(max_n, (uint32_t)N);
     bp_off[u + 1] = bp_off[u] + N * T;
@@ -1901,7 +1947,7 @@ static int align_common(sr_model* m, sr_corpus* c, const uint16_t* automata, con
   aa.pruning_threshold = thr; aa.backptr = c->backptr.p; aa.bp_off = c->bp_off.p; aa.max_positions = max_n;
   aa.out_states = c->out_states.p; aa.out_cost = c->out_cost.p;
   rc = run_chunks(m, sc.chunks,
-      [&](const Chunk& ch, double* table) -> int { return automaton_scoring_chunk(m, c, sc, ch, table); },
+      [&](const Chunk& ch, double* table) -> int { return score(sc, ch, table); },
       [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
         aa.scores = table; aa.frame_base = ch.f0; aa.utt_first = ch.u0; aa.n_utts = ch.u1 - ch.u0;
         HIP_TRY(pruned ? launch_align_pruned(aa, s) : launch_align_full(aa, s));
@@ -1920,7 +1966,7 @@ static int align_common(sr_model* m, sr_corpus* c, const uint16_t* automata, con
 int sr_align_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
                     uint16_t silence_state, int gmm_kernel, uint16_t* out_states, double* out_cost) {
   return guarded(__func__, [&]() -> int {
-  return align_common(m, c, automata, aut_off, tdp, silence_state, 0.0, false, gmm_kernel, out_states, out_cost);
+  return align_common(m, c, automata, aut_off, tdp, silence_state, 0.0, false, gmm_kernel, model_scores(m, c), out_states, out_cost);
   });
 }
 
@@ -1928,7 +1974,24 @@ int sr_align_corpus_pruned(sr_model* m, sr_corpus* c, const uint16_t* automata, 
                            const double tdp[3], uint16_t silence_state, double pruning_threshold, int gmm_kernel,
                            uint16_t* out_states, double* out_cost) {
   return guarded(__func__, [&]() -> int {
-  return align_common(m, c, automata, aut_off, tdp, silence_state, pruning_threshold, true, gmm_kernel, out_states, out_cost);
+  return align_common(m, c, automata, aut_off, tdp, silence_state, pruning_threshold, true, gmm_kernel, model_scores(m, c), out_states,
+                      out_cost);
+  });
+}
+
+// test hook: sr_align_corpus / sr_align_corpus_pruned with the chunk's score step replaced by a copy of the caller's rows
+int sr_align_corpus_scores(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
+                           uint16_t silence_state, int pruned, double pruning_threshold, const double* scores, uint64_t n_scores,
+                           uint16_t* out_states, double* out_cost) {
+  return guarded(__func__, [&]() -> int {
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  if (pruned != 0 && pruned != 1) return fail(SR_EINVAL, "pruned must be 0 or 1");
+  ScoreTable table;
+  if ((rc = table.set(m, c, scores, n_scores))) return rc;
+  // (SR_GMM_MFMA: no listed tables to set up for scores nobody computes)
+  return table.done(align_common(m, c, automata, aut_off, tdp, silence_state, pruned ? pruning_threshold : 0.0, pruned != 0, SR_GMM_MFMA,
+                                 std::cref(table), out_states, out_cost));
   });
 }
 
@@ -2254,8 +2317,9 @@ static int fb_check(sr_model* m, sr_corpus* c, const uint16_t* automata, const u
 // One pass over the corpus on the aligner's scoring chunks; inside a chunk, consecutive utterances whose trellises fit m->fb_budget
 // together (8 B per frame and position) run forward, backward and -- want_items -- the posterior items.  Leaves F_u in c->out_cost
 // and, with want_items, *n_items items in c->fb_item_* (frame order, ascending mixture id) with c->fb_item_off[F + 1].
+template <class Score>
 static int fb_pass(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
-                   uint16_t silence_state, int gmm_kernel, double posterior_floor, bool want_items, uint64_t* n_items) {
+                   uint16_t silence_state, int gmm_kernel, double posterior_floor, bool want_items, uint64_t* n_items, Score score) {
   const uint32_t U = c->n_utts;
   const uint64_t F = c->n_frames;
   *n_items = 0;
@@ -2290,7 +2354,7 @@ static int fb_pass(sr_model* m, sr_corpus* c, const uint16_t* automata, const ui
   ia.trellis_off = c->fb_trellis_off.p; ia.chain_off = c->aut_off.p; ia.mix_off = c->fb_mix_off.p; ia.by_frame = true;
   size_t ci = 0;  // run_chunks searches the chunks in order
   rc = run_chunks(m, sc.chunks,
-      [&](const Chunk& ch, double* table) -> int { return automaton_scoring_chunk(m, c, sc, ch, table); },
+      [&](const Chunk& ch, double* table) -> int { return score(sc, ch, table); },
       [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
         if (want_items && ci == 0) HIP_TRY(reset_item_count(c->fb_base, s));
         for (const Group& g : groups.of_chunk[ci]) {
@@ -2315,19 +2379,49 @@ static int fb_pass(sr_model* m, sr_corpus* c, const uint16_t* automata, const ui
   return SR_OK;
 }
 
-int sr_state_posteriors_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
-                               uint16_t silence_state, int gmm_kernel, double posterior_floor, uint32_t max_items, double* out_cost,
-                               uint16_t* out_count, uint16_t* out_state, double* out_weight) {
-  return guarded(__func__, [&]() -> int {
+// ... with the model's scores, as every production pass takes it
+static int fb_pass(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
+                   uint16_t silence_state, int gmm_kernel, double posterior_floor, bool want_items, uint64_t* n_items) {
+  return fb_pass(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, want_items, n_items, model_scores(m, c));
+}
+
+// sr_state_posteriors_corpus and its test hook: the checks, the pass on `score`'s scores, F_u and the top items to the host
+template <class Score>
+static int state_posteriors(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
+                            uint16_t silence_state, int gmm_kernel, double posterior_floor, uint32_t max_items, Score score,
+                            double* out_cost, uint16_t* out_count, uint16_t* out_state, double* out_weight) {
   int rc = fb_check(m, c, automata, aut_off, tdp, posterior_floor, out_cost);
   if (rc) return rc;
   bool post = false;
   if ((rc = top_items_arguments(out_count, out_state, out_weight, "out_state", max_items, &post))) return rc;
   const uint32_t U = c->n_utts;
   uint64_t n_items = 0;
-  if ((rc = fb_pass(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, post, &n_items))) return rc;
+  if ((rc = fb_pass(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, post, &n_items, score))) return rc;
   if (U) HIP_TRY(hipMemcpy(out_cost, c->out_cost.p, sizeof(double) * U, hipMemcpyDeviceToHost));
   return post ? top_of_items(m, c, max_items, out_count, out_state, out_weight) : SR_OK;
+}
+
+int sr_state_posteriors_corpus(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
+                               uint16_t silence_state, int gmm_kernel, double posterior_floor, uint32_t max_items, double* out_cost,
+                               uint16_t* out_count, uint16_t* out_state, double* out_weight) {
+  return guarded(__func__, [&]() -> int {
+  return state_posteriors(m, c, automata, aut_off, tdp, silence_state, gmm_kernel, posterior_floor, max_items, model_scores(m, c), out_cost,
+                          out_count, out_state, out_weight);
+  });
+}
+
+// test hook: sr_state_posteriors_corpus with the chunk's score step replaced by a copy of the caller's rows
+int sr_state_posteriors_corpus_scores(sr_model* m, sr_corpus* c, const uint16_t* automata, const uint64_t* aut_off, const double tdp[3],
+                                      uint16_t silence_state, const double* scores, uint64_t n_scores, double posterior_floor,
+                                      uint32_t max_items, double* out_cost, uint16_t* out_count, uint16_t* out_state,
+                                      double* out_weight) {
+  return guarded(__func__, [&]() -> int {
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  ScoreTable table;
+  if ((rc = table.set(m, c, scores, n_scores))) return rc;
+  return table.done(state_posteriors(m, c, automata, aut_off, tdp, silence_state, SR_GMM_MFMA, posterior_floor, max_items, std::cref(table),
+                                     out_cost, out_count, out_state, out_weight));
   });
 }
 

@@ -87,7 +87,10 @@ __global__ __launch_bounds__(kAlignThreads) void align_full_kernel(AlignArgs a) 
     int si = N - 1;
     for (int t = T - 1; t >= 0; t--) {  // :129-138
       out[t] = ref[si];
-      if (t > 0) si -= (int)__hip_atomic_load(&bp[(size_t)t * N + si], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      // Only a path of cost +inf or NaN leaves the window (a finite cell has a finite predecessor, and those lie inside): no back
+      // pointer was written there and the reference reads an unset one, so the walk stays at its position from there on.
+      const int lo = N - 1 - 2 * (T - 1 - t), hi = (N - 1 < 2 * t) ? N - 1 : 2 * t;
+      if (t > 0 && si >= lo && si <= hi) si -= (int)__hip_atomic_load(&bp[(size_t)t * N + si], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
 }
@@ -194,11 +197,12 @@ hipError_t launch_path_scores(const double* scores, uint32_t ld, uint64_t frame_
   return hipGetLastError();
 }
 
-uint32_t align_max_positions() { return 8192; }
+uint32_t align_max_positions() { return kAlignMaxPositions; }
 
 hipError_t launch_align_full(const AlignArgs& a, hipStream_t stream) {
   if (a.n_utts == 0) return hipSuccess;
-  const size_t smem = (size_t)a.max_positions * (2 * 8 + 2) + 16;
+  const size_t smem = align_full_lds_bytes(a.max_positions);
+  if (smem > kAlignLdsLimit) return hipErrorInvalidValue;
   hipError_t e = hipFuncSetAttribute((const void*)align_full_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(align_full_kernel, dim3(a.n_utts), dim3(kAlignThreads), smem, stream, a);
@@ -207,7 +211,8 @@ hipError_t launch_align_full(const AlignArgs& a, hipStream_t stream) {
 
 hipError_t launch_align_pruned(const AlignArgs& a, hipStream_t stream) {
   if (a.n_utts == 0) return hipSuccess;
-  const size_t smem = (size_t)a.max_positions * (2 * 8 + 2 + 2) + 4 * 8 + 16;
+  const size_t smem = align_pruned_lds_bytes(a.max_positions);
+  if (smem > kAlignLdsLimit) return hipErrorInvalidValue;
   hipError_t e = hipFuncSetAttribute((const void*)align_pruned_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(align_pruned_kernel, dim3(a.n_utts), dim3(kAlignThreads), smem, stream, a);

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fb_plan.h"
 #include "kernels.h"
 
 namespace srgpu {
@@ -28,11 +29,18 @@ __device__ inline double fb_tdp(uint32_t from, int jump, uint32_t sil, double tl
 
 // -log(exp(-a) + exp(-b) + exp(-c))
 __device__ inline double logadd3(double a, double b, double c) {
+  // A NaN cost (a NaN emission: outside the contract, but it must not leak) counts as +inf wherever it stands, so that alpha and beta
+  // leave out the same paths: the ordering below would drop a NaN in `a` alone but the finite terms beside a NaN in `c`, and the
+  // posteriors of a frame would then add up to more than 1.
+  a = a < kInf ? a : kInf;
+  b = b < kInf ? b : kInf;
+  c = c < kInf ? c : kInf;
   double m, x, y;
   if (a <= b && a <= c) { m = a; x = b; y = c; }
   else if (b <= c) { m = b; x = a; y = c; }
   else { m = c; x = a; y = b; }
   if (!(m < kInf)) return kInf;
+  if (!(m > -kInf)) return m;  // (a -inf emission, as little in the contract: it takes every path through it, and F_u, to -inf)
   double s = 0.0;
   if (x < kInf) s += exp(m - x);
   if (y < kInf) s += exp(m - y);
@@ -108,7 +116,7 @@ __global__ __launch_bounds__(kFbThreads) void fb_backward_kernel(FbArgs a) {
   const uint32_t sil = a.silence_state;
   const double tl = a.tdp_loop, tf = a.tdp_forward, ts = a.tdp_skip;
   const double F = a.out_cost[u];
-  const bool dead = !(F < kInf);  // no complete path: every posterior is 0
+  const bool dead = !(F < kInf && F > -kInf);  // no complete path (or a NaN or -inf emission took F along): every posterior is 0
 
   for (int s = tid; s < N; s += nt) {
     ref[s] = ref_g[s];
@@ -153,7 +161,8 @@ __global__ __launch_bounds__(kFbThreads) void fb_backward_kernel(FbArgs a) {
   }
 }
 
-static uint32_t fb_block(uint32_t max_positions) { return max_positions <= 64 ? 64u : (uint32_t)kFbThreads; }
+static_assert(kFbThreads == 256, "srplan::fb_block_threads' larger block is the kernels' launch bound");
+static uint32_t fb_block(uint32_t max_positions) { return srplan::fb_block_threads(max_positions); }
 
 hipError_t launch_fb_forward(const FbArgs& a, hipStream_t stream) {
   if (a.n_utts == 0) return hipSuccess;

@@ -11,6 +11,8 @@
 //        all of them as one group; over chain_off, or over frame_off for the free network)
 //   seg <n_ranges> <L>  bounds[n_ranges + 1]
 //     -> "begin ...", "len ...", "off ..."
+//   block <n>  max_positions[n]
+//     -> "threads ..." (fb_block_threads of each)
 #include <cstdio>
 #include <fstream>
 #include <string>
@@ -135,6 +137,14 @@ int main(int argc, char** argv) {
       ok = width == 16 ? occ_case<uint16_t>(in, chain != 0, lists != 0, U, P) : occ_case<uint32_t>(in, chain != 0, lists != 0, U, P);
     } else if (op == "seg") {
       ok = seg_case(in);
+    } else if (op == "block") {
+      size_t n = 0;
+      in >> n;
+      std::vector<uint32_t> v(n);
+      for (auto& x : v) in >> x;
+      ok = (bool)in;
+      for (auto& x : v) x = srplan::fb_block_threads(x);
+      line("threads", v);
     }
     if (!ok) { fprintf(stderr, "bad case file\n"); return 2; }
     printf("end\n");

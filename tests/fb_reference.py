@@ -4,7 +4,10 @@ pyoracle.Oracle.score_matrix, so the reference never touches the GPU.
 
 Topology (align_full's): s_0 = 0, s_{T-1} = N-1, s_t - s_{t-1} in {0, 1, 2}; the transition penalty is keyed on the SOURCE
 position's state, and any jump out of silence costs `forward`.  With semiring="min" the same recursion is the Viterbi
-alignment (ties: loop before forward before skip, as the aligner's strict `<`)."""
+alignment (ties: loop before forward before skip, as the aligner's strict `<`).
+
+The recursions take a `dtype` (default float64, the kernels' own precision): with np.longdouble (x87: 64 bits of mantissa) the same
+recursion is the yardstick the float64 one, and the kernels, are measured against (tests/test_gpu_fb_scores.py)."""
 from __future__ import annotations
 
 import numpy as np
@@ -12,10 +15,10 @@ import numpy as np
 INF = np.inf
 
 
-def _jump_costs(ref, tdp, sil):
+def _jump_costs(ref, tdp, sil, dtype=np.float64):
     """c[j, s]: penalty of jump j out of position s."""
     ref = np.asarray(ref)
-    c = np.empty((3, len(ref)))
+    c = np.empty((3, len(ref)), dtype=dtype)
     for j in range(3):
         c[j] = tdp[j]
     c[:, ref == sil] = tdp[1]
@@ -39,12 +42,12 @@ def _ladd(*xs):
     return -acc
 
 
-def forward(e, ref, tdp, sil, semiring="log"):
+def forward(e, ref, tdp, sil, semiring="log", dtype=np.float64):
     """alpha [T, N] (and, for semiring="min", the taken jumps [T, N])."""
-    E = np.asarray(e, dtype=np.float64)[:, np.asarray(ref, dtype=np.int64)]
+    E = np.asarray(e)[:, np.asarray(ref, dtype=np.int64)].astype(dtype)
     T, N = E.shape
-    c = _jump_costs(ref, tdp, sil)
-    A = np.full((T, N), INF)
+    c = _jump_costs(ref, tdp, sil, dtype)
+    A = np.full((T, N), INF, dtype=dtype)
     bp = np.zeros((T, N), dtype=np.int64)
     A[0, 0] = E[0, 0]
     for t in range(1, T):
@@ -72,17 +75,17 @@ def viterbi(e, ref, tdp, sil):
     return out, float(A[T - 1, N - 1])
 
 
-def backward(e, ref, tdp, sil):
-    E = np.asarray(e, dtype=np.float64)[:, np.asarray(ref, dtype=np.int64)]
+def backward(e, ref, tdp, sil, dtype=np.float64):
+    E = np.asarray(e)[:, np.asarray(ref, dtype=np.int64)].astype(dtype)
     T, N = E.shape
-    c = _jump_costs(ref, tdp, sil)
-    B = np.full((T, N), INF)
+    c = _jump_costs(ref, tdp, sil, dtype)
+    B = np.full((T, N), INF, dtype=dtype)
     B[T - 1, N - 1] = 0.0
     for t in range(T - 2, -1, -1):
         nxt = E[t + 1] + B[t + 1]
         cand = []
         for j in range(3):
-            v = np.full(N, INF)
+            v = np.full(N, INF, dtype=dtype)
             if j < N:
                 v[: N - j] = nxt[j:]
             cand.append(c[j] + v)
@@ -90,12 +93,12 @@ def backward(e, ref, tdp, sil):
     return B
 
 
-def posteriors(e, ref, tdp, sil):
-    """-> (F = -log P(X | automaton), gamma [T, N] per position)."""
-    A = forward(e, ref, tdp, sil)
-    B = backward(e, ref, tdp, sil)
+def posteriors(e, ref, tdp, sil, dtype=np.float64):
+    """-> (F = -log P(X | automaton), gamma [T, N] per position); F a Python float for float64, else a scalar of dtype."""
+    A = forward(e, ref, tdp, sil, dtype=dtype)
+    B = backward(e, ref, tdp, sil, dtype=dtype)
     T, N = A.shape
-    F = float(A[T - 1, N - 1])
+    F = float(A[T - 1, N - 1]) if dtype is np.float64 else A[T - 1, N - 1]
     with np.errstate(invalid="ignore", over="ignore"):
         g = np.exp(F - (A + B)) if np.isfinite(F) else np.zeros_like(A)
     g[~np.isfinite(A + B)] = 0.0
@@ -106,7 +109,7 @@ def mixture_posteriors(gamma, ref):
     """-> (mixtures ascending, [T, M] posterior per distinct mixture of the automaton)."""
     ref = np.asarray(ref, dtype=np.int64)
     mix = np.unique(ref)
-    out = np.zeros((gamma.shape[0], len(mix)))
+    out = np.zeros((gamma.shape[0], len(mix)), dtype=gamma.dtype)
     for j, k in enumerate(mix):
         out[:, j] = gamma[:, ref == k].sum(axis=1)
     return mix, out

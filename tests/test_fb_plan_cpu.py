@@ -253,6 +253,13 @@ def test_header_segments(driver, tmp_path):
             b0 += n
 
 
+def test_header_forward_backward_block(driver, tmp_path):
+    """one wave up to 64 positions, 256 threads from 65 on (tests/test_gpu_fb_scores.py runs 64 and 65 positions, alone and together)"""
+    ns = [1, 2, 63, 64, 65, 66, 127, 128, 129, 255, 256, 257, 600, 8192]
+    (a,), = run_cases(driver, tmp_path, [["block", len(ns)] + ns])
+    assert a == ("threads", [64 if n <= 64 else 256 for n in ns])
+
+
 def test_header_has_no_device_include():
     src = open(os.path.join(ROOT, "speechrecognition_amd", "csrc", "fb_plan.h")).read()
     assert "#include <hip" not in src and "handles.h" not in src
