@@ -1160,6 +1160,32 @@ SR_API int sr_state_posteriors_corpus_scores(sr_model* m, sr_corpus* c, const ui
                                              double posterior_floor, uint32_t max_items, double* out_cost, uint16_t* out_count,
                                              uint16_t* out_state, double* out_weight);
 
+/* Test hooks: the forward-backward passes over the recognition network alone on a score table the caller supplies:
+ * sr_word_posteriors_corpus', sr_net_occupancies_corpus' (the free network, or the transcripts' chains with trans / trans_off) and
+ * sr_net_accuracies_corpus' pass -- the same checks, chunks, launch groups (SRGPU_FB_MB), block sizes, item path and outputs -- except
+ * that a chunk's score step copies rows [f0, f1) of `scores` into the chunk's table (row stride: n_states rounded up to 8, the padding
+ * columns +inf).  scores: host, [total_frames x n_states] row-major; n_scores == total_frames * n_states or SR_EINVAL.  The corpus's
+ * features are never read and p->gmm_kernel is ignored.
+ * Entries (the contract of sr_state_posteriors_corpus_scores): any finite value and +inf are valid.  A NaN entry counts as +inf, as an
+ * entry: every path that pays that emission is dead, and paths that pay another emission at the same slot are not (position 1 of a
+ * word: a path entering there pays the word's FIRST state's emission, a path arriving inside the word the slot's own).  A -inf entry
+ * takes every path through it to -inf.  An utterance whose F_u is not finite (+inf: no path; -inf from such entries) returns F_u as
+ * computed and no items, and for the accuracies Abar_u = 0.  No weight returned is NaN; no posterior or occupancy exceeds 1 by more
+ * than rounding, and |gamma| <= T_u.  The other utterances of the call are unaffected.  The production passes
+ * (sr_word_posteriors_corpus, sr_recognize_confidence_corpus, sr_net_occupancies_corpus, sr_mmi_statistics_corpus,
+ * sr_net_accuracies_corpus, sr_smbr_statistics_corpus) run the same kernels, so the same holds for a model whose scores overflow. */
+SR_API int sr_word_posteriors_corpus_scores(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale,
+                                            double posterior_floor, uint32_t max_items, const double* scores, uint64_t n_scores,
+                                            double* out_cost, uint16_t* out_count, uint32_t* out_word, double* out_weight);
+SR_API int sr_net_occupancies_corpus_scores(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale,
+                                            double posterior_floor, uint32_t max_items, const uint32_t* trans, const uint64_t* trans_off,
+                                            const double* scores, uint64_t n_scores, double* out_cost, uint16_t* out_count,
+                                            uint16_t* out_state, double* out_weight);
+SR_API int sr_net_accuracies_corpus_scores(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale,
+                                           double posterior_floor, uint32_t max_items, const uint16_t* ref_states, const double* scores,
+                                           uint64_t n_scores, double* out_cost, double* out_acc, uint16_t* out_count, uint16_t* out_state,
+                                           double* out_weight);
+
 /* ---- measurement --------------------------------------------------------------------------------
  * When enabled, every kernel launch of this model handle is bracketed by HIP events on the
  * launch stream; sr_profile_read() synchronises and returns accumulated device times. */

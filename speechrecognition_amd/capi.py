@@ -54,6 +54,7 @@ SYMBOLS = [
     "sr_refine_masks", "sr_refine_geometry",
     "sr_gather_words", "sr_recognize_corpus_scores", "sr_recognize_bigram_corpus_scores", "sr_bigram_route",
     "sr_align_corpus_scores", "sr_state_posteriors_corpus_scores",
+    "sr_word_posteriors_corpus_scores", "sr_net_occupancies_corpus_scores", "sr_net_accuracies_corpus_scores",
     "sr_profile_enable", "sr_profile_reset", "sr_profile_read",
 ]
 
@@ -210,6 +211,9 @@ def lib():
         L.sr_recognize_corpus_scores.argtypes = [vp, vp, vp, C.POINTER(SearchParams), vp, u64, i32, vp, vp, vp, vp, vp, vp]
         L.sr_align_corpus_scores.argtypes = [vp, vp, vp, vp, C.POINTER(dbl * 3), C.c_uint16, i32, dbl, vp, u64, vp, vp]
         L.sr_state_posteriors_corpus_scores.argtypes = [vp, vp, vp, vp, C.POINTER(dbl * 3), C.c_uint16, vp, u64, dbl, u32, vp, vp, vp, vp]
+        L.sr_word_posteriors_corpus_scores.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, u64, vp, vp, vp, vp]
+        L.sr_net_occupancies_corpus_scores.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, u64, vp, vp, vp, vp]
+        L.sr_net_accuracies_corpus_scores.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, u64, vp, vp, vp, vp, vp]
         L.sr_profile_enable.argtypes = [vp, i32]
         L.sr_profile_reset.argtypes = [vp]
         L.sr_profile_read.argtypes = [vp, C.POINTER(Profile)]
@@ -951,6 +955,15 @@ class Corpus:
         """Forward-backward over the recognition network (sr_word_posteriors_corpus) -> (cost f64[n_utts] = -(1/scale) log P(X),
         count u16[total_frames], word u32[total_frames, max_items], weight f64[total_frames, max_items]): per frame the words with
         posterior >= floor, largest first, at most max_items."""
+        return self._word_posteriors(lexicon, word_penalty, scale, kernel, floor, max_items, None)
+
+    def word_posteriors_scores(self, lexicon, word_penalty, scores, scale=1.0, floor=0.0, max_items=8):
+        """sr_word_posteriors_corpus_scores (test hook): word_posteriors() on the caller's score table [n_frames, n_states] (the
+        corpus's features are not read)"""
+        return self._word_posteriors(lexicon, word_penalty, scale, GMM_PREFILTER, floor, max_items,
+                                     np.ascontiguousarray(scores, dtype=np.float64))
+
+    def _word_posteriors(self, lexicon, word_penalty, scale, kernel, floor, max_items, scores):
         F = max(self.n_frames, 1)
         K = max(int(max_items), 1)
         cost = np.zeros(max(self.n_utts, 1), dtype=np.float64)
@@ -958,8 +971,13 @@ class Corpus:
         word = np.zeros((F, K), dtype=np.uint32)
         weight = np.zeros((F, K), dtype=np.float64)
         sp = SearchParams(np.inf, word_penalty, kernel, 0)
-        _check(lib().sr_word_posteriors_corpus(self.model.h, self.h, lexicon.h, C.byref(sp), float(scale), float(floor), int(max_items),
-                                               _ptr(cost), _ptr(count), _ptr(word), _ptr(weight)))
+        if scores is None:
+            _check(lib().sr_word_posteriors_corpus(self.model.h, self.h, lexicon.h, C.byref(sp), float(scale), float(floor), int(max_items),
+                                                   _ptr(cost), _ptr(count), _ptr(word), _ptr(weight)))
+        else:
+            _check(lib().sr_word_posteriors_corpus_scores(self.model.h, self.h, lexicon.h, C.byref(sp), float(scale), float(floor),
+                                                          int(max_items), _ptr(scores), scores.size, _ptr(cost), _ptr(count), _ptr(word),
+                                                          _ptr(weight)))
         n = self.n_frames
         return cost[: self.n_utts], count[:n], word[:n], weight[:n]
 
@@ -976,6 +994,14 @@ class Corpus:
         """Mixture occupancies over the recognition network (sr_net_occupancies_corpus): the free network, or -- transcripts = one
         sequence of word ids per utterance, silence not listed -- the network restricted to them -> (cost f64[n_utts], count
         u16[total_frames], state u16[total_frames, max_items], weight f64[total_frames, max_items]) as state_posteriors."""
+        return self._net_occupancies(lexicon, word_penalty, scale, transcripts, kernel, floor, max_items, None)
+
+    def net_occupancies_scores(self, lexicon, word_penalty, scores, scale=1.0, transcripts=None, floor=0.0, max_items=8):
+        """sr_net_occupancies_corpus_scores (test hook): net_occupancies() on the caller's score table [n_frames, n_states]"""
+        return self._net_occupancies(lexicon, word_penalty, scale, transcripts, GMM_PREFILTER, floor, max_items,
+                                     np.ascontiguousarray(scores, dtype=np.float64))
+
+    def _net_occupancies(self, lexicon, word_penalty, scale, transcripts, kernel, floor, max_items, scores):
         F = max(self.n_frames, 1)
         K = max(int(max_items), 1)
         cost = np.zeros(max(self.n_utts, 1), dtype=np.float64)
@@ -984,8 +1010,13 @@ class Corpus:
         weight = np.zeros((F, K), dtype=np.float64)
         sp = SearchParams(np.inf, word_penalty, kernel, 0)
         flat, off = self._transcripts(transcripts)
-        _check(lib().sr_net_occupancies_corpus(self.model.h, self.h, lexicon.h, C.byref(sp), float(scale), float(floor), int(max_items),
-                                               _ptr(flat), _ptr(off), _ptr(cost), _ptr(count), _ptr(state), _ptr(weight)))
+        if scores is None:
+            _check(lib().sr_net_occupancies_corpus(self.model.h, self.h, lexicon.h, C.byref(sp), float(scale), float(floor), int(max_items),
+                                                   _ptr(flat), _ptr(off), _ptr(cost), _ptr(count), _ptr(state), _ptr(weight)))
+        else:
+            _check(lib().sr_net_occupancies_corpus_scores(self.model.h, self.h, lexicon.h, C.byref(sp), float(scale), float(floor),
+                                                          int(max_items), _ptr(flat), _ptr(off), _ptr(scores), scores.size, _ptr(cost),
+                                                          _ptr(count), _ptr(state), _ptr(weight)))
         n = self.n_frames
         return cost[: self.n_utts], count[:n], state[:n], weight[:n]
 
@@ -1007,6 +1038,14 @@ class Corpus:
         """Expected frame accuracy over the free recognition network (sr_net_accuracies_corpus); ref_states u16[total_frames] = the
         reference mixture of every frame -> (cost f64[n_utts], acc f64[n_utts], count u16[total_frames], state u16[total_frames,
         max_items], weight f64[total_frames, max_items]): per frame the signed gamma, largest |gamma| first."""
+        return self._net_accuracies(lexicon, word_penalty, ref_states, scale, kernel, floor, max_items, None)
+
+    def net_accuracies_scores(self, lexicon, word_penalty, ref_states, scores, scale=1.0, floor=0.0, max_items=8):
+        """sr_net_accuracies_corpus_scores (test hook): net_accuracies() on the caller's score table [n_frames, n_states]"""
+        return self._net_accuracies(lexicon, word_penalty, ref_states, scale, GMM_PREFILTER, floor, max_items,
+                                    np.ascontiguousarray(scores, dtype=np.float64))
+
+    def _net_accuracies(self, lexicon, word_penalty, ref_states, scale, kernel, floor, max_items, scores):
         F = max(self.n_frames, 1)
         K = max(int(max_items), 1)
         cost, acc = (np.zeros(max(self.n_utts, 1), dtype=np.float64) for _ in range(2))
@@ -1015,8 +1054,13 @@ class Corpus:
         weight = np.zeros((F, K), dtype=np.float64)
         sp = SearchParams(np.inf, word_penalty, kernel, 0)
         ref = np.ascontiguousarray(np.concatenate([np.asarray(ref_states, dtype=np.uint16), np.zeros(1, np.uint16)]))
-        _check(lib().sr_net_accuracies_corpus(self.model.h, self.h, lexicon.h, C.byref(sp), float(scale), float(floor), int(max_items),
-                                              _ptr(ref), _ptr(cost), _ptr(acc), _ptr(count), _ptr(state), _ptr(weight)))
+        if scores is None:
+            _check(lib().sr_net_accuracies_corpus(self.model.h, self.h, lexicon.h, C.byref(sp), float(scale), float(floor), int(max_items),
+                                                  _ptr(ref), _ptr(cost), _ptr(acc), _ptr(count), _ptr(state), _ptr(weight)))
+        else:
+            _check(lib().sr_net_accuracies_corpus_scores(self.model.h, self.h, lexicon.h, C.byref(sp), float(scale), float(floor),
+                                                         int(max_items), _ptr(ref), _ptr(scores), scores.size, _ptr(cost), _ptr(acc),
+                                                         _ptr(count), _ptr(state), _ptr(weight)))
         n = self.n_frames
         return cost[: self.n_utts], acc[: self.n_utts], count[:n], state[:n], weight[:n]
 

@@ -48,6 +48,9 @@ inline uint32_t max_positions(const Group& g, const uint64_t* off) {
 // positions: one wave while every position has a lane of its own, else four -- a barrier of one wave costs nothing, and at 65
 // positions a second wave already pays for itself.  (The kernels stride positions over whatever block they get: the same bits.)
 inline uint32_t fb_block_threads(uint32_t max_positions) { return max_positions <= 64 ? 64u : 256u; }
+// ... and of a launch over the transcripts' chains (viterbi_mmi.hip) whose longest chain has max_positions positions: a wave up to 64,
+// four up to 256, else the network kernels' eight.  (These kernels, too, stride positions over whatever block they get.)
+inline uint32_t chain_block_threads(uint32_t max_positions) { return max_positions <= 64 ? 64u : (max_positions <= 256 ? 256u : 512u); }
 
 // cost[u] = per_frame * frame_off[u] + u * per_utt
 inline std::vector<uint64_t> linear_cost(const uint64_t* frame_off, uint32_t U, uint64_t per_frame, uint64_t per_utt = 0) {

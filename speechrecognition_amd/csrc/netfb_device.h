@@ -12,31 +12,44 @@ static constexpr double kInf = __builtin_huge_val();
 static constexpr int kNetFbThreads = 512;
 static constexpr int kNetFbWaves = kNetFbThreads / 64;
 
+// Non-finite terms, in every sum below and in smbr_device.h's: a NaN cost (a NaN emission) counts as +inf in whichever slot it stands,
+// so that alpha and beta leave out the same paths; -inf is sticky (a -inf emission takes every path through it, and F_u, to -inf)
+// and never meets exp(-inf + inf).  For finite and +inf terms nothing here changes a bit.
+__device__ inline double nf_nan_inf(double x) { return x < kInf ? x : kInf; }
+
 // -log(exp(-a) + exp(-b))
 __device__ inline double nf_ladd(double a, double b) {
+  a = nf_nan_inf(a);
+  b = nf_nan_inf(b);
   const double m = a < b ? a : b, x = a < b ? b : a;
-  if (!(x < kInf)) return m;
+  if (!(x < kInf) || !(m > -kInf)) return m;
   return m - log1p(exp(m - x));
 }
 // -log(exp(-a) + exp(-b) + exp(-c))
 __device__ inline double nf_ladd3(double a, double b, double c) {
+  a = nf_nan_inf(a);
+  b = nf_nan_inf(b);
+  c = nf_nan_inf(c);
   double m, x, y;
   if (a <= b && a <= c) { m = a; x = b; y = c; }
   else if (b <= c) { m = b; x = a; y = c; }
   else { m = c; x = a; y = b; }
   if (!(m < kInf)) return kInf;
+  if (!(m > -kInf)) return m;
   double s = 0.0;
   if (x < kInf) s += exp(m - x);
   if (y < kInf) s += exp(m - y);
   return s == 0.0 ? m : m - log1p(s);
 }
 
-// running log-sum-exp (m = smallest cost seen, s = sum exp(m - x)); empty = (inf, 0)
+// running log-sum-exp (m = smallest cost seen, s = sum exp(m - x)); empty = (inf, 0); a NaN term is dropped, a -inf term leaves
+// (-inf, 1) whatever else is added
 struct Lse {
   double m, s;
   __device__ Lse() : m(kInf), s(0.0) {}
   __device__ void add(double x) {
-    if (!(x < kInf)) return;
+    if (!(x < kInf) || !(m > -kInf)) return;
+    if (!(x > -kInf)) { m = x; s = 1.0; return; }
     if (x < m) { s = s * exp(x - m) + 1.0; m = x; }
     else s += exp(m - x);
   }
@@ -44,6 +57,7 @@ struct Lse {
     if (!(om < kInf)) return;
     if (!(m < kInf)) { m = om; s = os; return; }
     const double n = m < om ? m : om;
+    if (!(n > -kInf)) { m = n; s = 1.0; return; }
     s = s * exp(n - m) + os * exp(n - om);
     m = n;
   }

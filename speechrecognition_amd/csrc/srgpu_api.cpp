@@ -1876,6 +1876,12 @@ static auto model_scores(sr_model* m, sr_corpus* c) {
   return [m, c](const AutomatonScoring& sc, const Chunk& ch, double* table) -> int { return automaton_scoring_chunk(m, c, sc, ch, table); };
 }
 
+// The score step of a pass over the recognition network (the word posteriors, occ_pass, smbr_accuracies): score_chunk with the caller's
+// kernel for every production pass; the test hooks sr_*_corpus_scores pass a ScoreTable.
+static auto gmm_scores(sr_model* m, sr_corpus* c, int gmm_kernel) {
+  return [m, c, gmm_kernel](const Chunk& ch, double* table) -> int { return score_chunk(m, c, ch.f0, ch.f1, gmm_kernel, table); };
+}
+
 // A caller's score table [F x n_states] as the hooks' score step: the rows padded to the chunk tables' stride m->ld with +inf, the
 // whole table once, so that a chunk is one copy.
 struct ScoreTable {
@@ -1892,7 +1898,8 @@ struct ScoreTable {
     for (uint64_t t = 0; t < F; t++) memcpy(padded.data() + t * ld, scores + t * S, sizeof(double) * S);
     return SR_OK;
   }
-  int operator()(const AutomatonScoring&, const Chunk& ch, double* table) const {
+  int operator()(const AutomatonScoring&, const Chunk& ch, double* table) const { return (*this)(ch, table); }
+  int operator()(const Chunk& ch, double* table) const {  // (the network passes' score step: run_chunks' own signature)
     if (ch.f1 > ch.f0)
       HIP_TRY(hipMemcpyAsync(table, padded.data() + ch.f0 * m->ld, sizeof(double) * (ch.f1 - ch.f0) * m->ld, hipMemcpyHostToDevice, m->s_gmm));
     return SR_OK;
@@ -3329,9 +3336,11 @@ static int netfb_costs(sr_corpus* c, double scale, double* out_cost) {
   return SR_OK;
 }
 
-int sr_word_posteriors_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
-                              uint32_t max_items, double* out_cost, uint16_t* out_count, uint32_t* out_word, double* out_weight) {
-  return guarded(__func__, [&]() -> int {
+// sr_word_posteriors_corpus and its test hook: the checks, the pass on `score`'s scores, F_u and the top words to the host
+template <class Score>
+static int word_posteriors(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
+                           uint32_t max_items, Score score, double* out_cost, uint16_t* out_count, uint32_t* out_word,
+                           double* out_weight) {
   int rc = netfb_check(m, c, l, p, scale, posterior_floor);
   if (rc) return rc;
   if (!out_cost) return fail(SR_EINVAL, "null argument");
@@ -3343,7 +3352,7 @@ int sr_word_posteriors_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr
   NetFbPass fp;
   if ((rc = fp.setup(m, c, l, p, scale, chunks))) return rc;
   if (post && (rc = ensure_top_items(F, max_items, c->nf_count, c->nf_word, c->nf_weight))) return rc;
-  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); },
+  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) -> int { return score(ch, table); },
       [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
         return fp.run(c, ch, table, s, [&](const NetFbArgs& a, uint64_t n) -> int {
           if (post) HIP_TRY(launch_netfb_top(a, n, max_items, posterior_floor, c->nf_count.p, c->nf_word.p, c->nf_weight.p, s));
@@ -3355,6 +3364,28 @@ int sr_word_posteriors_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr
   if ((rc = netfb_costs(c, scale, out_cost))) return rc;
   if (!post || F == 0) return SR_OK;
   return copy_top_items(F, max_items, c->nf_count, c->nf_word, c->nf_weight, out_count, out_word, out_weight);
+}
+
+int sr_word_posteriors_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
+                              uint32_t max_items, double* out_cost, uint16_t* out_count, uint32_t* out_word, double* out_weight) {
+  return guarded(__func__, [&]() -> int {
+  if (!p) return fail(SR_EINVAL, "null argument");
+  return word_posteriors(m, c, l, p, scale, posterior_floor, max_items, gmm_scores(m, c, p->gmm_kernel), out_cost, out_count, out_word,
+                         out_weight);
+  });
+}
+
+// test hook: sr_word_posteriors_corpus with the chunk's score step replaced by a copy of the caller's rows (p->gmm_kernel is not read)
+int sr_word_posteriors_corpus_scores(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale,
+                                     double posterior_floor, uint32_t max_items, const double* scores, uint64_t n_scores, double* out_cost,
+                                     uint16_t* out_count, uint32_t* out_word, double* out_weight) {
+  return guarded(__func__, [&]() -> int {
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  ScoreTable table;
+  if ((rc = table.set(m, c, scores, n_scores))) return rc;
+  return table.done(word_posteriors(m, c, l, p, scale, posterior_floor, max_items, std::cref(table), out_cost, out_count, out_word,
+                                    out_weight));
   });
 }
 
@@ -3639,8 +3670,10 @@ static int occ_check(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_p
 // Inside a chunk, consecutive utterances whose trellises fit m->fb_budget together (8 B per frame and position) run forward, backward and
 // -- want_items -- the occupancy items.  Leaves kappa F_u in c->out_cost and, with want_items, *n_items items in c->fb_item_* (frame
 // order, ascending mixture id) with c->fb_item_off[F + 1]; utterances whose gate (device, optional) is +inf give no items.
+template <class Score>
 static int occ_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
-                    const uint32_t* trans, const uint64_t* trans_off, bool want_items, const double* gate, uint64_t* n_items) {
+                    const uint32_t* trans, const uint64_t* trans_off, bool want_items, const double* gate, uint64_t* n_items,
+                    Score score) {
   const uint32_t U = c->n_utts;
   const uint64_t F = c->n_frames, P = l->net.n_slots;
   const bool chain = trans_off != nullptr;
@@ -3678,7 +3711,7 @@ static int occ_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_pa
   ItemArgs ia{};
   occ_item_fields(&ia, c, pl.ml, chain, P, c->fb_slot_pos, 0, gate, posterior_floor);
   size_t ci = 0;  // run_chunks searches the chunks in order
-  rc = run_chunks(m, chunks, [&](const Chunk& k, double* table) { return score_chunk(m, c, k.f0, k.f1, p->gmm_kernel, table); },
+  rc = run_chunks(m, chunks, [&](const Chunk& k, double* table) -> int { return score(k, table); },
       [&](const Chunk& k, const double* table, hipStream_t s) -> int {
         if (want_items && ci == 0) HIP_TRY(reset_item_count(c->fb_base, s));
         for (const Group& g : groups.of_chunk[ci]) {
@@ -3709,6 +3742,12 @@ static int occ_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_pa
   return SR_OK;
 }
 
+// ... with the model's scores, as every production pass takes it
+static int occ_pass(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
+                    const uint32_t* trans, const uint64_t* trans_off, bool want_items, const double* gate, uint64_t* n_items) {
+  return occ_pass(m, c, l, p, scale, posterior_floor, trans, trans_off, want_items, gate, n_items, gmm_scores(m, c, p->gmm_kernel));
+}
+
 // Numerator and denominator statistics of MMI training, for sr_mmi_statistics_corpus and sr_bigram_mmi_statistics_corpus:
 // pass(numerator, gate, &n_items) is the entry point's occupancy pass over the transcripts' chains (numerator) or the free network.
 template <class Pass>
@@ -3737,10 +3776,11 @@ static int mmi_statistics(sr_model* m, sr_corpus* c, double scale, int max_appro
   return rc;
 }
 
-int sr_net_occupancies_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
-                              uint32_t max_items, const uint32_t* trans, const uint64_t* trans_off, double* out_cost,
-                              uint16_t* out_count, uint16_t* out_state, double* out_weight) {
-  return guarded(__func__, [&]() -> int {
+// sr_net_occupancies_corpus and its test hook: the checks, the pass on `score`'s scores, F_u and the top items to the host
+template <class Score>
+static int net_occupancies(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
+                           uint32_t max_items, const uint32_t* trans, const uint64_t* trans_off, Score score, double* out_cost,
+                           uint16_t* out_count, uint16_t* out_state, double* out_weight) {
   bool constrained = false;
   int rc = occ_check(m, c, l, p, scale, posterior_floor, trans, trans_off, &constrained);
   if (rc) return rc;
@@ -3748,9 +3788,34 @@ int sr_net_occupancies_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr
   bool post = false;
   if ((rc = top_items_arguments(out_count, out_state, out_weight, "out_state", max_items, &post))) return rc;
   uint64_t n_items = 0;
-  if ((rc = occ_pass(m, c, l, p, scale, posterior_floor, trans, constrained ? trans_off : nullptr, post, nullptr, &n_items))) return rc;
+  if ((rc = occ_pass(m, c, l, p, scale, posterior_floor, trans, constrained ? trans_off : nullptr, post, nullptr, &n_items, score)))
+    return rc;
   if ((rc = netfb_costs(c, scale, out_cost))) return rc;
   return post ? top_of_items(m, c, max_items, out_count, out_state, out_weight) : SR_OK;
+}
+
+int sr_net_occupancies_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale, double posterior_floor,
+                              uint32_t max_items, const uint32_t* trans, const uint64_t* trans_off, double* out_cost,
+                              uint16_t* out_count, uint16_t* out_state, double* out_weight) {
+  return guarded(__func__, [&]() -> int {
+  if (!p) return fail(SR_EINVAL, "null argument");
+  return net_occupancies(m, c, l, p, scale, posterior_floor, max_items, trans, trans_off, gmm_scores(m, c, p->gmm_kernel), out_cost,
+                         out_count, out_state, out_weight);
+  });
+}
+
+// test hook: sr_net_occupancies_corpus with the chunk's score step replaced by a copy of the caller's rows (p->gmm_kernel is not read)
+int sr_net_occupancies_corpus_scores(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale,
+                                     double posterior_floor, uint32_t max_items, const uint32_t* trans, const uint64_t* trans_off,
+                                     const double* scores, uint64_t n_scores, double* out_cost, uint16_t* out_count, uint16_t* out_state,
+                                     double* out_weight) {
+  return guarded(__func__, [&]() -> int {
+  int rc = check_corpus(m, c);
+  if (rc) return rc;
+  ScoreTable table;
+  if ((rc = table.set(m, c, scores, n_scores))) return rc;
+  return table.done(net_occupancies(m, c, l, p, scale, posterior_floor, max_items, trans, trans_off, std::cref(table), out_cost, out_count,
+                                    out_state, out_weight));
   });
 }
 
@@ -3918,8 +3983,8 @@ struct SmbrPass {
 
 // What the accuracy and sMBR statistics calls of either network do once their check has passed.  Pass is the network's pass (SmbrPass,
 // BgSmbrPass), setup(pass, chunks, want_items) its set-up.
-template <class Pass, class Setup>
-static int smbr_accuracies(sr_model* m, sr_corpus* c, int gmm_kernel, double scale, uint32_t max_items, double* out_cost, double* out_acc,
+template <class Pass, class Setup, class Score>
+static int smbr_accuracies(sr_model* m, sr_corpus* c, Score score, double scale, uint32_t max_items, double* out_cost, double* out_acc,
                            uint16_t* out_count, uint16_t* out_state, double* out_weight, Setup setup) {
   if (!out_cost || !out_acc) return fail(SR_EINVAL, "null argument");
   bool post = false;
@@ -3929,7 +3994,7 @@ static int smbr_accuracies(sr_model* m, sr_corpus* c, int gmm_kernel, double sca
   if ((rc = prepare_chunks(m, c, &chunks))) return rc;
   Pass sp;
   if ((rc = setup(sp, chunks, post))) return rc;
-  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, gmm_kernel, table); },
+  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) -> int { return score(ch, table); },
       [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
         if (post && sp.ci == 0) HIP_TRY(reset_item_count(c->fb_base, s));
         return sp.run(c, ch, table, s, [&](const ItemArgs& ia, uint64_t n) -> int {
@@ -3997,10 +4062,27 @@ int sr_net_accuracies_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_
   return guarded(__func__, [&]() -> int {
   int rc = smbr_check(m, c, l, p, scale, posterior_floor, ref_states);
   if (rc) return rc;
-  return smbr_accuracies<SmbrPass>(m, c, p->gmm_kernel, scale, max_items, out_cost, out_acc, out_count, out_state, out_weight,
-                                   [&](SmbrPass& sp, const std::vector<Chunk>& chunks, bool want_items) {
+  return smbr_accuracies<SmbrPass>(m, c, gmm_scores(m, c, p->gmm_kernel), scale, max_items, out_cost, out_acc, out_count, out_state,
+                                   out_weight, [&](SmbrPass& sp, const std::vector<Chunk>& chunks, bool want_items) {
     return sp.setup(m, c, l, p, scale, posterior_floor, ref_states, want_items, chunks);
   });
+  });
+}
+
+// test hook: sr_net_accuracies_corpus with the chunk's score step replaced by a copy of the caller's rows (p->gmm_kernel is not read)
+int sr_net_accuracies_corpus_scores(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double scale,
+                                    double posterior_floor, uint32_t max_items, const uint16_t* ref_states, const double* scores,
+                                    uint64_t n_scores, double* out_cost, double* out_acc, uint16_t* out_count, uint16_t* out_state,
+                                    double* out_weight) {
+  return guarded(__func__, [&]() -> int {
+  int rc = smbr_check(m, c, l, p, scale, posterior_floor, ref_states);
+  if (rc) return rc;
+  ScoreTable table;
+  if ((rc = table.set(m, c, scores, n_scores))) return rc;
+  return table.done(smbr_accuracies<SmbrPass>(m, c, std::cref(table), scale, max_items, out_cost, out_acc, out_count, out_state, out_weight,
+                                              [&](SmbrPass& sp, const std::vector<Chunk>& chunks, bool want_items) {
+    return sp.setup(m, c, l, p, scale, posterior_floor, ref_states, want_items, chunks);
+  }));
   });
 }
 
@@ -4240,7 +4322,7 @@ int sr_bigram_accuracies_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm
   return guarded(__func__, [&]() -> int {
   int rc = bgsmbr_check(m, c, b, scale, posterior_floor, ref_states);
   if (rc) return rc;
-  return smbr_accuracies<BgSmbrPass>(m, c, gmm_kernel, scale, max_items, out_cost, out_acc, out_count, out_state, out_weight,
+  return smbr_accuracies<BgSmbrPass>(m, c, gmm_scores(m, c, gmm_kernel), scale, max_items, out_cost, out_acc, out_count, out_state, out_weight,
                                      [&](BgSmbrPass& sp, const std::vector<Chunk>& chunks, bool) {
     return sp.setup(m, c, b, scale, posterior_floor, ref_states, chunks);
   });

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fb_plan.h"
 #include "kernels.h"
 #include "netfb_device.h"
 
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(kNetFbThreads) void netocc_backward_kernel(NetFbArg
   const uint32_t* info = a.net.slot_info;
   const NfCosts c = nf_costs(a);
   const double F = a.out_cost[u];  // kappa F_u
-  const bool dead = !(F < kInf);  // no complete path: every occupancy is 0
+  const bool dead = !(F < kInf && F > -kInf);  // no complete path (or a -inf emission took F along): every occupancy is 0
 
   // beta_t is whole in b (after the frame's barrier): the occupancy parts over alpha_t in the trellis.  Row t - 1 still holds alpha.
   auto occupy = [&](int t, const double* b, const double* row) {
@@ -223,7 +224,7 @@ __global__ __launch_bounds__(kNetFbThreads) void chain_backward_kernel(ChainArgs
   const uint32_t* dst = a.dst + a.chain_off[u];
   const NfCosts c = chain_costs(a);
   const double F = a.out_cost[u];
-  const bool dead = !(F < kInf);
+  const bool dead = !(F < kInf && F > -kInf);
 
   auto occupy = [&](int t, const double* b, const double* row) {
     double* r = tr + (size_t)t * N;
@@ -288,8 +289,8 @@ __global__ __launch_bounds__(kNetFbThreads) void chain_backward_kernel(ChainArgs
   }
 }
 
-// a wave for chains of up to 64 positions, four up to 256, else the network kernels' eight
-static uint32_t chain_block(uint32_t max_positions) { return max_positions <= 64 ? 64u : (max_positions <= 256 ? 256u : (uint32_t)kNetFbThreads); }
+static_assert(kNetFbThreads == 512, "srplan::chain_block_threads' largest block is the kernels' launch bound");
+static uint32_t chain_block(uint32_t max_positions) { return srplan::chain_block_threads(max_positions); }
 
 hipError_t launch_chain_forward(const ChainArgs& a, hipStream_t stream) {
   if (a.n_utts == 0) return hipSuccess;

@@ -97,7 +97,7 @@ __global__ __launch_bounds__(kNetFbThreads) void netfb_backward_kernel(NetFbArgs
   const uint32_t* info = a.net.slot_info;
   const NfCosts c = nf_costs(a);
   const double F = a.out_cost[u];  // kappa F_u
-  const bool dead = !(F < kInf);  // no complete path: every posterior is 0
+  const bool dead = !(F < kInf && F > -kInf);  // no complete path (or a -inf emission took F along): every posterior is 0
 
   // beta_t(s) of the thread's slots is final: gamma_t over alpha_t in the trellis, and the slot's term of B_{t-1} (entry into
   // it at frame t: penalty, the entry's emission at t, beta_t)

@@ -105,7 +105,8 @@ __global__ __launch_bounds__(kNetFbThreads) void smbr_forward_kernel(SmbrArgs a)
     E = block_lsea_read(red + (t & 1) * 3 * kNetFbWaves);
     if (tid == 0) { ends[2 * t] = E.x; ends[2 * t + 1] = E.a; }
   }
-  if (tid == 0) { a.out_cost[u] = E.x; a.out_acc[u] = E.a; }  // kappa F_u (the host divides), Abar_u
+  // kappa F_u (the host divides), Abar_u (0 where F_u is not finite: no path, or a -inf emission)
+  if (tid == 0) { a.out_cost[u] = E.x; a.out_acc[u] = E.x > -kInf ? E.a : 0.0; }
 }
 
 // LDS: row[2][2][P] f64 (beta, bbar), red[2][3 * kNetFbWaves] f64.  Runs after smbr_forward_kernel on the same launch.
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(kNetFbThreads) void smbr_backward_kernel(SmbrArgs a
   const uint32_t* info = a.net.slot_info;
   const NfCosts c = smbr_costs(a);
   const double F = a.out_cost[u], A = a.out_acc[u];  // kappa F_u, Abar_u
-  const bool dead = !(F < kInf);  // no complete path: every weight is 0
+  const bool dead = !(F < kInf && F > -kInf);  // no complete path (or a -inf emission took F along): every weight is 0
 
   for (int t = T - 1; t >= 0; t--) {
     const double* nxt = be + (size_t)((t + 1) & 1) * 2 * P;

@@ -12,7 +12,7 @@
 //   seg <n_ranges> <L>  bounds[n_ranges + 1]
 //     -> "begin ...", "len ...", "off ..."
 //   block <n>  max_positions[n]
-//     -> "threads ..." (fb_block_threads of each)
+//     -> "threads ..." (fb_block_threads of each), "chain_threads ..." (chain_block_threads of each)
 #include <cstdio>
 #include <fstream>
 #include <string>
@@ -143,8 +143,11 @@ int main(int argc, char** argv) {
       std::vector<uint32_t> v(n);
       for (auto& x : v) in >> x;
       ok = (bool)in;
+      std::vector<uint32_t> c(v);
       for (auto& x : v) x = srplan::fb_block_threads(x);
+      for (auto& x : c) x = srplan::chain_block_threads(x);
       line("threads", v);
+      line("chain_threads", c);
     }
     if (!ok) { fprintf(stderr, "bad case file\n"); return 2; }
     printf("end\n");

@@ -13,7 +13,8 @@ The start hypothesis sits at slot 0 (position 0 of word 0 / of sil_0) on the vir
 end the row enters what that word end enters.  Entries cost wp(v) + tdp(first_v, init + 1) + e(t, first_v) at position 0 or 1.
 
 occupancies(): occ[t, k] = the posterior probability that frame t's emission is mixture k's = dF / d e(t, k).  A slot's gamma counts
-for its own state, except that the ENTRY part of a position-1 slot counts for the word's first state (which the entry emits)."""
+for its own state, except that the ENTRY part of a position-1 slot counts for the word's first state (which the entry emits).
+occupancies() takes a `dtype` as net_fb_reference's recursions do (np.longdouble: the yardstick of tests/test_gpu_netocc_scores.py)."""
 from __future__ import annotations
 
 import numpy as np
@@ -71,56 +72,59 @@ def chain_graph(net, transcript):
     return Graph(net, words, src, [G - 1] + ([G - 2] if G > 1 else []))
 
 
-def _penalties(gr, tdp, wp, scale):
-    tl, tf, ts = (scale * float(x) for x in tdp)
+def _penalties(gr, tdp, wp, scale, dtype=np.float64):
+    scale = dtype(scale)
+    tl, tf, ts = (scale * dtype(x) for x in tdp)
     sil = gr.state == gr.net.sil_state
-    into = np.array([np.where(sil, tf, v) for v in (tl, tf, ts)])
-    w = np.where(gr.sil_word, 0.0, scale * float(wp))
+    into = np.array([np.where(sil, tf, v) for v in (tl, tf, ts)], dtype=dtype)
+    w = np.where(gr.sil_word, dtype(0.0), scale * dtype(wp))
     t_init = np.where(gr.pos == 0, tf, np.where(gr.first == gr.net.sil_state, tf, ts))
     return into, w + t_init
 
 
-def _lsum(xs):
-    return R._lsum(np.asarray(list(xs), dtype=np.float64))
+def _lsum(xs, dtype=np.float64):
+    return R._lsum(np.asarray(list(xs), dtype=dtype))
 
 
-def occupancies(e, gr, tdp, wp, scale=1.0):
+def occupancies(e, gr, tdp, wp, scale=1.0, dtype=np.float64):
     """-> (F = -(1/kappa) log of the graph's path mass, occ [T, S])"""
-    e = np.asarray(e, dtype=np.float64)
+    e = np.asarray(e, dtype=np.float64).astype(dtype)
     T, S = e.shape
     P = gr.P
-    into, ent = _penalties(gr, tdp, wp, scale)
+    into, ent = _penalties(gr, tdp, wp, scale, dtype)
+    scale = dtype(scale)
+    lsum = lambda xs: _lsum(xs, dtype)
     if T == 0:
-        return INF, np.zeros((0, S))
+        return INF, np.zeros((0, S), dtype=dtype)
     # alpha; row 0 of A is the virtual row
-    A = np.full((T + 1, P), INF)
+    A = np.full((T + 1, P), INF, dtype=dtype)
     A[0, 0] = 0.0
-    Esum = np.full((T + 1, len(gr.src)), INF)  # Esum[t, g]: the entry sum of segment g from row t
-    inw = np.full((T + 1, P), INF)             # in-word part of alpha before the emission
+    Esum = np.full((T + 1, len(gr.src)), INF, dtype=dtype)  # Esum[t, g]: the entry sum of segment g from row t
+    inw = np.full((T + 1, P), INF, dtype=dtype)             # in-word part of alpha before the emission
     for t in range(1, T + 1):
         em = scale * e[t - 1]
         cache = {}
         for g, srcs in enumerate(gr.src):
             if srcs not in cache:
-                cache[srcs] = _lsum(A[t - 1, list(srcs)])
+                cache[srcs] = lsum(A[t - 1, list(srcs)])
             Esum[t - 1, g] = cache[srcs]
         for s in range(P):
             terms = []
             for j in range(3):
                 if gr.pos[s] >= j and not (j == 0 and gr.end[s]):
                     terms.append(A[t - 1, s - j] + into[j, s])
-            inw[t, s] = _lsum(terms)
+            inw[t, s] = lsum(terms)
             x = [inw[t, s] + em[gr.state[s]]]
             if gr.pos[s] == 0:
                 x.append(Esum[t - 1, gr.seg[s]] + ent[s] + em[gr.state[s]])
             elif gr.pos[s] == 1:
                 x.append(Esum[t - 1, gr.seg[s]] + ent[s] + em[gr.first[s]])
-            A[t, s] = _lsum(x)
-    F = _lsum(A[T, gr.final])
-    occ = np.zeros((T, S))
+            A[t, s] = lsum(x)
+    F = lsum(A[T, gr.final])
+    occ = np.zeros((T, S), dtype=dtype)
     if not np.isfinite(F):
         return INF, occ
-    B = np.full((T + 1, P), INF)
+    B = np.full((T + 1, P), INF, dtype=dtype)
     B[T, gr.final] = 0.0
     for t in range(T, 0, -1):
         em = scale * e[t - 1]
@@ -132,19 +136,19 @@ def occupancies(e, gr, tdp, wp, scale=1.0):
                 x = [ent[b] + en[gr.state[b]] + B[t + 1, b]]
                 if not gr.end[b]:
                     x.append(ent[b + 1] + en[gr.state[b]] + B[t + 1, b + 1])
-                X.append(_lsum(x))
+                X.append(lsum(x))
             cache = {}
             for s in range(P):
                 if gr.end[s]:
                     key = tuple(gr.dst[gr.seg[s]])
                     if key not in cache:
-                        cache[key] = _lsum(X[g] for g in key)
+                        cache[key] = lsum(X[g] for g in key)
                     B[t, s] = cache[key]
                 else:
                     x = [into[0, s] + en[gr.state[s]] + B[t + 1, s], into[1, s + 1] + en[gr.state[s + 1]] + B[t + 1, s + 1]]
                     if not gr.end[s + 1]:
                         x.append(into[2, s + 2] + en[gr.state[s + 2]] + B[t + 1, s + 2])
-                    B[t, s] = _lsum(x)
+                    B[t, s] = lsum(x)
         for s in range(P):
             if not np.isfinite(B[t, s]):
                 continue

@@ -8,7 +8,11 @@ DESTINATION state and a move into the silence state costs `forward`.  A word-end
 wp(v) + tdp(first_v, init + 1) + e(t, first_v) -- the first state's emission also for position 1 (the reference's quirk); an entry
 into position 1 of a one-position word reaches no slot.  F = -(1/kappa) log sum over the paths ending in a word end at frame T - 1
 of exp(-kappa cost).  With semiring="min" (and kappa = 1) the per-frame minimum over word ends is the decoder's tb_score[1..T] at
-an infinite beam, in the oracle's order of additions: ((h + wp) + tdp) + e and (h + tdp) + e."""
+an infinite beam, in the oracle's order of additions: ((h + wp) + tdp) + e and (h + tdp) + e.
+
+forward, backward and posteriors take a `dtype` (default float64, the kernels' own precision): with np.longdouble (x87: 64 bits of
+mantissa) the same recursion is the yardstick the float64 one, and the kernels, are measured against (tests/test_gpu_netfb_scores.py).
+A NaN entry is not defined here: the tests hand over the table with NaN set to +inf (tests/netfb_cases.sanitised)."""
 from __future__ import annotations
 
 import numpy as np
@@ -33,13 +37,14 @@ class Net:
         self.sil_state = silence_state
 
 
-def _costs(net, tdp, wp, scale):
+def _costs(net, tdp, wp, scale, dtype=np.float64):
     """per slot: into[j] = penalty of a jump of j INTO the slot; entry = wp + tdp(first, init + 1) for positions 0 / 1 (inf else)"""
-    tl, tf, ts = (scale * float(x) for x in tdp)
-    into = np.empty((3, net.P))
+    scale = dtype(scale)
+    tl, tf, ts = (scale * dtype(x) for x in tdp)
+    into = np.empty((3, net.P), dtype=dtype)
     for j, v in enumerate((tl, tf, ts)):
         into[j] = np.where(net.state == net.sil_state, tf, v)
-    w = np.where(net.sil_word, 0.0, scale * float(wp))
+    w = np.where(net.sil_word, dtype(0.0), scale * dtype(wp))
     t_init = np.where(net.pos == 0, tf, np.where(net.first == net.sil_state, tf, ts))
     return into, w, t_init
 
@@ -57,31 +62,34 @@ def _shift(v, j):
 
 
 def _ladd(*xs):
-    acc = -np.asarray(xs[0], dtype=np.float64)
+    acc = -np.asarray(xs[0])
     for x in xs[1:]:
-        acc = np.logaddexp(acc, -np.asarray(x, dtype=np.float64))
+        acc = np.logaddexp(acc, -np.asarray(x))
     return -acc
 
 
 def _lsum(x):
     """-log sum exp(-x) over a vector (+inf if empty or all +inf)"""
-    x = np.asarray(x, dtype=np.float64)
+    x = np.asarray(x)
+    if x.dtype != np.longdouble:
+        x = x.astype(np.float64)
     if x.size == 0 or not np.isfinite(x).any():
         return INF
     m = x.min()
     return m - np.log(np.exp(m - x[np.isfinite(x)]).sum())
 
 
-def forward(e, net, tdp, wp, semiring="log", scale=1.0):
+def forward(e, net, tdp, wp, semiring="log", scale=1.0, dtype=np.float64):
     """-> (alpha [T, P], E [T]): E[t] = the word-end sum (min) at frame t."""
-    E_tab = np.asarray(e, dtype=np.float64)
+    E_tab = np.asarray(e, dtype=np.float64).astype(dtype)
     T = E_tab.shape[0]
-    into, w, t_init = _costs(net, tdp, wp, scale)
-    A = np.full((T, net.P), INF)
-    Es = np.full(T, INF)
-    prev = np.full(net.P, INF)
+    into, w, t_init = _costs(net, tdp, wp, scale, dtype)
+    scale = dtype(scale)
+    A = np.full((T, net.P), INF, dtype=dtype)
+    Es = np.full(T, INF, dtype=dtype)
+    prev = np.full(net.P, INF, dtype=dtype)
     prev[0] = 0.0
-    Eprev = 0.0 if net.end[0] else INF
+    Eprev = dtype(0.0 if net.end[0] else INF)
     p0, p1 = net.pos == 0, net.pos == 1
     with np.errstate(invalid="ignore"):
         for t in range(T):
@@ -110,12 +118,13 @@ def forward(e, net, tdp, wp, semiring="log", scale=1.0):
     return A, Es
 
 
-def backward(e, net, tdp, wp, scale=1.0):
+def backward(e, net, tdp, wp, scale=1.0, dtype=np.float64):
     """beta [T, P]: the cost from after frame t to a word end at T - 1 (log semiring, scaled)."""
-    E_tab = np.asarray(e, dtype=np.float64)
+    E_tab = np.asarray(e, dtype=np.float64).astype(dtype)
     T = E_tab.shape[0]
-    into, w, t_init = _costs(net, tdp, wp, scale)
-    B = np.full((T, net.P), INF)
+    into, w, t_init = _costs(net, tdp, wp, scale, dtype)
+    scale = dtype(scale)
+    B = np.full((T, net.P), INF, dtype=dtype)
     B[T - 1, net.end] = 0.0
     entry = (net.pos == 0) | (net.pos == 1)
     nxt_end1 = np.append(net.end[1:], True)  # slot s + 1 is a word end (or does not exist)
@@ -133,22 +142,22 @@ def backward(e, net, tdp, wp, scale=1.0):
     return B
 
 
-def posteriors(e, net, tdp, wp, scale=1.0):
+def posteriors(e, net, tdp, wp, scale=1.0, dtype=np.float64):
     """-> (F, word posteriors [T, W]): F = -(1/kappa) log P(X); p[t, w] = sum over w's slots of gamma_t."""
-    A, Es = forward(e, net, tdp, wp, "log", scale)
+    A, Es = forward(e, net, tdp, wp, "log", scale, dtype)
     T = A.shape[0]
     if T == 0:
-        return INF, np.zeros((0, net.W))
+        return INF, np.zeros((0, net.W), dtype=dtype)
     F = Es[T - 1]
-    B = backward(e, net, tdp, wp, scale)
-    with np.errstate(invalid="ignore"):
+    B = backward(e, net, tdp, wp, scale, dtype)
+    with np.errstate(invalid="ignore", over="ignore"):
         G = np.exp(F - A - B)
-    G = np.where(np.isfinite(A) & np.isfinite(B) & np.isfinite(F), G, 0.0)
-    p = np.zeros((T, net.W))
+    G = np.where(np.isfinite(A) & np.isfinite(B) & np.isfinite(F), G, dtype(0.0))
+    p = np.zeros((T, net.W), dtype=dtype)
     for wd in range(net.W):
         a, b = net.word_off[wd], net.word_off[wd + 1]
         p[:, wd] = G[:, a:b].sum(axis=1)
-    return F / scale, p
+    return F / dtype(scale), p
 
 
 def best_ends(e, net, tdp, wp):

@@ -11,7 +11,9 @@ position 1 of a word emits, and is scored as, the word's FIRST state).  Beside a
 both as posterior-weighted means of their sources.  Abar = the mean of abar_{T-1} over the final slots, and
 
   gamma_t(k) = sum over the occupancy parts of (t, k) of part * (c_part - Abar),   c_part = abar-side + [k == ref_t] + bbar-side
-             = occ_t(k) (c_t(k) - Abar) = -(1 / kappa) d Abar / d e(t, k)."""
+             = occ_t(k) (c_t(k) - Abar) = -(1 / kappa) d Abar / d e(t, k).
+
+smbr() takes a `dtype` as net_fb_reference's recursions do (np.longdouble: the yardstick of tests/test_gpu_smbr_scores.py)."""
 from __future__ import annotations
 
 import numpy as np
@@ -21,41 +23,43 @@ from tests import mmi_reference as M
 INF = np.inf
 
 
-def _wmean(xs, vals):
+def _wmean(xs, vals, dtype=np.float64):
     """-> (-log sum exp(-x), the mean of vals weighted with exp(-x)); (+inf, 0) without a finite x"""
-    xs, vals = np.asarray(xs, dtype=np.float64), np.asarray(vals, dtype=np.float64)
+    xs, vals = np.asarray(xs, dtype=dtype), np.asarray(vals, dtype=dtype)
     ok = np.isfinite(xs)
     if not ok.any():
         return INF, 0.0
     m = xs[ok].min()
     w = np.exp(m - xs[ok])
-    return m - np.log(w.sum()), float((w * vals[ok]).sum() / w.sum())
+    return m - np.log(w.sum()), dtype((w * vals[ok]).sum() / w.sum())
 
 
-def smbr(e, gr, tdp, wp, ref, scale=1.0):
+def smbr(e, gr, tdp, wp, ref, scale=1.0, dtype=np.float64):
     """e [T, S] emission costs, gr a mmi_reference.Graph, ref [T] reference mixtures (>= S: none)
     -> (F, Abar, gamma [T, S]); F = +inf (or T = 0): Abar = 0, gamma = 0"""
-    e = np.asarray(e, dtype=np.float64)
+    e = np.asarray(e, dtype=np.float64).astype(dtype)
     T, S = e.shape
     P = gr.P
     ref = np.asarray(ref, dtype=np.int64)
-    gamma = np.zeros((T, S))
+    gamma = np.zeros((T, S), dtype=dtype)
     if T == 0:
         return INF, 0.0, gamma
-    into, ent = M._penalties(gr, tdp, wp, scale)
+    into, ent = M._penalties(gr, tdp, wp, scale, dtype)
+    scale = dtype(scale)
+    wm = lambda xs, vals: _wmean(xs, vals, dtype)
     hit = lambda k, t: 1.0 if k == ref[t] else 0.0
     G = len(gr.src)
     # rows 1 .. T are the frames, row 0 the virtual row
-    A, Aa = np.full((T + 1, P), INF), np.zeros((T + 1, P))
+    A, Aa = np.full((T + 1, P), INF, dtype=dtype), np.zeros((T + 1, P), dtype=dtype)
     A[0, 0] = 0.0
-    Es, Ea = np.full((T + 1, G), INF), np.zeros((T + 1, G))
-    inw, inwa = np.full((T + 1, P), INF), np.zeros((T + 1, P))
+    Es, Ea = np.full((T + 1, G), INF, dtype=dtype), np.zeros((T + 1, G), dtype=dtype)
+    inw, inwa = np.full((T + 1, P), INF, dtype=dtype), np.zeros((T + 1, P), dtype=dtype)
     for t in range(1, T + 1):
         em = scale * e[t - 1]
         cache = {}
         for g, srcs in enumerate(gr.src):
             if srcs not in cache:
-                cache[srcs] = _wmean(A[t - 1, list(srcs)], Aa[t - 1, list(srcs)])
+                cache[srcs] = wm(A[t - 1, list(srcs)], Aa[t - 1, list(srcs)])
             Es[t - 1, g], Ea[t - 1, g] = cache[srcs]
         for s in range(P):
             xs, vs = [], []
@@ -63,18 +67,18 @@ def smbr(e, gr, tdp, wp, ref, scale=1.0):
                 if gr.pos[s] >= j and not (j == 0 and gr.end[s]):
                     xs.append(A[t - 1, s - j] + into[j, s])
                     vs.append(Aa[t - 1, s - j])
-            inw[t, s], inwa[t, s] = _wmean(xs, vs)
+            inw[t, s], inwa[t, s] = wm(xs, vs)
             k = gr.state[s]
             xs, vs = [inw[t, s] + em[k]], [inwa[t, s] + hit(k, t - 1)]
             if gr.pos[s] <= 1:
                 kf = k if gr.pos[s] == 0 else gr.first[s]
                 xs.append(Es[t - 1, gr.seg[s]] + ent[s] + em[kf])
                 vs.append(Ea[t - 1, gr.seg[s]] + hit(kf, t - 1))
-            A[t, s], Aa[t, s] = _wmean(xs, vs)
-    F, Abar = _wmean(A[T, gr.final], Aa[T, gr.final])
+            A[t, s], Aa[t, s] = wm(xs, vs)
+    F, Abar = wm(A[T, gr.final], Aa[T, gr.final])
     if not np.isfinite(F):
         return INF, 0.0, gamma
-    B, Bb = np.full((T + 1, P), INF), np.zeros((T + 1, P))
+    B, Bb = np.full((T + 1, P), INF, dtype=dtype), np.zeros((T + 1, P), dtype=dtype)
     B[T, gr.final] = 0.0
     for t in range(T, 0, -1):
         em = scale * e[t - 1]
@@ -88,13 +92,13 @@ def smbr(e, gr, tdp, wp, ref, scale=1.0):
                 if not gr.end[b]:
                     xs.append(ent[b + 1] + en[k] + B[t + 1, b + 1])
                     vs.append(Bb[t + 1, b + 1] + hit(k, t))
-                X.append(_wmean(xs, vs))
+                X.append(wm(xs, vs))
             cache = {}
             for s in range(P):
                 if gr.end[s]:
                     key = tuple(gr.dst[gr.seg[s]])
                     if key not in cache:
-                        cache[key] = _wmean([X[g][0] for g in key], [X[g][1] for g in key])
+                        cache[key] = wm([X[g][0] for g in key], [X[g][1] for g in key])
                     B[t, s], Bb[t, s] = cache[key]
                 else:
                     xs, vs = [], []
@@ -104,7 +108,7 @@ def smbr(e, gr, tdp, wp, ref, scale=1.0):
                         k = gr.state[s + j]
                         xs.append(into[j, s + j] + en[k] + B[t + 1, s + j])
                         vs.append(Bb[t + 1, s + j] + hit(k, t))
-                    B[t, s], Bb[t, s] = _wmean(xs, vs)
+                    B[t, s], Bb[t, s] = wm(xs, vs)
         for s in range(P):
             if not np.isfinite(B[t, s]):
                 continue

@@ -256,8 +256,10 @@ def test_header_segments(driver, tmp_path):
 def test_header_forward_backward_block(driver, tmp_path):
     """one wave up to 64 positions, 256 threads from 65 on (tests/test_gpu_fb_scores.py runs 64 and 65 positions, alone and together)"""
     ns = [1, 2, 63, 64, 65, 66, 127, 128, 129, 255, 256, 257, 600, 8192]
-    (a,), = run_cases(driver, tmp_path, [["block", len(ns)] + ns])
+    (a, c), = run_cases(driver, tmp_path, [["block", len(ns)] + ns])
     assert a == ("threads", [64 if n <= 64 else 256 for n in ns])
+    # the transcripts' chains (tests/test_gpu_netocc_scores.py runs 64, 65, 256, 257 and 514 positions, and 10 with 300 in one group)
+    assert c == ("chain_threads", [64 if n <= 64 else 256 if n <= 256 else 512 for n in ns])
 
 
 def test_header_has_no_device_include():

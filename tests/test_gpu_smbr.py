@@ -1,7 +1,9 @@
 """sMBR training on the device: sr_net_accuracies_corpus and sr_smbr_statistics_corpus against the numpy restatement
 (tests/smbr_reference.py, pinned by tests/test_smbr_cpu.py), sr_net_occupancies_corpus and themselves.  Tolerances: costs 1e-10
 relative; Abar and every gamma 1e-9 (1 + T_u) absolute -- the project's 1e-9 occupancy tolerance times the range of c - Abar --;
-statistics 1e-9 relative to sum |w x| (test_gpu_mmi._check_stats)."""
+statistics 1e-9 relative to sum |w x| (test_gpu_mmi._check_stats).  F, Abar, every gamma and a frame's sum also, wherever that is
+tighter, by the measured rule of tests/test_gpu_smbr_scores.py against the restatement's np.longdouble run (Rule below; the `RULE` lines
+say which of the two holds)."""
 import ctypes as C
 
 import numpy as np
@@ -9,6 +11,7 @@ import pytest
 
 from speechrecognition_amd import capi, synth
 from tests import mmi_reference as M
+from tests import netfb_cases as nc
 from tests import smbr_reference as SM
 from tests.test_gpu_mmi import DIM, EINVAL, ELIMIT, LEXICA, MULTI_LENS, TDP, _capi_lex, _check_stats, _model, _net, _off, _rel, several_groups
 from tests.test_mmi_cpu import criterion_task
@@ -32,15 +35,51 @@ def _refs(lex, lens, seed):
     return ref
 
 
-def _check_signed_items(g, count, state, weight, floor, K, tol):
+def _smbr(e, graph, tdp, wp, ref, scale, tag=None):
+    """(F, Abar, gamma) of the restatement in float64, with the longdouble run and its bounds beside it"""
+    with np.errstate(all="ignore"):
+        return Rule(SM.smbr(e, graph, tdp, wp, ref, scale), SM.smbr(e, graph, tdp, wp, ref, scale, dtype=nc.LD), tag)
+
+
+class Rule(tuple):
+    """(F, Abar, gamma) in float64 -- what the fixed tolerances are held against -- carrying the np.longdouble run (F80, A80, g80) and,
+    against it, the measured bound where it is tighter than the fixed one (nc.tighter): tolF, tolA, tolg [T, S], tols (a frame's sum).  Abar
+    and a frame's sum are held to the larger of their own float64 distance and gamma's, as in tests/test_gpu_smbr_scores.py."""
+
+    def __new__(cls, r64, r80, tag=None):
+        self = super().__new__(cls, r64)
+        (F, A, g), (self.F80, self.A80, self.g80) = r64, r80
+        fixed = 1e-9 * (1 + g.shape[0])
+        if np.isfinite(self.F80):
+            self.tolF = nc.tighter(1e-10 * max(1.0, abs(float(F))), F, self.F80, tag and tag + " F")
+            self.tolg = nc.tighter(fixed, g, self.g80, tag and tag + " gamma")
+            dw = nc.dist(g, self.g80)
+            self.tolA = float(nc.bound(max(nc.dist(A, self.A80), dw), max(float(self.A80), 1.0)))
+            self.tols = float(nc.bound(max(nc.dist(g.sum(axis=1), self.g80.sum(axis=1)), dw), 1.0))
+            self.tolA, self.tols = (x if x <= fixed else np.inf for x in (self.tolA, self.tols))  # (as nc.tighter)
+        else:
+            self.tolF = self.tolA = self.tols = 0.0
+            self.tolg = np.zeros(g.shape)
+        return self
+
+    def holds(self, cost, acc):
+        if not np.isfinite(self.F80):
+            return cost == self.F80 and acc == 0.0
+        return abs(nc.LD(cost) - self.F80) <= self.tolF and abs(nc.LD(acc) - self.A80) <= self.tolA
+
+
+def _check_signed_items(g, count, state, weight, floor, K, tol, g80=None, tolv=None):
     """one frame: the items are the mixtures with g != 0 and |g| >= floor, largest |g| first (ties: smaller id), at most K; a
-    mixture whose |g| lies within tol of the floor (or of 0) may be on either side; the order is checked on |weight|"""
+    mixture whose |g| lies within tol of the floor (or of 0) may be on either side; the order is checked on |weight|.  g80, tolv: the
+    longdouble run's gamma and the bound that holds against it (Rule)"""
     n = int(count)
     assert n <= K and not weight[n:].any() and not state[n:].any()
     ks, ws = state[:n].astype(int), weight[:n]
     assert len(set(ks.tolist())) == n
     for k, w in zip(ks, ws):
         assert w != 0.0 and abs(w) >= floor and abs(w - g[k]) <= tol, (k, w, g[k])
+        if g80 is not None:
+            assert abs(nc.LD(w) - g80[k]) <= tolv[k], (k, w, g80[k], tolv[k])
     for i in range(n - 1):
         a, b = abs(ws[i]), abs(ws[i + 1])
         assert a > b or (a == b and ks[i] < ks[i + 1])
@@ -66,7 +105,8 @@ def restated(tmp_path_factory, oracle_lib):
             res = []
             for u in range(len(LENS)):
                 a, b = int(off[u]), int(off[u + 1])
-                res.append(SM.smbr(o.score_matrix(feats[a:b]), M.free_graph(net), tdp, wp, ref[a:b].astype(np.int64), scale))
+                res.append(_smbr(o.score_matrix(feats[a:b]), M.free_graph(net), tdp, wp, ref[a:b].astype(np.int64), scale,
+                                 f"lexicon {li} penalties {pi} utterance {u}"))
             out[li, pi] = dict(lex=lex, mp=mp, feats=feats, ref=ref, off=off, res=res, tables=o.tables())
             o.close()
     return out
@@ -85,22 +125,27 @@ def test_against_restatement(li, pi, restated):
         for floor in (0.0, 1e-6):
             for K in (1, 3, S):
                 cost, acc, count, state, weight = corpus.net_accuracies(L, wp, ref, scale, capi.GMM_PREFILTER, floor, K)
-                for u, (F, A, g) in enumerate(r["res"]):
+                for u, rule in enumerate(r["res"]):
+                    F, A, g = rule
                     T = g.shape[0]
                     tol = 1e-9 * (1 + T)
                     print("utt", u, cost[u], F, acc[u], A)
                     assert _rel(cost[u], F) <= 1e-10 and abs(acc[u] - A) <= tol and 0.0 <= acc[u] <= T + tol
+                    assert rule.holds(cost[u], acc[u]), (u, cost[u], rule.F80, rule.tolF, acc[u], rule.A80, rule.tolA)
                     for t in range(T):
                         ft = int(off[u]) + t
-                        _check_signed_items(g[t], count[ft], state[ft], weight[ft], floor, K, tol)
+                        _check_signed_items(g[t], count[ft], state[ft], weight[ft], floor, K, tol, rule.g80[t], rule.tolg[t])
                         if K == S and floor == 0.0:
                             assert abs(weight[ft].sum()) <= tol
+                            assert abs(weight[ft].astype(nc.LD).sum() - rule.g80[t].sum()) <= rule.tols
         assert acc[4] == 0.0 and not count[int(off[4]):].any()  # every reference out of range
         for max_approx, floor in ((True, 0.0), (False, 1e-6)):
             cost, acc, num, den = corpus.smbr_statistics(L, wp, ref, scale, capi.GMM_PREFILTER, floor, max_approx)
             items = [[], []]
-            for u, (F, A, g) in enumerate(r["res"]):
+            for u, rule in enumerate(r["res"]):
+                F, A, g = rule
                 assert _rel(cost[u], F) <= 1e-10 and abs(acc[u] - A) <= 1e-9 * (1 + g.shape[0])
+                assert rule.holds(cost[u], acc[u]), (u, cost[u], rule.F80, acc[u], rule.A80)
                 items[0] += SM.signed_items(g, +1, floor)
                 items[1] += SM.signed_items(g, -1, floor)
             _check_stats(num, feats, items[0], r["tables"], max_approx)
@@ -218,15 +263,17 @@ def test_several_launch_groups(tmp_path, oracle_lib, monkeypatch):
     # utterance 4 is the second of the group (3, 5)
     u, a, b = 4, int(off[4]), int(off[5])
     o = oracle_lib.Oracle(mp, DIM, lex, tdp=TDP)
-    F, A, g = SM.smbr(o.score_matrix(feats[a:b]), M.free_graph(_net(lex)), TDP, wp, ref[a:b].astype(np.int64), scale)
+    rule = _smbr(o.score_matrix(feats[a:b]), M.free_graph(_net(lex)), TDP, wp, ref[a:b].astype(np.int64), scale, "several groups utterance 4")
+    F, A, g = rule
     o.close()
     cost, acc, count, state, weight = cut["accs"]
     tol = 1e-9 * (1 + b - a)
     print("several groups", cost[u], F, acc[u], A)
     assert _rel(cost[u], F) <= 1e-10 and abs(acc[u] - A) <= tol
     assert _rel(cut["stats"][0][u], F) <= 1e-10 and abs(cut["stats"][1][u] - A) <= tol
+    assert rule.holds(cost[u], acc[u]) and rule.holds(cut["stats"][0][u], cut["stats"][1][u])
     for t in range(b - a):
-        _check_signed_items(g[t], count[a + t], state[a + t], weight[a + t], 1e-6, 3, tol)
+        _check_signed_items(g[t], count[a + t], state[a + t], weight[a + t], 1e-6, 3, tol, rule.g80[t], rule.tolg[t])
 
 
 def _big_lexicon(n_positions, n_states, seed):
