@@ -701,6 +701,80 @@ struct FeaturePostProcessor {
     }
     features.swap(seq);
   }
+
+  // srgpu.h's view of this configuration (mean / stddev point into this object)
+  sr_feature_post_params params() const {
+    sr_feature_post_params q{};
+    q.n_static = (uint32_t)n_features_in_file; q.n_first = (uint32_t)n_features_first; q.n_second = (uint32_t)n_features_second;
+    q.deriv_step = (uint32_t)deriv_step;
+    q.energy_max_norm = energy_max_norm ? 1 : 0;
+    q.mean = mean.empty() ? nullptr : mean.data();
+    q.stddev = mean.empty() ? nullptr : stddev.data();
+    return q;
+  }
+
+  // The corpus that process_features on every utterance and sr_corpus_upload would give, bit for bit, made on the device from the
+  // static features [frames x n_features_in_file] (sr_corpus_from_cepstra).  Destroyed before `model`.
+  std::shared_ptr<sr_corpus> device_corpus(sr_model* model, const float* cepstra, const uint64_t* frame_off, uint32_t n_utts) const {
+    const sr_feature_post_params q = params();
+    sr_frontend* fe = nullptr;
+    check(sr_frontend_create(model, nullptr, &q, &fe));
+    std::shared_ptr<sr_frontend> own(fe, sr_frontend_destroy);
+    sr_corpus* c = nullptr;
+    check(sr_corpus_from_cepstra(fe, cepstra, frame_off, n_utts, &c));
+    return std::shared_ptr<sr_corpus>(c, sr_corpus_destroy);
+  }
+};
+
+// ---- the audio front end on the device (srgpu.h: sr_frontend_*): SignalAnalysis' MFCC stage as srgpu.h defines it, then
+// FeaturePostProcessor's stage bit for bit.  Samples or static features in, a resident corpus of `model` out; every corpus is
+// destroyed before the model, and so is this object.
+class FrontEnd {
+ public:
+  FrontEnd(sr_model* model, sr_mfcc_params const& mfcc, FeaturePostProcessor const& post) {
+    const sr_feature_post_params q = post.params();
+    sr_frontend* fe = nullptr;
+    check(sr_frontend_create(model, &mfcc, &q, &fe));
+    fe_.reset(fe, sr_frontend_destroy);
+    n_static_ = q.n_static;
+  }
+  uint64_t frames(uint64_t n_samples) const {
+    uint64_t T = 0;
+    check(sr_frontend_frames(fe_.get(), n_samples, &T));
+    return T;
+  }
+  // both stages; frame_off [n_utts + 1] receives the corpus's frame offsets
+  std::shared_ptr<sr_corpus> from_audio(std::vector<int16_t> const& samples, std::vector<uint64_t> const& sample_off,
+                                        std::vector<uint64_t>& frame_off) {
+    frame_off.assign(sample_off.size(), 0);
+    sr_corpus* c = nullptr;
+    check(sr_corpus_from_audio(fe_.get(), samples.data(), sample_off.data(), (uint32_t)sample_off.size() - 1, &c, frame_off.data()));
+    return std::shared_ptr<sr_corpus>(c, sr_corpus_destroy);
+  }
+  std::shared_ptr<sr_corpus> from_cepstra(std::vector<float> const& cepstra, std::vector<uint64_t> const& frame_off) {
+    sr_corpus* c = nullptr;
+    check(sr_corpus_from_cepstra(fe_.get(), cepstra.data(), frame_off.data(), (uint32_t)frame_off.size() - 1, &c));
+    return std::shared_ptr<sr_corpus>(c, sr_corpus_destroy);
+  }
+  // the MFCC stage alone: the static features [frames x n_cepstra], what read_feature_file reads from an .mm2 file
+  std::vector<float> mfcc(std::vector<int16_t> const& samples, std::vector<uint64_t> const& sample_off, std::vector<uint64_t>& frame_off) {
+    uint64_t total = 0;
+    for (size_t u = 0; u + 1 < sample_off.size(); u++) total += frames(sample_off[u + 1] - sample_off[u]);
+    std::vector<float> out((size_t)total * n_static_);
+    frame_off.assign(sample_off.size(), 0);
+    check(sr_mfcc_corpus(fe_.get(), samples.data(), sample_off.data(), (uint32_t)sample_off.size() - 1, out.data(), frame_off.data()));
+    return out;
+  }
+  // a resident corpus's features [frames x dim] (sr_corpus_download)
+  static std::vector<float> download(sr_corpus* c, uint64_t n_frames, uint32_t dim) {
+    std::vector<float> out((size_t)n_frames * dim);
+    check(sr_corpus_download(c, out.data()));
+    return out;
+  }
+
+ private:
+  std::shared_ptr<sr_frontend> fe_;
+  uint32_t n_static_ = 0;
 };
 
 // alignment dump: size_t max_aligns; size_t num_frames; AlignmentItem[num_frames * max_aligns] (Alignment.cpp:303-318)

@@ -645,6 +645,77 @@ SR_API int sr_lda_estimate(uint32_t E, uint32_t n_classes, const double* count, 
 SR_API int sr_corpus_splice_transform(sr_model* m, sr_corpus* c, sr_model* target, uint32_t context, const double* M /*[p x (E+1)]*/,
                                       sr_corpus** out);
 
+/* ---- the audio front end: PCM samples or static cepstra in, a resident corpus out -------------------------------------------------
+ * What SignalAnalysis does before the recogniser sees a frame (SignalAnalysis.cpp: pre-emphasis, Hamming window, FFT, mel filterbank,
+ * DCT; then process_features: deltas, normalisation), on the device.  A front end hangs on a model -- for its device and its
+ * dimension, like a lexicon -- and is destroyed before it.  mfcc == NULL makes one that takes cepstra only.
+ *
+ * The MFCC stage.  The reference's source is not what is matched here; this definition is (tests/frontend_reference.py restates it in
+ * float64).  An utterance of N samples has T = 0 frames if N < window, else T = 1 + (N - window) / shift (integer division); frame t
+ * covers samples [t shift, t shift + window), no padding.
+ *   pre-emphasis   y[n] = x[n] - preemphasis * x[n - 1] over the utterance, x[-1] = 0 before the utterance's first sample only
+ *   window         w[i] = 0.54 - 0.46 cos(2 pi i / (window - 1)); the frame is zero-extended to n_fft
+ *   power          P[k] = |X[k]|^2, k = 0 .. n_fft / 2, X the DFT of the windowed frame
+ *   filterbank     n_mel triangles whose n_mel + 2 edge frequencies are equally spaced in mel(f) = 2595 log10(1 + f / 700) between f_low
+ *                  and f_high; bin k (f_k = k sample_rate / n_fft) has the weight max(0, min((f_k - l) / (c - l), (r - f_k) / (r - c))) in
+ *                  the filter of edges l < c < r;  E_m = sum_k weight P[k]
+ *   logarithm      L_m = log(max(E_m, energy_floor))
+ *   DCT-II         c_i = sqrt(2 / n_mel) sum_m L_m cos(pi i (m + 1/2) / n_mel), i = 0 .. n_cepstra - 1; c_0 is the energy-like component
+ * Window, twiddles, filter weights and the DCT matrix (the factor folded in) are computed on the host in double and stored as float;
+ * the device works in FP32 on them, in an order of its own (a half-length complex transform of radix-4 stages; a filter's bins and a
+ * cepstrum's filters ascending).  No atomics: two identical calls return identical bits, and an utterance gives the same bits alone
+ * as inside any batch.
+ * Limits (SR_ELIMIT): n_fft a power of two in 64 .. 2048, window <= n_fft, n_mel <= 64, an utterance of more than 65535 frames.
+ * SR_EINVAL: shift == 0, window < 2, n_cepstra == 0 or > n_mel, a sample rate that is not positive and finite, f_low < 0,
+ * f_high > sample_rate / 2, f_low >= f_high, a filter without a bin of positive weight, energy_floor not positive and finite, a
+ * pre-emphasis that is not finite, flags != 0, n_cepstra != n_static.
+ *
+ * The post-processing stage is sr::FeaturePostProcessor::process_features (include/sr_sietill.hpp) bit for bit, utterance by utterance:
+ * the n_static statics; the deltas of the first n_first of them, frame a = min(max(t, deriv_step), T - 1) minus frame a - deriv_step (frame
+ * 0 if a < deriv_step); the delta-deltas of the first n_second deltas, the delta at frame min(t, T - 1 - deriv_step) + deriv_step (frame
+ * T - 1 where T <= deriv_step) minus the delta at t; with mean / stddev, (float)((double)x - mean[k]) and then (float)((double)x /
+ * stddev[k]); with energy_max_norm, component 0 minus its maximum over the utterance.  Float subtraction, FP64 subtraction and
+ * division are correctly rounded and a maximum has no order, so the device's rows carry the host loop's bits.
+ * SR_EINVAL: the model's dimension != n_static + n_first + n_second, n_static == 0, n_first > n_static, n_second > n_first,
+ * deriv_step == 0, only one of mean and stddev given.
+ *
+ * Every check comes before any launch; a refused call leaves *out NULL and the host outputs untouched.  An utterance without frames
+ * is allowed, and so is a corpus of none. */
+typedef struct {
+  double sample_rate;            /* Hz */
+  uint32_t window, shift;        /* samples */
+  uint32_t n_fft, n_mel, n_cepstra;
+  double f_low, f_high;          /* Hz: the filterbank's outer edges */
+  float preemphasis, energy_floor;
+  uint32_t flags;                /* 0 */
+} sr_mfcc_params;
+typedef struct {
+  uint32_t n_static, n_first, n_second, deriv_step;  /* SignalAnalysis.cpp:53-56: 12, 12, 1, 3 */
+  int32_t energy_max_norm;
+  const double* mean;            /* [n_static + n_first + n_second] each, or both NULL: no mean / deviation normalisation */
+  const double* stddev;
+} sr_feature_post_params;
+typedef struct sr_frontend sr_frontend;
+SR_API int sr_frontend_create(sr_model* m, const sr_mfcc_params* mfcc /*NULL: cepstra in only*/, const sr_feature_post_params* post,
+                              sr_frontend** out);
+SR_API int sr_frontend_destroy(sr_frontend* fe);
+/* *frames = T of an utterance of n_samples (SR_EINVAL for a front end without an MFCC stage) */
+SR_API int sr_frontend_frames(const sr_frontend* fe, uint64_t n_samples, uint64_t* frames);
+/* samples of utterance u: samples[sample_off[u] .. sample_off[u + 1]), sample_off[0] == 0 and non-decreasing (else SR_EINVAL).  *out: a
+ * resident corpus of the front end's model, both stages applied, with buffers of its own like sr_corpus_transform's result: accepted
+ * wherever a corpus of that model is, destroyed with sr_corpus_destroy before the model.  out_frame_off[n_utts + 1]: its frame offsets. */
+SR_API int sr_corpus_from_audio(sr_frontend* fe, const int16_t* samples, const uint64_t* sample_off, uint32_t n_utts, sr_corpus** out,
+                                uint64_t* out_frame_off /*[n_utts+1]*/);
+/* the post-processing stage alone, on static cepstra [frames x n_static] with sr_corpus_upload's frame_off (the reference's .mm2 files) */
+SR_API int sr_corpus_from_cepstra(sr_frontend* fe, const float* cepstra, const uint64_t* frame_off, uint32_t n_utts, sr_corpus** out);
+/* the MFCC stage alone, back to the host: out_cepstra [frames x n_cepstra] -- room for sum_u sr_frontend_frames(N_u) rows -- and the frame
+ * offsets; what a caller writes as .mm2 and estimates the normalisation's mean and deviation from */
+SR_API int sr_mfcc_corpus(sr_frontend* fe, const int16_t* samples, const uint64_t* sample_off, uint32_t n_utts, float* out_cepstra,
+                          uint64_t* out_frame_off /*[n_utts+1]*/);
+/* the features of any resident corpus -- uploaded, transformed, projected or a front end's -- back to the host, out [frames x dim of the
+ * corpus's model]; an asynchronous upload is waited for first */
+SR_API int sr_corpus_download(sr_corpus* c, float* out);
+
 /* ---- word posteriors and confidences: forward-backward over the recognition network --------------------------------
  * The network sr_recognize_corpus searches (Recognizer.cpp:103-232: the start hypothesis at word 0 position 0, in-word 0-1-2 jumps
  * with the penalty keyed on the DESTINATION state, every word end entering every word at position 0 or 1 with the word penalty --

@@ -41,6 +41,8 @@ SYMBOLS = [
     "sr_map_statistics_corpus", "sr_map_statistics_bw_corpus", "sr_model_map_adapt",
     "sr_mllt_statistics_corpus", "sr_mllt_statistics_bw_corpus", "sr_mllt_estimate",
     "sr_lda_statistics_corpus", "sr_lda_estimate", "sr_corpus_splice_transform",
+    "sr_frontend_create", "sr_frontend_destroy", "sr_frontend_frames", "sr_corpus_from_audio", "sr_corpus_from_cepstra", "sr_mfcc_corpus",
+    "sr_corpus_download",
     "sr_bigram_create", "sr_bigram_destroy", "sr_bigram_describe", "sr_recognize_bigram_corpus",
     "sr_bigram_word_posteriors_corpus", "sr_recognize_bigram_confidence_corpus",
     "sr_bigram_occupancies_corpus", "sr_bigram_mmi_statistics_corpus",
@@ -85,6 +87,19 @@ class SearchParams(C.Structure):
 
 class BigramParams(C.Structure):
     _fields_ = [("acoustic_pruning", C.c_float), ("lm_pruning", C.c_float), ("gmm_kernel", C.c_int), ("max_word_ends", C.c_uint32), ("flags", C.c_int)]
+
+
+class MfccParams(C.Structure):
+    """sr_mfcc_params"""
+    _fields_ = [("sample_rate", C.c_double), ("window", C.c_uint32), ("shift", C.c_uint32), ("n_fft", C.c_uint32), ("n_mel", C.c_uint32),
+                ("n_cepstra", C.c_uint32), ("f_low", C.c_double), ("f_high", C.c_double), ("preemphasis", C.c_float),
+                ("energy_floor", C.c_float), ("flags", C.c_uint32)]
+
+
+class FeaturePostParams(C.Structure):
+    """sr_feature_post_params"""
+    _fields_ = [("n_static", C.c_uint32), ("n_first", C.c_uint32), ("n_second", C.c_uint32), ("deriv_step", C.c_uint32),
+                ("energy_max_norm", C.c_int32), ("mean", C.c_void_p), ("stddev", C.c_void_p)]
 
 
 class Profile(C.Structure):
@@ -162,6 +177,13 @@ def lib():
         L.sr_lda_statistics_corpus.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp, vp]
         L.sr_lda_estimate.argtypes = [u32, u32, vp, vp, vp, u32, i32, dbl, vp, vp, vp]
         L.sr_corpus_splice_transform.argtypes = [vp, vp, vp, u32, vp, C.POINTER(vp)]
+        L.sr_frontend_create.argtypes = [vp, C.POINTER(MfccParams), C.POINTER(FeaturePostParams), C.POINTER(vp)]
+        L.sr_frontend_destroy.argtypes = [vp]
+        L.sr_frontend_frames.argtypes = [vp, u64, C.POINTER(u64)]
+        L.sr_corpus_from_audio.argtypes = [vp, vp, vp, u32, C.POINTER(vp), vp]
+        L.sr_corpus_from_cepstra.argtypes = [vp, vp, vp, u32, C.POINTER(vp)]
+        L.sr_mfcc_corpus.argtypes = [vp, vp, vp, u32, vp, vp]
+        L.sr_corpus_download.argtypes = [vp, vp]
         L.sr_word_posteriors_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, vp]
         L.sr_recognize_confidence_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, vp, vp, vp, vp, vp]
         L.sr_net_occupancies_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, vp, vp, vp]
@@ -421,6 +443,13 @@ class Model:
     def upload(self, feats, frame_off, asynchronous=False):
         return Corpus(self, feats, frame_off, asynchronous)
 
+    def frontend(self, mfcc, post):
+        """sr_frontend_create: the audio front end of this model.  mfcc: a dict of sr_mfcc_params' fields (sample_rate, window, shift,
+        n_fft, n_mel, n_cepstra, f_low, f_high, preemphasis, energy_floor) or None for cepstra in only; post: a dict of n_static,
+        n_first, n_second, deriv_step, energy_max_norm and optionally mean, stddev (f64[n_static + n_first + n_second]).  Close it
+        before the model."""
+        return FrontEnd(self, mfcc, post)
+
     def recognize_batch(self, lexicon, feats, frame_off, am_threshold, word_penalty, kernel=GMM_PREFILTER):
         """sr_recognize_batch: host buffers in, words out (fed asynchronously while the first chunks are scored)."""
         feats = np.ascontiguousarray(feats, dtype=np.float32)
@@ -650,6 +679,12 @@ class Corpus:
         if self.h:
             lib().sr_corpus_destroy(self.h)
             self.h = None
+
+    def download(self):
+        """sr_corpus_download: the resident features -> f32[n_frames, dim] (an asynchronous upload is waited for first)"""
+        out = np.empty((self.n_frames, self.model.dim), dtype=np.float32)
+        _check(lib().sr_corpus_download(self.h, _ptr(out)))
+        return out
 
     def score(self, kernel=GMM_PREFILTER):
         out = np.empty((self.n_frames, self.model.n_states), dtype=np.float64)
@@ -1245,6 +1280,82 @@ class Corpus:
         out = np.zeros(max(self.n_frames, 1), dtype=np.float64)
         _check(lib().sr_path_scores_corpus(self.model.h, self.h, _ptr(states), kernel, _ptr(out)))
         return out[: self.n_frames]
+
+
+class FrontEnd:
+    """sr_frontend handle: PCM samples or static cepstra in, a resident Corpus of the model out (Model.frontend)."""
+
+    def __init__(self, model, mfcc, post):
+        self.model = model
+        post = dict(post)
+        mean, stddev = post.pop("mean", None), post.pop("stddev", None)
+        self._mean = None if mean is None else np.ascontiguousarray(mean, dtype=np.float64)
+        self._stddev = None if stddev is None else np.ascontiguousarray(stddev, dtype=np.float64)
+        self.post = FeaturePostParams(mean=_ptr(self._mean), stddev=_ptr(self._stddev), **{k: int(v) for k, v in post.items()})
+        self.mfcc_params = None
+        if mfcc is not None:
+            ints = ("window", "shift", "n_fft", "n_mel", "n_cepstra", "flags")
+            self.mfcc_params = MfccParams(**{k: (int(v) if k in ints else float(v)) for k, v in mfcc.items()})
+        self.n_static = self.post.n_static
+        self.h = C.c_void_p()
+        _check(lib().sr_frontend_create(model.h, None if self.mfcc_params is None else C.byref(self.mfcc_params), C.byref(self.post),
+                                        C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().sr_frontend_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def frames(self, n_samples):
+        """sr_frontend_frames: the frames of an utterance of n_samples"""
+        n = C.c_uint64()
+        _check(lib().sr_frontend_frames(self.h, int(n_samples), C.byref(n)))
+        return n.value
+
+    def _corpus(self, handle, frame_off):
+        out = Corpus.__new__(Corpus)
+        out.model, out.frame_off, out.n_utts, out.n_frames = self.model, frame_off, len(frame_off) - 1, int(frame_off[-1])
+        out.h = handle
+        return out
+
+    def from_audio(self, samples, sample_off):
+        """sr_corpus_from_audio: int16 samples, utterance u's at sample_off[u] .. sample_off[u + 1] -> Corpus (its frame_off tells the
+        frames); close it before the model."""
+        samples = np.ascontiguousarray(samples, dtype=np.int16)
+        sample_off = np.ascontiguousarray(sample_off, dtype=np.uint64)
+        n = len(sample_off) - 1
+        assert len(samples) >= int(sample_off[-1])
+        frame_off = np.zeros(n + 1, dtype=np.uint64)
+        h = C.c_void_p()
+        _check(lib().sr_corpus_from_audio(self.h, _ptr(samples), _ptr(sample_off), n, C.byref(h), _ptr(frame_off)))
+        return self._corpus(h, frame_off)
+
+    def from_cepstra(self, cepstra, frame_off):
+        """sr_corpus_from_cepstra: static cepstra f32[frames, n_static] -> Corpus; close it before the model."""
+        cepstra = np.ascontiguousarray(cepstra, dtype=np.float32)
+        frame_off = np.ascontiguousarray(frame_off, dtype=np.uint64)
+        assert cepstra.size == int(frame_off[-1]) * self.n_static
+        h = C.c_void_p()
+        _check(lib().sr_corpus_from_cepstra(self.h, _ptr(cepstra), _ptr(frame_off), len(frame_off) - 1, C.byref(h)))
+        return self._corpus(h, frame_off)
+
+    def mfcc(self, samples, sample_off):
+        """sr_mfcc_corpus: the static cepstra alone -> (f32[frames, n_cepstra], frame_off u64[n_utts + 1])"""
+        samples = np.ascontiguousarray(samples, dtype=np.int16)
+        sample_off = np.ascontiguousarray(sample_off, dtype=np.uint64)
+        n = len(sample_off) - 1
+        assert len(samples) >= int(sample_off[-1])
+        total = sum(self.frames(int(sample_off[u + 1]) - int(sample_off[u])) for u in range(n))
+        out = np.empty((total, self.n_static), dtype=np.float32)
+        frame_off = np.zeros(n + 1, dtype=np.uint64)
+        _check(lib().sr_mfcc_corpus(self.h, _ptr(samples), _ptr(sample_off), n, _ptr(out), _ptr(frame_off)))
+        return out, frame_off
 
 
 class Lexicon:

@@ -1,0 +1,211 @@
+// frontend.hip -- the audio front end's kernels: MFCC from PCM samples, and SignalAnalysis::process_features (static | delta |
+// delta-delta, mean / deviation, energy maximum) on resident cepstra.  The definitions are in include/srgpu.h (sr_frontend_*); the
+// host side -- checks, tables, entry points -- is frontend.cpp.
+//
+// mfcc_kernel.  A workgroup takes a span of consecutive frames of one utterance.  It reads the span's samples once, pre-emphasises
+// them (y[n] = x[n] - alpha x[n - 1], x[-1] = 0 before the utterance's first sample only, so a frame never knows where spans begin)
+// and keeps them in the LDS as floats.  Then every wave64 takes frames of the span in turn, one frame at a time, in LDS of its own:
+//   the windowed frame, zero-extended to n_fft, as M = n_fft / 2 complex points z[n] = (x[2n], x[2n + 1]);
+//   Z = FFT_M(z): Stockham stages of radix 4 (and one of radix 2 when log2 M is odd) between two buffers, so no digit reversal; the
+//   twiddles come from the host's table;
+//   X[k] = E[k] + w^k O[k], E = (Z[k] + conj Z[M - k]) / 2, O = (Z[k] - conj Z[M - k]) / 2i, w = exp(-2 pi i / n_fft), k = 0 .. M;
+//   P[k] = |X[k]|^2; lane m sums filter m's bins in ascending order and takes the clamped logarithm; lane i sums cepstrum i over
+//   the filters in ascending order.
+// No atomics, and nothing a frame computes depends on its span or its batch: the same samples give the same bits anywhere.
+//
+// Compiled with -ffp-contract=off: the post-processing is specified to the bit (float subtractions, FP64 subtraction and division),
+// and the MFCC stage's bits must not depend on what the compiler may fuse around a frame.
+#include <hip/hip_runtime.h>
+
+#include "kernels.h"
+
+namespace srgpu {
+
+#pragma clang fp contract(off)
+
+namespace {
+
+__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+
+__global__ __launch_bounds__(256) void mfcc_kernel(MfccArgs a, uint32_t y_floats) {
+  extern __shared__ float lds[];
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
+  const uint32_t M = a.n_fft >> 1;
+  const uint2 sp = a.spans[blockIdx.x];
+  const uint64_t f0 = a.frame_off[sp.x];
+  const uint32_t T = (uint32_t)(a.frame_off[sp.x + 1] - f0), t0 = sp.y;
+  const uint32_t nf = min(a.span_frames, T - t0);
+  const uint32_t n_samp = (nf - 1) * a.shift + a.window;  // <= mfcc_span_cap() by the choice of span_frames
+  const uint64_t first = (uint64_t)t0 * a.shift;          // the span's first sample within the utterance
+  const int16_t* x = a.samples + a.sample_off[sp.x] + first;
+  float* y = lds;
+  for (uint32_t i = threadIdx.x; i < n_samp; i += blockDim.x) {
+    const float prev = first + i ? (float)x[(int64_t)i - 1] : 0.0f;
+    y[i] = (float)x[i] - a.preemphasis * prev;
+  }
+  float* mine = lds + y_floats + (size_t)wave * (4 * M + 64);
+  float2* A = reinterpret_cast<float2*>(mine);
+  float2* B = A + M;
+  float* L = mine + 4 * M;
+  __syncthreads();
+  const uint32_t rounds = (a.span_frames + n_waves - 1) / n_waves;
+  for (uint32_t r = 0; r < rounds; r++) {
+    // every wave goes through every barrier: one without a frame left computes frame 0 again and stores nothing
+    const uint32_t fi = r * n_waves + wave;
+    const bool active = fi < nf;
+    const float* yf = y + (active ? fi : 0) * a.shift;
+    for (uint32_t n = lane; n < M; n += 64) {
+      const uint32_t i0 = 2 * n, i1 = 2 * n + 1;
+      A[n] = make_float2(i0 < a.window ? a.win[i0] * yf[i0] : 0.0f, i1 < a.window ? a.win[i1] * yf[i1] : 0.0f);
+    }
+    float2 *src = A, *dst = B;
+    uint32_t Ns = 1;
+    for (; Ns * 4 <= M; Ns *= 4) {
+      __syncthreads();
+      const uint32_t q = M >> 2, tstep = M / (2 * Ns);
+      for (uint32_t j = lane; j < q; j += 64) {
+        const uint32_t k = j & (Ns - 1);
+        const float2 v0 = src[j], v1 = cmul(src[j + q], a.twiddle[k * tstep]), v2 = cmul(src[j + 2 * q], a.twiddle[2 * k * tstep]),
+                     v3 = cmul(src[j + 3 * q], a.twiddle[3 * k * tstep]);
+        const float2 s02 = cadd(v0, v2), d02 = csub(v0, v2), s13 = cadd(v1, v3), d13 = csub(v1, v3);
+        const float2 md13 = make_float2(d13.y, -d13.x);  // -i (v1 - v3)
+        const uint32_t j0 = ((j - k) << 2) + k;
+        dst[j0] = cadd(s02, s13);
+        dst[j0 + Ns] = cadd(d02, md13);
+        dst[j0 + 2 * Ns] = csub(s02, s13);
+        dst[j0 + 3 * Ns] = csub(d02, md13);
+      }
+      float2* t = src; src = dst; dst = t;
+    }
+    if (Ns < M) {  // log2 M is odd: Ns == M / 2
+      __syncthreads();
+      for (uint32_t j = lane; j < Ns; j += 64) {
+        const float2 v0 = src[j], v1 = cmul(src[j + Ns], a.twiddle[2 * j]);
+        dst[j] = cadd(v0, v1);
+        dst[j + Ns] = csub(v0, v1);
+      }
+      float2* t = src; src = dst; dst = t;
+    }
+    __syncthreads();
+    float* P = reinterpret_cast<float*>(dst);  // [M + 1] of the buffer the transform is not in
+    for (uint32_t k = lane; k <= M; k += 64) {
+      const float2 zk = src[k & (M - 1)], zm = src[(M - k) & (M - 1)];
+      const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
+      const float2 o = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
+      const float2 xk = cadd(e, cmul(a.twiddle[k], o));
+      P[k] = xk.x * xk.x + xk.y * xk.y;
+    }
+    __syncthreads();
+    if (lane < a.n_mel) {
+      const float* w = a.mel_w + a.mel_off[lane];
+      const float* p = P + a.mel_first[lane];
+      const uint32_t n = a.mel_count[lane];
+      float e = 0.0f;
+      for (uint32_t j = 0; j < n; j++) e += w[j] * p[j];
+      L[lane] = logf(fmaxf(e, a.energy_floor));
+    }
+    __syncthreads();
+    if (lane < a.n_cepstra && active) {
+      const float* d = a.dct + lane * a.n_mel;
+      float c = 0.0f;
+      for (uint32_t m = 0; m < a.n_mel; m++) c += d[m] * L[m];
+      a.out[(f0 + t0 + fi) * a.n_cepstra + lane] = c;
+    }
+    __syncthreads();
+  }
+}
+
+// the utterance of frame f: the last u with frame_off[u] <= f (an empty utterance is never it)
+__device__ __forceinline__ uint32_t utterance_of(const uint64_t* frame_off, uint32_t n_utts, uint64_t f) {
+  uint32_t lo = 0, hi = n_utts;  // frame_off[lo] <= f < frame_off[hi]
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (frame_off[mid] <= f) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// a thread per (frame, output component): FeaturePostProcessor::process_features' statics, deltas and normalisation
+__global__ __launch_bounds__(256) void feature_post_kernel(FeaturePostArgs a) {
+  const uint32_t nt = a.n_static + a.n_first + a.n_second, nf = a.n_static;
+  const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= a.n_frames * nt) return;
+  const uint64_t f = e / nt;
+  const uint32_t c = (uint32_t)(e - f * nt);
+  const uint32_t u = utterance_of(a.frame_off, a.n_utts, f);
+  const uint64_t f0 = a.frame_off[u];
+  const uint32_t T = (uint32_t)(a.frame_off[u + 1] - f0), t = (uint32_t)(f - f0), step = a.step;
+  const float* s = a.cepstra + f0 * nf;
+  // delta of component k at frame t: window clamped at the start
+  auto delta = [&](uint32_t tt, uint32_t k) {
+    const uint32_t hi = min(max(tt, step), T - 1), lo = hi >= step ? hi - step : 0;
+    return s[(uint64_t)hi * nf + k] - s[(uint64_t)lo * nf + k];
+  };
+  float v;
+  if (c < nf) {
+    v = s[(uint64_t)t * nf + c];
+  } else if (c < nf + a.n_first) {
+    v = delta(t, c - nf);
+  } else {  // from the deltas, window clamped at the end
+    const uint32_t k = c - nf - a.n_first, ahead = T > step ? min(t, T - 1 - step) + step : T - 1;
+    v = delta(ahead, k) - delta(t, k);
+  }
+  if (a.mean) {
+    v = (float)((double)v - a.mean[c]);
+    v = (float)((double)v / a.stddev[c]);
+  }
+  a.out[e] = v;
+}
+
+// a workgroup per utterance: component 0 minus its maximum over the utterance.  The host loop keeps the first frame that reaches
+// the maximum (it replaces on `<` alone), which tells -0 from +0; the pairs (value, frame) are reduced to the same one.
+__global__ __launch_bounds__(256) void energy_max_kernel(const uint64_t* frame_off, uint32_t nt, float* out) {
+  __shared__ float sv[256];
+  __shared__ uint32_t si[256];
+  const uint64_t f0 = frame_off[blockIdx.x];
+  const uint32_t T = (uint32_t)(frame_off[blockIdx.x + 1] - f0);
+  float* x = out + f0 * nt;
+  float bv = -INFINITY;
+  uint32_t bi = 0xFFFFFFFFu;
+  for (uint32_t t = threadIdx.x; t < T; t += 256) {
+    const float v = x[(uint64_t)t * nt];
+    if (bv < v || (bv == v && t < bi)) { bv = v; bi = t; }
+  }
+  sv[threadIdx.x] = bv;
+  si[threadIdx.x] = bi;
+  __syncthreads();
+  for (uint32_t h = 128; h > 0; h >>= 1) {
+    if (threadIdx.x < h) {
+      const float v = sv[threadIdx.x + h];
+      const uint32_t i = si[threadIdx.x + h];
+      if (sv[threadIdx.x] < v || (sv[threadIdx.x] == v && i < si[threadIdx.x])) { sv[threadIdx.x] = v; si[threadIdx.x] = i; }
+    }
+    __syncthreads();
+  }
+  const float mx = sv[0];
+  for (uint32_t t = threadIdx.x; t < T; t += 256) x[(uint64_t)t * nt] -= mx;
+}
+
+}  // namespace
+
+hipError_t launch_mfcc(const MfccArgs& a, hipStream_t stream) {
+  if (a.n_spans == 0) return hipSuccess;
+  const uint32_t waves = mfcc_waves(a.n_fft), M = a.n_fft / 2;
+  const uint32_t y_floats = ((a.span_frames - 1) * a.shift + a.window + 3) & ~3u;
+  const size_t lds_bytes = sizeof(float) * ((size_t)y_floats + (size_t)waves * (4 * M + 64));
+  hipLaunchKernelGGL(mfcc_kernel, dim3(a.n_spans), dim3(64 * waves), lds_bytes, stream, a, y_floats);
+  return hipGetLastError();
+}
+
+hipError_t launch_feature_post(const FeaturePostArgs& a, hipStream_t stream) {
+  if (a.n_frames == 0) return hipSuccess;
+  const uint64_t n = a.n_frames * (a.n_static + a.n_first + a.n_second);
+  hipLaunchKernelGGL(feature_post_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+  if (a.energy_max_norm)
+    hipLaunchKernelGGL(energy_max_kernel, dim3(a.n_utts), dim3(256), 0, stream, a.frame_off, a.n_static + a.n_first + a.n_second, a.out);
+  return hipGetLastError();
+}
+
+}  // namespace srgpu

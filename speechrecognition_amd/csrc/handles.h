@@ -270,6 +270,20 @@ struct sr_lexicon {
   DevBuf<uint2> w_states;
 };
 
+// The audio front end of a model (sr_frontend_*, frontend.cpp): the parameters as checked and the MFCC stage's tables
+struct sr_frontend {
+  sr_model* model = nullptr;
+  bool has_mfcc = false;            // false: cepstra in only
+  sr_mfcc_params mfcc{};
+  sr_feature_post_params post{};    // (mean / stddev point at nothing: the device copies below are what is used)
+  bool normalise = false;
+  uint32_t span_frames = 1;         // frames per workgroup of mfcc_kernel
+  DevBuf<float> win, mel_w, dct;
+  DevBuf<float2> twiddle;
+  DevBuf<uint32_t> mel_first, mel_count, mel_off;
+  DevBuf<double> mean, stddev;
+};
+
 struct sr_bigram {
   sr_model* model = nullptr;
   srgpu::BigramArgs net{};  // the search net (kernels.h; build_bigram_net): only its network fields set, pointing into the buffers below

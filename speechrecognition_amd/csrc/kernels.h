@@ -971,4 +971,35 @@ hipError_t launch_lda_class_sums(const LdaArgs& a, hipStream_t stream);  // segm
 hipError_t launch_lda_project(const float* feats, const uint32_t* frame_span, uint64_t n_frames, uint32_t dim, uint32_t context,
                               const double* M, uint32_t p, float* out, hipStream_t stream);
 
+// ---- the audio front end (frontend.hip) -------------------------------------------------------------------------------------------
+// MFCC: one workgroup per span of at most span_frames consecutive frames of one utterance, one wave64 per frame at a time.
+struct MfccArgs {
+  const int16_t* samples; const uint64_t* sample_off;  // device: the utterances' samples, back to back
+  const uint64_t* frame_off;                           // device [n_utts + 1]
+  const uint2* spans; uint32_t n_spans;                // device: (utterance, first frame) of every workgroup
+  uint32_t span_frames;                                // frames a workgroup covers: (span_frames - 1) shift + window <= mfcc_span_cap()
+  uint32_t window, shift, n_fft, n_mel, n_cepstra;
+  float preemphasis, energy_floor;
+  // tables, device, computed on the host in double and stored as float
+  const float* win;                                    // [window]
+  const float2* twiddle;                               // [n_fft] (cos, -sin)(2 pi n / n_fft)
+  const uint32_t* mel_first; const uint32_t* mel_count; const uint32_t* mel_off;  // [n_mel] a filter's bins and where its weights begin
+  const float* mel_w;                                  // the filters' weights, filter by filter, bins ascending
+  const float* dct;                                    // [n_cepstra][n_mel], sqrt(2 / n_mel) folded in
+  float* out;                                          // [frames][n_cepstra]
+};
+constexpr uint32_t mfcc_span_cap() { return 4096; }    // pre-emphasised samples a workgroup keeps in the LDS
+constexpr uint32_t mfcc_waves(uint32_t n_fft) { return n_fft <= 1024 ? 4 : 2; }  // waves per workgroup: at most 48 KiB of LDS
+hipError_t launch_mfcc(const MfccArgs& a, hipStream_t stream);
+// FeaturePostProcessor::process_features on every utterance: static | delta | delta-delta, mean / deviation (NULL: none), then the
+// energy maximum of component 0.  cepstra [frames][n_static] -> out [frames][n_static + n_first + n_second]
+struct FeaturePostArgs {
+  const float* cepstra; const uint64_t* frame_off; uint32_t n_utts; uint64_t n_frames;
+  uint32_t n_static, n_first, n_second, step;
+  const double* mean; const double* stddev;
+  int energy_max_norm;
+  float* out;
+};
+hipError_t launch_feature_post(const FeaturePostArgs& a, hipStream_t stream);
+
 }  // namespace srgpu

@@ -2,7 +2,7 @@
 
 The host translation units (srgpu_api.cpp: handles, packing, shard/gather glue, the traceback walk; mixset.cpp: the
 MIXSET parser / writer / host finalize; feeder.cpp: feeder, sr_shard_utterances, the multi-device driver; fmllr.cpp: the fMLLR
-estimate) are compiled with
+estimate; frontend.cpp: the front end's checks and tables) are compiled with
 -fsanitize=address,undefined (device code untouched: -fno-gpu-sanitize) and linked with the regular kernel objects into
 csrc/build/asan/libsrgpu_asan.so; tests/cpp/host_mirror_driver.cpp (include/sr_sietill.hpp: lexicon, edit distance, feature
 post-processing, alignment dump) is built the same way.  Then the CPU tests of the boundary run against that library in a
@@ -25,7 +25,7 @@ from speechrecognition_amd import build as B  # noqa: E402
 
 OUT = os.path.join(B.CSRC, "build", "asan")
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-shared-libsan"]
-HOST_UNITS = ["srgpu_api.cpp", "mixset.cpp", "feeder.cpp", "fmllr.cpp"]
+HOST_UNITS = ["srgpu_api.cpp", "mixset.cpp", "feeder.cpp", "fmllr.cpp", "frontend.cpp"]
 # (test_fmllr_cpu.py's driver test links tests/cpp/fmllr_driver.cpp against the regular libsrgpu.so: in this run it is the only
 # fMLLR test that does not go through the sanitized estimate)
 TESTS = ["tests/test_capi_cpu.py", "tests/test_traceback_cpu.py", "tests/test_sanitized_host_paths.py", "tests/test_fmllr_cpu.py"]
