@@ -514,6 +514,7 @@ class Recognizer {
 // begin() opens an utterance; push() hands over new frames of one or several open utterances (one scoring and one search launch
 // per call); partial() is what recognizeSequence_pruned returns for the frames pushed so far; end() returns its result on the
 // whole utterance and frees the id.  Errors are thrown as std::runtime_error with sr_last_error()'s text.
+class FrontEnd;
 class StreamingRecognizer {
  public:
   StreamingRecognizer(Lexicon const& lexicon, MixtureModel& scorer, TdpModel const& tdp_model, double am_threshold = 20.0,
@@ -557,6 +558,15 @@ class StreamingRecognizer {
     const uint64_t off[2] = {0, n_frames};
     check(sr_stream_push(s_, 1, &id, frames, off));
   }
+  // Audio in (srgpu.h: sr_stream_push_audio): with a front end attached -- while no utterance is open; it outlives this object's
+  // use of it -- an utterance takes its samples as they arrive, in pieces of any size; the rows that became ready are searched.
+  // finish_audio() before end().  An utterance takes samples or frames, not both.
+  void set_frontend(FrontEnd& fe);
+  void push_audio(uint32_t id, const int16_t* samples, size_t n_samples) {
+    const uint64_t off[2] = {0, n_samples};
+    check(sr_stream_push_audio(s_, 1, &id, samples, off, nullptr, 0, nullptr));
+  }
+  void finish_audio(uint32_t id) { check(sr_stream_finish_audio(s_, 1, &id, nullptr, 0, nullptr)); }
   // new frames of several utterances back to back: ids[i] owns rows [frame_off[i], frame_off[i+1])
   void push(std::vector<uint32_t> const& ids, const float* frames, std::vector<uint64_t> const& frame_off) {
     if (frame_off.size() != ids.size() + 1) throw std::runtime_error("StreamingRecognizer::push: frame_off needs ids.size() + 1 entries");
@@ -771,11 +781,14 @@ class FrontEnd {
     check(sr_corpus_download(c, out.data()));
     return out;
   }
+  sr_frontend* handle() const { return fe_.get(); }
 
  private:
   std::shared_ptr<sr_frontend> fe_;
   uint32_t n_static_ = 0;
 };
+
+inline void StreamingRecognizer::set_frontend(FrontEnd& fe) { check(sr_stream_set_frontend(s_, fe.handle())); }
 
 // alignment dump: size_t max_aligns; size_t num_frames; AlignmentItem[num_frames * max_aligns] (Alignment.cpp:303-318)
 inline void write_alignment(std::ostream& out, std::vector<AlignmentItem> const& alignment, size_t max_aligns) {
@@ -1882,6 +1895,13 @@ class StreamingLinearSearch {
     check(sr_bigram_stream_push(s_, 1, &id, frames, off));
   }
   // new frames of several utterances back to back: ids[i] owns rows [frame_off[i], frame_off[i+1])
+  // audio in, as StreamingRecognizer's (srgpu.h: sr_bigram_stream_push_audio)
+  void set_frontend(FrontEnd& fe) { check(sr_bigram_stream_set_frontend(s_, fe.handle())); }
+  void push_audio(uint32_t id, const int16_t* samples, size_t n_samples) {
+    const uint64_t off[2] = {0, n_samples};
+    check(sr_bigram_stream_push_audio(s_, 1, &id, samples, off, nullptr, 0, nullptr));
+  }
+  void finish_audio(uint32_t id) { check(sr_bigram_stream_finish_audio(s_, 1, &id, nullptr, 0, nullptr)); }
   void push(std::vector<uint32_t> const& ids, const float* frames, std::vector<uint64_t> const& frame_off) {
     if (frame_off.size() != ids.size() + 1) throw std::runtime_error("StreamingLinearSearch::push: frame_off needs ids.size() + 1 entries");
     check(sr_bigram_stream_push(s_, (uint32_t)ids.size(), ids.data(), frames, frame_off.data()));

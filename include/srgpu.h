@@ -712,6 +712,56 @@ SR_API int sr_corpus_from_cepstra(sr_frontend* fe, const float* cepstra, const u
  * offsets; what a caller writes as .mm2 and estimates the normalisation's mean and deviation from */
 SR_API int sr_mfcc_corpus(sr_frontend* fe, const int16_t* samples, const uint64_t* sample_off, uint32_t n_utts, float* out_cepstra,
                           uint64_t* out_frame_off /*[n_utts+1]*/);
+
+/* ---- streaming from audio: PCM samples into a stream set, the front end on the device ------------------------------------------------
+ * With a front end attached, a stream set takes an utterance's samples as they arrive, in pieces of any size, instead of finished
+ * feature rows.  step = deriv_step.  An utterance fed as audio has received N samples so far and has S = sr_frontend_frames(N) static
+ * frames.
+ *   before the finish  frames 0 .. S - 1 - step have been searched (none while S <= step): row t needs the statics t - step .. t + step
+ *                      and nothing else, and every clamp of the post-processing that involves T is inactive while static t + step exists;
+ *   after the finish   all T = S frames have been searched, the last up to `step` rows with the clamped windows of the now-known T.
+ * The rows.  With energy_max_norm == 0, row t is exactly row t of sr_corpus_from_audio on the whole utterance, bit for bit, for every
+ * way of cutting the samples into pushes -- one sample at a time, pushes that complete no frame, and shift > window (the samples between
+ * two frames are passed over, but the pre-emphasis still reads the one before a frame's first) included.  So the words and the
+ * traceback are sr_recognize_corpus' (sr_recognize_bigram_corpus') on that corpus.
+ * The energy maximum, with energy_max_norm != 0.  Only this needs the whole utterance; it has a causal replacement.  Component 0 of
+ * row t is the value the front end produces without the maximum (the static, mean / stddev applied) minus m(t): the maximum of that
+ * same value over frames 0 .. min(t + step, T - 1), kept the way the host loop keeps it -- replaced on `<` alone, so the first frame
+ * that reaches it wins and -0 is told from +0.  One float subtraction; it does not depend on how the samples were cut.  It equals the
+ * batch's bits whenever the utterance's maximum lies in its first step + 1 frames.  Otherwise it is NOT the batch's value: rows before
+ * frame (argmax - step) carry a smaller maximum than sr_corpus_from_audio subtracts.
+ *
+ * sr_stream_set_frontend   attaches `fe` (NULL detaches) -- only while no id is open; the front end must belong to the stream set's model
+ *                          and have an MFCC stage; it is destroyed after the stream set.  Device memory: max_streams x (2 step n_static + 1)
+ *                          floats, the last 2 step statics and the running maximum of every slot.
+ * sr_stream_push_audio     n utterances, ids[n], each at most once; their new samples back to back, entry i's at samples[sample_off[i] ..
+ *                          sample_off[i + 1]), sample_off[0] == 0, an empty range allowed.  The rows that became ready are searched
+ *                          before it returns (one launch of stream_frontend_kernel, then the scoring and the search of sr_stream_push; a
+ *                          push that readies no row launches neither of those).  out_feats (may be NULL): those rows, [rows x dim], entry
+ *                          i's at out_frame_off[i] .. out_frame_off[i + 1] (out_frame_off [n + 1], may be NULL); cap_rows: the rows
+ *                          out_feats holds -- fewer than the push readies is SR_EINVAL, with the count in the error text and in
+ *                          out_frame_off[n] (it is sum_i of max(S_i' - step, 0) - max(S_i - step, 0), computable on the host).
+ * sr_stream_finish_audio   emits the last rows of the n utterances; afterwards the ids take no more audio.  sr_stream_partial, _stable
+ *                          and _end work as before on what has been searched (_partial's *frames is max(S - step, 0) before the finish).
+ * An id is an audio id from its first sr_stream_push_audio (or _finish_audio) and a feature id from its first sr_stream_push: the other
+ * kind of push on it is SR_EINVAL.  sr_stream_end on an audio id that was not finished is SR_EINVAL and leaves the id open.  max_frames
+ * bounds T (SR_ELIMIT).  Every check comes before any launch; a refused call changes no utterance, its carried samples included.
+ * Other errors (SR_EINVAL): no front end attached, an unknown, ended or finished id, an id twice in one call, sample_off[0] != 0 or
+ * falling.  The host keeps fewer than `window` samples (and the one before them) per utterance between pushes and uploads them in
+ * front of the new ones.  Threading as for the stream set.  Stream sets without a front end, and ids fed with rows, behave as before. */
+SR_API int sr_stream_set_frontend(sr_stream* s, sr_frontend* fe);
+SR_API int sr_stream_push_audio(sr_stream* s, uint32_t n, const uint32_t* ids, const int16_t* samples, const uint64_t* sample_off,
+                                float* out_feats /*optional*/, uint64_t cap_rows, uint64_t* out_frame_off /*[n+1], optional*/);
+SR_API int sr_stream_finish_audio(sr_stream* s, uint32_t n, const uint32_t* ids, float* out_feats /*optional*/, uint64_t cap_rows,
+                                  uint64_t* out_frame_off /*[n+1], optional*/);
+/* the same for the bigram stream set (declared below) */
+struct sr_bigram_stream;
+SR_API int sr_bigram_stream_set_frontend(struct sr_bigram_stream* s, sr_frontend* fe);
+SR_API int sr_bigram_stream_push_audio(struct sr_bigram_stream* s, uint32_t n, const uint32_t* ids, const int16_t* samples,
+                                       const uint64_t* sample_off, float* out_feats /*optional*/, uint64_t cap_rows,
+                                       uint64_t* out_frame_off /*[n+1], optional*/);
+SR_API int sr_bigram_stream_finish_audio(struct sr_bigram_stream* s, uint32_t n, const uint32_t* ids, float* out_feats /*optional*/,
+                                         uint64_t cap_rows, uint64_t* out_frame_off /*[n+1], optional*/);
 /* the features of any resident corpus -- uploaded, transformed, projected or a front end's -- back to the host, out [frames x dim of the
  * corpus's model]; an asynchronous upload is waited for first */
 SR_API int sr_corpus_download(sr_corpus* c, float* out);

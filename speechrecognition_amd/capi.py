@@ -52,6 +52,8 @@ SYMBOLS = [
     "sr_stream_stable", "sr_bigram_stream_stable", "sr_commit_points",
     "sr_bigram_stream_open", "sr_bigram_stream_begin", "sr_bigram_stream_push", "sr_bigram_stream_partial", "sr_bigram_stream_end",
     "sr_bigram_stream_destroy",
+    "sr_stream_set_frontend", "sr_stream_push_audio", "sr_stream_finish_audio",
+    "sr_bigram_stream_set_frontend", "sr_bigram_stream_push_audio", "sr_bigram_stream_finish_audio",
     "sr_probe_fp16_denormals", "sr_probe_fp16_accumulation", "sr_prefilter_masks", "sr_prefilter_range_frames",
     "sr_refine_masks", "sr_refine_geometry",
     "sr_gather_words", "sr_recognize_corpus_scores", "sr_recognize_bigram_corpus_scores", "sr_bigram_route",
@@ -221,6 +223,10 @@ def lib():
         L.sr_bigram_stream_partial.argtypes = [vp, u32, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(u64)]
         L.sr_bigram_stream_end.argtypes = [vp, u32, vp, vp, vp, u32, C.POINTER(u32)]
         L.sr_bigram_stream_destroy.argtypes = [vp]
+        for fn in ("sr_stream", "sr_bigram_stream"):
+            getattr(L, fn + "_set_frontend").argtypes = [vp, vp]
+            getattr(L, fn + "_push_audio").argtypes = [vp, u32, vp, vp, vp, vp, u64, vp]
+            getattr(L, fn + "_finish_audio").argtypes = [vp, u32, vp, vp, u64, vp]
         L.sr_probe_fp16_denormals.argtypes = [i32, C.POINTER(i32)]
         L.sr_probe_fp16_accumulation.argtypes = [i32, C.POINTER(i32), C.POINTER(dbl)]
         L.sr_prefilter_masks.argtypes = [vp, vp, u64, i32, C.POINTER(u32), vp, u64]
@@ -535,7 +541,9 @@ class _StreamSet:
     def __init__(self, model, net, params, max_streams, max_frames):
         self.model = model
         self.max_frames = int(max_frames)
-        self.frames = {}  # frames pushed per open id
+        self.frames = {}  # frames pushed (searched, for an id fed as audio) per open id
+        self.samples = {}  # samples pushed per open id fed as audio
+        self.frontend = None
         self.h = C.c_void_p()
         _check(getattr(lib(), self._fn + "_open")(model.h, net.h, C.byref(params), max_streams, max_frames, C.byref(self.h)))
 
@@ -544,6 +552,7 @@ class _StreamSet:
         i = C.c_uint32()
         _check(getattr(lib(), self._fn + "_begin")(self.h, C.byref(i)))
         self.frames[i.value] = 0
+        self.samples.pop(i.value, None)
         return i.value
 
     def push(self, frames):
@@ -555,6 +564,50 @@ class _StreamSet:
         _check(getattr(lib(), self._fn + "_push")(self.h, len(ids), _ptr(ids), _ptr(feats) if len(feats) else None, _ptr(off)))
         for i, f in zip(ids, parts):
             self.frames[int(i)] += len(f)
+
+    def set_frontend(self, fe):
+        """sr_stream_set_frontend: the front end push_audio runs (None detaches); only while no id is open.  Close it after the set."""
+        _check(getattr(lib(), self._fn + "_set_frontend")(self.h, None if fe is None else fe.h))
+        self.frontend = fe
+
+    def _audio_rows(self, ids, new_samples, call, feats):
+        """one audio call; new_samples: per id, or None for the finish -> {id: float32 [k x dim]} with feats, else None.  The rows a
+        call readies follow from the sample counts: max(S' - step, 0) - max(S - step, 0) per id, S = frames(N); all the rest at the finish."""
+        n = len(ids)
+        off, out, cap = np.zeros(n + 1, np.uint64), None, 0
+        if feats and self.frontend is not None:
+            fe, step = self.frontend, self.frontend.post.deriv_step
+            for j, i in enumerate(ids):
+                before = self.samples.get(int(i), 0)
+                s0 = fe.frames(before)
+                cap += s0 - max(s0 - step, 0) if new_samples is None else max(fe.frames(before + new_samples[j]) - step, 0) - max(s0 - step, 0)
+        if feats:
+            out = np.zeros((max(cap, 1), self.model.dim), np.float32)
+        _check(call(_ptr(out), cap, _ptr(off)))
+        for j, i in enumerate(ids):
+            self.frames[int(i)] += int(off[j + 1] - off[j])
+            if new_samples is not None:
+                self.samples[int(i)] = self.samples.get(int(i), 0) + new_samples[j]
+        if feats:
+            return {int(i): out[int(off[j]):int(off[j + 1])].copy() for j, i in enumerate(ids)}
+        return None
+
+    def push_audio(self, samples, feats=False):
+        """sr_stream_push_audio.  samples: {id: int16[]}, the new samples of every named utterance; the rows that became ready are
+        searched.  feats=True -> {id: float32 [k x dim]}, those rows."""
+        ids = np.ascontiguousarray(list(samples.keys()), dtype=np.uint32)
+        parts = [np.ascontiguousarray(x, dtype=np.int16).reshape(-1) for x in samples.values()]
+        soff = np.concatenate([[0], np.cumsum([len(x) for x in parts])]).astype(np.uint64)
+        pcm = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0, np.int16))
+        fn = getattr(lib(), self._fn + "_push_audio")
+        return self._audio_rows(ids, [len(x) for x in parts],
+                                lambda o, cap, off: fn(self.h, len(ids), _ptr(ids), _ptr(pcm) if len(pcm) else None, _ptr(soff), o, cap, off), feats)
+
+    def finish_audio(self, ids, feats=False):
+        """sr_stream_finish_audio: the last rows of the utterances, searched; the ids take no more audio.  feats=True -> {id: rows}."""
+        ids = np.ascontiguousarray(list(ids), dtype=np.uint32)
+        fn = getattr(lib(), self._fn + "_finish_audio")
+        return self._audio_rows(ids, None, lambda o, cap, off: fn(self.h, len(ids), _ptr(ids), o, cap, off), feats)
 
     def close(self):
         if self.h:

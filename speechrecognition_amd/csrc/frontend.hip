@@ -13,6 +13,11 @@
 //   the filters in ascending order.
 // No atomics, and nothing a frame computes depends on its span or its batch: the same samples give the same bits anywhere.
 //
+// stream_frontend_kernel (sr_stream_push_audio).  The same two stages for utterances whose samples arrive in pieces: a workgroup per
+// pushed utterance computes the new frames' statics with mfcc_kernel's per-frame body (mfcc_frame), stages them behind the 2 step
+// statics the slot keeps, and emits the rows whose windows are complete with feature_post_kernel's arithmetic (post_value).  With no
+// energy maximum a streamed row carries the batch's bits; the maximum is the causal one of include/srgpu.h.
+//
 // Compiled with -ffp-contract=off: the post-processing is specified to the bit (float subtractions, FP64 subtraction and division),
 // and the MFCC stage's bits must not depend on what the compiler may fuse around a frame.
 #include <hip/hip_runtime.h>
@@ -28,6 +33,72 @@ namespace {
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+
+// One frame through window, transform, filterbank, logarithm and DCT: one wave64 in LDS of its own (A, B: M complex points each, L: 64
+// floats).  yf: the frame's pre-emphasised samples; out: its n_cepstra cepstra, stored by an active wave only.  Every wave of the
+// workgroup goes through every barrier: one without a frame left computes some frame again and stores nothing.
+__device__ __forceinline__ void mfcc_frame(const MfccArgs& a, const float* yf, float2* A, float2* B, float* L, uint32_t lane, bool active,
+                                           float* out) {
+  const uint32_t M = a.n_fft >> 1;
+  for (uint32_t n = lane; n < M; n += 64) {
+    const uint32_t i0 = 2 * n, i1 = 2 * n + 1;
+    A[n] = make_float2(i0 < a.window ? a.win[i0] * yf[i0] : 0.0f, i1 < a.window ? a.win[i1] * yf[i1] : 0.0f);
+  }
+  float2 *src = A, *dst = B;
+  uint32_t Ns = 1;
+  for (; Ns * 4 <= M; Ns *= 4) {
+    __syncthreads();
+    const uint32_t q = M >> 2, tstep = M / (2 * Ns);
+    for (uint32_t j = lane; j < q; j += 64) {
+      const uint32_t k = j & (Ns - 1);
+      const float2 v0 = src[j], v1 = cmul(src[j + q], a.twiddle[k * tstep]), v2 = cmul(src[j + 2 * q], a.twiddle[2 * k * tstep]),
+                   v3 = cmul(src[j + 3 * q], a.twiddle[3 * k * tstep]);
+      const float2 s02 = cadd(v0, v2), d02 = csub(v0, v2), s13 = cadd(v1, v3), d13 = csub(v1, v3);
+      const float2 md13 = make_float2(d13.y, -d13.x);  // -i (v1 - v3)
+      const uint32_t j0 = ((j - k) << 2) + k;
+      dst[j0] = cadd(s02, s13);
+      dst[j0 + Ns] = cadd(d02, md13);
+      dst[j0 + 2 * Ns] = csub(s02, s13);
+      dst[j0 + 3 * Ns] = csub(d02, md13);
+    }
+    float2* t = src; src = dst; dst = t;
+  }
+  if (Ns < M) {  // log2 M is odd: Ns == M / 2
+    __syncthreads();
+    for (uint32_t j = lane; j < Ns; j += 64) {
+      const float2 v0 = src[j], v1 = cmul(src[j + Ns], a.twiddle[2 * j]);
+      dst[j] = cadd(v0, v1);
+      dst[j + Ns] = csub(v0, v1);
+    }
+    float2* t = src; src = dst; dst = t;
+  }
+  __syncthreads();
+  float* P = reinterpret_cast<float*>(dst);  // [M + 1] of the buffer the transform is not in
+  for (uint32_t k = lane; k <= M; k += 64) {
+    const float2 zk = src[k & (M - 1)], zm = src[(M - k) & (M - 1)];
+    const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
+    const float2 o = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
+    const float2 xk = cadd(e, cmul(a.twiddle[k], o));
+    P[k] = xk.x * xk.x + xk.y * xk.y;
+  }
+  __syncthreads();
+  if (lane < a.n_mel) {
+    const float* w = a.mel_w + a.mel_off[lane];
+    const float* p = P + a.mel_first[lane];
+    const uint32_t n = a.mel_count[lane];
+    float e = 0.0f;
+    for (uint32_t j = 0; j < n; j++) e += w[j] * p[j];
+    L[lane] = logf(fmaxf(e, a.energy_floor));
+  }
+  __syncthreads();
+  if (lane < a.n_cepstra && active) {
+    const float* d = a.dct + lane * a.n_mel;
+    float c = 0.0f;
+    for (uint32_t m = 0; m < a.n_mel; m++) c += d[m] * L[m];
+    out[lane] = c;
+  }
+  __syncthreads();
+}
 
 __global__ __launch_bounds__(256) void mfcc_kernel(MfccArgs a, uint32_t y_floats) {
   extern __shared__ float lds[];
@@ -47,73 +118,12 @@ __global__ __launch_bounds__(256) void mfcc_kernel(MfccArgs a, uint32_t y_floats
   }
   float* mine = lds + y_floats + (size_t)wave * (4 * M + 64);
   float2* A = reinterpret_cast<float2*>(mine);
-  float2* B = A + M;
-  float* L = mine + 4 * M;
   __syncthreads();
   const uint32_t rounds = (a.span_frames + n_waves - 1) / n_waves;
   for (uint32_t r = 0; r < rounds; r++) {
-    // every wave goes through every barrier: one without a frame left computes frame 0 again and stores nothing
     const uint32_t fi = r * n_waves + wave;
     const bool active = fi < nf;
-    const float* yf = y + (active ? fi : 0) * a.shift;
-    for (uint32_t n = lane; n < M; n += 64) {
-      const uint32_t i0 = 2 * n, i1 = 2 * n + 1;
-      A[n] = make_float2(i0 < a.window ? a.win[i0] * yf[i0] : 0.0f, i1 < a.window ? a.win[i1] * yf[i1] : 0.0f);
-    }
-    float2 *src = A, *dst = B;
-    uint32_t Ns = 1;
-    for (; Ns * 4 <= M; Ns *= 4) {
-      __syncthreads();
-      const uint32_t q = M >> 2, tstep = M / (2 * Ns);
-      for (uint32_t j = lane; j < q; j += 64) {
-        const uint32_t k = j & (Ns - 1);
-        const float2 v0 = src[j], v1 = cmul(src[j + q], a.twiddle[k * tstep]), v2 = cmul(src[j + 2 * q], a.twiddle[2 * k * tstep]),
-                     v3 = cmul(src[j + 3 * q], a.twiddle[3 * k * tstep]);
-        const float2 s02 = cadd(v0, v2), d02 = csub(v0, v2), s13 = cadd(v1, v3), d13 = csub(v1, v3);
-        const float2 md13 = make_float2(d13.y, -d13.x);  // -i (v1 - v3)
-        const uint32_t j0 = ((j - k) << 2) + k;
-        dst[j0] = cadd(s02, s13);
-        dst[j0 + Ns] = cadd(d02, md13);
-        dst[j0 + 2 * Ns] = csub(s02, s13);
-        dst[j0 + 3 * Ns] = csub(d02, md13);
-      }
-      float2* t = src; src = dst; dst = t;
-    }
-    if (Ns < M) {  // log2 M is odd: Ns == M / 2
-      __syncthreads();
-      for (uint32_t j = lane; j < Ns; j += 64) {
-        const float2 v0 = src[j], v1 = cmul(src[j + Ns], a.twiddle[2 * j]);
-        dst[j] = cadd(v0, v1);
-        dst[j + Ns] = csub(v0, v1);
-      }
-      float2* t = src; src = dst; dst = t;
-    }
-    __syncthreads();
-    float* P = reinterpret_cast<float*>(dst);  // [M + 1] of the buffer the transform is not in
-    for (uint32_t k = lane; k <= M; k += 64) {
-      const float2 zk = src[k & (M - 1)], zm = src[(M - k) & (M - 1)];
-      const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-      const float2 o = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
-      const float2 xk = cadd(e, cmul(a.twiddle[k], o));
-      P[k] = xk.x * xk.x + xk.y * xk.y;
-    }
-    __syncthreads();
-    if (lane < a.n_mel) {
-      const float* w = a.mel_w + a.mel_off[lane];
-      const float* p = P + a.mel_first[lane];
-      const uint32_t n = a.mel_count[lane];
-      float e = 0.0f;
-      for (uint32_t j = 0; j < n; j++) e += w[j] * p[j];
-      L[lane] = logf(fmaxf(e, a.energy_floor));
-    }
-    __syncthreads();
-    if (lane < a.n_cepstra && active) {
-      const float* d = a.dct + lane * a.n_mel;
-      float c = 0.0f;
-      for (uint32_t m = 0; m < a.n_mel; m++) c += d[m] * L[m];
-      a.out[(f0 + t0 + fi) * a.n_cepstra + lane] = c;
-    }
-    __syncthreads();
+    mfcc_frame(a, y + (active ? fi : 0) * a.shift, A, A + M, mine + 4 * M, lane, active, a.out + (f0 + t0 + (active ? fi : 0)) * a.n_cepstra);
   }
 }
 
@@ -127,6 +137,33 @@ __device__ __forceinline__ uint32_t utterance_of(const uint64_t* frame_off, uint
   return lo;
 }
 
+// Row t, component c of FeaturePostProcessor::process_features for an utterance of T frames: statics, deltas, normalisation (not the
+// energy maximum).  Static idx of the utterance is at s[(idx - origin) nf + k].  T == kStreamFrontendOpen, "not known yet", leaves
+// every clamp at the end inactive: such a row needs static t + step to exist.
+__device__ __forceinline__ float post_value(const float* s, int64_t origin, uint32_t nf, uint32_t n_first, uint32_t step, uint32_t T,
+                                            uint32_t t, uint32_t c, const double* mean, const double* stddev) {
+  auto at = [&](uint32_t idx, uint32_t k) { return s[(uint64_t)((int64_t)idx - origin) * nf + k]; };
+  // delta of component k at frame t: window clamped at the start
+  auto delta = [&](uint32_t tt, uint32_t k) {
+    const uint32_t hi = min(max(tt, step), T - 1), lo = hi >= step ? hi - step : 0;
+    return at(hi, k) - at(lo, k);
+  };
+  float v;
+  if (c < nf) {
+    v = at(t, c);
+  } else if (c < nf + n_first) {
+    v = delta(t, c - nf);
+  } else {  // from the deltas, window clamped at the end
+    const uint32_t k = c - nf - n_first, ahead = T > step ? min(t, T - 1 - step) + step : T - 1;
+    v = delta(ahead, k) - delta(t, k);
+  }
+  if (mean) {
+    v = (float)((double)v - mean[c]);
+    v = (float)((double)v / stddev[c]);
+  }
+  return v;
+}
+
 // a thread per (frame, output component): FeaturePostProcessor::process_features' statics, deltas and normalisation
 __global__ __launch_bounds__(256) void feature_post_kernel(FeaturePostArgs a) {
   const uint32_t nt = a.n_static + a.n_first + a.n_second, nf = a.n_static;
@@ -136,27 +173,8 @@ __global__ __launch_bounds__(256) void feature_post_kernel(FeaturePostArgs a) {
   const uint32_t c = (uint32_t)(e - f * nt);
   const uint32_t u = utterance_of(a.frame_off, a.n_utts, f);
   const uint64_t f0 = a.frame_off[u];
-  const uint32_t T = (uint32_t)(a.frame_off[u + 1] - f0), t = (uint32_t)(f - f0), step = a.step;
-  const float* s = a.cepstra + f0 * nf;
-  // delta of component k at frame t: window clamped at the start
-  auto delta = [&](uint32_t tt, uint32_t k) {
-    const uint32_t hi = min(max(tt, step), T - 1), lo = hi >= step ? hi - step : 0;
-    return s[(uint64_t)hi * nf + k] - s[(uint64_t)lo * nf + k];
-  };
-  float v;
-  if (c < nf) {
-    v = s[(uint64_t)t * nf + c];
-  } else if (c < nf + a.n_first) {
-    v = delta(t, c - nf);
-  } else {  // from the deltas, window clamped at the end
-    const uint32_t k = c - nf - a.n_first, ahead = T > step ? min(t, T - 1 - step) + step : T - 1;
-    v = delta(ahead, k) - delta(t, k);
-  }
-  if (a.mean) {
-    v = (float)((double)v - a.mean[c]);
-    v = (float)((double)v / a.stddev[c]);
-  }
-  a.out[e] = v;
+  const uint32_t T = (uint32_t)(a.frame_off[u + 1] - f0), t = (uint32_t)(f - f0);
+  a.out[e] = post_value(a.cepstra + f0 * nf, 0, nf, a.n_first, a.step, T, t, c, a.mean, a.stddev);
 }
 
 // a workgroup per utterance: component 0 minus its maximum over the utterance.  The host loop keeps the first frame that reaches
@@ -188,6 +206,60 @@ __global__ __launch_bounds__(256) void energy_max_kernel(const uint64_t* frame_o
   for (uint32_t t = threadIdx.x; t < T; t += 256) x[(uint64_t)t * nt] -= mx;
 }
 
+// Streaming: one workgroup per pushed utterance (kernels.h: StreamFrontendJob).  (a) the new statics, span by span through the LDS
+// exactly as mfcc_kernel computes them, (b) staged behind the slot's 2 step statics of history; after a barrier (c) the rows that
+// became ready, post_value on the staging rows, straight into the push's feature buffer, the running maximum advanced in frame
+// order by one thread; (d) the slot's new history and maximum.  No atomics: a slot's state is touched by its workgroup alone.
+__global__ __launch_bounds__(256) void stream_frontend_kernel(StreamFrontendArgs s, uint32_t y_floats) {
+  extern __shared__ float lds[];
+  const MfccArgs& a = s.mfcc;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
+  const uint32_t M = a.n_fft >> 1, nf = s.n_static, nt = s.n_static + s.n_first + s.n_second, H = 2 * s.step;
+  const StreamFrontendJob j = s.jobs[blockIdx.x];
+  float* st = s.state + (size_t)j.slot * ((size_t)H * nf + 1);
+  float* stage = s.stage + j.stage0 * nf;
+  for (uint32_t i = threadIdx.x; i < H * nf; i += blockDim.x) stage[i] = j.S ? st[i] : 0.0f;
+  const int16_t* x = a.samples + j.sample0 + 1;  // the first sample of frame S; x[-1] is the sample before it, 0 before sample 0
+  float* y = lds;
+  float* mine = lds + y_floats + (size_t)wave * (4 * M + 64);
+  float2* A = reinterpret_cast<float2*>(mine);
+  for (uint32_t j0 = 0; j0 < j.k; j0 += a.span_frames) {
+    const uint32_t n = min(a.span_frames, j.k - j0);
+    const uint32_t n_samp = (n - 1) * a.shift + a.window;
+    const int16_t* xs = x + (uint64_t)j0 * a.shift;
+    for (uint32_t i = threadIdx.x; i < n_samp; i += blockDim.x) y[i] = (float)xs[i] - a.preemphasis * (float)xs[(int64_t)i - 1];
+    __syncthreads();
+    for (uint32_t r = 0; r * n_waves < n; r++) {
+      const uint32_t fi = r * n_waves + wave;
+      const bool active = fi < n;
+      mfcc_frame(a, y + (active ? fi : 0) * a.shift, A, A + M, mine + 4 * M, lane, active, stage + (size_t)(H + j0 + (active ? fi : 0)) * nf);
+    }
+  }
+  __syncthreads();
+  const int64_t origin = (int64_t)j.S - H;  // the utterance's static at the first staging row
+  float* out = s.out + j.out0 * nt;
+  for (uint32_t e = threadIdx.x; e < j.rows * nt; e += blockDim.x) {
+    const uint32_t r = e / nt, c = e - r * nt;
+    out[e] = post_value(stage, origin, nf, s.n_first, s.step, j.T, j.row0 + r, c, s.mean, s.stddev);
+  }
+  if (s.energy_max_norm) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      // m after static i: the maximum over statics 0 .. i, replaced on `<` alone; row i - step takes it, the finish's last rows the last
+      float m = j.S ? st[(size_t)H * nf] : -INFINITY;
+      for (uint32_t i = j.S; i < j.S + j.k; i++) {
+        const float v = post_value(stage, origin, nf, s.n_first, s.step, j.T, i, 0, s.mean, s.stddev);
+        if (m < v) m = v;
+        if (i >= s.step) out[(size_t)(i - s.step - j.row0) * nt] -= m;
+      }
+      if (j.T != kStreamFrontendOpen)
+        for (uint32_t t = max(j.row0, j.T > s.step ? j.T - s.step : 0u); t < j.T; t++) out[(size_t)(t - j.row0) * nt] -= m;
+      st[(size_t)H * nf] = m;
+    }
+  }
+  for (uint32_t i = threadIdx.x; i < H * nf; i += blockDim.x) st[i] = stage[(size_t)j.k * nf + i];
+}
+
 }  // namespace
 
 hipError_t launch_mfcc(const MfccArgs& a, hipStream_t stream) {
@@ -205,6 +277,15 @@ hipError_t launch_feature_post(const FeaturePostArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(feature_post_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
   if (a.energy_max_norm)
     hipLaunchKernelGGL(energy_max_kernel, dim3(a.n_utts), dim3(256), 0, stream, a.frame_off, a.n_static + a.n_first + a.n_second, a.out);
+  return hipGetLastError();
+}
+
+hipError_t launch_stream_frontend(const StreamFrontendArgs& a, uint32_t n_jobs, hipStream_t stream) {
+  if (n_jobs == 0) return hipSuccess;
+  const uint32_t waves = mfcc_waves(a.mfcc.n_fft), M = a.mfcc.n_fft / 2;
+  const uint32_t y_floats = ((a.mfcc.span_frames - 1) * a.mfcc.shift + a.mfcc.window + 3) & ~3u;
+  const size_t lds_bytes = sizeof(float) * ((size_t)y_floats + (size_t)waves * (4 * M + 64));
+  hipLaunchKernelGGL(stream_frontend_kernel, dim3(n_jobs), dim3(64 * waves), lds_bytes, stream, a, y_floats);
   return hipGetLastError();
 }
 

@@ -16,6 +16,7 @@
 #include "../../include/srgpu.h"
 #include "host_util.h"
 #include "kernels.h"
+#include "stream_audio_plan.h"
 
 namespace srhost {
 // stores a printf-style message for sr_last_error() (thread-local) and returns `code`
@@ -343,6 +344,21 @@ struct StreamSlots {
   }
 };
 
+// The audio side of a stream set (sr_stream_set_frontend, _push_audio, _finish_audio and the bigram twins): the front end, what
+// kind of input each slot's utterance takes, the host carry of an audio utterance (stream_audio_plan.h) and the device state
+// stream_frontend_kernel keeps per slot.
+enum : uint8_t { kStreamFresh = 0, kStreamRows = 1, kStreamAudio = 2, kStreamAudioFinished = 3 };
+struct StreamAudio {
+  sr_frontend* fe = nullptr;
+  std::vector<uint8_t> kind;               // [max_streams] kStream*, kStreamFresh from begin to the first push that names the id
+  std::vector<srplan::AudioCarry> carry;   // [max_streams]
+  DevBuf<float> state;                     // [max_streams][2 step n_static + 1]: the last 2 step statics, the running maximum
+  // per push, sized by the largest push so far
+  DevBuf<int16_t> samples;
+  DevBuf<float> stage;
+  DevBuf<srgpu::StreamFrontendJob> jobs;
+};
+
 // A set of concurrently open utterances on one (model, lexicon) (sr_stream_*, srgpu_api.cpp).  The device state of slot i's
 // utterance (decode_stream_kernel) lives in the per-slot buffers below.
 struct sr_stream {
@@ -350,6 +366,7 @@ struct sr_stream {
   sr_lexicon* lex = nullptr;
   sr_search_params params{};
   StreamSlots slots;
+  StreamAudio audio;
   // per slot, device
   DevBuf<unsigned char> ws;         // decode_big_workspace(P) each
   DevBuf<srgpu::StreamState> state;
@@ -374,6 +391,7 @@ struct sr_bigram_stream {
   sr_bigram* bigram = nullptr;
   sr_bigram_params params{};
   StreamSlots slots;
+  StreamAudio audio;
   std::vector<srgpu::BigramStreamState> host_state;  // [max_streams] as of the slot's last push
   std::vector<uint8_t> failed;      // [max_streams] a push flagged the slot (SR_EINTERNAL until it ends)
   // per slot, device

@@ -1001,5 +1001,27 @@ struct FeaturePostArgs {
   float* out;
 };
 hipError_t launch_feature_post(const FeaturePostArgs& a, hipStream_t stream);
+// Streaming (sr_stream_push_audio): stream_frontend_kernel, one workgroup per pushed utterance, takes its piece of samples to the
+// rows that became ready, through the slot's state -- the last 2 step statics and the running energy maximum, 2 step n_static + 1
+// floats.  A job: the utterance had S statics before the push and gains k; its piece (the sample before it first) begins at
+// samples[sample0]; its staging rows -- 2 step of history, then the k new statics -- begin at row stage0 of `stage`; it emits
+// `rows` rows from row0 of the utterance into row out0 of `out`, clamped by T (kStreamFrontendOpen: the count is not known yet).
+constexpr uint32_t kStreamFrontendOpen = 0xFFFFFFFFu;
+struct StreamFrontendJob {
+  uint32_t slot, S, k, T;
+  uint32_t row0, rows;
+  uint64_t sample0, stage0, out0;
+};
+struct StreamFrontendArgs {
+  MfccArgs mfcc;                 // samples: the push's pieces; window .. dct as for mfcc_kernel (sample_off, frame_off, spans, out unused)
+  const StreamFrontendJob* jobs;
+  uint32_t n_static, n_first, n_second, step;
+  const double* mean; const double* stddev;
+  int energy_max_norm;
+  float* state;                  // [slots][2 step n_static + 1]
+  float* stage;                  // per push
+  float* out;                    // the push's feature rows [rows][n_static + n_first + n_second]
+};
+hipError_t launch_stream_frontend(const StreamFrontendArgs& a, uint32_t n_jobs, hipStream_t stream);
 
 }  // namespace srgpu

@@ -715,8 +715,9 @@ namespace {  // sr_stream_*, sr_bigram_stream_*
 // the push's features
 struct PushEntry { uint32_t slot; uint64_t t0, k, row0; };
 // checks a push against the open utterances -- every id open and named once, frame_off ascending from 0, no utterance past
-// max_frames -- and lists its entries with frames (none for an empty push)
-int check_push(const StreamSlots& sl, uint32_t n, const uint32_t* ids, const uint64_t* frame_off, std::vector<PushEntry>* out) {
+// max_frames, none of them fed as audio -- and lists its entries with frames (none for an empty push)
+int check_push(const StreamSlots& sl, const StreamAudio& au, uint32_t n, const uint32_t* ids, const uint64_t* frame_off,
+               std::vector<PushEntry>* out) {
   if (n == 0) return SR_OK;
   if (!ids || !frame_off) return fail(SR_EINVAL, "null argument");
   if (frame_off[0] != 0) return fail(SR_EINVAL, "frame_off[0] must be 0");
@@ -726,6 +727,7 @@ int check_push(const StreamSlots& sl, uint32_t n, const uint32_t* ids, const uin
     if (slot < 0) return fail(SR_EINVAL, "push entry %u: stream id %u is not open", i, ids[i]);
     if (seen[slot]) return fail(SR_EINVAL, "push entry %u: stream id %u appears twice in one push", i, ids[i]);
     seen[slot] = 1;
+    if (au.kind[slot] >= kStreamAudio) return fail(SR_EINVAL, "push entry %u: stream id %u is fed as audio; it takes no feature rows", i, ids[i]);
     if (frame_off[i + 1] < frame_off[i]) return fail(SR_EINVAL, "frame_off is not ascending at entry %u", i);
     const uint64_t k = frame_off[i + 1] - frame_off[i];
     if (k > sl.max_frames - sl.frames[slot])
@@ -736,14 +738,15 @@ int check_push(const StreamSlots& sl, uint32_t n, const uint32_t* ids, const uin
   return SR_OK;
 }
 // A push's pass: its F frames and its jobs staged on the device, then one chunk of run_chunks -- the frames scored into m->scores[0],
-// search(chunk, table, stream) enqueuing the push's search.  (Every call synchronises before it returns: the buffer is free.)
+// search(chunk, table, stream) enqueuing the push's search.  feats == nullptr: work queued on the scoring stream has the frames in
+// d_feats already (the audio pushes).  (Every call synchronises before it returns: the buffer is free.)
 template <class Job, class Search>
 int push_pass(sr_model* m, int gmm_kernel, const float* feats, uint64_t F, DevBuf<float>& d_feats, const std::vector<Job>& jobs,
               DevBuf<Job>& d_jobs, Search search) {
   HIP_TRY(d_feats.ensure((size_t)F * m->dim));
   HIP_TRY(m->scores[0].ensure((size_t)F * m->ld));
   HIP_TRY(d_jobs.ensure(jobs.size()));
-  HIP_TRY(hipMemcpyAsync(d_feats.p, feats, sizeof(float) * F * m->dim, hipMemcpyHostToDevice, m->s_gmm));
+  if (feats) HIP_TRY(hipMemcpyAsync(d_feats.p, feats, sizeof(float) * F * m->dim, hipMemcpyHostToDevice, m->s_gmm));
   HIP_TRY(hipMemcpyAsync(d_jobs.p, jobs.data(), sizeof(Job) * jobs.size(), hipMemcpyHostToDevice, m->s_gmm));
   return run_chunks(m, {Chunk{0, (uint32_t)jobs.size(), 0, F}},
                     [&](const Chunk&, double* table) { return launch_scoring(m, d_feats.p, F, gmm_kernel, table); }, search);
@@ -778,6 +781,228 @@ int bigram_stream_items(sr_bigram_stream* s, uint32_t slot, uint32_t id, uint32_
     HIP_TRY(hipMemcpy(out_score, s->out_score.p + o, sizeof(float) * st.count, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(out_time, s->out_time.p + o, sizeof(uint32_t) * st.count, hipMemcpyDeviceToHost));
   }
+  return SR_OK;
+}
+
+// The two stream sets' pushes behind their checks, for feature rows and audio alike.  stream_precheck: what the set itself has
+// against the entries, before any launch.  stream_run: the push's F rows (feats on the host, or nullptr: already in s->feats on the
+// device) scored and searched; the entries' frame counts advance.
+int stream_precheck(sr_stream*, const std::vector<PushEntry>&) { return SR_OK; }
+int stream_run(sr_stream* s, const std::vector<PushEntry>& entries, const float* feats, uint64_t F) {
+  sr_model* m = s->model;
+  const sr_lexicon* l = s->lex;
+  std::vector<StreamJob> jobs;
+  for (const PushEntry& e : entries) jobs.push_back({e.slot, (uint32_t)e.t0, (uint32_t)e.k, 0u, e.row0});
+  int rc = push_pass(m, s->params.gmm_kernel, feats, F, s->feats, jobs, s->jobs, [&](const Chunk&, const double* table, hipStream_t st) -> int {
+    StreamArgs a{};
+    a.net = l->net;
+    a.am_threshold = s->params.am_threshold; a.word_penalty = s->params.word_penalty;
+    a.scores = table; a.ld = m->ld; a.jobs = s->jobs.p;
+    a.ws = s->ws.p; a.ws_stride = decode_big_workspace(l->net.n_slots); a.state = s->state.p;
+    a.tb_score = s->tb_score.p; a.tb_word = s->tb_word.p; a.tb_bkp = s->tb_bkp.p; a.tb_stride = s->slots.max_frames + 1;
+    a.words = s->words.p; a.words_stride = s->slots.max_frames;
+    HIP_TRY(launch_decode_stream(a, (uint32_t)jobs.size(), st));
+    if (m->profiling) {
+      m->prof.search_bytes += (8.0 * m->n_states + 4.0 * l->net.n_slots) * (double)F;
+      m->prof.frames += F;
+    }
+    return SR_OK;
+  });
+  if (rc) return rc;
+  for (const StreamJob& j : jobs) s->slots.frames[j.slot] += j.k;
+  return SR_OK;
+}
+
+// per entry: the book entries the push may reach (n_book + W per frame: a frame keeps at most one word end per history)
+uint64_t book_need(const sr_bigram_stream* s, const PushEntry& e) {
+  return (e.t0 ? s->host_state[e.slot].n_book : 2u) + (uint64_t)s->bigram->net.n_words * e.k;
+}
+int stream_precheck(sr_bigram_stream* s, const std::vector<PushEntry>& entries) {
+  for (const PushEntry& e : entries) {
+    const uint32_t id = s->slots.id[e.slot];
+    if (s->failed[e.slot]) return fail(SR_EINTERNAL, "stream id %u: an earlier push overflowed its book", id);
+    const uint64_t nb = book_need(s, e);
+    if (nb > 0xFFFFFFFFull)
+      return fail(SR_ELIMIT, "stream id %u: this push may need %llu book entries, more than 2^32 - 1", id, (unsigned long long)nb);
+  }
+  return SR_OK;
+}
+int stream_run(sr_bigram_stream* s, const std::vector<PushEntry>& entries, const float* feats, uint64_t F) {
+  sr_model* m = s->model;
+  const sr_bigram* b = s->bigram;
+  std::vector<BigramStreamJob> jobs;
+  for (const PushEntry& e : entries) jobs.push_back({e.slot, (uint32_t)e.t0, (uint32_t)e.k, 0u, e.row0, nullptr, 0});
+  // every book to at least n_book + W k entries (geometric growth; the entries so far are copied: back pointers are indices)
+  for (size_t j = 0; j < jobs.size(); j++) {
+    DevBuf<uint4>& bk = *s->book[jobs[j].slot];
+    const uint64_t need = book_need(s, entries[j]);
+    if (bk.n < need) {
+      DevBuf<uint4> grown;
+      HIP_TRY(grown.ensure(std::max<uint64_t>(need, std::min<uint64_t>(2 * (uint64_t)bk.n, 0xFFFFFFFFull))));
+      if (jobs[j].t0) HIP_TRY(hipMemcpy(grown.p, bk.p, sizeof(uint4) * s->host_state[jobs[j].slot].n_book, hipMemcpyDeviceToDevice));
+      bk.swap(grown);
+    }
+    jobs[j].book = bk.p;
+    jobs[j].book_cap = bk.n;
+  }
+  int rc = push_pass(m, s->params.gmm_kernel, feats, F, s->feats, jobs, s->jobs, [&](const Chunk&, const double* table, hipStream_t stream) -> int {
+    BigramStreamArgs a{};
+    BigramArgs& ba = a.a;
+    ba = b->net;
+    ba.scores = table; ba.ld = m->ld;
+    ba.ac_pruning = s->params.acoustic_pruning; ba.lm_pruning = s->params.lm_pruning;
+    ba.global_states = 1;
+    ba.gs_ws = s->gs_ws.p; ba.gs_ws_words = bigram_gs_ws_words(ba.n_words, ba.n_positions);
+    ba.we_slot = s->we_slot.p; ba.we_bp = s->we_bp.p; ba.we_score = s->we_score.p;
+    a.jobs = s->jobs.p; a.state = s->state.p; a.lsave = s->lsave.p;
+    a.out_word = s->out_word.p; a.out_score = s->out_score.p; a.out_time = s->out_time.p; a.items_stride = s->slots.max_frames + 1;
+    HIP_TRY(launch_bigram_stream(a, (uint32_t)jobs.size(), stream));
+    if (m->profiling) {  // SURVEY 8(d)'s decoder model, 8 S + 4 P bytes per frame, as sr_recognize_bigram_corpus
+      m->prof.search_bytes += (8.0 * m->n_states + 4.0 * ba.n_positions) * (double)F;
+      m->prof.frames += F;
+    }
+    return SR_OK;
+  });
+  if (rc) return rc;
+  std::vector<BigramStreamState> st(s->slots.max_streams);  // (one copy of every slot's 32 bytes: cheaper than one per pushed slot)
+  HIP_TRY(hipMemcpy(st.data(), s->state.p, sizeof(BigramStreamState) * st.size(), hipMemcpyDeviceToHost));
+  uint32_t bad = 0xFFFFFFFFu;
+  for (const BigramStreamJob& j : jobs) {
+    s->slots.frames[j.slot] += j.k;
+    s->host_state[j.slot] = st[j.slot];
+    if (st[j.slot].flags & kBgStreamOverflow) { s->failed[j.slot] = 1; bad = s->slots.id[j.slot]; }
+  }
+  if (bad != 0xFFFFFFFFu) return fail(SR_EINTERNAL, "stream id %u: a book append passed the capacity the host grew it to", bad);
+  return SR_OK;
+}
+
+// the ids of a feature push take rows from now on
+void mark_rows(StreamAudio& au, const StreamSlots& sl, uint32_t n, const uint32_t* ids) {
+  for (uint32_t i = 0; i < n; i++) au.kind[sl.find(ids[i])] = kStreamRows;
+}
+
+// sr_stream_set_frontend and its bigram twin
+template <class Set>
+int set_frontend(Set* s, sr_frontend* fe) {
+  if (!s) return fail(SR_EINVAL, "null stream set");
+  for (uint32_t i = 0; i < s->slots.max_streams; i++)
+    if (s->slots.open[i]) return fail(SR_EINVAL, "stream id %u is open: the front end changes only while none is", s->slots.id[i]);
+  if (!fe) { s->audio.fe = nullptr; return SR_OK; }
+  if (fe->model != s->model) return fail(SR_EINVAL, "the front end does not belong to the stream set's model");
+  if (!fe->has_mfcc) return fail(SR_EINVAL, "this front end was made without an MFCC stage: it takes cepstra only");
+  int rc = check_model(s->model);
+  if (rc) return rc;
+  HIP_TRY(s->audio.state.ensure((size_t)s->slots.max_streams * (2 * (size_t)fe->post.deriv_step * fe->post.n_static + 1)));
+  s->audio.fe = fe;
+  return SR_OK;
+}
+
+// sr_stream_push_audio / sr_stream_finish_audio and their bigram twins (include/srgpu.h has the definition): the steps of
+// stream_audio_plan.h for every named utterance, all checks, then one launch of stream_frontend_kernel that leaves the ready rows
+// in s->feats, and the set's own scoring and search on them.  Nothing of the set changes before the launches have succeeded.
+template <class Set>
+int push_audio(Set* s, uint32_t n, const uint32_t* ids, const int16_t* samples, const uint64_t* sample_off, bool finishing, float* out_feats,
+               uint64_t cap_rows, uint64_t* out_frame_off) {
+  if (!s) return fail(SR_EINVAL, "null stream set");
+  StreamAudio& au = s->audio;
+  StreamSlots& sl = s->slots;
+  sr_frontend* fe = au.fe;
+  if (!fe) return fail(SR_EINVAL, "the stream set has no front end (sr_stream_set_frontend)");
+  if (n == 0) {
+    if (out_frame_off) out_frame_off[0] = 0;
+    return SR_OK;
+  }
+  if (!ids || (!finishing && !sample_off)) return fail(SR_EINVAL, "null argument");
+  if (sample_off && sample_off[0] != 0) return fail(SR_EINVAL, "sample_off[0] must be 0");
+  const sr_mfcc_params& p = fe->mfcc;
+  const uint32_t step = fe->post.deriv_step, nf = fe->post.n_static, H = 2 * step;
+  sr_model* m = s->model;
+  std::vector<uint8_t> seen(sl.max_streams, 0);
+  std::vector<srplan::AudioStep> steps(n);
+  std::vector<uint32_t> slots(n);
+  std::vector<uint64_t> row_off((size_t)n + 1, 0);
+  std::vector<PushEntry> entries;
+  for (uint32_t i = 0; i < n; i++) {
+    const int64_t slot = sl.find(ids[i]);
+    if (slot < 0) return fail(SR_EINVAL, "push entry %u: stream id %u is not open", i, ids[i]);
+    if (seen[slot]) return fail(SR_EINVAL, "push entry %u: stream id %u appears twice in one push", i, ids[i]);
+    seen[slot] = 1;
+    slots[i] = (uint32_t)slot;
+    if (au.kind[slot] == kStreamRows) return fail(SR_EINVAL, "push entry %u: stream id %u is fed feature rows; it takes no audio", i, ids[i]);
+    if (au.kind[slot] == kStreamAudioFinished) return fail(SR_EINVAL, "push entry %u: stream id %u is finished; it takes no more audio", i, ids[i]);
+    uint64_t k = 0;
+    if (sample_off) {
+      if (sample_off[i + 1] < sample_off[i]) return fail(SR_EINVAL, "sample_off is not ascending at entry %u", i);
+      k = sample_off[i + 1] - sample_off[i];
+    }
+    if (k && !samples) return fail(SR_EINVAL, "samples is null");
+    const srplan::AudioCarry& c = au.carry[slot];
+    if (srplan::audio_frames(p.window, p.shift, c.n_samples + k) > sl.max_frames)
+      return fail(SR_ELIMIT, "stream id %u: %llu + %llu samples make more than max_frames %llu frames", ids[i], (unsigned long long)c.n_samples,
+                  (unsigned long long)k, (unsigned long long)sl.max_frames);
+    steps[i] = srplan::plan_audio_step(p.window, p.shift, step, c, k ? samples + sample_off[i] : nullptr, k, finishing);
+    row_off[i + 1] = row_off[i] + steps[i].rows;
+    if (steps[i].rows) entries.push_back({(uint32_t)slot, sl.frames[slot], steps[i].rows, row_off[i]});
+  }
+  const uint64_t R = row_off[n];
+  if (out_feats && cap_rows < R) {
+    if (out_frame_off) out_frame_off[n] = R;
+    return fail(SR_EINVAL, "this push readies %llu rows, out_feats holds %llu", (unsigned long long)R, (unsigned long long)cap_rows);
+  }
+  int rc = stream_precheck(s, entries);
+  if (rc || (rc = check_model(m))) return rc;
+  // the pieces (prev | tail | new samples) and the kernel's jobs: every utterance that gains a static or a row
+  std::vector<int16_t> pieces;
+  std::vector<StreamFrontendJob> jobs;
+  uint64_t stage_rows = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const srplan::AudioStep& st = steps[i];
+    if (!st.new_statics && !st.rows) continue;
+    const srplan::AudioCarry& c = au.carry[slots[i]];
+    const uint64_t k = sample_off ? sample_off[i + 1] - sample_off[i] : 0;
+    StreamFrontendJob j{};
+    j.slot = slots[i]; j.S = (uint32_t)c.statics; j.k = (uint32_t)st.new_statics;
+    j.T = finishing ? (uint32_t)st.next.statics : kStreamFrontendOpen;
+    j.row0 = (uint32_t)st.row0; j.rows = (uint32_t)st.rows;
+    j.sample0 = pieces.size(); j.stage0 = stage_rows; j.out0 = row_off[i];
+    pieces.resize(pieces.size() + 1 + st.n_buf);
+    srplan::audio_fill(c, st, k ? samples + sample_off[i] : nullptr, k, pieces.data() + j.sample0);
+    stage_rows += H + st.new_statics;
+    jobs.push_back(j);
+  }
+  if (!jobs.empty()) {
+    HIP_TRY(au.samples.ensure(pieces.size()));
+    HIP_TRY(au.stage.ensure((size_t)stage_rows * nf));
+    HIP_TRY(au.jobs.ensure(jobs.size()));
+    HIP_TRY(s->feats.ensure((size_t)R * m->dim));
+    HIP_TRY(hipMemcpyAsync(au.samples.p, pieces.data(), sizeof(int16_t) * pieces.size(), hipMemcpyHostToDevice, m->s_gmm));
+    HIP_TRY(hipMemcpyAsync(au.jobs.p, jobs.data(), sizeof(StreamFrontendJob) * jobs.size(), hipMemcpyHostToDevice, m->s_gmm));
+    StreamFrontendArgs a{};
+    MfccArgs& f = a.mfcc;
+    f.samples = au.samples.p; f.span_frames = fe->span_frames;
+    f.window = p.window; f.shift = p.shift; f.n_fft = p.n_fft; f.n_mel = p.n_mel; f.n_cepstra = p.n_cepstra;
+    f.preemphasis = p.preemphasis; f.energy_floor = p.energy_floor;
+    f.win = fe->win.p; f.twiddle = fe->twiddle.p; f.mel_first = fe->mel_first.p; f.mel_count = fe->mel_count.p; f.mel_off = fe->mel_off.p;
+    f.mel_w = fe->mel_w.p; f.dct = fe->dct.p;
+    a.jobs = au.jobs.p;
+    a.n_static = nf; a.n_first = fe->post.n_first; a.n_second = fe->post.n_second; a.step = step;
+    a.mean = fe->normalise ? fe->mean.p : nullptr; a.stddev = fe->normalise ? fe->stddev.p : nullptr;
+    a.energy_max_norm = fe->post.energy_max_norm != 0;
+    a.state = au.state.p; a.stage = au.stage.p; a.out = s->feats.p;
+    EventPair ep{};
+    if ((rc = prof_begin(m, m->s_gmm, 1, &ep))) return rc;
+    HIP_TRY(launch_stream_frontend(a, (uint32_t)jobs.size(), m->s_gmm));
+    if ((rc = prof_end(m, m->s_gmm, &ep))) return rc;
+    if (R) rc = stream_run(s, entries, nullptr, R);  // (a push that readies no row launches no scoring and no search)
+    else HIP_TRY(hipStreamSynchronize(m->s_gmm));
+    if (rc) return rc;
+    if (R && out_feats) HIP_TRY(hipMemcpy(out_feats, s->feats.p, sizeof(float) * (size_t)R * m->dim, hipMemcpyDeviceToHost));
+  }
+  for (uint32_t i = 0; i < n; i++) {
+    au.carry[slots[i]] = std::move(steps[i].next);
+    au.kind[slots[i]] = finishing ? kStreamAudioFinished : kStreamAudio;
+  }
+  if (out_frame_off) memcpy(out_frame_off, row_off.data(), sizeof(uint64_t) * row_off.size());
   return SR_OK;
 }
 }  // namespace
@@ -4680,6 +4905,7 @@ int sr_stream_open(sr_model* m, sr_lexicon* l, const sr_search_params* p, uint32
   std::unique_ptr<sr_stream, int (*)(sr_stream*)> own(s, sr_stream_destroy);
   s->model = m; s->lex = l; s->params = *p; s->slots = StreamSlots(max_streams, max_frames);
   s->commit_fresh.assign(max_streams, 1);
+  s->audio.kind.assign(max_streams, kStreamFresh); s->audio.carry.resize(max_streams);
   const size_t S = max_streams;
   HIP_TRY(s->ws.ensure(S * decode_big_workspace(l->net.n_slots)));
   HIP_TRY(s->state.ensure(S));
@@ -4696,8 +4922,11 @@ int sr_stream_begin(sr_stream* s, uint32_t* id) {
   return guarded(__func__, [&]() -> int {
   if (!s || !id) return fail(SR_EINVAL, "null argument");
   const int rc = s->slots.begin(id);  // (the first push starts from the initial state: decode_stream_kernel)
-  if (rc == SR_OK) s->commit_fresh[*id % s->slots.max_streams] = 1;  // ... and the first sr_stream_stable from commit point 0
-  return rc;
+  if (rc) return rc;
+  const uint32_t slot = *id % s->slots.max_streams;
+  s->commit_fresh[slot] = 1;  // ... and the first sr_stream_stable from commit point 0
+  s->audio.kind[slot] = kStreamFresh; s->audio.carry[slot] = srplan::AudioCarry();
+  return SR_OK;
   });
 }
 
@@ -4705,34 +4934,26 @@ int sr_stream_push(sr_stream* s, uint32_t n, const uint32_t* ids, const float* f
   return guarded(__func__, [&]() -> int {
   if (!s) return fail(SR_EINVAL, "null stream set");
   std::vector<PushEntry> entries;
-  int rc = check_push(s->slots, n, ids, frame_off, &entries);
-  if (rc || entries.empty()) return rc;
-  if (!feats) return fail(SR_EINVAL, "null feats");
-  sr_model* m = s->model;
-  const sr_lexicon* l = s->lex;
-  if ((rc = check_model(m))) return rc;
-  std::vector<StreamJob> jobs;
-  for (const PushEntry& e : entries) jobs.push_back({e.slot, (uint32_t)e.t0, (uint32_t)e.k, 0u, e.row0});
-  const uint64_t F = frame_off[n];
-  rc = push_pass(m, s->params.gmm_kernel, feats, F, s->feats, jobs, s->jobs, [&](const Chunk&, const double* table, hipStream_t st) -> int {
-    StreamArgs a{};
-    a.net = l->net;
-    a.am_threshold = s->params.am_threshold; a.word_penalty = s->params.word_penalty;
-    a.scores = table; a.ld = m->ld; a.jobs = s->jobs.p;
-    a.ws = s->ws.p; a.ws_stride = decode_big_workspace(l->net.n_slots); a.state = s->state.p;
-    a.tb_score = s->tb_score.p; a.tb_word = s->tb_word.p; a.tb_bkp = s->tb_bkp.p; a.tb_stride = s->slots.max_frames + 1;
-    a.words = s->words.p; a.words_stride = s->slots.max_frames;
-    HIP_TRY(launch_decode_stream(a, (uint32_t)jobs.size(), st));
-    if (m->profiling) {
-      m->prof.search_bytes += (8.0 * m->n_states + 4.0 * l->net.n_slots) * (double)F;
-      m->prof.frames += F;
-    }
-    return SR_OK;
-  });
+  int rc = check_push(s->slots, s->audio, n, ids, frame_off, &entries);
   if (rc) return rc;
-  for (const StreamJob& j : jobs) s->slots.frames[j.slot] += j.k;
+  if (!entries.empty()) {
+    if (!feats) return fail(SR_EINVAL, "null feats");
+    if ((rc = check_model(s->model)) || (rc = stream_run(s, entries, feats, frame_off[n]))) return rc;
+  }
+  mark_rows(s->audio, s->slots, n, ids);
   return SR_OK;
   });
+}
+
+int sr_stream_set_frontend(sr_stream* s, sr_frontend* fe) {
+  return guarded(__func__, [&]() -> int { return set_frontend(s, fe); });
+}
+int sr_stream_push_audio(sr_stream* s, uint32_t n, const uint32_t* ids, const int16_t* samples, const uint64_t* sample_off, float* out_feats,
+                         uint64_t cap_rows, uint64_t* out_frame_off) {
+  return guarded(__func__, [&]() -> int { return push_audio(s, n, ids, samples, sample_off, false, out_feats, cap_rows, out_frame_off); });
+}
+int sr_stream_finish_audio(sr_stream* s, uint32_t n, const uint32_t* ids, float* out_feats, uint64_t cap_rows, uint64_t* out_frame_off) {
+  return guarded(__func__, [&]() -> int { return push_audio(s, n, ids, nullptr, nullptr, true, out_feats, cap_rows, out_frame_off); });
 }
 
 int sr_stream_partial(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_t cap, uint32_t* count, uint64_t* frames) {
@@ -4753,6 +4974,7 @@ int sr_stream_end(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_t cap, 
   if (!s || !count || (!out_words && cap)) return fail(SR_EINVAL, "null argument");
   const int64_t slot = s->slots.find(id);
   if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
+  if (s->audio.kind[slot] == kStreamAudio) return fail(SR_EINVAL, "stream id %u is fed as audio and not finished (sr_stream_finish_audio)", id);
   int rc = check_model(s->model);
   if (rc) return rc;
   rc = stream_words(s, (uint32_t)slot, id, out_words, cap, count);
@@ -4932,6 +5154,7 @@ int sr_bigram_stream_open(sr_model* m, sr_bigram* b, const sr_bigram_params* p, 
   s->model = m; s->bigram = b; s->params = *p; s->slots = StreamSlots(max_streams, max_frames);
   s->host_state.assign(max_streams, BigramStreamState{}); s->failed.assign(max_streams, 0);
   s->commit_fresh.assign(max_streams, 1);
+  s->audio.kind.assign(max_streams, kStreamFresh); s->audio.carry.resize(max_streams);
   const size_t S = max_streams, W = b->net.n_words;
   HIP_TRY(s->gs_ws.ensure(S * bigram_gs_ws_words(b->net.n_words, b->net.n_positions)));
   HIP_TRY(s->we_slot.ensure(S * 4 * W));
@@ -4958,6 +5181,7 @@ int sr_bigram_stream_begin(sr_bigram_stream* s, uint32_t* id) {
   s->host_state[slot].n_book = 2;  // the two start entries the first push writes
   s->failed[slot] = 0;
   s->commit_fresh[slot] = 1;  // the first sr_bigram_stream_stable starts from the start entry
+  s->audio.kind[slot] = kStreamFresh; s->audio.carry[slot] = srplan::AudioCarry();
   return SR_OK;
   });
 }
@@ -4966,67 +5190,27 @@ int sr_bigram_stream_push(sr_bigram_stream* s, uint32_t n, const uint32_t* ids, 
   return guarded(__func__, [&]() -> int {
   if (!s) return fail(SR_EINVAL, "null stream set");
   std::vector<PushEntry> entries;
-  int rc = check_push(s->slots, n, ids, frame_off, &entries);
-  if (rc) return rc;
-  const sr_bigram* b = s->bigram;
-  std::vector<BigramStreamJob> jobs;
-  std::vector<uint64_t> need;  // per job: book entries the push may reach (n_book + W per frame: a frame keeps at most one word end per history)
-  for (const PushEntry& e : entries) {
-    const uint32_t id = s->slots.id[e.slot];
-    if (s->failed[e.slot]) return fail(SR_EINTERNAL, "stream id %u: an earlier push overflowed its book", id);
-    const uint64_t nb = (e.t0 ? s->host_state[e.slot].n_book : 2u) + (uint64_t)b->net.n_words * e.k;
-    if (nb > 0xFFFFFFFFull)
-      return fail(SR_ELIMIT, "stream id %u: this push may need %llu book entries, more than 2^32 - 1", id, (unsigned long long)nb);
-    jobs.push_back({e.slot, (uint32_t)e.t0, (uint32_t)e.k, 0u, e.row0, nullptr, 0});
-    need.push_back(nb);
+  int rc = check_push(s->slots, s->audio, n, ids, frame_off, &entries);
+  if (rc || (rc = stream_precheck(s, entries))) return rc;
+  if (!entries.empty()) {
+    if (!feats) return fail(SR_EINVAL, "null feats");
+    if ((rc = check_model(s->model)) || (rc = stream_run(s, entries, feats, frame_off[n]))) return rc;
   }
-  if (jobs.empty()) return SR_OK;
-  if (!feats) return fail(SR_EINVAL, "null feats");
-  sr_model* m = s->model;
-  if ((rc = check_model(m))) return rc;
-  // every book to at least n_book + W k entries (geometric growth; the entries so far are copied: back pointers are indices)
-  for (size_t j = 0; j < jobs.size(); j++) {
-    DevBuf<uint4>& bk = *s->book[jobs[j].slot];
-    if (bk.n < need[j]) {
-      DevBuf<uint4> grown;
-      HIP_TRY(grown.ensure(std::max<uint64_t>(need[j], std::min<uint64_t>(2 * (uint64_t)bk.n, 0xFFFFFFFFull))));
-      if (jobs[j].t0) HIP_TRY(hipMemcpy(grown.p, bk.p, sizeof(uint4) * s->host_state[jobs[j].slot].n_book, hipMemcpyDeviceToDevice));
-      bk.swap(grown);
-    }
-    jobs[j].book = bk.p;
-    jobs[j].book_cap = bk.n;
-  }
-  const uint64_t F = frame_off[n];
-  rc = push_pass(m, s->params.gmm_kernel, feats, F, s->feats, jobs, s->jobs, [&](const Chunk&, const double* table, hipStream_t stream) -> int {
-    BigramStreamArgs a{};
-    BigramArgs& ba = a.a;
-    ba = b->net;
-    ba.scores = table; ba.ld = m->ld;
-    ba.ac_pruning = s->params.acoustic_pruning; ba.lm_pruning = s->params.lm_pruning;
-    ba.global_states = 1;
-    ba.gs_ws = s->gs_ws.p; ba.gs_ws_words = bigram_gs_ws_words(ba.n_words, ba.n_positions);
-    ba.we_slot = s->we_slot.p; ba.we_bp = s->we_bp.p; ba.we_score = s->we_score.p;
-    a.jobs = s->jobs.p; a.state = s->state.p; a.lsave = s->lsave.p;
-    a.out_word = s->out_word.p; a.out_score = s->out_score.p; a.out_time = s->out_time.p; a.items_stride = s->slots.max_frames + 1;
-    HIP_TRY(launch_bigram_stream(a, (uint32_t)jobs.size(), stream));
-    if (m->profiling) {  // SURVEY 8(d)'s decoder model, 8 S + 4 P bytes per frame, as sr_recognize_bigram_corpus
-      m->prof.search_bytes += (8.0 * m->n_states + 4.0 * ba.n_positions) * (double)F;
-      m->prof.frames += F;
-    }
-    return SR_OK;
-  });
-  if (rc) return rc;
-  std::vector<BigramStreamState> st(s->slots.max_streams);  // (one copy of every slot's 32 bytes: cheaper than one per pushed slot)
-  HIP_TRY(hipMemcpy(st.data(), s->state.p, sizeof(BigramStreamState) * st.size(), hipMemcpyDeviceToHost));
-  uint32_t bad = 0xFFFFFFFFu;
-  for (const BigramStreamJob& j : jobs) {
-    s->slots.frames[j.slot] += j.k;
-    s->host_state[j.slot] = st[j.slot];
-    if (st[j.slot].flags & kBgStreamOverflow) { s->failed[j.slot] = 1; bad = s->slots.id[j.slot]; }
-  }
-  if (bad != 0xFFFFFFFFu) return fail(SR_EINTERNAL, "stream id %u: a book append passed the capacity the host grew it to", bad);
+  mark_rows(s->audio, s->slots, n, ids);
   return SR_OK;
   });
+}
+
+int sr_bigram_stream_set_frontend(sr_bigram_stream* s, sr_frontend* fe) {
+  return guarded(__func__, [&]() -> int { return set_frontend(s, fe); });
+}
+int sr_bigram_stream_push_audio(sr_bigram_stream* s, uint32_t n, const uint32_t* ids, const int16_t* samples, const uint64_t* sample_off,
+                                float* out_feats, uint64_t cap_rows, uint64_t* out_frame_off) {
+  return guarded(__func__, [&]() -> int { return push_audio(s, n, ids, samples, sample_off, false, out_feats, cap_rows, out_frame_off); });
+}
+int sr_bigram_stream_finish_audio(sr_bigram_stream* s, uint32_t n, const uint32_t* ids, float* out_feats, uint64_t cap_rows,
+                                  uint64_t* out_frame_off) {
+  return guarded(__func__, [&]() -> int { return push_audio(s, n, ids, nullptr, nullptr, true, out_feats, cap_rows, out_frame_off); });
 }
 
 int sr_bigram_stream_partial(sr_bigram_stream* s, uint32_t id, uint32_t* out_word, float* out_score, uint32_t* out_time, uint32_t cap,
@@ -5048,6 +5232,8 @@ int sr_bigram_stream_end(sr_bigram_stream* s, uint32_t id, uint32_t* out_word, f
   if (!s || !count || ((!out_word || !out_score || !out_time) && cap)) return fail(SR_EINVAL, "null argument");
   const int64_t slot = s->slots.find(id);
   if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
+  if (s->audio.kind[slot] == kStreamAudio)
+    return fail(SR_EINVAL, "stream id %u is fed as audio and not finished (sr_bigram_stream_finish_audio)", id);
   int rc = check_model(s->model);
   if (rc) return rc;
   rc = bigram_stream_items(s, (uint32_t)slot, id, out_word, out_score, out_time, cap, count);

@@ -32,7 +32,7 @@ def code_object(name: str, workdir: str) -> str:
 
 def demangle(names):
     out = subprocess.run(["c++filt"], input="\n".join(names), text=True, capture_output=True, check=True).stdout
-    return [re.sub(r"^void ", "", d).replace("srgpu::", "").split("(")[0] for d in out.splitlines()]
+    return [re.sub(r"^void ", "", d).replace("srgpu::", "").replace("(anonymous namespace)::", "").split("(")[0] for d in out.splitlines()]
 
 
 def kernel_metadata(co: str) -> dict:

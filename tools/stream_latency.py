@@ -14,7 +14,14 @@ sr_recognize_bigram_corpus; the streamed items (words, score bits, times) are ch
 
 --stable: after every push also asks for the stable prefix of the pushed streams (sr_stream_stable / sr_bigram_stream_stable, one
 call for all of them) and prints the median and p99 wall time of that call beside the push's; every answer is checked to be a
-prefix of its utterance's final result (where that is not empty)."""
+prefix of its utterance's final result (where that is not empty).
+
+--audio: the same stream set fed PCM samples (sr_stream_push_audio / sr_bigram_stream_push_audio) through a front end of the model's
+shape -- window 400, shift 160, 512-point transform, 13 cepstra and their deltas and delta-deltas (39 dimensions), step 3, no energy
+maximum -- on noise utterances of U{200..400} frames: every push hands each open stream its next --piece x 160 samples.  In the same
+run the rows the batch front end gives for the same utterances are streamed as feature pushes of --piece rows, and the two pushes'
+median and p99 wall times are printed side by side.  stream_frontend_kernel's device time is the difference of the two runs' search
+windows (sr_profile's HIP events: the front end's launch is counted there).  The two runs' results are checked to be equal."""
 from __future__ import annotations
 
 import argparse
@@ -37,7 +44,10 @@ def main():
     ap.add_argument("--kernel", choices=["default", "prefilter", "exact", "mfma"], default="default")
     ap.add_argument("--decoder", choices=["zerogram", "bigram"], default="zerogram")
     ap.add_argument("--stable", action="store_true", help="after every push, time the stable-prefix call on the pushed streams")
+    ap.add_argument("--audio", action="store_true", help="time audio pushes beside feature pushes of the same rows")
     args = ap.parse_args()
+    if args.audio:
+        return main_audio(args)
     if args.decoder == "bigram":
         return main_bigram(args)
 
@@ -228,6 +238,102 @@ def main_bigram(args):
         print(f"stable items were a prefix of the final items: {'yes' if stable_ok else 'NO'}")
         ok = ok and stable_ok
     return 0 if ok else 1
+
+
+def main_audio(args):
+    from speechrecognition_amd import capi, synth
+
+    D, shift, window = 39, 160, 400
+    bigram = args.decoder == "bigram"
+    kernel = {"mfma": capi.GMM_MFMA, "exact": capi.GMM_EXACT, "prefilter": capi.GMM_PREFILTER, "default": capi.GMM_DEFAULT}[args.kernel]
+    lex = synth.make_lexicon(2666, 3, 1, extra_states_last=1) if bigram else synth.make_lexicon(1333, 3, 1)
+    tmp = tempfile.mkdtemp(prefix="srstream_")
+    mp = os.path.join(tmp, "model.mix")
+    synth.write_mixset(mp, synth.make_mixset(lex.n_states, 64 if bigram else 32, D, seed=23))
+    word_off, automaton, sil = lex.flatten()
+    rng = np.random.default_rng(7)
+    n = min(args.utts, 256)
+    lens = rng.integers(200, 401, size=n)
+    audio = [np.clip(np.rint(rng.normal(0.0, 300.0, window + (int(T) - 1) * shift)), -32768, 32767).astype(np.int16) for T in lens]
+    mfcc = dict(sample_rate=16000.0, window=window, shift=shift, n_fft=512, n_mel=24, n_cepstra=13, f_low=0.0, f_high=8000.0,
+                preemphasis=0.97, energy_floor=1.0)
+    post = dict(n_static=13, n_first=13, n_second=13, deriv_step=3, energy_max_norm=0)
+
+    with capi.Model.from_mixset(mp, D) as m, m.frontend(mfcc, post) as fe:
+        if bigram:
+            lm_rng = np.random.default_rng(99)
+            nW = lex.n_words
+            lm = np.empty((nW, nW), np.float32)
+            for h0 in range(0, nW, 256):
+                pr = lm_rng.dirichlet(np.ones(nW), size=min(256, nW - h0))
+                lm[:, h0:h0 + pr.shape[0]] = (-np.log(np.maximum(pr, 1e-30))).T
+            net = m.bigram(word_off, automaton, lex.silence_idx, lm, np.array([[3.0, 0.0, 3.0, 150.0], [0.0001, 3.0, np.inf, 15.0]], np.float32))
+            open_set = lambda: m.bigram_stream(net, 200.0, capi.FLT_MAX, kernel, max_streams=args.streams, max_frames=400)  # noqa: E731
+        else:
+            net = m.lexicon(word_off, automaton, lex.silence_idx, (3.0, 0.0, 30.0), sil)
+            open_set = lambda: m.stream(net, 200.0, 10.0, kernel, max_streams=args.streams, max_frames=400)  # noqa: E731
+        soff = np.concatenate([[0], np.cumsum([len(x) for x in audio])]).astype(np.uint64)
+        corpus = fe.from_audio(np.concatenate(audio), soff)
+        rows_all, foff = corpus.download(), corpus.frame_off.astype(np.int64)
+        corpus.close()
+        rows = [rows_all[foff[u]:foff[u + 1]] for u in range(n)]
+
+        def run(as_audio):
+            src, k = (audio, args.piece * shift) if as_audio else (rows, args.piece)
+            with open_set() as st:
+                st.set_frontend(fe)
+                warm = [st.begin() for _ in range(args.streams)]  # warm: staging at the full push size, the kernels' code objects
+                for _ in range(2):
+                    (st.push_audio if as_audio else st.push)({sid: src[0][:k] for sid in warm})
+                for sid in warm:
+                    if as_audio:
+                        st.finish_audio([sid])
+                    st.end(sid)
+                m.profile(True)
+                todo, open_, got, ms = list(range(n)), {}, {}, []
+                while todo or open_:
+                    while todo and len(open_) < args.streams:
+                        open_[st.begin()] = (todo.pop(0), 0)
+                    push = {sid: src[u][t0:t0 + k] for sid, (u, t0) in open_.items()}
+                    t = time.perf_counter()
+                    (st.push_audio if as_audio else st.push)(push)
+                    ms.append(1e3 * (time.perf_counter() - t))
+                    for sid in list(open_):
+                        u, t0 = open_[sid]
+                        t0 += len(push[sid])
+                        if t0 == len(src[u]):
+                            if as_audio:  # (the finish's three rows stay out of the pushes' device times)
+                                capi.lib().sr_profile_enable(m.h, 0)
+                                st.finish_audio([sid])
+                                capi.lib().sr_profile_enable(m.h, 1)
+                            got[u] = st.end(sid)
+                            del open_[sid]
+                        else:
+                            open_[sid] = (u, t0)
+                return np.asarray(ms), m.profile_read(), got
+
+        a_ms, a_prof, a_got = run(True)
+        f_ms, f_prof, f_got = run(False)
+        net.close()
+
+    def equal(x, y):
+        if bigram:
+            return all(np.array_equal(np.asarray(i).view(np.uint32), np.asarray(j).view(np.uint32)) for i, j in zip(x, y))
+        return np.array_equal(x, y)
+
+    same = all(equal(a_got[u], f_got[u]) for u in range(n))
+    shape = "configs[4] shape (8000 states x 64, 2666 words), bigram stream" if bigram else "configs[2] model (4000 states x 32, 1333 words)"
+    print(f"workload: {shape}, {n} noise utterances, {int(foff[-1])} frames, {args.streams} concurrent streams, gmm_kernel {args.kernel}")
+    print(f"front end: window {window}, shift {shift}, n_fft 512, 24 filters, 13 + 13 + 13 features, step 3, no energy maximum")
+    for name, ms, prof, what in (("audio push  ", a_ms, a_prof, f"{args.piece * shift} samples"), ("feature push", f_ms, f_prof, f"{args.piece} rows")):
+        print(f"{name} ({what} per stream): {len(ms)} pushes; wall median {np.median(ms):.3f} ms, p99 {np.percentile(ms, 99):.3f} ms, "
+              f"min {ms.min():.3f} ms; device per push: scoring {prof['gmm_ms'] / len(ms):.3f} ms, search window {prof['search_ms'] / len(ms):.3f} ms "
+              f"({prof['search_launches']} windows)")
+    fe_ms = a_prof["search_ms"] / len(a_ms) - f_prof["search_ms"] / len(f_ms)
+    print(f"stream_frontend_kernel (HIP events: the audio run's search windows minus the feature run's): {fe_ms:.3f} ms per push")
+    print(f"audio push / feature push at the median: {np.median(a_ms) / np.median(f_ms):.2f}x (+{np.median(a_ms) - np.median(f_ms):.3f} ms)")
+    print(f"the audio run's results equal the feature run's: {'yes' if same else 'NO'}")
+    return 0 if same else 1
 
 
 if __name__ == "__main__":
