@@ -850,28 +850,53 @@ __global__ __launch_bounds__(NT) void gmm_refine_kernel(GmmRefineArgs a) {
 #pragma unroll
     for (int j = 0; j < SPW; j++) dcnt[j] = 0;
   }
+  // Which frames a wave takes.  HANDED OUT (every launch but the DEFER one): the frame range is cut into blocks of 64 frames and a wave
+  // draws the next block from the workgroup's ticket (a.tickets, zeroed by the launcher) whenever it starts one -- one block ahead, so
+  // that the atomic's round trip lies under a main pass.  With a fixed share per wave (wave w: frames w * 64 + it * NT + lane) the three
+  // waves of a SIMD drift apart -- the SIMD serves its oldest wave first; stamps on the headline launch show their iteration heads
+  // 55-65 iterations apart after 100 of 198 iterations, profiles/refine_iteration_head.txt -- and the last quarter of the launch runs
+  // with two waves, then one, on a SIMD whose evaluation needs three to hide its LDS reads behind: 0.9 ms of 12.8 at the headline.
+  // Now a SIMD's waves finish within one block of each other.  Nothing depends on which wave takes a block: the lists are the wave's
+  // own and carry the frame, the scores are minima.  FIXED (DEFER): the segments' capacity is a share of the WAVE's pairs
+  // (defer_cap_for), so a wave keeps its share there.
+  constexpr bool DYN = !DEFER;
   const uint64_t f_wave = f_begin + (uint64_t)wave * 64;
-  auto frame_of = [&](uint32_t lf) -> uint64_t { return f_wave + (uint64_t)(lf >> 6) * kRThreads + (lf & 63u); };
+  auto frame_of = [&](uint32_t lf) -> uint64_t { return DYN ? f_begin + lf : f_wave + (uint64_t)(lf >> 6) * kRThreads + (lf & 63u); };
   // (CH == 1 reads the shift from the kernel argument although it is 0 there, and keeps the run-time branches of the round-3
   // kernel below: with the shift folded to a constant the compiler schedules the SAME instruction mix 1.0 ms slower on
   // configs[2] -- 16.0 against 15.0 ms, A/B on one box, gpurun_out/r4_ab_refine_cfg3.txt; profiles/r3_refine_closed.txt has
   // seen that before: "the present order is a local optimum somebody found")
   const uint32_t chunk_shift = CH == 1 ? (a.chunks == 1 ? 0u : a.chunks == 2 ? 1u : 2u) : CH == 2 ? 1u : VS == 2 ? 3u : 2u;
 
-  const uint32_t n_it = (uint32_t)((f_end - f_begin + kRThreads - 1) / kRThreads);
-  for (uint32_t it = 0; it < n_it; it++) {
-    const uint64_t fr = f_wave + (uint64_t)it * kRThreads + lane;
+  // blocks (DYN) or passes of the workgroup's threads (fixed shares) over the frame range; `it` = the block / the pass the wave is on
+  const uint32_t n_loop = (uint32_t)((f_end - f_begin + (DYN ? 64 : kRThreads) - 1) / (DYN ? 64 : kRThreads));
+  uint32_t* ticket = a.tickets + (blockIdx.y * gridDim.x + blockIdx.x);
+  auto draw = [&]() -> uint32_t {  // (lane 0's value counts)
+    return lane == 0 ? __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+  };
+  uint32_t tk = 0, it = 0;
+  if constexpr (DYN) { tk = draw(); it = (uint32_t)__builtin_amdgcn_readfirstlane(tk); }
+  while (it < n_loop) {
+    const uint64_t fr = DYN ? f_begin + (uint64_t)it * 64 + lane : f_wave + (uint64_t)it * kRThreads + lane;
     const bool valid = fr < f_end;
     const uint64_t f = valid ? fr : f_end - 1;  // lanes past the end shadow the last frame; they store and append nothing
     const uint32_t lf = it * 64u + (uint32_t)lane;
+    // every mask quad of the iteration is requested here, with the features: one round trip per iteration (the second quad used to be
+    // requested at the top of state 4's evaluation and waited for on the spot: 1 300-1 550 cycles of each wave's 25 500 per iteration)
+    uint4 mq[CH == 1 ? SPW / 4 : 1];
+    if constexpr (CH == 1) {
+#pragma unroll
+      for (int h = 0; h < SPW / 4; h++) mq[h] = reinterpret_cast<const uint4*>(a.mask)[(uint64_t)((s0 >> 2) + h) * a.n_frames + f];
+    }
     load_x(f);
+    if constexpr (DYN) tk = draw();  // the next block, behind the loads: back long before the main pass is over
     // main pass: the first candidate of every state -- one evaluation per state in every lane, no divergence
     constexpr int RS = SPW / (CH * VS);  // whole states of this workgroup
     double res[RS];
     if constexpr (CH == 1) {
 #pragma unroll
       for (int h = 0; h < SPW / 4; h++) {
-        const uint4 v = reinterpret_cast<const uint4*>(a.mask)[(uint64_t)((s0 >> 2) + h) * a.n_frames + f];
+        const uint4 v = mq[h];
         const uint32_t mk[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int jj = 0; jj < 4; jj++) {
@@ -1050,7 +1075,8 @@ __global__ __launch_bounds__(NT) void gmm_refine_kernel(GmmRefineArgs a) {
     // ---- work off the lists: every list is kept below 64 pending frames (one more iteration's appends must fit);
     // after the last iteration they are emptied.  One batch = <= 64 pairs of ONE state j (wave-uniform level, j, n):
     // level 1 evaluates each pair's second candidate, level 2 everything after the second.
-    const bool last = it + 1 == n_it;
+    const uint32_t it_next = DYN ? (uint32_t)__builtin_amdgcn_readfirstlane(tk) : it + 1;
+    const bool last = it_next >= n_loop;
     if constexpr (!DEFER)
     for (;;) {
       uint32_t level, j, n;
@@ -1133,6 +1159,7 @@ __global__ __launch_bounds__(NT) void gmm_refine_kernel(GmmRefineArgs a) {
         if (lower) (void)__builtin_amdgcn_global_atomic_fmin_f64((__attribute__((address_space(1))) double*)o, cur);
       }
     }
+    it = it_next;
   }
   if constexpr (DEFER) {
 #pragma unroll
@@ -1373,7 +1400,7 @@ static void refine_grid(const GmmRefineArgs& a, int spw, uint32_t* n_sgroups, ui
 size_t gmm_refine_ring_words(const GmmRefineArgs& a) {
   uint32_t g; uint64_t sp, fps;
   refine_grid(a, refine_spw(a), &g, &sp, &fps);
-  return (size_t)g * sp * kRWaves * kRingWave;
+  return (size_t)g * sp * kRWaves * kRingWave + (size_t)g * sp;  // the waves' lists, then one block ticket per workgroup
 }
 
 void gmm_refine_geometry(const GmmRefineArgs& a, uint32_t out[4]) {
@@ -1412,6 +1439,8 @@ static hipError_t launch_refine_one(const GmmRefineArgs& a0, hipStream_t stream)
   uint64_t splits;
   refine_grid(a, SPW, &n_sgroups, &splits, &a.frames_per_split);
   const dim3 grid(n_sgroups, (unsigned)splits), block(NT);
+  a.tickets = a.ring + (size_t)n_sgroups * splits * kRWaves * kRingWave;
+  if (hipError_t e = hipMemsetAsync(a.tickets, 0, (size_t)n_sgroups * splits * sizeof(uint32_t), stream); e != hipSuccess) return e;
   if constexpr (CH > 1 && NT == kRThreads && SPW == 8) {
     if (a.defer && a.defer_cnt && a.defer_cap) {  // main pass with deferred lists, then every wave on the leftovers
       auto k1 = gmm_refine_kernel<DT, NS, SPW, CH, NT, VS, true>;

@@ -97,6 +97,7 @@ struct GmmRefineArgs {
   uint64_t frames_per_split;    // set by the launcher
   unsigned long long* n_refined;  // optional: += densities evaluated (profiling)
   uint32_t* ring;               // workspace, gmm_refine_ring_words() u32: wave-private lists of pairs with further candidates
+  uint32_t* tickets;            // set by the launcher (the workspace's tail): per workgroup the next 64-frame block to hand out
   // deferred leftovers (mixtures of more than 32 densities, gmm_refine_defer_layout): per wave and panel a segment of defer_cap 16-byte
   // entries + its count; null: the lists are worked off inside the refinement kernel (rounds 2-4)
   void* defer;
@@ -109,7 +110,9 @@ void gmm_refine_defer_layout(const GmmRefineArgs& a, size_t budget_bytes, uint32
                              size_t* n_counts);
 size_t gmm_refine_ring_words(const GmmRefineArgs& a);  // needs n_frames, n_pstates, dim, n_slots
 // the grid launch_gmm_refine gives this shape (same fields): threads per workgroup, pseudo-states per workgroup, frames per workgroup,
-// chunks per state -- thread (wave, lane) of the workgroup over split y takes frame y * out[2] + wave * 64 + it * out[0] + lane in iteration it
+// chunks per state -- the workgroup over split y takes frames y * out[2] .. in blocks of 64, one block per wave at a time: on the deferred
+// route thread (wave, lane) takes frame y * out[2] + wave * 64 + it * out[0] + lane in iteration it, on every other route a wave draws its
+// next block when it starts one (in that order when the waves keep pace)
 void gmm_refine_geometry(const GmmRefineArgs& a, uint32_t out[4]);
 // route: kPfStaged -- frames stationary, the model streamed through LDS (needs split_begin, nx, ny); kPfStationary -- a 4-state group
 // stationary in a wave's registers, the frames' ready-made operands streamed past it (needs n_groups, bfrag, bnorm; builds the
