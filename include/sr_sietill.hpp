@@ -748,6 +748,42 @@ class FrontEnd {
     fe_.reset(fe, sr_frontend_destroy);
     n_static_ = q.n_static;
   }
+  // a warped front end (srgpu.h: sr_frontend_create_warped): a filterbank per warp factor beside the unwarped one
+  FrontEnd(sr_model* model, sr_mfcc_params const& mfcc, std::vector<double> const& alpha, double break_frac, FeaturePostProcessor const& post) {
+    const sr_feature_post_params q = post.params();
+    sr_vtln_params v{};
+    v.n_warps = (uint32_t)alpha.size(); v.alpha = alpha.data(); v.break_frac = break_frac;
+    sr_frontend* fe = nullptr;
+    check(sr_frontend_create_warped(model, &mfcc, &v, &q, &fe));
+    fe_.reset(fe, sr_frontend_destroy);
+    n_static_ = q.n_static;
+    n_warps_ = v.n_warps;
+  }
+  uint32_t n_warps() const { return n_warps_; }
+  // the chunks of warps vtln_costs takes for that many frames and utterances (sr_vtln_chunks)
+  uint32_t vtln_chunks(uint64_t n_frames, uint32_t n_utts) const {
+    uint32_t n = 0;
+    check(sr_vtln_chunks(fe_.get(), n_frames, n_utts, &n));
+    return n;
+  }
+  // both stages, utterance u through the filters of warp utt_warp[u]
+  std::shared_ptr<sr_corpus> from_audio_warped(std::vector<int16_t> const& samples, std::vector<uint64_t> const& sample_off,
+                                               std::vector<uint32_t> const& utt_warp, std::vector<uint64_t>& frame_off) {
+    frame_off.assign(sample_off.size(), 0);
+    sr_corpus* c = nullptr;
+    check(sr_corpus_from_audio_warped(fe_.get(), samples.data(), sample_off.data(), (uint32_t)sample_off.size() - 1, utt_warp.data(), &c,
+                                      frame_off.data()));
+    return std::shared_ptr<sr_corpus>(c, sr_corpus_destroy);
+  }
+  // the warp search: cost [n_speakers x n_warps] of the speakers' utterances along `states`, an alignment of the unwarped corpus;
+  // frames [n_speakers].  Smaller is better; no Jacobian term.
+  void vtln_costs(std::vector<int16_t> const& samples, std::vector<uint64_t> const& sample_off, std::vector<uint16_t> const& states,
+                  std::vector<uint32_t> const& utt_speaker, uint32_t n_speakers, std::vector<double>& cost, std::vector<uint64_t>& frames) {
+    cost.assign((size_t)n_speakers * n_warps_, 0.0);
+    frames.assign(n_speakers, 0);
+    check(sr_vtln_costs_corpus(fe_.get(), samples.data(), sample_off.data(), (uint32_t)sample_off.size() - 1, states.data(), utt_speaker.data(),
+                               n_speakers, cost.data(), frames.data()));
+  }
   uint64_t frames(uint64_t n_samples) const {
     uint64_t T = 0;
     check(sr_frontend_frames(fe_.get(), n_samples, &T));
@@ -785,8 +821,16 @@ class FrontEnd {
 
  private:
   std::shared_ptr<sr_frontend> fe_;
-  uint32_t n_static_ = 0;
+  uint32_t n_static_ = 0, n_warps_ = 0;
 };
+
+// per speaker the first warp of smallest cost; `fallback` for fewer than min_frames frames or costs that are not finite (sr_vtln_choose)
+inline std::vector<uint32_t> vtln_choose(std::vector<double> const& cost, std::vector<uint64_t> const& frames, uint32_t n_warps,
+                                         uint64_t min_frames, uint32_t fallback) {
+  std::vector<uint32_t> out(frames.size(), fallback);
+  check(sr_vtln_choose((uint32_t)frames.size(), n_warps, cost.data(), frames.data(), min_frames, fallback, out.data()));
+  return out;
+}
 
 inline void StreamingRecognizer::set_frontend(FrontEnd& fe) { check(sr_stream_set_frontend(s_, fe.handle())); }
 

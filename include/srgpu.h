@@ -713,6 +713,74 @@ SR_API int sr_corpus_from_cepstra(sr_frontend* fe, const float* cepstra, const u
 SR_API int sr_mfcc_corpus(sr_frontend* fe, const int16_t* samples, const uint64_t* sample_off, uint32_t n_utts, float* out_cepstra,
                           uint64_t* out_frame_off /*[n_utts+1]*/);
 
+/* ---- vocal-tract-length normalisation (VTLN): warped filterbanks, the warp search, warped corpora --------------------------------------
+ * The one speaker normalisation that lives inside the front end.  A warped front end holds, beside the unwarped filterbank, one
+ * filterbank per warp factor alpha[a]; a speaker's warp is found by scoring its utterances under every warp along an alignment
+ * (sr_vtln_costs_corpus, sr_vtln_choose), and a corpus is then made with a warp per utterance (sr_corpus_from_audio_warped).
+ *
+ * The warp has one break point and is piecewise linear.  For a warp factor alpha > 0 and break_frac in (0, 1):
+ *   f0 = break_frac * f_high * min(1, 1 / alpha)
+ *   g_alpha(f) = alpha * f                                                             for f <= f0
+ *              = alpha * f0 + (f_high - alpha * f0) / (f_high - f0) * (f - f0)           for f >  f0
+ * so g is continuous and monotone and g(f_high) = f_high.  alpha == 1.0 is the identity by definition: g(f) = f exactly, with no
+ * arithmetic.  The filters' edges stay where the MFCC stage's definition puts them; bin k has, in filter m of warp alpha, the weight of
+ * the unwarped triangle evaluated at g_alpha(f_k): max(0, min((g(f_k) - l) / (c - l), (r - g(f_k)) / (r - c))), computed in double and
+ * stored as float like the unwarped weights.  Window, twiddles and DCT are shared by all warps, so the filterbank of alpha == 1.0 is
+ * the unwarped front end's, bit for bit, and so are its cepstra.  (tests/vtln_reference.py restates all of this in float64.)
+ * NO JACOBIAN TERM is applied anywhere: the costs below are plain emission costs.  A caller who wants a per-warp penalty adds
+ * frames[s] * penalty[a] to the returned costs before choosing.
+ *
+ * sr_frontend_create_warped   a front end with n_warps filterbanks.  It checks everything sr_frontend_create checks, and: SR_EINVAL for
+ *     mfcc == NULL, vtln == NULL, n_warps == 0, alpha == NULL, an alpha that is not finite and positive, break_frac outside (0, 1), and --
+ *     naming warp and filter -- a filter of any warp without a bin of positive weight; SR_ELIMIT for n_warps > 32 or n_warps * n_mel >
+ *     1024 (the logarithms of one frame under every warp are kept in 4 KiB of a wave's LDS; 13 warps of 40 filters are 520).  The
+ *     unwarped filterbank is always built, whether or not 1.0 is among the alphas, and every entry point that takes a front end --
+ *     sr_corpus_from_audio, sr_mfcc_corpus, sr_corpus_from_cepstra, sr_stream_set_frontend and its bigram twin -- accepts a warped one
+ *     and behaves exactly as on an unwarped front end of the same parameters.  Streaming has no per-stream warp.
+ * sr_frontend_warps           *n_warps: the warps of the front end, 0 for an unwarped one.
+ * sr_corpus_from_audio_warped sr_corpus_from_audio with utterance u through the filters of warp utt_warp[u].  An index >= n_warps, a NULL
+ *     utt_warp and an unwarped front end are SR_EINVAL, before any launch.  The result is a corpus like sr_corpus_from_audio's, and an
+ *     utterance's rows depend on its samples and its warp alone, not on the batch.
+ * sr_vtln_costs_corpus        the warp search.  states [frames] is an alignment of the UNWARPED corpus: one state per frame, the frame
+ *     offsets being the front end's own (sr_frontend_frames; sr_corpus_from_audio's out_frame_off).  For every warp a, every utterance
+ *     goes through warp a's filters and the post-processing stage, and row t is scored against states[t]: MixtureModel::score(row,
+ *     states[t]), the value sr_path_scores_corpus returns on sr_corpus_from_audio_warped's corpus with every utterance on warp a, bit
+ *     for bit.  The order of summation is the definition: an utterance's sum is the sequential FP64 sum of its frames' scores in
+ *     ascending order; out_cost[s * n_warps + a] is the sequential FP64 sum of the sums of speaker s's utterances (utt_speaker[u] == s,
+ *     utterances without frames included) in ascending index.  The first addend of each sum is taken as is and an empty sum is +0.
+ *     No atomics: two calls give the same bits, and the bits do not depend on how the warps are processed in chunks.  A chunk is as
+ *     many warps as keep the buffers that grow with warps x frames -- cepstra, rows, the alignment's copies, scores -- within a
+ *     budget, a quarter of the score workspace (SRGPU_VTLN_KB, read when the model is made, sets it in KiB), and at least one warp;
+ *     the samples, the offsets and the n_warps x n_utts utterance sums are not counted, so the budget bounds the chunks, not the
+ *     call's whole device memory.  sr_vtln_chunks tells how many chunks a call on that many frames and utterances takes.
+ *     SRGPU_VTLN_TIMING, read with the budget, makes every call print one line to stderr, `vtln_timing chunks N mfcc_warps_ms ..
+ *     post_ms .. score_ms .. reduce_ms ..`, its stages' HIP-event times for tools/vtln_time.py (five event records per chunk more).
+ *     out_frames[s]: the speaker's frames.  Costs are costs: smaller is better.  A frame's power spectrum is computed once for all
+ *     warps (mfcc_warps_kernel).  Checked before any launch (SR_EINVAL): an unwarped front end, the offsets, a
+ *     state >= n_states, a speaker >= n_speakers, NULL arguments; SR_ELIMIT as for sr_corpus_from_audio.
+ * sr_vtln_choose              host only.  out_warp[s]: the first warp of smallest cost of speaker s -- or fallback_warp where the
+ *     speaker has fewer than min_frames frames, where its smallest cost is not finite, or where any of its costs is NaN.  SR_EINVAL
+ *     for n_warps == 0, fallback_warp >= n_warps, a NULL argument with n_speakers > 0.
+ * A refused call leaves *out NULL and the host outputs untouched. */
+typedef struct {
+  uint32_t n_warps;
+  const double* alpha;           /* [n_warps] warp factors, each finite and > 0 */
+  double break_frac;             /* in (0, 1): the break point as a fraction of f_high (0.875 is common) */
+} sr_vtln_params;
+SR_API int sr_frontend_create_warped(sr_model* m, const sr_mfcc_params* mfcc, const sr_vtln_params* vtln, const sr_feature_post_params* post,
+                                     sr_frontend** out);
+SR_API int sr_frontend_warps(const sr_frontend* fe, uint32_t* n_warps);
+SR_API int sr_corpus_from_audio_warped(sr_frontend* fe, const int16_t* samples, const uint64_t* sample_off, uint32_t n_utts,
+                                       const uint32_t* utt_warp /*[n_utts]*/, sr_corpus** out, uint64_t* out_frame_off /*[n_utts+1]*/);
+SR_API int sr_vtln_costs_corpus(sr_frontend* fe, const int16_t* samples, const uint64_t* sample_off, uint32_t n_utts,
+                                const uint16_t* states /*[frames]: an alignment*/, const uint32_t* utt_speaker /*[n_utts]*/,
+                                uint32_t n_speakers, double* out_cost /*[n_speakers][n_warps]*/, uint64_t* out_frames /*[n_speakers]*/);
+/* *out_chunks: the chunks of warps sr_vtln_costs_corpus takes for n_frames frames in n_utts utterances (host only; SR_EINVAL for an
+ * unwarped front end or a NULL argument, SR_ELIMIT where the call itself would return it) */
+SR_API int sr_vtln_chunks(const sr_frontend* fe, uint64_t n_frames, uint32_t n_utts, uint32_t* out_chunks);
+SR_API int sr_vtln_choose(uint32_t n_speakers, uint32_t n_warps, const double* cost, const uint64_t* frames, uint64_t min_frames,
+                          uint32_t fallback_warp, uint32_t* out_warp /*[n_speakers]*/);
+
 /* ---- streaming from audio: PCM samples into a stream set, the front end on the device ------------------------------------------------
  * With a front end attached, a stream set takes an utterance's samples as they arrive, in pieces of any size, instead of finished
  * feature rows.  step = deriv_step.  An utterance fed as audio has received N samples so far and has S = sr_frontend_frames(N) static

@@ -43,6 +43,7 @@ SYMBOLS = [
     "sr_lda_statistics_corpus", "sr_lda_estimate", "sr_corpus_splice_transform",
     "sr_frontend_create", "sr_frontend_destroy", "sr_frontend_frames", "sr_corpus_from_audio", "sr_corpus_from_cepstra", "sr_mfcc_corpus",
     "sr_corpus_download",
+    "sr_frontend_create_warped", "sr_frontend_warps", "sr_corpus_from_audio_warped", "sr_vtln_costs_corpus", "sr_vtln_chunks", "sr_vtln_choose",
     "sr_bigram_create", "sr_bigram_destroy", "sr_bigram_describe", "sr_recognize_bigram_corpus",
     "sr_bigram_word_posteriors_corpus", "sr_recognize_bigram_confidence_corpus",
     "sr_bigram_occupancies_corpus", "sr_bigram_mmi_statistics_corpus",
@@ -102,6 +103,11 @@ class FeaturePostParams(C.Structure):
     """sr_feature_post_params"""
     _fields_ = [("n_static", C.c_uint32), ("n_first", C.c_uint32), ("n_second", C.c_uint32), ("deriv_step", C.c_uint32),
                 ("energy_max_norm", C.c_int32), ("mean", C.c_void_p), ("stddev", C.c_void_p)]
+
+
+class VtlnParams(C.Structure):
+    """sr_vtln_params"""
+    _fields_ = [("n_warps", C.c_uint32), ("alpha", C.c_void_p), ("break_frac", C.c_double)]
 
 
 class Profile(C.Structure):
@@ -186,6 +192,12 @@ def lib():
         L.sr_corpus_from_cepstra.argtypes = [vp, vp, vp, u32, C.POINTER(vp)]
         L.sr_mfcc_corpus.argtypes = [vp, vp, vp, u32, vp, vp]
         L.sr_corpus_download.argtypes = [vp, vp]
+        L.sr_frontend_create_warped.argtypes = [vp, C.POINTER(MfccParams), C.POINTER(VtlnParams), C.POINTER(FeaturePostParams), C.POINTER(vp)]
+        L.sr_frontend_warps.argtypes = [vp, C.POINTER(u32)]
+        L.sr_corpus_from_audio_warped.argtypes = [vp, vp, vp, u32, vp, C.POINTER(vp), vp]
+        L.sr_vtln_costs_corpus.argtypes = [vp, vp, vp, u32, vp, vp, u32, vp, vp]
+        L.sr_vtln_chunks.argtypes = [vp, u64, u32, C.POINTER(u32)]
+        L.sr_vtln_choose.argtypes =[u32, u32, vp, vp, u64, u32, vp]
         L.sr_word_posteriors_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, vp]
         L.sr_recognize_confidence_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, vp, vp, vp, vp, vp]
         L.sr_net_occupancies_corpus.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, vp, vp, vp]
@@ -449,12 +461,13 @@ class Model:
     def upload(self, feats, frame_off, asynchronous=False):
         return Corpus(self, feats, frame_off, asynchronous)
 
-    def frontend(self, mfcc, post):
+    def frontend(self, mfcc, post, vtln=None):
         """sr_frontend_create: the audio front end of this model.  mfcc: a dict of sr_mfcc_params' fields (sample_rate, window, shift,
         n_fft, n_mel, n_cepstra, f_low, f_high, preemphasis, energy_floor) or None for cepstra in only; post: a dict of n_static,
-        n_first, n_second, deriv_step, energy_max_norm and optionally mean, stddev (f64[n_static + n_first + n_second]).  Close it
-        before the model."""
-        return FrontEnd(self, mfcc, post)
+        n_first, n_second, deriv_step, energy_max_norm and optionally mean, stddev (f64[n_static + n_first + n_second]).
+        vtln=dict(alpha=[...], break_frac=...): sr_frontend_create_warped, a filterbank per warp factor beside the unwarped one.
+        Close it before the model."""
+        return FrontEnd(self, mfcc, post, vtln)
 
     def recognize_batch(self, lexicon, feats, frame_off, am_threshold, word_penalty, kernel=GMM_PREFILTER):
         """sr_recognize_batch: host buffers in, words out (fed asynchronously while the first chunks are scored)."""
@@ -1338,8 +1351,9 @@ class Corpus:
 class FrontEnd:
     """sr_frontend handle: PCM samples or static cepstra in, a resident Corpus of the model out (Model.frontend)."""
 
-    def __init__(self, model, mfcc, post):
+    def __init__(self, model, mfcc, post, vtln=None):
         self.model = model
+        self.n_warps = 0
         post = dict(post)
         mean, stddev = post.pop("mean", None), post.pop("stddev", None)
         self._mean = None if mean is None else np.ascontiguousarray(mean, dtype=np.float64)
@@ -1351,8 +1365,16 @@ class FrontEnd:
             self.mfcc_params = MfccParams(**{k: (int(v) if k in ints else float(v)) for k, v in mfcc.items()})
         self.n_static = self.post.n_static
         self.h = C.c_void_p()
-        _check(lib().sr_frontend_create(model.h, None if self.mfcc_params is None else C.byref(self.mfcc_params), C.byref(self.post),
-                                        C.byref(self.h)))
+        mp = None if self.mfcc_params is None else C.byref(self.mfcc_params)
+        if vtln is None:
+            _check(lib().sr_frontend_create(model.h, mp, C.byref(self.post), C.byref(self.h)))
+            return
+        self.alpha = np.ascontiguousarray(vtln["alpha"], dtype=np.float64)
+        vp = VtlnParams(n_warps=len(self.alpha), alpha=_ptr(self.alpha), break_frac=float(vtln["break_frac"]))
+        _check(lib().sr_frontend_create_warped(model.h, mp, C.byref(vp), C.byref(self.post), C.byref(self.h)))
+        n = C.c_uint32()
+        _check(lib().sr_frontend_warps(self.h, C.byref(n)))
+        self.n_warps = n.value
 
     def close(self):
         if self.h:
@@ -1388,6 +1410,44 @@ class FrontEnd:
         h = C.c_void_p()
         _check(lib().sr_corpus_from_audio(self.h, _ptr(samples), _ptr(sample_off), n, C.byref(h), _ptr(frame_off)))
         return self._corpus(h, frame_off)
+
+    def from_audio_warped(self, samples, sample_off, utt_warp):
+        """sr_corpus_from_audio_warped: from_audio with utterance u through the filters of warp utt_warp[u] (a warped front end)"""
+        samples = np.ascontiguousarray(samples, dtype=np.int16)
+        sample_off = np.ascontiguousarray(sample_off, dtype=np.uint64)
+        utt_warp = np.ascontiguousarray(utt_warp, dtype=np.uint32)
+        n = len(sample_off) - 1
+        assert len(samples) >= int(sample_off[-1]) and len(utt_warp) == n
+        frame_off = np.zeros(n + 1, dtype=np.uint64)
+        h = C.c_void_p()
+        _check(lib().sr_corpus_from_audio_warped(self.h, _ptr(samples), _ptr(sample_off), n, _ptr(utt_warp), C.byref(h), _ptr(frame_off)))
+        return self._corpus(h, frame_off)
+
+    def vtln_chunks(self, n_frames, n_utts):
+        """sr_vtln_chunks: the chunks of warps vtln_costs takes for that many frames and utterances (the model's SRGPU_VTLN_KB budget)"""
+        n = C.c_uint32()
+        _check(lib().sr_vtln_chunks(self.h, int(n_frames), int(n_utts), C.byref(n)))
+        return n.value
+
+    def vtln_costs(self, samples, sample_off, states, utt_speaker, n_speakers):
+        """sr_vtln_costs_corpus: the warp search.  states u16[frames]: an alignment of the unwarped corpus; utt_speaker u32[n_utts]
+        -> (cost f64[n_speakers, n_warps], the emission cost of a speaker's utterances under every warp, smaller is better;
+        frames u64[n_speakers])"""
+        samples = np.ascontiguousarray(samples, dtype=np.int16)
+        sample_off = np.ascontiguousarray(sample_off, dtype=np.uint64)
+        states = np.ascontiguousarray(states, dtype=np.uint16)
+        utt_speaker = np.ascontiguousarray(utt_speaker, dtype=np.uint32)
+        n = len(sample_off) - 1
+        assert len(samples) >= int(sample_off[-1]) and len(utt_speaker) == n
+        if self.mfcc_params is not None and n and (np.diff(sample_off.astype(np.int64)) >= 0).all():
+            # sr_frontend_frames' rule on the host: the C side does not know how long `states` is
+            lens, window, shift = np.diff(sample_off.astype(np.int64)), self.mfcc_params.window, max(self.mfcc_params.shift, 1)
+            assert len(states) == int(np.where(lens < window, 0, 1 + (lens - window) // shift).sum())
+        cost = np.zeros((int(n_speakers), self.n_warps), dtype=np.float64)
+        frames = np.zeros(int(n_speakers), dtype=np.uint64)
+        _check(lib().sr_vtln_costs_corpus(self.h, _ptr(samples), _ptr(sample_off), n, _ptr(states), _ptr(utt_speaker), int(n_speakers),
+                                          _ptr(cost), _ptr(frames)))
+        return cost, frames
 
     def from_cepstra(self, cepstra, frame_off):
         """sr_corpus_from_cepstra: static cepstra f32[frames, n_static] -> Corpus; close it before the model."""
@@ -1584,6 +1644,17 @@ def mixset_write(path, dim, dens_off, dens_mean, dens_var, acc):
     ma, mw, va, vw = (np.ascontiguousarray(x, dtype=np.float64) for x in acc)
     _check(lib().sr_mixset_write(str(path).encode(), dim, len(dens_off) - 1, _ptr(dens_off), len(mw), len(vw), _ptr(dens_mean),
                                  _ptr(dens_var), _ptr(ma), _ptr(mw), _ptr(va), _ptr(vw)))
+
+
+def vtln_choose(cost, frames, min_frames=0, fallback=0):
+    """sr_vtln_choose (host only): cost f64[n_speakers, n_warps], frames u64[n_speakers] -> u32[n_speakers], per speaker the first warp
+    of smallest cost; `fallback` for fewer than min_frames frames, a smallest cost that is not finite, or a NaN among the costs"""
+    cost = np.ascontiguousarray(cost, dtype=np.float64)
+    frames = np.ascontiguousarray(frames, dtype=np.uint64)
+    assert cost.ndim == 2 and len(frames) == cost.shape[0]
+    out = np.zeros(max(cost.shape[0], 1), dtype=np.uint32)
+    _check(lib().sr_vtln_choose(cost.shape[0], cost.shape[1], _ptr(cost), _ptr(frames), int(min_frames), int(fallback), _ptr(out)))
+    return out[:cost.shape[0]]
 
 
 def shard_utterances(frame_off, n_shards):

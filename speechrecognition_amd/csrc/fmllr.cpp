@@ -137,3 +137,18 @@ extern "C" SR_API int sr_fmllr_estimate(uint32_t dim, uint32_t n_speakers, const
 #include "mllt.cpp"  // sr_mllt_estimate: the MLLT transform, likewise
 #include "lda.cpp"   // sr_lda_estimate: the LDA projection, likewise
 #include "map.cpp"   // the host part of sr_model_map_adapt: checks, the mean rows' plan, the weight update, likewise
+
+// sr_vtln_choose: a speaker's warp from the warp search's costs (vtln_tables.h); host code like the estimates above
+#include "vtln_tables.h"
+
+extern "C" SR_API int sr_vtln_choose(uint32_t n_speakers, uint32_t n_warps, const double* cost, const uint64_t* frames, uint64_t min_frames,
+                                     uint32_t fallback_warp, uint32_t* out_warp) {
+  return srhost::guarded(__func__, [&]() -> int {
+  if (n_warps == 0) return set_error(SR_EINVAL, "sr_vtln_choose: n_warps is 0");
+  if (fallback_warp >= n_warps) return set_error(SR_EINVAL, "sr_vtln_choose: fallback_warp >= n_warps");
+  if (n_speakers == 0) return SR_OK;
+  if (!cost || !frames || !out_warp) return set_error(SR_EINVAL, "sr_vtln_choose: null argument");
+  srplan::vtln_choose(n_speakers, n_warps, cost, frames, min_frames, fallback_warp, out_warp);
+  return SR_OK;
+  });
+}

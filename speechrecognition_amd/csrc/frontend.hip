@@ -12,9 +12,14 @@
 //   P[k] = |X[k]|^2; lane m sums filter m's bins in ascending order and takes the clamped logarithm; lane i sums cepstrum i over
 //   the filters in ascending order.
 // No atomics, and nothing a frame computes depends on its span or its batch: the same samples give the same bits anywhere.
+// With a per-utterance warp index (sr_corpus_from_audio_warped) a span's workgroup takes its utterance's filters instead of the
+// unwarped ones; nothing else changes.
+//
+// mfcc_warps_kernel and vtln_reduce_kernel (sr_vtln_costs_corpus): every warp's cepstra from one power spectrum per frame, and the
+// costs' sums in their defined order; described where they stand.
 //
 // stream_frontend_kernel (sr_stream_push_audio).  The same two stages for utterances whose samples arrive in pieces: a workgroup per
-// pushed utterance computes the new frames' statics with mfcc_kernel's per-frame body (mfcc_frame), stages them behind the 2 step
+// pushed utterance computes the new frames' statics with mfcc_kernel's per-frame body (mfcc_power, mfcc_cepstra), stages them behind the 2 step
 // statics the slot keeps, and emits the rows whose windows are complete with feature_post_kernel's arithmetic (post_value).  With no
 // energy maximum a streamed row carries the batch's bits; the maximum is the causal one of include/srgpu.h.
 //
@@ -34,11 +39,13 @@ __device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(
 __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
 
-// One frame through window, transform, filterbank, logarithm and DCT: one wave64 in LDS of its own (A, B: M complex points each, L: 64
-// floats).  yf: the frame's pre-emphasised samples; out: its n_cepstra cepstra, stored by an active wave only.  Every wave of the
-// workgroup goes through every barrier: one without a frame left computes some frame again and stores nothing.
-__device__ __forceinline__ void mfcc_frame(const MfccArgs& a, const float* yf, float2* A, float2* B, float* L, uint32_t lane, bool active,
-                                           float* out) {
+// One frame through window, transform, filterbank, logarithm and DCT, in two halves: one wave64 in LDS of its own (A, B: M complex
+// points each, L: 64 floats).  Every wave of the workgroup goes through every barrier: one without a frame left computes some frame
+// again and stores nothing.
+//
+// The first half: yf, the frame's pre-emphasised samples -> P[k] = |X[k]|^2, k = 0 .. M, in whichever of A and B the transform did not
+// end in; complete for the whole wave on return.
+__device__ __forceinline__ const float* mfcc_power(const MfccArgs& a, const float* yf, float2* A, float2* B, uint32_t lane) {
   const uint32_t M = a.n_fft >> 1;
   for (uint32_t n = lane; n < M; n += 64) {
     const uint32_t i0 = 2 * n, i1 = 2 * n + 1;
@@ -82,10 +89,22 @@ __device__ __forceinline__ void mfcc_frame(const MfccArgs& a, const float* yf, f
     P[k] = xk.x * xk.x + xk.y * xk.y;
   }
   __syncthreads();
+  return P;
+}
+
+// a filterbank: per filter its first bin, its bins and where its weights begin in w
+struct MelFilters {
+  const uint32_t* first; const uint32_t* count; const uint32_t* off;
+  const float* w;
+};
+
+// The second half: P, a filterbank and the DCT -> out, the frame's n_cepstra cepstra, stored by an active wave only.
+__device__ __forceinline__ void mfcc_cepstra(const MfccArgs& a, const MelFilters& f, const float* P, float* L, uint32_t lane, bool active,
+                                             float* out) {
   if (lane < a.n_mel) {
-    const float* w = a.mel_w + a.mel_off[lane];
-    const float* p = P + a.mel_first[lane];
-    const uint32_t n = a.mel_count[lane];
+    const float* w = f.w + f.off[lane];
+    const float* p = P + f.first[lane];
+    const uint32_t n = f.count[lane];
     float e = 0.0f;
     for (uint32_t j = 0; j < n; j++) e += w[j] * p[j];
     L[lane] = logf(fmaxf(e, a.energy_floor));
@@ -118,13 +137,90 @@ __global__ __launch_bounds__(256) void mfcc_kernel(MfccArgs a, uint32_t y_floats
   }
   float* mine = lds + y_floats + (size_t)wave * (4 * M + 64);
   float2* A = reinterpret_cast<float2*>(mine);
+  // the utterance's filters: its warp's, read once for the workgroup, or the unwarped ones
+  MelFilters f{a.mel_first, a.mel_count, a.mel_off, a.mel_w};
+  if (a.utt_warp) {
+    const uint32_t w0 = a.utt_warp[sp.x] * a.n_mel;
+    f = MelFilters{a.warp_first + w0, a.warp_count + w0, a.warp_off + w0, a.warp_w};
+  }
   __syncthreads();
   const uint32_t rounds = (a.span_frames + n_waves - 1) / n_waves;
   for (uint32_t r = 0; r < rounds; r++) {
     const uint32_t fi = r * n_waves + wave;
     const bool active = fi < nf;
-    mfcc_frame(a, y + (active ? fi : 0) * a.shift, A, A + M, mine + 4 * M, lane, active, a.out + (f0 + t0 + (active ? fi : 0)) * a.n_cepstra);
+    const float* P = mfcc_power(a, y + (active ? fi : 0) * a.shift, A, A + M, lane);
+    mfcc_cepstra(a, f, P, mine + 4 * M, lane, active, a.out + (f0 + t0 + (active ? fi : 0)) * a.n_cepstra);
   }
+}
+
+// The warp search's MFCC stage (kernels.h): mfcc_kernel's spans, but a frame's P is computed once and every warp's filters are applied
+// to it from the LDS.  The (warp, filter) pairs are dealt to the wave's lanes, pair q = warp n_mel + filter to lane q mod 64 -- 13 warps
+// of 24 filters are five rounds of 64, not 13 of 24 -- and so are the (warp, cepstrum) pairs.  A pair sums its bins (its filters)
+// ascending exactly as mfcc_cepstra's lane does, so warp w's cepstra carry the bits mfcc_kernel gives with warp w's filters.
+// mine: A, B, then L[n_warps][n_mel].  out [n_warps][n_frames][n_cepstra].
+__global__ __launch_bounds__(256) void mfcc_warps_kernel(MfccArgs a, uint32_t y_floats, uint32_t pair_floats) {
+  extern __shared__ float lds[];
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
+  const uint32_t M = a.n_fft >> 1;
+  const uint2 sp = a.spans[blockIdx.x];
+  const uint64_t f0 = a.frame_off[sp.x];
+  const uint32_t T = (uint32_t)(a.frame_off[sp.x + 1] - f0), t0 = sp.y;
+  const uint32_t nf = min(a.span_frames, T - t0);
+  const uint32_t n_samp = (nf - 1) * a.shift + a.window;
+  const uint64_t first = (uint64_t)t0 * a.shift;
+  const int16_t* x = a.samples + a.sample_off[sp.x] + first;
+  float* y = lds;
+  for (uint32_t i = threadIdx.x; i < n_samp; i += blockDim.x) {
+    const float prev = first + i ? (float)x[(int64_t)i - 1] : 0.0f;
+    y[i] = (float)x[i] - a.preemphasis * prev;
+  }
+  float* mine = lds + y_floats + (size_t)wave * (4 * M + pair_floats);
+  float2* A = reinterpret_cast<float2*>(mine);
+  float* L = mine + 4 * M;
+  const uint32_t n_pairs = a.n_warps * a.n_mel, n_outs = a.n_warps * a.n_cepstra;
+  __syncthreads();
+  const uint32_t rounds = (a.span_frames + n_waves - 1) / n_waves;
+  for (uint32_t r = 0; r < rounds; r++) {
+    const uint32_t fi = r * n_waves + wave;
+    const bool active = fi < nf;
+    const float* P = mfcc_power(a, y + (active ? fi : 0) * a.shift, A, A + M, lane);
+    for (uint32_t q = lane; q < n_pairs; q += 64) {
+      const float* w = a.warp_w + a.warp_off[q];
+      const float* p = P + a.warp_first[q];
+      const uint32_t n = a.warp_count[q];
+      float e = 0.0f;
+      for (uint32_t j = 0; j < n; j++) e += w[j] * p[j];
+      L[q] = logf(fmaxf(e, a.energy_floor));
+    }
+    __syncthreads();
+    if (active) {
+      float* out = a.out + (f0 + t0 + fi) * a.n_cepstra;
+      for (uint32_t q = lane; q < n_outs; q += 64) {
+        const uint32_t wq = q / a.n_cepstra, i = q - wq * a.n_cepstra;
+        const float* d = a.dct + i * a.n_mel;
+        const float* Lw = L + wq * a.n_mel;
+        float c = 0.0f;
+        for (uint32_t m = 0; m < a.n_mel; m++) c += d[m] * Lw[m];
+        out[(uint64_t)wq * a.n_frames * a.n_cepstra + i] = c;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// the sums of sr_vtln_costs_corpus (kernels.h: VtlnReduceArgs): a thread per (row, warp), neighbouring threads neighbouring rows
+__global__ __launch_bounds__(256) void vtln_reduce_kernel(VtlnReduceArgs a) {
+  const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (uint64_t)a.n_rows * a.n_warps) return;
+  const uint32_t w = (uint32_t)(e / a.n_rows), r = (uint32_t)(e - (uint64_t)w * a.n_rows);
+  const double* s = a.src + w * a.src_stride;
+  const uint64_t j0 = a.off[r], j1 = a.off[r + 1];
+  double sum = 0.0;
+  if (j1 > j0) {
+    sum = s[a.items ? a.items[j0] : j0];  // the first addend as it is
+    for (uint64_t j = j0 + 1; j < j1; j++) sum = sum + s[a.items ? a.items[j] : j];
+  }
+  a.out[r * a.out_row + w * a.out_warp] = sum;
 }
 
 // the utterance of frame f: the last u with frame_off[u] <= f (an empty utterance is never it)
@@ -223,6 +319,7 @@ __global__ __launch_bounds__(256) void stream_frontend_kernel(StreamFrontendArgs
   float* y = lds;
   float* mine = lds + y_floats + (size_t)wave * (4 * M + 64);
   float2* A = reinterpret_cast<float2*>(mine);
+  const MelFilters filters{a.mel_first, a.mel_count, a.mel_off, a.mel_w};  // a stream has no warp: the unwarped filters
   for (uint32_t j0 = 0; j0 < j.k; j0 += a.span_frames) {
     const uint32_t n = min(a.span_frames, j.k - j0);
     const uint32_t n_samp = (n - 1) * a.shift + a.window;
@@ -232,7 +329,8 @@ __global__ __launch_bounds__(256) void stream_frontend_kernel(StreamFrontendArgs
     for (uint32_t r = 0; r * n_waves < n; r++) {
       const uint32_t fi = r * n_waves + wave;
       const bool active = fi < n;
-      mfcc_frame(a, y + (active ? fi : 0) * a.shift, A, A + M, mine + 4 * M, lane, active, stage + (size_t)(H + j0 + (active ? fi : 0)) * nf);
+      const float* P = mfcc_power(a, y + (active ? fi : 0) * a.shift, A, A + M, lane);
+      mfcc_cepstra(a, filters, P, mine + 4 * M, lane, active, stage + (size_t)(H + j0 + (active ? fi : 0)) * nf);
     }
   }
   __syncthreads();
@@ -268,6 +366,24 @@ hipError_t launch_mfcc(const MfccArgs& a, hipStream_t stream) {
   const uint32_t y_floats = ((a.span_frames - 1) * a.shift + a.window + 3) & ~3u;
   const size_t lds_bytes = sizeof(float) * ((size_t)y_floats + (size_t)waves * (4 * M + 64));
   hipLaunchKernelGGL(mfcc_kernel, dim3(a.n_spans), dim3(64 * waves), lds_bytes, stream, a, y_floats);
+  return hipGetLastError();
+}
+
+hipError_t launch_mfcc_warps(const MfccArgs& a, hipStream_t stream) {
+  if (a.n_spans == 0 || a.n_warps == 0) return hipSuccess;
+  const uint32_t y_floats = ((a.span_frames - 1) * a.shift + a.window + 3) & ~3u;
+  const uint32_t pair_floats = mfcc_warps_pair_floats(a.n_warps, a.n_mel);
+  const uint32_t waves = mfcc_warps_waves(y_floats, a.n_fft, pair_floats);
+  const size_t lds_bytes = mfcc_warps_lds_bytes(y_floats, a.n_fft, pair_floats, waves);
+  if (lds_bytes > 65536) return hipErrorInvalidValue;  // (sr_frontend_create_warped's limits keep a single wave within it)
+  hipLaunchKernelGGL(mfcc_warps_kernel, dim3(a.n_spans), dim3(64 * waves), lds_bytes, stream, a, y_floats, pair_floats);
+  return hipGetLastError();
+}
+
+hipError_t launch_vtln_reduce(const VtlnReduceArgs& a, hipStream_t stream) {
+  const uint64_t n = (uint64_t)a.n_rows * a.n_warps;
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(vtln_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
   return hipGetLastError();
 }
 

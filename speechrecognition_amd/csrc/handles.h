@@ -17,6 +17,7 @@
 #include "host_util.h"
 #include "kernels.h"
 #include "stream_audio_plan.h"
+#include "vtln_tables.h"
 
 namespace srhost {
 // stores a printf-style message for sr_last_error() (thread-local) and returns `code`
@@ -161,6 +162,9 @@ struct sr_model {
   size_t fb_budget = (size_t)1 << 30;      // most bytes for the forward-backward trellises of one launch (SRGPU_FB_MB)
   size_t mllt_budget = (size_t)256 << 20;  // most bytes for the segment partials of one round of the MLLT statistics (SRGPU_MLLT_MB)
   size_t lda_budget = (size_t)256 << 20;   // likewise for the segment partials of the LDA scatter (SRGPU_LDA_MB)
+  size_t vtln_budget = 0;                  // most bytes for the cepstra, rows, states and scores of one chunk of warps of the warp search: a
+                                           // quarter of the score workspace (SRGPU_VTLN_KB; a chunk takes at least one warp)
+  bool vtln_timing = false;                // SRGPU_VTLN_TIMING: sr_vtln_costs_corpus prints its chunk count and its stages' HIP-event times to stderr
   // profiling
   bool profiling = false;
   std::vector<EventPair> events;
@@ -283,6 +287,10 @@ struct sr_frontend {
   DevBuf<float2> twiddle;
   DevBuf<uint32_t> mel_first, mel_count, mel_off;
   DevBuf<double> mean, stddev;
+  // a warped front end (sr_frontend_create_warped): the warps' filters, one CSR over (warp, filter); the tables above stay the unwarped ones
+  uint32_t n_warps = 0;             // 0: not warped
+  DevBuf<float> warp_w;
+  DevBuf<uint32_t> warp_first, warp_count, warp_off;
 };
 
 struct sr_bigram {

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "bigram_route.h"
+#include "vtln_tables.h"
 
 namespace srgpu {
 
@@ -989,11 +990,32 @@ struct MfccArgs {
   const uint32_t* mel_first; const uint32_t* mel_count; const uint32_t* mel_off;  // [n_mel] a filter's bins and where its weights begin
   const float* mel_w;                                  // the filters' weights, filter by filter, bins ascending
   const float* dct;                                    // [n_cepstra][n_mel], sqrt(2 / n_mel) folded in
-  float* out;                                          // [frames][n_cepstra]
+  float* out;                                          // [frames][n_cepstra]; mfcc_warps_kernel: [n_warps][frames][n_cepstra]
+  // a warped front end's filters (sr_frontend_create_warped): one CSR over (warp, filter), warp by warp; warp_off indexes warp_w
+  const uint32_t* warp_first; const uint32_t* warp_count; const uint32_t* warp_off;  // [n_warps][n_mel]
+  const float* warp_w;
+  uint32_t n_warps;                                    // mfcc_warps_kernel: the warps it applies, from the first of the CSR given
+  uint64_t n_frames;                                   // mfcc_warps_kernel: the corpus's frames, the stride between two warps' cepstra
+  const uint32_t* utt_warp;                            // mfcc_kernel, device [n_utts]: the utterance's warp; NULL: the unwarped filters above
 };
-constexpr uint32_t mfcc_span_cap() { return 4096; }    // pre-emphasised samples a workgroup keeps in the LDS
-constexpr uint32_t mfcc_waves(uint32_t n_fft) { return n_fft <= 1024 ? 4 : 2; }  // waves per workgroup: at most 48 KiB of LDS
+// (mfcc_span_cap(), mfcc_waves() and the warp search's LDS rule -- mfcc_warps_pair_floats(), mfcc_warps_lds_bytes(),
+// mfcc_warps_waves() -- are in vtln_tables.h, host-only, so that tests/cpp/vtln_tables_driver.cpp checks the functions the launch uses)
 hipError_t launch_mfcc(const MfccArgs& a, hipStream_t stream);
+// The warp search's MFCC stage: mfcc_kernel's spans and workgroups, but a frame's power spectrum is computed once and all n_warps
+// filterbanks are applied to it.  A wave keeps, beside its two transform buffers, the n_warps x n_mel logarithms.
+hipError_t launch_mfcc_warps(const MfccArgs& a, hipStream_t stream);
+// The warp search's sums (sr_vtln_costs_corpus), in their defined order and without atomics: vtln_reduce_kernel, a thread per (row,
+// warp), adds src[warp src_stride + j] for the row's j in ascending position -- j = off[row] .. off[row + 1] - 1 itself (items NULL) or
+// items[that position] -- taking the first addend as is; an empty sum is +0.  -> out[row out_row + warp out_warp].
+//   utterances  rows = utterances, off = the frame offsets, src = path scores [n_warps][frames]      -> [n_warps][n_utts]
+//   speakers    rows = speakers, items = a speaker's utterances ascending, src = the utterances' sums -> [n_speakers][n_warps]
+struct VtlnReduceArgs {
+  const double* src; uint64_t src_stride;
+  const uint64_t* off; const uint32_t* items;
+  uint32_t n_rows, n_warps;
+  double* out; uint64_t out_row, out_warp;
+};
+hipError_t launch_vtln_reduce(const VtlnReduceArgs& a, hipStream_t stream);
 // FeaturePostProcessor::process_features on every utterance: static | delta | delta-delta, mean / deviation (NULL: none), then the
 // energy maximum of component 0.  cepstra [frames][n_static] -> out [frames][n_static + n_first + n_second]
 struct FeaturePostArgs {

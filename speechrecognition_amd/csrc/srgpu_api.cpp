@@ -1093,6 +1093,9 @@ int model_shell(int device, uint32_t dim, uint32_t n_states, const uint32_t* den
   if (const char* e = getenv("SRGPU_FB_MB")) m->fb_budget = std::max<size_t>(1, (size_t)strtoull(e, nullptr, 10)) << 20;
   if (const char* e = getenv("SRGPU_MLLT_MB")) m->mllt_budget = std::max<size_t>(1, (size_t)strtoull(e, nullptr, 10)) << 20;
   if (const char* e = getenv("SRGPU_LDA_MB")) m->lda_budget = std::max<size_t>(1, (size_t)strtoull(e, nullptr, 10)) << 20;
+  m->vtln_budget = chunk_bytes / 4;
+  if (const char* e = getenv("SRGPU_VTLN_KB")) m->vtln_budget = (size_t)strtoull(e, nullptr, 10) << 10;  // (tests: several chunks of warps)
+  m->vtln_timing = getenv("SRGPU_VTLN_TIMING") != nullptr;  // (tools/vtln_time.py, and the tests' count of chunks)
   if (const char* e = getenv("SRGPU_DEFER_CAP")) m->defer_cap_limit = std::max(1u, (uint32_t)strtoul(e, nullptr, 10));  // (tests: full segments)
   *out = own.release();
   return SR_OK;
