@@ -1375,6 +1375,30 @@ SR_API int sr_net_accuracies_corpus_scores(sr_model* m, sr_corpus* c, sr_lexicon
                                            uint64_t n_scores, double* out_cost, double* out_acc, uint16_t* out_count, uint16_t* out_state,
                                            double* out_weight);
 
+/* Test hooks: the forward-backward passes over the bigram search network alone on a score table the caller supplies:
+ * sr_bigram_word_posteriors_corpus', sr_bigram_occupancies_corpus' (the free network, or the transcripts' chains with trans /
+ * trans_off) and sr_bigram_accuracies_corpus' pass -- the same checks, chunks, launch groups (SRGPU_FB_MB), utterance order, table
+ * cache, workspace, kernels, item path and outputs -- except that a chunk's score step copies rows [f0, f1) of `scores` into the chunk's
+ * table (row stride: n_states rounded up to 8, the padding columns +inf); there is no gmm_kernel argument.  scores: host,
+ * [total_frames x n_states] row-major; n_scores == total_frames * n_states or SR_EINVAL.  The corpus's features are never read.
+ * Entries: any finite value and +inf are valid.  A NaN entry counts as +inf: every path that pays that emission is dead.  A -inf
+ * entry is refused with SR_EINVAL before any launch: the word entry is a sum in the linear domain relative to the frame's best
+ * history, which has no meaning at -inf (the LM's -inf is refused for the same reason).  An utterance whose F_u is +inf (no path)
+ * returns no items, and for the accuracies Abar_u = 0; no weight returned is NaN; the other utterances of the call are unaffected.
+ * The linear-domain rule holds here as in production: a word all of whose entry terms underflow against the frame's best history is
+ * not entered at that frame. */
+SR_API int sr_bigram_word_posteriors_corpus_scores(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, double posterior_floor,
+                                                   uint32_t max_items, const double* scores, uint64_t n_scores, double* out_cost,
+                                                   uint16_t* out_count, uint32_t* out_word, double* out_weight);
+SR_API int sr_bigram_occupancies_corpus_scores(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, double posterior_floor,
+                                               uint32_t max_items, const uint32_t* trans, const uint64_t* trans_off,
+                                               const double* scores, uint64_t n_scores, double* out_cost, uint16_t* out_count,
+                                               uint16_t* out_state, double* out_weight);
+SR_API int sr_bigram_accuracies_corpus_scores(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, double posterior_floor,
+                                              uint32_t max_items, const uint16_t* ref_states, const double* scores, uint64_t n_scores,
+                                              double* out_cost, double* out_acc, uint16_t* out_count, uint16_t* out_state,
+                                              double* out_weight);
+
 /* ---- measurement --------------------------------------------------------------------------------
  * When enabled, every kernel launch of this model handle is bracketed by HIP events on the
  * launch stream; sr_profile_read() synchronises and returns accumulated device times. */

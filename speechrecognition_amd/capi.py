@@ -60,6 +60,7 @@ SYMBOLS = [
     "sr_gather_words", "sr_recognize_corpus_scores", "sr_recognize_bigram_corpus_scores", "sr_bigram_route",
     "sr_align_corpus_scores", "sr_state_posteriors_corpus_scores",
     "sr_word_posteriors_corpus_scores", "sr_net_occupancies_corpus_scores", "sr_net_accuracies_corpus_scores",
+    "sr_bigram_word_posteriors_corpus_scores", "sr_bigram_occupancies_corpus_scores", "sr_bigram_accuracies_corpus_scores",
     "sr_profile_enable", "sr_profile_reset", "sr_profile_read",
 ]
 
@@ -254,6 +255,9 @@ def lib():
         L.sr_word_posteriors_corpus_scores.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, u64, vp, vp, vp, vp]
         L.sr_net_occupancies_corpus_scores.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, vp, u64, vp, vp, vp, vp]
         L.sr_net_accuracies_corpus_scores.argtypes = [vp, vp, vp, C.POINTER(SearchParams), dbl, dbl, u32, vp, vp, u64, vp, vp, vp, vp, vp]
+        L.sr_bigram_word_posteriors_corpus_scores.argtypes = [vp, vp, vp, dbl, dbl, u32, vp, u64, vp, vp, vp, vp]
+        L.sr_bigram_occupancies_corpus_scores.argtypes = [vp, vp, vp, dbl, dbl, u32, vp, vp, vp, u64, vp, vp, vp, vp]
+        L.sr_bigram_accuracies_corpus_scores.argtypes = [vp, vp, vp, dbl, dbl, u32, vp, vp, u64, vp, vp, vp, vp, vp]
         L.sr_profile_enable.argtypes = [vp, i32]
         L.sr_profile_reset.argtypes = [vp]
         L.sr_profile_read.argtypes = [vp, C.POINTER(Profile)]
@@ -1240,14 +1244,27 @@ class Corpus:
     def bigram_word_posteriors(self, bigram, scale=1.0, kernel=GMM_PREFILTER, floor=0.0, max_items=8):
         """Forward-backward over the bigram search network (sr_bigram_word_posteriors_corpus) -> (cost, count, word, weight) as
         word_posteriors; the silence word's posterior includes its copies."""
+        return self._bigram_word_posteriors(bigram, scale, kernel, floor, max_items, None)
+
+    def bigram_word_posteriors_scores(self, bigram, scores, scale=1.0, floor=0.0, max_items=8):
+        """sr_bigram_word_posteriors_corpus_scores (test hook): bigram_word_posteriors() on the caller's score table [n_frames,
+        n_states] (the corpus's features are not read)"""
+        return self._bigram_word_posteriors(bigram, scale, GMM_PREFILTER, floor, max_items, np.ascontiguousarray(scores, dtype=np.float64))
+
+    def _bigram_word_posteriors(self, bigram, scale, kernel, floor, max_items, scores):
         F = max(self.n_frames, 1)
         K = max(int(max_items), 1)
         cost = np.zeros(max(self.n_utts, 1), dtype=np.float64)
         count = np.zeros(F, dtype=np.uint16)
         word = np.zeros((F, K), dtype=np.uint32)
         weight = np.zeros((F, K), dtype=np.float64)
-        _check(lib().sr_bigram_word_posteriors_corpus(self.model.h, self.h, bigram.h, kernel, float(scale), float(floor), int(max_items),
-                                                      _ptr(cost), _ptr(count), _ptr(word), _ptr(weight)))
+        if scores is None:
+            _check(lib().sr_bigram_word_posteriors_corpus(self.model.h, self.h, bigram.h, kernel, float(scale), float(floor), int(max_items),
+                                                          _ptr(cost), _ptr(count), _ptr(word), _ptr(weight)))
+        else:
+            _check(lib().sr_bigram_word_posteriors_corpus_scores(self.model.h, self.h, bigram.h, float(scale), float(floor), int(max_items),
+                                                                 _ptr(scores), scores.size, _ptr(cost), _ptr(count), _ptr(word),
+                                                                 _ptr(weight)))
         n = self.n_frames
         return cost[: self.n_utts], count[:n], word[:n], weight[:n]
 
@@ -1255,6 +1272,14 @@ class Corpus:
         """Mixture occupancies over the bigram search network (sr_bigram_occupancies_corpus): the free network, or -- transcripts =
         one sequence of word ids per utterance, silence not listed -- the network restricted to them -> (cost, count, state,
         weight) as net_occupancies."""
+        return self._bigram_occupancies(bigram, scale, transcripts, kernel, floor, max_items, None)
+
+    def bigram_occupancies_scores(self, bigram, scores, scale=1.0, transcripts=None, floor=0.0, max_items=8):
+        """sr_bigram_occupancies_corpus_scores (test hook): bigram_occupancies() on the caller's score table [n_frames, n_states]"""
+        return self._bigram_occupancies(bigram, scale, transcripts, GMM_PREFILTER, floor, max_items,
+                                        np.ascontiguousarray(scores, dtype=np.float64))
+
+    def _bigram_occupancies(self, bigram, scale, transcripts, kernel, floor, max_items, scores):
         F = max(self.n_frames, 1)
         K = max(int(max_items), 1)
         cost = np.zeros(max(self.n_utts, 1), dtype=np.float64)
@@ -1262,8 +1287,13 @@ class Corpus:
         state = np.zeros((F, K), dtype=np.uint16)
         weight = np.zeros((F, K), dtype=np.float64)
         flat, off = self._transcripts(transcripts)
-        _check(lib().sr_bigram_occupancies_corpus(self.model.h, self.h, bigram.h, kernel, float(scale), float(floor), int(max_items),
-                                                  _ptr(flat), _ptr(off), _ptr(cost), _ptr(count), _ptr(state), _ptr(weight)))
+        if scores is None:
+            _check(lib().sr_bigram_occupancies_corpus(self.model.h, self.h, bigram.h, kernel, float(scale), float(floor), int(max_items),
+                                                      _ptr(flat), _ptr(off), _ptr(cost), _ptr(count), _ptr(state), _ptr(weight)))
+        else:
+            _check(lib().sr_bigram_occupancies_corpus_scores(self.model.h, self.h, bigram.h, float(scale), float(floor), int(max_items),
+                                                             _ptr(flat), _ptr(off), _ptr(scores), scores.size, _ptr(cost), _ptr(count),
+                                                             _ptr(state), _ptr(weight)))
         n = self.n_frames
         return cost[: self.n_utts], count[:n], state[:n], weight[:n]
 
@@ -1284,6 +1314,14 @@ class Corpus:
         """Expected frame accuracy over the free bigram search network (sr_bigram_accuracies_corpus); ref_states u16[total_frames] =
         the reference mixture of every frame -> (cost, acc, count, state, weight) as net_accuracies: per frame the signed gamma,
         largest |gamma| first."""
+        return self._bigram_accuracies(bigram, ref_states, scale, kernel, floor, max_items, None)
+
+    def bigram_accuracies_scores(self, bigram, ref_states, scores, scale=1.0, floor=0.0, max_items=8):
+        """sr_bigram_accuracies_corpus_scores (test hook): bigram_accuracies() on the caller's score table [n_frames, n_states]"""
+        return self._bigram_accuracies(bigram, ref_states, scale, GMM_PREFILTER, floor, max_items,
+                                       np.ascontiguousarray(scores, dtype=np.float64))
+
+    def _bigram_accuracies(self, bigram, ref_states, scale, kernel, floor, max_items, scores):
         F = max(self.n_frames, 1)
         K = max(int(max_items), 1)
         cost, acc = (np.zeros(max(self.n_utts, 1), dtype=np.float64) for _ in range(2))
@@ -1291,8 +1329,13 @@ class Corpus:
         state = np.zeros((F, K), dtype=np.uint16)
         weight = np.zeros((F, K), dtype=np.float64)
         ref = np.ascontiguousarray(np.concatenate([np.asarray(ref_states, dtype=np.uint16), np.zeros(1, np.uint16)]))
-        _check(lib().sr_bigram_accuracies_corpus(self.model.h, self.h, bigram.h, kernel, float(scale), float(floor), int(max_items),
-                                                 _ptr(ref), _ptr(cost), _ptr(acc), _ptr(count), _ptr(state), _ptr(weight)))
+        if scores is None:
+            _check(lib().sr_bigram_accuracies_corpus(self.model.h, self.h, bigram.h, kernel, float(scale), float(floor), int(max_items),
+                                                     _ptr(ref), _ptr(cost), _ptr(acc), _ptr(count), _ptr(state), _ptr(weight)))
+        else:
+            _check(lib().sr_bigram_accuracies_corpus_scores(self.model.h, self.h, bigram.h, float(scale), float(floor), int(max_items),
+                                                            _ptr(ref), _ptr(scores), scores.size, _ptr(cost), _ptr(acc), _ptr(count),
+                                                            _ptr(state), _ptr(weight)))
         n = self.n_frames
         return cost[: self.n_utts], acc[: self.n_utts], count[:n], state[:n], weight[:n]
 

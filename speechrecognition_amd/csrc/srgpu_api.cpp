@@ -2126,6 +2126,14 @@ struct ScoreTable {
     for (uint64_t t = 0; t < F; t++) memcpy(padded.data() + t * ld, scores + t * S, sizeof(double) * S);
     return SR_OK;
   }
+  // the bigram-network hooks: their word entry is a product in the linear domain, where a cost of -inf (exp(+inf)) has no meaning
+  int refuse_neg_inf(const double* scores, uint64_t n_scores) const {
+    for (uint64_t i = 0; i < n_scores; i++)
+      if (scores[i] == -std::numeric_limits<double>::infinity())
+        return fail(SR_EINVAL, "score %llu (frame %llu, state %llu) is -inf", (unsigned long long)i, (unsigned long long)(i / m->n_states),
+                    (unsigned long long)(i % m->n_states));
+    return SR_OK;
+  }
   int operator()(const AutomatonScoring&, const Chunk& ch, double* table) const { return (*this)(ch, table); }
   int operator()(const Chunk& ch, double* table) const {  // (the network passes' score step: run_chunks' own signature)
     if (ch.f1 > ch.f0)
@@ -3798,11 +3806,12 @@ static int bgfb_top(const BgFbArgs& a, uint64_t n, uint32_t max_items, double fl
   return SR_OK;
 }
 
-int sr_bigram_word_posteriors_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, double scale, double posterior_floor,
-                                     uint32_t max_items, double* out_cost, uint16_t* out_count, uint32_t* out_word, double* out_weight) {
-  return guarded(__func__, [&]() -> int {
-  int rc = bgfb_check(m, c, b, scale, posterior_floor);
-  if (rc) return rc;
+// sr_bigram_word_posteriors_corpus and its test hook: the pass on `score`'s scores once bgfb_check has passed, F_u and the top words
+// to the host
+template <class Score>
+static int bigram_word_posteriors(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, double posterior_floor, uint32_t max_items,
+                                  Score score, double* out_cost, uint16_t* out_count, uint32_t* out_word, double* out_weight) {
+  int rc;
   if (!out_cost) return fail(SR_EINVAL, "null argument");
   bool post = false;
   if ((rc = top_items_arguments(out_count, out_word, out_weight, "out_word", max_items, &post))) return rc;
@@ -3812,7 +3821,7 @@ int sr_bigram_word_posteriors_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, in
   BgFbPass fp;
   if ((rc = fp.setup(m, c, b, scale, chunks))) return rc;
   if (post && (rc = ensure_top_items(F, max_items, c->nf_count, c->nf_word, c->nf_weight))) return rc;
-  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, gmm_kernel, table); },
+  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) -> int { return score(ch, table); },
       [&](const Chunk& ch, const double* table, hipStream_t s) -> int {
         return fp.run(c, ch, table, s, [&](const BgFbArgs& a, uint64_t n) -> int {
           return post ? bgfb_top(a, n, max_items, posterior_floor, c, s) : SR_OK;
@@ -3823,6 +3832,29 @@ int sr_bigram_word_posteriors_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, in
   if ((rc = netfb_costs(c, scale, out_cost))) return rc;
   if (!post || F == 0) return SR_OK;
   return copy_top_items(F, max_items, c->nf_count, c->nf_word, c->nf_weight, out_count, out_word, out_weight);
+}
+
+int sr_bigram_word_posteriors_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, double scale, double posterior_floor,
+                                     uint32_t max_items, double* out_cost, uint16_t* out_count, uint32_t* out_word, double* out_weight) {
+  return guarded(__func__, [&]() -> int {
+  int rc = bgfb_check(m, c, b, scale, posterior_floor);
+  if (rc) return rc;
+  return bigram_word_posteriors(m, c, b, scale, posterior_floor, max_items, gmm_scores(m, c, gmm_kernel), out_cost, out_count, out_word,
+                                out_weight);
+  });
+}
+
+// test hook: sr_bigram_word_posteriors_corpus with the chunk's score step replaced by a copy of the caller's rows
+int sr_bigram_word_posteriors_corpus_scores(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, double posterior_floor,
+                                            uint32_t max_items, const double* scores, uint64_t n_scores, double* out_cost,
+                                            uint16_t* out_count, uint32_t* out_word, double* out_weight) {
+  return guarded(__func__, [&]() -> int {
+  int rc = bgfb_check(m, c, b, scale, posterior_floor);
+  if (rc) return rc;
+  ScoreTable table;
+  if ((rc = table.set(m, c, scores, n_scores)) || (rc = table.refuse_neg_inf(scores, n_scores))) return rc;
+  return table.done(bigram_word_posteriors(m, c, b, scale, posterior_floor, max_items, std::cref(table), out_cost, out_count, out_word,
+                                           out_weight));
   });
 }
 
@@ -4372,8 +4404,9 @@ static constexpr uint32_t kBgItemsSerial = 16;
 // and table cache) or the transcripts' chains (consecutive utterances whose trellises fit m->fb_budget together).  Leaves kappa F_u in
 // c->out_cost and, with want_items, *n_items items in c->fb_item_* (frame order, ascending mixture id) with c->fb_item_off[F + 1];
 // utterances whose gate (device, optional) is +inf give no items.
-static int bgocc_pass(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, double scale, double posterior_floor, const uint32_t* trans,
-                      const uint64_t* trans_off, bool want_items, const double* gate, uint64_t* n_items) {
+template <class Score>
+static int bgocc_pass(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, double posterior_floor, const uint32_t* trans,
+                      const uint64_t* trans_off, bool want_items, const double* gate, uint64_t* n_items, Score score) {
   const uint32_t U = c->n_utts;
   const uint64_t F = c->n_frames, P = b->net.n_positions;
   const bool chain = trans_off != nullptr;
@@ -4421,7 +4454,7 @@ static int bgocc_pass(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, d
     return SR_OK;
   };
   size_t ci = 0;  // run_chunks searches the chunks in order
-  rc = run_chunks(m, chunks, [&](const Chunk& k, double* table) { return score_chunk(m, c, k.f0, k.f1, gmm_kernel, table); },
+  rc = run_chunks(m, chunks, [&](const Chunk& k, double* table) -> int { return score(k, table); },
       [&](const Chunk& k, const double* table, hipStream_t s) -> int {
         if (want_items && ci == 0) HIP_TRY(reset_item_count(c->fb_base, s));
         if (!chain) {
@@ -4454,20 +4487,53 @@ static int bgocc_pass(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, d
   return SR_OK;
 }
 
+// bgocc_check as sr_bigram_occupancies_corpus and its test hook call it
+static int bigram_occupancies_check(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, double posterior_floor, const uint32_t* trans,
+                                    const uint64_t* trans_off, const uint16_t* out_count, const uint16_t* out_state,
+                                    const double* out_weight, bool* constrained) {
+  return bgocc_check(m, c, b, scale, posterior_floor, trans, trans_off, !trans_off && (out_count || out_state || out_weight), constrained);
+}
+
+// sr_bigram_occupancies_corpus and its test hook: the pass on `score`'s scores once the check has passed, F_u and the top items to the
+// host
+template <class Score>
+static int bigram_occupancies(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, double posterior_floor, uint32_t max_items,
+                              const uint32_t* trans, const uint64_t* trans_off, bool constrained, Score score, double* out_cost,
+                              uint16_t* out_count, uint16_t* out_state, double* out_weight) {
+  int rc;
+  if (!out_cost) return fail(SR_EINVAL, "null argument");
+  bool post = false;
+  if ((rc = top_items_arguments(out_count, out_state, out_weight, "out_state", max_items, &post))) return rc;
+  uint64_t n_items = 0;
+  if ((rc = bgocc_pass(m, c, b, scale, posterior_floor, trans, constrained ? trans_off : nullptr, post, nullptr, &n_items, score))) return rc;
+  if ((rc = netfb_costs(c, scale, out_cost))) return rc;
+  return post ? top_of_items(m, c, max_items, out_count, out_state, out_weight) : SR_OK;
+}
+
 int sr_bigram_occupancies_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm_kernel, double scale, double posterior_floor,
                                  uint32_t max_items, const uint32_t* trans, const uint64_t* trans_off, double* out_cost,
                                  uint16_t* out_count, uint16_t* out_state, double* out_weight) {
   return guarded(__func__, [&]() -> int {
   bool constrained = false;
-  int rc = bgocc_check(m, c, b, scale, posterior_floor, trans, trans_off, !trans_off && (out_count || out_state || out_weight), &constrained);
+  int rc = bigram_occupancies_check(m, c, b, scale, posterior_floor, trans, trans_off, out_count, out_state, out_weight, &constrained);
   if (rc) return rc;
-  if (!out_cost) return fail(SR_EINVAL, "null argument");
-  bool post = false;
-  if ((rc = top_items_arguments(out_count, out_state, out_weight, "out_state", max_items, &post))) return rc;
-  uint64_t n_items = 0;
-  if ((rc = bgocc_pass(m, c, b, gmm_kernel, scale, posterior_floor, trans, constrained ? trans_off : nullptr, post, nullptr, &n_items))) return rc;
-  if ((rc = netfb_costs(c, scale, out_cost))) return rc;
-  return post ? top_of_items(m, c, max_items, out_count, out_state, out_weight) : SR_OK;
+  return bigram_occupancies(m, c, b, scale, posterior_floor, max_items, trans, trans_off, constrained, gmm_scores(m, c, gmm_kernel), out_cost,
+                            out_count, out_state, out_weight);
+  });
+}
+
+// test hook: sr_bigram_occupancies_corpus with the chunk's score step replaced by a copy of the caller's rows
+int sr_bigram_occupancies_corpus_scores(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, double posterior_floor, uint32_t max_items,
+                                        const uint32_t* trans, const uint64_t* trans_off, const double* scores, uint64_t n_scores,
+                                        double* out_cost, uint16_t* out_count, uint16_t* out_state, double* out_weight) {
+  return guarded(__func__, [&]() -> int {
+  bool constrained = false;
+  int rc = bigram_occupancies_check(m, c, b, scale, posterior_floor, trans, trans_off, out_count, out_state, out_weight, &constrained);
+  if (rc) return rc;
+  ScoreTable table;
+  if ((rc = table.set(m, c, scores, n_scores)) || (rc = table.refuse_neg_inf(scores, n_scores))) return rc;
+  return table.done(bigram_occupancies(m, c, b, scale, posterior_floor, max_items, trans, trans_off, constrained, std::cref(table), out_cost,
+                                       out_count, out_state, out_weight));
   });
 }
 
@@ -4482,8 +4548,8 @@ int sr_bigram_mmi_statistics_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int
   if (!constrained) return fail(SR_EINVAL, "null argument (MMI statistics need the transcripts)");
   return mmi_statistics(m, c, scale, max_approx, out_num_cost, out_den_cost, num_mean_acc, num_mean_w, num_var_acc, num_var_w, den_mean_acc,
                         den_mean_w, den_var_acc, den_var_w, [&](bool numerator, const double* gate, uint64_t* n_items) {
-    return bgocc_pass(m, c, b, gmm_kernel, scale, posterior_floor, numerator ? trans : nullptr, numerator ? trans_off : nullptr, true, gate,
-                      n_items);
+    return bgocc_pass(m, c, b, scale, posterior_floor, numerator ? trans : nullptr, numerator ? trans_off : nullptr, true, gate, n_items,
+                      gmm_scores(m, c, gmm_kernel));
   });
   });
 }
@@ -4554,6 +4620,22 @@ int sr_bigram_accuracies_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int gmm
                                      [&](BgSmbrPass& sp, const std::vector<Chunk>& chunks, bool) {
     return sp.setup(m, c, b, scale, posterior_floor, ref_states, chunks);
   });
+  });
+}
+
+// test hook: sr_bigram_accuracies_corpus with the chunk's score step replaced by a copy of the caller's rows
+int sr_bigram_accuracies_corpus_scores(sr_model* m, sr_corpus* c, sr_bigram* b, double scale, double posterior_floor, uint32_t max_items,
+                                       const uint16_t* ref_states, const double* scores, uint64_t n_scores, double* out_cost,
+                                       double* out_acc, uint16_t* out_count, uint16_t* out_state, double* out_weight) {
+  return guarded(__func__, [&]() -> int {
+  int rc = bgsmbr_check(m, c, b, scale, posterior_floor, ref_states);
+  if (rc) return rc;
+  ScoreTable table;
+  if ((rc = table.set(m, c, scores, n_scores)) || (rc = table.refuse_neg_inf(scores, n_scores))) return rc;
+  return table.done(smbr_accuracies<BgSmbrPass>(m, c, std::cref(table), scale, max_items, out_cost, out_acc, out_count, out_state, out_weight,
+                                                [&](BgSmbrPass& sp, const std::vector<Chunk>& chunks, bool) {
+    return sp.setup(m, c, b, scale, posterior_floor, ref_states, chunks);
+  }));
   });
 }
 

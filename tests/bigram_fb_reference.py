@@ -15,7 +15,10 @@ The network is the one orc_bigram_decode (oracle/sr_oracle.c) searches, every pa
     plus tdp[isSilence][3].
 F = -(1/kappa) log sum over the word ends after frame T of exp(-kappa cost); T = 0: F = 0.  Nothing here multiplies probabilities
 in the linear domain: the entry is a log-sum-exp per word, the independent statement of what the device computes as a matrix
-product."""
+product.
+
+forward, backward and posteriors take a `dtype` (default float64, the kernels' own precision): with np.longdouble (x87: 64 bits of
+mantissa) the same recursion is the yardstick the float64 one, and the kernels, are measured against (tests/bigram_fb_cases.py)."""
 from __future__ import annotations
 
 import numpy as np
@@ -45,17 +48,23 @@ class Net:
         self.hist = np.where(np.arange(2 * W) < W, np.arange(2 * W), np.arange(2 * W) - W)  # (the silence word: itself)
 
 
+def _arr(x):
+    """x as an array: longdouble stays, everything else is float64"""
+    x = np.asarray(x)
+    return x if x.dtype == np.longdouble else x.astype(np.float64)
+
+
 def _lsum(x, axis=None, semiring="log"):
     """-log sum exp(-x) (or the minimum); +inf where nothing is finite"""
-    x = np.asarray(x, dtype=np.float64)
+    x = _arr(x)
     if axis is None:
         x, axis = x.reshape(-1), 0
     if x.shape[axis] == 0:
-        return np.full(np.delete(x.shape, axis), INF)[()]
+        return np.full(np.delete(x.shape, axis), INF, dtype=x.dtype)[()]
     m = x.min(axis=axis, keepdims=True)
     if semiring == "min":
         return np.squeeze(m, axis)[()]
-    ms = np.where(np.isfinite(m), m, 0.0)
+    ms = np.where(np.isfinite(m), m, x.dtype.type(0.0))
     with np.errstate(divide="ignore", over="ignore"):
         s = np.exp(ms - x).sum(axis=axis, keepdims=True)
         out = np.where(np.isfinite(m), ms - np.log(s), INF)
@@ -63,7 +72,7 @@ def _lsum(x, axis=None, semiring="log"):
 
 
 def _comb(xs, semiring):
-    return _lsum(np.stack([np.asarray(x, dtype=np.float64) for x in xs]), axis=0, semiring=semiring)
+    return _lsum(np.stack([_arr(x) for x in xs]), axis=0, semiring=semiring)
 
 
 def _shift(v, j):
@@ -77,15 +86,15 @@ def _shift(v, j):
     return out
 
 
-def _klm(net, lm, scale):
-    klm = scale * np.asarray(lm, dtype=np.float64)
-    klm = np.where(np.isnan(klm), INF, klm)
+def _klm(net, lm, scale, dtype=np.float64):
+    klm = dtype(scale) * np.asarray(lm, dtype=np.float64).astype(dtype)
+    klm = np.where(np.isnan(klm), dtype(INF), klm)
     klm[net.sil, :] = INF  # no transition into silence through the LM
     return klm
 
 
-def _tdp(tdp, scale):
-    return scale * np.asarray(tdp, dtype=np.float64).reshape(2, 4)
+def _tdp(tdp, scale, dtype=np.float64):
+    return dtype(scale) * np.asarray(tdp, dtype=np.float64).reshape(2, 4).astype(dtype)
 
 
 def histories(net, we, semiring="log"):
@@ -105,7 +114,7 @@ def _entry_sum(vec, klm, axis, semiring="log"):
 def entries(net, we, klm, semiring="log", entry_sum=None):
     """word-end costs [2W] after a frame -> entry costs [2W] of the next"""
     W = net.W
-    ent = np.full(2 * W, INF)
+    ent = np.full(2 * W, INF, dtype=we.dtype)
     hist = histories(net, we, semiring)
     ent[:W] = entry_sum(hist, klm, 1) if entry_sum else _entry_sum(hist, klm, 1, semiring)
     ent[W:] = we[:W]
@@ -114,23 +123,24 @@ def entries(net, we, klm, semiring="log", entry_sum=None):
     return ent
 
 
-def start_ends(net):
-    we = np.full(2 * net.W, INF)
+def start_ends(net, dtype=np.float64):
+    we = np.full(2 * net.W, INF, dtype=dtype)
     we[net.sil] = 0.0
     return we
 
 
-def forward(e, net, lm, tdp, semiring="log", scale=1.0, entry_sum=None):
+def forward(e, net, lm, tdp, semiring="log", scale=1.0, entry_sum=None, dtype=np.float64):
     """-> (alpha [T, P], WE [T + 1, 2W]): WE[t] = the word-end costs after frame t (row 0: the start), all times kappa.
     entry_sum(vec, klm, axis) replaces the log-space W x W sum (tests: a second, linear-domain evaluation to measure its spread)."""
-    E = np.asarray(e, dtype=np.float64)
+    E = np.asarray(e, dtype=np.float64).astype(dtype)
     T = E.shape[0]
-    klm, td = _klm(net, lm, scale), _tdp(tdp, scale)
+    klm, td = _klm(net, lm, scale, dtype), _tdp(tdp, scale, dtype)
+    scale = dtype(scale)
     pt = td[net.is_sil]  # [P, 4]
-    A = np.full((T, net.P), INF)
-    WE = np.full((T + 1, 2 * net.W), INF)
-    WE[0] = start_ends(net)
-    prev = np.full(net.P, INF)
+    A = np.full((T, net.P), INF, dtype=dtype)
+    WE = np.full((T + 1, 2 * net.W), INF, dtype=dtype)
+    WE[0] = start_ends(net, dtype)
+    prev = np.full(net.P, INF, dtype=dtype)
     for t in range(T):
         ent = entries(net, WE[t], klm, semiring, entry_sum)[net.slot]
         c0 = prev + pt[:, 0]
@@ -146,15 +156,16 @@ def forward(e, net, lm, tdp, semiring="log", scale=1.0, entry_sum=None):
     return A, WE
 
 
-def backward(e, net, lm, tdp, scale=1.0, semiring="log", entry_sum=None):
+def backward(e, net, lm, tdp, scale=1.0, semiring="log", entry_sum=None, dtype=np.float64):
     """beta [T, P]: the cost from after frame t at a position to a word end after frame T (scaled)."""
-    E = np.asarray(e, dtype=np.float64)
+    E = np.asarray(e, dtype=np.float64).astype(dtype)
     T = E.shape[0]
     W = net.W
-    klm, td = _klm(net, lm, scale), _tdp(tdp, scale)
+    klm, td = _klm(net, lm, scale, dtype), _tdp(tdp, scale, dtype)
+    scale = dtype(scale)
     pt = td[net.is_sil]
     is_last = net.k == net.n - 1
-    B = np.full((T, net.P), INF)
+    B = np.full((T, net.P), INF, dtype=dtype)
     if T == 0:
         return B
     B[T - 1] = np.where(is_last, pt[:, 3], INF)
@@ -165,7 +176,7 @@ def backward(e, net, lm, tdp, scale=1.0, semiring="log", entry_sum=None):
         b2 = np.where(two, td[net.slot_sil, 2] + x[np.minimum(net.first + 1, net.P - 1)], INF)
         bent = _comb([x[net.first], b2], semiring)
         Y = entry_sum(bent[:W], klm, 0) if entry_sum else _entry_sum(bent[:W], klm, 0, semiring)  # [h]
-        R = np.empty(2 * W)
+        R = np.empty(2 * W, dtype=dtype)
         R[:W] = _comb([Y, bent[W:]], semiring)
         R[net.sil] = _comb([Y[net.sil], bent[net.sil]], semiring)
         R[W:] = Y
@@ -178,21 +189,35 @@ def backward(e, net, lm, tdp, scale=1.0, semiring="log", entry_sum=None):
     return B
 
 
-def posteriors(e, net, lm, tdp, scale=1.0, entry_sum=None):
-    """-> (F, word posteriors [T, W]); p[t, silence] sums the silence word and every copy."""
-    A, WE = forward(e, net, lm, tdp, "log", scale, entry_sum)
+def gammas(e, net, lm, tdp, scale=1.0, entry_sum=None, dtype=np.float64):
+    """-> (kappa F, gamma [T, P]): the posterior of every position at every frame (0 where no path goes, all 0 for F = +inf)"""
+    A, WE = forward(e, net, lm, tdp, "log", scale, entry_sum, dtype)
     T = A.shape[0]
     kF = _lsum(WE[T])
     if T == 0:
-        return kF / scale, np.zeros((0, net.W))
-    Bt = backward(e, net, lm, tdp, scale, entry_sum=entry_sum)
+        return kF, np.zeros((0, net.P), dtype=dtype)
+    Bt = backward(e, net, lm, tdp, scale, entry_sum=entry_sum, dtype=dtype)
     ok = np.isfinite(A) & np.isfinite(Bt) & np.isfinite(kF)
+    zero = dtype(0.0)
     with np.errstate(invalid="ignore", over="ignore"):
-        G = np.where(ok, np.exp(kF - np.where(ok, A + Bt, 0.0)), 0.0)
-    p = np.zeros((T, net.W))
-    for t in range(T):
-        p[t] = np.bincount(net.word, weights=G[t], minlength=net.W)
-    return kF / scale, p
+        G = np.where(ok, np.exp(kF - np.where(ok, A + Bt, zero)), zero)
+    return kF, G
+
+
+def collect(G, index, n):
+    """[T, P] -> [T, n]: the positions' values summed per index (np.bincount, which knows float64 only, in G's dtype)"""
+    if G.dtype != np.longdouble:
+        return np.stack([np.bincount(index, weights=g, minlength=n) for g in G]) if len(G) else np.zeros((0, n))
+    out = np.zeros((G.shape[0], n), dtype=G.dtype)
+    for t in range(G.shape[0]):
+        np.add.at(out[t], index, G[t])
+    return out
+
+
+def posteriors(e, net, lm, tdp, scale=1.0, entry_sum=None, dtype=np.float64):
+    """-> (F, word posteriors [T, W]); p[t, silence] sums the silence word and every copy."""
+    kF, G = gammas(e, net, lm, tdp, scale, entry_sum, dtype)
+    return kF / dtype(scale), collect(G, net.word, net.W)
 
 
 def best_cost(e, net, lm, tdp):

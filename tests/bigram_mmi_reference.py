@@ -21,41 +21,33 @@ from tests import bigram_fb_reference as R
 INF = np.inf
 
 
-def _lse(xs):
-    xs = [float(x) for x in xs if np.isfinite(x)]
+def _lse(xs, dtype=np.float64):
+    xs = [dtype(x) for x in xs if np.isfinite(x)]
     if not xs:
-        return INF
+        return dtype(INF)
     m = min(xs)
     return m - np.log(sum(np.exp(m - x) for x in xs))
 
 
-def free_occupancies(e, net, lm, tdp, scale=1.0, entry_sum=None):
-    """-> (F_den, occ [T, S]) of the free network"""
-    e = np.asarray(e, dtype=np.float64)
-    T, S = e.shape
-    A, WE = R.forward(e, net, lm, tdp, "log", scale, entry_sum)
-    kF = R._lsum(WE[T])
-    occ = np.zeros((T, S))
-    if T == 0 or not np.isfinite(kF):
-        return kF / scale, occ
-    B = R.backward(e, net, lm, tdp, scale, entry_sum=entry_sum)
-    ok = np.isfinite(A) & np.isfinite(B)
-    with np.errstate(invalid="ignore", over="ignore"):
-        G = np.where(ok, np.exp(kF - np.where(ok, A + B, 0.0)), 0.0)
-    for t in range(T):
-        occ[t] = np.bincount(net.state, weights=G[t], minlength=S)
-    return kF / scale, occ
+def free_occupancies(e, net, lm, tdp, scale=1.0, entry_sum=None, dtype=np.float64):
+    """-> (F_den, occ [T, S]) of the free network; dtype as bigram_fb_reference's"""
+    S = np.asarray(e).shape[1]
+    kF, G = R.gammas(e, net, lm, tdp, scale, entry_sum, dtype)
+    return kF / dtype(scale), R.collect(G, net.state, S)[:, :S]
 
 
-def chain_occupancies(e, net, lm, tdp, transcript, scale=1.0):
-    """-> (F_num, occ [T, S]) of the network restricted to the transcript (word ids, silence not listed)"""
-    e = np.asarray(e, dtype=np.float64)
+def chain_occupancies(e, net, lm, tdp, transcript, scale=1.0, dtype=np.float64):
+    """-> (F_num, occ [T, S]) of the network restricted to the transcript (word ids, silence not listed); dtype as
+    bigram_fb_reference's"""
+    e = np.asarray(e, dtype=np.float64).astype(dtype)
     T, S = e.shape
     W, sil = net.W, net.sil
-    td = scale * np.asarray(tdp, dtype=np.float64).reshape(2, 4)
-    lm = np.asarray(lm, dtype=np.float64)
+    scale = dtype(scale)
+    td = scale * np.asarray(tdp, dtype=np.float64).reshape(2, 4).astype(dtype)
+    lm = np.asarray(lm, dtype=np.float64).astype(dtype)
+    lse = lambda xs: _lse(xs, dtype)  # noqa: E731
     # segments: slot, states' mixtures, isSilence, entry LM cost, sources (segments whose word end enters it)
-    slots, klm, srcs = [sil], [0.0], [[0]]
+    slots, klm, srcs = [sil], [dtype(0.0)], [[0]]
     hist = sil
     for i, w in enumerate(transcript):
         w = int(w)
@@ -63,7 +55,7 @@ def chain_occupancies(e, net, lm, tdp, transcript, scale=1.0):
         g = len(slots)
         x = lm[w, hist]
         slots += [w, w + W]
-        klm += [scale * x if np.isfinite(x) or x == -INF else INF, 0.0]
+        klm += [scale * x if np.isfinite(x) or x == -INF else dtype(INF), dtype(0.0)]
         srcs += [[0] if i == 0 else [g - 2, g - 1], [g]]
         hist = w
     G = len(slots)
@@ -72,15 +64,15 @@ def chain_occupancies(e, net, lm, tdp, transcript, scale=1.0):
     n = [len(m) for m in mix]
     dsts = [[d for d in range(G) if g in srcs[d]] for g in range(G)]
     finals = [G - 1] + ([G - 2] if G > 1 else [])
-    occ = np.zeros((T, S))
+    occ = np.zeros((T, S), dtype=dtype)
     if T == 0:
-        return (0.0 if G == 1 else INF), occ
-    A = [[np.full(n[g], INF) for g in range(G)] for _ in range(T)]
-    we = [INF] * G
-    we[0] = 0.0  # the start's word end is the silence word's
+        return dtype(0.0 if G == 1 else INF), occ
+    A = [[np.full(n[g], INF, dtype=dtype) for g in range(G)] for _ in range(T)]
+    we = [dtype(INF)] * G
+    we[0] = dtype(0.0)  # the start's word end is the silence word's
     for t in range(T):
         for g in range(G):
-            ent = _lse(we[h] for h in srcs[g]) + klm[g]
+            ent = lse(we[h] for h in srcs[g]) + klm[g]
             p = td[isl[g]]
             for k in range(n[g]):
                 terms = []
@@ -90,12 +82,12 @@ def chain_occupancies(e, net, lm, tdp, transcript, scale=1.0):
                     terms.append(ent)
                 if k == 1:
                     terms.append(ent + p[2])
-                A[t][g][k] = _lse(terms) + scale * e[t, mix[g][k]]
+                A[t][g][k] = lse(terms) + scale * e[t, mix[g][k]]
         we = [A[t][g][n[g] - 1] + td[isl[g], 3] for g in range(G)]
-    kF = _lse(we[g] for g in finals)
+    kF = lse(we[g] for g in finals)
     if not np.isfinite(kF):
-        return INF, occ
-    B = [[np.full(n[g], INF) for g in range(G)] for _ in range(T)]
+        return dtype(INF), occ
+    B = [[np.full(n[g], INF, dtype=dtype) for g in range(G)] for _ in range(T)]
     for t in range(T - 1, -1, -1):
         for g in range(G):
             p = td[isl[g]]
@@ -110,8 +102,8 @@ def chain_occupancies(e, net, lm, tdp, transcript, scale=1.0):
                     if k == n[g] - 1:
                         for d in dsts[g]:
                             into = [x(d, 0)] + ([td[isl[d], 2] + x(d, 1)] if n[d] >= 2 else [])
-                            terms.append(p[3] + klm[d] + _lse(into))
-                B[t][g][k] = _lse(terms)
+                            terms.append(p[3] + klm[d] + lse(into))
+                B[t][g][k] = lse(terms)
                 y = A[t][g][k] + B[t][g][k]
                 if np.isfinite(y):
                     occ[t, mix[g][k]] += np.exp(kF - y)

@@ -27,21 +27,28 @@ INF = np.inf
 
 def _wmean(xs, vals, axis=0):
     """-> (-log sum exp(-x), the mean of vals weighted with exp(-x)) along axis; (+inf, 0) where no x is finite"""
-    xs = np.asarray(xs, dtype=np.float64)
-    vals = np.broadcast_to(np.asarray(vals, dtype=np.float64), xs.shape)
+    xs = R._arr(xs)
+    dt = xs.dtype.type
+    vals = np.broadcast_to(np.asarray(vals).astype(xs.dtype), xs.shape)
     if xs.shape[axis] == 0:
         shape = np.delete(xs.shape, axis)
-        return np.full(shape, INF)[()], np.zeros(shape)[()]
+        return np.full(shape, INF, dtype=xs.dtype)[()], np.zeros(shape, dtype=xs.dtype)[()]
     m = xs.min(axis=axis, keepdims=True)
     ok = np.isfinite(m)
-    ms = np.where(ok, m, 0.0)
+    ms = np.where(ok, m, dt(0.0))
     with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
-        w = np.where(np.isfinite(xs), np.exp(ms - xs), 0.0)
+        w = np.where(np.isfinite(xs), np.exp(ms - xs), dt(0.0))
         s = w.sum(axis=axis, keepdims=True)
-        s1 = np.where(ok, s, 1.0)
-        cost = np.where(ok, ms - np.log(s1), INF)
-        acc = np.where(ok, (w * np.where(np.isfinite(xs), vals, 0.0)).sum(axis=axis, keepdims=True) / s1, 0.0)
+        s1 = np.where(ok, s, dt(1.0))
+        cost = np.where(ok, ms - np.log(s1), dt(INF))
+        acc = np.where(ok, (w * np.where(np.isfinite(xs), vals, dt(0.0))).sum(axis=axis, keepdims=True) / s1, dt(0.0))
     return np.squeeze(cost, axis)[()], np.squeeze(acc, axis)[()]
+
+
+def _entry_mean(vec, vals, klm, axis):
+    """the W x W weighted mean of the word entry: over the histories (axis 1: vec = their costs) or over the words (axis 0), in log
+    space"""
+    return _wmean((vec[None, :] if axis == 1 else vec[:, None]) + klm, vals[None, :] if axis == 1 else vals[:, None], axis=axis)
 
 
 def _shift(v, j, fill):
@@ -55,37 +62,42 @@ def _shift(v, j, fill):
     return out
 
 
-def smbr(e, net, lm, tdp, ref, scale=1.0, shift=0.0):
+def smbr(e, net, lm, tdp, ref, scale=1.0, shift=0.0, dtype=np.float64, entry_sum=None):
     """e [T, S] emission costs, net a bigram_fb_reference.Net, lm [W, W] (lm[w, h]; NaN / +inf: forbidden), tdp [2][4], ref [T]
     reference mixtures (>= S: none) -> (F, Abar, gamma [T, S]); T = 0: F = 0; T = 0 or F = +inf: Abar = 0, gamma = 0.
     shift: every frame of every path scores that much more.  Abar (returned without it) and gamma do not depend on it in exact
-    arithmetic; in FP64 the difference between two shifts shows this restatement's own rounding error."""
-    e = np.asarray(e, dtype=np.float64)
+    arithmetic; in FP64 the difference between two shifts shows this restatement's own rounding error.
+    dtype as bigram_fb_reference's.  entry_sum(vec, values, klm, axis) -> (cost, mean) replaces the W x W weighted mean of the word
+    entry, as bigram_fb_reference's entry_sum does the sum (tests: the linear-domain evaluation and the underflow cut)."""
+    e = np.asarray(e, dtype=np.float64).astype(dtype)
     T, S = e.shape
     W, P, sil = net.W, net.P, net.sil
     ref = np.asarray(ref, dtype=np.int64)
-    gamma = np.zeros((T, S))
+    gamma = np.zeros((T, S), dtype=dtype)
     if T == 0:
-        return 0.0, 0.0, gamma
-    klm, td = R._klm(net, lm, scale), R._tdp(tdp, scale)
+        return dtype(0.0), dtype(0.0), gamma
+    klm, td = R._klm(net, lm, scale, dtype), R._tdp(tdp, scale, dtype)
+    scale, shift = dtype(scale), dtype(shift)
+    wsum = entry_sum or _entry_mean
     pt = td[net.is_sil]  # [P, 4]
-    hit = lambda t: (net.state == ref[t]).astype(np.float64) + shift  # noqa: E731
+    hit = lambda t: (net.state == ref[t]).astype(dtype) + shift  # noqa: E731
     k, n = net.k, net.n
     is_last = k == n - 1
     two = (net.slot_off[1:] - net.slot_off[:-1]) >= 2
 
-    A, Aa = np.full((T, P), INF), np.zeros((T, P))
-    we, wea = R.start_ends(net), np.zeros(2 * W)
-    prev, preva = np.full(P, INF), np.zeros(P)
+    A, Aa = np.full((T, P), INF, dtype=dtype), np.zeros((T, P), dtype=dtype)
+    we, wea = R.start_ends(net, dtype), np.zeros(2 * W, dtype=dtype)
+    prev, preva = np.full(P, INF, dtype=dtype), np.zeros(P, dtype=dtype)
     for t in range(T):
         # histories and entries: word w from every history through the LM, the copy h + W from word h's end, silence from its own
         hist, hista = _wmean([we[:W], we[W:]], [wea[:W], wea[W:]])
         hist[sil], hista[sil] = we[sil], wea[sil]
-        ent, enta = np.full(2 * W, INF), np.zeros(2 * W)
-        ent[:W], enta[:W] = _wmean(hist[None, :] + klm, hista[None, :], axis=1)
+        ent, enta = np.full(2 * W, INF, dtype=dtype), np.zeros(2 * W, dtype=dtype)
+        ent[:W], enta[:W] = wsum(hist, hista, klm, 1)
         ent[W:], enta[W:] = we[:W], wea[:W]
         ent[sil], enta[sil] = we[sil], wea[sil]
         ent[sil + W], enta[sil + W] = INF, 0.0
+        zero = dtype(0.0)
         ep, epa = ent[net.slot], enta[net.slot]
         xs = [prev + pt[:, 0],
               np.where(k >= 1, _shift(prev, 1, INF) + pt[:, 1], INF),
@@ -93,28 +105,29 @@ def smbr(e, net, lm, tdp, ref, scale=1.0, shift=0.0):
               np.where(k == 0, ep, INF),
               np.where(k == 1, ep + pt[:, 2], INF)]
         vs = [preva, _shift(preva, 1, 0.0), _shift(preva, 2, 0.0), epa, epa]
-        cur, cura = _wmean(np.where(np.isnan(xs), INF, xs), vs)
+        cur, cura = _wmean(np.where(np.isnan(xs), dtype(INF), xs), vs)
         ok = np.isfinite(cur)
-        cur = np.where(ok, cur + scale * e[t, net.state], INF)
-        cura = np.where(ok, cura + hit(t), 0.0)
+        cur = np.where(ok, cur + scale * e[t, net.state], dtype(INF))
+        cura = np.where(ok, cura + hit(t), zero)
         A[t], Aa[t] = cur, cura
         we, wea = cur[net.last] + td[net.slot_sil, 3], cura[net.last]
         prev, preva = cur, cura
     kF, Abar = _wmean(we, wea)
     if not np.isfinite(kF):
-        return INF, 0.0, gamma
+        return dtype(INF), dtype(0.0), gamma
 
-    B, Bb = np.full(P, INF), np.zeros(P)
+    zero = dtype(0.0)
+    B, Bb = np.full(P, INF, dtype=dtype), np.zeros(P, dtype=dtype)
     for t in range(T - 1, -1, -1):
         if t == T - 1:
-            cur, cura = np.where(is_last, pt[:, 3], INF), np.zeros(P)
+            cur, cura = np.where(is_last, pt[:, 3], dtype(INF)), np.zeros(P, dtype=dtype)
         else:
             x = scale * e[t + 1, net.state] + B          # the successor's emission and beta
-            xa = np.where(np.isfinite(x), hit(t + 1) + Bb, 0.0)   # the accuracy of frames t + 1 ..
+            xa = np.where(np.isfinite(x), hit(t + 1) + Bb, zero)   # the accuracy of frames t + 1 ..
             f1 = np.minimum(net.first + 1, P - 1)
             bent, benta = _wmean([x[net.first], np.where(two, td[net.slot_sil, 2] + x[f1], INF)], [xa[net.first], xa[f1]])
-            Y, Ya = _wmean(bent[:W, None] + klm, benta[:W, None], axis=0)  # [h]: into every word through the LM
-            Rc, Ra = np.empty(2 * W), np.empty(2 * W)
+            Y, Ya = wsum(bent[:W], benta[:W], klm, 0)  # [h]: into every word through the LM
+            Rc, Ra = np.empty(2 * W, dtype=dtype), np.empty(2 * W, dtype=dtype)
             Rc[:W], Ra[:W] = _wmean([Y, bent[W:]], [Ya, benta[W:]])
             Rc[sil], Ra[sil] = _wmean([Y[sil], bent[sil]], [Ya[sil], benta[sil]])
             Rc[W:], Ra[W:] = Y, Ya
@@ -123,11 +136,11 @@ def smbr(e, net, lm, tdp, ref, scale=1.0, shift=0.0):
                   np.where(k + 2 < n, _shift(pt[:, 2] + x, -2, INF), INF),
                   np.where(is_last, pt[:, 3] + Rc[net.slot], INF)]
             vs = [xa, _shift(xa, -1, 0.0), _shift(xa, -2, 0.0), Ra[net.slot]]
-            cur, cura = _wmean(np.where(np.isnan(xs), INF, xs), vs)
+            cur, cura = _wmean(np.where(np.isnan(xs), dtype(INF), xs), vs)
         B, Bb = cur, cura
         y = A[t] + B
         ok = np.isfinite(y)
         with np.errstate(invalid="ignore", over="ignore"):
-            g = np.where(ok, np.exp(kF - np.where(ok, y, 0.0)) * (Aa[t] + Bb - Abar), 0.0)
-        gamma[t] = np.bincount(net.state, weights=g, minlength=S)[:S]
-    return kF / scale, float(Abar) - T * shift, gamma
+            g = np.where(ok, np.exp(kF - np.where(ok, y, zero)) * (Aa[t] + Bb - Abar), zero)
+        gamma[t] = R.collect(g[None, :], net.state, S)[0, :S]
+    return kF / scale, dtype(Abar) - T * shift, gamma

@@ -1,7 +1,10 @@
 """MMI training against the bigram search network on the device: sr_bigram_occupancies_corpus and sr_bigram_mmi_statistics_corpus
 against the numpy restatement (tests/bigram_mmi_reference.py, pinned by tests/test_bigram_mmi_cpu.py), the bigram word posteriors,
 the decoder and themselves.  Tolerances are the project's (test_gpu_mmi.py / test_gpu_bigram_posteriors.py): costs 1e-10 relative,
-occupancies 1e-9 absolute, statistics 1e-9 relative to sum |w x|."""
+occupancies 1e-9 absolute, statistics 1e-9 relative to sum |w x|.  Beside them, wherever it is tighter, the measured rule of tests/test_gpu_bgfb_scores.py against the restatement's
+np.longdouble run (bigram_fb_cases.measured: 8 times the distance of the farther of the log-space and the linear-domain float64
+restatement plus 4 ulp of the value; the `RULE` lines say which of the two holds); test_scale_shape keeps the fixed pair (a
+longdouble run of its 2 667-word entry sums takes minutes)."""
 import json
 import os
 import struct
@@ -12,6 +15,7 @@ import numpy as np
 import pytest
 
 from speechrecognition_amd import capi, synth
+from tests import bigram_fb_cases as bc
 from tests import bigram_fb_reference as R
 from tests import bigram_mmi_reference as BM
 from tests.test_bigram import FLT_MAX, SIL_TDP, _setup
@@ -62,7 +66,21 @@ def _refs(o, utts, net, lm, tdp, trans, scale, S):
     return out
 
 
-def _against_restatement(o, m, bg, allf, off, trans, refs, scale, S, floors=(0.0, 1e-6), modes=((True, 0.0), (False, 1e-6))):
+def _rules(o, utts, net, lm, tdp, trans, scale, S, refs):
+    """per utterance and side the longdouble run and the measured bounds on F and on every occupancy, where they are tighter than 1e-10
+    relative and 1e-9 (bigram_fb_cases.measured; the `RULE` lines say which holds)"""
+    out = []
+    for u, (x, tr) in enumerate(zip(utts, trans)):
+        e = o.score_matrix(x) if len(x) else np.zeros((0, S))
+        num = lambda e=e, tr=tr, **kw: BM.chain_occupancies(e, net, lm, tdp, tr, scale, **kw)  # noqa: E731
+        den = lambda e=e, **kw: BM.free_occupancies(e, net, lm, tdp, scale, **kw)  # noqa: E731
+        fixed = lambda F: (1e-10 * max(1.0, abs(float(F))) if np.isfinite(F) else 0.0, 1e-9)  # noqa: E731
+        out.append((bc.measured(num, refs[u][0], None, fixed(refs[u][0][0]), f"utterance {u} kappa {scale} chain"),
+                    bc.measured(den, refs[u][1], bc.lin_entry(net.sil), fixed(refs[u][1][0]), f"utterance {u} kappa {scale} free")))
+    return out
+
+
+def _against_restatement(o, m, bg, allf, off, trans, refs, scale, S, floors=(0.0, 1e-6), modes=((True, 0.0), (False, 1e-6)), rules=None):
     """F_num, F_den, the occupancy items of both networks and both statistics sets"""
     tables = o.tables()
     corpus = m.upload(allf, off)
@@ -74,9 +92,11 @@ def _against_restatement(o, m, bg, allf, off, trans, refs, scale, S, floors=(0.0
                     F, occ = ref[side]
                     print("cost", side, u, cost[u], F)
                     assert _rel(cost[u], F) <= 1e-10, (side, u, cost[u], F)
+                    (F80, o80), (tolF, tolo) = rules[u][side] if rules else ((F, occ), (np.inf, np.full(occ.shape, np.inf)))
+                    assert cost[u] == F80 or abs(bc.LD(cost[u]) - F80) <= tolF, (side, u, cost[u], F80, tolF)
                     for t in range(occ.shape[0]):
                         ft = int(off[u]) + t
-                        _check_items(occ[t], count[ft], state[ft], weight[ft], floor, K)
+                        _check_items(occ[t], count[ft], state[ft], weight[ft], floor, K, o80[t], tolo[t])
                         if K == S and floor == 0.0 and np.isfinite(F):
                             assert abs(weight[ft].sum() - 1.0) <= 1e-8
     for max_approx, floor in modes:
@@ -109,7 +129,8 @@ def test_against_restatement(shape, tmp_path, oracle_lib):
             assert refs[5][0][0] == np.inf and np.isfinite(refs[5][1][0])  # too long for its utterance
             assert refs[6][0][0] == np.inf and refs[7][0][0] == np.inf     # forbidden LM entries
             assert np.isfinite(refs[0][0][0]) and np.isfinite(refs[3][0][0])
-            _against_restatement(o, m, bg, allf, off, trans, refs, scale, lex.n_states)
+            _against_restatement(o, m, bg, allf, off, trans, refs, scale, lex.n_states,
+                                 rules=_rules(o, utts, net, lm, tdp, trans, scale, lex.n_states, refs))
         bg.close()
     o.close()
 
@@ -132,7 +153,8 @@ def test_one_state_words_negative_costs(tmp_path, oracle_lib):
         bg = m.bigram(word_off, mixtures, lex.silence_idx, lm, tdp)
         refs = _refs(o, utts, net, lm, tdp, trans, 0.5, lex.n_states)
         assert np.isfinite(refs[0][0][0])
-        _against_restatement(o, m, bg, allf, off, trans, refs, 0.5, lex.n_states, floors=(0.0,), modes=((True, 0.0),))
+        _against_restatement(o, m, bg, allf, off, trans, refs, 0.5, lex.n_states, floors=(0.0,), modes=((True, 0.0),),
+                             rules=_rules(o, utts, net, lm, tdp, trans, 0.5, lex.n_states, refs))
         bg.close()
     o.close()
 

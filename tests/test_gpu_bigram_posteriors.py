@@ -2,11 +2,15 @@
 sr_recognize_bigram_confidence_corpus) against the numpy restatement of its network's forward-backward
 (tests/bigram_fb_reference.py) on the oracle's emission costs.  Tolerances: F_u 1e-10 relative, posteriors and confidences 1e-9
 absolute (the project's for the zerogram network; the product's summation error, about W T 2^-53 on an exponent, is far below them
-at these sizes)."""
+at these sizes).  Beside them, wherever it is tighter, the measured rule of tests/test_gpu_bgfb_scores.py against the restatement's
+np.longdouble run (bigram_fb_cases.measured: 8 times the distance of the farther of the log-space and the linear-domain float64
+restatement plus 4 ulp of the value; the `RULE` lines say which of the two holds); test_scale_shape keeps the fixed pair (a
+longdouble run of its 2 667-word entry sums takes minutes)."""
 import numpy as np
 import pytest
 
 from speechrecognition_amd import capi, synth
+from tests import bigram_fb_cases as bc
 from tests import bigram_fb_reference as R
 from tests.test_bigram import FLT_MAX, SIL_TDP, _setup
 from tests.test_gpu_word_posteriors import _check_items, _rel
@@ -30,15 +34,28 @@ def _refs(o, utts, net, lm, tdp, scale):
     return [R.posteriors(o.score_matrix(x) if len(x) else np.zeros((0, 1)), net, lm, tdp, scale) for x in utts]
 
 
-def _against(corpus, bg, refs, off, W, scale, floors=(0.0, 1e-6), Ks=None):
+def _rules(o, utts, net, lm, tdp, scale, refs):
+    """per utterance the longdouble run and the measured bounds on F and on every posterior, where they are tighter than 1e-10 relative
+    and 1e-9 (bigram_fb_cases.measured; the `RULE` lines say which holds)"""
+    out = []
+    for u, x in enumerate(utts):
+        e = o.score_matrix(x) if len(x) else np.zeros((0, 1))
+        run = lambda e=e, **kw: R.posteriors(e, net, lm, tdp, scale, **kw)  # noqa: E731
+        out.append(bc.measured(run, refs[u], bc.lin_entry(net.sil), (1e-10 * max(1.0, abs(float(refs[u][0]))), 1e-9), f"utterance {u} kappa {scale}"))
+    return out
+
+
+def _against(corpus, bg, refs, off, W, scale, floors=(0.0, 1e-6), Ks=None, rules=None):
     for floor in floors:
         for K in (Ks or (1, 3, W)):
             cost, count, word, weight = corpus.bigram_word_posteriors(bg, scale, capi.GMM_PREFILTER, floor, K)
             for u, (F, p) in enumerate(refs):
                 assert _rel(cost[u], F) <= 1e-10, (u, cost[u], F)
+                (F80, p80), (tolF, tolp) = rules[u] if rules else ((F, p), (np.inf, np.full(p.shape, np.inf)))
+                assert cost[u] == F80 or abs(bc.LD(cost[u]) - F80) <= tolF, (u, cost[u], F80, tolF)
                 for t in range(p.shape[0]):
                     ft = int(off[u]) + t
-                    _check_items(p[t], count[ft], word[ft], weight[ft], floor, K)
+                    _check_items(p[t], count[ft], word[ft], weight[ft], floor, K, p80[t], tolp[t])
 
 
 @pytest.mark.parametrize("shape", SHAPES)
@@ -54,7 +71,8 @@ def test_posteriors_against_restatement(shape, tmp_path, oracle_lib):
         for scale in (1.0, 0.3):  # (the second call rebuilds the cached table for its kappa)
             refs = _refs(o, utts, net, lm, tdp, scale)
             assert refs[2][0] == 0.0
-            _against(corpus, bg, refs, off, lex.n_words, scale, Ks=(1, lex.n_words) if W > 10 else None)
+            _against(corpus, bg, refs, off, lex.n_words, scale, Ks=(1, lex.n_words) if W > 10 else None,
+                     rules=_rules(o, utts, net, lm, tdp, scale, refs))
         corpus.close()
         bg.close()
     o.close()
@@ -79,7 +97,8 @@ def test_one_state_words_negative_costs_and_forbidden_transitions(tmp_path, orac
     with capi.Model.from_mixset(mp, 12) as m:
         bg = m.bigram(word_off, mixtures, lex.silence_idx, lm, tdp)
         corpus = m.upload(allf, off)
-        _against(corpus, bg, _refs(o, utts, net, lm, tdp, 0.5), off, lex.n_words, 0.5, floors=(0.0,))
+        refs = _refs(o, utts, net, lm, tdp, 0.5)
+        _against(corpus, bg, refs, off, lex.n_words, 0.5, floors=(0.0,), rules=_rules(o, utts, net, lm, tdp, 0.5, refs))
         corpus.close()
         bg.close()
     o.close()

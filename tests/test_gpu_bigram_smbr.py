@@ -1,7 +1,9 @@
 """sMBR training against the bigram search network on the device: sr_bigram_accuracies_corpus and sr_bigram_smbr_statistics_corpus
 against the numpy restatement (tests/bigram_smbr_reference.py, pinned by tests/test_bigram_smbr_cpu.py), the bigram word posteriors
 and occupancies, and themselves.  Tolerances are the project's (test_gpu_smbr.py / test_gpu_bigram_mmi.py): F 1e-10 relative; Abar
-and every gamma 1e-9 (1 + T_u) absolute; statistics 1e-9 relative to sum |w x| (test_gpu_mmi._check_stats).
+and every gamma 1e-9 (1 + T_u) absolute; statistics 1e-9 relative to sum |w x| (test_gpu_mmi._check_stats).  Beside them, wherever it is tighter, the measured rule of tests/test_gpu_bgfb_scores.py against the restatement's
+np.longdouble run (bigram_fb_cases.measured: 8 times the distance of the farther of the log-space and the linear-domain float64
+restatement plus 4 ulp of the value; the `RULE` lines say which of the two holds); the statistics keep their fixed bound.
 
 Where the statistics are compared.  A weight gamma = occ (c - Abar) carries the absolute rounding error of c - Abar, a few ulp of
 Abar, in the device and in the restatement alike.  Where one mixture holds ALL of a frame's posterior in FP64 (every other path's
@@ -21,6 +23,7 @@ import numpy as np
 import pytest
 
 from speechrecognition_amd import capi, synth
+from tests import bigram_fb_cases as bc
 from tests import bigram_fb_reference as R
 from tests import bigram_smbr_reference as BS
 from tests import fb_reference as FB
@@ -64,6 +67,20 @@ def _refs(o, utts, off, ref, net, lm, tdp, scale, S, shift=0.0):
     return out
 
 
+def _rules(o, utts, off, ref, net, lm, tdp, scale, S, res):
+    """per utterance the longdouble run and the measured bounds on F, Abar and every gamma, where they are tighter than 1e-10 relative
+    and 1e-9 (1 + T) (bigram_fb_cases.measured; the `RULE` lines say which holds)"""
+    out = []
+    for u, x in enumerate(utts):
+        e = o.score_matrix(x) if len(x) else np.zeros((0, S))
+        r = ref[int(off[u]):int(off[u + 1])].astype(np.int64)
+        run = lambda e=e, r=r, **kw: BS.smbr(e, net, lm, tdp, r, scale, **kw)  # noqa: E731
+        tol = 1e-9 * (1 + len(x))
+        out.append(bc.measured(run, res[u], bc.lin_entry_mean(net.sil), (1e-10 * max(1.0, abs(float(res[u][0]))), tol, tol),
+                               f"utterance {u} kappa {scale}"))
+    return out
+
+
 def _side_items(res, floor):
     items = [[], []]
     for _, _, g in res:
@@ -92,7 +109,8 @@ def _stats(got, feats, items, tables, max_approx, tag):
     _check_stats(got, feats, items, tables, max_approx)
 
 
-def _against_restatement(o, m, bg, allf, off, ref, res, scale, S, floors=(0.0, 1e-6), modes=((True, 0.0), (False, 1e-6)), shifted=None):
+def _against_restatement(o, m, bg, allf, off, ref, res, scale, S, floors=(0.0, 1e-6), modes=((True, 0.0), (False, 1e-6)), shifted=None,
+                         rules=None):
     """F, Abar and the signed items for every floor and K in (1, 3, S); then, with `shifted` (the restatement's second evaluation),
     both statistics sides for every membership mode; without it the statistics call's F and Abar alone"""
     tables = o.tables()
@@ -105,9 +123,13 @@ def _against_restatement(o, m, bg, allf, off, ref, res, scale, S, floors=(0.0, 1
                 tol = 1e-9 * (1 + T)
                 print("utt", u, cost[u], F, acc[u], A)
                 assert _rel(cost[u], F) <= 1e-10 and abs(acc[u] - A) <= tol and 0.0 <= acc[u] <= T + tol
+                (F80, A80, g80), (tolF, tolA, tolg) = rules[u] if rules else ((F, A, g), (np.inf, np.inf, np.full(g.shape, np.inf)))
+                assert cost[u] == F80 or abs(bc.LD(cost[u]) - F80) <= tolF, (u, cost[u], F80, tolF)
+                # (Abar, a sum of occupancies, is held to the larger of its own bound and the weights': test_gpu_bgsmbr_scores.py)
+                assert abs(bc.LD(acc[u]) - A80) <= max(float(tolA), float(np.max(tolg)) if tolg.size else 0.0), (u, acc[u], A80, tolA)
                 for t in range(T):
                     ft = int(off[u]) + t
-                    _check_signed_items(g[t], count[ft], state[ft], weight[ft], floor, K, tol)
+                    _check_signed_items(g[t], count[ft], state[ft], weight[ft], floor, K, tol, g80[t], tolg[t])
                     if K == S and floor == 0.0:
                         assert abs(weight[ft].sum()) <= tol
     for max_approx, floor in modes:
@@ -147,7 +169,8 @@ def test_against_restatement(shape, tmp_path, oracle_lib):
             assert np.isfinite(res[0][0]) and np.isfinite(res[3][0]) and res[0][1] > 0.0
             assert res[5][1] == 0.0 and not res[5][2].any()         # every reference out of range
             shifted = _refs(o, utts, off, ref, net, lm, tdp, scale, S, 1.0) if scale in STAT_SCALES else None
-            _against_restatement(o, m, bg, allf, off, ref, res, scale, S, shifted=shifted)
+            _against_restatement(o, m, bg, allf, off, ref, res, scale, S, shifted=shifted,
+                                 rules=_rules(o, utts, off, ref, net, lm, tdp, scale, S, res))
         bg.close()
     o.close()
 
@@ -170,7 +193,8 @@ def test_one_state_words_negative_costs(tmp_path, oracle_lib):
         bg = m.bigram(word_off, mixtures, lex.silence_idx, lm, tdp)
         res = _refs(o, utts, off, ref, net, lm, tdp, 0.5, S)
         assert np.isfinite(res[0][0])
-        _against_restatement(o, m, bg, allf, off, ref, res, 0.5, S, floors=(0.0,), modes=((True, 0.0),))
+        _against_restatement(o, m, bg, allf, off, ref, res, 0.5, S, floors=(0.0,), modes=((True, 0.0),),
+                             rules=_rules(o, utts, off, ref, net, lm, tdp, 0.5, S, res))
         bg.close()
     o.close()
 
