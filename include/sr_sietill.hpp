@@ -567,6 +567,16 @@ class StreamingRecognizer {
     check(sr_stream_push_audio(s_, 1, &id, samples, off, nullptr, 0, nullptr));
   }
   void finish_audio(uint32_t id) { check(sr_stream_finish_audio(s_, 1, &id, nullptr, 0, nullptr)); }
+  // The pipeline (srgpu.h: sr_stream_set_projection): rows of in_dim columns are spliced with `context` neighbours on either side and
+  // projected by M [dimension x ((2 context + 1) in_dim + 1)] (nullptr detaches; while no utterance is open), then the utterance's
+  // W [dimension x (dimension + 1)] (nullptr clears it; between begin() and its first push) is applied, on the device.  push_rows:
+  // n_frames rows of one utterance, in_dim columns with a projection; finish: no more follow, its last `context` rows are searched.
+  void set_projection(uint32_t in_dim, uint32_t context, const double* M) { check(sr_stream_set_projection(s_, in_dim, context, M)); }
+  void set_transform(uint32_t id, const double* W) { check(sr_stream_set_transform(s_, id, W)); }
+  void push_rows(uint32_t id, const float* frames, size_t n_frames, bool finish = false) {
+    const uint64_t off[2] = {0, n_frames};
+    check(sr_stream_push_rows(s_, 1, &id, frames, off, finish ? 1 : 0, nullptr, 0, nullptr));
+  }
   // new frames of several utterances back to back: ids[i] owns rows [frame_off[i], frame_off[i+1])
   void push(std::vector<uint32_t> const& ids, const float* frames, std::vector<uint64_t> const& frame_off) {
     if (frame_off.size() != ids.size() + 1) throw std::runtime_error("StreamingRecognizer::push: frame_off needs ids.size() + 1 entries");
@@ -1946,6 +1956,16 @@ class StreamingLinearSearch {
     check(sr_bigram_stream_push_audio(s_, 1, &id, samples, off, nullptr, 0, nullptr));
   }
   void finish_audio(uint32_t id) { check(sr_bigram_stream_finish_audio(s_, 1, &id, nullptr, 0, nullptr)); }
+  // The pipeline (srgpu.h: sr_bigram_stream_set_projection): rows of in_dim columns are spliced with `context` neighbours on either side and
+  // projected by M [dimension x ((2 context + 1) in_dim + 1)] (nullptr detaches; while no utterance is open), then the utterance's
+  // W [dimension x (dimension + 1)] (nullptr clears it; between begin() and its first push) is applied, on the device.  push_rows:
+  // n_frames rows of one utterance, in_dim columns with a projection; finish: no more follow, its last `context` rows are searched.
+  void set_projection(uint32_t in_dim, uint32_t context, const double* M) { check(sr_bigram_stream_set_projection(s_, in_dim, context, M)); }
+  void set_transform(uint32_t id, const double* W) { check(sr_bigram_stream_set_transform(s_, id, W)); }
+  void push_rows(uint32_t id, const float* frames, size_t n_frames, bool finish = false) {
+    const uint64_t off[2] = {0, n_frames};
+    check(sr_bigram_stream_push_rows(s_, 1, &id, frames, off, finish ? 1 : 0, nullptr, 0, nullptr));
+  }
   void push(std::vector<uint32_t> const& ids, const float* frames, std::vector<uint64_t> const& frame_off) {
     if (frame_off.size() != ids.size() + 1) throw std::runtime_error("StreamingLinearSearch::push: frame_off needs ids.size() + 1 entries");
     check(sr_bigram_stream_push(s_, (uint32_t)ids.size(), ids.data(), frames, frame_off.data()));

@@ -800,7 +800,7 @@ SR_API int sr_vtln_choose(uint32_t n_speakers, uint32_t n_warps, const double* c
  * frame (argmax - step) carry a smaller maximum than sr_corpus_from_audio subtracts.
  *
  * sr_stream_set_frontend   attaches `fe` (NULL detaches) -- only while no id is open; the front end must belong to the stream set's model
- *                          and have an MFCC stage; it is destroyed after the stream set.  Device memory: max_streams x (2 step n_static + 1)
+ *                          (with a projection attached: see sr_stream_set_projection) and have an MFCC stage; it is destroyed after the stream set.  Device memory: max_streams x (2 step n_static + 1)
  *                          floats, the last 2 step statics and the running maximum of every slot.
  * sr_stream_push_audio     n utterances, ids[n], each at most once; their new samples back to back, entry i's at samples[sample_off[i] ..
  *                          sample_off[i + 1]), sample_off[0] == 0, an empty range allowed.  The rows that became ready are searched
@@ -830,6 +830,59 @@ SR_API int sr_bigram_stream_push_audio(struct sr_bigram_stream* s, uint32_t n, c
                                        uint64_t* out_frame_off /*[n+1], optional*/);
 SR_API int sr_bigram_stream_finish_audio(struct sr_bigram_stream* s, uint32_t n, const uint32_t* ids, float* out_feats /*optional*/,
                                          uint64_t cap_rows, uint64_t* out_frame_off /*[n+1], optional*/);
+/* ---- streaming: splice, projection and per-utterance transform on the device ------------------------------------------
+ * A stream set of a model of dimension p may carry a pipeline of two optional stages, applied on the device (stream_pipeline_kernel,
+ * one launch per push, one workgroup per pushed utterance) to every row before it is scored.
+ *   1. projection  set for the whole stream set: in_dim = D, context = c, M [p x (E + 1)] doubles, E = (2c + 1) D.  Row t of an utterance
+ *                  of T input rows is sr_corpus_splice_transform's row, bit for bit:
+ *                    z_t[(o + c) D + j] = (double) x[min(max(t + o, 0), T - 1)][j], o = -c .. c;
+ *                    acc = M[i][E];  acc = acc + M[i][n] * z_t[n] for n ascending, FP64, no fused multiply-add;  the row is (float) acc.
+ *   2. transform   set per utterance: W [p x (p + 1)] = [A b], applied to the float row stage 1 produced (to the pushed row without a
+ *                  projection); sr_corpus_transform's row, bit for bit:
+ *                    acc = b_i;  acc = acc + A_ij * (double) y_j for j ascending, no FMA;  the row is (float) acc.
+ * The intermediate row is rounded to float between the stages, as it is when the batch calls run one after the other.  So, for every
+ * way of cutting an utterance into pushes, the rows searched are bit-identical to sr_corpus_upload (or sr_corpus_from_audio without
+ * the energy maximum), then sr_corpus_splice_transform, then sr_corpus_transform on the whole utterance, and the words and the
+ * traceback are sr_recognize_corpus' (sr_recognize_bigram_corpus') on that corpus.
+ * Delay.  An utterance has received R input rows so far.
+ *   before the finish  rows 0 .. R - 1 - c have been searched (none while R <= c): row t needs the input rows t - c .. t + c; the left clamp
+ *                      is known at once, the right clamp involves T;
+ *   after the finish   all T rows have been searched, the last up to c of them with the clamp of the now-known T (a one-row utterance
+ *                      splices 2c + 1 copies of its row).
+ * With c == 0, or without a projection, there is no delay and nothing to finish.  For audio ids R is the number of rows the front end
+ * has readied: the total delay is deriv_step + c frames, and sr_stream_finish_audio flushes both stages.
+ *
+ * sr_stream_set_projection  only while no id is open; M == NULL detaches.  SR_ELIMIT for E > 512; SR_EINVAL for in_dim == 0, for an attached
+ *                           front end whose model's dimension is not in_dim, and for detaching with an attached front end that does not
+ *                           belong to the stream set's model.  With a projection attached sr_stream_set_frontend accepts a front end of
+ *                           any model of dimension in_dim on the stream set's device (such a front end and its model are destroyed after
+ *                           the stream set); without one it behaves as before.  Device memory: M, max_streams x 2c x in_dim floats of
+ *                           history (the last 2c input rows of every slot) and one more per-push buffer, of input rows.
+ * sr_stream_set_transform   between sr_stream_begin and the id's first push of either kind, else SR_EINVAL.  W == NULL clears it; a fresh
+ *                           id has none.  SR_ELIMIT for a model dimension above 63 (sr_corpus_transform's limit).  Device memory:
+ *                           max_streams x p x (p + 1) doubles, allocated by the first call.
+ * sr_stream_push_rows       the general row push.  feats has in_dim columns with a projection attached, else p; ids, frame_off as
+ *                           sr_stream_push.  finish != 0: every named id is finished after its rows and its last c rows are emitted; a
+ *                           finish without new rows is allowed (frame_off, feats may then be NULL).  A finished id takes no more rows
+ *                           (SR_EINVAL).  out_feats, cap_rows, out_frame_off as in sr_stream_push_audio: the rows this call searched,
+ *                           in the model's space; too small a cap_rows is SR_EINVAL with the count in out_frame_off[n], and nothing
+ *                           changes.  A push that readies no row launches no scoring and no search.
+ *                           sr_stream_push(s, n, ids, feats, frame_off) is sr_stream_push_rows(.., 0, NULL, 0, NULL).
+ * sr_stream_end on a row id that has received rows not yet searched is SR_EINVAL and leaves the id open (possible only with context
+ * > 0).  sr_stream_partial's *frames, sr_stream_stable and the traceback refer to the rows searched; max_frames bounds the rows
+ * received (SR_ELIMIT).  Every check comes before any launch; a call refused by a check changes no utterance, its history included
+ * (a call that fails after its launches -- a HIP error, SR_EINTERNAL -- may leave a slot's device history ahead of the host's count: end
+ * such an utterance).  A VTLN warp
+ * per stream is not part of the pipeline: a stream set's front end is one (possibly warped) front end for all its ids. */
+SR_API int sr_stream_set_projection(sr_stream* s, uint32_t in_dim, uint32_t context, const double* M);
+SR_API int sr_stream_set_transform(sr_stream* s, uint32_t id, const double* W);
+SR_API int sr_stream_push_rows(sr_stream* s, uint32_t n, const uint32_t* ids, const float* feats, const uint64_t* frame_off, int finish,
+                               float* out_feats /*optional*/, uint64_t cap_rows, uint64_t* out_frame_off /*[n+1], optional*/);
+SR_API int sr_bigram_stream_set_projection(struct sr_bigram_stream* s, uint32_t in_dim, uint32_t context, const double* M);
+SR_API int sr_bigram_stream_set_transform(struct sr_bigram_stream* s, uint32_t id, const double* W);
+SR_API int sr_bigram_stream_push_rows(struct sr_bigram_stream* s, uint32_t n, const uint32_t* ids, const float* feats,
+                                      const uint64_t* frame_off, int finish, float* out_feats /*optional*/, uint64_t cap_rows,
+                                      uint64_t* out_frame_off /*[n+1], optional*/);
 /* the features of any resident corpus -- uploaded, transformed, projected or a front end's -- back to the host, out [frames x dim of the
  * corpus's model]; an asynchronous upload is waited for first */
 SR_API int sr_corpus_download(sr_corpus* c, float* out);

@@ -55,6 +55,8 @@ SYMBOLS = [
     "sr_bigram_stream_destroy",
     "sr_stream_set_frontend", "sr_stream_push_audio", "sr_stream_finish_audio",
     "sr_bigram_stream_set_frontend", "sr_bigram_stream_push_audio", "sr_bigram_stream_finish_audio",
+    "sr_stream_set_projection", "sr_stream_set_transform", "sr_stream_push_rows",
+    "sr_bigram_stream_set_projection", "sr_bigram_stream_set_transform", "sr_bigram_stream_push_rows",
     "sr_probe_fp16_denormals", "sr_probe_fp16_accumulation", "sr_prefilter_masks", "sr_prefilter_range_frames",
     "sr_refine_masks", "sr_refine_geometry",
     "sr_gather_words", "sr_recognize_corpus_scores", "sr_recognize_bigram_corpus_scores", "sr_bigram_route",
@@ -240,6 +242,9 @@ def lib():
             getattr(L, fn + "_set_frontend").argtypes = [vp, vp]
             getattr(L, fn + "_push_audio").argtypes = [vp, u32, vp, vp, vp, vp, u64, vp]
             getattr(L, fn + "_finish_audio").argtypes = [vp, u32, vp, vp, u64, vp]
+            getattr(L, fn + "_set_projection").argtypes = [vp, u32, u32, vp]
+            getattr(L, fn + "_set_transform").argtypes = [vp, u32, vp]
+            getattr(L, fn + "_push_rows").argtypes = [vp, u32, vp, vp, vp, i32, vp, u64, vp]
         L.sr_probe_fp16_denormals.argtypes = [i32, C.POINTER(i32)]
         L.sr_probe_fp16_accumulation.argtypes = [i32, C.POINTER(i32), C.POINTER(dbl)]
         L.sr_prefilter_masks.argtypes = [vp, vp, u64, i32, C.POINTER(u32), vp, u64]
@@ -560,7 +565,9 @@ class _StreamSet:
         self.max_frames = int(max_frames)
         self.frames = {}  # frames pushed (searched, for an id fed as audio) per open id
         self.samples = {}  # samples pushed per open id fed as audio
+        self.received = {}  # input rows pushed per open id fed with push_rows
         self.frontend = None
+        self.in_dim, self.context = None, 0  # the projection's (set_projection)
         self.h = C.c_void_p()
         _check(getattr(lib(), self._fn + "_open")(model.h, net.h, C.byref(params), max_streams, max_frames, C.byref(self.h)))
 
@@ -570,17 +577,79 @@ class _StreamSet:
         _check(getattr(lib(), self._fn + "_begin")(self.h, C.byref(i)))
         self.frames[i.value] = 0
         self.samples.pop(i.value, None)
+        self.received[i.value] = 0
         return i.value
 
     def push(self, frames):
-        """frames: {id: float32 [k x dim]} -> one scoring and one search launch for all of them"""
+        """frames: {id: float32 [k x dim]} (in_dim columns with a projection) -> one scoring and one search launch for all of them"""
         ids = np.ascontiguousarray(list(frames.keys()), dtype=np.uint32)
-        parts = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1, self.model.dim) for f in frames.values()]
+        cols = self.model.dim if self.in_dim is None else self.in_dim
+        parts = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1, cols) for f in frames.values()]
         off = np.concatenate([[0], np.cumsum([len(f) for f in parts])]).astype(np.uint64)
-        feats = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, self.model.dim), np.float32))
+        feats = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, cols), np.float32))
         _check(getattr(lib(), self._fn + "_push")(self.h, len(ids), _ptr(ids), _ptr(feats) if len(feats) else None, _ptr(off)))
-        for i, f in zip(ids, parts):
-            self.frames[int(i)] += len(f)
+        for i, f in zip(ids, parts):  # (with a projection the search runs `context` rows behind the rows received)
+            self.received[int(i)] = self.received.get(int(i), 0) + len(f)
+            self.frames[int(i)] = self._rows_out(self.received[int(i)], False)
+
+    def set_projection(self, in_dim, context, M):
+        """sr_stream_set_projection: rows of in_dim columns are spliced with `context` neighbours on either side and projected by
+        M [dim x ((2 context + 1) in_dim + 1)] (float64; None detaches) on the device before they are scored; only while no id is open."""
+        if M is None:
+            _check(getattr(lib(), self._fn + "_set_projection")(self.h, 0, 0, None))
+            self.in_dim, self.context = None, 0
+            return
+        M = np.ascontiguousarray(M, dtype=np.float64)
+        if M.shape != (self.model.dim, (2 * int(context) + 1) * int(in_dim) + 1):
+            raise ValueError(f"M must be [{self.model.dim} x {(2 * int(context) + 1) * int(in_dim) + 1}], got {M.shape}")
+        _check(getattr(lib(), self._fn + "_set_projection")(self.h, int(in_dim), int(context), _ptr(M)))
+        self.in_dim, self.context = int(in_dim), int(context)
+
+    def set_transform(self, id, W):
+        """sr_stream_set_transform: the utterance's affine transform W [dim x (dim + 1)] = [A b] (float64; None clears it), applied on
+        the device after the projection; between begin and the id's first push."""
+        if W is not None:
+            W = np.ascontiguousarray(W, dtype=np.float64)
+            if W.shape != (self.model.dim, self.model.dim + 1):
+                raise ValueError(f"W must be [{self.model.dim} x {self.model.dim + 1}], got {W.shape}")
+        _check(getattr(lib(), self._fn + "_set_transform")(self.h, int(id), None if W is None else _ptr(W)))
+
+    def _rows_out(self, received, finished):
+        """the rows searched of an utterance that has received so many input rows (sr_stream_set_projection's delay)"""
+        return received if finished else max(received - self.context, 0)
+
+    def _push_rows(self, frames, finish, feats):
+        cols = self.model.dim if self.in_dim is None else self.in_dim
+        ids = np.ascontiguousarray(list(frames.keys()), dtype=np.uint32)
+        parts = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1, cols) for f in frames.values()]
+        n = len(ids)
+        off = np.concatenate([[0], np.cumsum([len(f) for f in parts])]).astype(np.uint64)
+        x = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, cols), np.float32))
+        ooff, out, cap = np.zeros(n + 1, np.uint64), None, 0
+        if feats:
+            cap = sum(self._rows_out(self.received[int(i)] + len(f), finish) - self.frames[int(i)] for i, f in zip(ids, parts))
+            out = np.zeros((max(cap, 1), self.model.dim), np.float32)
+        _check(getattr(lib(), self._fn + "_push_rows")(self.h, n, _ptr(ids), _ptr(x) if len(x) else None, _ptr(off), int(finish),
+                                                        None if out is None else _ptr(out), cap, _ptr(ooff)))
+        for j, (i, f) in enumerate(zip(ids, parts)):
+            self.received[int(i)] += len(f)
+            self.frames[int(i)] += int(ooff[j + 1] - ooff[j])
+        if feats:
+            return {int(i): out[int(ooff[j]):int(ooff[j + 1])].copy() for j, i in enumerate(ids)}
+        return {}
+
+    def push_rows(self, frames, finish=False, feats=False):
+        """sr_stream_push_rows.  frames: {id: float32 [k x in_dim]} (dim columns without a projection); finish: True -- every named id is
+        finished after its rows -- or a list of ids to finish (with or without rows in `frames`; they go in a call of their own).
+        feats=True -> {id: float32 [rows x dim]}, the rows this call searched, in the model's space."""
+        if finish is True or finish is False:
+            got = self._push_rows(frames, bool(finish), feats)
+        else:
+            last = [int(i) for i in finish]
+            cols = self.model.dim if self.in_dim is None else self.in_dim
+            got = self._push_rows({i: f for i, f in frames.items() if int(i) not in last}, False, feats)
+            got.update(self._push_rows({i: frames.get(i, np.zeros((0, cols), np.float32)) for i in last}, True, feats))
+        return got if feats else None
 
     def set_frontend(self, fe):
         """sr_stream_set_frontend: the front end push_audio runs (None detaches); only while no id is open.  Close it after the set."""
@@ -596,8 +665,9 @@ class _StreamSet:
             fe, step = self.frontend, self.frontend.post.deriv_step
             for j, i in enumerate(ids):
                 before = self.samples.get(int(i), 0)
-                s0 = fe.frames(before)
-                cap += s0 - max(s0 - step, 0) if new_samples is None else max(fe.frames(before + new_samples[j]) - step, 0) - max(s0 - step, 0)
+                s0 = fe.frames(before)  # (the front end's rows are the input rows of the projection, if there is one)
+                rows_in = s0 if new_samples is None else max(fe.frames(before + new_samples[j]) - step, 0)
+                cap += self._rows_out(rows_in, new_samples is None) - self.frames.get(int(i), 0)
         if feats:
             out = np.zeros((max(cap, 1), self.model.dim), np.float32)
         _check(call(_ptr(out), cap, _ptr(off)))

@@ -17,6 +17,7 @@
 #include "host_util.h"
 #include "kernels.h"
 #include "stream_audio_plan.h"
+#include "stream_pipeline_plan.h"
 #include "vtln_tables.h"
 
 namespace srhost {
@@ -367,6 +368,23 @@ struct StreamAudio {
   DevBuf<srgpu::StreamFrontendJob> jobs;
 };
 
+// The pipeline of a stream set (sr_stream_set_projection, _set_transform, _push_rows and the bigram twins): the projection, the
+// slots' transforms, the host carry of every utterance (stream_pipeline_plan.h) and the history stream_pipeline_kernel keeps per slot.
+struct StreamPipeline {
+  bool projection = false;
+  uint32_t in_dim = 0, context = 0;        // D, c (0, 0 without a projection)
+  DevBuf<double> M;                        // [p][(2c + 1) D + 1]
+  DevBuf<float> hist;                      // [max_streams][2c][D]
+  DevBuf<double> W;                        // [max_streams][p][p + 1], allocated by the first sr_stream_set_transform
+  std::vector<uint8_t> has_w;              // [max_streams] the slot's utterance has a transform
+  std::vector<srplan::PipelineCarry> carry;  // [max_streams]
+  // per push, sized by the largest push so far
+  DevBuf<float> in;
+  DevBuf<srgpu::StreamPipelineJob> jobs;
+  void open(uint32_t max_streams) { has_w.assign(max_streams, 0); carry.assign(max_streams, srplan::PipelineCarry()); }
+  void begin(uint32_t slot) { has_w[slot] = 0; carry[slot] = srplan::PipelineCarry(); }
+};
+
 // A set of concurrently open utterances on one (model, lexicon) (sr_stream_*, srgpu_api.cpp).  The device state of slot i's
 // utterance (decode_stream_kernel) lives in the per-slot buffers below.
 struct sr_stream {
@@ -375,6 +393,7 @@ struct sr_stream {
   sr_search_params params{};
   StreamSlots slots;
   StreamAudio audio;
+  StreamPipeline pipe;
   // per slot, device
   DevBuf<unsigned char> ws;         // decode_big_workspace(P) each
   DevBuf<srgpu::StreamState> state;
@@ -400,6 +419,7 @@ struct sr_bigram_stream {
   sr_bigram_params params{};
   StreamSlots slots;
   StreamAudio audio;
+  StreamPipeline pipe;
   std::vector<srgpu::BigramStreamState> host_state;  // [max_streams] as of the slot's last push
   std::vector<uint8_t> failed;      // [max_streams] a push flagged the slot (SR_EINTERNAL until it ends)
   // per slot, device

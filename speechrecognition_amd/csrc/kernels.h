@@ -1049,4 +1049,27 @@ struct StreamFrontendArgs {
 };
 hipError_t launch_stream_frontend(const StreamFrontendArgs& a, uint32_t n_jobs, hipStream_t stream);
 
+// The pipeline of a stream set (stream_pipeline.hip; sr_stream_set_projection, sr_stream_set_transform): stream_pipeline_kernel, one
+// workgroup per pushed utterance, splices and projects the rows that became ready and applies the slot's transform.  A job: the
+// utterance had R input rows before the push and gains k, which begin at row in0 of `in`; it emits `rows` rows from row0 of the
+// utterance into row out0 of `out`, clamped by R + k (before the finish no emitted row reaches that far); has_w: the slot's W applies.
+struct StreamPipelineJob {
+  uint32_t slot, has_w, R, k;
+  uint32_t row0, rows;
+  uint64_t in0, out0;
+};
+struct StreamPipelineArgs {
+  const StreamPipelineJob* jobs;
+  uint32_t in_dim, context, dim;  // D, c, p; without a projection (M == nullptr) in_dim == dim and context == 0
+  const double* M;                // [p][(2c + 1) D + 1] or nullptr
+  const double* W;                // [slots][p][p + 1] or nullptr (no slot has a transform)
+  uint32_t w_doubles, y_floats;   // the kernel's LDS parts: p (p + 1) with W, stream_pipeline_group_rows() x p with M and W, else 0
+  float* hist;                    // [slots][2c][D]: input row g of a slot at ring position g mod 2c
+  const float* in;                // the push's new input rows [.][D]
+  float* out;                     // the push's rows [.][p], what the scoring reads
+};
+uint32_t stream_pipeline_group_rows();
+size_t stream_pipeline_lds_bytes(uint32_t in_dim, uint32_t context, uint32_t dim, bool projection, bool transforms);
+hipError_t launch_stream_pipeline(const StreamPipelineArgs& a, uint32_t n_jobs, hipStream_t stream);
+
 }  // namespace srgpu

@@ -32,6 +32,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "splice_clamp.h"
 
 namespace srgpu {
 
@@ -51,10 +52,7 @@ uint32_t lda_block() { return kBlock; }
 
 // x[clamp(t + o - c)][j] of frame t, whose utterance is [lo, hi)
 __device__ inline float lda_splice(const float* feats, uint32_t D, uint32_t c, uint32_t t, uint32_t lo, uint32_t hi, uint32_t o, uint32_t j) {
-  int64_t s = (int64_t)t + (int64_t)o - (int64_t)c;
-  s = s < (int64_t)lo ? (int64_t)lo : s;
-  s = s > (int64_t)hi - 1 ? (int64_t)hi - 1 : s;
-  return feats[(uint64_t)s * D + j];
+  return feats[(uint64_t)srplan::splice_frame(t, o, c, lo, hi) * D + j];
 }
 
 // grid (segments of the round, blocks I <= J)

@@ -714,29 +714,6 @@ namespace {  // sr_stream_*, sr_bigram_stream_*
 // an entry of a push with frames: its stream slot, the frames searched before the push, the frames in it, its first frame's row in
 // the push's features
 struct PushEntry { uint32_t slot; uint64_t t0, k, row0; };
-// checks a push against the open utterances -- every id open and named once, frame_off ascending from 0, no utterance past
-// max_frames, none of them fed as audio -- and lists its entries with frames (none for an empty push)
-int check_push(const StreamSlots& sl, const StreamAudio& au, uint32_t n, const uint32_t* ids, const uint64_t* frame_off,
-               std::vector<PushEntry>* out) {
-  if (n == 0) return SR_OK;
-  if (!ids || !frame_off) return fail(SR_EINVAL, "null argument");
-  if (frame_off[0] != 0) return fail(SR_EINVAL, "frame_off[0] must be 0");
-  std::vector<uint8_t> seen(sl.max_streams, 0);
-  for (uint32_t i = 0; i < n; i++) {
-    const int64_t slot = sl.find(ids[i]);
-    if (slot < 0) return fail(SR_EINVAL, "push entry %u: stream id %u is not open", i, ids[i]);
-    if (seen[slot]) return fail(SR_EINVAL, "push entry %u: stream id %u appears twice in one push", i, ids[i]);
-    seen[slot] = 1;
-    if (au.kind[slot] >= kStreamAudio) return fail(SR_EINVAL, "push entry %u: stream id %u is fed as audio; it takes no feature rows", i, ids[i]);
-    if (frame_off[i + 1] < frame_off[i]) return fail(SR_EINVAL, "frame_off is not ascending at entry %u", i);
-    const uint64_t k = frame_off[i + 1] - frame_off[i];
-    if (k > sl.max_frames - sl.frames[slot])
-      return fail(SR_ELIMIT, "stream id %u: %llu + %llu frames exceed max_frames %llu", ids[i], (unsigned long long)sl.frames[slot],
-                  (unsigned long long)k, (unsigned long long)sl.max_frames);
-    if (k) out->push_back({(uint32_t)slot, sl.frames[slot], k, frame_off[i]});
-  }
-  return SR_OK;
-}
 // A push's pass: its F frames and its jobs staged on the device, then one chunk of run_chunks -- the frames scored into m->scores[0],
 // search(chunk, table, stream) enqueuing the push's search.  feats == nullptr: work queued on the scoring stream has the frames in
 // d_feats already (the audio pushes).  (Every call synchronises before it returns: the buffer is free.)
@@ -876,19 +853,21 @@ int stream_run(sr_bigram_stream* s, const std::vector<PushEntry>& entries, const
   return SR_OK;
 }
 
-// the ids of a feature push take rows from now on
-void mark_rows(StreamAudio& au, const StreamSlots& sl, uint32_t n, const uint32_t* ids) {
-  for (uint32_t i = 0; i < n; i++) au.kind[sl.find(ids[i])] = kStreamRows;
-}
-
-// sr_stream_set_frontend and its bigram twin
+// sr_stream_set_frontend and its bigram twin.  With a projection attached the front end feeds the pipeline: any model of the
+// projection's input dimension on the set's device will do.
 template <class Set>
 int set_frontend(Set* s, sr_frontend* fe) {
   if (!s) return fail(SR_EINVAL, "null stream set");
   for (uint32_t i = 0; i < s->slots.max_streams; i++)
     if (s->slots.open[i]) return fail(SR_EINVAL, "stream id %u is open: the front end changes only while none is", s->slots.id[i]);
   if (!fe) { s->audio.fe = nullptr; return SR_OK; }
-  if (fe->model != s->model) return fail(SR_EINVAL, "the front end does not belong to the stream set's model");
+  if (!s->pipe.projection) {
+    if (fe->model != s->model) return fail(SR_EINVAL, "the front end does not belong to the stream set's model");
+  } else {
+    if (!fe->model || fe->model->device != s->model->device) return fail(SR_EINVAL, "the front end is not on the stream set's device");
+    if (fe->model->dim != s->pipe.in_dim)
+      return fail(SR_EINVAL, "the front end's rows have %u columns, the projection takes %u", fe->model->dim, s->pipe.in_dim);
+  }
   if (!fe->has_mfcc) return fail(SR_EINVAL, "this front end was made without an MFCC stage: it takes cepstra only");
   int rc = check_model(s->model);
   if (rc) return rc;
@@ -897,9 +876,206 @@ int set_frontend(Set* s, sr_frontend* fe) {
   return SR_OK;
 }
 
+// sr_stream_set_projection and its bigram twin
+template <class Set>
+int set_projection(Set* s, uint32_t in_dim, uint32_t context, const double* M) {
+  if (!s) return fail(SR_EINVAL, "null stream set");
+  for (uint32_t i = 0; i < s->slots.max_streams; i++)
+    if (s->slots.open[i]) return fail(SR_EINVAL, "stream id %u is open: the projection changes only while none is", s->slots.id[i]);
+  StreamPipeline& pl = s->pipe;
+  const sr_frontend* fe = s->audio.fe;
+  if (!M) {
+    if (fe && fe->model != s->model)
+      return fail(SR_EINVAL, "the attached front end does not belong to the stream set's model: detach it before the projection");
+    pl.projection = false; pl.in_dim = 0; pl.context = 0;
+    pl.M.release(); pl.hist.release();
+    return SR_OK;
+  }
+  if (in_dim == 0) return fail(SR_EINVAL, "in_dim must be positive");
+  const uint64_t E = (2 * (uint64_t)context + 1) * in_dim;
+  if (E > 512) return fail(SR_ELIMIT, "(2 context + 1) in_dim = %llu exceeds 512 (sr_corpus_splice_transform's limit)", (unsigned long long)E);
+  if (fe && fe->model->dim != in_dim)
+    return fail(SR_EINVAL, "the attached front end's rows have %u columns, not in_dim = %u", fe->model->dim, in_dim);
+  sr_model* m = s->model;
+  if (stream_pipeline_lds_bytes(in_dim, context, m->dim, true, m->dim <= 63) > 65536)
+    return fail(SR_ELIMIT, "the pipeline's LDS need exceeds 64 KB");
+  int rc = check_model(m);
+  if (rc) return rc;
+  DevBuf<double> dM;
+  DevBuf<float> hist;
+  HIP_TRY(dM.upload(M, (size_t)m->dim * (E + 1)));
+  HIP_TRY(hist.ensure((size_t)s->slots.max_streams * 2 * context * in_dim));
+  pl.M.swap(dM); pl.hist.swap(hist);
+  pl.projection = true; pl.in_dim = in_dim; pl.context = context;
+  return SR_OK;
+}
+
+// sr_stream_set_transform and its bigram twin
+template <class Set>
+int set_transform(Set* s, uint32_t id, const double* W) {
+  if (!s) return fail(SR_EINVAL, "null stream set");
+  const int64_t slot = s->slots.find(id);
+  if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
+  if (s->audio.kind[slot] != kStreamFresh)
+    return fail(SR_EINVAL, "stream id %u has been pushed to: its transform is set between begin and the first push", id);
+  StreamPipeline& pl = s->pipe;
+  if (!W) { pl.has_w[slot] = 0; return SR_OK; }
+  sr_model* m = s->model;
+  const size_t p = m->dim, n = p * (p + 1);
+  if (p > 63) return fail(SR_ELIMIT, "dim %u: the transform's kernel keeps W in the LDS (max 63, as sr_corpus_transform)", m->dim);
+  int rc = check_model(m);
+  if (rc) return rc;
+  HIP_TRY(pl.W.ensure((size_t)s->slots.max_streams * n));
+  HIP_TRY(hipMemcpy(pl.W.p + (size_t)slot * n, W, sizeof(double) * n, hipMemcpyHostToDevice));
+  pl.has_w[slot] = 1;
+  return SR_OK;
+}
+
+// The pipeline's part of a push over the ids in slots[]: entry i gains k[i] input rows (finishing: none follow).  plan_pipeline: the
+// steps of stream_pipeline_plan.h, where the rows they emit go in the push's output (out_off) and the entries to search.  The
+// pipeline is active for a push when the set has a projection or one of the named utterances a transform; otherwise the input rows
+// are the rows searched and no kernel of it runs.
+struct PipelinePush {
+  std::vector<srplan::PipelineStep> steps;
+  std::vector<uint64_t> out_off;
+  std::vector<PushEntry> entries;
+  std::vector<StreamPipelineJob> jobs;  // (uploaded asynchronously: alive until the caller has synchronised)
+  bool active = false;
+};
+template <class Set>
+void plan_pipeline(const Set* s, const std::vector<uint32_t>& slots, const std::vector<uint64_t>& k, bool finishing, PipelinePush* pp) {
+  const StreamPipeline& pl = s->pipe;
+  const size_t n = slots.size();
+  pp->steps.resize(n);
+  pp->out_off.assign(n + 1, 0);
+  pp->active = pl.projection;
+  for (size_t i = 0; i < n; i++) {
+    pp->steps[i] = srplan::plan_pipeline_step(pl.context, pl.carry[slots[i]], k[i], finishing);
+    pp->out_off[i + 1] = pp->out_off[i] + pp->steps[i].rows;
+    if (pp->steps[i].rows) pp->entries.push_back({slots[i], pp->steps[i].row0, pp->steps[i].rows, pp->out_off[i]});
+    if (pl.has_w[slots[i]]) pp->active = true;
+  }
+}
+// one launch of stream_pipeline_kernel on the scoring stream: entry i's new input rows begin at row in_off[i] of pl.in (uploaded or
+// written by work queued before); the rows that became ready land in s->feats.  The caller synchronises the stream.
+template <class Set>
+int launch_pipeline(Set* s, const std::vector<uint32_t>& slots, PipelinePush& pp, const uint64_t* in_off) {
+  StreamPipeline& pl = s->pipe;
+  sr_model* m = s->model;
+  std::vector<StreamPipelineJob>& jobs = pp.jobs;
+  for (size_t i = 0; i < slots.size(); i++) {
+    const srplan::PipelineStep& st = pp.steps[i];
+    if (!st.rows_in && !st.rows) continue;
+    const srplan::PipelineCarry& c = pl.carry[slots[i]];
+    jobs.push_back({slots[i], pl.has_w[slots[i]], (uint32_t)c.received, (uint32_t)st.rows_in, (uint32_t)st.row0, (uint32_t)st.rows,
+                    in_off ? in_off[i] : 0, pp.out_off[i]});
+  }
+  if (jobs.empty()) return SR_OK;
+  HIP_TRY(pl.jobs.ensure(jobs.size()));
+  HIP_TRY(s->feats.ensure((size_t)pp.out_off.back() * m->dim));
+  HIP_TRY(hipMemcpyAsync(pl.jobs.p, jobs.data(), sizeof(StreamPipelineJob) * jobs.size(), hipMemcpyHostToDevice, m->s_gmm));
+  StreamPipelineArgs a{};
+  a.jobs = pl.jobs.p;
+  a.in_dim = pl.projection ? pl.in_dim : m->dim; a.context = pl.context; a.dim = m->dim;
+  a.M = pl.projection ? pl.M.p : nullptr;
+  a.W = pl.W.p;
+  a.w_doubles = pl.W.p ? m->dim * (m->dim + 1) : 0;
+  a.y_floats = pl.projection && pl.W.p ? stream_pipeline_group_rows() * m->dim : 0;
+  a.hist = pl.hist.p; a.in = pl.in.p; a.out = s->feats.p;
+  EventPair ep{};
+  int rc = prof_begin(m, m->s_gmm, 1, &ep);
+  if (rc) return rc;
+  HIP_TRY(launch_stream_pipeline(a, (uint32_t)jobs.size(), m->s_gmm));
+  return prof_end(m, m->s_gmm, &ep);
+}
+template <class Set>
+void commit_pipeline(Set* s, const std::vector<uint32_t>& slots, const PipelinePush& pp) {
+  for (size_t i = 0; i < slots.size(); i++) s->pipe.carry[slots[i]] = pp.steps[i].next;
+}
+
+// sr_stream_push_rows and its bigram twin (sr_stream_push is this without a finish and without rows back): all checks, the
+// pipeline's steps, then -- with an active pipeline -- the rows uploaded as the pipeline's input and its launch, and the set's own
+// scoring and search on the rows that became ready.  Nothing of the set changes before the launches have succeeded.
+template <class Set>
+int push_rows(Set* s, uint32_t n, const uint32_t* ids, const float* feats, const uint64_t* frame_off, bool finishing, float* out_feats,
+              uint64_t cap_rows, uint64_t* out_frame_off) {
+  if (!s) return fail(SR_EINVAL, "null stream set");
+  if (n == 0) {
+    if (out_frame_off) out_frame_off[0] = 0;
+    return SR_OK;
+  }
+  if (!ids || (!finishing && !frame_off)) return fail(SR_EINVAL, "null argument");
+  if (frame_off && frame_off[0] != 0) return fail(SR_EINVAL, "frame_off[0] must be 0");
+  StreamSlots& sl = s->slots;
+  StreamPipeline& pl = s->pipe;
+  sr_model* m = s->model;
+  std::vector<uint8_t> seen(sl.max_streams, 0);
+  std::vector<uint32_t> slots(n);
+  std::vector<uint64_t> k(n, 0);
+  for (uint32_t i = 0; i < n; i++) {
+    const int64_t slot = sl.find(ids[i]);
+    if (slot < 0) return fail(SR_EINVAL, "push entry %u: stream id %u is not open", i, ids[i]);
+    if (seen[slot]) return fail(SR_EINVAL, "push entry %u: stream id %u appears twice in one push", i, ids[i]);
+    seen[slot] = 1;
+    slots[i] = (uint32_t)slot;
+    if (s->audio.kind[slot] >= kStreamAudio) return fail(SR_EINVAL, "push entry %u: stream id %u is fed as audio; it takes no feature rows", i, ids[i]);
+    if (pl.carry[slot].finished) return fail(SR_EINVAL, "push entry %u: stream id %u is finished; it takes no more rows", i, ids[i]);
+    if (frame_off) {
+      if (frame_off[i + 1] < frame_off[i]) return fail(SR_EINVAL, "frame_off is not ascending at entry %u", i);
+      k[i] = frame_off[i + 1] - frame_off[i];
+    }
+    const uint64_t got = pl.carry[slot].received;
+    if (k[i] > sl.max_frames - got)
+      return fail(SR_ELIMIT, "stream id %u: %llu + %llu frames exceed max_frames %llu", ids[i], (unsigned long long)got,
+                  (unsigned long long)k[i], (unsigned long long)sl.max_frames);
+  }
+  PipelinePush pp;
+  plan_pipeline(s, slots, k, finishing, &pp);
+  const uint64_t F = frame_off ? frame_off[n] : 0, R = pp.out_off[n];
+  if (out_feats && cap_rows < R) {
+    if (out_frame_off) out_frame_off[n] = R;
+    return fail(SR_EINVAL, "this push readies %llu rows, out_feats holds %llu", (unsigned long long)R, (unsigned long long)cap_rows);
+  }
+  int rc = stream_precheck(s, pp.entries);
+  if (rc) return rc;
+  if (F && !feats) return fail(SR_EINVAL, "null feats");
+  if (!pp.active) {  // (no delay: the rows pushed are the rows searched)
+    if (R) {
+      if ((rc = check_model(m)) || (rc = stream_run(s, pp.entries, feats, R))) return rc;
+      if (out_feats) memcpy(out_feats, feats, sizeof(float) * (size_t)R * m->dim);
+    }
+  } else if (F || R) {
+    if ((rc = check_model(m))) return rc;
+    const uint32_t D = pl.projection ? pl.in_dim : m->dim;
+    HIP_TRY(pl.in.ensure((size_t)F * D));
+    if (F) HIP_TRY(hipMemcpyAsync(pl.in.p, feats, sizeof(float) * (size_t)F * D, hipMemcpyHostToDevice, m->s_gmm));
+    if ((rc = launch_pipeline(s, slots, pp, frame_off))) return rc;
+    if (R) rc = stream_run(s, pp.entries, nullptr, R);  // (a push that readies no row launches no scoring and no search)
+    else HIP_TRY(hipStreamSynchronize(m->s_gmm));
+    if (rc) return rc;
+    if (R && out_feats) HIP_TRY(hipMemcpy(out_feats, s->feats.p, sizeof(float) * (size_t)R * m->dim, hipMemcpyDeviceToHost));
+  }
+  commit_pipeline(s, slots, pp);
+  for (uint32_t i = 0; i < n; i++) s->audio.kind[slots[i]] = kStreamRows;
+  if (out_frame_off) memcpy(out_frame_off, pp.out_off.data(), sizeof(uint64_t) * pp.out_off.size());
+  return SR_OK;
+}
+// sr_stream_end's check: rows received and not yet searched keep a row id open
+template <class Set>
+int check_end(const Set* s, uint32_t slot, uint32_t id, const char* finish_audio) {
+  if (s->audio.kind[slot] == kStreamAudio) return fail(SR_EINVAL, "stream id %u is fed as audio and not finished (%s)", id, finish_audio);
+  const srplan::PipelineCarry& c = s->pipe.carry[slot];
+  if (c.received > c.searched)
+    return fail(SR_EINVAL, "stream id %u has %llu rows that wait for their right context: finish it first (sr_stream_push_rows)", id,
+                (unsigned long long)(c.received - c.searched));
+  return SR_OK;
+}
+
 // sr_stream_push_audio / sr_stream_finish_audio and their bigram twins (include/srgpu.h has the definition): the steps of
 // stream_audio_plan.h for every named utterance, all checks, then one launch of stream_frontend_kernel that leaves the ready rows
-// in s->feats, and the set's own scoring and search on them.  Nothing of the set changes before the launches have succeeded.
+// in s->feats, and the set's own scoring and search on them.  With an active pipeline the front end's rows are the pipeline's input
+// instead: its steps are planned on them, its kernel follows the front end's on the same stream, and its rows are the ones searched.
+// Nothing of the set changes before the launches have succeeded.
 template <class Set>
 int push_audio(Set* s, uint32_t n, const uint32_t* ids, const int16_t* samples, const uint64_t* sample_off, bool finishing, float* out_feats,
                uint64_t cap_rows, uint64_t* out_frame_off) {
@@ -920,8 +1096,7 @@ int push_audio(Set* s, uint32_t n, const uint32_t* ids, const int16_t* samples, 
   std::vector<uint8_t> seen(sl.max_streams, 0);
   std::vector<srplan::AudioStep> steps(n);
   std::vector<uint32_t> slots(n);
-  std::vector<uint64_t> row_off((size_t)n + 1, 0);
-  std::vector<PushEntry> entries;
+  std::vector<uint64_t> row_off((size_t)n + 1, 0), rows_in(n, 0);  // (the front end's rows: the pipeline's input)
   for (uint32_t i = 0; i < n; i++) {
     const int64_t slot = sl.find(ids[i]);
     if (slot < 0) return fail(SR_EINVAL, "push entry %u: stream id %u is not open", i, ids[i]);
@@ -942,9 +1117,12 @@ int push_audio(Set* s, uint32_t n, const uint32_t* ids, const int16_t* samples, 
                   (unsigned long long)k, (unsigned long long)sl.max_frames);
     steps[i] = srplan::plan_audio_step(p.window, p.shift, step, c, k ? samples + sample_off[i] : nullptr, k, finishing);
     row_off[i + 1] = row_off[i] + steps[i].rows;
-    if (steps[i].rows) entries.push_back({(uint32_t)slot, sl.frames[slot], steps[i].rows, row_off[i]});
+    rows_in[i] = steps[i].rows;
   }
-  const uint64_t R = row_off[n];
+  PipelinePush pp;
+  plan_pipeline(s, slots, rows_in, finishing, &pp);
+  const std::vector<PushEntry>& entries = pp.entries;
+  const uint64_t R_in = row_off[n], R = pp.out_off[n];
   if (out_feats && cap_rows < R) {
     if (out_frame_off) out_frame_off[n] = R;
     return fail(SR_EINVAL, "this push readies %llu rows, out_feats holds %llu", (unsigned long long)R, (unsigned long long)cap_rows);
@@ -955,6 +1133,7 @@ int push_audio(Set* s, uint32_t n, const uint32_t* ids, const int16_t* samples, 
   std::vector<int16_t> pieces;
   std::vector<StreamFrontendJob> jobs;
   uint64_t stage_rows = 0;
+  bool launched = false;
   for (uint32_t i = 0; i < n; i++) {
     const srplan::AudioStep& st = steps[i];
     if (!st.new_statics && !st.rows) continue;
@@ -974,7 +1153,8 @@ int push_audio(Set* s, uint32_t n, const uint32_t* ids, const int16_t* samples, 
     HIP_TRY(au.samples.ensure(pieces.size()));
     HIP_TRY(au.stage.ensure((size_t)stage_rows * nf));
     HIP_TRY(au.jobs.ensure(jobs.size()));
-    HIP_TRY(s->feats.ensure((size_t)R * m->dim));
+    if (pp.active) HIP_TRY(s->pipe.in.ensure((size_t)R_in * fe->model->dim));
+    else HIP_TRY(s->feats.ensure((size_t)R * m->dim));
     HIP_TRY(hipMemcpyAsync(au.samples.p, pieces.data(), sizeof(int16_t) * pieces.size(), hipMemcpyHostToDevice, m->s_gmm));
     HIP_TRY(hipMemcpyAsync(au.jobs.p, jobs.data(), sizeof(StreamFrontendJob) * jobs.size(), hipMemcpyHostToDevice, m->s_gmm));
     StreamFrontendArgs a{};
@@ -988,21 +1168,27 @@ int push_audio(Set* s, uint32_t n, const uint32_t* ids, const int16_t* samples, 
     a.n_static = nf; a.n_first = fe->post.n_first; a.n_second = fe->post.n_second; a.step = step;
     a.mean = fe->normalise ? fe->mean.p : nullptr; a.stddev = fe->normalise ? fe->stddev.p : nullptr;
     a.energy_max_norm = fe->post.energy_max_norm != 0;
-    a.state = au.state.p; a.stage = au.stage.p; a.out = s->feats.p;
+    a.state = au.state.p; a.stage = au.stage.p; a.out = pp.active ? s->pipe.in.p : s->feats.p;
     EventPair ep{};
     if ((rc = prof_begin(m, m->s_gmm, 1, &ep))) return rc;
     HIP_TRY(launch_stream_frontend(a, (uint32_t)jobs.size(), m->s_gmm));
     if ((rc = prof_end(m, m->s_gmm, &ep))) return rc;
-    if (R) rc = stream_run(s, entries, nullptr, R);  // (a push that readies no row launches no scoring and no search)
-    else HIP_TRY(hipStreamSynchronize(m->s_gmm));
-    if (rc) return rc;
-    if (R && out_feats) HIP_TRY(hipMemcpy(out_feats, s->feats.p, sizeof(float) * (size_t)R * m->dim, hipMemcpyDeviceToHost));
+    launched = true;
   }
+  if (pp.active) {
+    if ((rc = launch_pipeline(s, slots, pp, row_off.data()))) return rc;
+    launched = launched || !pp.jobs.empty();
+  }
+  if (R) rc = stream_run(s, entries, nullptr, R);  // (a push that readies no row launches no scoring and no search)
+  else if (launched) HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  if (rc) return rc;
+  if (R && out_feats) HIP_TRY(hipMemcpy(out_feats, s->feats.p, sizeof(float) * (size_t)R * m->dim, hipMemcpyDeviceToHost));
+  commit_pipeline(s, slots, pp);
   for (uint32_t i = 0; i < n; i++) {
     au.carry[slots[i]] = std::move(steps[i].next);
     au.kind[slots[i]] = finishing ? kStreamAudioFinished : kStreamAudio;
   }
-  if (out_frame_off) memcpy(out_frame_off, row_off.data(), sizeof(uint64_t) * row_off.size());
+  if (out_frame_off) memcpy(out_frame_off, pp.out_off.data(), sizeof(uint64_t) * pp.out_off.size());
   return SR_OK;
 }
 }  // namespace
@@ -4991,6 +5177,7 @@ int sr_stream_open(sr_model* m, sr_lexicon* l, const sr_search_params* p, uint32
   s->model = m; s->lex = l; s->params = *p; s->slots = StreamSlots(max_streams, max_frames);
   s->commit_fresh.assign(max_streams, 1);
   s->audio.kind.assign(max_streams, kStreamFresh); s->audio.carry.resize(max_streams);
+  s->pipe.open(max_streams);
   const size_t S = max_streams;
   HIP_TRY(s->ws.ensure(S * decode_big_workspace(l->net.n_slots)));
   HIP_TRY(s->state.ensure(S));
@@ -5011,23 +5198,23 @@ int sr_stream_begin(sr_stream* s, uint32_t* id) {
   const uint32_t slot = *id % s->slots.max_streams;
   s->commit_fresh[slot] = 1;  // ... and the first sr_stream_stable from commit point 0
   s->audio.kind[slot] = kStreamFresh; s->audio.carry[slot] = srplan::AudioCarry();
+  s->pipe.begin(slot);
   return SR_OK;
   });
 }
 
 int sr_stream_push(sr_stream* s, uint32_t n, const uint32_t* ids, const float* feats, const uint64_t* frame_off) {
-  return guarded(__func__, [&]() -> int {
-  if (!s) return fail(SR_EINVAL, "null stream set");
-  std::vector<PushEntry> entries;
-  int rc = check_push(s->slots, s->audio, n, ids, frame_off, &entries);
-  if (rc) return rc;
-  if (!entries.empty()) {
-    if (!feats) return fail(SR_EINVAL, "null feats");
-    if ((rc = check_model(s->model)) || (rc = stream_run(s, entries, feats, frame_off[n]))) return rc;
-  }
-  mark_rows(s->audio, s->slots, n, ids);
-  return SR_OK;
-  });
+  return guarded(__func__, [&]() -> int { return push_rows(s, n, ids, feats, frame_off, false, nullptr, 0, nullptr); });
+}
+int sr_stream_push_rows(sr_stream* s, uint32_t n, const uint32_t* ids, const float* feats, const uint64_t* frame_off, int finish,
+                        float* out_feats, uint64_t cap_rows, uint64_t* out_frame_off) {
+  return guarded(__func__, [&]() -> int { return push_rows(s, n, ids, feats, frame_off, finish != 0, out_feats, cap_rows, out_frame_off); });
+}
+int sr_stream_set_projection(sr_stream* s, uint32_t in_dim, uint32_t context, const double* M) {
+  return guarded(__func__, [&]() -> int { return set_projection(s, in_dim, context, M); });
+}
+int sr_stream_set_transform(sr_stream* s, uint32_t id, const double* W) {
+  return guarded(__func__, [&]() -> int { return set_transform(s, id, W); });
 }
 
 int sr_stream_set_frontend(sr_stream* s, sr_frontend* fe) {
@@ -5059,9 +5246,8 @@ int sr_stream_end(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_t cap, 
   if (!s || !count || (!out_words && cap)) return fail(SR_EINVAL, "null argument");
   const int64_t slot = s->slots.find(id);
   if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
-  if (s->audio.kind[slot] == kStreamAudio) return fail(SR_EINVAL, "stream id %u is fed as audio and not finished (sr_stream_finish_audio)", id);
-  int rc = check_model(s->model);
-  if (rc) return rc;
+  int rc = check_end(s, (uint32_t)slot, id, "sr_stream_finish_audio");
+  if (rc || (rc = check_model(s->model))) return rc;
   rc = stream_words(s, (uint32_t)slot, id, out_words, cap, count);
   if (rc == SR_EINVAL) return rc;  // too small a buffer: the utterance stays open
   const uint64_t T = s->slots.frames[slot];
@@ -5240,6 +5426,7 @@ int sr_bigram_stream_open(sr_model* m, sr_bigram* b, const sr_bigram_params* p, 
   s->host_state.assign(max_streams, BigramStreamState{}); s->failed.assign(max_streams, 0);
   s->commit_fresh.assign(max_streams, 1);
   s->audio.kind.assign(max_streams, kStreamFresh); s->audio.carry.resize(max_streams);
+  s->pipe.open(max_streams);
   const size_t S = max_streams, W = b->net.n_words;
   HIP_TRY(s->gs_ws.ensure(S * bigram_gs_ws_words(b->net.n_words, b->net.n_positions)));
   HIP_TRY(s->we_slot.ensure(S * 4 * W));
@@ -5267,23 +5454,23 @@ int sr_bigram_stream_begin(sr_bigram_stream* s, uint32_t* id) {
   s->failed[slot] = 0;
   s->commit_fresh[slot] = 1;  // the first sr_bigram_stream_stable starts from the start entry
   s->audio.kind[slot] = kStreamFresh; s->audio.carry[slot] = srplan::AudioCarry();
+  s->pipe.begin(slot);
   return SR_OK;
   });
 }
 
 int sr_bigram_stream_push(sr_bigram_stream* s, uint32_t n, const uint32_t* ids, const float* feats, const uint64_t* frame_off) {
-  return guarded(__func__, [&]() -> int {
-  if (!s) return fail(SR_EINVAL, "null stream set");
-  std::vector<PushEntry> entries;
-  int rc = check_push(s->slots, s->audio, n, ids, frame_off, &entries);
-  if (rc || (rc = stream_precheck(s, entries))) return rc;
-  if (!entries.empty()) {
-    if (!feats) return fail(SR_EINVAL, "null feats");
-    if ((rc = check_model(s->model)) || (rc = stream_run(s, entries, feats, frame_off[n]))) return rc;
-  }
-  mark_rows(s->audio, s->slots, n, ids);
-  return SR_OK;
-  });
+  return guarded(__func__, [&]() -> int { return push_rows(s, n, ids, feats, frame_off, false, nullptr, 0, nullptr); });
+}
+int sr_bigram_stream_push_rows(sr_bigram_stream* s, uint32_t n, const uint32_t* ids, const float* feats, const uint64_t* frame_off, int finish,
+                               float* out_feats, uint64_t cap_rows, uint64_t* out_frame_off) {
+  return guarded(__func__, [&]() -> int { return push_rows(s, n, ids, feats, frame_off, finish != 0, out_feats, cap_rows, out_frame_off); });
+}
+int sr_bigram_stream_set_projection(sr_bigram_stream* s, uint32_t in_dim, uint32_t context, const double* M) {
+  return guarded(__func__, [&]() -> int { return set_projection(s, in_dim, context, M); });
+}
+int sr_bigram_stream_set_transform(sr_bigram_stream* s, uint32_t id, const double* W) {
+  return guarded(__func__, [&]() -> int { return set_transform(s, id, W); });
 }
 
 int sr_bigram_stream_set_frontend(sr_bigram_stream* s, sr_frontend* fe) {
@@ -5317,10 +5504,8 @@ int sr_bigram_stream_end(sr_bigram_stream* s, uint32_t id, uint32_t* out_word, f
   if (!s || !count || ((!out_word || !out_score || !out_time) && cap)) return fail(SR_EINVAL, "null argument");
   const int64_t slot = s->slots.find(id);
   if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
-  if (s->audio.kind[slot] == kStreamAudio)
-    return fail(SR_EINVAL, "stream id %u is fed as audio and not finished (sr_bigram_stream_finish_audio)", id);
-  int rc = check_model(s->model);
-  if (rc) return rc;
+  int rc = check_end(s, (uint32_t)slot, id, "sr_bigram_stream_finish_audio");
+  if (rc || (rc = check_model(s->model))) return rc;
   rc = bigram_stream_items(s, (uint32_t)slot, id, out_word, out_score, out_time, cap, count);
   if (rc == SR_EINVAL) return rc;  // too small a buffer: the utterance stays open
   s->slots.open[slot] = 0;

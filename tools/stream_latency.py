@@ -21,7 +21,14 @@ shape -- window 400, shift 160, 512-point transform, 13 cepstra and their deltas
 maximum -- on noise utterances of U{200..400} frames: every push hands each open stream its next --piece x 160 samples.  In the same
 run the rows the batch front end gives for the same utterances are streamed as feature pushes of --piece rows, and the two pushes'
 median and p99 wall times are printed side by side.  stream_frontend_kernel's device time is the difference of the two runs' search
-windows (sr_profile's HIP events: the front end's launch is counted there).  The two runs' results are checked to be equal."""
+windows (sr_profile's HIP events: the front end's launch is counted there).  The two runs' results are checked to be equal.
+
+--pipeline: the stream set with a projection and a transform per stream (sr_stream_set_projection, sr_stream_set_transform): rows of
+39 columns, context 4 (E = 351), into the 39-dimensional model, on noise utterances of U{200..400} rows (with --audio: the front end
+above on a placeholder model, its rows the pipeline's input).  In the same run the plain push of the same number of rows -- the batch
+route's rows as feature pushes, or the same audio through a front end of the model itself -- is timed, and the two pushes' median and
+p99 wall times are printed side by side.  stream_pipeline_kernel's device time is the difference of the two runs' search windows.  The
+pipeline run's results are checked against the batch route's (splice_transform, transform, one recognition call)."""
 from __future__ import annotations
 
 import argparse
@@ -45,7 +52,10 @@ def main():
     ap.add_argument("--decoder", choices=["zerogram", "bigram"], default="zerogram")
     ap.add_argument("--stable", action="store_true", help="after every push, time the stable-prefix call on the pushed streams")
     ap.add_argument("--audio", action="store_true", help="time audio pushes beside feature pushes of the same rows")
+    ap.add_argument("--pipeline", action="store_true", help="time pushes through a projection and a transform per stream beside plain pushes")
     args = ap.parse_args()
+    if args.pipeline:
+        return main_pipeline(args)
     if args.audio:
         return main_audio(args)
     if args.decoder == "bigram":
@@ -333,6 +343,146 @@ def main_audio(args):
     print(f"stream_frontend_kernel (HIP events: the audio run's search windows minus the feature run's): {fe_ms:.3f} ms per push")
     print(f"audio push / feature push at the median: {np.median(a_ms) / np.median(f_ms):.2f}x (+{np.median(a_ms) - np.median(f_ms):.3f} ms)")
     print(f"the audio run's results equal the feature run's: {'yes' if same else 'NO'}")
+    return 0 if same else 1
+
+
+def main_pipeline(args):
+    from speechrecognition_amd import capi, synth
+
+    D, c, p, shift, window = 39, 4, 39, 160, 400
+    E = (2 * c + 1) * D
+    bigram = args.decoder == "bigram"
+    kernel = {"mfma": capi.GMM_MFMA, "exact": capi.GMM_EXACT, "prefilter": capi.GMM_PREFILTER, "default": capi.GMM_DEFAULT}[args.kernel]
+    lex = synth.make_lexicon(2666, 3, 1, extra_states_last=1) if bigram else synth.make_lexicon(1333, 3, 1)
+    tmp = tempfile.mkdtemp(prefix="srstream_")
+    mp = os.path.join(tmp, "model.mix")
+    synth.write_mixset(mp, synth.make_mixset(lex.n_states, 64 if bigram else 32, p, seed=23))
+    word_off, automaton, sil = lex.flatten()
+    rng = np.random.default_rng(7)
+    n = min(args.utts, 256)
+    lens = rng.integers(200, 401, size=n)
+    M = np.hstack([rng.normal(size=(p, E)) / np.sqrt(E), rng.normal(size=(p, 1))])
+    Ws = np.stack([np.hstack([np.eye(p) + 0.05 * rng.normal(size=(p, p)), rng.normal(size=(p, 1))]) for _ in range(args.streams)])
+    mfcc = dict(sample_rate=16000.0, window=window, shift=shift, n_fft=512, n_mel=24, n_cepstra=13, f_low=0.0, f_high=8000.0,
+                preemphasis=0.97, energy_floor=1.0)
+    post = dict(n_static=13, n_first=13, n_second=13, deriv_step=3, energy_max_norm=0)
+    if args.audio:
+        inputs = [np.clip(np.rint(rng.normal(0.0, 300.0, window + (int(T) - 1) * shift)), -32768, 32767).astype(np.int16) for T in lens]
+    else:
+        inputs = [(rng.normal(size=(int(T), D)) * 3.0).astype(np.float32) for T in lens]
+    holder = capi.Model.from_tables(np.arange(4, dtype=np.uint32), np.zeros((3, D)), np.ones((3, D)), np.zeros(3), np.zeros(3))
+
+    with holder as src, capi.Model.from_mixset(mp, p) as m, src.frontend(mfcc, post) as fe_in, m.frontend(mfcc, post) as fe_own:
+        if bigram:
+            lm_rng = np.random.default_rng(99)
+            nW = lex.n_words
+            lm = np.empty((nW, nW), np.float32)
+            for h0 in range(0, nW, 256):
+                pr = lm_rng.dirichlet(np.ones(nW), size=min(256, nW - h0))
+                lm[:, h0:h0 + pr.shape[0]] = (-np.log(np.maximum(pr, 1e-30))).T
+            net = m.bigram(word_off, automaton, lex.silence_idx, lm, np.array([[3.0, 0.0, 3.0, 150.0], [0.0001, 3.0, np.inf, 15.0]], np.float32))
+            open_set = lambda: m.bigram_stream(net, 200.0, capi.FLT_MAX, kernel, max_streams=args.streams, max_frames=400)  # noqa: E731
+        else:
+            net = m.lexicon(word_off, automaton, lex.silence_idx, (3.0, 0.0, 30.0), sil)
+            open_set = lambda: m.stream(net, 200.0, 10.0, kernel, max_streams=args.streams, max_frames=400)  # noqa: E731
+        # the batch route: the utterance begun u-th takes the transform of slot u mod streams
+        ioff = np.concatenate([[0], np.cumsum([len(x) for x in inputs])]).astype(np.uint64)
+        inp = fe_in.from_audio(np.concatenate(inputs), ioff) if args.audio else src.upload(np.concatenate(inputs), ioff)
+        proj = inp.splice_transform(m, c, M)
+        corpus = proj.transform(np.arange(n) % args.streams, Ws)
+        rows_all, foff = corpus.download(), corpus.frame_off.astype(np.int64)
+        if bigram:
+            bw, bs, bt, boff = corpus.recognize_bigram(net, 200.0, capi.FLT_MAX, kernel)
+            want = [(bw[int(boff[u]):int(boff[u + 1])], bs[int(boff[u]):int(boff[u + 1])], bt[int(boff[u]):int(boff[u + 1])]) for u in range(n)]
+        else:
+            words, woff = corpus.recognize(net, 200.0, 10.0, kernel)
+            want = [words[int(woff[u]):int(woff[u + 1])] for u in range(n)]
+        for x in (corpus, proj, inp):
+            x.close()
+        rows = [rows_all[foff[u]:foff[u + 1]] for u in range(n)]
+
+        def run(piped):
+            src_, k = (inputs, args.piece * shift) if args.audio else (inputs if piped else rows, args.piece)
+            with open_set() as st:
+                if piped:
+                    st.set_projection(D, c, M)
+                if args.audio:
+                    st.set_frontend(fe_in if piped else fe_own)
+
+                def push(batch):
+                    if args.audio:
+                        st.push_audio(batch)
+                    elif piped:
+                        st.push_rows(batch)
+                    else:
+                        st.push(batch)
+
+                def finish(sid):  # (outside the pushes' device times, as the audio mode's)
+                    capi.lib().sr_profile_enable(m.h, 0)
+                    if args.audio:
+                        st.finish_audio([sid])
+                    elif piped:
+                        st.push_rows({}, finish=[sid])
+                    capi.lib().sr_profile_enable(m.h, 1)
+
+                def begin(u):
+                    sid = st.begin()
+                    if piped:
+                        st.set_transform(sid, Ws[u % args.streams])
+                    return sid
+
+                warm = [begin(i) for i in range(args.streams)]  # warm: staging at the full push size, the kernels' code objects
+                for i in range(3):
+                    push({sid: src_[0][i * k:(i + 1) * k] for sid in warm})
+                for sid in warm:
+                    finish(sid)
+                    st.end(sid)
+                m.profile(True)
+                todo, open_, got, ms = list(range(n)), {}, {}, []
+                while todo or open_:
+                    while todo and len(open_) < args.streams:
+                        u = todo.pop(0)
+                        open_[begin(u)] = (u, 0)
+                    batch = {sid: src_[u][t0:t0 + k] for sid, (u, t0) in open_.items()}
+                    t = time.perf_counter()
+                    push(batch)
+                    ms.append(1e3 * (time.perf_counter() - t))
+                    for sid in list(open_):
+                        u, t0 = open_[sid]
+                        t0 += len(batch[sid])
+                        if t0 == len(src_[u]):
+                            finish(sid)
+                            got[u] = st.end(sid)
+                            del open_[sid]
+                        else:
+                            open_[sid] = (u, t0)
+                return np.asarray(ms), m.profile_read(), got
+
+        p_ms, p_prof, p_got = run(True)
+        f_ms, f_prof, f_got = run(False)
+        net.close()
+
+    def equal(x, y):
+        if bigram:
+            return all(np.array_equal(np.asarray(i).view(np.uint32), np.asarray(j).view(np.uint32)) for i, j in zip(x, y))
+        return np.array_equal(x, y)
+
+    same = all(equal(p_got[u], want[u]) for u in range(n))
+    if not args.audio:  # (the plain run was fed the batch route's rows: the same results again)
+        same = same and all(equal(f_got[u], want[u]) for u in range(n))
+    shape = "configs[4] shape (8000 states x 64, 2666 words), bigram stream" if bigram else "configs[2] model (4000 states x 32, 1333 words)"
+    unit = f"{args.piece * shift} samples" if args.audio else f"{args.piece} rows"
+    print(f"workload: {shape}, {n} noise utterances, {int(foff[-1])} frames, {args.streams} concurrent streams, gmm_kernel {args.kernel}")
+    print(f"pipeline: in_dim {D}, context {c} (E = {E}), model dimension {p}, a transform per stream"
+          + ("; front end: window 400, shift 160, n_fft 512, 24 filters, 13 + 13 + 13 features, step 3, no energy maximum" if args.audio else ""))
+    for name, ms, prof in (("pipeline push", p_ms, p_prof), ("plain push   ", f_ms, f_prof)):
+        print(f"{name} ({unit} per stream): {len(ms)} pushes; wall median {np.median(ms):.3f} ms, p99 {np.percentile(ms, 99):.3f} ms, "
+              f"min {ms.min():.3f} ms; device per push: scoring {prof['gmm_ms'] / len(ms):.3f} ms, search window {prof['search_ms'] / len(ms):.3f} ms "
+              f"({prof['search_launches']} windows)")
+    k_ms = p_prof["search_ms"] / len(p_ms) - f_prof["search_ms"] / len(f_ms)
+    print(f"stream_pipeline_kernel (HIP events: the pipeline run's search windows minus the plain run's): {k_ms:.3f} ms per push")
+    print(f"pipeline push / plain push at the median: {np.median(p_ms) / np.median(f_ms):.2f}x (+{np.median(p_ms) - np.median(f_ms):.3f} ms)")
+    print(f"the pipeline run's results equal the batch route's: {'yes' if same else 'NO'}")
     return 0 if same else 1
 
 
