@@ -567,6 +567,9 @@ class StreamingRecognizer {
     check(sr_stream_push_audio(s_, 1, &id, samples, off, nullptr, 0, nullptr));
   }
   void finish_audio(uint32_t id) { check(sr_stream_finish_audio(s_, 1, &id, nullptr, 0, nullptr)); }
+  // the utterance's VTLN warp (srgpu.h: sr_stream_set_warp): an index into the attached warped front end's warps, SR_STREAM_NO_WARP
+  // clears it; between begin() and the utterance's first push.  Its rows are then FrontEnd::from_audio_warped's under that warp.
+  void set_warp(uint32_t id, uint32_t warp) { check(sr_stream_set_warp(s_, id, warp)); }
   // The pipeline (srgpu.h: sr_stream_set_projection): rows of in_dim columns are spliced with `context` neighbours on either side and
   // projected by M [dimension x ((2 context + 1) in_dim + 1)] (nullptr detaches; while no utterance is open), then the utterance's
   // W [dimension x (dimension + 1)] (nullptr clears it; between begin() and its first push) is applied, on the device.  push_rows:
@@ -1956,6 +1959,8 @@ class StreamingLinearSearch {
     check(sr_bigram_stream_push_audio(s_, 1, &id, samples, off, nullptr, 0, nullptr));
   }
   void finish_audio(uint32_t id) { check(sr_bigram_stream_finish_audio(s_, 1, &id, nullptr, 0, nullptr)); }
+  // the utterance's VTLN warp, as StreamingRecognizer's (srgpu.h: sr_bigram_stream_set_warp)
+  void set_warp(uint32_t id, uint32_t warp) { check(sr_bigram_stream_set_warp(s_, id, warp)); }
   // The pipeline (srgpu.h: sr_bigram_stream_set_projection): rows of in_dim columns are spliced with `context` neighbours on either side and
   // projected by M [dimension x ((2 context + 1) in_dim + 1)] (nullptr detaches; while no utterance is open), then the utterance's
   // W [dimension x (dimension + 1)] (nullptr clears it; between begin() and its first push) is applied, on the device.  push_rows:

@@ -872,8 +872,8 @@ SR_API int sr_bigram_stream_finish_audio(struct sr_bigram_stream* s, uint32_t n,
  * > 0).  sr_stream_partial's *frames, sr_stream_stable and the traceback refer to the rows searched; max_frames bounds the rows
  * received (SR_ELIMIT).  Every check comes before any launch; a call refused by a check changes no utterance, its history included
  * (a call that fails after its launches -- a HIP error, SR_EINTERNAL -- may leave a slot's device history ahead of the host's count: end
- * such an utterance).  A VTLN warp
- * per stream is not part of the pipeline: a stream set's front end is one (possibly warped) front end for all its ids. */
+ * such an utterance).  A VTLN warp per utterance is not a stage of this pipeline but a choice inside the front end: sr_stream_set_warp
+ * below. */
 SR_API int sr_stream_set_projection(sr_stream* s, uint32_t in_dim, uint32_t context, const double* M);
 SR_API int sr_stream_set_transform(sr_stream* s, uint32_t id, const double* W);
 SR_API int sr_stream_push_rows(sr_stream* s, uint32_t n, const uint32_t* ids, const float* feats, const uint64_t* frame_off, int finish,
@@ -883,6 +883,30 @@ SR_API int sr_bigram_stream_set_transform(struct sr_bigram_stream* s, uint32_t i
 SR_API int sr_bigram_stream_push_rows(struct sr_bigram_stream* s, uint32_t n, const uint32_t* ids, const float* feats,
                                       const uint64_t* frame_off, int finish, float* out_feats /*optional*/, uint64_t cap_rows,
                                       uint64_t* out_frame_off /*[n+1], optional*/);
+/* ---- streaming from audio: a VTLN warp per utterance -------------------------------------------------------------------------------
+ * With a warped front end attached (sr_frontend_create_warped, n_warps = sr_frontend_warps > 0), every audio id of a stream set may
+ * carry one of the front end's warps.  stream_frontend_kernel then builds that id's statics with the filters of its warp, as
+ * mfcc_kernel does for an utterance of sr_corpus_from_audio_warped; one launch still serves all the ids of a push, whatever their
+ * warps.  An id without a warp uses the unwarped filters, as every id did before.
+ * The rows.  With energy_max_norm == 0, row t of an id with warp w is exactly row t of sr_corpus_from_audio_warped on the whole
+ * utterance with utt_warp = w, bit for bit, for every way of cutting the samples into pushes and for every mix of warps among the ids
+ * of one push.  With a projection and / or a transform attached those rows are the pipeline's input, and the rows searched are the
+ * batch chain's: sr_corpus_from_audio_warped, sr_corpus_splice_transform, sr_corpus_transform.  With the energy maximum on, component 0
+ * is the causal maximum defined above, applied to the warped no-maximum rows.  The words and the traceback are the batch search's on
+ * that corpus.
+ *
+ * sr_stream_set_warp   between sr_stream_begin and the id's first push of either kind, as sr_stream_set_transform; later it is SR_EINVAL.
+ *                      SR_STREAM_NO_WARP clears the warp; a fresh id has none, and a slot reused by a new id does not inherit the warp of
+ *                      the utterance before it.  SR_EINVAL: no front end attached, a front end without warps, warp >= n_warps other
+ *                      than SR_STREAM_NO_WARP, an unknown or ended id.  Host state only: no launch, no device memory.
+ * An id that carries a warp is an audio id: sr_stream_push / sr_stream_push_rows on it is SR_EINVAL and changes nothing, the warp
+ * included.  Every check comes before any launch; a refused call changes nothing.  sr_stream_set_frontend is allowed only while no id
+ * is open, and a warp lives from its id's begin to its end, so no warp outlives the front end it was checked against.  Not offered:
+ * changing a warp after the first push, a Jacobian term for the warp, a warp search inside the stream set (INTEGRATION.md 5d composes
+ * one from existing calls), warps for ids fed with rows. */
+#define SR_STREAM_NO_WARP 0xFFFFFFFFu
+SR_API int sr_stream_set_warp(sr_stream* s, uint32_t id, uint32_t warp);
+SR_API int sr_bigram_stream_set_warp(struct sr_bigram_stream* s, uint32_t id, uint32_t warp);
 /* the features of any resident corpus -- uploaded, transformed, projected or a front end's -- back to the host, out [frames x dim of the
  * corpus's model]; an asynchronous upload is waited for first */
 SR_API int sr_corpus_download(sr_corpus* c, float* out);

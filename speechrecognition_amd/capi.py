@@ -24,6 +24,7 @@ BIGRAM_GLOBAL_STATES = 2
 SR_ECORRUPT = -7
 LDA_SKIP = 0xFFFFFFFF  # SR_LDA_SKIP: the class of a frame the LDA statistics leave out
 SR_ABI_VERSION = 4
+STREAM_NO_WARP = 0xFFFFFFFF  # SR_STREAM_NO_WARP: an utterance of a stream set without a VTLN warp
 
 # every symbol include/srgpu.h declares
 SYMBOLS = [
@@ -57,6 +58,7 @@ SYMBOLS = [
     "sr_bigram_stream_set_frontend", "sr_bigram_stream_push_audio", "sr_bigram_stream_finish_audio",
     "sr_stream_set_projection", "sr_stream_set_transform", "sr_stream_push_rows",
     "sr_bigram_stream_set_projection", "sr_bigram_stream_set_transform", "sr_bigram_stream_push_rows",
+    "sr_stream_set_warp", "sr_bigram_stream_set_warp",
     "sr_probe_fp16_denormals", "sr_probe_fp16_accumulation", "sr_prefilter_masks", "sr_prefilter_range_frames",
     "sr_refine_masks", "sr_refine_geometry",
     "sr_gather_words", "sr_recognize_corpus_scores", "sr_recognize_bigram_corpus_scores", "sr_bigram_route",
@@ -244,6 +246,7 @@ def lib():
             getattr(L, fn + "_finish_audio").argtypes = [vp, u32, vp, vp, u64, vp]
             getattr(L, fn + "_set_projection").argtypes = [vp, u32, u32, vp]
             getattr(L, fn + "_set_transform").argtypes = [vp, u32, vp]
+            getattr(L, fn + "_set_warp").argtypes = [vp, u32, u32]
             getattr(L, fn + "_push_rows").argtypes = [vp, u32, vp, vp, vp, i32, vp, u64, vp]
         L.sr_probe_fp16_denormals.argtypes = [i32, C.POINTER(i32)]
         L.sr_probe_fp16_accumulation.argtypes = [i32, C.POINTER(i32), C.POINTER(dbl)]
@@ -613,6 +616,11 @@ class _StreamSet:
             if W.shape != (self.model.dim, self.model.dim + 1):
                 raise ValueError(f"W must be [{self.model.dim} x {self.model.dim + 1}], got {W.shape}")
         _check(getattr(lib(), self._fn + "_set_transform")(self.h, int(id), None if W is None else _ptr(W)))
+
+    def set_warp(self, id, warp):
+        """sr_stream_set_warp: the utterance's VTLN warp, an index into the attached warped front end's warps (None or STREAM_NO_WARP
+        clears it: the unwarped filters); between begin and the id's first push.  An id with a warp takes audio only."""
+        _check(getattr(lib(), self._fn + "_set_warp")(self.h, int(id), STREAM_NO_WARP if warp is None else int(warp)))
 
     def _rows_out(self, received, finished):
         """the rows searched of an utterance that has received so many input rows (sr_stream_set_projection's delay)"""

@@ -21,7 +21,8 @@
 // stream_frontend_kernel (sr_stream_push_audio).  The same two stages for utterances whose samples arrive in pieces: a workgroup per
 // pushed utterance computes the new frames' statics with mfcc_kernel's per-frame body (mfcc_power, mfcc_cepstra), stages them behind the 2 step
 // statics the slot keeps, and emits the rows whose windows are complete with feature_post_kernel's arithmetic (post_value).  With no
-// energy maximum a streamed row carries the batch's bits; the maximum is the causal one of include/srgpu.h.
+// energy maximum a streamed row carries the batch's bits; the maximum is the causal one of include/srgpu.h.  A job may name a warp
+// (sr_stream_set_warp): its workgroup then takes that warp's filters as mfcc_kernel does, and the slot's history holds warped statics.
 //
 // Compiled with -ffp-contract=off: the post-processing is specified to the bit (float subtractions, FP64 subtraction and division),
 // and the MFCC stage's bits must not depend on what the compiler may fuse around a frame.
@@ -319,7 +320,12 @@ __global__ __launch_bounds__(256) void stream_frontend_kernel(StreamFrontendArgs
   float* y = lds;
   float* mine = lds + y_floats + (size_t)wave * (4 * M + 64);
   float2* A = reinterpret_cast<float2*>(mine);
-  const MelFilters filters{a.mel_first, a.mel_count, a.mel_off, a.mel_w};  // a stream has no warp: the unwarped filters
+  // the utterance's filters, chosen once for the workgroup as mfcc_kernel chooses them: its warp's, or the unwarped ones
+  MelFilters filters{a.mel_first, a.mel_count, a.mel_off, a.mel_w};
+  if (j.warp != kStreamNoWarp) {
+    const uint32_t w0 = j.warp * a.n_mel;
+    filters = MelFilters{a.warp_first + w0, a.warp_count + w0, a.warp_off + w0, a.warp_w};
+  }
   for (uint32_t j0 = 0; j0 < j.k; j0 += a.span_frames) {
     const uint32_t n = min(a.span_frames, j.k - j0);
     const uint32_t n_samp = (n - 1) * a.shift + a.window;

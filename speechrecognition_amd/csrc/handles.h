@@ -361,11 +361,17 @@ struct StreamAudio {
   sr_frontend* fe = nullptr;
   std::vector<uint8_t> kind;               // [max_streams] kStream*, kStreamFresh from begin to the first push that names the id
   std::vector<srplan::AudioCarry> carry;   // [max_streams]
+  std::vector<uint32_t> warp;              // [max_streams] the utterance's VTLN warp (sr_stream_set_warp), SR_STREAM_NO_WARP from begin and after end
   DevBuf<float> state;                     // [max_streams][2 step n_static + 1]: the last 2 step statics, the running maximum
   // per push, sized by the largest push so far
   DevBuf<int16_t> samples;
   DevBuf<float> stage;
   DevBuf<srgpu::StreamFrontendJob> jobs;
+  void open(uint32_t max_streams) {
+    kind.assign(max_streams, kStreamFresh); carry.assign(max_streams, srplan::AudioCarry()); warp.assign(max_streams, SR_STREAM_NO_WARP);
+  }
+  void begin(uint32_t slot) { kind[slot] = kStreamFresh; carry[slot] = srplan::AudioCarry(); warp[slot] = SR_STREAM_NO_WARP; }
+  void end(uint32_t slot) { warp[slot] = SR_STREAM_NO_WARP; }
 };
 
 // The pipeline of a stream set (sr_stream_set_projection, _set_transform, _push_rows and the bigram twins): the projection, the

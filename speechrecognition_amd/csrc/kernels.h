@@ -1031,14 +1031,18 @@ hipError_t launch_feature_post(const FeaturePostArgs& a, hipStream_t stream);
 // floats.  A job: the utterance had S statics before the push and gains k; its piece (the sample before it first) begins at
 // samples[sample0]; its staging rows -- 2 step of history, then the k new statics -- begin at row stage0 of `stage`; it emits
 // `rows` rows from row0 of the utterance into row out0 of `out`, clamped by T (kStreamFrontendOpen: the count is not known yet).
+// warp (sr_stream_set_warp): the utterance's filters are warp `warp` of the front end's warped CSR, as mfcc_kernel takes them by
+// utt_warp; kStreamNoWarp (== SR_STREAM_NO_WARP): the unwarped filters.  The jobs of one launch may carry any mix of warps.
 constexpr uint32_t kStreamFrontendOpen = 0xFFFFFFFFu;
+constexpr uint32_t kStreamNoWarp = 0xFFFFFFFFu;
 struct StreamFrontendJob {
   uint32_t slot, S, k, T;
-  uint32_t row0, rows;
+  uint32_t row0, rows, warp;
   uint64_t sample0, stage0, out0;
 };
 struct StreamFrontendArgs {
-  MfccArgs mfcc;                 // samples: the push's pieces; window .. dct as for mfcc_kernel (sample_off, frame_off, spans, out unused)
+  MfccArgs mfcc;                 // samples: the push's pieces; window .. dct and warp_first .. warp_w as for mfcc_kernel (sample_off,
+                                 // frame_off, spans, out, utt_warp unused; warp_* are NULL for a front end without warps)
   const StreamFrontendJob* jobs;
   uint32_t n_static, n_first, n_second, step;
   const double* mean; const double* stddev;

@@ -931,6 +931,23 @@ int set_transform(Set* s, uint32_t id, const double* W) {
   return SR_OK;
 }
 
+// sr_stream_set_warp and its bigram twin: host state only.  sr_stream_set_frontend runs only while no id is open and every begin and end
+// clears the slot's warp, so a warp never meets a front end other than the one it was checked against.
+template <class Set>
+int set_warp(Set* s, uint32_t id, uint32_t warp) {
+  if (!s) return fail(SR_EINVAL, "null stream set");
+  const int64_t slot = s->slots.find(id);
+  if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
+  if (s->audio.kind[slot] != kStreamFresh)
+    return fail(SR_EINVAL, "stream id %u has been pushed to: its warp is set between begin and the first push", id);
+  const sr_frontend* fe = s->audio.fe;
+  if (!fe) return fail(SR_EINVAL, "the stream set has no front end (sr_stream_set_frontend)");
+  if (fe->n_warps == 0) return fail(SR_EINVAL, "the stream set's front end has no warps: make it with sr_frontend_create_warped");
+  if (warp != SR_STREAM_NO_WARP && warp >= fe->n_warps) return fail(SR_EINVAL, "stream id %u: warp %u >= n_warps %u", id, warp, fe->n_warps);
+  s->audio.warp[slot] = warp;
+  return SR_OK;
+}
+
 // The pipeline's part of a push over the ids in slots[]: entry i gains k[i] input rows (finishing: none follow).  plan_pipeline: the
 // steps of stream_pipeline_plan.h, where the rows they emit go in the push's output (out_off) and the entries to search.  The
 // pipeline is active for a push when the set has a projection or one of the named utterances a transform; otherwise the input rows
@@ -1019,6 +1036,9 @@ int push_rows(Set* s, uint32_t n, const uint32_t* ids, const float* feats, const
     seen[slot] = 1;
     slots[i] = (uint32_t)slot;
     if (s->audio.kind[slot] >= kStreamAudio) return fail(SR_EINVAL, "push entry %u: stream id %u is fed as audio; it takes no feature rows", i, ids[i]);
+    if (s->audio.warp[slot] != SR_STREAM_NO_WARP)
+      return fail(SR_EINVAL, "push entry %u: stream id %u carries VTLN warp %u, which applies to audio; it takes no feature rows", i, ids[i],
+                  s->audio.warp[slot]);
     if (pl.carry[slot].finished) return fail(SR_EINVAL, "push entry %u: stream id %u is finished; it takes no more rows", i, ids[i]);
     if (frame_off) {
       if (frame_off[i + 1] < frame_off[i]) return fail(SR_EINVAL, "frame_off is not ascending at entry %u", i);
@@ -1142,7 +1162,7 @@ int push_audio(Set* s, uint32_t n, const uint32_t* ids, const int16_t* samples, 
     StreamFrontendJob j{};
     j.slot = slots[i]; j.S = (uint32_t)c.statics; j.k = (uint32_t)st.new_statics;
     j.T = finishing ? (uint32_t)st.next.statics : kStreamFrontendOpen;
-    j.row0 = (uint32_t)st.row0; j.rows = (uint32_t)st.rows;
+    j.row0 = (uint32_t)st.row0; j.rows = (uint32_t)st.rows; j.warp = au.warp[slots[i]];
     j.sample0 = pieces.size(); j.stage0 = stage_rows; j.out0 = row_off[i];
     pieces.resize(pieces.size() + 1 + st.n_buf);
     srplan::audio_fill(c, st, k ? samples + sample_off[i] : nullptr, k, pieces.data() + j.sample0);
@@ -1164,6 +1184,7 @@ int push_audio(Set* s, uint32_t n, const uint32_t* ids, const int16_t* samples, 
     f.preemphasis = p.preemphasis; f.energy_floor = p.energy_floor;
     f.win = fe->win.p; f.twiddle = fe->twiddle.p; f.mel_first = fe->mel_first.p; f.mel_count = fe->mel_count.p; f.mel_off = fe->mel_off.p;
     f.mel_w = fe->mel_w.p; f.dct = fe->dct.p;
+    f.warp_first = fe->warp_first.p; f.warp_count = fe->warp_count.p; f.warp_off = fe->warp_off.p; f.warp_w = fe->warp_w.p;  // (the jobs' warps)
     a.jobs = au.jobs.p;
     a.n_static = nf; a.n_first = fe->post.n_first; a.n_second = fe->post.n_second; a.step = step;
     a.mean = fe->normalise ? fe->mean.p : nullptr; a.stddev = fe->normalise ? fe->stddev.p : nullptr;
@@ -5176,7 +5197,7 @@ int sr_stream_open(sr_model* m, sr_lexicon* l, const sr_search_params* p, uint32
   std::unique_ptr<sr_stream, int (*)(sr_stream*)> own(s, sr_stream_destroy);
   s->model = m; s->lex = l; s->params = *p; s->slots = StreamSlots(max_streams, max_frames);
   s->commit_fresh.assign(max_streams, 1);
-  s->audio.kind.assign(max_streams, kStreamFresh); s->audio.carry.resize(max_streams);
+  s->audio.open(max_streams);
   s->pipe.open(max_streams);
   const size_t S = max_streams;
   HIP_TRY(s->ws.ensure(S * decode_big_workspace(l->net.n_slots)));
@@ -5197,7 +5218,7 @@ int sr_stream_begin(sr_stream* s, uint32_t* id) {
   if (rc) return rc;
   const uint32_t slot = *id % s->slots.max_streams;
   s->commit_fresh[slot] = 1;  // ... and the first sr_stream_stable from commit point 0
-  s->audio.kind[slot] = kStreamFresh; s->audio.carry[slot] = srplan::AudioCarry();
+  s->audio.begin(slot);
   s->pipe.begin(slot);
   return SR_OK;
   });
@@ -5219,6 +5240,9 @@ int sr_stream_set_transform(sr_stream* s, uint32_t id, const double* W) {
 
 int sr_stream_set_frontend(sr_stream* s, sr_frontend* fe) {
   return guarded(__func__, [&]() -> int { return set_frontend(s, fe); });
+}
+int sr_stream_set_warp(sr_stream* s, uint32_t id, uint32_t warp) {
+  return guarded(__func__, [&]() -> int { return set_warp(s, id, warp); });
 }
 int sr_stream_push_audio(sr_stream* s, uint32_t n, const uint32_t* ids, const int16_t* samples, const uint64_t* sample_off, float* out_feats,
                          uint64_t cap_rows, uint64_t* out_frame_off) {
@@ -5262,6 +5286,7 @@ int sr_stream_end(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_t cap, 
     if (tb_bkp) HIP_TRY(hipMemcpy(tb_bkp, s->tb_bkp.p + b, sizeof(uint16_t) * (T + 1), hipMemcpyDeviceToHost));
   }
   s->slots.open[slot] = 0;
+  s->audio.end((uint32_t)slot);
   return rc;
   });
 }
@@ -5425,7 +5450,7 @@ int sr_bigram_stream_open(sr_model* m, sr_bigram* b, const sr_bigram_params* p, 
   s->model = m; s->bigram = b; s->params = *p; s->slots = StreamSlots(max_streams, max_frames);
   s->host_state.assign(max_streams, BigramStreamState{}); s->failed.assign(max_streams, 0);
   s->commit_fresh.assign(max_streams, 1);
-  s->audio.kind.assign(max_streams, kStreamFresh); s->audio.carry.resize(max_streams);
+  s->audio.open(max_streams);
   s->pipe.open(max_streams);
   const size_t S = max_streams, W = b->net.n_words;
   HIP_TRY(s->gs_ws.ensure(S * bigram_gs_ws_words(b->net.n_words, b->net.n_positions)));
@@ -5453,7 +5478,7 @@ int sr_bigram_stream_begin(sr_bigram_stream* s, uint32_t* id) {
   s->host_state[slot].n_book = 2;  // the two start entries the first push writes
   s->failed[slot] = 0;
   s->commit_fresh[slot] = 1;  // the first sr_bigram_stream_stable starts from the start entry
-  s->audio.kind[slot] = kStreamFresh; s->audio.carry[slot] = srplan::AudioCarry();
+  s->audio.begin(slot);
   s->pipe.begin(slot);
   return SR_OK;
   });
@@ -5475,6 +5500,9 @@ int sr_bigram_stream_set_transform(sr_bigram_stream* s, uint32_t id, const doubl
 
 int sr_bigram_stream_set_frontend(sr_bigram_stream* s, sr_frontend* fe) {
   return guarded(__func__, [&]() -> int { return set_frontend(s, fe); });
+}
+int sr_bigram_stream_set_warp(sr_bigram_stream* s, uint32_t id, uint32_t warp) {
+  return guarded(__func__, [&]() -> int { return set_warp(s, id, warp); });
 }
 int sr_bigram_stream_push_audio(sr_bigram_stream* s, uint32_t n, const uint32_t* ids, const int16_t* samples, const uint64_t* sample_off,
                                 float* out_feats, uint64_t cap_rows, uint64_t* out_frame_off) {
@@ -5509,6 +5537,7 @@ int sr_bigram_stream_end(sr_bigram_stream* s, uint32_t id, uint32_t* out_word, f
   rc = bigram_stream_items(s, (uint32_t)slot, id, out_word, out_score, out_time, cap, count);
   if (rc == SR_EINVAL) return rc;  // too small a buffer: the utterance stays open
   s->slots.open[slot] = 0;
+  s->audio.end((uint32_t)slot);
   return rc;
   });
 }

@@ -28,7 +28,12 @@ windows (sr_profile's HIP events: the front end's launch is counted there).  The
 above on a placeholder model, its rows the pipeline's input).  In the same run the plain push of the same number of rows -- the batch
 route's rows as feature pushes, or the same audio through a front end of the model itself -- is timed, and the two pushes' median and
 p99 wall times are printed side by side.  stream_pipeline_kernel's device time is the difference of the two runs' search windows.  The
-pipeline run's results are checked against the batch route's (splice_transform, transform, one recognition call)."""
+pipeline run's results are checked against the batch route's (splice_transform, transform, one recognition call).
+
+--audio --vtln: the front end of --audio with 13 warps (alpha 0.88 .. 1.12, break 0.875); beside the audio run with no warp set, the same
+pushes with a warp on every id (sr_stream_set_warp / sr_bigram_stream_set_warp), dealt round-robin -- the utterance begun u-th takes warp
+u mod 13, so the 64 ids of a push carry all 13 -- and the two audio pushes' median and p99 wall times and stream_frontend_kernel's device
+time side by side.  The warped run's results are checked against one recognition call on sr_corpus_from_audio_warped's corpus."""
 from __future__ import annotations
 
 import argparse
@@ -52,8 +57,11 @@ def main():
     ap.add_argument("--decoder", choices=["zerogram", "bigram"], default="zerogram")
     ap.add_argument("--stable", action="store_true", help="after every push, time the stable-prefix call on the pushed streams")
     ap.add_argument("--audio", action="store_true", help="time audio pushes beside feature pushes of the same rows")
+    ap.add_argument("--vtln", action="store_true", help="with --audio: time audio pushes whose ids carry VTLN warps beside the same pushes without")
     ap.add_argument("--pipeline", action="store_true", help="time pushes through a projection and a transform per stream beside plain pushes")
     args = ap.parse_args()
+    if args.vtln and (args.pipeline or not args.audio):
+        ap.error("--vtln goes with --audio (and not with --pipeline)")
     if args.pipeline:
         return main_pipeline(args)
     if args.audio:
@@ -268,8 +276,10 @@ def main_audio(args):
     mfcc = dict(sample_rate=16000.0, window=window, shift=shift, n_fft=512, n_mel=24, n_cepstra=13, f_low=0.0, f_high=8000.0,
                 preemphasis=0.97, energy_floor=1.0)
     post = dict(n_static=13, n_first=13, n_second=13, deriv_step=3, energy_max_norm=0)
+    n_warps = 13
+    vtln = dict(alpha=[round(0.88 + 0.02 * i, 2) for i in range(n_warps)], break_frac=0.875) if args.vtln else None
 
-    with capi.Model.from_mixset(mp, D) as m, m.frontend(mfcc, post) as fe:
+    with capi.Model.from_mixset(mp, D) as m, m.frontend(mfcc, post, vtln=vtln) as fe:
         if bigram:
             lm_rng = np.random.default_rng(99)
             nW = lex.n_words
@@ -287,12 +297,28 @@ def main_audio(args):
         rows_all, foff = corpus.download(), corpus.frame_off.astype(np.int64)
         corpus.close()
         rows = [rows_all[foff[u]:foff[u + 1]] for u in range(n)]
+        if args.vtln:  # what the warped run must give: the batch search on the batch front end's corpus, utterance u under warp u mod 13
+            corpus = fe.from_audio_warped(np.concatenate(audio), soff, np.arange(n) % n_warps)
+            if bigram:
+                bw, bs, bt, boff = corpus.recognize_bigram(net, 200.0, capi.FLT_MAX, kernel)
+                want = [(bw[int(boff[u]):int(boff[u + 1])], bs[int(boff[u]):int(boff[u + 1])], bt[int(boff[u]):int(boff[u + 1])]) for u in range(n)]
+            else:
+                words, woff = corpus.recognize(net, 200.0, 10.0, kernel)
+                want = [words[int(woff[u]):int(woff[u + 1])] for u in range(n)]
+            corpus.close()
 
-        def run(as_audio):
+        def run(as_audio, warped=False):
             src, k = (audio, args.piece * shift) if as_audio else (rows, args.piece)
             with open_set() as st:
                 st.set_frontend(fe)
-                warm = [st.begin() for _ in range(args.streams)]  # warm: staging at the full push size, the kernels' code objects
+
+                def begin(u):
+                    sid = st.begin()
+                    if warped:
+                        st.set_warp(sid, u % n_warps)
+                    return sid
+
+                warm = [begin(i) for i in range(args.streams)]  # warm: staging at the full push size, the kernels' code objects
                 for _ in range(2):
                     (st.push_audio if as_audio else st.push)({sid: src[0][:k] for sid in warm})
                 for sid in warm:
@@ -303,7 +329,8 @@ def main_audio(args):
                 todo, open_, got, ms = list(range(n)), {}, {}, []
                 while todo or open_:
                     while todo and len(open_) < args.streams:
-                        open_[st.begin()] = (todo.pop(0), 0)
+                        u = todo.pop(0)
+                        open_[begin(u)] = (u, 0)
                     push = {sid: src[u][t0:t0 + k] for sid, (u, t0) in open_.items()}
                     t = time.perf_counter()
                     (st.push_audio if as_audio else st.push)(push)
@@ -323,6 +350,8 @@ def main_audio(args):
                 return np.asarray(ms), m.profile_read(), got
 
         a_ms, a_prof, a_got = run(True)
+        if args.vtln:
+            w_ms, w_prof, w_got = run(True, warped=True)
         f_ms, f_prof, f_got = run(False)
         net.close()
 
@@ -335,7 +364,12 @@ def main_audio(args):
     shape = "configs[4] shape (8000 states x 64, 2666 words), bigram stream" if bigram else "configs[2] model (4000 states x 32, 1333 words)"
     print(f"workload: {shape}, {n} noise utterances, {int(foff[-1])} frames, {args.streams} concurrent streams, gmm_kernel {args.kernel}")
     print(f"front end: window {window}, shift {shift}, n_fft 512, 24 filters, 13 + 13 + 13 features, step 3, no energy maximum")
-    for name, ms, prof, what in (("audio push  ", a_ms, a_prof, f"{args.piece * shift} samples"), ("feature push", f_ms, f_prof, f"{args.piece} rows")):
+    if args.vtln:
+        print(f"warps: {n_warps} (alpha 0.88 .. 1.12, break 0.875); the warped run's utterance u carries warp u mod {n_warps}, the other runs' ids none")
+    lines = [("audio push  ", a_ms, a_prof, f"{args.piece * shift} samples"), ("feature push", f_ms, f_prof, f"{args.piece} rows")]
+    if args.vtln:
+        lines.insert(1, ("warped audio", w_ms, w_prof, f"{args.piece * shift} samples"))
+    for name, ms, prof, what in lines:
         print(f"{name} ({what} per stream): {len(ms)} pushes; wall median {np.median(ms):.3f} ms, p99 {np.percentile(ms, 99):.3f} ms, "
               f"min {ms.min():.3f} ms; device per push: scoring {prof['gmm_ms'] / len(ms):.3f} ms, search window {prof['search_ms'] / len(ms):.3f} ms "
               f"({prof['search_launches']} windows)")
@@ -343,6 +377,14 @@ def main_audio(args):
     print(f"stream_frontend_kernel (HIP events: the audio run's search windows minus the feature run's): {fe_ms:.3f} ms per push")
     print(f"audio push / feature push at the median: {np.median(a_ms) / np.median(f_ms):.2f}x (+{np.median(a_ms) - np.median(f_ms):.3f} ms)")
     print(f"the audio run's results equal the feature run's: {'yes' if same else 'NO'}")
+    if args.vtln:
+        wk_ms = w_prof["search_ms"] / len(w_ms) - f_prof["search_ms"] / len(f_ms)
+        print(f"stream_frontend_kernel with warps (the warped run's search windows minus the feature run's): {wk_ms:.3f} ms per push "
+              f"({wk_ms - fe_ms:+.3f} ms against no warps)")
+        print(f"warped audio push / audio push at the median: {np.median(w_ms) / np.median(a_ms):.3f}x ({np.median(w_ms) - np.median(a_ms):+.3f} ms)")
+        w_same = all(equal(w_got[u], want[u]) for u in range(n))
+        print(f"the warped run's results equal the batch's on sr_corpus_from_audio_warped's corpus: {'yes' if w_same else 'NO'}")
+        same = same and w_same
     return 0 if same else 1
 
 
