@@ -585,10 +585,16 @@ class StreamingRecognizer {
     if (frame_off.size() != ids.size() + 1) throw std::runtime_error("StreamingRecognizer::push: frame_off needs ids.size() + 1 entries");
     check(sr_stream_push(s_, (uint32_t)ids.size(), ids.data(), frames, frame_off.data()));
   }
+  // (a trimmed utterance can hold more words than max_frames: a call that reports too small a buffer says how many it needs)
   std::vector<WordIdx> partial(uint32_t id) {
     std::vector<uint32_t> w(max_frames_);
     uint32_t n = 0;
-    check(sr_stream_partial(s_, id, w.data(), (uint32_t)w.size(), &n, nullptr));
+    int rc = sr_stream_partial(s_, id, w.data(), (uint32_t)w.size(), &n, nullptr);
+    if (rc == SR_EINVAL && n > w.size()) {
+      w.resize(n);
+      rc = sr_stream_partial(s_, id, w.data(), (uint32_t)w.size(), &n, nullptr);
+    }
+    check(rc);
     return std::vector<WordIdx>(w.begin(), w.begin() + n);
   }
   // the leading words of partial(id) that no later frame can change (sr_stream_stable): a prefix of every later partial() and of
@@ -598,15 +604,38 @@ class StreamingRecognizer {
     std::vector<uint32_t> w(max_frames_);
     uint64_t off[2] = {0, 0};
     uint32_t c = 0, sil = 0;
-    check(sr_stream_stable(s_, 1, &id, w.data(), w.size(), off, &c, &sil));
+    int rc = sr_stream_stable(s_, 1, &id, w.data(), w.size(), off, &c, &sil);
+    if (rc == SR_EINVAL && off[1] > w.size()) {
+      w.resize(off[1]);
+      rc = sr_stream_stable(s_, 1, &id, w.data(), w.size(), off, &c, &sil);
+    }
+    check(rc);
     if (commit) *commit = c;
     if (trailing_silence) *trailing_silence = sil;
     return std::vector<WordIdx>(w.begin(), w.begin() + off[1]);
   }
+  // Drops the frames of the utterance up to its commit point on the device and keeps their words on the host (sr_stream_trim):
+  // max_frames then bounds the frames since, not the utterance, which can go on without limit when it is trimmed every few pushes.
+  // partial(), stable() and end() still report the whole utterance.  -> the frames dropped (0: the commit point has not moved)
+  uint32_t trim(uint32_t id) {
+    uint32_t dropped = 0;
+    check(sr_stream_trim(s_, 1, &id, &dropped));
+    return dropped;
+  }
+  std::vector<uint32_t> trim(std::vector<uint32_t> const& ids) {
+    std::vector<uint32_t> dropped(ids.size(), 0);
+    check(sr_stream_trim(s_, (uint32_t)ids.size(), ids.data(), dropped.data()));
+    return dropped;
+  }
   std::vector<WordIdx> end(uint32_t id) {
     std::vector<uint32_t> w(max_frames_);
     uint32_t n = 0;
-    check(sr_stream_end(s_, id, w.data(), (uint32_t)w.size(), &n, nullptr, nullptr, nullptr));
+    int rc = sr_stream_end(s_, id, w.data(), (uint32_t)w.size(), &n, nullptr, nullptr, nullptr);
+    if (rc == SR_EINVAL && n > w.size()) {  // (the id is still open)
+      w.resize(n);
+      rc = sr_stream_end(s_, id, w.data(), (uint32_t)w.size(), &n, nullptr, nullptr, nullptr);
+    }
+    check(rc);
     return std::vector<WordIdx>(w.begin(), w.begin() + n);
   }
 

@@ -204,6 +204,8 @@ SR_API int sr_recognize_batch(sr_model* m, sr_lexicon* l, const sr_search_params
  *                    max_streams x (20 P + 12 (max_frames + 1) + 4 max_frames + 40) bytes (P = the lexicon's positions; 20 P
  *                    rounded up to 256), plus staging for the largest push: 4 dim + 8 n_states bytes per frame and the scoring
  *                    kernel's own workspaces.  The search always keeps its hypotheses in device memory (decode_stream_kernel).
+ *                    An utterance that is trimmed (sr_stream_trim, below) may be longer than max_frames: the limit then bounds
+ *                    the frames since the last one dropped.
  * sr_stream_begin    a fresh utterance (the initial hypothesis of Recognizer.cpp:116-120); *id names it until sr_stream_end.  Ids
  *                    are not reused soon after their utterance ended: an ended id is refused, not confused with a newer one.
  * sr_stream_push     n utterances, ids[n], each at most once; their new frames back to back in feats ([frames x dim] float32),
@@ -258,6 +260,39 @@ SR_API int sr_stream_destroy(sr_stream* s);
  * (nothing is written). */
 SR_API int sr_stream_stable(sr_stream* s, uint32_t n, const uint32_t* ids, uint32_t* out_words, uint64_t cap, uint64_t* out_word_off,
                             uint32_t* out_commit, uint32_t* out_silence);
+
+/* ---- endless streams: dropping the committed frames of an open utterance --------------------------------------------------
+ * Nothing below the commit point c(t) is read again except to spell out the words on the way to it.  sr_stream_trim moves those
+ * words to the host and drops the frames up to c(t) on the device; the search goes on bit for bit as if nothing had been dropped.
+ * After a trim the device state of the utterance is a WINDOW on it:
+ *   base        the frames dropped so far, a 64-bit host count.  Window frame f is the utterance's frame base + f; window frame 0
+ *               stands for the last commit point trimmed at and carries the entry (0.0, 0, 0).
+ *   archive     the words of the guarded walks from every commit point trimmed at down to the one before it, silence removed: a
+ *               host array per utterance that grows with words, not frames, and is reset by sr_stream_begin.
+ *   max_frames  bounds the WINDOW, not the utterance: a push is SR_ELIMIT when the rows received since the last dropped frame
+ *               would pass it (for an audio id: the frames its samples make).  An utterance that is trimmed as often as its commit
+ *               point moves runs on without limit in a set opened for the largest uncommitted stretch.  Only the utterance's own
+ *               row counts stay 32 bit: a push that would take one past 2^32 - 1 is SR_ELIMIT.
+ * sr_stream_trim     n utterances, ids[n], each at most once, in ONE launch (stream_trim_kernel: one workgroup per utterance).
+ *                    Per id: c = c(t) exactly as sr_stream_stable computes it (the same fold, the same floor; with no hypothesis
+ *                    alive it stays at the previous commit point); the words of the walk from c go to the archive; d = c frames
+ *                    are dropped: traceback entries (c, t] become (0, t - c] with their back pointers rebased (one below c -- the
+ *                    no-word-end record, or a dead node no later walk reaches -- becomes 0), the alive hypotheses' back pointers
+ *                    lose c, the commit point becomes 0, and the partial result is walked anew.  out_dropped[i] = d (the array may
+ *                    be NULL); d == 0 is a valid answer and changes nothing.  c <= t - 1 always: the window keeps a frame.  Feature,
+ *                    row and audio ids all trim: the front end's and the pipeline's own counters stay absolute.
+ * On a trimmed utterance
+ *   sr_stream_partial  returns archive + window words, *frames counts from the utterance's start.  Where the last searched frame
+ *                      has no surviving word end the result is the window walk's alone -- no archived word: ending there returns
+ *                      no earlier word at all, the reference's behaviour (above).
+ *   sr_stream_stable   returns archive + the window's stable words, out_commit = base + c (SR_ELIMIT if past 2^32 - 1).
+ *   sr_stream_end      returns the words sr_recognize_corpus returns for the whole utterance.  Its traceback arrays must be NULL:
+ *                      the dropped entries are gone, and a non-NULL array is SR_EINVAL and leaves the id open.
+ * An id that is never trimmed has base 0 and behaves as before.  The bigram stream set does not trim.
+ * Errors, everything checked before the launch: SR_EINVAL for an unknown, ended or repeated id (nothing is written); SR_ECORRUPT
+ * for an id whose walk fails its guards or with an alive back pointer below c -- that id is left as it was, on the device and
+ * here; the other ids of the call are trimmed and their out_dropped written. */
+SR_API int sr_stream_trim(sr_stream* s, uint32_t n, const uint32_t* ids, uint32_t* out_dropped);
 
 /* ---- several devices: the `#pragma omp parallel for` over segments of Recognizer::recognize (Recognizer.cpp:46-47) -------
  * Utterances are independent, so a batch shards across devices with no collective: sr_shard_utterances deals them by

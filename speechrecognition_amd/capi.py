@@ -51,7 +51,7 @@ SYMBOLS = [
     "sr_bigram_accuracies_corpus", "sr_bigram_smbr_statistics_corpus",
     "sr_bigram_word_lattice_corpus", "sr_bigram_lattice_nbest",
     "sr_stream_open", "sr_stream_begin", "sr_stream_push", "sr_stream_partial", "sr_stream_end", "sr_stream_destroy",
-    "sr_stream_stable", "sr_bigram_stream_stable", "sr_commit_points",
+    "sr_stream_stable", "sr_bigram_stream_stable", "sr_commit_points", "sr_stream_trim",
     "sr_bigram_stream_open", "sr_bigram_stream_begin", "sr_bigram_stream_push", "sr_bigram_stream_partial", "sr_bigram_stream_end",
     "sr_bigram_stream_destroy",
     "sr_stream_set_frontend", "sr_stream_push_audio", "sr_stream_finish_audio",
@@ -232,6 +232,7 @@ def lib():
         L.sr_stream_end.argtypes = [vp, u32, vp, u32, C.POINTER(u32), vp, vp, vp]
         L.sr_stream_destroy.argtypes = [vp]
         L.sr_stream_stable.argtypes = [vp, u32, vp, vp, u64, vp, vp, vp]
+        L.sr_stream_trim.argtypes = [vp, u32, vp, vp]
         L.sr_bigram_stream_stable.argtypes = [vp, u32, vp, vp, vp, vp, u64, vp, vp]
         L.sr_commit_points.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
         L.sr_bigram_stream_open.argtypes = [vp, vp, C.POINTER(BigramParams), u32, u64, C.POINTER(vp)]
@@ -725,9 +726,13 @@ class Stream(_StreamSet):
     def __init__(self, model, lexicon, am_threshold, word_penalty, kernel, max_streams, max_frames):
         super().__init__(model, lexicon, SearchParams(am_threshold, word_penalty, kernel, 0), max_streams, max_frames)
 
+    def _word_cap(self, id):
+        """a word takes a frame at least; a trimmed utterance (trim) can hold more frames than max_frames"""
+        return max(self.max_frames, self.frames.get(id, 0))
+
     def partial(self, id, frames=False):
         """-> the words so far (u32[]) [, frames pushed]"""
-        out = np.zeros(self.max_frames, np.uint32)
+        out = np.zeros(self._word_cap(id), np.uint32)
         n, t = C.c_uint32(), C.c_uint64()
         _check(lib().sr_stream_partial(self.h, id, _ptr(out), len(out), C.byref(n), C.byref(t)))
         return (out[: n.value].copy(), t.value) if frames else out[: n.value].copy()
@@ -743,9 +748,18 @@ class Stream(_StreamSet):
         _check(lib().sr_stream_stable(self.h, n, _ptr(ids), _ptr(out), cap, _ptr(off), _ptr(commit), _ptr(silence)))
         return [out[int(off[i]): int(off[i + 1])].copy() for i in range(n)], commit[:n], silence[:n]
 
+    def trim(self, ids):
+        """sr_stream_trim -> dropped u32[n]: the frames of every named utterance up to its commit point are dropped on the device and
+        their words kept on the host; max_frames bounds what is left, the results stay the whole utterance's.  end(traceback=True) is
+        refused on an id that has lost frames."""
+        ids = np.ascontiguousarray(list(ids), dtype=np.uint32)
+        dropped = np.zeros(max(len(ids), 1), np.uint32)
+        _check(lib().sr_stream_trim(self.h, len(ids), _ptr(ids), _ptr(dropped)))
+        return dropped[: len(ids)]
+
     def end(self, id, traceback=False):
         """-> final words (u32[]) [, (tb_score, tb_word, tb_bkp) of T + 1 entries]; frees the id"""
-        out = np.zeros(self.max_frames, np.uint32)
+        out = np.zeros(self._word_cap(id), np.uint32)
         n = C.c_uint32()
         tbs = tbw = tbb = None
         if traceback:

@@ -328,7 +328,7 @@ struct StreamSlots {
   std::vector<uint8_t> open;        // [max_streams]
   std::vector<uint32_t> id;         // [max_streams] id of the slot's current (or last) utterance
   std::vector<uint32_t> generation; // [max_streams] of the next utterance begun in the slot
-  std::vector<uint64_t> frames;     // [max_streams] frames pushed so far
+  std::vector<uint64_t> frames;     // [max_streams] frames searched so far (sr_stream: of the window, less what sr_stream_trim dropped)
   StreamSlots() = default;
   StreamSlots(uint32_t n, uint64_t max_frames_)
       : max_streams(n), max_frames(max_frames_), open(n, 0), id(n, 0), generation(n, 0), frames(n, 0) {}
@@ -414,6 +414,11 @@ struct sr_stream {
   std::vector<uint8_t> commit_fresh;  // [max_streams] no commit point computed for the slot's utterance yet
   DevBuf<uint32_t> commit, stable_words;
   PinnedBuf<unsigned char> stable_block;
+  // sr_stream_trim: the device state of a slot is a window on its utterance.  base = the frames dropped so far (window frame f is
+  // the utterance's frame base + f; slots.frames counts the window's searched frames), archive = the committed words of the dropped
+  // frames.  Both are reset by sr_stream_begin; an id that is never trimmed keeps base 0 and an empty archive.
+  std::vector<uint64_t> base;                   // [max_streams]
+  std::vector<std::vector<uint32_t>> archive;   // [max_streams] grows with words, not frames
 };
 
 // A set of concurrently open utterances on one (model, bigram search net) (sr_bigram_stream_*, srgpu_api.cpp).  The device state of

@@ -299,6 +299,29 @@ struct StableArgs {
   uint32_t* out_words;      // the block's word area
 };
 hipError_t launch_stream_commit(const StableArgs& a, uint32_t n_jobs, hipStream_t stream);
+// the trim (sr_stream_trim): stream_trim_kernel, one workgroup per requested stream, finds the commit point c as stream_commit_kernel
+// does (a StableJob; the same floor), hands the words of the walk from c to the call's result block (StableResult::commit = c, the
+// frames dropped; ::count, the words; ::silence unused), and renumbers what the search left: traceback entries (c, t] move to
+// (0, t - c], the alive hypotheses' back pointers lose c and land in the buffer of parity (t - c) & 1 with their scores, commit[slot]
+// becomes 0, and the walk from frame t - c refreshes the slot's partial result.  A result flagged kStableCorrupt has written nothing.
+struct TrimArgs {
+  DecodeNet net;
+  const StableJob* jobs;    // [workgroups]
+  unsigned char* ws;        // [slots x ws_stride]: the search's hypotheses
+  size_t ws_stride;
+  StreamState* state;       // [slots]: flags and count of the partial result
+  double* tb_score;         // [slots x tb_stride]
+  uint16_t* tb_word;
+  uint16_t* tb_bkp;
+  uint64_t tb_stride;
+  uint32_t* commit;         // [slots]
+  uint32_t* walk_words;     // [slots x words_stride] the committed walk's buffer (sr_stream_stable's)
+  uint32_t* words;          // [slots x words_stride] the slots' partial results
+  uint64_t words_stride;    // max_frames
+  StableResult* out_res;    // [workgroups]
+  uint32_t* out_words;      // the block's word area
+};
+hipError_t launch_stream_trim(const TrimArgs& a, uint32_t n_jobs, hipStream_t stream);
 // the fold alone (sr_commit_points): set i's nodes set[set_off[i] .. set_off[i + 1]) in the tree parent[node_off[i] ..], out[i] their
 // nearest common ancestor (kCommitCorrupt of commit_point.h where a parent is not below its child)
 struct CommitPointsArgs {

@@ -737,11 +737,26 @@ int stream_words(sr_stream* s, uint32_t slot, uint32_t id, uint32_t* out_words, 
   HIP_TRY(hipMemcpy(&st, s->state.p + slot, sizeof(st), hipMemcpyDeviceToHost));
   if (st.flags & kFlagCorrupt) return fail(SR_ECORRUPT, "stream %u: the traceback does not walk back to frame 0 (Recognizer.cpp:222-231)", id);
   if (st.count > s->slots.frames[slot]) return fail(SR_ECORRUPT, "stream %u: %u words for %llu frames", id, st.count, (unsigned long long)s->slots.frames[slot]);
-  *count = st.count;
-  if (st.count > cap) return fail(SR_EINVAL, "stream %u: %u words, out_words holds %u", id, st.count, cap);
-  if (st.count) HIP_TRY(hipMemcpy(out_words, s->words.p + (size_t)slot * s->slots.max_frames, sizeof(uint32_t) * st.count, hipMemcpyDeviceToHost));
+  // A trimmed utterance (sr_stream_trim): the window's walk ends at the last commit point, the words before it are in the archive.
+  // The reference's walk from an entry without a surviving word end reports no earlier word at all, so the archive
+  // leads only where the walk started at a finite entry.
+  const std::vector<uint32_t>& arch = s->archive[slot];
+  size_t lead = arch.size();
+  if (lead) {
+    double last = 0.0;
+    HIP_TRY(hipMemcpy(&last, s->tb_score.p + (size_t)slot * (s->slots.max_frames + 1) + s->slots.frames[slot], sizeof(double), hipMemcpyDeviceToHost));
+    if (!(last < __builtin_huge_val())) lead = 0;
+  }
+  const uint64_t total = (uint64_t)lead + st.count;
+  *count = (uint32_t)std::min<uint64_t>(total, 0xFFFFFFFFull);
+  if (total > cap) return fail(SR_EINVAL, "stream %u: %llu words, out_words holds %u", id, (unsigned long long)total, cap);
+  if (lead) memcpy(out_words, arch.data(), sizeof(uint32_t) * lead);
+  if (st.count) HIP_TRY(hipMemcpy(out_words + lead, s->words.p + (size_t)slot * s->slots.max_frames, sizeof(uint32_t) * st.count, hipMemcpyDeviceToHost));
   return SR_OK;
 }
+// the frames an utterance has lost to sr_stream_trim: the bigram set does not trim
+uint64_t stream_base(const sr_stream* s, uint32_t slot) { return s->base[slot]; }
+uint64_t stream_base(const sr_bigram_stream*, uint32_t) { return 0; }
 // the partial (after every push) or final traceback items of the utterance in `slot`: the state record read back after its last push
 int bigram_stream_items(sr_bigram_stream* s, uint32_t slot, uint32_t id, uint32_t* out_word, float* out_score, uint32_t* out_time,
                         uint32_t cap, uint32_t* count) {
@@ -969,7 +984,8 @@ void plan_pipeline(const Set* s, const std::vector<uint32_t>& slots, const std::
   for (size_t i = 0; i < n; i++) {
     pp->steps[i] = srplan::plan_pipeline_step(pl.context, pl.carry[slots[i]], k[i], finishing);
     pp->out_off[i + 1] = pp->out_off[i] + pp->steps[i].rows;
-    if (pp->steps[i].rows) pp->entries.push_back({slots[i], pp->steps[i].row0, pp->steps[i].rows, pp->out_off[i]});
+    // (the pipeline counts the utterance's rows, the search its window's: sr_stream_trim)
+    if (pp->steps[i].rows) pp->entries.push_back({slots[i], pp->steps[i].row0 - stream_base(s, slots[i]), pp->steps[i].rows, pp->out_off[i]});
     if (pl.has_w[slots[i]]) pp->active = true;
   }
 }
@@ -1044,10 +1060,14 @@ int push_rows(Set* s, uint32_t n, const uint32_t* ids, const float* feats, const
       if (frame_off[i + 1] < frame_off[i]) return fail(SR_EINVAL, "frame_off is not ascending at entry %u", i);
       k[i] = frame_off[i + 1] - frame_off[i];
     }
-    const uint64_t got = pl.carry[slot].received;
+    // max_frames bounds the window (the rows received since the last frame sr_stream_trim dropped), 32 bits the utterance's row count
+    const uint64_t got = pl.carry[slot].received - stream_base(s, (uint32_t)slot);
     if (k[i] > sl.max_frames - got)
       return fail(SR_ELIMIT, "stream id %u: %llu + %llu frames exceed max_frames %llu", ids[i], (unsigned long long)got,
                   (unsigned long long)k[i], (unsigned long long)sl.max_frames);
+    if (k[i] > 0xFFFFFFFFull - pl.carry[slot].received)
+      return fail(SR_ELIMIT, "stream id %u: %llu + %llu rows exceed 2^32 - 1", ids[i], (unsigned long long)pl.carry[slot].received,
+                  (unsigned long long)k[i]);
   }
   PipelinePush pp;
   plan_pipeline(s, slots, k, finishing, &pp);
@@ -1132,9 +1152,14 @@ int push_audio(Set* s, uint32_t n, const uint32_t* ids, const int16_t* samples, 
     }
     if (k && !samples) return fail(SR_EINVAL, "samples is null");
     const srplan::AudioCarry& c = au.carry[slot];
-    if (srplan::audio_frames(p.window, p.shift, c.n_samples + k) > sl.max_frames)
+    // max_frames bounds the window (the frames since the last one sr_stream_trim dropped), 32 bits the utterance's frame count
+    const uint64_t made = srplan::audio_frames(p.window, p.shift, c.n_samples + k);
+    if (made - stream_base(s, (uint32_t)slot) > sl.max_frames)
       return fail(SR_ELIMIT, "stream id %u: %llu + %llu samples make more than max_frames %llu frames", ids[i], (unsigned long long)c.n_samples,
                   (unsigned long long)k, (unsigned long long)sl.max_frames);
+    if (made > 0xFFFFFFFFull)
+      return fail(SR_ELIMIT, "stream id %u: %llu + %llu samples make more than 2^32 - 1 frames", ids[i], (unsigned long long)c.n_samples,
+                  (unsigned long long)k);
     steps[i] = srplan::plan_audio_step(p.window, p.shift, step, c, k ? samples + sample_off[i] : nullptr, k, finishing);
     row_off[i + 1] = row_off[i] + steps[i].rows;
     rows_in[i] = steps[i].rows;
@@ -5197,6 +5222,8 @@ int sr_stream_open(sr_model* m, sr_lexicon* l, const sr_search_params* p, uint32
   std::unique_ptr<sr_stream, int (*)(sr_stream*)> own(s, sr_stream_destroy);
   s->model = m; s->lex = l; s->params = *p; s->slots = StreamSlots(max_streams, max_frames);
   s->commit_fresh.assign(max_streams, 1);
+  s->base.assign(max_streams, 0);
+  s->archive.assign(max_streams, std::vector<uint32_t>());
   s->audio.open(max_streams);
   s->pipe.open(max_streams);
   const size_t S = max_streams;
@@ -5218,6 +5245,8 @@ int sr_stream_begin(sr_stream* s, uint32_t* id) {
   if (rc) return rc;
   const uint32_t slot = *id % s->slots.max_streams;
   s->commit_fresh[slot] = 1;  // ... and the first sr_stream_stable from commit point 0
+  s->base[slot] = 0;          // ... with nothing trimmed
+  s->archive[slot].clear();
   s->audio.begin(slot);
   s->pipe.begin(slot);
   return SR_OK;
@@ -5259,7 +5288,7 @@ int sr_stream_partial(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_t c
   if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
   int rc = check_model(s->model);
   if (rc) return rc;
-  if (frames) *frames = s->slots.frames[slot];
+  if (frames) *frames = s->base[slot] + s->slots.frames[slot];
   return stream_words(s, (uint32_t)slot, id, out_words, cap, count);
   });
 }
@@ -5272,6 +5301,9 @@ int sr_stream_end(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_t cap, 
   if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
   int rc = check_end(s, (uint32_t)slot, id, "sr_stream_finish_audio");
   if (rc || (rc = check_model(s->model))) return rc;
+  if (s->base[slot] && (tb_score || tb_word || tb_bkp))
+    return fail(SR_EINVAL, "stream id %u has been trimmed: the traceback entries of its first %llu frames are gone (pass NULL arrays)", id,
+                (unsigned long long)s->base[slot]);
   rc = stream_words(s, (uint32_t)slot, id, out_words, cap, count);
   if (rc == SR_EINVAL) return rc;  // too small a buffer: the utterance stays open
   const uint64_t T = s->slots.frames[slot];
@@ -5287,6 +5319,7 @@ int sr_stream_end(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_t cap, 
   }
   s->slots.open[slot] = 0;
   s->audio.end((uint32_t)slot);
+  std::vector<uint32_t>().swap(s->archive[slot]);
   return rc;
   });
 }
@@ -5296,10 +5329,12 @@ int sr_stream_end(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_t cap, 
 // Job[n] (in), StableResult[n], then the items, frame_bytes for every frame the n utterances have seen (an utterance gives at most
 // one item per frame; its items start `frames of the utterances before it` into each item area).  The caller supplies make_job(i,
 // slot, frames before, &job) -> rc, launch(jobs, results, items, frames, stream) -> rc over the block's three parts, copy_out(i, job,
-// result, out_off[i]) for utterance i's items, what a result that fails its checks says, and the middle of the capacity message.
-template <class Job, class Set, class MakeJob, class Launch, class CopyOut>
+// result, out_off[i]) for utterance i's items (it may restate out_commit[i]), what a result that fails its checks says, the middle of
+// the capacity message, and lead(slot): the items of the utterance that precede the kernel's (the archive of a trimmed zerogram id).
+template <class Job, class Set, class MakeJob, class Launch, class CopyOut, class Lead>
 static int stable_prefix(Set* s, uint32_t n, const uint32_t* ids, bool missing_array, uint64_t cap, uint64_t* out_off, uint32_t* out_commit,
-                         size_t frame_bytes, const char* corrupt, const char* holds, MakeJob make_job, Launch launch, CopyOut copy_out) {
+                         size_t frame_bytes, const char* corrupt, const char* holds, MakeJob make_job, Launch launch, CopyOut copy_out,
+                         Lead lead) {
   if (!s) return fail(SR_EINVAL, "null stream set");
   if (!out_off || (n && (!ids || !out_commit)) || missing_array) return fail(SR_EINVAL, "null argument");
   sr_model* m = s->model;
@@ -5334,12 +5369,12 @@ static int stable_prefix(Set* s, uint32_t n, const uint32_t* ids, bool missing_a
   }
   if (bad != 0xFFFFFFFFu) return fail(SR_ECORRUPT, "stream %u: %s", ids[bad], corrupt);
   uint64_t total = 0;
-  for (uint32_t i = 0; i < n; i++) { out_off[i] = total; total += res[i].count; }
+  for (uint32_t i = 0; i < n; i++) { out_off[i] = total; total += lead(jobs[i].slot) + res[i].count; }
   out_off[n] = total;
   if (total > cap) return fail(SR_EINVAL, "%llu stable %s %llu", (unsigned long long)total, holds, (unsigned long long)cap);
   for (uint32_t i = 0; i < n; i++) {
-    copy_out(i, jobs[i], res[i], out_off[i]);
     out_commit[i] = res[i].commit;
+    copy_out(i, jobs[i], res[i], out_off[i]);
   }
   return SR_OK;
 }
@@ -5353,6 +5388,8 @@ int sr_stream_stable(sr_stream* s, uint32_t n, const uint32_t* ids, uint32_t* ou
       s, n, ids, !out_words && cap, cap, out_word_off, out_commit, sizeof(uint32_t),
       "the traceback does not walk back from the commit point to frame 0 (Recognizer.cpp:222-231)", "words, out_words holds",
       [&](uint32_t, uint32_t slot, uint64_t off, StableJob* job) -> int {
+        if (s->base[slot] + s->slots.frames[slot] > 0xFFFFFFFFull)  // (out_commit = base + c, c <= the window's frames)
+          return fail(SR_ELIMIT, "stream id %u: a commit frame past 2^32 - 1 does not fit out_commit", s->slots.id[slot]);
         *job = StableJob{slot, (uint32_t)s->slots.frames[slot], s->commit_fresh[slot], 0u, off};
         return SR_OK;
       },
@@ -5370,9 +5407,74 @@ int sr_stream_stable(sr_stream* s, uint32_t n, const uint32_t* ids, uint32_t* ou
         return SR_OK;
       },
       [&](uint32_t i, const StableJob& job, const StableResult& r, uint64_t at) {
-        if (r.count) memcpy(out_words + at, a.out_words + job.word_off, sizeof(uint32_t) * r.count);
+        // a trimmed utterance: the archive's words lead (every commit point lies on the chain through the last one trimmed at),
+        // and the commit frame counts from the utterance's start
+        const std::vector<uint32_t>& arch = s->archive[job.slot];
+        if (!arch.empty()) memcpy(out_words + at, arch.data(), sizeof(uint32_t) * arch.size());
+        if (r.count) memcpy(out_words + at + arch.size(), a.out_words + job.word_off, sizeof(uint32_t) * r.count);
+        out_commit[i] = (uint32_t)(s->base[job.slot] + r.commit);
         if (out_silence) out_silence[i] = r.silence;
-      });
+      },
+      [&](uint32_t slot) -> uint64_t { return s->archive[slot].size(); });
+  });
+}
+
+// sr_stream_trim (include/srgpu.h has the definition): one launch of stream_trim_kernel, one workgroup per id, over the block
+// sr_stream_stable uses -- StableJob[n] in, StableResult[n] and the committed words out.  Everything is checked before the launch;
+// an id whose result is flagged has written nothing on the device and changes nothing here, the others are taken over first.
+int sr_stream_trim(sr_stream* s, uint32_t n, const uint32_t* ids, uint32_t* out_dropped) {
+  return guarded(__func__, [&]() -> int {
+  if (!s) return fail(SR_EINVAL, "null stream set");
+  if (n && !ids) return fail(SR_EINVAL, "null argument");
+  sr_model* m = s->model;
+  int rc = check_model(m);
+  if (rc) return rc;
+  StreamSlots& sl = s->slots;
+  std::vector<uint8_t> seen(sl.max_streams, 0);
+  std::vector<StableJob> jobs(n);
+  uint64_t F = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const int64_t slot = sl.find(ids[i]);
+    if (slot < 0) return fail(SR_EINVAL, "entry %u: stream id %u is not open", i, ids[i]);
+    if (seen[slot]) return fail(SR_EINVAL, "entry %u: stream id %u appears twice in one call", i, ids[i]);
+    seen[slot] = 1;
+    jobs[i] = StableJob{(uint32_t)slot, (uint32_t)sl.frames[slot], s->commit_fresh[slot], 0u, F};
+    F += sl.frames[slot];
+  }
+  if (n == 0) return SR_OK;
+  const sr_lexicon* l = s->lex;
+  HIP_TRY(s->commit.ensure(sl.max_streams));
+  HIP_TRY(s->stable_words.ensure((size_t)sl.max_streams * sl.max_frames));
+  const size_t res_at = sizeof(StableJob) * n, words_at = res_at + sizeof(StableResult) * n, need = words_at + sizeof(uint32_t) * F;
+  if (need > s->stable_block.n) HIP_TRY(s->stable_block.ensure(std::max<size_t>(need, 2 * s->stable_block.n)));
+  unsigned char* blk = s->stable_block.p;
+  memcpy(blk, jobs.data(), sizeof(StableJob) * n);
+  StableResult* res = reinterpret_cast<StableResult*>(blk + res_at);
+  const uint32_t* words = reinterpret_cast<const uint32_t*>(blk + words_at);
+  TrimArgs a{};
+  a.net = l->net;
+  a.jobs = reinterpret_cast<const StableJob*>(blk);
+  a.ws = s->ws.p; a.ws_stride = decode_big_workspace(l->net.n_slots); a.state = s->state.p;
+  a.tb_score = s->tb_score.p; a.tb_word = s->tb_word.p; a.tb_bkp = s->tb_bkp.p; a.tb_stride = sl.max_frames + 1;
+  a.commit = s->commit.p; a.walk_words = s->stable_words.p; a.words = s->words.p; a.words_stride = sl.max_frames;
+  a.out_res = res; a.out_words = reinterpret_cast<uint32_t*>(blk + words_at);
+  HIP_TRY(launch_stream_trim(a, n, m->s_gmm));
+  HIP_TRY(hipStreamSynchronize(m->s_gmm));
+  uint32_t bad = 0xFFFFFFFFu;
+  for (uint32_t i = 0; i < n; i++) {
+    const StableJob& j = jobs[i];
+    const StableResult& r = res[i];
+    // a hypothesis entered at frame t carries bkp = t - 1: the commit point is below t and the window keeps a frame
+    if (r.flags || r.count > r.commit || (j.t ? r.commit >= j.t : r.commit != 0)) { if (bad == 0xFFFFFFFFu) bad = i; continue; }
+    s->commit_fresh[j.slot] = 0;  // the kernel left commit point 0 in commit[slot]
+    s->archive[j.slot].insert(s->archive[j.slot].end(), words + j.word_off, words + j.word_off + r.count);
+    s->base[j.slot] += r.commit;
+    sl.frames[j.slot] -= r.commit;
+    if (out_dropped) out_dropped[i] = r.commit;
+  }
+  if (bad != 0xFFFFFFFFu)
+    return fail(SR_ECORRUPT, "stream %u: the traceback does not walk back from the commit point to frame 0, or an alive hypothesis starts below it", ids[bad]);
+  return SR_OK;
   });
 }
 
@@ -5576,7 +5678,8 @@ int sr_bigram_stream_stable(sr_bigram_stream* s, uint32_t n, const uint32_t* ids
         memcpy(out_word + at, a.out_word + job.item_off, sizeof(uint32_t) * r.count);
         memcpy(out_score + at, a.out_score + job.item_off, sizeof(float) * r.count);
         memcpy(out_time + at, a.out_time + job.item_off, sizeof(uint32_t) * r.count);
-      });
+      },
+      [](uint32_t) -> uint64_t { return 0; });
   });
 }
 

@@ -560,22 +560,13 @@ hipError_t launch_decode_stream(const StreamArgs& a, uint32_t n_jobs, hipStream_
 // commit point (commit_point.h).  The same pass keeps the alive hypothesis of least score (ties: the
 // smaller slot) for the trailing silence.  Thread 0 then walks from the commit point with traceback.h's guards into the slot's
 // own word buffer, and the workgroup copies the words into the call's result block.
-template <int NT>
-__global__ __launch_bounds__(NT) void stream_commit_kernel(StableArgs a) {
-  constexpr uint32_t kWavesPerWg = NT / 64;
-  __shared__ double red_sc[kWavesPerWg];
-  __shared__ uint32_t red[kWavesPerWg], red_idx[kWavesPerWg], n_out;
-  const StableJob job = a.jobs[blockIdx.x];
-  const uint32_t P = a.net.n_slots;
+// The scan both stream_commit_kernel and stream_trim_kernel start with, by every thread of the workgroup: the fold of the alive
+// hypotheses' back pointers (-> the return value: kCommitNone where none is alive, kCommitCorrupt) and, per wave, the alive hypothesis
+// of least score in red_sc / red_idx (commit_best reads them).  Ends behind a barrier.
+template <int NT, class Parent>
+__device__ __forceinline__ uint32_t commit_scan(uint32_t P, uint32_t t, const double* sc, const uint16_t* bk, uint32_t floor, Parent parent,
+                                                uint32_t* red, double* red_sc, uint32_t* red_idx) {
   const uint32_t tid = threadIdx.x;
-  const uint32_t t = job.t;
-  const unsigned char* ws = a.ws + (size_t)job.slot * a.ws_stride;
-  const double* sc = reinterpret_cast<const double*>(ws) + (size_t)(t & 1) * P;
-  const uint16_t* bk = reinterpret_cast<const uint16_t*>(ws + (size_t)P * 16) + (size_t)(t & 1) * P;
-  const uint64_t tb0 = (uint64_t)job.slot * a.tb_stride;
-  const uint32_t floor = job.fresh ? 0u : a.commit[job.slot];
-  auto parent = [&](uint32_t c) -> uint32_t { return a.tb_bkp[tb0 + c]; };
-
   uint32_t mine = kCommitNone, my_p = 0xFFFFFFFFu;
   double my_v = kInf;
   if (t == 0) {  // nothing searched yet (the buffers are not initialised): B = {0}
@@ -593,6 +584,26 @@ __global__ __launch_bounds__(NT) void stream_commit_kernel(StableArgs a) {
   wave_min_idx(my_v, my_p);
   if ((tid & 63) == 0) { red_sc[tid >> 6] = my_v; red_idx[tid >> 6] = my_p; }
   __syncthreads();
+  return all;
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void stream_commit_kernel(StableArgs a) {
+  constexpr uint32_t kWavesPerWg = NT / 64;
+  __shared__ double red_sc[kWavesPerWg];
+  __shared__ uint32_t red[kWavesPerWg], red_idx[kWavesPerWg], n_out;
+  const StableJob job = a.jobs[blockIdx.x];
+  const uint32_t P = a.net.n_slots;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t t = job.t;
+  const unsigned char* ws = a.ws + (size_t)job.slot * a.ws_stride;
+  const double* sc = reinterpret_cast<const double*>(ws) + (size_t)(t & 1) * P;
+  const uint16_t* bk = reinterpret_cast<const uint16_t*>(ws + (size_t)P * 16) + (size_t)(t & 1) * P;
+  const uint64_t tb0 = (uint64_t)job.slot * a.tb_stride;
+  const uint32_t floor = job.fresh ? 0u : a.commit[job.slot];
+  auto parent = [&](uint32_t c) -> uint32_t { return a.tb_bkp[tb0 + c]; };
+
+  const uint32_t all = commit_scan<NT>(P, t, sc, bk, floor, parent, red, red_sc, red_idx);
   uint32_t* words = a.words + (uint64_t)job.slot * a.words_stride;
   if (tid == 0) {
     double best = red_sc[0];
@@ -626,6 +637,117 @@ hipError_t launch_stream_commit(const StableArgs& a, uint32_t n_jobs, hipStream_
   if (n_jobs == 0) return hipSuccess;
   if (a.net.n_slots > decode_big_max_slots()) return hipErrorInvalidValue;
   hipLaunchKernelGGL((stream_commit_kernel<256>), dim3(n_jobs), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
+// ---- dropping the committed frames of an open utterance (sr_stream_trim) ---------------------------------
+// One workgroup per requested stream.  The commit point c is stream_commit_kernel's (commit_scan, the same floor).  Nothing below
+// c is read again except to spell out the words on the way to it, so: thread 0 walks from c into the committed-walk buffer, the
+// workgroup copies those words out, and what the search left is renumbered with c as the new frame 0.
+//   (1) checks, before anything is written: c is a node below t (a hypothesis entered at frame t carries bkp = t - 1, so c <= t - 1
+//       and the window keeps a frame), every alive back pointer is >= c, the walk from c passes its guards.
+//   (2) traceback entries (c, t] move to (0, t - c] in tiles of NT entries, ascending.  The move overlaps itself (destination
+//       i, source c + i), so a tile is READ INTO REGISTERS, then a BARRIER, then WRITTEN: within a tile no thread's write can land
+//       on an entry another thread has yet to read; across tiles the sources of tile k + 1 (> c + (k + 1) NT) lie above every
+//       destination written so far (<= (k + 1) NT), and tile k + 1's writes follow its own barrier, which no thread reaches before
+//       its reads of tile k are done.  A back pointer below c belongs to the no-word-end record (inf, word 0, bkp 0) or to a dead
+//       node, which no walk from a later finite entry reaches (section 4.5c(1)): it becomes 0.  Entry 0 becomes (0.0, 0, 0).
+//   (3) the alive hypotheses' back pointers lose c.  big_frame and stream_commit_kernel take the current buffer from the frame
+//       parity, so with c odd scores (unchanged: they stay absolute) and back pointers go to the other buffer, with c even the back
+//       pointers are rewritten in place.  A thread touches only its own slots p: no ordering needed.
+//   (4) commit[slot] = 0, and thread 0 redoes the partial result's walk from frame t - c behind a barrier.
+template <int NT>
+__global__ __launch_bounds__(NT) void stream_trim_kernel(TrimArgs a) {
+  constexpr uint32_t kWavesPerWg = NT / 64;
+  __shared__ double red_sc[kWavesPerWg];
+  __shared__ uint32_t red[kWavesPerWg], red_idx[kWavesPerWg], n_out;
+  const StableJob job = a.jobs[blockIdx.x];
+  const uint32_t P = a.net.n_slots;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t t = job.t;
+  unsigned char* ws = a.ws + (size_t)job.slot * a.ws_stride;
+  double* sc0 = reinterpret_cast<double*>(ws);                           // the two buffers of scores, then of back pointers
+  uint16_t* bk0 = reinterpret_cast<uint16_t*>(ws + (size_t)P * 16);
+  const double* sc = sc0 + (size_t)(t & 1) * P;
+  const uint16_t* bk = bk0 + (size_t)(t & 1) * P;
+  const uint64_t tb0 = (uint64_t)job.slot * a.tb_stride;
+  const uint32_t floor = job.fresh ? 0u : a.commit[job.slot];
+  auto parent = [&](uint32_t c) -> uint32_t { return a.tb_bkp[tb0 + c]; };
+
+  const uint32_t all = commit_scan<NT>(P, t, sc, bk, floor, parent, red, red_sc, red_idx);
+  const uint32_t c = all == kCommitNone ? floor : all;  // no hypothesis alive: the commit point stays where it was
+  // ---- (1) ----
+  bool bad = c == kCommitCorrupt || (t == 0 ? c != 0 : c >= t);
+  if (!bad && t)
+    for (uint32_t p = tid; p < P; p += NT)
+      if (sc[p] < kInf && bk[p] < c) bad = true;
+  uint32_t* walk_words = a.walk_words + (uint64_t)job.slot * a.words_stride;
+  if (tid == 0) {
+    uint32_t n = 0;
+    if (!bad) {
+      n = walk_traceback(
+          c, a.net.silence_word, a.net.n_words, [&](uint32_t f) -> uint32_t { return a.tb_word[tb0 + f]; },
+          [&](uint32_t f) -> uint32_t { return a.tb_bkp[tb0 + f]; }, walk_words, c);
+      if (n == kTbCorrupt) bad = true;
+    }
+    n_out = n;
+  }
+  bad = __syncthreads_or((int)bad) != 0;  // (also: thread 0's words and n_out are visible to the workgroup)
+  if (bad) {
+    if (tid == 0) a.out_res[blockIdx.x] = StableResult{0u, 0u, 0u, kStableCorrupt};
+    return;
+  }
+  const uint32_t n_words = n_out;
+  for (uint32_t i = tid; i < n_words; i += NT) a.out_words[job.word_off + i] = walk_words[i];
+  if (tid == 0) {
+    a.commit[job.slot] = 0;
+    a.out_res[blockIdx.x] = StableResult{c, 0u, n_words, 0u};
+  }
+  if (c == 0) return;  // nothing to drop (workgroup-uniform): the state stays as it is, bit for bit
+  // ---- (2) ----
+  const uint32_t n_keep = t - c;
+  for (uint32_t i0 = 1; i0 <= n_keep; i0 += NT) {  // (a uniform trip count: every thread meets every barrier)
+    const uint32_t i = i0 + tid;
+    double v = 0.0;
+    uint16_t w = 0, b = 0;
+    if (i <= n_keep) { v = a.tb_score[tb0 + c + i]; w = a.tb_word[tb0 + c + i]; b = a.tb_bkp[tb0 + c + i]; }
+    __syncthreads();
+    if (i <= n_keep) {
+      a.tb_score[tb0 + i] = v; a.tb_word[tb0 + i] = w;
+      a.tb_bkp[tb0 + i] = b >= c ? (uint16_t)(b - c) : (uint16_t)0;
+    }
+  }
+  if (tid == 0) { a.tb_score[tb0] = 0.0; a.tb_word[tb0] = 0; a.tb_bkp[tb0] = 0; }  // (entry 0 is no tile's source: sources are > c)
+  // ---- (3) ----
+  double* scn = sc0 + (size_t)(n_keep & 1) * P;
+  uint16_t* bkn = bk0 + (size_t)(n_keep & 1) * P;
+  const bool moved = (c & 1) != 0;
+  for (uint32_t p = tid; p < P; p += NT) {
+    const double v = sc[p];
+    const uint16_t b = bk[p];
+    if (moved) scn[p] = v;
+    if (v < kInf) bkn[p] = (uint16_t)(b - c);
+    else if (moved) bkn[p] = b;
+  }
+  // ---- (4) ----
+  __threadfence();
+  __syncthreads();
+  if (tid == 0) {
+    StreamState* st = a.state + job.slot;
+    const uint32_t n = walk_traceback(
+        n_keep, a.net.silence_word, a.net.n_words,
+        [&](uint32_t f) -> uint32_t { return __hip_atomic_load(&a.tb_word[tb0 + f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); },
+        [&](uint32_t f) -> uint32_t { return __hip_atomic_load(&a.tb_bkp[tb0 + f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); },
+        a.words + (uint64_t)job.slot * a.words_stride, n_keep);
+    st->flags = (st->flags & kFlagSlowPath) | (n == kTbCorrupt ? kFlagCorrupt : 0u);
+    st->count = n == kTbCorrupt ? 0u : n;
+  }
+}
+
+hipError_t launch_stream_trim(const TrimArgs& a, uint32_t n_jobs, hipStream_t stream) {
+  if (n_jobs == 0) return hipSuccess;
+  if (a.net.n_slots > decode_big_max_slots()) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((stream_trim_kernel<256>), dim3(n_jobs), dim3(256), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -16,6 +16,11 @@ sr_recognize_bigram_corpus; the streamed items (words, score bits, times) are ch
 call for all of them) and prints the median and p99 wall time of that call beside the push's; every answer is checked to be a
 prefix of its utterance's final result (where that is not empty).
 
+--trim (zerogram): after every push (and after the stable call, with --stable) also trims the pushed streams at their commit points
+(sr_stream_trim, one call for all of them) and prints the median, p99 and maximum wall time of that call, the frames dropped, and the
+largest window any stream held at a push -- the max_frames the corpus needs with a trim every push -- with sr_stream_open's device
+bytes per stream at that window and at 65535.  The words are still checked against the batch's.
+
 --audio: the same stream set fed PCM samples (sr_stream_push_audio / sr_bigram_stream_push_audio) through a front end of the model's
 shape -- window 400, shift 160, 512-point transform, 13 cepstra and their deltas and delta-deltas (39 dimensions), step 3, no energy
 maximum -- on noise utterances of U{200..400} frames: every push hands each open stream its next --piece x 160 samples.  In the same
@@ -56,12 +61,15 @@ def main():
     ap.add_argument("--kernel", choices=["default", "prefilter", "exact", "mfma"], default="default")
     ap.add_argument("--decoder", choices=["zerogram", "bigram"], default="zerogram")
     ap.add_argument("--stable", action="store_true", help="after every push, time the stable-prefix call on the pushed streams")
+    ap.add_argument("--trim", action="store_true", help="after every push, trim the pushed streams at their commit points and time the call")
     ap.add_argument("--audio", action="store_true", help="time audio pushes beside feature pushes of the same rows")
     ap.add_argument("--vtln", action="store_true", help="with --audio: time audio pushes whose ids carry VTLN warps beside the same pushes without")
     ap.add_argument("--pipeline", action="store_true", help="time pushes through a projection and a transform per stream beside plain pushes")
     args = ap.parse_args()
     if args.vtln and (args.pipeline or not args.audio):
         ap.error("--vtln goes with --audio (and not with --pipeline)")
+    if args.trim and (args.pipeline or args.audio or args.decoder == "bigram"):
+        ap.error("--trim times the zerogram feature push (the bigram stream set does not trim)")
     if args.pipeline:
         return main_pipeline(args)
     if args.audio:
@@ -104,14 +112,18 @@ def main():
             open_ = {}  # id -> (utterance, frames pushed)
             got = {}
             push_ms, stable_ms, last_stable, stable_ok = [], [], {}, True
+            trim_ms, base, dropped_total, window = [], {}, 0, 0
             t_all = time.perf_counter()
             while todo or open_:
                 while todo and len(open_) < args.streams:
                     u = todo.pop(0)
-                    open_[st.begin()] = (u, 0)
+                    sid = st.begin()
+                    open_[sid] = (u, 0)
+                    base[sid] = 0
                 batch = {}
                 for sid, (u, t0) in open_.items():
                     batch[sid] = utts[u][t0:t0 + args.piece]
+                    window = max(window, t0 + len(batch[sid]) - base[sid])  # the frames the stream holds once this push is in
                 t = time.perf_counter()
                 st.push(batch)
                 push_ms.append(1e3 * (time.perf_counter() - t))
@@ -120,6 +132,13 @@ def main():
                     sw, _, _ = st.stable(list(batch))
                     stable_ms.append(1e3 * (time.perf_counter() - t))
                     last_stable.update(zip(batch, sw))
+                if args.trim:
+                    t = time.perf_counter()
+                    dropped = st.trim(list(batch))
+                    trim_ms.append(1e3 * (time.perf_counter() - t))
+                    for sid, d in zip(batch, dropped):
+                        base[sid] += int(d)
+                        dropped_total += int(d)
                 for sid in list(open_):
                     u, t0 = open_[sid]
                     t0 += len(batch[sid])
@@ -154,6 +173,18 @@ def main():
               f"min {sm.min():.3f} ms, max {sm.max():.3f} ms ({np.median(sm) / np.median(pm):.1%} of a push at the median)")
         print(f"stable words were a prefix of the final words: {'yes' if stable_ok else 'NO'}")
         same = same and stable_ok
+    if args.trim:
+        tm = np.asarray(trim_ms)
+        print(f"sr_stream_trim on the pushed streams, after every push: median {np.median(tm):.3f} ms, p99 {np.percentile(tm, 99):.3f} ms, "
+              f"min {tm.min():.3f} ms, max {tm.max():.3f} ms ({np.median(tm) / np.median(pm):.1%} of a push at the median)")
+        print(f"frames dropped: {dropped_total} of {int(off[-1])}; the largest window a stream held at a push: {window} frames "
+              f"(the longest utterance: {int(np.diff(off.astype(np.int64)).max())})")
+        P = int(word_off[-1])
+
+        def slot_bytes(mf):  # sr_stream_open's formula, plus the first stable or trim call's 4 + 4 max_frames
+            return ((20 * P + 255) // 256) * 256 + 12 * (mf + 1) + 4 * mf + 40 + 4 + 4 * mf
+
+        print(f"device bytes per stream (P = {P} positions): {slot_bytes(65535)} at max_frames 65535, {slot_bytes(window)} at max_frames {window}")
     return 0 if same else 1
 
 
