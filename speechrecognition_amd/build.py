@@ -22,9 +22,9 @@ SOURCES = ["srgpu_api.cpp", "mixset.cpp", "feeder.cpp", "gmm_mfma.hip", "gmm_exa
            "viterbi_fast.hip", "viterbi_words.hip", "viterbi_align.hip", "viterbi_fb.hip", "viterbi_netfb.hip", "viterbi_mmi.hip", "viterbi_smbr.hip", "viterbi_lattice.hip", "viterbi_bigram.hip", "viterbi_bigram_fb.hip", "viterbi_bigram_mmi.hip", "viterbi_bigram_smbr.hip", "viterbi_bigram_lattice.hip", "posterior_items.hip",
            "em_accumulate.hip", "em_finalize.hip", "fmllr_stats.hip", "fmllr.cpp", "mllr_stats.hip", "map_stats.hip", "mllt_stats.hip", "lda_stats.hip", "model_structure.hip",
            "gather_words.hip", "frontend.hip", "frontend.cpp", "stream_pipeline.hip"]
-# (mllr.cpp, mllt.cpp, lda.cpp and map.cpp are included by fmllr.cpp, nbest.cpp and chains.cpp by srgpu_api.cpp: listed with the headers so
-# that their content enters the stamps)
-HEADERS = ["mllr.cpp", "mllt.cpp", "lda.cpp", "map.cpp", "nbest.cpp", "chains.cpp", "kernels.h", "host_util.h", "handles.h", "traceback.h", "commit_point.h", "dpp_util.h", "netfb_device.h", "smbr_device.h", "sym_contract.h", "structure_plan.h", "fb_plan.h", "stream_audio_plan.h", "stream_pipeline_plan.h", "splice_clamp.h", "vtln_tables.h", "bigram_route.h", os.path.join("..", "..", "include", "srgpu.h")]
+# (mllr.cpp, mllt.cpp, lda.cpp and map.cpp are included by fmllr.cpp, nbest.cpp, chains.cpp and stream_api.cpp by srgpu_api.cpp: listed with
+# the headers so that their content enters the stamps)
+HEADERS = ["mllr.cpp", "mllt.cpp", "lda.cpp", "map.cpp", "nbest.cpp", "chains.cpp", "stream_api.cpp", "kernels.h", "host_util.h", "handles.h", "traceback.h", "commit_point.h", "dpp_util.h", "netfb_device.h", "smbr_device.h", "sym_contract.h", "structure_plan.h", "fb_plan.h", "stream_audio_plan.h", "stream_pipeline_plan.h", "stream_set_plan.h", "splice_clamp.h", "vtln_tables.h", "bigram_route.h", os.path.join("..", "..", "include", "srgpu.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 # these replay the reference's SSE2 operation order and must not contract a*b+c into an FMA
 PER_FILE = {"gmm_exact.hip": ["-ffp-contract=off"], "gmm_prefilter.hip": ["-ffp-contract=off"], "em_accumulate.hip": ["-ffp-contract=off"],

@@ -18,6 +18,7 @@
 #include "kernels.h"
 #include "stream_audio_plan.h"
 #include "stream_pipeline_plan.h"
+#include "stream_set_plan.h"
 #include "vtln_tables.h"
 
 namespace srhost {
@@ -320,38 +321,8 @@ struct sr_bigram {
   bool lat_lm_built = false;
 };
 
-// The slots of a stream set (sr_stream_*, sr_bigram_stream_*): slot i holds one open utterance, named by the id
-// slot + max_streams * generation, and its frame count.
-struct StreamSlots {
-  uint32_t max_streams = 0;
-  uint64_t max_frames = 0;
-  std::vector<uint8_t> open;        // [max_streams]
-  std::vector<uint32_t> id;         // [max_streams] id of the slot's current (or last) utterance
-  std::vector<uint32_t> generation; // [max_streams] of the next utterance begun in the slot
-  std::vector<uint64_t> frames;     // [max_streams] frames searched so far (sr_stream: of the window, less what sr_stream_trim dropped)
-  StreamSlots() = default;
-  StreamSlots(uint32_t n, uint64_t max_frames_)
-      : max_streams(n), max_frames(max_frames_), open(n, 0), id(n, 0), generation(n, 0), frames(n, 0) {}
-  // opens the first free slot for a fresh utterance, *out_id its id: the generation wraps before the id leaves 32 bits
-  int begin(uint32_t* out_id) {
-    uint32_t slot = 0;
-    while (slot < max_streams && open[slot]) slot++;
-    if (slot == max_streams) return srhost::fail(SR_ELIMIT, "all %u streams are open", max_streams);
-    uint32_t g = generation[slot];
-    if ((uint64_t)slot + (uint64_t)max_streams * g > 0xFFFFFFFFull) g = 0;
-    generation[slot] = g + 1;
-    id[slot] = slot + max_streams * g;
-    open[slot] = 1;
-    frames[slot] = 0;  // the first push starts from the initial state
-    *out_id = id[slot];
-    return SR_OK;
-  }
-  // the slot of an open utterance's id, or -1
-  int64_t find(uint32_t i) const {
-    const uint32_t slot = i % max_streams;
-    return open[slot] && id[slot] == i ? (int64_t)slot : -1;
-  }
-};
+// The slots of a stream set (sr_stream_*, sr_bigram_stream_*) and their ids: stream_set_plan.h
+using srplan::StreamSlots;
 
 // The audio side of a stream set (sr_stream_set_frontend, _push_audio, _finish_audio and the bigram twins): the front end, what
 // kind of input each slot's utterance takes, the host carry of an audio utterance (stream_audio_plan.h) and the device state
@@ -391,46 +362,49 @@ struct StreamPipeline {
   void begin(uint32_t slot) { has_w[slot] = 0; carry[slot] = srplan::PipelineCarry(); }
 };
 
-// A set of concurrently open utterances on one (model, lexicon) (sr_stream_*, srgpu_api.cpp).  The device state of slot i's
-// utterance (decode_stream_kernel) lives in the per-slot buffers below.
-struct sr_stream {
+// What the two kinds of stream set share (stream_api.cpp): everything but the search.  The device state of a slot is a window on its
+// utterance: base = the frames dropped so far (window frame f is the utterance's frame base + f; slots.frames counts the window's
+// searched frames).  Reset by every begin; only sr_stream_trim moves it, so it stays 0 in the bigram set.
+struct StreamSet {
   sr_model* model = nullptr;
-  sr_lexicon* lex = nullptr;
-  sr_search_params params{};
   StreamSlots slots;
   StreamAudio audio;
   StreamPipeline pipe;
+  DevBuf<float> feats;                // the rows a push searches, sized by the largest push so far
+  // the stable and trim calls, allocated by their first call: the previous commit point (zerogram: a frame; bigram: a book index) per
+  // slot (a separate array: the state records are the search kernels'), and the call's pinned block -- its jobs in, its results and
+  // items out (stream_set_plan.h: block_layout)
+  std::vector<uint8_t> commit_fresh;  // [max_streams] no commit point computed for the slot's utterance yet
+  DevBuf<uint32_t> commit;
+  PinnedBuf<unsigned char> stable_block;
+  std::vector<uint64_t> base;         // [max_streams]
+  virtual ~StreamSet() = default;     // (sr_stream_destroy and its twin delete through this type)
+};
+
+// A set of concurrently open utterances on one (model, lexicon) (sr_stream_*).  The device state of slot i's utterance
+// (decode_stream_kernel) lives in the per-slot buffers below.
+struct sr_stream : StreamSet {
+  sr_lexicon* lex = nullptr;
+  sr_search_params params{};
   // per slot, device
   DevBuf<unsigned char> ws;         // decode_big_workspace(P) each
   DevBuf<srgpu::StreamState> state;
   DevBuf<double> tb_score;          // max_frames + 1 each
   DevBuf<uint16_t> tb_word, tb_bkp;
   DevBuf<uint32_t> words;           // max_frames each
-  // per push, sized by the largest push so far
-  DevBuf<float> feats;
-  DevBuf<srgpu::StreamJob> jobs;
-  // sr_stream_stable, allocated by its first call: the previous commit point per slot (a separate array: StreamState is the search
-  // kernel's), the walk's words (max_frames each), and the call's pinned block -- its jobs in, its results and words out
-  std::vector<uint8_t> commit_fresh;  // [max_streams] no commit point computed for the slot's utterance yet
-  DevBuf<uint32_t> commit, stable_words;
-  PinnedBuf<unsigned char> stable_block;
-  // sr_stream_trim: the device state of a slot is a window on its utterance.  base = the frames dropped so far (window frame f is
-  // the utterance's frame base + f; slots.frames counts the window's searched frames), archive = the committed words of the dropped
-  // frames.  Both are reset by sr_stream_begin; an id that is never trimmed keeps base 0 and an empty archive.
-  std::vector<uint64_t> base;                   // [max_streams]
+  DevBuf<srgpu::StreamJob> jobs;    // per push, sized by the largest push so far
+  DevBuf<uint32_t> stable_words;    // sr_stream_stable, sr_stream_trim: the walk's words (max_frames each)
+  // sr_stream_trim: the committed words of the frames dropped (base).  Reset by sr_stream_begin; an id that is never trimmed keeps an
+  // empty archive.
   std::vector<std::vector<uint32_t>> archive;   // [max_streams] grows with words, not frames
 };
 
-// A set of concurrently open utterances on one (model, bigram search net) (sr_bigram_stream_*, srgpu_api.cpp).  The device state of
-// slot i's utterance (bigram_stream_kernel, global-states layout) lives in the per-slot buffers below, a copy of its BigramStreamState
-// (read back after every push) on the host.
-struct sr_bigram_stream {
-  sr_model* model = nullptr;
+// A set of concurrently open utterances on one (model, bigram search net) (sr_bigram_stream_*).  The device state of slot i's
+// utterance (bigram_stream_kernel, global-states layout) lives in the per-slot buffers below, a copy of its BigramStreamState (read
+// back after every push) on the host.
+struct sr_bigram_stream : StreamSet {
   sr_bigram* bigram = nullptr;
   sr_bigram_params params{};
-  StreamSlots slots;
-  StreamAudio audio;
-  StreamPipeline pipe;
   std::vector<srgpu::BigramStreamState> host_state;  // [max_streams] as of the slot's last push
   std::vector<uint8_t> failed;      // [max_streams] a push flagged the slot (SR_EINTERNAL until it ends)
   // per slot, device
@@ -442,14 +416,7 @@ struct sr_bigram_stream {
   DevBuf<uint32_t> out_word, out_time;  // max_frames + 1 each
   DevBuf<float> out_score;
   std::vector<std::unique_ptr<DevBuf<uint4>>> book;  // [max_streams] grown before a push to n_book + W x (its frames)
-  // per push, sized by the largest push so far
-  DevBuf<float> feats;
-  DevBuf<srgpu::BigramStreamJob> jobs;
-  // sr_bigram_stream_stable, allocated by its first call: the previous commit entry per slot (a book index; a separate array:
-  // BigramStreamState is the search kernel's) and the call's pinned block -- its jobs in, its results and items out
-  std::vector<uint8_t> commit_fresh;  // [max_streams] no commit entry computed for the slot's utterance yet
-  DevBuf<uint32_t> commit;
-  PinnedBuf<unsigned char> stable_block;
+  DevBuf<srgpu::BigramStreamJob> jobs;               // per push, sized by the largest push so far
 };
 
 namespace srhost {

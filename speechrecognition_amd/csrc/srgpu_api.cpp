@@ -7,7 +7,8 @@
 // The forward-backward style passes (fb_check .. sr_bigram_word_lattice_corpus) plan their launch groups, step order and mixture lists
 // with fb_plan.h, host code that is tested on its own.  Host algorithms on plain arrays, with no handle and no HIP call, are files of
 // their own that this unit includes, each complete by itself and built alone under the sanitizers by a test driver: chains.cpp (the
-// transcripts' chains of the MMI passes) and nbest.cpp (sr_lattice_nbest, sr_bigram_lattice_nbest).
+// transcripts' chains of the MMI passes) and nbest.cpp (sr_lattice_nbest, sr_bigram_lattice_nbest).  The streaming entry points
+// (sr_stream_*, sr_bigram_stream_*) and their helpers are stream_api.cpp, included behind the scoring and chunk helpers they use.
 // Every entry point is declared extern "C" with SR_API in include/srgpu.h: the definitions here take linkage and visibility from there.
 #include <hip/hip_runtime.h>
 
@@ -24,6 +25,7 @@
 #include <mutex>
 #include <numeric>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/srgpu.h"
@@ -708,535 +710,6 @@ int check_corpus(const sr_model* m, const sr_corpus* c) {
   return SR_OK;
 }
 
-}  // namespace
-
-namespace {  // sr_stream_*, sr_bigram_stream_*
-// an entry of a push with frames: its stream slot, the frames searched before the push, the frames in it, its first frame's row in
-// the push's features
-struct PushEntry { uint32_t slot; uint64_t t0, k, row0; };
-// A push's pass: its F frames and its jobs staged on the device, then one chunk of run_chunks -- the frames scored into m->scores[0],
-// search(chunk, table, stream) enqueuing the push's search.  feats == nullptr: work queued on the scoring stream has the frames in
-// d_feats already (the audio pushes).  (Every call synchronises before it returns: the buffer is free.)
-template <class Job, class Search>
-int push_pass(sr_model* m, int gmm_kernel, const float* feats, uint64_t F, DevBuf<float>& d_feats, const std::vector<Job>& jobs,
-              DevBuf<Job>& d_jobs, Search search) {
-  HIP_TRY(d_feats.ensure((size_t)F * m->dim));
-  HIP_TRY(m->scores[0].ensure((size_t)F * m->ld));
-  HIP_TRY(d_jobs.ensure(jobs.size()));
-  if (feats) HIP_TRY(hipMemcpyAsync(d_feats.p, feats, sizeof(float) * F * m->dim, hipMemcpyHostToDevice, m->s_gmm));
-  HIP_TRY(hipMemcpyAsync(d_jobs.p, jobs.data(), sizeof(Job) * jobs.size(), hipMemcpyHostToDevice, m->s_gmm));
-  return run_chunks(m, {Chunk{0, (uint32_t)jobs.size(), 0, F}},
-                    [&](const Chunk&, double* table) { return launch_scoring(m, d_feats.p, F, gmm_kernel, table); }, search);
-}
-
-// the partial (after every push) or final words of the utterance in `slot`
-int stream_words(sr_stream* s, uint32_t slot, uint32_t id, uint32_t* out_words, uint32_t cap, uint32_t* count) {
-  *count = 0;
-  if (s->slots.frames[slot] == 0) return SR_OK;  // nothing searched yet: the empty utterance's (no) words
-  StreamState st;
-  HIP_TRY(hipMemcpy(&st, s->state.p + slot, sizeof(st), hipMemcpyDeviceToHost));
-  if (st.flags & kFlagCorrupt) return fail(SR_ECORRUPT, "stream %u: the traceback does not walk back to frame 0 (Recognizer.cpp:222-231)", id);
-  if (st.count > s->slots.frames[slot]) return fail(SR_ECORRUPT, "stream %u: %u words for %llu frames", id, st.count, (unsigned long long)s->slots.frames[slot]);
-  // A trimmed utterance (sr_stream_trim): the window's walk ends at the last commit point, the words before it are in the archive.
-  // The reference's walk from an entry without a surviving word end reports no earlier word at all, so the archive
-  // leads only where the walk started at a finite entry.
-  const std::vector<uint32_t>& arch = s->archive[slot];
-  size_t lead = arch.size();
-  if (lead) {
-    double last = 0.0;
-    HIP_TRY(hipMemcpy(&last, s->tb_score.p + (size_t)slot * (s->slots.max_frames + 1) + s->slots.frames[slot], sizeof(double), hipMemcpyDeviceToHost));
-    if (!(last < __builtin_huge_val())) lead = 0;
-  }
-  const uint64_t total = (uint64_t)lead + st.count;
-  *count = (uint32_t)std::min<uint64_t>(total, 0xFFFFFFFFull);
-  if (total > cap) return fail(SR_EINVAL, "stream %u: %llu words, out_words holds %u", id, (unsigned long long)total, cap);
-  if (lead) memcpy(out_words, arch.data(), sizeof(uint32_t) * lead);
-  if (st.count) HIP_TRY(hipMemcpy(out_words + lead, s->words.p + (size_t)slot * s->slots.max_frames, sizeof(uint32_t) * st.count, hipMemcpyDeviceToHost));
-  return SR_OK;
-}
-// the frames an utterance has lost to sr_stream_trim: the bigram set does not trim
-uint64_t stream_base(const sr_stream* s, uint32_t slot) { return s->base[slot]; }
-uint64_t stream_base(const sr_bigram_stream*, uint32_t) { return 0; }
-// the partial (after every push) or final traceback items of the utterance in `slot`: the state record read back after its last push
-int bigram_stream_items(sr_bigram_stream* s, uint32_t slot, uint32_t id, uint32_t* out_word, float* out_score, uint32_t* out_time,
-                        uint32_t cap, uint32_t* count) {
-  *count = 0;
-  if (s->slots.frames[slot] == 0) return SR_OK;  // nothing searched yet: the empty utterance's (no) items
-  if (s->failed[slot]) return fail(SR_EINTERNAL, "stream %u: a push overflowed its book", id);
-  const BigramStreamState& st = s->host_state[slot];
-  if (st.flags & kBgStreamCorrupt) return fail(SR_ECORRUPT, "stream %u: the book walk does not end at its start entry", id);
-  *count = st.count;
-  if (st.count > cap) return fail(SR_EINVAL, "stream %u: %u items, the output arrays hold %u", id, st.count, cap);
-  const size_t o = (size_t)slot * (s->slots.max_frames + 1);
-  if (st.count) {
-    HIP_TRY(hipMemcpy(out_word, s->out_word.p + o, sizeof(uint32_t) * st.count, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_score, s->out_score.p + o, sizeof(float) * st.count, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_time, s->out_time.p + o, sizeof(uint32_t) * st.count, hipMemcpyDeviceToHost));
-  }
-  return SR_OK;
-}
-
-// The two stream sets' pushes behind their checks, for feature rows and audio alike.  stream_precheck: what the set itself has
-// against the entries, before any launch.  stream_run: the push's F rows (feats on the host, or nullptr: already in s->feats on the
-// device) scored and searched; the entries' frame counts advance.
-int stream_precheck(sr_stream*, const std::vector<PushEntry>&) { return SR_OK; }
-int stream_run(sr_stream* s, const std::vector<PushEntry>& entries, const float* feats, uint64_t F) {
-  sr_model* m = s->model;
-  const sr_lexicon* l = s->lex;
-  std::vector<StreamJob> jobs;
-  for (const PushEntry& e : entries) jobs.push_back({e.slot, (uint32_t)e.t0, (uint32_t)e.k, 0u, e.row0});
-  int rc = push_pass(m, s->params.gmm_kernel, feats, F, s->feats, jobs, s->jobs, [&](const Chunk&, const double* table, hipStream_t st) -> int {
-    StreamArgs a{};
-    a.net = l->net;
-    a.am_threshold = s->params.am_threshold; a.word_penalty = s->params.word_penalty;
-    a.scores = table; a.ld = m->ld; a.jobs = s->jobs.p;
-    a.ws = s->ws.p; a.ws_stride = decode_big_workspace(l->net.n_slots); a.state = s->state.p;
-    a.tb_score = s->tb_score.p; a.tb_word = s->tb_word.p; a.tb_bkp = s->tb_bkp.p; a.tb_stride = s->slots.max_frames + 1;
-    a.words = s->words.p; a.words_stride = s->slots.max_frames;
-    HIP_TRY(launch_decode_stream(a, (uint32_t)jobs.size(), st));
-    if (m->profiling) {
-      m->prof.search_bytes += (8.0 * m->n_states + 4.0 * l->net.n_slots) * (double)F;
-      m->prof.frames += F;
-    }
-    return SR_OK;
-  });
-  if (rc) return rc;
-  for (const StreamJob& j : jobs) s->slots.frames[j.slot] += j.k;
-  return SR_OK;
-}
-
-// per entry: the book entries the push may reach (n_book + W per frame: a frame keeps at most one word end per history)
-uint64_t book_need(const sr_bigram_stream* s, const PushEntry& e) {
-  return (e.t0 ? s->host_state[e.slot].n_book : 2u) + (uint64_t)s->bigram->net.n_words * e.k;
-}
-int stream_precheck(sr_bigram_stream* s, const std::vector<PushEntry>& entries) {
-  for (const PushEntry& e : entries) {
-    const uint32_t id = s->slots.id[e.slot];
-    if (s->failed[e.slot]) return fail(SR_EINTERNAL, "stream id %u: an earlier push overflowed its book", id);
-    const uint64_t nb = book_need(s, e);
-    if (nb > 0xFFFFFFFFull)
-      return fail(SR_ELIMIT, "stream id %u: this push may need %llu book entries, more than 2^32 - 1", id, (unsigned long long)nb);
-  }
-  return SR_OK;
-}
-int stream_run(sr_bigram_stream* s, const std::vector<PushEntry>& entries, const float* feats, uint64_t F) {
-  sr_model* m = s->model;
-  const sr_bigram* b = s->bigram;
-  std::vector<BigramStreamJob> jobs;
-  for (const PushEntry& e : entries) jobs.push_back({e.slot, (uint32_t)e.t0, (uint32_t)e.k, 0u, e.row0, nullptr, 0});
-  // every book to at least n_book + W k entries (geometric growth; the entries so far are copied: back pointers are indices)
-  for (size_t j = 0; j < jobs.size(); j++) {
-    DevBuf<uint4>& bk = *s->book[jobs[j].slot];
-    const uint64_t need = book_need(s, entries[j]);
-    if (bk.n < need) {
-      DevBuf<uint4> grown;
-      HIP_TRY(grown.ensure(std::max<uint64_t>(need, std::min<uint64_t>(2 * (uint64_t)bk.n, 0xFFFFFFFFull))));
-      if (jobs[j].t0) HIP_TRY(hipMemcpy(grown.p, bk.p, sizeof(uint4) * s->host_state[jobs[j].slot].n_book, hipMemcpyDeviceToDevice));
-      bk.swap(grown);
-    }
-    jobs[j].book = bk.p;
-    jobs[j].book_cap = bk.n;
-  }
-  int rc = push_pass(m, s->params.gmm_kernel, feats, F, s->feats, jobs, s->jobs, [&](const Chunk&, const double* table, hipStream_t stream) -> int {
-    BigramStreamArgs a{};
-    BigramArgs& ba = a.a;
-    ba = b->net;
-    ba.scores = table; ba.ld = m->ld;
-    ba.ac_pruning = s->params.acoustic_pruning; ba.lm_pruning = s->params.lm_pruning;
-    ba.global_states = 1;
-    ba.gs_ws = s->gs_ws.p; ba.gs_ws_words = bigram_gs_ws_words(ba.n_words, ba.n_positions);
-    ba.we_slot = s->we_slot.p; ba.we_bp = s->we_bp.p; ba.we_score = s->we_score.p;
-    a.jobs = s->jobs.p; a.state = s->state.p; a.lsave = s->lsave.p;
-    a.out_word = s->out_word.p; a.out_score = s->out_score.p; a.out_time = s->out_time.p; a.items_stride = s->slots.max_frames + 1;
-    HIP_TRY(launch_bigram_stream(a, (uint32_t)jobs.size(), stream));
-    if (m->profiling) {  // SURVEY 8(d)'s decoder model, 8 S + 4 P bytes per frame, as sr_recognize_bigram_corpus
-      m->prof.search_bytes += (8.0 * m->n_states + 4.0 * ba.n_positions) * (double)F;
-      m->prof.frames += F;
-    }
-    return SR_OK;
-  });
-  if (rc) return rc;
-  std::vector<BigramStreamState> st(s->slots.max_streams);  // (one copy of every slot's 32 bytes: cheaper than one per pushed slot)
-  HIP_TRY(hipMemcpy(st.data(), s->state.p, sizeof(BigramStreamState) * st.size(), hipMemcpyDeviceToHost));
-  uint32_t bad = 0xFFFFFFFFu;
-  for (const BigramStreamJob& j : jobs) {
-    s->slots.frames[j.slot] += j.k;
-    s->host_state[j.slot] = st[j.slot];
-    if (st[j.slot].flags & kBgStreamOverflow) { s->failed[j.slot] = 1; bad = s->slots.id[j.slot]; }
-  }
-  if (bad != 0xFFFFFFFFu) return fail(SR_EINTERNAL, "stream id %u: a book append passed the capacity the host grew it to", bad);
-  return SR_OK;
-}
-
-// sr_stream_set_frontend and its bigram twin.  With a projection attached the front end feeds the pipeline: any model of the
-// projection's input dimension on the set's device will do.
-template <class Set>
-int set_frontend(Set* s, sr_frontend* fe) {
-  if (!s) return fail(SR_EINVAL, "null stream set");
-  for (uint32_t i = 0; i < s->slots.max_streams; i++)
-    if (s->slots.open[i]) return fail(SR_EINVAL, "stream id %u is open: the front end changes only while none is", s->slots.id[i]);
-  if (!fe) { s->audio.fe = nullptr; return SR_OK; }
-  if (!s->pipe.projection) {
-    if (fe->model != s->model) return fail(SR_EINVAL, "the front end does not belong to the stream set's model");
-  } else {
-    if (!fe->model || fe->model->device != s->model->device) return fail(SR_EINVAL, "the front end is not on the stream set's device");
-    if (fe->model->dim != s->pipe.in_dim)
-      return fail(SR_EINVAL, "the front end's rows have %u columns, the projection takes %u", fe->model->dim, s->pipe.in_dim);
-  }
-  if (!fe->has_mfcc) return fail(SR_EINVAL, "this front end was made without an MFCC stage: it takes cepstra only");
-  int rc = check_model(s->model);
-  if (rc) return rc;
-  HIP_TRY(s->audio.state.ensure((size_t)s->slots.max_streams * (2 * (size_t)fe->post.deriv_step * fe->post.n_static + 1)));
-  s->audio.fe = fe;
-  return SR_OK;
-}
-
-// sr_stream_set_projection and its bigram twin
-template <class Set>
-int set_projection(Set* s, uint32_t in_dim, uint32_t context, const double* M) {
-  if (!s) return fail(SR_EINVAL, "null stream set");
-  for (uint32_t i = 0; i < s->slots.max_streams; i++)
-    if (s->slots.open[i]) return fail(SR_EINVAL, "stream id %u is open: the projection changes only while none is", s->slots.id[i]);
-  StreamPipeline& pl = s->pipe;
-  const sr_frontend* fe = s->audio.fe;
-  if (!M) {
-    if (fe && fe->model != s->model)
-      return fail(SR_EINVAL, "the attached front end does not belong to the stream set's model: detach it before the projection");
-    pl.projection = false; pl.in_dim = 0; pl.context = 0;
-    pl.M.release(); pl.hist.release();
-    return SR_OK;
-  }
-  if (in_dim == 0) return fail(SR_EINVAL, "in_dim must be positive");
-  const uint64_t E = (2 * (uint64_t)context + 1) * in_dim;
-  if (E > 512) return fail(SR_ELIMIT, "(2 context + 1) in_dim = %llu exceeds 512 (sr_corpus_splice_transform's limit)", (unsigned long long)E);
-  if (fe && fe->model->dim != in_dim)
-    return fail(SR_EINVAL, "the attached front end's rows have %u columns, not in_dim = %u", fe->model->dim, in_dim);
-  sr_model* m = s->model;
-  if (stream_pipeline_lds_bytes(in_dim, context, m->dim, true, m->dim <= 63) > 65536)
-    return fail(SR_ELIMIT, "the pipeline's LDS need exceeds 64 KB");
-  int rc = check_model(m);
-  if (rc) return rc;
-  DevBuf<double> dM;
-  DevBuf<float> hist;
-  HIP_TRY(dM.upload(M, (size_t)m->dim * (E + 1)));
-  HIP_TRY(hist.ensure((size_t)s->slots.max_streams * 2 * context * in_dim));
-  pl.M.swap(dM); pl.hist.swap(hist);
-  pl.projection = true; pl.in_dim = in_dim; pl.context = context;
-  return SR_OK;
-}
-
-// sr_stream_set_transform and its bigram twin
-template <class Set>
-int set_transform(Set* s, uint32_t id, const double* W) {
-  if (!s) return fail(SR_EINVAL, "null stream set");
-  const int64_t slot = s->slots.find(id);
-  if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
-  if (s->audio.kind[slot] != kStreamFresh)
-    return fail(SR_EINVAL, "stream id %u has been pushed to: its transform is set between begin and the first push", id);
-  StreamPipeline& pl = s->pipe;
-  if (!W) { pl.has_w[slot] = 0; return SR_OK; }
-  sr_model* m = s->model;
-  const size_t p = m->dim, n = p * (p + 1);
-  if (p > 63) return fail(SR_ELIMIT, "dim %u: the transform's kernel keeps W in the LDS (max 63, as sr_corpus_transform)", m->dim);
-  int rc = check_model(m);
-  if (rc) return rc;
-  HIP_TRY(pl.W.ensure((size_t)s->slots.max_streams * n));
-  HIP_TRY(hipMemcpy(pl.W.p + (size_t)slot * n, W, sizeof(double) * n, hipMemcpyHostToDevice));
-  pl.has_w[slot] = 1;
-  return SR_OK;
-}
-
-// sr_stream_set_warp and its bigram twin: host state only.  sr_stream_set_frontend runs only while no id is open and every begin and end
-// clears the slot's warp, so a warp never meets a front end other than the one it was checked against.
-template <class Set>
-int set_warp(Set* s, uint32_t id, uint32_t warp) {
-  if (!s) return fail(SR_EINVAL, "null stream set");
-  const int64_t slot = s->slots.find(id);
-  if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
-  if (s->audio.kind[slot] != kStreamFresh)
-    return fail(SR_EINVAL, "stream id %u has been pushed to: its warp is set between begin and the first push", id);
-  const sr_frontend* fe = s->audio.fe;
-  if (!fe) return fail(SR_EINVAL, "the stream set has no front end (sr_stream_set_frontend)");
-  if (fe->n_warps == 0) return fail(SR_EINVAL, "the stream set's front end has no warps: make it with sr_frontend_create_warped");
-  if (warp != SR_STREAM_NO_WARP && warp >= fe->n_warps) return fail(SR_EINVAL, "stream id %u: warp %u >= n_warps %u", id, warp, fe->n_warps);
-  s->audio.warp[slot] = warp;
-  return SR_OK;
-}
-
-// The pipeline's part of a push over the ids in slots[]: entry i gains k[i] input rows (finishing: none follow).  plan_pipeline: the
-// steps of stream_pipeline_plan.h, where the rows they emit go in the push's output (out_off) and the entries to search.  The
-// pipeline is active for a push when the set has a projection or one of the named utterances a transform; otherwise the input rows
-// are the rows searched and no kernel of it runs.
-struct PipelinePush {
-  std::vector<srplan::PipelineStep> steps;
-  std::vector<uint64_t> out_off;
-  std::vector<PushEntry> entries;
-  std::vector<StreamPipelineJob> jobs;  // (uploaded asynchronously: alive until the caller has synchronised)
-  bool active = false;
-};
-template <class Set>
-void plan_pipeline(const Set* s, const std::vector<uint32_t>& slots, const std::vector<uint64_t>& k, bool finishing, PipelinePush* pp) {
-  const StreamPipeline& pl = s->pipe;
-  const size_t n = slots.size();
-  pp->steps.resize(n);
-  pp->out_off.assign(n + 1, 0);
-  pp->active = pl.projection;
-  for (size_t i = 0; i < n; i++) {
-    pp->steps[i] = srplan::plan_pipeline_step(pl.context, pl.carry[slots[i]], k[i], finishing);
-    pp->out_off[i + 1] = pp->out_off[i] + pp->steps[i].rows;
-    // (the pipeline counts the utterance's rows, the search its window's: sr_stream_trim)
-    if (pp->steps[i].rows) pp->entries.push_back({slots[i], pp->steps[i].row0 - stream_base(s, slots[i]), pp->steps[i].rows, pp->out_off[i]});
-    if (pl.has_w[slots[i]]) pp->active = true;
-  }
-}
-// one launch of stream_pipeline_kernel on the scoring stream: entry i's new input rows begin at row in_off[i] of pl.in (uploaded or
-// written by work queued before); the rows that became ready land in s->feats.  The caller synchronises the stream.
-template <class Set>
-int launch_pipeline(Set* s, const std::vector<uint32_t>& slots, PipelinePush& pp, const uint64_t* in_off) {
-  StreamPipeline& pl = s->pipe;
-  sr_model* m = s->model;
-  std::vector<StreamPipelineJob>& jobs = pp.jobs;
-  for (size_t i = 0; i < slots.size(); i++) {
-    const srplan::PipelineStep& st = pp.steps[i];
-    if (!st.rows_in && !st.rows) continue;
-    const srplan::PipelineCarry& c = pl.carry[slots[i]];
-    jobs.push_back({slots[i], pl.has_w[slots[i]], (uint32_t)c.received, (uint32_t)st.rows_in, (uint32_t)st.row0, (uint32_t)st.rows,
-                    in_off ? in_off[i] : 0, pp.out_off[i]});
-  }
-  if (jobs.empty()) return SR_OK;
-  HIP_TRY(pl.jobs.ensure(jobs.size()));
-  HIP_TRY(s->feats.ensure((size_t)pp.out_off.back() * m->dim));
-  HIP_TRY(hipMemcpyAsync(pl.jobs.p, jobs.data(), sizeof(StreamPipelineJob) * jobs.size(), hipMemcpyHostToDevice, m->s_gmm));
-  StreamPipelineArgs a{};
-  a.jobs = pl.jobs.p;
-  a.in_dim = pl.projection ? pl.in_dim : m->dim; a.context = pl.context; a.dim = m->dim;
-  a.M = pl.projection ? pl.M.p : nullptr;
-  a.W = pl.W.p;
-  a.w_doubles = pl.W.p ? m->dim * (m->dim + 1) : 0;
-  a.y_floats = pl.projection && pl.W.p ? stream_pipeline_group_rows() * m->dim : 0;
-  a.hist = pl.hist.p; a.in = pl.in.p; a.out = s->feats.p;
-  EventPair ep{};
-  int rc = prof_begin(m, m->s_gmm, 1, &ep);
-  if (rc) return rc;
-  HIP_TRY(launch_stream_pipeline(a, (uint32_t)jobs.size(), m->s_gmm));
-  return prof_end(m, m->s_gmm, &ep);
-}
-template <class Set>
-void commit_pipeline(Set* s, const std::vector<uint32_t>& slots, const PipelinePush& pp) {
-  for (size_t i = 0; i < slots.size(); i++) s->pipe.carry[slots[i]] = pp.steps[i].next;
-}
-
-// sr_stream_push_rows and its bigram twin (sr_stream_push is this without a finish and without rows back): all checks, the
-// pipeline's steps, then -- with an active pipeline -- the rows uploaded as the pipeline's input and its launch, and the set's own
-// scoring and search on the rows that became ready.  Nothing of the set changes before the launches have succeeded.
-template <class Set>
-int push_rows(Set* s, uint32_t n, const uint32_t* ids, const float* feats, const uint64_t* frame_off, bool finishing, float* out_feats,
-              uint64_t cap_rows, uint64_t* out_frame_off) {
-  if (!s) return fail(SR_EINVAL, "null stream set");
-  if (n == 0) {
-    if (out_frame_off) out_frame_off[0] = 0;
-    return SR_OK;
-  }
-  if (!ids || (!finishing && !frame_off)) return fail(SR_EINVAL, "null argument");
-  if (frame_off && frame_off[0] != 0) return fail(SR_EINVAL, "frame_off[0] must be 0");
-  StreamSlots& sl = s->slots;
-  StreamPipeline& pl = s->pipe;
-  sr_model* m = s->model;
-  std::vector<uint8_t> seen(sl.max_streams, 0);
-  std::vector<uint32_t> slots(n);
-  std::vector<uint64_t> k(n, 0);
-  for (uint32_t i = 0; i < n; i++) {
-    const int64_t slot = sl.find(ids[i]);
-    if (slot < 0) return fail(SR_EINVAL, "push entry %u: stream id %u is not open", i, ids[i]);
-    if (seen[slot]) return fail(SR_EINVAL, "push entry %u: stream id %u appears twice in one push", i, ids[i]);
-    seen[slot] = 1;
-    slots[i] = (uint32_t)slot;
-    if (s->audio.kind[slot] >= kStreamAudio) return fail(SR_EINVAL, "push entry %u: stream id %u is fed as audio; it takes no feature rows", i, ids[i]);
-    if (s->audio.warp[slot] != SR_STREAM_NO_WARP)
-      return fail(SR_EINVAL, "push entry %u: stream id %u carries VTLN warp %u, which applies to audio; it takes no feature rows", i, ids[i],
-                  s->audio.warp[slot]);
-    if (pl.carry[slot].finished) return fail(SR_EINVAL, "push entry %u: stream id %u is finished; it takes no more rows", i, ids[i]);
-    if (frame_off) {
-      if (frame_off[i + 1] < frame_off[i]) return fail(SR_EINVAL, "frame_off is not ascending at entry %u", i);
-      k[i] = frame_off[i + 1] - frame_off[i];
-    }
-    // max_frames bounds the window (the rows received since the last frame sr_stream_trim dropped), 32 bits the utterance's row count
-    const uint64_t got = pl.carry[slot].received - stream_base(s, (uint32_t)slot);
-    if (k[i] > sl.max_frames - got)
-      return fail(SR_ELIMIT, "stream id %u: %llu + %llu frames exceed max_frames %llu", ids[i], (unsigned long long)got,
-                  (unsigned long long)k[i], (unsigned long long)sl.max_frames);
-    if (k[i] > 0xFFFFFFFFull - pl.carry[slot].received)
-      return fail(SR_ELIMIT, "stream id %u: %llu + %llu rows exceed 2^32 - 1", ids[i], (unsigned long long)pl.carry[slot].received,
-                  (unsigned long long)k[i]);
-  }
-  PipelinePush pp;
-  plan_pipeline(s, slots, k, finishing, &pp);
-  const uint64_t F = frame_off ? frame_off[n] : 0, R = pp.out_off[n];
-  if (out_feats && cap_rows < R) {
-    if (out_frame_off) out_frame_off[n] = R;
-    return fail(SR_EINVAL, "this push readies %llu rows, out_feats holds %llu", (unsigned long long)R, (unsigned long long)cap_rows);
-  }
-  int rc = stream_precheck(s, pp.entries);
-  if (rc) return rc;
-  if (F && !feats) return fail(SR_EINVAL, "null feats");
-  if (!pp.active) {  // (no delay: the rows pushed are the rows searched)
-    if (R) {
-      if ((rc = check_model(m)) || (rc = stream_run(s, pp.entries, feats, R))) return rc;
-      if (out_feats) memcpy(out_feats, feats, sizeof(float) * (size_t)R * m->dim);
-    }
-  } else if (F || R) {
-    if ((rc = check_model(m))) return rc;
-    const uint32_t D = pl.projection ? pl.in_dim : m->dim;
-    HIP_TRY(pl.in.ensure((size_t)F * D));
-    if (F) HIP_TRY(hipMemcpyAsync(pl.in.p, feats, sizeof(float) * (size_t)F * D, hipMemcpyHostToDevice, m->s_gmm));
-    if ((rc = launch_pipeline(s, slots, pp, frame_off))) return rc;
-    if (R) rc = stream_run(s, pp.entries, nullptr, R);  // (a push that readies no row launches no scoring and no search)
-    else HIP_TRY(hipStreamSynchronize(m->s_gmm));
-    if (rc) return rc;
-    if (R && out_feats) HIP_TRY(hipMemcpy(out_feats, s->feats.p, sizeof(float) * (size_t)R * m->dim, hipMemcpyDeviceToHost));
-  }
-  commit_pipeline(s, slots, pp);
-  for (uint32_t i = 0; i < n; i++) s->audio.kind[slots[i]] = kStreamRows;
-  if (out_frame_off) memcpy(out_frame_off, pp.out_off.data(), sizeof(uint64_t) * pp.out_off.size());
-  return SR_OK;
-}
-// sr_stream_end's check: rows received and not yet searched keep a row id open
-template <class Set>
-int check_end(const Set* s, uint32_t slot, uint32_t id, const char* finish_audio) {
-  if (s->audio.kind[slot] == kStreamAudio) return fail(SR_EINVAL, "stream id %u is fed as audio and not finished (%s)", id, finish_audio);
-  const srplan::PipelineCarry& c = s->pipe.carry[slot];
-  if (c.received > c.searched)
-    return fail(SR_EINVAL, "stream id %u has %llu rows that wait for their right context: finish it first (sr_stream_push_rows)", id,
-                (unsigned long long)(c.received - c.searched));
-  return SR_OK;
-}
-
-// sr_stream_push_audio / sr_stream_finish_audio and their bigram twins (include/srgpu.h has the definition): the steps of
-// stream_audio_plan.h for every named utterance, all checks, then one launch of stream_frontend_kernel that leaves the ready rows
-// in s->feats, and the set's own scoring and search on them.  With an active pipeline the front end's rows are the pipeline's input
-// instead: its steps are planned on them, its kernel follows the front end's on the same stream, and its rows are the ones searched.
-// Nothing of the set changes before the launches have succeeded.
-template <class Set>
-int push_audio(Set* s, uint32_t n, const uint32_t* ids, const int16_t* samples, const uint64_t* sample_off, bool finishing, float* out_feats,
-               uint64_t cap_rows, uint64_t* out_frame_off) {
-  if (!s) return fail(SR_EINVAL, "null stream set");
-  StreamAudio& au = s->audio;
-  StreamSlots& sl = s->slots;
-  sr_frontend* fe = au.fe;
-  if (!fe) return fail(SR_EINVAL, "the stream set has no front end (sr_stream_set_frontend)");
-  if (n == 0) {
-    if (out_frame_off) out_frame_off[0] = 0;
-    return SR_OK;
-  }
-  if (!ids || (!finishing && !sample_off)) return fail(SR_EINVAL, "null argument");
-  if (sample_off && sample_off[0] != 0) return fail(SR_EINVAL, "sample_off[0] must be 0");
-  const sr_mfcc_params& p = fe->mfcc;
-  const uint32_t step = fe->post.deriv_step, nf = fe->post.n_static, H = 2 * step;
-  sr_model* m = s->model;
-  std::vector<uint8_t> seen(sl.max_streams, 0);
-  std::vector<srplan::AudioStep> steps(n);
-  std::vector<uint32_t> slots(n);
-  std::vector<uint64_t> row_off((size_t)n + 1, 0), rows_in(n, 0);  // (the front end's rows: the pipeline's input)
-  for (uint32_t i = 0; i < n; i++) {
-    const int64_t slot = sl.find(ids[i]);
-    if (slot < 0) return fail(SR_EINVAL, "push entry %u: stream id %u is not open", i, ids[i]);
-    if (seen[slot]) return fail(SR_EINVAL, "push entry %u: stream id %u appears twice in one push", i, ids[i]);
-    seen[slot] = 1;
-    slots[i] = (uint32_t)slot;
-    if (au.kind[slot] == kStreamRows) return fail(SR_EINVAL, "push entry %u: stream id %u is fed feature rows; it takes no audio", i, ids[i]);
-    if (au.kind[slot] == kStreamAudioFinished) return fail(SR_EINVAL, "push entry %u: stream id %u is finished; it takes no more audio", i, ids[i]);
-    uint64_t k = 0;
-    if (sample_off) {
-      if (sample_off[i + 1] < sample_off[i]) return fail(SR_EINVAL, "sample_off is not ascending at entry %u", i);
-      k = sample_off[i + 1] - sample_off[i];
-    }
-    if (k && !samples) return fail(SR_EINVAL, "samples is null");
-    const srplan::AudioCarry& c = au.carry[slot];
-    // max_frames bounds the window (the frames since the last one sr_stream_trim dropped), 32 bits the utterance's frame count
-    const uint64_t made = srplan::audio_frames(p.window, p.shift, c.n_samples + k);
-    if (made - stream_base(s, (uint32_t)slot) > sl.max_frames)
-      return fail(SR_ELIMIT, "stream id %u: %llu + %llu samples make more than max_frames %llu frames", ids[i], (unsigned long long)c.n_samples,
-                  (unsigned long long)k, (unsigned long long)sl.max_frames);
-    if (made > 0xFFFFFFFFull)
-      return fail(SR_ELIMIT, "stream id %u: %llu + %llu samples make more than 2^32 - 1 frames", ids[i], (unsigned long long)c.n_samples,
-                  (unsigned long long)k);
-    steps[i] = srplan::plan_audio_step(p.window, p.shift, step, c, k ? samples + sample_off[i] : nullptr, k, finishing);
-    row_off[i + 1] = row_off[i] + steps[i].rows;
-    rows_in[i] = steps[i].rows;
-  }
-  PipelinePush pp;
-  plan_pipeline(s, slots, rows_in, finishing, &pp);
-  const std::vector<PushEntry>& entries = pp.entries;
-  const uint64_t R_in = row_off[n], R = pp.out_off[n];
-  if (out_feats && cap_rows < R) {
-    if (out_frame_off) out_frame_off[n] = R;
-    return fail(SR_EINVAL, "this push readies %llu rows, out_feats holds %llu", (unsigned long long)R, (unsigned long long)cap_rows);
-  }
-  int rc = stream_precheck(s, entries);
-  if (rc || (rc = check_model(m))) return rc;
-  // the pieces (prev | tail | new samples) and the kernel's jobs: every utterance that gains a static or a row
-  std::vector<int16_t> pieces;
-  std::vector<StreamFrontendJob> jobs;
-  uint64_t stage_rows = 0;
-  bool launched = false;
-  for (uint32_t i = 0; i < n; i++) {
-    const srplan::AudioStep& st = steps[i];
-    if (!st.new_statics && !st.rows) continue;
-    const srplan::AudioCarry& c = au.carry[slots[i]];
-    const uint64_t k = sample_off ? sample_off[i + 1] - sample_off[i] : 0;
-    StreamFrontendJob j{};
-    j.slot = slots[i]; j.S = (uint32_t)c.statics; j.k = (uint32_t)st.new_statics;
-    j.T = finishing ? (uint32_t)st.next.statics : kStreamFrontendOpen;
-    j.row0 = (uint32_t)st.row0; j.rows = (uint32_t)st.rows; j.warp = au.warp[slots[i]];
-    j.sample0 = pieces.size(); j.stage0 = stage_rows; j.out0 = row_off[i];
-    pieces.resize(pieces.size() + 1 + st.n_buf);
-    srplan::audio_fill(c, st, k ? samples + sample_off[i] : nullptr, k, pieces.data() + j.sample0);
-    stage_rows += H + st.new_statics;
-    jobs.push_back(j);
-  }
-  if (!jobs.empty()) {
-    HIP_TRY(au.samples.ensure(pieces.size()));
-    HIP_TRY(au.stage.ensure((size_t)stage_rows * nf));
-    HIP_TRY(au.jobs.ensure(jobs.size()));
-    if (pp.active) HIP_TRY(s->pipe.in.ensure((size_t)R_in * fe->model->dim));
-    else HIP_TRY(s->feats.ensure((size_t)R * m->dim));
-    HIP_TRY(hipMemcpyAsync(au.samples.p, pieces.data(), sizeof(int16_t) * pieces.size(), hipMemcpyHostToDevice, m->s_gmm));
-    HIP_TRY(hipMemcpyAsync(au.jobs.p, jobs.data(), sizeof(StreamFrontendJob) * jobs.size(), hipMemcpyHostToDevice, m->s_gmm));
-    StreamFrontendArgs a{};
-    MfccArgs& f = a.mfcc;
-    f.samples = au.samples.p; f.span_frames = fe->span_frames;
-    f.window = p.window; f.shift = p.shift; f.n_fft = p.n_fft; f.n_mel = p.n_mel; f.n_cepstra = p.n_cepstra;
-    f.preemphasis = p.preemphasis; f.energy_floor = p.energy_floor;
-    f.win = fe->win.p; f.twiddle = fe->twiddle.p; f.mel_first = fe->mel_first.p; f.mel_count = fe->mel_count.p; f.mel_off = fe->mel_off.p;
-    f.mel_w = fe->mel_w.p; f.dct = fe->dct.p;
-    f.warp_first = fe->warp_first.p; f.warp_count = fe->warp_count.p; f.warp_off = fe->warp_off.p; f.warp_w = fe->warp_w.p;  // (the jobs' warps)
-    a.jobs = au.jobs.p;
-    a.n_static = nf; a.n_first = fe->post.n_first; a.n_second = fe->post.n_second; a.step = step;
-    a.mean = fe->normalise ? fe->mean.p : nullptr; a.stddev = fe->normalise ? fe->stddev.p : nullptr;
-    a.energy_max_norm = fe->post.energy_max_norm != 0;
-    a.state = au.state.p; a.stage = au.stage.p; a.out = pp.active ? s->pipe.in.p : s->feats.p;
-    EventPair ep{};
-    if ((rc = prof_begin(m, m->s_gmm, 1, &ep))) return rc;
-    HIP_TRY(launch_stream_frontend(a, (uint32_t)jobs.size(), m->s_gmm));
-    if ((rc = prof_end(m, m->s_gmm, &ep))) return rc;
-    launched = true;
-  }
-  if (pp.active) {
-    if ((rc = launch_pipeline(s, slots, pp, row_off.data()))) return rc;
-    launched = launched || !pp.jobs.empty();
-  }
-  if (R) rc = stream_run(s, entries, nullptr, R);  // (a push that readies no row launches no scoring and no search)
-  else if (launched) HIP_TRY(hipStreamSynchronize(m->s_gmm));
-  if (rc) return rc;
-  if (R && out_feats) HIP_TRY(hipMemcpy(out_feats, s->feats.p, sizeof(float) * (size_t)R * m->dim, hipMemcpyDeviceToHost));
-  commit_pipeline(s, slots, pp);
-  for (uint32_t i = 0; i < n; i++) {
-    au.carry[slots[i]] = std::move(steps[i].next);
-    au.kind[slots[i]] = finishing ? kStreamAudioFinished : kStreamAudio;
-  }
-  if (out_frame_off) memcpy(out_frame_off, pp.out_off.data(), sizeof(uint64_t) * pp.out_off.size());
-  return SR_OK;
-}
 }  // namespace
 
 const char* sr_last_error(void) { return g_err; }
@@ -5202,495 +4675,8 @@ int sr_probe_fp16_denormals(int device, int* preserved) {
   });
 }
 
-// ---- streaming recognition (sr_stream_*): decode_stream_kernel over per-slot state in device memory ---------------------------
-
-int sr_stream_open(sr_model* m, sr_lexicon* l, const sr_search_params* p, uint32_t max_streams, uint64_t max_frames, sr_stream** out) {
-  return guarded(__func__, [&]() -> int {
-  if (!out) return fail(SR_EINVAL, "out is null");
-  *out = nullptr;
-  int rc = check_model(m);
-  if (rc) return rc;
-  if (!l || l->model != m) return fail(SR_EINVAL, "lexicon does not belong to this model");
-  if (!p) return fail(SR_EINVAL, "null search params");
-  if (p->flags != 0) return fail(SR_EINVAL, "sr_search_params.flags must be 0 for streaming (got 0x%x)", (unsigned)p->flags);
-  if (p->gmm_kernel < SR_GMM_MFMA || p->gmm_kernel > SR_GMM_DEFAULT) return fail(SR_EINVAL, "unknown gmm_kernel %d", p->gmm_kernel);
-  if (max_streams == 0) return fail(SR_EINVAL, "max_streams must be at least 1");
-  if (max_frames == 0) return fail(SR_EINVAL, "max_frames must be at least 1");
-  if (max_frames > 65535) return fail(SR_ELIMIT, "max_frames %llu: back pointers are 16 bit like the reference's Book::bkp (max 65535)", (unsigned long long)max_frames);
-  if (l->net.n_slots > decode_big_max_slots()) return fail(SR_ELIMIT, "%u trellis positions exceed the stream search's limit of %u", l->net.n_slots, decode_big_max_slots());
-  sr_stream* s = new sr_stream();
-  std::unique_ptr<sr_stream, int (*)(sr_stream*)> own(s, sr_stream_destroy);
-  s->model = m; s->lex = l; s->params = *p; s->slots = StreamSlots(max_streams, max_frames);
-  s->commit_fresh.assign(max_streams, 1);
-  s->base.assign(max_streams, 0);
-  s->archive.assign(max_streams, std::vector<uint32_t>());
-  s->audio.open(max_streams);
-  s->pipe.open(max_streams);
-  const size_t S = max_streams;
-  HIP_TRY(s->ws.ensure(S * decode_big_workspace(l->net.n_slots)));
-  HIP_TRY(s->state.ensure(S));
-  HIP_TRY(s->tb_score.ensure(S * (max_frames + 1)));
-  HIP_TRY(s->tb_word.ensure(S * (max_frames + 1)));
-  HIP_TRY(s->tb_bkp.ensure(S * (max_frames + 1)));
-  HIP_TRY(s->words.ensure(S * max_frames));
-  *out = own.release();
-  return SR_OK;
-  });
-}
-
-int sr_stream_begin(sr_stream* s, uint32_t* id) {
-  return guarded(__func__, [&]() -> int {
-  if (!s || !id) return fail(SR_EINVAL, "null argument");
-  const int rc = s->slots.begin(id);  // (the first push starts from the initial state: decode_stream_kernel)
-  if (rc) return rc;
-  const uint32_t slot = *id % s->slots.max_streams;
-  s->commit_fresh[slot] = 1;  // ... and the first sr_stream_stable from commit point 0
-  s->base[slot] = 0;          // ... with nothing trimmed
-  s->archive[slot].clear();
-  s->audio.begin(slot);
-  s->pipe.begin(slot);
-  return SR_OK;
-  });
-}
-
-int sr_stream_push(sr_stream* s, uint32_t n, const uint32_t* ids, const float* feats, const uint64_t* frame_off) {
-  return guarded(__func__, [&]() -> int { return push_rows(s, n, ids, feats, frame_off, false, nullptr, 0, nullptr); });
-}
-int sr_stream_push_rows(sr_stream* s, uint32_t n, const uint32_t* ids, const float* feats, const uint64_t* frame_off, int finish,
-                        float* out_feats, uint64_t cap_rows, uint64_t* out_frame_off) {
-  return guarded(__func__, [&]() -> int { return push_rows(s, n, ids, feats, frame_off, finish != 0, out_feats, cap_rows, out_frame_off); });
-}
-int sr_stream_set_projection(sr_stream* s, uint32_t in_dim, uint32_t context, const double* M) {
-  return guarded(__func__, [&]() -> int { return set_projection(s, in_dim, context, M); });
-}
-int sr_stream_set_transform(sr_stream* s, uint32_t id, const double* W) {
-  return guarded(__func__, [&]() -> int { return set_transform(s, id, W); });
-}
-
-int sr_stream_set_frontend(sr_stream* s, sr_frontend* fe) {
-  return guarded(__func__, [&]() -> int { return set_frontend(s, fe); });
-}
-int sr_stream_set_warp(sr_stream* s, uint32_t id, uint32_t warp) {
-  return guarded(__func__, [&]() -> int { return set_warp(s, id, warp); });
-}
-int sr_stream_push_audio(sr_stream* s, uint32_t n, const uint32_t* ids, const int16_t* samples, const uint64_t* sample_off, float* out_feats,
-                         uint64_t cap_rows, uint64_t* out_frame_off) {
-  return guarded(__func__, [&]() -> int { return push_audio(s, n, ids, samples, sample_off, false, out_feats, cap_rows, out_frame_off); });
-}
-int sr_stream_finish_audio(sr_stream* s, uint32_t n, const uint32_t* ids, float* out_feats, uint64_t cap_rows, uint64_t* out_frame_off) {
-  return guarded(__func__, [&]() -> int { return push_audio(s, n, ids, nullptr, nullptr, true, out_feats, cap_rows, out_frame_off); });
-}
-
-int sr_stream_partial(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_t cap, uint32_t* count, uint64_t* frames) {
-  return guarded(__func__, [&]() -> int {
-  if (!s || !count || (!out_words && cap)) return fail(SR_EINVAL, "null argument");
-  const int64_t slot = s->slots.find(id);
-  if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
-  int rc = check_model(s->model);
-  if (rc) return rc;
-  if (frames) *frames = s->base[slot] + s->slots.frames[slot];
-  return stream_words(s, (uint32_t)slot, id, out_words, cap, count);
-  });
-}
-
-int sr_stream_end(sr_stream* s, uint32_t id, uint32_t* out_words, uint32_t cap, uint32_t* count, double* tb_score, uint16_t* tb_word,
-                  uint16_t* tb_bkp) {
-  return guarded(__func__, [&]() -> int {
-  if (!s || !count || (!out_words && cap)) return fail(SR_EINVAL, "null argument");
-  const int64_t slot = s->slots.find(id);
-  if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
-  int rc = check_end(s, (uint32_t)slot, id, "sr_stream_finish_audio");
-  if (rc || (rc = check_model(s->model))) return rc;
-  if (s->base[slot] && (tb_score || tb_word || tb_bkp))
-    return fail(SR_EINVAL, "stream id %u has been trimmed: the traceback entries of its first %llu frames are gone (pass NULL arrays)", id,
-                (unsigned long long)s->base[slot]);
-  rc = stream_words(s, (uint32_t)slot, id, out_words, cap, count);
-  if (rc == SR_EINVAL) return rc;  // too small a buffer: the utterance stays open
-  const uint64_t T = s->slots.frames[slot];
-  if (rc == SR_OK && T == 0) {  // traceback[0] of the empty utterance (Recognizer.cpp:118-120)
-    if (tb_score) tb_score[0] = 0.0;
-    if (tb_word) tb_word[0] = 0;
-    if (tb_bkp) tb_bkp[0] = 0;
-  } else if (rc == SR_OK) {
-    const size_t b = (size_t)slot * (s->slots.max_frames + 1);
-    if (tb_score) HIP_TRY(hipMemcpy(tb_score, s->tb_score.p + b, sizeof(double) * (T + 1), hipMemcpyDeviceToHost));
-    if (tb_word) HIP_TRY(hipMemcpy(tb_word, s->tb_word.p + b, sizeof(uint16_t) * (T + 1), hipMemcpyDeviceToHost));
-    if (tb_bkp) HIP_TRY(hipMemcpy(tb_bkp, s->tb_bkp.p + b, sizeof(uint16_t) * (T + 1), hipMemcpyDeviceToHost));
-  }
-  s->slots.open[slot] = 0;
-  s->audio.end((uint32_t)slot);
-  std::vector<uint32_t>().swap(s->archive[slot]);
-  return rc;
-  });
-}
-
-// The stable prefix of n open utterances of either stream set (Set: sr_stream with StableJob, sr_bigram_stream with BigramStableJob):
-// one launch of the set's commit kernel, one workgroup per utterance, which writes straight into the call's pinned block.  Block:
-// Job[n] (in), StableResult[n], then the items, frame_bytes for every frame the n utterances have seen (an utterance gives at most
-// one item per frame; its items start `frames of the utterances before it` into each item area).  The caller supplies make_job(i,
-// slot, frames before, &job) -> rc, launch(jobs, results, items, frames, stream) -> rc over the block's three parts, copy_out(i, job,
-// result, out_off[i]) for utterance i's items (it may restate out_commit[i]), what a result that fails its checks says, the middle of
-// the capacity message, and lead(slot): the items of the utterance that precede the kernel's (the archive of a trimmed zerogram id).
-template <class Job, class Set, class MakeJob, class Launch, class CopyOut, class Lead>
-static int stable_prefix(Set* s, uint32_t n, const uint32_t* ids, bool missing_array, uint64_t cap, uint64_t* out_off, uint32_t* out_commit,
-                         size_t frame_bytes, const char* corrupt, const char* holds, MakeJob make_job, Launch launch, CopyOut copy_out,
-                         Lead lead) {
-  if (!s) return fail(SR_EINVAL, "null stream set");
-  if (!out_off || (n && (!ids || !out_commit)) || missing_array) return fail(SR_EINVAL, "null argument");
-  sr_model* m = s->model;
-  int rc = check_model(m);
-  if (rc) return rc;
-  const StreamSlots& sl = s->slots;
-  std::vector<uint8_t> seen(sl.max_streams, 0);
-  std::vector<Job> jobs(n);
-  uint64_t F = 0;
-  for (uint32_t i = 0; i < n; i++) {
-    const int64_t slot = sl.find(ids[i]);
-    if (slot < 0) return fail(SR_EINVAL, "entry %u: stream id %u is not open", i, ids[i]);
-    if (seen[slot]) return fail(SR_EINVAL, "entry %u: stream id %u appears twice in one call", i, ids[i]);
-    seen[slot] = 1;
-    if ((rc = make_job(i, (uint32_t)slot, F, &jobs[i]))) return rc;
-    F += sl.frames[slot];
-  }
-  if (n == 0) { out_off[0] = 0; return SR_OK; }
-  HIP_TRY(s->commit.ensure(sl.max_streams));
-  const size_t res_at = sizeof(Job) * n, items_at = res_at + sizeof(StableResult) * n, need = items_at + frame_bytes * F;
-  if (need > s->stable_block.n)  // (grown geometrically: pinning costs milliseconds, the need grows with every push)
-    HIP_TRY(s->stable_block.ensure(std::max<size_t>(need, 2 * s->stable_block.n)));
-  unsigned char* blk = s->stable_block.p;
-  memcpy(blk, jobs.data(), sizeof(Job) * n);
-  StableResult* res = reinterpret_cast<StableResult*>(blk + res_at);
-  if ((rc = launch(reinterpret_cast<const Job*>(blk), res, blk + items_at, F, m->s_gmm))) return rc;
-  HIP_TRY(hipStreamSynchronize(m->s_gmm));
-  uint32_t bad = 0xFFFFFFFFu;
-  for (uint32_t i = 0; i < n; i++) {
-    if (res[i].flags || res[i].count > jobs[i].t || res[i].commit > jobs[i].t) { if (bad == 0xFFFFFFFFu) bad = i; }
-    else s->commit_fresh[jobs[i].slot] = 0;  // the kernel left its commit point in commit[slot]
-  }
-  if (bad != 0xFFFFFFFFu) return fail(SR_ECORRUPT, "stream %u: %s", ids[bad], corrupt);
-  uint64_t total = 0;
-  for (uint32_t i = 0; i < n; i++) { out_off[i] = total; total += lead(jobs[i].slot) + res[i].count; }
-  out_off[n] = total;
-  if (total > cap) return fail(SR_EINVAL, "%llu stable %s %llu", (unsigned long long)total, holds, (unsigned long long)cap);
-  for (uint32_t i = 0; i < n; i++) {
-    out_commit[i] = res[i].commit;
-    copy_out(i, jobs[i], res[i], out_off[i]);
-  }
-  return SR_OK;
-}
-
-// The zerogram set's block holds the words (4 bytes a frame), utterance i's at jobs[i].word_off.
-int sr_stream_stable(sr_stream* s, uint32_t n, const uint32_t* ids, uint32_t* out_words, uint64_t cap, uint64_t* out_word_off,
-                     uint32_t* out_commit, uint32_t* out_silence) {
-  return guarded(__func__, [&]() -> int {
-  StableArgs a{};
-  return stable_prefix<StableJob>(
-      s, n, ids, !out_words && cap, cap, out_word_off, out_commit, sizeof(uint32_t),
-      "the traceback does not walk back from the commit point to frame 0 (Recognizer.cpp:222-231)", "words, out_words holds",
-      [&](uint32_t, uint32_t slot, uint64_t off, StableJob* job) -> int {
-        if (s->base[slot] + s->slots.frames[slot] > 0xFFFFFFFFull)  // (out_commit = base + c, c <= the window's frames)
-          return fail(SR_ELIMIT, "stream id %u: a commit frame past 2^32 - 1 does not fit out_commit", s->slots.id[slot]);
-        *job = StableJob{slot, (uint32_t)s->slots.frames[slot], s->commit_fresh[slot], 0u, off};
-        return SR_OK;
-      },
-      [&](const StableJob* jobs, StableResult* res, unsigned char* items, uint64_t, hipStream_t stream) -> int {
-        const StreamSlots& sl = s->slots;
-        const sr_lexicon* l = s->lex;
-        HIP_TRY(s->stable_words.ensure((size_t)sl.max_streams * sl.max_frames));
-        a.net = l->net;
-        a.jobs = jobs;
-        a.ws = s->ws.p; a.ws_stride = decode_big_workspace(l->net.n_slots);
-        a.tb_word = s->tb_word.p; a.tb_bkp = s->tb_bkp.p; a.tb_stride = sl.max_frames + 1;
-        a.commit = s->commit.p; a.words = s->stable_words.p; a.words_stride = sl.max_frames;
-        a.out_res = res; a.out_words = reinterpret_cast<uint32_t*>(items);
-        HIP_TRY(launch_stream_commit(a, n, stream));
-        return SR_OK;
-      },
-      [&](uint32_t i, const StableJob& job, const StableResult& r, uint64_t at) {
-        // a trimmed utterance: the archive's words lead (every commit point lies on the chain through the last one trimmed at),
-        // and the commit frame counts from the utterance's start
-        const std::vector<uint32_t>& arch = s->archive[job.slot];
-        if (!arch.empty()) memcpy(out_words + at, arch.data(), sizeof(uint32_t) * arch.size());
-        if (r.count) memcpy(out_words + at + arch.size(), a.out_words + job.word_off, sizeof(uint32_t) * r.count);
-        out_commit[i] = (uint32_t)(s->base[job.slot] + r.commit);
-        if (out_silence) out_silence[i] = r.silence;
-      },
-      [&](uint32_t slot) -> uint64_t { return s->archive[slot].size(); });
-  });
-}
-
-// sr_stream_trim (include/srgpu.h has the definition): one launch of stream_trim_kernel, one workgroup per id, over the block
-// sr_stream_stable uses -- StableJob[n] in, StableResult[n] and the committed words out.  Everything is checked before the launch;
-// an id whose result is flagged has written nothing on the device and changes nothing here, the others are taken over first.
-int sr_stream_trim(sr_stream* s, uint32_t n, const uint32_t* ids, uint32_t* out_dropped) {
-  return guarded(__func__, [&]() -> int {
-  if (!s) return fail(SR_EINVAL, "null stream set");
-  if (n && !ids) return fail(SR_EINVAL, "null argument");
-  sr_model* m = s->model;
-  int rc = check_model(m);
-  if (rc) return rc;
-  StreamSlots& sl = s->slots;
-  std::vector<uint8_t> seen(sl.max_streams, 0);
-  std::vector<StableJob> jobs(n);
-  uint64_t F = 0;
-  for (uint32_t i = 0; i < n; i++) {
-    const int64_t slot = sl.find(ids[i]);
-    if (slot < 0) return fail(SR_EINVAL, "entry %u: stream id %u is not open", i, ids[i]);
-    if (seen[slot]) return fail(SR_EINVAL, "entry %u: stream id %u appears twice in one call", i, ids[i]);
-    seen[slot] = 1;
-    jobs[i] = StableJob{(uint32_t)slot, (uint32_t)sl.frames[slot], s->commit_fresh[slot], 0u, F};
-    F += sl.frames[slot];
-  }
-  if (n == 0) return SR_OK;
-  const sr_lexicon* l = s->lex;
-  HIP_TRY(s->commit.ensure(sl.max_streams));
-  HIP_TRY(s->stable_words.ensure((size_t)sl.max_streams * sl.max_frames));
-  const size_t res_at = sizeof(StableJob) * n, words_at = res_at + sizeof(StableResult) * n, need = words_at + sizeof(uint32_t) * F;
-  if (need > s->stable_block.n) HIP_TRY(s->stable_block.ensure(std::max<size_t>(need, 2 * s->stable_block.n)));
-  unsigned char* blk = s->stable_block.p;
-  memcpy(blk, jobs.data(), sizeof(StableJob) * n);
-  StableResult* res = reinterpret_cast<StableResult*>(blk + res_at);
-  const uint32_t* words = reinterpret_cast<const uint32_t*>(blk + words_at);
-  TrimArgs a{};
-  a.net = l->net;
-  a.jobs = reinterpret_cast<const StableJob*>(blk);
-  a.ws = s->ws.p; a.ws_stride = decode_big_workspace(l->net.n_slots); a.state = s->state.p;
-  a.tb_score = s->tb_score.p; a.tb_word = s->tb_word.p; a.tb_bkp = s->tb_bkp.p; a.tb_stride = sl.max_frames + 1;
-  a.commit = s->commit.p; a.walk_words = s->stable_words.p; a.words = s->words.p; a.words_stride = sl.max_frames;
-  a.out_res = res; a.out_words = reinterpret_cast<uint32_t*>(blk + words_at);
-  HIP_TRY(launch_stream_trim(a, n, m->s_gmm));
-  HIP_TRY(hipStreamSynchronize(m->s_gmm));
-  uint32_t bad = 0xFFFFFFFFu;
-  for (uint32_t i = 0; i < n; i++) {
-    const StableJob& j = jobs[i];
-    const StableResult& r = res[i];
-    // a hypothesis entered at frame t carries bkp = t - 1: the commit point is below t and the window keeps a frame
-    if (r.flags || r.count > r.commit || (j.t ? r.commit >= j.t : r.commit != 0)) { if (bad == 0xFFFFFFFFu) bad = i; continue; }
-    s->commit_fresh[j.slot] = 0;  // the kernel left commit point 0 in commit[slot]
-    s->archive[j.slot].insert(s->archive[j.slot].end(), words + j.word_off, words + j.word_off + r.count);
-    s->base[j.slot] += r.commit;
-    sl.frames[j.slot] -= r.commit;
-    if (out_dropped) out_dropped[i] = r.commit;
-  }
-  if (bad != 0xFFFFFFFFu)
-    return fail(SR_ECORRUPT, "stream %u: the traceback does not walk back from the commit point to frame 0, or an alive hypothesis starts below it", ids[bad]);
-  return SR_OK;
-  });
-}
-
-// test hook: the nearest-common-ancestor fold of commit_point.h alone, on forests the caller supplies
-int sr_commit_points(sr_model* m, uint32_t n_sets, const uint64_t* node_off, const uint32_t* parent, const uint64_t* set_off,
-                     const uint32_t* set, const uint32_t* floor, uint32_t* out) {
-  return guarded(__func__, [&]() -> int {
-  int rc = check_model(m);
-  if (rc) return rc;
-  if (n_sets == 0) return SR_OK;
-  if (!node_off || !parent || !set_off || !set || !floor || !out) return fail(SR_EINVAL, "null argument");
-  if (node_off[0] != 0 || set_off[0] != 0) return fail(SR_EINVAL, "node_off[0] and set_off[0] must be 0");
-  for (uint32_t i = 0; i < n_sets; i++) {
-    if (node_off[i + 1] <= node_off[i]) return fail(SR_EINVAL, "set %u: a tree has at least its root", i);
-    if (set_off[i + 1] <= set_off[i]) return fail(SR_EINVAL, "set %u is empty", i);
-    const uint64_t nn = node_off[i + 1] - node_off[i];
-    if (nn >= 0xFFFFFFFEull) return fail(SR_ELIMIT, "set %u: %llu nodes, node indices are 32 bit", i, (unsigned long long)nn);
-    const uint32_t* par = parent + node_off[i];
-    if (par[0] != 0) return fail(SR_EINVAL, "set %u: parent[0] must be 0", i);
-    for (uint64_t j = 1; j < nn; j++)
-      if (par[j] >= j) return fail(SR_EINVAL, "set %u: parent[%llu] = %u is not below its child", i, (unsigned long long)j, par[j]);
-    for (uint64_t j = set_off[i]; j < set_off[i + 1]; j++)
-      if (set[j] >= nn) return fail(SR_EINVAL, "set %u: node %u out of range (%llu nodes)", i, set[j], (unsigned long long)nn);
-    if (floor[i] >= nn) return fail(SR_EINVAL, "set %u: floor %u out of range (%llu nodes)", i, floor[i], (unsigned long long)nn);
-  }
-  DevBuf<uint64_t> d_node_off, d_set_off;
-  DevBuf<uint32_t> d_parent, d_set, d_floor, d_out;
-  HIP_TRY(d_node_off.upload(node_off, (size_t)n_sets + 1));
-  HIP_TRY(d_set_off.upload(set_off, (size_t)n_sets + 1));
-  HIP_TRY(d_parent.upload(parent, node_off[n_sets]));
-  HIP_TRY(d_set.upload(set, set_off[n_sets]));
-  HIP_TRY(d_floor.upload(floor, n_sets));
-  HIP_TRY(d_out.ensure(n_sets));
-  CommitPointsArgs a{d_node_off.p, d_parent.p, d_set_off.p, d_set.p, d_floor.p, d_out.p};
-  HIP_TRY(launch_commit_points(a, n_sets, m->s_gmm));
-  HIP_TRY(hipStreamSynchronize(m->s_gmm));
-  std::vector<uint32_t> got(n_sets);
-  HIP_TRY(hipMemcpy(got.data(), d_out.p, sizeof(uint32_t) * n_sets, hipMemcpyDeviceToHost));
-  for (uint32_t i = 0; i < n_sets; i++)
-    if (got[i] >= node_off[i + 1] - node_off[i]) return fail(SR_ECORRUPT, "set %u: the fold left the tree", i);
-  memcpy(out, got.data(), sizeof(uint32_t) * n_sets);
-  return SR_OK;
-  });
-}
-
-int sr_stream_destroy(sr_stream* s) {
-  return guarded(__func__, [&]() -> int {
-  if (!s) return SR_OK;
-  if (s->model) { (void)hipSetDevice(s->model->device); (void)hipDeviceSynchronize(); }
-  delete s;
-  return SR_OK;
-  });
-}
-
-// ---- streaming bigram-LM recognition (sr_bigram_stream_*): bigram_stream_kernel over per-slot state in device memory --------------
-
-int sr_bigram_stream_open(sr_model* m, sr_bigram* b, const sr_bigram_params* p, uint32_t max_streams, uint64_t max_frames,
-                          sr_bigram_stream** out) {
-  return guarded(__func__, [&]() -> int {
-  if (!out) return fail(SR_EINVAL, "out is null");
-  *out = nullptr;
-  int rc = check_model(m);
-  if (rc) return rc;
-  if (!b || b->model != m) return fail(SR_EINVAL, "bigram search net does not belong to this model");
-  if (!p) return fail(SR_EINVAL, "null bigram params");
-  if (p->flags != 0) return fail(SR_EINVAL, "sr_bigram_params.flags must be 0 for streaming (got 0x%x)", (unsigned)p->flags);
-  if (p->max_word_ends != 0)
-    return fail(SR_EINVAL, "sr_bigram_params.max_word_ends must be 0 for streaming (got %u): the book grows with the utterance", p->max_word_ends);
-  if (p->gmm_kernel < SR_GMM_MFMA || p->gmm_kernel > SR_GMM_DEFAULT) return fail(SR_EINVAL, "unknown gmm_kernel %d", p->gmm_kernel);
-  if (max_streams == 0) return fail(SR_EINVAL, "max_streams must be at least 1");
-  if (max_frames == 0) return fail(SR_EINVAL, "max_frames must be at least 1");
-  if (max_frames > 0xFFFFFFFEull) return fail(SR_ELIMIT, "max_frames %llu: frame times are 32 bit", (unsigned long long)max_frames);
-  sr_bigram_stream* s = new sr_bigram_stream();
-  std::unique_ptr<sr_bigram_stream, int (*)(sr_bigram_stream*)> own(s, sr_bigram_stream_destroy);
-  s->model = m; s->bigram = b; s->params = *p; s->slots = StreamSlots(max_streams, max_frames);
-  s->host_state.assign(max_streams, BigramStreamState{}); s->failed.assign(max_streams, 0);
-  s->commit_fresh.assign(max_streams, 1);
-  s->audio.open(max_streams);
-  s->pipe.open(max_streams);
-  const size_t S = max_streams, W = b->net.n_words;
-  HIP_TRY(s->gs_ws.ensure(S * bigram_gs_ws_words(b->net.n_words, b->net.n_positions)));
-  HIP_TRY(s->we_slot.ensure(S * 4 * W));
-  HIP_TRY(s->we_bp.ensure(S * 4 * W));
-  HIP_TRY(s->we_score.ensure(S * 4 * W));
-  HIP_TRY(s->lsave.ensure(S * 2 * W));
-  HIP_TRY(s->state.ensure(S));
-  HIP_TRY(s->out_word.ensure(S * (max_frames + 1)));
-  HIP_TRY(s->out_time.ensure(S * (max_frames + 1)));
-  HIP_TRY(s->out_score.ensure(S * (max_frames + 1)));
-  for (size_t i = 0; i < S; i++) s->book.emplace_back(new DevBuf<uint4>());
-  *out = own.release();
-  return SR_OK;
-  });
-}
-
-int sr_bigram_stream_begin(sr_bigram_stream* s, uint32_t* id) {
-  return guarded(__func__, [&]() -> int {
-  if (!s || !id) return fail(SR_EINVAL, "null argument");
-  int rc = s->slots.begin(id);  // (the first push starts from the initial state: bigram_stream_kernel)
-  if (rc) return rc;
-  const uint32_t slot = *id % s->slots.max_streams;
-  s->host_state[slot] = BigramStreamState{};
-  s->host_state[slot].n_book = 2;  // the two start entries the first push writes
-  s->failed[slot] = 0;
-  s->commit_fresh[slot] = 1;  // the first sr_bigram_stream_stable starts from the start entry
-  s->audio.begin(slot);
-  s->pipe.begin(slot);
-  return SR_OK;
-  });
-}
-
-int sr_bigram_stream_push(sr_bigram_stream* s, uint32_t n, const uint32_t* ids, const float* feats, const uint64_t* frame_off) {
-  return guarded(__func__, [&]() -> int { return push_rows(s, n, ids, feats, frame_off, false, nullptr, 0, nullptr); });
-}
-int sr_bigram_stream_push_rows(sr_bigram_stream* s, uint32_t n, const uint32_t* ids, const float* feats, const uint64_t* frame_off, int finish,
-                               float* out_feats, uint64_t cap_rows, uint64_t* out_frame_off) {
-  return guarded(__func__, [&]() -> int { return push_rows(s, n, ids, feats, frame_off, finish != 0, out_feats, cap_rows, out_frame_off); });
-}
-int sr_bigram_stream_set_projection(sr_bigram_stream* s, uint32_t in_dim, uint32_t context, const double* M) {
-  return guarded(__func__, [&]() -> int { return set_projection(s, in_dim, context, M); });
-}
-int sr_bigram_stream_set_transform(sr_bigram_stream* s, uint32_t id, const double* W) {
-  return guarded(__func__, [&]() -> int { return set_transform(s, id, W); });
-}
-
-int sr_bigram_stream_set_frontend(sr_bigram_stream* s, sr_frontend* fe) {
-  return guarded(__func__, [&]() -> int { return set_frontend(s, fe); });
-}
-int sr_bigram_stream_set_warp(sr_bigram_stream* s, uint32_t id, uint32_t warp) {
-  return guarded(__func__, [&]() -> int { return set_warp(s, id, warp); });
-}
-int sr_bigram_stream_push_audio(sr_bigram_stream* s, uint32_t n, const uint32_t* ids, const int16_t* samples, const uint64_t* sample_off,
-                                float* out_feats, uint64_t cap_rows, uint64_t* out_frame_off) {
-  return guarded(__func__, [&]() -> int { return push_audio(s, n, ids, samples, sample_off, false, out_feats, cap_rows, out_frame_off); });
-}
-int sr_bigram_stream_finish_audio(sr_bigram_stream* s, uint32_t n, const uint32_t* ids, float* out_feats, uint64_t cap_rows,
-                                  uint64_t* out_frame_off) {
-  return guarded(__func__, [&]() -> int { return push_audio(s, n, ids, nullptr, nullptr, true, out_feats, cap_rows, out_frame_off); });
-}
-
-int sr_bigram_stream_partial(sr_bigram_stream* s, uint32_t id, uint32_t* out_word, float* out_score, uint32_t* out_time, uint32_t cap,
-                             uint32_t* count, uint64_t* frames) {
-  return guarded(__func__, [&]() -> int {
-  if (!s || !count || ((!out_word || !out_score || !out_time) && cap)) return fail(SR_EINVAL, "null argument");
-  const int64_t slot = s->slots.find(id);
-  if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
-  int rc = check_model(s->model);
-  if (rc) return rc;
-  if (frames) *frames = s->slots.frames[slot];
-  return bigram_stream_items(s, (uint32_t)slot, id, out_word, out_score, out_time, cap, count);
-  });
-}
-
-int sr_bigram_stream_end(sr_bigram_stream* s, uint32_t id, uint32_t* out_word, float* out_score, uint32_t* out_time, uint32_t cap,
-                         uint32_t* count) {
-  return guarded(__func__, [&]() -> int {
-  if (!s || !count || ((!out_word || !out_score || !out_time) && cap)) return fail(SR_EINVAL, "null argument");
-  const int64_t slot = s->slots.find(id);
-  if (slot < 0) return fail(SR_EINVAL, "stream id %u is not open", id);
-  int rc = check_end(s, (uint32_t)slot, id, "sr_bigram_stream_finish_audio");
-  if (rc || (rc = check_model(s->model))) return rc;
-  rc = bigram_stream_items(s, (uint32_t)slot, id, out_word, out_score, out_time, cap, count);
-  if (rc == SR_EINVAL) return rc;  // too small a buffer: the utterance stays open
-  s->slots.open[slot] = 0;
-  s->audio.end((uint32_t)slot);
-  return rc;
-  });
-}
-
-// The stable prefix (stable_prefix above): the bigram set's block holds three item areas (word, score, time: 12 bytes a frame),
-// utterance i's items at jobs[i].item_off of each.
-int sr_bigram_stream_stable(sr_bigram_stream* s, uint32_t n, const uint32_t* ids, uint32_t* out_word, float* out_score,
-                            uint32_t* out_time, uint64_t cap, uint64_t* out_off, uint32_t* out_commit) {
-  return guarded(__func__, [&]() -> int {
-  BigramStableArgs a{};
-  return stable_prefix<BigramStableJob>(
-      s, n, ids, (!out_word || !out_score || !out_time) && cap, cap, out_off, out_commit, 12,
-      "the book walk from the commit entry does not end at its start entry", "items, the output arrays hold",
-      [&](uint32_t i, uint32_t slot, uint64_t off, BigramStableJob* job) -> int {
-        if (s->failed[slot]) return fail(SR_EINTERNAL, "stream %u: a push overflowed its book", ids[i]);
-        const uint64_t t = s->slots.frames[slot];
-        *job = BigramStableJob{slot, (uint32_t)t, s->commit_fresh[slot], 0u, t ? s->book[slot]->p : nullptr, off};
-        return SR_OK;
-      },
-      [&](const BigramStableJob* jobs, StableResult* res, unsigned char* items, uint64_t N, hipStream_t stream) -> int {
-        const sr_bigram* b = s->bigram;
-        a.n_words = b->net.n_words; a.silence = b->net.silence; a.n_positions = b->net.n_positions; a.slot_off = b->net.slot_off;
-        a.gs_ws = s->gs_ws.p; a.gs_ws_words = bigram_gs_ws_words(b->net.n_words, b->net.n_positions);
-        a.we_bp = s->we_bp.p; a.lsave = s->lsave.p; a.state = s->state.p;
-        a.jobs = jobs;
-        a.commit = s->commit.p;
-        a.out_res = res;
-        a.out_word = reinterpret_cast<uint32_t*>(items);
-        a.out_score = reinterpret_cast<float*>(items + 4 * N);
-        a.out_time = reinterpret_cast<uint32_t*>(items + 8 * N);
-        HIP_TRY(launch_bigram_stream_commit(a, n, stream));
-        return SR_OK;
-      },
-      [&](uint32_t, const BigramStableJob& job, const StableResult& r, uint64_t at) {
-        if (!r.count) return;
-        memcpy(out_word + at, a.out_word + job.item_off, sizeof(uint32_t) * r.count);
-        memcpy(out_score + at, a.out_score + job.item_off, sizeof(float) * r.count);
-        memcpy(out_time + at, a.out_time + job.item_off, sizeof(uint32_t) * r.count);
-      },
-      [](uint32_t) -> uint64_t { return 0; });
-  });
-}
-
-int sr_bigram_stream_destroy(sr_bigram_stream* s) {
-  return guarded(__func__, [&]() -> int {
-  if (!s) return SR_OK;
-  if (s->model) { (void)hipSetDevice(s->model->device); (void)hipDeviceSynchronize(); }
-  delete s;
-  return SR_OK;
-  });
-}
+// ---- streaming recognition: sr_stream_*, sr_bigram_stream_*, sr_commit_points ------------------------------------------------------
+#include "stream_api.cpp"
 
 int sr_profile_enable(sr_model* m, int on) {
   return guarded(__func__, [&]() -> int {
