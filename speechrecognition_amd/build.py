@@ -24,7 +24,7 @@ SOURCES = ["srgpu_api.cpp", "mixset.cpp", "feeder.cpp", "gmm_mfma.hip", "gmm_exa
            "gather_words.hip", "frontend.hip", "frontend.cpp", "stream_pipeline.hip"]
 # (mllr.cpp, mllt.cpp, lda.cpp and map.cpp are included by fmllr.cpp, nbest.cpp, chains.cpp and stream_api.cpp by srgpu_api.cpp: listed with
 # the headers so that their content enters the stamps)
-HEADERS = ["mllr.cpp", "mllt.cpp", "lda.cpp", "map.cpp", "nbest.cpp", "chains.cpp", "stream_api.cpp", "kernels.h", "host_util.h", "handles.h", "traceback.h", "commit_point.h", "dpp_util.h", "netfb_device.h", "smbr_device.h", "sym_contract.h", "structure_plan.h", "fb_plan.h", "stream_audio_plan.h", "stream_pipeline_plan.h", "stream_set_plan.h", "splice_clamp.h", "vtln_tables.h", "bigram_route.h", os.path.join("..", "..", "include", "srgpu.h")]
+HEADERS = ["mllr.cpp", "mllt.cpp", "lda.cpp", "map.cpp", "nbest.cpp", "chains.cpp", "stream_api.cpp", "kernels.h", "host_util.h", "handles.h", "traceback.h", "commit_point.h", "dpp_util.h", "netfb_device.h", "smbr_device.h", "bigram_device.h", "lattice_emit.h", "sym_contract.h", "structure_plan.h", "fb_plan.h", "stream_audio_plan.h", "stream_pipeline_plan.h", "stream_set_plan.h", "splice_clamp.h", "vtln_tables.h", "bigram_route.h", os.path.join("..", "..", "include", "srgpu.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 # these replay the reference's SSE2 operation order and must not contract a*b+c into an FMA
 PER_FILE = {"gmm_exact.hip": ["-ffp-contract=off"], "gmm_prefilter.hip": ["-ffp-contract=off"], "em_accumulate.hip": ["-ffp-contract=off"],

@@ -1,5 +1,5 @@
 // dpp_util.h -- wave and row reductions with DPP, v_min_f64, LDS ds_min_f64: shared by the search kernels
-// (viterbi_fast.hip, viterbi_words.hip).
+// (viterbi_fast.hip, viterbi_words.hip); shfl_xor_f64 for every kernel that moves a double across the wave.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -19,6 +19,10 @@ __device__ inline double dpp_d(double v) {
 }
 __device__ inline double readlane63_d(double v) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
+}
+// __shfl_xor of a double, as two 32-bit halves: the butterfly step of the forward-backward, sMBR, lattice and item kernels
+__device__ inline double shfl_xor_f64(double v, int k) {
+  return __hiloint2double(__shfl_xor(__double2hiint(v), k), __shfl_xor(__double2loint(v), k));
 }
 // v_min_f64 directly: one instruction per reduction step instead of compare + two selects (fmin() would canonicalise
 // its operands first).  Hypothesis scores are never NaN; +inf is an ordinary operand.

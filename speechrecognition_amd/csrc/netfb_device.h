@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dpp_util.h"
 #include "kernels.h"
 
 namespace srgpu {
@@ -69,8 +70,7 @@ struct Lse {
 __device__ inline void block_lse_store(Lse v, double* red) {
 #pragma unroll
   for (int k = 1; k < 64; k <<= 1) {
-    const double om = __hiloint2double(__shfl_xor(__double2hiint(v.m), k), __shfl_xor(__double2loint(v.m), k));
-    const double os = __hiloint2double(__shfl_xor(__double2hiint(v.s), k), __shfl_xor(__double2loint(v.s), k));
+    const double om = shfl_xor_f64(v.m, k), os = shfl_xor_f64(v.s, k);
     v.merge(om, os);
   }
   if ((threadIdx.x & 63) == 0) {

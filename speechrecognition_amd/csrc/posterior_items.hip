@@ -18,16 +18,13 @@
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
+#include "dpp_util.h"
 #include "kernels.h"
 
 namespace srgpu {
 
 static constexpr double kInf = __builtin_huge_val();
 static constexpr int kItemsSplit = 8;  // workgroups (of four waves) per utterance
-
-__device__ inline double shfl_xor_f64(double v, int k) {
-  return __hiloint2double(__shfl_xor(__double2hiint(v), k), __shfl_xor(__double2loint(v), k));
-}
 
 // Workgroup (u, y): its waves take every (4 * kItemsSplit)-th frame of utterance u; lane l of round r owns the utterance's mixture
 // 64 r + l.  WRITE = false counts the items of each frame, WRITE = true stores them at *item_base + the exclusive scan of the counts,

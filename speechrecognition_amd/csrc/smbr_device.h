@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dpp_util.h"
 #include "netfb_device.h"
 
 namespace srgpu {
@@ -62,9 +63,9 @@ struct LseA {
   __device__ La value() const { return m < kInf ? La{m - log(s), sa / s} : La{kInf, 0.0}; }
 };
 
-__device__ inline double shfl_xor_f64(double v, int k) {
-  return __hiloint2double(__shfl_xor(__double2hiint(v), k), __shfl_xor(__double2loint(v), k));
-}
+// a frame's accuracy term: does the position with slot_info / pos_info word f carry the reference mixture?
+__device__ inline double hit(uint32_t f, uint32_t ref) { return (f & 0xFFFFu) == ref ? 1.0 : 0.0; }
+
 // block_lse_store with the third component: lane 0 of each wave stores to red[3 * wave]
 __device__ inline void block_lsea_store(LseA v, double* red) {
 #pragma unroll

@@ -3403,6 +3403,16 @@ static int bgfb_tables(sr_model* m, sr_bigram* b, double scale) {
   return SR_OK;
 }
 
+// The search net's fields of a BgFbArgs or a BgLatArgs (both name them alike), with the model's row length and the corpus' offsets
+template <class Args>
+static void bg_net_args(const sr_model* m, const sr_corpus* c, const sr_bigram* b, Args* a) {
+  a->n_words = b->net.n_words; a->silence = b->net.silence; a->n_positions = (uint32_t)b->net.n_positions;
+  a->Kp = bgfb_padded(b->net.n_words);
+  a->slot_off = b->slot_off.p; a->pos_info = b->pos_info.p; a->pos_slot = b->pos_slot.p; a->lmT = b->lmT.p;
+  memcpy(a->tdp, b->net.tdp, sizeof(a->tdp));
+  a->ld = m->ld; a->frame_off = c->d_frame_off.p;
+}
+
 // The time-step recursion over the bigram search network with `mult` operand vectors per utterance (1: BgFbPass; 2: BgSmbrPass, the
 // accuracy side beside every cost).  The launch groups are cut like NetFbPass' on a cost prefix that counts the per-utterance vectors
 // in, each with its utterances ordered longest first.  run_groups() enqueues a chunk's groups: per frame the step and the product,
@@ -3442,10 +3452,8 @@ struct BgStepPass {
     HIP_TRY(hipMemset(c->bgfb_vec.p, 0, rows * Kp * sizeof(double)));  // (the padding columns h >= W stay 0 from here on)
     if (U) HIP_TRY(hipMemset(c->out_cost.p, 0, sizeof(double) * U));  // T_u = 0: F_u = 0, the start hypothesis is a word end
     HIP_TRY(hipDeviceSynchronize());
-    a->n_words = W; a->silence = b->net.silence; a->n_positions = (uint32_t)P; a->Kp = Kp;
-    a->slot_off = b->slot_off.p; a->pos_info = b->pos_info.p; a->pos_slot = b->pos_slot.p; a->lmT = b->lmT.p;
-    memcpy(a->tdp, b->net.tdp, sizeof(a->tdp));
-    a->scale = scale; a->ld = m->ld; a->frame_off = c->d_frame_off.p;
+    bg_net_args(m, c, b, a);
+    a->scale = scale;
     a->trellis = c->fb_trellis.p; a->vec = c->bgfb_vec.p; a->prod = c->bgfb_prod.p; a->wend = c->bgfb_wend.p; a->m = c->bgfb_m.p; a->xb = c->bgfb_xb.p;
     a->out_cost = c->out_cost.p;
     return SR_OK;
@@ -4390,14 +4398,74 @@ static hipError_t copy_arcs(T* out, const DevBuf<T>& arcs, uint64_t n_arcs) {
   return n_arcs ? hipMemcpy(out, arcs.p, sizeof(T) * n_arcs, hipMemcpyDeviceToHost) : hipSuccess;
 }
 
+// The emit side of both lattice passes (lattice_emit.h).  setup(): the count / scan workspace for launch groups of at most max_gf frames,
+// the arc counter cleared, the shared arc arrays for arc_cap arcs (0: the sizing call, none) bound into either args struct.
+struct LatticeEmit {
+  size_t scan_bytes = 0;
+  uint64_t cap = 0;
+
+  template <class Args>
+  int setup(sr_corpus* c, uint64_t max_gf, uint64_t arc_cap, Args* a, double*& arc_cost) {  // arc_cost: a->arc_cost or a->arc_am
+    HIP_TRY(c->lat_cnt.ensure(max_gf)); HIP_TRY(c->lat_scan.ensure(max_gf)); HIP_TRY(c->lat_base.ensure(1));
+    HIP_TRY(c->lat_frame_arc.ensure(c->n_frames + 1));
+    scan_bytes = lattice_scan_temp_bytes(max_gf);
+    HIP_TRY(c->fb_scan_temp.ensure(scan_bytes));
+    HIP_TRY(hipMemset(c->lat_base.p, 0, sizeof(uint64_t)));
+    cap = arc_cap;
+    if (!cap) return SR_OK;
+    HIP_TRY(c->lat_arc_word.ensure(cap)); HIP_TRY(c->lat_arc_first.ensure(cap)); HIP_TRY(c->lat_arc_last.ensure(cap));
+    HIP_TRY(c->lat_arc_fwd.ensure(cap)); HIP_TRY(c->lat_arc_bwd.ensure(cap)); HIP_TRY(c->lat_arc_cost.ensure(cap));
+    a->arc_word = c->lat_arc_word.p; a->arc_first = c->lat_arc_first.p; a->arc_last = c->lat_arc_last.p;
+    a->arc_fwd = c->lat_arc_fwd.p; a->arc_bwd = c->lat_arc_bwd.p; arc_cost = c->lat_arc_cost.p;
+    return SR_OK;
+  }
+  template <class Args, class Emit>
+  hipError_t launch(Emit emit, const Args& a, sr_corpus* c, const Group& g, hipStream_t s) {
+    return emit(a, c->frame_off[g.u1] - c->frame_off[g.u0], c->fb_scan_temp.p, scan_bytes, c->lat_cnt.p, c->lat_scan.p, c->lat_base.p,
+                c->lat_frame_arc.p, cap, s);
+  }
+};
+
+// Both lattice entry points after their own argument checks, with their pass `lp`, its bytes per utterance (`cost`, prefix sums) and slots
+// per frame: limits, chunks, setup(device cap, chunks), the pass, the offsets and the shared arrays.  *n_arcs: arcs to copy besides (0: none).
+struct LatticeOut {  // the caller's arrays both lattices have: offsets and best costs, then the six per arc (all null: the sizing call)
+  uint64_t* arc_off; double* best; uint32_t *word, *first, *last; double *fwd, *bwd, *cost;
+};
+template <class Pass, class Setup>
+static int lattice_corpus(sr_model* m, sr_corpus* c, int gmm_kernel, const std::vector<uint64_t>& cost, uint64_t slots, uint64_t cap,
+                          bool fill, Pass& lp, Setup setup, const LatticeOut& out, uint64_t* n_arcs) {
+  int rc;
+  for (uint32_t u = 0; u < c->n_utts; u++) {
+    const uint64_t T = c->frame_off[u + 1] - c->frame_off[u];
+    if (T > 65535) return fail(SR_ELIMIT, "utterance %u: %llu frames exceed the lattice's 65535", u, (unsigned long long)T);
+    if ((rc = check_fits(m, u, cost[u + 1] - cost[u], true))) return rc;
+  }
+  std::vector<Chunk> chunks;
+  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
+  const uint64_t dev_cap = fill ? std::min<uint64_t>(cap, c->n_frames * slots) : 0;  // (no lattice has more arcs than that)
+  if ((rc = setup(dev_cap, chunks))) return rc;
+  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, gmm_kernel, table); },
+                  [&](const Chunk& ch, const double* table, hipStream_t s) -> int { return lp.run(c, ch, table, s); });
+  if (rc) return rc;
+  if (m->profiling) m->prof.frames += c->n_frames;
+  if ((rc = lattice_offsets(c, cap, fill, out.arc_off, out.best, n_arcs))) return rc;
+  HIP_TRY(copy_arcs(out.word, c->lat_arc_word, *n_arcs));
+  HIP_TRY(copy_arcs(out.first, c->lat_arc_first, *n_arcs));
+  HIP_TRY(copy_arcs(out.last, c->lat_arc_last, *n_arcs));
+  HIP_TRY(copy_arcs(out.fwd, c->lat_arc_fwd, *n_arcs));
+  HIP_TRY(copy_arcs(out.bwd, c->lat_arc_bwd, *n_arcs));
+  HIP_TRY(copy_arcs(out.cost, c->lat_arc_cost, *n_arcs));
+  return SR_OK;
+}
+
 // The launch groups of a lattice pass -- NetFbPass' grouping on the lattice's bytes per frame: consecutive utterances of a chunk
 // whose word-end tables fit m->fb_budget together (every utterance fits alone: checked by the entry point).  run() enqueues a
 // chunk's groups in order: forward, backward, emit.
 struct LatticePass {
   srplan::Groups groups;
   LatticeArgs a{};
-  size_t ci = 0, scan_bytes = 0;
-  uint64_t cap = 0;
+  LatticeEmit emit;
+  size_t ci = 0;
 
   int setup(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_search_params* p, double beam, uint64_t arc_cap,
             const std::vector<Chunk>& chunks) {
@@ -4409,24 +4477,11 @@ struct LatticePass {
     HIP_TRY(c->lat_first.ensure(max_gf * W));
     HIP_TRY(c->lat_ends.ensure(max_gf));
     HIP_TRY(c->lat_bend.ensure(max_gf));
-    HIP_TRY(c->lat_cnt.ensure(max_gf));
-    HIP_TRY(c->lat_scan.ensure(max_gf));
-    HIP_TRY(c->lat_base.ensure(1));
-    HIP_TRY(c->lat_frame_arc.ensure(c->n_frames + 1));
     HIP_TRY(c->out_cost.ensure(c->n_utts));
-    scan_bytes = lattice_scan_temp_bytes(max_gf);
-    HIP_TRY(c->fb_scan_temp.ensure(scan_bytes));
-    HIP_TRY(hipMemset(c->lat_base.p, 0, sizeof(uint64_t)));
+    if (int rc = emit.setup(c, max_gf, arc_cap, &a, a.arc_cost)) return rc;
     a.net = l->net; a.ld = m->ld; a.frame_off = c->d_frame_off.p;
     a.word_penalty = p->word_penalty; a.beam = beam;
     a.fwd = c->lat_fwd.p; a.first = c->lat_first.p; a.ends = c->lat_ends.p; a.bend = c->lat_bend.p; a.out_best = c->out_cost.p;
-    cap = arc_cap;
-    if (cap) {
-      HIP_TRY(c->lat_arc_word.ensure(cap)); HIP_TRY(c->lat_arc_first.ensure(cap)); HIP_TRY(c->lat_arc_last.ensure(cap));
-      HIP_TRY(c->lat_arc_fwd.ensure(cap)); HIP_TRY(c->lat_arc_bwd.ensure(cap)); HIP_TRY(c->lat_arc_cost.ensure(cap));
-      a.arc_word = c->lat_arc_word.p; a.arc_first = c->lat_arc_first.p; a.arc_last = c->lat_arc_last.p;
-      a.arc_fwd = c->lat_arc_fwd.p; a.arc_bwd = c->lat_arc_bwd.p; a.arc_cost = c->lat_arc_cost.p;
-    }
     // word-end tables per frame: fwd, first, E and Bend out, then in again for the count and for the write
     if (m->profiling) m->prof.search_bytes += (30.0 * (double)W + 48.0) * (double)c->n_frames;
     return SR_OK;
@@ -4434,11 +4489,9 @@ struct LatticePass {
   int run(sr_corpus* c, const Chunk& ch, const double* table, hipStream_t s) {
     for (const Group& g : groups.of_chunk[ci]) {
       a.scores = table; a.frame_base = ch.f0; a.utt_first = g.u0; a.n_utts = g.u1 - g.u0; a.group_f0 = c->frame_off[g.u0];
-      const uint64_t n = c->frame_off[g.u1] - c->frame_off[g.u0];
       HIP_TRY(launch_lattice_forward(a, s));
       HIP_TRY(launch_lattice_backward(a, s));
-      HIP_TRY(launch_lattice_emit(a, n, c->fb_scan_temp.p, scan_bytes, c->lat_cnt.p, c->lat_scan.p, c->lat_base.p,
-                                  c->lat_frame_arc.p, cap, s));
+      HIP_TRY(emit.launch(launch_lattice_emit, a, c, g, s));
     }
     ci++;
     return SR_OK;
@@ -4462,32 +4515,11 @@ int sr_word_lattice_corpus(sr_model* m, sr_corpus* c, sr_lexicon* l, const sr_se
   if (P > lattice_max_slots())
     return fail(SR_ELIMIT, "%llu lexicon positions exceed the word lattice's %llu", (unsigned long long)P,
                 (unsigned long long)lattice_max_slots());
-  const uint32_t U = c->n_utts;
-  const uint64_t F = c->n_frames;
-  const std::vector<uint64_t> cost = lattice_cost(c, l);
-  for (uint32_t u = 0; u < U; u++) {
-    const uint64_t T = c->frame_off[u + 1] - c->frame_off[u];
-    if (T > 65535) return fail(SR_ELIMIT, "utterance %u: %llu frames exceed the lattice's 65535", u, (unsigned long long)T);
-    if ((rc = check_fits(m, u, cost[u + 1] - cost[u], true))) return rc;
-  }
-  std::vector<Chunk> chunks;
-  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
   LatticePass lp;
-  const uint64_t dev_cap = fill ? std::min<uint64_t>(cap, F * l->net.n_words) : 0;  // (no lattice has more than F * W arcs)
-  if ((rc = lp.setup(m, c, l, p, lattice_beam, dev_cap, chunks))) return rc;
-  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, p->gmm_kernel, table); },
-                  [&](const Chunk& ch, const double* table, hipStream_t s) -> int { return lp.run(c, ch, table, s); });
-  if (rc) return rc;
-  if (m->profiling) m->prof.frames += F;
   uint64_t n = 0;
-  if ((rc = lattice_offsets(c, cap, fill, out_arc_off, out_best, &n))) return rc;
-  HIP_TRY(copy_arcs(out_word, c->lat_arc_word, n));
-  HIP_TRY(copy_arcs(out_first, c->lat_arc_first, n));
-  HIP_TRY(copy_arcs(out_last, c->lat_arc_last, n));
-  HIP_TRY(copy_arcs(out_fwd, c->lat_arc_fwd, n));
-  HIP_TRY(copy_arcs(out_bwd, c->lat_arc_bwd, n));
-  HIP_TRY(copy_arcs(out_cost, c->lat_arc_cost, n));
-  return SR_OK;
+  return lattice_corpus(m, c, p->gmm_kernel, lattice_cost(c, l), l->net.n_words, cap, fill, lp,
+                        [&](uint64_t dev_cap, const std::vector<Chunk>& chunks) { return lp.setup(m, c, l, p, lattice_beam, dev_cap, chunks); },
+                        LatticeOut{out_arc_off, out_best, out_word, out_first, out_last, out_fwd, out_bwd, out_cost}, &n);
   });
 }
 
@@ -4508,8 +4540,8 @@ struct BgLatPass {
   BgLatArgs a{};
   const float *tab_fwd = nullptr, *tab_bwd = nullptr;
   const uint32_t* d_order = nullptr;
-  size_t ci = 0, scan_bytes = 0;
-  uint64_t cap = 0;
+  LatticeEmit emit;
+  size_t ci = 0;
   uint32_t rows = 0;
   int argmin = 0;
 
@@ -4546,32 +4578,19 @@ struct BgLatPass {
     HIP_TRY(c->bglat_row_pred.ensure(2 * (size_t)max_gu * P));
     HIP_TRY(c->bgfb_order.upload(steps.order.data(), steps.order.size()));
     d_order = c->bgfb_order.p;
-    HIP_TRY(c->lat_cnt.ensure(max_gf));
-    HIP_TRY(c->lat_scan.ensure(max_gf));
-    HIP_TRY(c->lat_base.ensure(1));
-    HIP_TRY(c->lat_frame_arc.ensure(c->n_frames + 1));
     HIP_TRY(c->out_cost.ensure(U));
-    scan_bytes = lattice_scan_temp_bytes(max_gf);
-    HIP_TRY(c->fb_scan_temp.ensure(scan_bytes));
-    HIP_TRY(hipMemset(c->lat_base.p, 0, sizeof(uint64_t)));
+    if (int rc = emit.setup(c, max_gf, arc_cap, &a, a.arc_am)) return rc;
     if (U) HIP_TRY(hipMemset(c->out_cost.p, 0, sizeof(double) * U));  // T_u = 0: the empty path ends at the start's word end
     HIP_TRY(hipDeviceSynchronize());
-    a.n_words = W; a.silence = b->net.silence; a.n_positions = (uint32_t)P; a.Kp = Kp;
-    a.slot_off = b->slot_off.p; a.pos_info = b->pos_info.p; a.pos_slot = b->pos_slot.p; a.lmT = b->lmT.p;
-    memcpy(a.tdp, b->net.tdp, sizeof(a.tdp));
-    a.ld = m->ld; a.frame_off = c->d_frame_off.p; a.beam = beam;
+    bg_net_args(m, c, b, &a);
+    a.beam = beam;
     a.fwd = c->bglat_fwd.p; a.bwd = c->bglat_bwd.p; a.first = c->bglat_first.p; a.pred = c->bglat_pred.p;
     a.vec = c->bgfb_vec.p; a.prod = c->bgfb_prod.p; a.wend = c->bgfb_wend.p; a.arg = c->bglat_arg.p;
     a.row = c->bgfb_xb.p; a.row_first = c->bglat_row_first.p; a.row_pred = c->bglat_row_pred.p;
     a.out_best = c->out_cost.p;
-    cap = arc_cap;
-    if (cap) {
-      HIP_TRY(c->lat_arc_word.ensure(cap)); HIP_TRY(c->bglat_arc_hist.ensure(cap)); HIP_TRY(c->bglat_arc_pred.ensure(cap));
-      HIP_TRY(c->lat_arc_first.ensure(cap)); HIP_TRY(c->lat_arc_last.ensure(cap));
-      HIP_TRY(c->lat_arc_fwd.ensure(cap)); HIP_TRY(c->lat_arc_bwd.ensure(cap)); HIP_TRY(c->lat_arc_cost.ensure(cap));
-      a.arc_word = c->lat_arc_word.p; a.arc_hist = c->bglat_arc_hist.p; a.arc_pred = c->bglat_arc_pred.p;
-      a.arc_first = c->lat_arc_first.p; a.arc_last = c->lat_arc_last.p;
-      a.arc_fwd = c->lat_arc_fwd.p; a.arc_bwd = c->lat_arc_bwd.p; a.arc_am = c->lat_arc_cost.p;
+    if (arc_cap) {
+      HIP_TRY(c->bglat_arc_hist.ensure(arc_cap)); HIP_TRY(c->bglat_arc_pred.ensure(arc_cap));
+      a.arc_hist = c->bglat_arc_hist.p; a.arc_pred = c->bglat_arc_pred.p;
     }
     // per frame: the rows of both walks (cost, first, pred in and out forward: 28, e + beta in and out backward: 16 per position) and
     // the word-end tables (22 per slot out, fwd and bwd in again for the count, all of it for the write: 60 per slot, 2 W slots)
@@ -4595,8 +4614,7 @@ struct BgLatPass {
         HIP_TRY(launch_bglat_backward(a, s));
         if (t) HIP_TRY(launch_bglat_entry(tab_bwd, a.vec, a.prod, nullptr, a.n_words, a.Kp, a.n_alive, argmin, s));
       }
-      const uint64_t n = c->frame_off[g.u1] - c->frame_off[g.u0];
-      HIP_TRY(launch_bglat_emit(a, n, c->fb_scan_temp.p, scan_bytes, c->lat_cnt.p, c->lat_scan.p, c->lat_base.p, c->lat_frame_arc.p, cap, s));
+      HIP_TRY(emit.launch(launch_bglat_emit, a, c, g, s));
     }
     ci++;
     return SR_OK;
@@ -4616,33 +4634,14 @@ int sr_bigram_word_lattice_corpus(sr_model* m, sr_corpus* c, sr_bigram* b, int g
   if (fill && (!out_word || !out_hist || !out_pred || !out_first || !out_last || !out_fwd || !out_bwd || !out_am))
     return fail(SR_EINVAL, "null output (pass all eight arc arrays, or none)");
   if (b->lm_min == -std::numeric_limits<float>::infinity()) return fail(SR_EINVAL, "the language model has a score of -inf");
-  const uint32_t U = c->n_utts;
-  const uint64_t F = c->n_frames, S = 2ull * b->net.n_words;
-  const std::vector<uint64_t> cost = bglat_cost(c, b);
-  for (uint32_t u = 0; u < U; u++) {
-    const uint64_t T = c->frame_off[u + 1] - c->frame_off[u];
-    if (T > 65535) return fail(SR_ELIMIT, "utterance %u: %llu frames exceed the lattice's 65535", u, (unsigned long long)T);
-    if ((rc = check_fits(m, u, cost[u + 1] - cost[u], true))) return rc;
-  }
-  std::vector<Chunk> chunks;
-  if ((rc = prepare_chunks(m, c, &chunks))) return rc;
   BgLatPass lp;
-  const uint64_t dev_cap = fill ? std::min<uint64_t>(cap, F * S) : 0;  // (no lattice has more than F * 2W arcs)
-  if ((rc = lp.setup(m, c, b, lattice_beam, dev_cap, chunks))) return rc;
-  rc = run_chunks(m, chunks, [&](const Chunk& ch, double* table) { return score_chunk(m, c, ch.f0, ch.f1, gmm_kernel, table); },
-                  [&](const Chunk& ch, const double* table, hipStream_t s) -> int { return lp.run(c, ch, table, s); });
-  if (rc) return rc;
-  if (m->profiling) m->prof.frames += F;
   uint64_t n = 0;
-  if ((rc = lattice_offsets(c, cap, fill, out_arc_off, out_best, &n))) return rc;
-  HIP_TRY(copy_arcs(out_word, c->lat_arc_word, n));
+  rc = lattice_corpus(m, c, gmm_kernel, bglat_cost(c, b), 2ull * b->net.n_words, cap, fill, lp,
+                      [&](uint64_t dev_cap, const std::vector<Chunk>& chunks) { return lp.setup(m, c, b, lattice_beam, dev_cap, chunks); },
+                      LatticeOut{out_arc_off, out_best, out_word, out_first, out_last, out_fwd, out_bwd, out_am}, &n);
+  if (rc) return rc;
   HIP_TRY(copy_arcs(out_hist, c->bglat_arc_hist, n));
   HIP_TRY(copy_arcs(out_pred, c->bglat_arc_pred, n));
-  HIP_TRY(copy_arcs(out_first, c->lat_arc_first, n));
-  HIP_TRY(copy_arcs(out_last, c->lat_arc_last, n));
-  HIP_TRY(copy_arcs(out_fwd, c->lat_arc_fwd, n));
-  HIP_TRY(copy_arcs(out_bwd, c->lat_arc_bwd, n));
-  HIP_TRY(copy_arcs(out_am, c->lat_arc_cost, n));
   return SR_OK;
   });
 }

@@ -31,6 +31,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bigram_device.h"
 #include "kernels.h"
 #include "netfb_device.h"
 
@@ -59,13 +60,6 @@ hipError_t launch_bgfb_table(const float* lmT, uint32_t W, uint32_t Kp, uint32_t
   return hipGetLastError();
 }
 
-struct BgCosts { double t[2][4]; };
-__device__ inline BgCosts bg_costs(const BgFbArgs& a) {
-  BgCosts c;
-  for (int s = 0; s < 2; s++)
-    for (int j = 0; j < 4; j++) c.t[s][j] = a.scale * (double)a.tdp[s][j];
-  return c;
-}
 // the block-wide sum of every thread's Lse (netfb_device.h's butterfly), the minimum kept beside the cost
 __device__ inline Lse block_lse(Lse v, double* red) {
   block_lse_store(v, red);
@@ -74,8 +68,6 @@ __device__ inline Lse block_lse(Lse v, double* red) {
   for (int w = 0; w < kNetFbWaves; w++) r.merge(red[2 * w], red[2 * w + 1]);
   return r;
 }
-// cost of a linear-domain sum x relative to the offset m
-__device__ inline double bg_unscale(double m, double x) { return (m < kInf && x > 0.0) ? m - log(x) : kInf; }
 
 // workgroup b: frame a.t of utterance a.order[b]
 __global__ __launch_bounds__(kNetFbThreads) void bgfb_forward_kernel(BgFbArgs a) {
@@ -90,7 +82,7 @@ __global__ __launch_bounds__(kNetFbThreads) void bgfb_forward_kernel(BgFbArgs a)
   const double* X = a.prod + (size_t)j * a.Kp;
   double* vec = a.vec + (size_t)j * a.Kp;
   double* wend = a.wend + (size_t)j * a.Kp;
-  const BgCosts c = bg_costs(a);
+  const BgCosts c = bg_costs(a.tdp, a.scale);
   const double m_in = t ? a.m[j] : 0.0;
 
   for (uint32_t p = tid; p < P; p += kNetFbThreads) {
@@ -149,7 +141,7 @@ __global__ __launch_bounds__(kNetFbThreads) void bgfb_backward_kernel(BgFbArgs a
   const double* Y = a.prod + (size_t)j * a.Kp;
   double* vec = a.vec + (size_t)j * a.Kp;
   double* wend = a.wend + (size_t)j * a.Kp;
-  const BgCosts c = bg_costs(a);
+  const BgCosts c = bg_costs(a.tdp, a.scale);
   const double F = a.out_cost[u];
   const bool dead = !(F < kInf), final = t + 1 == T;
   const double m_in = final ? kInf : a.m[j];

@@ -19,34 +19,25 @@
 //   bglat_backward_kernel  the mirror image on rolling rows of e_t + beta_t; bwd [frame][2W] = the cheapest continuation from a
 //                          word end of the slot after frame t (0 at the last frame) leaves
 //   bglat_count_kernel /   per frame the arcs (slot x, fwd finite) with fwd + bwd <= best + beam, an exclusive scan over the
-//   bglat_write_kernel     group's frames (hipcub) and the arcs compacted in (frame, slot) order behind those of the groups before
+//   bglat_write_kernel     group's frames (hipcub) and the arcs compacted in (frame, slot) order behind those of the groups before:
+//                          lattice_emit.h's stage, shared with viterbi_lattice.hip; here its policy, BgLatEmit
 //
 // The utterances of a group are ordered longest first, so the ones alive at frame t are a prefix of that order; no kernel waits on
 // another workgroup.  min and + only, no atomics: two identical calls return identical bits; +inf stays +inf.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
+#include "bigram_device.h"
+#include "dpp_util.h"
 #include "kernels.h"
+#include "lattice_emit.h"
 
 namespace srgpu {
 
-static constexpr double kInf = __builtin_huge_val();
 static constexpr int kBgLatThreads = 512;
 static constexpr int kBgLatWaves = kBgLatThreads / 64;
 
 __device__ inline double bglat_min(double a, double b) { return b < a ? b : a; }
-__device__ inline double bglat_shfl_xor(double v, int k) {
-  return __hiloint2double(__shfl_xor(__double2hiint(v), k), __shfl_xor(__double2loint(v), k));
-}
-
-struct BgLatCosts { double t[2][4]; };
-__device__ inline BgLatCosts bglat_costs(const BgLatArgs& a) {
-  BgLatCosts c;
-  for (int s = 0; s < 2; s++)
-    for (int j = 0; j < 4; j++) c.t[s][j] = (double)a.tdp[s][j];
-  return c;
-}
 
 // out[h * W + w] = in[w * W + h]
 __global__ __launch_bounds__(256) void bglat_transpose_kernel(const float* in, uint32_t W, float* out) {
@@ -191,7 +182,7 @@ __global__ __launch_bounds__(kBgLatThreads) void bglat_forward_kernel(BgLatArgs 
   const double* X = a.prod + (size_t)j * a.Kp;
   const uint32_t* XA = a.arg + (size_t)j * a.Kp;
   const double* wprev = a.fwd + (t ? g - 1 : g) * S;  // the word ends of the frame before (read only for t > 0)
-  const BgLatCosts c = bglat_costs(a);
+  const BgCosts c = bg_costs(a.tdp);
 
   for (uint32_t p = tid; p < P; p += kBgLatThreads) {
     const uint32_t info = a.pos_info[p], fl = info >> 16, x = a.pos_slot[p];
@@ -240,7 +231,7 @@ __global__ __launch_bounds__(kBgLatThreads) void bglat_forward_kernel(BgLatArgs 
   }
   if (t + 1 != T) return;
 #pragma unroll
-  for (int k = 1; k < 64; k <<= 1) mine = bglat_min(mine, bglat_shfl_xor(mine, k));
+  for (int k = 1; k < 64; k <<= 1) mine = bglat_min(mine, shfl_xor_f64(mine, k));
   if ((tid & 63) == 0) red[tid >> 6] = mine;
   __syncthreads();
   if (tid == 0) {
@@ -264,7 +255,7 @@ __global__ __launch_bounds__(kBgLatThreads) void bglat_backward_kernel(BgLatArgs
   double* vec = a.vec + (size_t)j * a.Kp;
   double* wend = a.wend + (size_t)j * a.Kp;
   double* bw = a.bwd + g * S;
-  const BgLatCosts c = bglat_costs(a);
+  const BgCosts c = bg_costs(a.tdp);
   const bool final = t + 1 == T;
 
   for (uint32_t p = tid; p < P; p += kBgLatThreads) {
@@ -319,102 +310,56 @@ hipError_t launch_bglat_backward(const BgLatArgs& a, hipStream_t stream) {
   return hipGetLastError();
 }
 
-// ---- the arcs -------------------------------------------------------------------------------------------------------------------
-// is (slot x, frame g of the group) an arc inside the beam?  limit = best + beam of the frame's utterance
-__device__ inline bool bglat_keep(const BgLatArgs& a, uint64_t g, uint32_t x, double limit) {
-  const size_t i = g * 2 * a.n_words + x;
-  const double f = a.fwd[i];
-  const double tot = f + a.bwd[i];
-  return f < kInf && tot < kInf && tot <= limit;
-}
-// the utterance of the group that owns corpus frame gf: the last u with frame_off[u] <= gf
-__device__ inline uint32_t bglat_utt_of(const BgLatArgs& a, uint64_t gf) {
-  uint32_t lo = a.utt_first, hi = a.utt_first + a.n_group;  // frame_off[lo] <= gf < frame_off[hi]
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (a.frame_off[mid] <= gf) lo = mid; else hi = mid;
+// ---- the arcs (lattice_emit.h) ----------------------------------------------------------------------------------------------------
+struct BgLatEmit {
+  const BgLatArgs& a;
+  __device__ uint32_t n_utts() const { return a.n_group; }
+  __device__ uint32_t slots() const { return 2 * a.n_words; }
+  __device__ bool keep(uint64_t g, uint32_t x, double limit) const {
+    const size_t i = g * 2 * a.n_words + x;
+    const double f = a.fwd[i];
+    const double tot = f + a.bwd[i];
+    return f < kInf && tot < kInf && tot <= limit;
   }
-  return lo;
-}
+  __device__ int frame(uint64_t) const { return 0; }  // (bwd depends on the slot: nothing to hold)
+  __device__ void write(uint64_t i, uint64_t g, uint32_t x, uint64_t uf, int) const {
+    const uint32_t W = a.n_words, S = 2 * W, sil = a.silence;
+    const double f = a.fwd[g * S + x];
+    const uint32_t b = a.first[g * S + x], pr = a.pred[g * S + x];
+    const bool word = x < W && x != sil;
+    double c_in = 0.0;  // the cost the entry started from (the start: 0)
+    if (b) {
+      const double* we = a.fwd + (uf + b - 1) * S;
+      if (!word) c_in = we[x < W ? sil : x - W];
+      else c_in = pr == sil ? we[sil] : bglat_min(we[pr], we[pr + W]);
+    }
+    const double lmc = word ? (double)a.lmT[(size_t)pr * W + x] : 0.0;
+    a.arc_word[i] = x < W ? x : sil;
+    a.arc_hist[i] = x < W ? x : x - W;
+    a.arc_pred[i] = pr;
+    a.arc_first[i] = b;
+    a.arc_last[i] = (uint32_t)(g - uf);
+    a.arc_fwd[i] = f;
+    a.arc_bwd[i] = a.bwd[g * S + x];
+    a.arc_am[i] = (f - c_in) - lmc;
+  }
+};
 
-// one wave per frame of the group: cnt[g] = its arcs inside the beam
 __global__ __launch_bounds__(256) void bglat_count_kernel(BgLatArgs a, uint64_t n_frames, uint64_t* cnt) {
-  const uint64_t g = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (g >= n_frames) return;
-  const uint32_t lane = threadIdx.x & 63, S = 2 * a.n_words;
-  const uint32_t u = bglat_utt_of(a, a.group_f0 + g);
-  const double limit = a.out_best[u] + a.beam;
-  uint32_t n = 0;
-  for (uint32_t x0 = 0; x0 < S; x0 += 64) {
-    const uint32_t x = x0 + lane;
-    const bool keep = x < S && bglat_keep(a, g, x, limit);
-    n += (uint32_t)__popcll(__ballot(keep));
-  }
-  if (lane == 0) cnt[g] = n;
+  emit_count(BgLatEmit{a}, n_frames, cnt);
 }
-
-// one wave per frame of the group: the frame's arcs at arc_base[0] + scan[g] ..., in slot order; frame_arc[corpus frame] = that
-// position.  Nothing is written at or beyond cap.
 __global__ __launch_bounds__(256) void bglat_write_kernel(BgLatArgs a, uint64_t n_frames, const uint64_t* scan, const uint64_t* arc_base,
                                                           uint64_t* frame_arc, uint64_t cap) {
-  const uint64_t g = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (g >= n_frames) return;
-  const uint32_t lane = threadIdx.x & 63, W = a.n_words, S = 2 * W, sil = a.silence;
-  const uint64_t gf = a.group_f0 + g;
-  const uint32_t u = bglat_utt_of(a, gf);
-  const uint64_t uf = a.frame_off[u] - a.group_f0;  // the utterance's first frame within the group
-  const double limit = a.out_best[u] + a.beam;
-  uint64_t pos = arc_base[0] + scan[g];
-  if (lane == 0) frame_arc[gf] = pos;
-  if (!a.arc_word) return;  // the sizing call
-  for (uint32_t x0 = 0; x0 < S; x0 += 64) {
-    const uint32_t x = x0 + lane;
-    const bool keep = x < S && bglat_keep(a, g, x, limit);
-    const uint64_t mask = __ballot(keep);
-    if (keep) {
-      const uint64_t i = pos + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
-      if (i < cap) {
-        const double f = a.fwd[g * S + x];
-        const uint32_t b = a.first[g * S + x], pr = a.pred[g * S + x];
-        const bool word = x < W && x != sil;
-        double c_in = 0.0;  // the cost the entry started from (the start: 0)
-        if (b) {
-          const double* we = a.fwd + (uf + b - 1) * S;
-          if (!word) c_in = we[x < W ? sil : x - W];
-          else c_in = pr == sil ? we[sil] : bglat_min(we[pr], we[pr + W]);
-        }
-        const double lmc = word ? (double)a.lmT[(size_t)pr * W + x] : 0.0;
-        a.arc_word[i] = x < W ? x : sil;
-        a.arc_hist[i] = x < W ? x : x - W;
-        a.arc_pred[i] = pr;
-        a.arc_first[i] = b;
-        a.arc_last[i] = (uint32_t)(g - uf);
-        a.arc_fwd[i] = f;
-        a.arc_bwd[i] = a.bwd[g * S + x];
-        a.arc_am[i] = (f - c_in) - lmc;
-      }
-    }
-    pos += (uint64_t)__popcll(mask);
-  }
+  emit_write(BgLatEmit{a}, n_frames, scan, arc_base, frame_arc, cap);
 }
-
-// arc_base[0] += the group's arcs
 __global__ void bglat_advance_kernel(const uint64_t* cnt, const uint64_t* scan, uint64_t n_frames, uint64_t* arc_base) {
-  arc_base[0] += scan[n_frames - 1] + cnt[n_frames - 1];
+  emit_advance(cnt, scan, n_frames, arc_base);
 }
 
 hipError_t launch_bglat_emit(const BgLatArgs& a, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes, uint64_t* cnt, uint64_t* scan,
                              uint64_t* arc_base, uint64_t* frame_arc, uint64_t cap, hipStream_t stream) {
-  if (a.n_group == 0 || n_frames == 0) return hipSuccess;
-  const dim3 grid((unsigned)((n_frames + 3) / 4));
-  hipLaunchKernelGGL(bglat_count_kernel, grid, dim3(256), 0, stream, a, n_frames, cnt);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  e = hipcub::DeviceScan::ExclusiveSum(scan_temp, scan_temp_bytes, cnt, scan, (int)n_frames, stream);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(bglat_write_kernel, grid, dim3(256), 0, stream, a, n_frames, scan, arc_base, frame_arc, cap);
-  hipLaunchKernelGGL(bglat_advance_kernel, dim3(1), dim3(1), 0, stream, cnt, scan, n_frames, arc_base);
-  return hipGetLastError();
+  return launch_emit(bglat_count_kernel, bglat_write_kernel, bglat_advance_kernel, a, a.n_group, n_frames, scan_temp, scan_temp_bytes,
+                     cnt, scan, arc_base, frame_arc, cap, stream);
 }
 
 }  // namespace srgpu

@@ -23,21 +23,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bigram_device.h"
 #include "kernels.h"
 #include "netfb_device.h"
 
 namespace srgpu {
 
 static constexpr uint32_t kNoLink = 0xFFFFu;
-
-struct BgcCosts { double t[2][4]; };
-__device__ inline BgcCosts bgc_costs(const BgChainArgs& a) {
-  BgcCosts c;
-  for (int s = 0; s < 2; s++)
-    for (int j = 0; j < 4; j++) c.t[s][j] = a.scale * (double)a.tdp[s][j];
-  return c;
-}
-__device__ inline int bgc_sil(uint32_t info) { return (info >> 16) & 8u ? 1 : 0; }
 
 // LDS: alpha[2][N] f64
 __global__ __launch_bounds__(kNetFbThreads) void bgchain_forward_kernel(BgChainArgs a) {
@@ -56,7 +48,7 @@ __global__ __launch_bounds__(kNetFbThreads) void bgchain_forward_kernel(BgChainA
   const uint32_t* info = a.info + a.chain_off[u];
   const uint32_t* src = a.src + a.chain_off[u];
   const double* lmc = a.lmc + a.chain_off[u];
-  const BgcCosts c = bgc_costs(a);
+  const BgCosts c = bg_costs(a.tdp, a.scale);
   const uint32_t end_S = a.sil_len - 1;
   for (int t = 0; t < T; t++) {
     const double* prev = al + (size_t)((t + 1) & 1) * N;  // (read only for t > 0)
@@ -107,7 +99,7 @@ __global__ __launch_bounds__(kNetFbThreads) void bgchain_backward_kernel(BgChain
   const uint32_t* info = a.info + a.chain_off[u];
   const uint32_t* dst = a.dst + a.chain_off[u];
   const double* lmc = a.lmc + a.chain_off[u];
-  const BgcCosts c = bgc_costs(a);
+  const BgCosts c = bg_costs(a.tdp, a.scale);
   const double F = a.out_cost[u];
   const bool dead = !(F < kInf);  // no complete path: every occupancy is 0
   for (int t = T - 1; t >= 0; t--) {

@@ -26,27 +26,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bigram_device.h"
 #include "kernels.h"
 #include "netfb_device.h"
 #include "smbr_device.h"
 
 namespace srgpu {
-
-// the penalties times kappa; s and j select by comparison, so the table stays in scalar registers
-struct BgsCosts { double t[2][4]; };
-__device__ inline BgsCosts bgs_costs(const BgFbArgs& a) {
-  BgsCosts c;
-#pragma unroll
-  for (int s = 0; s < 2; s++)
-#pragma unroll
-    for (int j = 0; j < 4; j++) c.t[s][j] = a.scale * (double)a.tdp[s][j];
-  return c;
-}
-template <int J>
-__device__ inline double bgs_pen(const BgsCosts& c, bool sil) { return sil ? c.t[1][J] : c.t[0][J]; }
-// cost of a linear-domain sum x relative to the offset m (viterbi_bigram_fb.hip's bg_unscale)
-__device__ inline double bgs_unscale(double m, double x) { return (m < kInf && x > 0.0) ? m - log(x) : kInf; }
-__device__ inline double bgs_hit(uint32_t info, uint32_t ref) { return (info & 0xFFFFu) == ref ? 1.0 : 0.0; }
 
 // workgroup b: frame a.t of utterance a.order[b]
 __global__ __launch_bounds__(kNetFbThreads) void bgsmbr_forward_kernel(BgSmbrArgs sa) {
@@ -67,7 +52,7 @@ __global__ __launch_bounds__(kNetFbThreads) void bgsmbr_forward_kernel(BgSmbrArg
   double* veca = vec + a.Kp;
   double* wend = a.wend + (size_t)2 * j * a.Kp;
   double* wenda = wend + a.Kp;
-  const BgsCosts c = bgs_costs(a);
+  const BgCosts c = bg_costs(a.tdp, a.scale);
   const double m_in = t ? a.m[j] : 0.0;
   const uint32_t rf = sa.ref[f0 + t];
 
@@ -81,7 +66,7 @@ __global__ __launch_bounds__(kNetFbThreads) void bgsmbr_forward_kernel(BgSmbrArg
         else if (x < W) { const double l = (double)a.lmT[(size_t)sil * W + x]; if (l < kInf) ent.x = a.scale * l; }
       } else if (x < W && x != sil) {
         const double y = X[x];
-        ent.x = bgs_unscale(m_in, y);
+        ent.x = bg_unscale(m_in, y);
         if (ent.x < kInf) ent.a = Xa[x] / y;
       } else if (x == sil) ent = La{wend[sil], wenda[sil]};
       else if (x - W != sil) ent = La{wend[x - W], wenda[x - W]};
@@ -97,7 +82,7 @@ __global__ __launch_bounds__(kNetFbThreads) void bgsmbr_forward_kernel(BgSmbrArg
     }
     const bool ok = v.x < kInf;
     cur[p] = ok ? v.x + a.scale * row[info & 0xFFFFu] : kInf;
-    cura[p] = ok ? v.a + bgs_hit(info, rf) : 0.0;
+    cura[p] = ok ? v.a + hit(info, rf) : 0.0;
   }
   __syncthreads();  // the row is read back below at the slots' last positions
   LseA ends;
@@ -163,7 +148,7 @@ __global__ __launch_bounds__(kNetFbThreads) void bgsmbr_backward_kernel(BgSmbrAr
   double* veca = vec + a.Kp;
   double* wend = a.wend + (size_t)2 * j * a.Kp;
   double* wenda = wend + a.Kp;
-  const BgsCosts c = bgs_costs(a);
+  const BgCosts c = bg_costs(a.tdp, a.scale);
   const double F = a.out_cost[u], A = sa.out_acc[u];  // kappa F_u, Abar_u
   const bool dead = !(F < kInf), final = t + 1 == T;
   const double m_in = final ? kInf : a.m[j];
@@ -185,7 +170,7 @@ __global__ __launch_bounds__(kNetFbThreads) void bgsmbr_backward_kernel(BgSmbrAr
       if (fl & 4u) {  // a word end: into every word through the LM, and into the own copy (the silence word: into itself)
         const uint32_t h = x < W ? x : x - W;
         const double y = Y[h];
-        La r{bgs_unscale(m_in, y), 0.0};
+        La r{bg_unscale(m_in, y), 0.0};
         if (r.x < kInf) r.a = Ya[h] / y;
         if (x < W) r = la_add(r, La{wend[x], wenda[x]});
         b = la_add(b, La{bgs_pen<3>(c, s) + r.x, r.a});
@@ -200,7 +185,7 @@ __global__ __launch_bounds__(kNetFbThreads) void bgsmbr_backward_kernel(BgSmbrAr
     }
     tr[p] = g;
     xcur[p] = ok ? a.scale * row[info & 0xFFFFu] + b.x : kInf;
-    xcura[p] = ok ? bgs_hit(info, rf) + b.a : 0.0;
+    xcura[p] = ok ? hit(info, rf) + b.a : 0.0;
   }
   if (t == 0) return;
   __syncthreads();

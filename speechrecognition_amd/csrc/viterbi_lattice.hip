@@ -14,7 +14,8 @@
 //                            additions in the order ((wp + tdp) + e) + B and (tdp + e) + B; Bend_{T-1} = 0.
 //   lattice_count_kernel /   per frame the arcs (word w ending at t, fwd finite) with fwd + bwd <= E_{T-1} + beam, an exclusive scan
 //   lattice_write_kernel     over the launch's frames (hipcub), and the arcs compacted in (frame, word) order behind those of the
-//                            launches before: word, first, last, fwd, bwd = Bend_t, cost = fwd - E_{first-1} (E_{-1} = 0).
+//                            launches before: word, first, last, fwd, bwd = Bend_t, cost = fwd - E_{first-1} (E_{-1} = 0).  The
+//                            stage is lattice_emit.h's, shared with viterbi_bigram_lattice.hip; here its policy, LatEmit.
 //
 // One workgroup per utterance, slots strided over the threads, FP64.  The forward's two cost rows and two 16-bit start rows live in
 // LDS (20 B per slot), the backward's two rows likewise (16 B per slot).  The min over the word ends is one block-wide reduction per
@@ -22,10 +23,11 @@
 // bits.  No atomics.  min and + only: +inf stays +inf and never turns into NaN (costs are never subtracted, except fwd - E of a
 // reachable arc, both finite).
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
+#include "dpp_util.h"
 #include "kernels.h"
+#include "lattice_emit.h"
 
 namespace srgpu {
 
@@ -49,10 +51,6 @@ __device__ inline double lat_wp(uint32_t f, const LatCosts& c) { return (f & kSl
 // tdp(first state, init + 1) of an entry into the slot (position 0 or 1 of its word)
 __device__ inline double lat_tinit(uint32_t f, const LatCosts& c) {
   return (f & kSlotPos0) ? c.tf : ((f & kSlotFirstSil) ? c.tf : c.ts);
-}
-
-__device__ inline double shfl_xor_f64(double v, int k) {
-  return __hiloint2double(__shfl_xor(__double2hiint(v), k), __shfl_xor(__double2loint(v), k));
 }
 
 // LDS: cost[2][P] f64, red cost[2][kLatWaves] f64, red slot[2][kLatWaves] u32, start[2][P] u16
@@ -257,77 +255,39 @@ hipError_t launch_lattice_backward(const LatticeArgs& a, hipStream_t stream) {
   return hipGetLastError();
 }
 
-// is (word w, frame g of the launch) an arc inside the beam?  limit = E_{T-1} + beam of the frame's utterance
-__device__ inline bool lat_keep(const LatticeArgs& a, uint64_t g, uint32_t w, double limit) {
-  const double f = a.fwd[g * a.net.n_words + w];
-  const double tot = f + a.bend[g];
-  return f < kInf && tot < kInf && tot <= limit;
-}
-// the utterance of the launch that owns corpus frame gf: the last u with frame_off[u] <= gf
-__device__ inline uint32_t lat_utt_of(const LatticeArgs& a, uint64_t gf) {
-  uint32_t lo = a.utt_first, hi = a.utt_first + a.n_utts;  // frame_off[lo] <= gf < frame_off[hi]
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (a.frame_off[mid] <= gf) lo = mid; else hi = mid;
+// ---- the arcs (lattice_emit.h) ----------------------------------------------------------------------------------------------
+struct LatEmit {
+  const LatticeArgs& a;
+  __device__ uint32_t n_utts() const { return a.n_utts; }
+  __device__ uint32_t slots() const { return a.net.n_words; }
+  __device__ bool keep(uint64_t g, uint32_t w, double limit) const {
+    const double f = a.fwd[g * a.net.n_words + w];
+    const double tot = f + a.bend[g];
+    return f < kInf && tot < kInf && tot <= limit;
   }
-  return lo;
-}
+  __device__ double frame(uint64_t g) const { return a.bend[g]; }
+  __device__ void write(uint64_t i, uint64_t g, uint32_t w, uint64_t uf, double bwd) const {
+    const uint32_t W = a.net.n_words;
+    const double f = a.fwd[g * W + w];
+    const uint32_t b = a.first[g * W + w];
+    a.arc_word[i] = w;
+    a.arc_first[i] = b;
+    a.arc_last[i] = (uint32_t)(g - uf);
+    a.arc_fwd[i] = f;
+    a.arc_bwd[i] = bwd;
+    a.arc_cost[i] = f - (b ? a.ends[uf + b - 1] : 0.0);
+  }
+};
 
-// one wave per frame of the launch: cnt[g] = its arcs inside the beam
 __global__ __launch_bounds__(256) void lattice_count_kernel(LatticeArgs a, uint64_t n_frames, uint64_t* cnt) {
-  const uint64_t g = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (g >= n_frames) return;
-  const uint32_t lane = threadIdx.x & 63, W = a.net.n_words;
-  const uint32_t u = lat_utt_of(a, a.group_f0 + g);
-  const double limit = a.out_best[u] + a.beam;
-  uint32_t n = 0;
-  for (uint32_t w0 = 0; w0 < W; w0 += 64) {
-    const uint32_t w = w0 + lane;
-    const bool keep = w < W && lat_keep(a, g, w, limit);
-    n += (uint32_t)__popcll(__ballot(keep));
-  }
-  if (lane == 0) cnt[g] = n;
+  emit_count(LatEmit{a}, n_frames, cnt);
 }
-
-// one wave per frame of the launch: the frame's arcs at arc_base[0] + scan[g] ..., in word order; frame_arc[corpus frame] = that
-// position (the per-utterance offsets are read from it).  Nothing is written at or beyond cap.
 __global__ __launch_bounds__(256) void lattice_write_kernel(LatticeArgs a, uint64_t n_frames, const uint64_t* scan,
                                                             const uint64_t* arc_base, uint64_t* frame_arc, uint64_t cap) {
-  const uint64_t g = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (g >= n_frames) return;
-  const uint32_t lane = threadIdx.x & 63, W = a.net.n_words;
-  const uint64_t gf = a.group_f0 + g;
-  const uint32_t u = lat_utt_of(a, gf);
-  const uint64_t uf = a.frame_off[u] - a.group_f0;  // the utterance's first frame within the launch
-  const double limit = a.out_best[u] + a.beam;
-  uint64_t pos = arc_base[0] + scan[g];
-  if (lane == 0) frame_arc[gf] = pos;
-  if (!a.arc_word) return;  // the sizing call
-  const double bwd = a.bend[g];
-  for (uint32_t w0 = 0; w0 < W; w0 += 64) {
-    const uint32_t w = w0 + lane;
-    const bool keep = w < W && lat_keep(a, g, w, limit);
-    const uint64_t mask = __ballot(keep);
-    if (keep) {
-      const uint64_t i = pos + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
-      if (i < cap) {
-        const double f = a.fwd[g * W + w];
-        const uint32_t b = a.first[g * W + w];
-        a.arc_word[i] = w;
-        a.arc_first[i] = b;
-        a.arc_last[i] = (uint32_t)(g - uf);
-        a.arc_fwd[i] = f;
-        a.arc_bwd[i] = bwd;
-        a.arc_cost[i] = f - (b ? a.ends[uf + b - 1] : 0.0);
-      }
-    }
-    pos += (uint64_t)__popcll(mask);
-  }
+  emit_write(LatEmit{a}, n_frames, scan, arc_base, frame_arc, cap);
 }
-
-// arc_base[0] += the launch's arcs
 __global__ void lattice_advance_kernel(const uint64_t* cnt, const uint64_t* scan, uint64_t n_frames, uint64_t* arc_base) {
-  arc_base[0] += scan[n_frames - 1] + cnt[n_frames - 1];
+  emit_advance(cnt, scan, n_frames, arc_base);
 }
 
 size_t lattice_scan_temp_bytes(uint64_t n_frames) {
@@ -338,16 +298,8 @@ size_t lattice_scan_temp_bytes(uint64_t n_frames) {
 
 hipError_t launch_lattice_emit(const LatticeArgs& a, uint64_t n_frames, void* scan_temp, size_t scan_temp_bytes, uint64_t* cnt,
                                uint64_t* scan, uint64_t* arc_base, uint64_t* frame_arc, uint64_t cap, hipStream_t stream) {
-  if (a.n_utts == 0 || n_frames == 0) return hipSuccess;
-  const dim3 grid((unsigned)((n_frames + 3) / 4));
-  hipLaunchKernelGGL(lattice_count_kernel, grid, dim3(256), 0, stream, a, n_frames, cnt);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  e = hipcub::DeviceScan::ExclusiveSum(scan_temp, scan_temp_bytes, cnt, scan, (int)n_frames, stream);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(lattice_write_kernel, grid, dim3(256), 0, stream, a, n_frames, scan, arc_base, frame_arc, cap);
-  hipLaunchKernelGGL(lattice_advance_kernel, dim3(1), dim3(1), 0, stream, cnt, scan, n_frames, arc_base);
-  return hipGetLastError();
+  return launch_emit(lattice_count_kernel, lattice_write_kernel, lattice_advance_kernel, a, a.n_utts, n_frames, scan_temp,
+                     scan_temp_bytes, cnt, scan, arc_base, frame_arc, cap, stream);
 }
 
 }  // namespace srgpu

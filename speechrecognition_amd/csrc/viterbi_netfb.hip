@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dpp_util.h"
 #include "kernels.h"
 #include "netfb_device.h"
 
@@ -222,7 +223,7 @@ __global__ __launch_bounds__(256) void netfb_top_kernel(NetFbArgs a, uint64_t n_
     }
 #pragma unroll
     for (int k = 1; k < 64; k <<= 1) {
-      const double ow = __hiloint2double(__shfl_xor(__double2hiint(bw), k), __shfl_xor(__double2loint(bw), k));
+      const double ow = shfl_xor_f64(bw, k);
       const uint32_t oid = (uint32_t)__shfl_xor((int)bid, k);
       if (ow > bw || (ow == bw && oid < bid)) { bw = ow; bid = oid; }
     }

@@ -42,7 +42,6 @@ __device__ inline NfCosts smbr_costs(const SmbrArgs& a) {
   const double k = a.scale;
   return NfCosts{k * a.net.tdp_loop, k * a.net.tdp_forward, k * a.net.tdp_skip, k * a.word_penalty, k};
 }
-__device__ inline double hit(uint32_t f, uint32_t ref) { return (f & 0xFFFFu) == ref ? 1.0 : 0.0; }
 
 // LDS: row[2][2][P] f64 (alpha, abar), red[2][3 * kNetFbWaves] f64
 __global__ __launch_bounds__(kNetFbThreads) void smbr_forward_kernel(SmbrArgs a) {
